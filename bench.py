@@ -3,6 +3,8 @@
 MI355X, at BASELINE.json's shape n=m=200 objects, d=512 (`method='semanticgrav'`).
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+  python bench.py ... --full                          (every leg below; without it: set up, warm up, time K steps, one line)
+  python bench.py ... --dump-outputs DIR              (the last timed step's results as DIR/<name>.npy)
 
 Workloads (`--workload`, default `pairs` at every N, so that the per-N values of a scaling sweep are one workload):
   pairs  BASELINE config 3: a batch of 256 independent synthetic submap pairs per GPU per step (config 2 is the
@@ -12,14 +14,14 @@ Workloads (`--workload`, default `pairs` at every N, so that the per-N values of
          are packed ONCE into one feature pool that every rank holds; the 4096 pairs are dealt round-robin to the
          ranks (512 per rank at N=8) and aligned in calls of at most 512 pairs: strong scaling, a step = the whole
          grid.
-The `pairs` run is followed by a `grid` leg (`--grid-steps`, `--grid-warmup`) whose result is reported in the same
+With --full the `pairs` run is followed by a `grid` leg (`--grid-steps`, `--grid-warmup`) whose result is reported in the same
 line as `grid_config4` — config 4's strong-scaling number next to the weak one, at every N.
 A "step" is one pass of the hot path (score -> solve -> select -> pose; roman_align_batch_dev calls) over the
 workload.  Inputs are resident in HBM before the timed region (`value_incl_h2d` is the same loop with the upload of
 every batch inside it).  There is no data-path collective; one RCCL all_gather of the fixed-size result records
 (inlier sets + poses) per call collects the results on every rank.
 
-The printed JSON line also carries (rank 0, N=1; `--no-extras` leaves the side legs out)
+With --full the printed JSON line also carries (rank 0, N=1; `--no-extras` leaves the side legs out)
   roofline             the dominant kernel (k_solve_up): algorithmic bytes per launch / its hipEvent
                        time against the 8 TB/s HBM3E peak, the counter-based traffic fraction next to it, the other
                        kernels' own bounds (`kernels`) and the whole step against §8(d)'s ideal time (`step`);
@@ -45,6 +47,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 F64_PEAK_TFLOPS = 78.6         # MI355X f64 vector (= matrix) peak, vendor figure quoted in SURVEY.md §8(d)
 F64_MFMA_MEASURED_TFLOPS = 67.0   # v_mfma_f64_16x16x4 issue ceiling measured on this part (tools/ubench/mfma_rate.hip, round 1)
+METRIC = "submap-pair alignments/sec + p50 latency at n=m=200 objects, d=512"
+DTYPE = "f64 (fixed-point SpMV sums)"
 
 
 def parse():
@@ -72,6 +76,13 @@ def parse():
     ap.add_argument("--pipeline", type=int, default=3, choices=[1, 2, 3, 4, 5, 6],
                     help="batches in flight per GPU (roman_ctx_set_pipeline): the straggler tail of one call's solver overlaps the "
                          "next calls' affinity builds; results are complete at the closing device-wide synchronise")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the sustained / grid / h2d legs, single-pair latency, "
+                         "roofline (with the live rocprofv3 PMC passes), CPU oracle baseline and result check, caller and side legs, the full "
+                         "record in bench_extras.json.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's calls: associations, counts, poses, status, statistics) "
+                         "as DIR/<name>.npy in float64")
     return ap.parse_args()
 
 
@@ -112,7 +123,7 @@ def live_traffic(kernel="k_solve_up<8", timeout_s=150):
         try:
             cmd = [exe, "--kernel-trace", "--pmc", ctr, "--output-format", "csv", "-d", td, "-o", "b", "--", sys.executable, os.path.abspath(__file__),
                    "--steps", "3", "--warmup", "2", "--pipeline", "1", "--latency-reps", "-1", "--cpu-sample", "0", "--no-extras", "--no-grid", "--check-pairs", "0",
-                   "--no-live-traffic"]
+                   "--no-live-traffic", "--full"]
             env = dict(os.environ); env["TMPDIR"] = "/tmp"
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=timeout_s)
             files = glob.glob(os.path.join(td, "**", "*counter_collection.csv"), recursive=True)
@@ -139,6 +150,58 @@ def live_traffic(kernel="k_solve_up<8", timeout_s=150):
         finally:
             shutil.rmtree(td, ignore_errors=True)
     return (2.0 * raw["FETCH_SIZE_KB_per_launch"] + raw["WRITE_SIZE_KB_per_launch"]) * 1024.0, raw
+
+
+DUMP_MAX_BYTES = 60_000_000                # under 64 MB with the .npy headers
+
+
+def dump_outputs(path, M):
+    """What the last timed step of measure() `M` computed, as a caller of the timed path receives it: per problem the selected
+    associations (rows past the count are -1), their count, the pose, the status and the solver statistics — this rank's calls of
+    the step, in problem order.  Everything as float64 (the integers are exact).  Above DUMP_MAX_BYTES a fixed, seeded sample of
+    the problems is written; `problem` holds the workload's index of every row."""
+    from roman_amd.runtime import stats_dtype
+    S, calls = M.stream_, M.calls
+    ncall = len(calls)
+    last = S.loop.call_no                                        # calls issued since the reset after the warm-up
+    held = range(max(ncall - S.nset, 0), ncall)                  # a step of more calls than output sets keeps its last nset only
+    parts = {k: [] for k in ("problem", "assoc", "n_assoc", "T", "status")}
+    stats = []
+    for ci in held:
+        O = S.sets[(last - ncall + ci) % S.nset]
+        c = len(calls[ci])
+        a, n, T, st, sv = O.host(c)
+        a = a.astype(np.float64)
+        a[np.arange(a.shape[1])[None, :] >= n[:, None]] = -1.0
+        parts["problem"].append(np.asarray(calls[ci], dtype=np.float64)); parts["assoc"].append(a)
+        parts["n_assoc"].append(n.astype(np.float64)); parts["T"].append(T.astype(np.float64))
+        parts["status"].append(st.astype(np.float64)); stats.append(sv)
+    arrs = {k: np.concatenate(v) for k, v in parts.items()}
+    sv = np.concatenate(stats)
+    for name in stats_dtype().names:
+        arrs["stats_" + name] = sv[name].astype(np.float64)
+    rows = len(arrs["problem"])
+    row_bytes = sum(v[:1].nbytes for v in arrs.values())
+    if rows * row_bytes > DUMP_MAX_BYTES:
+        pick = np.sort(np.random.default_rng(0).choice(rows, size=DUMP_MAX_BYTES // row_bytes, replace=False))
+        arrs = {k: v[pick] for k, v in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(v))
+
+
+def plain_line(args, M, world):
+    """The result line of a run without --full: the headline keys only."""
+    line = {"metric": METRIC, "value": M.total_per_step * M.steps / M.dt, "unit": "alignments/s", "n_gpus": world,
+            "steps": M.steps, "warmup": M.warmup, "ms_per_step": M.dt / M.steps * 1e3, "higher_is_better": True, "scaling": M.scaling,
+            "vs_baseline": None, "dtype": DTYPE, "data": "synthetic", "timed_region_s": M.dt,
+            "config": {"workload": M.wl_text, "alignments_per_step": M.total_per_step, "pairs_per_call": M.CB, "calls_per_step_per_gpu": len(M.calls),
+                       "n": args.n, "m": args.m, "d": args.d, "method": args.method,
+                       "sharding": f"pairs x{world}, all_gather of records" if world > 1 else "single GPU", "batches_in_flight": args.pipeline},
+            "skipped_in_timed_steps": M.skipped}
+    if world > 1:
+        line["ms_per_step_by_rank"] = M.rank_ms
+    return json.dumps(_sig(line), separators=(",", ":"))
 
 
 def cpu_model():
@@ -327,9 +390,18 @@ def main():
             rank_ms = [float(x) for x in tr.cpu().tolist()]
         return types.SimpleNamespace(workload=workload, batch=batch, truth=truth, calls=calls, meta=meta, feats=feats, kmax=kmax, CB=CB, O=O,
                                      total_per_step=total_per_step, scaling=scaling, wl_text=wl_text, dt=dt, prof=prof, steps=steps, warmup=warmup,
-                                     skipped=skipped, rank_ms=rank_ms, gathers=getattr(S, "gathers", 0))
+                                     skipped=skipped, rank_ms=rank_ms, gathers=getattr(S, "gathers", 0), stream_=S)
 
     M = measure(workload, args.steps, args.warmup, not args.no_profile)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, M)
+    if not args.full:
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(plain_line(args, M, world), flush=True)
+        return
     batch, truth, calls, meta, feats, kmax, CB, O = M.batch, M.truth, M.calls, M.meta, M.feats, M.kmax, M.CB, M.O
     total_per_step, scaling, wl_text, dt, prof = M.total_per_step, M.scaling, M.wl_text, M.dt, M.prof
 
@@ -448,10 +520,10 @@ def main():
     value = total_per_step * args.steps / dt
     ms_step = dt / args.steps * 1e3
     out = {
-        "metric": "submap-pair alignments/sec + p50 latency at n=m=200 objects, d=512",
+        "metric": METRIC,
         "value": value, "unit": "alignments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": ms_step, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-        "dtype": "f64 (fixed-point SpMV sums)", "data": "synthetic",
+        "dtype": DTYPE, "data": "synthetic",
         "dtype_note": "every gate and every stored value is IEEE f64; the stream solver's matrix-vector sums are 64-bit FIXED POINT "
                       "(each term rint(v*x*2^s), s = 48 - exponent(max x), added as integers: order-free, absolute error 2^-48 * max x "
                       "per term against 2^-53 relative for a double sum; u agrees with the oracle's double sums to <= 1e-9, selected sets "

@@ -339,11 +339,63 @@ def gen_submap_align():
     print("submap_align_golden.npz written")
 
 
+def gen_shim_trace():
+    """shim_trace_golden.npz — the `clipperpy` calls the reference's unmodified plugin files make (factory, register, get_MCA,
+    mno_clipper) over the register_golden pairs, recorded at the shim's surface (tests/_shim_trace.py) with the C ABI answered by
+    the CPU oracle (tests/_recording_lib.py), so that tests/test_reference_files_on_shim.py can replay them without the reference.
+    Runs in a child process: this one has the oracle-backed `clipperpy` of the other fixtures installed."""
+    import subprocess
+    subprocess.check_call([sys.executable, os.path.abspath(__file__), "_shim_trace_child"])
+
+
+def _shim_trace_child():
+    import roman_amd.clipperpy as shim
+    from roman_amd import _abi, synth
+    from oracle import oracle as orc
+    from _recording_lib import RecordingLib
+    from _shim_trace import Recorder
+    from conftest import golden_register_cases, golden_pair
+    _abi._LIB = RecordingLib(orc)                                  # what load_library() returns: the C ABI, answered by the oracle
+    rec = Recorder(shim)
+    rec.install()
+    from roman.params.submap_align_params import SubmapAlignParams as RefParams
+    from roman.align.object_registration import InsufficientAssociationsException
+    from roman.align.dist_reg_with_pruning import GravityConstraintError
+    for i, case in enumerate(golden_register_cases()):
+        rec.segment(f"case{i}")
+        reg = RefParams(method=case["method"], **case["kw"]).get_object_registration()
+        pr = golden_pair(case)
+        status = "ok"
+        try:
+            assoc = np.asarray(reg.register(pr.map1, pr.map2)).astype(np.int64).reshape(-1, 2)
+            T = reg.T_align(pr.map1, pr.map2, assoc) if len(assoc) >= reg.dim else np.full((reg.dim + 1,) * 2, np.nan)
+        except InsufficientAssociationsException:
+            assoc = np.zeros((0, 2), np.int64); T = np.full((reg.dim + 1,) * 2, np.nan); status = "insufficient"
+        except GravityConstraintError:
+            assoc = np.zeros((0, 2), np.int64); T = np.full((reg.dim + 1,) * 2, np.nan); status = "gravity"
+        # the recorded run is the golden one: the shim under the reference's files lost nothing
+        assert status == case["status"] and np.array_equal(assoc, case["assoc"]), (i, case["method"], status)
+        assert np.allclose(np.nan_to_num(T, nan=-7.0), np.nan_to_num(case["T"], nan=-7.0), atol=1e-12), (i, case["method"])
+    rec.segment("mca_setup")
+    reg = RefParams(method="clipper").get_object_registration()
+    pr = synth.make_pair(14, 12, 0, 77)
+    reg.register(pr.map1, pr.map2)
+    rec.segment("mca")                                             # get_MCA + mno_clipper of the reference's base class
+    reg.get_MCA(pr.map1, pr.map2)
+    rec.segment("mno")
+    reg.mno_clipper(pr.map1, pr.map2, num_solutions=2)
+    rec.save(os.path.join(HERE, "shim_trace_golden.npz"))
+    print(f"shim_trace_golden.npz written: {sum(len(s['events']) for s in rec.segments)} calls, {len(rec.arrays)} arrays")
+
+
 if __name__ == "__main__":
     if not os.path.isdir(REF):
         sys.exit("reference checkout not present: golden fixtures can only be regenerated where /root/reference exists")
-    install_reference_stubs()
-    which = sys.argv[1:] or ["t_align", "register", "gravity", "submap_align"]
+    install_reference_stubs()                                      # the child's `clipperpy` is then replaced by the recorder
+    if sys.argv[1:] == ["_shim_trace_child"]:
+        _shim_trace_child()
+        sys.exit(0)
+    which = sys.argv[1:] or ["t_align", "register", "gravity", "submap_align", "shim_trace"]
     if "t_align" in which:
         gen_t_align()
     if "register" in which:
@@ -352,3 +404,5 @@ if __name__ == "__main__":
         gen_gravity()
     if "submap_align" in which:
         gen_submap_align()
+    if "shim_trace" in which:
+        gen_shim_trace()

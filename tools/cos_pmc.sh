@@ -6,7 +6,7 @@ for mode in 0 16; do
 for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_MFMA SQ_WAVES" "TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum"; do
   g=$(echo $grp | tr ' ' '_' | cut -c1-30)
   export ROMAN_COS=$mode
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/cp_${mode}_$g -o b -- python $REPO/bench.py --steps 2 --warmup 1 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid > /dev/null 2>$OUT/cp_err.txt )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/cp_${mode}_$g -o b -- python $REPO/bench.py --full --steps 2 --warmup 1 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid > /dev/null 2>$OUT/cp_err.txt )
   F=$(find $OUT/cp_${mode}_$g -name "*counter_collection.csv" | head -1)
   python - "$F" "mode=$mode" <<'PY'
 import csv, sys, collections

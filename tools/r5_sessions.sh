@@ -11,7 +11,7 @@ export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 1500 python -m pytest tests -q -m gpu --durations=6 > $OUT/r5a_pytest.txt 2>&1; echo "pytest rc=$?"; tail -40 $OUT/r5a_pytest.txt
 bash tools/ab_libs.sh roman_amd/csrc/variants/libR4.so roman_amd/csrc/variants/libF1.so k_solve_up k_count k_upper > $OUT/r5a_ab.txt 2>&1; cat $OUT/r5a_ab.txt
 for L in libR4 libF1 libR4 libF1; do
-  ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/$L.so timeout 600 python bench.py --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 > $OUT/r5a_bench_$L.txt 2>$OUT/r5a_bench_$L.err
+  ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/$L.so timeout 600 python bench.py --full --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 > $OUT/r5a_bench_$L.txt 2>$OUT/r5a_bench_$L.err
   echo "== $L"; python tools/bench_digest.py $OUT/r5a_bench_$L.txt | head -3
 done
 ;;
@@ -25,7 +25,7 @@ for cfg in R4:0 C2:0 F2:0 C2:1 F2:1 R4:0 F2:0 C2:0; do
   L=${cfg%%:*}; DEEP=${cfg##*:}
   export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/lib$L.so
   if [ "$DEEP" = "1" ]; then export ROMAN_SOLVE_DEEP=1; else unset ROMAN_SOLVE_DEEP; fi
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "$L deep=$DEEP" <<'PY'
 import csv, sys
@@ -33,7 +33,7 @@ for r in csv.DictReader(open(sys.argv[1])):
     if 'k_solve_up<8' in r['Name']: print(sys.argv[2], r['Name'][:44], round(float(r['AverageNs']) / 1e3, 1), 'us')
 PY
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5b_bench_${L}_$DEEP.txt 2>$OUT/r5b_bench_${L}_$DEEP.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5b_bench_${L}_$DEEP.txt 2>$OUT/r5b_bench_${L}_$DEEP.err
   echo "== $L deep=$DEEP"; python tools/bench_digest.py $OUT/r5b_bench_${L}_$DEEP.txt | head -1
 done
 ;;
@@ -45,7 +45,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_full_config
 for cfg in R4 F3 R4 F3; do
   L=$cfg
   export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/lib$L.so
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "$L" <<'PY'
 import csv, sys
@@ -53,14 +53,14 @@ for r in csv.DictReader(open(sys.argv[1])):
     if 'k_solve_up<8' in r['Name']: print(sys.argv[2], r['Name'][:44], round(float(r['AverageNs']) / 1e3, 1), 'us')
 PY
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5c_bench_${L}.txt 2>$OUT/r5c_bench_${L}.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5c_bench_${L}.txt 2>$OUT/r5c_bench_${L}.err
   echo "== $L"; python tools/bench_digest.py $OUT/r5c_bench_${L}.txt | head -3
 done
 ;;
 d)
 # round-5 session D: per-phase cycle counters of the stream solver (timing build), B = 256 and B = 1
 export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
-ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5d_bench.txt 2> $OUT/r5d_timing.txt
+ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --full --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5d_bench.txt 2> $OUT/r5d_timing.txt
 grep -A5 "solve timing" $OUT/r5d_timing.txt | tail -40
 ;;
 e)
@@ -70,7 +70,7 @@ export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_full_configs.py tests/test_gpu_batch.py tests/test_u0_stability.py -q -m gpu -k "stagewise or config3 or config4_grid or demo_scale or fixed_point or dense_matrix or ragged or tie_fallback or explicit_u0 or random_start" > $OUT/r5e_pytest.txt 2>&1; echo "pytest rc=$?"; tail -6 $OUT/r5e_pytest.txt
 for L in F3 F4 F5 F3 F4 F5; do
   export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/lib$L.so
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "$L" <<'PY'
 import csv, sys
@@ -78,10 +78,10 @@ for r in csv.DictReader(open(sys.argv[1])):
     if 'k_solve_up<8' in r['Name']: print(sys.argv[2], r['Name'][:44], round(float(r['AverageNs']) / 1e3, 1), 'us')
 PY
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5e_bench_${L}.txt 2>$OUT/r5e_bench_${L}.err
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5e_bench_${L}.txt 2>$OUT/r5e_bench_${L}.err
   echo "== $L"; python tools/bench_digest.py $OUT/r5e_bench_${L}.txt | head -1
 done
-ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5e_benchT.txt 2> $OUT/r5e_timing.txt
+ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --full --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5e_benchT.txt 2> $OUT/r5e_timing.txt
 grep -A5 "solve timing" $OUT/r5e_timing.txt | grep -v "^--" | sed -n '1,6p;$p'
 ;;
 f)
@@ -89,7 +89,7 @@ f)
 export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 900 python -m pytest tests/test_gpu_batch.py tests/test_submap_align.py -q -m gpu -k "align_resident or large_host_batch or sharded or submap" > $OUT/r5f_pytest.txt 2>&1; echo "pytest rc=$?"; tail -25 $OUT/r5f_pytest.txt
 t0=$(date +%s)
-timeout 1200 python bench.py --steps 20 --warmup 5 > $OUT/r5f_bench.txt 2>$OUT/r5f_bench.err; echo "bench rc=$? in $(( $(date +%s) - t0 )) s"; tail -5 $OUT/r5f_bench.err
+timeout 1200 python bench.py --full --steps 20 --warmup 5 > $OUT/r5f_bench.txt 2>$OUT/r5f_bench.err; echo "bench rc=$? in $(( $(date +%s) - t0 )) s"; tail -5 $OUT/r5f_bench.err
 python tools/bench_digest.py $OUT/r5f_bench.txt | head -4
 python - <<'PY'
 import json
@@ -108,7 +108,7 @@ export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_full_configs.py -q -m gpu -k "stagewise or config3 or threshold" > $OUT/r5h_pytest.txt 2>&1; echo "pytest rc=$?"; tail -3 $OUT/r5h_pytest.txt
 for cfg in 0 1 0 1; do
   export ROMAN_COUNT_SHARE=$cfg
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "share=$cfg" <<'PY'
 import csv, sys
@@ -116,7 +116,7 @@ for r in csv.DictReader(open(sys.argv[1])):
     if 'k_count<1, 2, false' in r['Name'] or 'k_solve_up<8' in r['Name']: print(sys.argv[2], r['Name'][:40], round(float(r['AverageNs']) / 1e3, 1), 'us')
 PY
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 10 > $OUT/r5h_bench_$cfg.txt 2>$OUT/r5h_bench_$cfg.err
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 10 > $OUT/r5h_bench_$cfg.txt 2>$OUT/r5h_bench_$cfg.err
   echo "== share=$cfg"; python tools/bench_digest.py $OUT/r5h_bench_$cfg.txt | head -1
 done
 ;;
@@ -129,7 +129,7 @@ for cfg in F6:0 F7:0 F7:1 F6:0 F7:0 F7:1; do
   L=${cfg%%:*}; DEEP=${cfg##*:}
   export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/lib$L.so
   if [ "$DEEP" = "1" ]; then export ROMAN_SOLVE_DEEP=1; else unset ROMAN_SOLVE_DEEP; fi
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "$L deep=$DEEP" <<'PY'
 import csv, sys
@@ -137,11 +137,11 @@ for r in csv.DictReader(open(sys.argv[1])):
     if 'k_solve_up<8' in r['Name']: print(sys.argv[2], r['Name'][:44], round(float(r['AverageNs']) / 1e3, 1), 'us')
 PY
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5i_bench_${L}_$DEEP.txt 2>$OUT/r5i_bench_${L}_$DEEP.err
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5i_bench_${L}_$DEEP.txt 2>$OUT/r5i_bench_${L}_$DEEP.err
   echo "== $L deep=$DEEP"; python tools/bench_digest.py $OUT/r5i_bench_${L}_$DEEP.txt | head -1
 done
 unset ROMAN_SOLVE_DEEP
-ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5i_benchT.txt 2> $OUT/r5i_timing.txt
+ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --full --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5i_benchT.txt 2> $OUT/r5i_timing.txt
 grep -A5 "solve timing" $OUT/r5i_timing.txt | grep -v "^--" | sed -n '1,6p;$p'
 ;;
 j)
@@ -150,7 +150,7 @@ export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 1200 python -m pytest tests/test_gpu_parity.py tests/test_gpu_full_configs.py tests/test_gpu_batch.py tests/test_gpu_shim.py tests/test_gpu_golden.py -q -x -m gpu -k "not fixed_point and not config4_full" > $OUT/r5j_pytest.txt 2>&1; echo "pytest rc=$?"; tail -8 $OUT/r5j_pytest.txt
 for cfg in 0 1 0 1; do
   export ROMAN_LISTS=$cfg
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "lists=$cfg" <<'PY'
 import csv, sys
@@ -161,7 +161,7 @@ for r in csv.DictReader(open(sys.argv[1])):
         print(sys.argv[2], n[:36].replace('void roman::', '').replace('roman::', ''), round(float(r['AverageNs']) / 1e3, 1), 'us', r['Calls'])
 PY
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 256 --latency-reps 20 > $OUT/r5j_bench_$cfg.txt 2>$OUT/r5j_bench_$cfg.err
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 256 --latency-reps 20 > $OUT/r5j_bench_$cfg.txt 2>$OUT/r5j_bench_$cfg.err
   echo "== lists=$cfg"; python tools/bench_digest.py $OUT/r5j_bench_$cfg.txt | head -1; python - <<PY
 import json
 d=json.loads(open("$OUT/r5j_bench_$cfg.txt").read().strip().splitlines()[-1]); print("   check", d["result_check"].get("oracle_identical"), "stage", {k: round(v,3) for k,v in d["roofline"]["isolated"]["stage_ms_per_call"].items()})
@@ -174,7 +174,7 @@ export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 1200 python -m pytest tests/test_gpu_parity.py tests/test_gpu_full_configs.py tests/test_gpu_batch.py -q -x -m gpu -k "stagewise or config3 or config4_grid or demo_scale or mixed or large_host_batch or align_resident or ragged" > $OUT/r5k_pytest.txt 2>&1; echo "pytest rc=$?"; tail -5 $OUT/r5k_pytest.txt
 for cfg in 0 1 x; do
   if [ "$cfg" = "x" ]; then unset ROMAN_LISTS; else export ROMAN_LISTS=$cfg; fi
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "lists=$cfg" <<'PY'
 import csv, sys
@@ -184,7 +184,7 @@ for r in csv.DictReader(open(sys.argv[1])):
         print(sys.argv[2], n[:36].replace('void roman::', '').replace('roman::', ''), round(float(r['AverageNs']) / 1e3, 1), 'us', r['Calls'])
 PY
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 256 --latency-reps 20 > $OUT/r5k_bench_$cfg.txt 2>$OUT/r5k_bench_$cfg.err
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 256 --latency-reps 20 > $OUT/r5k_bench_$cfg.txt 2>$OUT/r5k_bench_$cfg.err
   echo "== lists=$cfg"; python tools/bench_digest.py $OUT/r5k_bench_$cfg.txt | head -1
 done
 ;;
@@ -192,10 +192,10 @@ l)
 # round-5 session L: k_lists, second cut (six steps in flight, one table read per column, two bits per round, wave-local sort stages)
 export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 1200 python -m pytest tests/test_gpu_parity.py tests/test_gpu_full_configs.py tests/test_gpu_batch.py -q -x -m gpu -k "stagewise or config3 or config4_grid or demo_scale or mixed or large_host_batch or align_resident or ragged" > $OUT/r5l_pytest.txt 2>&1; echo "pytest rc=$?"; tail -5 $OUT/r5l_pytest.txt
-ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libLT.so timeout 300 python bench.py --steps 1 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps -1 2>&1 | grep "k_lists" | tail -4
+ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libLT.so timeout 300 python bench.py --full --steps 1 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps -1 2>&1 | grep "k_lists" | tail -4
 for cfg in 0 x 0 x; do
   if [ "$cfg" = "x" ]; then unset ROMAN_LISTS; else export ROMAN_LISTS=$cfg; fi
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "lists=$cfg" <<'PY'
 import csv, sys
@@ -205,7 +205,7 @@ for r in csv.DictReader(open(sys.argv[1])):
         print(sys.argv[2], n[:36].replace('void roman::', '').replace('roman::', ''), round(float(r['AverageNs']) / 1e3, 1), 'us', r['Calls'])
 PY
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 256 --latency-reps 20 > $OUT/r5l_bench_$cfg.txt 2>$OUT/r5l_bench_$cfg.err
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 256 --latency-reps 20 > $OUT/r5l_bench_$cfg.txt 2>$OUT/r5l_bench_$cfg.err
   echo "== lists=$cfg"; python tools/bench_digest.py $OUT/r5l_bench_$cfg.txt | head -1
 done
 ;;
@@ -216,7 +216,7 @@ export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_full_configs.py tests/test_gpu_batch.py tests/test_u0_stability.py -q -m gpu -k "stagewise or config3 or config4_grid or demo_scale or fixed_point or dense_matrix or ragged or tie_fallback or explicit_u0 or random_start" > $OUT/r5n_pytest.txt 2>&1; echo "pytest rc=$?"; tail -4 $OUT/r5n_pytest.txt
 for ST in 0 1 0 1; do
   export ROMAN_SOLVE_STRIDED=$ST
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "strided=$ST" <<'PY'
 import csv, sys
@@ -224,11 +224,11 @@ for r in csv.DictReader(open(sys.argv[1])):
     if 'k_solve_up<8' in r['Name']: print(sys.argv[2], r['Name'][:44], round(float(r['AverageNs']) / 1e3, 1), 'us')
 PY
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 64 --latency-reps 20 > $OUT/r5n_bench_$ST.txt 2>$OUT/r5n_bench_$ST.err
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 64 --latency-reps 20 > $OUT/r5n_bench_$ST.txt 2>$OUT/r5n_bench_$ST.err
   echo "== strided=$ST"; python tools/bench_digest.py $OUT/r5n_bench_$ST.txt | head -1
 done
 for ST in 0 1; do
-  ROMAN_SOLVE_STRIDED=$ST ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5n_benchT_$ST.txt 2> $OUT/r5n_timing_$ST.txt
+  ROMAN_SOLVE_STRIDED=$ST ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --full --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5n_benchT_$ST.txt 2> $OUT/r5n_timing_$ST.txt
   echo "== phases strided=$ST"; grep -A5 "solve timing" $OUT/r5n_timing_$ST.txt | grep -v "^--" | sed -n '1,6p;$p'
 done
 ;;
@@ -255,10 +255,10 @@ timeout 1500 python -m pytest tests -q -m gpu -x --durations=5 > $OUT/r5q_pytest
 ( export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libST.so
   python tools/gpu_demo_latency.py 4 2>&1 | grep "finish_one\|k_small" | sort | uniq -c | sort -rn | head -4
   python tools/gpu_demo_scale.py 2>&1 | grep "finish_one\|k_small" | tail -6
-  python bench.py --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 2>&1 | grep "finish_one" | tail -4 )
-timeout 900 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 256 --latency-reps 20 > $OUT/r5q_bench.txt 2>$OUT/r5q_bench.err
+  python bench.py --full --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 2>&1 | grep "finish_one" | tail -4 )
+timeout 900 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 256 --latency-reps 20 > $OUT/r5q_bench.txt 2>$OUT/r5q_bench.err
 python tools/bench_digest.py $OUT/r5q_bench.txt | head -4
-( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
 F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
 python - "$F" <<'PY'
 import csv, sys
@@ -276,7 +276,7 @@ r)
 export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 for L in R5m new R5m new; do
   if [ "$L" = "new" ]; then unset ROMAN_HIP_LIBRARY; else export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/lib$L.so; fi
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5r_bench_$L.txt 2>$OUT/r5r_bench_$L.err
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5r_bench_$L.txt 2>$OUT/r5r_bench_$L.err
   echo "== $L"; python tools/bench_digest.py $OUT/r5r_bench_$L.txt | head -1
   python - $OUT/r5r_bench_$L.txt <<'PY'
 import json, sys
@@ -285,7 +285,7 @@ print("   isolated launch", d["roofline"]["isolated"]["avg_launch_ms"], "ms, roo
 PY
 done
 unset ROMAN_HIP_LIBRARY
-ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5r_benchT.txt 2> $OUT/r5r_timing.txt
+ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --full --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5r_benchT.txt 2> $OUT/r5r_timing.txt
 grep -A5 "solve timing" $OUT/r5r_timing.txt | grep -v "^--" | sed -n '1,6p;$p'
 python tools/gpu_cos_block_sweep.py 2>&1 | tee $OUT/r5r_cos_block_sweep.txt
 ;;
@@ -297,10 +297,10 @@ export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 1500 python -m pytest tests -q -m gpu -x > $OUT/r5s_pytest.txt 2>&1; echo "pytest rc=$?"; tail -3 $OUT/r5s_pytest.txt
 ( export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libST.so
   python tools/gpu_demo_latency.py 4 2>&1 | grep "finish_one" | sort | uniq -c | sort -rn | head -2
-  python bench.py --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 2>&1 | grep "finish_one" | tail -3 )
+  python bench.py --full --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 2>&1 | grep "finish_one" | tail -3 )
 for L in R5z new R5z new; do
   if [ "$L" = "new" ]; then unset ROMAN_HIP_LIBRARY; else export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/lib$L.so; fi
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 64 --latency-reps 20 > $OUT/r5s_bench_$L.txt 2>$OUT/r5s_bench_$L.err
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 64 --latency-reps 20 > $OUT/r5s_bench_$L.txt 2>$OUT/r5s_bench_$L.err
   echo "== $L"; python tools/bench_digest.py $OUT/r5s_bench_$L.txt | head -1
   python - $OUT/r5s_bench_$L.txt <<'PY'
 import json, sys
@@ -317,9 +317,9 @@ export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 1500 python -m pytest tests -q -m gpu -x > $OUT/r5t_pytest.txt 2>&1; echo "pytest rc=$?"; tail -3 $OUT/r5t_pytest.txt
 for L in R5s new R5s new; do
   if [ "$L" = "new" ]; then unset ROMAN_HIP_LIBRARY; else export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/lib$L.so; fi
-  timeout 600 python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5t_bench_$L.txt 2>$OUT/r5t_bench_$L.err
+  timeout 600 python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 > $OUT/r5t_bench_$L.txt 2>$OUT/r5t_bench_$L.err
   echo "== $L"; python tools/bench_digest.py $OUT/r5t_bench_$L.txt | head -1
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps 100 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps 100 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "$L" <<'PY'
 import csv, sys
@@ -334,7 +334,7 @@ z)
 # stats + the four PMC groups, solver phase cycles, the serial caller at demo scale, the N > 1 code path on one GPU
 bash tools/gpu_session.sh r5z tests smoke bench prof pmc
 export TMPDIR=/tmp; OUT=$PWD/gpurun_out; REPO=$PWD
-ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5z_benchT.txt 2> $OUT/r5z_timing.txt
+ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/libT.so timeout 600 python bench.py --full --steps 2 --warmup 1 --pipeline 1 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 2 > $OUT/r5z_benchT.txt 2> $OUT/r5z_timing.txt
 grep -A5 "solve timing" $OUT/r5z_timing.txt | grep -v "^--" | sed -n '1,6p;$p' | tee $OUT/r5z_phase_cycles.txt
 python tools/gpu_demo_latency.py 24 2>&1 | tee $OUT/r5z_demo_latency.txt
 bash tools/scale_preflight.sh 2>&1 | tail -6

@@ -6,7 +6,7 @@ TAG=${1:-r6m}; export TMPDIR=/tmp; OUT=$PWD/gpurun_out; mkdir -p $OUT; REPO=$PWD
 timeout 1200 python -m pytest tests -q -x -m gpu -k "bounded_solver or config3 or config4 or ragged or two_batches or candidate" > $OUT/${TAG}_pytest.txt 2>&1; echo "pytest rc=$?"; tail -4 $OUT/${TAG}_pytest.txt
 for cap in default 0 default 0; do
   if [ "$cap" = "default" ]; then unset ROMAN_SOLVE_CAP; else export ROMAN_SOLVE_CAP=$cap; fi
-  timeout 900 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --check-pairs 0 > $OUT/${TAG}_bench_cap$cap.txt 2>/dev/null
+  timeout 900 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --check-pairs 0 > $OUT/${TAG}_bench_cap$cap.txt 2>/dev/null
   python - $OUT/${TAG}_bench_cap$cap.txt bench_extras.json "cap=$cap" <<'PY'
 import json, sys
 line = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); ex = json.load(open(sys.argv[2]))

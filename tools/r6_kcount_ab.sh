@@ -12,7 +12,7 @@ for p in $CFGS; do
     1) ;;
     *) export ROMAN_HIP_LIBRARY=$REPO/roman_amd/csrc/variants/lib$p.so ;;
   esac
-  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
+  ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ab_tmp -o b -- python $REPO/bench.py --full --steps 5 --warmup 2 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras --no-grid --check-pairs 0 > /dev/null 2>&1 )
   F=$(find $OUT/ab_tmp -name "*kernel_stats.csv" | head -1)
   python - "$F" "cfg=$p" <<'PY'
 import csv, sys
@@ -21,5 +21,5 @@ for r in csv.DictReader(open(sys.argv[1])):
 PY
   cp "$F" $OUT/${TAG}_kernel_stats_cfg$p.csv
   rm -rf $OUT/ab_tmp
-  timeout 600 python bench.py --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 2>/dev/null | python tools/bench_digest.py /dev/stdin | head -1
+  timeout 600 python bench.py --full --steps 20 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps 20 2>/dev/null | python tools/bench_digest.py /dev/stdin | head -1
 done

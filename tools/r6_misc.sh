@@ -8,5 +8,5 @@ for r in csv.DictReader(open(sys.argv[1])):
     if float(r["Percentage"]) > 0.9: print(r["Name"][:50], r["Calls"], round(float(r["AverageNs"]) / 1e3, 1))
 PY
 for d in 3 4 2 3 4; do
-  python bench.py --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps -1 --pipeline $d 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('depth $d', round(d['value']), round(d['ms_per_step'], 4))"
+  python bench.py --full --steps 40 --warmup 5 --no-extras --no-grid --cpu-sample 0 --check-pairs 0 --latency-reps -1 --pipeline $d 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('depth $d', round(d['value']), round(d['ms_per_step'], 4))"
 done

@@ -10,6 +10,6 @@ run() {   # tag, library ("" = the in-tree one), command...
 PY="import sys; sys.path.insert(0, '$REPO');"
 run smoke "" python -c "$PY import __graft_entry__ as g; g.smoke()"
 run smoke_old "$REPO/roman_amd/csrc/variants/libOLD.so" python -c "$PY import __graft_entry__ as g; g.smoke()"
-run bench "" python $REPO/bench.py --steps 3 --warmup 1 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras
-run bench_old "$REPO/roman_amd/csrc/variants/libOLD.so" python $REPO/bench.py --steps 3 --warmup 1 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras
-run bench_p3 "" python $REPO/bench.py --steps 3 --warmup 1 --latency-reps -1 --cpu-sample 0 --no-extras
+run bench "" python $REPO/bench.py --full --steps 3 --warmup 1 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras
+run bench_old "$REPO/roman_amd/csrc/variants/libOLD.so" python $REPO/bench.py --full --steps 3 --warmup 1 --pipeline 1 --latency-reps -1 --cpu-sample 0 --no-extras
+run bench_p3 "" python $REPO/bench.py --full --steps 3 --warmup 1 --latency-reps -1 --cpu-sample 0 --no-extras
