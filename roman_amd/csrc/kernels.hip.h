@@ -985,20 +985,25 @@ __global__ void __launch_bounds__(256, CosDeal<T>::WAVES) k_cos_deal(DevParams D
 // (single_score(): an association with (cos - cosine_min) / (cosine_max - cosine_min) <= 0 scores 0 whatever its cosine is).
 // k_cos_deal computes all n1 x n2 cosines in f64 on the matrix core and is POWER-bound (295 us at config 3); ~95 % of its
 // products are thrown away by the gate.  Here one workgroup of 16 waves takes a problem:
-//   pass 1  approximate cosines of all pairs: rows converted to bf16 on the way into LDS, v_mfma_f32_16x16x32_bf16 (1/32 of the
-//           f64 MFMA's matrix-pipe time), divided by the EXACT f64 norms (summed here in the oracle's stated order: four chains,
-//           (s0 + s1) + (s2 + s3));
-//   select  pair (i, j) is a CANDIDATE unless approx < cosine_min - delta.  |approx - cos| <= 2^-8 (two bf16 roundings of 2^-9
-//           each, Cauchy-Schwarz over the contraction) + 512 * 2^-22 (f32 accumulation, any order, truncating or not) < 0.0041
-//           for rows whose norm lies in [2^-40, 2^40] (no element over- or underflows in bf16 / f32 beyond 2^-86 of the product of
-//           the norms); rows with any other non-zero norm (huge, tiny, inf, NaN) make all their pairs candidates.  delta = 2^-6.
+//   pass 1  approximate cosines of all pairs: rows converted to bf16 on the way into LDS (f64 -> f32 -> bf16, each conversion ROUND TO
+//           NEAREST EVEN: the bound below needs a unit roundoff of 2^-8 for bf16, and a truncating conversion doubles it),
+//           v_mfma_f32_16x16x32_bf16 (1/32 of the f64 MFMA's matrix-pipe time), divided by the bf16 rows' OWN norms (the diagonals of the
+//           same bf16 products, accumulated in f32) — not by the exact f64 norms;
+//   select  pair (i, j) is a CANDIDATE unless approx < cosine_min - delta.  The screen is the exact cosine of the rounded rows a^, b^;
+//           each rounding turns a row by an angle of at most asin(2^-8 (1 + 2^-24)), so |cos(a^, b^) - cos(a, b)| <= ~2 * 2^-8 = 2^-7,
+//           plus ~3 Fc 2^-24 (the f32 accumulation of the product and of the two norms, any order, truncating or not: 2^-13 at
+//           Fc = 512) — about 0.0079 for rows whose norm lies in [2^-40, 2^40] (no element over- or underflows in bf16 / f32 beyond 2^-86 of the product of
+//           the norms); rows with any other non-zero norm (huge, tiny, inf, NaN) make all their pairs candidates.  delta = 2^-6: a
+//           margin of 2x the bound.
 //   pass 2  the candidates' dot products in f64 with k_cos_deal's own contraction order (oracle dot_fixed(): per chunk of 16, t = 0..3
 //           outer, g = 0..3 inner, k = k0 + 4 g + t, ONE fma chain), rows staged through LDS chunk by chunk, candidates sorted by i so
-//           that the lanes of a wave read few distinct a rows (LDS broadcast); cos = dot / (na * nb) as everywhere.
-// A non-candidate's entry of the pool holds the APPROXIMATE cosine (< cosine_min - delta + 0.0041 < cosine_min, and so is the exact one:
+//           that the lanes of a wave read few distinct a rows (LDS broadcast); the exact norms summed from the same staged chunks in the
+//           oracle's stated order (four chains, (s0 + s1) + (s2 + s3)); cos = dot / (na * nb) as everywhere.
+// A non-candidate's entry of the pool holds the APPROXIMATE cosine (< cosine_min - delta + 2^-7 < cosine_min, and so is the exact one:
 // both fail the gate alike).  Candidates' entries are bit-identical to k_cos_deal's.  A problem with more than CSEL_CAP candidates (or maps
 // of more than 256 objects) is flagged in dense[] and left to k_cos_deal<., ., true>, which the launcher runs behind this kernel for the
-// flagged problems only.  Never used for roman_debug_cosine / the pruned prefilter (raw products) / cosine_max <= cosine_min.
+// flagged problems only.  Never used for the pruned prefilter (raw products) / cosine_max <= cosine_min.  k_cos_sel itself serves
+// roman_debug_cosine (ROMAN_COS_SEL=approx / gated); the batched path takes k_cos_live (below: the same passes, no cosine matrix).
 // ---------------------------------------------------------------------------------------------
 constexpr int CSEL_ROWS = 512;                   // staged rows: A rows [0, 16 nb1), B rows [16 nb1, 16 nb1 + 16 nb2)
 constexpr int CSEL_MAXN = 256;                   // objects per map
@@ -1016,9 +1021,19 @@ struct __attribute__((packed, aligned(8))) d8u_t { double v[8]; };     // 8-byte
 
 __device__ __forceinline__ bool csel_unsafe(double n) { return !(n >= 0x1p-40 && n <= 0x1p40); }
 
-__global__ void __launch_bounds__(1024) k_cos_sel(DevParams D, int B, const ProbDesc* __restrict__ probs, const double* __restrict__ feats,
-                                                  double* __restrict__ cosPool, int32_t* __restrict__ dense /* [B] out: 1 = left to the dense kernel */,
-                                                  double thr /* cosine_min - delta; +inf: no candidates (the approximate matrix, tests) */)
+// (a problem's live associations: the kind of solver its live count takes — k_live<1> and k_cos_live)
+__device__ __forceinline__ int live_kind(const DevParams& D, int L)
+{
+    return (L <= D.stream_maxL && D.p.maxiniters >= 1 && D.p.maxlsiters >= 1) ? 0 : (D.allow_fallback ? 1 : 2);
+}
+
+// The body of k_cos_sel (LIVE = false: the cosine matrix) and of k_cos_live (LIVE = true: gate, single scores and the live pools of the
+// problem; nothing in cosPool).  `lv` is only read with LIVE.
+struct CselLive { ProbState* st; int32_t* lp; int32_t* li; int32_t* lj; double* ls; double* ld; double* lza; double* lzb; };
+
+template <bool LIVE>
+__device__ __forceinline__ void cos_sel_body(const DevParams& D, int B, const ProbDesc* __restrict__ probs, const double* __restrict__ feats,
+                                             double* __restrict__ cosPool, int32_t* __restrict__ dense, double thr, const CselLive& lv)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* stage = smem;
@@ -1032,7 +1047,16 @@ __global__ void __launch_bounds__(1024) k_cos_sel(DevParams D, int B, const Prob
     const ProbDesc pd = probs[b];
     const int tid = threadIdx.x, lane = tid & 63, w = uni_i(tid >> 6);
     const int n1 = pd.n1, n2 = pd.n2;
-    if (n1 <= 0 || n2 <= 0) { if (tid == 0) dense[b] = 0; return; }
+    auto publish = [&](int L) {                                          // (LIVE: what k_live<1> writes for the problem)
+        if (LIVE && tid == 0) { lv.st[b].L = L; lv.st[b].nnzUpper = 0ull; lv.st[b].kind = live_kind(D, L); }
+    };
+#ifdef ROMAN_CSEL_TIMING
+    unsigned long long tc_[5]; tc_[0] = __builtin_readcyclecounter();
+#define CMARK(i_) tc_[i_] = __builtin_readcyclecounter()
+#else
+#define CMARK(i_) do { } while (0)
+#endif
+    if (n1 <= 0 || n2 <= 0) { if (tid == 0) dense[b] = 0; publish(0); return; }
     const int nb1 = (n1 + 15) >> 4, nb2 = (n2 + 15) >> 4, RB = 16 * nb1, nblk = nb1 * nb2, rowsTot = RB + 16 * nb2;
     if (n1 > CSEL_MAXN || n2 > CSEL_MAXN || nblk > 16 * CSEL_MP) { if (tid == 0) dense[b] = 1; return; }
     const int Fc = D.p.cos_feature_dim, coff = D.p.point_dim + D.p.ratio_feature_dim;
@@ -1048,7 +1072,7 @@ __global__ void __launch_bounds__(1024) k_cos_sel(DevParams D, int B, const Prob
     // 128 elements of every row as bf16 (rows x 272 B); wave w owns the rows w, w + 16, ...; four rows per register set, two sets, each
     // re-loaded as soon as it is staged — also across the tile's barrier and its MFMAs.
     // The screen's norms are the bf16 rows' own (the diagonals of the products of every block of 16 rows with itself: wave w the
-    // blocks w, w + 16 — no f64 arithmetic in this pass): cos(a^, b^) against cos(a, b) — two angles of at most asin(2^-9).
+    // blocks w, w + 16 — no f64 arithmetic in this pass): cos(a^, b^) against cos(a, b) — two angles of at most asin(2^-8) (see the bound above).
     constexpr int KT = 128, G1 = 4;
     const int nt = rowsTot >> 4;                                         // rows of a wave
     // No branch and no address arithmetic inside the stream of loads (a branch makes the compiler wait for ALL outstanding loads at its
@@ -1161,6 +1185,7 @@ __global__ void __launch_bounds__(1024) k_cos_sel(DevParams D, int B, const Prob
             if (((lane & 15) >> 2) == (lane >> 4)) nrm[16 * (w + 16 * m) + (lane & 15)] = sqrt((double)v);
         }
     __syncthreads();
+    CMARK(1);
 
     // ---- select -------------------------------------------------------------------------------------------
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -1178,7 +1203,7 @@ __global__ void __launch_bounds__(1024) k_cos_sel(DevParams D, int B, const Prob
                 // (a row whose f32 norm is zero, tiny, huge or no number is left to the exact pass altogether: its guard for zero norms too)
                 const double cv = (double)acc[m][rr] / (na * nbv);
                 const bool cand = ok && (csel_unsafe(na) || csel_unsafe(nbv) || !(cv < thr));
-                if (ok && !cand) cosPool[pd.cosOff + (int64_t)i * n2 + j] = cv;
+                if (!LIVE && ok && !cand) cosPool[pd.cosOff + (int64_t)i * n2 + j] = cv;
                 const unsigned long long bm = __ballot(cand);
                 if (bm) {
                     int base = 0;
@@ -1196,7 +1221,7 @@ __global__ void __launch_bounds__(1024) k_cos_sel(DevParams D, int B, const Prob
     const int nc = hist[256];
     if (nc > CSEL_CAP) { if (tid == 0) dense[b] = 1; return; }
     if (tid == 0) dense[b] = 0;
-    if (nc == 0) return;
+    if (nc == 0) { publish(0); return; }
     if (w == 0) {                                // cursors: exclusive prefix of the 256 row counts
         const int c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
         int incl = c0 + c1 + c2 + c3;
@@ -1208,6 +1233,7 @@ __global__ void __launch_bounds__(1024) k_cos_sel(DevParams D, int B, const Prob
     __syncthreads();
     for (int q = tid; q < nc; q += 1024) { const uint32_t v = U[q]; S[atomicAdd(&cur[v & 0xffffu], 1)] = v; }
     __syncthreads();
+    CMARK(2);
 
     // ---- pass 2 -------------------------------------------------------------------------------------------
     // The rows come again, chunk by chunk, as f64 (the same lanes, the same two register sets in flight).  The exact norms (the oracle's
@@ -1306,18 +1332,103 @@ __global__ void __launch_bounds__(1024) k_cos_sel(DevParams D, int B, const Prob
             __syncthreads();
         }
     }
+    CMARK(3);
+    // (LIVE: the live bits of the problem, 4 words per row of map 1, where pass 2's chunk was — every wave is behind its last barrier)
+    unsigned long long* liveBits = reinterpret_cast<unsigned long long*>(stage);
+    static_assert(CSEL_MAXN * (CSEL_MAXN / 64) <= 1024 && CSEL_MAXN * (CSEL_MAXN / 64) * 8 <= CSEL_ROWS * CSEL_P2, "one word per thread, in pass 2's chunk");
+    if (LIVE) liveBits[tid] = 0ull;
     {
         const double p = s0 + s1, q = __shfl_xor(p, 1);
         if (hN == 0) nrm[rN] = sqrt(p + q);      // (s0 + s1) + (s2 + s3)
     }
     __syncthreads();
+    double sc[CSEL_NPT];
+    bool live[CSEL_NPT];
 #pragma unroll
-    for (int m = 0; m < CSEL_NPT; ++m)
+    for (int m = 0; m < CSEL_NPT; ++m) {
+        live[m] = false; sc[m] = 0.0;
         if (m < cnt2) {
             const int i = (int)(my[m] & 0xffffu), j = (int)(my[m] >> 16);
             const double na = nrm[i], nbv = nrm[RB + j];
-            cosPool[pd.cosOff + (int64_t)i * n2 + j] = (na > 0.0 && nbv > 0.0) ? dot[m] / (na * nbv) : 0.0;
+            const double cosv = (na > 0.0 && nbv > 0.0) ? dot[m] / (na * nbv) : 0.0;
+            if (!LIVE) cosPool[pd.cosOff + (int64_t)i * n2 + j] = cosv;
+            // k_live<0>'s gate and full score on the exact cosine (a non-candidate fails the gate: see above)
+            else if ((cosv - D.p.cosine_min) / (D.p.cosine_max - D.p.cosine_min) > 0.0) {
+                const int pdm = D.p.point_dim;
+                const double* fi = feats + (pd.off1 + i) * D.F + pdm; const double* fj = feats + (pd.off2 + j) * D.F + pdm;
+                sc[m] = single_score(D, [&](int f) { return fi[f]; }, [&](int f) { return fj[f]; }, cosv);
+                live[m] = sc[m] > 0.0;
+                if (live[m]) atomicOr(&liveBits[4 * i + (j >> 6)], 1ull << (j & 63));
+            }
         }
+    }
+    if (!LIVE) { CMARK(4); }
+    else {
+        // ordered compaction: the live association (i, j) goes to position (live in rows < i) + (live in row i at columns < j) — ascending
+        // association index i n2 + j, whatever order the candidates arrived in
+        __syncthreads();
+        if (w == 0) {                            // row bases: exclusive prefix of the 256 row counts; cur[256]: the problem's total
+            int c4[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const unsigned long long* rw = liveBits + 4 * (4 * lane + k);
+                c4[k] = __popcll(rw[0]) + __popcll(rw[1]) + __popcll(rw[2]) + __popcll(rw[3]);
+            }
+            int incl = c4[0] + c4[1] + c4[2] + c4[3];
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+            const int ex = incl - (c4[0] + c4[1] + c4[2] + c4[3]);
+            cur[4 * lane] = ex; cur[4 * lane + 1] = ex + c4[0]; cur[4 * lane + 2] = ex + c4[0] + c4[1]; cur[4 * lane + 3] = ex + c4[0] + c4[1] + c4[2];
+            if (lane == 63) cur[256] = incl;
+        }
+        __syncthreads();
+        const int64_t lo = pd.liveOff;
+        const bool has_z = D.p.point_dim == 3;
+#pragma unroll
+        for (int m = 0; m < CSEL_NPT; ++m)
+            if (live[m]) {
+                const int i = (int)(my[m] & 0xffffu), j = (int)(my[m] >> 16), wj = j >> 6;
+                const unsigned long long* rw = liveBits + 4 * i;
+                int pos = cur[i] + __popcll(rw[wj] & ((1ull << (j & 63)) - 1ull));
+                for (int k = 0; k < wj; ++k) pos += __popcll(rw[k]);
+                const double s = sc[m];
+                lv.lp[lo + pos] = i * n2 + j; lv.li[lo + pos] = i; lv.lj[lo + pos] = j; lv.ls[lo + pos] = s;
+                lv.ld[lo + pos] = D.diag_one ? 1.0 : s;
+                lv.lza[lo + pos] = has_z ? feats[(pd.off1 + i) * D.F + 2] : 0.0;
+                lv.lzb[lo + pos] = has_z ? feats[(pd.off2 + j) * D.F + 2] : 0.0;
+            }
+        publish(cur[256]);
+        CMARK(4);
+    }
+#ifdef ROMAN_CSEL_TIMING
+    if (tid == 0 && (b & 63) == 0) printf("[%s] b=%d candidates=%d cycles: pass1 %llu select %llu pass2 %llu tail %llu\n", LIVE ? "k_cos_live" : "k_cos_sel", b, nc,
+                                          tc_[1] - tc_[0], tc_[2] - tc_[1], tc_[3] - tc_[2], tc_[4] - tc_[3]);
+#endif
+#undef CMARK
+}
+
+__global__ void __launch_bounds__(1024) k_cos_sel(DevParams D, int B, const ProbDesc* __restrict__ probs, const double* __restrict__ feats,
+                                                  double* __restrict__ cosPool, int32_t* __restrict__ dense /* [B] out: 1 = left to the dense kernel */,
+                                                  double thr /* cosine_min - delta; +inf: no candidates (the approximate matrix, tests) */)
+{
+    cos_sel_body<false>(D, B, probs, feats, cosPool, dense, thr, CselLive{});
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_cos_live: the cosine stage AND k_live<0> + k_live<1> of a batch of all-to-all problems (assocOff < 0) whose single scores are gated
+// (the conditions of k_cos_sel, and not keep_all) in one workgroup per problem: k_cos_sel's passes (the same screen and bound, the
+// same candidates, cosines bit-identical to k_cos_deal's), then, for every candidate, k_live<0>'s gate on its exact cosine and
+// single_score() with the same operands, and the problem's live pools in ascending association index with L / kind / nnzUpper as
+// k_live<1> writes them.  Non-candidates fail the gate (their exact cosine is below cosine_min).  No cosine matrix is written: the
+// 8 bytes per pair of the batch that k_live<0> read back only to gate.  A problem flagged in dense[] (more than CSEL_CAP candidates,
+// maps beyond the block budget) is left whole to k_cos_deal + k_live, which the launcher runs behind this kernel for those only.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(1024) k_cos_live(DevParams D, int B, const ProbDesc* __restrict__ probs, const double* __restrict__ feats,
+                                                   int32_t* __restrict__ dense /* [B] out: 1 = left to the dense kernels */, double thr /* cosine_min - delta */,
+                                                   ProbState* __restrict__ st, int32_t* __restrict__ lp, int32_t* __restrict__ li, int32_t* __restrict__ lj,
+                                                   double* __restrict__ ls, double* __restrict__ ld, double* __restrict__ lza, double* __restrict__ lzb)
+{
+    cos_sel_body<true>(D, B, probs, feats, nullptr, dense, thr, CselLive{st, lp, li, lj, ls, ld, lza, lzb});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1389,11 +1500,13 @@ __global__ void __launch_bounds__(256) k_live(DevParams D, const ProbDesc* __res
                                               int32_t* __restrict__ segCnt, int maxChunks,
                                               int32_t* __restrict__ lp, int32_t* __restrict__ li,
                                               int32_t* __restrict__ lj, double* __restrict__ ls, double* __restrict__ ld,
-                                              double* __restrict__ lza, double* __restrict__ lzb)
+                                              double* __restrict__ lza, double* __restrict__ lzb,
+                                              const int32_t* __restrict__ only /* NULL, or [B]: problems with a 0 are skipped (k_cos_live completed them) */)
 {
     __shared__ int cbase[2];
     __shared__ uint16_t survQ[PHASE == 0 ? 4 : 1][PHASE == 0 ? LIVE_CHUNK / 4 : 1];     // phase 0: per wave, the associations behind the cosine gate
     const int b = blockIdx.y, c = blockIdx.x;
+    if (only && !only[b]) return;
     const ProbDesc pd = probs[b];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     const int nA = pd.nA;
@@ -1489,7 +1602,7 @@ __global__ void __launch_bounds__(256) k_live(DevParams D, const ProbDesc* __res
     const int Ltot = all_live ? nA : cbase[1];
     if (c == 0 && tid == 0) {
         st[b].L = Ltot; st[b].nnzUpper = 0ull;
-        st[b].kind = (Ltot <= D.stream_maxL && D.p.maxiniters >= 1 && D.p.maxlsiters >= 1) ? 0 : (D.allow_fallback ? 1 : 2);
+        st[b].kind = live_kind(D, Ltot);
     }
     if (c >= nChunks) return;
     int base = cbase[0];

@@ -370,6 +370,8 @@ int make_solve_out(roman_ctx* c, int B, int64_t sumA, const BatchOut& out, Solve
 // The cosines of a batch that are only used behind the gate cos > cosine_min: k_cos_sel (bf16 screen of all pairs, exact f64 for the
 // candidates), then k_cos_deal for the problems it flagged (more candidates than its list holds).  `approx`: no candidates at all —
 // the screen's own matrix (tests).
+static hipError_t launch_cos_flagged(roman_ctx* c, hipStream_t stream, const DevParams& D, int B, int maxN1, int maxN2, const ProbDesc* dP, const double* feats,
+                                     double* cosPool, const int32_t* dense);
 static hipError_t launch_cos_sel(roman_ctx* c, hipStream_t stream, const DevParams& D, int B, int maxN1, int maxN2, const ProbDesc* dP, const double* feats, double* cosPool,
                                  int32_t* dense, bool approx)
 {
@@ -379,6 +381,26 @@ static hipError_t launch_cos_sel(roman_ctx* c, hipStream_t stream, const DevPara
     hipLaunchKernelGGL(k_cos_sel, dim3((unsigned)B), dim3(1024), (size_t)CSEL_LDS, stream, D, B, dP, feats, cosPool, dense, thr);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_cos_flagged(c, stream, D, B, maxN1, maxN2, dP, feats, cosPool, dense);
+}
+// The cosine stage AND the single scores / live pools of a batch of all-to-all problems (k_cos_live), then, for the problems it flagged,
+// k_cos_deal; the launcher runs k_live behind it for those only.
+static hipError_t launch_cos_live(roman_ctx* c, hipStream_t stream, const DevParams& D, int B, int maxN1, int maxN2, const ProbDesc* dP, const double* feats, double* cosPool,
+                                  int32_t* dense, ProbState* st, const LivePools& LP)
+{
+    hipError_t e = dyn_lds(c, reinterpret_cast<const void*>(k_cos_live), (size_t)CSEL_LDS);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cos_live, dim3((unsigned)B), dim3(1024), (size_t)CSEL_LDS, stream, D, B, dP, feats, dense, D.p.cosine_min - 0x1p-6,
+                       st, LP.lp, LP.li, LP.lj, LP.ls, LP.ld, LP.lza, LP.lzb);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_cos_flagged(c, stream, D, B, maxN1, maxN2, dP, feats, cosPool, dense);
+}
+// k_cos_deal behind k_cos_sel / k_cos_live for the problems they flagged (more candidates than their list holds, maps beyond the block budget)
+static hipError_t launch_cos_flagged(roman_ctx* c, hipStream_t stream, const DevParams& D, int B, int maxN1, int maxN2, const ProbDesc* dP, const double* feats,
+                                     double* cosPool, const int32_t* dense)
+{
+    hipError_t e;
     constexpr int TD = 5;
     using CD = CosDeal<TD>;
     const int Gd = CD::tiles(maxN1) * CD::tiles(maxN2);
@@ -497,6 +519,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     hd.assign(B, ProbDesc{});
     int64_t sumA = 0, sumCos = 0, sumTab = 0, sumQ4 = 0;
     int maxN12 = 0, maxN = 0, maxA = 0, maxN1 = 0, maxN2 = 0; int64_t maxTab = 0, poolRows = 0 /* rows of the feature pool the batch names */;
+    bool allToAll = true;                              // no problem carries an explicit association list (k_cos_live's condition)
     for (int b = 0; b < B; ++b) {
         ProbDesc& d = hd[b];
         d.off1 = in.off1[b]; d.off2 = in.off2[b]; d.n1 = in.n1[b]; d.n2 = in.n2[b];
@@ -506,6 +529,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
         if (in.assoc && na_list > 0) {
             d.assocOff = in.assoc_off[b];
             d.nA = (int32_t)na_list;
+            allToAll = false;
         } else {                                       // no list, or an EMPTY one: all-to-all (clipperpy replaces an empty A likewise)
             d.assocOff = -1;
             const int64_t na = (int64_t)d.n1 * d.n2;
@@ -605,13 +629,17 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     const LivePools PP{WS.plp.as<int32_t>(), WS.pli.as<int32_t>(), WS.plj.as<int32_t>(), WS.pls.as<double>(), WS.pld.as<double>(), WS.plza.as<double>(), WS.plzb.as<double>()};
 
     StageTimer t0(c, ROMAN_STAGE_SINGLE);
-    bool cosScreen = false;
+    bool cosScreen = false, cosLive = false;           // cosLive: k_cos_live has scored the problems it did not flag, k_live takes the flagged ones
     if (cosOn && maxN1 > 0 && maxN2 > 0) {
         cosScreen = cos_sel_applies(c, D, B, maxN1, maxN2, poolRows);
         ++(cosScreen ? c->cosScreenBatches : c->cosDenseBatches);
         if (cosScreen) {
             HIPCHK(c, WS.cosDense.ensure(sizeof(int32_t) * (size_t)B));
-            HIPCHK(c, launch_cos_sel(c, WS.stream, D, B, maxN1, maxN2, dP, in.feats, WS.cosPool.as<double>(), WS.cosDense.as<int32_t>(), false));
+            cosLive = allToAll && !D.keep_all;
+            if (cosLive)
+                HIPCHK(c, launch_cos_live(c, WS.stream, D, B, maxN1, maxN2, dP, in.feats, WS.cosPool.as<double>(), WS.cosDense.as<int32_t>(), dS, LP));
+            else
+                HIPCHK(c, launch_cos_sel(c, WS.stream, D, B, maxN1, maxN2, dP, in.feats, WS.cosPool.as<double>(), WS.cosDense.as<int32_t>(), false));
         } else
         HIPCHK(c, launch_cos(c, WS.stream, D, B, maxN1, maxN2, dP, in.feats, WS.cosPool.as<double>()));
     DBG(c, "k_cos");
@@ -633,13 +661,14 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
         hipLaunchKernelGGL(k_tables, dim3((unsigned)((maxN + RBt - 1) / RBt), 2, B), dim3(thr), tabLds, WS.stream, D, dP, in.feats, WS.tabPool.as<double>(), RBt, qtab);
     DBG(c, "k_tables");
     }
-    {   // single scores, then the ordered compaction of the live associations: chunks x problems
+    {   // single scores, then the ordered compaction of the live associations: chunks x problems (behind k_cos_live: its flagged problems only)
         const int maxChunks = std::max(1, (maxA + LIVE_CHUNK - 1) / LIVE_CHUNK);
+        const int32_t* only = cosLive ? WS.cosDense.as<int32_t>() : nullptr;
         HIPCHK(c, WS.chunkCnt.ensure(sizeof(int32_t) * (size_t)B * (size_t)maxChunks * 4));      // live associations per wave segment
         hipLaunchKernelGGL(k_live<0>, dim3((unsigned)maxChunks, (unsigned)B), dim3(256), 0, WS.stream, D, dP, dS, in.feats, in.assoc, WS.cosPool.as<double>(), WS.sTmp.as<double>(), PP.lp /* scratch until k_upper */,
-                           WS.chunkCnt.as<int32_t>(), maxChunks, LP.lp, LP.li, LP.lj, LP.ls, LP.ld, LP.lza, LP.lzb);
+                           WS.chunkCnt.as<int32_t>(), maxChunks, LP.lp, LP.li, LP.lj, LP.ls, LP.ld, LP.lza, LP.lzb, only);
         hipLaunchKernelGGL(k_live<1>, dim3((unsigned)maxChunks, (unsigned)B), dim3(256), 0, WS.stream, D, dP, dS, in.feats, in.assoc, WS.cosPool.as<double>(), WS.sTmp.as<double>(), PP.lp /* scratch until k_upper */,
-                           WS.chunkCnt.as<int32_t>(), maxChunks, LP.lp, LP.li, LP.lj, LP.ls, LP.ld, LP.lza, LP.lzb);
+                           WS.chunkCnt.as<int32_t>(), maxChunks, LP.lp, LP.li, LP.lj, LP.ls, LP.ld, LP.lza, LP.lzb, only);
     DBG(c, "k_live");
     }
     t0.stop();
