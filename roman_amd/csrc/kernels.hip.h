@@ -2814,9 +2814,14 @@ __global__ void __launch_bounds__(1024) k_upper(const ProbDesc* __restrict__ pro
 // The ENTRIES of a list arrive in the order the cursors were taken, not ascending: where an entry sits in its row is immaterial
 // (the fill labels it with its column's position, the solver's sums are exact integers) — roman_get_upper_csr sorts its rows.
 // Sweep: 16 lanes per row, four rows per wave step, lane = one 64-column word of the row's upper part (the diagonal word keeps
-// its bits behind the row's own); a row's words come in one or two coalesced 128-byte pieces.
+// its bits behind the row's own); a row's words come in one or two coalesced 128-byte pieces.  In the second sweep the bit loop
+// only queues the pairs (per-wave LDS queue); they are placed 256 at a time with every lane busy.  The lists are laid out in
+// position order, so the problem's first winCap list entries are one range of the pool: they are built in dynamic LDS and
+// written out in whole quads (512 contiguous bytes per wave store) instead of one 2-byte store each.
 // ---------------------------------------------------------------------------------------------
 constexpr int LISTS_NT = 1024;
+constexpr int LISTS_QRUN = 256;           // pairs a wave places at once (four per lane)
+constexpr int LISTS_QCAP = 512;           // queue entries per wave: a step's pairs go in at once when they fit (else 64 at a time)
 
 __global__ void __launch_bounds__(LISTS_NT) k_lists(int B, const ProbDesc* __restrict__ probs, ProbState* __restrict__ st, BatchTotals* __restrict__ tot,
                                                    const unsigned long long* __restrict__ maskPool,
@@ -2824,15 +2829,19 @@ __global__ void __launch_bounds__(LISTS_NT) k_lists(int B, const ProbDesc* __res
                                                    uint32_t* __restrict__ rowCnt, uint32_t* __restrict__ perm, uint32_t* __restrict__ rowPos,
                                                    LivePools src, LivePools dst, long long capList,
                                                    int eqMax /* place_keys(): rows of one degree at most; 0: always the bitonic sort */,
-                                                   int degGiven /* rowCnt holds every live row's full degree (k_count counted the pairs as they passed: whole problems): no degree sweep */)
+                                                   int degGiven /* rowCnt holds every live row's full degree (k_count counted the pairs as they passed: whole problems): no degree sweep */,
+                                                   int winCap /* list entries of the window in dynamic LDS (a multiple of 4; 0: every entry stored where it goes) */)
 {
+    extern __shared__ __attribute__((aligned(16))) uint16_t winS[];    // the problem's first winCap list entries, written out in whole quads
     __shared__ uint32_t degS[STREAM_MAXL + 64];                 // full degree of a live row; after the sort: the row's list cursor
-    __shared__ uint32_t keyS[4096];                             // sort keys
+    __shared__ uint32_t keyS[(LISTS_NT / 64) * LISTS_QCAP];    // sort keys (4096); in the pair sweep: per wave, pairs (k << 16 | q) waiting to be placed
     __shared__ unsigned long long tabS[STREAM_MAXL + 64];       // per live row: list offset << 16 | position (one LDS read serves both); before: place_keys()' two tables
-    __shared__ uint16_t tmpS[STREAM_MAXL + 64];                 // place_keys(): the rows in their degree's range
+    __shared__ uint16_t tmpS[STREAM_MAXL + 64];                 // place_keys(): the rows in their degree's range; after: the row at position p
     __shared__ uint32_t wsum[LISTS_NT / 64 + 4];
     __shared__ int okS;
     static_assert(STREAM_MAXL <= 4096, "sort capacity");
+    static_assert(LISTS_QRUN % 64 == 0 && LISTS_QCAP >= LISTS_QRUN + 64 && (LISTS_NT / 64) * LISTS_QCAP >= 4096, "k_lists queue");
+    uint32_t* const qS = keyS;                                  // (the keys are spent once the lists have their room: the tail reads tmpS)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     constexpr int NW = LISTS_NT / 64;
     const int g = lane >> 4, sl = lane & 15;                    // row of the wave step, word of the row's piece
@@ -2909,6 +2918,7 @@ __global__ void __launch_bounds__(LISTS_NT) k_lists(int B, const ProbDesc* __res
         }
         LMARK(2);
         // ---- list room per position (whole quads), the problem's base from the batch's bump pointer ----
+        uint32_t total = 0;                                     // list entries of the problem (whole quads)
         {
             const int PER = (L + LISTS_NT - 1) / LISTS_NT;      // consecutive positions per thread (<= 3)
             uint32_t sum = 0;
@@ -2919,7 +2929,7 @@ __global__ void __launch_bounds__(LISTS_NT) k_lists(int B, const ProbDesc* __res
             const uint32_t inc = wave_incl_scan(sum);
             if (lane == WAVE - 1) wsum[w] = inc;
             __syncthreads();
-            uint32_t wbase = 0, total = 0;
+            uint32_t wbase = 0;
             for (int t = 0; t < NW; ++t) { if (t < w) wbase += wsum[t]; total += wsum[t]; }
             if (tid == 0) {
                 const unsigned long long base = atomicAdd(&tot->listTop, (unsigned long long)total);
@@ -2933,7 +2943,7 @@ __global__ void __launch_bounds__(LISTS_NT) k_lists(int B, const ProbDesc* __res
                 const int q = tid * PER + t;
                 if (q < L) {
                     const uint32_t k = 4095u - (keyS[q] & 4095u);
-                    perm[lo + q] = k; rowPos[lo + k] = (uint32_t)q;
+                    perm[lo + q] = k; rowPos[lo + k] = (uint32_t)q; tmpS[q] = (uint16_t)k;
                     tabS[k] = ((unsigned long long)run << 16) | (unsigned long long)q; listOff[lo + q] = run; degS[k] = 0u;     // (degS: now the row's list cursor)
                     run += (min((keyS[q] >> 12) - 1u, (uint32_t)(L - 1 - q)) + 3u) & ~3u;
                 }
@@ -2944,29 +2954,90 @@ __global__ void __launch_bounds__(LISTS_NT) k_lists(int B, const ProbDesc* __res
         uint16_t* const lists = listPool + st[b].listOff;
         LMARK(3);
         // ---- every stored pair to its endpoint of smaller position ----
-        sweep([&](int k, unsigned long long m, int c) {
-            if (!m) return;
-            const unsigned long long tk = tabS[k];
-            const uint32_t pk = (uint32_t)tk & 0xffffu, ok = (uint32_t)(tk >> 16);
-            while (m) {
-                const uint32_t q = (uint32_t)((c << 6) + __builtin_ctzll(m));
-                m &= m - 1ull;
-                const unsigned long long tq = tabS[q];
-                const bool mine = pk < ((uint32_t)tq & 0xffffu);                       // the pair belongs to its endpoint of smaller position
-                const uint32_t slot = atomicAdd(&degS[mine ? (uint32_t)k : q], 1u);
-                lists[(mine ? ok : (uint32_t)(tq >> 16)) + slot] = (uint16_t)(mine ? q : (uint32_t)k);
+        // The sweep's per-lane bit loop only appends (k << 16 | q) to the wave's queue (offsets from a scan of the words'
+        // popcounts); the pairs are placed LISTS_QRUN at a time with every lane busy (a word has 1.8 set bits on average, a wave
+        // step runs to its lanes' maximum, ~6.5: 28 % of the lanes placed pairs inside the bit loop)
+        {
+        uint32_t* const qw = qS + w * LISTS_QCAP;
+        uint32_t qn = 0;                                        // queue fill (wave-uniform)
+        auto lds_order = [&]() {                                // LDS operations of one wave execute in order: this is for the compiler
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        };
+        // four pairs per lane: every LDS read of the four requested before the first is used, then the four cursor atomics
+        auto place = [&](uint32_t base, uint32_t n, auto full) {
+            constexpr int CH = LISTS_QRUN / WAVE;
+            uint32_t kk[CH], qq[CH], slot[CH]; unsigned long long tk[CH], tq[CH]; bool act[CH];
+#pragma unroll
+            for (int x = 0; x < CH; ++x) {
+                const uint32_t idx = (uint32_t)(x * WAVE + lane);
+                act[x] = decltype(full)::value || idx < n;
+                const uint32_t e = qw[base + (act[x] ? idx : 0u)];
+                kk[x] = e >> 16; qq[x] = e & 0xffffu;
+                tk[x] = tabS[kk[x]]; tq[x] = tabS[qq[x]];
             }
+#pragma unroll
+            for (int x = 0; x < CH; ++x) {
+                const bool mine = ((uint32_t)tk[x] & 0xffffu) < ((uint32_t)tq[x] & 0xffffu);   // the pair belongs to its endpoint of smaller position
+                if (act[x]) slot[x] = atomicAdd(&degS[mine ? kk[x] : qq[x]], 1u);
+            }
+#pragma unroll
+            for (int x = 0; x < CH; ++x) {
+                const bool mine = ((uint32_t)tk[x] & 0xffffu) < ((uint32_t)tq[x] & 0xffffu);
+                const uint32_t at = (uint32_t)((mine ? tk[x] : tq[x]) >> 16) + slot[x];
+                const uint16_t v = (uint16_t)(mine ? qq[x] : kk[x]);
+                if (act[x]) { if (at < (uint32_t)winCap) winS[at] = v; else lists[at] = v; }
+            }
+        };
+        auto drain = [&]() {
+            if (qn >= (uint32_t)LISTS_QRUN) {
+                lds_order();
+                while (qn >= (uint32_t)LISTS_QRUN) { qn -= LISTS_QRUN; place(qn, LISTS_QRUN, std::true_type{}); }
+                lds_order();
+            }
+        };
+        sweep([&](int k, unsigned long long m, int c) {
+            const uint32_t cnt = (uint32_t)__popcll(m);
+            const uint32_t incl = wave_incl_scan(cnt);
+            const uint32_t npairs = (uint32_t)__builtin_amdgcn_readlane((int)incl, WAVE - 1);
+            const uint32_t kq = ((uint32_t)k << 16) | (uint32_t)(c << 6);
+            if (qn + npairs <= (uint32_t)LISTS_QCAP) {
+                uint32_t at = qn + incl - cnt;
+                while (m) { qw[at++] = kq + (uint32_t)__builtin_ctzll(m); m &= m - 1ull; }
+                qn += npairs;
+            } else {
+                // a step with more pairs than the queue has room for (dense rows): 64 at a time, placed in between
+                while (true) {
+                    const unsigned long long bm = __ballot(m != 0ull);
+                    if (bm == 0ull) break;
+                    if (m) {
+                        qw[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u))] = kq + (uint32_t)__builtin_ctzll(m);
+                        m &= m - 1ull;
+                    }
+                    qn += (uint32_t)__popcll(bm);
+                    drain();
+                }
+            }
+            drain();
         });
+        lds_order();
+        if (qn) place(0u, qn, std::false_type{});
+        }
         __syncthreads();
         LMARK(4);
         // ---- padding, upper degrees and the position-ordered pools ----
         for (int p = tid; p < L; p += LISTS_NT) {
-            const uint32_t k = 4095u - (keyS[p] & 4095u);
+            const uint32_t k = tmpS[p];
             const uint32_t cnt = degS[k];
             rowCnt[lo + p] = cnt;
-            uint16_t* lst = lists + (uint32_t)(tabS[k] >> 16);
-            for (uint32_t e = cnt; e < ((cnt + 3u) & ~3u); ++e) lst[e] = (uint16_t)0xffffu;
+            const uint32_t o = (uint32_t)(tabS[k] >> 16);
+            for (uint32_t e = o + cnt; e < o + ((cnt + 3u) & ~3u); ++e) { if (e < (uint32_t)winCap) winS[e] = (uint16_t)0xffffu; else lists[e] = (uint16_t)0xffffu; }
             dst.lp[lo + p] = src.lp[lo + k]; dst.ld[lo + p] = src.ld[lo + k];
+        }
+        {   // the window: whole quads (8 bytes: a problem's lists start at a multiple of four entries), 512 contiguous bytes per wave store
+            const uint32_t nq = min(total, (uint32_t)winCap) >> 2;
+            __syncthreads();
+            for (uint32_t i = (uint32_t)tid; i < nq; i += LISTS_NT)
+                reinterpret_cast<uint2*>(lists)[i] = reinterpret_cast<const uint2*>(winS)[i];
         }
 #ifdef ROMAN_LISTS_TIMING
         LMARK(5);

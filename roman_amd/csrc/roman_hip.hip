@@ -349,6 +349,8 @@ void estimate_sizes(roman_ctx* c, const DevParams& D, const roman_params_t* para
     // tests: force the first attempt of a batch to overflow (exercises the skip / retry path)
     const char* tcap = getenv("ROMAN_TEST_CAPNNZ");            // (read per call: a test sets it for some of its contexts)
     if (tcap && !H.valid) S->capNnz = atoll(tcap);
+    const char* tlist = getenv("ROMAN_TEST_CAPLIST");          // ... or its list pool too small (k_lists' overflow: kind 2)
+    if (tlist && !H.valid) S->capList = atoll(tlist);
 }
 
 int may_fallback(const DevParams& D, const std::vector<ProbDesc>& hd);
@@ -808,18 +810,28 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
         const char* listsEnv = getenv("ROMAN_LISTS");           // "0": never, "1": always (A/B and tests: read per call)
         const int fusedLists = listsEnv ? (listsEnv[0] == '0' ? 0 : 1) : (B >= std::max(8, c->num_cu / 8) ? 1 : 0);
         if (fusedLists) {
-            // ROMAN_LISTS_LDS=n: n bytes of unused dynamic LDS on top of the kernel's ~60 KB (above 20 KB a compute unit holds ONE workgroup).
+            // The LDS the kernel leaves (~83 KB of 160: one workgroup per compute unit either way, by its registers) holds the window of
+            // list entries it builds in place and writes out in whole quads; entries beyond it are stored where they go, one at a time.
+            // ROMAN_LISTS_LDS=n: a window of n bytes instead (0: none — every entry stored on its own, A/B).
             // Probe of round 6: behind the prefiltered k_count with whole problems as work items k_lists takes 162-165 us in some
             // processes and 192-210 us in others (every launch of a process alike; identical instruction and byte counters,
             // SQ_WAIT_INST_ANY 122 M -> 190-220 M wave-cycles; behind the plain sweep or row-block work items always 160-169 us).  NOT the
-            // cause, each measured with a throw-away build (tools/r6_lists_probe.sh is the per-process probe): two workgroups on one compute unit (this pad), which workgroup takes which
+            // cause, each measured with a throw-away build (tools/r6_lists_probe.sh is the per-process probe): two workgroups on one compute unit (an LDS pad), which workgroup takes which
             // problem (rotations by 1, 4, 8, 128), dirty mask lines in L2 (non-temporal stores: -3 us).  Open.
+            static size_t listsStatic = 0;
+            if (listsStatic == 0) {
+                hipFuncAttributes fa;
+                HIPCHK(c, hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_lists)));
+                listsStatic = std::max<size_t>(fa.sharedSizeBytes, 1);
+            }
             const char* llEnv = getenv("ROMAN_LISTS_LDS");
-            const size_t listsPad = llEnv ? (size_t)std::max(0, atoi(llEnv)) : 0;
-            if (listsPad) HIPCHK(c, dyn_lds(c, reinterpret_cast<const void*>(k_lists), listsPad));
-            hipLaunchKernelGGL(k_lists, dim3((unsigned)std::max(1, std::min(B, 2 * c->num_cu))), dim3(LISTS_NT), listsPad, WS.stream, B, dP, dS, dT,
+            const size_t room = c->lds_max > listsStatic ? c->lds_max - listsStatic : 0;
+            const size_t winBytes = std::min(room, llEnv ? (size_t)std::max(0, atoi(llEnv)) : room) & ~(size_t)15;
+            if (winBytes) HIPCHK(c, dyn_lds(c, reinterpret_cast<const void*>(k_lists), winBytes));
+            hipLaunchKernelGGL(k_lists, dim3((unsigned)std::max(1, std::min(B, 2 * c->num_cu))), dim3(LISTS_NT), winBytes, WS.stream, B, dP, dS, dT,
                                WS.maskPool.as<unsigned long long>(), WS.listPool.as<uint16_t>(), WS.listOff.as<uint32_t>(),
-                               WS.rowCnt.as<uint32_t>(), WS.perm.as<uint32_t>(), WS.rowPos.as<uint32_t>(), LP, PP, (long long)SZ.capList, sort_eq_max(), degGiven);
+                               WS.rowCnt.as<uint32_t>(), WS.perm.as<uint32_t>(), WS.rowPos.as<uint32_t>(), LP, PP, (long long)SZ.capList, sort_eq_max(), degGiven,
+                               (int)(winBytes / sizeof(uint16_t)));
     DBG(c, "k_lists");
         }
         if (!fusedLists || D.allow_fallback) {
