@@ -986,7 +986,9 @@ __global__ void __launch_bounds__(256, CosDeal<T>::WAVES) k_cos_deal(DevParams D
 // k_cos_deal computes all n1 x n2 cosines in f64 on the matrix core and is POWER-bound (295 us at config 3); ~95 % of its
 // products are thrown away by the gate.  Here one workgroup of 16 waves takes a problem:
 //   pass 1  approximate cosines of all pairs: rows converted to bf16 on the way into LDS (f64 -> f32 -> bf16, each conversion ROUND TO
-//           NEAREST EVEN: the bound below needs a unit roundoff of 2^-8 for bf16, and a truncating conversion doubles it),
+//           NEAREST EVEN: a unit roundoff of 2^-8 for bf16.  tests/_bf16_screen.py models exactly this conversion and the device's
+//           screen is held to the model within the accumulation term below; a truncating conversion would keep the bound — it only
+//           shrinks: a uniform 2^-8 that the rows' own norms divide out, plus a symmetric 2^-8 — but not that agreement),
 //           v_mfma_f32_16x16x32_bf16 (1/32 of the f64 MFMA's matrix-pipe time), divided by the bf16 rows' OWN norms (the diagonals of the
 //           same bf16 products, accumulated in f32) — not by the exact f64 norms;
 //   select  pair (i, j) is a CANDIDATE unless approx < cosine_min - delta.  The screen is the exact cosine of the rounded rows a^, b^;

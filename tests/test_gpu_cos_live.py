@@ -5,7 +5,9 @@ What must hold, against the dense kernels (ROMAN_COS_SEL=0: k_cos_deal's whole m
   * every output of a batched call bit for bit: status, associations incl. order, poses, live counts, nnz, pass counts, scores;
   * also when some problems of the batch overflow the candidate list (they go to k_cos_deal + k_live, the rest through k_cos_live, in one
     call), for descriptor lengths that are not a multiple of the tile / chunk, and for pairs planted right at the gate
-    (exact cosines in [cosine_min - 2^-7, cosine_min + 2^-7]: the screen's bound around the gate)."""
+    (exact cosines in [cosine_min - 2^-7, cosine_min + 2^-7], the width of the screen's bound around the gate — but the planted descriptors
+    are random, so their rounding errors cancel and the screen is off by ~2^-8 / sqrt(d) only; pairs whose rounding is the worst case, and
+    the comparison with a plain exact cosine, are in tests/test_gpu_cos_screen_adversarial.py)."""
 import numpy as np
 import pytest
 

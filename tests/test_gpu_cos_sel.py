@@ -1,7 +1,9 @@
 """k_cos_sel — the cosine stage of a batch whose cosines only matter behind the gate cos > cosine_min
 ([REF roman/align/roman_registration.py:52-59]: scores of 0 below cosine_min): a bf16 matrix-core screen of all pairs, then the exact f64
 contraction (the oracle's stated order) for the pairs the screen cannot rule out.  What must hold:
-  * the screen's matrix lies within 0.0042 of the exact one (the bound the kernel's margin 2^-6 is set against);
+  * the screen's matrix lies within 0.0042 of the exact one.  That is what RANDOM descriptors stay within (their rounding errors cancel:
+    ~2^-8 / sqrt(d)), not the screen's bound: the bound is 2^-7 + 3 d 2^-24, the margin 2^-6 is twice it, and inputs built to use it are in
+    tests/test_gpu_cos_screen_adversarial.py (worst-case rounding, against a plain model and an exact cosine instead of the dense kernel);
   * every pair whose exact cosine is not below cosine_min - 2^-6 + 0.0042 — in particular every pair that passes the gate — holds the
     oracle's BITS; every other pair holds either those bits or a value that is below cosine_min like the exact one;
   * descriptors whose norm the screen cannot bound (huge, tiny, inf, NaN), zero descriptors, more candidates than the list holds, maps beyond
