@@ -358,6 +358,108 @@ ROMAN_API int roman_deal_problems(int32_t B, const int32_t* n1, const int32_t* n
                                   int32_t world, int32_t rank, int32_t* idx_out, int32_t* n_out);
 
 /* ------------------------------------------------------------------------------------------- */
+/* loop closures: the tail behind the pose (gravity filters, error metrics, acceptance, edge)  */
+/* ------------------------------------------------------------------------------------------- */
+
+/* What the reference does with a pose before it reaches RPGO ([REF roman/align/submap_align.py:160-200],
+   [REF roman/align/results.py:156-198]), per problem, on the device.  Flag bits of roman_lc_record_t.flags: */
+#define ROMAN_LC_ACCEPTED             1  /* association count >= lc_association_thresh and enabled: the problem is a loop closure,
+                                            edge_t / edge_q are set and its index is in the accepted list [REF roman/align/results.py:158-162] */
+#define ROMAN_LC_FAILED_INSUFFICIENT  2  /* ROMAN_ST_INSUFFICIENT / ROMAN_ST_EMPTY_MAP: T_align raised [REF roman/align/submap_align.py:179-184] */
+#define ROMAN_LC_FAILED_TILT          4  /* roll or pitch of the estimate not below tilt_thresh: GravityConstraintError of the pruning
+                                            plugin [REF roman/align/dist_reg_with_pruning.py:38-45] */
+#define ROMAN_LC_FAILED_UPSIDE_DOWN   8  /* |roll| or |pitch| above 90 degrees with force_rm_upside_down [REF roman/align/submap_align.py:167-170] */
+#define ROMAN_LC_SKIPPED             16  /* ROMAN_ST_WORKSPACE: the batch call skipped the problem; neither failed nor accepted — issue it again */
+#define ROMAN_LC_INTERNAL            32  /* ROMAN_ST_INTERNAL: the problem has no result; neither failed nor accepted */
+
+/* The switches of the tail: SubmapAlignParams.force_rm_upside_down / force_rm_lc_roll_pitch
+   [REF roman/params/submap_align_params.py:66-74], DistRegWithPruning.roll_pitch_thresh
+   [REF roman/align/dist_reg_with_pruning.py:17-27] and SubmapAlignInputOutput.lc_association_thresh
+   [REF roman/params/submap_align_params.py:153-198]. */
+typedef struct roman_lc_params {
+    int32_t dim;                     /* 2 or 3: layout of the poses (row-major (dim+1)^2 in the leading entries of 16 doubles) */
+    int32_t force_rm_upside_down;    /* 0/1 (dim 3 only)                                                   */
+    int32_t force_rm_lc_roll_pitch;  /* 0/1 (dim 3 only): keep the yaw of the estimate only                */
+    int32_t lc_association_thresh;   /* accepted: association count >= this                                */
+    double  tilt_thresh;             /* radians; < 0: no tilt check (dim 3 only)                           */
+    int32_t reserved[2];             /* must be 0                                                          */
+} roman_lc_params_t;
+
+/* One record per problem.  A failed, skipped or internal problem carries the sentinels of
+   [REF roman/align/submap_align.py:179-184]: NaN pose, theta 180.0, dist 1e6, no associations. */
+typedef struct roman_lc_record {
+    int32_t problem;       /* index of the problem in the call                                              */
+    int32_t n_assoc;       /* association count after the failure checks (0 when failed)                    */
+    int32_t flags;         /* ROMAN_LC_*                                                                    */
+    int32_t reserved;      /* 0                                                                             */
+    double  T_hat[16];     /* row-major 4x4: the estimate after the post-filters (dim 2: lifted to SE(3))   */
+    double  theta;         /* radians: rotation magnitude (dim 3) / signed planar angle (dim 2) of inv(T_hat) T_ref; NaN without T_ref */
+    double  dist;          /* norm of the translation of inv(T_hat) T_ref; NaN without T_ref               */
+    double  edge_t[3];     /* accepted: translation of FL[iL] T_hat FR[iR]; NaN otherwise                   */
+    double  edge_q[4];     /* accepted: its rotation as a quaternion, xyzw, scipy's as_quat() sign: the component picked by the first
+                              maximum of (R00, R11, R22, trace) is non-negative, nothing else is normalised; NaN otherwise */
+} roman_lc_record_t;
+
+/*
+ * roman_lc_tail_dev: the tail on its own, for a caller that holds batch outputs in HBM.  All bulk pointers DEVICE; a pure
+ * enqueue on the context's stream (complete once that stream is synchronised).  At pipeline depth >= 2 the batch calls write
+ * their outputs on internal streams: order them in front of the tail with roman_ctx_join().
+ *
+ * Replaces, per problem, pass 2 of the pair loop [REF roman/align/submap_align.py:160-200] (post-filters, error metrics,
+ * sentinels) and the edge of save_submap_align_results [REF roman/align/results.py:156-198] (acceptance by association count,
+ * composition into the odometry frames, translation + quaternion).
+ *
+ *   T, n_assoc, status   the outputs of a batch call: float64[B][16], int32[B], int32[B]
+ *   T_ref         float64[B][16] row-major 4x4 reference transforms (T_ij of [REF roman/align/submap_align.py:120-127]) or NULL
+ *   enable        int32[B] or NULL: a zero entry keeps the problem from being accepted (the single-robot time gate of
+ *                 [REF roman/align/results.py:160-162] is evaluated by the caller)
+ *   FL, iL        float64[SL][16] per-SUBMAP frames of the left side and int32[B] the submap of each problem, or both NULL
+ *                 (identity): what [REF roman/align/results.py:163-169] computes as inv(T_odomi_pi) T_odomi_ci
+ *   FR, iR        the same for the right side: inv(T_odomj_cj) T_odomj_pj
+ *   records       roman_lc_record_t[B]
+ *   accepted_idx  int32[B] capacity: the indices of the accepted problems in ASCENDING order (the order in which the
+ *                 reference writes its edges), found by a prefix sum, not by atomics
+ *   n_accepted    int32[1]
+ */
+ROMAN_API int roman_lc_tail_dev(roman_ctx_t* ctx, const roman_lc_params_t* lc_params, int32_t B,
+                                const double* T, const int32_t* n_assoc, const int32_t* status,
+                                const double* T_ref, const int32_t* enable,
+                                const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                                roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted);
+
+/* roman_align_batch_dev followed by the tail over its outputs, enqueued on the SAME stream as that call's solver (the internal
+   stream of its workspace at pipeline depth >= 2): the body of the pair loop [REF roman/align/submap_align.py:93-200] and the
+   edge of [REF roman/align/results.py:156-198] in one pure enqueue.  Complete after roman_ctx_sync() like the batch call.
+   A problem the batch call skipped (ROMAN_ST_WORKSPACE) has a ROMAN_LC_SKIPPED record: issue it again. */
+ROMAN_API int roman_align_lc_batch_dev(roman_ctx_t* ctx, const roman_params_t* params, int32_t B,
+                          const double* feats, const int64_t* off1, const int32_t* n1,
+                          const int64_t* off2, const int32_t* n2, int32_t F,
+                          const int32_t* assoc, const int64_t* assoc_off,
+                          const double* u0,
+                          int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
+                          double* T_out, int32_t* status_out, roman_stats_t* stats_out,
+                          const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                          const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                          roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted);
+
+/* The same with HOST pointers everywhere (n_left / n_right: submaps in FL / FR): roman_align_batch with its chunking and
+   re-issues first, THEN the tail over the final device block — a record is never built from a skipped attempt —, then one
+   read-back of outputs, records, index list and count through the pinned landing block.  What the caller of the reference's
+   submap_align() + save_submap_align_results() needs ([REF roman/align/submap_align.py:74-220],
+   [REF roman/align/results.py:122-198]). */
+ROMAN_API int roman_align_lc_batch(roman_ctx_t* ctx, const roman_params_t* params, int32_t B,
+                      const double* feats, int64_t n_objects,
+                      const int64_t* off1, const int32_t* n1,
+                      const int64_t* off2, const int32_t* n2, int32_t F,
+                      const int32_t* assoc, const int64_t* assoc_off,
+                      const double* u0,
+                      int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
+                      double* T_out, int32_t* status_out, roman_stats_t* stats_out,
+                      const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                      const double* FL, int32_t n_left, const int32_t* iL, const double* FR, int32_t n_right, const int32_t* iR,
+                      roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted);
+
+/* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */
 /* ------------------------------------------------------------------------------------------- */
 

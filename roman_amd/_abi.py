@@ -44,6 +44,15 @@ ROMAN_STAGE_SOLVE = 3
 ROMAN_STAGE_COUNT = 4
 STAGE_NAMES = ("single", "count", "fill", "solve")
 
+# flag bits of roman_lc_record_t.flags
+ROMAN_LC_ACCEPTED = 1
+ROMAN_LC_FAILED_INSUFFICIENT = 2
+ROMAN_LC_FAILED_TILT = 4
+ROMAN_LC_FAILED_UPSIDE_DOWN = 8
+ROMAN_LC_SKIPPED = 16
+ROMAN_LC_INTERNAL = 32
+ROMAN_LC_FAILED = ROMAN_LC_FAILED_INSUFFICIENT | ROMAN_LC_FAILED_TILT | ROMAN_LC_FAILED_UPSIDE_DOWN
+
 
 class RomanParams(C.Structure):
     """roman_params_t"""
@@ -122,7 +131,36 @@ class RomanStats(C.Structure):
     ]
 
 
+class RomanLcParams(C.Structure):
+    """roman_lc_params_t"""
+    _fields_ = [
+        ("dim", C.c_int32),
+        ("force_rm_upside_down", C.c_int32),
+        ("force_rm_lc_roll_pitch", C.c_int32),
+        ("lc_association_thresh", C.c_int32),
+        ("tilt_thresh", C.c_double),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+class RomanLcRecord(C.Structure):
+    """roman_lc_record_t"""
+    _fields_ = [
+        ("problem", C.c_int32),
+        ("n_assoc", C.c_int32),
+        ("flags", C.c_int32),
+        ("reserved", C.c_int32),
+        ("T_hat", C.c_double * 16),
+        ("theta", C.c_double),
+        ("dist", C.c_double),
+        ("edge_t", C.c_double * 3),
+        ("edge_q", C.c_double * 4),
+    ]
+
+
 STATS_NBYTES = C.sizeof(RomanStats)
+LC_PARAMS_NBYTES = C.sizeof(RomanLcParams)
+LC_RECORD_NBYTES = C.sizeof(RomanLcRecord)
 PARAMS_NBYTES = C.sizeof(RomanParams)
 
 _LIB = None
@@ -169,6 +207,13 @@ def load_library():
                                         vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "roman_align_batch_resident": (C.c_int, [ctxp, P(RomanParams), i32, vp, vp, vp, vp, vp, i32,
                                                  vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "roman_lc_tail_dev": (C.c_int, [ctxp, P(RomanLcParams), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "roman_align_lc_batch_dev": (C.c_int, [ctxp, P(RomanParams), i32, vp, vp, vp, vp, vp, i32,
+                                               vp, vp, vp, i32, vp, vp, vp, vp, vp,
+                                               P(RomanLcParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "roman_align_lc_batch": (C.c_int, [ctxp, P(RomanParams), i32, vp, i64, vp, vp, vp, vp, i32,
+                                           vp, vp, vp, i32, vp, vp, vp, vp, vp,
+                                           P(RomanLcParams), vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
         "roman_ctx_has_history": (C.c_int, [ctxp, P(RomanParams), i32, P(i32)]),
         "roman_ctx_cosine_screen_stats": (C.c_int, [ctxp, P(C.c_int64), P(C.c_int64), P(C.c_double)]),
         "roman_create_all_to_all": (C.c_int, [i32, i32, vp]),
@@ -203,7 +248,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

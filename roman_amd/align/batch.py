@@ -108,6 +108,14 @@ def run_batch(registration, batch: AlignmentBatch, u0=None, ctx=None):
                            assoc=batch.assoc, assoc_off=batch.assoc_off, u0=u0, kmax=batch.kmax())
 
 
+def run_lc_batch(registration, batch: AlignmentBatch, lc, u0=None, ctx=None):
+    """One roman_align_lc_batch call for `batch` with the loop-closure tail `lc` (runtime.LcInputs) behind it
+    -> runtime.LoopClosureResult."""
+    ctx = ctx or registration._context()
+    return ctx.align_lc_batch(registration._abi_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2, lc,
+                              assoc=batch.assoc, assoc_off=batch.assoc_off, u0=u0, kmax=batch.kmax())
+
+
 def align_pairs(registration, pairs, u0=None):
     """register() + T_align() for every (map1, map2) in `pairs`, one device call."""
     return run_batch(registration, batch_from_pairs(registration, pairs), u0=u0)

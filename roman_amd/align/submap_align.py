@@ -17,6 +17,7 @@ over submap objects exposing the attributes of [REF roman/map/map.py:94-141] (`s
 `pose_flu_gt`, `descriptor`, `time`); `Submap` below is a minimal stand-in with the same semantics, including
 the reference's quirk that `pose_gravity_aligned` flattens `pose_flu` IN PLACE [REF roman/utils.py:128-130].
 """
+import copy
 import json
 import pickle
 import time
@@ -27,8 +28,10 @@ import numpy as np
 from scipy.spatial.transform import Rotation as Rot
 
 from .. import _abi
-from .batch import AlignmentBatch, pack_submaps, run_batch
+from ..runtime import LcInputs
+from .batch import AlignmentBatch, pack_submaps, run_batch, run_lc_batch
 from .dist_reg_with_pruning import _zyx_euler
+from .object_registration import ObjectRegistration
 
 
 # ---------------------------------------------------------------------------------------------
@@ -149,6 +152,9 @@ class SubmapAlignResults:
     submap_align_params: object
     submap_io: object
     total_time: float = -np.inf
+    # submap_align_grid only: the loop-closure edges as the device computed them — {'pairs': (K, 2) int (i, j) in loop order,
+    # 't': (K, 3), 'q': (K, 4) xyzw}.  loop_closure_edges() and the writers then do no per-pair matrix work.
+    lc_edges: Optional[dict] = None
 
 
 def submap_align(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, registration=None,
@@ -294,6 +300,248 @@ def submap_align(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, regi
 
 
 # ---------------------------------------------------------------------------------------------
+# the grid form: pass 1 vectorised over the S0 x S1 grid, pass 2 and the edges behind the solver on the device
+# ---------------------------------------------------------------------------------------------
+def _read_times(sm, prop, attr, times):
+    """Read `sm.<prop>` (`pose_gravity_aligned[_gt]`) `times` times, as the pair loop does — the stand-in Submap (like the
+    reference's) rewrites `sm.<attr>` in place on every read.  Stops early once a read leaves the pose bitwise unchanged (a
+    deterministic function applied to its own fixed point changes nothing), which a yaw-only pose does after one or two reads
+    and a class that returns a copy does at once.  -> the last value read."""
+    val = None
+    for _ in range(int(times)):
+        before = np.asarray(getattr(sm, attr)).tobytes()
+        val = getattr(sm, prop)
+        if np.asarray(getattr(sm, attr)).tobytes() == before:
+            break
+    return val
+
+
+def _host_similarity(descs0, descs1):
+    """Submap.similarity for every pair at once (the CPU double's descriptor gate): vector descriptors or stacked frames."""
+    flat = descs0 + descs1
+    if all(d.ndim == 1 for d in flat):
+        A, B = np.stack(descs0), np.stack(descs1)
+        norm_prod = np.linalg.norm(A, axis=1)[:, None] * np.linalg.norm(B, axis=1)[None, :]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            sim = (A @ B.T) / norm_prod
+        sim[np.isclose(norm_prod, 0.0, atol=1e-9, rtol=0.0)] = 0.0
+        return sim
+    if all(d.ndim == 2 and d.shape[0] > 0 and d.shape[1] == flat[0].shape[1] for d in flat):
+        o0 = np.concatenate([[0], np.cumsum([d.shape[0] for d in descs0])]).astype(np.int64)
+        o1 = np.concatenate([[0], np.cumsum([d.shape[0] for d in descs1])]).astype(np.int64)
+        A, B = np.concatenate(descs0, axis=0), np.concatenate(descs1, axis=0)
+        norm_prod = np.linalg.norm(A, axis=1)[:, None] * np.linalg.norm(B, axis=1)[None, :]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            frames = (A @ B.T) / norm_prod
+        frames[np.isclose(norm_prod, 0.0, atol=1e-9, rtol=0.0)] = 0.0
+        return np.maximum.reduceat(np.maximum.reduceat(frames, o0[:-1], axis=0), o1[:-1], axis=1)
+    return None
+
+
+def _edge_frames(sm):
+    """What loop_closure_edges() composes around the estimate for this submap — (inv(T_odom_p) @ T_odom_c,
+    inv(T_odom_c) @ T_odom_p) — evaluated through the submap's OWN properties on a copy, so that a class whose
+    `pose_gravity_aligned` flattens `pose_flu` in place (both then name the same matrix) gives what it gives there."""
+    c = copy.copy(sm)
+    c.pose_flu = np.array(sm.pose_flu, dtype=np.float64)
+    T_c = c.pose_gravity_aligned
+    T_p = c.pose_flu
+    return np.linalg.inv(T_p) @ T_c, np.linalg.inv(T_c) @ T_p
+
+
+def _quat_to_matrix(q):
+    """(K, 4) xyzw unit quaternions -> (K, 3, 3)."""
+    x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R = np.empty((q.shape[0], 3, 3))
+    R[:, 0, 0] = 1 - 2 * (y * y + z * z); R[:, 0, 1] = 2 * (x * y - z * w); R[:, 0, 2] = 2 * (x * z + y * w)
+    R[:, 1, 0] = 2 * (x * y + z * w); R[:, 1, 1] = 1 - 2 * (x * x + z * z); R[:, 1, 2] = 2 * (y * z - x * w)
+    R[:, 2, 0] = 2 * (x * z - y * w); R[:, 2, 1] = 2 * (y * z + x * w); R[:, 2, 2] = 1 - 2 * (x * x + y * y)
+    return R
+
+
+def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, registration=None,
+                      compute: Optional[Callable] = None) -> SubmapAlignResults:
+    """submap_align() for callers that hand over the whole S0 x S1 grid: the same results (and the same state of the caller's
+    submaps), with pass 1 ([REF roman/align/submap_align.py:93-149]) vectorised in NumPy over the grid and pass 2
+    ([REF :160-200]) plus the loop-closure edges ([REF roman/align/results.py:156-171]) computed behind the solver on the device
+    (roman_align_lc_batch).  Python loops run over SUBMAPS (packing, per-submap frames), never over pairs — except where a
+    per-pair list is the input itself: the shared-segment removal of `single_robot_lc` and a registration plugin's host
+    prefilter.
+
+    `compute(registration, AlignmentBatch, runtime.LcInputs) -> runtime.LoopClosureResult` defaults to the HIP path
+    (`run_lc_batch`); tests inject a CPU double."""
+    sm_io = sm_io or SubmapAlignIO()
+    registration = registration or sm_params.get_object_registration()
+    on_device = compute is None
+    compute = compute or run_lc_batch
+    S = [list(submaps[0]), list(submaps[1])]
+    n0, n1 = len(S[0]), len(S[1])
+    nan = lambda *s: np.zeros(s) * np.nan
+    clipper_angle_mat, clipper_dist_mat, clipper_num_associations = nan(n0, n1), nan(n0, n1), nan(n0, n1)
+    similarity_mat, robots_nearby_mat, submap_yaw_diff_mat = nan(n0, n1), nan(n0, n1), nan(n0, n1)
+    T_ij_mat, T_ij_hat_mat = nan(n0, n1, 4, 4), nan(n0, n1, 4, 4)
+    associated_objs_mat = [[[] for _ in range(n1)] for _ in range(n0)]
+    total_time_t0 = time.time()
+    make = lambda lc_edges=None, timing_list=(): SubmapAlignResults(
+        robots_nearby_mat=robots_nearby_mat, clipper_angle_mat=clipper_angle_mat, clipper_dist_mat=clipper_dist_mat,
+        clipper_num_associations=clipper_num_associations,
+        similarity_mat=similarity_mat if sm_params.submap_descriptor is not None else None,
+        submap_yaw_diff_mat=submap_yaw_diff_mat, T_ij_mat=T_ij_mat, T_ij_hat_mat=T_ij_hat_mat,
+        associated_objs_mat=associated_objs_mat, timing_list=list(timing_list), submap_align_params=sm_params,
+        submap_io=sm_io, total_time=time.time() - total_time_t0, lc_edges=lc_edges)
+    device_edges = sm_io.lc_association_thresh > 0       # (a threshold <= 0 would accept pairs that never reach the device)
+    empty_edges = dict(pairs=np.zeros((0, 2), np.int64), t=np.zeros((0, 3)), q=np.zeros((0, 4))) if device_edges else None
+    if n0 == 0 or n1 == 0:
+        return make(empty_edges)
+
+    # ---- per submap: sizes, positions, ground truth ---------------------------------------------------------
+    lens = [np.array([len(sm) for sm in S[r]]) for r in range(2)]
+    has_gt = [np.array([sm.has_gt for sm in S[r]], dtype=bool) for r in range(2)]
+    pos = [np.stack([np.asarray(sm.position, dtype=np.float64) for sm in S[r]]) for r in range(2)]
+    pos_gt = [np.stack([np.asarray(sm.position_gt, dtype=np.float64) if sm.has_gt else np.full(3, np.nan) for sm in S[r]]) for r in range(2)]
+    both_gt = has_gt[0][:, None] & has_gt[1][None, :]
+    with np.errstate(invalid="ignore"):
+        dist = np.where(both_gt, np.linalg.norm(pos_gt[0][:, None, :] - pos_gt[1][None, :, :], axis=2),
+                        np.linalg.norm(pos[0][:, None, :] - pos[1][None, :, :], axis=2))
+
+    # ---- the in-place flattening of the pair loop, per submap: `pose_gravity_aligned[_gt]` rewrites the pose it reads, once
+    # per pair the submap takes part in (and once more per AABB test); the count per pose is a function of the grid's shape ----
+    aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
+    other = (n1, n0)
+    boxes = [[None] * n0, [None] * n1]
+    T_w = [[], []]
+    for r in range(2):
+        n_other_nonempty = int(np.count_nonzero(lens[1 - r]))
+        for k, sm in enumerate(S[r]):
+            n_aabb = n_other_nonempty if (aabb_mode and lens[r][k]) else 0
+            uses = {"gt": 0, "flu": 0}
+            uses["gt" if sm.has_gt else "flu"] += n_aabb
+            uses["gt" if sm_io.gt_available[r] else "flu"] += other[r]
+            if n_aabb:                                   # the global points of the first AABB test (one read of the pose)
+                pts = sm.segments_as_global_points
+                boxes[r][k] = (np.min(pts, axis=0)[:3], np.max(pts, axis=0)[:3])
+                uses["gt" if sm.has_gt else "flu"] -= 1
+            got = {}
+            if uses["gt"]:
+                got["gt"] = _read_times(sm, "pose_gravity_aligned_gt", "pose_flu_gt", uses["gt"])
+            if uses["flu"]:
+                got["flu"] = _read_times(sm, "pose_gravity_aligned", "pose_flu", uses["flu"])
+            T_w[r].append(np.array(got["gt" if sm_io.gt_available[r] else "flu"], dtype=np.float64))
+    T_w = [np.stack(T_w[r]) for r in range(2)]
+
+    # ---- pass 1 over the grid: the radius / AABB gate, reference transforms, yaw differences, descriptor gate ----
+    if not aabb_mode:
+        nearby = dist < sm_params.submap_radius * 2
+    else:
+        nearby = np.zeros((n0, n1), dtype=bool)
+        u0 = [k for k in range(n0) if boxes[0][k] is not None]; u1 = [k for k in range(n1) if boxes[1][k] is not None]
+        if u0 and u1:
+            lo0 = np.stack([boxes[0][k][0] for k in u0]); hi0 = np.stack([boxes[0][k][1] for k in u0])
+            lo1 = np.stack([boxes[1][k][0] for k in u1]); hi1 = np.stack([boxes[1][k][1] for k in u1])
+            hit = np.all(lo0[:, None, :] <= hi1[None, :, :], axis=2) & np.all(hi0[:, None, :] >= lo1[None, :, :], axis=2)
+            nearby[np.ix_(u0, u1)] = hit
+    robots_nearby_mat[nearby] = dist[nearby]
+    T_ij_mat[:] = np.matmul(np.linalg.inv(T_w[0])[:, None, :, :], T_w[1][None, :, :, :])
+    yaw = np.arctan2(T_ij_mat[:, :, 1, 0], T_ij_mat[:, :, 0, 0])      # the fixed-axis xyz yaw of a rotation about z
+    submap_yaw_diff_mat[nearby] = np.abs(np.rad2deg(yaw[nearby]))
+    if sm_params.submap_descriptor is None:
+        sim = np.full((n0, n1), np.inf)
+    else:
+        descs = [[np.asarray(sm.descriptor) for sm in S[r]] for r in range(2)]
+        flat = descs[0] + descs[1]
+        sim = None
+        if on_device:                                    # row f2: every cosine of the gate in ONE device call
+            if all(d.ndim == 1 for d in flat):
+                sim = registration._context().cosine_matrix(np.stack(descs[0]), np.stack(descs[1]))
+            elif all(d.ndim == 2 and d.shape[0] > 0 and d.shape[1] == flat[0].shape[1] for d in flat):
+                sim = stacked_similarity(registration._context(), descs[0], descs[1])
+        else:
+            sim = _host_similarity(descs[0], descs[1])
+        if sim is None:                                  # mixed descriptor kinds: the per-pair definition
+            sim = np.array([[Submap.similarity(si, sj) for sj in S[1]] for si in S[0]], dtype=np.float64)
+    skip = dist > sm_io.skip_distance
+    clipper_num_associations[skip] = 0
+    similarity_mat[~skip] = sim[~skip]
+    with np.errstate(invalid="ignore"):
+        gated = ~skip & (sim < sm_params.submap_descriptor_thresh)
+    todo = ~skip & ~gated
+    # pairs the descriptor gate stopped: the sentinels of [REF :179-184]
+    clipper_num_associations[gated] = 0
+    clipper_angle_mat[gated & nearby] = np.abs(np.rad2deg(180.0)); clipper_dist_mat[gated & nearby] = 1e6
+    ti, tj = np.nonzero(todo)                            # row-major: the order of the pair loop
+    B = int(ti.shape[0])
+    if B == 0:
+        return make(empty_edges)
+
+    # ---- the hot path: every submap (variant) packed once, ONE batched call with the tail behind it ---------
+    if not sm_params.single_robot_lc:
+        ui, uj = np.unique(ti), np.unique(tj)
+        pool = [list(S[0][i].segments) for i in ui] + [list(S[1][j].segments) for j in uj]
+        slot_i = np.zeros(n0, dtype=np.int64); slot_i[ui] = np.arange(len(ui))
+        slot_j = np.zeros(n1, dtype=np.int64); slot_j[uj] = len(ui) + np.arange(len(uj))
+        ii, jj = slot_i[ti], slot_j[tj]
+        pair_segs = None
+    else:                                                # self loop closures: drop the segments both submaps hold (per pair by nature)
+        pool, pair_segs = [], []
+        for i, j in zip(ti.tolist(), tj.tolist()):
+            segs_i, segs_j = list(S[0][i].segments), list(S[1][j].segments)
+            common = {seg.id for seg in segs_i} & {seg.id for seg in segs_j}
+            segs_i = [s for s in segs_i if s.id not in common]; segs_j = [s for s in segs_j if s.id not in common]
+            pool.append(segs_i); pool.append(segs_j); pair_segs.append((segs_i, segs_j))
+        ii, jj = 2 * np.arange(B), 2 * np.arange(B) + 1
+    feats, offs = pack_submaps(registration, pool)
+    plen = np.diff(offs).astype(np.int32)
+    batch = AlignmentBatch(feats, offs[ii].astype(np.int64), plen[ii], offs[jj].astype(np.int64), plen[jj],
+                           pair_index=np.stack([ti, tj], axis=1))
+    scorer = getattr(type(registration), "_associations_to_score", None)
+    if scorer is not None and scorer is not ObjectRegistration._associations_to_score:
+        # a pruning plugin scores explicit association lists: its host prefilter reads both maps of a pair
+        segs_of = (lambda b: (pool[ii[b]], pool[jj[b]])) if pair_segs is None else (lambda b: pair_segs[b])
+        lists = [registration._association_list(*segs_of(b)) if (plen[ii[b]] and plen[jj[b]]) else None for b in range(B)]
+        if any(l is not None for l in lists):
+            from ..clipperpy.utils import create_all_to_all
+            lists = [l if l is not None else create_all_to_all(int(plen[ii[b]]), int(plen[jj[b]])) for b, l in enumerate(lists)]
+            batch.assoc_off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int64)
+            batch.assoc = np.concatenate(lists, axis=0).astype(np.int32)
+    frames = [{int(k): _edge_frames(S[r][int(k)]) for k in np.unique(t)} for r, t in ((0, ti), (1, tj))]
+    FL = np.tile(np.eye(4), (n0, 1, 1)); FR = np.tile(np.eye(4), (n1, 1, 1))
+    for k, f in frames[0].items():
+        FL[k] = f[0]
+    for k, f in frames[1].items():
+        FR[k] = f[1]
+    times = [np.array([float(sm.time) for sm in S[r]]) for r in range(2)]
+    enable = np.ones(B, dtype=np.int32)
+    if sm_params.single_robot_lc:                        # the time gate of [REF roman/align/results.py:160-162]
+        enable[np.abs(times[0][ti] - times[1][tj]) < sm_params.single_robot_lc_time_thresh] = 0
+    lc = LcInputs(dim=sm_params.dim, force_rm_upside_down=sm_params.force_rm_upside_down,
+                  force_rm_lc_roll_pitch=sm_params.force_rm_lc_roll_pitch,
+                  tilt_thresh=registration.roll_pitch_thresh if getattr(registration, "use_gravity", False) else None,
+                  lc_association_thresh=int(np.ceil(sm_io.lc_association_thresh)) if device_edges else 1,
+                  T_ref=T_ij_mat[ti, tj], enable=enable, FL=FL, iL=ti, FR=FR, iR=tj)
+    t0 = time.time()
+    res = compute(registration, batch, lc)
+    timing_list = [(time.time() - t0) / B] * B
+
+    # ---- pass 2: the records into the result matrices -------------------------------------------------------
+    rec = res.records
+    if np.any(rec["flags"] & (_abi.ROMAN_LC_SKIPPED | _abi.ROMAN_LC_INTERNAL)):
+        raise _abi.RomanHipError("the batched call left problems without a result (ROMAN_LC_SKIPPED / ROMAN_LC_INTERNAL records)")
+    near = nearby[ti, tj]
+    clipper_angle_mat[ti[near], tj[near]] = np.abs(np.rad2deg(rec["theta"][near]))
+    clipper_dist_mat[ti[near], tj[near]] = rec["dist"][near]
+    clipper_num_associations[ti, tj] = rec["n_assoc"]
+    T_ij_hat_mat[ti, tj] = rec["T_hat"]
+    failed = (rec["flags"] & _abi.ROMAN_LC_FAILED) != 0
+    for b in np.nonzero(~failed)[0].tolist():            # (placing the association arrays: no arithmetic)
+        associated_objs_mat[ti[b]][tj[b]] = res.assoc[b]
+    lc_edges = None
+    if device_edges:
+        acc = np.asarray(res.accepted, dtype=np.int64)
+        lc_edges = dict(pairs=np.stack([ti[acc], tj[acc]], axis=1).astype(np.int64), t=np.array(rec["edge_t"][acc]), q=np.array(rec["edge_q"][acc]))
+    return make(lc_edges, timing_list)
+
+
+# ---------------------------------------------------------------------------------------------
 # writers (row f3): the wire formats g2o_file_fusion / Kimera-RPGO consume
 # ---------------------------------------------------------------------------------------------
 def nearest_index(times, t):
@@ -306,6 +554,8 @@ def loop_closure_edges(results: SubmapAlignResults, submaps):
     """The (i, j, T_pi_pj) triples the reference writes ([REF roman/align/results.py:156-171]): pairs with at
     least `lc_association_thresh` associations (and far enough apart in time for single-robot runs), with the
     estimated submap-centre transform composed into pose-frame i -> pose-frame j."""
+    if getattr(results, "lc_edges", None) is not None:
+        return [(i, j, T) for (i, j, T, _, _) in _device_edges(results, submaps)]
     out = []
     p, io = results.submap_align_params, results.submap_io
     for i in range(len(submaps[0])):
@@ -324,6 +574,36 @@ def loop_closure_edges(results: SubmapAlignResults, submaps):
     return out
 
 
+def _device_edges(results, submaps):
+    """(i, j, T_pi_pj, t, q) per accepted pair from the edges the device computed (submap_align_grid): no per-pair matrix
+    work.  Leaves the submaps as the per-pair loop does: it reads `pose_gravity_aligned` of both submaps of every accepted
+    pair, which may flatten `pose_flu` in place."""
+    e = results.lc_edges
+    pairs, t, q = np.asarray(e["pairs"]).reshape(-1, 2), np.asarray(e["t"]).reshape(-1, 3), np.asarray(e["q"]).reshape(-1, 4)
+    for r in range(2):
+        ks, counts = np.unique(pairs[:, r], return_counts=True)
+        for k, n in zip(ks.tolist(), counts.tolist()):
+            sm = submaps[r][k]
+            before = np.array(sm.pose_flu, dtype=np.float64).tobytes()
+            for _ in range(n):                           # (stops at the fixed point a yaw-only pose is)
+                sm.pose_gravity_aligned
+                now = np.array(sm.pose_flu, dtype=np.float64).tobytes()
+                if now == before:
+                    break
+                before = now
+    T = np.tile(np.eye(4), (pairs.shape[0], 1, 1))
+    T[:, :3, :3] = _quat_to_matrix(q); T[:, :3, 3] = t
+    return [(int(pairs[k, 0]), int(pairs[k, 1]), T[k], t[k].copy(), q[k].copy()) for k in range(pairs.shape[0])]
+
+
+def _edges_xyz_quat(results, submaps):
+    """(i, j, translation, quaternion xyzw) of every loop closure: from the device's edges when the result carries them,
+    otherwise loop_closure_edges() + transform_to_xyz_quat()."""
+    if getattr(results, "lc_edges", None) is not None:
+        return [(i, j, t, q) for (i, j, _, t, q) in _device_edges(results, submaps)]
+    return [(i, j) + transform_to_xyz_quat(T) for (i, j, T) in loop_closure_edges(results, submaps)]
+
+
 def write_g2o(path, results: SubmapAlignResults, submaps, trajectory_times):
     """`.g2o` loop closures, same text as [REF roman/align/results.py:156-194]: per edge a `# LC: <n>` comment
     (read by g2o_file_fusion, [REF roman/offline_rpgo/g2o_file_fusion.py:54-68]) and an `EDGE_SE3:QUAT` line with
@@ -332,8 +612,7 @@ def write_g2o(path, results: SubmapAlignResults, submaps, trajectory_times):
     I_t, I_r = 1 / (io.g2o_t_std ** 2), 1 / (io.g2o_r_std ** 2)
     I = np.diag([I_t, I_t, I_t, I_r, I_r, I_r])
     with open(path, 'w') as f:
-        for (i, j, T) in loop_closure_edges(results, submaps):
-            t, q = transform_to_xyz_quat(T)
+        for (i, j, t, q) in _edges_xyz_quat(results, submaps):
             idx_a = nearest_index(trajectory_times[0], submaps[0][i].time)
             idx_b = nearest_index(trajectory_times[1], submaps[1][j].time)
             f.write(f"# LC: {int(results.clipper_num_associations[i, j])}\n")
@@ -352,8 +631,7 @@ def write_g2o(path, results: SubmapAlignResults, submaps, trajectory_times):
 def write_lc_json(path, results: SubmapAlignResults, submaps):
     """Loop-closure json, same records as [REF roman/align/results.py:172-179,196-198]."""
     out = []
-    for (i, j, T) in loop_closure_edges(results, submaps):
-        t, q = transform_to_xyz_quat(T)
+    for (i, j, t, q) in _edges_xyz_quat(results, submaps):
         out.append({
             'seconds': [int(submaps[0][i].time), int(submaps[1][j].time)],
             'nanoseconds': [int((submaps[0][i].time % 1) * 1e9), int((submaps[1][j].time % 1) * 1e9)],

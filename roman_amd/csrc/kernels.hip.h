@@ -6719,6 +6719,168 @@ __global__ void __launch_bounds__(64) k_pose(int dim, const double* __restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// loop-closure tail: what the caller of the pair loop does with a pose before it reaches the pose graph
+// (post-filters, error metrics, acceptance, edge, compaction).  A few hundred f64 operations per problem: launch- and
+// latency-bound, one thread per problem; the accepted list comes from k_rowbase's one-workgroup scan.
+// ---------------------------------------------------------------------------------------------
+struct LcIn {
+    const double* T; const int32_t* n_assoc; const int32_t* status;      // batch outputs
+    const double* T_ref; const int32_t* enable;                          // optional
+    const double* FL; const int32_t* iL; const double* FR; const int32_t* iR;   // optional frame pools
+};
+
+// C = A B for row-major 4x4 matrices, left to right as NumPy's `@` chain does
+__device__ __forceinline__ void lc_mul4(const double* A, const double* Bm, double* Cm)
+{
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s += A[r * 4 + k] * Bm[k * 4 + c];
+            Cm[r * 4 + c] = s;
+        }
+}
+
+// inverse of an affine 4x4 (bottom row 0 0 0 1) through the cofactors of its 3x3 block: np.linalg.inv's result for ANY
+// invertible block, not only a rotation (the estimate is orthogonal only to rounding)
+__device__ __forceinline__ void lc_inv_affine(const double* A, double* I)
+{
+    const double a = A[0], b = A[1], c = A[2], d = A[4], e = A[5], f = A[6], g = A[8], h = A[9], i = A[10];
+    const double c00 = e * i - f * h, c01 = c * h - b * i, c02 = b * f - c * e;
+    const double c10 = f * g - d * i, c11 = a * i - c * g, c12 = c * d - a * f;
+    const double c20 = d * h - e * g, c21 = b * g - a * h, c22 = a * e - b * d;
+    const double det = a * c00 + b * c10 + c * c20;
+    const double r = 1.0 / det;
+    I[0] = c00 * r; I[1] = c01 * r; I[2] = c02 * r;
+    I[4] = c10 * r; I[5] = c11 * r; I[6] = c12 * r;
+    I[8] = c20 * r; I[9] = c21 * r; I[10] = c22 * r;
+    const double tx = A[3], ty = A[7], tz = A[11];
+    I[3] = -(I[0] * tx + I[1] * ty + I[2] * tz);
+    I[7] = -(I[4] * tx + I[5] * ty + I[6] * tz);
+    I[11] = -(I[8] * tx + I[9] * ty + I[10] * tz);
+    I[12] = 0.0; I[13] = 0.0; I[14] = 0.0; I[15] = 1.0;
+}
+
+// k_lc_tail: one record per problem.  GATES compare what the host compares — the angles themselves (roll, pitch from atan2 /
+// asin) against the thresholds, the association count against lc_association_thresh — so a decision depends on a library
+// function's last bit exactly where the host's does.
+// Quaternion: the branch rule of scipy's Rotation.from_matrix — the FIRST maximum of (R00, R11, R22, trace) picks the
+// component that is computed as a sum (hence non-negative), the other three follow from it, the vector is normalised and
+// NOT canonicalised (w may be negative): as_quat()'s component order xyzw and sign.
+__global__ void __launch_bounds__(256) k_lc_tail(roman_lc_params_t P, int B, LcIn in, roman_lc_record_t* __restrict__ rec)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int st = in.status[b];
+    int flags = 0;
+    if (st & ROMAN_ST_WORKSPACE) flags = ROMAN_LC_SKIPPED;
+    else if (st & ROMAN_ST_INTERNAL) flags = ROMAN_LC_INTERNAL;
+    else if (st & (ROMAN_ST_INSUFFICIENT | ROMAN_ST_EMPTY_MAP)) flags = ROMAN_LC_FAILED_INSUFFICIENT;
+    double Th[16];
+    if (!flags) {
+        const double* T = in.T + (int64_t)b * 16;
+        if (P.dim == 2) {                                        // planar estimate lifted to SE(3), identity in z
+#pragma unroll
+            for (int t = 0; t < 16; ++t) Th[t] = (t % 5 == 0) ? 1.0 : 0.0;
+            Th[0] = T[0]; Th[1] = T[1]; Th[4] = T[3]; Th[5] = T[4]; Th[3] = T[2]; Th[7] = T[5];
+        } else {
+#pragma unroll
+            for (int t = 0; t < 16; ++t) Th[t] = T[t];
+            // R = Rz(yaw) Ry(pitch) Rx(roll): the angles of as_euler('ZYX') and, reversed, of the fixed-axis 'xyz'
+            const double pitch = -asin(fmin(fmax(Th[8], -1.0), 1.0));
+            const double roll = atan2(Th[9], Th[10]);
+            if (P.tilt_thresh >= 0.0 && !(fabs(roll) < P.tilt_thresh && fabs(pitch) < P.tilt_thresh)) flags = ROMAN_LC_FAILED_TILT;
+            else if (P.force_rm_upside_down) {
+                const double half_pi = 90.0 * (3.141592653589793 / 180.0);      // np.deg2rad(90.)
+                if (fabs(roll) > half_pi || fabs(pitch) > half_pi) flags = ROMAN_LC_FAILED_UPSIDE_DOWN;
+            }
+            if (!flags && P.force_rm_lc_roll_pitch) {            // yaw only; the translation stays
+                const double yaw = atan2(Th[4], Th[0]);
+                const double cy = cos(yaw), sy = sin(yaw);
+                Th[0] = cy; Th[1] = -sy; Th[2] = 0.0; Th[4] = sy; Th[5] = cy; Th[6] = 0.0; Th[8] = 0.0; Th[9] = 0.0; Th[10] = 1.0;
+            }
+        }
+    }
+    roman_lc_record_t R;
+    R.problem = b; R.reserved = 0;
+    double theta = 180.0, dist = 1e6;                            // the sentinels of the except-branch
+    int n = 0;
+    if (!flags) {
+        n = in.n_assoc[b];
+        theta = d_nan(); dist = d_nan();
+        if (in.T_ref) {
+            double Ti[16], E[16];
+            lc_inv_affine(Th, Ti);
+            lc_mul4(Ti, in.T_ref + (int64_t)b * 16, E);
+            if (P.dim == 2) { theta = atan2(E[4], E[0]); dist = sqrt(E[3] * E[3] + E[7] * E[7]); }
+            else {
+                // rotation magnitude: 2 atan2(|q_xyz|, |q_w|) == atan2(|skew part| / 2, (trace - 1) / 2) on [0, pi]
+                const double sx = E[9] - E[6], sy = E[2] - E[8], sz = E[4] - E[1];
+                theta = atan2(0.5 * sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (E[0] + E[5] + E[10] - 1.0));
+                dist = sqrt(E[3] * E[3] + E[7] * E[7] + E[11] * E[11]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < 16; ++t) Th[t] = d_nan();
+    }
+    const bool countable = !(flags & (ROMAN_LC_SKIPPED | ROMAN_LC_INTERNAL));
+    const bool accepted = countable && n >= P.lc_association_thresh && (!in.enable || in.enable[b] != 0);
+    double et[3] = {d_nan(), d_nan(), d_nan()}, eq[4] = {d_nan(), d_nan(), d_nan(), d_nan()};
+    if (accepted) {
+        flags |= ROMAN_LC_ACCEPTED;
+        double A[16], E[16];
+        const double* Ep = Th;
+        if (in.FL) { lc_mul4(in.FL + (int64_t)in.iL[b] * 16, Th, A); Ep = A; }
+        if (in.FR) { lc_mul4(Ep, in.FR + (int64_t)in.iR[b] * 16, E); Ep = E; }
+        et[0] = Ep[3]; et[1] = Ep[7]; et[2] = Ep[11];
+        const double m00 = Ep[0], m11 = Ep[5], m22 = Ep[10], tr = m00 + m11 + m22;
+        int choice = 0; double best = m00;
+        if (m11 > best) { best = m11; choice = 1; }
+        if (m22 > best) { best = m22; choice = 2; }
+        if (tr > best) { best = tr; choice = 3; }
+        double q[4];
+        if (choice == 3) { q[0] = Ep[9] - Ep[6]; q[1] = Ep[2] - Ep[8]; q[2] = Ep[4] - Ep[1]; q[3] = 1.0 + tr; }
+        else {
+            const int i = choice, j = (i + 1) % 3, k = (j + 1) % 3;
+            q[i] = 1.0 - tr + 2.0 * Ep[i * 4 + i];
+            q[j] = Ep[j * 4 + i] + Ep[i * 4 + j];
+            q[k] = Ep[k * 4 + i] + Ep[i * 4 + k];
+            q[3] = Ep[k * 4 + j] - Ep[j * 4 + k];
+        }
+        const double nq = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) eq[t] = q[t] / nq;
+    }
+    R.n_assoc = n; R.flags = flags; R.theta = theta; R.dist = dist;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) R.T_hat[t] = Th[t];
+#pragma unroll
+    for (int t = 0; t < 3; ++t) R.edge_t[t] = et[t];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) R.edge_q[t] = eq[t];
+    rec[b] = R;
+}
+
+// k_lc_compact: the indices of the accepted problems in ascending order and their count.  One workgroup; a thread takes PER
+// consecutive problems and k_rowbase's block scan places them — deterministic, the order of the reference's edge loop.
+__global__ void __launch_bounds__(1024) k_lc_compact(int B, const roman_lc_record_t* __restrict__ rec, int32_t* __restrict__ idx, int32_t* __restrict__ count)
+{
+    __shared__ int shi[17];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int PER = (B + nt - 1) / nt;
+    const int b0 = min(B, tid * PER), b1 = min(B, b0 + PER);
+    int mine = 0;
+    for (int b = b0; b < b1; ++b) mine += (rec[b].flags & ROMAN_LC_ACCEPTED) ? 1 : 0;
+    int total;
+    int pos = block_excl_scan(mine, shi, total);
+    for (int b = b0; b < b1; ++b) if (rec[b].flags & ROMAN_LC_ACCEPTED) idx[pos++] = b;
+    if (tid == 0) *count = total;
+}
+
 
 // elementwise math probe for tests
 __global__ void k_debug_math(int kind, const double* __restrict__ a, const double* __restrict__ b,

@@ -82,7 +82,8 @@ struct roman_ctx {
         long long capMaskWords = 0, capNnz = 0, capList = 0;       // what the sparse pools hold (elements)
         // staging for the host-pointer entry points
         DevBuf hFeats, hAssoc, hU0, oAssoc, oN, oT, oStatus, oStats, hAux1, hAux2, hAux3;
-        DevBuf oAll;                           // outputs of a host-output batch call as ONE block (T | stats | assoc | n | status): one copy brings it back
+        DevBuf oAll;                           // outputs of a host-output batch call as ONE block (T | stats | assoc | n | status [| records | accepted | count]): one copy brings it back
+        DevBuf lcStage;                        // inputs of the loop-closure tail of roman_align_lc_batch (T_ref | FL | FR | enable | iL | iR)
         // totals of the most recent batch on this workspace, copied back without waiting
         BatchTotals* pinnedTotals = nullptr;
         ProbDesc* pinnedProbs = nullptr; size_t pinnedProbsCap = 0;   // staging of the problem descriptors (truly asynchronous upload)
@@ -1472,7 +1473,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
                          &W.lp, &W.li, &W.lj, &W.ls, &W.ld, &W.lza, &W.lzb, &W.plp, &W.pli, &W.plj, &W.pls, &W.pld, &W.plza, &W.plzb,
                          &W.rowCnt, &W.rowPos, &W.perm, &W.sliceWidth, &W.sliceBase, &W.items, &W.maskPool, &W.prefPool, &W.listPool, &W.listOff,
                          &W.vMu, &W.vCu, &W.vMun, &W.vCun, &W.gU, &W.gUn, &W.uOut, &W.nodesOrig, &W.nSel, &W.widePart, &W.wideSlots, &W.wideBar, &W.wideBm, &W.wideY, &W.wideUp, &W.fbList, &W.cols16, &W.cols32, &W.vals, &W.colsC, &W.valsC, &W.contSpill, &W.contList,
-                         &W.hFeats, &W.hAssoc, &W.hU0, &W.oAssoc, &W.oN, &W.oT, &W.oStatus, &W.oStats, &W.hAux1, &W.hAux2, &W.hAux3, &W.oAll};
+                         &W.hFeats, &W.hAssoc, &W.hU0, &W.oAssoc, &W.oN, &W.oT, &W.oStatus, &W.oStats, &W.hAux1, &W.hAux2, &W.hAux3, &W.oAll, &W.lcStage};
         for (DevBuf* b : all) b->release();
         if (W.pinnedTotals) (void)hipHostFree(W.pinnedTotals);
         if (W.totEvent) (void)hipEventDestroy(W.totEvent);
@@ -1583,17 +1584,63 @@ int roman_profile_get(roman_ctx_t* c, double ms[ROMAN_STAGE_COUNT], int64_t laun
     return ROMAN_OK;
 }
 
+}  // extern "C"
+
+namespace {
+// The loop-closure tail of a call: switches, device inputs, device outputs.
+struct LcTail { roman_lc_params_t P; LcIn in; roman_lc_record_t* rec; int32_t* idx; int32_t* cnt; };
+
+int check_lc_params(roman_ctx* c, const roman_lc_params_t* lp)
+{
+    if (!lp) return fail(c, ROMAN_E_INVALID, "lc_params is NULL");
+    if (lp->dim != 2 && lp->dim != 3) return fail(c, ROMAN_E_INVALID, "lc_params.dim must be 2 or 3 (got %d)", lp->dim);
+    if (lp->reserved[0] != 0 || lp->reserved[1] != 0) return fail(c, ROMAN_E_INVALID, "roman_lc_params_t.reserved must be 0");
+    if (lp->tilt_thresh != lp->tilt_thresh) return fail(c, ROMAN_E_INVALID, "lc_params.tilt_thresh is NaN");
+    return ROMAN_OK;
+}
+
+int make_lc_tail(roman_ctx* c, const roman_lc_params_t* lp, const double* T, const int32_t* n_assoc, const int32_t* status,
+                 const double* T_ref, const int32_t* enable, const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                 roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted, LcTail* t)
+{
+    int rc = check_lc_params(c, lp);
+    if (rc) return rc;
+    if (!n_accepted) return fail(c, ROMAN_E_INVALID, "n_accepted is NULL");
+    if ((FL != nullptr) != (iL != nullptr) || (FR != nullptr) != (iR != nullptr)) return fail(c, ROMAN_E_INVALID, "a frame pool and its index array come together (FL with iL, FR with iR)");
+    t->P = *lp;
+    t->in = LcIn{T, n_assoc, status, T_ref, enable, FL, iL, FR, iR};
+    t->rec = records; t->idx = accepted_idx; t->cnt = n_accepted;
+    return ROMAN_OK;
+}
+
+// k_lc_tail + k_lc_compact behind whatever is queued on `stream`
+int enqueue_lc_tail(roman_ctx* c, hipStream_t stream, int B, const LcTail& t)
+{
+    if (B > 0) {
+        if (!t.in.T || !t.in.n_assoc || !t.in.status || !t.rec || !t.idx) return fail(c, ROMAN_E_INVALID, "NULL pointer in the loop-closure tail's arguments");
+        hipLaunchKernelGGL(k_lc_tail, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, t.P, (int)B, t.in, t.rec);
+        HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_lc_compact, dim3(1), dim3(B > 256 ? 1024 : 256), 0, stream, (int)B, (const roman_lc_record_t*)t.rec, t.idx, t.cnt);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
 // --- the batched hot path --------------------------------------------------------------------------
-int roman_align_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+// roman_align_batch_dev, optionally with the loop-closure tail behind the solver on the same stream
+int align_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
                           const double* feats, const int64_t* off1, const int32_t* n1,
                           const int64_t* off2, const int32_t* n2, int32_t F,
                           const int32_t* assoc, const int64_t* assoc_off, const double* u0,
                           int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
-                          double* T_out, int32_t* status_out, roman_stats_t* stats_out)
+                          double* T_out, int32_t* status_out, roman_stats_t* stats_out, const LcTail* tail)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
-    if (B == 0) return ROMAN_OK;
+    if (B == 0) {
+        if (tail) { HIPCHK(c, hipSetDevice(c->device)); return enqueue_lc_tail(c, c->stream, 0, *tail); }
+        return ROMAN_OK;
+    }
     if (!off1 || !n1 || !off2 || !n2 || !assoc_out || !n_assoc_out || !T_out || !status_out || kmax < 0)
         return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer or kmax < 0");
     if (assoc && !assoc_off) return fail(c, ROMAN_E_INVALID, "assoc given without assoc_off");
@@ -1616,6 +1663,7 @@ int roman_align_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t 
         HIPCHK(c, hipStreamWaitEvent(c->istream[k], c->evIn, 0));
         c->cur = k; c->ws[k].stream = c->istream[k];
         rc = run_batch(c, D, params, in, u0, out);
+        if (!rc && tail) rc = enqueue_lc_tail(c, c->ws[k].stream, B, *tail);
         if (!rc) {
             HIPCHK(c, hipEventRecord(c->ws[k].done, c->ws[k].stream));
             c->ws[k].issued = true;
@@ -1628,7 +1676,57 @@ int roman_align_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t 
     rc = run_batch(c, D, params, in, u0, out);
     if (rc) return rc;
     c->last.scored = false; c->last.solved = false;
+    if (tail) return enqueue_lc_tail(c, c->stream, B, *tail);
     return ROMAN_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int roman_align_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                          const double* feats, const int64_t* off1, const int32_t* n1,
+                          const int64_t* off2, const int32_t* n2, int32_t F,
+                          const int32_t* assoc, const int64_t* assoc_off, const double* u0,
+                          int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
+                          double* T_out, int32_t* status_out, roman_stats_t* stats_out)
+{
+    return align_batch_dev(c, params, B, feats, off1, n1, off2, n2, F, assoc, assoc_off, u0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out, nullptr);
+}
+
+// The tail on its own, on the context's stream.  At pipeline depth >= 2 the batch outputs it reads are written on internal
+// streams: the caller orders them in front with roman_ctx_join().
+int roman_lc_tail_dev(roman_ctx_t* c, const roman_lc_params_t* lc_params, int32_t B,
+                      const double* T, const int32_t* n_assoc, const int32_t* status,
+                      const double* T_ref, const int32_t* enable,
+                      const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                      roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
+    LcTail t;
+    int rc = make_lc_tail(c, lc_params, T, n_assoc, status, T_ref, enable, FL, iL, FR, iR, records, accepted_idx, n_accepted, &t);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_lc_tail(c, c->stream, B, t);
+}
+
+int roman_align_lc_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                          const double* feats, const int64_t* off1, const int32_t* n1,
+                          const int64_t* off2, const int32_t* n2, int32_t F,
+                          const int32_t* assoc, const int64_t* assoc_off, const double* u0,
+                          int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
+                          double* T_out, int32_t* status_out, roman_stats_t* stats_out,
+                          const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                          const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                          roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (B > 0 && (!records || !accepted_idx)) return fail(c, ROMAN_E_INVALID, "records / accepted_idx is NULL");
+    LcTail t;
+    int rc = make_lc_tail(c, lc_params, T_out, n_assoc_out, status_out, T_ref, enable, FL, iL, FR, iR, records, accepted_idx, n_accepted, &t);
+    if (rc) return rc;
+    if (params && lc_params->dim != params->point_dim) return fail(c, ROMAN_E_INVALID, "lc_params.dim (%d) differs from params.point_dim (%d)", lc_params->dim, params->point_dim);
+    return align_batch_dev(c, params, B, feats, off1, n1, off2, n2, F, assoc, assoc_off, u0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out, &t);
 }
 
 int roman_ctx_cosine_screen_stats(roman_ctx_t* c, int64_t* screened_batches, int64_t* dense_batches, double* latest_fallback_share)
@@ -1752,15 +1850,26 @@ namespace {
 // The synchronous part shared by the two host-output entry points: inputs are on the device (`in`, dU0), the outputs of every call
 // land in ONE device block (T | stats | assoc | n | status) and come back with ONE copy through a pinned landing block — a single
 // pair's whole result is 1.8 KB, and five separate read-backs cost more than its build kernels.
+// The loop-closure tail of a host-output call: switches, its inputs already staged on the device, its outputs on the HOST.
+struct LcHost {
+    roman_lc_params_t P; const double* dTref; const int32_t* dEnable; const double* dFL; const int32_t* diL; const double* dFR; const int32_t* diR;
+    roman_lc_record_t* records; int32_t* idx; int32_t* cnt;
+};
+
 int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params, const BatchIn& in, const double* dU0,
-                  int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out, double* T_out, int32_t* status_out, roman_stats_t* stats_out)
+                  int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out, double* T_out, int32_t* status_out, roman_stats_t* stats_out,
+                  const LcHost* lc = nullptr)
 {
     const int32_t B = in.B;
     int rc = ROMAN_OK;
     bool copied = false;
     const size_t kb = (size_t)B * (size_t)std::max(kmax, 1);
     const size_t oT = 0, oS = oT + sizeof(double) * 16 * (size_t)B, oA = oS + sizeof(roman_stats_t) * (size_t)B,
-                 oNn = oA + sizeof(int32_t) * 2 * kb, oSt = oNn + sizeof(int32_t) * (size_t)B, total = oSt + sizeof(int32_t) * (size_t)B;
+                 oNn = oA + sizeof(int32_t) * 2 * kb, oSt = oNn + sizeof(int32_t) * (size_t)B, endSt = oSt + sizeof(int32_t) * (size_t)B;
+    // with a tail: records | accepted indices | count behind the batch outputs, in the same block and the same copy
+    const size_t oRec = (endSt + 7) & ~(size_t)7, oIdx = oRec + sizeof(roman_lc_record_t) * (size_t)B, oCnt = oIdx + sizeof(int32_t) * (size_t)B;
+    const size_t total = lc ? oCnt + sizeof(int32_t) : endSt;
+    static_assert(sizeof(roman_lc_record_t) % 8 == 0, "records are 8-byte aligned");
     static_assert(sizeof(roman_stats_t) % 8 == 0, "the blocks behind the statistics stay 8-byte aligned");
     HIPCHK(c, WS.oAll.ensure(total));
     if (c->hostOutCap < total) {
@@ -1772,10 +1881,18 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
     char* const dev = WS.oAll.as<char>();
     const BatchOut out{kmax, reinterpret_cast<int32_t*>(dev + oA), reinterpret_cast<int32_t*>(dev + oNn), reinterpret_cast<double*>(dev + oT),
                        reinterpret_cast<int32_t*>(dev + oSt), reinterpret_cast<roman_stats_t*>(dev + oS)};
+    LcTail tail;
+    if (lc) {
+        tail.P = lc->P;
+        tail.in = LcIn{out.T_out, out.n_assoc_out, out.status_out, lc->dTref, lc->dEnable, lc->dFL, lc->diL, lc->dFR, lc->diR};
+        tail.rec = reinterpret_cast<roman_lc_record_t*>(dev + oRec); tail.idx = reinterpret_cast<int32_t*>(dev + oIdx); tail.cnt = reinterpret_cast<int32_t*>(dev + oCnt);
+    }
     if (B > c->host_chunk && c->host_depth >= 2) {
         // many problems: calls of host_chunk problems, host_depth of them in flight, skipped problems issued again (align_chunked)
         rc = align_chunked(c, params, in, dU0, out);
         if (rc) return rc;
+        // the tail over the FINAL device block: every re-issue has landed (align_chunked returns synchronised, on workspace 0)
+        if (lc) { rc = enqueue_lc_tail(c, WS.stream, B, tail); if (rc) return rc; }
     } else
     // this entry point is synchronous anyway: when a problem did not fit the speculatively sized pools, run again
     // with the need the first attempt recorded
@@ -1784,6 +1901,7 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
         for (int attempt = 0; ; ++attempt) {
             c->teams_launched = false;
             rc = run_batch(c, D, params, in, dU0, out);
+            if (!rc && lc) rc = enqueue_lc_tail(c, WS.stream, B, tail);   // behind this attempt's solver; a retry below runs it again over the new results
             if (rc) { c->wide_teams = teams_saved; return rc; }
             // the read-back rides behind the batch on the same stream: ONE wait covers both (a retry below overwrites the landing block)
             if (hipMemcpyAsync(c->hostOut, dev, total, hipMemcpyDeviceToHost, WS.stream) != hipSuccess) { (void)hipGetLastError(); c->wide_teams = teams_saved; return fail(c, ROMAN_E_HIP, "result read-back failed"); }
@@ -1814,6 +1932,11 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
         memcpy(T_out, h + oT, sizeof(double) * 16 * (size_t)B);
         memcpy(status_out, h + oSt, sizeof(int32_t) * (size_t)B);
         if (stats_out) memcpy(stats_out, h + oS, sizeof(roman_stats_t) * (size_t)B);
+        if (lc) {
+            memcpy(lc->records, h + oRec, sizeof(roman_lc_record_t) * (size_t)B);
+            memcpy(lc->idx, h + oIdx, sizeof(int32_t) * (size_t)B);
+            memcpy(lc->cnt, h + oCnt, sizeof(int32_t));
+        }
     }
     c->last.scored = false; c->last.solved = false;
     {   // a problem the whole-device solver gave up on has no result: an error, not a quiet "0 associations"
@@ -1825,15 +1948,35 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
 }
 }  // namespace
 
-int roman_align_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+namespace {
+// The host arrays of the tail of roman_align_lc_batch (checked and staged behind the batch inputs).
+struct LcHostIn {
+    const roman_lc_params_t* P; const double* T_ref; const int32_t* enable; const double* FL; int32_t n_left; const int32_t* iL;
+    const double* FR; int32_t n_right; const int32_t* iR; roman_lc_record_t* records; int32_t* idx; int32_t* cnt;
+};
+
+int align_batch_host(roman_ctx_t* c, const roman_params_t* params, int32_t B,
                       const double* feats, int64_t n_objects,
                       const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
                       const int32_t* assoc, const int64_t* assoc_off, const double* u0,
                       int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
-                      double* T_out, int32_t* status_out, roman_stats_t* stats_out)
+                      double* T_out, int32_t* status_out, roman_stats_t* stats_out, const LcHostIn* lci)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (B < 0 || n_objects < 0 || F < 0) return fail(c, ROMAN_E_INVALID, "negative size");
+    if (lci) {
+        int rc0 = check_lc_params(c, lci->P);
+        if (rc0) return rc0;
+        if (!lci->cnt) return fail(c, ROMAN_E_INVALID, "n_accepted is NULL");
+        if (B > 0 && (!lci->records || !lci->idx)) return fail(c, ROMAN_E_INVALID, "records / accepted_idx is NULL");
+        if ((lci->FL != nullptr) != (lci->iL != nullptr) || (lci->FR != nullptr) != (lci->iR != nullptr)) return fail(c, ROMAN_E_INVALID, "a frame pool and its index array come together (FL with iL, FR with iR)");
+        if (params && lci->P->dim != params->point_dim) return fail(c, ROMAN_E_INVALID, "lc_params.dim (%d) differs from params.point_dim (%d)", lci->P->dim, params->point_dim);
+        for (int b = 0; b < B; ++b) {                            // the device indexes the frame pools with these
+            if (lci->iL && (lci->iL[b] < 0 || lci->iL[b] >= lci->n_left)) return fail(c, ROMAN_E_INVALID, "iL[%d] = %d outside the %d left frames", b, lci->iL[b], lci->n_left);
+            if (lci->iR && (lci->iR[b] < 0 || lci->iR[b] >= lci->n_right)) return fail(c, ROMAN_E_INVALID, "iR[%d] = %d outside the %d right frames", b, lci->iR[b], lci->n_right);
+        }
+        if (B == 0) { *lci->cnt = 0; return ROMAN_OK; }
+    }
     if (B == 0) return ROMAN_OK;
     if (!off1 || !n1 || !off2 || !n2 || !assoc_out || !n_assoc_out || !T_out || !status_out || kmax < 0)
         return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer or kmax < 0");
@@ -1874,7 +2017,56 @@ int roman_align_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
         dU0 = WS.hU0.as<double>();
     }
     const BatchIn in{B, WS.hFeats.as<double>(), off1, n1, off2, n2, F, dA, assoc_off};
-    return align_to_host(c, D, params, in, dU0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out);
+    if (!lci) return align_to_host(c, D, params, in, dU0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out);
+    // the tail's inputs in one staging block: doubles first (T_ref | FL | FR), then the int32 arrays (enable | iL | iR)
+    const size_t nRef = lci->T_ref ? (size_t)B * 16 : 0, nFL = lci->FL ? (size_t)lci->n_left * 16 : 0, nFR = lci->FR ? (size_t)lci->n_right * 16 : 0;
+    const size_t oFL = sizeof(double) * nRef, oFR = oFL + sizeof(double) * nFL, oEn = oFR + sizeof(double) * nFR;
+    const size_t oIL = oEn + (lci->enable ? sizeof(int32_t) * (size_t)B : 0), oIR = oIL + (lci->iL ? sizeof(int32_t) * (size_t)B : 0);
+    const size_t stageBytes = oIR + (lci->iR ? sizeof(int32_t) * (size_t)B : 0);
+    HIPCHK(c, WS.lcStage.ensure(std::max<size_t>(stageBytes, 8)));
+    char* const sd = WS.lcStage.as<char>();
+    auto up = [&](size_t off, const void* src, size_t bytes) -> hipError_t { return bytes ? hipMemcpyAsync(sd + off, src, bytes, hipMemcpyHostToDevice, WS.stream) : hipSuccess; };
+    HIPCHK(c, up(0, lci->T_ref, sizeof(double) * nRef));
+    HIPCHK(c, up(oFL, lci->FL, sizeof(double) * nFL));
+    HIPCHK(c, up(oFR, lci->FR, sizeof(double) * nFR));
+    HIPCHK(c, up(oEn, lci->enable, lci->enable ? sizeof(int32_t) * (size_t)B : 0));
+    HIPCHK(c, up(oIL, lci->iL, lci->iL ? sizeof(int32_t) * (size_t)B : 0));
+    HIPCHK(c, up(oIR, lci->iR, lci->iR ? sizeof(int32_t) * (size_t)B : 0));
+    LcHost lh;
+    lh.P = *lci->P;
+    lh.dTref = lci->T_ref ? reinterpret_cast<const double*>(sd) : nullptr;
+    lh.dFL = lci->FL ? reinterpret_cast<const double*>(sd + oFL) : nullptr;
+    lh.dFR = lci->FR ? reinterpret_cast<const double*>(sd + oFR) : nullptr;
+    lh.dEnable = lci->enable ? reinterpret_cast<const int32_t*>(sd + oEn) : nullptr;
+    lh.diL = lci->iL ? reinterpret_cast<const int32_t*>(sd + oIL) : nullptr;
+    lh.diR = lci->iR ? reinterpret_cast<const int32_t*>(sd + oIR) : nullptr;
+    lh.records = lci->records; lh.idx = lci->idx; lh.cnt = lci->cnt;
+    return align_to_host(c, D, params, in, dU0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out, &lh);
+}
+}  // namespace
+
+int roman_align_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                      const double* feats, int64_t n_objects,
+                      const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
+                      const int32_t* assoc, const int64_t* assoc_off, const double* u0,
+                      int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
+                      double* T_out, int32_t* status_out, roman_stats_t* stats_out)
+{
+    return align_batch_host(c, params, B, feats, n_objects, off1, n1, off2, n2, F, assoc, assoc_off, u0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out, nullptr);
+}
+
+int roman_align_lc_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                      const double* feats, int64_t n_objects,
+                      const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
+                      const int32_t* assoc, const int64_t* assoc_off, const double* u0,
+                      int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
+                      double* T_out, int32_t* status_out, roman_stats_t* stats_out,
+                      const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                      const double* FL, int32_t n_left, const int32_t* iL, const double* FR, int32_t n_right, const int32_t* iR,
+                      roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted)
+{
+    const LcHostIn lci{lc_params, T_ref, enable, FL, n_left, iL, FR, n_right, iR, records, accepted_idx, n_accepted};
+    return align_batch_host(c, params, B, feats, n_objects, off1, n1, off2, n2, F, assoc, assoc_off, u0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out, &lci);
 }
 
 /* roman_align_batch_resident: inputs in HBM (as roman_align_batch_dev), results on the HOST (as roman_align_batch). */

@@ -6,11 +6,12 @@ without a gfx950 device raises RomanHipError.
 """
 import ctypes as C
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
 from . import _abi
-from ._abi import RomanHipError, RomanParams, RomanStats
+from ._abi import RomanHipError, RomanLcParams, RomanParams, RomanStats
 
 
 def _ptr(a):
@@ -34,6 +35,58 @@ class BatchResult:
     T: np.ndarray          # (B, dim+1, dim+1) float64, NaN where status has INSUFFICIENT/EMPTY_MAP
     status: np.ndarray     # (B,) int32 ROMAN_ST_* flags
     stats: np.ndarray      # (B,) structured array (stats_dtype)
+
+
+def lc_record_dtype():
+    """roman_lc_record_t as a structured dtype."""
+    return np.dtype([("problem", np.int32), ("n_assoc", np.int32), ("flags", np.int32), ("reserved", np.int32),
+                     ("T_hat", np.float64, (4, 4)), ("theta", np.float64), ("dist", np.float64),
+                     ("edge_t", np.float64, (3,)), ("edge_q", np.float64, (4,))])
+
+
+@dataclass
+class LcInputs:
+    """What the loop-closure tail needs besides the batch outputs (roman_lc_tail_dev in include/roman_hip.h): the switches of
+    roman_lc_params_t and the optional per-problem / per-submap arrays."""
+    dim: int = 3
+    force_rm_upside_down: bool = False
+    force_rm_lc_roll_pitch: bool = False
+    tilt_thresh: Optional[float] = None          # radians; None = no tilt check
+    lc_association_thresh: int = 4
+    T_ref: Optional[np.ndarray] = None           # (B, 4, 4) reference transforms
+    enable: Optional[np.ndarray] = None          # (B,) non-zero = may be accepted
+    FL: Optional[np.ndarray] = None              # (S0, 4, 4) per-submap frames of the left side, with iL (B,)
+    iL: Optional[np.ndarray] = None
+    FR: Optional[np.ndarray] = None              # (S1, 4, 4) and iR (B,) for the right side
+    iR: Optional[np.ndarray] = None
+
+    def params(self):
+        p = RomanLcParams()
+        p.dim = int(self.dim)
+        p.force_rm_upside_down = int(bool(self.force_rm_upside_down))
+        p.force_rm_lc_roll_pitch = int(bool(self.force_rm_lc_roll_pitch))
+        p.lc_association_thresh = int(self.lc_association_thresh)
+        p.tilt_thresh = -1.0 if self.tilt_thresh is None else float(self.tilt_thresh)
+        return p
+
+    def arrays(self, B):
+        """The optional arrays in the C ABI's layouts (None stays None)."""
+        T_ref = None if self.T_ref is None else _f64(self.T_ref).reshape(B, 16)
+        enable = None if self.enable is None else np.ascontiguousarray(self.enable, dtype=np.int32).reshape(B)
+        FL = None if self.FL is None else _f64(self.FL).reshape(-1, 16)
+        FR = None if self.FR is None else _f64(self.FR).reshape(-1, 16)
+        iL = None if self.iL is None else np.ascontiguousarray(self.iL, dtype=np.int32).reshape(B)
+        iR = None if self.iR is None else np.ascontiguousarray(self.iR, dtype=np.int32).reshape(B)
+        if (FL is None) != (iL is None) or (FR is None) != (iR is None):
+            raise ValueError("a frame pool and its index array come together (FL with iL, FR with iR)")
+        return T_ref, enable, FL, iL, FR, iR
+
+
+@dataclass
+class LoopClosureResult(BatchResult):
+    """A batch result with the loop-closure tail behind it."""
+    records: np.ndarray    # (B,) structured array (lc_record_dtype)
+    accepted: np.ndarray   # (n_accepted,) int32: accepted problems, ascending
 
 
 class Context:
@@ -213,6 +266,72 @@ class Context:
                                              vp(u0_ptr), int(kmax), vp(assoc_out_ptr), vp(n_assoc_out_ptr),
                                              vp(T_out_ptr), vp(status_out_ptr), vp(stats_out_ptr))
         self._check(rc, "roman_align_batch_dev")
+
+    # ------------------------------------------------------------------ loop closures
+    def align_lc_batch(self, params, feats, off1, n1, off2, n2, lc, assoc=None, assoc_off=None, u0=None, kmax=None):
+        """Host-pointer batch call with the loop-closure tail behind it (roman_align_lc_batch): `lc` is an LcInputs.
+        -> LoopClosureResult; one read-back brings outputs, records and the accepted list."""
+        feats = _f64(feats)
+        if feats.ndim != 2:
+            raise ValueError("feats must be (n_objects, F)")
+        n_obj, F = feats.shape
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        B = int(n1.shape[0])
+        if assoc is not None:
+            assoc = np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2)
+            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        if u0 is not None:
+            u0 = _f64(u0)
+        if kmax is None:
+            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
+        a_out = np.zeros((B, kmax, 2), dtype=np.int32); n_out = np.zeros(B, dtype=np.int32)
+        T = np.zeros((B, 16), dtype=np.float64); status = np.zeros(B, dtype=np.int32); stats = np.zeros(B, dtype=stats_dtype())
+        records = np.zeros(B, dtype=lc_record_dtype()); idx = np.zeros(max(B, 1), dtype=np.int32); cnt = np.zeros(1, dtype=np.int32)
+        assert records.dtype.itemsize == _abi.LC_RECORD_NBYTES
+        lp = lc.params()
+        T_ref, enable, FL, iL, FR, iR = lc.arrays(B)
+        self._generation += 1
+        rc = self._lib.roman_align_lc_batch(self._h, C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
+                                            _ptr(assoc), _ptr(assoc_off), _ptr(u0), kmax, _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats),
+                                            C.byref(lp), _ptr(T_ref), _ptr(enable), _ptr(FL), 0 if FL is None else FL.shape[0], _ptr(iL),
+                                            _ptr(FR), 0 if FR is None else FR.shape[0], _ptr(iR), _ptr(records), _ptr(idx), _ptr(cnt))
+        s = params.point_dim + 1
+        res = lambda: LoopClosureResult([a_out[b, :n_out[b]].copy() for b in range(B)], T[:, :s * s].reshape(B, s, s).copy(), status, stats,
+                                        records, idx[:int(cnt[0])].copy())
+        if rc == _abi.ROMAN_E_INTERNAL:                          # outputs were copied: the error says which problems have no result
+            msg = self._lib.roman_last_error(self._h)
+            err = RomanHipError(f"roman_align_lc_batch failed ({rc}): {msg.decode() if msg else ''}")
+            err.result = res()
+            raise err
+        self._check(rc, "roman_align_lc_batch")
+        return res()
+
+    def lc_tail_dev(self, lc_params, B, T_ptr, n_assoc_ptr, status_ptr, records_ptr, accepted_idx_ptr, n_accepted_ptr,
+                    T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None, FR_ptr=None, iR_ptr=None):
+        """The tail on its own over batch outputs in HBM (roman_lc_tail_dev): every pointer a device address (an integer, e.g.
+        torch.Tensor.data_ptr()); lc_params a RomanLcParams (LcInputs.params()).  A pure enqueue on the context's stream."""
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_lc_tail_dev(self._h, C.byref(lc_params), int(B), vp(T_ptr), vp(n_assoc_ptr), vp(status_ptr), vp(T_ref_ptr), vp(enable_ptr),
+                                         vp(FL_ptr), vp(iL_ptr), vp(FR_ptr), vp(iR_ptr), vp(records_ptr), vp(accepted_idx_ptr), vp(n_accepted_ptr))
+        self._check(rc, "roman_lc_tail_dev")
+
+    def align_lc_batch_dev(self, params, feats_ptr, F, off1, n1, off2, n2, kmax, assoc_out_ptr, n_assoc_out_ptr, T_out_ptr, status_out_ptr,
+                           lc_params, records_ptr, accepted_idx_ptr, n_accepted_ptr, stats_out_ptr=None, assoc_ptr=None, assoc_off=None, u0_ptr=None,
+                           T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None, FR_ptr=None, iR_ptr=None):
+        """align_batch_dev with the tail enqueued behind the solver on the same stream (roman_align_lc_batch_dev): a pure enqueue,
+        complete after sync()."""
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        if assoc_off is not None:
+            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        self._generation += 1
+        rc = self._lib.roman_align_lc_batch_dev(self._h, C.byref(params), int(n1.shape[0]), vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                                int(F), vp(assoc_ptr), _ptr(assoc_off), vp(u0_ptr), int(kmax), vp(assoc_out_ptr), vp(n_assoc_out_ptr),
+                                                vp(T_out_ptr), vp(status_out_ptr), vp(stats_out_ptr), C.byref(lc_params), vp(T_ref_ptr), vp(enable_ptr),
+                                                vp(FL_ptr), vp(iL_ptr), vp(FR_ptr), vp(iR_ptr), vp(records_ptr), vp(accepted_idx_ptr), vp(n_accepted_ptr))
+        self._check(rc, "roman_align_lc_batch_dev")
 
     # ------------------------------------------------------------------ stepwise (clipperpy shim)
     def score(self, params, D1, D2, assoc=None):
