@@ -460,6 +460,69 @@ ROMAN_API int roman_align_lc_batch(roman_ctx_t* ctx, const roman_params_t* param
                       roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted);
 
 /* ------------------------------------------------------------------------------------------- */
+/* multi-solution extraction, batched                                                          */
+/* ------------------------------------------------------------------------------------------- */
+
+/* ObjectRegistration.mno_clipper(map1, map2, num_solutions) [REF roman/align/object_registration.py:57-86] for B
+   independent submap pairs: score the pair as the batch call does, then num_solutions times — solve, record the
+   selected set, zero that set's block of M — without a host round trip between the rounds.  Per problem:
+     - every solve is a PLAIN CLIPPER solve ([REF :60] builds CLIPPER(PairwiseInvariant(), Params())) over ALL A input
+       associations: strict upper triangles of the scored M and C, unit diagonal, u0 all ones, the solver parameters
+       of `params`.  An association whose single score is 0 under the ROMAN invariant stays a node (an isolated one,
+       as in the dense matrices get_affinity_matrix() exports).  Solution 0 is therefore register()'s result for the
+       invariants without single scores, and in general NOT for ROMAN_INV_ROMAN;
+     - a solution's associations are in clipperpy order (descending u, the tie rule of the batch call);
+       score = u_s' M u_s / (u_s' u_s) with u_s = u restricted to the selected nodes and M the scored matrix as
+       exported, never masked (its diagonal: the single score for ROMAN, 1 otherwise); 0 for an empty selection;
+     - before the next solve M[p][q] becomes 0 for all selected p, q; C keeps its pattern (a masked pair is a
+       consistent pair of weight 0); masks accumulate;
+     - T is the pose of T_align [REF :88-129] on the solution's associations (the reference's loop returns none).
+   One record per (problem, solution): */
+typedef struct roman_mno_solution {
+    int32_t n_assoc;       /* rows of this solution in assoc_out (at most kmax)                                   */
+    int32_t status;        /* ROMAN_ST_* of this solution                                                         */
+    double  score;         /* Rayleigh quotient on the unmasked M, 0 when the selection is empty                  */
+    double  T[16];         /* pose of this hypothesis, row-major (dim+1)^2 in the leading entries; NaN when the
+                              status has ROMAN_ST_INSUFFICIENT / ROMAN_ST_EMPTY_MAP / ROMAN_ST_WORKSPACE          */
+} roman_mno_solution_t;
+
+#define ROMAN_MNO_MAX_SOLUTIONS   64    /* num_solutions above this: ROMAN_E_INVALID                              */
+#define ROMAN_MNO_MAX_ASSOC     3072    /* associations per problem this call serves (the matrix layout whose values
+                                           the mask rewrites); a longer list: ROMAN_E_TOO_LARGE                  */
+
+/*
+ * roman_mno_batch_dev: bulk data device-resident, arguments as for roman_align_batch_dev (u0 is always all ones).
+ *   num_solutions  1 ... ROMAN_MNO_MAX_SOLUTIONS (else ROMAN_E_INVALID)
+ *   assoc_out      DEVICE, int32[B][num_solutions][kmax][2]
+ *   sol_out        DEVICE, roman_mno_solution_t[B][num_solutions]
+ *   stats_out      DEVICE, roman_stats_t[B][num_solutions] or NULL: the statistics of every solve
+ * A PURE ENQUEUE like roman_align_batch_dev (same streams, same pipeline rules): all rounds of all problems are queued
+ * at once.  A problem that found no workspace is skipped: ROMAN_ST_WORKSPACE on EVERY one of its solutions — issue it
+ * again.  An empty map: ROMAN_ST_EMPTY_MAP, num_solutions empty solutions of score 0 with NaN poses.  More selected
+ * associations than kmax: ROMAN_ST_ASSOC_TRUNCATED on that solution; score and pose come from the full set.
+ * The sizing history of the plain-CLIPPER view is kept apart from the one of the batch call with the same block
+ * (the context holds one history: alternating the two calls makes each start from its first-call estimates).
+ */
+ROMAN_API int roman_mno_batch_dev(roman_ctx_t* ctx, const roman_params_t* params, int32_t B,
+                                  const double* feats, const int64_t* off1, const int32_t* n1,
+                                  const int64_t* off2, const int32_t* n2, int32_t F,
+                                  const int32_t* assoc, const int64_t* assoc_off,
+                                  int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                                  roman_mno_solution_t* sol_out, roman_stats_t* stats_out);
+
+/* The same with HOST pointers everywhere ([REF roman/align/object_registration.py:57-86] for a caller that holds
+   NumPy arrays); `n_objects` = number of objects in `feats`.  Synchronous; copies in, issues the batch in calls of the
+   host-batching chunk (roman_ctx_set_host_batching) with its depth in flight, issues skipped problems again (those
+   only, at most 5 attempts, then ROMAN_E_NOMEM) and brings the three output arrays back. */
+ROMAN_API int roman_mno_batch(roman_ctx_t* ctx, const roman_params_t* params, int32_t B,
+                              const double* feats, int64_t n_objects,
+                              const int64_t* off1, const int32_t* n1,
+                              const int64_t* off2, const int32_t* n2, int32_t F,
+                              const int32_t* assoc, const int64_t* assoc_off,
+                              int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                              roman_mno_solution_t* sol_out, roman_stats_t* stats_out);
+
+/* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */
 /* ------------------------------------------------------------------------------------------- */
 

@@ -158,7 +158,21 @@ class RomanLcRecord(C.Structure):
     ]
 
 
+class RomanMnoSolution(C.Structure):
+    """roman_mno_solution_t"""
+    _fields_ = [
+        ("n_assoc", C.c_int32),
+        ("status", C.c_int32),
+        ("score", C.c_double),
+        ("T", C.c_double * 16),
+    ]
+
+
+ROMAN_MNO_MAX_SOLUTIONS = 64
+ROMAN_MNO_MAX_ASSOC = 3072
+
 STATS_NBYTES = C.sizeof(RomanStats)
+MNO_SOLUTION_NBYTES = C.sizeof(RomanMnoSolution)
 LC_PARAMS_NBYTES = C.sizeof(RomanLcParams)
 LC_RECORD_NBYTES = C.sizeof(RomanLcRecord)
 PARAMS_NBYTES = C.sizeof(RomanParams)
@@ -214,6 +228,10 @@ def load_library():
         "roman_align_lc_batch": (C.c_int, [ctxp, P(RomanParams), i32, vp, i64, vp, vp, vp, vp, i32,
                                            vp, vp, vp, i32, vp, vp, vp, vp, vp,
                                            P(RomanLcParams), vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
+        "roman_mno_batch_dev": (C.c_int, [ctxp, P(RomanParams), i32, vp, vp, vp, vp, vp, i32,
+                                          vp, vp, i32, i32, vp, vp, vp]),
+        "roman_mno_batch": (C.c_int, [ctxp, P(RomanParams), i32, vp, i64, vp, vp, vp, vp, i32,
+                                      vp, vp, i32, i32, vp, vp, vp]),
         "roman_ctx_has_history": (C.c_int, [ctxp, P(RomanParams), i32, P(i32)]),
         "roman_ctx_cosine_screen_stats": (C.c_int, [ctxp, P(C.c_int64), P(C.c_int64), P(C.c_double)]),
         "roman_create_all_to_all": (C.c_int, [i32, i32, vp]),
@@ -248,7 +266,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_mno_batch_dev", "roman_mno_batch", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

@@ -116,6 +116,14 @@ def run_lc_batch(registration, batch: AlignmentBatch, lc, u0=None, ctx=None):
                               assoc=batch.assoc, assoc_off=batch.assoc_off, u0=u0, kmax=batch.kmax())
 
 
+def run_mno_batch(registration, batch: AlignmentBatch, num_solutions=2, ctx=None):
+    """One roman_mno_batch call for `batch`: `num_solutions` hypotheses per problem
+    ([REF roman/align/object_registration.py:57-86] for every pair at once) -> runtime.MnoResult."""
+    ctx = ctx or registration._context()
+    return ctx.mno_batch(registration._abi_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2,
+                         num_solutions=num_solutions, assoc=batch.assoc, assoc_off=batch.assoc_off, kmax=batch.kmax())
+
+
 def align_pairs(registration, pairs, u0=None):
     """register() + T_align() for every (map1, map2) in `pairs`, one device call."""
     return run_batch(registration, batch_from_pairs(registration, pairs), u0=u0)

@@ -120,6 +120,25 @@ class ObjectRegistration:
                 M[np.ix_(nodes, nodes)] = 0.0
         return solutions
 
+    def mno_clipper_batch(self, pairs, num_solutions=2, return_result=False, ctx=None):
+        """mno_clipper() for many (map1, map2) pairs in one device call (roman_mno_batch): no dense matrix is formed, and
+        the rounds run back to back on the device.  Returns (solutions, poses): solutions[b] is exactly the list
+        [(Ain int64 (k,2), score), ...] that mno_clipper(*pairs[b], num_solutions) returns, poses[b][k] the
+        (dim+1, dim+1) transform of T_align on hypothesis k (NaN where T_align would raise).  return_result=True adds the
+        runtime.MnoResult (status flags, solver statistics) as a third value; `ctx` replaces the registration's context
+        (anything with runtime.Context.mno_batch's signature)."""
+        from .batch import batch_from_pairs, run_mno_batch
+        res = run_mno_batch(self, batch_from_pairs(self, pairs), num_solutions, ctx=ctx)
+        solutions, poses = [], []
+        for b in range(len(pairs)):
+            sols = []
+            for k in range(num_solutions):
+                Ain = np.asarray(res.assoc[b][k]).astype(np.int64).reshape(-1, 2)
+                sols.append((Ain, 0 if len(Ain) == 0 and res.score[b, k] == 0 else float(res.score[b, k])))
+            solutions.append(sols)
+            poses.append([res.T[b, k].copy() for k in range(num_solutions)])
+        return (solutions, poses, res) if return_result else (solutions, poses)
+
     def T_align(self, map1: List, map2: List, correspondences: np.array = None):
         """Transformation that aligns map2 to map1 (Arun's method),
         [REF roman/align/object_registration.py:88-129]."""

@@ -67,6 +67,8 @@ struct DevParams {
     int32_t stream_maxL;     // problems of up to this many live associations take the stream layout (<= STREAM_MAXL; set per launch:
                              // it is also the column capacity of k_fill_slice's LDS tile and of the stream solver's LDS vectors)
     int32_t pre_K;           // k_count's integer prefilter: a pair goes to the exact gate iff its two quantised table entries differ by at most pre_K bins
+    int32_t plain_all;       // plain-CLIPPER view of a scored matrix (roman_mno_batch*): an association with a zero single score stays a NODE — live, with
+                             // an empty row (fuse_pair gives its pairs the value 0: inert slots) and, like every node of the view, a unit diagonal (diag_one)
     double  pre_invw;        // ... bins per metre (1 / bin width; bin width = epsilon / 32)
 };
 
@@ -1540,12 +1542,12 @@ __global__ void __launch_bounds__(256) k_live(DevParams D, const ProbDesc* __res
         };
         int nlive = 0;
         auto emit = [&](bool valid, int p, double s) {          // ordered append of the lanes with a live association
-            const bool live = valid && (s > 0.0 || D.keep_all);
+            const bool live = valid && (s > 0.0 || D.keep_all || D.plain_all);
             const unsigned long long m = __ballot(live);
             if (live) { const int k = p_beg + nlive + __popcll(m & lt); qP[lo + k] = p; qS[lo + k] = s; }
             nlive += __popcll(m);
         };
-        if (D.single && Fc > 0 && !D.keep_all) {
+        if (D.single && Fc > 0 && !D.keep_all && !D.plain_all) {
             uint16_t* q = survQ[w];
             const double cden = D.p.cosine_max - D.p.cosine_min;
             int ns = 0;
@@ -6691,6 +6693,129 @@ __global__ void __launch_bounds__(256) k_skipped(int B, const ProbDesc* __restri
     for (int t = 0; t < 16; ++t) O.T_out[(int64_t)b * 16 + t] = d_nan();
     O.n_assoc_out[b] = 0; O.status_out[b] = ROMAN_ST_WORKSPACE; O.nSel[b] = 0;
     if (O.stats_out) { roman_stats_t S{}; S.n_assoc_in = probs[b].nA; S.n_live = st[b].L; O.stats_out[b] = S; }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Multi-solution extraction (roman_mno_batch*, [REF roman/align/object_registration.py:57-86]): the step between two
+// solves of the plain-CLIPPER view of a batch.  One workgroup per problem, one pass over the problem's stored entries
+// (stream layout: quads of 256 slots, lane = row slot):
+//   score    u_s' M_orig u_s / (u_s' u_s) in f64 over the round's nodes — the diagonal the invariant exports (the single
+//            score, or 1) plus twice the stored pairs whose two endpoints are nodes, read from the UNMASKED values;
+//   record   the round's count, status, pose, statistics and association rows from the solver's per-round block into
+//            solution (b, r) of the caller's arrays;
+//   mask     the values of those pairs become 0 in the copy the next solve reads; the column words stay as they are
+//            (a masked pair remains a consistent pair of weight 0).  maskMode 1 (first round) writes the whole copy,
+//            2 zeroes in place, 0 (last round) writes nothing.
+// Membership is a bit map over positions in LDS (L <= STREAM_MAXL bits).  Bound by the 2-byte column words of the pass
+// (+ 16 bytes per entry in the round that makes the copy).
+// ---------------------------------------------------------------------------------------------
+struct MnoRound {
+    const int32_t* n_assoc; const int32_t* status; const double* T; const roman_stats_t* stats; const int32_t* assoc;   // the solver's block of this round ([B] / [B][kmax][2])
+    int32_t* assoc_out; roman_mno_solution_t* sol_out; roman_stats_t* stats_out;                                       // the caller's arrays ([B][K]...)
+    int32_t K, r, kmax, maskMode, diagOne;
+};
+constexpr int MNO_NT = 512;
+
+__global__ void __launch_bounds__(MNO_NT) k_mno_round(int B, MnoRound R, const ProbDesc* __restrict__ probs, const ProbState* __restrict__ st,
+                                                      const int32_t* __restrict__ lpAsc, const double* __restrict__ ls, const uint32_t* __restrict__ rowPos,
+                                                      const uint32_t* __restrict__ sliceBase, const uint16_t* __restrict__ cols,
+                                                      const double* __restrict__ valsOrig, double* __restrict__ valsMasked,
+                                                      const int32_t* __restrict__ nodesOrig, const int32_t* __restrict__ nSel, const double* __restrict__ uOut)
+{
+    __shared__ double uL[STREAM_MAXL];                          // final u by position
+    __shared__ unsigned long long bm[STREAM_MAXL / 64];         // the round's nodes, by position
+    __shared__ uint32_t sq[STREAM_MAXL / 64 + 1];               // first quad of every slice (+ the total)
+    __shared__ double red[2 * (MNO_NT / 64)];
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    constexpr int NWV = MNO_NT / 64;
+    const ProbDesc pd = probs[b];
+    const ProbState ps = st[b];
+    const int64_t lo = pd.liveOff;
+    const bool solved = ps.kind == 0 && ps.L > 0 && ps.L <= STREAM_MAXL;
+    const int L = solved ? ps.L : 0;
+    const int nsel = solved ? min(max(nSel[b], 0), L) : 0;
+    const int nsl = (L + 63) >> 6;
+    for (int p = tid; p < L; p += MNO_NT) uL[p] = uOut[ps.rowBase + p];
+    if (tid < STREAM_MAXL / 64) bm[tid] = 0ull;
+    if (tid <= nsl && solved) sq[tid] = tid < nsl ? (sliceBase[lo + tid] >> 8) : (ps.nnzCap >> 8);
+    __syncthreads();
+    // nodes -> positions: association index -> live index (the live list is ascending) -> position; diagonal part of the quotient
+    double num = 0.0, den = 0.0;
+    for (int t = tid; t < nsel; t += MNO_NT) {
+        const int a = nodesOrig[ps.rowBase + t];
+        int lo_ = 0, hi_ = L - 1;
+        while (lo_ < hi_) { const int mid = (lo_ + hi_) >> 1; if (lpAsc[lo + mid] < a) lo_ = mid + 1; else hi_ = mid; }
+        const int k = lo_;
+        const uint32_t p = rowPos[lo + k];
+        if (lpAsc[lo + k] == a && p < (uint32_t)L) {
+            atomicOr(&bm[p >> 6], 1ull << (p & 63u));
+            const double up = uL[p];
+            num += (R.diagOne ? 1.0 : ls[lo + k]) * up * up;
+            den += up * up;
+        }
+    }
+    __syncthreads();
+    // the stored pairs: quad q of the problem's segment holds entries 4g..4g+3 of the 64 rows of its slice
+    if (solved && (nsel > 0 || R.maskMode == 1)) {
+        const uint32_t Q = sq[nsl];
+        const uint16_t* cp = cols + ps.nnzOff;
+        const double* vo = valsOrig + ps.nnzOff;
+        double* vm = valsMasked ? valsMasked + ps.nnzOff : nullptr;
+        int s = 0;
+        double off2 = 0.0;
+        for (uint32_t q = (uint32_t)w; q < Q; q += NWV) {
+            while (s + 1 < nsl && q >= sq[s + 1]) ++s;          // wave-uniform
+            const int p = s * 64 + lane;
+            const bool rowIn = p < L && ((bm[p >> 6] >> (p & 63)) & 1ull);
+            const uint2 cw = *reinterpret_cast<const uint2*>(cp + (size_t)q * 256 + lane * 4);
+            unsigned hit = 0u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t lab = ((j < 2 ? cw.x : cw.y) >> (16 * (j & 1))) & 0xffffu, c = lab & 0x7fffu;
+                if (rowIn && c < (uint32_t)L && ((bm[c >> 6] >> (c & 63u)) & 1ull)) hit |= 1u << j;
+            }
+            const size_t v0 = (size_t)q * 256 + lane * 2, v1 = v0 + 128;     // entries 0,1 and 2,3 of this lane
+            if (R.maskMode == 1) {
+                double2 a0 = *reinterpret_cast<const double2*>(vo + v0), a1 = *reinterpret_cast<const double2*>(vo + v1);
+                if (hit) {
+                    const double up = uL[p];
+                    if (hit & 1u) { off2 += a0.x * up * uL[cw.x & 0x7fffu]; a0.x = 0.0; }
+                    if (hit & 2u) { off2 += a0.y * up * uL[(cw.x >> 16) & 0x7fffu]; a0.y = 0.0; }
+                    if (hit & 4u) { off2 += a1.x * up * uL[cw.y & 0x7fffu]; a1.x = 0.0; }
+                    if (hit & 8u) { off2 += a1.y * up * uL[(cw.y >> 16) & 0x7fffu]; a1.y = 0.0; }
+                }
+                *reinterpret_cast<double2*>(vm + v0) = a0; *reinterpret_cast<double2*>(vm + v1) = a1;
+            } else if (hit) {
+                const double up = uL[p];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!(hit & (1u << j))) continue;
+                    const uint32_t c = ((j < 2 ? cw.x : cw.y) >> (16 * (j & 1))) & 0x7fffu;
+                    const size_t at = (j < 2 ? v0 : v1) + (size_t)(j & 1);
+                    off2 += vo[at] * up * uL[c];
+                    if (R.maskMode == 2) vm[at] = 0.0;
+                }
+            }
+        }
+        num += 2.0 * off2;
+    }
+    for (int off = 32; off > 0; off >>= 1) { num += __shfl_xor(num, off); den += __shfl_xor(den, off); }
+    if (lane == 0) { red[2 * w] = num; red[2 * w + 1] = den; }
+    __syncthreads();
+    // record
+    const int64_t o = (int64_t)b * R.K + R.r;
+    const int n = min(max(R.n_assoc[b], 0), R.kmax);
+    for (int t = tid; t < 2 * n; t += MNO_NT) R.assoc_out[o * R.kmax * 2 + t] = R.assoc[(int64_t)b * R.kmax * 2 + t];
+    if (tid < 16) R.sol_out[o].T[tid] = R.T[(int64_t)b * 16 + tid];
+    if (tid == 0) {
+        double sn = 0.0, sd = 0.0;
+        for (int i = 0; i < NWV; ++i) { sn += red[2 * i]; sd += red[2 * i + 1]; }
+        R.sol_out[o].n_assoc = n; R.sol_out[o].status = R.status[b];
+        R.sol_out[o].score = (nsel > 0 && sd > 0.0) ? sn / sd : 0.0;
+        if (R.stats_out) R.stats_out[o] = R.stats[b];
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -84,6 +84,8 @@ struct roman_ctx {
         DevBuf hFeats, hAssoc, hU0, oAssoc, oN, oT, oStatus, oStats, hAux1, hAux2, hAux3;
         DevBuf oAll;                           // outputs of a host-output batch call as ONE block (T | stats | assoc | n | status [| records | accepted | count]): one copy brings it back
         DevBuf lcStage;                        // inputs of the loop-closure tail of roman_align_lc_batch (T_ref | FL | FR | enable | iL | iR)
+        DevBuf mnoVals, mnoOut;                // roman_mno_batch*: the masked copy of the matrix values; the solver's per-round block (T | stats | assoc | n | status)
+        DevBuf mnoHost;                        // roman_mno_batch (host pointers): the three output arrays on the device
         // totals of the most recent batch on this workspace, copied back without waiting
         BatchTotals* pinnedTotals = nullptr;
         ProbDesc* pinnedProbs = nullptr; size_t pinnedProbsCap = 0;   // staging of the problem descriptors (truly asynchronous upload)
@@ -326,7 +328,7 @@ void estimate_sizes(roman_ctx* c, const DevParams& D, const roman_params_t* para
         ++c->histEpoch;                                         // totals still in flight belong to the old block: harvest_totals drops them
     }
     harvest_totals(c, false);
-    const bool prunes = D.single && !D.keep_all;              // single scores can remove associations: L <= A, else L == A
+    const bool prunes = D.single && !D.keep_all && !D.plain_all;   // single scores can remove associations: L <= A, else L == A
     double heurMask = 0, heurNnz = 0; int heurMaxL = 0;
     for (const ProbDesc& d : hd) {
         const double nA = d.nA;
@@ -516,7 +518,7 @@ static hipError_t launch_cos(roman_ctx* c, hipStream_t stream, const DevParams& 
 // and pass the rest of the sequence by.  The stepwise entry points (roman_score, then roman_solve / the export calls) keep
 // the general layout for every problem.
 int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* params, const BatchIn& in, std::vector<ProbDesc>& hd, DevParams* Dout,
-                  const BatchOut* smallOut = nullptr, const double* smallU0 = nullptr)
+                  const BatchOut* smallOut = nullptr, const double* smallU0 = nullptr, bool mno = false /* roman_mno_batch*: every problem in the stream layout */)
 {
     const int B = in.B;
     hd.assign(B, ProbDesc{});
@@ -567,6 +569,10 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     // problem that turns out too large for the LDS tiles of this launch is skipped (ROMAN_ST_WORKSPACE) and, the
     // history corrected, takes them on its second run.
     D.allow_fallback = (!c->hist.valid || SZ.expectMaxL > D.stream_maxL || D.p.maxiniters < 1 || D.p.maxlsiters < 1) ? 1 : 0;
+    if (mno) {                                             // the mask rewrites the stream layout's values: every problem takes it (the caller has checked the list lengths)
+        D.stream_maxL = std::min(STREAM_MAXL, std::max(64, (maxA + 63) & ~63));
+        D.allow_fallback = 0;
+    }
     {   // Which solver takes the fallback problems: few (large) ones -> k_solve_wide, every compute unit on one problem at a
         // time; many -> k_solve, one workgroup per problem.  Decided here because the fill writes 16-bit column labels for
         // the wide solver when every position fits (10 instead of 12 bytes per entry of the stream it is bound by).
@@ -638,7 +644,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
         ++(cosScreen ? c->cosScreenBatches : c->cosDenseBatches);
         if (cosScreen) {
             HIPCHK(c, WS.cosDense.ensure(sizeof(int32_t) * (size_t)B));
-            cosLive = allToAll && !D.keep_all;
+            cosLive = allToAll && !D.keep_all && !D.plain_all;
             if (cosLive)
                 HIPCHK(c, launch_cos_live(c, WS.stream, D, B, maxN1, maxN2, dP, in.feats, WS.cosPool.as<double>(), WS.cosDense.as<int32_t>(), dS, LP));
             else
@@ -1473,7 +1479,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
                          &W.lp, &W.li, &W.lj, &W.ls, &W.ld, &W.lza, &W.lzb, &W.plp, &W.pli, &W.plj, &W.pls, &W.pld, &W.plza, &W.plzb,
                          &W.rowCnt, &W.rowPos, &W.perm, &W.sliceWidth, &W.sliceBase, &W.items, &W.maskPool, &W.prefPool, &W.listPool, &W.listOff,
                          &W.vMu, &W.vCu, &W.vMun, &W.vCun, &W.gU, &W.gUn, &W.uOut, &W.nodesOrig, &W.nSel, &W.widePart, &W.wideSlots, &W.wideBar, &W.wideBm, &W.wideY, &W.wideUp, &W.fbList, &W.cols16, &W.cols32, &W.vals, &W.colsC, &W.valsC, &W.contSpill, &W.contList,
-                         &W.hFeats, &W.hAssoc, &W.hU0, &W.oAssoc, &W.oN, &W.oT, &W.oStatus, &W.oStats, &W.hAux1, &W.hAux2, &W.hAux3, &W.oAll, &W.lcStage};
+                         &W.hFeats, &W.hAssoc, &W.hU0, &W.oAssoc, &W.oN, &W.oT, &W.oStatus, &W.oStats, &W.hAux1, &W.hAux2, &W.hAux3, &W.oAll, &W.lcStage, &W.mnoVals, &W.mnoOut, &W.mnoHost};
         for (DevBuf* b : all) b->release();
         if (W.pinnedTotals) (void)hipHostFree(W.pinnedTotals);
         if (W.totEvent) (void)hipEventDestroy(W.totEvent);
@@ -2098,6 +2104,203 @@ int roman_align_batch_resident(roman_ctx_t* c, const roman_params_t* params, int
     if (rc) return rc;
     const BatchIn in{B, feats, off1, n1, off2, n2, F, assoc, assoc_off};
     return align_to_host(c, D, params, in, u0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out);
+}
+
+// --- multi-solution extraction, batched ([REF roman/align/object_registration.py:57-86]) ------------------------------------------
+// The rounds of one call on workspace c->cur and its stream (pure enqueue): the batch is scored once into the stream layout as the
+// plain-CLIPPER view (every input association a node, unit diagonal), then per round the stream solver runs on the current values
+// and k_mno_round scores the selection on the unmasked values, files the solution and zeroes the selected block in the copy the
+// next solve reads (WS.vals stays as scored; WS.mnoVals is the masked copy, made by the first round's pass).
+static int run_mno(roman_ctx* c, const DevParams& D0, const roman_params_t* params, const BatchIn& in, int32_t K, int32_t kmax,
+                   int32_t* assoc_out, roman_mno_solution_t* sol_out, roman_stats_t* stats_out)
+{
+    const int B = in.B;
+    DevParams Dv = D0;
+    const int diagOne = (!D0.single || D0.diag_one) ? 1 : 0;    // the diagonal of M as exported: 1, or the single scores (k_live leaves them in ls)
+    if (Dv.single && !Dv.pruned) { Dv.plain_all = 1; Dv.diag_one = 1; }   // (the pruned prefilter's survivors ARE the list clipperpy is handed: already plain)
+    // the view's pools are sized by a history of its own: tagged with a parameter block no caller can pass (reserved != 0)
+    roman_params_t tag = *params; tag.reserved = 0x4d4e4f;
+    std::vector<ProbDesc> hd;
+    DevParams D;
+    int rc = enqueue_score(c, Dv, &tag, in, hd, &D, nullptr, nullptr, true);
+    if (rc) return rc;
+    int64_t sumA = 0, maxA = 0; for (const ProbDesc& d : hd) { sumA += d.nA; maxA = std::max<int64_t>(maxA, d.nA); }
+    // the solver's block of one round: T | stats | assoc | n | status
+    const size_t kb = (size_t)B * (size_t)std::max(kmax, 1);
+    const size_t oT = 0, oS = oT + sizeof(double) * 16 * (size_t)B, oA = oS + sizeof(roman_stats_t) * (size_t)B,
+                 oNn = oA + sizeof(int32_t) * 2 * kb, oSt = oNn + sizeof(int32_t) * (size_t)B, total = oSt + sizeof(int32_t) * (size_t)B;
+    HIPCHK(c, WS.mnoOut.ensure(total));
+    if (K > 1) HIPCHK(c, WS.mnoVals.ensure(sizeof(double) * (size_t)std::max<long long>(WS.capNnz, 1)));
+    char* const dev = WS.mnoOut.as<char>();
+    const BatchOut out{kmax, reinterpret_cast<int32_t*>(dev + oA), reinterpret_cast<int32_t*>(dev + oNn), reinterpret_cast<double*>(dev + oT),
+                       reinterpret_cast<int32_t*>(dev + oSt), reinterpret_cast<roman_stats_t*>(dev + oS)};
+    for (int r = 0; r < K && !rc; ++r) {
+        if (r > 0) std::swap(WS.vals, WS.mnoVals);              // this round's solve reads the masked copy
+        rc = enqueue_solve(c, D, B, sumA, maxA, in.feats, in.assoc, nullptr, false, 0, out);
+        if (r > 0) std::swap(WS.vals, WS.mnoVals);
+        if (rc) break;
+        MnoRound R;
+        R.n_assoc = out.n_assoc_out; R.status = out.status_out; R.T = out.T_out; R.stats = out.stats_out; R.assoc = out.assoc_out;
+        R.assoc_out = assoc_out; R.sol_out = sol_out; R.stats_out = stats_out;
+        R.K = K; R.r = r; R.kmax = kmax; R.maskMode = (r + 1 >= K) ? 0 : (r == 0 ? 1 : 2); R.diagOne = diagOne;
+        hipLaunchKernelGGL(k_mno_round, dim3((unsigned)B), dim3(MNO_NT), 0, WS.stream, B, R, WS.probs.as<ProbDesc>(), WS.state.as<ProbState>(),
+                           WS.lp.as<int32_t>(), WS.ls.as<double>(), WS.rowPos.as<uint32_t>(), WS.sliceBase.as<uint32_t>(), WS.cols16.as<uint16_t>(),
+                           WS.vals.as<double>(), K > 1 ? WS.mnoVals.as<double>() : (double*)nullptr,
+                           WS.nodesOrig.as<int32_t>(), WS.nSel.as<int32_t>(), WS.uOut.as<double>());
+        HIPCHK(c, hipGetLastError());
+        DBG(c, "k_mno_round");
+    }
+    return rc;
+}
+
+static int mno_check(roman_ctx* c, const roman_params_t* params, int32_t B, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                     const int32_t* assoc, const int64_t* assoc_off, int32_t K, int32_t kmax, const void* assoc_out, const void* sol_out)
+{
+    if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
+    if (K < 1 || K > ROMAN_MNO_MAX_SOLUTIONS) return fail(c, ROMAN_E_INVALID, "num_solutions must be 1..%d (got %d)", ROMAN_MNO_MAX_SOLUTIONS, K);
+    if (B == 0) return ROMAN_OK;
+    if (!params) return fail(c, ROMAN_E_INVALID, "params is NULL");
+    if (!off1 || !n1 || !off2 || !n2 || !assoc_out || !sol_out || kmax < 0) return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer or kmax < 0");
+    if (assoc && !assoc_off) return fail(c, ROMAN_E_INVALID, "assoc given without assoc_off");
+    if (params->maxiniters < 1 || params->maxlsiters < 1) return fail(c, ROMAN_E_UNSUPPORTED, "roman_mno_batch needs maxiniters >= 1 and maxlsiters >= 1");
+    for (int b = 0; b < B; ++b) {
+        if (n1[b] < 0 || n2[b] < 0) return fail(c, ROMAN_E_INVALID, "negative map size in problem %d", b);
+        const int64_t nl = assoc ? assoc_off[b + 1] - assoc_off[b] : 0;
+        const int64_t na = nl > 0 ? nl : (int64_t)n1[b] * n2[b];
+        if (na > ROMAN_MNO_MAX_ASSOC) return fail(c, ROMAN_E_TOO_LARGE, "problem %d has %lld associations; roman_mno_batch serves at most %d per problem", b, (long long)na, ROMAN_MNO_MAX_ASSOC);
+    }
+    return ROMAN_OK;
+}
+
+int roman_mno_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                        const double* feats, const int64_t* off1, const int32_t* n1,
+                        const int64_t* off2, const int32_t* n2, int32_t F,
+                        const int32_t* assoc, const int64_t* assoc_off,
+                        int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                        roman_mno_solution_t* sol_out, roman_stats_t* stats_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = mno_check(c, params, B, off1, n1, off2, n2, assoc, assoc_off, num_solutions, kmax, assoc_out, sol_out);
+    if (rc || B == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevParams D;
+    rc = make_dev_params(c, params, F, &D);
+    if (rc) return rc;
+    if (!feats) {
+        bool any = false;
+        for (int b = 0; b < B; ++b) any = any || (n1[b] > 0 || n2[b] > 0);
+        if (any) return fail(c, ROMAN_E_INVALID, "feats is NULL");
+    }
+    static_assert(STREAM_MAXL == ROMAN_MNO_MAX_ASSOC, "the documented cap is the stream layout's");
+    const BatchIn in{B, feats, off1, n1, off2, n2, F, assoc, assoc_off};
+    c->last.scored = false; c->last.solved = false;            // workspace 0 is reused: the stepwise problem it held is gone
+    if (c->pipeline >= 2) {                                     // the workspace rotation of roman_align_batch_dev
+        const int k = c->next_ws;
+        c->next_ws = (c->next_ws + 1) % c->pipeline; c->latest_ws = k;
+        HIPCHK(c, hipEventRecord(c->evIn, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->istream[k], c->evIn, 0));
+        c->cur = k; c->ws[k].stream = c->istream[k];
+        rc = run_mno(c, D, params, in, num_solutions, kmax, assoc_out, sol_out, stats_out);
+        if (!rc) {
+            HIPCHK(c, hipEventRecord(c->ws[k].done, c->ws[k].stream));
+            c->ws[k].issued = true;
+        }
+        c->cur = 0;
+        return rc;
+    }
+    c->cur = 0; WS.stream = c->stream;
+    return run_mno(c, D, params, in, num_solutions, kmax, assoc_out, sol_out, stats_out);
+}
+
+int roman_mno_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                    const double* feats, int64_t n_objects,
+                    const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
+                    const int32_t* assoc, const int64_t* assoc_off,
+                    int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                    roman_mno_solution_t* sol_out, roman_stats_t* stats_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (n_objects < 0 || F < 0) return fail(c, ROMAN_E_INVALID, "negative size");
+    if (B > 0 && assoc && assoc_off && assoc_off[0] != 0) return fail(c, ROMAN_E_INVALID, "assoc_off[0] must be 0");
+    if (B > 0 && assoc && assoc_off)
+        for (int b = 0; b < B; ++b) if (assoc_off[b + 1] < assoc_off[b]) return fail(c, ROMAN_E_INVALID, "assoc_off is not non-decreasing at problem %d", b);
+    int rc = mno_check(c, params, B, off1, n1, off2, n2, assoc, assoc_off, num_solutions, kmax, assoc_out, sol_out);
+    if (rc || B == 0) return rc;
+    const int K = num_solutions;
+    for (int b = 0; b < B; ++b) {
+        if (off1[b] < 0 || off2[b] < 0 || off1[b] + n1[b] > n_objects || off2[b] + n2[b] > n_objects)
+            return fail(c, ROMAN_E_INVALID, "problem %d reads objects outside feats[0..%lld)", b, (long long)n_objects);
+        if (assoc)
+            for (int64_t k = assoc_off[b]; k < assoc_off[b + 1]; ++k)
+                if (assoc[2 * k] < 0 || assoc[2 * k] >= n1[b] || assoc[2 * k + 1] < 0 || assoc[2 * k + 1] >= n2[b])
+                    return fail(c, ROMAN_E_INVALID, "problem %d: association %lld = (%d,%d) out of range", b, (long long)(k - assoc_off[b]), assoc[2 * k], assoc[2 * k + 1]);
+    }
+    if (!feats && n_objects * F > 0) return fail(c, ROMAN_E_INVALID, "feats is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    { DevParams Dchk; rc = make_dev_params(c, params, F, &Dchk); if (rc) return rc; }
+    HIPCHK(c, WS.hFeats.ensure(sizeof(double) * (size_t)std::max<int64_t>(n_objects * F, 1)));
+    if (n_objects * F > 0) HIPCHK(c, hipMemcpyAsync(WS.hFeats.p, feats, sizeof(double) * (size_t)(n_objects * F), hipMemcpyHostToDevice, WS.stream));
+    const int32_t* dA = nullptr;
+    if (assoc) {
+        const int64_t rows = assoc_off[B];
+        HIPCHK(c, WS.hAssoc.ensure(sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(rows, 1)));
+        if (rows > 0) HIPCHK(c, hipMemcpyAsync(WS.hAssoc.p, assoc, sizeof(int32_t) * 2 * (size_t)rows, hipMemcpyHostToDevice, WS.stream));
+        dA = WS.hAssoc.as<int32_t>();
+    }
+    // outputs on the device: solutions | statistics | association rows
+    const size_t nSol = (size_t)B * (size_t)K, rowsPer = (size_t)std::max(kmax, 0) * 2;
+    const size_t oSol = 0, oStats = oSol + sizeof(roman_mno_solution_t) * nSol, oAssoc = oStats + sizeof(roman_stats_t) * nSol,
+                 total = oAssoc + sizeof(int32_t) * nSol * std::max<size_t>(rowsPer, 1);
+    static_assert(sizeof(roman_mno_solution_t) % 8 == 0 && sizeof(roman_stats_t) % 8 == 0, "the blocks stay 8-byte aligned");
+    HIPCHK(c, WS.mnoHost.ensure(total));
+    char* const dev = WS.mnoHost.as<char>();
+    roman_mno_solution_t* dSol = reinterpret_cast<roman_mno_solution_t*>(dev + oSol);
+    roman_stats_t* dStats = reinterpret_cast<roman_stats_t*>(dev + oStats);
+    int32_t* dAssoc = reinterpret_cast<int32_t*>(dev + oAssoc);
+    const double* dFeats = WS.hFeats.as<double>();
+    // calls of host_chunk problems, host_depth of them in flight; skipped problems are issued again, those only
+    const int chunk = std::max(1, c->host_chunk), saved = c->pipeline;
+    const int depth = B > chunk ? c->host_depth : 1;
+    rc = roman_ctx_set_pipeline(c, depth);
+    if (rc) return rc;
+    auto restore = [&](int code) -> int { const int r2 = roman_ctx_set_pipeline(c, saved); c->cur = 0; c->ws[0].stream = c->stream; return code ? code : r2; };
+    auto issue = [&](int lo, int hi) -> int {
+        return roman_mno_batch_dev(c, params, hi - lo, dFeats, off1 + lo, n1 + lo, off2 + lo, n2 + lo, F, dA, dA ? assoc_off + lo : nullptr, K, kmax,
+                                   dAssoc + (size_t)lo * (size_t)K * rowsPer, dSol + (size_t)lo * (size_t)K, dStats + (size_t)lo * (size_t)K);
+    };
+    int lo = 0;
+    if (depth >= 2) {                                           // the first call alone: the calls behind it size their pools from what it needed
+        rc = issue(0, std::min(B, chunk));
+        if (!rc) rc = roman_ctx_sync(c);
+        if (rc) return restore(rc);
+        harvest_totals(c, true);
+        lo = std::min(B, chunk);
+    }
+    for (; lo < B; lo += chunk) { rc = issue(lo, std::min(B, lo + chunk)); if (rc) return restore(rc); }
+    std::vector<roman_mno_solution_t> hs(nSol);
+    for (int attempt = 1; ; ++attempt) {
+        rc = roman_ctx_sync(c);
+        if (rc) return restore(rc);
+        harvest_totals(c, true);
+        if (hipMemcpy(hs.data(), dSol, sizeof(roman_mno_solution_t) * nSol, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return restore(fail(c, ROMAN_E_HIP, "solution read-back failed")); }
+        int nskip = 0;
+        for (int b = 0; b < B; ++b) nskip += (hs[(size_t)b * K].status & ROMAN_ST_WORKSPACE) ? 1 : 0;
+        if (!nskip) break;
+        if (attempt >= MAX_ATTEMPTS) return restore(fail(c, ROMAN_E_NOMEM, "the sparse workspace of %d problem(s) still does not fit after %d attempts", nskip, attempt));
+        for (int b = 0; b < B; ) {
+            if (!(hs[(size_t)b * K].status & ROMAN_ST_WORKSPACE)) { ++b; continue; }
+            int e = b + 1;
+            while (e < B && e - b < chunk && (hs[(size_t)e * K].status & ROMAN_ST_WORKSPACE)) ++e;
+            rc = issue(b, e);
+            if (rc) return restore(rc);
+            b = e;
+        }
+    }
+    memcpy(sol_out, hs.data(), sizeof(roman_mno_solution_t) * nSol);
+    if (stats_out && hipMemcpy(stats_out, dStats, sizeof(roman_stats_t) * nSol, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return restore(fail(c, ROMAN_E_HIP, "statistics read-back failed")); }
+    if (rowsPer && hipMemcpy(assoc_out, dAssoc, sizeof(int32_t) * nSol * rowsPer, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return restore(fail(c, ROMAN_E_HIP, "association read-back failed")); }
+    return restore(ROMAN_OK);
 }
 
 // --- the deal of a batch over ranks (pure host function; roman_amd.align.distributed.deal_by_cost states the same) ------------

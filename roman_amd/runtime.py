@@ -82,6 +82,21 @@ class LcInputs:
         return T_ref, enable, FL, iL, FR, iR
 
 
+def mno_solution_dtype():
+    """roman_mno_solution_t as a structured dtype."""
+    return np.dtype([("n_assoc", np.int32), ("status", np.int32), ("score", np.float64), ("T", np.float64, (16,))])
+
+
+@dataclass
+class MnoResult:
+    """Results of one batched multi-solution call: K solutions per problem."""
+    assoc: list            # assoc[b][k]: (n, 2) int32 array of solution k of problem b, clipperpy order
+    score: np.ndarray      # (B, K) float64 Rayleigh quotient on the unmasked M (0 for an empty selection)
+    T: np.ndarray          # (B, K, dim+1, dim+1) float64, NaN where status has INSUFFICIENT / EMPTY_MAP
+    status: np.ndarray     # (B, K) int32 ROMAN_ST_* flags
+    stats: np.ndarray      # (B, K) structured array (stats_dtype): the statistics of every solve
+
+
 @dataclass
 class LoopClosureResult(BatchResult):
     """A batch result with the loop-closure tail behind it."""
@@ -266,6 +281,50 @@ class Context:
                                              vp(u0_ptr), int(kmax), vp(assoc_out_ptr), vp(n_assoc_out_ptr),
                                              vp(T_out_ptr), vp(status_out_ptr), vp(stats_out_ptr))
         self._check(rc, "roman_align_batch_dev")
+
+    # ------------------------------------------------------------------ multi-solution extraction
+    def mno_batch(self, params, feats, off1, n1, off2, n2, num_solutions=2, assoc=None, assoc_off=None, kmax=None):
+        """Host-pointer batched mno_clipper (roman_mno_batch): `num_solutions` plain-CLIPPER solves per problem with the
+        selected block of M zeroed between them, all on the device.  feats: (n_objects, F) float64.  -> MnoResult."""
+        feats = _f64(feats)
+        if feats.ndim != 2:
+            raise ValueError("feats must be (n_objects, F)")
+        n_obj, F = feats.shape
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        B, K = int(n1.shape[0]), int(num_solutions)
+        if assoc is not None:
+            assoc = np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2)
+            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        if kmax is None:
+            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
+        Kc = max(K, 0)
+        a_out = np.zeros((B, Kc, kmax, 2), dtype=np.int32)
+        sol = np.zeros((B, Kc), dtype=mno_solution_dtype())
+        stats = np.zeros((B, Kc), dtype=stats_dtype())
+        assert sol.dtype.itemsize == _abi.MNO_SOLUTION_NBYTES
+        self._generation += 1
+        rc = self._lib.roman_mno_batch(self._h, C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
+                                       _ptr(assoc), _ptr(assoc_off), K, int(kmax), _ptr(a_out), _ptr(sol), _ptr(stats))
+        self._check(rc, "roman_mno_batch")
+        s = params.point_dim + 1
+        return MnoResult([[a_out[b, k, :sol["n_assoc"][b, k]].copy() for k in range(K)] for b in range(B)],
+                         sol["score"].copy(), sol["T"][:, :, :s * s].reshape(B, K, s, s).copy(), sol["status"].copy(), stats)
+
+    def mno_batch_dev(self, params, feats_ptr, F, off1, n1, off2, n2, num_solutions, kmax, assoc_out_ptr, sol_out_ptr,
+                      stats_out_ptr=None, assoc_ptr=None, assoc_off=None):
+        """Device-pointer batched mno_clipper (roman_mno_batch_dev): pointers are integers, metadata arrays host NumPy arrays.
+        A pure enqueue; skipped problems carry ROMAN_ST_WORKSPACE on every solution (issue them again)."""
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        if assoc_off is not None:
+            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        self._generation += 1
+        rc = self._lib.roman_mno_batch_dev(self._h, C.byref(params), int(n1.shape[0]), vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                           int(F), vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax), vp(assoc_out_ptr),
+                                           vp(sol_out_ptr), vp(stats_out_ptr))
+        self._check(rc, "roman_mno_batch_dev")
 
     # ------------------------------------------------------------------ loop closures
     def align_lc_batch(self, params, feats, off1, n1, off2, n2, lc, assoc=None, assoc_off=None, u0=None, kmax=None):
