@@ -1,7 +1,7 @@
 // kernels.hip.h — gfx950 (CDNA4, wave64) device code of libroman_hip.so.
 //
 // Pipeline for a batch of B independent submap pairs (one "problem" each):
-//   k_cos        normalised cosine matrix (+ descriptor norms), f64 MFMA 16x16x4   (cos_feature_dim > 0)
+//   k_cos_*      normalised cosine matrix (+ descriptor norms), f64 MFMA 16x16x4   (cos_feature_dim > 0)
 //   k_tables     intra-map distance tables with NaN sentinels      (n1^2 + n2^2 entries)
 //   k_live       single scores + ordered compaction of live associations; picks the problem's KIND
 //   k_rowbase / k_items   prefix of live counts over problems, work-item list
@@ -60,8 +60,6 @@ struct DevParams {
                              // SKIPPED (kind 2, ROMAN_ST_WORKSPACE) and runs again with them (set per launch, from the sizing history)
     int32_t wide;            // fallback problems of this launch go to k_solve_wide (few, large) instead of k_solve (set per launch)
     int32_t idx16;           // ... and their column labels are 16 bits wide (no C flag; 0xffff = inert): 10 instead of 12 bytes per entry
-    int32_t solve_flags;     // experiments: bit 0 = the one-wave solver keeps the quad stream (no coordinate list in registers); bit 1 = k_fill_list does NOT rotate
-                             // the entries of a row (the rotation decorrelates the lanes' LDS pushes in the solver)
     int32_t small_only;      // the general kernels are NOT part of this launch (every problem of this parameter block has so far been finished by
                              // k_small): a problem k_small leaves behind is skipped (kind 2, ROMAN_ST_WORKSPACE) and takes them on its second run
     int32_t stream_maxL;     // problems of up to this many live associations take the stream layout (<= STREAM_MAXL; set per launch:
@@ -279,118 +277,17 @@ __device__ __forceinline__ double fuse_pair(const DevParams& D, double sa, doubl
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_cos: cos[i][j] = <d1_i, d2_j> / (|d1_i| |d2_j|) on the f64 matrix core (v_mfma_f64_16x16x4_f64).
-// One wave owns a 32x32 output tile (2x2 MFMA tiles).  Operand layout of one MFMA: lane l supplies
-// A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15]; result reg r of lane l is C[row = (l>>4) + 4r][col = l&15].
-// Per 16 descriptor elements a lane loads 4 CONSECUTIVE doubles of each of its 2+2 rows (32-byte
-// loads) and feeds element t of every load to MFMA t: MFMA t contracts k = k0 + 4*(l>>4) + t — any
-// bijection k <-> (MFMA, l>>4) is a valid contraction order as long as A and B use the same one.
-// 16 MFMAs per 4 wide loads (the previous 16x16 tile issued 1 MFMA per 2 scalar loads).
+// The cosine kernels: cos[i][j] = <d1_i, d2_j> / (|d1_i| |d2_j|) on the f64 matrix core (v_mfma_f64_16x16x4_f64).
+// Operand layout of one MFMA: lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15]; result reg r of lane l is
+// C[row = (l>>4) + 4r][col = l&15].  Per 16 descriptor elements a lane holds 4 CONSECUTIVE doubles of each of its rows and
+// feeds element t of them to MFMA t: MFMA t contracts k = k0 + 4*(l>>4) + t — any bijection k <-> (MFMA, l>>4) is a valid
+// contraction order as long as A and B use the same one.  Every kernel below keeps this one order (chunks of 16 ascending,
+// then t = 0..3) and the same order of the norm sums — "k_cos's own" in their comments, after the first kernel that had it
+// (one 32x32 tile per wave, operands from global memory; retired: DESIGN.md) — so all of them give identical bits.
 // ---------------------------------------------------------------------------------------------
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef double dbl2_t __attribute__((ext_vector_type(2)));
 struct __attribute__((packed, aligned(8))) d4u_t { double v[4]; };     // 8-byte aligned 32-byte load
-
-constexpr int COS_TILE = 32;
-
-__global__ void __launch_bounds__(256) k_cos(DevParams D, int B, int G /* workgroups (4 tiles each) per problem */,
-                                             const ProbDesc* __restrict__ probs,
-                                             const double* __restrict__ feats,
-                                             double* __restrict__ cosPool)
-{
-    // Workgroups are dealt to the 8 XCDs round-robin by linear id.  All G workgroups of a problem get ids that are
-    // congruent modulo 8, i.e. one XCD and one L2: the descriptors of a problem are read from HBM once instead
-    // of once per XCD (8 problems are interleaved: id = 8 * (G * (b / 8) + g) + b % 8).
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int b = (slot / G) * 8 + xcd;
-    if (b >= B) return;
-    const ProbDesc pd = probs[b];
-    const int tj_n = (pd.n2 + COS_TILE - 1) / COS_TILE, ti_n = (pd.n1 + COS_TILE - 1) / COS_TILE;
-    const int tile = (slot % G) * 4 + (threadIdx.x >> 6);
-    if (tile >= ti_n * tj_n) return;
-    const int lane = threadIdx.x & 63;
-    const int i0 = (tile / tj_n) * COS_TILE, j0 = (tile % tj_n) * COS_TILE;
-    const int Fc = D.p.cos_feature_dim, coff = D.p.point_dim + D.p.ratio_feature_dim;
-    const int lr = lane & 15, kq = lane >> 4;
-    const double* fa[2]; const double* fb[2]; bool va[2], vb[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int ia = i0 + 16 * h + lr, jb = j0 + 16 * h + lr;
-        va[h] = ia < pd.n1; vb[h] = jb < pd.n2;
-        fa[h] = feats + (pd.off1 + (va[h] ? ia : 0)) * D.F + coff + 4 * kq;
-        fb[h] = feats + (pd.off2 + (vb[h] ? jb : 0)) * D.F + coff + 4 * kq;
-    }
-    // A map of 200 objects ends 8 rows into its last 32-row tile: the second 16-row block of that tile holds no object at
-    // all.  Such blocks are skipped (wave-uniform: loads and MFMAs): 13 instead of 14 blocks per dimension at n = 200.
-    const bool on[2][2] = {{true, uni_i(j0 + 16 < pd.n2) != 0}, {uni_i(i0 + 16 < pd.n1) != 0, uni_i(i0 + 16 < pd.n1) != 0 && uni_i(j0 + 16 < pd.n2) != 0}};
-    const bool onA1 = on[1][0], onB1 = on[0][1];
-    double4_t acc[2][2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) acc[x][y] = double4_t{0.0, 0.0, 0.0, 0.0};
-    // squared norms of the tile's 32 + 32 descriptors ride along on the VALU (the operands are in registers
-    // anyway): lane (lr, kq) accumulates the elements it holds, the four kq-lanes of a row are added at the end
-    double sa[2] = {0.0, 0.0}, sb[2] = {0.0, 0.0};
-    int k0 = 0;
-    for (; k0 + 16 <= Fc; k0 += 16) {
-        d4u_t a[2], b[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            if (h == 0 || onA1) a[h] = *reinterpret_cast<const d4u_t*>(fa[h] + k0); else a[h] = d4u_t{{0.0, 0.0, 0.0, 0.0}};
-            if (h == 0 || onB1) b[h] = *reinterpret_cast<const d4u_t*>(fb[h] + k0); else b[h] = d4u_t{{0.0, 0.0, 0.0, 0.0}};
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) { sa[h] = fma(a[h].v[t], a[h].v[t], sa[h]); sb[h] = fma(b[h].v[t], b[h].v[t], sb[h]); }
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < 2; ++y)
-                    if (on[x][y]) acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[x] ? a[x].v[t] : 0.0, vb[y] ? b[y].v[t] : 0.0, acc[x][y], 0, 0, 0);
-        }
-    }
-    if (k0 < Fc) {                                   // ragged tail of the descriptor (< 16 elements)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int kk = k0 + 4 * kq + t;
-            const bool vk = kk < Fc;
-            double av[2], bv[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                av[h] = (va[h] && vk) ? fa[h][k0 + t] : 0.0;
-                bv[h] = (vb[h] && vk) ? fb[h][k0 + t] : 0.0;
-                sa[h] = fma(av[h], av[h], sa[h]); sb[h] = fma(bv[h], bv[h], sb[h]);
-            }
-#pragma unroll
-            for (int x = 0; x < 2; ++x)
-#pragma unroll
-                for (int y = 0; y < 2; ++y)
-                    if (on[x][y]) acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[x], bv[y], acc[x][y], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {                    // every lane (lr, *) ends with the norm of row 16h + lr
-        sa[h] += __shfl_xor(sa[h], 16); sa[h] += __shfl_xor(sa[h], 32);
-        sb[h] += __shfl_xor(sb[h], 16); sb[h] += __shfl_xor(sb[h], 32);
-        sa[h] = sqrt(sa[h]); sb[h] = sqrt(sb[h]);
-    }
-#pragma unroll
-    for (int y = 0; y < 2; ++y) {
-        const int col = j0 + 16 * y + lr;
-        const double nb = sb[y];
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = i0 + 16 * x + kq + 4 * r;
-                const double na = __shfl(sa[x], kq + 4 * r);       // norm of row 16x + (kq + 4r): held by lanes with lr == kq + 4r
-                if (row < pd.n1 && col < pd.n2)
-                    cosPool[pd.cosOff + (int64_t)row * pd.n2 + col] = D.pruned ? acc[x][y][r] : ((na > 0.0 && nb > 0.0) ? acc[x][y][r] / (na * nb) : 0.0);
-            }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // k_cos_wave: the reference's DEMO scale (submaps of at most 48 objects): ONE WAVE computes a problem's whole cosine matrix —
@@ -587,7 +484,7 @@ __global__ void __launch_bounds__(256) k_cos_block(DevParams D, int B, int nbx, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_cos_tile<KC>: the same products, operands staged through LDS.  A workgroup (4 waves) owns an output tile of up to 64x64,
+// k_cos_tile: the same products, operands staged through LDS.  A workgroup (4 waves) owns an output tile of up to 64x64,
 // wave (wy, wx) the 2x2 MFMA blocks of its quarter.  Per stage of KC descriptor elements the 256 threads copy the tile's
 // row pieces of KC doubles from global memory to LDS with 16-byte loads whose lanes run ALONG a row (SEGS lanes cover one
 // row piece contiguously): every cache line that is touched is used completely, and a row is fetched once per workgroup
@@ -605,20 +502,21 @@ __global__ void __launch_bounds__(256) k_cos_block(DevParams D, int B, int nbx, 
 struct __attribute__((packed, aligned(8))) d2u_t { double v[2]; };      // 8-byte aligned 16-byte load
 
 __device__ __forceinline__ int cos_tiles(int n) { return (((n + 15) >> 4) + 3) >> 2; }            // tiles along a dimension of n rows
+constexpr int COS_KC = 16;                   // descriptor elements per stage of k_cos_tile
 
-template <int KC>
 __global__ void __launch_bounds__(256) k_cos_tile(DevParams D, int B, int G /* workgroups (tiles) per problem */,
                                                   const ProbDesc* __restrict__ probs,
                                                   const double* __restrict__ feats,
                                                   double* __restrict__ cosPool)
 {
+    constexpr int KC = COS_KC;
     constexpr int PITCH = KC * 8 + 16;           // bytes per staged row piece (the 16 spread the rows over the banks)
     constexpr int SEGS = KC / 2;                 // 16-byte segments per row piece
     constexpr int RPI = 256 / SEGS;              // rows per load instruction of the workgroup
     constexpr int NLD = 128 / RPI;               // load instructions per stage and thread (first half: A rows, second half: B rows)
     constexpr int STAGE = 128 * PITCH;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // 2 stages x (64 A rows + 64 B rows) x PITCH
-    // (the grid may be smaller than the number of tiles: the workgroups then loop)
+    // (the grid is rounded up to whole groups of eight problems: slots behind the last tile are passed by)
     const int xcd = blockIdx.x & 7, nSlots = G * ((B + 7) >> 3);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     for (int slot = blockIdx.x >> 3; slot < nSlots; slot += gridDim.x >> 3) {
@@ -796,7 +694,7 @@ __global__ void __launch_bounds__(256) k_cos_tile(DevParams D, int B, int G /* w
 // the norms are summed by a separate pass over the staged rows in the order of k_cos_tile's (lane (lr, kq): its k's ascending,
 // then the two cross-quarter adds) and handed over through LDS.  Identical bits.
 // ---------------------------------------------------------------------------------------------
-constexpr int COSD_PITCH = 16 * 8 + 16;          // bytes per staged row piece (k_cos_tile<16>'s)
+constexpr int COSD_PITCH = 16 * 8 + 16;          // bytes per staged row piece (k_cos_tile's)
 template <int T> struct CosDeal {                // T: blocks per tile and dimension
     static constexpr int ROWS = 2 * 16 * T;      // staged row pieces: A rows 0..16T-1, B rows 16T..32T-1
     static constexpr int STAGE = ROWS * COSD_PITCH;
@@ -1957,10 +1855,7 @@ __device__ __forceinline__ void count_rows_lds(const DevParams& D, const ProbDes
 constexpr int PRE_NR = 4;                 // rows a wave sweeps together (their bins share an LDS word)
 constexpr int PRE_COLPAD = 128;           // sentinel columns behind the column tile (a sweep starts at the rows' own 64-column block and advances by 128)
 constexpr int PRE_QCAP = 640;             // queue entries: the exact gate runs while 256 are waiting; a window's candidates go in at once when they fit (else 64 at a time)
-#ifndef ROMAN_PRE_WAVES
-#define ROMAN_PRE_WAVES 16                // waves per workgroup of the prefiltered sweep (118 registers per lane: no spills; 12 waves measured 7 % slower)
-#endif
-constexpr int PRE_WAVES = ROMAN_PRE_WAVES;
+constexpr int PRE_WAVES = 16;             // waves per workgroup of the prefiltered sweep (118 registers per lane: no spills; 12 waves measured 7 % slower)
 // per-wave LDS of the prefiltered sweep: PRE_NR mask rows (TC / 64 words), the packed bin table (n1 + 1 + n2 entries of 8 bytes, ldsPerRow
 // rounded), the queue (16-bit entries), the rows' own data (4 x 32 bytes)
 __host__ __device__ constexpr int count_pre_wave_bytes(int ldsPerRow, int TC)
@@ -1981,11 +1876,9 @@ __device__ __forceinline__ void count_rows_pre(const DevParams& D, const ProbDes
                                                PreRow* rowinfo,
                                                unsigned long long* __restrict__ mbase,
                                                const double* __restrict__ gZa, const double* __restrict__ gZb,
-                                               uint32_t* degS /* LDS, or NULL: the full degree of every live row, counted as the pairs pass (whole problems only) */,
-                                               const dbl2_t* sO /* LDS: the objects' coordinates, (x, y) (z, -), map 1 at 0, map 2 at NO */, int NO /* 0: the exact gate reads the tables */)
+                                               uint32_t* degS /* LDS, or NULL: the full degree of every live row, counted as the pairs pass (whole problems only) */)
 {
     constexpr int NR = PRE_NR;
-    const bool horiz = D.gmode == 1 || D.gmode == 2;            // the tables hold horizontal distances (k_tables)
     const int W = (L + 63) >> 6;
     const int Lpad = (L + 2 * WAVE - 1) & ~(2 * WAVE - 1);
     const uint32_t K2 = (uint32_t)D.pre_K * 0x00010001u;
@@ -2038,24 +1931,9 @@ __device__ __forceinline__ void count_rows_pre(const DevParams& D, const ProbDes
             const bool act = (int)qq < L;                       // (a sentinel column can only get here through the last bin)
             const uint32_t pk = cIJ[act ? qq : 0u];
             const PreRow* ri = rowinfo + (e[c] >> 14);
-            if (NO > 0) {
-                // the two distances RECOMPUTED from the coordinates in LDS with k_tables' own operation sequence (dx*dx + dy*dy (+ dz*dz), one
-                // correctly rounded sqrt: the same bits, as in k_fill_list), the heights from there too: no request leaves the compute unit
-                // (four L2 gathers per candidate before: 136 M per batch of 256 — the exact gate was a third of a quad's cycles)
-                const dbl2_t oa0 = sO[2 * ri->rowA], oa1 = sO[2 * ri->rowA + 1], ob0 = sO[2 * (NO + ri->rowB)], ob1 = sO[2 * (NO + ri->rowB) + 1];   // (rowA, rowB: the row's OBJECTS here)
-                const uint32_t iq = pk & 0xffffu, jq = (pk >> 16) - (uint32_t)(n1 + 1);
-                const dbl2_t pa0 = sO[2 * iq], pa1 = sO[2 * iq + 1], pb0 = sO[2 * (NO + jq)], pb1 = sO[2 * (NO + jq) + 1];
-                const double dxa = oa0.x - pa0.x, dya = oa0.y - pa0.y, dxb = ob0.x - pb0.x, dyb = ob0.y - pb0.y;
-                const double dza = oa1.x - pa1.x, dzb = ob1.x - pb1.x;
-                const double h2a = dxa * dxa + dya * dya, h2b = dxb * dxb + dyb * dyb;
-                a[c] = horiz ? sqrt(h2a) : sqrt(h2a + dza * dza);
-                bb[c] = horiz ? sqrt(h2b) : sqrt(h2b + dzb * dzb);
-                if (GM) { za[c] = pa1.x; zb[c] = pb1.x; }
-            } else {
             a[c] = TA[ri->rowA + (pk & 0xffffu)];               // (32-bit element offsets: maps of at most 32767 objects take this sweep)
             bb[c] = TB[ri->rowB + (pk >> 16)];                  // (rowB is short of the row's start by n1 + 1: the packed index carries it)
             if (GM) { za[c] = gZa[act ? qq : 0u]; zb[c] = gZb[act ? qq : 0u]; }
-            }
         }
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
@@ -2140,7 +2018,6 @@ __device__ __forceinline__ void count_rows_pre(const DevParams& D, const ProbDes
 #pragma unroll
             for (int x = 1; x < NR; ++x) if (lane == x) { i_ = pi[x]; j_ = pj[x]; }
             PreRow ri; ri.rowA = (uint32_t)i_ * (uint32_t)n1; ri.rowB = (uint32_t)j_ * (uint32_t)n2 - (uint32_t)(n1 + 1);
-            if (NO > 0) { ri.rowA = (uint32_t)i_; ri.rowB = (uint32_t)j_; }
             ri.moff = (uint32_t)lane * (uint32_t)Wcap * 8u; ri.zi = pzi; ri.zj = pzj;
             int kr_ = k[0];
 #pragma unroll
@@ -2278,8 +2155,7 @@ __global__ void __launch_bounds__(PRE ? PRE_WAVES * 64 : 1024) k_count(DevParams
                                                 unsigned long long* __restrict__ maskPool,
                                                 uint32_t* __restrict__ prefPool,
                                                 int TC /* LDS column tile (multiple of 256) */, int ldsPerWave /* doubles: NR table slices */, int RPB,
-                                                const uint16_t* __restrict__ qtabPool /* PRE: the tables as bins (k_tables) */,
-                                                const double* __restrict__ feats, int NO /* PRE: object capacity per map of the coordinate tile in LDS (0: none — the exact gate reads the tables) */)
+                                                const uint16_t* __restrict__ qtabPool /* PRE: the tables as bins (k_tables) */)
 {
     // LDS: [GM: cZZ[TC]] cIJ[TC] | per wave NR table slices (n1 + 1 + n2 doubles each)
     // PRE (NR is ignored: PRE_NR rows per wave; ldsPerWave = entries of the packed bin table): cIJ[TC] | per wave count_pre_wave_bytes()
@@ -2299,9 +2175,6 @@ __global__ void __launch_bounds__(PRE ? PRE_WAVES * 64 : 1024) k_count(DevParams
     uint2* qT = reinterpret_cast<uint2*>(rmask + PRE_NR * (TC >> 6));
     uint16_t* queue = reinterpret_cast<uint16_t*>(qT + ldsPerWave);
     PreRow* rowinfo = reinterpret_cast<PreRow*>(queue + PRE_QCAP);
-    // (PRE) behind the waves' regions: the objects' coordinates of the item's problem, 32 bytes per object
-    const size_t sOoff = ((size_t)(reinterpret_cast<unsigned char*>(cIJ + TC + PRE_COLPAD + 4 + ((PRE && RPB < 0) ? TC : 0)) - smem) + (size_t)wpb * (size_t)preBytes + 15) & ~(size_t)15;
-    dbl2_t* sO = reinterpret_cast<dbl2_t*>(smem + sOoff);
     if (PRE) { for (int x = lane; x < PRE_NR * (TC >> 6); x += WAVE) rmask[x] = 0ull; }
     // PRE with RPB < 0: a work item is a whole PROBLEM (B = -RPB problems; batches with at least a problem per compute unit): the
     // column tile is staged once per problem instead of once per 128 rows, and the rows go to the waves quad by quad
@@ -2337,22 +2210,13 @@ __global__ void __launch_bounds__(PRE ? PRE_WAVES * 64 : 1024) k_count(DevParams
                 cIJ[q] = v ? ((uint32_t)li[lo + q] | ((uint32_t)(pd.n1 + 1 + lj[lo + q]) << 16)) : ((uint32_t)pd.n1 | ((uint32_t)(pd.n1 + 1) << 16));
                 if (GM && !PRE) cZZ[q] = v ? make_double2(lza[lo + q], lzb[lo + q]) : make_double2(0.0, 0.0);
             }
-            if (PRE && NO > 0) {
-                const int pdim = D.p.point_dim;
-                for (int o = tid; o < pd.n1 + pd.n2; o += nt) {
-                    const double* f = feats + (o < pd.n1 ? pd.off1 + o : pd.off2 + (o - pd.n1)) * D.F;
-                    const int slot = o < pd.n1 ? o : NO + (o - pd.n1);
-                    sO[2 * slot] = dbl2_t{f[0], pdim > 1 ? f[1] : 0.0};
-                    sO[2 * slot + 1] = dbl2_t{pdim > 2 ? f[2] : 0.0, 0.0};
-                }
-            }
             if (PRE && tid == 0) *qctr = 0u;
             if (PRE && whole) for (int q = tid; q < L; q += nt) degL[q] = 0u;
             __syncthreads();
             if (PRE) {
                 count_rows_pre<GM>(D, pd, L, it.row0, nrows, qctr, lane, cIJ, TA, TB,
                                    qtabPool + 4 * (int64_t)pd.qtabOff4, qtabPool + 4 * (int64_t)pd.qtabOff4 + (int64_t)pd.n1 * ((pd.n1 + 3) & ~3),
-                                   qT, queue, rmask, TC >> 6, rowinfo, maskPool + mo, lza + lo, lzb + lo, whole ? degL : nullptr, sO, NO);
+                                   qT, queue, rmask, TC >> 6, rowinfo, maskPool + mo, lza + lo, lzb + lo, whole ? degL : nullptr);
                 if (whole) {                                    // the problem's degrees, for k_lists (live order)
                     __syncthreads();
                     for (int q = tid; q < L; q += nt) rowCnt[lo + q] = degL[q];
@@ -3441,6 +3305,8 @@ __device__ __forceinline__ double fill_value(const DevParams& D, double a, doubl
     return fuse_pair(D, sa, sk, sq);
 }
 
+constexpr uint32_t FILL_ROTATE = 5;      // k_fill_list rotates the list quads of row x by FILL_ROTATE * x (why: at the rotation itself)
+
 template <bool GRAV, bool FAST, bool OBJ>
 __global__ void __launch_bounds__(1024) k_fill_list(DevParams D, int B, const ProbDesc* __restrict__ probs,
                                                     ProbState* __restrict__ st, const BatchTotals* __restrict__ tot,
@@ -3543,7 +3409,7 @@ __global__ void __launch_bounds__(1024) k_fill_list(DevParams D, int B, const Pr
             // without a further rotation inside the quad: 1.04-1.06 ms, p50 0.64-0.65 (same boxes, alternating): the plain one stays.
             const uint32_t nq = (cnt + 3u) >> 2;
             uint32_t e0 = g << 2;
-            if (!(D.solve_flags & 2)) { if (g < nq) e0 = ((g + (uint32_t)x * (uint32_t)(D.solve_flags >> 8)) % nq) << 2; }   // (ROMAN_FILL_ROTATE=0 keeps the list order)
+            if (g < nq) e0 = ((g + (uint32_t)x * FILL_ROTATE) % nq) << 2;
             uint2 qq = make_uint2(0u, 0u);
             if (e0 < cnt) qq = *reinterpret_cast<const uint2*>(lists + gOff[x] + e0);
             const int k = (kraw == 0xffffffffu) ? 0 : (int)kraw;
@@ -3718,43 +3584,6 @@ struct SolveOut {           // device pointers of the batch outputs
     double*  uOut;          // row pool: final u over live associations
     unsigned long long* dbg;   // timing build only: 16 counters per problem
 };
-
-// Bounded launches of the stream solver (round 6).  A problem never leaves its workgroup, and a call with more problems than compute
-// units hands them out from a queue: a problem of 400 passes that is claimed late holds its unit long after the others have nothing left
-// to claim.  With a pass budget `cap` a problem that is still iterating after `cap` passes of this launch is SUSPENDED at the top of a
-// pass: its iterate (u, the fused product of u, the vector about to be multiplied: 3 L doubles) and sixteen scalars go to a slot of
-// `spill`, its number to `list`; a second launch of the same kernel (`resume`) picks the suspended problems up — all at once, one
-// workgroup each — and runs them to the end.  The resumed iteration executes the same instructions on the same values (order-free sums,
-// the same thread-to-element mapping, the same reduction trees): identical bits, identical pass counts.  No slot free: the problem
-// simply keeps running.
-struct SolveCont {
-    double*  spill;        // slots * slotDoubles
-    int32_t* list;         // problem number of every used slot
-    int*     counters;     // [0]: slots handed out (may exceed `slots`), [1]: the resume launch's claim counter
-    int32_t  cap;          // passes a problem may run in this launch before it is suspended (0: no limit)
-    int32_t  slots, slotDoubles, maxL;   // a slot: 16 scalars, then u, Wu, x at distances of maxL doubles
-    int32_t  resume;       // this launch takes the suspended problems
-};
-
-// The two copies between a slot and the workgroup's LDS (out of line: the solver's registers are full, and neither belongs in its loop).
-// LDS image: x0 = u, x1 = the fused product of u, x2 = the vector about to be multiplied (L doubles each), sc = the sixteen scalars.
-__device__ __noinline__ void cont_spill(const SolveCont* cont, int slot, int b, int L, const double* x0, const double* x1, const double* x2, const double* sc)
-{
-    double* sp = cont->spill + (size_t)slot * (size_t)cont->slotDoubles;
-    const int Lm = cont->maxL;
-    for (int p = threadIdx.x; p < L; p += blockDim.x) { sp[16 + p] = x0[p]; sp[16 + Lm + p] = x1[p]; sp[16 + 2 * Lm + p] = x2[p]; }
-    if (threadIdx.x < 16) sp[threadIdx.x] = sc[threadIdx.x];
-    if (threadIdx.x == 0) cont->list[slot] = b;
-    __threadfence();                                            // the resume launch (same stream) reads it
-}
-__device__ __noinline__ void cont_load(const SolveCont* cont, int slot, int L, double* x0, double* x1, double* x2, double* sc)
-{
-    const double* sp = cont->spill + (size_t)slot * (size_t)cont->slotDoubles;
-    const int Lm = cont->maxL;
-    for (int p = threadIdx.x; p < L; p += blockDim.x) { x0[p] = sp[16 + p]; x1[p] = sp[16 + Lm + p]; x2[p] = sp[16 + 2 * Lm + p]; }
-    if (threadIdx.x < 16) sc[threadIdx.x] = sp[threadIdx.x];
-    __syncthreads();
-}
 
 // Sum of (a, b) over the block, identical in every thread; fixed reduction tree.  `red` holds two
 // ping-pong scratch areas of 32 doubles (`par` flips on every call), so consecutive reductions need a
@@ -4449,16 +4278,10 @@ __global__ void __launch_bounds__(1024) k_solve(DevParams D, int B, const ProbDe
 // [w T / NW, (w+1) T / NW) with ST_D quads (9 wide loads) in flight per lane, whatever slices the range covers
 // (lane = row slot of the current slice) and flushes its pulled sums when it leaves a slice or its range.
 // ---------------------------------------------------------------------------------------------
-#ifndef ROMAN_SOLVE_WAVES
-#define ROMAN_SOLVE_WAVES 8              // waves of the stream solver's workgroup (one problem per workgroup; measured: 8 beats 16)
-#endif
+constexpr int SOLVE_WAVES = 8;           // waves of the stream solver's workgroup (one problem per workgroup; measured: 8 beats 16, and beats 4)
 constexpr int ST_D = 3;                  // quads in flight per lane
 constexpr int ST_MAXSL = STREAM_MAXL / 64;
 constexpr int SMALL_MAXL = 128;           // live associations the one-wave-per-problem instantiation of k_solve_up takes
-constexpr int LEAN_MAXL = STREAM_MAXL;    // live associations the 128-register instantiation takes (two workgroups per compute unit)
-constexpr int LEAN_D = 2;                 // ... and its quads in flight per lane
-constexpr int DEEP_D = 4;                 // quads in flight per lane of the ROMAN_SOLVE_DEEP=1 instantiation (round 5: four — six no longer fit 256 registers
-                                          // next to the gathers held one quad ahead; measured 0.953-0.961 against 0.941-0.950 ms per launch: no gain)
 constexpr int COO_E = 6;                  // one-wave instantiation: stored pairs a lane holds in registers (coordinate form)
 constexpr int COO_CAP = 64 * COO_E;       // ... per problem; larger matrices take the quad stream
 constexpr uint32_t ST_CZ = 0x8000u, ST_MASK = 0x7fffu;
@@ -4618,8 +4441,7 @@ __device__ __forceinline__ double fx_decode(unsigned long long a, double inv)
     return fma((double)(uint32_t)(a >> 32), 4294967296.0, (double)(uint32_t)a) * inv;
 }
 
-template <int NW, bool HASCZ, int MAXL, int DEPTH = ST_D, bool LEAN = false, bool COOONLY = false /* the matrix is ALWAYS a pre-built coordinate list (k_small): no quad stream in the code */,
-          bool BUDGET = false /* pass budgets / suspended problems (SolveCont): an instantiation of its own — the extra live state cost the default one 4 % */>
+template <int NW, bool HASCZ, int MAXL, bool COOONLY = false /* the matrix is ALWAYS a pre-built coordinate list (k_small): no quad stream in the code */>
 __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbState* st,
                          const double* __restrict__ feats, const int32_t* __restrict__ assoc,
                          const int32_t* __restrict__ plp /* position -> association index */, const int32_t* __restrict__ lpAsc,
@@ -4630,8 +4452,7 @@ __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbStat
                          double* xg /* [Lc] */, unsigned long long* accM /* [Lc] */, unsigned long long* accC /* [Lc] */, int Lc,
                          uint32_t* cumQ /* [ST_MAXSL + 1] */, double* red, int* sint, unsigned char* cooLds /* one-wave instantiation: COO_CAP * 12 bytes */,
                          int cooPre = -1 /* >= 0: cooLds already holds that many entries (k_small); no quad layout exists for the problem */,
-                         int rbPre = -1 /* >= 0: offset of the problem in the row pools (k_small runs before k_rowbase) */,
-                         const SolveCont* cont = nullptr /* pass budget / suspended problems (general instantiation only) */, int resumeSlot = -1)
+                         int rbPre = -1 /* >= 0: offset of the problem in the row pools (k_small runs before k_rowbase) */)
 {
     constexpr int NT = NW * 64;
 #ifdef ROMAN_SOLVE_TIMING
@@ -4726,7 +4547,7 @@ __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbStat
             }
             __syncthreads();
         } else
-        if (!COOONLY && (unsigned long long)st[b].nnzUpper <= (unsigned long long)COO_CAP && nsl <= 2 && !(D.solve_flags & 1)) {
+        if (!COOONLY && (unsigned long long)st[b].nnzUpper <= (unsigned long long)COO_CAP && nsl <= 2) {
             for (uint32_t qq = 0; qq < Tq; ++qq) {
                 const unsigned long long cw = cbase[(size_t)qq * 64];
                 const dbl2_t v0 = vbase[(size_t)(2 * qq) * 64], v1 = vbase[(size_t)(2 * qq + 1) * 64];
@@ -4785,7 +4606,7 @@ __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbStat
         if (de > 0.0) s_ -= (int)((__double_as_longlong(1.0 + de) >> 52) & 0x7ff) - 1023 + 1;
         s_ = s_ > 960 ? 960 : (s_ < -960 ? -960 : s_);
         const double sc = bits_f64((unsigned long long)(1023 + s_) << 52), inv = bits_f64((unsigned long long)(1023 - s_) << 52);
-        // This wave's range of the stream and its first DEPTH quads, requested BEFORE the vector is published: the matrix does
+        // This wave's range of the stream and its first ST_D quads, requested BEFORE the vector is published: the matrix does
         // not depend on x, and a narrow pass is a dozen quads per wave — four or five dependent round trips to the L2 —, so the
         // first of them now runs under the publish, the barrier and its skew instead of behind them.  (Unconditional loads at
         // clamped indices, as in the loop below: the wait counters stay exact.  No quads at all: any valid address.)
@@ -4794,13 +4615,13 @@ __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbStat
         const int Sx = (COOONLY || streamed) ? 0 : min(nsl, (mp1 + 63) >> 6);
         const uint32_t T = COOONLY ? 0u : CUMQ(Sx);
         const uint32_t qs = (uint32_t)(((unsigned long long)T * (unsigned)w) / NW), qe = (uint32_t)(((unsigned long long)T * (unsigned)(w + 1)) / NW);
-        [[maybe_unused]] unsigned long long rc[DEPTH]; [[maybe_unused]] dbl2_t rv0[DEPTH], rv1[DEPTH];
+        [[maybe_unused]] unsigned long long rc[ST_D]; [[maybe_unused]] dbl2_t rv0[ST_D], rv1[ST_D];
         if constexpr (!COOONLY) {
             const uint32_t qlast = (qe > qs ? qe : qs + 1u) - 1u;
             g_quad_cp cb0 = T ? cbase : (g_quad_cp)colsPool + lane;
             g_pair_cp vb0 = T ? vbase : (g_pair_cp)valsPool + lane;
 #pragma unroll
-            for (int t = 0; t < DEPTH; ++t) {
+            for (int t = 0; t < ST_D; ++t) {
                 const uint32_t qq = min(qs + (uint32_t)t, qlast);
                 rc[t] = cb0[(size_t)qq * 64];
                 rv0[t] = vb0[(size_t)(2 * qq) * 64]; rv1[t] = vb0[(size_t)(2 * qq + 1) * 64];
@@ -4845,7 +4666,7 @@ __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbStat
                 s = lo_;
             }
             uint32_t nextB = CUMQ(s + 1);
-            // ring of DEPTH quads in flight per lane (filled above, in front of the barrier); loads are issued unconditionally
+            // ring of ST_D quads in flight per lane (filled above, in front of the barrier); loads are issued unconditionally
             // (clamped index) so that the wait counters stay exact
             unsigned long long smI = 0ull; [[maybe_unused]] unsigned long long scI = 0ull;   // pulled sums of this lane's row: sum of bits(MAGIC + term)
             uint32_t pieceQ = qs;                               // first quad of the current piece
@@ -4916,26 +4737,26 @@ __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbStat
             }
             UP_GATHER(rc[0], ga, xa)
             uint32_t q0 = qs;
-            for (; q0 + DEPTH <= qe; q0 += DEPTH) {
+            for (; q0 + ST_D <= qe; q0 += ST_D) {
 #pragma unroll
-                for (int t = 0; t < DEPTH; ++t) {
+                for (int t = 0; t < ST_D; ++t) {
                     const uint32_t q = q0 + t;
                     const unsigned long long c = rc[t];
                     const dbl2_t v0 = rv0[t], v1 = rv1[t];
-                    const uint32_t qn = min(q + (uint32_t)DEPTH, qe - 1u);
+                    const uint32_t qn = min(q + (uint32_t)ST_D, qe - 1u);
                     rc[t] = cbase[(size_t)qn * 64];
                     rv0[t] = vbase[(size_t)(2 * qn) * 64]; rv1[t] = vbase[(size_t)(2 * qn + 1) * 64];
-                    UP_GATHER(rc[(t + 1) % DEPTH], gn, xn)           // quad q + 1 (behind the last quad: a duplicate, unused)
+                    UP_GATHER(rc[(t + 1) % ST_D], gn, xn)           // quad q + 1 (behind the last quad: a duplicate, unused)
                     UP_CONSUME(q, c, v0, v1)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { ga[e] = gn[e]; xa[e] = xn[e]; }
                 }
             }
 #pragma unroll
-            for (int t = 0; t < DEPTH; ++t) {                    // tail: fewer than DEPTH quads, already in the ring
+            for (int t = 0; t < ST_D; ++t) {                    // tail: fewer than ST_D quads, already in the ring
                 const uint32_t q = q0 + t;
                 if (q < qe) {
-                    UP_GATHER(rc[(t + 1) % DEPTH], gn, xn)
+                    UP_GATHER(rc[(t + 1) % ST_D], gn, xn)
                     UP_CONSUME(q, rc[t], rv0[t], rv1[t])
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { ga[e] = gn[e]; xa[e] = xn[e]; }
@@ -4955,10 +4776,7 @@ __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbStat
             if (p < L) {
                 Mn[k] = fx_decode(accM[p], inv); accM[p] = 0ull;            // clean for the next pass (published by its barrier)
                 if (split) { Cn[k] = fx_decode(accC[p], inv); accC[p] = 0ull; } else Cn[k] = 0.0;
-                // LEAN: the multiplied vector was not kept in registers across the stream: xg holds x * 2^s, and a power-of-two
-                // scaling is exact in both directions
-                if (LEAN) tk[k] = xg[p] * inv;
-            } else { Mn[k] = 0.0; Cn[k] = 0.0; if (LEAN) tk[k] = 0.0; }
+            } else { Mn[k] = 0.0; Cn[k] = 0.0; }
         }
         ++n_pass;
         TMARK(2);
@@ -5044,54 +4862,9 @@ __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbStat
         acc = r2[0]; cnt = r2[1];
     };
 
-    [[maybe_unused]] int passes0 = 0;                           // n_pass when this launch took the problem
-    [[maybe_unused]] bool budget = false;
-    if constexpr (BUDGET && NW != 1 && !COOONLY) budget = cont != nullptr && cont->cap > 0;
-    bool resumed = false;
-    if constexpr (BUDGET && NW != 1 && !COOONLY) {
-        if (cont != nullptr && resumeSlot >= 0) {               // a suspended problem: the state it was spilled with, through LDS
-            double* x1 = reinterpret_cast<double*>(accM); double* x2 = reinterpret_cast<double*>(accC);
-            cont_load(cont, resumeSlot, L, xg, x1, x2, red);
-            phase = (int)uni(red[1]); i = (int)uni(red[2]); j = (int)uni(red[3]); kk = (int)uni(red[4]); n_pass = (int)uni(red[5]);
-            ls_trials = (int)uni(red[6]); inner_iters = (int)uni(red[7]); mp1T = (int)uni(red[8]);
-            alpha = uni(red[9]); F = uni(red[10]); d = uni(red[11]); usum = uni(red[12]); unsum = uni(red[13]); du2 = uni(red[14]); xmaxT = uni(red[15]);
-            FOR_K_ALL(k, p) {
-                const bool in = p < L;
-                u[k] = in ? xg[p] : 0.0; Wu[k] = in ? x1[p] : 0.0; tk[k] = in ? x2[p] : 0.0;
-            }
-            __syncthreads();
-            for (int p = tid; p < L; p += NT) { xg[p] = 0.0; accM[p] = 0ull; accC[p] = 0ull; }     // clean again: the first pass publishes into them
-            __syncthreads();
-            passes0 = n_pass; resumed = true;
-        }
-    }
-    if (!resumed) {
-        if (phase == PH_INIT) normalize_u();
-        load_u_as_x();
-    }
+    if (phase == PH_INIT) normalize_u();
+    load_u_as_x();
     for (;;) {
-        if constexpr (BUDGET && NW != 1 && !COOONLY) {
-            if (budget && n_pass - passes0 >= cont->cap) {      // out of budget: suspend here, in front of a pass (workgroup-uniform)
-                if (pend) { __syncthreads(); collect_pending(); }
-                __syncthreads();
-                if (tid == 0) sint[5] = atomicAdd(cont->counters, 1);
-                __syncthreads();
-                const int slot = uni(sint[5]);
-                if (slot < cont->slots) {
-                    double* x1 = reinterpret_cast<double*>(accM); double* x2 = reinterpret_cast<double*>(accC);
-                    FOR_K(k, p) if (p < L) { xg[p] = u[k]; x1[p] = Wu[k]; x2[p] = tk[k]; }
-                    if (tid == 0) {
-                        red[0] = (double)b; red[1] = (double)phase; red[2] = (double)i; red[3] = (double)j; red[4] = (double)kk; red[5] = (double)n_pass;
-                        red[6] = (double)ls_trials; red[7] = (double)inner_iters; red[8] = (double)mp1T; red[9] = alpha; red[10] = F; red[11] = d;
-                        red[12] = usum; red[13] = unsum; red[14] = du2; red[15] = xmaxT;
-                    }
-                    __syncthreads();
-                    cont_spill(cont, slot, b, L, xg, x1, x2, red);
-                    return;
-                }
-                budget = false;                                 // no slot left: this problem runs on
-            }
-        }
         // RESCALE: M x alone (a fused pass with nothing added); INIT / SPLIT: both products; TRIAL: (M + d C) x
         spmv(xmaxT, mp1T, phase == PH_INIT || phase == PH_SPLIT, phase == PH_TRIAL ? d : 0.0);
         if (phase == PH_RESCALE) {                              // u = normalize(M u0 + diag u0)
@@ -5185,8 +4958,8 @@ __device__ void solve_up(const DevParams& D, int b, const ProbDesc& pd, ProbStat
 // reductions at all), 64-thread workgroups, many of them per compute unit: submaps of the reference's demo scale (20-40
 // objects, ~60 live associations) would otherwise occupy a whole 8-wave workgroup — a whole compute unit, given the
 // registers of the general instantiation — for ~100 entries of matrix.  [Llo, Lhi]: the live-set sizes this launch takes.
-template <int NW, bool HASCZ, int MAXL, int DEPTH = ST_D, bool LEAN = false, bool BUDGET = false>
-__global__ void __launch_bounds__(NW * 64, LEAN ? 4 : (NW == 1 ? 3 : 1)) k_solve_up(DevParams D, int B, const ProbDesc* __restrict__ probs,
+template <int NW, bool HASCZ, int MAXL>
+__global__ void __launch_bounds__(NW * 64, NW == 1 ? 3 : 1) k_solve_up(DevParams D, int B, const ProbDesc* __restrict__ probs,
                                                       ProbState* __restrict__ st,
                                                       const double* __restrict__ feats, const int32_t* __restrict__ assoc,
                                                       const int32_t* __restrict__ plp, const int32_t* __restrict__ lpAsc,
@@ -5194,8 +4967,7 @@ __global__ void __launch_bounds__(NW * 64, LEAN ? 4 : (NW == 1 ? 3 : 1)) k_solve
                                                       const uint32_t* __restrict__ sliceBase,
                                                       const uint16_t* __restrict__ cols, const double* __restrict__ vals,
                                                       const double* __restrict__ u0, SolveOut O,
-                                                      int* __restrict__ queue, int Lc, int Llo, int Lhi, int R /* problems per claim: 1..64 */,
-                                                      SolveCont cont /* pass budget / the suspended problems of the launch in front (NW == 1: unused) */)
+                                                      int* __restrict__ queue, int Lc, int Llo, int Lhi, int R /* problems per claim: 1..64 */)
 {
     // LDS: xg[Lc] f64 | accM[Lc] u64 | accC[Lc] u64 | red[red_doubles(NW)] | cumQ[ST_MAXSL + 2] u32 | sint[8]
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -5207,23 +4979,6 @@ __global__ void __launch_bounds__(NW * 64, LEAN ? 4 : (NW == 1 ? 3 : 1)) k_solve
     uint32_t* cumQ = reinterpret_cast<uint32_t*>(red + red_doubles(NW));
     int* sint = reinterpret_cast<int*>(cumQ + ST_MAXSL + 2);
     unsigned char* cooLds = reinterpret_cast<unsigned char*>(sint + 8);        // (one-wave instantiation only: COO_CAP * 12 bytes)
-    if constexpr (BUDGET && NW != 1) {
-        if (cont.resume) {                                      // the suspended problems of the launch in front, one workgroup each
-            for (;;) {
-                if (threadIdx.x == 0) sint[2] = atomicAdd(cont.counters + 1, 1);
-                __syncthreads();
-                const int slot = uni(sint[2]);
-                __syncthreads();
-                if (slot >= min(*cont.counters, cont.slots)) break;
-                const int b = cont.list[slot];
-                const ProbDesc pd = probs[b];
-                solve_up<NW, HASCZ, MAXL, DEPTH, LEAN, false, true>(D, b, pd, st, feats, assoc, plp, lpAsc, rowPos, pld, sliceBase, cols, vals, u0, O,
-                                          xg, accM, accC, Lc, cumQ, red, sint, cooLds, -1, -1, &cont, slot);
-                __syncthreads();
-            }
-            return;
-        }
-    }
     for (;;) {
         // The first wave claims R consecutive problems at a time (R = 1 unless this launch expects to find nothing: a batch
         // of small problems passes through the general instantiation and vice versa) until the range holds one this launch
@@ -5254,8 +5009,8 @@ __global__ void __launch_bounds__(NW * 64, LEAN ? 4 : (NW == 1 ? 3 : 1)) k_solve
         const int b = base + __builtin_ctzll(mask);
         mask &= mask - 1ull;
         const ProbDesc pd = probs[b];
-        solve_up<NW, HASCZ, MAXL, DEPTH, LEAN, false, BUDGET>(D, b, pd, st, feats, assoc, plp, lpAsc, rowPos, pld, sliceBase, cols, vals, u0, O,
-                                  xg, accM, accC, Lc, cumQ, red, sint, cooLds, -1, -1, (BUDGET && NW != 1) ? &cont : nullptr, -1);
+        solve_up<NW, HASCZ, MAXL>(D, b, pd, st, feats, assoc, plp, lpAsc, rowPos, pld, sliceBase, cols, vals, u0, O,
+                                  xg, accM, accC, Lc, cumQ, red, sint, cooLds);
         __syncthreads();                                         // the next problem of the range reuses the LDS state
         }
     }
@@ -5472,7 +5227,7 @@ __global__ void __launch_bounds__(64, 3) k_small(DevParams D, int B, const ProbD
             if (lane == 0) st[b].nnzUpper = (unsigned long long)nk;
             __syncthreads();                                    // the pair list is spent: its LDS becomes the solver's vectors
             SMARK(5);
-            solve_up<1, false, SMALL_MAXL, ST_D, false, true>(D, b, pd, st, feats, assoc, plp, lp, rowPos, pld, nullptr, nullptr, nullptr, u0, O,
+            solve_up<1, false, SMALL_MAXL, true>(D, b, pd, st, feats, assoc, plp, lp, rowPos, pld, nullptr, nullptr, nullptr, u0, O,
                                            xg, accM, accC, Lc1, cumQ, red, sint, cooLds, (int)nk, (int)lo);
             if (lane == 0) st[b].kind = 3;                      // done: the general kernels pass it by
 #ifdef ROMAN_SMALL_TIMING
@@ -5520,10 +5275,7 @@ constexpr int WIDE_NW = WIDE_NT / 64;
 constexpr int WIDE_KW = 2;               // vector elements a thread can own: L <= WIDE_KW * 64 * (waves of the grid)
 constexpr int WIDE_NRED = 10;            // doubles per workgroup slot of a grid reduction
 constexpr int WIDE_MAXBLK = 8;           // column blocks of the half copy (pull + push passes) at most
-#ifndef ROMAN_WIDE_U
-#define ROMAN_WIDE_U 3
-#endif
-constexpr int WIDE_U = ROMAN_WIDE_U;     // quads (of 4 entries per lane) per block of the stream; two blocks in flight per wave
+constexpr int WIDE_U = 3;                // quads (of 4 entries per lane) per block of the stream; two blocks in flight per wave
 constexpr int WIDE_MAXCH = 8;            // chunks of the flat stream a wave takes per pass at most
 
 // dynamic LDS of k_solve_wide in front of the gathered vector's leading part: three bit maps of bmWords 64-bit words and the
@@ -5722,7 +5474,6 @@ __global__ void __launch_bounds__(WIDE_NT) k_solve_wide(DevParams D, int B, cons
                                                         unsigned long long* __restrict__ bmPool /* [2][bmWords]: support bit maps of the two published vectors */,
                                                         int bmWords /* 64-bit words of one bit map (and of its LDS copy) */,
                                                         int xcap /* doubles of dynamic LDS behind the bit map: the gathered vector's leading part */,
-                                                        int tune /* experiments: bit 0 never gather from LDS, bit 1 non-temporal matrix loads, bits 8.. chunks per wave */,
                                                         unsigned long long spinTicks /* wall-clock ticks a barrier wait may last (host: 4 s at the device's wall-clock rate) */,
                                                         int teams /* 0: the whole device on one problem at a time; s >= 1: s teams per XCD, a problem each */,
                                                         const int32_t* __restrict__ fbList /* the batch's fallback problems (k_skipped) */,
@@ -5751,7 +5502,6 @@ __global__ void __launch_bounds__(WIDE_NT) k_solve_wide(DevParams D, int B, cons
     if (!wide_census(sh, wb, ltid)) return;
     const int G = wb.tG, NWG = G * WIDE_NW;                      // my team (whole-device mode: the grid)
     const int gw = w * G + wb.tRank;                            // wave id in the team: consecutive ids on different compute units
-    const int gwc = (tune & 4) ? wb.tRank * WIDE_NW + w : gw;   // wave id for the deal of stream chunks (experiment: the waves of a compute unit take consecutive chunks)
     part += (size_t)wb.team * (size_t)partStride;
     bmPool += (size_t)wb.team * 3 * (size_t)bmWords;            // two bit maps + the new slice widths of a compaction
     uint32_t* wNew = reinterpret_cast<uint32_t*>(bmPool + 2 * (size_t)bmWords);
@@ -5799,7 +5549,7 @@ __global__ void __launch_bounds__(WIDE_NT) k_solve_wide(DevParams D, int B, cons
         // m <= WIDE_MAXCH of chunks (the last round may be short): about 96 steps per chunk (chunk_steps), more when the matrix is larger.
         uint32_t T = Tfull, CS = 1u, nCh = 0u;
         int cmode = 0 /* stream in use: 0 full, 1 the column-compacted copy, 2 my column block of the half copy (pull + push) */, ncomp = 0, winPass = 0, winOut = 0; bool haveCopy = false;
-        int cNWG = NWG, cgw = gwc;                              // the waves the stream in use is dealt to and my id among them (half copy: the workgroups of my column block)
+        int cNWG = NWG, cgw = gw;                              // the waves the stream in use is dealt to and my id among them (half copy: the workgroups of my column block)
         // the half copy: column blocks, their width, my block, its workgroups / my rank among them, its first column, the fixed-point scale of the pass
         bool upOn = false;                                      // (everything else about the copy lives in sh.up*: read where needed, no registers across the passes)
         uint32_t copyCols = 0u, Tcopy = 0u;                     // compaction state (identical in every workgroup of the team)
@@ -5809,8 +5559,7 @@ __global__ void __launch_bounds__(WIDE_NT) k_solve_wide(DevParams D, int B, cons
             // (about 96 steps per chunk: one or two long chunks per wave — round 3 had settled on 16 steps, up to eight chunks per wave; measured
             //  again in round 6, one / two / four / auto chunks per wave: 64 x L = 10 000 37.8 / 37.9 / 38.4 / 40.0 ms of solve, on the half copy
             //  35.5 / 35.1 / 37.4 / 37.0; n = m = 200 21.8 / 22.3 / 22.8 / 22.4 — fewer pieces per slice for the owners to collect)
-            uint32_t mch = max(1u, min((uint32_t)WIDE_MAXCH, (T_ + nwg_ * 96u - 1u) / (nwg_ * 96u)));
-            if ((tune >> 8) & 0xff) mch = min((uint32_t)WIDE_MAXCH, (uint32_t)((tune >> 8) & 0xff));
+            const uint32_t mch = max(1u, min((uint32_t)WIDE_MAXCH, (T_ + nwg_ * 96u - 1u) / (nwg_ * 96u)));
             return max(1u, (T_ + nwg_ * mch - 1u) / (nwg_ * mch));
         };
         auto geometry = [&]() {                                 // (cw, T, cNWG and cgw are set; every thread of the workgroup calls this)
@@ -5842,7 +5591,7 @@ __global__ void __launch_bounds__(WIDE_NT) k_solve_wide(DevParams D, int B, cons
         auto full_stream = [&]() {                              // cw <- the layout's own slice bases
             __syncthreads();
             for (int p = ltid; p <= nsl; p += WIDE_NT) cw[p] = p < nsl ? MEMW(p) : Tfull;
-            T = Tfull; cmode = 0; cNWG = NWG; cgw = gwc;
+            T = Tfull; cmode = 0; cNWG = NWG; cgw = gw;
             geometry();
         };
         auto copy_stream = [&]() {                              // cw <- prefix of the copy's slice widths (wNew, written by its compaction)
@@ -5858,7 +5607,7 @@ __global__ void __launch_bounds__(WIDE_NT) k_solve_wide(DevParams D, int B, cons
                 if (lane == 0) cw[nsl] = run;
             }
             __syncthreads();
-            T = cw[nsl]; Tcopy = T; cmode = 1; cNWG = NWG; cgw = gwc;
+            T = cw[nsl]; Tcopy = T; cmode = 1; cNWG = NWG; cgw = gw;
             geometry();
         };
         full_stream();
@@ -5920,8 +5669,7 @@ __global__ void __launch_bounds__(WIDE_NT) k_solve_wide(DevParams D, int B, cons
 #define WIDE_ISSUE(C_, V0_, V1_, off_, n_)                                                                    \
             _Pragma("unroll") for (int e = 0; e < WIDE_U; ++e) {                                              \
                 const uint32_t q_ = (off_) + min((uint32_t)e, (n_) - 1u);     /* clamped: a repeated quad is skipped by the consumer */ \
-                if (tune & 2) { C_[e] = __builtin_nontemporal_load(cp + (size_t)q_ * 64); V0_[e] = __builtin_nontemporal_load(vp + (size_t)(2u * q_) * 64); V1_[e] = __builtin_nontemporal_load(vp + (size_t)(2u * q_ + 1u) * 64); } \
-                else { C_[e] = cp[(size_t)q_ * 64]; V0_[e] = vp[(size_t)(2u * q_) * 64]; V1_[e] = vp[(size_t)(2u * q_ + 1u) * 64]; } \
+                C_[e] = cp[(size_t)q_ * 64]; V0_[e] = vp[(size_t)(2u * q_) * 64]; V1_[e] = vp[(size_t)(2u * q_ + 1u) * 64]; \
             }
 #define WIDE_CONSUME(C_, V0_, V1_, n_)                                                                        \
             _Pragma("unroll") for (int e = 0; e < WIDE_U; ++e) {                                              \
@@ -6099,7 +5847,7 @@ __global__ void __launch_bounds__(WIDE_NT) k_solve_wide(DevParams D, int B, cons
         // elements are the columns most entries point at, and the support collapses onto them within a few passes.  A
         // gather is then an LDS read; only a column beyond the LDS part whose bit is set goes to L2.
         auto stream = [&](const double* xv, const unsigned long long* bm, uint32_t mp1, double xmax /* largest element of xv */) -> bool {
-            const uint32_t nl = (tune & 1) ? 0u : min(mp1, (uint32_t)xcap);
+            const uint32_t nl = min(mp1, (uint32_t)xcap);
             for (uint32_t p = (uint32_t)ltid; p < (uint32_t)nsl; p += WIDE_NT) bml[p] = bm[p];
             const bool upIn = upOn;
             if (!upOn) for (uint32_t p = (uint32_t)ltid; p < nl; p += WIDE_NT) xl[p] = xv[p];
@@ -6145,7 +5893,7 @@ __global__ void __launch_bounds__(WIDE_NT) k_solve_wide(DevParams D, int B, cons
                     if (doc == 2 && cmode != 0) full_stream();
                     upOn = false;                               // (the compacted copy takes the mirror pools: the half copy is gone)
                     const IdxT* srcC = doc == 1 ? (const IdxT*)colsK : cols; const double* srcV = doc == 1 ? (const double*)valsK : vals;
-                    for (int s_ = gwc; s_ < nsl; s_ += NWG) slice_compact(s_, srcC, srcV);
+                    for (int s_ = gw; s_ < nsl; s_ += NWG) slice_compact(s_, srcC, srcV);
                     for (uint32_t p = (uint32_t)ltid; p < (uint32_t)nsl; p += WIDE_NT) bmC[p] = bmA[p];
                     if (!wide_sync<true>(sh, wb, ltid)) return false;
                     haveCopy = true; copyCols = cntA; ++ncomp; fits = true;
@@ -6681,7 +6429,7 @@ __global__ void __launch_bounds__(256) k_skipped(int B, const ProbDesc* __restri
                                                  int* __restrict__ queue /* the solvers' problem queues (8 ints): cleared here */,
                                                  int32_t* __restrict__ fbList, unsigned* __restrict__ wideBar)
 {
-    if (blockIdx.x == 0 && (threadIdx.x < 8 || threadIdx.x == 10 || threadIdx.x == 11)) queue[threadIdx.x] = 0;   // ([10], [11]: the stream solver's continuation counters)
+    if (blockIdx.x == 0 && threadIdx.x < 8) queue[threadIdx.x] = 0;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B && fbList != nullptr && st[b].kind == 1) {
         fbList[atomicAdd(wideBar + 32 * 21, 1u)] = b;

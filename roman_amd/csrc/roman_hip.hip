@@ -78,7 +78,7 @@ struct roman_ctx {
         DevBuf plp, pli, plj, pls, pld, plza, plzb;                // the same in position order (stream layout)
         DevBuf rowCnt, rowPos, perm, sliceWidth, sliceBase, items, maskPool, prefPool, listPool, listOff;
         DevBuf vMu, vCu, vMun, vCun, gU, gUn, uOut, nodesOrig, nSel, widePart, wideSlots, wideBar, wideBm, wideY, wideUp, fbList;
-        DevBuf cols16, cols32, vals, colsC, valsC, contSpill, contList;
+        DevBuf cols16, cols32, vals, colsC, valsC;
         long long capMaskWords = 0, capNnz = 0, capList = 0;       // what the sparse pools hold (elements)
         // staging for the host-pointer entry points
         DevBuf hFeats, hAssoc, hU0, oAssoc, oN, oT, oStatus, oStats, hAux1, hAux2, hAux3;
@@ -245,12 +245,6 @@ int make_dev_params(roman_ctx* c, const roman_params_t* p, int32_t F, DevParams*
     D->pre_invw = (p->epsilon > 0.0 && std::isfinite(p->epsilon)) ? 32.0 / p->epsilon : 0.0;
     D->pre_K = 34;
     D->allow_fallback = 1;
-    { static const char* cooEnv = getenv("ROMAN_COO"); D->solve_flags = (cooEnv && cooEnv[0] == '0') ? 1 : 0; }   // ROMAN_COO=0: A/B switch of the one-wave solver's coordinate form
-    {   // ROMAN_FILL_ROTATE=0: list order inside a row (A/B); =m: rotate a row's quads by m * row (default 5)
-        static const char* rotEnv = getenv("ROMAN_FILL_ROTATE");
-        const int m = rotEnv ? atoi(rotEnv) : 5;
-        if (m <= 0) D->solve_flags |= 2; else D->solve_flags |= (m & 0xffff) << 8;
-    }
     return ROMAN_OK;
 }
 
@@ -447,20 +441,17 @@ static int sort_eq_max()
 }
 
 // Cosine matrices of B problems: k_cos_tile (64x64 tile per workgroup, operands through LDS) by default, k_cos_deal (80x80 tiles, blocks
-// dealt evenly to the waves) for batches of mid-size maps, k_cos_wave (one wave per problem) for maps of at most 48 objects; ROMAN_COS=0 selects
-// k_cos (32x32 tile per wave, operands from global memory), ROMAN_COS=16 / 32 the stage depth.
+// dealt evenly to the waves) for batches of mid-size maps, k_cos_wave (one wave per problem) or k_cos_block (one wave per block) for
+// maps of at most 48 objects, k_cos_block again for a few problems of larger maps.
 static hipError_t launch_cos(roman_ctx* c, hipStream_t stream, const DevParams& D, int B, int maxN1, int maxN2, const ProbDesc* dP, const double* feats, double* cosPool)
 {
-    static const char* env = getenv("ROMAN_COS");
-    const int mode = env ? atoi(env) : 16;
-    static const char* waveEnv = getenv("ROMAN_COS_WAVE");      // "0": never the one-wave-per-problem kernel (A/B)
     {   // a batch with at least two workgroups per compute unit of 5 x 5-block tiles: k_cos_deal (blocks dealt evenly to the waves).
         // ROMAN_COS_DEAL=0 never, =1 always (A/B, tests; read per call)
         const char* dealEnv = getenv("ROMAN_COS_DEAL");
         constexpr int TD = 5;
         using CD = CosDeal<TD>;
         const int Gd = CD::tiles(maxN1) * CD::tiles(maxN2);
-        const bool deal = (dealEnv && dealEnv[0]) ? dealEnv[0] == '1' : (mode == 16 && (maxN1 > 16 * COSW_NB || maxN2 > 16 * COSW_NB) && (int64_t)Gd * B >= 2 * (int64_t)c->num_cu);
+        const bool deal = (dealEnv && dealEnv[0]) ? dealEnv[0] == '1' : ((maxN1 > 16 * COSW_NB || maxN2 > 16 * COSW_NB) && (int64_t)Gd * B >= 2 * (int64_t)c->num_cu);
         if (deal) {
             const hipError_t e = dyn_lds(c, reinterpret_cast<const void*>(k_cos_deal<TD, 0>), (size_t)CD::LDS);
             if (e != hipSuccess) return e;
@@ -468,7 +459,7 @@ static hipError_t launch_cos(roman_ctx* c, hipStream_t stream, const DevParams& 
             return hipGetLastError();
         }
     }
-    if (mode != 0 && maxN1 <= 16 * COSW_NB && maxN2 <= 16 * COSW_NB && !(waveEnv && waveEnv[0] == '0')) {
+    if (maxN1 <= 16 * COSW_NB && maxN2 <= 16 * COSW_NB) {
         // the reference's demo scale: one wave per problem, no LDS, no barrier (k_cos_wave); up to two problems per compute unit (a
         // serial caller's one pair per call, a small batch): one wave per 16 x 16 block (k_cos_block: 31 against 80 us for one pair,
         // 75 against 127 for 256, 114 against 135 for 512, 196 against 152 for 1024 — tools/gpu_cos_block_sweep.py).
@@ -480,7 +471,7 @@ static hipError_t launch_cos(roman_ctx* c, hipStream_t stream, const DevParams& 
         else hipLaunchKernelGGL(k_cos_wave, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, D, B, dP, feats, cosPool);
         return hipGetLastError();
     }
-    if (mode == 16) {
+    {
         // a few problems of larger maps (the single-pair call: 200 x 200 objects = 169 blocks): one wave per 16 x 16 block as well, eight
         // chunks of loads in flight per wave — the tile kernel below gives such a call sixteen workgroups with two stages in flight
         // (29 us; the contraction over the descriptor is serial either way).  Up to eight waves per compute unit; ROMAN_COS_BLOCK=0: never
@@ -491,25 +482,13 @@ static hipError_t launch_cos(roman_ctx* c, hipStream_t stream, const DevParams& 
             return hipGetLastError();
         }
     }
-    if (mode == 0) {
-        const int tiles = ((maxN1 + COS_TILE - 1) / COS_TILE) * ((maxN2 + COS_TILE - 1) / COS_TILE), G = (tiles + 3) / 4;
-        hipLaunchKernelGGL(k_cos, dim3((unsigned)(G * ((B + 7) / 8) * 8)), dim3(256), 0, stream, D, B, G, dP, feats, cosPool);
-        return hipGetLastError();
-    }
     auto tiles = [](int n) { return (((n + 15) >> 4) + 3) >> 2; };     // cos_tiles()
     const int G = tiles(maxN1) * tiles(maxN2);
-    const int KC = mode == 32 ? 32 : 16;
-    const size_t lds = (size_t)2 * 128 * (KC * 8 + 16);
-    auto kf = KC == 16 ? k_cos_tile<16> : k_cos_tile<32>;
-    const hipError_t e = dyn_lds(c, reinterpret_cast<const void*>(kf), lds);
+    const size_t lds = (size_t)2 * 128 * (COS_KC * 8 + 16);
+    const hipError_t e = dyn_lds(c, reinterpret_cast<const void*>(k_cos_tile), lds);
     if (e != hipSuccess) return e;
-    // one workgroup per tile; ROMAN_COS_WGS=n: n persistent workgroups per compute unit looping over the tiles (measured
-    // slower at config 3: 376 against 324 us — the static deal balances worse than the dispatcher)
-    static const char* wgEnv = getenv("ROMAN_COS_WGS");
-    const int perCu = wgEnv ? atoi(wgEnv) : 0;
-    const int total = G * ((B + 7) / 8) * 8;
-    const int grid = perCu > 0 ? std::min(total, (c->num_cu & ~7) * perCu) : total;
-    hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(256), lds, stream, D, B, G, dP, feats, cosPool);
+    // one workgroup per tile, all tiles of a problem on one XCD: whole groups of eight problems
+    hipLaunchKernelGGL(k_cos_tile, dim3((unsigned)(G * ((B + 7) / 8) * 8)), dim3(256), lds, stream, D, B, G, dP, feats, cosPool);
     return hipGetLastError();
 }
 
@@ -563,7 +542,6 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     SZ.capMaskWords = std::max(SZ.capMaskWords, WS.capMaskWords); SZ.capNnz = std::max(SZ.capNnz, WS.capNnz); SZ.capList = std::max(SZ.capList, WS.capList);
     // stream layout: as many live associations as the LDS tiles of this launch are sized for
     D.stream_maxL = std::min(STREAM_MAXL, std::max(64, (SZ.expectMaxL + 63) & ~63));
-    { static const char* smEnv = getenv("ROMAN_STREAM_MAXL"); if (smEnv) D.stream_maxL = std::max(64, std::min(D.stream_maxL, atoi(smEnv))); }   // experiments: force the fallback layout for smaller live sets
     // The fallback layout's kernels (symmetric SELL fill, k_solve / k_solve_wide) are launched only when a problem can
     // need them: no history yet, a live set beyond the stream layout expected, or parameters only k_solve handles.  Else a
     // problem that turns out too large for the LDS tiles of this launch is skipped (ROMAN_ST_WORKSPACE) and, the
@@ -613,7 +591,6 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     // work items: blocks of RPB consecutive live rows of one problem (more, smaller items for small batches)
     int RPB = 32;
     while (RPB < 128 && (int64_t)RPB * c->num_cu * 64 < sumA) RPB <<= 1;     // 128: ~17 items per problem balance the static item loop best (measured 32..1024)
-    { const char* e_ = getenv("ROMAN_RPB"); if (e_ && e_[0]) { const int v_ = atoi(e_); if (v_ == 32 || v_ == 64 || v_ == 128) RPB = v_; } }   // (experiments: read per call)
     const size_t maxItems = (size_t)(sumA / RPB) + (size_t)B + 1;
     HIPCHK(c, WS.items.ensure(sizeof(ItemDesc) * maxItems));
 
@@ -691,12 +668,8 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     const int Lneed = (expL + 255) & ~255;
     // (two rows per wave when their table slices leave room for the whole expected live set — or, for live sets beyond any
     //  tile, for a tile of at least 2048 columns: k_count sweeps larger live sets tile by tile)
-    int NRc = ((size_t)16 * 2 * ldsPerRow * sizeof(double) + (size_t)std::min(Lneed, 2048) * colBytesC <= c->lds_max) ? 2 : 1;
+    const int NRc = ((size_t)16 * 2 * ldsPerRow * sizeof(double) + (size_t)std::min(Lneed, 2048) * colBytesC <= c->lds_max) ? 2 : 1;
     int wpb = 16;
-    static const char* nrEnv = getenv("ROMAN_COUNT_NR");
-    static const char* wpbEnv = getenv("ROMAN_COUNT_WPB");
-    if (nrEnv) NRc = atoi(nrEnv) == 2 ? 2 : 1;
-    if (wpbEnv) wpb = std::max(1, std::min(16, atoi(wpbEnv)));
     while (wpb > 1 && (size_t)wpb * NRc * ldsPerRow * sizeof(double) + 256 * colBytesC > c->lds_max) wpb >>= 1;
     if ((size_t)wpb * NRc * ldsPerRow * sizeof(double) + 256 * colBytesC > c->lds_max)
         return fail(c, ROMAN_E_TOO_LARGE, "maps of %d objects exceed the LDS table staging of this build", maxN);
@@ -710,7 +683,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     // pairs (the exact gate reads them from memory for the ~6 % of the columns that reach it) + per wave the table slices, their
     // 16-bit bin slices, the candidate queue and the rows' mask words.  Taken when the whole expected live set fits its tile;
     // ROMAN_COUNT_PRE=0 / 1 in the environment forces the plain sweep / the prefilter where it fits (A/B and tests: read per call).
-    int preNR = 0, preWpb = 0, preTC = 0, preNO = 0; size_t preLds = 0;
+    int preNR = 0, preWpb = 0, preTC = 0; size_t preLds = 0;
     const int preRow = (2 * std::max(maxN, 1) + 1 + 3) & ~3;                 // entries of the packed bin table (n1 + sentinel + n2)
     {
         const char* preEnv = getenv("ROMAN_COUNT_PRE");
@@ -720,20 +693,6 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
             for (int wp = PRE_WAVES; wp >= 8; wp -= 4) {
                 const size_t need = (size_t)(tc + PRE_COLPAD + 4) * 4 + (size_t)wp * (size_t)count_pre_wave_bytes(preRow, tc);
                 if (need <= c->lds_max) { preNR = PRE_NR; preWpb = wp; preTC = tc; preLds = need; break; }
-            }
-            if (wpbEnv && preNR) {                               // (A/B: ROMAN_COUNT_WPB also caps the prefiltered sweep's waves)
-                preWpb = std::min(preWpb, wpb);
-                preLds = (size_t)(preTC + PRE_COLPAD + 4) * 4 + (size_t)preWpb * (size_t)count_pre_wave_bytes(preRow, preTC);
-            }
-            // ROMAN_COUNT_OBJ=1 (A/B and tests; read per call): the exact gate recomputes its two distances from the objects' coordinates in
-            // LDS (32 bytes per object) instead of reading the tables and the heights from memory — four L2 gathers per candidate fewer,
-            // bit-identical masks (146 parity tests either way), and SLOWER: 397 against 373 us per batch of 256 on one box, twice: the
-            // sweep is bound by its LDS, which the eight extra reads per candidate load further; sixteen waves hide the L2 round trips.  Off.
-            if (preNR) {
-                const char* objEnv = getenv("ROMAN_COUNT_OBJ");
-                const int no = (std::max(maxN, 1) + 1) & ~1;
-                const size_t objBytes = (size_t)2 * no * 32 + 16;
-                if (objEnv && objEnv[0] == '1' && preLds + (size_t)preTC * 4 + objBytes <= c->lds_max) { preNO = no; preLds += objBytes; }
             }
         }
     }
@@ -804,8 +763,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
             int a_TC = usePre ? preTC : TCc, a_lpw = usePre ? preRow : ldsPerWave;
             int a_RPB = wholeP ? -B : RPB;
             const uint16_t* a_qtab = WS.qtabPool.as<uint16_t>();
-            const double* a_feats = in.feats; int a_NO = usePre ? preNO : 0;
-            void* args[] = {&a_D, &a_dP, &a_dS, &a_dT, &a_items, &a_tab, &a_li, &a_lj, &a_za, &a_zb, &a_rc, &a_mask, &a_pref, &a_TC, &a_lpw, &a_RPB, &a_qtab, &a_feats, &a_NO};
+            void* args[] = {&a_D, &a_dP, &a_dS, &a_dT, &a_items, &a_tab, &a_li, &a_lj, &a_za, &a_zb, &a_rc, &a_mask, &a_pref, &a_TC, &a_lpw, &a_RPB, &a_qtab};
             HIPCHK(c, hipLaunchKernel(kc, dim3(gridK), dim3(wpbK * 64), args, ldsK + (wholeP ? (size_t)preTC * 4 : 0), WS.stream));
         }
     DBG(c, "k_count");
@@ -877,7 +835,6 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     // (about 3 groups per CU, EVERY problem cut into the same number NG of groups: the static deal of the groups to the
     // workgroups then gives each one heavy (first slices) and two light groups; whole problems per workgroup or cuts
     // that differ between problems measured 0.46-0.63 ms against 0.38-0.40)
-    static const char* ngEnv = getenv("ROMAN_FILL_NG");
     int NG = (int)std::max<int64_t>(1, std::min<int64_t>(FILLS_MAXSPI, (3 * (int64_t)c->num_cu + B / 2) / std::max(B, 1)));
     {   // a workgroup takes every (grid/8)-th group of its XCD's range: the residues it meets (which part of a problem
         // a group is) rotate through all NG values only if that stride is coprime to NG — NG = 4 on 256 CUs (stride 32)
@@ -886,7 +843,6 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
         auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
         while (NG > 1 && gcd(stride % NG, NG) != 1) --NG;
     }
-    if (ngEnv) NG = std::max(1, std::min(FILLS_MAXSPI, atoi(ngEnv)));
     const int Wmax = std::max(1, D.stream_maxL / 64);
     const int SPI = (Wmax + std::min(NG, Wmax) - 1) / std::min(NG, Wmax);       // slices per group at most (LDS capacity)
     if (!D.small_only) {
@@ -902,10 +858,9 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
         const int TCs = D.stream_maxL;
         // the objects' coordinates in LDS (32 bytes per object) instead of the z columns, when they fit: the fill then
         // recomputes the distances instead of gathering them from the tables
-        static const char* objEnv = getenv("ROMAN_FILL_OBJ");
         const int NO = (std::max(maxN, 1) + 1) & ~1;
         const size_t groupLds = sizeof(uint32_t) * (size_t)(3 * SPI * 64 + 2 * (SPI + 1) + 2);
-        const bool obj = (objEnv ? atoi(objEnv) != 0 : true) && (size_t)TCs * (16 + 2) + (size_t)64 * NO + groupLds <= c->lds_max;
+        const bool obj = (size_t)TCs * (16 + 2) + (size_t)64 * NO + groupLds <= c->lds_max;
         const size_t sliceLds = obj ? (size_t)TCs * (16 + 2) + (size_t)64 * NO + groupLds : (size_t)TCs * (colBytesF + 2) + groupLds;
         if (sliceLds > c->lds_max) return fail(c, ROMAN_E_TOO_LARGE, "internal: stream column tile does not fit the LDS");
         const bool fast = D.single && (D.p.single_mode == ROMAN_SINGLE_BOTH || D.p.single_mode == ROMAN_SINGLE_OFFDIAG) && D.p.distance_weight == 1.0 &&
@@ -972,35 +927,11 @@ int enqueue_solve(roman_ctx* c, const DevParams& D, int B, int64_t sumA, int64_t
 #endif
     // stream solver: LDS = three vectors of Lc elements (Lc: whole slices of stream_maxL + the 64 dummy elements the
     // inert padding entries point at) + reduction scratch + slice table
-    constexpr int NW = ROMAN_SOLVE_WAVES;
+    constexpr int NW = SOLVE_WAVES;
     const int Lc = STREAM_MAXL + 64;                            // (fixed: the kernel addresses the three vectors at compile-time distances)
     const size_t ldsUp = (size_t)3 * 8 * Lc + sizeof(double) * red_doubles(NW) + sizeof(uint32_t) * (ST_MAXSL + 2) + sizeof(int) * 8 + 16;
     const int wgPerCu = std::max(1, std::min((int)(c->lds_max / ldsUp), 2048 / (NW * 64)));
     const int gridUp = std::max(1, std::min(B, c->num_cu * wgPerCu));
-
-    // Bounded launches (SolveCont, kernels.hip.h): a problem still iterating after `cap` passes of the launch is suspended and a second
-    // launch resumes the suspended ones, all at once, one workgroup each.  Built for the round-5 review's item 2 (a call with more
-    // problems than workgroups hands them out from a queue, and a 400-pass problem claimed late was thought to hold the tail), correct
-    // bit for bit (tests/test_gpu_batch.py::test_bounded_solver_launches_...), and MEASURED WITHOUT EFFECT (round 6, one box, budget 64
-    // against none, alternating): a rank's 512-pair share of the config-4 grid 4.4 ... 6.5 ms either way, the slowest rank 6.5 ms, one
-    // shot of the 4096-pair grid 32-33 ms, headline 157-160 k alignments/s.  The tail IS the long problem's own passes — 364 x ~10 us on
-    // its one compute unit, whenever they start —, not its place in the queue.  OFF unless ROMAN_SOLVE_CAP=n asks for a budget of n
-    // passes (read per call).
-    SolveCont cont{}; SolveCont contResume{};
-    {
-        const char* capEnv = getenv("ROMAN_SOLVE_CAP");
-        const int cap = capEnv ? std::max(0, atoi(capEnv)) : 0;
-        if (cap > 0 && !D.small_only) {
-            const int slots = std::max(64, std::min(B, 1024));
-            const int maxL = std::max(64, (D.stream_maxL + 63) & ~63);
-            const int slotDoubles = 16 + 3 * maxL;
-            HIPCHK(c, WS.contSpill.ensure(sizeof(double) * (size_t)slots * (size_t)slotDoubles));
-            HIPCHK(c, WS.contList.ensure(sizeof(int32_t) * (size_t)slots));
-            cont.spill = WS.contSpill.as<double>(); cont.list = WS.contList.as<int32_t>(); cont.counters = WS.queue.as<int>() + 10;
-            cont.cap = cap; cont.slots = slots; cont.slotDoubles = slotDoubles; cont.maxL = maxL; cont.resume = 0;
-            contResume = cont; contResume.cap = 0; contResume.resume = 1;
-        }
-    }
 
     StageTimer t3(c, ROMAN_STAGE_SOLVE);
     const bool coopPlanned = mayFallback && D.wide != 0 && c->coop_ok;
@@ -1023,37 +954,18 @@ int enqueue_solve(roman_ctx* c, const DevParams& D, int B, int64_t sumA, int64_t
     const int Lc1 = SMALL_MAXL + 64;
     const size_t ldsUp1 = (size_t)3 * 8 * Lc1 + sizeof(double) * red_doubles(1) + sizeof(uint32_t) * (ST_MAXSL + 2) + sizeof(int) * 8 + 16 + (size_t)COO_CAP * 12;
     const int gridUp1 = std::max(1, std::min(B, c->num_cu * 24));
-    // The general instantiation keeps a thread's six vector elements and three quads of the stream in flight in 189 registers:
-    // one workgroup per compute unit.  ROMAN_SOLVE_LEAN=1 selects the 128-register instantiation instead (the multiplied vector
-    // not held across the stream, two quads in flight, the rest of the state spilled by the compiler around the stream loop):
-    // two workgroups — two problems, or a problem and another batch's kernels — per compute unit.  MEASURED SLOWER (round 4,
-    // config 3: 1.34 against 1.09 ms per isolated launch, 119-121 k against 123-125 k alignments/s with three batches in
-    // flight; B = 1: 0.52 against 0.47 ms): the second workgroup does not buy back what the thinner stream loses.  Off by default.
-    static const char* leanEnv = getenv("ROMAN_SOLVE_LEAN");    // "1": use it
-    const bool lean = leanEnv && leanEnv[0] == '1' && D.stream_maxL <= LEAN_MAXL;
-    // A handful of problems (the single-pair call whose latency bench.py reports): the wide passes are bound by how many bytes
-    // ONE compute unit keeps in flight, not by the memory system — twice the quads in flight per lane (ROMAN_SOLVE_DEEP=0/1 forces).
-    // MEASURED (round 4, config 2, B = 1): p50 0.678 ms with six quads in flight against 0.667 with three — no gain: off unless forced.
-    // Round 5 (four quads, the rebuilt stream loop): 0.953-0.961 against 0.941-0.950 ms per isolated launch of 256 problems, p50 0.588 / 0.586.
-    static const char* deepEnv = getenv("ROMAN_SOLVE_DEEP");
-    const bool deep = deepEnv && deepEnv[0] == '1';
 #define ROMAN_LAUNCH_UP(CZ_)                                                                                                  \
     do {                                                                                                                      \
-        auto kup = cont.cap > 0 ? k_solve_up<NW, CZ_, STREAM_MAXL, ST_D, false, true>     /* (the budgeted instantiation: plain stream depth only) */ \
-                                : (lean ? k_solve_up<NW, CZ_, LEAN_MAXL, LEAN_D, true> : (deep ? k_solve_up<NW, CZ_, STREAM_MAXL, DEEP_D> : k_solve_up<NW, CZ_, STREAM_MAXL>)); \
+        auto kup = k_solve_up<NW, CZ_, STREAM_MAXL>;                                                                          \
         HIPCHK(c, dyn_lds(c, reinterpret_cast<const void*>(kup), ldsUp)); \
         hipLaunchKernelGGL(kup, dim3(gridUp), dim3(NW * 64), ldsUp, WS.stream, D, B, WS.probs.as<ProbDesc>(), WS.state.as<ProbState>(), feats, assoc, \
                            WS.plp.as<int32_t>(), WS.lp.as<int32_t>(), WS.rowPos.as<uint32_t>(), WS.pld.as<double>(), WS.sliceBase.as<uint32_t>(), \
-                           WS.cols16.as<uint16_t>(), WS.vals.as<double>(), u0, O, WS.queue.as<int>(), Lc, small ? SMALL_MAXL + 1 : 0, STREAM_MAXL, (small && c->hist.valid && !c->hist.largeSeen) ? 64 : 1, cont); \
-        if (cont.cap > 0)         /* the suspended problems, one workgroup each, to the end */                                  \
-            hipLaunchKernelGGL(kup, dim3(std::min(cont.slots, gridUp)), dim3(NW * 64), ldsUp, WS.stream, D, B, WS.probs.as<ProbDesc>(), WS.state.as<ProbState>(), feats, assoc, \
-                               WS.plp.as<int32_t>(), WS.lp.as<int32_t>(), WS.rowPos.as<uint32_t>(), WS.pld.as<double>(), WS.sliceBase.as<uint32_t>(), \
-                               WS.cols16.as<uint16_t>(), WS.vals.as<double>(), u0, O, WS.queue.as<int>(), Lc, small ? SMALL_MAXL + 1 : 0, STREAM_MAXL, 1, contResume); \
+                           WS.cols16.as<uint16_t>(), WS.vals.as<double>(), u0, O, WS.queue.as<int>(), Lc, small ? SMALL_MAXL + 1 : 0, STREAM_MAXL, (small && c->hist.valid && !c->hist.largeSeen) ? 64 : 1); \
         if (small) {                                                                                                          \
             HIPCHK(c, dyn_lds(c, reinterpret_cast<const void*>(k_solve_up<1, CZ_, SMALL_MAXL>), ldsUp1));                       \
             hipLaunchKernelGGL((k_solve_up<1, CZ_, SMALL_MAXL>), dim3(gridUp1), dim3(64), ldsUp1, WS.stream, D, B, WS.probs.as<ProbDesc>(), WS.state.as<ProbState>(), feats, assoc, \
                                WS.plp.as<int32_t>(), WS.lp.as<int32_t>(), WS.rowPos.as<uint32_t>(), WS.pld.as<double>(), WS.sliceBase.as<uint32_t>(), \
-                               WS.cols16.as<uint16_t>(), WS.vals.as<double>(), u0, O, WS.queue.as<int>() + 1, Lc1, 0, SMALL_MAXL, 1, SolveCont{}); \
+                               WS.cols16.as<uint16_t>(), WS.vals.as<double>(), u0, O, WS.queue.as<int>() + 1, Lc1, 0, SMALL_MAXL, 1); \
         }                                                                                                                     \
     } while (0)
     if (hascz) ROMAN_LAUNCH_UP(true); else ROMAN_LAUNCH_UP(false);
@@ -1080,8 +992,7 @@ int enqueue_solve(roman_ctx* c, const DevParams& D, int B, int64_t sumA, int64_t
             // with the whole device per problem (roman_ctx_set_wide_teams(ctx, 0) does the same for a device-pointer caller).
             const int perXcd = std::max(1, (G + c->num_xcc - 1) / c->num_xcc);
             {
-                static const char* marginEnv = getenv("ROMAN_WIDE_MARGIN");
-                const int margin = marginEnv ? atoi(marginEnv) : 2;
+                constexpr int margin = 2;
                 auto cap = [&](int sub) { return (int64_t)WIDE_KW * std::max(1, perXcd / sub - margin) * WIDE_NW * 64; };   // (a margin of two workgroups against uneven placement)
                 // more, smaller teams while there are problems for them and the live sets fit their registers: a pass of a team is a stream the
                 // whole device's bandwidth bounds however it is shared out, plus two barriers and a collect whose latencies only other teams can
@@ -1153,12 +1064,10 @@ int enqueue_solve(roman_ctx* c, const DevParams& D, int B, int64_t sumA, int64_t
             const void* wideFn = D.idx16 ? (a_ucfg ? reinterpret_cast<const void*>(k_solve_wide<uint16_t, true>) : reinterpret_cast<const void*>(k_solve_wide<uint16_t, false>))
                                          : reinterpret_cast<const void*>(k_solve_wide<uint32_t, false>);
             HIPCHK(c, dyn_lds(c, wideFn, wideLds));
-            static const char* tuneEnv = getenv("ROMAN_WIDE_TUNE");
-            int a_tune = tuneEnv ? (int)strtol(tuneEnv, nullptr, 0) : 0;
             unsigned long long a_ticks = c->spin_ticks;        // 4 s of the device's wall clock (test hook ROMAN_WIDE_SPIN_MS: shorter)
             const int32_t* a_fb = WS.fbList.as<int32_t>();
             void* args[] = {&Dv, &Bv, &a_probs, &a_state, &a_feats, &a_assoc, &a_lp, &a_ld, &a_perm, &a_rpos, &a_sb, &a_cols, &a_vals,
-                            &a_vU, &a_vX, &a_vX2, &a_s0, &a_s1, &a_s2, &a_plp, &a_u0, &a_O, &a_part, &a_slots, &a_bar, &a_bm, &a_bmw, &a_xcap, &a_tune, &a_ticks,
+                            &a_vU, &a_vX, &a_vX2, &a_s0, &a_s1, &a_s2, &a_plp, &a_u0, &a_O, &a_part, &a_slots, &a_bar, &a_bm, &a_bmw, &a_xcap, &a_ticks,
                             &a_teams, &a_fb, &a_partStride, &a_colsC, &a_valsC, &a_ccfg, &a_ucfg, &a_yPart, &a_ySlots, &a_ycap, &a_upMeta};
             // Two whole-device kernels must never be resident together (each would hold compute units while waiting at a
             // grid barrier for workgroups the other one keeps out): with batches in flight on several streams, a
@@ -1478,7 +1387,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
         DevBuf* all[] = {&W.probs, &W.state, &W.totals, &W.queue, &W.cosPool, &W.cosDense, &W.tabPool, &W.qtabPool, &W.sTmp, &W.chunkCnt,
                          &W.lp, &W.li, &W.lj, &W.ls, &W.ld, &W.lza, &W.lzb, &W.plp, &W.pli, &W.plj, &W.pls, &W.pld, &W.plza, &W.plzb,
                          &W.rowCnt, &W.rowPos, &W.perm, &W.sliceWidth, &W.sliceBase, &W.items, &W.maskPool, &W.prefPool, &W.listPool, &W.listOff,
-                         &W.vMu, &W.vCu, &W.vMun, &W.vCun, &W.gU, &W.gUn, &W.uOut, &W.nodesOrig, &W.nSel, &W.widePart, &W.wideSlots, &W.wideBar, &W.wideBm, &W.wideY, &W.wideUp, &W.fbList, &W.cols16, &W.cols32, &W.vals, &W.colsC, &W.valsC, &W.contSpill, &W.contList,
+                         &W.vMu, &W.vCu, &W.vMun, &W.vCun, &W.gU, &W.gUn, &W.uOut, &W.nodesOrig, &W.nSel, &W.widePart, &W.wideSlots, &W.wideBar, &W.wideBm, &W.wideY, &W.wideUp, &W.fbList, &W.cols16, &W.cols32, &W.vals, &W.colsC, &W.valsC,
                          &W.hFeats, &W.hAssoc, &W.hU0, &W.oAssoc, &W.oN, &W.oT, &W.oStatus, &W.oStats, &W.hAux1, &W.hAux2, &W.hAux3, &W.oAll, &W.lcStage, &W.mnoVals, &W.mnoOut, &W.mnoHost};
         for (DevBuf* b : all) b->release();
         if (W.pinnedTotals) (void)hipHostFree(W.pinnedTotals);

@@ -288,24 +288,6 @@ def test_large_single_cosine_product_takes_the_dealt_kernel_by_itself(ctx, monke
     assert np.array_equal(got, other)
 
 
-def test_both_cosine_kernels_give_the_same_bits(ctx, tmp_path):
-    """ROMAN_COS=0 selects the per-wave kernel k_cos (32x32 tile per wave, operands from global memory) that k_cos_tile
-    replaced as the default: same contraction order per element, same bits.  The switch is read once per process, so the
-    other kernel runs in a child process."""
-    import subprocess, sys
-    rng = np.random.default_rng(5)
-    P = _abi.RomanParams.default(); P.cos_feature_dim = 70
-    D1 = rng.standard_normal((137, 73)); D2 = rng.standard_normal((53, 73))
-    here = ctx.debug_cosine(P, D1, D2)
-    np.savez(tmp_path / "in.npz", D1=D1, D2=D2)
-    code = ("import numpy as np, sys; from roman_amd import _abi; from roman_amd.runtime import Context\n"
-            "z = np.load(sys.argv[1]); P = _abi.RomanParams.default(); P.cos_feature_dim = 70\n"
-            "c = Context(0); np.save(sys.argv[2], c.debug_cosine(P, z['D1'], z['D2'])); c.close()\n")
-    env = dict(os.environ, ROMAN_COS="0", PYTHONPATH=os.pathsep.join([os.path.dirname(os.path.dirname(os.path.abspath(__file__)))] + sys.path))
-    subprocess.run([sys.executable, "-c", code, str(tmp_path / "in.npz"), str(tmp_path / "out.npy")], check=True, env=env, timeout=300)
-    assert np.array_equal(here, np.load(tmp_path / "out.npy"))
-
-
 def _nudge(x, k):
     for _ in range(abs(k)):
         x = np.nextafter(x, np.inf if k > 0 else -np.inf)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The reference's demo scale (method 'roman', n, m in [20, 40], d = 768) as the all-pairs grid of 64 + 64 distinct submaps:
-stage times of one device-pointer call of 4096 problems.  Run under different environment switches (ROMAN_COO=0, ...) for A/B.
+stage times of one device-pointer call of 4096 problems.  Run under different environment switches (ROMAN_SMALL_FUSED=0, ...) for A/B.
 usage (GPU box): python tools/gpu_demo_scale.py"""
 import os
 import sys
@@ -60,7 +60,7 @@ print("ms per call by calls in flight:", {k: round(v * 1e3, 3) for k, v in tps.i
 ctx.set_pipeline(1)
 ctx.profile_enable(True); ctx.profile_reset(); call(); torch.cuda.synchronize(dev); pf = ctx.profile_get(); ctx.profile_enable(False)
 st = np.frombuffer(O[4].cpu().numpy().tobytes(), dtype=stats_dtype())[:ND]
-print(f"ROMAN_COO={os.environ.get('ROMAN_COO')} ROMAN_SMALL_FUSED={os.environ.get('ROMAN_SMALL_FUSED')} ROMAN_SMALL_ONLY={os.environ.get('ROMAN_SMALL_ONLY')}: "
+print(f"ROMAN_SMALL_FUSED={os.environ.get('ROMAN_SMALL_FUSED')} ROMAN_SMALL_ONLY={os.environ.get('ROMAN_SMALL_ONLY')}: "
       f"one call at a time {ND / td / 1e6:.2f} M alignments/s ({td * 1e3:.3f} ms per call), three in flight {ND / tp / 1e6:.2f} M/s ({tp * 1e3:.3f} ms per call), stages " + ", ".join(f"{k} {v[0]:.3f}" for k, v in pf.items()) +
       f" | mean live {st['n_live'].mean():.1f}, nnz {st['nnz_upper'].mean():.1f}, passes {st['n_pass'].mean():.2f}, L<=128: {(st['n_live'] <= 128).mean():.3f}, nnz<=384: {(st['nnz_upper'] <= 384).mean():.3f}, "
       f"checksum {int(O[1].sum().item())} {int(O[0].sum().item())}")

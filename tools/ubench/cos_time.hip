@@ -1,5 +1,5 @@
 // Microbenchmark: the cosine kernels of the library on config 3's shape (256 problems of 200 x 200 objects, 512-d descriptors),
-// alone on the device: k_cos_tile<16>, k_cos_deal, and k_cos_deal with parts stripped (template DBG) to see what the rest costs.
+// alone on the device: k_cos_tile, k_cos_deal, and k_cos_deal with parts stripped (template DBG) to see what the rest costs.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o cos_time cos_time.hip
 #include "../../roman_amd/csrc/kernels.hip.h"
 #include <cstdio>
@@ -71,7 +71,7 @@ int main(int argc, char** argv)
     auto ct = [](int n_) { return (((n_ + 15) >> 4) + 3) >> 2; };
     const int Gt = ct(n) * ct(n);
     const dim3 gt((unsigned)(Gt * ((B + 7) / 8) * 8));
-    if (run("k_cos_tile<16>", k_cos_tile<16>, gt, (size_t)2 * 128 * (16 * 8 + 16), D, B, Gt, dP, feats, cosPool)) return 1;
+    if (run("k_cos_tile", k_cos_tile, gt, (size_t)2 * 128 * (16 * 8 + 16), D, B, Gt, dP, feats, cosPool)) return 1;
     std::vector<double> ref((size_t)B * n * n), got(ref.size());
     CK(hipMemcpy(ref.data(), cosPool, ref.size() * 8, hipMemcpyDeviceToHost));
     auto check = [&](const char* name) {
@@ -99,7 +99,7 @@ int main(int argc, char** argv)
     DEAL(5, 2, "k_cos_deal<5> no stores/barriers");
 #define PROBE(T, DBG, label) { using CD = CosDeal<T>; const int Gd = CD::tiles(n) * CD::tiles(n); const dim3 gd((unsigned)(B >= 8 ? Gd * ((B + 7) / 8) * 8 : Gd * B)); \
         if (probe(label, k_cos_deal<T, DBG>, gd, (size_t)CD::LDS, D, B, Gd, dP, feats, cosPool, (const int32_t*)nullptr)) return 1; }
-    if (probe("k_cos_tile<16>", k_cos_tile<16>, gt, (size_t)2 * 128 * (16 * 8 + 16), D, B, Gt, dP, feats, cosPool)) return 1;
+    if (probe("k_cos_tile", k_cos_tile, gt, (size_t)2 * 128 * (16 * 8 + 16), D, B, Gt, dP, feats, cosPool)) return 1;
     PROBE(7, 0, "k_cos_deal<7>");
     PROBE(7, 11, "k_cos_deal<7> no loads/stores/barriers/norms");
     PROBE(5, 0, "k_cos_deal<5>");
