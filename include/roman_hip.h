@@ -460,6 +460,66 @@ ROMAN_API int roman_align_lc_batch(roman_ctx_t* ctx, const roman_params_t* param
                       roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted);
 
 /* ------------------------------------------------------------------------------------------- */
+/* self loop closures: segments both submaps of a pair hold are removed first                  */
+/* ------------------------------------------------------------------------------------------- */
+
+/*
+ * roman_shared_ids_dev: which objects of a pair stay.  For one robot closing loops against its own map
+ * (SubmapAlignParams.single_robot_lc) the reference removes from both submaps every segment whose id occurs in both before it
+ * registers the pair — the ids of either side as sets, their intersection, and both segment lists without the members of it
+ * [REF roman/align/submap_align.py:108-115].  This is that membership test for B pairs over one pool, as a PURE ENQUEUE on the
+ * context's stream (complete once that stream is synchronised).
+ *
+ *   ids        DEVICE, int64: one id per row of the feature pool (full 64-bit equality; an id repeated inside a map is kept or
+ *              dropped with all its repetitions)
+ *   off1/off2  HOST, int64[B], n1/n2 HOST, int32[B]: the two maps of problem b are ids[off1[b] .. +n1[b]) and
+ *              ids[off2[b] .. +n2[b]), as for roman_align_batch_dev (problems may share slices; the two sides may be the same
+ *              slice); the call trusts them to lie inside `ids`.  Maps of length 0 and B == 0 are legal
+ *   keep       DEVICE, int32[sum over b of (n1[b] + n2[b])]: problem b's side-1 list starts at the sum over c < b of
+ *              (n1[c] + n2[c]), its side-2 list n1[b] entries later; each list holds the LOCAL indices (0 .. n-1) of the
+ *              objects that stay, ascending, in its first kept[b][side] entries (the rest of the slot is not written)
+ *   kept       DEVICE, int32[B][2]: objects that stay on side 1 / side 2
+ */
+ROMAN_API int roman_shared_ids_dev(roman_ctx_t* ctx, int32_t B, const int64_t* ids,
+                                   const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                                   int32_t* keep, int32_t* kept);
+
+/*
+ * roman_align_lc_batch_ids: roman_align_lc_batch (HOST pointers everywhere, same arguments, same results) for pairs that first
+ * lose the segments both sides hold — the whole body of the reference's loop for single_robot_lc
+ * ([REF roman/align/submap_align.py:108-115] in front of [REF :150-200] and [REF roman/align/results.py:156-198]) with every
+ * submap uploaded ONCE instead of one reduced copy per pair.
+ *
+ *   ids        int64[n_objects]: one id per row of feats
+ *   n1_kept, n2_kept   int32[B] out: objects of either side that stayed
+ *   keep       int32[sum (n1[b] + n2[b])] out, the layout of roman_shared_ids_dev, or NULL
+ *   assoc      must be NULL: explicit lists index the maps before the removal; given together with ids the call returns
+ *              ROMAN_E_INVALID (text in roman_last_error)
+ *   u0         NULL, or per problem the all-to-all order of the REDUCED maps
+ *
+ * The pool and the ids are uploaded once; the mark step runs; the kept counts come back (8 bytes per problem, one
+ * synchronisation) and size the gather region on the host; k_shared_gather copies the kept rows of the AFFECTED problems
+ * (those that lost an object) behind the pool, bit for bit; those problems then read the gather region with their reduced
+ * sizes — a side reduced to nothing is a map of length 0: ROMAN_ST_EMPTY_MAP — and the others read the shared pool as
+ * given.  From there on the call IS roman_align_lc_batch: chunks, calls in flight, the sizing history, re-issues of skipped
+ * problems, the tail after the final attempt only.  Returned associations index the reduced maps, as the reference's do.
+ * The extra device memory is the rows of the affected problems; when it cannot be had the call returns ROMAN_E_NOMEM and the
+ * context stays usable.
+ */
+ROMAN_API int roman_align_lc_batch_ids(roman_ctx_t* ctx, const roman_params_t* params, int32_t B,
+                      const double* feats, int64_t n_objects,
+                      const int64_t* off1, const int32_t* n1,
+                      const int64_t* off2, const int32_t* n2, int32_t F,
+                      const int32_t* assoc, const int64_t* assoc_off,
+                      const double* u0,
+                      int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
+                      double* T_out, int32_t* status_out, roman_stats_t* stats_out,
+                      const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                      const double* FL, int32_t n_left, const int32_t* iL, const double* FR, int32_t n_right, const int32_t* iR,
+                      roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted,
+                      const int64_t* ids, int32_t* n1_kept, int32_t* n2_kept, int32_t* keep);
+
+/* ------------------------------------------------------------------------------------------- */
 /* multi-solution extraction, batched                                                          */
 /* ------------------------------------------------------------------------------------------- */
 

@@ -24,6 +24,7 @@ class AlignmentBatch:
     assoc: Optional[np.ndarray] = None        # (sum A_b, 2) int32 explicit association lists
     assoc_off: Optional[np.ndarray] = None    # (B+1,) int64
     pair_index: Optional[np.ndarray] = None   # (B,2) (i,j) submap indices, for grid batches
+    ids: Optional[np.ndarray] = None          # (n_objects,) int64 one id per pool row: every problem first loses the ids both its maps hold
 
     def __len__(self):
         return int(self.n1.shape[0])
@@ -114,6 +115,15 @@ def run_lc_batch(registration, batch: AlignmentBatch, lc, u0=None, ctx=None):
     ctx = ctx or registration._context()
     return ctx.align_lc_batch(registration._abi_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2, lc,
                               assoc=batch.assoc, assoc_off=batch.assoc_off, u0=u0, kmax=batch.kmax())
+
+
+def run_lc_batch_ids(registration, batch: AlignmentBatch, lc, u0=None, ctx=None):
+    """One roman_align_lc_batch_ids call for a batch that carries `ids`: the shared-segment removal of self loop closures
+    ([REF roman/align/submap_align.py:108-115]) on the device in front of run_lc_batch's work -> runtime.LoopClosureResult
+    with n1_kept / n2_kept."""
+    ctx = ctx or registration._context()
+    return ctx.align_lc_batch_ids(registration._abi_params(), batch.feats, batch.ids, batch.off1, batch.n1, batch.off2, batch.n2, lc,
+                                  assoc=batch.assoc, assoc_off=batch.assoc_off, u0=u0, kmax=batch.kmax(), want_keep=False)
 
 
 def run_mno_batch(registration, batch: AlignmentBatch, num_solutions=2, ctx=None):

@@ -29,7 +29,7 @@ from scipy.spatial.transform import Rotation as Rot
 
 from .. import _abi
 from ..runtime import LcInputs
-from .batch import AlignmentBatch, pack_submaps, run_batch, run_lc_batch
+from .batch import AlignmentBatch, pack_submaps, run_batch, run_lc_batch, run_lc_batch_ids
 from .dist_reg_with_pruning import _zyx_euler
 from .object_registration import ObjectRegistration
 
@@ -359,14 +359,29 @@ def _quat_to_matrix(q):
     return R
 
 
+def _int64_ids(pool):
+    """seg.id of every object of the pool, one per row, as int64 — or None when an id is not an integer int64 can hold (the
+    device compares 64-bit integers; anything else keeps the set arithmetic of the host)."""
+    out = []
+    for segs in pool:
+        for seg in segs:
+            v = seg.id
+            if not isinstance(v, (int, np.integer)) or not (-2 ** 63 <= int(v) < 2 ** 63):
+                return None
+            out.append(int(v))
+    return np.array(out, dtype=np.int64)
+
+
 def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, registration=None,
                       compute: Optional[Callable] = None) -> SubmapAlignResults:
     """submap_align() for callers that hand over the whole S0 x S1 grid: the same results (and the same state of the caller's
     submaps), with pass 1 ([REF roman/align/submap_align.py:93-149]) vectorised in NumPy over the grid and pass 2
     ([REF :160-200]) plus the loop-closure edges ([REF roman/align/results.py:156-171]) computed behind the solver on the device
     (roman_align_lc_batch).  Python loops run over SUBMAPS (packing, per-submap frames), never over pairs — except where a
-    per-pair list is the input itself: the shared-segment removal of `single_robot_lc` and a registration plugin's host
-    prefilter.
+    per-pair list is the input itself: a registration plugin's host prefilter.  The shared-segment removal of
+    `single_robot_lc` ([REF :108-115]) runs on the device too (roman_align_lc_batch_ids: one id per pool row); it stays a
+    per-pair host loop only with an injected `compute`, with such a plugin (its prefilter reads the reduced lists) or when
+    an id is not an integer that int64 holds.
 
     `compute(registration, AlignmentBatch, runtime.LcInputs) -> runtime.LoopClosureResult` defaults to the HIP path
     (`run_lc_batch`); tests inject a CPU double."""
@@ -474,14 +489,19 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
         return make(empty_edges)
 
     # ---- the hot path: every submap (variant) packed once, ONE batched call with the tail behind it ---------
-    if not sm_params.single_robot_lc:
-        ui, uj = np.unique(ti), np.unique(tj)
-        pool = [list(S[0][i].segments) for i in ui] + [list(S[1][j].segments) for j in uj]
+    scorer = getattr(type(registration), "_associations_to_score", None)
+    host_lists = scorer is not None and scorer is not ObjectRegistration._associations_to_score
+    ui, uj = np.unique(ti), np.unique(tj)
+    pool = [list(S[0][i].segments) for i in ui] + [list(S[1][j].segments) for j in uj]
+    pool_ids = None
+    if sm_params.single_robot_lc and on_device and not host_lists:
+        pool_ids = _int64_ids(pool)                      # self loop closures: the device drops the segments both submaps hold
+    if not sm_params.single_robot_lc or pool_ids is not None:
         slot_i = np.zeros(n0, dtype=np.int64); slot_i[ui] = np.arange(len(ui))
         slot_j = np.zeros(n1, dtype=np.int64); slot_j[uj] = len(ui) + np.arange(len(uj))
         ii, jj = slot_i[ti], slot_j[tj]
         pair_segs = None
-    else:                                                # self loop closures: drop the segments both submaps hold (per pair by nature)
+    else:                                                # ... or the host does, per pair: a reduced copy of both submaps for every pair
         pool, pair_segs = [], []
         for i, j in zip(ti.tolist(), tj.tolist()):
             segs_i, segs_j = list(S[0][i].segments), list(S[1][j].segments)
@@ -492,9 +512,8 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
     feats, offs = pack_submaps(registration, pool)
     plen = np.diff(offs).astype(np.int32)
     batch = AlignmentBatch(feats, offs[ii].astype(np.int64), plen[ii], offs[jj].astype(np.int64), plen[jj],
-                           pair_index=np.stack([ti, tj], axis=1))
-    scorer = getattr(type(registration), "_associations_to_score", None)
-    if scorer is not None and scorer is not ObjectRegistration._associations_to_score:
+                           pair_index=np.stack([ti, tj], axis=1), ids=pool_ids)
+    if host_lists:
         # a pruning plugin scores explicit association lists: its host prefilter reads both maps of a pair
         segs_of = (lambda b: (pool[ii[b]], pool[jj[b]])) if pair_segs is None else (lambda b: pair_segs[b])
         lists = [registration._association_list(*segs_of(b)) if (plen[ii[b]] and plen[jj[b]]) else None for b in range(B)]
@@ -519,7 +538,7 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
                   lc_association_thresh=int(np.ceil(sm_io.lc_association_thresh)) if device_edges else 1,
                   T_ref=T_ij_mat[ti, tj], enable=enable, FL=FL, iL=ti, FR=FR, iR=tj)
     t0 = time.time()
-    res = compute(registration, batch, lc)
+    res = run_lc_batch_ids(registration, batch, lc) if pool_ids is not None else compute(registration, batch, lc)
     timing_list = [(time.time() - t0) / B] * B
 
     # ---- pass 2: the records into the result matrices -------------------------------------------------------

@@ -6754,6 +6754,90 @@ __global__ void __launch_bounds__(1024) k_lc_compact(int B, const roman_lc_recor
     if (tid == 0) *count = total;
 }
 
+// ---------------------------------------------------------------------------------------------
+// shared-segment removal for self loop closures: the reference drops from both submaps of a pair every segment whose id
+// occurs in both before it registers them ([REF roman/align/submap_align.py:108-115]).  One int64 id per row of the feature
+// pool; k_shared_mark lists, per problem and side, the local indices that stay; k_shared_gather copies those rows of the
+// problems that lost something into a region behind the pool (the others keep pointing at the pool).
+// ---------------------------------------------------------------------------------------------
+struct ShareDesc { int64_t off1, off2, keep; int32_t n1, n2; };   // keep: start of the problem's slice of the keep lists (side 1, then side 2)
+struct GatherJob { int64_t src, dst, keep; int32_t n, pad; };     // one side of an affected problem: pool rows src + keep[.] -> rows dst ..
+
+constexpr int SHARE_TILE = 1024;                                 // ids of the other side staged in LDS at a time (8 KB)
+
+// k_shared_mark: one workgroup (NT = 256) or one wave (NT = 64, every map of the call at most 64 objects) per problem.  A lane
+// holds one object of its own side and walks the other side's ids, staged in LDS in tiles and read as broadcasts (every lane
+// the same address); the comparison is the full 64-bit equality, so every repetition of an id inside a map meets the same
+// fate.  Ranks come from the ballot of the survivors plus the counts of the waves in front: the list is ascending, no atomics.
+template <int NT>
+__global__ void __launch_bounds__(NT) k_shared_mark(int B, const ShareDesc* __restrict__ probs, const int64_t* __restrict__ ids,
+                                                    int32_t* __restrict__ keep, int32_t* __restrict__ kept)
+{
+    __shared__ int64_t tile[SHARE_TILE];
+    __shared__ int wcnt[NT / 64];
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const ShareDesc P = probs[b];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (int side = 0; side < 2; ++side) {
+        const int64_t* own = ids + (side ? P.off2 : P.off1); const int nOwn = side ? P.n2 : P.n1;
+        const int64_t* oth = ids + (side ? P.off1 : P.off2); const int nOth = side ? P.n1 : P.n2;
+        int32_t* out = keep + P.keep + (side ? P.n1 : 0);
+        int base = 0;
+        for (int i0 = 0; i0 < nOwn; i0 += NT) {                  // (uniform bounds: every barrier below is met by the whole workgroup)
+            const int i = i0 + tid;
+            const bool valid = i < nOwn;
+            const int64_t mine = valid ? own[i] : 0;
+            bool found = false;
+            for (int t0 = 0; t0 < nOth; t0 += SHARE_TILE) {
+                const int tn = min(SHARE_TILE, nOth - t0);
+                __syncthreads();                                 // the readers of the previous tile are done
+                for (int k = tid; k < tn; k += NT) tile[k] = oth[t0 + k];
+                __syncthreads();
+#pragma unroll 8
+                for (int k = 0; k < tn; ++k) found |= (tile[k] == mine);
+            }
+            const bool stays = valid && !found;
+            const unsigned long long m = __ballot(stays);
+            int before = 0, total = __popcll(m);
+            if (NT > 64) {
+                __syncthreads();                                 // the counts of the previous chunk have been read
+                if (lane == 0) wcnt[wave] = total;
+                __syncthreads();
+                total = 0;
+#pragma unroll
+                for (int w = 0; w < NT / 64; ++w) { const int cw = wcnt[w]; before += (w < wave) ? cw : 0; total += cw; }
+            }
+            if (stays) out[base + before + __popcll(m & lt)] = i;
+            base += total;
+        }
+        if (tid == 0) kept[2 * b + side] = base;
+    }
+}
+
+// k_shared_gather: the kept rows of one side of an affected problem, in order, F doubles per row moved as 64-bit words (bit for
+// bit).  A wave per row, lanes along the row: V2 (F even: every row of the pool and of the gather region is 16-byte aligned)
+// moves 16 bytes per lane, otherwise 8.  grid (jobs, row groups).
+template <bool V2>
+__global__ void __launch_bounds__(256) k_shared_gather(int F, const GatherJob* __restrict__ jobs, const int32_t* __restrict__ keep,
+                                                       unsigned long long* pool)
+{
+    const GatherJob J = jobs[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = blockIdx.y * 4 + wave; r < J.n; r += 4 * gridDim.y) {
+        const unsigned long long* s = pool + (J.src + keep[J.keep + r]) * (int64_t)F;
+        unsigned long long* d = pool + (J.dst + r) * (int64_t)F;
+        if (V2) {
+            const ulonglong2* s2 = reinterpret_cast<const ulonglong2*>(s);
+            ulonglong2* d2 = reinterpret_cast<ulonglong2*>(d);
+            for (int k = lane; k < (F >> 1); k += 64) d2[k] = s2[k];
+        } else {
+            for (int k = lane; k < F; k += 64) d[k] = s[k];
+        }
+    }
+}
+
 
 // elementwise math probe for tests
 __global__ void k_debug_math(int kind, const double* __restrict__ a, const double* __restrict__ b,

@@ -130,6 +130,12 @@ struct roman_ctx {
     unsigned histEpoch = 1;                    // bumped whenever the history is reset for another parameter block
     long long skippedTotal = 0;                // problems reported ROMAN_ST_WORKSPACE so far (harvested totals)
 
+    // shared-segment removal (roman_shared_ids_dev / roman_align_lc_batch_ids): problem descriptors (through pinned staging, so that the
+    // mark step is a pure enqueue), and the host-pointer call's ids | keep lists | kept counts | gather jobs on the device
+    DevBuf shareDesc, shareIds, shareKeep, shareKept, shareJobs;
+    ShareDesc* pinnedShare = nullptr; size_t pinnedShareCap = 0;
+    hipEvent_t shareEvent = nullptr; bool sharePending = false;
+
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
     bool profile = false;
@@ -1398,6 +1404,9 @@ int roman_ctx_destroy(roman_ctx_t* c)
         if (W.done) (void)hipEventDestroy(W.done);
     }
     if (c->hostOut) (void)hipHostFree(c->hostOut);
+    { DevBuf* share[] = {&c->shareDesc, &c->shareIds, &c->shareKeep, &c->shareKept, &c->shareJobs}; for (DevBuf* b : share) b->release(); }
+    if (c->pinnedShare) (void)hipHostFree(c->pinnedShare);
+    if (c->shareEvent) (void)hipEventDestroy(c->shareEvent);
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -1864,6 +1873,100 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
 }  // namespace
 
 namespace {
+// --- shared-segment removal ([REF roman/align/submap_align.py:108-115]) ---------------------------------------------------------
+// k_shared_mark behind whatever is queued on `stream`: a pure enqueue — the problem descriptors travel through pinned staging,
+// and only the previous call's upload out of that staging is waited for.
+int enqueue_shared_mark(roman_ctx* c, hipStream_t stream, int32_t B, const int64_t* dIds, const int64_t* off1, const int32_t* n1,
+                        const int64_t* off2, const int32_t* n2, int32_t* dKeep, int32_t* dKept)
+{
+    if (B <= 0) return ROMAN_OK;
+    if (!c->shareEvent) HIPCHK(c, hipEventCreateWithFlags(&c->shareEvent, hipEventDisableTiming));
+    if (c->sharePending) { HIPCHK(c, hipEventSynchronize(c->shareEvent)); c->sharePending = false; }
+    if (c->pinnedShareCap < (size_t)B) {
+        if (c->pinnedShare) (void)hipHostFree(c->pinnedShare);
+        c->pinnedShare = nullptr; c->pinnedShareCap = 0;
+        const size_t cap = (size_t)B + (size_t)B / 4 + 64;
+        HIPCHK(c, hipHostMalloc((void**)&c->pinnedShare, sizeof(ShareDesc) * cap, hipHostMallocDefault));
+        c->pinnedShareCap = cap;
+    }
+    int64_t kb = 0; int32_t maxN = 0;
+    for (int b = 0; b < B; ++b) {
+        c->pinnedShare[b] = ShareDesc{off1[b], off2[b], kb, n1[b], n2[b]};
+        kb += (int64_t)n1[b] + n2[b];
+        maxN = std::max(maxN, std::max(n1[b], n2[b]));
+    }
+    HIPCHK(c, c->shareDesc.ensure(sizeof(ShareDesc) * (size_t)B));
+    HIPCHK(c, hipMemcpyAsync(c->shareDesc.p, c->pinnedShare, sizeof(ShareDesc) * (size_t)B, hipMemcpyHostToDevice, stream));
+    HIPCHK(c, hipEventRecord(c->shareEvent, stream));
+    c->sharePending = true;
+    if (maxN <= 64) hipLaunchKernelGGL(k_shared_mark<64>, dim3((unsigned)B), dim3(64), 0, stream, (int)B, c->shareDesc.as<ShareDesc>(), dIds, dKeep, dKept);
+    else hipLaunchKernelGGL(k_shared_mark<256>, dim3((unsigned)B), dim3(256), 0, stream, (int)B, c->shareDesc.as<ShareDesc>(), dIds, dKeep, dKept);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+// The ids of a host-pointer call and where the removal's results go (roman_align_lc_batch_ids).
+struct IdsHostIn { const int64_t* ids; int32_t* n1_kept; int32_t* n2_kept; int32_t* keep; };
+
+// The problem list after the removal: affected problems (those that lost an object on either side) point into the gather region
+// behind the pool with their reduced sizes, the others are as the caller gave them.
+struct ReducedProblems {
+    std::vector<int64_t> off1, off2; std::vector<int32_t> n1, n2;
+    std::vector<GatherJob> jobs; int64_t rows = 0; int32_t maxRows = 0;     // gather region: rows of the affected problems only
+};
+
+// Upload the ids, run the mark step, read the kept counts back (one synchronisation) and lay the gather region out on the host.
+int shared_mark_host(roman_ctx* c, int32_t B, int64_t n_objects, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                     const IdsHostIn& I, ReducedProblems* R)
+{
+    int64_t sumN = 0;
+    for (int b = 0; b < B; ++b) sumN += (int64_t)n1[b] + n2[b];
+    HIPCHK(c, c->shareIds.ensure(sizeof(int64_t) * (size_t)std::max<int64_t>(n_objects, 1)));
+    HIPCHK(c, c->shareKeep.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(sumN, 1)));
+    HIPCHK(c, c->shareKept.ensure(sizeof(int32_t) * 2 * (size_t)B));
+    if (n_objects > 0) HIPCHK(c, hipMemcpyAsync(c->shareIds.p, I.ids, sizeof(int64_t) * (size_t)n_objects, hipMemcpyHostToDevice, WS.stream));
+    int rc = enqueue_shared_mark(c, WS.stream, B, c->shareIds.as<int64_t>(), off1, n1, off2, n2, c->shareKeep.as<int32_t>(), c->shareKept.as<int32_t>());
+    if (rc) return rc;
+    std::vector<int32_t> kv((size_t)B * 2);
+    HIPCHK(c, hipMemcpyAsync(kv.data(), c->shareKept.p, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyDeviceToHost, WS.stream));
+    if (I.keep && sumN > 0) HIPCHK(c, hipMemcpyAsync(I.keep, c->shareKeep.p, sizeof(int32_t) * (size_t)sumN, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipStreamSynchronize(WS.stream));
+    R->off1.assign(off1, off1 + B); R->off2.assign(off2, off2 + B); R->n1.assign(n1, n1 + B); R->n2.assign(n2, n2 + B);
+    int64_t kb = 0, g = n_objects;
+    for (int b = 0; b < B; ++b) {
+        const int32_t k1 = kv[2 * (size_t)b], k2 = kv[2 * (size_t)b + 1];
+        if (k1 < 0 || k1 > n1[b] || k2 < 0 || k2 > n2[b]) return fail(c, ROMAN_E_HIP, "problem %d: the mark step reported %d / %d kept of %d / %d objects", b, k1, k2, n1[b], n2[b]);
+        I.n1_kept[b] = k1; I.n2_kept[b] = k2;
+        if (k1 != n1[b] || k2 != n2[b]) {
+            if (k1 > 0) R->jobs.push_back(GatherJob{off1[b], g, kb, k1, 0});
+            R->off1[b] = g; R->n1[b] = k1; g += k1;
+            if (k2 > 0) R->jobs.push_back(GatherJob{off2[b], g, kb + n1[b], k2, 0});
+            R->off2[b] = g; R->n2[b] = k2; g += k2;
+            R->maxRows = std::max(R->maxRows, std::max(k1, k2));
+        }
+        kb += (int64_t)n1[b] + n2[b];
+    }
+    R->rows = g - n_objects;
+    return ROMAN_OK;
+}
+
+// k_shared_gather: the kept rows of the affected problems into the gather region behind the pool (dFeats holds pool + region).
+int enqueue_shared_gather(roman_ctx* c, hipStream_t stream, int32_t F, const ReducedProblems& R, double* dFeats)
+{
+    if (R.jobs.empty() || F <= 0) return ROMAN_OK;
+    if (R.jobs.size() > (size_t)0x7fffffff) return fail(c, ROMAN_E_TOO_LARGE, "too many problems lost shared segments for one gather launch");
+    HIPCHK(c, c->shareJobs.ensure(sizeof(GatherJob) * R.jobs.size()));
+    HIPCHK(c, hipMemcpyAsync(c->shareJobs.p, R.jobs.data(), sizeof(GatherJob) * R.jobs.size(), hipMemcpyHostToDevice, stream));
+    const dim3 grid((unsigned)R.jobs.size(), (unsigned)std::min(8, std::max(1, (R.maxRows + 3) / 4)));
+    unsigned long long* pool = reinterpret_cast<unsigned long long*>(dFeats);
+    if (F % 2 == 0) hipLaunchKernelGGL(k_shared_gather<true>, grid, dim3(256), 0, stream, (int)F, c->shareJobs.as<GatherJob>(), c->shareKeep.as<int32_t>(), pool);
+    else hipLaunchKernelGGL(k_shared_gather<false>, grid, dim3(256), 0, stream, (int)F, c->shareJobs.as<GatherJob>(), c->shareKeep.as<int32_t>(), pool);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+}  // namespace
+
+namespace {
 // The host arrays of the tail of roman_align_lc_batch (checked and staged behind the batch inputs).
 struct LcHostIn {
     const roman_lc_params_t* P; const double* T_ref; const int32_t* enable; const double* FL; int32_t n_left; const int32_t* iL;
@@ -1875,10 +1978,15 @@ int align_batch_host(roman_ctx_t* c, const roman_params_t* params, int32_t B,
                       const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
                       const int32_t* assoc, const int64_t* assoc_off, const double* u0,
                       int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
-                      double* T_out, int32_t* status_out, roman_stats_t* stats_out, const LcHostIn* lci)
+                      double* T_out, int32_t* status_out, roman_stats_t* stats_out, const LcHostIn* lci, const IdsHostIn* idh = nullptr)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (B < 0 || n_objects < 0 || F < 0) return fail(c, ROMAN_E_INVALID, "negative size");
+    if (idh) {
+        if (assoc) return fail(c, ROMAN_E_INVALID, "explicit association lists cannot be combined with the removal of shared ids (they would index the lists before the removal): assoc must be NULL");
+        if (!idh->ids && n_objects > 0) return fail(c, ROMAN_E_INVALID, "ids is NULL");
+        if (B > 0 && (!idh->n1_kept || !idh->n2_kept)) return fail(c, ROMAN_E_INVALID, "n1_kept / n2_kept is NULL");
+    }
     if (lci) {
         int rc0 = check_lc_params(c, lci->P);
         if (rc0) return rc0;
@@ -1915,9 +2023,19 @@ int align_batch_host(roman_ctx_t* c, const roman_params_t* params, int32_t B,
         const int64_t na = assoc ? (assoc_off[b + 1] - assoc_off[b]) : 0;
         sumA += na > 0 ? na : (int64_t)n1[b] * n2[b];      // an empty list means all-to-all
     }
-    const size_t fbytes = sizeof(double) * (size_t)std::max<int64_t>(n_objects * F, 1);
+    ReducedProblems red;
+    if (idh) {
+        // mark, read the kept counts back, size the gather region: from here on the problems are the reduced ones
+        rc = shared_mark_host(c, B, n_objects, off1, n1, off2, n2, *idh, &red);
+        if (rc) return rc;
+        off1 = red.off1.data(); n1 = red.n1.data(); off2 = red.off2.data(); n2 = red.n2.data();
+        sumA = 0;
+        for (int b = 0; b < B; ++b) sumA += (int64_t)n1[b] * n2[b];
+    }
+    const size_t fbytes = sizeof(double) * (size_t)std::max<int64_t>((n_objects + red.rows) * F, 1);   // the pool, and the rows of the affected problems behind it
     HIPCHK(c, WS.hFeats.ensure(fbytes));
     if (n_objects * F > 0) HIPCHK(c, hipMemcpyAsync(WS.hFeats.p, feats, sizeof(double) * (size_t)(n_objects * F), hipMemcpyHostToDevice, WS.stream));
+    if (idh) { rc = enqueue_shared_gather(c, WS.stream, F, red, WS.hFeats.as<double>()); if (rc) return rc; }
     const int32_t* dA = nullptr;
     if (assoc) {
         const int64_t rows = assoc_off[B];
@@ -1982,6 +2100,42 @@ int roman_align_lc_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B
 {
     const LcHostIn lci{lc_params, T_ref, enable, FL, n_left, iL, FR, n_right, iR, records, accepted_idx, n_accepted};
     return align_batch_host(c, params, B, feats, n_objects, off1, n1, off2, n2, F, assoc, assoc_off, u0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out, &lci);
+}
+
+/* roman_align_lc_batch with the shared-segment removal of single-robot loop closures in front
+   ([REF roman/align/submap_align.py:108-115]): every submap is uploaded once, the removal runs on the device. */
+int roman_align_lc_batch_ids(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                      const double* feats, int64_t n_objects,
+                      const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
+                      const int32_t* assoc, const int64_t* assoc_off, const double* u0,
+                      int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
+                      double* T_out, int32_t* status_out, roman_stats_t* stats_out,
+                      const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                      const double* FL, int32_t n_left, const int32_t* iL, const double* FR, int32_t n_right, const int32_t* iR,
+                      roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted,
+                      const int64_t* ids, int32_t* n1_kept, int32_t* n2_kept, int32_t* keep)
+{
+    const LcHostIn lci{lc_params, T_ref, enable, FL, n_left, iL, FR, n_right, iR, records, accepted_idx, n_accepted};
+    const IdsHostIn idh{ids, n1_kept, n2_kept, keep};
+    return align_batch_host(c, params, B, feats, n_objects, off1, n1, off2, n2, F, assoc, assoc_off, u0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out, &lci, &idh);
+}
+
+/* The mark step alone on the context's stream, all bulk pointers DEVICE: a pure enqueue. */
+int roman_shared_ids_dev(roman_ctx_t* c, int32_t B, const int64_t* ids, const int64_t* off1, const int32_t* n1,
+                         const int64_t* off2, const int32_t* n2, int32_t* keep, int32_t* kept)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
+    if (B == 0) return ROMAN_OK;
+    if (!off1 || !n1 || !off2 || !n2 || !kept) return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer");
+    int64_t sumN = 0;
+    for (int b = 0; b < B; ++b) {
+        if (n1[b] < 0 || n2[b] < 0 || off1[b] < 0 || off2[b] < 0) return fail(c, ROMAN_E_INVALID, "problem %d: negative size or offset", b);
+        sumN += (int64_t)n1[b] + n2[b];
+    }
+    if (sumN > 0 && (!ids || !keep)) return fail(c, ROMAN_E_INVALID, "ids / keep is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_shared_mark(c, c->stream, B, ids, off1, n1, off2, n2, keep, kept);
 }
 
 /* roman_align_batch_resident: inputs in HBM (as roman_align_batch_dev), results on the HOST (as roman_align_batch). */

@@ -102,6 +102,11 @@ class LoopClosureResult(BatchResult):
     """A batch result with the loop-closure tail behind it."""
     records: np.ndarray    # (B,) structured array (lc_record_dtype)
     accepted: np.ndarray   # (n_accepted,) int32: accepted problems, ascending
+    # align_lc_batch_ids only (shared-segment removal in front): the objects of either side that stayed, and the ascending local
+    # indices of those objects (problem b's side-1 list from sum over c < b of (n1[c] + n2[c]), its side-2 list n1[b] later)
+    n1_kept: Optional[np.ndarray] = None
+    n2_kept: Optional[np.ndarray] = None
+    keep: Optional[np.ndarray] = None
 
 
 class Context:
@@ -365,6 +370,61 @@ class Context:
             raise err
         self._check(rc, "roman_align_lc_batch")
         return res()
+
+    def align_lc_batch_ids(self, params, feats, ids, off1, n1, off2, n2, lc, assoc=None, assoc_off=None, u0=None, kmax=None, want_keep=True):
+        """align_lc_batch() for self loop closures (roman_align_lc_batch_ids): `ids` holds one int64 per row of `feats`; every
+        problem first loses the objects whose id occurs on both of its sides — on the device, over the pool that holds every
+        submap once.  -> LoopClosureResult with n1_kept, n2_kept (and keep, the kept local indices, unless want_keep is False);
+        associations index the reduced maps.  `assoc` must stay None (the library refuses explicit lists together with ids)."""
+        feats = _f64(feats)
+        if feats.ndim != 2:
+            raise ValueError("feats must be (n_objects, F)")
+        n_obj, F = feats.shape
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        if ids.shape[0] != n_obj:
+            raise ValueError("ids must hold one entry per row of feats")
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        B = int(n1.shape[0])
+        if assoc is not None:
+            assoc = np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2)
+            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        if u0 is not None:
+            u0 = _f64(u0)
+        if kmax is None:
+            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
+        a_out = np.zeros((B, kmax, 2), dtype=np.int32); n_out = np.zeros(B, dtype=np.int32)
+        T = np.zeros((B, 16), dtype=np.float64); status = np.zeros(B, dtype=np.int32); stats = np.zeros(B, dtype=stats_dtype())
+        records = np.zeros(B, dtype=lc_record_dtype()); idx = np.zeros(max(B, 1), dtype=np.int32); cnt = np.zeros(1, dtype=np.int32)
+        k1 = np.zeros(B, dtype=np.int32); k2 = np.zeros(B, dtype=np.int32)
+        keep = np.full(int(n1.sum(dtype=np.int64) + n2.sum(dtype=np.int64)), -1, dtype=np.int32) if want_keep else None
+        lp = lc.params()
+        T_ref, enable, FL, iL, FR, iR = lc.arrays(B)
+        self._generation += 1
+        rc = self._lib.roman_align_lc_batch_ids(self._h, C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
+                                                _ptr(assoc), _ptr(assoc_off), _ptr(u0), kmax, _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats),
+                                                C.byref(lp), _ptr(T_ref), _ptr(enable), _ptr(FL), 0 if FL is None else FL.shape[0], _ptr(iL),
+                                                _ptr(FR), 0 if FR is None else FR.shape[0], _ptr(iR), _ptr(records), _ptr(idx), _ptr(cnt),
+                                                _ptr(ids), _ptr(k1), _ptr(k2), _ptr(keep))
+        s = params.point_dim + 1
+        res = lambda: LoopClosureResult([a_out[b, :n_out[b]].copy() for b in range(B)], T[:, :s * s].reshape(B, s, s).copy(), status, stats,
+                                        records, idx[:int(cnt[0])].copy(), k1, k2, keep)
+        if rc == _abi.ROMAN_E_INTERNAL:                          # outputs were copied: the error says which problems have no result
+            msg = self._lib.roman_last_error(self._h)
+            err = RomanHipError(f"roman_align_lc_batch_ids failed ({rc}): {msg.decode() if msg else ''}")
+            err.result = res()
+            raise err
+        self._check(rc, "roman_align_lc_batch_ids")
+        return res()
+
+    def shared_ids_dev(self, B, ids_ptr, off1, n1, off2, n2, keep_ptr, kept_ptr):
+        """The mark step of the shared-segment removal on its own (roman_shared_ids_dev): ids, keep and kept are device addresses
+        (integers), the offsets and sizes host arrays.  A pure enqueue on the context's stream; complete after sync()."""
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_shared_ids_dev(self._h, int(B), vp(ids_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), vp(keep_ptr), vp(kept_ptr))
+        self._check(rc, "roman_shared_ids_dev")
 
     def lc_tail_dev(self, lc_params, B, T_ptr, n_assoc_ptr, status_ptr, records_ptr, accepted_idx_ptr, n_accepted_ptr,
                     T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None, FR_ptr=None, iR_ptr=None):
