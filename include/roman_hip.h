@@ -583,6 +583,79 @@ ROMAN_API int roman_mno_batch(roman_ctx_t* ctx, const roman_params_t* params, in
                               roman_mno_solution_t* sol_out, roman_stats_t* stats_out);
 
 /* ------------------------------------------------------------------------------------------- */
+/* RANSAC registration on object centres, batched (method 'ransac')                            */
+/* ------------------------------------------------------------------------------------------- */
+
+/* RansacReg.register(map1, map2) [REF roman/align/ransac_reg.py:16-53] for B independent submap pairs, with the pose of the
+   inherited T_align [REF roman/align/object_registration.py:88-129] on the result.  The reference hands the object centres and
+   all n1*n2 correspondences (i, j), row-major, to open3d's registration_ransac_based_on_correspondence (ransac_n 3, an
+   edge-length checker, max_correspondence_distance 0.5, confidence 0.999).  open3d samples from a thread-local generator and
+   stops on thread timing, so its result cannot be reproduced; this call runs a DETERMINISTIC procedure with the same
+   ingredients (DESIGN.md §4.7 is the contract).  Per problem, P = the n1 centres of map 1 (source), Q = the n2 of map 2 (target):
+     - hypothesis h takes the correspondences a_k = mulhi64(draw(3h + k), n1*n2), k = 0, 1, 2, (i_k, j_k) = (a_k / n2, a_k % n2);
+       draw(c) is output c + 1 of splitmix64 seeded with `seed` (the same seed for every problem of a batch);
+     - DEVIATION: a hypothesis two of whose correspondences share a source or a target index is dropped (open3d lets such
+       zero-edge triples through its checker).  Otherwise open3d's edge-length check: for each of the three index pairs, with
+       ds = |P[i_k] - P[i_l]|, dt = |Q[j_k] - Q[j_l]|, dropped when ds < dt * edge_len or dt < ds * edge_len;
+     - the rigid transform source -> target of the three pairs is the library's Kabsch fit (the arithmetic of T_align);
+     - every correspondence (i, j) with d2 = |R P[i] + t - Q[j]|^2 < max_dist^2 is an inlier; key = (count, sum of d2 over the
+       inliers in row-major order); higher count wins, then lower sum, then lower h (open3d's IsBetterRANSACThan made total);
+     - DEVIATION: hypotheses are processed in rounds of `round` consecutive indices and the early stop is decided after whole
+       rounds only: with f = best count / (n1*n2), K = max_iteration when f = 0 (or when log(1 - f^3) rounds to 0), 0 when
+       f = 1, else min(max_iteration, ceil(log(1 - confidence) / log(1 - f^3))); the problem stops once the hypotheses
+       processed reach K or max_iteration (the last round is cut there).  The result is a function of the inputs alone;
+     - the winner's inliers go out as (i, j) rows in row-major order (open3d's correspondence_set), the pose is Arun's fit on
+       exactly those rows, map 2 -> map 1. */
+typedef struct roman_ransac_params {
+    int64_t  max_iteration;   /* >= 1: RansacReg.max_iteration [REF roman/align/ransac_reg.py:10,50]                         */
+    int32_t  round;           /* >= 1: hypotheses between two evaluations of the stop rule                                   */
+    double   edge_len;        /* (0, 1]: RansacReg.edge_len [REF roman/align/ransac_reg.py:49]                               */
+    double   max_dist;        /* > 0: max_correspondence_distance [REF roman/align/ransac_reg.py:47]                         */
+    double   confidence;      /* (0, 1): open3d's RANSACConvergenceCriteria.confidence (0.999)                               */
+    uint64_t seed;
+} roman_ransac_params_t;
+
+typedef struct roman_ransac_record {
+    int32_t n_assoc;          /* inliers of the winner (the FULL count, also when assoc_out holds only kmax of them)          */
+    int32_t status;           /* ROMAN_ST_OK / EMPTY_MAP / INSUFFICIENT (no surviving hypothesis, or fewer than 3 inliers) / ASSOC_TRUNCATED */
+    int64_t n_hyp;            /* hypotheses processed                                                                        */
+    int64_t n_scored;         /* ... of which survived the prune                                                             */
+    int64_t best_hyp;         /* index of the winner; -1: none                                                               */
+    int32_t best_count;       /* its inlier count                                                                            */
+    double  best_sse;         /* its sum of squared inlier distances                                                         */
+    double  T[16];            /* pose map 2 -> map 1, row-major 4x4; NaN with ROMAN_ST_INSUFFICIENT / ROMAN_ST_EMPTY_MAP     */
+} roman_ransac_record_t;
+
+#define ROMAN_RANSAC_MAX_OBJECTS 1024   /* objects per side (both point sets of a problem stay in LDS: 48 KB); more: ROMAN_E_TOO_LARGE */
+
+/*
+ * roman_ransac_batch_dev [REF roman/align/ransac_reg.py:16-53]: bulk data device-resident; a PURE ENQUEUE on the context's
+ * stream (at every pipeline depth), complete once that stream is synchronised.  One workgroup per problem runs all rounds.
+ *   pts        DEVICE, float64: pool of object centres, 3 doubles per object (dim 3 only, as the reference asserts)
+ *   off1/off2  HOST, int64[B], n1/n2 HOST, int32[B]: as for roman_align_batch_dev (trusted to lie inside `pts`)
+ *   kmax       capacity (rows) of each problem's slot in assoc_out
+ *   assoc_out  DEVICE, int32[B][kmax][2]: the winner's inliers, row-major order; more inliers than kmax:
+ *              ROMAN_ST_ASSOC_TRUNCATED, the first kmax rows, n_assoc / key / pose from the full set
+ *   rec_out    DEVICE, roman_ransac_record_t[B]
+ *   counts_out DEVICE, int32[B][max_iteration] or NULL: the inlier count of every processed hypothesis, -1 for a pruned one;
+ *              untouched beyond n_hyp (one extra store per hypothesis: how the tests see inside)
+ * Errors: max_iteration < 1, round < 1, edge_len outside (0, 1], max_dist <= 0, confidence outside (0, 1) -> ROMAN_E_INVALID;
+ * a side above ROMAN_RANSAC_MAX_OBJECTS -> ROMAN_E_TOO_LARGE.  An empty map: ROMAN_ST_EMPTY_MAP, no rows, NaN pose.
+ */
+ROMAN_API int roman_ransac_batch_dev(roman_ctx_t* ctx, const roman_ransac_params_t* rparams, int32_t B,
+                                     const double* pts, const int64_t* off1, const int32_t* n1,
+                                     const int64_t* off2, const int32_t* n2,
+                                     int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out);
+
+/* The same with HOST pointers everywhere ([REF roman/align/ransac_reg.py:16-53] for a caller that holds NumPy arrays);
+   `n_objects` = number of objects in `pts`.  Synchronous; the batch is issued in calls of the host-batching chunk
+   (roman_ctx_set_host_batching), all on the context's stream. */
+ROMAN_API int roman_ransac_batch(roman_ctx_t* ctx, const roman_ransac_params_t* rparams, int32_t B,
+                                 const double* pts, int64_t n_objects, const int64_t* off1, const int32_t* n1,
+                                 const int64_t* off2, const int32_t* n2,
+                                 int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out);
+
+/* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */
 /* ------------------------------------------------------------------------------------------- */
 

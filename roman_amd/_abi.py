@@ -11,6 +11,8 @@ ROMAN_MAX_RATIO_FEATURES = 8
 
 # error codes / status flags (include/roman_hip.h)
 ROMAN_OK = 0
+ROMAN_E_INVALID = -1
+ROMAN_E_TOO_LARGE = -6
 ROMAN_E_INTERNAL = -7
 ROMAN_ST_OK = 0
 ROMAN_ST_EMPTY_MAP = 1
@@ -171,8 +173,38 @@ class RomanMnoSolution(C.Structure):
 ROMAN_MNO_MAX_SOLUTIONS = 64
 ROMAN_MNO_MAX_ASSOC = 3072
 
+
+class RomanRansacParams(C.Structure):
+    """roman_ransac_params_t"""
+    _fields_ = [
+        ("max_iteration", C.c_int64),
+        ("round", C.c_int32),
+        ("edge_len", C.c_double),
+        ("max_dist", C.c_double),
+        ("confidence", C.c_double),
+        ("seed", C.c_uint64),
+    ]
+
+
+class RomanRansacRecord(C.Structure):
+    """roman_ransac_record_t"""
+    _fields_ = [
+        ("n_assoc", C.c_int32),
+        ("status", C.c_int32),
+        ("n_hyp", C.c_int64),
+        ("n_scored", C.c_int64),
+        ("best_hyp", C.c_int64),
+        ("best_count", C.c_int32),
+        ("best_sse", C.c_double),
+        ("T", C.c_double * 16),
+    ]
+
+
+ROMAN_RANSAC_MAX_OBJECTS = 1024
+
 STATS_NBYTES = C.sizeof(RomanStats)
 MNO_SOLUTION_NBYTES = C.sizeof(RomanMnoSolution)
+RANSAC_RECORD_NBYTES = C.sizeof(RomanRansacRecord)
 LC_PARAMS_NBYTES = C.sizeof(RomanLcParams)
 LC_RECORD_NBYTES = C.sizeof(RomanLcRecord)
 PARAMS_NBYTES = C.sizeof(RomanParams)
@@ -237,6 +269,8 @@ def load_library():
                                           vp, vp, i32, i32, vp, vp, vp]),
         "roman_mno_batch": (C.c_int, [ctxp, P(RomanParams), i32, vp, i64, vp, vp, vp, vp, i32,
                                       vp, vp, i32, i32, vp, vp, vp]),
+        "roman_ransac_batch_dev": (C.c_int, [ctxp, P(RomanRansacParams), i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
+        "roman_ransac_batch": (C.c_int, [ctxp, P(RomanRansacParams), i32, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]),
         "roman_ctx_has_history": (C.c_int, [ctxp, P(RomanParams), i32, P(i32)]),
         "roman_ctx_cosine_screen_stats": (C.c_int, [ctxp, P(C.c_int64), P(C.c_int64), P(C.c_double)]),
         "roman_create_all_to_all": (C.c_int, [i32, i32, vp]),
@@ -271,7 +305,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

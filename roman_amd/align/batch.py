@@ -11,6 +11,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from .. import _abi
+from .ransac_reg import RansacReg
 
 
 @dataclass
@@ -103,10 +104,23 @@ def batch_from_submap_grid(registration, submaps0, submaps1, mask=None) -> Align
 
 
 def run_batch(registration, batch: AlignmentBatch, u0=None, ctx=None):
-    """One roman_align_batch call for `batch` -> runtime.BatchResult."""
+    """One roman_align_batch call for `batch` -> runtime.BatchResult (a RansacReg: one roman_ransac_batch call ->
+    runtime.RansacResult)."""
     ctx = ctx or registration._context()
+    if isinstance(registration, RansacReg):
+        if u0 is not None:
+            raise ValueError("RANSAC registration has no initial vector")
+        return run_ransac_batch(registration, batch, ctx=ctx)
     return ctx.align_batch(registration._abi_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2,
                            assoc=batch.assoc, assoc_off=batch.assoc_off, u0=u0, kmax=batch.kmax())
+
+
+def run_ransac_batch(registration, batch: AlignmentBatch, ctx=None, counts=None):
+    """One roman_ransac_batch call for `batch` (its pool holds object centres, 3 columns): register() + T_align() of a RansacReg
+    ([REF roman/align/ransac_reg.py:16-53]) for every pair -> runtime.RansacResult."""
+    ctx = ctx or registration._context()
+    kmax = int(max(1, np.max(batch.n1.astype(np.int64) * batch.n2))) if len(batch) else 1       # every correspondence may be an inlier
+    return ctx.ransac_batch(registration._ransac_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2, kmax=kmax, counts=counts)
 
 
 def run_lc_batch(registration, batch: AlignmentBatch, lc, u0=None, ctx=None):

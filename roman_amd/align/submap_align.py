@@ -32,6 +32,7 @@ from ..runtime import LcInputs
 from .batch import AlignmentBatch, pack_submaps, run_batch, run_lc_batch, run_lc_batch_ids
 from .dist_reg_with_pruning import _zyx_euler
 from .object_registration import ObjectRegistration
+from .ransac_reg import RansacReg
 
 
 # ---------------------------------------------------------------------------------------------
@@ -387,6 +388,9 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
     (`run_lc_batch`); tests inject a CPU double."""
     sm_io = sm_io or SubmapAlignIO()
     registration = registration or sm_params.get_object_registration()
+    if isinstance(registration, RansacReg):
+        raise NotImplementedError("submap_align_grid builds on roman_align_lc_batch; RANSAC registration has no device tail yet "
+                                  "(use submap_align)")
     on_device = compute is None
     compute = compute or run_lc_batch
     S = [list(submaps[0]), list(submaps[1])]

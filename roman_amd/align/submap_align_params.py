@@ -8,6 +8,7 @@ import yaml
 
 from .. import _abi
 from .dist_reg_with_pruning import DistRegWithPruning
+from .ransac_reg import RansacReg
 from .roman_registration import ROMANParams, ROMANRegistration
 
 
@@ -89,9 +90,9 @@ class SubmapAlignParams:
                 sigma=self.sigma, epsilon=self.epsilon, mindist=self.mindist,
                 shape_epsilon=self.epsilon_shape, cos_min=self.cosine_min, dim=self.dim, use_gravity=True)
         elif self.method == 'ransac':
-            # [REF roman/align/ransac_reg.py:14]: the reference's own constructor raises TypeError
-            # (4 positional args to a 1-arg base) — an open3d comparison baseline, out of scope.
-            raise NotImplementedError("method 'ransac' is an open3d baseline outside the roman.align hot path")
+            # [REF roman/params/submap_align_params.py:145-147] builds RansacReg(dim=..., max_iteration=ransac_iter); the
+            # reference's own constructor then raises TypeError ([REF roman/align/ransac_reg.py:14]) — this one runs
+            registration = RansacReg(dim=self.dim, max_iteration=self.ransac_iter)
         else:
             assert False, "Invalid method"
         return registration

@@ -6593,6 +6593,330 @@ __global__ void __launch_bounds__(64) k_pose(int dim, const double* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_ransac: RANSAC registration on object centres ([REF roman/align/ransac_reg.py:16-53]; the deterministic procedure of
+// DESIGN.md §4.7), one 256-thread workgroup per problem, every round inside the kernel.
+//   - both point sets are staged in LDS once (24 bytes per object);
+//   - generation: every lane draws and prunes one hypothesis of the round (integer mixing, six LDS point reads); the survivors of
+//     a wave are compacted with a ballot into that wave's LDS queue (k_lists' idea);
+//   - scoring: as soon as a queue holds 64 survivors the wave scores them, one per lane — the Kabsch fit in registers, then a
+//     uniform loop over i (transform P[i] once) and j (compare with Q[j]): every lane reads the same LDS address in a step, a
+//     broadcast; count and sum stay in registers.  A round's last, partial set is scored with the idle lanes masked;
+//   - argmax: each lane keeps the best key (count, sse, h) it has seen; after a round the keys are reduced over the wave
+//     (cross-lane moves) and over the four waves (LDS), and EVERY thread evaluates the stop rule on the same numbers;
+//   - output: each wave sweeps a contiguous quarter of the n1*n2 correspondences twice — counts and centroid sums first, then
+//     the rows (ballot + running prefix: row-major order) and the centred cross-covariance — and thread 0 forms the pose with
+//     write_pose.  The sums cover ALL inliers whatever kmax is; nothing here depends on what else is in the batch.
+// ---------------------------------------------------------------------------------------------
+struct RansacDesc { int64_t off1, off2; int32_t n1, n2; };
+
+constexpr int RANSAC_NT = 256, RANSAC_NW = RANSAC_NT / 64, RANSAC_QCAP = 128;
+
+// output c + 1 of splitmix64 seeded with `seed`
+__device__ __forceinline__ uint64_t ransac_draw(uint64_t seed, uint64_t c)
+{
+    uint64_t z = seed + (c + 1ull) * 0x9E3779B97F4A7C15ull;
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull; z ^= z >> 27; z *= 0x94D049BB133111EBull; z ^= z >> 31;
+    return z;
+}
+
+// the three correspondences of hypothesis h
+__device__ __forceinline__ void ransac_sample(uint64_t seed, uint64_t nm, uint32_t m, int64_t h, int (&si)[3], int (&sj)[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t a = (uint32_t)__umul64hi(ransac_draw(seed, 3ull * (uint64_t)h + (uint64_t)k), nm);   // < nm <= 2^20
+        si[k] = (int)(a / m); sj[k] = (int)(a % m);
+    }
+}
+
+// the prune: distinct indices on both sides, then open3d's edge-length check on the three index pairs
+__device__ __forceinline__ bool ransac_keep(const double* sP, const double* sQ, const int (&si)[3], const int (&sj)[3], double edge_len)
+{
+    if (si[0] == si[1] || si[0] == si[2] || si[1] == si[2] || sj[0] == sj[1] || sj[0] == sj[2] || sj[1] == sj[2]) return false;
+    bool keep = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int l = (k + 1) % 3;
+        double s2 = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double a = sP[si[k] * 3 + c] - sP[si[l] * 3 + c], q = sQ[sj[k] * 3 + c] - sQ[sj[l] * 3 + c];
+            s2 += a * a; t2 += q * q;
+        }
+        const double ds = sqrt(s2), dt = sqrt(t2);
+        if (ds < dt * edge_len || dt < ds * edge_len) keep = false;
+    }
+    return keep;
+}
+
+// Kabsch fit source -> target of the three sampled pairs: T (row-major 4x4) with T P[i_k] ~ Q[j_k]
+__device__ __forceinline__ void ransac_fit(const double* sP, const double* sQ, const int (&si)[3], const int (&sj)[3], double (&T)[16])
+{
+    double mq[3], mp[3], H[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        mq[c] = (sQ[sj[0] * 3 + c] + sQ[sj[1] * 3 + c] + sQ[sj[2] * 3 + c]) / 3.0;
+        mp[c] = (sP[si[0] * 3 + c] + sP[si[1] * 3 + c] + sP[si[2] * 3 + c]) / 3.0;
+    }
+#pragma unroll
+    for (int e = 0; e < 9; ++e) H[e] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) H[r * 3 + c] += (sQ[sj[k] * 3 + r] - mq[r]) * (sP[si[k] * 3 + c] - mp[c]);
+    write_pose(T, 3, H, mq, mp);
+}
+
+// R p + t, and the squared distance to q: ONE expression for the scoring loop and the output sweeps (same bits, same decisions)
+__device__ __forceinline__ void ransac_apply(const double (&T)[16], const double* p, double (&tp)[3])
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r) tp[r] = T[r * 4] * p[0] + T[r * 4 + 1] * p[1] + T[r * 4 + 2] * p[2] + T[r * 4 + 3];
+}
+__device__ __forceinline__ double ransac_d2(const double (&tp)[3], const double* q)
+{
+    const double dx = tp[0] - q[0], dy = tp[1] - q[1], dz = tp[2] - q[2];
+    return dx * dx + dy * dy + dz * dz;
+}
+
+// higher count, then lower sse, then lower h
+__device__ __forceinline__ bool ransac_better(int ca, double sa, int64_t ha, int cb, double sb, int64_t hb)
+{
+    return ca > cb || (ca == cb && (sa < sb || (sa == sb && ha < hb)));
+}
+
+// one record, every byte of it (the padding behind best_count included: records of equal results are equal as bytes)
+__device__ __forceinline__ void ransac_record(roman_ransac_record_t* rec, int n_assoc, int status, int64_t n_hyp, int64_t n_scored, int64_t best_hyp,
+                                              int best_count, double best_sse, const double* T /* NULL: NaN */)
+{
+    static_assert(offsetof(roman_ransac_record_t, best_sse) == offsetof(roman_ransac_record_t, best_count) + 8, "one padding word behind best_count");
+    rec->n_assoc = n_assoc; rec->status = status; rec->n_hyp = n_hyp; rec->n_scored = n_scored; rec->best_hyp = best_hyp;
+    rec->best_count = best_count; (&rec->best_count)[1] = 0; rec->best_sse = best_sse;
+    for (int t = 0; t < 16; ++t) rec->T[t] = T ? T[t] : d_nan();
+}
+
+#define RANSAC_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
+
+__global__ void __launch_bounds__(RANSAC_NT) k_ransac(roman_ransac_params_t P, int B, const RansacDesc* __restrict__ probs, const double* __restrict__ pts,
+                                                       int kmax, int32_t* __restrict__ assoc_out, roman_ransac_record_t* __restrict__ rec_out,
+                                                       int32_t* __restrict__ counts_out)
+{
+    extern __shared__ __attribute__((aligned(16))) double ransac_pts[];   // P (n1 x 3) | Q (n2 x 3)
+    __shared__ uint32_t queue[RANSAC_NW][RANSAC_QCAP];          // per wave: survivors of the round, as h - (start of the round)
+    __shared__ int wCnt[2][RANSAC_NW];                          // per wave best key of a round (two areas: a round's writes never meet the previous round's reads)
+    __shared__ double wSse[2][RANSAC_NW];
+    __shared__ long long wHyp[2][RANSAC_NW];
+    __shared__ long long wScored[RANSAC_NW];
+    __shared__ double sweep[RANSAC_NW][16];                     // output sweeps: per wave (count, sums of either side) / cross-covariance
+
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (b >= B) return;
+    const RansacDesc pd = probs[b];
+    const int n = pd.n1, m = pd.n2;
+    roman_ransac_record_t* rec = rec_out + b;
+    if (n <= 0 || m <= 0) {
+        if (tid == 0) ransac_record(rec, 0, ROMAN_ST_EMPTY_MAP, 0, 0, -1, 0, 0.0, nullptr);
+        return;
+    }
+    double* sP = ransac_pts; double* sQ = ransac_pts + (size_t)n * 3;
+    for (int t = tid; t < n * 3; t += RANSAC_NT) sP[t] = pts[pd.off1 * 3 + t];
+    for (int t = tid; t < m * 3; t += RANSAC_NT) sQ[t] = pts[pd.off2 * 3 + t];
+    __syncthreads();
+
+    const uint64_t nm = (uint64_t)n * (uint64_t)m;
+    const int64_t maxIter = P.max_iteration;
+    const double md2 = P.max_dist * P.max_dist;
+    int32_t* counts = counts_out ? counts_out + (int64_t)b * maxIter : nullptr;
+    const unsigned long long ltmask = (1ull << lane) - 1ull;
+
+    int bc = -1; double bs = 0.0; int64_t bh = -1;             // this lane's best key so far
+    int64_t nScoredWave = 0;                                    // wave-uniform
+    int64_t done = 0;
+    for (int par = 0; ; par ^= 1) {
+        const int64_t r0 = done, r1 = (maxIter - r0 < (int64_t)P.round) ? maxIter : r0 + (int64_t)P.round;
+        int qn = 0;                                             // wave-uniform: survivors waiting in this wave's queue
+        // one queued survivor per lane: fit, score against all n * m correspondences, fold into the lane's best
+        auto score = [&](uint32_t hrel, bool valid) {
+            const int64_t h = r0 + (int64_t)hrel;
+            double T[16];
+#pragma unroll
+            for (int t = 0; t < 16; ++t) T[t] = 0.0;
+            if (valid) {
+                int si[3], sj[3];
+                ransac_sample(P.seed, nm, (uint32_t)m, h, si, sj);
+                ransac_fit(sP, sQ, si, sj, T);
+            }
+            int cnt = 0; double sse = 0.0;
+            for (int i = 0; i < n; ++i) {
+                double tp[3];
+                ransac_apply(T, sP + i * 3, tp);
+#pragma unroll 4
+                for (int j = 0; j < m; ++j) {
+                    const double d2 = ransac_d2(tp, sQ + j * 3);
+                    const bool in = d2 < md2;
+                    cnt += in ? 1 : 0; sse += in ? d2 : 0.0;
+                }
+            }
+            if (valid) {
+                if (counts) counts[h] = cnt;
+                if (ransac_better(cnt, sse, h, bc, bs, bh)) { bc = cnt; bs = sse; bh = h; }
+            }
+        };
+        for (int64_t hb = r0 + (int64_t)w * 64; hb < r1; hb += RANSAC_NT) {      // (hb is wave-uniform)
+            const int64_t h = hb + lane;
+            bool keep = false;
+            if (h < r1) {
+                int si[3], sj[3];
+                ransac_sample(P.seed, nm, (uint32_t)m, h, si, sj);
+                keep = ransac_keep(sP, sQ, si, sj, P.edge_len);
+                if (!keep && counts) counts[h] = -1;
+            }
+            const unsigned long long bm = __ballot(keep);
+            if (keep) queue[w][qn + __popcll(bm & ltmask)] = (uint32_t)(h - r0);
+            qn += __popcll(bm); nScoredWave += __popcll(bm);
+            RANSAC_WAVE_SYNC();
+            if (qn >= 64) {                                     // (qn < 64 before the push: at most 127 entries)
+                const uint32_t hrel = queue[w][qn - 64 + lane];
+                qn -= 64;
+                RANSAC_WAVE_SYNC();                             // the next push may rewrite these slots
+                score(hrel, true);
+            }
+        }
+        if (qn > 0) {
+            const uint32_t hrel = lane < qn ? queue[w][lane] : 0u;
+            RANSAC_WAVE_SYNC();
+            score(hrel, lane < qn);
+        }
+        done = r1;
+        // the round's best key: over the wave, then over the waves; every thread ends with the same (bc, bs, bh)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int oc = __shfl_xor(bc, off); const double os = __shfl_xor(bs, off); const long long oh = __shfl_xor((long long)bh, off);
+            if (ransac_better(oc, os, (int64_t)oh, bc, bs, bh)) { bc = oc; bs = os; bh = (int64_t)oh; }
+        }
+        if (lane == 0) { wCnt[par][w] = bc; wSse[par][w] = bs; wHyp[par][w] = (long long)bh; }
+        __syncthreads();
+#pragma unroll
+        for (int x = 0; x < RANSAC_NW; ++x) {
+            const int oc = wCnt[par][x]; const double os = wSse[par][x]; const int64_t oh = (int64_t)wHyp[par][x];
+            if (ransac_better(oc, os, oh, bc, bs, bh)) { bc = oc; bs = os; bh = oh; }
+        }
+        // stop rule on whole rounds
+        if (done >= maxIter) break;
+        double K = (double)maxIter;
+        if (bc > 0) {
+            const double f = (double)bc / (double)nm;
+            if (f >= 1.0) K = 0.0;
+            else {
+                const double den = log(1.0 - f * f * f);
+                if (den != 0.0) K = fmin((double)maxIter, ceil(log(1.0 - P.confidence) / den));
+            }
+        }
+        if ((double)done >= K) break;
+    }
+    if (lane == 0) wScored[w] = (long long)nScoredWave;
+
+    // ---- the winner's inliers and the pose on them ----
+    if (bh < 0) {                                               // nothing survived the prune
+        __syncthreads();
+        if (tid == 0) ransac_record(rec, 0, ROMAN_ST_INSUFFICIENT, done, 0, -1, 0, 0.0, nullptr);
+        return;
+    }
+    double T[16];
+    {
+        int si[3], sj[3];
+        ransac_sample(P.seed, nm, (uint32_t)m, bh, si, sj);
+        ransac_fit(sP, sQ, si, sj, T);
+    }
+    const int64_t len = (int64_t)((nm + RANSAC_NT - 1) / RANSAC_NT) * 64;                 // correspondences per wave, a multiple of 64
+    const int64_t a0 = (int64_t)w * len, a1 = a0 + len < (int64_t)nm ? a0 + len : (int64_t)nm;
+    auto inlier = [&](int64_t a, int& i, int& j) -> bool {
+        if (a >= a1) return false;
+        i = (int)((uint32_t)a / (uint32_t)m); j = (int)((uint32_t)a % (uint32_t)m);
+        double tp[3];
+        ransac_apply(T, sP + i * 3, tp);
+        return ransac_d2(tp, sQ + j * 3) < md2;
+    };
+    int wn = 0;                                                 // wave-uniform: inliers of this wave's range
+    double s1[3] = {0, 0, 0}, s2[3] = {0, 0, 0};
+    for (int64_t ab = a0; ab < a1; ab += 64) {
+        int i = 0, j = 0;
+        const bool in = inlier(ab + lane, i, j);
+        wn += __popcll(__ballot(in));
+        if (in) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { s1[c] += sP[i * 3 + c]; s2[c] += sQ[j * 3 + c]; }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { s1[c] = readlane63(wave_sum63(s1[c])); s2[c] = readlane63(wave_sum63(s2[c])); }
+    if (lane == 0) {
+        sweep[w][0] = (double)wn;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { sweep[w][1 + c] = s1[c]; sweep[w][4 + c] = s2[c]; }
+    }
+    __syncthreads();
+    int total = 0, base = 0;
+    double m1[3] = {0, 0, 0}, m2[3] = {0, 0, 0};
+#pragma unroll
+    for (int x = 0; x < RANSAC_NW; ++x) {
+        const int cx = (int)sweep[x][0];
+        if (x < w) base += cx;
+        total += cx;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { m1[c] += sweep[x][1 + c]; m2[c] += sweep[x][4 + c]; }
+    }
+    if (total > 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { m1[c] /= (double)total; m2[c] /= (double)total; }
+    }
+    __syncthreads();                                            // `sweep` is rewritten below
+    double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int run = base;
+    int32_t* rows = assoc_out + (int64_t)b * kmax * 2;
+    for (int64_t ab = a0; ab < a1; ab += 64) {
+        int i = 0, j = 0;
+        const bool in = inlier(ab + lane, i, j);
+        const unsigned long long bm = __ballot(in);
+        if (in) {
+            const int pos = run + __popcll(bm & ltmask);
+            if (pos < kmax) { rows[2 * (int64_t)pos] = i; rows[2 * (int64_t)pos + 1] = j; }
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) H[r * 3 + c] += (sP[i * 3 + r] - m1[r]) * (sQ[j * 3 + c] - m2[c]);
+        }
+        run += __popcll(bm);
+    }
+#pragma unroll
+    for (int e = 0; e < 9; ++e) H[e] = readlane63(wave_sum63(H[e]));
+    if (lane == 0) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) sweep[w][e] = H[e];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        long long scored = 0;
+        for (int x = 0; x < RANSAC_NW; ++x) scored += wScored[x];
+        int status = ROMAN_ST_OK;
+        double To[16];
+        if (total < 3) {
+            status |= ROMAN_ST_INSUFFICIENT;
+            for (int t = 0; t < 16; ++t) To[t] = d_nan();
+        } else {
+            double Hs[9];
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Hs[e] = ((sweep[0][e] + sweep[1][e]) + sweep[2][e]) + sweep[3][e];
+            write_pose(To, 3, Hs, m1, m2);
+        }
+        if (total > kmax) status |= ROMAN_ST_ASSOC_TRUNCATED;
+        ransac_record(rec, total, status, done, scored, bh, bc, bs, To);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // loop-closure tail: what the caller of the pair loop does with a pose before it reaches the pose graph
 // (post-filters, error metrics, acceptance, edge, compaction).  A few hundred f64 operations per problem: launch- and
 // latency-bound, one thread per problem; the accepted list comes from k_rowbase's one-workgroup scan.

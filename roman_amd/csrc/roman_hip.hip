@@ -136,6 +136,12 @@ struct roman_ctx {
     ShareDesc* pinnedShare = nullptr; size_t pinnedShareCap = 0;
     hipEvent_t shareEvent = nullptr; bool sharePending = false;
 
+    // RANSAC registration (roman_ransac_batch*): problem descriptors through pinned staging (a pure enqueue), and the host-pointer
+    // call's outputs on the device (records | association rows | counts)
+    DevBuf ransacDesc, ransacHost;
+    RansacDesc* pinnedRansac = nullptr; size_t pinnedRansacCap = 0;
+    hipEvent_t ransacEvent = nullptr; bool ransacPending = false;
+
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
     bool profile = false;
@@ -1407,6 +1413,9 @@ int roman_ctx_destroy(roman_ctx_t* c)
     { DevBuf* share[] = {&c->shareDesc, &c->shareIds, &c->shareKeep, &c->shareKept, &c->shareJobs}; for (DevBuf* b : share) b->release(); }
     if (c->pinnedShare) (void)hipHostFree(c->pinnedShare);
     if (c->shareEvent) (void)hipEventDestroy(c->shareEvent);
+    c->ransacDesc.release(); c->ransacHost.release();
+    if (c->pinnedRansac) (void)hipHostFree(c->pinnedRansac);
+    if (c->ransacEvent) (void)hipEventDestroy(c->ransacEvent);
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -2364,6 +2373,103 @@ int roman_mno_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
     if (stats_out && hipMemcpy(stats_out, dStats, sizeof(roman_stats_t) * nSol, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return restore(fail(c, ROMAN_E_HIP, "statistics read-back failed")); }
     if (rowsPer && hipMemcpy(assoc_out, dAssoc, sizeof(int32_t) * nSol * rowsPer, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return restore(fail(c, ROMAN_E_HIP, "association read-back failed")); }
     return restore(ROMAN_OK);
+}
+
+// --- RANSAC registration on object centres, batched ([REF roman/align/ransac_reg.py:16-53]) ----------------------
+static int ransac_check(roman_ctx* c, const roman_ransac_params_t* P, int32_t B, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                        int32_t kmax, const void* assoc_out, const void* rec_out)
+{
+    if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
+    if (!P) return fail(c, ROMAN_E_INVALID, "rparams is NULL");
+    if (P->max_iteration < 1) return fail(c, ROMAN_E_INVALID, "max_iteration must be >= 1 (got %lld)", (long long)P->max_iteration);
+    if (P->round < 1) return fail(c, ROMAN_E_INVALID, "round must be >= 1 (got %d)", P->round);
+    if (!(P->edge_len > 0.0 && P->edge_len <= 1.0)) return fail(c, ROMAN_E_INVALID, "edge_len must lie in (0, 1] (got %g)", P->edge_len);
+    if (!(P->max_dist > 0.0) || !std::isfinite(P->max_dist)) return fail(c, ROMAN_E_INVALID, "max_dist must be > 0 (got %g)", P->max_dist);
+    if (!(P->confidence > 0.0 && P->confidence < 1.0)) return fail(c, ROMAN_E_INVALID, "confidence must lie in (0, 1) (got %g)", P->confidence);
+    if (B == 0) return ROMAN_OK;
+    if (!off1 || !n1 || !off2 || !n2 || !rec_out || kmax < 0 || (kmax > 0 && !assoc_out)) return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer or kmax < 0");
+    for (int b = 0; b < B; ++b) {
+        if (n1[b] < 0 || n2[b] < 0 || off1[b] < 0 || off2[b] < 0) return fail(c, ROMAN_E_INVALID, "problem %d: negative size or offset", b);
+        if (n1[b] > ROMAN_RANSAC_MAX_OBJECTS || n2[b] > ROMAN_RANSAC_MAX_OBJECTS)
+            return fail(c, ROMAN_E_TOO_LARGE, "problem %d has %d x %d objects; roman_ransac_batch serves at most %d per side", b, n1[b], n2[b], ROMAN_RANSAC_MAX_OBJECTS);
+    }
+    return ROMAN_OK;
+}
+
+int roman_ransac_batch_dev(roman_ctx_t* c, const roman_ransac_params_t* rparams, int32_t B,
+                           const double* pts, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                           int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, kmax, assoc_out, rec_out);
+    if (rc || B == 0) return rc;
+    int maxN = 0; bool any = false;
+    for (int b = 0; b < B; ++b) { maxN = std::max(maxN, n1[b] + n2[b]); any = any || (n1[b] > 0 && n2[b] > 0); }
+    if (!pts && any) return fail(c, ROMAN_E_INVALID, "pts is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    if (!c->ransacEvent) HIPCHK(c, hipEventCreateWithFlags(&c->ransacEvent, hipEventDisableTiming));
+    if (c->ransacPending) { HIPCHK(c, hipEventSynchronize(c->ransacEvent)); c->ransacPending = false; }   // (the previous call's upload: the staging is rewritten)
+    if (c->pinnedRansacCap < (size_t)B) {
+        if (c->pinnedRansac) (void)hipHostFree(c->pinnedRansac);
+        c->pinnedRansac = nullptr; c->pinnedRansacCap = 0;
+        const size_t cap = (size_t)B + (size_t)B / 4 + 64;
+        HIPCHK(c, hipHostMalloc((void**)&c->pinnedRansac, sizeof(RansacDesc) * cap, hipHostMallocDefault));
+        c->pinnedRansacCap = cap;
+    }
+    for (int b = 0; b < B; ++b) c->pinnedRansac[b] = RansacDesc{off1[b], off2[b], n1[b], n2[b]};
+    HIPCHK(c, c->ransacDesc.ensure(sizeof(RansacDesc) * (size_t)B));
+    HIPCHK(c, hipMemcpyAsync(c->ransacDesc.p, c->pinnedRansac, sizeof(RansacDesc) * (size_t)B, hipMemcpyHostToDevice, stream));
+    HIPCHK(c, hipEventRecord(c->ransacEvent, stream));
+    c->ransacPending = true;
+    const size_t lds = sizeof(double) * 3 * (size_t)std::max(maxN, 1);          // both point sets of the largest problem (at most 48 KB)
+    hipLaunchKernelGGL(k_ransac, dim3((unsigned)B), dim3(RANSAC_NT), lds, stream, *rparams, (int)B, c->ransacDesc.as<RansacDesc>(), pts,
+                       (int)kmax, assoc_out, rec_out, counts_out);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_ransac_batch(roman_ctx_t* c, const roman_ransac_params_t* rparams, int32_t B,
+                       const double* pts, int64_t n_objects, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                       int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (n_objects < 0) return fail(c, ROMAN_E_INVALID, "negative size");
+    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, kmax, assoc_out, rec_out);
+    if (rc || B == 0) return rc;
+    for (int b = 0; b < B; ++b)
+        if (off1[b] + n1[b] > n_objects || off2[b] + n2[b] > n_objects)
+            return fail(c, ROMAN_E_INVALID, "problem %d reads objects outside pts[0..%lld)", b, (long long)n_objects);
+    if (!pts && n_objects > 0) return fail(c, ROMAN_E_INVALID, "pts is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    c->last.scored = false; c->last.solved = false;            // workspace 0's feature staging is reused: the stepwise problem it held is gone
+    HIPCHK(c, WS.hFeats.ensure(sizeof(double) * 3 * (size_t)std::max<int64_t>(n_objects, 1)));
+    if (n_objects > 0) HIPCHK(c, hipMemcpyAsync(WS.hFeats.p, pts, sizeof(double) * 3 * (size_t)n_objects, hipMemcpyHostToDevice, WS.stream));
+    // outputs on the device: records | association rows | counts
+    const size_t rowsPer = (size_t)kmax * 2, nCounts = counts_out ? (size_t)B * (size_t)rparams->max_iteration : 0;
+    const size_t oRec = 0, oAssoc = oRec + sizeof(roman_ransac_record_t) * (size_t)B, oCnt = oAssoc + sizeof(int32_t) * std::max<size_t>((size_t)B * rowsPer, 2),
+                 total = oCnt + sizeof(int32_t) * nCounts;
+    static_assert(sizeof(roman_ransac_record_t) % 8 == 0, "the blocks stay 8-byte aligned");
+    HIPCHK(c, c->ransacHost.ensure(total));
+    char* const dev = c->ransacHost.as<char>();
+    roman_ransac_record_t* dRec = reinterpret_cast<roman_ransac_record_t*>(dev + oRec);
+    int32_t* dAssoc = reinterpret_cast<int32_t*>(dev + oAssoc);
+    int32_t* dCnt = counts_out ? reinterpret_cast<int32_t*>(dev + oCnt) : nullptr;
+    // the caller's counts go up first: entries beyond n_hyp come back as they were
+    if (nCounts) HIPCHK(c, hipMemcpyAsync(dCnt, counts_out, sizeof(int32_t) * nCounts, hipMemcpyHostToDevice, WS.stream));
+    const int chunk = std::max(1, c->host_chunk);
+    for (int lo = 0; lo < B; lo += chunk) {
+        const int hi = std::min(B, lo + chunk);
+        rc = roman_ransac_batch_dev(c, rparams, hi - lo, WS.hFeats.as<double>(), off1 + lo, n1 + lo, off2 + lo, n2 + lo, kmax,
+                                    dAssoc + (size_t)lo * rowsPer, dRec + lo, dCnt ? dCnt + (size_t)lo * (size_t)rparams->max_iteration : nullptr);
+        if (rc) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(rec_out, dRec, sizeof(roman_ransac_record_t) * (size_t)B, hipMemcpyDeviceToHost, WS.stream));
+    if (rowsPer) HIPCHK(c, hipMemcpyAsync(assoc_out, dAssoc, sizeof(int32_t) * (size_t)B * rowsPer, hipMemcpyDeviceToHost, WS.stream));
+    if (nCounts) HIPCHK(c, hipMemcpyAsync(counts_out, dCnt, sizeof(int32_t) * nCounts, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipStreamSynchronize(WS.stream));
+    return ROMAN_OK;
 }
 
 // --- the deal of a batch over ranks (pure host function; roman_amd.align.distributed.deal_by_cost states the same) ------------

@@ -97,6 +97,24 @@ class MnoResult:
     stats: np.ndarray      # (B, K) structured array (stats_dtype): the statistics of every solve
 
 
+def ransac_record_dtype():
+    """roman_ransac_record_t as a structured dtype (the C compiler's padding included)."""
+    return np.dtype({"names": ["n_assoc", "status", "n_hyp", "n_scored", "best_hyp", "best_count", "best_sse", "T"],
+                     "formats": [np.int32, np.int32, np.int64, np.int64, np.int64, np.int32, np.float64, (np.float64, (16,))],
+                     "offsets": [getattr(_abi.RomanRansacRecord, f).offset for f, _ in _abi.RomanRansacRecord._fields_],
+                     "itemsize": _abi.RANSAC_RECORD_NBYTES})
+
+
+@dataclass
+class RansacResult:
+    """Results of one batched RANSAC call, one entry per problem."""
+    assoc: list            # list of (k_b, 2) int32 arrays: the winner's inliers (map-1 index, map-2 index), row-major order
+    T: np.ndarray          # (B, 4, 4) float64 map 2 -> map 1, NaN where status has INSUFFICIENT / EMPTY_MAP
+    status: np.ndarray     # (B,) int32 ROMAN_ST_* flags
+    records: np.ndarray    # (B,) structured array (ransac_record_dtype)
+    counts: Optional[np.ndarray] = None   # (B, max_iteration) int32 when asked for: inlier count per processed hypothesis, -1 = pruned
+
+
 @dataclass
 class LoopClosureResult(BatchResult):
     """A batch result with the loop-closure tail behind it."""
@@ -199,7 +217,9 @@ class Context:
     def _check(self, rc, what):
         if rc != 0:
             msg = self._lib.roman_last_error(self._h)
-            raise RomanHipError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            err = RomanHipError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            err.code = int(rc)                                   # the ROMAN_E_* code
+            raise err
 
     # ------------------------------------------------------------------ batched hot path
     def align_batch(self, params, feats, off1, n1, off2, n2, assoc=None, assoc_off=None, u0=None,
@@ -330,6 +350,43 @@ class Context:
                                            int(F), vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax), vp(assoc_out_ptr),
                                            vp(sol_out_ptr), vp(stats_out_ptr))
         self._check(rc, "roman_mno_batch_dev")
+
+    # ------------------------------------------------------------------ RANSAC registration
+    def ransac_batch(self, rparams, pts, off1, n1, off2, n2, kmax=None, counts=None):
+        """Host-pointer batched RANSAC registration on object centres (roman_ransac_batch).  rparams: a RomanRansacParams;
+        pts: (n_objects, 3) float64.  counts: None, True (a fresh (B, max_iteration) int32 array filled with -2) or such an
+        array of the caller's (entries beyond a problem's n_hyp come back untouched).  -> RansacResult."""
+        pts = _f64(pts)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError("pts must be (n_objects, 3)")
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        B = int(n1.shape[0])
+        if kmax is None:
+            kmax = int(max(1, np.max(n1.astype(np.int64) * n2))) if B else 1
+        if counts is True:
+            counts = np.full((B, max(int(rparams.max_iteration), 0)), -2, dtype=np.int32)
+        elif counts is not None:
+            if counts.dtype != np.int32 or not counts.flags.c_contiguous or counts.shape != (B, int(rparams.max_iteration)):
+                raise ValueError("counts must be a C-contiguous (B, max_iteration) int32 array")
+        a_out = np.zeros((B, kmax, 2), dtype=np.int32)
+        rec = np.zeros(B, dtype=ransac_record_dtype())
+        self._generation += 1
+        rc = self._lib.roman_ransac_batch(self._h, C.byref(rparams), B, _ptr(pts), pts.shape[0], _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                          int(kmax), _ptr(a_out), _ptr(rec), _ptr(counts))
+        self._check(rc, "roman_ransac_batch")
+        rows = np.minimum(rec["n_assoc"], kmax)
+        return RansacResult([a_out[b, :rows[b]].copy() for b in range(B)], rec["T"].reshape(B, 4, 4).copy(), rec["status"].copy(), rec, counts)
+
+    def ransac_batch_dev(self, rparams, pts_ptr, off1, n1, off2, n2, kmax, assoc_out_ptr, rec_out_ptr, counts_out_ptr=None):
+        """Device-pointer batched RANSAC registration (roman_ransac_batch_dev): pointers are integers, metadata arrays host
+        NumPy arrays.  A pure enqueue on the context's stream; complete after sync()."""
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_ransac_batch_dev(self._h, C.byref(rparams), int(n1.shape[0]), vp(pts_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                              int(kmax), vp(assoc_out_ptr), vp(rec_out_ptr), vp(counts_out_ptr))
+        self._check(rc, "roman_ransac_batch_dev")
 
     # ------------------------------------------------------------------ loop closures
     def align_lc_batch(self, params, feats, off1, n1, off2, n2, lc, assoc=None, assoc_off=None, u0=None, kmax=None):
