@@ -43,6 +43,37 @@ struct DevBuf {
     template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// grow-only pinned staging of one kind of descriptor (a pageable source makes the runtime stage the copy itself, at several times
+// the cost).  An upload out of it is a pure enqueue: the only thing ever waited for is the previous upload, which must have left
+// the staging before it is rewritten — so stage() synchronises on the event first and upload() records it behind the copy.
+template <typename T> struct PinnedStage {
+    T* p = nullptr; size_t cap = 0;
+    hipEvent_t ev = nullptr; bool pending = false;
+    // the staging, free to be written, for at least n elements
+    hipError_t stage(size_t n, T** out) {
+        hipError_t e;
+        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+        if (pending) { if ((e = hipEventSynchronize(ev)) != hipSuccess) return e; pending = false; }
+        if (cap < n) {
+            if (p) (void)hipHostFree(p);
+            p = nullptr; cap = 0;
+            const size_t want = n + n / 4 + 64;
+            if ((e = hipHostMalloc((void**)&p, sizeof(T) * want, hipHostMallocDefault)) != hipSuccess) { p = nullptr; return e; }
+            cap = want;
+        }
+        *out = p; return hipSuccess;
+    }
+    // its first n elements into `dst`, behind whatever is queued on `stream`
+    hipError_t upload(DevBuf& dst, size_t n, hipStream_t stream) {
+        hipError_t e = dst.ensure(sizeof(T) * n);
+        if (e == hipSuccess) e = hipMemcpyAsync(dst.p, p, sizeof(T) * n, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipEventRecord(ev, stream);
+        if (e == hipSuccess) pending = true;
+        return e;
+    }
+    void release() { if (p) (void)hipHostFree(p); if (ev) (void)hipEventDestroy(ev); p = nullptr; cap = 0; ev = nullptr; pending = false; }
+};
+
 }  // namespace
 
 constexpr int ROMAN_MAX_PIPELINE = 6;        // workspaces (batches in flight) a context can hold (3 serves the headline; calls of thousands of small
@@ -88,8 +119,7 @@ struct roman_ctx {
         DevBuf mnoHost;                        // roman_mno_batch (host pointers): the three output arrays on the device
         // totals of the most recent batch on this workspace, copied back without waiting
         BatchTotals* pinnedTotals = nullptr;
-        ProbDesc* pinnedProbs = nullptr; size_t pinnedProbsCap = 0;   // staging of the problem descriptors (truly asynchronous upload)
-        hipEvent_t probsEvent = nullptr; bool probsPending = false;
+        PinnedStage<ProbDesc> probStage;       // staging of the problem descriptors (truly asynchronous upload)
         hipEvent_t totEvent = nullptr;
         bool totPending = false;
         double totMaskBound = 0.0, totSumA = 0.0, totMaxA = 0.0;   // the bounds the pending totals relate to
@@ -133,14 +163,12 @@ struct roman_ctx {
     // shared-segment removal (roman_shared_ids_dev / roman_align_lc_batch_ids): problem descriptors (through pinned staging, so that the
     // mark step is a pure enqueue), and the host-pointer call's ids | keep lists | kept counts | gather jobs on the device
     DevBuf shareDesc, shareIds, shareKeep, shareKept, shareJobs;
-    ShareDesc* pinnedShare = nullptr; size_t pinnedShareCap = 0;
-    hipEvent_t shareEvent = nullptr; bool sharePending = false;
+    PinnedStage<ShareDesc> shareStage;
 
     // RANSAC registration (roman_ransac_batch*): problem descriptors through pinned staging (a pure enqueue), and the host-pointer
     // call's outputs on the device (records | association rows | counts)
     DevBuf ransacDesc, ransacHost;
-    RansacDesc* pinnedRansac = nullptr; size_t pinnedRansacCap = 0;
-    hipEvent_t ransacEvent = nullptr; bool ransacPending = false;
+    PinnedStage<RansacDesc> ransacStage;
 
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
@@ -606,19 +634,11 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     const size_t maxItems = (size_t)(sumA / RPB) + (size_t)B + 1;
     HIPCHK(c, WS.items.ensure(sizeof(ItemDesc) * maxItems));
 
-    {   // descriptors: through pinned staging (a pageable source makes the runtime stage the copy itself, at several times the cost)
-        if (WS.probsPending) { HIPCHK(c, hipEventSynchronize(WS.probsEvent)); WS.probsPending = false; }   // the previous upload has left the staging
-        if (WS.pinnedProbsCap < (size_t)B) {
-            if (WS.pinnedProbs) (void)hipHostFree(WS.pinnedProbs);
-            WS.pinnedProbs = nullptr; WS.pinnedProbsCap = 0;
-            const size_t cap = std::max<size_t>((size_t)B * 2, 64);
-            HIPCHK(c, hipHostMalloc((void**)&WS.pinnedProbs, sizeof(ProbDesc) * cap, hipHostMallocDefault));
-            WS.pinnedProbsCap = cap;
-        }
-        memcpy(WS.pinnedProbs, hd.data(), sizeof(ProbDesc) * (size_t)B);
-        HIPCHK(c, hipMemcpyAsync(WS.probs.p, WS.pinnedProbs, sizeof(ProbDesc) * (size_t)B, hipMemcpyHostToDevice, WS.stream));
-        HIPCHK(c, hipEventRecord(WS.probsEvent, WS.stream));
-        WS.probsPending = true;
+    {   // descriptors: through pinned staging
+        ProbDesc* staged = nullptr;
+        HIPCHK(c, WS.probStage.stage((size_t)B, &staged));
+        memcpy(staged, hd.data(), sizeof(ProbDesc) * (size_t)B);
+        HIPCHK(c, WS.probStage.upload(WS.probs, (size_t)B, WS.stream));
     }
     const ProbDesc* dP = WS.probs.as<ProbDesc>();
     ProbState* dS = WS.state.as<ProbState>();
@@ -1379,8 +1399,7 @@ int roman_ctx_create(roman_ctx_t** out, int device, void* stream)
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) c->ws[k].stream = c->stream;
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) {
         if (hipHostMalloc((void**)&c->ws[k].pinnedTotals, sizeof(BatchTotals), hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ws[k].totEvent, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ws[k].probsEvent, hipEventDisableTiming) != hipSuccess) {
+            hipEventCreateWithFlags(&c->ws[k].totEvent, hipEventDisableTiming) != hipSuccess) {
             roman_ctx_destroy(c); return fail(nullptr, ROMAN_E_NOMEM, "hipHostMalloc / hipEventCreate failed");
         }
         memset(c->ws[k].pinnedTotals, 0, sizeof(BatchTotals));
@@ -1404,18 +1423,14 @@ int roman_ctx_destroy(roman_ctx_t* c)
         for (DevBuf* b : all) b->release();
         if (W.pinnedTotals) (void)hipHostFree(W.pinnedTotals);
         if (W.totEvent) (void)hipEventDestroy(W.totEvent);
-        if (W.pinnedProbs) (void)hipHostFree(W.pinnedProbs);
-        if (W.probsEvent) (void)hipEventDestroy(W.probsEvent);
+        W.probStage.release();
         for (int s = 0; s < ROMAN_STAGE_COUNT; ++s) { if (W.evA[s]) (void)hipEventDestroy(W.evA[s]); if (W.evB[s]) (void)hipEventDestroy(W.evB[s]); }
         if (W.done) (void)hipEventDestroy(W.done);
     }
     if (c->hostOut) (void)hipHostFree(c->hostOut);
     { DevBuf* share[] = {&c->shareDesc, &c->shareIds, &c->shareKeep, &c->shareKept, &c->shareJobs}; for (DevBuf* b : share) b->release(); }
-    if (c->pinnedShare) (void)hipHostFree(c->pinnedShare);
-    if (c->shareEvent) (void)hipEventDestroy(c->shareEvent);
     c->ransacDesc.release(); c->ransacHost.release();
-    if (c->pinnedRansac) (void)hipHostFree(c->pinnedRansac);
-    if (c->ransacEvent) (void)hipEventDestroy(c->ransacEvent);
+    c->shareStage.release(); c->ransacStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -1559,14 +1574,148 @@ int enqueue_lc_tail(roman_ctx* c, hipStream_t stream, int B, const LcTail& t)
     return ROMAN_OK;
 }
 
+// --- what the batch entry points share ---------------------------------------------------------------
+// What an entry point knows about its batch besides the four metadata arrays (host arrays for every entry point).
+struct BatchCheck {
+    int64_t n_objects = -1;                    // rows of the pool the offsets index; -1: not known here (device-pointer callers)
+    const int32_t* assoc = nullptr; const int64_t* assoc_off = nullptr;
+    bool assoc_on_host = false;                // `assoc` can be read here: its indices are range-checked (a device array never is)
+    bool whole_list = false;                   // assoc_off starts at 0 (not so for the slices of it the chunked host entry points hand the device-pointer ones)
+    int32_t side_cap = 0; int cap_code = ROMAN_OK; const char* cap_who = "";   // the largest map the entry point serves (0: no cap)
+};
+
+// The one check of a batch's metadata (B > 0).  Only host-readable metadata is read, and the bulk array `assoc` only where the
+// caller says it is a host array.  `any`: some problem has objects (the callers that need a non-NULL pool then).
+int check_batch(roman_ctx* c, int32_t B, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, const BatchCheck& k, bool* any = nullptr)
+{
+    if (!off1 || !n1 || !off2 || !n2) return fail(c, ROMAN_E_INVALID, "NULL metadata pointer");
+    if (k.assoc && !k.assoc_off) return fail(c, ROMAN_E_INVALID, "assoc given without assoc_off");
+    if (k.assoc && k.whole_list && k.assoc_off[0] != 0) return fail(c, ROMAN_E_INVALID, "assoc_off[0] must be 0");
+    bool some = false;
+    for (int b = 0; b < B; ++b) {
+        if (n1[b] < 0 || n2[b] < 0 || off1[b] < 0 || off2[b] < 0) return fail(c, ROMAN_E_INVALID, "problem %d: negative size or offset", b);
+        if (k.side_cap > 0 && (n1[b] > k.side_cap || n2[b] > k.side_cap)) return fail(c, k.cap_code, "problem %d has %d x %d objects; %s serves at most %d per side", b, n1[b], n2[b], k.cap_who, k.side_cap);
+        if (k.n_objects >= 0 && (off1[b] + n1[b] > k.n_objects || off2[b] + n2[b] > k.n_objects))
+            return fail(c, ROMAN_E_INVALID, "problem %d reads objects outside the pool's rows [0..%lld)", b, (long long)k.n_objects);
+        if (k.assoc) {
+            if (k.assoc_off[b + 1] < k.assoc_off[b]) return fail(c, ROMAN_E_INVALID, "assoc_off is not non-decreasing at problem %d", b);
+            if (k.assoc_on_host)
+                for (int64_t r = k.assoc_off[b]; r < k.assoc_off[b + 1]; ++r)
+                    if (k.assoc[2 * r] < 0 || k.assoc[2 * r] >= n1[b] || k.assoc[2 * r + 1] < 0 || k.assoc[2 * r + 1] >= n2[b])
+                        return fail(c, ROMAN_E_INVALID, "problem %d: association %lld = (%d,%d) out of range", b, (long long)(r - k.assoc_off[b]), k.assoc[2 * r], k.assoc[2 * r + 1]);
+        }
+        some = some || n1[b] > 0 || n2[b] > 0;
+    }
+    if (any) *any = some;
+    return ROMAN_OK;
+}
+
+// One call of a device-pointer entry point: `work(stream)` enqueues it on workspace 0 and the context's stream (depth 1) or, at
+// depth >= 2, on the next workspace of the rotation, whose internal stream starts behind the work already queued on the caller's
+// stream.  After an error the workspace's `done` is not recorded and it does not count as issued; c->cur is 0 again either way.
+template <typename Work> int on_next_workspace(roman_ctx* c, Work work)
+{
+    int k = 0;
+    if (c->pipeline >= 2) {
+        k = c->next_ws;
+        c->next_ws = (c->next_ws + 1) % c->pipeline; c->latest_ws = k;
+        HIPCHK(c, hipEventRecord(c->evIn, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->istream[k], c->evIn, 0));
+    }
+    c->cur = k; c->ws[k].stream = c->pipeline >= 2 ? c->istream[k] : c->stream;
+    int rc = work(c->ws[k].stream);
+    if (!rc && c->pipeline >= 2) {
+        const hipError_t e = hipEventRecord(c->ws[k].done, c->ws[k].stream);
+        if (e == hipSuccess) c->ws[k].issued = true;
+        else { (void)hipGetLastError(); rc = fail(c, ROMAN_E_HIP, "hipEventRecord failed: %s", hipGetErrorString(e)); }
+    }
+    c->cur = 0; c->last.scored = false; c->last.solved = false;   // workspace 0 is reused: the stepwise problem it held is gone
+    return rc;
+}
+
+// The host inputs of a call onto workspace 0: the pool (`rows` x F doubles, room for `extra` rows behind it: the shared-id gather's
+// region) into WS.hFeats and, when there is one, the association list (`assocRows` rows) into WS.hAssoc.
+int upload_inputs(roman_ctx* c, const double* feats, int64_t rows, int32_t F, int64_t extra, const int32_t* assoc, int64_t assocRows,
+                  const double** dFeats, const int32_t** dAssoc = nullptr)
+{
+    if (!feats && rows * F > 0) return fail(c, ROMAN_E_INVALID, "the pool (feats / pts) is NULL");
+    HIPCHK(c, WS.hFeats.ensure(sizeof(double) * (size_t)std::max<int64_t>((rows + extra) * F, 1)));
+    if (rows * F > 0) HIPCHK(c, hipMemcpyAsync(WS.hFeats.p, feats, sizeof(double) * (size_t)(rows * F), hipMemcpyHostToDevice, WS.stream));
+    *dFeats = WS.hFeats.as<double>();
+    if (dAssoc) *dAssoc = nullptr;
+    if (assoc) {
+        HIPCHK(c, WS.hAssoc.ensure(sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(assocRows, 1)));
+        if (assocRows > 0) HIPCHK(c, hipMemcpyAsync(WS.hAssoc.p, assoc, sizeof(int32_t) * 2 * (size_t)assocRows, hipMemcpyHostToDevice, WS.stream));
+        *dAssoc = WS.hAssoc.as<int32_t>();
+    }
+    return ROMAN_OK;
+}
+
+// The solver's outputs of B problems as ONE block of a device buffer: T | stats | assoc | n | status
+struct SolverBlock {
+    int32_t kmax; size_t oT, oS, oA, oNn, oSt, end;
+    SolverBlock(int32_t B, int32_t kmax_) : kmax(kmax_) {
+        static_assert(sizeof(roman_stats_t) % 8 == 0, "the blocks behind the statistics stay 8-byte aligned");
+        const size_t nb = (size_t)B, kb = nb * (size_t)std::max(kmax, 1);
+        oT = 0; oS = oT + sizeof(double) * 16 * nb; oA = oS + sizeof(roman_stats_t) * nb;
+        oNn = oA + sizeof(int32_t) * 2 * kb; oSt = oNn + sizeof(int32_t) * nb; end = oSt + sizeof(int32_t) * nb;
+    }
+    BatchOut at(char* dev) const {
+        return BatchOut{kmax, reinterpret_cast<int32_t*>(dev + oA), reinterpret_cast<int32_t*>(dev + oNn), reinterpret_cast<double*>(dev + oT),
+                        reinterpret_cast<int32_t*>(dev + oSt), reinterpret_cast<roman_stats_t*>(dev + oS)};
+    }
+};
+
+// The pipeline depth a host-pointer entry point sets for its own calls (`rc`: whether that worked): every exit puts the caller's
+// depth (and the team mode, which align_chunked changes) back and leaves workspace 0 on the context's stream.
+struct DepthScope {
+    roman_ctx* c; const int depth, teams; const int rc; bool open = true;
+    DepthScope(roman_ctx* c_, int d) : c(c_), depth(c_->pipeline), teams(c_->wide_teams), rc(roman_ctx_set_pipeline(c_, d)) {}
+    int close(int code) {
+        if (!open) return code;
+        open = false; c->wide_teams = teams;
+        const int r2 = roman_ctx_set_pipeline(c, depth);
+        c->cur = 0; c->ws[0].stream = c->stream;
+        return code ? code : r2;
+    }
+    ~DepthScope() { (void)close(ROMAN_OK); }
+};
+
+// B problems as calls of `chunk`.  first_alone: the first call is waited for, so that the calls queued behind it size their pools
+// from what it needed instead of repeating its guess.
+template <typename Issue> int issue_chunks(roman_ctx* c, int B, int chunk, bool first_alone, Issue issue)
+{
+    int lo = 0;
+    if (first_alone) {
+        lo = std::min(B, chunk);
+        int rc = issue(0, lo);
+        if (!rc) rc = roman_ctx_sync(c);
+        if (rc) return rc;
+        harvest_totals(c, true);
+    }
+    for (; lo < B; lo += chunk) { const int rc = issue(lo, std::min(B, lo + chunk)); if (rc) return rc; }
+    return ROMAN_OK;
+}
+
+// The flagged problems once more, in runs of consecutive problems at most a chunk long.
+template <typename Flagged, typename Issue> int reissue_runs(int B, int chunk, Flagged flagged, Issue issue)
+{
+    for (int b = 0; b < B; ) {
+        if (!flagged(b)) { ++b; continue; }
+        int e = b + 1;
+        while (e < B && e - b < chunk && flagged(e)) ++e;
+        const int rc = issue(b, e);
+        if (rc) return rc;
+        b = e;
+    }
+    return ROMAN_OK;
+}
+
 // --- the batched hot path --------------------------------------------------------------------------
 // roman_align_batch_dev, optionally with the loop-closure tail behind the solver on the same stream
-int align_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
-                          const double* feats, const int64_t* off1, const int32_t* n1,
-                          const int64_t* off2, const int32_t* n2, int32_t F,
-                          const int32_t* assoc, const int64_t* assoc_off, const double* u0,
-                          int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out,
-                          double* T_out, int32_t* status_out, roman_stats_t* stats_out, const LcTail* tail)
+int align_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B, const double* feats, const int64_t* off1, const int32_t* n1,
+                    const int64_t* off2, const int32_t* n2, int32_t F, const int32_t* assoc, const int64_t* assoc_off, const double* u0,
+                    int32_t kmax, int32_t* assoc_out, int32_t* n_assoc_out, double* T_out, int32_t* status_out, roman_stats_t* stats_out, const LcTail* tail)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
@@ -1574,43 +1723,22 @@ int align_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
         if (tail) { HIPCHK(c, hipSetDevice(c->device)); return enqueue_lc_tail(c, c->stream, 0, *tail); }
         return ROMAN_OK;
     }
-    if (!off1 || !n1 || !off2 || !n2 || !assoc_out || !n_assoc_out || !T_out || !status_out || kmax < 0)
-        return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer or kmax < 0");
-    if (assoc && !assoc_off) return fail(c, ROMAN_E_INVALID, "assoc given without assoc_off");
+    if (!assoc_out || !n_assoc_out || !T_out || !status_out || kmax < 0) return fail(c, ROMAN_E_INVALID, "NULL output pointer or kmax < 0");
+    BatchCheck chk; chk.assoc = assoc; chk.assoc_off = assoc_off;
+    bool any = false;
+    int rc = check_batch(c, B, off1, n1, off2, n2, chk, &any);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     DevParams D;
-    int rc = make_dev_params(c, params, F, &D);
+    rc = make_dev_params(c, params, F, &D);
     if (rc) return rc;
-    if (!feats) {
-        bool any = false;
-        for (int b = 0; b < B; ++b) any = any || (n1[b] > 0 || n2[b] > 0);
-        if (any) return fail(c, ROMAN_E_INVALID, "feats is NULL");
-    }
+    if (!feats && any) return fail(c, ROMAN_E_INVALID, "feats is NULL");
     const BatchIn in{B, feats, off1, n1, off2, n2, F, assoc, assoc_off};
     const BatchOut out{kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out};
-    if (c->pipeline >= 2) {
-        // next workspace: its internal stream starts behind the work already queued on the caller's stream
-        const int k = c->next_ws;
-        c->next_ws = (c->next_ws + 1) % c->pipeline; c->latest_ws = k;
-        HIPCHK(c, hipEventRecord(c->evIn, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->istream[k], c->evIn, 0));
-        c->cur = k; c->ws[k].stream = c->istream[k];
-        rc = run_batch(c, D, params, in, u0, out);
-        if (!rc && tail) rc = enqueue_lc_tail(c, c->ws[k].stream, B, *tail);
-        if (!rc) {
-            HIPCHK(c, hipEventRecord(c->ws[k].done, c->ws[k].stream));
-            c->ws[k].issued = true;
-        }
-        c->cur = 0;
-        c->last.scored = false; c->last.solved = false;        // workspace 0 is reused: the stepwise problem it held is gone
-        return rc;
-    }
-    c->cur = 0; WS.stream = c->stream;
-    rc = run_batch(c, D, params, in, u0, out);
-    if (rc) return rc;
-    c->last.scored = false; c->last.solved = false;
-    if (tail) return enqueue_lc_tail(c, c->stream, B, *tail);
-    return ROMAN_OK;
+    return on_next_workspace(c, [&](hipStream_t stream) -> int {
+        const int r = run_batch(c, D, params, in, u0, out);
+        return (!r && tail) ? enqueue_lc_tail(c, stream, B, *tail) : r;
+    });
 }
 }  // namespace
 
@@ -1709,13 +1837,12 @@ constexpr int MAX_ATTEMPTS = 5;
 // device-pointer caller does, for callers that hold host arrays — the straggler tail of one call's solver
 // overlaps the next calls' affinity builds.  Inputs are already on the device; every call writes its own rows of the output
 // arrays.  Problems a call skipped for workspace (ROMAN_ST_WORKSPACE) are issued again, those only, in runs of consecutive
-// problems.  With no sizing history for this parameter block the first call runs alone and is waited for: the calls queued
-// behind it size their pools from what it needed instead of repeating its guess.
+// problems.  With no sizing history for this parameter block the first call runs alone and is waited for (issue_chunks).
 int align_chunked(roman_ctx* c, const roman_params_t* params, const BatchIn& in, const double* dU0, const BatchOut& out)
 {
     const int B = in.B, chunk = c->host_chunk;
-    const int saved = c->pipeline;
-    int rc = roman_ctx_set_pipeline(c, c->host_depth);
+    DepthScope scope(c, c->host_depth);
+    int rc = scope.rc;
     if (rc) return rc;
     c->teams_launched = false;
     std::vector<int64_t> uoff;                                  // start of problem b's slice of u0
@@ -1732,27 +1859,17 @@ int align_chunked(roman_ctx* c, const roman_params_t* params, const BatchIn& in,
                                      out.assoc_out + (size_t)lo * (size_t)out.kmax * 2, out.n_assoc_out + lo, out.T_out + (size_t)lo * 16, out.status_out + lo,
                                      out.stats_out ? out.stats_out + lo : nullptr);
     };
-    auto restore = [&](int code) -> int { const int r2 = roman_ctx_set_pipeline(c, saved); c->cur = 0; c->ws[0].stream = c->stream; return code ? code : r2; };
-    int lo = 0;
     const roman_ctx::Hist& H = c->hist;
-    if (!(H.valid && H.tagged && H.F == in.F && memcmp(&H.params, params, sizeof(roman_params_t)) == 0)) {
-        rc = issue(0, std::min(B, chunk));
-        if (rc) return restore(rc);
-        rc = roman_ctx_sync(c);
-        if (rc) return restore(rc);
-        harvest_totals(c, true);
-        lo = std::min(B, chunk);
-    }
-    for (; lo < B; lo += chunk) { rc = issue(lo, std::min(B, lo + chunk)); if (rc) return restore(rc); }
+    const bool history = H.valid && H.tagged && H.F == in.F && memcmp(&H.params, params, sizeof(roman_params_t)) == 0;
+    rc = issue_chunks(c, B, chunk, !history, issue);
+    if (rc) return rc;
     std::vector<int32_t> st((size_t)B);
-    const int teams_saved = c->wide_teams;
     bool no_teams_tried = false;
-    auto restore2 = [&](int code) -> int { c->wide_teams = teams_saved; return restore(code); };
     for (int attempt = 1; ; ++attempt) {
         rc = roman_ctx_sync(c);
-        if (rc) return restore2(rc);
+        if (rc) return rc;
         harvest_totals(c, true);
-        if (hipMemcpy(st.data(), out.status_out, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return restore2(fail(c, ROMAN_E_HIP, "status read-back failed")); }
+        if (hipMemcpy(st.data(), out.status_out, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return fail(c, ROMAN_E_HIP, "status read-back failed"); }
         int nskip = 0, nint = 0;
         for (int b = 0; b < B; ++b) { nskip += (st[b] & ROMAN_ST_WORKSPACE) ? 1 : 0; nint += (st[b] & ROMAN_ST_INTERNAL) ? 1 : 0; }
         int again = ROMAN_ST_WORKSPACE;
@@ -1764,22 +1881,14 @@ int align_chunked(roman_ctx* c, const roman_params_t* params, const BatchIn& in,
         // (a final ROMAN_ST_INTERNAL does not end the loop while skipped problems remain: they are still solvable)
         if (attempt >= MAX_ATTEMPTS) {
             if (!nskip) break;                                  // only the teams-off retry was pending: the ROMAN_ST_INTERNAL records speak for themselves
-            return restore2(fail(c, ROMAN_E_NOMEM, "the sparse workspace of %d problem(s) still does not fit after %d attempts", nskip, attempt));
+            return fail(c, ROMAN_E_NOMEM, "the sparse workspace of %d problem(s) still does not fit after %d attempts", nskip, attempt);
         }
-        for (int b = 0; b < B; ) {                              // runs of consecutive problems to issue again, at most a chunk long
-            if (!(st[b] & again)) { ++b; continue; }
-            int e = b + 1;
-            while (e < B && e - b < chunk && (st[e] & again)) ++e;
-            rc = issue(b, e);
-            if (rc) return restore2(rc);
-            b = e;
-        }
+        rc = reissue_runs(B, chunk, [&](int b) { return (st[b] & again) != 0; }, issue);
+        if (rc) return rc;
     }
-    return restore2(ROMAN_OK);
+    return scope.close(ROMAN_OK);
 }
-}  // namespace
 
-namespace {
 // The synchronous part shared by the two host-output entry points: inputs are on the device (`in`, dU0), the outputs of every call
 // land in ONE device block (T | stats | assoc | n | status) and come back with ONE copy through a pinned landing block — a single
 // pair's whole result is 1.8 KB, and five separate read-backs cost more than its build kernels.
@@ -1796,14 +1905,11 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
     const int32_t B = in.B;
     int rc = ROMAN_OK;
     bool copied = false;
-    const size_t kb = (size_t)B * (size_t)std::max(kmax, 1);
-    const size_t oT = 0, oS = oT + sizeof(double) * 16 * (size_t)B, oA = oS + sizeof(roman_stats_t) * (size_t)B,
-                 oNn = oA + sizeof(int32_t) * 2 * kb, oSt = oNn + sizeof(int32_t) * (size_t)B, endSt = oSt + sizeof(int32_t) * (size_t)B;
+    const SolverBlock blk(B, kmax);
     // with a tail: records | accepted indices | count behind the batch outputs, in the same block and the same copy
-    const size_t oRec = (endSt + 7) & ~(size_t)7, oIdx = oRec + sizeof(roman_lc_record_t) * (size_t)B, oCnt = oIdx + sizeof(int32_t) * (size_t)B;
-    const size_t total = lc ? oCnt + sizeof(int32_t) : endSt;
+    const size_t oRec = (blk.end + 7) & ~(size_t)7, oIdx = oRec + sizeof(roman_lc_record_t) * (size_t)B, oCnt = oIdx + sizeof(int32_t) * (size_t)B;
+    const size_t total = lc ? oCnt + sizeof(int32_t) : blk.end;
     static_assert(sizeof(roman_lc_record_t) % 8 == 0, "records are 8-byte aligned");
-    static_assert(sizeof(roman_stats_t) % 8 == 0, "the blocks behind the statistics stay 8-byte aligned");
     HIPCHK(c, WS.oAll.ensure(total));
     if (c->hostOutCap < total) {
         if (c->hostOut) { (void)hipHostFree(c->hostOut); c->hostOut = nullptr; c->hostOutCap = 0; }
@@ -1812,8 +1918,7 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
         c->hostOutCap = want;
     }
     char* const dev = WS.oAll.as<char>();
-    const BatchOut out{kmax, reinterpret_cast<int32_t*>(dev + oA), reinterpret_cast<int32_t*>(dev + oNn), reinterpret_cast<double*>(dev + oT),
-                       reinterpret_cast<int32_t*>(dev + oSt), reinterpret_cast<roman_stats_t*>(dev + oS)};
+    const BatchOut out = blk.at(dev);
     LcTail tail;
     if (lc) {
         tail.P = lc->P;
@@ -1845,7 +1950,7 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
                 continue;
             }
             if (c->teams_launched && c->wide_teams != 0) {      // a team that could not hold its problem leaves ROMAN_ST_INTERNAL: once more, the whole device per problem
-                const int32_t* stv = reinterpret_cast<const int32_t*>(static_cast<const char*>(c->hostOut) + oSt);
+                const int32_t* stv = reinterpret_cast<const int32_t*>(static_cast<const char*>(c->hostOut) + blk.oSt);
                 bool anyInt = false;
                 for (int b = 0; b < B; ++b) anyInt = anyInt || (stv[b] & ROMAN_ST_INTERNAL);
                 if (anyInt && attempt + 1 < MAX_ATTEMPTS) { c->wide_teams = 0; continue; }
@@ -1860,11 +1965,11 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
     }
     {
         const char* h = static_cast<const char*>(c->hostOut);
-        if (kmax > 0) memcpy(assoc_out, h + oA, sizeof(int32_t) * 2 * (size_t)B * (size_t)kmax);
-        memcpy(n_assoc_out, h + oNn, sizeof(int32_t) * (size_t)B);
-        memcpy(T_out, h + oT, sizeof(double) * 16 * (size_t)B);
-        memcpy(status_out, h + oSt, sizeof(int32_t) * (size_t)B);
-        if (stats_out) memcpy(stats_out, h + oS, sizeof(roman_stats_t) * (size_t)B);
+        if (kmax > 0) memcpy(assoc_out, h + blk.oA, sizeof(int32_t) * 2 * (size_t)B * (size_t)kmax);
+        memcpy(n_assoc_out, h + blk.oNn, sizeof(int32_t) * (size_t)B);
+        memcpy(T_out, h + blk.oT, sizeof(double) * 16 * (size_t)B);
+        memcpy(status_out, h + blk.oSt, sizeof(int32_t) * (size_t)B);
+        if (stats_out) memcpy(stats_out, h + blk.oS, sizeof(roman_stats_t) * (size_t)B);
         if (lc) {
             memcpy(lc->records, h + oRec, sizeof(roman_lc_record_t) * (size_t)B);
             memcpy(lc->idx, h + oIdx, sizeof(int32_t) * (size_t)B);
@@ -1879,9 +1984,7 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
     }
     return ROMAN_OK;
 }
-}  // namespace
 
-namespace {
 // --- shared-segment removal ([REF roman/align/submap_align.py:108-115]) ---------------------------------------------------------
 // k_shared_mark behind whatever is queued on `stream`: a pure enqueue — the problem descriptors travel through pinned staging,
 // and only the previous call's upload out of that staging is waited for.
@@ -1889,25 +1992,15 @@ int enqueue_shared_mark(roman_ctx* c, hipStream_t stream, int32_t B, const int64
                         const int64_t* off2, const int32_t* n2, int32_t* dKeep, int32_t* dKept)
 {
     if (B <= 0) return ROMAN_OK;
-    if (!c->shareEvent) HIPCHK(c, hipEventCreateWithFlags(&c->shareEvent, hipEventDisableTiming));
-    if (c->sharePending) { HIPCHK(c, hipEventSynchronize(c->shareEvent)); c->sharePending = false; }
-    if (c->pinnedShareCap < (size_t)B) {
-        if (c->pinnedShare) (void)hipHostFree(c->pinnedShare);
-        c->pinnedShare = nullptr; c->pinnedShareCap = 0;
-        const size_t cap = (size_t)B + (size_t)B / 4 + 64;
-        HIPCHK(c, hipHostMalloc((void**)&c->pinnedShare, sizeof(ShareDesc) * cap, hipHostMallocDefault));
-        c->pinnedShareCap = cap;
-    }
+    ShareDesc* staged = nullptr;
+    HIPCHK(c, c->shareStage.stage((size_t)B, &staged));
     int64_t kb = 0; int32_t maxN = 0;
     for (int b = 0; b < B; ++b) {
-        c->pinnedShare[b] = ShareDesc{off1[b], off2[b], kb, n1[b], n2[b]};
+        staged[b] = ShareDesc{off1[b], off2[b], kb, n1[b], n2[b]};
         kb += (int64_t)n1[b] + n2[b];
         maxN = std::max(maxN, std::max(n1[b], n2[b]));
     }
-    HIPCHK(c, c->shareDesc.ensure(sizeof(ShareDesc) * (size_t)B));
-    HIPCHK(c, hipMemcpyAsync(c->shareDesc.p, c->pinnedShare, sizeof(ShareDesc) * (size_t)B, hipMemcpyHostToDevice, stream));
-    HIPCHK(c, hipEventRecord(c->shareEvent, stream));
-    c->sharePending = true;
+    HIPCHK(c, c->shareStage.upload(c->shareDesc, (size_t)B, stream));
     if (maxN <= 64) hipLaunchKernelGGL(k_shared_mark<64>, dim3((unsigned)B), dim3(64), 0, stream, (int)B, c->shareDesc.as<ShareDesc>(), dIds, dKeep, dKept);
     else hipLaunchKernelGGL(k_shared_mark<256>, dim3((unsigned)B), dim3(256), 0, stream, (int)B, c->shareDesc.as<ShareDesc>(), dIds, dKeep, dKept);
     HIPCHK(c, hipGetLastError());
@@ -1973,9 +2066,7 @@ int enqueue_shared_gather(roman_ctx* c, hipStream_t stream, int32_t F, const Red
     HIPCHK(c, hipGetLastError());
     return ROMAN_OK;
 }
-}  // namespace
 
-namespace {
 // The host arrays of the tail of roman_align_lc_batch (checked and staged behind the batch inputs).
 struct LcHostIn {
     const roman_lc_params_t* P; const double* T_ref; const int32_t* enable; const double* FL; int32_t n_left; const int32_t* iL;
@@ -2010,25 +2101,17 @@ int align_batch_host(roman_ctx_t* c, const roman_params_t* params, int32_t B,
         if (B == 0) { *lci->cnt = 0; return ROMAN_OK; }
     }
     if (B == 0) return ROMAN_OK;
-    if (!off1 || !n1 || !off2 || !n2 || !assoc_out || !n_assoc_out || !T_out || !status_out || kmax < 0)
-        return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer or kmax < 0");
-    if (assoc && !assoc_off) return fail(c, ROMAN_E_INVALID, "assoc given without assoc_off");
+    if (!assoc_out || !n_assoc_out || !T_out || !status_out || kmax < 0) return fail(c, ROMAN_E_INVALID, "NULL output pointer or kmax < 0");
+    BatchCheck chk; chk.n_objects = n_objects; chk.assoc = assoc; chk.assoc_off = assoc_off; chk.assoc_on_host = true; chk.whole_list = true;
+    int rc = check_batch(c, B, off1, n1, off2, n2, chk);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
     DevParams D;
-    int rc = make_dev_params(c, params, F, &D);
+    rc = make_dev_params(c, params, F, &D);
     if (rc) return rc;
     int64_t sumA = 0;
-    if (assoc && assoc_off[0] != 0) return fail(c, ROMAN_E_INVALID, "assoc_off[0] must be 0");
     for (int b = 0; b < B; ++b) {
-        if (n1[b] < 0 || n2[b] < 0 || off1[b] < 0 || off2[b] < 0 || off1[b] + n1[b] > n_objects || off2[b] + n2[b] > n_objects)
-            return fail(c, ROMAN_E_INVALID, "problem %d reads objects outside feats[0..%lld)", b, (long long)n_objects);
-        if (assoc) {
-            if (assoc_off[b + 1] < assoc_off[b]) return fail(c, ROMAN_E_INVALID, "assoc_off is not non-decreasing at problem %d", b);
-            for (int64_t k = assoc_off[b]; k < assoc_off[b + 1]; ++k)
-                if (assoc[2 * k] < 0 || assoc[2 * k] >= n1[b] || assoc[2 * k + 1] < 0 || assoc[2 * k + 1] >= n2[b])
-                    return fail(c, ROMAN_E_INVALID, "problem %d: association %lld = (%d,%d) out of range", b, (long long)(k - assoc_off[b]), assoc[2 * k], assoc[2 * k + 1]);
-        }
         const int64_t na = assoc ? (assoc_off[b + 1] - assoc_off[b]) : 0;
         sumA += na > 0 ? na : (int64_t)n1[b] * n2[b];      // an empty list means all-to-all
     }
@@ -2041,24 +2124,17 @@ int align_batch_host(roman_ctx_t* c, const roman_params_t* params, int32_t B,
         sumA = 0;
         for (int b = 0; b < B; ++b) sumA += (int64_t)n1[b] * n2[b];
     }
-    const size_t fbytes = sizeof(double) * (size_t)std::max<int64_t>((n_objects + red.rows) * F, 1);   // the pool, and the rows of the affected problems behind it
-    HIPCHK(c, WS.hFeats.ensure(fbytes));
-    if (n_objects * F > 0) HIPCHK(c, hipMemcpyAsync(WS.hFeats.p, feats, sizeof(double) * (size_t)(n_objects * F), hipMemcpyHostToDevice, WS.stream));
+    const double* dFeats = nullptr; const int32_t* dA = nullptr;
+    rc = upload_inputs(c, feats, n_objects, F, red.rows /* the rows of the affected problems, behind the pool */, assoc, assoc ? assoc_off[B] : 0, &dFeats, &dA);
+    if (rc) return rc;
     if (idh) { rc = enqueue_shared_gather(c, WS.stream, F, red, WS.hFeats.as<double>()); if (rc) return rc; }
-    const int32_t* dA = nullptr;
-    if (assoc) {
-        const int64_t rows = assoc_off[B];
-        HIPCHK(c, WS.hAssoc.ensure(sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(rows, 1)));
-        if (rows > 0) HIPCHK(c, hipMemcpyAsync(WS.hAssoc.p, assoc, sizeof(int32_t) * 2 * (size_t)rows, hipMemcpyHostToDevice, WS.stream));
-        dA = WS.hAssoc.as<int32_t>();
-    }
     const double* dU0 = nullptr;
     if (u0) {
         HIPCHK(c, WS.hU0.ensure(sizeof(double) * (size_t)std::max<int64_t>(sumA, 1)));
         if (sumA > 0) HIPCHK(c, hipMemcpyAsync(WS.hU0.p, u0, sizeof(double) * (size_t)sumA, hipMemcpyHostToDevice, WS.stream));
         dU0 = WS.hU0.as<double>();
     }
-    const BatchIn in{B, WS.hFeats.as<double>(), off1, n1, off2, n2, F, dA, assoc_off};
+    const BatchIn in{B, dFeats, off1, n1, off2, n2, F, dA, assoc_off};
     if (!lci) return align_to_host(c, D, params, in, dU0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out);
     // the tail's inputs in one staging block: doubles first (T_ref | FL | FR), then the int32 arrays (enable | iL | iR)
     const size_t nRef = lci->T_ref ? (size_t)B * 16 : 0, nFL = lci->FL ? (size_t)lci->n_left * 16 : 0, nFR = lci->FR ? (size_t)lci->n_right * 16 : 0;
@@ -2136,13 +2212,11 @@ int roman_shared_ids_dev(roman_ctx_t* c, int32_t B, const int64_t* ids, const in
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
     if (B == 0) return ROMAN_OK;
-    if (!off1 || !n1 || !off2 || !n2 || !kept) return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer");
-    int64_t sumN = 0;
-    for (int b = 0; b < B; ++b) {
-        if (n1[b] < 0 || n2[b] < 0 || off1[b] < 0 || off2[b] < 0) return fail(c, ROMAN_E_INVALID, "problem %d: negative size or offset", b);
-        sumN += (int64_t)n1[b] + n2[b];
-    }
-    if (sumN > 0 && (!ids || !keep)) return fail(c, ROMAN_E_INVALID, "ids / keep is NULL");
+    if (!kept) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
+    bool any = false;
+    const int rc = check_batch(c, B, off1, n1, off2, n2, BatchCheck{}, &any);
+    if (rc) return rc;
+    if (any && (!ids || !keep)) return fail(c, ROMAN_E_INVALID, "ids / keep is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     return enqueue_shared_mark(c, c->stream, B, ids, off1, n1, off2, n2, keep, kept);
 }
@@ -2158,21 +2232,16 @@ int roman_align_batch_resident(roman_ctx_t* c, const roman_params_t* params, int
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (B < 0 || F < 0) return fail(c, ROMAN_E_INVALID, "negative size");
     if (B == 0) return ROMAN_OK;
-    if (!off1 || !n1 || !off2 || !n2 || !assoc_out || !n_assoc_out || !T_out || !status_out || kmax < 0)
-        return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer or kmax < 0");
-    if (assoc && !assoc_off) return fail(c, ROMAN_E_INVALID, "assoc given without assoc_off");
-    if (assoc && assoc_off[0] != 0) return fail(c, ROMAN_E_INVALID, "assoc_off[0] must be 0");
+    if (!assoc_out || !n_assoc_out || !T_out || !status_out || kmax < 0) return fail(c, ROMAN_E_INVALID, "NULL output pointer or kmax < 0");
+    BatchCheck chk; chk.assoc = assoc; chk.assoc_off = assoc_off; chk.whole_list = true;
     bool any = false;
-    for (int b = 0; b < B; ++b) {
-        if (n1[b] < 0 || n2[b] < 0 || off1[b] < 0 || off2[b] < 0) return fail(c, ROMAN_E_INVALID, "problem %d: negative size or offset", b);
-        if (assoc && assoc_off[b + 1] < assoc_off[b]) return fail(c, ROMAN_E_INVALID, "assoc_off is not non-decreasing at problem %d", b);
-        any = any || n1[b] > 0 || n2[b] > 0;
-    }
+    int rc = check_batch(c, B, off1, n1, off2, n2, chk, &any);
+    if (rc) return rc;
     if (!feats && any) return fail(c, ROMAN_E_INVALID, "feats is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
     DevParams D;
-    int rc = make_dev_params(c, params, F, &D);
+    rc = make_dev_params(c, params, F, &D);
     if (rc) return rc;
     const BatchIn in{B, feats, off1, n1, off2, n2, F, assoc, assoc_off};
     return align_to_host(c, D, params, in, u0, kmax, assoc_out, n_assoc_out, T_out, status_out, stats_out);
@@ -2198,14 +2267,10 @@ static int run_mno(roman_ctx* c, const DevParams& D0, const roman_params_t* para
     if (rc) return rc;
     int64_t sumA = 0, maxA = 0; for (const ProbDesc& d : hd) { sumA += d.nA; maxA = std::max<int64_t>(maxA, d.nA); }
     // the solver's block of one round: T | stats | assoc | n | status
-    const size_t kb = (size_t)B * (size_t)std::max(kmax, 1);
-    const size_t oT = 0, oS = oT + sizeof(double) * 16 * (size_t)B, oA = oS + sizeof(roman_stats_t) * (size_t)B,
-                 oNn = oA + sizeof(int32_t) * 2 * kb, oSt = oNn + sizeof(int32_t) * (size_t)B, total = oSt + sizeof(int32_t) * (size_t)B;
-    HIPCHK(c, WS.mnoOut.ensure(total));
+    const SolverBlock blk(B, kmax);
+    HIPCHK(c, WS.mnoOut.ensure(blk.end));
     if (K > 1) HIPCHK(c, WS.mnoVals.ensure(sizeof(double) * (size_t)std::max<long long>(WS.capNnz, 1)));
-    char* const dev = WS.mnoOut.as<char>();
-    const BatchOut out{kmax, reinterpret_cast<int32_t*>(dev + oA), reinterpret_cast<int32_t*>(dev + oNn), reinterpret_cast<double*>(dev + oT),
-                       reinterpret_cast<int32_t*>(dev + oSt), reinterpret_cast<roman_stats_t*>(dev + oS)};
+    const BatchOut out = blk.at(WS.mnoOut.as<char>());
     for (int r = 0; r < K && !rc; ++r) {
         if (r > 0) std::swap(WS.vals, WS.mnoVals);              // this round's solve reads the masked copy
         rc = enqueue_solve(c, D, B, sumA, maxA, in.feats, in.assoc, nullptr, false, 0, out);
@@ -2226,18 +2291,18 @@ static int run_mno(roman_ctx* c, const DevParams& D0, const roman_params_t* para
 }
 
 static int mno_check(roman_ctx* c, const roman_params_t* params, int32_t B, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
-                     const int32_t* assoc, const int64_t* assoc_off, int32_t K, int32_t kmax, const void* assoc_out, const void* sol_out)
+                     const BatchCheck& chk, int32_t K, int32_t kmax, const void* assoc_out, const void* sol_out, bool* any = nullptr)
 {
     if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
     if (K < 1 || K > ROMAN_MNO_MAX_SOLUTIONS) return fail(c, ROMAN_E_INVALID, "num_solutions must be 1..%d (got %d)", ROMAN_MNO_MAX_SOLUTIONS, K);
     if (B == 0) return ROMAN_OK;
     if (!params) return fail(c, ROMAN_E_INVALID, "params is NULL");
-    if (!off1 || !n1 || !off2 || !n2 || !assoc_out || !sol_out || kmax < 0) return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer or kmax < 0");
-    if (assoc && !assoc_off) return fail(c, ROMAN_E_INVALID, "assoc given without assoc_off");
+    if (!assoc_out || !sol_out || kmax < 0) return fail(c, ROMAN_E_INVALID, "NULL output pointer or kmax < 0");
+    const int rc = check_batch(c, B, off1, n1, off2, n2, chk, any);
+    if (rc) return rc;
     if (params->maxiniters < 1 || params->maxlsiters < 1) return fail(c, ROMAN_E_UNSUPPORTED, "roman_mno_batch needs maxiniters >= 1 and maxlsiters >= 1");
     for (int b = 0; b < B; ++b) {
-        if (n1[b] < 0 || n2[b] < 0) return fail(c, ROMAN_E_INVALID, "negative map size in problem %d", b);
-        const int64_t nl = assoc ? assoc_off[b + 1] - assoc_off[b] : 0;
+        const int64_t nl = chk.assoc ? chk.assoc_off[b + 1] - chk.assoc_off[b] : 0;
         const int64_t na = nl > 0 ? nl : (int64_t)n1[b] * n2[b];
         if (na > ROMAN_MNO_MAX_ASSOC) return fail(c, ROMAN_E_TOO_LARGE, "problem %d has %lld associations; roman_mno_batch serves at most %d per problem", b, (long long)na, ROMAN_MNO_MAX_ASSOC);
     }
@@ -2252,36 +2317,18 @@ int roman_mno_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
                         roman_mno_solution_t* sol_out, roman_stats_t* stats_out)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = mno_check(c, params, B, off1, n1, off2, n2, assoc, assoc_off, num_solutions, kmax, assoc_out, sol_out);
+    BatchCheck chk; chk.assoc = assoc; chk.assoc_off = assoc_off;
+    bool any = false;
+    int rc = mno_check(c, params, B, off1, n1, off2, n2, chk, num_solutions, kmax, assoc_out, sol_out, &any);
     if (rc || B == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     DevParams D;
     rc = make_dev_params(c, params, F, &D);
     if (rc) return rc;
-    if (!feats) {
-        bool any = false;
-        for (int b = 0; b < B; ++b) any = any || (n1[b] > 0 || n2[b] > 0);
-        if (any) return fail(c, ROMAN_E_INVALID, "feats is NULL");
-    }
+    if (!feats && any) return fail(c, ROMAN_E_INVALID, "feats is NULL");
     static_assert(STREAM_MAXL == ROMAN_MNO_MAX_ASSOC, "the documented cap is the stream layout's");
     const BatchIn in{B, feats, off1, n1, off2, n2, F, assoc, assoc_off};
-    c->last.scored = false; c->last.solved = false;            // workspace 0 is reused: the stepwise problem it held is gone
-    if (c->pipeline >= 2) {                                     // the workspace rotation of roman_align_batch_dev
-        const int k = c->next_ws;
-        c->next_ws = (c->next_ws + 1) % c->pipeline; c->latest_ws = k;
-        HIPCHK(c, hipEventRecord(c->evIn, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->istream[k], c->evIn, 0));
-        c->cur = k; c->ws[k].stream = c->istream[k];
-        rc = run_mno(c, D, params, in, num_solutions, kmax, assoc_out, sol_out, stats_out);
-        if (!rc) {
-            HIPCHK(c, hipEventRecord(c->ws[k].done, c->ws[k].stream));
-            c->ws[k].issued = true;
-        }
-        c->cur = 0;
-        return rc;
-    }
-    c->cur = 0; WS.stream = c->stream;
-    return run_mno(c, D, params, in, num_solutions, kmax, assoc_out, sol_out, stats_out);
+    return on_next_workspace(c, [&](hipStream_t) -> int { return run_mno(c, D, params, in, num_solutions, kmax, assoc_out, sol_out, stats_out); });
 }
 
 int roman_mno_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
@@ -2293,33 +2340,16 @@ int roman_mno_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (n_objects < 0 || F < 0) return fail(c, ROMAN_E_INVALID, "negative size");
-    if (B > 0 && assoc && assoc_off && assoc_off[0] != 0) return fail(c, ROMAN_E_INVALID, "assoc_off[0] must be 0");
-    if (B > 0 && assoc && assoc_off)
-        for (int b = 0; b < B; ++b) if (assoc_off[b + 1] < assoc_off[b]) return fail(c, ROMAN_E_INVALID, "assoc_off is not non-decreasing at problem %d", b);
-    int rc = mno_check(c, params, B, off1, n1, off2, n2, assoc, assoc_off, num_solutions, kmax, assoc_out, sol_out);
+    BatchCheck chk; chk.n_objects = n_objects; chk.assoc = assoc; chk.assoc_off = assoc_off; chk.assoc_on_host = true; chk.whole_list = true;
+    int rc = mno_check(c, params, B, off1, n1, off2, n2, chk, num_solutions, kmax, assoc_out, sol_out);
     if (rc || B == 0) return rc;
     const int K = num_solutions;
-    for (int b = 0; b < B; ++b) {
-        if (off1[b] < 0 || off2[b] < 0 || off1[b] + n1[b] > n_objects || off2[b] + n2[b] > n_objects)
-            return fail(c, ROMAN_E_INVALID, "problem %d reads objects outside feats[0..%lld)", b, (long long)n_objects);
-        if (assoc)
-            for (int64_t k = assoc_off[b]; k < assoc_off[b + 1]; ++k)
-                if (assoc[2 * k] < 0 || assoc[2 * k] >= n1[b] || assoc[2 * k + 1] < 0 || assoc[2 * k + 1] >= n2[b])
-                    return fail(c, ROMAN_E_INVALID, "problem %d: association %lld = (%d,%d) out of range", b, (long long)(k - assoc_off[b]), assoc[2 * k], assoc[2 * k + 1]);
-    }
-    if (!feats && n_objects * F > 0) return fail(c, ROMAN_E_INVALID, "feats is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
     { DevParams Dchk; rc = make_dev_params(c, params, F, &Dchk); if (rc) return rc; }
-    HIPCHK(c, WS.hFeats.ensure(sizeof(double) * (size_t)std::max<int64_t>(n_objects * F, 1)));
-    if (n_objects * F > 0) HIPCHK(c, hipMemcpyAsync(WS.hFeats.p, feats, sizeof(double) * (size_t)(n_objects * F), hipMemcpyHostToDevice, WS.stream));
-    const int32_t* dA = nullptr;
-    if (assoc) {
-        const int64_t rows = assoc_off[B];
-        HIPCHK(c, WS.hAssoc.ensure(sizeof(int32_t) * 2 * (size_t)std::max<int64_t>(rows, 1)));
-        if (rows > 0) HIPCHK(c, hipMemcpyAsync(WS.hAssoc.p, assoc, sizeof(int32_t) * 2 * (size_t)rows, hipMemcpyHostToDevice, WS.stream));
-        dA = WS.hAssoc.as<int32_t>();
-    }
+    const double* dFeats = nullptr; const int32_t* dA = nullptr;
+    rc = upload_inputs(c, feats, n_objects, F, 0, assoc, assoc ? assoc_off[B] : 0, &dFeats, &dA);
+    if (rc) return rc;
     // outputs on the device: solutions | statistics | association rows
     const size_t nSol = (size_t)B * (size_t)K, rowsPer = (size_t)std::max(kmax, 0) * 2;
     const size_t oSol = 0, oStats = oSol + sizeof(roman_mno_solution_t) * nSol, oAssoc = oStats + sizeof(roman_stats_t) * nSol,
@@ -2330,54 +2360,39 @@ int roman_mno_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
     roman_mno_solution_t* dSol = reinterpret_cast<roman_mno_solution_t*>(dev + oSol);
     roman_stats_t* dStats = reinterpret_cast<roman_stats_t*>(dev + oStats);
     int32_t* dAssoc = reinterpret_cast<int32_t*>(dev + oAssoc);
-    const double* dFeats = WS.hFeats.as<double>();
     // calls of host_chunk problems, host_depth of them in flight; skipped problems are issued again, those only
-    const int chunk = std::max(1, c->host_chunk), saved = c->pipeline;
-    const int depth = B > chunk ? c->host_depth : 1;
-    rc = roman_ctx_set_pipeline(c, depth);
-    if (rc) return rc;
-    auto restore = [&](int code) -> int { const int r2 = roman_ctx_set_pipeline(c, saved); c->cur = 0; c->ws[0].stream = c->stream; return code ? code : r2; };
+    const int chunk = std::max(1, c->host_chunk);
+    DepthScope scope(c, B > chunk ? c->host_depth : 1);
+    if (scope.rc) return scope.rc;
     auto issue = [&](int lo, int hi) -> int {
         return roman_mno_batch_dev(c, params, hi - lo, dFeats, off1 + lo, n1 + lo, off2 + lo, n2 + lo, F, dA, dA ? assoc_off + lo : nullptr, K, kmax,
                                    dAssoc + (size_t)lo * (size_t)K * rowsPer, dSol + (size_t)lo * (size_t)K, dStats + (size_t)lo * (size_t)K);
     };
-    int lo = 0;
-    if (depth >= 2) {                                           // the first call alone: the calls behind it size their pools from what it needed
-        rc = issue(0, std::min(B, chunk));
-        if (!rc) rc = roman_ctx_sync(c);
-        if (rc) return restore(rc);
-        harvest_totals(c, true);
-        lo = std::min(B, chunk);
-    }
-    for (; lo < B; lo += chunk) { rc = issue(lo, std::min(B, lo + chunk)); if (rc) return restore(rc); }
+    rc = issue_chunks(c, B, chunk, c->pipeline >= 2, issue);
+    if (rc) return rc;
     std::vector<roman_mno_solution_t> hs(nSol);
     for (int attempt = 1; ; ++attempt) {
         rc = roman_ctx_sync(c);
-        if (rc) return restore(rc);
+        if (rc) return rc;
         harvest_totals(c, true);
-        if (hipMemcpy(hs.data(), dSol, sizeof(roman_mno_solution_t) * nSol, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return restore(fail(c, ROMAN_E_HIP, "solution read-back failed")); }
+        if (hipMemcpy(hs.data(), dSol, sizeof(roman_mno_solution_t) * nSol, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return fail(c, ROMAN_E_HIP, "solution read-back failed"); }
+        auto skipped = [&](int b) { return (hs[(size_t)b * K].status & ROMAN_ST_WORKSPACE) != 0; };
         int nskip = 0;
-        for (int b = 0; b < B; ++b) nskip += (hs[(size_t)b * K].status & ROMAN_ST_WORKSPACE) ? 1 : 0;
+        for (int b = 0; b < B; ++b) nskip += skipped(b) ? 1 : 0;
         if (!nskip) break;
-        if (attempt >= MAX_ATTEMPTS) return restore(fail(c, ROMAN_E_NOMEM, "the sparse workspace of %d problem(s) still does not fit after %d attempts", nskip, attempt));
-        for (int b = 0; b < B; ) {
-            if (!(hs[(size_t)b * K].status & ROMAN_ST_WORKSPACE)) { ++b; continue; }
-            int e = b + 1;
-            while (e < B && e - b < chunk && (hs[(size_t)e * K].status & ROMAN_ST_WORKSPACE)) ++e;
-            rc = issue(b, e);
-            if (rc) return restore(rc);
-            b = e;
-        }
+        if (attempt >= MAX_ATTEMPTS) return fail(c, ROMAN_E_NOMEM, "the sparse workspace of %d problem(s) still does not fit after %d attempts", nskip, attempt);
+        rc = reissue_runs(B, chunk, skipped, issue);
+        if (rc) return rc;
     }
     memcpy(sol_out, hs.data(), sizeof(roman_mno_solution_t) * nSol);
-    if (stats_out && hipMemcpy(stats_out, dStats, sizeof(roman_stats_t) * nSol, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return restore(fail(c, ROMAN_E_HIP, "statistics read-back failed")); }
-    if (rowsPer && hipMemcpy(assoc_out, dAssoc, sizeof(int32_t) * nSol * rowsPer, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return restore(fail(c, ROMAN_E_HIP, "association read-back failed")); }
-    return restore(ROMAN_OK);
+    if (stats_out && hipMemcpy(stats_out, dStats, sizeof(roman_stats_t) * nSol, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return fail(c, ROMAN_E_HIP, "statistics read-back failed"); }
+    if (rowsPer && hipMemcpy(assoc_out, dAssoc, sizeof(int32_t) * nSol * rowsPer, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return fail(c, ROMAN_E_HIP, "association read-back failed"); }
+    return scope.close(ROMAN_OK);
 }
 
 // --- RANSAC registration on object centres, batched ([REF roman/align/ransac_reg.py:16-53]) ----------------------
 static int ransac_check(roman_ctx* c, const roman_ransac_params_t* P, int32_t B, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
-                        int32_t kmax, const void* assoc_out, const void* rec_out)
+                        int64_t n_objects /* -1: not known (device pointers) */, int32_t kmax, const void* assoc_out, const void* rec_out)
 {
     if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
     if (!P) return fail(c, ROMAN_E_INVALID, "rparams is NULL");
@@ -2387,13 +2402,9 @@ static int ransac_check(roman_ctx* c, const roman_ransac_params_t* P, int32_t B,
     if (!(P->max_dist > 0.0) || !std::isfinite(P->max_dist)) return fail(c, ROMAN_E_INVALID, "max_dist must be > 0 (got %g)", P->max_dist);
     if (!(P->confidence > 0.0 && P->confidence < 1.0)) return fail(c, ROMAN_E_INVALID, "confidence must lie in (0, 1) (got %g)", P->confidence);
     if (B == 0) return ROMAN_OK;
-    if (!off1 || !n1 || !off2 || !n2 || !rec_out || kmax < 0 || (kmax > 0 && !assoc_out)) return fail(c, ROMAN_E_INVALID, "NULL metadata/output pointer or kmax < 0");
-    for (int b = 0; b < B; ++b) {
-        if (n1[b] < 0 || n2[b] < 0 || off1[b] < 0 || off2[b] < 0) return fail(c, ROMAN_E_INVALID, "problem %d: negative size or offset", b);
-        if (n1[b] > ROMAN_RANSAC_MAX_OBJECTS || n2[b] > ROMAN_RANSAC_MAX_OBJECTS)
-            return fail(c, ROMAN_E_TOO_LARGE, "problem %d has %d x %d objects; roman_ransac_batch serves at most %d per side", b, n1[b], n2[b], ROMAN_RANSAC_MAX_OBJECTS);
-    }
-    return ROMAN_OK;
+    if (!rec_out || kmax < 0 || (kmax > 0 && !assoc_out)) return fail(c, ROMAN_E_INVALID, "NULL output pointer or kmax < 0");
+    BatchCheck chk; chk.n_objects = n_objects; chk.side_cap = ROMAN_RANSAC_MAX_OBJECTS; chk.cap_code = ROMAN_E_TOO_LARGE; chk.cap_who = "roman_ransac_batch";
+    return check_batch(c, B, off1, n1, off2, n2, chk);
 }
 
 int roman_ransac_batch_dev(roman_ctx_t* c, const roman_ransac_params_t* rparams, int32_t B,
@@ -2401,27 +2412,17 @@ int roman_ransac_batch_dev(roman_ctx_t* c, const roman_ransac_params_t* rparams,
                            int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, kmax, assoc_out, rec_out);
+    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, -1, kmax, assoc_out, rec_out);
     if (rc || B == 0) return rc;
     int maxN = 0; bool any = false;
     for (int b = 0; b < B; ++b) { maxN = std::max(maxN, n1[b] + n2[b]); any = any || (n1[b] > 0 && n2[b] > 0); }
     if (!pts && any) return fail(c, ROMAN_E_INVALID, "pts is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t stream = c->stream;
-    if (!c->ransacEvent) HIPCHK(c, hipEventCreateWithFlags(&c->ransacEvent, hipEventDisableTiming));
-    if (c->ransacPending) { HIPCHK(c, hipEventSynchronize(c->ransacEvent)); c->ransacPending = false; }   // (the previous call's upload: the staging is rewritten)
-    if (c->pinnedRansacCap < (size_t)B) {
-        if (c->pinnedRansac) (void)hipHostFree(c->pinnedRansac);
-        c->pinnedRansac = nullptr; c->pinnedRansacCap = 0;
-        const size_t cap = (size_t)B + (size_t)B / 4 + 64;
-        HIPCHK(c, hipHostMalloc((void**)&c->pinnedRansac, sizeof(RansacDesc) * cap, hipHostMallocDefault));
-        c->pinnedRansacCap = cap;
-    }
-    for (int b = 0; b < B; ++b) c->pinnedRansac[b] = RansacDesc{off1[b], off2[b], n1[b], n2[b]};
-    HIPCHK(c, c->ransacDesc.ensure(sizeof(RansacDesc) * (size_t)B));
-    HIPCHK(c, hipMemcpyAsync(c->ransacDesc.p, c->pinnedRansac, sizeof(RansacDesc) * (size_t)B, hipMemcpyHostToDevice, stream));
-    HIPCHK(c, hipEventRecord(c->ransacEvent, stream));
-    c->ransacPending = true;
+    RansacDesc* staged = nullptr;
+    HIPCHK(c, c->ransacStage.stage((size_t)B, &staged));
+    for (int b = 0; b < B; ++b) staged[b] = RansacDesc{off1[b], off2[b], n1[b], n2[b]};
+    HIPCHK(c, c->ransacStage.upload(c->ransacDesc, (size_t)B, stream));
     const size_t lds = sizeof(double) * 3 * (size_t)std::max(maxN, 1);          // both point sets of the largest problem (at most 48 KB)
     hipLaunchKernelGGL(k_ransac, dim3((unsigned)B), dim3(RANSAC_NT), lds, stream, *rparams, (int)B, c->ransacDesc.as<RansacDesc>(), pts,
                        (int)kmax, assoc_out, rec_out, counts_out);
@@ -2435,17 +2436,14 @@ int roman_ransac_batch(roman_ctx_t* c, const roman_ransac_params_t* rparams, int
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (n_objects < 0) return fail(c, ROMAN_E_INVALID, "negative size");
-    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, kmax, assoc_out, rec_out);
+    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, n_objects, kmax, assoc_out, rec_out);
     if (rc || B == 0) return rc;
-    for (int b = 0; b < B; ++b)
-        if (off1[b] + n1[b] > n_objects || off2[b] + n2[b] > n_objects)
-            return fail(c, ROMAN_E_INVALID, "problem %d reads objects outside pts[0..%lld)", b, (long long)n_objects);
-    if (!pts && n_objects > 0) return fail(c, ROMAN_E_INVALID, "pts is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
     c->last.scored = false; c->last.solved = false;            // workspace 0's feature staging is reused: the stepwise problem it held is gone
-    HIPCHK(c, WS.hFeats.ensure(sizeof(double) * 3 * (size_t)std::max<int64_t>(n_objects, 1)));
-    if (n_objects > 0) HIPCHK(c, hipMemcpyAsync(WS.hFeats.p, pts, sizeof(double) * 3 * (size_t)n_objects, hipMemcpyHostToDevice, WS.stream));
+    const double* dPts = nullptr;
+    rc = upload_inputs(c, pts, n_objects, 3, 0, nullptr, 0, &dPts);
+    if (rc) return rc;
     // outputs on the device: records | association rows | counts
     const size_t rowsPer = (size_t)kmax * 2, nCounts = counts_out ? (size_t)B * (size_t)rparams->max_iteration : 0;
     const size_t oRec = 0, oAssoc = oRec + sizeof(roman_ransac_record_t) * (size_t)B, oCnt = oAssoc + sizeof(int32_t) * std::max<size_t>((size_t)B * rowsPer, 2),
@@ -2461,7 +2459,7 @@ int roman_ransac_batch(roman_ctx_t* c, const roman_ransac_params_t* rparams, int
     const int chunk = std::max(1, c->host_chunk);
     for (int lo = 0; lo < B; lo += chunk) {
         const int hi = std::min(B, lo + chunk);
-        rc = roman_ransac_batch_dev(c, rparams, hi - lo, WS.hFeats.as<double>(), off1 + lo, n1 + lo, off2 + lo, n2 + lo, kmax,
+        rc = roman_ransac_batch_dev(c, rparams, hi - lo, dPts, off1 + lo, n1 + lo, off2 + lo, n2 + lo, kmax,
                                     dAssoc + (size_t)lo * rowsPer, dRec + lo, dCnt ? dCnt + (size_t)lo * (size_t)rparams->max_iteration : nullptr);
         if (rc) return rc;
     }
