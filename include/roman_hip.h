@@ -656,6 +656,75 @@ ROMAN_API int roman_ransac_batch(roman_ctx_t* ctx, const roman_ransac_params_t* 
                                  int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out);
 
 /* ------------------------------------------------------------------------------------------- */
+/* submaps from a whole map: slice, prune, pack (radius mode)                                  */
+/* ------------------------------------------------------------------------------------------- */
+
+/* The radius mode of submaps_from_roman_map [REF roman/map/map.py:297-339] (force_fill_submaps=False) for the S submap
+   centres of one map, on the device: which of the N map segments belong to each submap, in which order, and their feature
+   rows in the submap's gravity-aligned frame — the feature pool the batch calls consume, in fixed slots of `cap` rows per
+   submap (submap s owns rows [s*cap, s*cap + count[s])), so offsets are known before the call.  DESIGN.md §4.8 is the contract.
+   The centres themselves come from a sequential scan of the trajectory [REF :300-309], which stays on the host
+   (roman_amd.align.submaps.submap_centers), as does the force_fill_submaps mode [REF :264-295] (slices of a time-sorted list). */
+typedef struct roman_submap_params {
+    int32_t point_dim;       /* 2 or 3: leading centre components an output row keeps (the input row always carries x y z)        */
+    int32_t max_size;        /* SubmapParams.max_size [REF roman/map/map.py:332-339]; <= 0: None (no sort, rows in map order)     */
+    int32_t cap;             /* rows per submap slot, >= 1; must equal max_size when max_size > 0                                 */
+    int32_t prune_by_time;   /* pruning_method == 'time' [REF :333-334]; 0: distance [REF :335-336]; read only with max_size > 0  */
+    int32_t use_radius;      /* 0: SubmapParams.radius is None [REF :323]                                                         */
+    int32_t reserved0;       /* must be 0                                                                                         */
+    double  radius;          /* SubmapParams.radius (read only with use_radius)                                                   */
+    int32_t reserved[2];     /* must be 0                                                                                         */
+} roman_submap_params_t;
+
+/* One submap centre, prepared by the host (S is small) */
+typedef struct roman_submap_desc {
+    double pos[3];             /* pose_flu[:3,3], the centre the radius test measures from [REF roman/map/map.py:324]             */
+    double T_center_odom[16];  /* row-major 4x4 inv(pose_gravity_aligned) [REF :328-330]                                          */
+    double time;               /* the submap's time (key of the time pruning [REF :334])                                          */
+    double t_hi;               /* next submap's time + time_threshold, +inf for the last submap [REF :316-318]                    */
+    double t_lo;               /* previous submap's time - time_threshold, -inf for the first [REF :315,319]                      */
+} roman_submap_desc_t;
+
+/*
+ * roman_submaps_dev: bulk pointers DEVICE, the descriptors HOST (the library stages them).  A PURE ENQUEUE on the context's
+ * stream, complete once that stream is synchronised.  S == 0 and N == 0 are legal.
+ *   seg_feats  float64[N][F]: one row per map segment in map order, odom frame: [x y z | ratio features | descriptor]
+ *   seg_times  float64[N][2]: first_seen, last_seen
+ *   seg_ids    int64[N] or NULL
+ *   Segment k belongs to submap s when  (no radius, or sqrt(((cx-px)^2 + (cy-py)^2) + (cz-pz)^2) < radius)  and
+ *   NOT (first_seen > t_hi OR last_seen < t_lo) [REF :317-326].  Its centre becomes c' = R c + t of T_center_odom, each component
+ *   ((r0 x + r1 y) + r2 z) + t, without fused multiply-adds; every other column is copied bit for bit.  With max_size set the rows
+ *   are ordered by ascending key — |c'| (distance pruning) or |(first_seen + last_seen) / 2 - time| (time pruning) —, ties by
+ *   ascending map index (Python's stable sorted() [REF :338]), and cut to max_size; the sort happens also when fewer qualify.
+ *   Without max_size the rows stay in map order and a submap with more than `cap` members keeps the first `cap` and reports
+ *   ROMAN_ST_ASSOC_TRUNCATED.  Keys must not be NaN (one that is sorts as +inf).
+ *   pool       float64[S*cap][point_dim + F - 3]; rows beyond count[s] in a slot are not written
+ *   count      int32[S]: rows of each submap (0: the reference drops such a submap afterwards [REF :341]; so does the Python layer)
+ *   src        int32[S*cap]: map index of every row
+ *   ids_out    int64[S*cap] or NULL (needs seg_ids)
+ *   status     int32[S]: ROMAN_ST_OK / ROMAN_ST_ASSOC_TRUNCATED
+ *   desc_dim, desc_out   float64[S][desc_dim] or NULL: submap_descriptor 'mean_semantic' [REF :343-346] — the LAST desc_dim columns
+ *              of the rows, added in output order, divided by the count; untouched for an empty submap
+ * A submap's candidates beyond the first 4096 go through a per-submap scratch the context owns (S * (N - 4096) entries of 12 bytes).
+ * Errors: bad dims (point_dim, F < 3, N / S < 0, desc_dim outside [0, F - 3]), cap < 1, cap != max_size > 0, reserved words not 0,
+ * a NULL pointer that is needed -> ROMAN_E_INVALID; a scratch allocation that fails -> ROMAN_E_NOMEM, the context stays usable.
+ */
+ROMAN_API int roman_submaps_dev(roman_ctx_t* ctx, const roman_submap_params_t* sparams, int32_t N, int32_t F,
+                                const double* seg_feats, const double* seg_times, const int64_t* seg_ids,
+                                int32_t S, const roman_submap_desc_t* descs,
+                                double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status,
+                                int32_t desc_dim, double* desc_out);
+
+/* The same with HOST pointers everywhere ([REF roman/map/map.py:297-346] for a caller that holds NumPy arrays).  Synchronous:
+   copies in, runs roman_submaps_dev, brings count, src, ids_out, status, desc_out and — pool != NULL — the pool back.  The
+   caller's src, ids_out, desc_out and pool go up first: what the device call leaves untouched comes back as it was. */
+ROMAN_API int roman_submaps(roman_ctx_t* ctx, const roman_submap_params_t* sparams, int32_t N, int32_t F,
+                            const double* seg_feats, const double* seg_times, const int64_t* seg_ids,
+                            int32_t S, const roman_submap_desc_t* descs,
+                            double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status,
+                            int32_t desc_dim, double* desc_out);
+
+/* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */
 /* ------------------------------------------------------------------------------------------- */
 

@@ -202,9 +202,39 @@ class RomanRansacRecord(C.Structure):
 
 ROMAN_RANSAC_MAX_OBJECTS = 1024
 
+
+class RomanSubmapParams(C.Structure):
+    """roman_submap_params_t"""
+    _fields_ = [
+        ("point_dim", C.c_int32),
+        ("max_size", C.c_int32),
+        ("cap", C.c_int32),
+        ("prune_by_time", C.c_int32),
+        ("use_radius", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("radius", C.c_double),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+class RomanSubmapDesc(C.Structure):
+    """roman_submap_desc_t"""
+    _fields_ = [
+        ("pos", C.c_double * 3),
+        ("T_center_odom", C.c_double * 16),
+        ("time", C.c_double),
+        ("t_hi", C.c_double),
+        ("t_lo", C.c_double),
+    ]
+
+
+SUBMAP_LDS_CAND = 4096      # candidates of a submap the select kernel holds in LDS (kernels.hip.h); more go through the context's scratch
+
 STATS_NBYTES = C.sizeof(RomanStats)
 MNO_SOLUTION_NBYTES = C.sizeof(RomanMnoSolution)
 RANSAC_RECORD_NBYTES = C.sizeof(RomanRansacRecord)
+SUBMAP_PARAMS_NBYTES = C.sizeof(RomanSubmapParams)
+SUBMAP_DESC_NBYTES = C.sizeof(RomanSubmapDesc)
 LC_PARAMS_NBYTES = C.sizeof(RomanLcParams)
 LC_RECORD_NBYTES = C.sizeof(RomanLcRecord)
 PARAMS_NBYTES = C.sizeof(RomanParams)
@@ -271,6 +301,8 @@ def load_library():
                                       vp, vp, i32, i32, vp, vp, vp]),
         "roman_ransac_batch_dev": (C.c_int, [ctxp, P(RomanRansacParams), i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
         "roman_ransac_batch": (C.c_int, [ctxp, P(RomanRansacParams), i32, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]),
+        "roman_submaps_dev": (C.c_int, [ctxp, P(RomanSubmapParams), i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
+        "roman_submaps": (C.c_int, [ctxp, P(RomanSubmapParams), i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
         "roman_ctx_has_history": (C.c_int, [ctxp, P(RomanParams), i32, P(i32)]),
         "roman_ctx_cosine_screen_stats": (C.c_int, [ctxp, P(C.c_int64), P(C.c_int64), P(C.c_double)]),
         "roman_create_all_to_all": (C.c_int, [i32, i32, vp]),
@@ -305,7 +337,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_submaps_dev", "roman_submaps", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

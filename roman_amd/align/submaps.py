@@ -1,0 +1,245 @@
+"""Submaps from a whole map on the device: slice, prune, pack in one call.
+
+The reference's `submap_align()` first turns each robot's map into submaps with `submaps_from_roman_map`
+[REF roman/map/map.py:244-357] — for the default radius mode a Python loop over S centres x N segments with a deepcopy per kept
+(submap, segment) — and `pack_submaps` then packs every submap's rows again.  Here the map is packed ONCE as a per-segment
+table (`MapTable`), the sequential centre scan [REF :300-309] stays on the host (`submap_centers`, S is small), and one device
+call (`build_submap_pool` -> roman_submaps_dev) produces the feature pool of all submaps in HBM, in fixed slots of `cap` rows per
+submap: exactly what roman_align_batch_dev / roman_align_batch_resident / roman_align_lc_batch_dev consume (`SubmapPool.grid_batch`).
+No segment object is copied; `SubmapPool.to_submaps` hands out light views for the host-side callers (`submap_align_grid`, the
+writers).  The force_fill_submaps mode [REF :264-295] is plain slicing of a time-sorted list and is not covered.
+
+torch is used for device memory only; nothing numerical happens here.
+"""
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+
+from .. import _abi
+from ..runtime import submap_desc_dtype
+from .batch import AlignmentBatch
+from .submap_align import Submap, transform_rm_roll_pitch
+
+
+@dataclass
+class SubmapParams:
+    """The fields of [REF roman/map/map.py:165-178] the radius mode reads."""
+    max_size: Optional[int] = 40
+    radius: Optional[float] = 15.0
+    distance: float = 10.0
+    time_threshold: float = np.inf
+    pruning_method: str = 'time'
+    submap_descriptor: Optional[str] = None
+
+    @classmethod
+    def from_submap_align_params(cls, p):
+        """[REF roman/map/map.py:180-192]"""
+        if p.force_fill_submaps:
+            raise ValueError("force_fill_submaps slices a time-sorted list on the host; the device call covers the radius mode")
+        return cls(max_size=p.submap_max_size, radius=p.submap_radius, distance=p.submap_center_dist,
+                   time_threshold=p.submap_center_time, pruning_method=p.submap_pruning_method,
+                   submap_descriptor=p.submap_descriptor)
+
+
+@dataclass
+class SubmapCenters:
+    """The S submap centres of one map, in the order the scan found them."""
+    index: np.ndarray            # (S,) trajectory index of every centre
+    time: np.ndarray             # (S,)
+    pose_flu: np.ndarray         # (S, 4, 4) COPIES of the trajectory poses with roll and pitch removed
+    T_center_odom: np.ndarray    # (S, 4, 4) inv(pose_gravity_aligned) [REF roman/map/map.py:328]
+    t_lo: np.ndarray             # (S,) previous centre's time - time_threshold (-inf for the first) [REF :315-320]
+    t_hi: np.ndarray             # (S,) next centre's time + time_threshold (+inf for the last)
+
+    def __len__(self):
+        return int(self.index.shape[0])
+
+    def descs(self):
+        """-> the roman_submap_desc_t array of the C ABI."""
+        d = np.zeros(len(self), dtype=submap_desc_dtype())
+        if len(self):
+            d["pos"] = self.pose_flu[:, :3, 3]; d["T_center_odom"] = self.T_center_odom
+            d["time"] = self.time; d["t_lo"] = self.t_lo; d["t_hi"] = self.t_hi
+        return d
+
+
+def submap_centers(trajectory, times, params) -> SubmapCenters:
+    """The sequential centre scan of [REF roman/map/map.py:300-309]: pose i opens a submap when it is the first, lies more than
+    `params.distance` from the latest centre, or is more than `params.time_threshold` later.  It fixes S.
+
+    Works on COPIES: the reference stores the trajectory's own pose matrices in its submaps and `pose_gravity_aligned` then
+    removes their roll and pitch IN PLACE, so the caller's trajectory comes back changed; here the caller's
+    trajectory is NOT flattened — `pose_flu` of the result holds flattened copies (the rotation is all that changes: the
+    radius test reads the translation only)."""
+    idx = []
+    for i, (pose, t) in enumerate(zip(trajectory, times)):
+        if i == 0 or np.linalg.norm(np.asarray(pose)[:-1, -1] - np.asarray(trajectory[idx[-1]])[:-1, -1]) > params.distance \
+                or (t - times[idx[-1]] > params.time_threshold):
+            idx.append(i)
+    S = len(idx)
+    tm = np.array([times[i] for i in idx], dtype=np.float64)
+    flat = np.array([transform_rm_roll_pitch(np.array(trajectory[i], dtype=np.float64)) for i in idx]).reshape(S, 4, 4)
+    inv = np.array([np.linalg.inv(T) for T in flat]).reshape(S, 4, 4)
+    t_lo = np.concatenate([[-np.inf], tm[:-1] - params.time_threshold])[:S]
+    t_hi = np.concatenate([tm[1:] + params.time_threshold, [np.inf]])[-S:] if S else np.zeros(0)
+    return SubmapCenters(np.array(idx, dtype=np.int64), tm, flat, inv, t_lo, t_hi)
+
+
+@dataclass
+class MapTable:
+    """A whole map as the per-segment table of the C ABI: rows in map order, odom frame."""
+    feats: np.ndarray            # (N, 3 + ratio features + descriptor) float64: [x y z | the registration's feature columns behind the point]
+    times: np.ndarray            # (N, 2) first_seen, last_seen
+    ids: np.ndarray              # (N,) int64
+    point_dim: int               # centre components an output row keeps (the registration's dim)
+    desc_dim: int                # trailing descriptor columns (0: none)
+
+    @classmethod
+    def from_segments(cls, registration, segments):
+        """Packs the map ONCE with `registration.pack` (the row layout of the batch calls), plus times and ids.  The table's point
+        is always x y z, whatever the registration's dim."""
+        packed = registration.pack(segments)
+        dim = registration.dim
+        n = len(segments)
+        cen = np.array([np.asarray(s.center, dtype=np.float64).reshape(-1)[:3] for s in segments], dtype=np.float64).reshape(n, 3)
+        feats = np.ascontiguousarray(np.hstack([cen, packed[:, dim:]]))
+        times = np.array([[s.first_seen, s.last_seen] for s in segments], dtype=np.float64).reshape(n, 2)
+        ids = np.array([s.id for s in segments], dtype=np.int64).reshape(n)
+        P = registration._abi_params()
+        d = int(P.cos_feature_dim) if P.invariant != _abi.ROMAN_INV_EUCLIDEAN else 0
+        return cls(feats, times, ids, int(dim), d)
+
+    def __len__(self):
+        return int(self.feats.shape[0])
+
+
+class SegmentView:
+    """A segment of the map as a submap holds it: every attribute of the map's segment, the centre in the submap's frame."""
+    __slots__ = ("_seg", "centroid")
+
+    def __init__(self, seg, center):
+        self._seg = seg
+        self.centroid = np.asarray(center, dtype=np.float64).reshape(-1, 1)
+
+    @property
+    def center(self):
+        return self.centroid
+
+    def __getattr__(self, name):
+        if name == "_seg":
+            raise AttributeError(name)
+        return getattr(self._seg, name)
+
+
+@dataclass
+class SubmapPool:
+    """The submaps of one map in HBM: submap s owns rows [s * cap, s * cap + count[s]) of `pool`."""
+    pool: object                 # torch tensor (S * cap, F) float64 on the device
+    cap: int
+    count: np.ndarray            # (S,) int32, host
+    src: np.ndarray              # (S, cap) int32 map index of every row (-1 beyond count), host
+    ids: np.ndarray              # (S, cap) int64, host
+    status: np.ndarray           # (S,) int32 ROMAN_ST_OK / ROMAN_ST_ASSOC_TRUNCATED
+    desc: Optional[np.ndarray]   # (S, d) mean_semantic descriptors (NaN rows for empty submaps) or None
+    centers: SubmapCenters
+    table: MapTable
+
+    @property
+    def nonempty(self):
+        """Indices of the submaps that hold a segment (the reference drops the others, [REF roman/map/map.py:341])."""
+        return np.nonzero(self.count > 0)[0]
+
+    def offsets(self):
+        """(first row, rows) of every non-empty submap."""
+        k = self.nonempty
+        return k.astype(np.int64) * self.cap, self.count[k].astype(np.int32)
+
+    def grid_batch(self, other, mask=None):
+        """The S0 x S1 problems (row-major over the NON-EMPTY submaps of either pool; mask[i, j] False leaves a pair out) over the
+        two pools concatenated on the device -> (AlignmentBatch, pool tensor).  The batch carries offsets, counts, pair indices
+        and the ids of every pool row; its `feats` is a shape-only placeholder (the rows live on the device), which is what
+        pipeline.align_resident(registration, batch, pool) and Context.align_lc_batch_dev(params, pool.data_ptr(), F, batch.off1,
+        ...) need.  `other is self` (self loop closures): one pool, no copy."""
+        import torch
+        same = other is self
+        if not same and int(other.pool.shape[1]) != int(self.pool.shape[1]):
+            raise ValueError("the two pools have different row widths")
+        pool = self.pool if same else torch.cat([self.pool, other.pool], dim=0)
+        base1 = 0 if same else int(self.pool.shape[0])
+        o0, c0 = self.offsets(); o1, c1 = other.offsets()
+        ii, jj = np.meshgrid(np.arange(len(o0)), np.arange(len(o1)), indexing='ij')
+        ii, jj = ii.ravel(), jj.ravel()
+        if mask is not None:
+            keep = np.asarray(mask, dtype=bool).ravel()
+            ii, jj = ii[keep], jj[keep]
+        ids = self.ids.reshape(-1) if same else np.concatenate([self.ids.reshape(-1), other.ids.reshape(-1)])
+        feats = np.broadcast_to(np.float64(0.0), tuple(int(x) for x in pool.shape))
+        batch = AlignmentBatch(feats, o0[ii], c0[ii], o1[jj] + base1, c1[jj], pair_index=np.stack([ii, jj], axis=1), ids=ids)
+        return batch, pool
+
+    def to_submaps(self, segments) -> List[Submap]:
+        """Light `Submap` objects of the non-empty submaps for the host-side callers (the unchanged submap_align_grid, the
+        writers): segment views in output order with the transformed centre, plus id (the centre's number, as the reference
+        numbers them before it drops the empty ones), time, pose_flu and descriptor.  No segment is copied."""
+        cen = self.pool[:, :self.table.point_dim].cpu().numpy()
+        out = []
+        for s in self.nonempty:
+            rows = self.src[s, :self.count[s]]
+            c = cen[s * self.cap: s * self.cap + self.count[s]]
+            if self.table.point_dim < 3:                                     # the row keeps x y only: z on the host, same operation order
+                T = self.centers.T_center_odom[s]; p = self.table.feats[rows, :3]
+                z = ((T[2, 0] * p[:, 0] + T[2, 1] * p[:, 1]) + T[2, 2] * p[:, 2]) + T[2, 3]
+                c = np.hstack([c, z[:, None]])
+            segs = [SegmentView(segments[k], c[r]) for r, k in enumerate(rows)]
+            out.append(Submap(id=int(s), time=float(self.centers.time[s]), segments=segs, pose_flu=self.centers.pose_flu[s].copy(),
+                              descriptor=None if self.desc is None else self.desc[s].copy()))
+        return out
+
+
+def submap_call_params(table: MapTable, params: SubmapParams, cap=None) -> _abi.RomanSubmapParams:
+    """SubmapParams -> roman_submap_params_t.  `cap`: rows per slot when max_size is None (default: the whole map)."""
+    P = _abi.RomanSubmapParams()
+    P.point_dim = table.point_dim
+    P.max_size = int(params.max_size) if params.max_size is not None else 0
+    if params.max_size is not None and int(params.max_size) < 1:
+        raise ValueError("max_size must be None or >= 1")
+    P.cap = P.max_size if P.max_size > 0 else int(cap if cap is not None else max(len(table), 1))
+    P.prune_by_time = int(params.pruning_method == 'time')                   # [REF roman/map/map.py:333-336]: anything else prunes by distance
+    P.use_radius = int(params.radius is not None)
+    P.radius = float(params.radius) if params.radius is not None else 0.0
+    return P
+
+
+def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, params: SubmapParams, ctx=None, device=None, cap=None) -> SubmapPool:
+    """The submaps of `table` around `centers` as a device-resident feature pool: ONE roman_submaps_dev call (membership, prune,
+    order, transform, gather, mean_semantic descriptors), then one synchronisation that brings count, src, ids, status and the
+    descriptors to the host.  The table is uploaded here (once per call); the pool never leaves the device."""
+    import torch
+    ctx = ctx or registration._context()
+    dev = torch.device(device if device is not None else f"cuda:{getattr(ctx, 'device', 0)}")
+    on_host = dev.type == "cpu"                                              # CPU tensors + a stand-in context (tests)
+    P = submap_call_params(table, params, cap)
+    S, N, F = len(centers), len(table), int(table.feats.shape[1])
+    d = 0
+    if params.submap_descriptor == 'mean_semantic':
+        if table.desc_dim <= 0:
+            raise ValueError("submap_descriptor 'mean_semantic' needs a registration with semantic descriptors")
+        d = table.desc_dim
+    elif params.submap_descriptor is not None:
+        raise ValueError("frame descriptors (mean_frame_descriptor / stacked_frame_descriptors) are extracted on the host")
+    Fo, rows = P.point_dim + F - 3, S * P.cap
+    feats = torch.from_numpy(table.feats).to(dev); times = torch.from_numpy(table.times).to(dev); ids = torch.from_numpy(table.ids).to(dev)
+    pool = torch.zeros((rows, Fo), dtype=torch.float64, device=dev)
+    count = torch.zeros(max(S, 1), dtype=torch.int32, device=dev); status = torch.zeros(max(S, 1), dtype=torch.int32, device=dev)
+    src = torch.full((max(rows, 1),), -1, dtype=torch.int32, device=dev); ids_out = torch.full((max(rows, 1),), -1, dtype=torch.int64, device=dev)
+    desc = torch.full((max(S, 1), max(d, 1)), float("nan"), dtype=torch.float64, device=dev)
+    if not on_host:
+        torch.cuda.current_stream(dev).synchronize()                         # inputs and cleared outputs are in place before the library's stream touches them
+    ctx.submaps_dev(P, N, F, feats.data_ptr(), times.data_ptr(), centers.descs(), pool.data_ptr(), count.data_ptr(), src.data_ptr(),
+                    status.data_ptr(), seg_ids_ptr=ids.data_ptr(), ids_out_ptr=ids_out.data_ptr(), desc_dim=d,
+                    desc_out_ptr=desc.data_ptr() if d else None)
+    ctx.sync()
+    return SubmapPool(pool, int(P.cap), count.cpu().numpy()[:S].copy(), src.cpu().numpy()[:rows].reshape(S, P.cap).copy(),
+                      ids_out.cpu().numpy()[:rows].reshape(S, P.cap).copy(), status.cpu().numpy()[:S].copy(),
+                      desc.cpu().numpy()[:S, :d].copy() if d else None, centers, table)

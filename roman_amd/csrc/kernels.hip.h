@@ -7162,6 +7162,158 @@ __global__ void __launch_bounds__(256) k_shared_gather(int F, const GatherJob* _
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// submaps from a whole map, radius mode ([REF roman/map/map.py:297-339]): which segments of the map belong to
+// each submap, in which order, and their feature rows in the submap's gravity-aligned frame — the feature pool the batch
+// calls consume, in fixed slots of `cap` rows per submap.
+//   k_submap_points   the N centres out of the N x F segment table into a dense N x 3 array: every submap's sweep then reads
+//                     centres (and the N x 2 times) coalesced instead of one 24-byte piece per F-double row;
+//   k_submap_select   one workgroup per submap sweeps the N segments: the radius and the time-window test, the survivors
+//                     compacted in map order into a candidate list of (key, map index) with a ballot plus the counts of the
+//                     waves in front (k_shared_mark's idiom: no atomics).  The first SUBMAP_LDS_CAND candidates live in LDS
+//                     (48 KB), the others in the submap's slice of a global scratch the context owns: none is dropped.  With
+//                     max_size set, a candidate's output position is its rank under (key, map index) — Python's stable
+//                     sorted() over the list in map order [REF :332-339] — counted with uniform (broadcast) reads of the list;
+//                     ranks are a permutation, so order needs no atomics either.  A NaN key sorts as +inf;
+//   k_submap_gather   a wave per selected row: the centre through T_center_odom, each component ((r0 x + r1 y) + r2 z) + t,
+//                     the other columns bit for bit as 64-bit words — 16 bytes per lane where source and destination of the
+//                     row's tail share their 16-byte phase (one leading word peeled when both are odd), 8 otherwise;
+//   k_submap_desc     mean_semantic [REF :343-346]: a thread per descriptor column adds the rows in output order.
+// ---------------------------------------------------------------------------------------------
+constexpr int SUBMAP_NT = 256;
+constexpr int SUBMAP_LDS_CAND = 4096;                            // candidates of a submap held in LDS (8 + 4 bytes each)
+
+__global__ void __launch_bounds__(256) k_submap_points(int N, int F, const double* __restrict__ feats, double* __restrict__ pts)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const double* r = feats + i * (int64_t)F;
+    pts[3 * i] = r[0]; pts[3 * i + 1] = r[1]; pts[3 * i + 2] = r[2];
+}
+
+__global__ void __launch_bounds__(SUBMAP_NT) k_submap_select(roman_submap_params_t P, int S, int N, const roman_submap_desc_t* __restrict__ descs,
+                                                             const double* __restrict__ pts, const double* __restrict__ times,
+                                                             double* spillKey, int32_t* spillIdx, int64_t spillStride,
+                                                             int32_t* __restrict__ count, int32_t* __restrict__ src, int32_t* __restrict__ status)
+{
+    __shared__ double keyL[SUBMAP_LDS_CAND];
+    __shared__ int32_t idxL[SUBMAP_LDS_CAND];
+    __shared__ int wcnt[SUBMAP_NT / 64];
+    const int s = blockIdx.x;
+    if (s >= S) return;
+    const roman_submap_desc_t D = descs[s];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    double* const gKey = spillKey + (int64_t)s * spillStride;      // candidates SUBMAP_LDS_CAND, SUBMAP_LDS_CAND + 1, ... of this submap
+    int32_t* const gIdx = spillIdx + (int64_t)s * spillStride;
+    const bool ordered = P.max_size > 0;
+    int base = 0;
+    for (int i0 = 0; i0 < N; i0 += SUBMAP_NT) {                   // (uniform bounds: every barrier below is met by the whole workgroup)
+        const int i = i0 + tid;
+        bool member = i < N;
+        double key = 0.0;
+        if (member) {
+            const double x = pts[3 * (int64_t)i], y = pts[3 * (int64_t)i + 1], z = pts[3 * (int64_t)i + 2];
+            const double first = times[2 * (int64_t)i], last = times[2 * (int64_t)i + 1];
+            if (P.use_radius) {
+                const double dx = x - D.pos[0], dy = y - D.pos[1], dz = z - D.pos[2];
+                member = sqrt((dx * dx + dy * dy) + dz * dz) < P.radius;
+            }
+            member = member && !(first > D.t_hi || last < D.t_lo);
+            if (member && ordered) {
+                if (P.prune_by_time) key = fabs((first + last) / 2.0 - D.time);
+                else {
+                    const double* T = D.T_center_odom;
+                    const double cx = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+                    const double cy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+                    const double cz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+                    key = sqrt((cx * cx + cy * cy) + cz * cz);
+                }
+                if (!(key == key)) key = INFINITY;
+            }
+        }
+        const unsigned long long m = __ballot(member);
+        __syncthreads();                                         // the counts of the previous chunk have been read
+        if (lane == 0) wcnt[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < SUBMAP_NT / 64; ++w) { const int cw = wcnt[w]; before += (w < wave) ? cw : 0; total += cw; }
+        if (member) {
+            const int p = base + before + __popcll(m & lt);
+            if (p < SUBMAP_LDS_CAND) { keyL[p] = key; idxL[p] = i; }
+            else { gKey[p - SUBMAP_LDS_CAND] = key; gIdx[p - SUBMAP_LDS_CAND] = i; }
+        }
+        base += total;
+    }
+    __syncthreads();                                             // the list is complete (LDS and, at workgroup scope, the spill)
+    const int n = base, outN = min(n, P.cap), nL = min(n, SUBMAP_LDS_CAND);
+    if (tid == 0) { count[s] = outN; status[s] = (!ordered && n > P.cap) ? ROMAN_ST_ASSOC_TRUNCATED : ROMAN_ST_OK; }
+    int32_t* const out = src + (int64_t)s * P.cap;
+    if (!ordered) {                                              // map order: the list as it stands
+        for (int i = tid; i < outN; i += SUBMAP_NT) out[i] = i < SUBMAP_LDS_CAND ? idxL[i] : gIdx[i - SUBMAP_LDS_CAND];
+        return;
+    }
+    for (int i = tid; i < n; i += SUBMAP_NT) {
+        const double ki = i < SUBMAP_LDS_CAND ? keyL[i] : gKey[i - SUBMAP_LDS_CAND];
+        const int32_t ii = i < SUBMAP_LDS_CAND ? idxL[i] : gIdx[i - SUBMAP_LDS_CAND];
+        int r = 0;
+#pragma unroll 4
+        for (int j = 0; j < nL; ++j) { const double kj = keyL[j]; r += (kj < ki || (kj == ki && idxL[j] < ii)) ? 1 : 0; }
+        for (int j = SUBMAP_LDS_CAND; j < n; ++j) { const double kj = gKey[j - SUBMAP_LDS_CAND]; r += (kj < ki || (kj == ki && gIdx[j - SUBMAP_LDS_CAND] < ii)) ? 1 : 0; }
+        if (r < outN) out[r] = ii;
+    }
+}
+
+// grid (submaps, row groups); a wave per selected row
+__global__ void __launch_bounds__(256) k_submap_gather(int point_dim, int cap, int F, const roman_submap_desc_t* __restrict__ descs,
+                                                       const unsigned long long* __restrict__ feats, const int64_t* __restrict__ ids,
+                                                       const int32_t* __restrict__ count, const int32_t* __restrict__ src,
+                                                       unsigned long long* __restrict__ pool, int64_t* __restrict__ ids_out)
+{
+    const int s = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = count[s], Fo = point_dim + F - 3, rest = F - 3;
+    for (int r = blockIdx.y * 4 + wave; r < n; r += 4 * gridDim.y) {
+        const int64_t row = (int64_t)s * cap + r;
+        const int k = src[row];
+        const unsigned long long* in = feats + (int64_t)k * F;
+        unsigned long long* out = pool + row * Fo;
+        if (lane == 0) {
+            const double* T = descs[s].T_center_odom;
+            const double x = __longlong_as_double((long long)in[0]), y = __longlong_as_double((long long)in[1]), z = __longlong_as_double((long long)in[2]);
+            for (int c = 0; c < point_dim; ++c)
+                out[c] = (unsigned long long)__double_as_longlong(((T[4 * c] * x + T[4 * c + 1] * y) + T[4 * c + 2] * z) + T[4 * c + 3]);
+            if (ids_out) ids_out[row] = ids[k];
+        }
+        const unsigned long long* a = in + 3;
+        unsigned long long* b = out + point_dim;
+        const unsigned oa = (unsigned)(((uintptr_t)a >> 3) & 1u), ob = (unsigned)(((uintptr_t)b >> 3) & 1u);
+        if (oa == ob) {                                          // one 16-byte phase: a leading word when odd, pairs, a trailing word
+            const int head = min((int)oa, rest), pairs = (rest - head) >> 1;
+            if (lane == 0 && head) b[0] = a[0];
+            const ulonglong2* a2 = reinterpret_cast<const ulonglong2*>(a + head);
+            ulonglong2* b2 = reinterpret_cast<ulonglong2*>(b + head);
+            for (int q = lane; q < pairs; q += 64) b2[q] = a2[q];
+            if (lane == 63 && head + 2 * pairs < rest) b[rest - 1] = a[rest - 1];
+        } else {
+            for (int q = lane; q < rest; q += 64) b[q] = a[q];
+        }
+    }
+}
+
+// grid (submaps, column groups): desc_out[s][c] = (sum over the rows of submap s, in output order, of descriptor column c) / count
+__global__ void __launch_bounds__(256) k_submap_desc(int cap, int F, int d, const double* __restrict__ feats, const int32_t* __restrict__ count,
+                                                     const int32_t* __restrict__ src, double* __restrict__ desc_out)
+{
+    const int s = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
+    const int n = count[s];
+    if (c >= d || n == 0) return;                                // an empty submap's descriptor is left as it was
+    const int32_t* rows = src + (int64_t)s * cap;
+    double acc = 0.0;
+    for (int r = 0; r < n; ++r) acc += feats[(int64_t)rows[r] * F + (F - d) + c];
+    desc_out[(int64_t)s * d + c] = acc / (double)n;
+}
 
 // elementwise math probe for tests
 __global__ void k_debug_math(int kind, const double* __restrict__ a, const double* __restrict__ b,

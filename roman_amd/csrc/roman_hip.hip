@@ -170,6 +170,11 @@ struct roman_ctx {
     DevBuf ransacDesc, ransacHost;
     PinnedStage<RansacDesc> ransacStage;
 
+    // submaps from a whole map (roman_submaps*): the submap descriptors through pinned staging (a pure enqueue), the dense centres of
+    // the map, the per-submap spill of candidate lists beyond SUBMAP_LDS_CAND, and the host-pointer call's arrays on the device
+    DevBuf smDesc, smPts, smSpillKey, smSpillIdx, smHost;
+    PinnedStage<roman_submap_desc_t> smStage;
+
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
     bool profile = false;
@@ -1431,6 +1436,8 @@ int roman_ctx_destroy(roman_ctx_t* c)
     { DevBuf* share[] = {&c->shareDesc, &c->shareIds, &c->shareKeep, &c->shareKept, &c->shareJobs}; for (DevBuf* b : share) b->release(); }
     c->ransacDesc.release(); c->ransacHost.release();
     c->shareStage.release(); c->ransacStage.release();
+    { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx, &c->smHost}; for (DevBuf* b : sm) b->release(); }
+    c->smStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -2466,6 +2473,109 @@ int roman_ransac_batch(roman_ctx_t* c, const roman_ransac_params_t* rparams, int
     HIPCHK(c, hipMemcpyAsync(rec_out, dRec, sizeof(roman_ransac_record_t) * (size_t)B, hipMemcpyDeviceToHost, WS.stream));
     if (rowsPer) HIPCHK(c, hipMemcpyAsync(assoc_out, dAssoc, sizeof(int32_t) * (size_t)B * rowsPer, hipMemcpyDeviceToHost, WS.stream));
     if (nCounts) HIPCHK(c, hipMemcpyAsync(counts_out, dCnt, sizeof(int32_t) * nCounts, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipStreamSynchronize(WS.stream));
+    return ROMAN_OK;
+}
+
+// --- submaps from a whole map, radius mode ([REF roman/map/map.py:297-346]) ---------------------------------------
+static int submaps_check(roman_ctx* c, const roman_submap_params_t* P, int32_t N, int32_t F, const void* seg_feats, const void* seg_times, const void* seg_ids,
+                         int32_t S, const void* descs, const void* pool, const void* count, const void* src, const void* ids_out, const void* status,
+                         int32_t desc_dim, const void* desc_out, bool pool_needed)
+{
+    if (!P) return fail(c, ROMAN_E_INVALID, "sparams is NULL");
+    if (P->point_dim != 2 && P->point_dim != 3) return fail(c, ROMAN_E_INVALID, "point_dim must be 2 or 3 (got %d)", P->point_dim);
+    if (N < 0 || S < 0) return fail(c, ROMAN_E_INVALID, "N < 0 or S < 0");
+    if (F < 3) return fail(c, ROMAN_E_INVALID, "F=%d: a segment row starts with x y z", F);
+    if (P->cap < 1) return fail(c, ROMAN_E_INVALID, "cap must be >= 1 (got %d)", P->cap);
+    if (P->max_size > 0 && P->cap != P->max_size) return fail(c, ROMAN_E_INVALID, "cap (%d) must equal max_size (%d) when max_size is set", P->cap, P->max_size);
+    if (P->reserved0 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0) return fail(c, ROMAN_E_INVALID, "roman_submap_params_t reserved words must be 0");
+    if (P->use_radius && P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
+    if (desc_dim < 0 || desc_dim > F - 3) return fail(c, ROMAN_E_INVALID, "desc_dim=%d outside [0, F - 3]", desc_dim);
+    if (desc_out && desc_dim == 0) return fail(c, ROMAN_E_INVALID, "desc_out given with desc_dim 0");
+    if (ids_out && !seg_ids) return fail(c, ROMAN_E_INVALID, "ids_out given without seg_ids");
+    if (S == 0) return ROMAN_OK;
+    if (!descs || !count || !src || !status || (pool_needed && !pool)) return fail(c, ROMAN_E_INVALID, "NULL descriptor or output pointer");
+    if (N > 0 && (!seg_feats || !seg_times)) return fail(c, ROMAN_E_INVALID, "seg_feats / seg_times is NULL");
+    return ROMAN_OK;
+}
+
+int roman_submaps_dev(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t N, int32_t F,
+                      const double* seg_feats, const double* seg_times, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
+                      double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = submaps_check(c, sparams, N, F, seg_feats, seg_times, seg_ids, S, descs, pool, count, src, ids_out, status, desc_dim, desc_out, true);
+    if (rc || S == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    // scratch first: a failure leaves nothing enqueued
+    const int64_t spill = std::max<int64_t>((int64_t)N - SUBMAP_LDS_CAND, 0);
+    HIPCHK(c, c->smSpillKey.ensure(sizeof(double) * (size_t)std::max<int64_t>(spill * S, 1)));
+    HIPCHK(c, c->smSpillIdx.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(spill * S, 1)));
+    HIPCHK(c, c->smPts.ensure(sizeof(double) * 3 * (size_t)std::max(N, 1)));
+    roman_submap_desc_t* staged = nullptr;
+    HIPCHK(c, c->smStage.stage((size_t)S, &staged));
+    memcpy(staged, descs, sizeof(roman_submap_desc_t) * (size_t)S);
+    HIPCHK(c, c->smStage.upload(c->smDesc, (size_t)S, stream));
+    const roman_submap_desc_t* dDesc = c->smDesc.as<roman_submap_desc_t>();
+    if (N > 0) hipLaunchKernelGGL(k_submap_points, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (int)N, (int)F, seg_feats, c->smPts.as<double>());
+    hipLaunchKernelGGL(k_submap_select, dim3((unsigned)S), dim3(SUBMAP_NT), 0, stream, *sparams, (int)S, (int)N, dDesc, c->smPts.as<double>(), seg_times,
+                       c->smSpillKey.as<double>(), c->smSpillIdx.as<int32_t>(), spill, count, src, status);
+    HIPCHK(c, hipGetLastError());
+    if (N > 0) {
+        // a wave per row, four rows per workgroup and pass: enough row groups for the largest slot, at most 64 per submap
+        const unsigned groups = (unsigned)std::min(64, (std::min(sparams->cap, N) + 3) / 4);
+        hipLaunchKernelGGL(k_submap_gather, dim3((unsigned)S, groups), dim3(256), 0, stream, (int)sparams->point_dim, (int)sparams->cap, (int)F, dDesc,
+                           reinterpret_cast<const unsigned long long*>(seg_feats), seg_ids, count, src, reinterpret_cast<unsigned long long*>(pool), ids_out);
+        if (desc_out) hipLaunchKernelGGL(k_submap_desc, dim3((unsigned)S, (unsigned)((desc_dim + 255) / 256)), dim3(256), 0, stream, (int)sparams->cap, (int)F, (int)desc_dim,
+                                         seg_feats, count, src, desc_out);
+        HIPCHK(c, hipGetLastError());
+    }
+    return ROMAN_OK;
+}
+
+int roman_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t N, int32_t F,
+                  const double* seg_feats, const double* seg_times, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
+                  double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = submaps_check(c, sparams, N, F, seg_feats, seg_times, seg_ids, S, descs, pool, count, src, ids_out, status, desc_dim, desc_out, false);
+    if (rc || S == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    c->last.scored = false; c->last.solved = false;            // workspace 0's feature staging is reused: the stepwise problem it held is gone
+    const double* dFeats = nullptr;
+    rc = upload_inputs(c, seg_feats, N, F, 0, nullptr, 0, &dFeats);
+    if (rc) return rc;
+    // the other arrays on the device, 8-byte blocks first: times | ids | pool | ids_out | desc_out | src | count | status
+    const size_t rows = (size_t)S * (size_t)sparams->cap, Fo = (size_t)(sparams->point_dim + F - 3);
+    const size_t bTimes = sizeof(double) * 2 * (size_t)N, bIds = seg_ids ? sizeof(int64_t) * (size_t)N : 0, bPool = sizeof(double) * rows * Fo,
+                 bIdsOut = ids_out ? sizeof(int64_t) * rows : 0, bDesc = desc_out ? sizeof(double) * (size_t)S * (size_t)desc_dim : 0,
+                 bSrc = sizeof(int32_t) * rows, bCnt = sizeof(int32_t) * (size_t)S;
+    const size_t oTimes = 0, oIds = oTimes + bTimes, oPool = oIds + bIds, oIdsOut = oPool + bPool, oDesc = oIdsOut + bIdsOut, oSrc = oDesc + bDesc,
+                 oCnt = oSrc + bSrc, oSt = oCnt + bCnt, total = oSt + bCnt;
+    HIPCHK(c, c->smHost.ensure(std::max<size_t>(total, 8)));
+    char* const dev = c->smHost.as<char>();
+    double* dPool = reinterpret_cast<double*>(dev + oPool);
+    int64_t* dIdsOut = ids_out ? reinterpret_cast<int64_t*>(dev + oIdsOut) : nullptr;
+    double* dDescOut = desc_out ? reinterpret_cast<double*>(dev + oDesc) : nullptr;
+    int32_t* dSrc = reinterpret_cast<int32_t*>(dev + oSrc);
+    if (bTimes) HIPCHK(c, hipMemcpyAsync(dev + oTimes, seg_times, bTimes, hipMemcpyHostToDevice, WS.stream));
+    if (bIds) HIPCHK(c, hipMemcpyAsync(dev + oIds, seg_ids, bIds, hipMemcpyHostToDevice, WS.stream));
+    // the caller's outputs go up first: what the device call leaves untouched comes back as it was
+    if (pool && bPool) HIPCHK(c, hipMemcpyAsync(dPool, pool, bPool, hipMemcpyHostToDevice, WS.stream));
+    if (bIdsOut) HIPCHK(c, hipMemcpyAsync(dIdsOut, ids_out, bIdsOut, hipMemcpyHostToDevice, WS.stream));
+    if (bDesc) HIPCHK(c, hipMemcpyAsync(dDescOut, desc_out, bDesc, hipMemcpyHostToDevice, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(dSrc, src, bSrc, hipMemcpyHostToDevice, WS.stream));
+    rc = roman_submaps_dev(c, sparams, N, F, dFeats, reinterpret_cast<const double*>(dev + oTimes), seg_ids ? reinterpret_cast<const int64_t*>(dev + oIds) : nullptr,
+                           S, descs, dPool, reinterpret_cast<int32_t*>(dev + oCnt), dSrc, dIdsOut, reinterpret_cast<int32_t*>(dev + oSt), desc_dim, dDescOut);
+    if (rc) return rc;
+    if (pool && bPool) HIPCHK(c, hipMemcpyAsync(pool, dPool, bPool, hipMemcpyDeviceToHost, WS.stream));
+    if (bIdsOut) HIPCHK(c, hipMemcpyAsync(ids_out, dIdsOut, bIdsOut, hipMemcpyDeviceToHost, WS.stream));
+    if (bDesc) HIPCHK(c, hipMemcpyAsync(desc_out, dDescOut, bDesc, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(src, dSrc, bSrc, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(count, dev + oCnt, bCnt, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(status, dev + oSt, bCnt, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipStreamSynchronize(WS.stream));
     return ROMAN_OK;
 }

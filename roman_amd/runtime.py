@@ -115,6 +115,23 @@ class RansacResult:
     counts: Optional[np.ndarray] = None   # (B, max_iteration) int32 when asked for: inlier count per processed hypothesis, -1 = pruned
 
 
+def submap_desc_dtype():
+    """roman_submap_desc_t as a structured dtype."""
+    return np.dtype([("pos", np.float64, (3,)), ("T_center_odom", np.float64, (4, 4)), ("time", np.float64),
+                     ("t_hi", np.float64), ("t_lo", np.float64)])
+
+
+@dataclass
+class SubmapsResult:
+    """Results of one roman_submaps call: fixed slots of `cap` rows per submap, submap s owns rows [s * cap, s * cap + count[s])."""
+    pool: Optional[np.ndarray]     # (S * cap, point_dim + F - 3) float64, or None when not asked for
+    count: np.ndarray              # (S,) int32
+    src: np.ndarray                # (S * cap,) int32 map index of every row
+    ids: Optional[np.ndarray]      # (S * cap,) int64, or None without seg_ids
+    status: np.ndarray             # (S,) int32: ROMAN_ST_OK / ROMAN_ST_ASSOC_TRUNCATED
+    desc: Optional[np.ndarray]     # (S, desc_dim) float64 mean_semantic descriptors, or None
+
+
 @dataclass
 class LoopClosureResult(BatchResult):
     """A batch result with the loop-closure tail behind it."""
@@ -387,6 +404,60 @@ class Context:
         rc = self._lib.roman_ransac_batch_dev(self._h, C.byref(rparams), int(n1.shape[0]), vp(pts_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
                                               int(kmax), vp(assoc_out_ptr), vp(rec_out_ptr), vp(counts_out_ptr))
         self._check(rc, "roman_ransac_batch_dev")
+
+    # ------------------------------------------------------------------ submaps from a whole map
+    @staticmethod
+    def _submap_descs(descs):
+        descs = np.ascontiguousarray(descs, dtype=submap_desc_dtype()).reshape(-1)
+        assert descs.dtype.itemsize == _abi.SUBMAP_DESC_NBYTES
+        return descs
+
+    def submaps(self, sparams, seg_feats, seg_times, descs, seg_ids=None, desc_dim=0, want_pool=True,
+                pool=None, src=None, ids_out=None, desc_out=None):
+        """Host-pointer submap extraction (roman_submaps): the radius mode of submaps_from_roman_map [REF roman/map/map.py:297-346]
+        for the S centres in `descs` (a submap_desc_dtype array) over the map table seg_feats (N, F) / seg_times (N, 2) /
+        seg_ids (N,).  sparams: a RomanSubmapParams.  Output arrays may be handed in (C-contiguous, the C ABI's shapes and
+        types): what the call leaves untouched comes back as it was; fresh ones are filled with 0 (pool), -1 (src, ids) and
+        NaN (descriptors).  -> SubmapsResult."""
+        seg_feats = _f64(seg_feats); seg_times = _f64(seg_times)
+        if seg_feats.ndim != 2 or seg_times.shape != (seg_feats.shape[0], 2):
+            raise ValueError("seg_feats must be (N, F) and seg_times (N, 2)")
+        N, F = seg_feats.shape
+        if seg_ids is not None:
+            seg_ids = np.ascontiguousarray(seg_ids, dtype=np.int64).reshape(-1)
+            if seg_ids.shape[0] != N:
+                raise ValueError("seg_ids must hold one entry per segment")
+        descs = self._submap_descs(descs)
+        S, rows, Fo = int(descs.shape[0]), int(descs.shape[0]) * max(int(sparams.cap), 0), int(sparams.point_dim) + F - 3
+        d = int(desc_dim)
+
+        def given(a, shape, dtype, fill):
+            if a is None:
+                return np.full(shape, fill, dtype=dtype)
+            if a.dtype != dtype or not a.flags.c_contiguous or a.shape != shape:
+                raise ValueError(f"an output array must be C-contiguous {np.dtype(dtype).name} of shape {shape}")
+            return a
+        pool = given(pool, (rows, max(Fo, 0)), np.float64, 0.0) if (want_pool or pool is not None) else None
+        src = given(src, (rows,), np.int32, -1)
+        ids_out = given(ids_out, (rows,), np.int64, -1) if seg_ids is not None else None
+        desc_out = given(desc_out, (S, d), np.float64, np.nan) if d > 0 else None
+        count = np.zeros(S, dtype=np.int32); status = np.zeros(S, dtype=np.int32)
+        self._generation += 1
+        rc = self._lib.roman_submaps(self._h, C.byref(sparams), N, F, _ptr(seg_feats), _ptr(seg_times), _ptr(seg_ids), S, _ptr(descs),
+                                     _ptr(pool), _ptr(count), _ptr(src), _ptr(ids_out), _ptr(status), d, _ptr(desc_out))
+        self._check(rc, "roman_submaps")
+        return SubmapsResult(pool, count, src, ids_out, status, desc_out)
+
+    def submaps_dev(self, sparams, N, F, seg_feats_ptr, seg_times_ptr, descs, pool_ptr, count_ptr, src_ptr, status_ptr,
+                    seg_ids_ptr=None, ids_out_ptr=None, desc_dim=0, desc_out_ptr=None):
+        """Device-pointer submap extraction (roman_submaps_dev): bulk pointers are device addresses (integers), `descs` a host
+        submap_desc_dtype array.  A pure enqueue on the context's stream; complete after sync()."""
+        descs = self._submap_descs(descs)
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_submaps_dev(self._h, C.byref(sparams), int(N), int(F), vp(seg_feats_ptr), vp(seg_times_ptr), vp(seg_ids_ptr),
+                                         int(descs.shape[0]), _ptr(descs), vp(pool_ptr), vp(count_ptr), vp(src_ptr), vp(ids_out_ptr),
+                                         vp(status_ptr), int(desc_dim), vp(desc_out_ptr))
+        self._check(rc, "roman_submaps_dev")
 
     # ------------------------------------------------------------------ loop closures
     def align_lc_batch(self, params, feats, off1, n1, off2, n2, lc, assoc=None, assoc_off=None, u0=None, kmax=None):

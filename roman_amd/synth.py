@@ -273,3 +273,39 @@ def map_segments_of(submap_segment_lists):
                 sg.points = c + 0.1 * np.array([[1, 0, 0], [0, 1, 0], [0, 0, 1], [-1, -1, -1.0]])
             out.append(sg)
     return out
+
+
+# --------------------------------------------------------------------------------------------------
+# a whole map: segments in the odom frame with sighting times along a looping trajectory, for the
+# submap extraction [REF roman/map/map.py:297-346]
+# --------------------------------------------------------------------------------------------------
+def make_map(n_segments=300, d=16, seed=8100, n_poses=400, loop_radius=25.0, laps=1.3, dt=1.0, spread=12.0):
+    """-> (segments, trajectory, times): `n_segments` SyntheticSegments scattered around a circular trajectory that is driven
+    `laps` times (so that submaps of the second lap overlap those of the first), each with first_seen / last_seen around the
+    time the trajectory passes it and id 1000 + its map index; `trajectory` a list of 4x4 poses (yaw along the path, a small
+    roll and pitch), `times` their time stamps."""
+    rng = np.random.default_rng(seed)
+    ang = np.linspace(0.0, 2.0 * np.pi * laps, n_poses)
+    times = np.arange(n_poses, dtype=np.float64) * dt
+    trajectory = []
+    for a in ang:
+        T = yaw_transform(a + np.pi / 2, [loop_radius * np.cos(a), loop_radius * np.sin(a), 0.2 * np.sin(3 * a)],
+                          roll=0.04 * np.sin(5 * a), pitch=0.03 * np.cos(7 * a))
+        trajectory.append(T)
+    protos = None
+    if d > 0:
+        protos = rng.standard_normal((20, d))
+        protos /= np.linalg.norm(protos, axis=1, keepdims=True)
+    segments = []
+    for k in range(n_segments):
+        j = int(rng.integers(0, n_poses))
+        c = trajectory[j][:3, 3] + np.array([rng.uniform(-spread, spread), rng.uniform(-spread, spread), rng.uniform(-1.0, 2.0)])
+        dsc = None
+        if d > 0:
+            v = protos[int(rng.integers(0, 20))] + 0.35 * rng.standard_normal(d) / np.sqrt(d)
+            dsc = v / np.linalg.norm(v)
+        vol, lin, pla, sca, ext = _shape_attrs(rng)
+        sg = SyntheticSegment(1000 + k, c, vol, lin, pla, sca, ext, dsc)
+        sg.first_seen = float(times[j] - rng.uniform(0.0, 8.0)); sg.last_seen = float(times[j] + rng.uniform(0.0, 8.0))
+        segments.append(sg)
+    return segments, trajectory, times
