@@ -725,6 +725,77 @@ ROMAN_API int roman_submaps(roman_ctx_t* ctx, const roman_submap_params_t* spara
                             int32_t desc_dim, double* desc_out);
 
 /* ------------------------------------------------------------------------------------------- */
+/* pass 1 of the pair loop over a whole grid of submaps (radius mode)                          */
+/* ------------------------------------------------------------------------------------------- */
+
+/* What the reference decides about a pair of submaps before it registers them ([REF roman/align/submap_align.py:93-149]), for
+   every pair (i, j) of an S0 x S1 grid at once, on the device: the distance between the centres and the radius gate, the
+   reference transform T_ij and its yaw, the cosine of the two submap descriptors [REF roman/map/map.py:144-153], skip_distance
+   [REF :136] and the descriptor threshold [REF :144-149] — and the pairs that go on to register(), compacted in the order of
+   the reference's loop with what the loop-closure tail needs for each (roman_lc_tail_dev's T_ref and enable).  Radius mode,
+   vector (1-D) descriptors or none; the AABB mode (force_fill_submaps / no radius), stacked frame descriptors and the
+   shared-segment removal of single_robot_lc stay with the caller.  DESIGN.md §4.9 is the contract.  Bits of flags[]: */
+#define ROMAN_GRID_NEARBY  1   /* dist < 2 * radius (strict): robots_nearby_mat holds dist, submap_yaw_diff_mat the yaw [REF :101-103, :127-129] */
+#define ROMAN_GRID_SKIP    2   /* dist > skip_distance [REF :136]: no registration, association count 0                                    */
+#define ROMAN_GRID_GATED   4   /* not skipped and sim < desc_thresh [REF :144-149]: the sentinels of [REF :179-184]                         */
+#define ROMAN_GRID_TODO    8   /* neither: the pair is registered; it is in the compact list                                               */
+
+typedef struct roman_grid_gate_params {
+    double  radius;            /* SubmapAlignParams.submap_radius; NaN: ROMAN_E_INVALID; < 0 ("no radius"): ROMAN_E_UNSUPPORTED           */
+    double  skip_distance;     /* SubmapAlignInputOutput.skip_distance; +inf is legal (nothing is skipped)                                  */
+    int32_t desc_dim;          /* d: length of a submap descriptor; 0: no descriptor (sim = +inf)                                          */
+    int32_t reserved0;         /* must be 0                                                                                                */
+    double  desc_thresh;       /* SubmapAlignParams.submap_descriptor_thresh                                                               */
+    int32_t single_robot_lc;   /* 0/1: evaluate the time gate of [REF roman/align/results.py:160-162] into enable[]                        */
+    int32_t reserved1;         /* must be 0                                                                                                */
+    double  lc_time_thresh;    /* SubmapAlignParams.single_robot_lc_time_thresh                                                            */
+    int32_t reserved[2];       /* must be 0                                                                                                */
+} roman_grid_gate_params_t;
+
+/*
+ * roman_grid_gate_dev [REF roman/align/submap_align.py:93-149]: every pointer DEVICE; a PURE ENQUEUE on the context's stream,
+ * complete once that stream is synchronised.  Per side r (0: rows i, 1: columns j) arrays over that side's S_r submaps:
+ *   pos_r      float64[S_r][3]   submap.position
+ *   pos_gt_r   float64[S_r][3] or NULL: submap.position_gt.  The distance is taken on pos_gt when BOTH sides give it, on pos
+ *              otherwise [REF :96-99]
+ *   T_w_r      float64[S_r][16] row-major 4x4: the gravity-aligned pose the reference transform is built from (ground truth or
+ *              not [REF :118-126]: the caller resolves that)
+ *   time_r     float64[S_r]      submap.time (read only with single_robot_lc)
+ *   desc_r     float64[S_r][desc_dim], or NULL when desc_dim == 0
+ * Per pair, p = i * S1 + j:
+ *   dist       sqrt((dx^2 + dy^2) + dz^2), without fused multiply-adds
+ *   T_ij       inv(T_w0[i]) T_w1[j] (the inverse through the cofactors of the 3x3 block, as in the tail)
+ *   yaw_deg    |atan2(T_ij[1][0], T_ij[0][0]) * (180 / pi)| for a NEARBY pair, NaN otherwise [REF :127-129]
+ *   sim        +inf without descriptors; otherwise dot / (|a| |b|), and 0 when |a| |b| <= 1e-9 [REF roman/map/map.py:151-153].
+ *              The norms are computed once per submap; every sum over d has a fixed order: two calls agree bit for bit
+ *   flags      ROMAN_GRID_*: SKIP = dist > skip_distance; GATED = !SKIP && sim < desc_thresh; TODO = !SKIP && !GATED
+ * Dense outputs (S0 * S1 entries each, row-major): dist, flags (int32), yaw_deg, sim, T_ij (16 doubles per pair).
+ * Compact outputs, capacity S0 * S1 slots, of which the first n_todo[0] are written and the others left untouched: the TODO
+ * pairs in row-major order — the order of the reference's loop, found by a prefix sum, never by atomics:
+ *   pairs      int32[.][2]   (i, j)
+ *   T_ref      float64[.][16] T_ij of the pair
+ *   enable     int32[.]      0 when single_robot_lc and |time0[i] - time1[j]| < lc_time_thresh, 1 otherwise
+ *   n_todo     int32[1]
+ * S0 == 0 or S1 == 0: ROMAN_OK, n_todo = 0, nothing else written.  Errors: a NULL pointer that is needed, S < 0, a NaN radius,
+ * desc_dim < 0, desc NULL with desc_dim > 0, reserved words not 0 -> ROMAN_E_INVALID; radius < 0 -> ROMAN_E_UNSUPPORTED;
+ * S0 * S1 * 16 beyond int32 -> ROMAN_E_TOO_LARGE.
+ */
+ROMAN_API int roman_grid_gate_dev(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                                  const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                                  const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                                  double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                  int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo);
+
+/* The same with HOST pointers everywhere ([REF roman/align/submap_align.py:93-149] for a caller that holds NumPy arrays).
+   Synchronous: copies in, runs roman_grid_gate_dev, brings every output back.  The caller's pairs, T_ref and enable go up
+   first: the slots beyond n_todo come back as they were. */
+ROMAN_API int roman_grid_gate(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                              const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                              const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                              double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                              int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo);
+
+/* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */
 /* ------------------------------------------------------------------------------------------- */
 

@@ -12,6 +12,7 @@ ROMAN_MAX_RATIO_FEATURES = 8
 # error codes / status flags (include/roman_hip.h)
 ROMAN_OK = 0
 ROMAN_E_INVALID = -1
+ROMAN_E_UNSUPPORTED = -5
 ROMAN_E_TOO_LARGE = -6
 ROMAN_E_INTERNAL = -7
 ROMAN_ST_OK = 0
@@ -228,6 +229,27 @@ class RomanSubmapDesc(C.Structure):
     ]
 
 
+class RomanGridGateParams(C.Structure):
+    """roman_grid_gate_params_t"""
+    _fields_ = [
+        ("radius", C.c_double),
+        ("skip_distance", C.c_double),
+        ("desc_dim", C.c_int32),
+        ("reserved0", C.c_int32),
+        ("desc_thresh", C.c_double),
+        ("single_robot_lc", C.c_int32),
+        ("reserved1", C.c_int32),
+        ("lc_time_thresh", C.c_double),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+# flag bits of roman_grid_gate's flags[]
+ROMAN_GRID_NEARBY = 1
+ROMAN_GRID_SKIP = 2
+ROMAN_GRID_GATED = 4
+ROMAN_GRID_TODO = 8
+
 SUBMAP_LDS_CAND = 4096      # candidates of a submap the select kernel holds in LDS (kernels.hip.h); more go through the context's scratch
 
 STATS_NBYTES = C.sizeof(RomanStats)
@@ -235,6 +257,7 @@ MNO_SOLUTION_NBYTES = C.sizeof(RomanMnoSolution)
 RANSAC_RECORD_NBYTES = C.sizeof(RomanRansacRecord)
 SUBMAP_PARAMS_NBYTES = C.sizeof(RomanSubmapParams)
 SUBMAP_DESC_NBYTES = C.sizeof(RomanSubmapDesc)
+GRID_GATE_PARAMS_NBYTES = C.sizeof(RomanGridGateParams)
 LC_PARAMS_NBYTES = C.sizeof(RomanLcParams)
 LC_RECORD_NBYTES = C.sizeof(RomanLcRecord)
 PARAMS_NBYTES = C.sizeof(RomanParams)
@@ -303,6 +326,8 @@ def load_library():
         "roman_ransac_batch": (C.c_int, [ctxp, P(RomanRansacParams), i32, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp]),
         "roman_submaps_dev": (C.c_int, [ctxp, P(RomanSubmapParams), i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
         "roman_submaps": (C.c_int, [ctxp, P(RomanSubmapParams), i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
+        "roman_grid_gate_dev": (C.c_int, [ctxp, P(RomanGridGateParams), i32, i32] + [vp] * 19),
+        "roman_grid_gate": (C.c_int, [ctxp, P(RomanGridGateParams), i32, i32] + [vp] * 19),
         "roman_ctx_has_history": (C.c_int, [ctxp, P(RomanParams), i32, P(i32)]),
         "roman_ctx_cosine_screen_stats": (C.c_int, [ctxp, P(C.c_int64), P(C.c_int64), P(C.c_double)]),
         "roman_create_all_to_all": (C.c_int, [i32, i32, vp]),
@@ -337,7 +362,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_submaps_dev", "roman_submaps", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_submaps_dev", "roman_submaps", "roman_grid_gate_dev", "roman_grid_gate", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

@@ -7,6 +7,9 @@ Mirrors the part of the reference's caller that surrounds the hot path:
     `T_align()` for every surviving pair, the gravity post-filters, the error metrics against the reference
     transform, and the result matrices.  Instead of the serial double loop with a device round trip per pair,
     all surviving pairs go to ONE `roman_align_batch` call and every submap is packed once.
+    `submap_align_grid()` vectorises pass 1 over the grid and leaves pass 2 and the edges to the device; `submap_align_pools()`
+    starts from two device-resident submap pools (align.submaps.SubmapPool) and runs pass 1 on the device too
+    (roman_grid_gate_dev).
   * `save_submap_align_results()` [REF roman/align/results.py:122-194] — the `.g2o` loop-closure edges
     (`# LC: <n>` + `EDGE_SE3:QUAT`), the loop-closure json, the matrix pickle and the timing text, byte for byte
     in the reference's formats, and the per-robot `sm.json` dump ([REF :200-243]).  Plots and the pickled results
@@ -373,6 +376,27 @@ def _int64_ids(pool):
     return np.array(out, dtype=np.int64)
 
 
+def _records_into_results(res, ti, tj, nearby, device_edges, clipper_angle_mat, clipper_dist_mat, clipper_num_associations,
+                          T_ij_hat_mat, associated_objs_mat):
+    """Pass 2 of the grid forms ([REF roman/align/submap_align.py:186-200]): the tail's records of the registered pairs (ti, tj)
+    into the result matrices, IN PLACE -> the loop-closure edges (None unless the device decided them)."""
+    rec = res.records
+    if np.any(rec["flags"] & (_abi.ROMAN_LC_SKIPPED | _abi.ROMAN_LC_INTERNAL)):
+        raise _abi.RomanHipError("the batched call left problems without a result (ROMAN_LC_SKIPPED / ROMAN_LC_INTERNAL records)")
+    near = nearby[ti, tj]
+    clipper_angle_mat[ti[near], tj[near]] = np.abs(np.rad2deg(rec["theta"][near]))
+    clipper_dist_mat[ti[near], tj[near]] = rec["dist"][near]
+    clipper_num_associations[ti, tj] = rec["n_assoc"]
+    T_ij_hat_mat[ti, tj] = rec["T_hat"]
+    failed = (rec["flags"] & _abi.ROMAN_LC_FAILED) != 0
+    for b in np.nonzero(~failed)[0].tolist():            # (placing the association arrays: no arithmetic)
+        associated_objs_mat[ti[b]][tj[b]] = res.assoc[b]
+    if not device_edges:
+        return None
+    acc = np.asarray(res.accepted, dtype=np.int64)
+    return dict(pairs=np.stack([ti[acc], tj[acc]], axis=1).astype(np.int64), t=np.array(rec["edge_t"][acc]), q=np.array(rec["edge_q"][acc]))
+
+
 def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, registration=None,
                       compute: Optional[Callable] = None) -> SubmapAlignResults:
     """submap_align() for callers that hand over the whole S0 x S1 grid: the same results (and the same state of the caller's
@@ -546,21 +570,170 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
     timing_list = [(time.time() - t0) / B] * B
 
     # ---- pass 2: the records into the result matrices -------------------------------------------------------
-    rec = res.records
-    if np.any(rec["flags"] & (_abi.ROMAN_LC_SKIPPED | _abi.ROMAN_LC_INTERNAL)):
-        raise _abi.RomanHipError("the batched call left problems without a result (ROMAN_LC_SKIPPED / ROMAN_LC_INTERNAL records)")
-    near = nearby[ti, tj]
-    clipper_angle_mat[ti[near], tj[near]] = np.abs(np.rad2deg(rec["theta"][near]))
-    clipper_dist_mat[ti[near], tj[near]] = rec["dist"][near]
-    clipper_num_associations[ti, tj] = rec["n_assoc"]
-    T_ij_hat_mat[ti, tj] = rec["T_hat"]
-    failed = (rec["flags"] & _abi.ROMAN_LC_FAILED) != 0
-    for b in np.nonzero(~failed)[0].tolist():            # (placing the association arrays: no arithmetic)
-        associated_objs_mat[ti[b]][tj[b]] = res.assoc[b]
-    lc_edges = None
-    if device_edges:
-        acc = np.asarray(res.accepted, dtype=np.int64)
-        lc_edges = dict(pairs=np.stack([ti[acc], tj[acc]], axis=1).astype(np.int64), t=np.array(rec["edge_t"][acc]), q=np.array(rec["edge_q"][acc]))
+    lc_edges = _records_into_results(res, ti, tj, nearby, device_edges, clipper_angle_mat, clipper_dist_mat, clipper_num_associations,
+                                     T_ij_hat_mat, associated_objs_mat)
+    return make(lc_edges, timing_list)
+
+
+def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, registration=None, gt_poses=(None, None)) -> SubmapAlignResults:
+    """submap_align_grid() for two maps whose submaps are ALREADY in HBM (`pools`: two align.submaps.SubmapPool, as
+    build_submap_pool leaves them): the same results as submap_align_grid(sm_params, [p.to_submaps(segments) for p in pools]),
+    without a segment row coming back to the host or going up twice.  Pass 1 ([REF roman/align/submap_align.py:93-149])
+    is ONE device call over the grid of the non-empty submaps (roman_grid_gate_dev: radius gate, reference transforms, yaw
+    differences, descriptor gate, the pairs to register in loop order with the tail's T_ref and enable); the host uploads the
+    per-submap arrays (centres, poses, times: O(S)) and reads back the pair list and the S0 x S1 matrices.  The pairs then run
+    over the resident pools (pipeline.issue_chunked), the tail over the final outputs (roman_ctx_join, roman_lc_tail_dev) with
+    T_ref and enable where the gate wrote them.
+
+    gt_poses[r]: None, or (S, 4, 4) ground-truth `pose_flu_gt` of EVERY centre of pool r (empty submaps included) — then every
+    submap of that side has ground truth ([REF :96-99]); sm_io.gt_available[r] selects it for the reference transform.
+
+    Not covered — ValueError; SubmapPool.to_submaps() + submap_align_grid is the way: single_robot_lc over submaps that share
+    segment ids (one pool against itself), force_fill_submaps / no submap_radius (the AABB gate), stacked or frame descriptors,
+    RansacReg, registration plugins with a host prefilter."""
+    import torch
+    from ..runtime import LoopClosureResult, grid_gate_params, lc_record_dtype, stats_dtype
+    from .pipeline import issue_chunked
+    sm_io = sm_io or SubmapAlignIO()
+    registration = registration or sm_params.get_object_registration()
+    way = " (not on the device-resident path: use SubmapPool.to_submaps() + submap_align_grid)"
+    p = list(pools)
+    if len(p) != 2:
+        raise ValueError("pools must hold two SubmapPool objects")
+    if isinstance(registration, RansacReg):
+        raise ValueError("RansacReg has no device tail" + way)
+    if sm_params.force_fill_submaps or sm_params.submap_radius is None:
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes" + way)
+    if sm_params.submap_descriptor not in (None, 'mean_semantic'):
+        raise ValueError(f"submap_descriptor {sm_params.submap_descriptor!r}: stacked or frame descriptors are not in the pool" + way)
+    scorer = getattr(type(registration), "_associations_to_score", None)
+    if scorer is not None and scorer is not ObjectRegistration._associations_to_score:
+        raise ValueError("the registration plugin prefilters association lists on the host" + way)
+    if sm_params.single_robot_lc:
+        shared = p[0] is p[1] or np.intersect1d(p[0].ids[p[0].src >= 0], p[1].ids[p[1].src >= 0]).size > 0
+        if shared:
+            raise ValueError("single_robot_lc over submaps that share segment ids: the shared-segment removal has no device-pointer form yet" + way)
+    d = 0
+    if sm_params.submap_descriptor is not None:
+        if p[0].desc_dev is None or p[1].desc_dev is None:
+            raise ValueError("submap_descriptor 'mean_semantic' needs pools built with it (build_submap_pool keeps the descriptors on the device)")
+        d = int(p[0].desc_dev.shape[1])
+        if int(p[1].desc_dev.shape[1]) != d:
+            raise ValueError("the two pools have descriptors of different lengths")
+    for r in range(2):
+        if sm_io.gt_available[r] and gt_poses[r] is None:
+            raise ValueError(f"sm_io.gt_available[{r}] is set without gt_poses[{r}]")
+    ctx = registration._context()
+    dev = p[0].pool.device
+    on_host = dev.type == "cpu"                              # CPU tensors + a stand-in context (tests)
+    wait_torch = (lambda: None) if on_host else (lambda: torch.cuda.current_stream(dev).synchronize())
+    keep = [q.nonempty for q in p]                           # [REF roman/map/map.py:341]: the reference drops the empty submaps
+    n0, n1 = len(keep[0]), len(keep[1])
+    nan = lambda *s: np.zeros(s) * np.nan
+    clipper_angle_mat, clipper_dist_mat, clipper_num_associations = nan(n0, n1), nan(n0, n1), nan(n0, n1)
+    similarity_mat, robots_nearby_mat, submap_yaw_diff_mat = nan(n0, n1), nan(n0, n1), nan(n0, n1)
+    T_ij_mat, T_ij_hat_mat = nan(n0, n1, 4, 4), nan(n0, n1, 4, 4)
+    associated_objs_mat = [[[] for _ in range(n1)] for _ in range(n0)]
+    total_time_t0 = time.time()
+    make = lambda lc_edges=None, timing_list=(): SubmapAlignResults(
+        robots_nearby_mat=robots_nearby_mat, clipper_angle_mat=clipper_angle_mat, clipper_dist_mat=clipper_dist_mat,
+        clipper_num_associations=clipper_num_associations,
+        similarity_mat=similarity_mat if sm_params.submap_descriptor is not None else None,
+        submap_yaw_diff_mat=submap_yaw_diff_mat, T_ij_mat=T_ij_mat, T_ij_hat_mat=T_ij_hat_mat,
+        associated_objs_mat=associated_objs_mat, timing_list=list(timing_list), submap_align_params=sm_params,
+        submap_io=sm_io, total_time=time.time() - total_time_t0, lc_edges=lc_edges)
+    device_edges = sm_io.lc_association_thresh > 0
+    empty_edges = dict(pairs=np.zeros((0, 2), np.int64), t=np.zeros((0, 3)), q=np.zeros((0, 4))) if device_edges else None
+    if n0 == 0 or n1 == 0:
+        return make(empty_edges)
+
+    # ---- per submap, on the host (O(S)): centre, the pose the reference transform is built from, time, the edge frames —
+    # through the stand-in Submap's own properties, read as often as the pair loop reads them (submap_align_grid does the same) ----
+    other = (n1, n0)
+    pos, pos_gt, T_w, times, frames = [], [], [], [], []
+    for r in range(2):
+        c = p[r].centers
+        gt = None if gt_poses[r] is None else np.asarray(gt_poses[r], dtype=np.float64).reshape(len(c), 4, 4)
+        sms = [Submap(id=int(s), time=float(c.time[s]), segments=(), pose_flu=np.array(c.pose_flu[s], dtype=np.float64),
+                      pose_flu_gt=None if gt is None else gt[s].copy()) for s in keep[r]]
+        pos.append(np.stack([np.array(sm.position) for sm in sms]))
+        pos_gt.append(None if gt is None else np.stack([np.array(sm.position_gt) for sm in sms]))
+        if sm_io.gt_available[r]:
+            T_w.append(np.stack([np.array(_read_times(sm, "pose_gravity_aligned_gt", "pose_flu_gt", other[r]), dtype=np.float64) for sm in sms]))
+        else:
+            T_w.append(np.stack([np.array(_read_times(sm, "pose_gravity_aligned", "pose_flu", other[r]), dtype=np.float64) for sm in sms]))
+        times.append(np.array([sm.time for sm in sms], dtype=np.float64))
+        frames.append(np.stack([_edge_frames(sm)[r] for sm in sms]))
+
+    # ---- pass 1 on the device: one enqueue, one synchronisation, the pair list and the dense matrices back ----
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    f64, i32 = torch.float64, torch.int32
+    cap = n0 * n1
+    d_in = [dict(pos=up(pos[r]), gt=None if pos_gt[r] is None else up(pos_gt[r]), T_w=up(T_w[r].reshape(-1, 16)), time=up(times[r]),
+                 desc=p[r].desc_dev[torch.from_numpy(keep[r].astype(np.int64)).to(dev)].contiguous() if d else None) for r in range(2)]
+    d_dist = torch.empty((n0, n1), dtype=f64, device=dev); d_yaw = torch.empty((n0, n1), dtype=f64, device=dev)
+    d_sim = torch.empty((n0, n1), dtype=f64, device=dev); d_flags = torch.empty((n0, n1), dtype=i32, device=dev)
+    d_Tij = torch.empty((cap, 16), dtype=f64, device=dev); d_Tref = torch.empty((cap, 16), dtype=f64, device=dev)
+    d_pairs = torch.empty((cap, 2), dtype=i32, device=dev); d_enable = torch.empty(cap, dtype=i32, device=dev)
+    d_ntodo = torch.zeros(1, dtype=i32, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    gp = grid_gate_params(sm_params.submap_radius, sm_io.skip_distance, d, sm_params.submap_descriptor_thresh if d else 0.0,
+                          sm_params.single_robot_lc, sm_params.single_robot_lc_time_thresh)
+    wait_torch()                                             # the uploads are in place before the library's stream reads them
+    ctx.grid_gate_dev(gp, n0, n1, ptr(d_in[0]["pos"]), ptr(d_in[0]["T_w"]), ptr(d_in[1]["pos"]), ptr(d_in[1]["T_w"]),
+                      d_dist.data_ptr(), d_flags.data_ptr(), d_yaw.data_ptr(), d_sim.data_ptr(), d_Tij.data_ptr(),
+                      d_pairs.data_ptr(), d_Tref.data_ptr(), d_enable.data_ptr(), d_ntodo.data_ptr(),
+                      time0_ptr=ptr(d_in[0]["time"]), time1_ptr=ptr(d_in[1]["time"]), desc0_ptr=ptr(d_in[0]["desc"]), desc1_ptr=ptr(d_in[1]["desc"]),
+                      pos_gt0_ptr=ptr(d_in[0]["gt"]), pos_gt1_ptr=ptr(d_in[1]["gt"]))
+    ctx.sync()
+    B = int(d_ntodo.cpu().numpy()[0])
+    pairs = d_pairs[:B].cpu().numpy().astype(np.int64)
+    dist, flags, yaw, sim = d_dist.cpu().numpy(), d_flags.cpu().numpy(), d_yaw.cpu().numpy(), d_sim.cpu().numpy()
+    nearby, skip = (flags & _abi.ROMAN_GRID_NEARBY) != 0, (flags & _abi.ROMAN_GRID_SKIP) != 0
+    gated, todo = (flags & _abi.ROMAN_GRID_GATED) != 0, (flags & _abi.ROMAN_GRID_TODO) != 0
+    robots_nearby_mat[nearby] = dist[nearby]
+    T_ij_mat[:] = d_Tij.cpu().numpy().reshape(n0, n1, 4, 4)
+    submap_yaw_diff_mat[nearby] = yaw[nearby]
+    clipper_num_associations[skip] = 0
+    similarity_mat[~skip] = sim[~skip]
+    clipper_num_associations[gated] = 0                  # pairs the descriptor gate stopped: the sentinels of [REF :179-184]
+    clipper_angle_mat[gated & nearby] = np.abs(np.rad2deg(180.0)); clipper_dist_mat[gated & nearby] = 1e6
+    if not np.array_equal(pairs, np.stack(np.nonzero(todo), axis=1)):
+        raise _abi.RomanHipError("roman_grid_gate_dev: the compact pair list is not the TODO pairs in row-major order")
+    if B == 0:
+        return make(empty_edges)
+    ti, tj = pairs[:, 0], pairs[:, 1]
+
+    # ---- the hot path over the resident pools: offsets and counts from the pools, the batch in chunks, then the tail ----
+    batch, pool = p[0].grid_batch(p[1], mask=todo)
+    P = registration._abi_params()
+    kmax = batch.kmax()
+    a_out = torch.full((B, kmax, 2), -1, dtype=i32, device=dev); n_out = torch.zeros(B, dtype=i32, device=dev)
+    T_out = torch.zeros((B, 16), dtype=f64, device=dev); st_out = torch.zeros(B, dtype=i32, device=dev)
+    FL, FR = up(frames[0].reshape(-1, 16)), up(frames[1].reshape(-1, 16))
+    iL, iR = d_pairs[:B, 0].contiguous(), d_pairs[:B, 1].contiguous()
+    records = torch.zeros(B * _abi.LC_RECORD_NBYTES, dtype=torch.uint8, device=dev)
+    acc_idx = torch.zeros(B, dtype=i32, device=dev); acc_n = torch.zeros(1, dtype=i32, device=dev)
+    lp = LcInputs(dim=sm_params.dim, force_rm_upside_down=sm_params.force_rm_upside_down,
+                  force_rm_lc_roll_pitch=sm_params.force_rm_lc_roll_pitch,
+                  tilt_thresh=registration.roll_pitch_thresh if getattr(registration, "use_gravity", False) else None,
+                  lc_association_thresh=int(np.ceil(sm_io.lc_association_thresh)) if device_edges else 1).params()
+    wait_torch()                                             # the pool (torch.cat), the cleared outputs and the frames are in place
+    t0 = time.time()
+    status = issue_chunked(ctx, P, pool, batch, kmax, a_out, n_out, T_out, st_out)     # re-issues skipped problems, then synchronises:
+    ctx.join()                                               # ... the tail below sees the FINAL attempt of every problem only
+    ctx.lc_tail_dev(lp, B, T_out.data_ptr(), n_out.data_ptr(), st_out.data_ptr(), records.data_ptr(), acc_idx.data_ptr(), acc_n.data_ptr(),
+                    T_ref_ptr=d_Tref.data_ptr(), enable_ptr=d_enable.data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
+                    FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr())
+    ctx.sync()
+    timing_list = [(time.time() - t0) / B] * B
+    rec = np.frombuffer(records.cpu().numpy().tobytes(), dtype=lc_record_dtype()).copy()
+    n_h, a_h = n_out.cpu().numpy(), a_out.cpu().numpy()
+    s = sm_params.dim + 1
+    res = LoopClosureResult([a_h[b, :n_h[b]].copy() for b in range(B)], T_out.cpu().numpy()[:, :s * s].reshape(B, s, s).copy(), status,
+                            np.zeros(B, dtype=stats_dtype()), rec, acc_idx.cpu().numpy()[:int(acc_n.cpu().numpy()[0])].copy())
+    lc_edges = _records_into_results(res, ti, tj, nearby, device_edges, clipper_angle_mat, clipper_dist_mat, clipper_num_associations,
+                                     T_ij_hat_mat, associated_objs_mat)
     return make(lc_edges, timing_list)
 
 

@@ -144,6 +144,7 @@ class SubmapPool:
     desc: Optional[np.ndarray]   # (S, d) mean_semantic descriptors (NaN rows for empty submaps) or None
     centers: SubmapCenters
     table: MapTable
+    desc_dev: Optional[object] = None   # the same descriptors as the call left them on the device: torch tensor (S, d) float64, or None (submap_align_pools reads it)
 
     @property
     def nonempty(self):
@@ -242,4 +243,4 @@ def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, par
     ctx.sync()
     return SubmapPool(pool, int(P.cap), count.cpu().numpy()[:S].copy(), src.cpu().numpy()[:rows].reshape(S, P.cap).copy(),
                       ids_out.cpu().numpy()[:rows].reshape(S, P.cap).copy(), status.cpu().numpy()[:S].copy(),
-                      desc.cpu().numpy()[:S, :d].copy() if d else None, centers, table)
+                      desc.cpu().numpy()[:S, :d].copy() if d else None, centers, table, desc_dev=desc[:S, :d] if d else None)

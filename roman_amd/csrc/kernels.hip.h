@@ -7315,6 +7315,130 @@ __global__ void __launch_bounds__(256) k_submap_desc(int cap, int F, int d, cons
     desc_out[(int64_t)s * d + c] = acc / (double)n;
 }
 
+// ---------------------------------------------------------------------------------------------
+// pass 1 of the pair loop for a whole S0 x S1 grid ([REF roman/align/submap_align.py:93-149], radius mode):
+// distance and radius gate, reference transform, yaw difference, submap-descriptor similarity, the skip / gated / todo
+// classes, and the TODO pairs compacted in row-major order with their reference transform and time-gate flag — what
+// roman_align_lc_batch_dev / roman_lc_tail_dev read.
+//   k_grid_norms    a wave per submap (both sides): the descriptor's norm, once per submap instead of once per pair;
+//   k_grid_gate     a wave per (i, GRID_TJ consecutive j): lane l walks components l, l + 64, ... of descriptor i ONCE against
+//                   GRID_TJ descriptors of the other side (coalesced 512-byte row pieces, GRID_TJ independent sums), a butterfly
+//                   adds the 64 partial sums — a fixed order, no atomics: two runs agree bit for bit —, then lane t finishes pair
+//                   (i, j0 + t): a few dozen f64 operations and the dense outputs;
+//   k_grid_compact  one workgroup: the TODO pairs in row-major order through block_excl_scan (k_lc_compact's idiom);
+//   k_grid_fill     16 threads per compact slot: T_ref <- T_ij of the slot's pair, bit for bit, and the time gate
+//                   [REF roman/align/results.py:160-162].  Slots beyond n_todo are not written.
+// ---------------------------------------------------------------------------------------------
+constexpr int GRID_TJ = 4;                                       // pairs of one row a wave of k_grid_gate handles
+constexpr int GRID_NEARBY = 1, GRID_SKIP = 2, GRID_GATED = 4, GRID_TODO = 8;    // ROMAN_GRID_* of roman_hip.h
+
+struct GridSide { const double* pos; const double* pos_gt; const double* T_w; const double* time; const double* desc; };
+struct GridOut { double* dist; int32_t* flags; double* yaw_deg; double* sim; double* T_ij; };
+
+// sum over the 64 lanes, the same bits in every lane (x + y == y + x)
+__device__ __forceinline__ double wave_sum_all(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__global__ void __launch_bounds__(256) k_grid_norms(int S0, int S1, int d, const double* __restrict__ desc0, const double* __restrict__ desc1,
+                                                    double* __restrict__ norm)
+{
+    const int lane = threadIdx.x & 63, w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= S0 + S1) return;                                    // (wave-uniform)
+    const double* v = w < S0 ? desc0 + (int64_t)w * d : desc1 + (int64_t)(w - S0) * d;
+    double s = 0.0;
+    for (int k = lane; k < d; k += 64) { const double x = v[k]; s += x * x; }
+    s = wave_sum_all(s);
+    if (lane == 0) norm[w] = sqrt(s);
+}
+
+__global__ void __launch_bounds__(256) k_grid_gate(roman_grid_gate_params_t P, int S0, int S1, GridSide a, GridSide b,
+                                                   const double* __restrict__ norm, GridOut out)
+{
+    const int lane = threadIdx.x & 63;
+    const int nT = (S1 + GRID_TJ - 1) / GRID_TJ;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= (int64_t)S0 * nT) return;                           // (wave-uniform)
+    const int i = (int)(w / nT), j0 = (int)(w % nT) * GRID_TJ;
+    const int d = P.desc_dim;
+    double acc[GRID_TJ];
+#pragma unroll
+    for (int t = 0; t < GRID_TJ; ++t) acc[t] = 0.0;
+    if (d > 0) {
+        const double* va = a.desc + (int64_t)i * d;
+        const double* vb[GRID_TJ];
+#pragma unroll
+        for (int t = 0; t < GRID_TJ; ++t) vb[t] = b.desc + (int64_t)min(j0 + t, S1 - 1) * d;    // (a tile's tail repeats the last row: in bounds, never stored)
+        for (int k = lane; k < d; k += 64) {
+            const double x = va[k];
+#pragma unroll
+            for (int t = 0; t < GRID_TJ; ++t) acc[t] += x * vb[t][k];
+        }
+#pragma unroll
+        for (int t = 0; t < GRID_TJ; ++t) acc[t] = wave_sum_all(acc[t]);
+    }
+    const int j = j0 + lane;
+    if (lane >= GRID_TJ || j >= S1) return;
+    double dot = acc[0];
+#pragma unroll
+    for (int t = 1; t < GRID_TJ; ++t) dot = (lane == t) ? acc[t] : dot;
+    const int64_t p = (int64_t)i * S1 + j;
+    const bool gt = a.pos_gt != nullptr && b.pos_gt != nullptr;  // [REF :96-99]
+    const double* pa = (gt ? a.pos_gt : a.pos) + 3 * (int64_t)i;
+    const double* pb = (gt ? b.pos_gt : b.pos) + 3 * (int64_t)j;
+    const double dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
+    const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
+    const bool nearby = dist < 2.0 * P.radius;
+    double Ti[16], T[16];
+    lc_inv_affine(a.T_w + 16 * (int64_t)i, Ti);
+    lc_mul4(Ti, b.T_w + 16 * (int64_t)j, T);
+    const double yaw = nearby ? fabs(atan2(T[4], T[0]) * (180.0 / 3.141592653589793)) : d_nan();    // |np.rad2deg(yaw)|
+    double sim = INFINITY;
+    if (d > 0) {
+        const double np_ = norm[i] * norm[S0 + j];
+        sim = (np_ <= 1e-9) ? 0.0 : dot / np_;                   // np.isclose(norm_prod, 0, atol=1e-9, rtol=0) [REF roman/map/map.py:151-153]
+    }
+    const bool skip = dist > P.skip_distance;                    // [REF :136]
+    const bool gated = !skip && sim < P.desc_thresh;
+    const bool todo = !skip && !gated;
+    out.dist[p] = dist; out.yaw_deg[p] = yaw; out.sim[p] = sim;
+    out.flags[p] = (nearby ? GRID_NEARBY : 0) | (skip ? GRID_SKIP : 0) | (gated ? GRID_GATED : 0) | (todo ? GRID_TODO : 0);
+    double* To = out.T_ij + 16 * p;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) To[t] = T[t];
+}
+
+__global__ void __launch_bounds__(1024) k_grid_compact(int B, int S1, const int32_t* __restrict__ flags, int32_t* __restrict__ pairs, int32_t* __restrict__ n_todo)
+{
+    __shared__ int shi[17];
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int PER = (B + nt - 1) / nt;
+    const int b0 = min(B, tid * PER), b1 = min(B, b0 + PER);
+    int mine = 0;
+    for (int b = b0; b < b1; ++b) mine += (flags[b] & GRID_TODO) ? 1 : 0;
+    int total;
+    int pos = block_excl_scan(mine, shi, total);
+    for (int b = b0; b < b1; ++b)
+        if (flags[b] & GRID_TODO) { pairs[2 * (int64_t)pos] = b / S1; pairs[2 * (int64_t)pos + 1] = b % S1; ++pos; }
+    if (tid == 0) *n_todo = total;
+}
+
+__global__ void __launch_bounds__(256) k_grid_fill(roman_grid_gate_params_t P, int S1, const int32_t* __restrict__ n_todo, const int32_t* __restrict__ pairs,
+                                                   const double* __restrict__ T_ij, const double* __restrict__ time0, const double* __restrict__ time1,
+                                                   double* __restrict__ T_ref, int32_t* __restrict__ enable)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t s = g >> 4;
+    const int e = (int)(g & 15);
+    if (s >= *n_todo) return;
+    const int i = pairs[2 * s], j = pairs[2 * s + 1];
+    T_ref[16 * s + e] = T_ij[16 * ((int64_t)i * S1 + j) + e];
+    if (e == 0) enable[s] = (P.single_robot_lc && fabs(time0[i] - time1[j]) < P.lc_time_thresh) ? 0 : 1;
+}
+
 // elementwise math probe for tests
 __global__ void k_debug_math(int kind, const double* __restrict__ a, const double* __restrict__ b,
                              int64_t n, double* __restrict__ out)

@@ -175,6 +175,9 @@ struct roman_ctx {
     DevBuf smDesc, smPts, smSpillKey, smSpillIdx, smHost;
     PinnedStage<roman_submap_desc_t> smStage;
 
+    // pass 1 of a grid (roman_grid_gate*): the descriptor norms of both sides, and the host-pointer call's arrays on the device
+    DevBuf ggNorm, ggHost;
+
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
     bool profile = false;
@@ -1438,6 +1441,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     c->shareStage.release(); c->ransacStage.release();
     { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx, &c->smHost}; for (DevBuf* b : sm) b->release(); }
     c->smStage.release();
+    c->ggNorm.release(); c->ggHost.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -2576,6 +2580,111 @@ int roman_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t 
     HIPCHK(c, hipMemcpyAsync(src, dSrc, bSrc, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(count, dev + oCnt, bCnt, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(status, dev + oSt, bCnt, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipStreamSynchronize(WS.stream));
+    return ROMAN_OK;
+}
+
+// --- pass 1 of the pair loop over a grid, radius mode ([REF roman/align/submap_align.py:93-149]) -------------------
+static int grid_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int32_t S0, int32_t S1,
+                           const void* pos0, const void* T_w0, const void* time0, const void* desc0,
+                           const void* pos1, const void* T_w1, const void* time1, const void* desc1,
+                           const void* dist, const void* flags, const void* yaw_deg, const void* sim, const void* T_ij,
+                           const void* pairs, const void* T_ref, const void* enable, const void* n_todo)
+{
+    if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
+    if (S0 < 0 || S1 < 0) return fail(c, ROMAN_E_INVALID, "S0 < 0 or S1 < 0");
+    if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
+        return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
+    if (P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
+    if (P->desc_dim < 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d is negative", P->desc_dim);
+    if (P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: without a radius the gate is the AABB test, which stays on the host", P->radius);
+    if (!n_todo) return fail(c, ROMAN_E_INVALID, "n_todo is NULL");
+    if (S0 == 0 || S1 == 0) return ROMAN_OK;
+    if ((int64_t)S0 * S1 > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "S0 * S1 = %lld pairs exceed the index width", (long long)S0 * S1);
+    if (P->desc_dim > 0 && (!desc0 || !desc1)) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
+    if (!pos0 || !pos1 || !T_w0 || !T_w1) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
+    if (P->single_robot_lc && (!time0 || !time1)) return fail(c, ROMAN_E_INVALID, "time is NULL with single_robot_lc");
+    if (!dist || !flags || !yaw_deg || !sim || !T_ij || !pairs || !T_ref || !enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
+    return ROMAN_OK;
+}
+
+int roman_grid_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                        const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                        const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                        double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                        int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    if (S0 == 0 || S1 == 0) { HIPCHK(c, hipMemsetAsync(n_todo, 0, sizeof(int32_t), stream)); return ROMAN_OK; }
+    const int d = gparams->desc_dim, B = S0 * S1;
+    HIPCHK(c, c->ggNorm.ensure(sizeof(double) * (size_t)(S0 + S1)));            // scratch first: a failure leaves nothing enqueued
+    double* dNorm = c->ggNorm.as<double>();
+    if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S0 + S1 + 3) / 4)), dim3(256), 0, stream, (int)S0, (int)S1, d, desc0, desc1, dNorm);
+    const GridSide a{pos0, pos_gt0, T_w0, time0, desc0}, b{pos1, pos_gt1, T_w1, time1, desc1};
+    const GridOut out{dist, flags, yaw_deg, sim, T_ij};
+    const int64_t waves = (int64_t)S0 * ((S1 + GRID_TJ - 1) / GRID_TJ);
+    hipLaunchKernelGGL(k_grid_gate, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
+    hipLaunchKernelGGL(k_grid_compact, dim3(1), dim3(B > 256 ? 1024 : 256), 0, stream, B, (int)S1, (const int32_t*)flags, pairs, n_todo);
+    hipLaunchKernelGGL(k_grid_fill, dim3((unsigned)(((int64_t)B * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, (int)S1, (const int32_t*)n_todo,
+                       (const int32_t*)pairs, (const double*)T_ij, time0, time1, T_ref, enable);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_grid_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                    const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                    const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                    double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                    int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo);
+    if (rc) return rc;
+    if (S0 == 0 || S1 == 0) { *n_todo = 0; return ROMAN_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    // one device block, 8-byte arrays first: per side pos | pos_gt | T_w | time | desc, then dist | yaw | sim | T_ij | T_ref | flags | pairs | enable | n_todo
+    const size_t d = (size_t)gparams->desc_dim, B = (size_t)S0 * (size_t)S1;
+    const double* in[2][5] = {{pos0, pos_gt0, T_w0, time0, desc0}, {pos1, pos_gt1, T_w1, time1, desc1}};
+    const size_t S[2] = {(size_t)S0, (size_t)S1};
+    size_t inB[2][5], inO[2][5], total = 0;
+    for (int r = 0; r < 2; ++r) {
+        const size_t per[5] = {3, 3, 16, 1, d};
+        for (int k = 0; k < 5; ++k) { inB[r][k] = in[r][k] ? sizeof(double) * per[k] * S[r] : 0; inO[r][k] = total; total += inB[r][k]; }
+    }
+    const size_t oDist = total, oYaw = oDist + 8 * B, oSim = oYaw + 8 * B, oTij = oSim + 8 * B, oTref = oTij + 128 * B, oFlags = oTref + 128 * B,
+                 oPairs = oFlags + 4 * B, oEn = oPairs + 8 * B, oCnt = oEn + 4 * B;
+    total = oCnt + 4;
+    HIPCHK(c, c->ggHost.ensure(total));
+    char* const dev = c->ggHost.as<char>();
+    const double* dIn[2][5];
+    for (int r = 0; r < 2; ++r)
+        for (int k = 0; k < 5; ++k) {
+            dIn[r][k] = inB[r][k] ? reinterpret_cast<const double*>(dev + inO[r][k]) : nullptr;
+            if (inB[r][k]) HIPCHK(c, hipMemcpyAsync(dev + inO[r][k], in[r][k], inB[r][k], hipMemcpyHostToDevice, WS.stream));
+        }
+    // the caller's compact outputs go up first: the slots beyond n_todo come back as they were
+    HIPCHK(c, hipMemcpyAsync(dev + oTref, T_ref, 128 * B, hipMemcpyHostToDevice, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(dev + oPairs, pairs, 8 * B, hipMemcpyHostToDevice, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(dev + oEn, enable, 4 * B, hipMemcpyHostToDevice, WS.stream));
+    rc = roman_grid_gate_dev(c, gparams, S0, S1, dIn[0][0], dIn[0][1], dIn[0][2], dIn[0][3], dIn[0][4], dIn[1][0], dIn[1][1], dIn[1][2], dIn[1][3], dIn[1][4],
+                             reinterpret_cast<double*>(dev + oDist), reinterpret_cast<int32_t*>(dev + oFlags), reinterpret_cast<double*>(dev + oYaw),
+                             reinterpret_cast<double*>(dev + oSim), reinterpret_cast<double*>(dev + oTij), reinterpret_cast<int32_t*>(dev + oPairs),
+                             reinterpret_cast<double*>(dev + oTref), reinterpret_cast<int32_t*>(dev + oEn), reinterpret_cast<int32_t*>(dev + oCnt));
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(dist, dev + oDist, 8 * B, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(yaw_deg, dev + oYaw, 8 * B, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(sim, dev + oSim, 8 * B, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(T_ij, dev + oTij, 128 * B, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(T_ref, dev + oTref, 128 * B, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(flags, dev + oFlags, 4 * B, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(pairs, dev + oPairs, 8 * B, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(enable, dev + oEn, 4 * B, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(n_todo, dev + oCnt, 4, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipStreamSynchronize(WS.stream));
     return ROMAN_OK;
 }

@@ -133,6 +133,32 @@ class SubmapsResult:
 
 
 @dataclass
+class GridGateResult:
+    """Results of one roman_grid_gate call over an S0 x S1 grid: dense matrices and the compact list of the TODO pairs."""
+    dist: np.ndarray       # (S0, S1) float64
+    flags: np.ndarray      # (S0, S1) int32 ROMAN_GRID_* bits
+    yaw_deg: np.ndarray    # (S0, S1) float64, NaN where the pair is not nearby
+    sim: np.ndarray        # (S0, S1) float64 (+inf without descriptors)
+    T_ij: np.ndarray       # (S0, S1, 4, 4) float64
+    pairs: np.ndarray      # (S0 * S1, 2) int32: the first n_todo rows are the TODO pairs, row-major; the others as handed in
+    T_ref: np.ndarray      # (S0 * S1, 4, 4) float64, likewise
+    enable: np.ndarray     # (S0 * S1,) int32, likewise
+    n_todo: int
+
+
+def grid_gate_params(radius, skip_distance=np.inf, desc_dim=0, desc_thresh=0.0, single_robot_lc=False, lc_time_thresh=0.0):
+    """-> roman_grid_gate_params_t (a missing radius — None — is passed as -1: the library answers ROMAN_E_UNSUPPORTED)."""
+    P = _abi.RomanGridGateParams()
+    P.radius = -1.0 if radius is None else float(radius)
+    P.skip_distance = float(skip_distance)
+    P.desc_dim = int(desc_dim)
+    P.desc_thresh = float(desc_thresh)
+    P.single_robot_lc = int(bool(single_robot_lc))
+    P.lc_time_thresh = float(lc_time_thresh)
+    return P
+
+
+@dataclass
 class LoopClosureResult(BatchResult):
     """A batch result with the loop-closure tail behind it."""
     records: np.ndarray    # (B,) structured array (lc_record_dtype)
@@ -458,6 +484,58 @@ class Context:
                                          int(descs.shape[0]), _ptr(descs), vp(pool_ptr), vp(count_ptr), vp(src_ptr), vp(ids_out_ptr),
                                          vp(status_ptr), int(desc_dim), vp(desc_out_ptr))
         self._check(rc, "roman_submaps_dev")
+
+    # ------------------------------------------------------------------ pass 1 of a grid of submaps
+    def grid_gate(self, gparams, pos0, T_w0, pos1, T_w1, time0=None, time1=None, desc0=None, desc1=None, pos_gt0=None, pos_gt1=None,
+                  pairs=None, T_ref=None, enable=None):
+        """Host-pointer pass 1 of the pair loop over an S0 x S1 grid (roman_grid_gate, [REF roman/align/submap_align.py:93-149],
+        radius mode): gparams a RomanGridGateParams (grid_gate_params()); per side pos (S, 3), T_w (S, 4, 4), optionally time
+        (S,), desc (S, desc_dim) and pos_gt (S, 3).  The compact outputs may be handed in (C-contiguous, the C ABI's shapes and
+        types): the slots beyond n_todo come back as they were; fresh ones are filled with -1 / NaN / -1.  -> GridGateResult."""
+        side = []
+        for pos, T_w, tm, desc, gt in ((pos0, T_w0, time0, desc0, pos_gt0), (pos1, T_w1, time1, desc1, pos_gt1)):
+            pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
+            T_w = _f64(T_w).reshape(-1, 16)
+            tm = None if tm is None else _f64(tm).reshape(-1)
+            desc = None if desc is None else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
+            gt = None if gt is None else _f64(gt).reshape(-1, 3)
+            if T_w.shape[0] != S or (tm is not None and tm.shape[0] != S) or (gt is not None and gt.shape[0] != S):
+                raise ValueError("the per-submap arrays of a side must hold one entry per submap")
+            if desc is not None and gparams.desc_dim > 0 and desc.shape[1] != gparams.desc_dim:
+                raise ValueError("desc must be (S, desc_dim)")
+            side.append((S, pos, gt, T_w, tm, desc))
+        S0, S1 = side[0][0], side[1][0]
+        B = S0 * S1
+
+        def given(a, shape, dtype, fill):
+            if a is None:
+                return np.full(shape, fill, dtype=dtype)
+            if a.dtype != dtype or not a.flags.c_contiguous or a.shape != shape:
+                raise ValueError(f"an output array must be C-contiguous {np.dtype(dtype).name} of shape {shape}")
+            return a
+        pairs = given(pairs, (B, 2), np.int32, -1); T_ref = given(T_ref, (B, 4, 4), np.float64, np.nan); enable = given(enable, (B,), np.int32, -1)
+        dist = np.zeros((S0, S1)); flags = np.zeros((S0, S1), dtype=np.int32); yaw = np.zeros((S0, S1)); sim = np.zeros((S0, S1))
+        T_ij = np.zeros((S0, S1, 4, 4)); n_todo = np.zeros(1, dtype=np.int32)
+        self._generation += 1
+        ins = [_ptr(a) for s in side for a in s[1:]]
+        rc = self._lib.roman_grid_gate(self._h, C.byref(gparams), S0, S1, *ins, _ptr(dist), _ptr(flags), _ptr(yaw), _ptr(sim), _ptr(T_ij),
+                                       _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(n_todo))
+        self._check(rc, "roman_grid_gate")
+        return GridGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, int(n_todo[0]))
+
+    def grid_gate_dev(self, gparams, S0, S1, pos0_ptr, T_w0_ptr, pos1_ptr, T_w1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
+                      pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr, time0_ptr=None, time1_ptr=None, desc0_ptr=None, desc1_ptr=None,
+                      pos_gt0_ptr=None, pos_gt1_ptr=None):
+        """Device-pointer pass 1 of the pair loop over an S0 x S1 grid (roman_grid_gate_dev): every pointer a device address (an
+        integer, e.g. torch.Tensor.data_ptr()).  A pure enqueue on the context's stream; complete after sync().  T_ref_ptr and
+        enable_ptr are what lc_tail_dev / align_lc_batch_dev take for the problems of `pairs`."""
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_grid_gate_dev(self._h, C.byref(gparams), int(S0), int(S1),
+                                           vp(pos0_ptr), vp(pos_gt0_ptr), vp(T_w0_ptr), vp(time0_ptr), vp(desc0_ptr),
+                                           vp(pos1_ptr), vp(pos_gt1_ptr), vp(T_w1_ptr), vp(time1_ptr), vp(desc1_ptr),
+                                           vp(dist_ptr), vp(flags_ptr), vp(yaw_deg_ptr), vp(sim_ptr), vp(T_ij_ptr),
+                                           vp(pairs_ptr), vp(T_ref_ptr), vp(enable_ptr), vp(n_todo_ptr))
+        self._check(rc, "roman_grid_gate_dev")
 
     # ------------------------------------------------------------------ loop closures
     def align_lc_batch(self, params, feats, off1, n1, off2, n2, lc, assoc=None, assoc_off=None, u0=None, kmax=None):
