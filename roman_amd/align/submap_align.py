@@ -2,14 +2,18 @@
 
 Mirrors the part of the reference's caller that surrounds the hot path:
 
-  * `submap_align()` [REF roman/align/submap_align.py:74-220] — gating (distance / AABB, submap descriptor
-    similarity, `skip_distance`, shared-segment removal for single-robot loop closures), `register()` +
-    `T_align()` for every surviving pair, the gravity post-filters, the error metrics against the reference
-    transform, and the result matrices.  Instead of the serial double loop with a device round trip per pair,
-    all surviving pairs go to ONE `roman_align_batch` call and every submap is packed once.
-    `submap_align_grid()` vectorises pass 1 over the grid and leaves pass 2 and the edges to the device; `submap_align_pools()`
-    starts from two device-resident submap pools (align.submaps.SubmapPool) and runs pass 1 on the device too
-    (roman_grid_gate_dev).
+  * `submap_align()` [REF roman/align/submap_align.py:74-220] in three forms that return the same `SubmapAlignResults` and leave
+    the caller's submaps in the same state.  They share one skeleton: `_GridResults` holds the NaN-filled result matrices and
+    builds the results object; pass 1 [REF :93-149] gates every pair of the S0 x S1 grid (distance / AABB, `skip_distance`,
+    submap descriptor similarity: `_grid_similarity`, `_gates`) and `_GridResults.pass1()` is the one place where its outcome
+    (`nearby`, `skip`, `gated`, the sentinels of [REF :179-184]) becomes matrix entries; the surviving pairs go to ONE batched
+    device call over a pool that holds every submap once (`_drop_shared`, `_set_association_lists`, `_lc_inputs`); pass 2
+    [REF :160-200] — gravity post-filters, error metrics against the reference transform — fills the rest.  The forms differ
+    in where a step runs.  `submap_align()`, the pair loop, reads the submaps pair by pair in the reference's order, calls
+    `roman_align_batch` and does pass 2 per pair on the host.  `submap_align_grid()` does pass 1 in NumPy over the whole grid
+    and leaves pass 2 and the loop-closure edges to the device (`roman_align_lc_batch`, `_records_into_results`).
+    `submap_align_pools()` starts from two device-resident submap pools (align.submaps.SubmapPool) and runs pass 1 on the
+    device too (`roman_grid_gate_dev`), decoding its flags into the same `pass1()` call.
   * `save_submap_align_results()` [REF roman/align/results.py:122-194] — the `.g2o` loop-closure edges
     (`# LC: <n>` + `EDGE_SE3:QUAT`), the loop-closure json, the matrix pickle and the timing text, byte for byte
     in the reference's formats, and the per-robot `sm.json` dump ([REF :200-243]).  Plots and the pickled results
@@ -31,7 +35,7 @@ import numpy as np
 from scipy.spatial.transform import Rotation as Rot
 
 from .. import _abi
-from ..runtime import LcInputs
+from ..runtime import LcInputs, LoopClosureResult, grid_gate_params, lc_record_dtype, stats_dtype
 from .batch import AlignmentBatch, pack_submaps, run_batch, run_lc_batch, run_lc_batch_ids
 from .dist_reg_with_pruning import _zyx_euler
 from .object_registration import ObjectRegistration
@@ -61,6 +65,11 @@ def aabb_intersects(p1, p2):
     """[REF roman/utils.py:160-169]"""
     p1_min, p1_max, p2_min, p2_max = np.min(p1, axis=0), np.max(p1, axis=0), np.min(p2, axis=0), np.max(p2, axis=0)
     return bool(np.all(p1_min[:3] <= p2_max[:3]) and np.all(p1_max[:3] >= p2_min[:3]))
+
+
+def _zero_norm(norm_prod):
+    """The reference's guard [REF roman/map/map.py:148-150, 159-160]: a cosine over such a product of norms is 0."""
+    return np.isclose(norm_prod, 0.0, atol=1e-9, rtol=0.0)
 
 
 @dataclass
@@ -108,24 +117,50 @@ class Submap:
         desc1, desc2 = np.asarray(submap1.descriptor), np.asarray(submap2.descriptor)
         if desc1.ndim == desc2.ndim == 1:
             norm_prod = np.linalg.norm(desc1) * np.linalg.norm(desc2)
-            if np.isclose(norm_prod, 0.0, atol=1e-9, rtol=0.0):
+            if _zero_norm(norm_prod):
                 return 0.0
             return np.dot(desc1, desc2) / norm_prod
         d1 = desc1.reshape(desc1.shape[0], 1, desc1.shape[1]); d2 = desc2.reshape(1, desc2.shape[0], desc2.shape[1])
         norm_prods = np.linalg.norm(d1, axis=2) * np.linalg.norm(d2, axis=2)
         with np.errstate(invalid="ignore", divide="ignore"):
             sims = np.sum(d1 * d2, axis=2) / norm_prods
-        sims[np.isclose(norm_prods, 0.0, atol=1e-9, rtol=0.0)] = 0.0
+        sims[_zero_norm(norm_prods)] = 0.0
         return np.max(sims)
+
+
+def _host_cosine(A, B):
+    """What Context.cosine_matrix computes on the device, in NumPy (the CPU doubles' descriptor gate): (a, d) x (b, d) -> (a, b)."""
+    norm_prod = np.linalg.norm(A, axis=1)[:, None] * np.linalg.norm(B, axis=1)[None, :]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sim = (A @ B.T) / norm_prod
+    sim[_zero_norm(norm_prod)] = 0.0
+    return sim
+
+
+def _grid_similarity(descs0, descs1, cosine):
+    """Submap.similarity for every pair of the grid at once (row f2) -> (S0, S1), or None when the descriptors are of mixed kinds.
+    `cosine(A, B)` is Context.cosine_matrix or _host_cosine: ONE call either way.  Vector descriptors: the cosine matrix itself.
+    Stacked per-frame descriptors ([REF roman/map/map.py:152-162]: the best cosine over all frame pairs, zero-norm frames scoring
+    0): all frames of all submaps at once, then a segmented maximum."""
+    flat = descs0 + descs1
+    if all(d.ndim == 1 for d in flat):
+        return cosine(np.stack(descs0), np.stack(descs1))
+    if all(d.ndim == 2 and d.shape[0] > 0 and d.shape[1] == flat[0].shape[1] for d in flat):
+        o0 = np.concatenate([[0], np.cumsum([d.shape[0] for d in descs0])]).astype(np.int64)
+        o1 = np.concatenate([[0], np.cumsum([d.shape[0] for d in descs1])]).astype(np.int64)
+        frames = cosine(np.concatenate(descs0, axis=0), np.concatenate(descs1, axis=0))
+        return np.maximum.reduceat(np.maximum.reduceat(frames, o0[:-1], axis=0), o1[:-1], axis=1)
+    return None
 
 
 def stacked_similarity(ctx, descs0, descs1):
     """Best pairwise cosine between the frame descriptors of every submap of robot 0 and every submap of robot 1
     ([REF roman/map/map.py:152-162]) -> (S0, S1).  One cosine kernel over all frames, then a segmented maximum."""
-    o0 = np.concatenate([[0], np.cumsum([d.shape[0] for d in descs0])]).astype(np.int64)
-    o1 = np.concatenate([[0], np.cumsum([d.shape[0] for d in descs1])]).astype(np.int64)
-    frames = ctx.cosine_matrix(np.concatenate(descs0, axis=0), np.concatenate(descs1, axis=0))     # zero-norm frames: 0
-    return np.maximum.reduceat(np.maximum.reduceat(frames, o0[:-1], axis=0), o1[:-1], axis=1)
+    return _grid_similarity(list(descs0), list(descs1), ctx.cosine_matrix)
+
+
+def _device_cosine(registration):
+    return lambda A, B: registration._context().cosine_matrix(A, B)      # (the context is made only if a cosine is asked for)
 
 
 @dataclass
@@ -156,9 +191,101 @@ class SubmapAlignResults:
     submap_align_params: object
     submap_io: object
     total_time: float = -np.inf
-    # submap_align_grid only: the loop-closure edges as the device computed them — {'pairs': (K, 2) int (i, j) in loop order,
+    # submap_align_grid / submap_align_pools only: the loop-closure edges as the device computed them — {'pairs': (K, 2) int (i, j) in loop order,
     # 't': (K, 3), 'q': (K, 4) xyzw}.  loop_closure_edges() and the writers then do no per-pair matrix work.
     lc_edges: Optional[dict] = None
+
+
+# ---------------------------------------------------------------------------------------------
+# what the three forms share: the result matrices, the rules of pass 1, the inputs of the batched call
+# ---------------------------------------------------------------------------------------------
+_NO_ESTIMATE = (180.0, 1e6)          # (theta, dist) of a pair without an estimate; it has 0 associations [REF :179-184]
+
+
+def _edges_on_device(sm_io):
+    return sm_io.lc_association_thresh > 0               # (a threshold <= 0 would accept pairs that never reach the device)
+
+
+class _GridResults:
+    """The result matrices of an (n0, n1) grid, NaN-filled as [REF roman/align/submap_align.py:80-91] allocates them; the rules
+    that turn pass 1's outcome into their entries; the SubmapAlignResults at the end."""
+
+    def __init__(self, sm_params, sm_io, n0, n1):
+        nan = lambda *s: np.zeros(s) * np.nan
+        self.sm_params, self.sm_io, self.t0 = sm_params, sm_io, time.time()
+        self.clipper_angle_mat, self.clipper_dist_mat, self.clipper_num_associations = nan(n0, n1), nan(n0, n1), nan(n0, n1)
+        self.similarity_mat, self.robots_nearby_mat, self.submap_yaw_diff_mat = nan(n0, n1), nan(n0, n1), nan(n0, n1)
+        self.T_ij_mat, self.T_ij_hat_mat = nan(n0, n1, 4, 4), nan(n0, n1, 4, 4)
+        self.associated_objs_mat = [[[] for _ in range(n1)] for _ in range(n0)]
+        self.device_edges = _edges_on_device(sm_io)
+
+    def empty_edges(self):
+        return dict(pairs=np.zeros((0, 2), np.int64), t=np.zeros((0, 3)), q=np.zeros((0, 4))) if self.device_edges else None
+
+    def pass1(self, dist, nearby, skip, gated, yaw_deg, sim, T_ij):
+        """[REF :136-149, 179-184] over (n0, n1) arrays: `nearby` pairs get their distance and yaw difference; a pair beyond
+        `skip_distance` (`skip`) has 0 associations and nothing else; every other pair gets its similarity, and one the
+        descriptor gate stopped (`gated`) the sentinels of a pair without an estimate."""
+        self.robots_nearby_mat[nearby] = dist[nearby]
+        self.submap_yaw_diff_mat[nearby] = yaw_deg[nearby]
+        self.T_ij_mat[:] = T_ij
+        self.clipper_num_associations[skip] = 0
+        self.similarity_mat[~skip] = sim[~skip]
+        self.clipper_num_associations[gated] = 0
+        self.clipper_angle_mat[gated & nearby] = np.abs(np.rad2deg(_NO_ESTIMATE[0])); self.clipper_dist_mat[gated & nearby] = _NO_ESTIMATE[1]
+
+    def results(self, timing_list=(), lc_edges=None):
+        return SubmapAlignResults(
+            robots_nearby_mat=self.robots_nearby_mat, clipper_angle_mat=self.clipper_angle_mat, clipper_dist_mat=self.clipper_dist_mat,
+            clipper_num_associations=self.clipper_num_associations,
+            similarity_mat=self.similarity_mat if self.sm_params.submap_descriptor is not None else None,
+            submap_yaw_diff_mat=self.submap_yaw_diff_mat, T_ij_mat=self.T_ij_mat, T_ij_hat_mat=self.T_ij_hat_mat,
+            associated_objs_mat=self.associated_objs_mat, timing_list=list(timing_list), submap_align_params=self.sm_params,
+            submap_io=self.sm_io, total_time=time.time() - self.t0, lc_edges=lc_edges)
+
+
+def _gates(dist, sim, sm_params, sm_io):
+    """The gate decisions of [REF :136-149] -> (skip, gated), for one pair or for arrays over the grid: beyond `skip_distance` a
+    pair is skipped; otherwise the descriptor gate stops it below the threshold.  What neither holds for is registered."""
+    skip = dist > sm_io.skip_distance
+    with np.errstate(invalid="ignore"):
+        gated = np.logical_not(skip) & (sim < sm_params.submap_descriptor_thresh)
+    return skip, gated
+
+
+def _drop_shared(segs_i, segs_j):
+    """Self loop closures [REF :108-115]: both lists without the segments (by id) that both submaps hold."""
+    common = {seg.id for seg in segs_i} & {seg.id for seg in segs_j}
+    return [s for s in segs_i if s.id not in common], [s for s in segs_j if s.id not in common]
+
+
+def _has_host_prefilter(registration):
+    """A pruning plugin that scores explicit association lists: its host prefilter reads both maps of a pair."""
+    scorer = getattr(type(registration), "_associations_to_score", None)
+    return scorer is not None and scorer is not ObjectRegistration._associations_to_score
+
+
+def _set_association_lists(registration, batch, segs_of):
+    """`batch.assoc` / `batch.assoc_off` from the registration's association list of every problem (`segs_of(b)` -> its two
+    segment lists), all-to-all where it gives None for one; left unset when it gives None for all."""
+    lists = [registration._association_list(*segs_of(b)) if (batch.n1[b] and batch.n2[b]) else None for b in range(len(batch))]
+    if any(l is not None for l in lists):
+        from ..clipperpy.utils import create_all_to_all
+        lists = [l if l is not None else create_all_to_all(int(batch.n1[b]), int(batch.n2[b])) for b, l in enumerate(lists)]
+        batch.assoc_off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int64)
+        batch.assoc = np.concatenate(lists, axis=0).astype(np.int32)
+
+
+def _tilt_thresh(registration):
+    """DistRegWithPruning.register's own roll / pitch check [REF dist_reg_with_pruning.py:38-45], or None."""
+    return registration.roll_pitch_thresh if getattr(registration, "use_gravity", False) else None
+
+
+def _lc_inputs(sm_params, sm_io, registration, **arrays):
+    """The switches of the device's loop-closure tail from the parameters; `arrays`: T_ref, enable, FL, iL, FR, iR where the host has them."""
+    return LcInputs(dim=sm_params.dim, force_rm_upside_down=sm_params.force_rm_upside_down,
+                    force_rm_lc_roll_pitch=sm_params.force_rm_lc_roll_pitch, tilt_thresh=_tilt_thresh(registration),
+                    lc_association_thresh=int(np.ceil(sm_io.lc_association_thresh)) if _edges_on_device(sm_io) else 1, **arrays)
 
 
 def submap_align(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, registration=None,
@@ -173,61 +300,39 @@ def submap_align(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, regi
     registration = registration or sm_params.get_object_registration()
     compute = compute or run_batch
     n0, n1 = len(submaps[0]), len(submaps[1])
-    nan = lambda *s: np.zeros(s) * np.nan
-    clipper_angle_mat, clipper_dist_mat, clipper_num_associations = nan(n0, n1), nan(n0, n1), nan(n0, n1)
-    similarity_mat, robots_nearby_mat, submap_yaw_diff_mat = nan(n0, n1), nan(n0, n1), nan(n0, n1)
-    T_ij_mat, T_ij_hat_mat = nan(n0, n1, 4, 4), nan(n0, n1, 4, 4)
-    associated_objs_mat = [[[] for _ in range(n1)] for _ in range(n0)]
-    total_time_t0 = time.time()
+    M = _GridResults(sm_params, sm_io, n0, n1)
 
-    # ---- submap-descriptor gate (row f2): every cosine of the S0 x S1 gate in ONE device call (k_cos, f64 matrix
-    # core).  Plain vector descriptors: the S0 x S1 cosine matrix itself.  Stacked per-frame descriptors
-    # ([REF roman/map/map.py:152-162]: the best cosine over all frame pairs, zero-norm frames scoring 0): all frames
-    # of all submaps go through the same kernel at once and the per-pair maximum is a segmented reduction of its
-    # output.  (The CPU test double uses the per-pair numpy form below.) -----------------------------------------
+    # ---- submap-descriptor gate (row f2): every cosine of the S0 x S1 gate in ONE device call (k_cos, f64 matrix core).
+    # (The CPU test double, and descriptors of mixed kinds, use the per-pair definition below.) ----------------------
     sim_all = None
     if sm_params.submap_descriptor is not None and compute is run_batch and n0 and n1:
-        descs = [[np.asarray(sm.descriptor) for sm in submaps[r]] for r in range(2)]
-        flat = [d for r in range(2) for d in descs[r]]
-        if all(d.ndim == 1 for d in flat):
-            sim_all = registration._context().cosine_matrix(np.stack(descs[0]), np.stack(descs[1]))
-        elif all(d.ndim == 2 and d.shape[0] > 0 and d.shape[1] == flat[0].shape[1] for d in flat):
-            sim_all = stacked_similarity(registration._context(), descs[0], descs[1])
+        sim_all = _grid_similarity(*[[np.asarray(sm.descriptor) for sm in submaps[r]] for r in range(2)], _device_cosine(registration))
 
-    # ---- pass 1: gating, reference transforms, the list of pairs to register ([REF :93-149]) -------------------
-    todo = []                                            # (i, j, segs_i, segs_j)
-    skipped_sim = []
+    # ---- pass 1: gating, reference transforms, the list of pairs to register ([REF :93-149]), read pair by pair in the
+    # reference's order (`pose_gravity_aligned[_gt]` flattens the pose it reads in place) ---------------------------------
+    dist, yaw_deg, sim = np.full((n0, n1), np.nan), np.full((n0, n1), np.nan), np.full((n0, n1), np.inf)
+    nearby, T_ij = np.zeros((n0, n1), dtype=bool), np.empty((n0, n1, 4, 4))
     for i in range(n0):
         for j in range(n1):
             si, sj = submaps[0][i], submaps[1][j]
-            if si.has_gt and sj.has_gt:
-                submap_distance = np.linalg.norm(si.position_gt - sj.position_gt)
-            else:
-                submap_distance = np.linalg.norm(si.position - sj.position)
-            if (not sm_params.force_fill_submaps and sm_params.submap_radius is not None and submap_distance < sm_params.submap_radius * 2) or \
-                    ((sm_params.force_fill_submaps or sm_params.submap_radius is None) and len(si) and len(sj)
-                     and aabb_intersects(si.segments_as_global_points, sj.segments_as_global_points)):
-                robots_nearby_mat[i, j] = submap_distance
-            segs_i, segs_j = list(si.segments), list(sj.segments)
-            if sm_params.single_robot_lc:                # self loop closures: drop the segments both submaps hold
-                common = {seg.id for seg in segs_i} & {seg.id for seg in segs_j}
-                segs_i = [s for s in segs_i if s.id not in common]; segs_j = [s for s in segs_j if s.id not in common]
+            both_gt = si.has_gt and sj.has_gt
+            dist[i, j] = np.linalg.norm(si.position_gt - sj.position_gt) if both_gt else np.linalg.norm(si.position - sj.position)
+            nearby[i, j] = (not sm_params.force_fill_submaps and sm_params.submap_radius is not None and dist[i, j] < sm_params.submap_radius * 2) or \
+                ((sm_params.force_fill_submaps or sm_params.submap_radius is None) and len(si) and len(sj)
+                 and aabb_intersects(si.segments_as_global_points, sj.segments_as_global_points))
             T_wi = si.pose_gravity_aligned_gt if sm_io.gt_available[0] else si.pose_gravity_aligned
             T_wj = sj.pose_gravity_aligned_gt if sm_io.gt_available[1] else sj.pose_gravity_aligned
-            T_ij = np.linalg.inv(T_wi) @ T_wj
-            if not np.isnan(robots_nearby_mat[i, j]):
-                submap_yaw_diff_mat[i, j] = np.abs(np.rad2deg(transform_to_xyzrpy(T_ij)[5]))
-            submap_sim = np.inf if sm_params.submap_descriptor is None else (sim_all[i, j] if sim_all is not None else Submap.similarity(si, sj))
-            T_ij_mat[i, j] = T_ij
-            if submap_distance > sm_io.skip_distance:
-                clipper_num_associations[i, j] = 0
-                T_ij_hat_mat[i, j] = nan(4, 4)
-                continue
-            similarity_mat[i, j] = submap_sim
-            if submap_sim < sm_params.submap_descriptor_thresh:
-                skipped_sim.append((i, j, len(segs_i), len(segs_j)))
-            else:
-                todo.append((i, j, segs_i, segs_j))
+            T_ij[i, j] = np.linalg.inv(T_wi) @ T_wj
+            if nearby[i, j]:
+                yaw_deg[i, j] = np.abs(np.rad2deg(transform_to_xyzrpy(T_ij[i, j])[5]))
+            if sm_params.submap_descriptor is not None:
+                sim[i, j] = sim_all[i, j] if sim_all is not None else Submap.similarity(si, sj)
+    skip, gated = _gates(dist, sim, sm_params, sm_io)
+    M.pass1(dist, nearby, skip, gated, yaw_deg, sim, T_ij)
+    todo = []                                            # (i, j, segs_i, segs_j), in loop order
+    for i, j in np.argwhere(~skip & ~gated).tolist():
+        segs_i, segs_j = list(submaps[0][i].segments), list(submaps[1][j].segments)
+        todo.append((i, j) + (_drop_shared(segs_i, segs_j) if sm_params.single_robot_lc else (segs_i, segs_j)))
 
     # ---- the hot path: every submap (variant) packed once, one batched call ---------------------------------
     timing_list = []
@@ -244,34 +349,19 @@ def submap_align(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, regi
         feats, offs = pack_submaps(registration, pool)
         lens = np.diff(offs).astype(np.int32)
         batch = AlignmentBatch(feats, offs[ii].astype(np.int64), lens[ii], offs[jj].astype(np.int64), lens[jj])
-        lists = [registration._association_list(a, b) if (len(a) and len(b)) else None for (_, _, a, b) in todo]
-        if any(l is not None for l in lists):            # pruning plugins score explicit association lists
-            from ..clipperpy.utils import create_all_to_all
-            lists = [l if l is not None else create_all_to_all(len(a), len(b)) for l, (_, _, a, b) in zip(lists, todo)]
-            batch.assoc_off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int64)
-            batch.assoc = np.concatenate(lists, axis=0).astype(np.int32)
+        _set_association_lists(registration, batch, lambda b: todo[b][2:])
         t0 = time.time()
         res = compute(registration, batch)
         timing_list = [(time.time() - t0) / len(todo)] * len(todo)
 
     # ---- pass 2: post-filters, error metrics, result matrices ([REF :160-200]) ---------------------------------
-    def report(i, j, T_ij_hat, theta, dist, associations, len_i, len_j):
-        if not np.isnan(robots_nearby_mat[i, j]):
-            clipper_angle_mat[i, j] = np.abs(np.rad2deg(theta)); clipper_dist_mat[i, j] = dist
-        clipper_num_associations[i, j] = len(associations)
-        T_ij_hat_mat[i, j] = T_ij_hat
-        associated_objs_mat[i][j] = associations
-
-    prune_tilt = registration.roll_pitch_thresh if getattr(registration, "use_gravity", False) else None
-    for (i, j, li, lj) in skipped_sim:
-        report(i, j, nan(4, 4), 180.0, 1e6, [], li, lj)
-    for b, (i, j, segs_i, segs_j) in enumerate(todo):
-        T_ij = T_ij_mat[i, j]
+    prune_tilt = _tilt_thresh(registration)
+    for b, (i, j, _, _) in enumerate(todo):
         failed = bool(res.status[b] & (_abi.ROMAN_ST_INSUFFICIENT | _abi.ROMAN_ST_EMPTY_MAP))   # T_align would raise
         associations = res.assoc[b]
         if not failed:
             T_ij_hat = np.array(res.T[b], dtype=np.float64)
-            if prune_tilt is not None:                   # DistRegWithPruning.register's own check [REF dist_reg_with_pruning.py:38-45]
+            if prune_tilt is not None:
                 _, pitch, roll = _zyx_euler(T_ij_hat[:sm_params.dim, :sm_params.dim])
                 failed = not (np.abs(roll) < prune_tilt and np.abs(pitch) < prune_tilt)
         if not failed:
@@ -279,8 +369,8 @@ def submap_align(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, regi
                 # The reference multiplies a 3x3 estimate into the 4x4 reference transform here and cannot run
                 # ([REF :159-162]); the planar estimate is lifted to SE(3) (identity in z) instead.
                 T2 = T_ij_hat; T_ij_hat = np.eye(4); T_ij_hat[:2, :2] = T2[:2, :2]; T_ij_hat[:2, 3] = T2[:2, 2]
-                T_error = np.linalg.inv(T_ij_hat) @ T_ij
-                theta = np.arctan2(T_error[1, 0], T_error[0, 0]); dist = np.linalg.norm(T_error[:2, 3])
+                T_error = np.linalg.inv(T_ij_hat) @ T_ij[i, j]
+                theta = np.arctan2(T_error[1, 0], T_error[0, 0]); d_err = np.linalg.norm(T_error[:2, 3])
             else:
                 if sm_params.force_rm_upside_down:       # GravityConstraintError branch [REF :167-170]
                     xyzrpy = transform_to_xyzrpy(T_ij_hat)
@@ -288,19 +378,16 @@ def submap_align(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None, regi
                 if not failed:
                     if sm_params.force_rm_lc_roll_pitch:
                         T_ij_hat = transform_rm_roll_pitch(T_ij_hat)
-                    T_error = np.linalg.inv(T_ij_hat) @ T_ij
-                    theta = Rot.from_matrix(T_error[:3, :3]).magnitude(); dist = np.linalg.norm(T_error[:3, 3])
+                    T_error = np.linalg.inv(T_ij_hat) @ T_ij[i, j]
+                    theta = Rot.from_matrix(T_error[:3, :3]).magnitude(); d_err = np.linalg.norm(T_error[:3, 3])
         if failed:                                       # the except-branch sentinel [REF :179-184]
-            T_ij_hat, theta, dist, associations = nan(4, 4), 180.0, 1e6, []
-        report(i, j, T_ij_hat, theta, dist, associations, len(segs_i), len(segs_j))
-
-    return SubmapAlignResults(
-        robots_nearby_mat=robots_nearby_mat, clipper_angle_mat=clipper_angle_mat, clipper_dist_mat=clipper_dist_mat,
-        clipper_num_associations=clipper_num_associations,
-        similarity_mat=similarity_mat if sm_params.submap_descriptor is not None else None,
-        submap_yaw_diff_mat=submap_yaw_diff_mat, T_ij_mat=T_ij_mat, T_ij_hat_mat=T_ij_hat_mat,
-        associated_objs_mat=associated_objs_mat, timing_list=timing_list, submap_align_params=sm_params,
-        submap_io=sm_io, total_time=time.time() - total_time_t0)
+            T_ij_hat, (theta, d_err), associations = np.full((4, 4), np.nan), _NO_ESTIMATE, []
+        if nearby[i, j]:
+            M.clipper_angle_mat[i, j] = np.abs(np.rad2deg(theta)); M.clipper_dist_mat[i, j] = d_err
+        M.clipper_num_associations[i, j] = len(associations)
+        M.T_ij_hat_mat[i, j] = T_ij_hat
+        M.associated_objs_mat[i][j] = associations
+    return M.results(timing_list)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -318,28 +405,6 @@ def _read_times(sm, prop, attr, times):
         if np.asarray(getattr(sm, attr)).tobytes() == before:
             break
     return val
-
-
-def _host_similarity(descs0, descs1):
-    """Submap.similarity for every pair at once (the CPU double's descriptor gate): vector descriptors or stacked frames."""
-    flat = descs0 + descs1
-    if all(d.ndim == 1 for d in flat):
-        A, B = np.stack(descs0), np.stack(descs1)
-        norm_prod = np.linalg.norm(A, axis=1)[:, None] * np.linalg.norm(B, axis=1)[None, :]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            sim = (A @ B.T) / norm_prod
-        sim[np.isclose(norm_prod, 0.0, atol=1e-9, rtol=0.0)] = 0.0
-        return sim
-    if all(d.ndim == 2 and d.shape[0] > 0 and d.shape[1] == flat[0].shape[1] for d in flat):
-        o0 = np.concatenate([[0], np.cumsum([d.shape[0] for d in descs0])]).astype(np.int64)
-        o1 = np.concatenate([[0], np.cumsum([d.shape[0] for d in descs1])]).astype(np.int64)
-        A, B = np.concatenate(descs0, axis=0), np.concatenate(descs1, axis=0)
-        norm_prod = np.linalg.norm(A, axis=1)[:, None] * np.linalg.norm(B, axis=1)[None, :]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            frames = (A @ B.T) / norm_prod
-        frames[np.isclose(norm_prod, 0.0, atol=1e-9, rtol=0.0)] = 0.0
-        return np.maximum.reduceat(np.maximum.reduceat(frames, o0[:-1], axis=0), o1[:-1], axis=1)
-    return None
 
 
 def _edge_frames(sm):
@@ -376,22 +441,21 @@ def _int64_ids(pool):
     return np.array(out, dtype=np.int64)
 
 
-def _records_into_results(res, ti, tj, nearby, device_edges, clipper_angle_mat, clipper_dist_mat, clipper_num_associations,
-                          T_ij_hat_mat, associated_objs_mat):
+def _records_into_results(M, res, ti, tj, nearby):
     """Pass 2 of the grid forms ([REF roman/align/submap_align.py:186-200]): the tail's records of the registered pairs (ti, tj)
-    into the result matrices, IN PLACE -> the loop-closure edges (None unless the device decided them)."""
+    into the result matrices of `M`, IN PLACE -> the loop-closure edges (None unless the device decided them)."""
     rec = res.records
     if np.any(rec["flags"] & (_abi.ROMAN_LC_SKIPPED | _abi.ROMAN_LC_INTERNAL)):
         raise _abi.RomanHipError("the batched call left problems without a result (ROMAN_LC_SKIPPED / ROMAN_LC_INTERNAL records)")
     near = nearby[ti, tj]
-    clipper_angle_mat[ti[near], tj[near]] = np.abs(np.rad2deg(rec["theta"][near]))
-    clipper_dist_mat[ti[near], tj[near]] = rec["dist"][near]
-    clipper_num_associations[ti, tj] = rec["n_assoc"]
-    T_ij_hat_mat[ti, tj] = rec["T_hat"]
+    M.clipper_angle_mat[ti[near], tj[near]] = np.abs(np.rad2deg(rec["theta"][near]))
+    M.clipper_dist_mat[ti[near], tj[near]] = rec["dist"][near]
+    M.clipper_num_associations[ti, tj] = rec["n_assoc"]
+    M.T_ij_hat_mat[ti, tj] = rec["T_hat"]
     failed = (rec["flags"] & _abi.ROMAN_LC_FAILED) != 0
     for b in np.nonzero(~failed)[0].tolist():            # (placing the association arrays: no arithmetic)
-        associated_objs_mat[ti[b]][tj[b]] = res.assoc[b]
-    if not device_edges:
+        M.associated_objs_mat[ti[b]][tj[b]] = res.assoc[b]
+    if not M.device_edges:
         return None
     acc = np.asarray(res.accepted, dtype=np.int64)
     return dict(pairs=np.stack([ti[acc], tj[acc]], axis=1).astype(np.int64), t=np.array(rec["edge_t"][acc]), q=np.array(rec["edge_q"][acc]))
@@ -419,23 +483,9 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
     compute = compute or run_lc_batch
     S = [list(submaps[0]), list(submaps[1])]
     n0, n1 = len(S[0]), len(S[1])
-    nan = lambda *s: np.zeros(s) * np.nan
-    clipper_angle_mat, clipper_dist_mat, clipper_num_associations = nan(n0, n1), nan(n0, n1), nan(n0, n1)
-    similarity_mat, robots_nearby_mat, submap_yaw_diff_mat = nan(n0, n1), nan(n0, n1), nan(n0, n1)
-    T_ij_mat, T_ij_hat_mat = nan(n0, n1, 4, 4), nan(n0, n1, 4, 4)
-    associated_objs_mat = [[[] for _ in range(n1)] for _ in range(n0)]
-    total_time_t0 = time.time()
-    make = lambda lc_edges=None, timing_list=(): SubmapAlignResults(
-        robots_nearby_mat=robots_nearby_mat, clipper_angle_mat=clipper_angle_mat, clipper_dist_mat=clipper_dist_mat,
-        clipper_num_associations=clipper_num_associations,
-        similarity_mat=similarity_mat if sm_params.submap_descriptor is not None else None,
-        submap_yaw_diff_mat=submap_yaw_diff_mat, T_ij_mat=T_ij_mat, T_ij_hat_mat=T_ij_hat_mat,
-        associated_objs_mat=associated_objs_mat, timing_list=list(timing_list), submap_align_params=sm_params,
-        submap_io=sm_io, total_time=time.time() - total_time_t0, lc_edges=lc_edges)
-    device_edges = sm_io.lc_association_thresh > 0       # (a threshold <= 0 would accept pairs that never reach the device)
-    empty_edges = dict(pairs=np.zeros((0, 2), np.int64), t=np.zeros((0, 3)), q=np.zeros((0, 4))) if device_edges else None
+    M = _GridResults(sm_params, sm_io, n0, n1)
     if n0 == 0 or n1 == 0:
-        return make(empty_edges)
+        return M.results(lc_edges=M.empty_edges())
 
     # ---- per submap: sizes, positions, ground truth ---------------------------------------------------------
     lens = [np.array([len(sm) for sm in S[r]]) for r in range(2)]
@@ -483,42 +533,24 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
             lo1 = np.stack([boxes[1][k][0] for k in u1]); hi1 = np.stack([boxes[1][k][1] for k in u1])
             hit = np.all(lo0[:, None, :] <= hi1[None, :, :], axis=2) & np.all(hi0[:, None, :] >= lo1[None, :, :], axis=2)
             nearby[np.ix_(u0, u1)] = hit
-    robots_nearby_mat[nearby] = dist[nearby]
-    T_ij_mat[:] = np.matmul(np.linalg.inv(T_w[0])[:, None, :, :], T_w[1][None, :, :, :])
-    yaw = np.arctan2(T_ij_mat[:, :, 1, 0], T_ij_mat[:, :, 0, 0])      # the fixed-axis xyz yaw of a rotation about z
-    submap_yaw_diff_mat[nearby] = np.abs(np.rad2deg(yaw[nearby]))
+    T_ij = np.matmul(np.linalg.inv(T_w[0])[:, None, :, :], T_w[1][None, :, :, :])
+    yaw = np.arctan2(T_ij[:, :, 1, 0], T_ij[:, :, 0, 0])              # the fixed-axis xyz yaw of a rotation about z
     if sm_params.submap_descriptor is None:
         sim = np.full((n0, n1), np.inf)
-    else:
+    else:                                                # row f2: every cosine of the gate in ONE call
         descs = [[np.asarray(sm.descriptor) for sm in S[r]] for r in range(2)]
-        flat = descs[0] + descs[1]
-        sim = None
-        if on_device:                                    # row f2: every cosine of the gate in ONE device call
-            if all(d.ndim == 1 for d in flat):
-                sim = registration._context().cosine_matrix(np.stack(descs[0]), np.stack(descs[1]))
-            elif all(d.ndim == 2 and d.shape[0] > 0 and d.shape[1] == flat[0].shape[1] for d in flat):
-                sim = stacked_similarity(registration._context(), descs[0], descs[1])
-        else:
-            sim = _host_similarity(descs[0], descs[1])
+        sim = _grid_similarity(descs[0], descs[1], _device_cosine(registration) if on_device else _host_cosine)
         if sim is None:                                  # mixed descriptor kinds: the per-pair definition
             sim = np.array([[Submap.similarity(si, sj) for sj in S[1]] for si in S[0]], dtype=np.float64)
-    skip = dist > sm_io.skip_distance
-    clipper_num_associations[skip] = 0
-    similarity_mat[~skip] = sim[~skip]
-    with np.errstate(invalid="ignore"):
-        gated = ~skip & (sim < sm_params.submap_descriptor_thresh)
-    todo = ~skip & ~gated
-    # pairs the descriptor gate stopped: the sentinels of [REF :179-184]
-    clipper_num_associations[gated] = 0
-    clipper_angle_mat[gated & nearby] = np.abs(np.rad2deg(180.0)); clipper_dist_mat[gated & nearby] = 1e6
-    ti, tj = np.nonzero(todo)                            # row-major: the order of the pair loop
+    skip, gated = _gates(dist, sim, sm_params, sm_io)
+    M.pass1(dist, nearby, skip, gated, np.abs(np.rad2deg(yaw)), sim, T_ij)
+    ti, tj = np.nonzero(~skip & ~gated)                  # row-major: the order of the pair loop
     B = int(ti.shape[0])
     if B == 0:
-        return make(empty_edges)
+        return M.results(lc_edges=M.empty_edges())
 
     # ---- the hot path: every submap (variant) packed once, ONE batched call with the tail behind it ---------
-    scorer = getattr(type(registration), "_associations_to_score", None)
-    host_lists = scorer is not None and scorer is not ObjectRegistration._associations_to_score
+    host_lists = _has_host_prefilter(registration)
     ui, uj = np.unique(ti), np.unique(tj)
     pool = [list(S[0][i].segments) for i in ui] + [list(S[1][j].segments) for j in uj]
     pool_ids = None
@@ -528,51 +560,61 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
         slot_i = np.zeros(n0, dtype=np.int64); slot_i[ui] = np.arange(len(ui))
         slot_j = np.zeros(n1, dtype=np.int64); slot_j[uj] = len(ui) + np.arange(len(uj))
         ii, jj = slot_i[ti], slot_j[tj]
-        pair_segs = None
     else:                                                # ... or the host does, per pair: a reduced copy of both submaps for every pair
-        pool, pair_segs = [], []
-        for i, j in zip(ti.tolist(), tj.tolist()):
-            segs_i, segs_j = list(S[0][i].segments), list(S[1][j].segments)
-            common = {seg.id for seg in segs_i} & {seg.id for seg in segs_j}
-            segs_i = [s for s in segs_i if s.id not in common]; segs_j = [s for s in segs_j if s.id not in common]
-            pool.append(segs_i); pool.append(segs_j); pair_segs.append((segs_i, segs_j))
+        pool = [segs for i, j in zip(ti.tolist(), tj.tolist()) for segs in _drop_shared(list(S[0][i].segments), list(S[1][j].segments))]
         ii, jj = 2 * np.arange(B), 2 * np.arange(B) + 1
     feats, offs = pack_submaps(registration, pool)
     plen = np.diff(offs).astype(np.int32)
     batch = AlignmentBatch(feats, offs[ii].astype(np.int64), plen[ii], offs[jj].astype(np.int64), plen[jj],
                            pair_index=np.stack([ti, tj], axis=1), ids=pool_ids)
     if host_lists:
-        # a pruning plugin scores explicit association lists: its host prefilter reads both maps of a pair
-        segs_of = (lambda b: (pool[ii[b]], pool[jj[b]])) if pair_segs is None else (lambda b: pair_segs[b])
-        lists = [registration._association_list(*segs_of(b)) if (plen[ii[b]] and plen[jj[b]]) else None for b in range(B)]
-        if any(l is not None for l in lists):
-            from ..clipperpy.utils import create_all_to_all
-            lists = [l if l is not None else create_all_to_all(int(plen[ii[b]]), int(plen[jj[b]])) for b, l in enumerate(lists)]
-            batch.assoc_off = np.concatenate([[0], np.cumsum([len(l) for l in lists])]).astype(np.int64)
-            batch.assoc = np.concatenate(lists, axis=0).astype(np.int32)
-    frames = [{int(k): _edge_frames(S[r][int(k)]) for k in np.unique(t)} for r, t in ((0, ti), (1, tj))]
+        _set_association_lists(registration, batch, lambda b: (pool[ii[b]], pool[jj[b]]))
     FL = np.tile(np.eye(4), (n0, 1, 1)); FR = np.tile(np.eye(4), (n1, 1, 1))
-    for k, f in frames[0].items():
-        FL[k] = f[0]
-    for k, f in frames[1].items():
-        FR[k] = f[1]
+    for k in ui.tolist():
+        FL[k] = _edge_frames(S[0][k])[0]
+    for k in uj.tolist():
+        FR[k] = _edge_frames(S[1][k])[1]
     times = [np.array([float(sm.time) for sm in S[r]]) for r in range(2)]
     enable = np.ones(B, dtype=np.int32)
     if sm_params.single_robot_lc:                        # the time gate of [REF roman/align/results.py:160-162]
         enable[np.abs(times[0][ti] - times[1][tj]) < sm_params.single_robot_lc_time_thresh] = 0
-    lc = LcInputs(dim=sm_params.dim, force_rm_upside_down=sm_params.force_rm_upside_down,
-                  force_rm_lc_roll_pitch=sm_params.force_rm_lc_roll_pitch,
-                  tilt_thresh=registration.roll_pitch_thresh if getattr(registration, "use_gravity", False) else None,
-                  lc_association_thresh=int(np.ceil(sm_io.lc_association_thresh)) if device_edges else 1,
-                  T_ref=T_ij_mat[ti, tj], enable=enable, FL=FL, iL=ti, FR=FR, iR=tj)
+    lc = _lc_inputs(sm_params, sm_io, registration, T_ref=T_ij[ti, tj], enable=enable, FL=FL, iL=ti, FR=FR, iR=tj)
     t0 = time.time()
     res = run_lc_batch_ids(registration, batch, lc) if pool_ids is not None else compute(registration, batch, lc)
     timing_list = [(time.time() - t0) / B] * B
 
     # ---- pass 2: the records into the result matrices -------------------------------------------------------
-    lc_edges = _records_into_results(res, ti, tj, nearby, device_edges, clipper_angle_mat, clipper_dist_mat, clipper_num_associations,
-                                     T_ij_hat_mat, associated_objs_mat)
-    return make(lc_edges, timing_list)
+    return M.results(timing_list, _records_into_results(M, res, ti, tj, nearby))
+
+
+def _gate_buffers(torch, dev, n0, n1):
+    """What roman_grid_gate_dev writes for an (n0, n1) grid, on `dev`, in the order of its output arguments: the dense matrices,
+    and the compact list of the pairs to register with the tail's T_ref and enable (room for every pair)."""
+    f64, i32, cap = torch.float64, torch.int32, n0 * n1
+    spec = dict(dist=((n0, n1), f64), flags=((n0, n1), i32), yaw=((n0, n1), f64), sim=((n0, n1), f64), T_ij=((cap, 16), f64),
+                pairs=((cap, 2), i32), T_ref=((cap, 16), f64), enable=((cap,), i32))
+    g = {k: torch.empty(shape, dtype=t, device=dev) for k, (shape, t) in spec.items()}
+    g["n_todo"] = torch.zeros(1, dtype=i32, device=dev)
+    return g
+
+
+class _TailBuffers:
+    """The outputs of B problems over resident pools (issue_chunked) and of the tail behind them (roman_lc_tail_dev), on `dev`."""
+
+    def __init__(self, torch, dev, B, kmax):
+        f64, i32 = torch.float64, torch.int32
+        self.assoc = torch.full((B, kmax, 2), -1, dtype=i32, device=dev); self.n = torch.zeros(B, dtype=i32, device=dev)
+        self.T = torch.zeros((B, 16), dtype=f64, device=dev); self.status = torch.zeros(B, dtype=i32, device=dev)
+        self.records = torch.zeros(B * _abi.LC_RECORD_NBYTES, dtype=torch.uint8, device=dev)
+        self.acc_idx = torch.zeros(B, dtype=i32, device=dev); self.acc_n = torch.zeros(1, dtype=i32, device=dev)
+
+    def result(self, status, dim):
+        """-> runtime.LoopClosureResult on the host (`status`: the final status of every problem, as issue_chunked returns it)."""
+        B, s = int(self.n.shape[0]), dim + 1
+        rec = np.frombuffer(self.records.cpu().numpy().tobytes(), dtype=lc_record_dtype()).copy()
+        n_h, a_h = self.n.cpu().numpy(), self.assoc.cpu().numpy()
+        return LoopClosureResult([a_h[b, :n_h[b]].copy() for b in range(B)], self.T.cpu().numpy()[:, :s * s].reshape(B, s, s).copy(), status,
+                                 np.zeros(B, dtype=stats_dtype()), rec, self.acc_idx.cpu().numpy()[:int(self.acc_n.cpu().numpy()[0])].copy())
 
 
 def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, registration=None, gt_poses=(None, None)) -> SubmapAlignResults:
@@ -592,7 +634,6 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     segment ids (one pool against itself), force_fill_submaps / no submap_radius (the AABB gate), stacked or frame descriptors,
     RansacReg, registration plugins with a host prefilter."""
     import torch
-    from ..runtime import LoopClosureResult, grid_gate_params, lc_record_dtype, stats_dtype
     from .pipeline import issue_chunked
     sm_io = sm_io or SubmapAlignIO()
     registration = registration or sm_params.get_object_registration()
@@ -606,8 +647,7 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes" + way)
     if sm_params.submap_descriptor not in (None, 'mean_semantic'):
         raise ValueError(f"submap_descriptor {sm_params.submap_descriptor!r}: stacked or frame descriptors are not in the pool" + way)
-    scorer = getattr(type(registration), "_associations_to_score", None)
-    if scorer is not None and scorer is not ObjectRegistration._associations_to_score:
+    if _has_host_prefilter(registration):
         raise ValueError("the registration plugin prefilters association lists on the host" + way)
     if sm_params.single_robot_lc:
         shared = p[0] is p[1] or np.intersect1d(p[0].ids[p[0].src >= 0], p[1].ids[p[1].src >= 0]).size > 0
@@ -627,114 +667,70 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     dev = p[0].pool.device
     on_host = dev.type == "cpu"                              # CPU tensors + a stand-in context (tests)
     wait_torch = (lambda: None) if on_host else (lambda: torch.cuda.current_stream(dev).synchronize())
+    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
     keep = [q.nonempty for q in p]                           # [REF roman/map/map.py:341]: the reference drops the empty submaps
     n0, n1 = len(keep[0]), len(keep[1])
-    nan = lambda *s: np.zeros(s) * np.nan
-    clipper_angle_mat, clipper_dist_mat, clipper_num_associations = nan(n0, n1), nan(n0, n1), nan(n0, n1)
-    similarity_mat, robots_nearby_mat, submap_yaw_diff_mat = nan(n0, n1), nan(n0, n1), nan(n0, n1)
-    T_ij_mat, T_ij_hat_mat = nan(n0, n1, 4, 4), nan(n0, n1, 4, 4)
-    associated_objs_mat = [[[] for _ in range(n1)] for _ in range(n0)]
-    total_time_t0 = time.time()
-    make = lambda lc_edges=None, timing_list=(): SubmapAlignResults(
-        robots_nearby_mat=robots_nearby_mat, clipper_angle_mat=clipper_angle_mat, clipper_dist_mat=clipper_dist_mat,
-        clipper_num_associations=clipper_num_associations,
-        similarity_mat=similarity_mat if sm_params.submap_descriptor is not None else None,
-        submap_yaw_diff_mat=submap_yaw_diff_mat, T_ij_mat=T_ij_mat, T_ij_hat_mat=T_ij_hat_mat,
-        associated_objs_mat=associated_objs_mat, timing_list=list(timing_list), submap_align_params=sm_params,
-        submap_io=sm_io, total_time=time.time() - total_time_t0, lc_edges=lc_edges)
-    device_edges = sm_io.lc_association_thresh > 0
-    empty_edges = dict(pairs=np.zeros((0, 2), np.int64), t=np.zeros((0, 3)), q=np.zeros((0, 4))) if device_edges else None
+    M = _GridResults(sm_params, sm_io, n0, n1)
     if n0 == 0 or n1 == 0:
-        return make(empty_edges)
+        return M.results(lc_edges=M.empty_edges())
 
     # ---- per submap, on the host (O(S)): centre, the pose the reference transform is built from, time, the edge frames —
     # through the stand-in Submap's own properties, read as often as the pair loop reads them (submap_align_grid does the same) ----
     other = (n1, n0)
-    pos, pos_gt, T_w, times, frames = [], [], [], [], []
+    side, frames = [], []
     for r in range(2):
         c = p[r].centers
         gt = None if gt_poses[r] is None else np.asarray(gt_poses[r], dtype=np.float64).reshape(len(c), 4, 4)
         sms = [Submap(id=int(s), time=float(c.time[s]), segments=(), pose_flu=np.array(c.pose_flu[s], dtype=np.float64),
                       pose_flu_gt=None if gt is None else gt[s].copy()) for s in keep[r]]
-        pos.append(np.stack([np.array(sm.position) for sm in sms]))
-        pos_gt.append(None if gt is None else np.stack([np.array(sm.position_gt) for sm in sms]))
-        if sm_io.gt_available[r]:
-            T_w.append(np.stack([np.array(_read_times(sm, "pose_gravity_aligned_gt", "pose_flu_gt", other[r]), dtype=np.float64) for sm in sms]))
-        else:
-            T_w.append(np.stack([np.array(_read_times(sm, "pose_gravity_aligned", "pose_flu", other[r]), dtype=np.float64) for sm in sms]))
-        times.append(np.array([sm.time for sm in sms], dtype=np.float64))
+        pos = np.stack([np.array(sm.position) for sm in sms])
+        pos_gt = None if gt is None else np.stack([np.array(sm.position_gt) for sm in sms])
+        read = ("pose_gravity_aligned_gt", "pose_flu_gt") if sm_io.gt_available[r] else ("pose_gravity_aligned", "pose_flu")
+        T_w = np.stack([np.array(_read_times(sm, *read, other[r]), dtype=np.float64) for sm in sms])
+        times = np.array([sm.time for sm in sms], dtype=np.float64)
         frames.append(np.stack([_edge_frames(sm)[r] for sm in sms]))
+        side.append(dict(pos=up(pos), gt=up(pos_gt), T_w=up(T_w.reshape(-1, 16)), time=up(times),
+                         desc=p[r].desc_dev[torch.from_numpy(keep[r].astype(np.int64)).to(dev)].contiguous() if d else None))
 
     # ---- pass 1 on the device: one enqueue, one synchronisation, the pair list and the dense matrices back ----
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    f64, i32 = torch.float64, torch.int32
-    cap = n0 * n1
-    d_in = [dict(pos=up(pos[r]), gt=None if pos_gt[r] is None else up(pos_gt[r]), T_w=up(T_w[r].reshape(-1, 16)), time=up(times[r]),
-                 desc=p[r].desc_dev[torch.from_numpy(keep[r].astype(np.int64)).to(dev)].contiguous() if d else None) for r in range(2)]
-    d_dist = torch.empty((n0, n1), dtype=f64, device=dev); d_yaw = torch.empty((n0, n1), dtype=f64, device=dev)
-    d_sim = torch.empty((n0, n1), dtype=f64, device=dev); d_flags = torch.empty((n0, n1), dtype=i32, device=dev)
-    d_Tij = torch.empty((cap, 16), dtype=f64, device=dev); d_Tref = torch.empty((cap, 16), dtype=f64, device=dev)
-    d_pairs = torch.empty((cap, 2), dtype=i32, device=dev); d_enable = torch.empty(cap, dtype=i32, device=dev)
-    d_ntodo = torch.zeros(1, dtype=i32, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
+    g = _gate_buffers(torch, dev, n0, n1)
     gp = grid_gate_params(sm_params.submap_radius, sm_io.skip_distance, d, sm_params.submap_descriptor_thresh if d else 0.0,
                           sm_params.single_robot_lc, sm_params.single_robot_lc_time_thresh)
     wait_torch()                                             # the uploads are in place before the library's stream reads them
-    ctx.grid_gate_dev(gp, n0, n1, ptr(d_in[0]["pos"]), ptr(d_in[0]["T_w"]), ptr(d_in[1]["pos"]), ptr(d_in[1]["T_w"]),
-                      d_dist.data_ptr(), d_flags.data_ptr(), d_yaw.data_ptr(), d_sim.data_ptr(), d_Tij.data_ptr(),
-                      d_pairs.data_ptr(), d_Tref.data_ptr(), d_enable.data_ptr(), d_ntodo.data_ptr(),
-                      time0_ptr=ptr(d_in[0]["time"]), time1_ptr=ptr(d_in[1]["time"]), desc0_ptr=ptr(d_in[0]["desc"]), desc1_ptr=ptr(d_in[1]["desc"]),
-                      pos_gt0_ptr=ptr(d_in[0]["gt"]), pos_gt1_ptr=ptr(d_in[1]["gt"]))
+    ctx.grid_gate_dev(gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *[t.data_ptr() for t in g.values()],
+                      time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), desc0_ptr=ptr(side[0]["desc"]), desc1_ptr=ptr(side[1]["desc"]),
+                      pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
     ctx.sync()
-    B = int(d_ntodo.cpu().numpy()[0])
-    pairs = d_pairs[:B].cpu().numpy().astype(np.int64)
-    dist, flags, yaw, sim = d_dist.cpu().numpy(), d_flags.cpu().numpy(), d_yaw.cpu().numpy(), d_sim.cpu().numpy()
-    nearby, skip = (flags & _abi.ROMAN_GRID_NEARBY) != 0, (flags & _abi.ROMAN_GRID_SKIP) != 0
-    gated, todo = (flags & _abi.ROMAN_GRID_GATED) != 0, (flags & _abi.ROMAN_GRID_TODO) != 0
-    robots_nearby_mat[nearby] = dist[nearby]
-    T_ij_mat[:] = d_Tij.cpu().numpy().reshape(n0, n1, 4, 4)
-    submap_yaw_diff_mat[nearby] = yaw[nearby]
-    clipper_num_associations[skip] = 0
-    similarity_mat[~skip] = sim[~skip]
-    clipper_num_associations[gated] = 0                  # pairs the descriptor gate stopped: the sentinels of [REF :179-184]
-    clipper_angle_mat[gated & nearby] = np.abs(np.rad2deg(180.0)); clipper_dist_mat[gated & nearby] = 1e6
+    B = int(g["n_todo"].cpu().numpy()[0])
+    pairs = g["pairs"][:B].cpu().numpy().astype(np.int64)
+    h = {k: g[k].cpu().numpy() for k in ("dist", "flags", "yaw", "sim", "T_ij")}
+    flags = h["flags"]
+    nearby, todo = (flags & _abi.ROMAN_GRID_NEARBY) != 0, (flags & _abi.ROMAN_GRID_TODO) != 0
+    M.pass1(h["dist"], nearby, (flags & _abi.ROMAN_GRID_SKIP) != 0, (flags & _abi.ROMAN_GRID_GATED) != 0, h["yaw"], h["sim"],
+            h["T_ij"].reshape(n0, n1, 4, 4))
     if not np.array_equal(pairs, np.stack(np.nonzero(todo), axis=1)):
         raise _abi.RomanHipError("roman_grid_gate_dev: the compact pair list is not the TODO pairs in row-major order")
     if B == 0:
-        return make(empty_edges)
-    ti, tj = pairs[:, 0], pairs[:, 1]
+        return M.results(lc_edges=M.empty_edges())
 
     # ---- the hot path over the resident pools: offsets and counts from the pools, the batch in chunks, then the tail ----
     batch, pool = p[0].grid_batch(p[1], mask=todo)
-    P = registration._abi_params()
     kmax = batch.kmax()
-    a_out = torch.full((B, kmax, 2), -1, dtype=i32, device=dev); n_out = torch.zeros(B, dtype=i32, device=dev)
-    T_out = torch.zeros((B, 16), dtype=f64, device=dev); st_out = torch.zeros(B, dtype=i32, device=dev)
+    o = _TailBuffers(torch, dev, B, kmax)
     FL, FR = up(frames[0].reshape(-1, 16)), up(frames[1].reshape(-1, 16))
-    iL, iR = d_pairs[:B, 0].contiguous(), d_pairs[:B, 1].contiguous()
-    records = torch.zeros(B * _abi.LC_RECORD_NBYTES, dtype=torch.uint8, device=dev)
-    acc_idx = torch.zeros(B, dtype=i32, device=dev); acc_n = torch.zeros(1, dtype=i32, device=dev)
-    lp = LcInputs(dim=sm_params.dim, force_rm_upside_down=sm_params.force_rm_upside_down,
-                  force_rm_lc_roll_pitch=sm_params.force_rm_lc_roll_pitch,
-                  tilt_thresh=registration.roll_pitch_thresh if getattr(registration, "use_gravity", False) else None,
-                  lc_association_thresh=int(np.ceil(sm_io.lc_association_thresh)) if device_edges else 1).params()
+    iL, iR = g["pairs"][:B, 0].contiguous(), g["pairs"][:B, 1].contiguous()
+    lp = _lc_inputs(sm_params, sm_io, registration).params()
     wait_torch()                                             # the pool (torch.cat), the cleared outputs and the frames are in place
     t0 = time.time()
-    status = issue_chunked(ctx, P, pool, batch, kmax, a_out, n_out, T_out, st_out)     # re-issues skipped problems, then synchronises:
+    status = issue_chunked(ctx, registration._abi_params(), pool, batch, kmax, o.assoc, o.n, o.T, o.status)   # re-issues skipped problems, then synchronises:
     ctx.join()                                               # ... the tail below sees the FINAL attempt of every problem only
-    ctx.lc_tail_dev(lp, B, T_out.data_ptr(), n_out.data_ptr(), st_out.data_ptr(), records.data_ptr(), acc_idx.data_ptr(), acc_n.data_ptr(),
-                    T_ref_ptr=d_Tref.data_ptr(), enable_ptr=d_enable.data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
+    ctx.lc_tail_dev(lp, B, o.T.data_ptr(), o.n.data_ptr(), o.status.data_ptr(), o.records.data_ptr(), o.acc_idx.data_ptr(), o.acc_n.data_ptr(),
+                    T_ref_ptr=g["T_ref"].data_ptr(), enable_ptr=g["enable"].data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
                     FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr())
     ctx.sync()
     timing_list = [(time.time() - t0) / B] * B
-    rec = np.frombuffer(records.cpu().numpy().tobytes(), dtype=lc_record_dtype()).copy()
-    n_h, a_h = n_out.cpu().numpy(), a_out.cpu().numpy()
-    s = sm_params.dim + 1
-    res = LoopClosureResult([a_h[b, :n_h[b]].copy() for b in range(B)], T_out.cpu().numpy()[:, :s * s].reshape(B, s, s).copy(), status,
-                            np.zeros(B, dtype=stats_dtype()), rec, acc_idx.cpu().numpy()[:int(acc_n.cpu().numpy()[0])].copy())
-    lc_edges = _records_into_results(res, ti, tj, nearby, device_edges, clipper_angle_mat, clipper_dist_mat, clipper_num_associations,
-                                     T_ij_hat_mat, associated_objs_mat)
-    return make(lc_edges, timing_list)
+    return M.results(timing_list, _records_into_results(M, o.result(status, sm_params.dim), pairs[:, 0], pairs[:, 1], nearby))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -779,14 +775,7 @@ def _device_edges(results, submaps):
     for r in range(2):
         ks, counts = np.unique(pairs[:, r], return_counts=True)
         for k, n in zip(ks.tolist(), counts.tolist()):
-            sm = submaps[r][k]
-            before = np.array(sm.pose_flu, dtype=np.float64).tobytes()
-            for _ in range(n):                           # (stops at the fixed point a yaw-only pose is)
-                sm.pose_gravity_aligned
-                now = np.array(sm.pose_flu, dtype=np.float64).tobytes()
-                if now == before:
-                    break
-                before = now
+            _read_times(submaps[r][k], "pose_gravity_aligned", "pose_flu", n)      # (stops at the fixed point a yaw-only pose is)
     T = np.tile(np.eye(4), (pairs.shape[0], 1, 1))
     T[:, :3, :3] = _quat_to_matrix(q); T[:, :3, 3] = t
     return [(int(pairs[k, 0]), int(pairs[k, 1]), T[k], t[k].copy(), q[k].copy()) for k in range(pairs.shape[0])]
