@@ -664,7 +664,9 @@ ROMAN_API int roman_ransac_batch(roman_ctx_t* ctx, const roman_ransac_params_t* 
    rows in the submap's gravity-aligned frame — the feature pool the batch calls consume, in fixed slots of `cap` rows per
    submap (submap s owns rows [s*cap, s*cap + count[s])), so offsets are known before the call.  DESIGN.md §4.8 is the contract.
    The centres themselves come from a sequential scan of the trajectory [REF :300-309], which stays on the host
-   (roman_amd.align.submaps.submap_centers), as does the force_fill_submaps mode [REF :264-295] (slices of a time-sorted list). */
+   (roman_amd.align.submaps.submap_centers), as does the force_fill_submaps mode [REF :264-295] (slices of a time-sorted list).
+   The frame-descriptor modes of submap_descriptor [REF :348-355] run behind this call on the same stream: roman_frame_select_dev
+   below reads the count and src it wrote. */
 typedef struct roman_submap_params {
     int32_t point_dim;       /* 2 or 3: leading centre components an output row keeps (the input row always carries x y z)        */
     int32_t max_size;        /* SubmapParams.max_size [REF roman/map/map.py:332-339]; <= 0: None (no sort, rows in map order)     */
@@ -725,6 +727,77 @@ ROMAN_API int roman_submaps(roman_ctx_t* ctx, const roman_submap_params_t* spara
                             int32_t desc_dim, double* desc_out);
 
 /* ------------------------------------------------------------------------------------------- */
+/* frame descriptors of the submaps of a pool                                                  */
+/* ------------------------------------------------------------------------------------------- */
+
+/* extract_submap_descriptors [REF roman/map/map.py:210-242] for all S submaps of one pool in one enqueue: which of the map's Nf
+   frames every submap holds ('stacked_frame_descriptors', with and without frame_descriptor_dist) and their mean
+   ('mean_frame_descriptor').  DESIGN.md §4.10 is the contract. */
+typedef struct roman_frame_select_params {
+    int32_t thin;            /* 0/1: SubmapParams.frame_descriptor_dist is set [REF roman/map/map.py:226-242]                     */
+    int32_t want_mean;       /* 0/1: write `mean` [REF :216-219]                                                                  */
+    double  thin_dist;       /* frame_descriptor_dist (read only with thin); NaN or < 0: ROMAN_E_INVALID                          */
+    int32_t reserved[2];     /* must be 0                                                                                         */
+} roman_frame_select_params_t;
+
+/*
+ * roman_frame_select_dev: every pointer DEVICE; a PURE ENQUEUE on the context's stream, complete once that stream is synchronised.
+ *   count      int32[S], src int32[S*cap]: as roman_submaps_dev wrote them (rows [s*cap, s*cap + count[s]) are map indices < N)
+ *   seg_times  float64[N][2]: first_seen, last_seen of the map table
+ *   frame_times float64[Nf]; frame_pos float64[Nf][3] (trajectory pose[:3,3]; read only with thin, may be NULL without);
+ *   frame_desc float64[Nf][d] (read only with want_mean, may be NULL without)
+ * Per submap s: span[s] = (min first_seen, max last_seen) over the rows the submap keeps — after the prune, as Submap.first_seen /
+ * last_seen read them [REF :125-131]; frame f is a candidate when span lo <= frame_times[f] <= span hi [REF :218]; frame order is
+ * index order, times need not be sorted.  Without thin every candidate is selected.  With thin the candidates are walked in
+ * ascending index: the first is selected, each later one when sqrt((dx^2 + dy^2) + dz^2) to the LAST SELECTED candidate is
+ * >= thin_dist [REF :236-240] (no fused multiply-adds).
+ *   mask       uint64[S][W], W = ceil(Nf / 64): bit f % 64 of word f / 64; whole words are written, zero where nothing is selected
+ *   n_sel      int32[S]
+ *   span       float64[S][2]; an empty submap (count 0): n_sel 0, span (+inf, -inf)
+ *   mean       float64[S][d] with want_mean: the selected rows added in ascending frame index, then divided by n_sel
+ *              (descriptors_np[frame_mask].mean(axis=0) [REF :219]); a fixed order: two calls agree bit for bit; 0 / 0 = NaN for n_sel 0
+ * S == 0 and Nf == 0 are legal.  Errors: a NULL pointer that is needed, negative sizes, cap < 1, thin_dist NaN or < 0 with thin,
+ * want_mean with d < 1 or frame_desc NULL, reserved words not 0 -> ROMAN_E_INVALID.
+ */
+ROMAN_API int roman_frame_select_dev(roman_ctx_t* ctx, const roman_frame_select_params_t* fparams, int32_t S, int32_t cap,
+                                     const int32_t* count, const int32_t* src, int32_t N, const double* seg_times,
+                                     int32_t Nf, const double* frame_times, const double* frame_pos, int32_t d, const double* frame_desc,
+                                     uint64_t* mask, int32_t* n_sel, double* span, double* mean);
+
+/* The same with HOST pointers everywhere.  Synchronous: copies in, runs roman_frame_select_dev, brings mask, n_sel, span and mean back. */
+ROMAN_API int roman_frame_select(roman_ctx_t* ctx, const roman_frame_select_params_t* fparams, int32_t S, int32_t cap,
+                                 const int32_t* count, const int32_t* src, int32_t N, const double* seg_times,
+                                 int32_t Nf, const double* frame_times, const double* frame_pos, int32_t d, const double* frame_desc,
+                                 uint64_t* mask, int32_t* n_sel, double* span, double* mean);
+
+/*
+ * roman_stacked_sim_dev: Submap.similarity for 2-D (stacked) descriptors [REF roman/map/map.py:155-162] for every pair of an
+ * S0 x S1 grid, from the two maps' frame tables and the masks roman_frame_select_dev wrote.  Every pointer DEVICE; a PURE ENQUEUE
+ * on the context's stream.
+ *   desc_r     float64[Nf_r][d]: the frame descriptors of map r;  mask_r  uint64[S_r][ceil(Nf_r / 64)]
+ *   sim[i * S1 + j] = max over a in mask0[i], b in mask1[j] of c(a, b);   c(a, b) = 0 when |a| |b| <= 1e-9, dot(a, b) / (|a| |b|) otherwise
+ * Every DISTINCT frame pair is contracted once (f64 matrix core), whatever number of submaps hold it; the norms are computed once
+ * per frame.  The maximum is taken in two exact stages (R[i][b] = max over a in mask0[i] of c(a, b), then the maximum over
+ * b in mask1[j]), without floating-point atomics.  max of finite doubles is exact and order-free; the only rounding is inside c,
+ * whose d-long sums have a fixed order: two calls agree bit for bit, whatever the band height.  The frame-cosine matrix goes in row
+ * BANDS of map 0's frames through a workspace the context owns (roman_ctx_set_stacked_band), sized once per call; a failed
+ * allocation returns ROMAN_E_NOMEM, nothing is enqueued and the context stays usable.
+ * An empty mask on either side gives -inf (the maximum over nothing).  Descriptors must be finite: the effect of a NaN is
+ * unspecified.  S0 == 0, S1 == 0 or an Nf of 0 are legal: nothing is written, or -inf where a pair exists.
+ * Errors: d < 1, negative sizes, a NULL pointer that is needed -> ROMAN_E_INVALID; S0 * S1 beyond int32 -> ROMAN_E_TOO_LARGE.
+ */
+ROMAN_API int roman_stacked_sim_dev(roman_ctx_t* ctx, int32_t d, int32_t Nf0, const double* desc0, int32_t S0, const uint64_t* mask0,
+                                    int32_t Nf1, const double* desc1, int32_t S1, const uint64_t* mask1, double* sim);
+
+/* The same with HOST pointers everywhere.  Synchronous. */
+ROMAN_API int roman_stacked_sim(roman_ctx_t* ctx, int32_t d, int32_t Nf0, const double* desc0, int32_t S0, const uint64_t* mask0,
+                                int32_t Nf1, const double* desc1, int32_t S1, const uint64_t* mask1, double* sim);
+
+/* Rows of map 0's frames one band of roman_stacked_sim* takes: 0 (the default) sizes the band workspace to at most 64 MiB; any
+   other value is rounded up to a multiple of 32, the smallest band.  The result does not depend on it. */
+ROMAN_API int roman_ctx_set_stacked_band(roman_ctx_t* ctx, int32_t rows);
+
+/* ------------------------------------------------------------------------------------------- */
 /* pass 1 of the pair loop over a whole grid of submaps (radius mode)                          */
 /* ------------------------------------------------------------------------------------------- */
 
@@ -733,7 +806,8 @@ ROMAN_API int roman_submaps(roman_ctx_t* ctx, const roman_submap_params_t* spara
    reference transform T_ij and its yaw, the cosine of the two submap descriptors [REF roman/map/map.py:144-153], skip_distance
    [REF :136] and the descriptor threshold [REF :144-149] — and the pairs that go on to register(), compacted in the order of
    the reference's loop with what the loop-closure tail needs for each (roman_lc_tail_dev's T_ref and enable).  Radius mode,
-   vector (1-D) descriptors or none; the AABB mode (force_fill_submaps / no radius), stacked frame descriptors and the
+   vector (1-D) descriptors — mean_semantic, or the means roman_frame_select_dev wrote — or none; stacked frame descriptors go
+   through roman_stacked_sim_dev and roman_grid_gate_sim_dev below.  The AABB mode (force_fill_submaps / no radius) and the
    shared-segment removal of single_robot_lc stay with the caller.  DESIGN.md §4.9 is the contract.  Bits of flags[]: */
 #define ROMAN_GRID_NEARBY  1   /* dist < 2 * radius (strict): robots_nearby_mat holds dist, submap_yaw_diff_mat the yaw [REF :101-103, :127-129] */
 #define ROMAN_GRID_SKIP    2   /* dist > skip_distance [REF :136]: no registration, association count 0                                    */
@@ -794,6 +868,25 @@ ROMAN_API int roman_grid_gate(roman_ctx_t* ctx, const roman_grid_gate_params_t* 
                               const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
                               double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
                               int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo);
+
+/*
+ * roman_grid_gate_sim_dev: roman_grid_gate_dev on a similarity that is already there (roman_stacked_sim_dev's).  The arguments are
+ * roman_grid_gate_dev's without desc0 / desc1;  sim float64[S0*S1] is an INPUT: read, never written.  gparams->desc_dim must be 0
+ * (ROMAN_E_INVALID otherwise).  Everything else is roman_grid_gate_dev's contract: the flags, GATED = !SKIP && sim < desc_thresh,
+ * the compact list of the TODO pairs in row-major order by a prefix sum, T_ref, enable, the untouched slots, the errors.
+ */
+ROMAN_API int roman_grid_gate_sim_dev(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                                      const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0,
+                                      const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1,
+                                      double* dist, int32_t* flags, double* yaw_deg, const double* sim, double* T_ij,
+                                      int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo);
+
+/* The same with HOST pointers everywhere.  Synchronous; sim goes up and is not brought back. */
+ROMAN_API int roman_grid_gate_sim(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                                  const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0,
+                                  const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1,
+                                  double* dist, int32_t* flags, double* yaw_deg, const double* sim, double* T_ij,
+                                  int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo);
 
 /* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */

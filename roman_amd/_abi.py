@@ -12,6 +12,7 @@ ROMAN_MAX_RATIO_FEATURES = 8
 # error codes / status flags (include/roman_hip.h)
 ROMAN_OK = 0
 ROMAN_E_INVALID = -1
+ROMAN_E_NOMEM = -4
 ROMAN_E_UNSUPPORTED = -5
 ROMAN_E_TOO_LARGE = -6
 ROMAN_E_INTERNAL = -7
@@ -244,6 +245,16 @@ class RomanGridGateParams(C.Structure):
     ]
 
 
+class RomanFrameSelectParams(C.Structure):
+    """roman_frame_select_params_t"""
+    _fields_ = [
+        ("thin", C.c_int32),
+        ("want_mean", C.c_int32),
+        ("thin_dist", C.c_double),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
 # flag bits of roman_grid_gate's flags[]
 ROMAN_GRID_NEARBY = 1
 ROMAN_GRID_SKIP = 2
@@ -258,6 +269,8 @@ RANSAC_RECORD_NBYTES = C.sizeof(RomanRansacRecord)
 SUBMAP_PARAMS_NBYTES = C.sizeof(RomanSubmapParams)
 SUBMAP_DESC_NBYTES = C.sizeof(RomanSubmapDesc)
 GRID_GATE_PARAMS_NBYTES = C.sizeof(RomanGridGateParams)
+FRAME_SELECT_PARAMS_NBYTES = C.sizeof(RomanFrameSelectParams)
+STACKED_BAND_MIN = 32       # the smallest row band of roman_stacked_sim* (kernels.hip.h STACK_TILE)
 LC_PARAMS_NBYTES = C.sizeof(RomanLcParams)
 LC_RECORD_NBYTES = C.sizeof(RomanLcRecord)
 PARAMS_NBYTES = C.sizeof(RomanParams)
@@ -328,6 +341,13 @@ def load_library():
         "roman_submaps": (C.c_int, [ctxp, P(RomanSubmapParams), i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp]),
         "roman_grid_gate_dev": (C.c_int, [ctxp, P(RomanGridGateParams), i32, i32] + [vp] * 19),
         "roman_grid_gate": (C.c_int, [ctxp, P(RomanGridGateParams), i32, i32] + [vp] * 19),
+        "roman_grid_gate_sim_dev": (C.c_int, [ctxp, P(RomanGridGateParams), i32, i32] + [vp] * 17),
+        "roman_grid_gate_sim": (C.c_int, [ctxp, P(RomanGridGateParams), i32, i32] + [vp] * 17),
+        "roman_frame_select_dev": (C.c_int, [ctxp, P(RomanFrameSelectParams), i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "roman_frame_select": (C.c_int, [ctxp, P(RomanFrameSelectParams), i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "roman_stacked_sim_dev": (C.c_int, [ctxp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
+        "roman_stacked_sim": (C.c_int, [ctxp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
+        "roman_ctx_set_stacked_band": (C.c_int, [ctxp, i32]),
         "roman_ctx_has_history": (C.c_int, [ctxp, P(RomanParams), i32, P(i32)]),
         "roman_ctx_cosine_screen_stats": (C.c_int, [ctxp, P(C.c_int64), P(C.c_int64), P(C.c_double)]),
         "roman_create_all_to_all": (C.c_int, [i32, i32, vp]),
@@ -362,7 +382,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_submaps_dev", "roman_submaps", "roman_grid_gate_dev", "roman_grid_gate", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_submaps_dev", "roman_submaps", "roman_grid_gate_dev", "roman_grid_gate", "roman_grid_gate_sim_dev", "roman_grid_gate_sim", "roman_frame_select_dev", "roman_frame_select", "roman_stacked_sim_dev", "roman_stacked_sim", "roman_ctx_set_stacked_band", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

@@ -631,8 +631,13 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     submap of that side has ground truth ([REF :96-99]); sm_io.gt_available[r] selects it for the reference transform.
 
     Not covered — ValueError; SubmapPool.to_submaps() + submap_align_grid is the way: single_robot_lc over submaps that share
-    segment ids (one pool against itself), force_fill_submaps / no submap_radius (the AABB gate), stacked or frame descriptors,
-    RansacReg, registration plugins with a host prefilter."""
+    segment ids (one pool against itself), force_fill_submaps / no submap_radius (the AABB gate), RansacReg, registration plugins
+    with a host prefilter.
+
+    Frame descriptors need pools built with them (build_submap_pool(frames=...)): 'mean_frame_descriptor' goes
+    through the same gate as 'mean_semantic'; 'stacked_frame_descriptors' through roman_stacked_sim_dev over the two pools' frame
+    masks — every distinct frame pair contracted once — and roman_grid_gate_sim_dev on that similarity.  similarity_mat is what
+    the device computed."""
     import torch
     from .pipeline import issue_chunked
     sm_io = sm_io or SubmapAlignIO()
@@ -645,8 +650,12 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         raise ValueError("RansacReg has no device tail" + way)
     if sm_params.force_fill_submaps or sm_params.submap_radius is None:
         raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes" + way)
-    if sm_params.submap_descriptor not in (None, 'mean_semantic'):
-        raise ValueError(f"submap_descriptor {sm_params.submap_descriptor!r}: stacked or frame descriptors are not in the pool" + way)
+    mode = sm_params.submap_descriptor
+    stacked = mode == 'stacked_frame_descriptors'
+    if mode not in (None, 'mean_semantic', 'mean_frame_descriptor', 'stacked_frame_descriptors'):
+        raise ValueError(f"submap_descriptor {mode!r} is not one the pools carry" + way)
+    if mode in ('mean_frame_descriptor', 'stacked_frame_descriptors') and any(q.descriptor_mode != mode for q in p):
+        raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool(frames=...) keeps the frame masks on the device)" + way)
     if _has_host_prefilter(registration):
         raise ValueError("the registration plugin prefilters association lists on the host" + way)
     if sm_params.single_robot_lc:
@@ -654,9 +663,12 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         if shared:
             raise ValueError("single_robot_lc over submaps that share segment ids: the shared-segment removal has no device-pointer form yet" + way)
     d = 0
-    if sm_params.submap_descriptor is not None:
+    if stacked:
+        if int(p[0].frame_desc_dev.shape[1]) != int(p[1].frame_desc_dev.shape[1]):
+            raise ValueError("the two pools have frame descriptors of different lengths")
+    elif mode is not None:
         if p[0].desc_dev is None or p[1].desc_dev is None:
-            raise ValueError("submap_descriptor 'mean_semantic' needs pools built with it (build_submap_pool keeps the descriptors on the device)")
+            raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool keeps the descriptors on the device)")
         d = int(p[0].desc_dev.shape[1])
         if int(p[1].desc_dev.shape[1]) != d:
             raise ValueError("the two pools have descriptors of different lengths")
@@ -697,10 +709,20 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     g = _gate_buffers(torch, dev, n0, n1)
     gp = grid_gate_params(sm_params.submap_radius, sm_io.skip_distance, d, sm_params.submap_descriptor_thresh if d else 0.0,
                           sm_params.single_robot_lc, sm_params.single_robot_lc_time_thresh)
+    if stacked:
+        gp.desc_thresh = float(sm_params.submap_descriptor_thresh)
+        masks = [q.frame_mask[torch.from_numpy(k.astype(np.int64)).to(dev)].contiguous() for q, k in zip(p, keep)]     # rows gathered on the device
     wait_torch()                                             # the uploads are in place before the library's stream reads them
-    ctx.grid_gate_dev(gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *[t.data_ptr() for t in g.values()],
-                      time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), desc0_ptr=ptr(side[0]["desc"]), desc1_ptr=ptr(side[1]["desc"]),
-                      pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
+    if stacked:                                              # similarity first, then the gate that reads it: both on the context's stream
+        fd = [q.frame_desc_dev for q in p]
+        ctx.stacked_sim_dev(int(fd[0].shape[1]), int(fd[0].shape[0]), ptr(fd[0]), n0, ptr(masks[0]), int(fd[1].shape[0]), ptr(fd[1]), n1, ptr(masks[1]),
+                            g["sim"].data_ptr())
+        ctx.grid_gate_sim_dev(gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *[t.data_ptr() for t in g.values()],
+                              time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
+    else:
+        ctx.grid_gate_dev(gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *[t.data_ptr() for t in g.values()],
+                          time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), desc0_ptr=ptr(side[0]["desc"]), desc1_ptr=ptr(side[1]["desc"]),
+                          pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
     ctx.sync()
     B = int(g["n_todo"].cpu().numpy()[0])
     pairs = g["pairs"][:B].cpu().numpy().astype(np.int64)

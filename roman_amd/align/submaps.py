@@ -6,6 +6,8 @@ The reference's `submap_align()` first turns each robot's map into submaps with 
 table (`MapTable`), the sequential centre scan [REF :300-309] stays on the host (`submap_centers`, S is small), and one device
 call (`build_submap_pool` -> roman_submaps_dev) produces the feature pool of all submaps in HBM, in fixed slots of `cap` rows per
 submap: exactly what roman_align_batch_dev / roman_align_batch_resident / roman_align_lc_batch_dev consume (`SubmapPool.grid_batch`).
+With a `FrameTable` the frame-descriptor modes [REF roman/map/map.py:210-242] run behind it on the same stream (roman_frame_select_dev,
+DESIGN.md §4.10): which frames every submap holds, as bit masks that stay on the device, and their mean.
 No segment object is copied; `SubmapPool.to_submaps` hands out light views for the host-side callers (`submap_align_grid`, the
 writers).  The force_fill_submaps mode [REF :264-295] is plain slicing of a time-sorted list and is not covered.
 
@@ -17,7 +19,7 @@ from typing import List, Optional
 import numpy as np
 
 from .. import _abi
-from ..runtime import submap_desc_dtype
+from ..runtime import frame_select_params, mask_indices, submap_desc_dtype
 from .batch import AlignmentBatch
 from .submap_align import Submap, transform_rm_roll_pitch
 
@@ -31,6 +33,7 @@ class SubmapParams:
     time_threshold: float = np.inf
     pruning_method: str = 'time'
     submap_descriptor: Optional[str] = None
+    frame_descriptor_dist: Optional[float] = None
 
     @classmethod
     def from_submap_align_params(cls, p):
@@ -39,7 +42,7 @@ class SubmapParams:
             raise ValueError("force_fill_submaps slices a time-sorted list on the host; the device call covers the radius mode")
         return cls(max_size=p.submap_max_size, radius=p.submap_radius, distance=p.submap_center_dist,
                    time_threshold=p.submap_center_time, pruning_method=p.submap_pruning_method,
-                   submap_descriptor=p.submap_descriptor)
+                   submap_descriptor=p.submap_descriptor, frame_descriptor_dist=p.frame_descriptor_dist)
 
 
 @dataclass
@@ -114,6 +117,33 @@ class MapTable:
         return int(self.feats.shape[0])
 
 
+FRAME_MODES = ('mean_frame_descriptor', 'stacked_frame_descriptors')
+
+
+@dataclass
+class FrameTable:
+    """The frames of a whole map, in frame order: what extract_submap_descriptors reads [REF roman/map/map.py:210-214, 228]."""
+    times: np.ndarray            # (Nf,) float64
+    pos: np.ndarray              # (Nf, 3) float64 trajectory pose[:3, 3]
+    desc: np.ndarray             # (Nf, d) float64 frame descriptors
+
+    @classmethod
+    def from_map(cls, trajectory, times, descriptors):
+        """The ROMANMap fields trajectory, times and descriptors (one each per frame)."""
+        t = np.ascontiguousarray(np.asarray(times, dtype=np.float64).reshape(-1))
+        n = t.shape[0]
+        pos = np.ascontiguousarray(np.array([np.asarray(T, dtype=np.float64)[:3, 3] for T in trajectory], dtype=np.float64).reshape(-1, 3))
+        if descriptors is None:
+            raise ValueError("the map has no frame descriptors")      # [REF roman/map/map.py:212]
+        desc = np.ascontiguousarray(np.vstack([np.asarray(x, dtype=np.float64).reshape(1, -1) for x in descriptors])) if n else np.zeros((0, 1))
+        if pos.shape[0] != n or desc.shape[0] != n:
+            raise ValueError("trajectory, times and descriptors must hold one entry per frame")
+        return cls(t, pos, desc)
+
+    def __len__(self):
+        return int(self.times.shape[0])
+
+
 class SegmentView:
     """A segment of the map as a submap holds it: every attribute of the map's segment, the centre in the submap's frame."""
     __slots__ = ("_seg", "centroid")
@@ -145,6 +175,12 @@ class SubmapPool:
     centers: SubmapCenters
     table: MapTable
     desc_dev: Optional[object] = None   # the same descriptors as the call left them on the device: torch tensor (S, d) float64, or None (submap_align_pools reads it)
+    descriptor_mode: Optional[str] = None      # the submap_descriptor the pool was built with
+    # the frame-descriptor modes (build_submap_pool(frames=...)): which of the map's frames every submap holds
+    frames: Optional[FrameTable] = None
+    frame_mask: Optional[object] = None        # torch tensor (S, ceil(Nf / 64)) int64 on the device: bit f % 64 of word f / 64
+    frame_n: Optional[np.ndarray] = None       # (S,) int32 frames selected per submap, host
+    frame_desc_dev: Optional[object] = None    # torch tensor (Nf, d) float64 on the device: the frame table's descriptors
 
     @property
     def nonempty(self):
@@ -185,6 +221,8 @@ class SubmapPool:
         numbers them before it drops the empty ones), time, pose_flu and descriptor.  No segment is copied."""
         cen = self.pool[:, :self.table.point_dim].cpu().numpy()
         out = []
+        stacked = self.descriptor_mode == 'stacked_frame_descriptors'
+        fmask = self.frame_mask.cpu().numpy().view(np.uint64) if stacked else None
         for s in self.nonempty:
             rows = self.src[s, :self.count[s]]
             c = cen[s * self.cap: s * self.cap + self.count[s]]
@@ -193,8 +231,12 @@ class SubmapPool:
                 z = ((T[2, 0] * p[:, 0] + T[2, 1] * p[:, 1]) + T[2, 2] * p[:, 2]) + T[2, 3]
                 c = np.hstack([c, z[:, None]])
             segs = [SegmentView(segments[k], c[r]) for r, k in enumerate(rows)]
+            if stacked:                                                      # the (k, d) stack, frames in index order [REF roman/map/map.py:225, 242]
+                descriptor = self.frames.desc[mask_indices(fmask[s])].copy()
+            else:
+                descriptor = None if self.desc is None else self.desc[s].copy()
             out.append(Submap(id=int(s), time=float(self.centers.time[s]), segments=segs, pose_flu=self.centers.pose_flu[s].copy(),
-                              descriptor=None if self.desc is None else self.desc[s].copy()))
+                              descriptor=descriptor))
         return out
 
 
@@ -212,10 +254,16 @@ def submap_call_params(table: MapTable, params: SubmapParams, cap=None) -> _abi.
     return P
 
 
-def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, params: SubmapParams, ctx=None, device=None, cap=None) -> SubmapPool:
+def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, params: SubmapParams, ctx=None, device=None, cap=None,
+                      frames: Optional[FrameTable] = None) -> SubmapPool:
     """The submaps of `table` around `centers` as a device-resident feature pool: ONE roman_submaps_dev call (membership, prune,
     order, transform, gather, mean_semantic descriptors), then one synchronisation that brings count, src, ids, status and the
-    descriptors to the host.  The table is uploaded here (once per call); the pool never leaves the device."""
+    descriptors to the host.  The table is uploaded here (once per call); the pool never leaves the device.
+
+    `frames` (a FrameTable) serves submap_descriptor 'mean_frame_descriptor' / 'stacked_frame_descriptors' with
+    params.frame_descriptor_dist [REF roman/map/map.py:210-242]: the frame table goes up once, roman_frame_select_dev runs behind
+    roman_submaps_dev on the same stream, and the pool keeps frame_mask, frame_n and frame_desc_dev (the mean mode fills desc /
+    desc_dev as mean_semantic does).  A non-empty submap that selects no frame is a ValueError: the reference fails on it."""
     import torch
     ctx = ctx or registration._context()
     dev = torch.device(device if device is not None else f"cuda:{getattr(ctx, 'device', 0)}")
@@ -227,20 +275,47 @@ def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, par
         if table.desc_dim <= 0:
             raise ValueError("submap_descriptor 'mean_semantic' needs a registration with semantic descriptors")
         d = table.desc_dim
+    elif params.submap_descriptor in FRAME_MODES:
+        if frames is None:
+            raise ValueError(f"submap_descriptor {params.submap_descriptor!r} needs the map's frames: pass frames=FrameTable.from_map(trajectory, times, descriptors)")
     elif params.submap_descriptor is not None:
-        raise ValueError("frame descriptors (mean_frame_descriptor / stacked_frame_descriptors) are extracted on the host")
+        raise ValueError(f"unknown submap_descriptor {params.submap_descriptor!r}")
+    framed = params.submap_descriptor in FRAME_MODES
+    mean_frames = params.submap_descriptor == 'mean_frame_descriptor'
+    if mean_frames:
+        d = int(frames.desc.shape[1])
     Fo, rows = P.point_dim + F - 3, S * P.cap
     feats = torch.from_numpy(table.feats).to(dev); times = torch.from_numpy(table.times).to(dev); ids = torch.from_numpy(table.ids).to(dev)
     pool = torch.zeros((rows, Fo), dtype=torch.float64, device=dev)
     count = torch.zeros(max(S, 1), dtype=torch.int32, device=dev); status = torch.zeros(max(S, 1), dtype=torch.int32, device=dev)
     src = torch.full((max(rows, 1),), -1, dtype=torch.int32, device=dev); ids_out = torch.full((max(rows, 1),), -1, dtype=torch.int64, device=dev)
     desc = torch.full((max(S, 1), max(d, 1)), float("nan"), dtype=torch.float64, device=dev)
+    if framed:
+        Nf, W = len(frames), (len(frames) + 63) // 64
+        thin = params.frame_descriptor_dist if params.submap_descriptor == 'stacked_frame_descriptors' else None      # [REF roman/map/map.py:216-226]
+        f_times = torch.from_numpy(frames.times).to(dev); f_pos = torch.from_numpy(frames.pos).to(dev); f_desc = torch.from_numpy(frames.desc).to(dev)
+        f_mask = torch.zeros((max(S, 1), max(W, 1)), dtype=torch.int64, device=dev)
+        f_n = torch.zeros(max(S, 1), dtype=torch.int32, device=dev); f_span = torch.zeros((max(S, 1), 2), dtype=torch.float64, device=dev)
     if not on_host:
         torch.cuda.current_stream(dev).synchronize()                         # inputs and cleared outputs are in place before the library's stream touches them
     ctx.submaps_dev(P, N, F, feats.data_ptr(), times.data_ptr(), centers.descs(), pool.data_ptr(), count.data_ptr(), src.data_ptr(),
-                    status.data_ptr(), seg_ids_ptr=ids.data_ptr(), ids_out_ptr=ids_out.data_ptr(), desc_dim=d,
-                    desc_out_ptr=desc.data_ptr() if d else None)
+                    status.data_ptr(), seg_ids_ptr=ids.data_ptr(), ids_out_ptr=ids_out.data_ptr(), desc_dim=0 if framed else d,
+                    desc_out_ptr=desc.data_ptr() if d and not framed else None)
+    if framed and S:                                                         # behind it on the same stream: reads the count and src it wrote
+        ctx.frame_select_dev(frame_select_params(thin, mean_frames), S, P.cap, count.data_ptr(), src.data_ptr(), N, times.data_ptr(), Nf,
+                             f_times.data_ptr(), f_mask.data_ptr(), f_n.data_ptr(), f_span.data_ptr(), frame_pos_ptr=f_pos.data_ptr(),
+                             d=int(frames.desc.shape[1]), frame_desc_ptr=f_desc.data_ptr(), mean_ptr=desc.data_ptr() if mean_frames else None)
     ctx.sync()
-    return SubmapPool(pool, int(P.cap), count.cpu().numpy()[:S].copy(), src.cpu().numpy()[:rows].reshape(S, P.cap).copy(),
+    count_h = count.cpu().numpy()[:S].copy()
+    extra = {}
+    if framed:
+        n_h = f_n.cpu().numpy()[:S].copy()
+        bad = np.nonzero((count_h > 0) & (n_h == 0))[0]
+        if len(bad):
+            raise ValueError(f"submap {int(bad[0])} holds {int(count_h[bad[0]])} segments but no frame of the map lies in its time span: "
+                             "the reference cannot build its frame descriptor")
+        extra = dict(frames=frames, frame_mask=f_mask[:S, :W], frame_n=n_h, frame_desc_dev=f_desc)
+    return SubmapPool(pool, int(P.cap), count_h, src.cpu().numpy()[:rows].reshape(S, P.cap).copy(),
                       ids_out.cpu().numpy()[:rows].reshape(S, P.cap).copy(), status.cpu().numpy()[:S].copy(),
-                      desc.cpu().numpy()[:S, :d].copy() if d else None, centers, table, desc_dev=desc[:S, :d] if d else None)
+                      desc.cpu().numpy()[:S, :d].copy() if d else None, centers, table, desc_dev=desc[:S, :d] if d else None,
+                      descriptor_mode=params.submap_descriptor, **extra)

@@ -7355,6 +7355,8 @@ __global__ void __launch_bounds__(256) k_grid_norms(int S0, int S1, int d, const
     if (lane == 0) norm[w] = sqrt(s);
 }
 
+// SIM_IN (roman_grid_gate_sim*): the similarity of every pair is already in out.sim — read, never written — and no descriptor is touched
+template <bool SIM_IN>
 __global__ void __launch_bounds__(256) k_grid_gate(roman_grid_gate_params_t P, int S0, int S1, GridSide a, GridSide b,
                                                    const double* __restrict__ norm, GridOut out)
 {
@@ -7363,7 +7365,7 @@ __global__ void __launch_bounds__(256) k_grid_gate(roman_grid_gate_params_t P, i
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= (int64_t)S0 * nT) return;                           // (wave-uniform)
     const int i = (int)(w / nT), j0 = (int)(w % nT) * GRID_TJ;
-    const int d = P.desc_dim;
+    const int d = SIM_IN ? 0 : P.desc_dim;
     double acc[GRID_TJ];
 #pragma unroll
     for (int t = 0; t < GRID_TJ; ++t) acc[t] = 0.0;
@@ -7397,14 +7399,16 @@ __global__ void __launch_bounds__(256) k_grid_gate(roman_grid_gate_params_t P, i
     lc_mul4(Ti, b.T_w + 16 * (int64_t)j, T);
     const double yaw = nearby ? fabs(atan2(T[4], T[0]) * (180.0 / 3.141592653589793)) : d_nan();    // |np.rad2deg(yaw)|
     double sim = INFINITY;
-    if (d > 0) {
+    if (SIM_IN) sim = out.sim[p];
+    else if (d > 0) {
         const double np_ = norm[i] * norm[S0 + j];
         sim = (np_ <= 1e-9) ? 0.0 : dot / np_;                   // np.isclose(norm_prod, 0, atol=1e-9, rtol=0) [REF roman/map/map.py:151-153]
     }
     const bool skip = dist > P.skip_distance;                    // [REF :136]
     const bool gated = !skip && sim < P.desc_thresh;
     const bool todo = !skip && !gated;
-    out.dist[p] = dist; out.yaw_deg[p] = yaw; out.sim[p] = sim;
+    out.dist[p] = dist; out.yaw_deg[p] = yaw;
+    if (!SIM_IN) out.sim[p] = sim;
     out.flags[p] = (nearby ? GRID_NEARBY : 0) | (skip ? GRID_SKIP : 0) | (gated ? GRID_GATED : 0) | (todo ? GRID_TODO : 0);
     double* To = out.T_ij + 16 * p;
 #pragma unroll
@@ -7437,6 +7441,216 @@ __global__ void __launch_bounds__(256) k_grid_fill(roman_grid_gate_params_t P, i
     const int i = pairs[2 * s], j = pairs[2 * s + 1];
     T_ref[16 * s + e] = T_ij[16 * ((int64_t)i * S1 + j) + e];
     if (e == 0) enable[s] = (P.single_robot_lc && fabs(time0[i] - time1[j]) < P.lc_time_thresh) ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Frame-descriptor submaps ([REF roman/map/map.py:210-242], [REF :155-162]): which frames of a map every submap of
+// a pool holds, their mean, and the stacked similarity of a whole grid from the two maps' frame tables.
+//   k_frame_select   ONE WAVE per submap.  The span (min first_seen, max last_seen over the rows the submap keeps) by a lane-strided
+//                    sweep and a butterfly; then the frames in words of 64: the candidate test (lo <= t <= hi) in every lane, a
+//                    ballot is the mask word.  Thinning walks the set bits of the word in ascending order — a wave-uniform loop;
+//                    the candidate's position comes from its lane by a shuffle, the last selected position is carried in
+//                    (uniform) registers across words.  Distance sqrt((dx^2 + dy^2) + dz^2), no fused multiply-adds;
+//   k_frame_mean     a thread per descriptor column adds the selected rows in ascending frame index (k_submap_desc's idiom);
+//   k_stacked_band   a wave per 32 x 32 tile of the frame-cosine matrix of one row BAND of map 0 against all frames of map 1:
+//                    2 x 2 blocks of v_mfma_f64_16x16x4, operands straight from global memory with 32-byte loads, k_cos's
+//                    contraction order (chunks of 16 ascending, step t contracts k = k0 + 4 * (lane >> 4) + t); the epilogue
+//                    divides by the norms (k_grid_norms, once per frame) with the reference's zero guard;
+//   k_stacked_colmax R[i][b] = max(R[i][b], max over the band's frames a in mask0[i] of c(a, b)): a thread per (i, b) owns its
+//                    element alone, walks the (uniform) set bits of the band, reads coalesced along b.  No atomics;
+//   k_stacked_rowmax sim[i][j] = max over b in mask1[j] of R[i][b]: a wave per pair, coalesced along b, a butterfly of maxima.
+// max of finite doubles is exact and order-free: the only rounding is inside c, whose sums have a fixed order.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double wave_min_all(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmin(v, __shfl_xor(v, off));
+    return v;
+}
+__device__ __forceinline__ double wave_max_all(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    return v;
+}
+
+__global__ void __launch_bounds__(256) k_frame_select(roman_frame_select_params_t P, int S, int cap, const int32_t* __restrict__ count,
+                                                      const int32_t* __restrict__ src, int N, const double* __restrict__ seg_times,
+                                                      int Nf, const double* __restrict__ frame_times, const double* __restrict__ frame_pos,
+                                                      unsigned long long* __restrict__ mask, int32_t* __restrict__ n_sel, double* __restrict__ span)
+{
+    const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= S) return;                                          // (wave-uniform)
+    const int n = min(count[s], cap), W = (Nf + 63) >> 6;
+    double lo = INFINITY, hi = -INFINITY;
+    for (int r = lane; r < n; r += 64) {
+        const int64_t k = src[(int64_t)s * cap + r];
+        if (k < 0 || k >= N) continue;                           // (not what roman_submaps_dev writes: never read out of the table)
+        lo = fmin(lo, seg_times[2 * k]); hi = fmax(hi, seg_times[2 * k + 1]);
+    }
+    lo = wave_min_all(lo); hi = wave_max_all(hi);
+    double lx = 0.0, ly = 0.0, lz = 0.0;                         // the last selected candidate (uniform)
+    bool have = false;
+    int total = 0;
+    for (int w = 0; w < W; ++w) {
+        const int f = 64 * w + lane;
+        bool cand = false;
+        double px = 0.0, py = 0.0, pz = 0.0;
+        if (f < Nf) {
+            const double t = frame_times[f];
+            cand = lo <= t && t <= hi;
+            if (P.thin && cand) { px = frame_pos[3 * (int64_t)f]; py = frame_pos[3 * (int64_t)f + 1]; pz = frame_pos[3 * (int64_t)f + 2]; }
+        }
+        unsigned long long m = __ballot(cand), sel = m;
+        if (P.thin) {
+            sel = 0ull;
+            while (m) {                                          // (uniform) ascending frame index [REF :236-240]
+                const int t = __ffsll((long long)m) - 1;
+                m &= m - 1ull;
+                const double x = __shfl(px, t), y = __shfl(py, t), z = __shfl(pz, t);
+                bool take = !have;
+                if (have) {
+                    const double dx = x - lx, dy = y - ly, dz = z - lz;
+                    take = sqrt((dx * dx + dy * dy) + dz * dz) >= P.thin_dist;
+                }
+                if (take) { sel |= 1ull << t; lx = x; ly = y; lz = z; have = true; }
+            }
+        }
+        if (lane == 0) mask[(int64_t)s * W + w] = sel;
+        total += __popcll(sel);
+    }
+    if (lane == 0) { n_sel[s] = total; span[2 * (int64_t)s] = lo; span[2 * (int64_t)s + 1] = hi; }
+}
+
+// grid (submaps, column groups): mean[s][c] = (sum over the selected frames of submap s, ascending, of column c) / n_sel
+__global__ void __launch_bounds__(256) k_frame_mean(int Nf, int d, const double* __restrict__ frame_desc, const unsigned long long* __restrict__ mask,
+                                                    const int32_t* __restrict__ n_sel, double* __restrict__ mean)
+{
+    const int s = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
+    if (c >= d) return;
+    const int W = (Nf + 63) >> 6;
+    double acc = 0.0;
+    for (int w = 0; w < W; ++w) {
+        unsigned long long bits = mask[(int64_t)s * W + w];      // (uniform)
+        while (bits) {
+            const int t = __ffsll((long long)bits) - 1;
+            bits &= bits - 1ull;
+            acc += frame_desc[(int64_t)(64 * w + t) * d + c];
+        }
+    }
+    mean[(int64_t)s * d + c] = acc / (double)n_sel[s];          // 0 / 0 = NaN for a submap that selects nothing, as NumPy gives
+}
+
+__global__ void __launch_bounds__(256) k_fill_f64(int64_t n, double v, double* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = v;
+}
+
+constexpr int STACK_TILE = 32;                                   // rows and columns of the frame-cosine matrix a wave of k_stacked_band owns
+
+// rows [a0, a0 + H) of map 0 (a0 + H <= Nf0) against the Nf1 frames of map 1 -> Cb[H][Nf1]
+__global__ void __launch_bounds__(256) k_stacked_band(int d, int a0, int H, int Nf1, const double* __restrict__ desc0, const double* __restrict__ desc1,
+                                                      const double* __restrict__ norm0, const double* __restrict__ norm1, double* __restrict__ Cb)
+{
+    const int nty = (Nf1 + STACK_TILE - 1) / STACK_TILE, ntx = (H + STACK_TILE - 1) / STACK_TILE;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= (int64_t)ntx * nty) return;                         // (wave-uniform)
+    const int xt = (int)(w / nty), yt = (int)(w % nty);
+    const int lane = threadIdx.x & 63, lr = lane & 15, kq = lane >> 4;
+    const double* fa[2]; const double* fb[2]; bool va[2], vb[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int ia = STACK_TILE * xt + 16 * h + lr, jb = STACK_TILE * yt + 16 * h + lr;
+        va[h] = ia < H; vb[h] = jb < Nf1;
+        fa[h] = desc0 + (int64_t)(a0 + (va[h] ? ia : 0)) * d + 4 * kq;      // (an invalid row reads the band's first: in bounds, multiplied as 0)
+        fb[h] = desc1 + (int64_t)(vb[h] ? jb : 0) * d + 4 * kq;
+    }
+    double4_t acc[2][2];
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[x][y] = double4_t{0.0, 0.0, 0.0, 0.0};
+    const int nfull = d >> 4;
+    for (int c = 0; c < nfull; ++c) {
+        d4u_t ra[2], rb[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) { ra[h] = *reinterpret_cast<const d4u_t*>(fa[h] + 16 * c); rb[h] = *reinterpret_cast<const d4u_t*>(fb[h] + 16 * c); }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 2; ++y)
+                    acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[x] ? ra[x].v[t] : 0.0, vb[y] ? rb[y].v[t] : 0.0, acc[x][y], 0, 0, 0);
+    }
+    const int k0 = 16 * nfull;
+    if (k0 < d) {                                                // ragged tail of the descriptor (< 16 elements)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const bool vk = k0 + 4 * kq + t < d;
+            double av[2], bv[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) { av[h] = (va[h] && vk) ? fa[h][k0 + t] : 0.0; bv[h] = (vb[h] && vk) ? fb[h][k0 + t] : 0.0; }
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 2; ++y) acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[x], bv[y], acc[x][y], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+        const int col = STACK_TILE * yt + 16 * y + lr;
+        const double nb = col < Nf1 ? norm1[col] : 0.0;
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = STACK_TILE * xt + 16 * x + kq + 4 * r;
+                if (row < H && col < Nf1) {
+                    const double np_ = norm0[a0 + row] * nb;
+                    Cb[(int64_t)row * Nf1 + col] = (np_ <= 1e-9) ? 0.0 : acc[x][y][r] / np_;       // [REF roman/map/map.py:159-161]
+                }
+            }
+    }
+}
+
+// nbx workgroups per submap i; `first`: the band opens R (nothing is read)
+__global__ void __launch_bounds__(256) k_stacked_colmax(int nbx, int W0, int a0, int H, int Nf1, int first, const unsigned long long* __restrict__ mask0,
+                                                        const double* __restrict__ Cb, double* __restrict__ R)
+{
+    const int i = blockIdx.x / nbx, b = (blockIdx.x % nbx) * 256 + threadIdx.x;
+    if (b >= Nf1) return;
+    double m = first ? -INFINITY : R[(int64_t)i * Nf1 + b];
+    for (int w = a0 >> 6; w <= (a0 + H - 1) >> 6; ++w) {
+        unsigned long long bits = mask0[(int64_t)i * W0 + w];    // (uniform); clipped to the band's frames
+        const int lo = max(a0 - 64 * w, 0), hi = min(a0 + H - 64 * w, 64);
+        if (lo > 0) bits &= ~0ull << lo;
+        if (hi < 64) bits &= (1ull << hi) - 1ull;
+        while (bits) {
+            const int t = __ffsll((long long)bits) - 1;
+            bits &= bits - 1ull;
+            m = fmax(m, Cb[(int64_t)(64 * w + t - a0) * Nf1 + b]);
+        }
+    }
+    R[(int64_t)i * Nf1 + b] = m;
+}
+
+__global__ void __launch_bounds__(256) k_stacked_rowmax(int S0, int S1, int W1, int Nf1, const unsigned long long* __restrict__ mask1,
+                                                        const double* __restrict__ R, double* __restrict__ sim)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= (int64_t)S0 * S1) return;                           // (wave-uniform)
+    const int i = (int)(p / S1), j = (int)(p % S1);
+    double m = -INFINITY;
+    for (int w = 0; w < W1; ++w) {
+        const unsigned long long bits = mask1[(int64_t)j * W1 + w];      // (uniform)
+        const int b = 64 * w + lane;
+        if (((bits >> lane) & 1ull) && b < Nf1) m = fmax(m, R[(int64_t)i * Nf1 + b]);
+    }
+    m = wave_max_all(m);
+    if (lane == 0) sim[p] = m;
 }
 
 // elementwise math probe for tests

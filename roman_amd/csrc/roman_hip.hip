@@ -178,6 +178,11 @@ struct roman_ctx {
     // pass 1 of a grid (roman_grid_gate*): the descriptor norms of both sides, and the host-pointer call's arrays on the device
     DevBuf ggNorm, ggHost;
 
+    // frame descriptors (roman_frame_select* / roman_stacked_sim*): the frame norms of both maps, one row band of the frame-cosine
+    // matrix, the column maxima R, and the host-pointer calls' arrays on the device
+    DevBuf fsHost, ssNorm, ssBand, ssR, ssHost;
+    int stacked_band = 0;                      // rows per band (roman_ctx_set_stacked_band); 0: automatic
+
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
     bool profile = false;
@@ -1442,6 +1447,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx, &c->smHost}; for (DevBuf* b : sm) b->release(); }
     c->smStage.release();
     c->ggNorm.release(); c->ggHost.release();
+    c->fsHost.release(); c->ssNorm.release(); c->ssBand.release(); c->ssR.release(); c->ssHost.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -2589,9 +2595,10 @@ static int grid_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int3
                            const void* pos0, const void* T_w0, const void* time0, const void* desc0,
                            const void* pos1, const void* T_w1, const void* time1, const void* desc1,
                            const void* dist, const void* flags, const void* yaw_deg, const void* sim, const void* T_ij,
-                           const void* pairs, const void* T_ref, const void* enable, const void* n_todo)
+                           const void* pairs, const void* T_ref, const void* enable, const void* n_todo, bool sim_in = false)
 {
     if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
+    if (sim_in && P->desc_dim != 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d: the similarity is given, desc_dim must be 0", P->desc_dim);
     if (S0 < 0 || S1 < 0) return fail(c, ROMAN_E_INVALID, "S0 < 0 or S1 < 0");
     if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
         return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
@@ -2608,14 +2615,15 @@ static int grid_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int3
     return ROMAN_OK;
 }
 
-int roman_grid_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
-                        const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
-                        const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
-                        double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                        int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
+// the device-pointer gate; sim_in: `sim` holds every pair's similarity already (roman_grid_gate_sim_dev) and is only read
+static int grid_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                         const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                         const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                         double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                         int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo, bool sim_in)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo);
+    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo, sim_in);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t stream = c->stream;
@@ -2627,7 +2635,8 @@ int roman_grid_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams,
     const GridSide a{pos0, pos_gt0, T_w0, time0, desc0}, b{pos1, pos_gt1, T_w1, time1, desc1};
     const GridOut out{dist, flags, yaw_deg, sim, T_ij};
     const int64_t waves = (int64_t)S0 * ((S1 + GRID_TJ - 1) / GRID_TJ);
-    hipLaunchKernelGGL(k_grid_gate, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
+    if (sim_in) hipLaunchKernelGGL(k_grid_gate<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
+    else hipLaunchKernelGGL(k_grid_gate<false>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
     hipLaunchKernelGGL(k_grid_compact, dim3(1), dim3(B > 256 ? 1024 : 256), 0, stream, B, (int)S1, (const int32_t*)flags, pairs, n_todo);
     hipLaunchKernelGGL(k_grid_fill, dim3((unsigned)(((int64_t)B * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, (int)S1, (const int32_t*)n_todo,
                        (const int32_t*)pairs, (const double*)T_ij, time0, time1, T_ref, enable);
@@ -2635,14 +2644,35 @@ int roman_grid_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams,
     return ROMAN_OK;
 }
 
-int roman_grid_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
-                    const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
-                    const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
-                    double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                    int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
+int roman_grid_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                        const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                        const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                        double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                        int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
+{
+    return grid_gate_dev(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, desc0, pos1, pos_gt1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij,
+                         pairs, T_ref, enable, n_todo, false);
+}
+
+int roman_grid_gate_sim_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                            const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0,
+                            const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1,
+                            double* dist, int32_t* flags, double* yaw_deg, const double* sim, double* T_ij,
+                            int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
+{
+    return grid_gate_dev(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, nullptr, pos1, pos_gt1, T_w1, time1, nullptr, dist, flags, yaw_deg,
+                         const_cast<double*>(sim) /* k_grid_gate<true> only reads it */, T_ij, pairs, T_ref, enable, n_todo, true);
+}
+
+// the host-pointer gate; sim_in: the caller's sim goes up and is not brought back
+static int grid_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                          const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                          const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                          double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                          int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo, bool sim_in)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo);
+    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo, sim_in);
     if (rc) return rc;
     if (S0 == 0 || S1 == 0) { *n_todo = 0; return ROMAN_OK; }
     HIPCHK(c, hipSetDevice(c->device));
@@ -2671,20 +2701,208 @@ int roman_grid_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int
     HIPCHK(c, hipMemcpyAsync(dev + oTref, T_ref, 128 * B, hipMemcpyHostToDevice, WS.stream));
     HIPCHK(c, hipMemcpyAsync(dev + oPairs, pairs, 8 * B, hipMemcpyHostToDevice, WS.stream));
     HIPCHK(c, hipMemcpyAsync(dev + oEn, enable, 4 * B, hipMemcpyHostToDevice, WS.stream));
-    rc = roman_grid_gate_dev(c, gparams, S0, S1, dIn[0][0], dIn[0][1], dIn[0][2], dIn[0][3], dIn[0][4], dIn[1][0], dIn[1][1], dIn[1][2], dIn[1][3], dIn[1][4],
-                             reinterpret_cast<double*>(dev + oDist), reinterpret_cast<int32_t*>(dev + oFlags), reinterpret_cast<double*>(dev + oYaw),
-                             reinterpret_cast<double*>(dev + oSim), reinterpret_cast<double*>(dev + oTij), reinterpret_cast<int32_t*>(dev + oPairs),
-                             reinterpret_cast<double*>(dev + oTref), reinterpret_cast<int32_t*>(dev + oEn), reinterpret_cast<int32_t*>(dev + oCnt));
+    if (sim_in) HIPCHK(c, hipMemcpyAsync(dev + oSim, sim, 8 * B, hipMemcpyHostToDevice, WS.stream));
+    rc = grid_gate_dev(c, gparams, S0, S1, dIn[0][0], dIn[0][1], dIn[0][2], dIn[0][3], dIn[0][4], dIn[1][0], dIn[1][1], dIn[1][2], dIn[1][3], dIn[1][4],
+                       reinterpret_cast<double*>(dev + oDist), reinterpret_cast<int32_t*>(dev + oFlags), reinterpret_cast<double*>(dev + oYaw),
+                       reinterpret_cast<double*>(dev + oSim), reinterpret_cast<double*>(dev + oTij), reinterpret_cast<int32_t*>(dev + oPairs),
+                       reinterpret_cast<double*>(dev + oTref), reinterpret_cast<int32_t*>(dev + oEn), reinterpret_cast<int32_t*>(dev + oCnt), sim_in);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(dist, dev + oDist, 8 * B, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(yaw_deg, dev + oYaw, 8 * B, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(sim, dev + oSim, 8 * B, hipMemcpyDeviceToHost, WS.stream));
+    if (!sim_in) HIPCHK(c, hipMemcpyAsync(sim, dev + oSim, 8 * B, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(T_ij, dev + oTij, 128 * B, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(T_ref, dev + oTref, 128 * B, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(flags, dev + oFlags, 4 * B, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(pairs, dev + oPairs, 8 * B, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(enable, dev + oEn, 4 * B, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(n_todo, dev + oCnt, 4, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipStreamSynchronize(WS.stream));
+    return ROMAN_OK;
+}
+
+int roman_grid_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                    const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                    const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                    double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                    int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
+{
+    return grid_gate_host(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, desc0, pos1, pos_gt1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij,
+                          pairs, T_ref, enable, n_todo, false);
+}
+
+int roman_grid_gate_sim(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                        const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0,
+                        const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1,
+                        double* dist, int32_t* flags, double* yaw_deg, const double* sim, double* T_ij,
+                        int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
+{
+    return grid_gate_host(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, nullptr, pos1, pos_gt1, T_w1, time1, nullptr, dist, flags, yaw_deg,
+                          const_cast<double*>(sim) /* uploaded, never written */, T_ij, pairs, T_ref, enable, n_todo, true);
+}
+
+// --- frame descriptors of the submaps of a pool ([REF roman/map/map.py:210-242], [REF :155-162]) ------------------
+static int frame_select_check(roman_ctx* c, const roman_frame_select_params_t* P, int32_t S, int32_t cap, const void* count, const void* src,
+                              int32_t N, const void* seg_times, int32_t Nf, const void* frame_times, const void* frame_pos, int32_t d,
+                              const void* frame_desc, const void* mask, const void* n_sel, const void* span, const void* mean)
+{
+    if (!P) return fail(c, ROMAN_E_INVALID, "fparams is NULL");
+    if (S < 0 || N < 0 || Nf < 0 || d < 0) return fail(c, ROMAN_E_INVALID, "S, N, Nf or d is negative");
+    if (cap < 1) return fail(c, ROMAN_E_INVALID, "cap must be >= 1 (got %d)", cap);
+    if (P->reserved[0] != 0 || P->reserved[1] != 0) return fail(c, ROMAN_E_INVALID, "roman_frame_select_params_t reserved words must be 0");
+    if (P->thin && (P->thin_dist != P->thin_dist || P->thin_dist < 0.0)) return fail(c, ROMAN_E_INVALID, "thin_dist=%g must be a distance >= 0", P->thin_dist);
+    if (P->want_mean && (d < 1 || (Nf > 0 && !frame_desc))) return fail(c, ROMAN_E_INVALID, "want_mean needs d >= 1 and frame_desc");
+    if ((int64_t)S * cap > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "S * cap = %lld rows exceed the index width", (long long)S * cap);
+    if (S == 0) return ROMAN_OK;
+    if (!count || !src || !n_sel || !span || (Nf > 0 && !mask) || (P->want_mean && !mean)) return fail(c, ROMAN_E_INVALID, "NULL count, src or output pointer");
+    if (N > 0 && !seg_times) return fail(c, ROMAN_E_INVALID, "seg_times is NULL");
+    if (Nf > 0 && (!frame_times || (P->thin && !frame_pos))) return fail(c, ROMAN_E_INVALID, "frame_times / frame_pos is NULL");
+    return ROMAN_OK;
+}
+
+int roman_frame_select_dev(roman_ctx_t* c, const roman_frame_select_params_t* fparams, int32_t S, int32_t cap,
+                           const int32_t* count, const int32_t* src, int32_t N, const double* seg_times,
+                           int32_t Nf, const double* frame_times, const double* frame_pos, int32_t d, const double* frame_desc,
+                           uint64_t* mask, int32_t* n_sel, double* span, double* mean)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = frame_select_check(c, fparams, S, cap, count, src, N, seg_times, Nf, frame_times, frame_pos, d, frame_desc, mask, n_sel, span, mean);
+    if (rc || S == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    hipLaunchKernelGGL(k_frame_select, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, stream, *fparams, (int)S, (int)cap, count, src, (int)N, seg_times,
+                       (int)Nf, frame_times, frame_pos, reinterpret_cast<unsigned long long*>(mask), n_sel, span);
+    if (fparams->want_mean)
+        hipLaunchKernelGGL(k_frame_mean, dim3((unsigned)S, (unsigned)((d + 255) / 256)), dim3(256), 0, stream, (int)Nf, (int)d, frame_desc,
+                           reinterpret_cast<const unsigned long long*>(mask), (const int32_t*)n_sel, mean);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+// one device block for a host-pointer call: the pieces in the order given, each 8-byte aligned
+struct HostBlock {
+    size_t total = 0;
+    size_t add(size_t bytes) { const size_t o = total; total += (bytes + 7) & ~(size_t)7; return o; }
+};
+
+int roman_frame_select(roman_ctx_t* c, const roman_frame_select_params_t* fparams, int32_t S, int32_t cap,
+                       const int32_t* count, const int32_t* src, int32_t N, const double* seg_times,
+                       int32_t Nf, const double* frame_times, const double* frame_pos, int32_t d, const double* frame_desc,
+                       uint64_t* mask, int32_t* n_sel, double* span, double* mean)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = frame_select_check(c, fparams, S, cap, count, src, N, seg_times, Nf, frame_times, frame_pos, d, frame_desc, mask, n_sel, span, mean);
+    if (rc || S == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const bool thin = fparams->thin != 0, wm = fparams->want_mean != 0;
+    const size_t W = ((size_t)Nf + 63) / 64;
+    HostBlock hb;
+    const size_t bCnt = 4 * (size_t)S, bSrc = 4 * (size_t)S * (size_t)cap, bSeg = 16 * (size_t)N, bFt = 8 * (size_t)Nf, bFp = thin ? 24 * (size_t)Nf : 0,
+                 bFd = wm ? 8 * (size_t)Nf * (size_t)d : 0, bMask = 8 * (size_t)S * W, bSpan = 16 * (size_t)S, bMean = wm ? 8 * (size_t)S * (size_t)d : 0;
+    const size_t oCnt = hb.add(bCnt), oSrc = hb.add(bSrc), oSeg = hb.add(bSeg), oFt = hb.add(bFt), oFp = hb.add(bFp), oFd = hb.add(bFd),
+                 oMask = hb.add(bMask), oSel = hb.add(bCnt), oSpan = hb.add(bSpan), oMean = hb.add(bMean);
+    HIPCHK(c, c->fsHost.ensure(std::max<size_t>(hb.total, 8)));
+    char* const dev = c->fsHost.as<char>();
+    const struct { size_t o, b; const void* h; } up[6] = {{oCnt, bCnt, count}, {oSrc, bSrc, src}, {oSeg, bSeg, seg_times}, {oFt, bFt, frame_times},
+                                                          {oFp, bFp, frame_pos}, {oFd, bFd, frame_desc}};
+    for (const auto& u : up) if (u.b) HIPCHK(c, hipMemcpyAsync(dev + u.o, u.h, u.b, hipMemcpyHostToDevice, WS.stream));
+    rc = roman_frame_select_dev(c, fparams, S, cap, reinterpret_cast<const int32_t*>(dev + oCnt), reinterpret_cast<const int32_t*>(dev + oSrc), N,
+                                reinterpret_cast<const double*>(dev + oSeg), Nf, reinterpret_cast<const double*>(dev + oFt),
+                                thin ? reinterpret_cast<const double*>(dev + oFp) : nullptr, d, wm ? reinterpret_cast<const double*>(dev + oFd) : nullptr,
+                                reinterpret_cast<uint64_t*>(dev + oMask), reinterpret_cast<int32_t*>(dev + oSel), reinterpret_cast<double*>(dev + oSpan),
+                                wm ? reinterpret_cast<double*>(dev + oMean) : nullptr);
+    if (rc) return rc;
+    if (bMask) HIPCHK(c, hipMemcpyAsync(mask, dev + oMask, bMask, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(n_sel, dev + oSel, bCnt, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(span, dev + oSpan, bSpan, hipMemcpyDeviceToHost, WS.stream));
+    if (bMean) HIPCHK(c, hipMemcpyAsync(mean, dev + oMean, bMean, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipStreamSynchronize(WS.stream));
+    return ROMAN_OK;
+}
+
+static int stacked_sim_check(roman_ctx* c, int32_t d, int32_t Nf0, const void* desc0, int32_t S0, const void* mask0,
+                             int32_t Nf1, const void* desc1, int32_t S1, const void* mask1, const void* sim)
+{
+    if (d < 1) return fail(c, ROMAN_E_INVALID, "d=%d: a frame descriptor has at least one component", d);
+    if (Nf0 < 0 || Nf1 < 0 || S0 < 0 || S1 < 0) return fail(c, ROMAN_E_INVALID, "a size is negative");
+    if ((int64_t)S0 * S1 > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "S0 * S1 = %lld pairs exceed the index width", (long long)S0 * S1);
+    if (S0 == 0 || S1 == 0) return ROMAN_OK;
+    if (!sim) return fail(c, ROMAN_E_INVALID, "sim is NULL");
+    if ((Nf0 > 0 && (!desc0 || !mask0)) || (Nf1 > 0 && (!desc1 || !mask1))) return fail(c, ROMAN_E_INVALID, "desc / mask is NULL");
+    if (((int64_t)S0 * (((int64_t)Nf1 + 255) / 256)) > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "S0 * Nf1 exceeds the launch width");
+    return ROMAN_OK;
+}
+
+int roman_ctx_set_stacked_band(roman_ctx_t* c, int32_t rows)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (rows < 0) return fail(c, ROMAN_E_INVALID, "rows=%d is negative", rows);
+    c->stacked_band = rows == 0 ? 0 : (int)std::min<int64_t>((((int64_t)rows + STACK_TILE - 1) / STACK_TILE) * STACK_TILE, INT32_MAX / STACK_TILE * STACK_TILE);
+    return ROMAN_OK;
+}
+
+int roman_stacked_sim_dev(roman_ctx_t* c, int32_t d, int32_t Nf0, const double* desc0, int32_t S0, const uint64_t* mask0,
+                          int32_t Nf1, const double* desc1, int32_t S1, const uint64_t* mask1, double* sim)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = stacked_sim_check(c, d, Nf0, desc0, S0, mask0, Nf1, desc1, S1, mask1, sim);
+    if (rc || S0 == 0 || S1 == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    const int64_t B = (int64_t)S0 * S1;
+    if (Nf0 == 0 || Nf1 == 0) {                                  // no frame pair: the maximum over nothing
+        hipLaunchKernelGGL(k_fill_f64, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, B, -(double)INFINITY, sim);
+        HIPCHK(c, hipGetLastError());
+        return ROMAN_OK;
+    }
+    // rows of a band: what was set, or what 64 MiB hold; a multiple of STACK_TILE, at most the frames there are
+    const int64_t rounded = (((int64_t)Nf0 + STACK_TILE - 1) / STACK_TILE) * STACK_TILE;
+    int64_t H = c->stacked_band > 0 ? c->stacked_band : std::max<int64_t>(STACK_TILE, ((int64_t)(64 << 20) / 8 / Nf1) / STACK_TILE * STACK_TILE);
+    H = std::min(H, rounded);
+    // scratch first: a failure leaves nothing enqueued
+    HIPCHK(c, c->ssNorm.ensure(sizeof(double) * ((size_t)Nf0 + (size_t)Nf1)));
+    HIPCHK(c, c->ssBand.ensure(sizeof(double) * (size_t)std::min<int64_t>(H, Nf0) * (size_t)Nf1));
+    HIPCHK(c, c->ssR.ensure(sizeof(double) * (size_t)S0 * (size_t)Nf1));
+    double* const dNorm = c->ssNorm.as<double>();
+    double* const Cb = c->ssBand.as<double>();
+    double* const R = c->ssR.as<double>();
+    const int W0 = (Nf0 + 63) / 64, W1 = (Nf1 + 63) / 64, nbx = (Nf1 + 255) / 256;
+    hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)(((int64_t)Nf0 + Nf1 + 3) / 4)), dim3(256), 0, stream, (int)Nf0, (int)Nf1, (int)d, desc0, desc1, dNorm);
+    for (int64_t a0 = 0; a0 < Nf0; a0 += H) {                    // bands ordered on the stream: each updates R in place
+        const int h = (int)std::min<int64_t>(H, Nf0 - a0);
+        const int64_t tiles = (int64_t)((h + STACK_TILE - 1) / STACK_TILE) * ((Nf1 + STACK_TILE - 1) / STACK_TILE);
+        hipLaunchKernelGGL(k_stacked_band, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, (int)d, (int)a0, h, (int)Nf1, desc0, desc1,
+                           (const double*)dNorm, (const double*)(dNorm + Nf0), Cb);
+        hipLaunchKernelGGL(k_stacked_colmax, dim3((unsigned)((int64_t)S0 * nbx)), dim3(256), 0, stream, nbx, W0, (int)a0, h, (int)Nf1, a0 == 0 ? 1 : 0,
+                           reinterpret_cast<const unsigned long long*>(mask0), (const double*)Cb, R);
+    }
+    hipLaunchKernelGGL(k_stacked_rowmax, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, (int)S0, (int)S1, W1, (int)Nf1,
+                       reinterpret_cast<const unsigned long long*>(mask1), (const double*)R, sim);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_stacked_sim(roman_ctx_t* c, int32_t d, int32_t Nf0, const double* desc0, int32_t S0, const uint64_t* mask0,
+                      int32_t Nf1, const double* desc1, int32_t S1, const uint64_t* mask1, double* sim)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = stacked_sim_check(c, d, Nf0, desc0, S0, mask0, Nf1, desc1, S1, mask1, sim);
+    if (rc || S0 == 0 || S1 == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    HostBlock hb;
+    const size_t bD0 = 8 * (size_t)Nf0 * (size_t)d, bD1 = 8 * (size_t)Nf1 * (size_t)d, bM0 = 8 * (size_t)S0 * (((size_t)Nf0 + 63) / 64),
+                 bM1 = 8 * (size_t)S1 * (((size_t)Nf1 + 63) / 64), bSim = 8 * (size_t)S0 * (size_t)S1;
+    const size_t oD0 = hb.add(bD0), oD1 = hb.add(bD1), oM0 = hb.add(bM0), oM1 = hb.add(bM1), oSim = hb.add(bSim);
+    HIPCHK(c, c->ssHost.ensure(std::max<size_t>(hb.total, 8)));
+    char* const dev = c->ssHost.as<char>();
+    const struct { size_t o, b; const void* h; } up[4] = {{oD0, bD0, desc0}, {oD1, bD1, desc1}, {oM0, bM0, mask0}, {oM1, bM1, mask1}};
+    for (const auto& u : up) if (u.b) HIPCHK(c, hipMemcpyAsync(dev + u.o, u.h, u.b, hipMemcpyHostToDevice, WS.stream));
+    rc = roman_stacked_sim_dev(c, d, Nf0, reinterpret_cast<const double*>(dev + oD0), S0, reinterpret_cast<const uint64_t*>(dev + oM0),
+                               Nf1, reinterpret_cast<const double*>(dev + oD1), S1, reinterpret_cast<const uint64_t*>(dev + oM1),
+                               reinterpret_cast<double*>(dev + oSim));
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(sim, dev + oSim, bSim, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipStreamSynchronize(WS.stream));
     return ROMAN_OK;
 }

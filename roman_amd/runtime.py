@@ -146,6 +146,35 @@ class GridGateResult:
     n_todo: int
 
 
+@dataclass
+class FrameSelectResult:
+    """Results of one roman_frame_select call over the S submaps of a pool and the Nf frames of its map."""
+    mask: np.ndarray       # (S, ceil(Nf / 64)) uint64: bit f % 64 of word f / 64
+    n_sel: np.ndarray      # (S,) int32
+    span: np.ndarray       # (S, 2) float64: min first_seen, max last_seen of the submap's rows ((+inf, -inf) for an empty one)
+    mean: Optional[np.ndarray]     # (S, d) float64 with want_mean (NaN rows where nothing is selected), else None
+
+    def selected(self, s):
+        """Ascending frame indices of submap s."""
+        return mask_indices(self.mask[s])
+
+
+def mask_indices(words):
+    """uint64 mask words -> the ascending indices of the set bits."""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")
+    return np.nonzero(bits)[0].astype(np.int64)
+
+
+def frame_select_params(thin_dist=None, want_mean=False):
+    """-> roman_frame_select_params_t (thin_dist None: every candidate frame is selected)."""
+    P = _abi.RomanFrameSelectParams()
+    P.thin = int(thin_dist is not None)
+    P.thin_dist = float(thin_dist) if thin_dist is not None else 0.0
+    P.want_mean = int(bool(want_mean))
+    return P
+
+
 def grid_gate_params(radius, skip_distance=np.inf, desc_dim=0, desc_thresh=0.0, single_robot_lc=False, lc_time_thresh=0.0):
     """-> roman_grid_gate_params_t (a missing radius — None — is passed as -1: the library answers ROMAN_E_UNSUPPORTED)."""
     P = _abi.RomanGridGateParams()
@@ -536,6 +565,114 @@ class Context:
                                            vp(dist_ptr), vp(flags_ptr), vp(yaw_deg_ptr), vp(sim_ptr), vp(T_ij_ptr),
                                            vp(pairs_ptr), vp(T_ref_ptr), vp(enable_ptr), vp(n_todo_ptr))
         self._check(rc, "roman_grid_gate_dev")
+
+    def grid_gate_sim(self, gparams, sim, pos0, T_w0, pos1, T_w1, time0=None, time1=None, pos_gt0=None, pos_gt1=None,
+                      pairs=None, T_ref=None, enable=None):
+        """grid_gate() on a similarity that is already there (roman_grid_gate_sim): `sim` (S0, S1) is read, never written;
+        gparams.desc_dim must be 0.  -> GridGateResult whose sim is the array handed in."""
+        side = []
+        for pos, T_w, tm, gt in ((pos0, T_w0, time0, pos_gt0), (pos1, T_w1, time1, pos_gt1)):
+            pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
+            T_w = _f64(T_w).reshape(-1, 16)
+            tm = None if tm is None else _f64(tm).reshape(-1)
+            gt = None if gt is None else _f64(gt).reshape(-1, 3)
+            if T_w.shape[0] != S or (tm is not None and tm.shape[0] != S) or (gt is not None and gt.shape[0] != S):
+                raise ValueError("the per-submap arrays of a side must hold one entry per submap")
+            side.append((S, pos, gt, T_w, tm))
+        S0, S1 = side[0][0], side[1][0]
+        B = S0 * S1
+        sim = _f64(sim)
+        if sim.shape != (S0, S1):
+            raise ValueError("sim must be (S0, S1)")
+
+        def given(a, shape, dtype, fill):
+            if a is None:
+                return np.full(shape, fill, dtype=dtype)
+            if a.dtype != dtype or not a.flags.c_contiguous or a.shape != shape:
+                raise ValueError(f"an output array must be C-contiguous {np.dtype(dtype).name} of shape {shape}")
+            return a
+        pairs = given(pairs, (B, 2), np.int32, -1); T_ref = given(T_ref, (B, 4, 4), np.float64, np.nan); enable = given(enable, (B,), np.int32, -1)
+        dist = np.zeros((S0, S1)); flags = np.zeros((S0, S1), dtype=np.int32); yaw = np.zeros((S0, S1))
+        T_ij = np.zeros((S0, S1, 4, 4)); n_todo = np.zeros(1, dtype=np.int32)
+        self._generation += 1
+        ins = [_ptr(a) for s in side for a in s[1:]]
+        rc = self._lib.roman_grid_gate_sim(self._h, C.byref(gparams), S0, S1, *ins, _ptr(dist), _ptr(flags), _ptr(yaw), _ptr(sim), _ptr(T_ij),
+                                           _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(n_todo))
+        self._check(rc, "roman_grid_gate_sim")
+        return GridGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, int(n_todo[0]))
+
+    def grid_gate_sim_dev(self, gparams, S0, S1, pos0_ptr, T_w0_ptr, pos1_ptr, T_w1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
+                          pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr, time0_ptr=None, time1_ptr=None, pos_gt0_ptr=None, pos_gt1_ptr=None):
+        """grid_gate_dev() on a similarity that is already there (roman_grid_gate_sim_dev): sim_ptr is an INPUT."""
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_grid_gate_sim_dev(self._h, C.byref(gparams), int(S0), int(S1),
+                                               vp(pos0_ptr), vp(pos_gt0_ptr), vp(T_w0_ptr), vp(time0_ptr),
+                                               vp(pos1_ptr), vp(pos_gt1_ptr), vp(T_w1_ptr), vp(time1_ptr),
+                                               vp(dist_ptr), vp(flags_ptr), vp(yaw_deg_ptr), vp(sim_ptr), vp(T_ij_ptr),
+                                               vp(pairs_ptr), vp(T_ref_ptr), vp(enable_ptr), vp(n_todo_ptr))
+        self._check(rc, "roman_grid_gate_sim_dev")
+
+    # ------------------------------------------------------------------ frame descriptors of the submaps of a pool
+    def frame_select(self, fparams, count, src, seg_times, frame_times, frame_pos=None, frame_desc=None):
+        """Host-pointer frame selection (roman_frame_select, [REF roman/map/map.py:210-242]): count (S,) and src (S, cap) as
+        roman_submaps wrote them, seg_times (N, 2), frame_times (Nf,), frame_pos (Nf, 3) for thinning, frame_desc (Nf, d) for the
+        mean.  fparams: frame_select_params().  -> FrameSelectResult."""
+        count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1); S = count.shape[0]
+        src = np.ascontiguousarray(src, dtype=np.int32)
+        if src.ndim != 2 or src.shape[0] != S or src.shape[1] < 1:
+            raise ValueError("src must be (S, cap)")
+        cap = src.shape[1]
+        seg_times = _f64(seg_times).reshape(-1, 2)
+        frame_times = _f64(frame_times).reshape(-1); Nf = frame_times.shape[0]
+        frame_pos = None if frame_pos is None else _f64(frame_pos).reshape(Nf, 3)
+        frame_desc = None if frame_desc is None else _f64(frame_desc).reshape(Nf, -1)
+        d = 0 if frame_desc is None else frame_desc.shape[1]
+        W = (Nf + 63) // 64
+        mask = np.zeros((S, W), dtype=np.uint64); n_sel = np.zeros(S, dtype=np.int32); span = np.zeros((S, 2))
+        mean = np.full((S, d), np.nan) if fparams.want_mean else None
+        self._generation += 1
+        rc = self._lib.roman_frame_select(self._h, C.byref(fparams), S, cap, _ptr(count), _ptr(src), seg_times.shape[0], _ptr(seg_times),
+                                          Nf, _ptr(frame_times), _ptr(frame_pos), d, _ptr(frame_desc), _ptr(mask), _ptr(n_sel), _ptr(span), _ptr(mean))
+        self._check(rc, "roman_frame_select")
+        return FrameSelectResult(mask, n_sel, span, mean)
+
+    def frame_select_dev(self, fparams, S, cap, count_ptr, src_ptr, N, seg_times_ptr, Nf, frame_times_ptr, mask_ptr, n_sel_ptr, span_ptr,
+                         frame_pos_ptr=None, d=0, frame_desc_ptr=None, mean_ptr=None):
+        """Device-pointer frame selection (roman_frame_select_dev): a pure enqueue on the context's stream, behind submaps_dev."""
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_frame_select_dev(self._h, C.byref(fparams), int(S), int(cap), vp(count_ptr), vp(src_ptr), int(N), vp(seg_times_ptr),
+                                              int(Nf), vp(frame_times_ptr), vp(frame_pos_ptr), int(d), vp(frame_desc_ptr),
+                                              vp(mask_ptr), vp(n_sel_ptr), vp(span_ptr), vp(mean_ptr))
+        self._check(rc, "roman_frame_select_dev")
+
+    def stacked_sim(self, desc0, mask0, desc1, mask1):
+        """Host-pointer stacked similarity of a grid (roman_stacked_sim, [REF roman/map/map.py:155-162]): desc_r (Nf_r, d) the
+        frame descriptors of map r, mask_r (S_r, ceil(Nf_r / 64)) uint64 as frame_select wrote it -> sim (S0, S1)."""
+        desc0, desc1 = _f64(desc0), _f64(desc1)
+        if desc0.ndim != 2 or desc1.ndim != 2 or desc0.shape[1] != desc1.shape[1]:
+            raise ValueError("stacked_sim needs two (Nf, d) frame tables of the same d")
+        mask0 = np.ascontiguousarray(mask0, dtype=np.uint64); mask1 = np.ascontiguousarray(mask1, dtype=np.uint64)
+        for m, D in ((mask0, desc0), (mask1, desc1)):
+            if m.ndim != 2 or m.shape[1] != (D.shape[0] + 63) // 64:
+                raise ValueError("a mask must be (S, ceil(Nf / 64))")
+        sim = np.zeros((mask0.shape[0], mask1.shape[0]))
+        self._generation += 1
+        rc = self._lib.roman_stacked_sim(self._h, desc0.shape[1], desc0.shape[0], _ptr(desc0), mask0.shape[0], _ptr(mask0),
+                                         desc1.shape[0], _ptr(desc1), mask1.shape[0], _ptr(mask1), _ptr(sim))
+        self._check(rc, "roman_stacked_sim")
+        return sim
+
+    def stacked_sim_dev(self, d, Nf0, desc0_ptr, S0, mask0_ptr, Nf1, desc1_ptr, S1, mask1_ptr, sim_ptr):
+        """Device-pointer stacked similarity of a grid (roman_stacked_sim_dev): a pure enqueue on the context's stream."""
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_stacked_sim_dev(self._h, int(d), int(Nf0), vp(desc0_ptr), int(S0), vp(mask0_ptr), int(Nf1), vp(desc1_ptr),
+                                             int(S1), vp(mask1_ptr), vp(sim_ptr))
+        self._check(rc, "roman_stacked_sim_dev")
+
+    def set_stacked_band(self, rows=0):
+        """Rows of map 0's frames one band of stacked_sim takes (roman_ctx_set_stacked_band): 0 automatic, otherwise rounded up to
+        a multiple of _abi.STACKED_BAND_MIN.  The result does not depend on it."""
+        self._check(self._lib.roman_ctx_set_stacked_band(self._h, int(rows)), "roman_ctx_set_stacked_band")
 
     # ------------------------------------------------------------------ loop closures
     def align_lc_batch(self, params, feats, off1, n1, off2, n2, lc, assoc=None, assoc_off=None, u0=None, kmax=None):
