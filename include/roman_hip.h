@@ -485,6 +485,36 @@ ROMAN_API int roman_shared_ids_dev(roman_ctx_t* ctx, int32_t B, const int64_t* i
                                    int32_t* keep, int32_t* kept);
 
 /*
+ * roman_shared_reduce_dev: the whole removal of [REF roman/align/submap_align.py:108-115] for B pairs over a pool that is
+ * ALREADY in HBM — which objects stay (as roman_shared_ids_dev) and the reduced maps themselves — in ONE launch, as a PURE
+ * ENQUEUE on the context's stream (complete once that stream is synchronised; nothing is waited for but the previous call's
+ * upload of its problem descriptors).  The host needs no count to place anything:
+ *
+ *   feats      DEVICE, double: the pool's rows (F doubles each), and behind them, from row region_row0 on, a gather region of
+ *              sum over b of (n1[b] + n2[b]) rows in the same allocation
+ *   ids        DEVICE, int64: one id per pool row
+ *   off1/off2  HOST, int64[B], n1/n2 HOST, int32[B]: as for roman_shared_ids_dev; every slice lies in front of the region
+ *              (off + n <= region_row0)
+ *   keep, kept DEVICE, out: exactly what roman_shared_ids_dev writes
+ *
+ * With kb[b] = sum over c < b of (n1[c] + n2[c]) (the start of problem b's keep lists), a problem that lost an object on either
+ * side (kept[b][0] != n1[b] or kept[b][1] != n2[b]) has its kept rows copied bit for bit, in list order, into FIXED slots:
+ * side 1 to rows region_row0 + kb[b] .. + kept[b][0], side 2 to rows region_row0 + kb[b] + n1[b] .. + kept[b][1].  The rows of
+ * a slot behind the kept ones are not written, and a problem with kept == n on both sides writes no row at all: it reads the
+ * pool as given.  The caller reads `kept` back (8 bytes per problem) and hands the batch calls off = region_row0 + kb (+ n1),
+ * n = kept for the problems that lost something and the original off, n for the others; a side reduced to nothing is a map of
+ * length 0 (ROMAN_ST_EMPTY_MAP).  The price of placing without counts is memory: the region takes 8 * F * sum (n1 + n2) bytes
+ * whatever is lost (roman_align_lc_batch_ids, which reads the counts back first, takes the rows of the affected problems only).
+ *
+ * ROMAN_E_INVALID (text in roman_last_error; nothing is enqueued): NULL context, B < 0, F < 1, region_row0 < 0, NULL metadata,
+ * a negative size or offset, a slice that reaches past region_row0, NULL kept, NULL feats / ids / keep when any map has a row.
+ * B == 0 is legal and enqueues nothing.
+ */
+ROMAN_API int roman_shared_reduce_dev(roman_ctx_t* ctx, int32_t B, int32_t F, double* feats, int64_t region_row0, const int64_t* ids,
+                                      const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                                      int32_t* keep, int32_t* kept);
+
+/*
  * roman_align_lc_batch_ids: roman_align_lc_batch (HOST pointers everywhere, same arguments, same results) for pairs that first
  * lose the segments both sides hold — the whole body of the reference's loop for single_robot_lc
  * ([REF roman/align/submap_align.py:108-115] in front of [REF :150-200] and [REF roman/align/results.py:156-198]) with every

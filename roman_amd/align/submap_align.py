@@ -617,6 +617,23 @@ class _TailBuffers:
                                  np.zeros(B, dtype=stats_dtype()), rec, self.acc_idx.cpu().numpy()[:int(self.acc_n.cpu().numpy()[0])].copy())
 
 
+def reduced_problems(off1, n1, off2, n2, kept, region_row0):
+    """The problem list behind roman_shared_reduce_dev (include/roman_hip.h), from the kept counts it wrote (`kept`: (B, 2)):
+    a problem that lost an object on either side reads its fixed slots of the gather region — side 1 at row
+    region_row0 + kb, side 2 n1 rows later, kb the sum of n1 + n2 over the problems in front — with n = kept (0: an empty map);
+    every other problem is unchanged.  -> (off1, n1, off2, n2).  No loop over problems."""
+    off1 = np.asarray(off1, dtype=np.int64); off2 = np.asarray(off2, dtype=np.int64)
+    n1 = np.asarray(n1, dtype=np.int32); n2 = np.asarray(n2, dtype=np.int32)
+    kept = np.asarray(kept, dtype=np.int32).reshape(-1, 2)
+    if kept.shape[0] != n1.shape[0] or np.any(kept < 0) or np.any(kept[:, 0] > n1) or np.any(kept[:, 1] > n2):
+        raise _abi.RomanHipError("roman_shared_reduce_dev: a kept count lies outside its map")
+    tot = n1.astype(np.int64) + n2.astype(np.int64)
+    kb = np.cumsum(tot) - tot
+    lost = (kept[:, 0] != n1) | (kept[:, 1] != n2)
+    return (np.where(lost, int(region_row0) + kb, off1), np.where(lost, kept[:, 0], n1).astype(np.int32),
+            np.where(lost, int(region_row0) + kb + n1, off2), np.where(lost, kept[:, 1], n2).astype(np.int32))
+
+
 def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, registration=None, gt_poses=(None, None)) -> SubmapAlignResults:
     """submap_align_grid() for two maps whose submaps are ALREADY in HBM (`pools`: two align.submaps.SubmapPool, as
     build_submap_pool leaves them): the same results as submap_align_grid(sm_params, [p.to_submaps(segments) for p in pools]),
@@ -630,9 +647,13 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     gt_poses[r]: None, or (S, 4, 4) ground-truth `pose_flu_gt` of EVERY centre of pool r (empty submaps included) — then every
     submap of that side has ground truth ([REF :96-99]); sm_io.gt_available[r] selects it for the reference transform.
 
-    Not covered — ValueError; SubmapPool.to_submaps() + submap_align_grid is the way: single_robot_lc over submaps that share
-    segment ids (one pool against itself), force_fill_submaps / no submap_radius (the AABB gate), RansacReg, registration plugins
-    with a host prefilter.
+    Self loop closures (`single_robot_lc` over pools that share segment ids — one pool against itself: submap_align_pools(p,
+    [pool, pool])): the shared-segment removal of [REF :108-115] runs over the resident pools (roman_shared_reduce_dev, DESIGN.md
+    §4.11: the ids build_submap_pool kept on the device, one launch, 8 bytes per pair back); returned associations index the
+    reduced lists, as the reference's do.  Pools that share no id take the path without it.
+
+    Not covered — ValueError; SubmapPool.to_submaps() + submap_align_grid is the way: force_fill_submaps / no submap_radius (the
+    AABB gate), RansacReg, registration plugins with a host prefilter, shared ids over pools without `ids_dev`.
 
     Frame descriptors need pools built with them (build_submap_pool(frames=...)): 'mean_frame_descriptor' goes
     through the same gate as 'mean_semantic'; 'stacked_frame_descriptors' through roman_stacked_sim_dev over the two pools' frame
@@ -658,10 +679,6 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool(frames=...) keeps the frame masks on the device)" + way)
     if _has_host_prefilter(registration):
         raise ValueError("the registration plugin prefilters association lists on the host" + way)
-    if sm_params.single_robot_lc:
-        shared = p[0] is p[1] or np.intersect1d(p[0].ids[p[0].src >= 0], p[1].ids[p[1].src >= 0]).size > 0
-        if shared:
-            raise ValueError("single_robot_lc over submaps that share segment ids: the shared-segment removal has no device-pointer form yet" + way)
     d = 0
     if stacked:
         if int(p[0].frame_desc_dev.shape[1]) != int(p[1].frame_desc_dev.shape[1]):
@@ -676,6 +693,12 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         if sm_io.gt_available[r] and gt_poses[r] is None:
             raise ValueError(f"sm_io.gt_available[{r}] is set without gt_poses[{r}]")
     ctx = registration._context()
+    # self loop closures over submaps that share segment ids: the removal of [REF :108-115] runs over the resident pools too
+    # (roman_shared_reduce_dev) — with the ids build_submap_pool left on the device
+    shared = bool(sm_params.single_robot_lc) and (p[0] is p[1] or np.intersect1d(p[0].ids[p[0].src >= 0], p[1].ids[p[1].src >= 0]).size > 0)
+    if shared and (any(q.ids_dev is None for q in p) or not hasattr(ctx, "shared_reduce_dev")):
+        raise ValueError("single_robot_lc over submaps that share segment ids needs pools that kept their ids on the device (SubmapPool.ids_dev, "
+                         "as build_submap_pool leaves it) and a context with roman_shared_reduce_dev" + way)
     dev = p[0].pool.device
     on_host = dev.type == "cpu"                              # CPU tensors + a stand-in context (tests)
     wait_torch = (lambda: None) if on_host else (lambda: torch.cuda.current_stream(dev).synchronize())
@@ -738,7 +761,24 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
 
     # ---- the hot path over the resident pools: offsets and counts from the pools, the batch in chunks, then the tail ----
     batch, pool = p[0].grid_batch(p[1], mask=todo)
-    kmax = batch.kmax()
+    kmax = batch.kmax()                                      # (of the unreduced sizes: still a bound after the removal)
+    if shared:
+        # the pool's rows and behind them the fixed slots of the gather region in ONE allocation; mark + gather in one launch;
+        # the kept counts back (8 bytes per problem: the one extra synchronisation); the problems that lost something then read
+        # their slots, the others the pool as given
+        rows, F = int(pool.shape[0]), int(pool.shape[1])
+        n_slots = int(batch.n1.sum(dtype=np.int64) + batch.n2.sum(dtype=np.int64))
+        work = torch.empty((rows + n_slots, F), dtype=torch.float64, device=dev)
+        work[:rows].copy_(pool)
+        ids_dev = p[0].ids_dev if p[0] is p[1] else torch.cat([p[0].ids_dev, p[1].ids_dev])
+        keep_dev = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev); kept_dev = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+        wait_torch()                                         # the copy of the pool and the ids are in place
+        ctx.shared_reduce_dev(B, F, work.data_ptr(), rows, ids_dev.data_ptr(), batch.off1, batch.n1, batch.off2, batch.n2,
+                              keep_dev.data_ptr(), kept_dev.data_ptr())
+        ctx.sync()
+        off1, n1, off2, n2 = reduced_problems(batch.off1, batch.n1, batch.off2, batch.n2, kept_dev.cpu().numpy(), rows)
+        batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), (rows + n_slots, F)), off1, n1, off2, n2, pair_index=batch.pair_index)
+        pool = work
     o = _TailBuffers(torch, dev, B, kmax)
     FL, FR = up(frames[0].reshape(-1, 16)), up(frames[1].reshape(-1, 16))
     iL, iR = g["pairs"][:B, 0].contiguous(), g["pairs"][:B, 1].contiguous()

@@ -176,6 +176,8 @@ class SubmapPool:
     table: MapTable
     desc_dev: Optional[object] = None   # the same descriptors as the call left them on the device: torch tensor (S, d) float64, or None (submap_align_pools reads it)
     descriptor_mode: Optional[str] = None      # the submap_descriptor the pool was built with
+    ids_dev: Optional[object] = None           # `ids` as the call left them on the device: torch tensor (S * cap,) int64, one per pool row (submap_align_pools'
+                                               # shared-segment removal of self loop closures reads it), or None for a pool built by other means
     # the frame-descriptor modes (build_submap_pool(frames=...)): which of the map's frames every submap holds
     frames: Optional[FrameTable] = None
     frame_mask: Optional[object] = None        # torch tensor (S, ceil(Nf / 64)) int64 on the device: bit f % 64 of word f / 64
@@ -318,4 +320,4 @@ def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, par
     return SubmapPool(pool, int(P.cap), count_h, src.cpu().numpy()[:rows].reshape(S, P.cap).copy(),
                       ids_out.cpu().numpy()[:rows].reshape(S, P.cap).copy(), status.cpu().numpy()[:S].copy(),
                       desc.cpu().numpy()[:S, :d].copy() if d else None, centers, table, desc_dev=desc[:S, :d] if d else None,
-                      descriptor_mode=params.submap_descriptor, **extra)
+                      descriptor_mode=params.submap_descriptor, ids_dev=ids_out[:rows], **extra)

@@ -7082,26 +7082,23 @@ __global__ void __launch_bounds__(1024) k_lc_compact(int B, const roman_lc_recor
 // shared-segment removal for self loop closures: the reference drops from both submaps of a pair every segment whose id
 // occurs in both before it registers them ([REF roman/align/submap_align.py:108-115]).  One int64 id per row of the feature
 // pool; k_shared_mark lists, per problem and side, the local indices that stay; k_shared_gather copies those rows of the
-// problems that lost something into a region behind the pool (the others keep pointing at the pool).
+// problems that lost something into a region behind the pool (the others keep pointing at the pool); k_shared_reduce does both
+// in one launch for device-pointer callers, into fixed slots of the region.
 // ---------------------------------------------------------------------------------------------
 struct ShareDesc { int64_t off1, off2, keep; int32_t n1, n2; };   // keep: start of the problem's slice of the keep lists (side 1, then side 2)
 struct GatherJob { int64_t src, dst, keep; int32_t n, pad; };     // one side of an affected problem: pool rows src + keep[.] -> rows dst ..
 
 constexpr int SHARE_TILE = 1024;                                 // ids of the other side staged in LDS at a time (8 KB)
 
-// k_shared_mark: one workgroup (NT = 256) or one wave (NT = 64, every map of the call at most 64 objects) per problem.  A lane
-// holds one object of its own side and walks the other side's ids, staged in LDS in tiles and read as broadcasts (every lane
-// the same address); the comparison is the full 64-bit equality, so every repetition of an id inside a map meets the same
-// fate.  Ranks come from the ballot of the survivors plus the counts of the waves in front: the list is ascending, no atomics.
+// shared_mark_problem: the mark step of problem b by its workgroup of NT threads (NT = 256, or one wave: NT = 64, every map of
+// the call at most 64 objects).  A lane holds one object of its own side and walks the other side's ids, staged in LDS in
+// tiles and read as broadcasts (every lane the same address); the comparison is the full 64-bit equality, so every repetition
+// of an id inside a map meets the same fate.  Ranks come from the ballot of the survivors plus the counts of the waves in
+// front: the list is ascending, no atomics.  -> nKept[side], the same in every thread.
 template <int NT>
-__global__ void __launch_bounds__(NT) k_shared_mark(int B, const ShareDesc* __restrict__ probs, const int64_t* __restrict__ ids,
-                                                    int32_t* __restrict__ keep, int32_t* __restrict__ kept)
+__device__ __forceinline__ void shared_mark_problem(const ShareDesc& P, int b, const int64_t* __restrict__ ids, int32_t* keep,
+                                                    int32_t* __restrict__ kept, int64_t* tile, int* wcnt, int (&nKept)[2])
 {
-    __shared__ int64_t tile[SHARE_TILE];
-    __shared__ int wcnt[NT / 64];
-    const int b = blockIdx.x;
-    if (b >= B) return;
-    const ShareDesc P = probs[b];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
     for (int side = 0; side < 2; ++side) {
@@ -7137,6 +7134,65 @@ __global__ void __launch_bounds__(NT) k_shared_mark(int B, const ShareDesc* __re
             base += total;
         }
         if (tid == 0) kept[2 * b + side] = base;
+        nKept[side] = base;
+    }
+}
+
+// k_shared_mark: the mark step alone, one workgroup (or one wave) per problem.
+template <int NT>
+__global__ void __launch_bounds__(NT) k_shared_mark(int B, const ShareDesc* __restrict__ probs, const int64_t* __restrict__ ids,
+                                                    int32_t* __restrict__ keep, int32_t* __restrict__ kept)
+{
+    __shared__ int64_t tile[SHARE_TILE];
+    __shared__ int wcnt[NT / 64];
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const ShareDesc P = probs[b];
+    int nKept[2];
+    shared_mark_problem<NT>(P, b, ids, keep, kept, tile, wcnt, nKept);
+}
+
+// copy_row: F doubles of one row as 64-bit words by one wave, lanes along the row (bit for bit): V2 (F even, 16-byte aligned
+// base: every row is then 16-byte aligned) moves 16 bytes per lane, otherwise 8.
+template <bool V2>
+__device__ __forceinline__ void copy_row(unsigned long long* __restrict__ d, const unsigned long long* __restrict__ s, int F, int lane)
+{
+    if (V2) {
+        const ulonglong2* s2 = reinterpret_cast<const ulonglong2*>(s);
+        ulonglong2* d2 = reinterpret_cast<ulonglong2*>(d);
+        for (int k = lane; k < (F >> 1); k += 64) d2[k] = s2[k];
+    } else {
+        for (int k = lane; k < F; k += 64) d[k] = s[k];
+    }
+}
+
+// k_shared_reduce: mark and gather of one problem in ONE launch, one workgroup (NT = 256) or one wave (NT = 64) per problem: the
+// host places nothing by a count.  The mark step is shared_mark_problem; behind a workgroup barrier (the keep entries the
+// workgroup wrote are then visible to all its waves) a problem that lost an object on either side copies the kept rows of both
+// sides, in list order, into its FIXED slots of the gather region behind the pool: side 1 at rows region_row0 + P.keep ..,
+// side 2 at rows region_row0 + P.keep + n1 .. — the slot offset is the keep-list offset.  A problem that lost nothing writes no
+// row; rows of a slot behind the kept ones are not written.  Every wave of the workgroup copies (a wave per row): at demo scale a
+// row is about 6 KB and the copy, not the mark, is the time.  `feats`: pool rows, then the region (the pool slices lie in front
+// of region_row0, so no row is read and written).
+template <int NT, bool V2>
+__global__ void __launch_bounds__(NT) k_shared_reduce(int B, int F, const ShareDesc* __restrict__ probs, const int64_t* __restrict__ ids,
+                                                      int32_t* keep, int32_t* __restrict__ kept, unsigned long long* feats, int64_t region_row0)
+{
+    __shared__ int64_t tile[SHARE_TILE];
+    __shared__ int wcnt[NT / 64];
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const ShareDesc P = probs[b];
+    int nKept[2];
+    shared_mark_problem<NT>(P, b, ids, keep, kept, tile, wcnt, nKept);
+    if (nKept[0] == P.n1 && nKept[1] == P.n2) return;            // (uniform) nothing lost: the problem reads the pool as given
+    __syncthreads();                                             // the keep lists of this workgroup are written and visible
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int side = 0; side < 2; ++side) {
+        const int64_t src = side ? P.off2 : P.off1, slot = P.keep + (side ? P.n1 : 0);
+        const int32_t* list = keep + slot;
+        for (int r = wave; r < nKept[side]; r += NT / 64)
+            copy_row<V2>(feats + (region_row0 + slot + r) * (int64_t)F, feats + (src + list[r]) * (int64_t)F, F, lane);
     }
 }
 
@@ -7152,13 +7208,7 @@ __global__ void __launch_bounds__(256) k_shared_gather(int F, const GatherJob* _
     for (int r = blockIdx.y * 4 + wave; r < J.n; r += 4 * gridDim.y) {
         const unsigned long long* s = pool + (J.src + keep[J.keep + r]) * (int64_t)F;
         unsigned long long* d = pool + (J.dst + r) * (int64_t)F;
-        if (V2) {
-            const ulonglong2* s2 = reinterpret_cast<const ulonglong2*>(s);
-            ulonglong2* d2 = reinterpret_cast<ulonglong2*>(d);
-            for (int k = lane; k < (F >> 1); k += 64) d2[k] = s2[k];
-        } else {
-            for (int k = lane; k < F; k += 64) d[k] = s[k];
-        }
+        copy_row<V2>(d, s, F, lane);
     }
 }
 

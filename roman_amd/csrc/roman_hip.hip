@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -2003,23 +2004,57 @@ int align_to_host(roman_ctx* c, const DevParams& D, const roman_params_t* params
 }
 
 // --- shared-segment removal ([REF roman/align/submap_align.py:108-115]) ---------------------------------------------------------
-// k_shared_mark behind whatever is queued on `stream`: a pure enqueue — the problem descriptors travel through pinned staging,
-// and only the previous call's upload out of that staging is waited for.
+// The problem descriptors of a call through pinned staging into c->shareDesc, behind whatever is queued on `stream`: a pure
+// enqueue — only the previous call's upload out of that staging is waited for.  -> the largest map of the call.
+int stage_share_descs(roman_ctx* c, hipStream_t stream, int32_t B, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t* maxN)
+{
+    ShareDesc* staged = nullptr;
+    HIPCHK(c, c->shareStage.stage((size_t)B, &staged));
+    int64_t kb = 0; int32_t m = 0;
+    for (int b = 0; b < B; ++b) {
+        staged[b] = ShareDesc{off1[b], off2[b], kb, n1[b], n2[b]};
+        kb += (int64_t)n1[b] + n2[b];
+        m = std::max(m, std::max(n1[b], n2[b]));
+    }
+    HIPCHK(c, c->shareStage.upload(c->shareDesc, (size_t)B, stream));
+    *maxN = m;
+    return ROMAN_OK;
+}
+
+// k_shared_mark behind whatever is queued on `stream`: a pure enqueue.
 int enqueue_shared_mark(roman_ctx* c, hipStream_t stream, int32_t B, const int64_t* dIds, const int64_t* off1, const int32_t* n1,
                         const int64_t* off2, const int32_t* n2, int32_t* dKeep, int32_t* dKept)
 {
     if (B <= 0) return ROMAN_OK;
-    ShareDesc* staged = nullptr;
-    HIPCHK(c, c->shareStage.stage((size_t)B, &staged));
-    int64_t kb = 0; int32_t maxN = 0;
-    for (int b = 0; b < B; ++b) {
-        staged[b] = ShareDesc{off1[b], off2[b], kb, n1[b], n2[b]};
-        kb += (int64_t)n1[b] + n2[b];
-        maxN = std::max(maxN, std::max(n1[b], n2[b]));
-    }
-    HIPCHK(c, c->shareStage.upload(c->shareDesc, (size_t)B, stream));
+    int32_t maxN = 0;
+    const int rc = stage_share_descs(c, stream, B, off1, n1, off2, n2, &maxN);
+    if (rc) return rc;
     if (maxN <= 64) hipLaunchKernelGGL(k_shared_mark<64>, dim3((unsigned)B), dim3(64), 0, stream, (int)B, c->shareDesc.as<ShareDesc>(), dIds, dKeep, dKept);
     else hipLaunchKernelGGL(k_shared_mark<256>, dim3((unsigned)B), dim3(256), 0, stream, (int)B, c->shareDesc.as<ShareDesc>(), dIds, dKeep, dKept);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+// k_shared_reduce behind whatever is queued on `stream`: mark and gather in one launch, a pure enqueue.  One wave per problem
+// when every map of the call has at most 64 objects, otherwise 256 threads; 16 bytes per lane when every row is 16-byte aligned.
+int enqueue_shared_reduce(roman_ctx* c, hipStream_t stream, int32_t B, int32_t F, double* dFeats, int64_t region_row0, const int64_t* dIds,
+                          const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t* dKeep, int32_t* dKept)
+{
+    if (B <= 0) return ROMAN_OK;
+    int32_t maxN = 0;
+    const int rc = stage_share_descs(c, stream, B, off1, n1, off2, n2, &maxN);
+    if (rc) return rc;
+    const bool v2 = F % 2 == 0 && reinterpret_cast<uintptr_t>(dFeats) % 16 == 0;
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(dFeats);
+    const ShareDesc* descs = c->shareDesc.as<ShareDesc>();
+    const dim3 grid((unsigned)B);
+    if (maxN <= 64) {
+        if (v2) hipLaunchKernelGGL((k_shared_reduce<64, true>), grid, dim3(64), 0, stream, (int)B, (int)F, descs, dIds, dKeep, dKept, words, region_row0);
+        else hipLaunchKernelGGL((k_shared_reduce<64, false>), grid, dim3(64), 0, stream, (int)B, (int)F, descs, dIds, dKeep, dKept, words, region_row0);
+    } else {
+        if (v2) hipLaunchKernelGGL((k_shared_reduce<256, true>), grid, dim3(256), 0, stream, (int)B, (int)F, descs, dIds, dKeep, dKept, words, region_row0);
+        else hipLaunchKernelGGL((k_shared_reduce<256, false>), grid, dim3(256), 0, stream, (int)B, (int)F, descs, dIds, dKeep, dKept, words, region_row0);
+    }
     HIPCHK(c, hipGetLastError());
     return ROMAN_OK;
 }
@@ -2236,6 +2271,25 @@ int roman_shared_ids_dev(roman_ctx_t* c, int32_t B, const int64_t* ids, const in
     if (any && (!ids || !keep)) return fail(c, ROMAN_E_INVALID, "ids / keep is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     return enqueue_shared_mark(c, c->stream, B, ids, off1, n1, off2, n2, keep, kept);
+}
+
+/* Mark and gather in one launch on the context's stream, all bulk pointers DEVICE: a pure enqueue. */
+int roman_shared_reduce_dev(roman_ctx_t* c, int32_t B, int32_t F, double* feats, int64_t region_row0, const int64_t* ids,
+                            const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t* keep, int32_t* kept)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
+    if (F < 1) return fail(c, ROMAN_E_INVALID, "F = %d: a row has at least one column", F);
+    if (region_row0 < 0) return fail(c, ROMAN_E_INVALID, "region_row0 < 0");
+    if (B == 0) return ROMAN_OK;
+    if (!kept) return fail(c, ROMAN_E_INVALID, "kept is NULL");
+    bool any = false;
+    BatchCheck chk; chk.n_objects = region_row0;                 // the pool slices lie in front of the gather region
+    const int rc = check_batch(c, B, off1, n1, off2, n2, chk, &any);
+    if (rc) return rc;
+    if (any && (!feats || !ids || !keep)) return fail(c, ROMAN_E_INVALID, "feats / ids / keep is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_shared_reduce(c, c->stream, B, F, feats, region_row0, ids, off1, n1, off2, n2, keep, kept);
 }
 
 /* roman_align_batch_resident: inputs in HBM (as roman_align_batch_dev), results on the HOST (as roman_align_batch). */

@@ -769,6 +769,17 @@ class Context:
         rc = self._lib.roman_shared_ids_dev(self._h, int(B), vp(ids_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), vp(keep_ptr), vp(kept_ptr))
         self._check(rc, "roman_shared_ids_dev")
 
+    def shared_reduce_dev(self, B, F, feats_ptr, region_row0, ids_ptr, off1, n1, off2, n2, keep_ptr, kept_ptr):
+        """Mark and gather of the shared-segment removal in one launch (roman_shared_reduce_dev): feats (the pool's rows, then a
+        gather region of sum(n1 + n2) rows from row region_row0 on), ids, keep and kept are device addresses (integers), the
+        offsets and sizes host arrays.  A pure enqueue on the context's stream; complete after sync()."""
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_shared_reduce_dev(self._h, int(B), int(F), vp(feats_ptr), int(region_row0), vp(ids_ptr), _ptr(off1), _ptr(n1),
+                                               _ptr(off2), _ptr(n2), vp(keep_ptr), vp(kept_ptr))
+        self._check(rc, "roman_shared_reduce_dev")
+
     def lc_tail_dev(self, lc_params, B, T_ptr, n_assoc_ptr, status_ptr, records_ptr, accepted_idx_ptr, n_accepted_ptr,
                     T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None, FR_ptr=None, iR_ptr=None):
         """The tail on its own over batch outputs in HBM (roman_lc_tail_dev): every pointer a device address (an integer, e.g.
