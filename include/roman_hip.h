@@ -694,7 +694,8 @@ ROMAN_API int roman_ransac_batch(roman_ctx_t* ctx, const roman_ransac_params_t* 
    rows in the submap's gravity-aligned frame — the feature pool the batch calls consume, in fixed slots of `cap` rows per
    submap (submap s owns rows [s*cap, s*cap + count[s])), so offsets are known before the call.  DESIGN.md §4.8 is the contract.
    The centres themselves come from a sequential scan of the trajectory [REF :300-309], which stays on the host
-   (roman_amd.align.submaps.submap_centers), as does the force_fill_submaps mode [REF :264-295] (slices of a time-sorted list).
+   (roman_amd.align.submaps.submap_centers).  The force_fill_submaps mode [REF :264-295] (slices of a time-sorted list) orders
+   its slices on the host too (roman_amd.align.submaps.fill_centers) and gathers them with roman_submaps_fill_dev below.
    The frame-descriptor modes of submap_descriptor [REF :348-355] run behind this call on the same stream: roman_frame_select_dev
    below reads the count and src it wrote. */
 typedef struct roman_submap_params {
@@ -837,15 +838,16 @@ ROMAN_API int roman_ctx_set_stacked_band(roman_ctx_t* ctx, int32_t rows);
    [REF :136] and the descriptor threshold [REF :144-149] — and the pairs that go on to register(), compacted in the order of
    the reference's loop with what the loop-closure tail needs for each (roman_lc_tail_dev's T_ref and enable).  Radius mode,
    vector (1-D) descriptors — mean_semantic, or the means roman_frame_select_dev wrote — or none; stacked frame descriptors go
-   through roman_stacked_sim_dev and roman_grid_gate_sim_dev below.  The AABB mode (force_fill_submaps / no radius) and the
-   shared-segment removal of single_robot_lc stay with the caller.  DESIGN.md §4.9 is the contract.  Bits of flags[]: */
-#define ROMAN_GRID_NEARBY  1   /* dist < 2 * radius (strict): robots_nearby_mat holds dist, submap_yaw_diff_mat the yaw [REF :101-103, :127-129] */
+   through roman_stacked_sim_dev and roman_grid_gate_sim_dev below.  The AABB mode (force_fill_submaps / no radius) is
+   roman_grid_gate_aabb_dev further down; the shared-segment removal of single_robot_lc is roman_shared_reduce_dev
+   (§4.11).  DESIGN.md §4.9 is the contract.  Bits of flags[]: */
+#define ROMAN_GRID_NEARBY  1   /* dist < 2 * radius (strict) — the AABB gate: the boxes intersect —: robots_nearby_mat holds dist, submap_yaw_diff_mat the yaw [REF :101-103, :127-129] */
 #define ROMAN_GRID_SKIP    2   /* dist > skip_distance [REF :136]: no registration, association count 0                                    */
 #define ROMAN_GRID_GATED   4   /* not skipped and sim < desc_thresh [REF :144-149]: the sentinels of [REF :179-184]                         */
 #define ROMAN_GRID_TODO    8   /* neither: the pair is registered; it is in the compact list                                               */
 
 typedef struct roman_grid_gate_params {
-    double  radius;            /* SubmapAlignParams.submap_radius; NaN: ROMAN_E_INVALID; < 0 ("no radius"): ROMAN_E_UNSUPPORTED           */
+    double  radius;            /* SubmapAlignParams.submap_radius; NaN: ROMAN_E_INVALID; < 0 ("no radius"): ROMAN_E_UNSUPPORTED (the AABB gate does not read it) */
     double  skip_distance;     /* SubmapAlignInputOutput.skip_distance; +inf is legal (nothing is skipped)                                  */
     int32_t desc_dim;          /* d: length of a submap descriptor; 0: no descriptor (sim = +inf)                                          */
     int32_t reserved0;         /* must be 0                                                                                                */
@@ -917,6 +919,91 @@ ROMAN_API int roman_grid_gate_sim(roman_ctx_t* ctx, const roman_grid_gate_params
                                   const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1,
                                   double* dist, int32_t* flags, double* yaw_deg, const double* sim, double* T_ij,
                                   int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo);
+
+/* ------------------------------------------------------------------------------------------- */
+/* force-fill submaps, the boxes of a pool and the bounding-box gate                           */
+/* ------------------------------------------------------------------------------------------- */
+
+/* The other way of cutting a map into submaps (force_fill_submaps [REF roman/map/map.py:264-295]: overlapping slices of max_size
+   segments of the time-sorted map) and the other "robots nearby" gate (aabb_intersects over segments_as_global_points,
+   [REF roman/align/submap_align.py:101-103], [REF roman/utils.py:160-169], [REF roman/map/map.py:133-139]: force_fill_submaps or
+   no submap_radius).  DESIGN.md §4.12 is the contract. */
+
+/*
+ * roman_submaps_fill_dev: the gather half of roman_submaps_dev over lists the caller made (the ordering of [REF :267-271] is
+ * sequential and small: roman_amd.align.submaps.fill_centers).  Bulk pointers DEVICE, the descriptors HOST (the library stages
+ * them; pos, time, t_lo and t_hi are not read).  A PURE ENQUEUE on the context's stream.  No membership test, no sort.
+ *   seg_feats  float64[N][F], seg_ids int64[N] or NULL: the map table, as for roman_submaps_dev
+ *   count      int32[S]: rows of each submap, 0 <= count[s] <= cap;  src int32[S*cap]: rows [s*cap, s*cap + count[s]) are map
+ *              indices in [0, N).  The device call trusts both; the host call checks them (ROMAN_E_INVALID)
+ *   pool       float64[S*cap][point_dim + F - 3]: row r of submap s is segment src[s*cap + r], its centre through T_center_odom with
+ *              roman_submaps_dev's arithmetic (((r0 x + r1 y) + r2 z) + t, no fused multiply-adds), every other column bit for bit;
+ *              rows beyond count[s] are not written
+ *   ids_out    int64[S*cap] or NULL (needs seg_ids)
+ *   desc_dim, desc_out   float64[S][desc_dim] or NULL: 'mean_semantic' in output order, as roman_submaps_dev writes it
+ * S == 0 and N == 0 are legal.  Errors: bad dims (point_dim, F < 3, N / S < 0, desc_dim outside [0, F - 3]), cap < 1, a NULL
+ * pointer that is needed -> ROMAN_E_INVALID.
+ */
+ROMAN_API int roman_submaps_fill_dev(roman_ctx_t* ctx, int32_t point_dim, int32_t cap, int32_t N, int32_t F,
+                                     const double* seg_feats, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
+                                     const int32_t* count, const int32_t* src, double* pool, int64_t* ids_out,
+                                     int32_t desc_dim, double* desc_out);
+
+/* The same with HOST pointers everywhere.  Synchronous; pool may be NULL (only ids_out / desc_out come back).  The caller's pool,
+   ids_out and desc_out go up first: what the device call leaves untouched comes back as it was. */
+ROMAN_API int roman_submaps_fill(roman_ctx_t* ctx, int32_t point_dim, int32_t cap, int32_t N, int32_t F,
+                                 const double* seg_feats, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
+                                 const int32_t* count, const int32_t* src, double* pool, int64_t* ids_out,
+                                 int32_t desc_dim, double* desc_out);
+
+/*
+ * roman_submap_boxes_dev: what aabb_intersects reads of Submap.segments_as_global_points [REF roman/map/map.py:133-139] for the
+ * S submaps of a pool.  Every pointer DEVICE; a PURE ENQUEUE on the context's stream.
+ *   pool       float64[S*cap][F], F >= 3: the first three columns of rows [s*cap, s*cap + count[s]) are read (a pool built
+ *              with point_dim 2 holds no z and cannot be used)
+ *   count      int32[S]
+ *   T_odom_center  float64[S][16] row-major 4x4: the pose that takes submap s to the global frame (the caller resolves
+ *              ground truth or not, as has_gt does [REF :138])
+ *   box        float64[S][6] = (min x, min y, min z, max x, max y, max z) of the rows' points in the global frame, each component
+ *              ((r0 x + r1 y) + r2 z) + t, without fused multiply-adds.  min / max of finite doubles are exact and order-free: two
+ *              calls agree bit for bit.  count[s] == 0: (+inf, +inf, +inf, -inf, -inf, -inf) — never nearby.
+ * Inputs must be finite.  S == 0 is legal.  Errors: S < 0, F < 3, cap < 1, a NULL pointer that is needed -> ROMAN_E_INVALID.
+ */
+ROMAN_API int roman_submap_boxes_dev(roman_ctx_t* ctx, int32_t S, int32_t F, int32_t cap, const double* pool, const int32_t* count,
+                                     const double* T_odom_center, double* box);
+
+/* The same with HOST pointers everywhere.  Synchronous. */
+ROMAN_API int roman_submap_boxes(roman_ctx_t* ctx, int32_t S, int32_t F, int32_t cap, const double* pool, const int32_t* count,
+                                 const double* T_odom_center, double* box);
+
+/*
+ * roman_grid_gate_aabb_dev: roman_grid_gate_dev with the bounding-box gate [REF roman/align/submap_align.py:101-103].  The first
+ * 23 arguments are roman_grid_gate_dev's; then
+ *   box0 float64[S0][6], box1 float64[S1][6]: as roman_submap_boxes_dev wrote them.  NEARBY(i, j) is the six comparisons of
+ *              [REF roman/utils.py:167-169]: min0 <= max1 and max0 >= min1 on every axis — <= and >= as they stand: touching boxes
+ *              intersect; an empty submap's box intersects nothing.  gparams->radius is NOT read (any value, NaN included)
+ *   sim_in     float64[S0*S1] or NULL.  Given: the similarity of every pair is already there (roman_stacked_sim_dev's), read as
+ *              roman_grid_gate_sim_dev reads it and never written; gparams->desc_dim must then be 0 (ROMAN_E_INVALID otherwise),
+ *              desc0 / desc1 are not read and `sim` is not written (it may be NULL)
+ * Everything else is roman_grid_gate_dev's contract, untouched: dist, T_ij, yaw_deg for NEARBY pairs only, sim, SKIP / GATED / TODO,
+ * the compact list of the TODO pairs in row-major order by a prefix sum (no atomics), T_ref, enable, the untouched slots, the
+ * errors — without those of the radius, plus box NULL -> ROMAN_E_INVALID.  Every pointer DEVICE; a PURE ENQUEUE on the context's stream.
+ */
+ROMAN_API int roman_grid_gate_aabb_dev(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                                       const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                                       const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                                       double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                       int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo,
+                                       const double* box0, const double* box1, const double* sim_in);
+
+/* The same with HOST pointers everywhere.  Synchronous: copies in, runs roman_grid_gate_aabb_dev, brings every output back (sim
+   only without sim_in).  The caller's pairs, T_ref and enable go up first: the slots beyond n_todo come back as they were. */
+ROMAN_API int roman_grid_gate_aabb(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                                   const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                                   const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                                   double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                   int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo,
+                                   const double* box0, const double* box1, const double* sim_in);
 
 /* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */

@@ -652,8 +652,15 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     §4.11: the ids build_submap_pool kept on the device, one launch, 8 bytes per pair back); returned associations index the
     reduced lists, as the reference's do.  Pools that share no id take the path without it.
 
-    Not covered — ValueError; SubmapPool.to_submaps() + submap_align_grid is the way: force_fill_submaps / no submap_radius (the
-    AABB gate), RansacReg, registration plugins with a host prefilter, shared ids over pools without `ids_dev`.
+    force_fill_submaps / no submap_radius: the gate is aabb_intersects over segments_as_global_points
+    [REF :101-103].  Per side the host resolves T_odom_center (the ground-truth pose where gt_poses[r] is given, as `has_gt` does
+    [REF roman/map/map.py:138]); roman_submap_boxes_dev reduces every submap of either pool to its box, roman_grid_gate_aabb_dev
+    is the gate — behind roman_stacked_sim_dev for stacked descriptors — all on the context's stream.  Pools built by
+    build_submap_pool(fill=...) (force-fill slices) and radius-mode pools are served alike.
+
+    Not covered — ValueError; SubmapPool.to_submaps() + submap_align_grid is the way: the AABB gate over pools with dim 2 (their
+    rows hold no z) or a context without roman_grid_gate_aabb_dev, RansacReg, registration plugins with a host prefilter, shared
+    ids over pools without `ids_dev`.
 
     Frame descriptors need pools built with them (build_submap_pool(frames=...)): 'mean_frame_descriptor' goes
     through the same gate as 'mean_semantic'; 'stacked_frame_descriptors' through roman_stacked_sim_dev over the two pools' frame
@@ -669,8 +676,7 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         raise ValueError("pools must hold two SubmapPool objects")
     if isinstance(registration, RansacReg):
         raise ValueError("RansacReg has no device tail" + way)
-    if sm_params.force_fill_submaps or sm_params.submap_radius is None:
-        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes" + way)
+    aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
     mode = sm_params.submap_descriptor
     stacked = mode == 'stacked_frame_descriptors'
     if mode not in (None, 'mean_semantic', 'mean_frame_descriptor', 'stacked_frame_descriptors'):
@@ -693,6 +699,10 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         if sm_io.gt_available[r] and gt_poses[r] is None:
             raise ValueError(f"sm_io.gt_available[{r}] is set without gt_poses[{r}]")
     ctx = registration._context()
+    if aabb_mode and not (hasattr(ctx, "grid_gate_aabb_dev") and hasattr(ctx, "submap_boxes_dev")):
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes" + way)
+    if aabb_mode and any(int(q.table.point_dim) != 3 for q in p):
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes, and pools of dim 2 hold no z" + way)
     # self loop closures over submaps that share segment ids: the removal of [REF :108-115] runs over the resident pools too
     # (roman_shared_reduce_dev) — with the ids build_submap_pool left on the device
     shared = bool(sm_params.single_robot_lc) and (p[0] is p[1] or np.intersect1d(p[0].ids[p[0].src >= 0], p[1].ids[p[1].src >= 0]).size > 0)
@@ -721,11 +731,15 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
                       pose_flu_gt=None if gt is None else gt[s].copy()) for s in keep[r]]
         pos = np.stack([np.array(sm.position) for sm in sms])
         pos_gt = None if gt is None else np.stack([np.array(sm.position_gt) for sm in sms])
+        # the AABB gate reads the pose once more per submap, in front of the pair loop (segments_as_global_points, by has_gt
+        # [REF roman/map/map.py:138]).  The pools' poses are yaw-only COPIES already, so how often the pair loop flattens them in
+        # place does not matter here: _read_times below stops at the fixed point either way
+        T_oc = None if not aabb_mode else np.stack([np.array(sm.pose_gravity_aligned_gt if sm.has_gt else sm.pose_gravity_aligned, dtype=np.float64) for sm in sms])
         read = ("pose_gravity_aligned_gt", "pose_flu_gt") if sm_io.gt_available[r] else ("pose_gravity_aligned", "pose_flu")
         T_w = np.stack([np.array(_read_times(sm, *read, other[r]), dtype=np.float64) for sm in sms])
         times = np.array([sm.time for sm in sms], dtype=np.float64)
         frames.append(np.stack([_edge_frames(sm)[r] for sm in sms]))
-        side.append(dict(pos=up(pos), gt=up(pos_gt), T_w=up(T_w.reshape(-1, 16)), time=up(times),
+        side.append(dict(pos=up(pos), gt=up(pos_gt), T_w=up(T_w.reshape(-1, 16)), time=up(times), T_oc=None if T_oc is None else up(T_oc.reshape(-1, 16)),
                          desc=p[r].desc_dev[torch.from_numpy(keep[r].astype(np.int64)).to(dev)].contiguous() if d else None))
 
     # ---- pass 1 on the device: one enqueue, one synchronisation, the pair list and the dense matrices back ----
@@ -735,11 +749,27 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     if stacked:
         gp.desc_thresh = float(sm_params.submap_descriptor_thresh)
         masks = [q.frame_mask[torch.from_numpy(k.astype(np.int64)).to(dev)].contiguous() for q, k in zip(p, keep)]     # rows gathered on the device
+    if aabb_mode:                                            # the boxes of the non-empty submaps of either pool: slot rows and counts gathered per kept submap
+        boxes = [torch.empty((len(k), 6), dtype=torch.float64, device=dev) for k in keep]
+        counts = [up(q.count[k].astype(np.int32)) for q, k in zip(p, keep)]
+        slots = [q.pool if len(k) == len(q.count) else
+                 q.pool.reshape(len(q.count), q.cap, -1)[torch.from_numpy(k.astype(np.int64)).to(dev)].reshape(len(k) * q.cap, -1).contiguous() for q, k in zip(p, keep)]
     wait_torch()                                             # the uploads are in place before the library's stream reads them
+    if aabb_mode:
+        for r in range(2):
+            ctx.submap_boxes_dev(len(keep[r]), int(slots[r].shape[1]), p[r].cap, slots[r].data_ptr(), counts[r].data_ptr(), side[r]["T_oc"].data_ptr(),
+                                 boxes[r].data_ptr())
     if stacked:                                              # similarity first, then the gate that reads it: both on the context's stream
         fd = [q.frame_desc_dev for q in p]
         ctx.stacked_sim_dev(int(fd[0].shape[1]), int(fd[0].shape[0]), ptr(fd[0]), n0, ptr(masks[0]), int(fd[1].shape[0]), ptr(fd[1]), n1, ptr(masks[1]),
                             g["sim"].data_ptr())
+    if aabb_mode:
+        outs = [t.data_ptr() for t in g.values()]
+        ctx.grid_gate_aabb_dev(gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *outs,
+                               box0_ptr=boxes[0].data_ptr(), box1_ptr=boxes[1].data_ptr(), sim_in_ptr=g["sim"].data_ptr() if stacked else None,
+                               time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), desc0_ptr=ptr(side[0]["desc"]), desc1_ptr=ptr(side[1]["desc"]),
+                               pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
+    elif stacked:
         ctx.grid_gate_sim_dev(gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *[t.data_ptr() for t in g.values()],
                               time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
     else:

@@ -9,7 +9,11 @@ submap: exactly what roman_align_batch_dev / roman_align_batch_resident / roman_
 With a `FrameTable` the frame-descriptor modes [REF roman/map/map.py:210-242] run behind it on the same stream (roman_frame_select_dev,
 DESIGN.md §4.10): which frames every submap holds, as bit masks that stay on the device, and their mean.
 No segment object is copied; `SubmapPool.to_submaps` hands out light views for the host-side callers (`submap_align_grid`, the
-writers).  The force_fill_submaps mode [REF :264-295] is plain slicing of a time-sorted list and is not covered.
+writers).
+
+The force_fill_submaps mode [REF :264-295] — overlapping slices of max_size segments of the time-sorted map — is covered too
+(DESIGN.md §4.12): its ordering is sequential and small and stays on the host (`fill_centers`), and `build_submap_pool(...,
+fill=slices)` gathers the slices with roman_submaps_fill_dev, the gather half of roman_submaps_dev, into the same kind of pool.
 
 torch is used for device memory only; nothing numerical happens here.
 """
@@ -43,6 +47,23 @@ class SubmapParams:
         return cls(max_size=p.submap_max_size, radius=p.submap_radius, distance=p.submap_center_dist,
                    time_threshold=p.submap_center_time, pruning_method=p.submap_pruning_method,
                    submap_descriptor=p.submap_descriptor, frame_descriptor_dist=p.frame_descriptor_dist)
+
+
+@dataclass
+class FillSubmapParams:
+    """The fields of [REF roman/map/map.py:165-178] the force_fill_submaps mode reads."""
+    max_size: int = 40
+    overlap: int = 20
+    submap_descriptor: Optional[str] = None
+    frame_descriptor_dist: Optional[float] = None
+
+    @classmethod
+    def from_submap_align_params(cls, p):
+        """[REF roman/map/map.py:180-192]"""
+        if not p.force_fill_submaps:
+            raise ValueError("force_fill_submaps is not set: SubmapParams.from_submap_align_params serves the radius mode")
+        return cls(max_size=p.submap_max_size, overlap=p.submap_overlap, submap_descriptor=p.submap_descriptor,
+                   frame_descriptor_dist=p.frame_descriptor_dist)
 
 
 @dataclass
@@ -87,6 +108,34 @@ def submap_centers(trajectory, times, params) -> SubmapCenters:
     t_lo = np.concatenate([[-np.inf], tm[:-1] - params.time_threshold])[:S]
     t_hi = np.concatenate([tm[1:] + params.time_threshold, [np.inf]])[-S:] if S else np.zeros(0)
     return SubmapCenters(np.array(idx, dtype=np.int64), tm, flat, inv, t_lo, t_hi)
+
+
+def fill_centers(table, trajectory, times, fparams):
+    """The force_fill_submaps mode of [REF roman/map/map.py:264-295] up to the gather: the segments of `table` in a stable order of
+    their reference time (first_seen + last_seen) / 2 (Python's sorted() is stable [REF :267]), cut into slices order[i : i + max_size]
+    for i in range(0, N, max_size - overlap) [REF :269-271]; a submap's time is the trajectory time nearest to the mean of its
+    slice's reference times [REF :274-278], its pose a flattened COPY of that trajectory pose (as in `submap_centers`: the caller's
+    trajectory is not changed).  -> (SubmapCenters, list of (n_s,) int32 index arrays, one per submap, in output order).
+    t_lo / t_hi are -inf / +inf: this mode has no time window."""
+    max_size, overlap = int(fparams.max_size), int(fparams.overlap)
+    step = max_size - overlap
+    if step < 1:
+        raise ValueError(f"max_size - overlap = {step}: range() needs a step >= 1 [REF roman/map/map.py:269]")
+    if max_size < 1:
+        raise ValueError("max_size must be >= 1")
+    key = (table.times[:, 0] + table.times[:, 1]) / 2.0
+    order = np.argsort(key, kind='stable')
+    times = np.asarray(times, dtype=np.float64).reshape(-1)
+    slices, idx = [], []
+    for i in range(0, len(order), step):
+        sl = order[i:i + max_size]
+        slices.append(sl.astype(np.int32))
+        idx.append(int(np.argmin(np.abs(times - np.average(key[sl])))))
+    S = len(idx)
+    tm = times[idx] if S else np.zeros(0)
+    flat = np.array([transform_rm_roll_pitch(np.array(trajectory[i], dtype=np.float64)) for i in idx]).reshape(S, 4, 4)
+    inv = np.array([np.linalg.inv(T) for T in flat]).reshape(S, 4, 4)
+    return SubmapCenters(np.array(idx, dtype=np.int64), np.array(tm, dtype=np.float64), flat, inv, np.full(S, -np.inf), np.full(S, np.inf)), slices
 
 
 @dataclass
@@ -256,8 +305,8 @@ def submap_call_params(table: MapTable, params: SubmapParams, cap=None) -> _abi.
     return P
 
 
-def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, params: SubmapParams, ctx=None, device=None, cap=None,
-                      frames: Optional[FrameTable] = None) -> SubmapPool:
+def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, params, ctx=None, device=None, cap=None,
+                      frames: Optional[FrameTable] = None, fill=None) -> SubmapPool:
     """The submaps of `table` around `centers` as a device-resident feature pool: ONE roman_submaps_dev call (membership, prune,
     order, transform, gather, mean_semantic descriptors), then one synchronisation that brings count, src, ids, status and the
     descriptors to the host.  The table is uploaded here (once per call); the pool never leaves the device.
@@ -265,12 +314,27 @@ def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, par
     `frames` (a FrameTable) serves submap_descriptor 'mean_frame_descriptor' / 'stacked_frame_descriptors' with
     params.frame_descriptor_dist [REF roman/map/map.py:210-242]: the frame table goes up once, roman_frame_select_dev runs behind
     roman_submaps_dev on the same stream, and the pool keeps frame_mask, frame_n and frame_desc_dev (the mean mode fills desc /
-    desc_dev as mean_semantic does).  A non-empty submap that selects no frame is a ValueError: the reference fails on it."""
+    desc_dev as mean_semantic does).  A non-empty submap that selects no frame is a ValueError: the reference fails on it.
+
+    `fill` (the slices of `fill_centers`, with its centres as `centers` and a FillSubmapParams as `params`): the force_fill_submaps
+    mode [REF roman/map/map.py:264-295].  count and src come from the slices and go up; roman_submaps_fill_dev — the gather half
+    of roman_submaps_dev, no membership test, no sort — writes the pool, the ids and the mean_semantic descriptors.  The result
+    is an ordinary SubmapPool: the frame modes, to_submaps, grid_batch and submap_align_pools read it as any other."""
     import torch
     ctx = ctx or registration._context()
     dev = torch.device(device if device is not None else f"cuda:{getattr(ctx, 'device', 0)}")
     on_host = dev.type == "cpu"                                              # CPU tensors + a stand-in context (tests)
-    P = submap_call_params(table, params, cap)
+    if fill is not None:
+        if len(fill) != len(centers):
+            raise ValueError("fill must hold one slice per centre")
+        P = _abi.RomanSubmapParams()
+        P.point_dim, P.max_size, P.cap = table.point_dim, int(params.max_size), int(params.max_size)
+        if P.cap < 1 or any(len(sl) > P.cap for sl in fill):
+            raise ValueError("a slice is longer than max_size")
+        if any(len(sl) and (int(np.min(sl)) < 0 or int(np.max(sl)) >= len(table)) for sl in fill):
+            raise ValueError("a slice holds an index outside the map")
+    else:
+        P = submap_call_params(table, params, cap)
     S, N, F = len(centers), len(table), int(table.feats.shape[1])
     d = 0
     if params.submap_descriptor == 'mean_semantic':
@@ -290,7 +354,14 @@ def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, par
     feats = torch.from_numpy(table.feats).to(dev); times = torch.from_numpy(table.times).to(dev); ids = torch.from_numpy(table.ids).to(dev)
     pool = torch.zeros((rows, Fo), dtype=torch.float64, device=dev)
     count = torch.zeros(max(S, 1), dtype=torch.int32, device=dev); status = torch.zeros(max(S, 1), dtype=torch.int32, device=dev)
-    src = torch.full((max(rows, 1),), -1, dtype=torch.int32, device=dev); ids_out = torch.full((max(rows, 1),), -1, dtype=torch.int64, device=dev)
+    if fill is None:
+        src = torch.full((max(rows, 1),), -1, dtype=torch.int32, device=dev)
+    else:                                                                    # the lists are the input here: count and src go up
+        src_h = np.full((max(S, 1), P.cap), -1, dtype=np.int32); count_h = np.zeros(max(S, 1), dtype=np.int32)
+        for s_, sl in enumerate(fill):
+            src_h[s_, :len(sl)] = sl; count_h[s_] = len(sl)
+        src = torch.from_numpy(src_h.reshape(-1)).to(dev); count = torch.from_numpy(count_h).to(dev)
+    ids_out = torch.full((max(rows, 1),), -1, dtype=torch.int64, device=dev)
     desc = torch.full((max(S, 1), max(d, 1)), float("nan"), dtype=torch.float64, device=dev)
     if framed:
         Nf, W = len(frames), (len(frames) + 63) // 64
@@ -300,9 +371,14 @@ def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, par
         f_n = torch.zeros(max(S, 1), dtype=torch.int32, device=dev); f_span = torch.zeros((max(S, 1), 2), dtype=torch.float64, device=dev)
     if not on_host:
         torch.cuda.current_stream(dev).synchronize()                         # inputs and cleared outputs are in place before the library's stream touches them
-    ctx.submaps_dev(P, N, F, feats.data_ptr(), times.data_ptr(), centers.descs(), pool.data_ptr(), count.data_ptr(), src.data_ptr(),
-                    status.data_ptr(), seg_ids_ptr=ids.data_ptr(), ids_out_ptr=ids_out.data_ptr(), desc_dim=0 if framed else d,
-                    desc_out_ptr=desc.data_ptr() if d and not framed else None)
+    if fill is not None:
+        ctx.submaps_fill_dev(P.point_dim, P.cap, N, F, feats.data_ptr(), centers.descs(), count.data_ptr(), src.data_ptr(), pool.data_ptr(),
+                             seg_ids_ptr=ids.data_ptr(), ids_out_ptr=ids_out.data_ptr(), desc_dim=0 if framed else d,
+                             desc_out_ptr=desc.data_ptr() if d and not framed else None)
+    else:
+        ctx.submaps_dev(P, N, F, feats.data_ptr(), times.data_ptr(), centers.descs(), pool.data_ptr(), count.data_ptr(), src.data_ptr(),
+                        status.data_ptr(), seg_ids_ptr=ids.data_ptr(), ids_out_ptr=ids_out.data_ptr(), desc_dim=0 if framed else d,
+                        desc_out_ptr=desc.data_ptr() if d and not framed else None)
     if framed and S:                                                         # behind it on the same stream: reads the count and src it wrote
         ctx.frame_select_dev(frame_select_params(thin, mean_frames), S, P.cap, count.data_ptr(), src.data_ptr(), N, times.data_ptr(), Nf,
                              f_times.data_ptr(), f_mask.data_ptr(), f_n.data_ptr(), f_span.data_ptr(), frame_pos_ptr=f_pos.data_ptr(),

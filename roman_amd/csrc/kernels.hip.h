@@ -7365,6 +7365,38 @@ __global__ void __launch_bounds__(256) k_submap_desc(int cap, int F, int d, cons
     desc_out[(int64_t)s * d + c] = acc / (double)n;
 }
 
+// Submap.segments_as_global_points [REF roman/map/map.py:133-139] reduced to what aabb_intersects [REF roman/utils.py:160-169] reads
+// of it: ONE WAVE per submap takes rows [s * cap, s * cap + count[s]) of the pool to the global frame with the submap's
+// T_odom_center — each component ((r0 x + r1 y) + r2 z) + t, k_submap_gather's arithmetic — and reduces them to
+// box[s] = (min x, min y, min z, max x, max y, max z).  Rows beyond 64 are taken in further steps of the same wave; min and max of
+// finite doubles are exact and order-free, so the butterfly's order is free.  An empty submap: (+inf x 3, -inf x 3), never nearby.
+__global__ void __launch_bounds__(256) k_submap_boxes(int S, int F, int cap, const double* __restrict__ pool, const int32_t* __restrict__ count,
+                                                      const double* __restrict__ T_odom_center, double* __restrict__ box)
+{
+    const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= S) return;                                          // (wave-uniform)
+    const double* T = T_odom_center + 16 * (int64_t)s;
+    const int n = max(0, min(count[s], cap));                    // (a count outside its slot reads nothing beyond it)
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int r = lane; r < n; r += 64) {
+        const double* p = pool + ((int64_t)s * cap + r) * F;
+        const double x = p[0], y = p[1], z = p[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double v = ((T[4 * c] * x + T[4 * c + 1] * y) + T[4 * c + 2] * z) + T[4 * c + 3];
+            lo[c] = fmin(lo[c], v); hi[c] = fmax(hi[c], v);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) { lo[c] = fmin(lo[c], __shfl_xor(lo[c], off)); hi[c] = fmax(hi[c], __shfl_xor(hi[c], off)); }
+    if (lane < 3) {
+        const double l = lane == 0 ? lo[0] : (lane == 1 ? lo[1] : lo[2]), h = lane == 0 ? hi[0] : (lane == 1 ? hi[1] : hi[2]);
+        box[6 * (int64_t)s + lane] = l; box[6 * (int64_t)s + 3 + lane] = h;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // pass 1 of the pair loop for a whole S0 x S1 grid ([REF roman/align/submap_align.py:93-149], radius mode):
 // distance and radius gate, reference transform, yaw difference, submap-descriptor similarity, the skip / gated / todo
@@ -7374,7 +7406,9 @@ __global__ void __launch_bounds__(256) k_submap_desc(int cap, int F, int d, cons
 //   k_grid_gate     a wave per (i, GRID_TJ consecutive j): lane l walks components l, l + 64, ... of descriptor i ONCE against
 //                   GRID_TJ descriptors of the other side (coalesced 512-byte row pieces, GRID_TJ independent sums), a butterfly
 //                   adds the 64 partial sums — a fixed order, no atomics: two runs agree bit for bit —, then lane t finishes pair
-//                   (i, j0 + t): a few dozen f64 operations and the dense outputs;
+//                   (i, j0 + t): a few dozen f64 operations and the dense outputs.  With AABB (roman_grid_gate_aabb*, DESIGN.md
+//                   §4.12) NEARBY is the six comparisons of aabb_intersects [REF roman/utils.py:167-169] on the two submaps'
+//                   boxes (k_submap_boxes) instead of dist < 2 * radius; nothing else changes;
 //   k_grid_compact  one workgroup: the TODO pairs in row-major order through block_excl_scan (k_lc_compact's idiom);
 //   k_grid_fill     16 threads per compact slot: T_ref <- T_ij of the slot's pair, bit for bit, and the time gate
 //                   [REF roman/align/results.py:160-162].  Slots beyond n_todo are not written.
@@ -7382,7 +7416,7 @@ __global__ void __launch_bounds__(256) k_submap_desc(int cap, int F, int d, cons
 constexpr int GRID_TJ = 4;                                       // pairs of one row a wave of k_grid_gate handles
 constexpr int GRID_NEARBY = 1, GRID_SKIP = 2, GRID_GATED = 4, GRID_TODO = 8;    // ROMAN_GRID_* of roman_hip.h
 
-struct GridSide { const double* pos; const double* pos_gt; const double* T_w; const double* time; const double* desc; };
+struct GridSide { const double* pos; const double* pos_gt; const double* T_w; const double* time; const double* desc; const double* box; };
 struct GridOut { double* dist; int32_t* flags; double* yaw_deg; double* sim; double* T_ij; };
 
 // sum over the 64 lanes, the same bits in every lane (x + y == y + x)
@@ -7406,7 +7440,8 @@ __global__ void __launch_bounds__(256) k_grid_norms(int S0, int S1, int d, const
 }
 
 // SIM_IN (roman_grid_gate_sim*): the similarity of every pair is already in out.sim — read, never written — and no descriptor is touched
-template <bool SIM_IN>
+// AABB (roman_grid_gate_aabb*): NEARBY from a.box[i] and b.box[j] (float64[6]: min x y z, max x y z), P.radius is not read
+template <bool SIM_IN, bool AABB>
 __global__ void __launch_bounds__(256) k_grid_gate(roman_grid_gate_params_t P, int S0, int S1, GridSide a, GridSide b,
                                                    const double* __restrict__ norm, GridOut out)
 {
@@ -7443,7 +7478,12 @@ __global__ void __launch_bounds__(256) k_grid_gate(roman_grid_gate_params_t P, i
     const double* pb = (gt ? b.pos_gt : b.pos) + 3 * (int64_t)j;
     const double dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
     const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
-    const bool nearby = dist < 2.0 * P.radius;
+    bool nearby;
+    if (AABB) {                                                  // <= and >= as they stand: touching boxes intersect [REF roman/utils.py:167-169]
+        const double* A = a.box + 6 * (int64_t)i;
+        const double* Bx = b.box + 6 * (int64_t)j;
+        nearby = A[0] <= Bx[3] && A[3] >= Bx[0] && A[1] <= Bx[4] && A[4] >= Bx[1] && A[2] <= Bx[5] && A[5] >= Bx[2];
+    } else nearby = dist < 2.0 * P.radius;
     double Ti[16], T[16];
     lc_inv_affine(a.T_w + 16 * (int64_t)i, Ti);
     lc_mul4(Ti, b.T_w + 16 * (int64_t)j, T);

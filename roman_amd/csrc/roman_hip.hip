@@ -2644,26 +2644,167 @@ int roman_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t 
     return ROMAN_OK;
 }
 
+// --- force-fill submaps and the boxes of a pool ([REF roman/map/map.py:264-295], [REF :133-139]) -------------------
+static int submaps_fill_check(roman_ctx* c, int32_t point_dim, int32_t cap, int32_t N, int32_t F, const void* seg_feats, const void* seg_ids,
+                              int32_t S, const void* descs, const void* count, const void* src, const void* pool, const void* ids_out,
+                              int32_t desc_dim, const void* desc_out, bool pool_needed)
+{
+    if (point_dim != 2 && point_dim != 3) return fail(c, ROMAN_E_INVALID, "point_dim must be 2 or 3 (got %d)", point_dim);
+    if (N < 0 || S < 0) return fail(c, ROMAN_E_INVALID, "N < 0 or S < 0");
+    if (F < 3) return fail(c, ROMAN_E_INVALID, "F=%d: a segment row starts with x y z", F);
+    if (cap < 1) return fail(c, ROMAN_E_INVALID, "cap must be >= 1 (got %d)", cap);
+    if (desc_dim < 0 || desc_dim > F - 3) return fail(c, ROMAN_E_INVALID, "desc_dim=%d outside [0, F - 3]", desc_dim);
+    if (desc_out && desc_dim == 0) return fail(c, ROMAN_E_INVALID, "desc_out given with desc_dim 0");
+    if (ids_out && !seg_ids) return fail(c, ROMAN_E_INVALID, "ids_out given without seg_ids");
+    if (S == 0) return ROMAN_OK;
+    if (!descs || !count || !src || (pool_needed && !pool)) return fail(c, ROMAN_E_INVALID, "NULL descriptor, count, src or pool pointer");
+    if (N > 0 && !seg_feats) return fail(c, ROMAN_E_INVALID, "seg_feats is NULL");
+    return ROMAN_OK;
+}
+
+int roman_submaps_fill_dev(roman_ctx_t* c, int32_t point_dim, int32_t cap, int32_t N, int32_t F,
+                           const double* seg_feats, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
+                           const int32_t* count, const int32_t* src, double* pool, int64_t* ids_out, int32_t desc_dim, double* desc_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = submaps_fill_check(c, point_dim, cap, N, F, seg_feats, seg_ids, S, descs, count, src, pool, ids_out, desc_dim, desc_out, true);
+    if (rc || S == 0 || N == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    roman_submap_desc_t* staged = nullptr;
+    HIPCHK(c, c->smStage.stage((size_t)S, &staged));
+    memcpy(staged, descs, sizeof(roman_submap_desc_t) * (size_t)S);
+    HIPCHK(c, c->smStage.upload(c->smDesc, (size_t)S, stream));
+    const roman_submap_desc_t* dDesc = c->smDesc.as<roman_submap_desc_t>();
+    // the gather half of roman_submaps_dev, launched as there
+    const unsigned groups = (unsigned)std::min(64, (std::min(cap, N) + 3) / 4);
+    hipLaunchKernelGGL(k_submap_gather, dim3((unsigned)S, groups), dim3(256), 0, stream, (int)point_dim, (int)cap, (int)F, dDesc,
+                       reinterpret_cast<const unsigned long long*>(seg_feats), seg_ids, count, src, reinterpret_cast<unsigned long long*>(pool), ids_out);
+    if (desc_out) hipLaunchKernelGGL(k_submap_desc, dim3((unsigned)S, (unsigned)((desc_dim + 255) / 256)), dim3(256), 0, stream, (int)cap, (int)F, (int)desc_dim,
+                                     seg_feats, count, src, desc_out);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_submaps_fill(roman_ctx_t* c, int32_t point_dim, int32_t cap, int32_t N, int32_t F,
+                       const double* seg_feats, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
+                       const int32_t* count, const int32_t* src, double* pool, int64_t* ids_out, int32_t desc_dim, double* desc_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = submaps_fill_check(c, point_dim, cap, N, F, seg_feats, seg_ids, S, descs, count, src, pool, ids_out, desc_dim, desc_out, false);
+    if (rc || S == 0) return rc;
+    // the host holds the lists: every row a map index, every count inside its slot
+    for (int32_t s = 0; s < S; ++s) {
+        if (count[s] < 0 || count[s] > cap) return fail(c, ROMAN_E_INVALID, "count[%d]=%d outside [0, cap]", s, count[s]);
+        for (int32_t r = 0; r < count[s]; ++r) {
+            const int32_t k = src[(size_t)s * (size_t)cap + (size_t)r];
+            if (k < 0 || k >= N) return fail(c, ROMAN_E_INVALID, "src[%d][%d]=%d is not a map index", s, r, k);
+        }
+    }
+    if (N == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    c->last.scored = false; c->last.solved = false;            // workspace 0's feature staging is reused: the stepwise problem it held is gone
+    const double* dFeats = nullptr;
+    rc = upload_inputs(c, seg_feats, N, F, 0, nullptr, 0, &dFeats);
+    if (rc) return rc;
+    // the other arrays on the device, 8-byte blocks first: ids | pool | ids_out | desc_out | src | count
+    const size_t rows = (size_t)S * (size_t)cap, Fo = (size_t)(point_dim + F - 3);
+    const size_t bIds = seg_ids ? sizeof(int64_t) * (size_t)N : 0, bPool = pool ? sizeof(double) * rows * Fo : 0, bIdsOut = ids_out ? sizeof(int64_t) * rows : 0,
+                 bDesc = desc_out ? sizeof(double) * (size_t)S * (size_t)desc_dim : 0, bSrc = sizeof(int32_t) * rows, bCnt = sizeof(int32_t) * (size_t)S;
+    const size_t oIds = 0, oPool = oIds + bIds, oIdsOut = oPool + sizeof(double) * rows * Fo, oDesc = oIdsOut + bIdsOut, oSrc = oDesc + bDesc, oCnt = oSrc + bSrc,
+                 total = oCnt + bCnt;
+    HIPCHK(c, c->smHost.ensure(std::max<size_t>(total, 8)));
+    char* const dev = c->smHost.as<char>();
+    double* dPool = reinterpret_cast<double*>(dev + oPool);
+    int64_t* dIdsOut = ids_out ? reinterpret_cast<int64_t*>(dev + oIdsOut) : nullptr;
+    double* dDescOut = desc_out ? reinterpret_cast<double*>(dev + oDesc) : nullptr;
+    if (bIds) HIPCHK(c, hipMemcpyAsync(dev + oIds, seg_ids, bIds, hipMemcpyHostToDevice, WS.stream));
+    // the caller's outputs go up first: what the device call leaves untouched comes back as it was
+    if (bPool) HIPCHK(c, hipMemcpyAsync(dPool, pool, bPool, hipMemcpyHostToDevice, WS.stream));
+    if (bIdsOut) HIPCHK(c, hipMemcpyAsync(dIdsOut, ids_out, bIdsOut, hipMemcpyHostToDevice, WS.stream));
+    if (bDesc) HIPCHK(c, hipMemcpyAsync(dDescOut, desc_out, bDesc, hipMemcpyHostToDevice, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(dev + oSrc, src, bSrc, hipMemcpyHostToDevice, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(dev + oCnt, count, bCnt, hipMemcpyHostToDevice, WS.stream));
+    rc = roman_submaps_fill_dev(c, point_dim, cap, N, F, dFeats, seg_ids ? reinterpret_cast<const int64_t*>(dev + oIds) : nullptr, S, descs,
+                                reinterpret_cast<const int32_t*>(dev + oCnt), reinterpret_cast<const int32_t*>(dev + oSrc), dPool, dIdsOut, desc_dim, dDescOut);
+    if (rc) return rc;
+    if (bPool) HIPCHK(c, hipMemcpyAsync(pool, dPool, bPool, hipMemcpyDeviceToHost, WS.stream));
+    if (bIdsOut) HIPCHK(c, hipMemcpyAsync(ids_out, dIdsOut, bIdsOut, hipMemcpyDeviceToHost, WS.stream));
+    if (bDesc) HIPCHK(c, hipMemcpyAsync(desc_out, dDescOut, bDesc, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipStreamSynchronize(WS.stream));
+    return ROMAN_OK;
+}
+
+static int submap_boxes_check(roman_ctx* c, int32_t S, int32_t F, int32_t cap, const void* pool, const void* count, const void* T_odom_center, const void* box)
+{
+    if (S < 0) return fail(c, ROMAN_E_INVALID, "S < 0");
+    if (F < 3) return fail(c, ROMAN_E_INVALID, "F=%d: a pool row starts with x y z", F);
+    if (cap < 1) return fail(c, ROMAN_E_INVALID, "cap must be >= 1 (got %d)", cap);
+    if (S == 0) return ROMAN_OK;
+    if (!pool || !count || !T_odom_center || !box) return fail(c, ROMAN_E_INVALID, "NULL pool, count, T_odom_center or box pointer");
+    return ROMAN_OK;
+}
+
+int roman_submap_boxes_dev(roman_ctx_t* c, int32_t S, int32_t F, int32_t cap, const double* pool, const int32_t* count,
+                           const double* T_odom_center, double* box)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = submap_boxes_check(c, S, F, cap, pool, count, T_odom_center, box);
+    if (rc || S == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_submap_boxes, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, c->stream, (int)S, (int)F, (int)cap, pool, count, T_odom_center, box);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_submap_boxes(roman_ctx_t* c, int32_t S, int32_t F, int32_t cap, const double* pool, const int32_t* count,
+                       const double* T_odom_center, double* box)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = submap_boxes_check(c, S, F, cap, pool, count, T_odom_center, box);
+    if (rc || S == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    // one device block: pool | T_odom_center | box | count
+    const size_t bPool = sizeof(double) * (size_t)S * (size_t)cap * (size_t)F, bT = sizeof(double) * 16 * (size_t)S, bBox = sizeof(double) * 6 * (size_t)S,
+                 bCnt = sizeof(int32_t) * (size_t)S;
+    const size_t oT = bPool, oBox = oT + bT, oCnt = oBox + bBox;
+    HIPCHK(c, c->smHost.ensure(oCnt + bCnt));
+    char* const dev = c->smHost.as<char>();
+    HIPCHK(c, hipMemcpyAsync(dev, pool, bPool, hipMemcpyHostToDevice, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(dev + oT, T_odom_center, bT, hipMemcpyHostToDevice, WS.stream));
+    HIPCHK(c, hipMemcpyAsync(dev + oCnt, count, bCnt, hipMemcpyHostToDevice, WS.stream));
+    rc = roman_submap_boxes_dev(c, S, F, cap, reinterpret_cast<const double*>(dev), reinterpret_cast<const int32_t*>(dev + oCnt),
+                                reinterpret_cast<const double*>(dev + oT), reinterpret_cast<double*>(dev + oBox));
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(box, dev + oBox, bBox, hipMemcpyDeviceToHost, WS.stream));
+    HIPCHK(c, hipStreamSynchronize(WS.stream));
+    return ROMAN_OK;
+}
+
 // --- pass 1 of the pair loop over a grid, radius mode ([REF roman/align/submap_align.py:93-149]) -------------------
 static int grid_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int32_t S0, int32_t S1,
                            const void* pos0, const void* T_w0, const void* time0, const void* desc0,
                            const void* pos1, const void* T_w1, const void* time1, const void* desc1,
                            const void* dist, const void* flags, const void* yaw_deg, const void* sim, const void* T_ij,
-                           const void* pairs, const void* T_ref, const void* enable, const void* n_todo, bool sim_in = false)
+                           const void* pairs, const void* T_ref, const void* enable, const void* n_todo, bool sim_in = false,
+                           bool aabb = false, const void* box0 = nullptr, const void* box1 = nullptr)
 {
     if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
     if (sim_in && P->desc_dim != 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d: the similarity is given, desc_dim must be 0", P->desc_dim);
     if (S0 < 0 || S1 < 0) return fail(c, ROMAN_E_INVALID, "S0 < 0 or S1 < 0");
     if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
         return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
-    if (P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
+    if (!aabb && P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
     if (P->desc_dim < 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d is negative", P->desc_dim);
-    if (P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: without a radius the gate is the AABB test, which stays on the host", P->radius);
+    if (!aabb && P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: without a radius the gate is the AABB test (roman_grid_gate_aabb*)", P->radius);
     if (!n_todo) return fail(c, ROMAN_E_INVALID, "n_todo is NULL");
     if (S0 == 0 || S1 == 0) return ROMAN_OK;
     if ((int64_t)S0 * S1 > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "S0 * S1 = %lld pairs exceed the index width", (long long)S0 * S1);
     if (P->desc_dim > 0 && (!desc0 || !desc1)) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
     if (!pos0 || !pos1 || !T_w0 || !T_w1) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
+    if (aabb && (!box0 || !box1)) return fail(c, ROMAN_E_INVALID, "box is NULL");
     if (P->single_robot_lc && (!time0 || !time1)) return fail(c, ROMAN_E_INVALID, "time is NULL with single_robot_lc");
     if (!dist || !flags || !yaw_deg || !sim || !T_ij || !pairs || !T_ref || !enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
     return ROMAN_OK;
@@ -2674,10 +2815,12 @@ static int grid_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, 
                          const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
                          const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
                          double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                         int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo, bool sim_in)
+                         int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo, bool sim_in,
+                         bool aabb = false, const double* box0 = nullptr, const double* box1 = nullptr)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo, sim_in);
+    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo, sim_in,
+                             aabb, box0, box1);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t stream = c->stream;
@@ -2686,11 +2829,14 @@ static int grid_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, 
     HIPCHK(c, c->ggNorm.ensure(sizeof(double) * (size_t)(S0 + S1)));            // scratch first: a failure leaves nothing enqueued
     double* dNorm = c->ggNorm.as<double>();
     if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S0 + S1 + 3) / 4)), dim3(256), 0, stream, (int)S0, (int)S1, d, desc0, desc1, dNorm);
-    const GridSide a{pos0, pos_gt0, T_w0, time0, desc0}, b{pos1, pos_gt1, T_w1, time1, desc1};
+    const GridSide a{pos0, pos_gt0, T_w0, time0, desc0, box0}, b{pos1, pos_gt1, T_w1, time1, desc1, box1};
     const GridOut out{dist, flags, yaw_deg, sim, T_ij};
     const int64_t waves = (int64_t)S0 * ((S1 + GRID_TJ - 1) / GRID_TJ);
-    if (sim_in) hipLaunchKernelGGL(k_grid_gate<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
-    else hipLaunchKernelGGL(k_grid_gate<false>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
+    const dim3 gateGrid((unsigned)((waves + 3) / 4));
+    if (aabb && sim_in) hipLaunchKernelGGL((k_grid_gate<true, true>), gateGrid, dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
+    else if (aabb) hipLaunchKernelGGL((k_grid_gate<false, true>), gateGrid, dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
+    else if (sim_in) hipLaunchKernelGGL((k_grid_gate<true, false>), gateGrid, dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
+    else hipLaunchKernelGGL((k_grid_gate<false, false>), gateGrid, dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
     hipLaunchKernelGGL(k_grid_compact, dim3(1), dim3(B > 256 ? 1024 : 256), 0, stream, B, (int)S1, (const int32_t*)flags, pairs, n_todo);
     hipLaunchKernelGGL(k_grid_fill, dim3((unsigned)(((int64_t)B * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, (int)S1, (const int32_t*)n_todo,
                        (const int32_t*)pairs, (const double*)T_ij, time0, time1, T_ref, enable);
@@ -2715,7 +2861,20 @@ int roman_grid_gate_sim_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gpar
                             int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
 {
     return grid_gate_dev(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, nullptr, pos1, pos_gt1, T_w1, time1, nullptr, dist, flags, yaw_deg,
-                         const_cast<double*>(sim) /* k_grid_gate<true> only reads it */, T_ij, pairs, T_ref, enable, n_todo, true);
+                         const_cast<double*>(sim) /* k_grid_gate<true, .> only reads it */, T_ij, pairs, T_ref, enable, n_todo, true);
+}
+
+// the AABB gate: NEARBY from the boxes roman_submap_boxes_dev wrote; with sim_in the similarity is an input
+int roman_grid_gate_aabb_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                             const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                             const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                             double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                             int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo,
+                             const double* box0, const double* box1, const double* sim_in)
+{
+    return grid_gate_dev(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, sim_in ? nullptr : desc0, pos1, pos_gt1, T_w1, time1, sim_in ? nullptr : desc1,
+                         dist, flags, yaw_deg, sim_in ? const_cast<double*>(sim_in) /* only read */ : sim, T_ij, pairs, T_ref, enable, n_todo, sim_in != nullptr,
+                         true, box0, box1);
 }
 
 // the host-pointer gate; sim_in: the caller's sim goes up and is not brought back
@@ -2723,31 +2882,33 @@ static int grid_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gparams,
                           const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
                           const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
                           double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                          int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo, bool sim_in)
+                          int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo, bool sim_in,
+                          bool aabb = false, const double* box0 = nullptr, const double* box1 = nullptr)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo, sim_in);
+    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo, sim_in,
+                             aabb, box0, box1);
     if (rc) return rc;
     if (S0 == 0 || S1 == 0) { *n_todo = 0; return ROMAN_OK; }
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    // one device block, 8-byte arrays first: per side pos | pos_gt | T_w | time | desc, then dist | yaw | sim | T_ij | T_ref | flags | pairs | enable | n_todo
+    // one device block, 8-byte arrays first: per side pos | pos_gt | T_w | time | desc | box, then dist | yaw | sim | T_ij | T_ref | flags | pairs | enable | n_todo
     const size_t d = (size_t)gparams->desc_dim, B = (size_t)S0 * (size_t)S1;
-    const double* in[2][5] = {{pos0, pos_gt0, T_w0, time0, desc0}, {pos1, pos_gt1, T_w1, time1, desc1}};
+    const double* in[2][6] = {{pos0, pos_gt0, T_w0, time0, desc0, box0}, {pos1, pos_gt1, T_w1, time1, desc1, box1}};
     const size_t S[2] = {(size_t)S0, (size_t)S1};
-    size_t inB[2][5], inO[2][5], total = 0;
+    size_t inB[2][6], inO[2][6], total = 0;
     for (int r = 0; r < 2; ++r) {
-        const size_t per[5] = {3, 3, 16, 1, d};
-        for (int k = 0; k < 5; ++k) { inB[r][k] = in[r][k] ? sizeof(double) * per[k] * S[r] : 0; inO[r][k] = total; total += inB[r][k]; }
+        const size_t per[6] = {3, 3, 16, 1, d, 6};
+        for (int k = 0; k < 6; ++k) { inB[r][k] = in[r][k] ? sizeof(double) * per[k] * S[r] : 0; inO[r][k] = total; total += inB[r][k]; }
     }
     const size_t oDist = total, oYaw = oDist + 8 * B, oSim = oYaw + 8 * B, oTij = oSim + 8 * B, oTref = oTij + 128 * B, oFlags = oTref + 128 * B,
                  oPairs = oFlags + 4 * B, oEn = oPairs + 8 * B, oCnt = oEn + 4 * B;
     total = oCnt + 4;
     HIPCHK(c, c->ggHost.ensure(total));
     char* const dev = c->ggHost.as<char>();
-    const double* dIn[2][5];
+    const double* dIn[2][6];
     for (int r = 0; r < 2; ++r)
-        for (int k = 0; k < 5; ++k) {
+        for (int k = 0; k < 6; ++k) {
             dIn[r][k] = inB[r][k] ? reinterpret_cast<const double*>(dev + inO[r][k]) : nullptr;
             if (inB[r][k]) HIPCHK(c, hipMemcpyAsync(dev + inO[r][k], in[r][k], inB[r][k], hipMemcpyHostToDevice, WS.stream));
         }
@@ -2759,7 +2920,8 @@ static int grid_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gparams,
     rc = grid_gate_dev(c, gparams, S0, S1, dIn[0][0], dIn[0][1], dIn[0][2], dIn[0][3], dIn[0][4], dIn[1][0], dIn[1][1], dIn[1][2], dIn[1][3], dIn[1][4],
                        reinterpret_cast<double*>(dev + oDist), reinterpret_cast<int32_t*>(dev + oFlags), reinterpret_cast<double*>(dev + oYaw),
                        reinterpret_cast<double*>(dev + oSim), reinterpret_cast<double*>(dev + oTij), reinterpret_cast<int32_t*>(dev + oPairs),
-                       reinterpret_cast<double*>(dev + oTref), reinterpret_cast<int32_t*>(dev + oEn), reinterpret_cast<int32_t*>(dev + oCnt), sim_in);
+                       reinterpret_cast<double*>(dev + oTref), reinterpret_cast<int32_t*>(dev + oEn), reinterpret_cast<int32_t*>(dev + oCnt), sim_in,
+                       aabb, dIn[0][5], dIn[1][5]);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(dist, dev + oDist, 8 * B, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipMemcpyAsync(yaw_deg, dev + oYaw, 8 * B, hipMemcpyDeviceToHost, WS.stream));
@@ -2792,6 +2954,18 @@ int roman_grid_gate_sim(roman_ctx_t* c, const roman_grid_gate_params_t* gparams,
 {
     return grid_gate_host(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, nullptr, pos1, pos_gt1, T_w1, time1, nullptr, dist, flags, yaw_deg,
                           const_cast<double*>(sim) /* uploaded, never written */, T_ij, pairs, T_ref, enable, n_todo, true);
+}
+
+int roman_grid_gate_aabb(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
+                         const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
+                         const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
+                         double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                         int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo,
+                         const double* box0, const double* box1, const double* sim_in)
+{
+    return grid_gate_host(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, sim_in ? nullptr : desc0, pos1, pos_gt1, T_w1, time1, sim_in ? nullptr : desc1,
+                          dist, flags, yaw_deg, sim_in ? const_cast<double*>(sim_in) /* uploaded, never written */ : sim, T_ij, pairs, T_ref, enable, n_todo,
+                          sim_in != nullptr, true, box0, box1);
 }
 
 // --- frame descriptors of the submaps of a pool ([REF roman/map/map.py:210-242], [REF :155-162]) ------------------

@@ -176,7 +176,8 @@ def frame_select_params(thin_dist=None, want_mean=False):
 
 
 def grid_gate_params(radius, skip_distance=np.inf, desc_dim=0, desc_thresh=0.0, single_robot_lc=False, lc_time_thresh=0.0):
-    """-> roman_grid_gate_params_t (a missing radius — None — is passed as -1: the library answers ROMAN_E_UNSUPPORTED)."""
+    """-> roman_grid_gate_params_t (a missing radius — None — is passed as -1: roman_grid_gate* answers ROMAN_E_UNSUPPORTED,
+    roman_grid_gate_aabb* does not read it)."""
     P = _abi.RomanGridGateParams()
     P.radius = -1.0 if radius is None else float(radius)
     P.skip_distance = float(skip_distance)
@@ -611,6 +612,121 @@ class Context:
                                                vp(dist_ptr), vp(flags_ptr), vp(yaw_deg_ptr), vp(sim_ptr), vp(T_ij_ptr),
                                                vp(pairs_ptr), vp(T_ref_ptr), vp(enable_ptr), vp(n_todo_ptr))
         self._check(rc, "roman_grid_gate_sim_dev")
+
+    # ------------------------------------------------------------------ force-fill submaps, boxes, the bounding-box gate
+    def submaps_fill(self, point_dim, cap, seg_feats, descs, count, src, seg_ids=None, desc_dim=0, want_pool=True):
+        """Host-pointer gather of force-fill submaps (roman_submaps_fill, [REF roman/map/map.py:264-295]): `src` (S, cap) holds the
+        map indices of every submap's rows (the first count[s] of a row are read), `descs` a submap_desc_dtype array whose
+        T_center_odom takes the centres to the submap's frame.  -> SubmapsResult (count and src are the arrays handed in; status 0)."""
+        seg_feats = _f64(seg_feats)
+        if seg_feats.ndim != 2:
+            raise ValueError("seg_feats must be (N, F)")
+        N, F = seg_feats.shape
+        if seg_ids is not None:
+            seg_ids = np.ascontiguousarray(seg_ids, dtype=np.int64).reshape(-1)
+            if seg_ids.shape[0] != N:
+                raise ValueError("seg_ids must hold one entry per segment")
+        descs = self._submap_descs(descs)
+        S, cap, d = int(descs.shape[0]), int(cap), int(desc_dim)
+        count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        src = np.ascontiguousarray(src, dtype=np.int32).reshape(-1)
+        if count.shape[0] != S or src.shape[0] != S * max(cap, 0):
+            raise ValueError("count must be (S,) and src (S, cap)")
+        rows, Fo = S * max(cap, 0), int(point_dim) + F - 3
+        pool = np.zeros((rows, max(Fo, 0))) if want_pool else None
+        ids_out = np.full(rows, -1, dtype=np.int64) if seg_ids is not None else None
+        desc_out = np.full((S, d), np.nan) if d > 0 else None
+        self._generation += 1
+        rc = self._lib.roman_submaps_fill(self._h, int(point_dim), cap, N, F, _ptr(seg_feats), _ptr(seg_ids), S, _ptr(descs), _ptr(count), _ptr(src),
+                                          _ptr(pool), _ptr(ids_out), d, _ptr(desc_out))
+        self._check(rc, "roman_submaps_fill")
+        return SubmapsResult(pool, count, src, ids_out, np.zeros(S, dtype=np.int32), desc_out)
+
+    def submaps_fill_dev(self, point_dim, cap, N, F, seg_feats_ptr, descs, count_ptr, src_ptr, pool_ptr, seg_ids_ptr=None, ids_out_ptr=None,
+                         desc_dim=0, desc_out_ptr=None):
+        """Device-pointer gather of force-fill submaps (roman_submaps_fill_dev): count and src are device arrays the caller uploaded,
+        `descs` a host submap_desc_dtype array.  A pure enqueue on the context's stream; complete after sync()."""
+        descs = self._submap_descs(descs)
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_submaps_fill_dev(self._h, int(point_dim), int(cap), int(N), int(F), vp(seg_feats_ptr), vp(seg_ids_ptr), int(descs.shape[0]),
+                                              _ptr(descs), vp(count_ptr), vp(src_ptr), vp(pool_ptr), vp(ids_out_ptr), int(desc_dim), vp(desc_out_ptr))
+        self._check(rc, "roman_submaps_fill_dev")
+
+    def submap_boxes(self, pool, cap, count, T_odom_center):
+        """Host-pointer boxes of the submaps of a pool (roman_submap_boxes, [REF roman/map/map.py:133-139]): pool (S * cap, F),
+        count (S,), T_odom_center (S, 4, 4) -> (S, 6) float64: min x y z, max x y z in the global frame."""
+        pool = _f64(pool); count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        S, cap = int(count.shape[0]), int(cap)
+        T = _f64(T_odom_center).reshape(-1, 16)
+        if pool.ndim != 2 or pool.shape[0] != S * max(cap, 0) or T.shape[0] != S:
+            raise ValueError("pool must be (S * cap, F), count (S,) and T_odom_center (S, 4, 4)")
+        if S and (count.min() < 0 or count.max() > cap):
+            raise ValueError("a count lies outside [0, cap]")
+        box = np.zeros((S, 6))
+        self._generation += 1
+        rc = self._lib.roman_submap_boxes(self._h, S, int(pool.shape[1]), cap, _ptr(pool), _ptr(count), _ptr(T), _ptr(box))
+        self._check(rc, "roman_submap_boxes")
+        return box
+
+    def submap_boxes_dev(self, S, F, cap, pool_ptr, count_ptr, T_odom_center_ptr, box_ptr):
+        """Device-pointer boxes of the submaps of a pool (roman_submap_boxes_dev): a pure enqueue on the context's stream."""
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_submap_boxes_dev(self._h, int(S), int(F), int(cap), vp(pool_ptr), vp(count_ptr), vp(T_odom_center_ptr), vp(box_ptr))
+        self._check(rc, "roman_submap_boxes_dev")
+
+    def grid_gate_aabb(self, gparams, box0, box1, pos0, T_w0, pos1, T_w1, time0=None, time1=None, desc0=None, desc1=None, pos_gt0=None, pos_gt1=None,
+                       sim_in=None, pairs=None, T_ref=None, enable=None):
+        """grid_gate() with the bounding-box gate (roman_grid_gate_aabb): box_r (S_r, 6) as submap_boxes() gives them; gparams.radius
+        is not read.  `sim_in` (S0, S1): the similarity is already there (gparams.desc_dim must be 0); the result's sim is then
+        that array.  -> GridGateResult."""
+        side = []
+        for pos, T_w, tm, desc, gt, box in ((pos0, T_w0, time0, desc0, pos_gt0, box0), (pos1, T_w1, time1, desc1, pos_gt1, box1)):
+            pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
+            T_w = _f64(T_w).reshape(-1, 16); box = _f64(box).reshape(-1, 6)
+            tm = None if tm is None else _f64(tm).reshape(-1)
+            desc = None if (desc is None or sim_in is not None) else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
+            gt = None if gt is None else _f64(gt).reshape(-1, 3)
+            if T_w.shape[0] != S or box.shape[0] != S or (tm is not None and tm.shape[0] != S) or (gt is not None and gt.shape[0] != S):
+                raise ValueError("the per-submap arrays of a side must hold one entry per submap")
+            if desc is not None and gparams.desc_dim > 0 and desc.shape[1] != gparams.desc_dim:
+                raise ValueError("desc must be (S, desc_dim)")
+            side.append((S, pos, gt, T_w, tm, desc, box))
+        S0, S1 = side[0][0], side[1][0]
+        B = S0 * S1
+        if sim_in is not None:
+            sim_in = _f64(sim_in)
+            if sim_in.shape != (S0, S1):
+                raise ValueError("sim_in must be (S0, S1)")
+
+        def given(a, shape, dtype, fill):
+            if a is None:
+                return np.full(shape, fill, dtype=dtype)
+            if a.dtype != dtype or not a.flags.c_contiguous or a.shape != shape:
+                raise ValueError(f"an output array must be C-contiguous {np.dtype(dtype).name} of shape {shape}")
+            return a
+        pairs = given(pairs, (B, 2), np.int32, -1); T_ref = given(T_ref, (B, 4, 4), np.float64, np.nan); enable = given(enable, (B,), np.int32, -1)
+        dist = np.zeros((S0, S1)); flags = np.zeros((S0, S1), dtype=np.int32); yaw = np.zeros((S0, S1))
+        sim = np.zeros((S0, S1)) if sim_in is None else None
+        T_ij = np.zeros((S0, S1, 4, 4)); n_todo = np.zeros(1, dtype=np.int32)
+        self._generation += 1
+        ins = [_ptr(a) for s in side for a in s[1:6]]
+        rc = self._lib.roman_grid_gate_aabb(self._h, C.byref(gparams), S0, S1, *ins, _ptr(dist), _ptr(flags), _ptr(yaw), _ptr(sim), _ptr(T_ij),
+                                            _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(n_todo), _ptr(side[0][6]), _ptr(side[1][6]), _ptr(sim_in))
+        self._check(rc, "roman_grid_gate_aabb")
+        return GridGateResult(dist, flags, yaw, sim if sim_in is None else sim_in, T_ij, pairs, T_ref, enable, int(n_todo[0]))
+
+    def grid_gate_aabb_dev(self, gparams, S0, S1, pos0_ptr, T_w0_ptr, pos1_ptr, T_w1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
+                           pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr, box0_ptr=None, box1_ptr=None, sim_in_ptr=None, time0_ptr=None, time1_ptr=None,
+                           desc0_ptr=None, desc1_ptr=None, pos_gt0_ptr=None, pos_gt1_ptr=None):
+        """grid_gate_dev() with the bounding-box gate (roman_grid_gate_aabb_dev): box_r as submap_boxes_dev wrote them; with
+        sim_in_ptr the similarity is an input (sim_ptr is then not written).  A pure enqueue on the context's stream."""
+        vp = lambda x: C.c_void_p(int(x)) if x else None
+        rc = self._lib.roman_grid_gate_aabb_dev(self._h, C.byref(gparams), int(S0), int(S1),
+                                                vp(pos0_ptr), vp(pos_gt0_ptr), vp(T_w0_ptr), vp(time0_ptr), vp(desc0_ptr),
+                                                vp(pos1_ptr), vp(pos_gt1_ptr), vp(T_w1_ptr), vp(time1_ptr), vp(desc1_ptr),
+                                                vp(dist_ptr), vp(flags_ptr), vp(yaw_deg_ptr), vp(sim_ptr), vp(T_ij_ptr),
+                                                vp(pairs_ptr), vp(T_ref_ptr), vp(enable_ptr), vp(n_todo_ptr), vp(box0_ptr), vp(box1_ptr), vp(sim_in_ptr))
+        self._check(rc, "roman_grid_gate_aabb_dev")
 
     # ------------------------------------------------------------------ frame descriptors of the submaps of a pool
     def frame_select(self, fparams, count, src, seg_times, frame_times, frame_pos=None, frame_desc=None):
