@@ -763,19 +763,16 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         fd = [q.frame_desc_dev for q in p]
         ctx.stacked_sim_dev(int(fd[0].shape[1]), int(fd[0].shape[0]), ptr(fd[0]), n0, ptr(masks[0]), int(fd[1].shape[0]), ptr(fd[1]), n1, ptr(masks[1]),
                             g["sim"].data_ptr())
+    gate_args = (gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *[t.data_ptr() for t in g.values()])
+    gate_kw = dict(time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
+    desc_kw = dict(desc0_ptr=ptr(side[0]["desc"]), desc1_ptr=ptr(side[1]["desc"]))
     if aabb_mode:
-        outs = [t.data_ptr() for t in g.values()]
-        ctx.grid_gate_aabb_dev(gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *outs,
-                               box0_ptr=boxes[0].data_ptr(), box1_ptr=boxes[1].data_ptr(), sim_in_ptr=g["sim"].data_ptr() if stacked else None,
-                               time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), desc0_ptr=ptr(side[0]["desc"]), desc1_ptr=ptr(side[1]["desc"]),
-                               pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
+        ctx.grid_gate_aabb_dev(*gate_args, box0_ptr=boxes[0].data_ptr(), box1_ptr=boxes[1].data_ptr(), sim_in_ptr=g["sim"].data_ptr() if stacked else None,
+                               **gate_kw, **desc_kw)
     elif stacked:
-        ctx.grid_gate_sim_dev(gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *[t.data_ptr() for t in g.values()],
-                              time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
+        ctx.grid_gate_sim_dev(*gate_args, **gate_kw)
     else:
-        ctx.grid_gate_dev(gp, n0, n1, ptr(side[0]["pos"]), ptr(side[0]["T_w"]), ptr(side[1]["pos"]), ptr(side[1]["T_w"]), *[t.data_ptr() for t in g.values()],
-                          time0_ptr=ptr(side[0]["time"]), time1_ptr=ptr(side[1]["time"]), desc0_ptr=ptr(side[0]["desc"]), desc1_ptr=ptr(side[1]["desc"]),
-                          pos_gt0_ptr=ptr(side[0]["gt"]), pos_gt1_ptr=ptr(side[1]["gt"]))
+        ctx.grid_gate_dev(*gate_args, **gate_kw, **desc_kw)
     ctx.sync()
     B = int(g["n_todo"].cpu().numpy()[0])
     pairs = g["pairs"][:B].cpu().numpy().astype(np.int64)

@@ -166,22 +166,25 @@ struct roman_ctx {
     DevBuf shareDesc, shareIds, shareKeep, shareKept, shareJobs;
     PinnedStage<ShareDesc> shareStage;
 
-    // RANSAC registration (roman_ransac_batch*): problem descriptors through pinned staging (a pure enqueue), and the host-pointer
-    // call's outputs on the device (records | association rows | counts)
-    DevBuf ransacDesc, ransacHost;
+    // the arrays of a host-pointer stage call on the device (HostMirror).  One buffer serves every such call: each ends with a stream
+    // synchronise before it returns, so no two of them ever have the block live at the same time.
+    DevBuf hostMirror;
+
+    // RANSAC registration (roman_ransac_batch*): problem descriptors through pinned staging (a pure enqueue)
+    DevBuf ransacDesc;
     PinnedStage<RansacDesc> ransacStage;
 
     // submaps from a whole map (roman_submaps*): the submap descriptors through pinned staging (a pure enqueue), the dense centres of
-    // the map, the per-submap spill of candidate lists beyond SUBMAP_LDS_CAND, and the host-pointer call's arrays on the device
-    DevBuf smDesc, smPts, smSpillKey, smSpillIdx, smHost;
+    // the map, and the per-submap spill of candidate lists beyond SUBMAP_LDS_CAND
+    DevBuf smDesc, smPts, smSpillKey, smSpillIdx;
     PinnedStage<roman_submap_desc_t> smStage;
 
-    // pass 1 of a grid (roman_grid_gate*): the descriptor norms of both sides, and the host-pointer call's arrays on the device
-    DevBuf ggNorm, ggHost;
+    // pass 1 of a grid (roman_grid_gate*): the descriptor norms of both sides
+    DevBuf ggNorm;
 
     // frame descriptors (roman_frame_select* / roman_stacked_sim*): the frame norms of both maps, one row band of the frame-cosine
-    // matrix, the column maxima R, and the host-pointer calls' arrays on the device
-    DevBuf fsHost, ssNorm, ssBand, ssR, ssHost;
+    // matrix, and the column maxima R
+    DevBuf ssNorm, ssBand, ssR;
     int stacked_band = 0;                      // rows per band (roman_ctx_set_stacked_band); 0: automatic
 
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
@@ -1443,12 +1446,12 @@ int roman_ctx_destroy(roman_ctx_t* c)
     }
     if (c->hostOut) (void)hipHostFree(c->hostOut);
     { DevBuf* share[] = {&c->shareDesc, &c->shareIds, &c->shareKeep, &c->shareKept, &c->shareJobs}; for (DevBuf* b : share) b->release(); }
-    c->ransacDesc.release(); c->ransacHost.release();
+    c->hostMirror.release(); c->ransacDesc.release();
     c->shareStage.release(); c->ransacStage.release();
-    { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx, &c->smHost}; for (DevBuf* b : sm) b->release(); }
+    { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx}; for (DevBuf* b : sm) b->release(); }
     c->smStage.release();
-    c->ggNorm.release(); c->ggHost.release();
-    c->fsHost.release(); c->ssNorm.release(); c->ssBand.release(); c->ssR.release(); c->ssHost.release();
+    c->ggNorm.release();
+    c->ssNorm.release(); c->ssBand.release(); c->ssR.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -1668,6 +1671,49 @@ int upload_inputs(roman_ctx* c, const double* feats, int64_t rows, int32_t F, in
     }
     return ROMAN_OK;
 }
+
+// The arrays of one host-pointer stage call as ONE block of c->hostMirror.  The call declares each array once (in, out, inout, or room
+// that exists on the device only); every piece is 8-byte aligned, and a piece of 0 bytes is a nullptr on the device (an optional array
+// that is absent).  An inout piece goes up with the inputs, so what the device call leaves untouched comes back as it was.
+struct HostMirror {
+    static constexpr int CAP = 24;             // the gate, the largest call, declares 21 pieces
+    enum : unsigned { UP = 1, DOWN = 2 };
+    template <typename T> struct Piece {
+        const HostMirror* m; int k;
+        T* dev() const { return m->bytes[k] ? reinterpret_cast<T*>(m->base + m->off[k]) : nullptr; }   // valid after upload()
+    };
+    roman_ctx* const c;
+    void* host[CAP]; size_t off[CAP], bytes[CAP]; unsigned dir[CAP];
+    int n = 0; size_t total = 0; char* base = nullptr;
+    explicit HostMirror(roman_ctx* c_) : c(c_) {}
+    template <typename T> Piece<T> in(const T* h, size_t b) { return Piece<T>{this, add(const_cast<T*>(h), b, UP)}; }
+    template <typename T> Piece<T> out(T* h, size_t b) { return Piece<T>{this, add(h, b, DOWN)}; }
+    template <typename T> Piece<T> inout(T* h, size_t b) { return Piece<T>{this, add(h, b, UP | DOWN)}; }
+    template <typename T> Piece<T> room(size_t b) { return Piece<T>{this, add(nullptr, b, 0)}; }
+    // the block on the device, and the in and inout pieces on their way into it
+    int upload() {
+        if (n > CAP) return fail(c, ROMAN_E_INTERNAL, "a host-pointer call declares more than %d arrays", CAP);
+        HIPCHK(c, c->hostMirror.ensure(total));
+        base = c->hostMirror.as<char>();
+        for (int k = 0; k < n; ++k)
+            if ((dir[k] & UP) && bytes[k]) HIPCHK(c, hipMemcpyAsync(base + off[k], host[k], bytes[k], hipMemcpyHostToDevice, WS.stream));
+        return ROMAN_OK;
+    }
+    // the out and inout pieces back in the caller's arrays, waited for
+    int download() {
+        for (int k = 0; k < n; ++k)
+            if ((dir[k] & DOWN) && bytes[k]) HIPCHK(c, hipMemcpyAsync(host[k], base + off[k], bytes[k], hipMemcpyDeviceToHost, WS.stream));
+        HIPCHK(c, hipStreamSynchronize(WS.stream));
+        return ROMAN_OK;
+    }
+private:
+    int add(void* h, size_t b, unsigned d) {
+        if (n >= CAP) { n = CAP + 1; return 0; }
+        host[n] = h; off[n] = total; bytes[n] = b; dir[n] = d;
+        total += (b + 7) & ~(size_t)7;
+        return n++;
+    }
+};
 
 // The solver's outputs of B problems as ONE block of a device buffer: T | stats | assoc | n | status
 struct SolverBlock {
@@ -2515,30 +2561,21 @@ int roman_ransac_batch(roman_ctx_t* c, const roman_ransac_params_t* rparams, int
     const double* dPts = nullptr;
     rc = upload_inputs(c, pts, n_objects, 3, 0, nullptr, 0, &dPts);
     if (rc) return rc;
-    // outputs on the device: records | association rows | counts
     const size_t rowsPer = (size_t)kmax * 2, nCounts = counts_out ? (size_t)B * (size_t)rparams->max_iteration : 0;
-    const size_t oRec = 0, oAssoc = oRec + sizeof(roman_ransac_record_t) * (size_t)B, oCnt = oAssoc + sizeof(int32_t) * std::max<size_t>((size_t)B * rowsPer, 2),
-                 total = oCnt + sizeof(int32_t) * nCounts;
-    static_assert(sizeof(roman_ransac_record_t) % 8 == 0, "the blocks stay 8-byte aligned");
-    HIPCHK(c, c->ransacHost.ensure(total));
-    char* const dev = c->ransacHost.as<char>();
-    roman_ransac_record_t* dRec = reinterpret_cast<roman_ransac_record_t*>(dev + oRec);
-    int32_t* dAssoc = reinterpret_cast<int32_t*>(dev + oAssoc);
-    int32_t* dCnt = counts_out ? reinterpret_cast<int32_t*>(dev + oCnt) : nullptr;
-    // the caller's counts go up first: entries beyond n_hyp come back as they were
-    if (nCounts) HIPCHK(c, hipMemcpyAsync(dCnt, counts_out, sizeof(int32_t) * nCounts, hipMemcpyHostToDevice, WS.stream));
+    HostMirror m(c);
+    const auto rec = m.out(rec_out, sizeof(roman_ransac_record_t) * (size_t)B);
+    const auto rows = m.out(assoc_out, sizeof(int32_t) * (size_t)B * rowsPer);
+    const auto cnt = m.inout(counts_out, sizeof(int32_t) * nCounts);            // entries beyond n_hyp come back as they were
+    rc = m.upload();
+    if (rc) return rc;
     const int chunk = std::max(1, c->host_chunk);
     for (int lo = 0; lo < B; lo += chunk) {
         const int hi = std::min(B, lo + chunk);
         rc = roman_ransac_batch_dev(c, rparams, hi - lo, dPts, off1 + lo, n1 + lo, off2 + lo, n2 + lo, kmax,
-                                    dAssoc + (size_t)lo * rowsPer, dRec + lo, dCnt ? dCnt + (size_t)lo * (size_t)rparams->max_iteration : nullptr);
+                                    rows.dev() + (size_t)lo * rowsPer, rec.dev() + lo, nCounts ? cnt.dev() + (size_t)lo * (size_t)rparams->max_iteration : nullptr);
         if (rc) return rc;
     }
-    HIPCHK(c, hipMemcpyAsync(rec_out, dRec, sizeof(roman_ransac_record_t) * (size_t)B, hipMemcpyDeviceToHost, WS.stream));
-    if (rowsPer) HIPCHK(c, hipMemcpyAsync(assoc_out, dAssoc, sizeof(int32_t) * (size_t)B * rowsPer, hipMemcpyDeviceToHost, WS.stream));
-    if (nCounts) HIPCHK(c, hipMemcpyAsync(counts_out, dCnt, sizeof(int32_t) * nCounts, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipStreamSynchronize(WS.stream));
-    return ROMAN_OK;
+    return m.download();
 }
 
 // --- submaps from a whole map, radius mode ([REF roman/map/map.py:297-346]) ---------------------------------------
@@ -2611,37 +2648,22 @@ int roman_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t 
     const double* dFeats = nullptr;
     rc = upload_inputs(c, seg_feats, N, F, 0, nullptr, 0, &dFeats);
     if (rc) return rc;
-    // the other arrays on the device, 8-byte blocks first: times | ids | pool | ids_out | desc_out | src | count | status
-    const size_t rows = (size_t)S * (size_t)sparams->cap, Fo = (size_t)(sparams->point_dim + F - 3);
-    const size_t bTimes = sizeof(double) * 2 * (size_t)N, bIds = seg_ids ? sizeof(int64_t) * (size_t)N : 0, bPool = sizeof(double) * rows * Fo,
-                 bIdsOut = ids_out ? sizeof(int64_t) * rows : 0, bDesc = desc_out ? sizeof(double) * (size_t)S * (size_t)desc_dim : 0,
-                 bSrc = sizeof(int32_t) * rows, bCnt = sizeof(int32_t) * (size_t)S;
-    const size_t oTimes = 0, oIds = oTimes + bTimes, oPool = oIds + bIds, oIdsOut = oPool + bPool, oDesc = oIdsOut + bIdsOut, oSrc = oDesc + bDesc,
-                 oCnt = oSrc + bSrc, oSt = oCnt + bCnt, total = oSt + bCnt;
-    HIPCHK(c, c->smHost.ensure(std::max<size_t>(total, 8)));
-    char* const dev = c->smHost.as<char>();
-    double* dPool = reinterpret_cast<double*>(dev + oPool);
-    int64_t* dIdsOut = ids_out ? reinterpret_cast<int64_t*>(dev + oIdsOut) : nullptr;
-    double* dDescOut = desc_out ? reinterpret_cast<double*>(dev + oDesc) : nullptr;
-    int32_t* dSrc = reinterpret_cast<int32_t*>(dev + oSrc);
-    if (bTimes) HIPCHK(c, hipMemcpyAsync(dev + oTimes, seg_times, bTimes, hipMemcpyHostToDevice, WS.stream));
-    if (bIds) HIPCHK(c, hipMemcpyAsync(dev + oIds, seg_ids, bIds, hipMemcpyHostToDevice, WS.stream));
-    // the caller's outputs go up first: what the device call leaves untouched comes back as it was
-    if (pool && bPool) HIPCHK(c, hipMemcpyAsync(dPool, pool, bPool, hipMemcpyHostToDevice, WS.stream));
-    if (bIdsOut) HIPCHK(c, hipMemcpyAsync(dIdsOut, ids_out, bIdsOut, hipMemcpyHostToDevice, WS.stream));
-    if (bDesc) HIPCHK(c, hipMemcpyAsync(dDescOut, desc_out, bDesc, hipMemcpyHostToDevice, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(dSrc, src, bSrc, hipMemcpyHostToDevice, WS.stream));
-    rc = roman_submaps_dev(c, sparams, N, F, dFeats, reinterpret_cast<const double*>(dev + oTimes), seg_ids ? reinterpret_cast<const int64_t*>(dev + oIds) : nullptr,
-                           S, descs, dPool, reinterpret_cast<int32_t*>(dev + oCnt), dSrc, dIdsOut, reinterpret_cast<int32_t*>(dev + oSt), desc_dim, dDescOut);
+    const size_t rows = (size_t)S * (size_t)sparams->cap, bPool = sizeof(double) * rows * (size_t)(sparams->point_dim + F - 3);
+    HostMirror m(c);
+    const auto times = m.in(seg_times, sizeof(double) * 2 * (size_t)N);
+    const auto ids = m.in(seg_ids, seg_ids ? sizeof(int64_t) * (size_t)N : 0);
+    const auto dPool = pool ? m.inout(pool, bPool) : m.room<double>(bPool);     // without a pool the device call still writes one
+    const auto idsOut = m.inout(ids_out, ids_out ? sizeof(int64_t) * rows : 0);
+    const auto descOut = m.inout(desc_out, desc_out ? sizeof(double) * (size_t)S * (size_t)desc_dim : 0);
+    const auto dSrc = m.inout(src, sizeof(int32_t) * rows);
+    const auto cnt = m.out(count, sizeof(int32_t) * (size_t)S);
+    const auto st = m.out(status, sizeof(int32_t) * (size_t)S);
+    rc = m.upload();
     if (rc) return rc;
-    if (pool && bPool) HIPCHK(c, hipMemcpyAsync(pool, dPool, bPool, hipMemcpyDeviceToHost, WS.stream));
-    if (bIdsOut) HIPCHK(c, hipMemcpyAsync(ids_out, dIdsOut, bIdsOut, hipMemcpyDeviceToHost, WS.stream));
-    if (bDesc) HIPCHK(c, hipMemcpyAsync(desc_out, dDescOut, bDesc, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(src, dSrc, bSrc, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(count, dev + oCnt, bCnt, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(status, dev + oSt, bCnt, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipStreamSynchronize(WS.stream));
-    return ROMAN_OK;
+    rc = roman_submaps_dev(c, sparams, N, F, dFeats, times.dev(), ids.dev(), S, descs, dPool.dev(), cnt.dev(), dSrc.dev(), idsOut.dev(), st.dev(),
+                           desc_dim, descOut.dev());
+    if (rc) return rc;
+    return m.download();
 }
 
 // --- force-fill submaps and the boxes of a pool ([REF roman/map/map.py:264-295], [REF :133-139]) -------------------
@@ -2708,32 +2730,19 @@ int roman_submaps_fill(roman_ctx_t* c, int32_t point_dim, int32_t cap, int32_t N
     const double* dFeats = nullptr;
     rc = upload_inputs(c, seg_feats, N, F, 0, nullptr, 0, &dFeats);
     if (rc) return rc;
-    // the other arrays on the device, 8-byte blocks first: ids | pool | ids_out | desc_out | src | count
-    const size_t rows = (size_t)S * (size_t)cap, Fo = (size_t)(point_dim + F - 3);
-    const size_t bIds = seg_ids ? sizeof(int64_t) * (size_t)N : 0, bPool = pool ? sizeof(double) * rows * Fo : 0, bIdsOut = ids_out ? sizeof(int64_t) * rows : 0,
-                 bDesc = desc_out ? sizeof(double) * (size_t)S * (size_t)desc_dim : 0, bSrc = sizeof(int32_t) * rows, bCnt = sizeof(int32_t) * (size_t)S;
-    const size_t oIds = 0, oPool = oIds + bIds, oIdsOut = oPool + sizeof(double) * rows * Fo, oDesc = oIdsOut + bIdsOut, oSrc = oDesc + bDesc, oCnt = oSrc + bSrc,
-                 total = oCnt + bCnt;
-    HIPCHK(c, c->smHost.ensure(std::max<size_t>(total, 8)));
-    char* const dev = c->smHost.as<char>();
-    double* dPool = reinterpret_cast<double*>(dev + oPool);
-    int64_t* dIdsOut = ids_out ? reinterpret_cast<int64_t*>(dev + oIdsOut) : nullptr;
-    double* dDescOut = desc_out ? reinterpret_cast<double*>(dev + oDesc) : nullptr;
-    if (bIds) HIPCHK(c, hipMemcpyAsync(dev + oIds, seg_ids, bIds, hipMemcpyHostToDevice, WS.stream));
-    // the caller's outputs go up first: what the device call leaves untouched comes back as it was
-    if (bPool) HIPCHK(c, hipMemcpyAsync(dPool, pool, bPool, hipMemcpyHostToDevice, WS.stream));
-    if (bIdsOut) HIPCHK(c, hipMemcpyAsync(dIdsOut, ids_out, bIdsOut, hipMemcpyHostToDevice, WS.stream));
-    if (bDesc) HIPCHK(c, hipMemcpyAsync(dDescOut, desc_out, bDesc, hipMemcpyHostToDevice, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(dev + oSrc, src, bSrc, hipMemcpyHostToDevice, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(dev + oCnt, count, bCnt, hipMemcpyHostToDevice, WS.stream));
-    rc = roman_submaps_fill_dev(c, point_dim, cap, N, F, dFeats, seg_ids ? reinterpret_cast<const int64_t*>(dev + oIds) : nullptr, S, descs,
-                                reinterpret_cast<const int32_t*>(dev + oCnt), reinterpret_cast<const int32_t*>(dev + oSrc), dPool, dIdsOut, desc_dim, dDescOut);
+    const size_t rows = (size_t)S * (size_t)cap, bPool = sizeof(double) * rows * (size_t)(point_dim + F - 3);
+    HostMirror m(c);
+    const auto ids = m.in(seg_ids, seg_ids ? sizeof(int64_t) * (size_t)N : 0);
+    const auto dPool = pool ? m.inout(pool, bPool) : m.room<double>(bPool);     // without a pool the device call still writes one
+    const auto idsOut = m.inout(ids_out, ids_out ? sizeof(int64_t) * rows : 0);
+    const auto descOut = m.inout(desc_out, desc_out ? sizeof(double) * (size_t)S * (size_t)desc_dim : 0);
+    const auto dSrc = m.in(src, sizeof(int32_t) * rows);
+    const auto cnt = m.in(count, sizeof(int32_t) * (size_t)S);
+    rc = m.upload();
     if (rc) return rc;
-    if (bPool) HIPCHK(c, hipMemcpyAsync(pool, dPool, bPool, hipMemcpyDeviceToHost, WS.stream));
-    if (bIdsOut) HIPCHK(c, hipMemcpyAsync(ids_out, dIdsOut, bIdsOut, hipMemcpyDeviceToHost, WS.stream));
-    if (bDesc) HIPCHK(c, hipMemcpyAsync(desc_out, dDescOut, bDesc, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipStreamSynchronize(WS.stream));
-    return ROMAN_OK;
+    rc = roman_submaps_fill_dev(c, point_dim, cap, N, F, dFeats, ids.dev(), S, descs, cnt.dev(), dSrc.dev(), dPool.dev(), idsOut.dev(), desc_dim, descOut.dev());
+    if (rc) return rc;
+    return m.download();
 }
 
 static int submap_boxes_check(roman_ctx* c, int32_t S, int32_t F, int32_t cap, const void* pool, const void* count, const void* T_odom_center, const void* box)
@@ -2766,21 +2775,16 @@ int roman_submap_boxes(roman_ctx_t* c, int32_t S, int32_t F, int32_t cap, const 
     if (rc || S == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    // one device block: pool | T_odom_center | box | count
-    const size_t bPool = sizeof(double) * (size_t)S * (size_t)cap * (size_t)F, bT = sizeof(double) * 16 * (size_t)S, bBox = sizeof(double) * 6 * (size_t)S,
-                 bCnt = sizeof(int32_t) * (size_t)S;
-    const size_t oT = bPool, oBox = oT + bT, oCnt = oBox + bBox;
-    HIPCHK(c, c->smHost.ensure(oCnt + bCnt));
-    char* const dev = c->smHost.as<char>();
-    HIPCHK(c, hipMemcpyAsync(dev, pool, bPool, hipMemcpyHostToDevice, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(dev + oT, T_odom_center, bT, hipMemcpyHostToDevice, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(dev + oCnt, count, bCnt, hipMemcpyHostToDevice, WS.stream));
-    rc = roman_submap_boxes_dev(c, S, F, cap, reinterpret_cast<const double*>(dev), reinterpret_cast<const int32_t*>(dev + oCnt),
-                                reinterpret_cast<const double*>(dev + oT), reinterpret_cast<double*>(dev + oBox));
+    HostMirror m(c);
+    const auto dPool = m.in(pool, sizeof(double) * (size_t)S * (size_t)cap * (size_t)F);
+    const auto cnt = m.in(count, sizeof(int32_t) * (size_t)S);
+    const auto T = m.in(T_odom_center, sizeof(double) * 16 * (size_t)S);
+    const auto dBox = m.out(box, sizeof(double) * 6 * (size_t)S);
+    rc = m.upload();
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(box, dev + oBox, bBox, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipStreamSynchronize(WS.stream));
-    return ROMAN_OK;
+    rc = roman_submap_boxes_dev(c, S, F, cap, dPool.dev(), cnt.dev(), T.dev(), dBox.dev());
+    if (rc) return rc;
+    return m.download();
 }
 
 // --- pass 1 of the pair loop over a grid, radius mode ([REF roman/align/submap_align.py:93-149]) -------------------
@@ -2892,48 +2896,26 @@ static int grid_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gparams,
     if (S0 == 0 || S1 == 0) { *n_todo = 0; return ROMAN_OK; }
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    // one device block, 8-byte arrays first: per side pos | pos_gt | T_w | time | desc | box, then dist | yaw | sim | T_ij | T_ref | flags | pairs | enable | n_todo
     const size_t d = (size_t)gparams->desc_dim, B = (size_t)S0 * (size_t)S1;
-    const double* in[2][6] = {{pos0, pos_gt0, T_w0, time0, desc0, box0}, {pos1, pos_gt1, T_w1, time1, desc1, box1}};
-    const size_t S[2] = {(size_t)S0, (size_t)S1};
-    size_t inB[2][6], inO[2][6], total = 0;
-    for (int r = 0; r < 2; ++r) {
-        const size_t per[6] = {3, 3, 16, 1, d, 6};
-        for (int k = 0; k < 6; ++k) { inB[r][k] = in[r][k] ? sizeof(double) * per[k] * S[r] : 0; inO[r][k] = total; total += inB[r][k]; }
-    }
-    const size_t oDist = total, oYaw = oDist + 8 * B, oSim = oYaw + 8 * B, oTij = oSim + 8 * B, oTref = oTij + 128 * B, oFlags = oTref + 128 * B,
-                 oPairs = oFlags + 4 * B, oEn = oPairs + 8 * B, oCnt = oEn + 4 * B;
-    total = oCnt + 4;
-    HIPCHK(c, c->ggHost.ensure(total));
-    char* const dev = c->ggHost.as<char>();
-    const double* dIn[2][6];
+    HostMirror m(c);
+    const double* side[2][6] = {{pos0, pos_gt0, T_w0, time0, desc0, box0}, {pos1, pos_gt1, T_w1, time1, desc1, box1}};
+    const size_t S[2] = {(size_t)S0, (size_t)S1}, per[6] = {3, 3, 16, 1, d, 6};
+    HostMirror::Piece<double> dIn[2][6];
     for (int r = 0; r < 2; ++r)
-        for (int k = 0; k < 6; ++k) {
-            dIn[r][k] = inB[r][k] ? reinterpret_cast<const double*>(dev + inO[r][k]) : nullptr;
-            if (inB[r][k]) HIPCHK(c, hipMemcpyAsync(dev + inO[r][k], in[r][k], inB[r][k], hipMemcpyHostToDevice, WS.stream));
-        }
-    // the caller's compact outputs go up first: the slots beyond n_todo come back as they were
-    HIPCHK(c, hipMemcpyAsync(dev + oTref, T_ref, 128 * B, hipMemcpyHostToDevice, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(dev + oPairs, pairs, 8 * B, hipMemcpyHostToDevice, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(dev + oEn, enable, 4 * B, hipMemcpyHostToDevice, WS.stream));
-    if (sim_in) HIPCHK(c, hipMemcpyAsync(dev + oSim, sim, 8 * B, hipMemcpyHostToDevice, WS.stream));
-    rc = grid_gate_dev(c, gparams, S0, S1, dIn[0][0], dIn[0][1], dIn[0][2], dIn[0][3], dIn[0][4], dIn[1][0], dIn[1][1], dIn[1][2], dIn[1][3], dIn[1][4],
-                       reinterpret_cast<double*>(dev + oDist), reinterpret_cast<int32_t*>(dev + oFlags), reinterpret_cast<double*>(dev + oYaw),
-                       reinterpret_cast<double*>(dev + oSim), reinterpret_cast<double*>(dev + oTij), reinterpret_cast<int32_t*>(dev + oPairs),
-                       reinterpret_cast<double*>(dev + oTref), reinterpret_cast<int32_t*>(dev + oEn), reinterpret_cast<int32_t*>(dev + oCnt), sim_in,
-                       aabb, dIn[0][5], dIn[1][5]);
+        for (int k = 0; k < 6; ++k) dIn[r][k] = m.in(side[r][k], side[r][k] ? sizeof(double) * per[k] * S[r] : 0);
+    const auto dDist = m.out(dist, 8 * B), dYaw = m.out(yaw_deg, 8 * B), dSim = sim_in ? m.in(sim, 8 * B) : m.out(sim, 8 * B), dTij = m.out(T_ij, 128 * B);
+    const auto dFlags = m.out(flags, 4 * B);
+    // the compact outputs are inout: the slots beyond n_todo come back as they were
+    const auto dTref = m.inout(T_ref, 128 * B);
+    const auto dPairs = m.inout(pairs, 8 * B), dEn = m.inout(enable, 4 * B), dCnt = m.out(n_todo, 4);
+    rc = m.upload();
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(dist, dev + oDist, 8 * B, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(yaw_deg, dev + oYaw, 8 * B, hipMemcpyDeviceToHost, WS.stream));
-    if (!sim_in) HIPCHK(c, hipMemcpyAsync(sim, dev + oSim, 8 * B, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(T_ij, dev + oTij, 128 * B, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(T_ref, dev + oTref, 128 * B, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(flags, dev + oFlags, 4 * B, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(pairs, dev + oPairs, 8 * B, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(enable, dev + oEn, 4 * B, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(n_todo, dev + oCnt, 4, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipStreamSynchronize(WS.stream));
-    return ROMAN_OK;
+    rc = grid_gate_dev(c, gparams, S0, S1, dIn[0][0].dev(), dIn[0][1].dev(), dIn[0][2].dev(), dIn[0][3].dev(), dIn[0][4].dev(),
+                       dIn[1][0].dev(), dIn[1][1].dev(), dIn[1][2].dev(), dIn[1][3].dev(), dIn[1][4].dev(),
+                       dDist.dev(), dFlags.dev(), dYaw.dev(), dSim.dev(), dTij.dev(), dPairs.dev(), dTref.dev(), dEn.dev(), dCnt.dev(), sim_in,
+                       aabb, dIn[0][5].dev(), dIn[1][5].dev());
+    if (rc) return rc;
+    return m.download();
 }
 
 int roman_grid_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
@@ -3006,12 +2988,6 @@ int roman_frame_select_dev(roman_ctx_t* c, const roman_frame_select_params_t* fp
     return ROMAN_OK;
 }
 
-// one device block for a host-pointer call: the pieces in the order given, each 8-byte aligned
-struct HostBlock {
-    size_t total = 0;
-    size_t add(size_t bytes) { const size_t o = total; total += (bytes + 7) & ~(size_t)7; return o; }
-};
-
 int roman_frame_select(roman_ctx_t* c, const roman_frame_select_params_t* fparams, int32_t S, int32_t cap,
                        const int32_t* count, const int32_t* src, int32_t N, const double* seg_times,
                        int32_t Nf, const double* frame_times, const double* frame_pos, int32_t d, const double* frame_desc,
@@ -3024,28 +3000,23 @@ int roman_frame_select(roman_ctx_t* c, const roman_frame_select_params_t* fparam
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
     const bool thin = fparams->thin != 0, wm = fparams->want_mean != 0;
     const size_t W = ((size_t)Nf + 63) / 64;
-    HostBlock hb;
-    const size_t bCnt = 4 * (size_t)S, bSrc = 4 * (size_t)S * (size_t)cap, bSeg = 16 * (size_t)N, bFt = 8 * (size_t)Nf, bFp = thin ? 24 * (size_t)Nf : 0,
-                 bFd = wm ? 8 * (size_t)Nf * (size_t)d : 0, bMask = 8 * (size_t)S * W, bSpan = 16 * (size_t)S, bMean = wm ? 8 * (size_t)S * (size_t)d : 0;
-    const size_t oCnt = hb.add(bCnt), oSrc = hb.add(bSrc), oSeg = hb.add(bSeg), oFt = hb.add(bFt), oFp = hb.add(bFp), oFd = hb.add(bFd),
-                 oMask = hb.add(bMask), oSel = hb.add(bCnt), oSpan = hb.add(bSpan), oMean = hb.add(bMean);
-    HIPCHK(c, c->fsHost.ensure(std::max<size_t>(hb.total, 8)));
-    char* const dev = c->fsHost.as<char>();
-    const struct { size_t o, b; const void* h; } up[6] = {{oCnt, bCnt, count}, {oSrc, bSrc, src}, {oSeg, bSeg, seg_times}, {oFt, bFt, frame_times},
-                                                          {oFp, bFp, frame_pos}, {oFd, bFd, frame_desc}};
-    for (const auto& u : up) if (u.b) HIPCHK(c, hipMemcpyAsync(dev + u.o, u.h, u.b, hipMemcpyHostToDevice, WS.stream));
-    rc = roman_frame_select_dev(c, fparams, S, cap, reinterpret_cast<const int32_t*>(dev + oCnt), reinterpret_cast<const int32_t*>(dev + oSrc), N,
-                                reinterpret_cast<const double*>(dev + oSeg), Nf, reinterpret_cast<const double*>(dev + oFt),
-                                thin ? reinterpret_cast<const double*>(dev + oFp) : nullptr, d, wm ? reinterpret_cast<const double*>(dev + oFd) : nullptr,
-                                reinterpret_cast<uint64_t*>(dev + oMask), reinterpret_cast<int32_t*>(dev + oSel), reinterpret_cast<double*>(dev + oSpan),
-                                wm ? reinterpret_cast<double*>(dev + oMean) : nullptr);
+    HostMirror m(c);
+    const auto cnt = m.in(count, 4 * (size_t)S);
+    const auto dSrc = m.in(src, 4 * (size_t)S * (size_t)cap);
+    const auto seg = m.in(seg_times, 16 * (size_t)N);
+    const auto ft = m.in(frame_times, 8 * (size_t)Nf);
+    const auto fp = m.in(frame_pos, thin ? 24 * (size_t)Nf : 0);
+    const auto fd = m.in(frame_desc, wm ? 8 * (size_t)Nf * (size_t)d : 0);
+    const auto dMask = m.out(mask, 8 * (size_t)S * W);
+    const auto sel = m.out(n_sel, 4 * (size_t)S);
+    const auto dSpan = m.out(span, 16 * (size_t)S);
+    const auto dMean = m.out(mean, wm ? 8 * (size_t)S * (size_t)d : 0);
+    rc = m.upload();
     if (rc) return rc;
-    if (bMask) HIPCHK(c, hipMemcpyAsync(mask, dev + oMask, bMask, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(n_sel, dev + oSel, bCnt, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipMemcpyAsync(span, dev + oSpan, bSpan, hipMemcpyDeviceToHost, WS.stream));
-    if (bMean) HIPCHK(c, hipMemcpyAsync(mean, dev + oMean, bMean, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipStreamSynchronize(WS.stream));
-    return ROMAN_OK;
+    rc = roman_frame_select_dev(c, fparams, S, cap, cnt.dev(), dSrc.dev(), N, seg.dev(), Nf, ft.dev(), fp.dev(), d, fd.dev(),
+                                dMask.dev(), sel.dev(), dSpan.dev(), dMean.dev());
+    if (rc) return rc;
+    return m.download();
 }
 
 static int stacked_sim_check(roman_ctx* c, int32_t d, int32_t Nf0, const void* desc0, int32_t S0, const void* mask0,
@@ -3118,21 +3089,15 @@ int roman_stacked_sim(roman_ctx_t* c, int32_t d, int32_t Nf0, const double* desc
     if (rc || S0 == 0 || S1 == 0) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    HostBlock hb;
-    const size_t bD0 = 8 * (size_t)Nf0 * (size_t)d, bD1 = 8 * (size_t)Nf1 * (size_t)d, bM0 = 8 * (size_t)S0 * (((size_t)Nf0 + 63) / 64),
-                 bM1 = 8 * (size_t)S1 * (((size_t)Nf1 + 63) / 64), bSim = 8 * (size_t)S0 * (size_t)S1;
-    const size_t oD0 = hb.add(bD0), oD1 = hb.add(bD1), oM0 = hb.add(bM0), oM1 = hb.add(bM1), oSim = hb.add(bSim);
-    HIPCHK(c, c->ssHost.ensure(std::max<size_t>(hb.total, 8)));
-    char* const dev = c->ssHost.as<char>();
-    const struct { size_t o, b; const void* h; } up[4] = {{oD0, bD0, desc0}, {oD1, bD1, desc1}, {oM0, bM0, mask0}, {oM1, bM1, mask1}};
-    for (const auto& u : up) if (u.b) HIPCHK(c, hipMemcpyAsync(dev + u.o, u.h, u.b, hipMemcpyHostToDevice, WS.stream));
-    rc = roman_stacked_sim_dev(c, d, Nf0, reinterpret_cast<const double*>(dev + oD0), S0, reinterpret_cast<const uint64_t*>(dev + oM0),
-                               Nf1, reinterpret_cast<const double*>(dev + oD1), S1, reinterpret_cast<const uint64_t*>(dev + oM1),
-                               reinterpret_cast<double*>(dev + oSim));
+    HostMirror m(c);
+    const auto d0 = m.in(desc0, 8 * (size_t)Nf0 * (size_t)d), d1 = m.in(desc1, 8 * (size_t)Nf1 * (size_t)d);
+    const auto m0 = m.in(mask0, 8 * (size_t)S0 * (((size_t)Nf0 + 63) / 64)), m1 = m.in(mask1, 8 * (size_t)S1 * (((size_t)Nf1 + 63) / 64));
+    const auto dSim = m.out(sim, 8 * (size_t)S0 * (size_t)S1);
+    rc = m.upload();
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(sim, dev + oSim, bSim, hipMemcpyDeviceToHost, WS.stream));
-    HIPCHK(c, hipStreamSynchronize(WS.stream));
-    return ROMAN_OK;
+    rc = roman_stacked_sim_dev(c, d, Nf0, d0.dev(), S0, m0.dev(), Nf1, d1.dev(), S1, m1.dev(), dSim.dev());
+    if (rc) return rc;
+    return m.download();
 }
 
 // --- the deal of a batch over ranks (pure host function; roman_amd.align.distributed.deal_by_cost states the same) ------------

@@ -22,6 +22,20 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _vp(x):
+    """A device address (an integer; 0 or None: absent) as a ctypes pointer argument."""
+    return C.c_void_p(int(x)) if x else None
+
+
+def _given(a, shape, dtype, fill):
+    """An output array of a host-pointer call: the caller's, checked, or a fresh one filled with `fill`."""
+    if a is None:
+        return np.full(shape, fill, dtype=dtype)
+    if a.dtype != dtype or not a.flags.c_contiguous or a.shape != shape:
+        raise ValueError(f"an output array must be C-contiguous {np.dtype(dtype).name} of shape {shape}")
+    return a
+
+
 def stats_dtype():
     return np.dtype([("n_assoc_in", np.int32), ("n_live", np.int32), ("nnz_upper", np.int64),
                      ("n_pass", np.int32), ("outer_iters", np.int32), ("inner_iters", np.int32),
@@ -346,10 +360,9 @@ class Context:
             kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
         a_out = np.empty((B, kmax, 2), dtype=np.int32); n_out = np.empty(B, dtype=np.int32)
         T = np.empty((B, 16), dtype=np.float64); status = np.empty(B, dtype=np.int32); stats = np.empty(B, dtype=stats_dtype())
-        vp = lambda x: C.c_void_p(int(x)) if x else None
         self._generation += 1
-        rc = self._lib.roman_align_batch_resident(self._h, C.byref(params), B, vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                                  int(F), vp(assoc_ptr), _ptr(assoc_off), vp(u0_ptr), int(kmax),
+        rc = self._lib.roman_align_batch_resident(self._h, C.byref(params), B, _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                                  int(F), _vp(assoc_ptr), _ptr(assoc_off), _vp(u0_ptr), int(kmax),
                                                   _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats))
         s = params.point_dim + 1
         res = lambda: BatchResult([a_out[b, :n_out[b]].copy() for b in range(B)], T[:, :s * s].reshape(B, s, s).copy(), status, stats)
@@ -372,12 +385,11 @@ class Context:
         n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
         if assoc_off is not None:
             assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        vp = lambda x: C.c_void_p(int(x)) if x else None
         self._generation += 1
-        rc = self._lib.roman_align_batch_dev(self._h, C.byref(params), int(n1.shape[0]), vp(feats_ptr), _ptr(off1),
-                                             _ptr(n1), _ptr(off2), _ptr(n2), int(F), vp(assoc_ptr), _ptr(assoc_off),
-                                             vp(u0_ptr), int(kmax), vp(assoc_out_ptr), vp(n_assoc_out_ptr),
-                                             vp(T_out_ptr), vp(status_out_ptr), vp(stats_out_ptr))
+        rc = self._lib.roman_align_batch_dev(self._h, C.byref(params), int(n1.shape[0]), _vp(feats_ptr), _ptr(off1),
+                                             _ptr(n1), _ptr(off2), _ptr(n2), int(F), _vp(assoc_ptr), _ptr(assoc_off),
+                                             _vp(u0_ptr), int(kmax), _vp(assoc_out_ptr), _vp(n_assoc_out_ptr),
+                                             _vp(T_out_ptr), _vp(status_out_ptr), _vp(stats_out_ptr))
         self._check(rc, "roman_align_batch_dev")
 
     # ------------------------------------------------------------------ multi-solution extraction
@@ -417,11 +429,10 @@ class Context:
         n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
         if assoc_off is not None:
             assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        vp = lambda x: C.c_void_p(int(x)) if x else None
         self._generation += 1
-        rc = self._lib.roman_mno_batch_dev(self._h, C.byref(params), int(n1.shape[0]), vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                           int(F), vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax), vp(assoc_out_ptr),
-                                           vp(sol_out_ptr), vp(stats_out_ptr))
+        rc = self._lib.roman_mno_batch_dev(self._h, C.byref(params), int(n1.shape[0]), _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                           int(F), _vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax), _vp(assoc_out_ptr),
+                                           _vp(sol_out_ptr), _vp(stats_out_ptr))
         self._check(rc, "roman_mno_batch_dev")
 
     # ------------------------------------------------------------------ RANSAC registration
@@ -456,9 +467,8 @@ class Context:
         NumPy arrays.  A pure enqueue on the context's stream; complete after sync()."""
         off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
         n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_ransac_batch_dev(self._h, C.byref(rparams), int(n1.shape[0]), vp(pts_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                              int(kmax), vp(assoc_out_ptr), vp(rec_out_ptr), vp(counts_out_ptr))
+        rc = self._lib.roman_ransac_batch_dev(self._h, C.byref(rparams), int(n1.shape[0]), _vp(pts_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                              int(kmax), _vp(assoc_out_ptr), _vp(rec_out_ptr), _vp(counts_out_ptr))
         self._check(rc, "roman_ransac_batch_dev")
 
     # ------------------------------------------------------------------ submaps from a whole map
@@ -486,17 +496,10 @@ class Context:
         descs = self._submap_descs(descs)
         S, rows, Fo = int(descs.shape[0]), int(descs.shape[0]) * max(int(sparams.cap), 0), int(sparams.point_dim) + F - 3
         d = int(desc_dim)
-
-        def given(a, shape, dtype, fill):
-            if a is None:
-                return np.full(shape, fill, dtype=dtype)
-            if a.dtype != dtype or not a.flags.c_contiguous or a.shape != shape:
-                raise ValueError(f"an output array must be C-contiguous {np.dtype(dtype).name} of shape {shape}")
-            return a
-        pool = given(pool, (rows, max(Fo, 0)), np.float64, 0.0) if (want_pool or pool is not None) else None
-        src = given(src, (rows,), np.int32, -1)
-        ids_out = given(ids_out, (rows,), np.int64, -1) if seg_ids is not None else None
-        desc_out = given(desc_out, (S, d), np.float64, np.nan) if d > 0 else None
+        pool = _given(pool, (rows, max(Fo, 0)), np.float64, 0.0) if (want_pool or pool is not None) else None
+        src = _given(src, (rows,), np.int32, -1)
+        ids_out = _given(ids_out, (rows,), np.int64, -1) if seg_ids is not None else None
+        desc_out = _given(desc_out, (S, d), np.float64, np.nan) if d > 0 else None
         count = np.zeros(S, dtype=np.int32); status = np.zeros(S, dtype=np.int32)
         self._generation += 1
         rc = self._lib.roman_submaps(self._h, C.byref(sparams), N, F, _ptr(seg_feats), _ptr(seg_times), _ptr(seg_ids), S, _ptr(descs),
@@ -509,10 +512,9 @@ class Context:
         """Device-pointer submap extraction (roman_submaps_dev): bulk pointers are device addresses (integers), `descs` a host
         submap_desc_dtype array.  A pure enqueue on the context's stream; complete after sync()."""
         descs = self._submap_descs(descs)
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_submaps_dev(self._h, C.byref(sparams), int(N), int(F), vp(seg_feats_ptr), vp(seg_times_ptr), vp(seg_ids_ptr),
-                                         int(descs.shape[0]), _ptr(descs), vp(pool_ptr), vp(count_ptr), vp(src_ptr), vp(ids_out_ptr),
-                                         vp(status_ptr), int(desc_dim), vp(desc_out_ptr))
+        rc = self._lib.roman_submaps_dev(self._h, C.byref(sparams), int(N), int(F), _vp(seg_feats_ptr), _vp(seg_times_ptr), _vp(seg_ids_ptr),
+                                         int(descs.shape[0]), _ptr(descs), _vp(pool_ptr), _vp(count_ptr), _vp(src_ptr), _vp(ids_out_ptr),
+                                         _vp(status_ptr), int(desc_dim), _vp(desc_out_ptr))
         self._check(rc, "roman_submaps_dev")
 
     # ------------------------------------------------------------------ pass 1 of a grid of submaps
@@ -522,36 +524,42 @@ class Context:
         radius mode): gparams a RomanGridGateParams (grid_gate_params()); per side pos (S, 3), T_w (S, 4, 4), optionally time
         (S,), desc (S, desc_dim) and pos_gt (S, 3).  The compact outputs may be handed in (C-contiguous, the C ABI's shapes and
         types): the slots beyond n_todo come back as they were; fresh ones are filled with -1 / NaN / -1.  -> GridGateResult."""
-        side = []
-        for pos, T_w, tm, desc, gt in ((pos0, T_w0, time0, desc0, pos_gt0), (pos1, T_w1, time1, desc1, pos_gt1)):
+        return self._grid_gate_host("roman_grid_gate", gparams, (pos0, T_w0, time0, desc0, pos_gt0, None), (pos1, T_w1, time1, desc1, pos_gt1, None),
+                                    pairs, T_ref, enable)
+
+    def _grid_gate_host(self, fn, gparams, side0, side1, pairs, T_ref, enable, sim_in=None, sim_name="sim_in"):
+        """The host-pointer gate behind grid_gate / grid_gate_sim / grid_gate_aabb: a side is (pos, T_w, time, desc, pos_gt, box);
+        only roman_grid_gate_aabb reads box, and with sim_in (the similarity is an input) desc is not read."""
+        aabb, side = fn == "roman_grid_gate_aabb", []
+        for pos, T_w, tm, desc, gt, box in (side0, side1):
             pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
-            T_w = _f64(T_w).reshape(-1, 16)
+            T_w = _f64(T_w).reshape(-1, 16); box = _f64(box).reshape(-1, 6) if aabb else None
             tm = None if tm is None else _f64(tm).reshape(-1)
-            desc = None if desc is None else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
+            desc = None if (desc is None or sim_in is not None) else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
             gt = None if gt is None else _f64(gt).reshape(-1, 3)
-            if T_w.shape[0] != S or (tm is not None and tm.shape[0] != S) or (gt is not None and gt.shape[0] != S):
+            if T_w.shape[0] != S or (aabb and box.shape[0] != S) or (tm is not None and tm.shape[0] != S) or (gt is not None and gt.shape[0] != S):
                 raise ValueError("the per-submap arrays of a side must hold one entry per submap")
             if desc is not None and gparams.desc_dim > 0 and desc.shape[1] != gparams.desc_dim:
                 raise ValueError("desc must be (S, desc_dim)")
-            side.append((S, pos, gt, T_w, tm, desc))
+            side.append((S, pos, gt, T_w, tm, desc, box))
         S0, S1 = side[0][0], side[1][0]
         B = S0 * S1
-
-        def given(a, shape, dtype, fill):
-            if a is None:
-                return np.full(shape, fill, dtype=dtype)
-            if a.dtype != dtype or not a.flags.c_contiguous or a.shape != shape:
-                raise ValueError(f"an output array must be C-contiguous {np.dtype(dtype).name} of shape {shape}")
-            return a
-        pairs = given(pairs, (B, 2), np.int32, -1); T_ref = given(T_ref, (B, 4, 4), np.float64, np.nan); enable = given(enable, (B,), np.int32, -1)
-        dist = np.zeros((S0, S1)); flags = np.zeros((S0, S1), dtype=np.int32); yaw = np.zeros((S0, S1)); sim = np.zeros((S0, S1))
+        if sim_in is not None:
+            sim_in = _f64(sim_in)
+            if sim_in.shape != (S0, S1):
+                raise ValueError(f"{sim_name} must be (S0, S1)")
+        pairs = _given(pairs, (B, 2), np.int32, -1); T_ref = _given(T_ref, (B, 4, 4), np.float64, np.nan); enable = _given(enable, (B,), np.int32, -1)
+        dist = np.zeros((S0, S1)); flags = np.zeros((S0, S1), dtype=np.int32); yaw = np.zeros((S0, S1))
+        sim = np.zeros((S0, S1)) if sim_in is None else None
         T_ij = np.zeros((S0, S1, 4, 4)); n_todo = np.zeros(1, dtype=np.int32)
         self._generation += 1
-        ins = [_ptr(a) for s in side for a in s[1:]]
-        rc = self._lib.roman_grid_gate(self._h, C.byref(gparams), S0, S1, *ins, _ptr(dist), _ptr(flags), _ptr(yaw), _ptr(sim), _ptr(T_ij),
-                                       _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(n_todo))
-        self._check(rc, "roman_grid_gate")
-        return GridGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, int(n_todo[0]))
+        # roman_grid_gate_sim takes no desc and the similarity in the sim slot; roman_grid_gate_aabb the boxes and sim_in behind the outputs
+        ins = [_ptr(a) for s in side for a in s[1:(5 if fn == "roman_grid_gate_sim" else 6)]]
+        tail = [_ptr(side[0][6]), _ptr(side[1][6]), _ptr(sim_in)] if aabb else []
+        rc = getattr(self._lib, fn)(self._h, C.byref(gparams), S0, S1, *ins, _ptr(dist), _ptr(flags), _ptr(yaw),
+                                    _ptr(sim_in if fn == "roman_grid_gate_sim" else sim), _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(n_todo), *tail)
+        self._check(rc, fn)
+        return GridGateResult(dist, flags, yaw, sim if sim_in is None else sim_in, T_ij, pairs, T_ref, enable, int(n_todo[0]))
 
     def grid_gate_dev(self, gparams, S0, S1, pos0_ptr, T_w0_ptr, pos1_ptr, T_w1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
                       pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr, time0_ptr=None, time1_ptr=None, desc0_ptr=None, desc1_ptr=None,
@@ -559,59 +567,28 @@ class Context:
         """Device-pointer pass 1 of the pair loop over an S0 x S1 grid (roman_grid_gate_dev): every pointer a device address (an
         integer, e.g. torch.Tensor.data_ptr()).  A pure enqueue on the context's stream; complete after sync().  T_ref_ptr and
         enable_ptr are what lc_tail_dev / align_lc_batch_dev take for the problems of `pairs`."""
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_grid_gate_dev(self._h, C.byref(gparams), int(S0), int(S1),
-                                           vp(pos0_ptr), vp(pos_gt0_ptr), vp(T_w0_ptr), vp(time0_ptr), vp(desc0_ptr),
-                                           vp(pos1_ptr), vp(pos_gt1_ptr), vp(T_w1_ptr), vp(time1_ptr), vp(desc1_ptr),
-                                           vp(dist_ptr), vp(flags_ptr), vp(yaw_deg_ptr), vp(sim_ptr), vp(T_ij_ptr),
-                                           vp(pairs_ptr), vp(T_ref_ptr), vp(enable_ptr), vp(n_todo_ptr))
-        self._check(rc, "roman_grid_gate_dev")
+        self._grid_gate_dev("roman_grid_gate_dev", gparams, S0, S1, pos0_ptr, pos_gt0_ptr, T_w0_ptr, time0_ptr, desc0_ptr,
+                            pos1_ptr, pos_gt1_ptr, T_w1_ptr, time1_ptr, desc1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
+                            pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr)
+
+    def _grid_gate_dev(self, fn, gparams, S0, S1, *ptrs):
+        """The device-pointer gate behind grid_gate_dev / grid_gate_sim_dev / grid_gate_aabb_dev: `ptrs` in the C function's order."""
+        rc = getattr(self._lib, fn)(self._h, C.byref(gparams), int(S0), int(S1), *[_vp(p) for p in ptrs])
+        self._check(rc, fn)
 
     def grid_gate_sim(self, gparams, sim, pos0, T_w0, pos1, T_w1, time0=None, time1=None, pos_gt0=None, pos_gt1=None,
                       pairs=None, T_ref=None, enable=None):
         """grid_gate() on a similarity that is already there (roman_grid_gate_sim): `sim` (S0, S1) is read, never written;
         gparams.desc_dim must be 0.  -> GridGateResult whose sim is the array handed in."""
-        side = []
-        for pos, T_w, tm, gt in ((pos0, T_w0, time0, pos_gt0), (pos1, T_w1, time1, pos_gt1)):
-            pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
-            T_w = _f64(T_w).reshape(-1, 16)
-            tm = None if tm is None else _f64(tm).reshape(-1)
-            gt = None if gt is None else _f64(gt).reshape(-1, 3)
-            if T_w.shape[0] != S or (tm is not None and tm.shape[0] != S) or (gt is not None and gt.shape[0] != S):
-                raise ValueError("the per-submap arrays of a side must hold one entry per submap")
-            side.append((S, pos, gt, T_w, tm))
-        S0, S1 = side[0][0], side[1][0]
-        B = S0 * S1
-        sim = _f64(sim)
-        if sim.shape != (S0, S1):
-            raise ValueError("sim must be (S0, S1)")
-
-        def given(a, shape, dtype, fill):
-            if a is None:
-                return np.full(shape, fill, dtype=dtype)
-            if a.dtype != dtype or not a.flags.c_contiguous or a.shape != shape:
-                raise ValueError(f"an output array must be C-contiguous {np.dtype(dtype).name} of shape {shape}")
-            return a
-        pairs = given(pairs, (B, 2), np.int32, -1); T_ref = given(T_ref, (B, 4, 4), np.float64, np.nan); enable = given(enable, (B,), np.int32, -1)
-        dist = np.zeros((S0, S1)); flags = np.zeros((S0, S1), dtype=np.int32); yaw = np.zeros((S0, S1))
-        T_ij = np.zeros((S0, S1, 4, 4)); n_todo = np.zeros(1, dtype=np.int32)
-        self._generation += 1
-        ins = [_ptr(a) for s in side for a in s[1:]]
-        rc = self._lib.roman_grid_gate_sim(self._h, C.byref(gparams), S0, S1, *ins, _ptr(dist), _ptr(flags), _ptr(yaw), _ptr(sim), _ptr(T_ij),
-                                           _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(n_todo))
-        self._check(rc, "roman_grid_gate_sim")
-        return GridGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, int(n_todo[0]))
+        return self._grid_gate_host("roman_grid_gate_sim", gparams, (pos0, T_w0, time0, None, pos_gt0, None), (pos1, T_w1, time1, None, pos_gt1, None),
+                                    pairs, T_ref, enable, sim_in=_f64(sim), sim_name="sim")
 
     def grid_gate_sim_dev(self, gparams, S0, S1, pos0_ptr, T_w0_ptr, pos1_ptr, T_w1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
                           pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr, time0_ptr=None, time1_ptr=None, pos_gt0_ptr=None, pos_gt1_ptr=None):
         """grid_gate_dev() on a similarity that is already there (roman_grid_gate_sim_dev): sim_ptr is an INPUT."""
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_grid_gate_sim_dev(self._h, C.byref(gparams), int(S0), int(S1),
-                                               vp(pos0_ptr), vp(pos_gt0_ptr), vp(T_w0_ptr), vp(time0_ptr),
-                                               vp(pos1_ptr), vp(pos_gt1_ptr), vp(T_w1_ptr), vp(time1_ptr),
-                                               vp(dist_ptr), vp(flags_ptr), vp(yaw_deg_ptr), vp(sim_ptr), vp(T_ij_ptr),
-                                               vp(pairs_ptr), vp(T_ref_ptr), vp(enable_ptr), vp(n_todo_ptr))
-        self._check(rc, "roman_grid_gate_sim_dev")
+        self._grid_gate_dev("roman_grid_gate_sim_dev", gparams, S0, S1, pos0_ptr, pos_gt0_ptr, T_w0_ptr, time0_ptr,
+                            pos1_ptr, pos_gt1_ptr, T_w1_ptr, time1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
+                            pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr)
 
     # ------------------------------------------------------------------ force-fill submaps, boxes, the bounding-box gate (DESIGN.md §4.12)
     def submaps_fill(self, point_dim, cap, seg_feats, descs, count, src, seg_ids=None, desc_dim=0, want_pool=True):
@@ -647,9 +624,8 @@ class Context:
         """Device-pointer gather of force-fill submaps (roman_submaps_fill_dev): count and src are device arrays the caller uploaded,
         `descs` a host submap_desc_dtype array.  A pure enqueue on the context's stream; complete after sync()."""
         descs = self._submap_descs(descs)
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_submaps_fill_dev(self._h, int(point_dim), int(cap), int(N), int(F), vp(seg_feats_ptr), vp(seg_ids_ptr), int(descs.shape[0]),
-                                              _ptr(descs), vp(count_ptr), vp(src_ptr), vp(pool_ptr), vp(ids_out_ptr), int(desc_dim), vp(desc_out_ptr))
+        rc = self._lib.roman_submaps_fill_dev(self._h, int(point_dim), int(cap), int(N), int(F), _vp(seg_feats_ptr), _vp(seg_ids_ptr), int(descs.shape[0]),
+                                              _ptr(descs), _vp(count_ptr), _vp(src_ptr), _vp(pool_ptr), _vp(ids_out_ptr), int(desc_dim), _vp(desc_out_ptr))
         self._check(rc, "roman_submaps_fill_dev")
 
     def submap_boxes(self, pool, cap, count, T_odom_center):
@@ -670,8 +646,7 @@ class Context:
 
     def submap_boxes_dev(self, S, F, cap, pool_ptr, count_ptr, T_odom_center_ptr, box_ptr):
         """Device-pointer boxes of the submaps of a pool (roman_submap_boxes_dev): a pure enqueue on the context's stream."""
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_submap_boxes_dev(self._h, int(S), int(F), int(cap), vp(pool_ptr), vp(count_ptr), vp(T_odom_center_ptr), vp(box_ptr))
+        rc = self._lib.roman_submap_boxes_dev(self._h, int(S), int(F), int(cap), _vp(pool_ptr), _vp(count_ptr), _vp(T_odom_center_ptr), _vp(box_ptr))
         self._check(rc, "roman_submap_boxes_dev")
 
     def grid_gate_aabb(self, gparams, box0, box1, pos0, T_w0, pos1, T_w1, time0=None, time1=None, desc0=None, desc1=None, pos_gt0=None, pos_gt1=None,
@@ -679,54 +654,17 @@ class Context:
         """grid_gate() with the bounding-box gate (roman_grid_gate_aabb): box_r (S_r, 6) as submap_boxes() gives them; gparams.radius
         is not read.  `sim_in` (S0, S1): the similarity is already there (gparams.desc_dim must be 0); the result's sim is then
         that array.  -> GridGateResult."""
-        side = []
-        for pos, T_w, tm, desc, gt, box in ((pos0, T_w0, time0, desc0, pos_gt0, box0), (pos1, T_w1, time1, desc1, pos_gt1, box1)):
-            pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
-            T_w = _f64(T_w).reshape(-1, 16); box = _f64(box).reshape(-1, 6)
-            tm = None if tm is None else _f64(tm).reshape(-1)
-            desc = None if (desc is None or sim_in is not None) else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
-            gt = None if gt is None else _f64(gt).reshape(-1, 3)
-            if T_w.shape[0] != S or box.shape[0] != S or (tm is not None and tm.shape[0] != S) or (gt is not None and gt.shape[0] != S):
-                raise ValueError("the per-submap arrays of a side must hold one entry per submap")
-            if desc is not None and gparams.desc_dim > 0 and desc.shape[1] != gparams.desc_dim:
-                raise ValueError("desc must be (S, desc_dim)")
-            side.append((S, pos, gt, T_w, tm, desc, box))
-        S0, S1 = side[0][0], side[1][0]
-        B = S0 * S1
-        if sim_in is not None:
-            sim_in = _f64(sim_in)
-            if sim_in.shape != (S0, S1):
-                raise ValueError("sim_in must be (S0, S1)")
-
-        def given(a, shape, dtype, fill):
-            if a is None:
-                return np.full(shape, fill, dtype=dtype)
-            if a.dtype != dtype or not a.flags.c_contiguous or a.shape != shape:
-                raise ValueError(f"an output array must be C-contiguous {np.dtype(dtype).name} of shape {shape}")
-            return a
-        pairs = given(pairs, (B, 2), np.int32, -1); T_ref = given(T_ref, (B, 4, 4), np.float64, np.nan); enable = given(enable, (B,), np.int32, -1)
-        dist = np.zeros((S0, S1)); flags = np.zeros((S0, S1), dtype=np.int32); yaw = np.zeros((S0, S1))
-        sim = np.zeros((S0, S1)) if sim_in is None else None
-        T_ij = np.zeros((S0, S1, 4, 4)); n_todo = np.zeros(1, dtype=np.int32)
-        self._generation += 1
-        ins = [_ptr(a) for s in side for a in s[1:6]]
-        rc = self._lib.roman_grid_gate_aabb(self._h, C.byref(gparams), S0, S1, *ins, _ptr(dist), _ptr(flags), _ptr(yaw), _ptr(sim), _ptr(T_ij),
-                                            _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(n_todo), _ptr(side[0][6]), _ptr(side[1][6]), _ptr(sim_in))
-        self._check(rc, "roman_grid_gate_aabb")
-        return GridGateResult(dist, flags, yaw, sim if sim_in is None else sim_in, T_ij, pairs, T_ref, enable, int(n_todo[0]))
+        return self._grid_gate_host("roman_grid_gate_aabb", gparams, (pos0, T_w0, time0, desc0, pos_gt0, box0), (pos1, T_w1, time1, desc1, pos_gt1, box1),
+                                    pairs, T_ref, enable, sim_in=sim_in)
 
     def grid_gate_aabb_dev(self, gparams, S0, S1, pos0_ptr, T_w0_ptr, pos1_ptr, T_w1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
                            pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr, box0_ptr=None, box1_ptr=None, sim_in_ptr=None, time0_ptr=None, time1_ptr=None,
                            desc0_ptr=None, desc1_ptr=None, pos_gt0_ptr=None, pos_gt1_ptr=None):
         """grid_gate_dev() with the bounding-box gate (roman_grid_gate_aabb_dev): box_r as submap_boxes_dev wrote them; with
         sim_in_ptr the similarity is an input (sim_ptr is then not written).  A pure enqueue on the context's stream."""
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_grid_gate_aabb_dev(self._h, C.byref(gparams), int(S0), int(S1),
-                                                vp(pos0_ptr), vp(pos_gt0_ptr), vp(T_w0_ptr), vp(time0_ptr), vp(desc0_ptr),
-                                                vp(pos1_ptr), vp(pos_gt1_ptr), vp(T_w1_ptr), vp(time1_ptr), vp(desc1_ptr),
-                                                vp(dist_ptr), vp(flags_ptr), vp(yaw_deg_ptr), vp(sim_ptr), vp(T_ij_ptr),
-                                                vp(pairs_ptr), vp(T_ref_ptr), vp(enable_ptr), vp(n_todo_ptr), vp(box0_ptr), vp(box1_ptr), vp(sim_in_ptr))
-        self._check(rc, "roman_grid_gate_aabb_dev")
+        self._grid_gate_dev("roman_grid_gate_aabb_dev", gparams, S0, S1, pos0_ptr, pos_gt0_ptr, T_w0_ptr, time0_ptr, desc0_ptr,
+                            pos1_ptr, pos_gt1_ptr, T_w1_ptr, time1_ptr, desc1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
+                            pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr, box0_ptr, box1_ptr, sim_in_ptr)
 
     # ------------------------------------------------------------------ frame descriptors of the submaps of a pool
     def frame_select(self, fparams, count, src, seg_times, frame_times, frame_pos=None, frame_desc=None):
@@ -755,10 +693,9 @@ class Context:
     def frame_select_dev(self, fparams, S, cap, count_ptr, src_ptr, N, seg_times_ptr, Nf, frame_times_ptr, mask_ptr, n_sel_ptr, span_ptr,
                          frame_pos_ptr=None, d=0, frame_desc_ptr=None, mean_ptr=None):
         """Device-pointer frame selection (roman_frame_select_dev): a pure enqueue on the context's stream, behind submaps_dev."""
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_frame_select_dev(self._h, C.byref(fparams), int(S), int(cap), vp(count_ptr), vp(src_ptr), int(N), vp(seg_times_ptr),
-                                              int(Nf), vp(frame_times_ptr), vp(frame_pos_ptr), int(d), vp(frame_desc_ptr),
-                                              vp(mask_ptr), vp(n_sel_ptr), vp(span_ptr), vp(mean_ptr))
+        rc = self._lib.roman_frame_select_dev(self._h, C.byref(fparams), int(S), int(cap), _vp(count_ptr), _vp(src_ptr), int(N), _vp(seg_times_ptr),
+                                              int(Nf), _vp(frame_times_ptr), _vp(frame_pos_ptr), int(d), _vp(frame_desc_ptr),
+                                              _vp(mask_ptr), _vp(n_sel_ptr), _vp(span_ptr), _vp(mean_ptr))
         self._check(rc, "roman_frame_select_dev")
 
     def stacked_sim(self, desc0, mask0, desc1, mask1):
@@ -780,9 +717,8 @@ class Context:
 
     def stacked_sim_dev(self, d, Nf0, desc0_ptr, S0, mask0_ptr, Nf1, desc1_ptr, S1, mask1_ptr, sim_ptr):
         """Device-pointer stacked similarity of a grid (roman_stacked_sim_dev): a pure enqueue on the context's stream."""
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_stacked_sim_dev(self._h, int(d), int(Nf0), vp(desc0_ptr), int(S0), vp(mask0_ptr), int(Nf1), vp(desc1_ptr),
-                                             int(S1), vp(mask1_ptr), vp(sim_ptr))
+        rc = self._lib.roman_stacked_sim_dev(self._h, int(d), int(Nf0), _vp(desc0_ptr), int(S0), _vp(mask0_ptr), int(Nf1), _vp(desc1_ptr),
+                                             int(S1), _vp(mask1_ptr), _vp(sim_ptr))
         self._check(rc, "roman_stacked_sim_dev")
 
     def set_stacked_band(self, rows=0):
@@ -881,8 +817,7 @@ class Context:
         (integers), the offsets and sizes host arrays.  A pure enqueue on the context's stream; complete after sync()."""
         off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
         n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_shared_ids_dev(self._h, int(B), vp(ids_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), vp(keep_ptr), vp(kept_ptr))
+        rc = self._lib.roman_shared_ids_dev(self._h, int(B), _vp(ids_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), _vp(keep_ptr), _vp(kept_ptr))
         self._check(rc, "roman_shared_ids_dev")
 
     def shared_reduce_dev(self, B, F, feats_ptr, region_row0, ids_ptr, off1, n1, off2, n2, keep_ptr, kept_ptr):
@@ -891,18 +826,16 @@ class Context:
         offsets and sizes host arrays.  A pure enqueue on the context's stream; complete after sync()."""
         off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
         n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_shared_reduce_dev(self._h, int(B), int(F), vp(feats_ptr), int(region_row0), vp(ids_ptr), _ptr(off1), _ptr(n1),
-                                               _ptr(off2), _ptr(n2), vp(keep_ptr), vp(kept_ptr))
+        rc = self._lib.roman_shared_reduce_dev(self._h, int(B), int(F), _vp(feats_ptr), int(region_row0), _vp(ids_ptr), _ptr(off1), _ptr(n1),
+                                               _ptr(off2), _ptr(n2), _vp(keep_ptr), _vp(kept_ptr))
         self._check(rc, "roman_shared_reduce_dev")
 
     def lc_tail_dev(self, lc_params, B, T_ptr, n_assoc_ptr, status_ptr, records_ptr, accepted_idx_ptr, n_accepted_ptr,
                     T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None, FR_ptr=None, iR_ptr=None):
         """The tail on its own over batch outputs in HBM (roman_lc_tail_dev): every pointer a device address (an integer, e.g.
         torch.Tensor.data_ptr()); lc_params a RomanLcParams (LcInputs.params()).  A pure enqueue on the context's stream."""
-        vp = lambda x: C.c_void_p(int(x)) if x else None
-        rc = self._lib.roman_lc_tail_dev(self._h, C.byref(lc_params), int(B), vp(T_ptr), vp(n_assoc_ptr), vp(status_ptr), vp(T_ref_ptr), vp(enable_ptr),
-                                         vp(FL_ptr), vp(iL_ptr), vp(FR_ptr), vp(iR_ptr), vp(records_ptr), vp(accepted_idx_ptr), vp(n_accepted_ptr))
+        rc = self._lib.roman_lc_tail_dev(self._h, C.byref(lc_params), int(B), _vp(T_ptr), _vp(n_assoc_ptr), _vp(status_ptr), _vp(T_ref_ptr), _vp(enable_ptr),
+                                         _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(accepted_idx_ptr), _vp(n_accepted_ptr))
         self._check(rc, "roman_lc_tail_dev")
 
     def align_lc_batch_dev(self, params, feats_ptr, F, off1, n1, off2, n2, kmax, assoc_out_ptr, n_assoc_out_ptr, T_out_ptr, status_out_ptr,
@@ -914,12 +847,11 @@ class Context:
         n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
         if assoc_off is not None:
             assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        vp = lambda x: C.c_void_p(int(x)) if x else None
         self._generation += 1
-        rc = self._lib.roman_align_lc_batch_dev(self._h, C.byref(params), int(n1.shape[0]), vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                                int(F), vp(assoc_ptr), _ptr(assoc_off), vp(u0_ptr), int(kmax), vp(assoc_out_ptr), vp(n_assoc_out_ptr),
-                                                vp(T_out_ptr), vp(status_out_ptr), vp(stats_out_ptr), C.byref(lc_params), vp(T_ref_ptr), vp(enable_ptr),
-                                                vp(FL_ptr), vp(iL_ptr), vp(FR_ptr), vp(iR_ptr), vp(records_ptr), vp(accepted_idx_ptr), vp(n_accepted_ptr))
+        rc = self._lib.roman_align_lc_batch_dev(self._h, C.byref(params), int(n1.shape[0]), _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                                int(F), _vp(assoc_ptr), _ptr(assoc_off), _vp(u0_ptr), int(kmax), _vp(assoc_out_ptr), _vp(n_assoc_out_ptr),
+                                                _vp(T_out_ptr), _vp(status_out_ptr), _vp(stats_out_ptr), C.byref(lc_params), _vp(T_ref_ptr), _vp(enable_ptr),
+                                                _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(accepted_idx_ptr), _vp(n_accepted_ptr))
         self._check(rc, "roman_align_lc_batch_dev")
 
     # ------------------------------------------------------------------ stepwise (clipperpy shim)
