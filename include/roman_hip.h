@@ -685,6 +685,51 @@ ROMAN_API int roman_ransac_batch(roman_ctx_t* ctx, const roman_ransac_params_t* 
                                  const int64_t* off2, const int32_t* n2,
                                  int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out);
 
+/*
+ * RANSAC loop closures: RansacReg.register + T_align [REF roman/align/ransac_reg.py:16-53] for B pairs whose
+ * centres lie in a pool of F-double ROWS — a submap pool built for any registration: columns 0-2 of a row are the centre, no
+ * other column is read —, pass 2 of the pair loop [REF roman/align/submap_align.py:160-200] and the loop-closure edge
+ * [REF roman/align/results.py:156-198] behind it: the baseline of the paper over the pools the ROMAN run uses, in one call.
+ *   rows       float64, rows of F >= 3 doubles; problem b reads rows off1[b] .. +n1[b] and off2[b] .. +n2[b] (F = 3: the packed
+ *              pool of roman_ransac_batch_dev, which is this kernel with F = 3 and no split outputs)
+ *   kmax, assoc_out, rec_out, counts_out   as for roman_ransac_batch_dev
+ *   T_out, n_assoc_out, status_out   float64[B][16], int32[B], int32[B], each or NULL: exactly the record's T (NaN with
+ *              ROMAN_ST_INSUFFICIENT / ROMAN_ST_EMPTY_MAP), n_assoc (the FULL inlier count, also under ROMAN_ST_ASSOC_TRUNCATED)
+ *              and status — what roman_lc_tail_dev reads; required when lc_params is given
+ *   lc_params  NULL: no tail, the arguments behind it are ignored.  Otherwise roman_lc_tail_dev's arguments and contract, to
+ *              the byte (ROMAN_ST_INSUFFICIENT / ROMAN_ST_EMPTY_MAP -> ROMAN_LC_FAILED_INSUFFICIENT with the sentinels;
+ *              tilt_thresh honoured as given); dim must be 3
+ * Errors (nothing is enqueued): everything roman_ransac_batch_dev rejects, F < 3, a NULL split output with lc_params,
+ * lc_params->dim != 3, non-zero reserved words, FL without iL (FR without iR) or the reverse -> ROMAN_E_INVALID; a side above
+ * ROMAN_RANSAC_MAX_OBJECTS -> ROMAN_E_TOO_LARGE.  B == 0 is legal and writes n_accepted = 0 when a tail is asked for.
+ */
+
+/* DEVICE bulk pointers; pure enqueue on the context's stream: k_ransac over strided rows, then k_lc_tail + k_lc_compact
+   behind it on the same stream (RANSAC never runs on the pipeline's internal streams: no roman_ctx_join needed).
+   [REF roman/align/ransac_reg.py:16-53], [REF roman/align/submap_align.py:160-200], [REF roman/align/results.py:156-198] */
+ROMAN_API int roman_ransac_lc_batch_dev(roman_ctx_t* ctx, const roman_ransac_params_t* rparams, int32_t B,
+                                        const double* rows, int32_t F, const int64_t* off1, const int32_t* n1,
+                                        const int64_t* off2, const int32_t* n2,   /* metadata HOST */
+                                        int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out /* or NULL */,
+                                        double* T_out, int32_t* n_assoc_out, int32_t* status_out,
+                                        const roman_lc_params_t* lc_params /* NULL: no tail and the lc arguments are ignored */,
+                                        const double* T_ref, const int32_t* enable,
+                                        const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                                        roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted);
+
+/* The same with HOST pointers everywhere (n_objects rows of F doubles; n_left / n_right submaps in FL / FR): staged through
+   the context's one HostMirror block like roman_ransac_batch, issued in calls of the host-batching chunk on the context's
+   stream, the tail ONCE over the whole batch behind the last chunk, one read-back.  iL / iR are range-checked here.
+   [REF roman/align/ransac_reg.py:16-53], [REF roman/align/submap_align.py:160-200], [REF roman/align/results.py:156-198] */
+ROMAN_API int roman_ransac_lc_batch(roman_ctx_t* ctx, const roman_ransac_params_t* rparams, int32_t B,
+                                    const double* rows, int64_t n_objects, int32_t F, const int64_t* off1, const int32_t* n1,
+                                    const int64_t* off2, const int32_t* n2,
+                                    int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out,
+                                    double* T_out, int32_t* n_assoc_out, int32_t* status_out,
+                                    const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                                    const double* FL, int32_t n_left, const int32_t* iL, const double* FR, int32_t n_right, const int32_t* iR,
+                                    roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted);
+
 /* ------------------------------------------------------------------------------------------- */
 /* submaps from a whole map: slice, prune, pack (radius mode)                                  */
 /* ------------------------------------------------------------------------------------------- */

@@ -125,10 +125,22 @@ def run_ransac_batch(registration, batch: AlignmentBatch, ctx=None, counts=None)
 
 def run_lc_batch(registration, batch: AlignmentBatch, lc, u0=None, ctx=None):
     """One roman_align_lc_batch call for `batch` with the loop-closure tail `lc` (runtime.LcInputs) behind it
-    -> runtime.LoopClosureResult."""
+    -> runtime.LoopClosureResult (a RansacReg: one roman_ransac_lc_batch call, run_ransac_lc_batch)."""
     ctx = ctx or registration._context()
+    if isinstance(registration, RansacReg):
+        if u0 is not None:
+            raise ValueError("RANSAC registration has no initial vector")
+        return run_ransac_lc_batch(registration, batch, lc, ctx=ctx)
     return ctx.align_lc_batch(registration._abi_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2, lc,
                               assoc=batch.assoc, assoc_off=batch.assoc_off, u0=u0, kmax=batch.kmax())
+
+
+def run_ransac_lc_batch(registration, batch: AlignmentBatch, lc, ctx=None):
+    """One roman_ransac_lc_batch call for `batch` — its pool may have any row width F >= 3, the centre in columns 0-2 — with the
+    loop-closure tail `lc` (runtime.LcInputs) behind the RANSAC kernel -> runtime.LoopClosureResult."""
+    ctx = ctx or registration._context()
+    kmax = int(max(1, np.max(batch.n1.astype(np.int64) * batch.n2))) if len(batch) else 1       # every correspondence may be an inlier
+    return ctx.ransac_lc_batch(registration._ransac_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2, lc, kmax=kmax)
 
 
 def run_lc_batch_ids(registration, batch: AlignmentBatch, lc, u0=None, ctx=None):

@@ -477,8 +477,8 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
     sm_io = sm_io or SubmapAlignIO()
     registration = registration or sm_params.get_object_registration()
     if isinstance(registration, RansacReg):
-        raise NotImplementedError("submap_align_grid builds on roman_align_lc_batch; RANSAC registration has no device tail yet "
-                                  "(use submap_align)")
+        raise NotImplementedError("submap_align_grid builds on roman_align_lc_batch, which a RansacReg does not go through "
+                                  "(use submap_align, or submap_align_pools over device-resident pools)")
     on_device = compute is None
     compute = compute or run_lc_batch
     S = [list(submaps[0]), list(submaps[1])]
@@ -608,12 +608,15 @@ class _TailBuffers:
         self.records = torch.zeros(B * _abi.LC_RECORD_NBYTES, dtype=torch.uint8, device=dev)
         self.acc_idx = torch.zeros(B, dtype=i32, device=dev); self.acc_n = torch.zeros(1, dtype=i32, device=dev)
 
-    def result(self, status, dim):
-        """-> runtime.LoopClosureResult on the host (`status`: the final status of every problem, as issue_chunked returns it)."""
+    def result(self, status, dim, assoc=None):
+        """-> runtime.LoopClosureResult on the host (`status`: the final status of every problem, as issue_chunked returns it;
+        `assoc`: the association lists where the caller has read them back already, as the RANSAC path does chunk by chunk)."""
         B, s = int(self.n.shape[0]), dim + 1
         rec = np.frombuffer(self.records.cpu().numpy().tobytes(), dtype=lc_record_dtype()).copy()
-        n_h, a_h = self.n.cpu().numpy(), self.assoc.cpu().numpy()
-        return LoopClosureResult([a_h[b, :n_h[b]].copy() for b in range(B)], self.T.cpu().numpy()[:, :s * s].reshape(B, s, s).copy(), status,
+        if assoc is None:
+            n_h, a_h = self.n.cpu().numpy(), self.assoc.cpu().numpy()
+            assoc = [a_h[b, :n_h[b]].copy() for b in range(B)]
+        return LoopClosureResult(assoc, self.T.cpu().numpy()[:, :s * s].reshape(B, s, s).copy(), status,
                                  np.zeros(B, dtype=stats_dtype()), rec, self.acc_idx.cpu().numpy()[:int(self.acc_n.cpu().numpy()[0])].copy())
 
 
@@ -632,6 +635,55 @@ def reduced_problems(off1, n1, off2, n2, kept, region_row0):
     lost = (kept[:, 0] != n1) | (kept[:, 1] != n2)
     return (np.where(lost, int(region_row0) + kb, off1), np.where(lost, kept[:, 0], n1).astype(np.int32),
             np.where(lost, int(region_row0) + kb + n1, off2), np.where(lost, kept[:, 1], n2).astype(np.int32))
+
+
+# A RansacReg over resident pools: the association block of one roman_ransac_lc_batch_dev call (problems x kmax x 8 bytes, kmax the
+# largest n1 * n2: every correspondence may be an inlier) stays under this many bytes; more problems go in several calls.
+RANSAC_ASSOC_CHUNK_BYTES = 256 << 20
+
+
+def _ransac_lc_over_pool(torch, ctx, registration, pool, batch, lp, o, tail_ptrs, wait_torch):
+    """The RANSAC baseline for the problems of `batch` over the resident `pool` (rows of any width F >= 3 whose columns 0-2 are
+    the centre: a pool built for any registration), DESIGN.md §4.13: roman_ransac_lc_batch_dev writes the split outputs into `o`
+    (a _TailBuffers), the tail follows with `tail_ptrs` (T_ref, enable, frames).  One fused call when the association block of
+    the whole batch fits RANSAC_ASSOC_CHUNK_BYTES; otherwise calls without a tail over chunks of problems — one chunk-sized
+    association buffer, read back between them — and ONE roman_lc_tail_dev over all problems at the end.
+    -> runtime.LoopClosureResult with ransac_records."""
+    from ..runtime import ransac_record_dtype
+    B, F, dev = len(batch), int(pool.shape[1]), pool.device
+    rp = registration._ransac_params()
+    kmax = int(max(1, np.max(batch.n1.astype(np.int64) * batch.n2)))
+    chunk = max(1, int(RANSAC_ASSOC_CHUNK_BYTES // (8 * kmax)))
+    nb = _abi.RANSAC_RECORD_NBYTES
+    rec = torch.zeros(B * nb, dtype=torch.uint8, device=dev)
+    rows = torch.full((min(B, chunk), kmax, 2), -1, dtype=torch.int32, device=dev)
+    wait_torch()                                             # the cleared buffers are in place before the library's stream writes them
+    assoc = []
+
+    def harvest(lo, hi):                                     # after a sync: the chunk's counts, then only the columns that hold rows
+        n = np.minimum(o.n[lo:hi].cpu().numpy(), kmax)
+        a = rows[:hi - lo, :int(n.max())].cpu().numpy()
+        assoc.extend(a[b, :n[b]].copy() for b in range(hi - lo))
+    if chunk >= B:
+        ctx.ransac_lc_batch_dev(rp, pool.data_ptr(), F, batch.off1, batch.n1, batch.off2, batch.n2, kmax, rows.data_ptr(), rec.data_ptr(),
+                                T_out_ptr=o.T.data_ptr(), n_assoc_out_ptr=o.n.data_ptr(), status_out_ptr=o.status.data_ptr(), lc_params=lp,
+                                records_ptr=o.records.data_ptr(), accepted_idx_ptr=o.acc_idx.data_ptr(), n_accepted_ptr=o.acc_n.data_ptr(), **tail_ptrs)
+        ctx.sync()
+        harvest(0, B)
+    else:
+        for lo in range(0, B, chunk):
+            hi = min(B, lo + chunk)
+            ctx.ransac_lc_batch_dev(rp, pool.data_ptr(), F, batch.off1[lo:hi], batch.n1[lo:hi], batch.off2[lo:hi], batch.n2[lo:hi], kmax,
+                                    rows.data_ptr(), rec.data_ptr() + lo * nb, T_out_ptr=o.T.data_ptr() + lo * 128,
+                                    n_assoc_out_ptr=o.n.data_ptr() + lo * 4, status_out_ptr=o.status.data_ptr() + lo * 4)
+            ctx.sync()
+            harvest(lo, hi)
+        ctx.lc_tail_dev(lp, B, o.T.data_ptr(), o.n.data_ptr(), o.status.data_ptr(), o.records.data_ptr(), o.acc_idx.data_ptr(), o.acc_n.data_ptr(),
+                        **tail_ptrs)
+        ctx.sync()
+    res = o.result(o.status.cpu().numpy().copy(), 3, assoc=assoc)
+    res.ransac_records = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=ransac_record_dtype()).copy()
+    return res
 
 
 def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, registration=None, gt_poses=(None, None)) -> SubmapAlignResults:
@@ -659,8 +711,14 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     build_submap_pool(fill=...) (force-fill slices) and radius-mode pools are served alike.
 
     Not covered — ValueError; SubmapPool.to_submaps() + submap_align_grid is the way: the AABB gate over pools with dim 2 (their
-    rows hold no z) or a context without roman_grid_gate_aabb_dev, RansacReg, registration plugins with a host prefilter, shared
-    ids over pools without `ids_dev`.
+    rows hold no z) or a context without roman_grid_gate_aabb_dev, registration plugins with a host prefilter, shared ids over
+    pools without `ids_dev`.
+
+    A RansacReg (method='ransac') runs over the same pools — built with ANY registration: roman_ransac_lc_batch_dev
+    reads the centre from columns 0-2 of a row and nothing else — with pass 1 and the shared-segment removal unchanged; in place
+    of issue_chunked, join and the tail there are RANSAC calls (chunked by RANSAC_ASSOC_CHUNK_BYTES) and one tail
+    (`_ransac_lc_over_pool`).  Refused for it: pools of dim 2, a `cap` above ROMAN_RANSAC_MAX_OBJECTS, a context without
+    roman_ransac_lc_batch_dev, and host-tensor pools while the registration has no context set.
 
     Frame descriptors need pools built with them (build_submap_pool(frames=...)): 'mean_frame_descriptor' goes
     through the same gate as 'mean_semantic'; 'stacked_frame_descriptors' through roman_stacked_sim_dev over the two pools' frame
@@ -674,8 +732,16 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     p = list(pools)
     if len(p) != 2:
         raise ValueError("pools must hold two SubmapPool objects")
-    if isinstance(registration, RansacReg):
-        raise ValueError("RansacReg has no device tail" + way)
+    ransac = isinstance(registration, RansacReg)
+    if ransac:                                               # (every check in front of registration._context(): nothing here makes a HIP context)
+        if any(int(q.table.point_dim) != 3 for q in p):
+            raise ValueError("RansacReg reads x y z from columns 0-2 of a pool row, and pools of dim 2 hold no z" + way)
+        if any(int(q.cap) > _abi.ROMAN_RANSAC_MAX_OBJECTS for q in p):
+            raise ValueError(f"RansacReg serves at most {_abi.ROMAN_RANSAC_MAX_OBJECTS} objects per submap (the pools' cap is larger)" + way)
+        if getattr(registration, "_ctx", None) is None and any(q.pool.device.type == "cpu" for q in p):
+            raise ValueError("RansacReg has no context set and the pools are host tensors: no device to run on" + way)
+        if not hasattr(registration._context(), "ransac_lc_batch_dev"):
+            raise ValueError("the context has no roman_ransac_lc_batch_dev" + way)
     aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
     mode = sm_params.submap_descriptor
     stacked = mode == 'stacked_frame_descriptors'
@@ -806,12 +872,18 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         off1, n1, off2, n2 = reduced_problems(batch.off1, batch.n1, batch.off2, batch.n2, kept_dev.cpu().numpy(), rows)
         batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), (rows + n_slots, F)), off1, n1, off2, n2, pair_index=batch.pair_index)
         pool = work
-    o = _TailBuffers(torch, dev, B, kmax)
+    o = _TailBuffers(torch, dev, B, 0 if ransac else kmax)   # (a RansacReg keeps its association rows in a buffer of its own)
     FL, FR = up(frames[0].reshape(-1, 16)), up(frames[1].reshape(-1, 16))
     iL, iR = g["pairs"][:B, 0].contiguous(), g["pairs"][:B, 1].contiguous()
     lp = _lc_inputs(sm_params, sm_io, registration).params()
     wait_torch()                                             # the pool (torch.cat), the cleared outputs and the frames are in place
     t0 = time.time()
+    if ransac:                                               # k_ransac over the rows as they are, the tail behind it
+        res = _ransac_lc_over_pool(torch, ctx, registration, pool, batch, lp, o,
+                                   dict(T_ref_ptr=g["T_ref"].data_ptr(), enable_ptr=g["enable"].data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
+                                        FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr()), wait_torch)
+        timing_list = [(time.time() - t0) / B] * B
+        return M.results(timing_list, _records_into_results(M, res, pairs[:, 0], pairs[:, 1], nearby))
     status = issue_chunked(ctx, registration._abi_params(), pool, batch, kmax, o.assoc, o.n, o.T, o.status)   # re-issues skipped problems, then synchronises:
     ctx.join()                                               # ... the tail below sees the FINAL attempt of every problem only
     ctx.lc_tail_dev(lp, B, o.T.data_ptr(), o.n.data_ptr(), o.status.data_ptr(), o.records.data_ptr(), o.acc_idx.data_ptr(), o.acc_n.data_ptr(),

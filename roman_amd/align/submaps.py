@@ -25,6 +25,7 @@ import numpy as np
 from .. import _abi
 from ..runtime import frame_select_params, mask_indices, submap_desc_dtype
 from .batch import AlignmentBatch
+from .ransac_reg import RansacReg
 from .submap_align import Submap, transform_rm_roll_pitch
 
 
@@ -150,7 +151,7 @@ class MapTable:
     @classmethod
     def from_segments(cls, registration, segments):
         """Packs the map ONCE with `registration.pack` (the row layout of the batch calls), plus times and ids.  The table's point
-        is always x y z, whatever the registration's dim."""
+        is always x y z, whatever the registration's dim.  A RansacReg packs centres only: rows of 3 doubles, desc_dim 0."""
         packed = registration.pack(segments)
         dim = registration.dim
         n = len(segments)
@@ -158,6 +159,8 @@ class MapTable:
         feats = np.ascontiguousarray(np.hstack([cen, packed[:, dim:]]))
         times = np.array([[s.first_seen, s.last_seen] for s in segments], dtype=np.float64).reshape(n, 2)
         ids = np.array([s.id for s in segments], dtype=np.int64).reshape(n)
+        if isinstance(registration, RansacReg):                                  # centres only: rows of 3 doubles, no descriptor
+            return cls(feats, times, ids, int(dim), 0)
         P = registration._abi_params()
         d = int(P.cos_feature_dim) if P.invariant != _abi.ROMAN_INV_EUCLIDEAN else 0
         return cls(feats, times, ids, int(dim), d)

@@ -6606,6 +6606,8 @@ __global__ void __launch_bounds__(64) k_pose(int dim, const double* __restrict__
 //   - output: each wave sweeps a contiguous quarter of the n1*n2 correspondences twice — counts and centroid sums first, then
 //     the rows (ballot + running prefix: row-major order) and the centred cross-covariance — and thread 0 forms the pose with
 //     write_pose.  The sums cover ALL inliers whatever kmax is; nothing here depends on what else is in the batch.
+//   - the pool may be a submap pool: rows of F >= 3 doubles whose columns 0-2 are the centre — only the two
+//     staging loops know —, and thread 0 repeats T, n_assoc and status into the split arrays the loop-closure tail reads.
 // ---------------------------------------------------------------------------------------------
 struct RansacDesc { int64_t off1, off2; int32_t n1, n2; };
 
@@ -6687,21 +6689,28 @@ __device__ __forceinline__ bool ransac_better(int ca, double sa, int64_t ha, int
     return ca > cb || (ca == cb && (sa < sb || (sa == sb && ha < hb)));
 }
 
-// one record, every byte of it (the padding behind best_count included: records of equal results are equal as bytes)
-__device__ __forceinline__ void ransac_record(roman_ransac_record_t* rec, int n_assoc, int status, int64_t n_hyp, int64_t n_scored, int64_t best_hyp,
-                                              int best_count, double best_sse, const double* T /* NULL: NaN */)
+// The split copies of a record's T, n_assoc and status (the arrays k_lc_tail reads: LcIn), each optional.
+struct RansacSplit { double* T; int32_t* n_assoc; int32_t* status; };
+
+// one record, every byte of it (the padding behind best_count included: records of equal results are equal as bytes), and the
+// split outputs of problem b wherever a record is written: the same T, n_assoc and status
+__device__ __forceinline__ void ransac_record(roman_ransac_record_t* rec, const RansacSplit& out, int b, int n_assoc, int status, int64_t n_hyp,
+                                              int64_t n_scored, int64_t best_hyp, int best_count, double best_sse, const double* T /* NULL: NaN */)
 {
     static_assert(offsetof(roman_ransac_record_t, best_sse) == offsetof(roman_ransac_record_t, best_count) + 8, "one padding word behind best_count");
     rec->n_assoc = n_assoc; rec->status = status; rec->n_hyp = n_hyp; rec->n_scored = n_scored; rec->best_hyp = best_hyp;
     rec->best_count = best_count; (&rec->best_count)[1] = 0; rec->best_sse = best_sse;
     for (int t = 0; t < 16; ++t) rec->T[t] = T ? T[t] : d_nan();
+    if (out.T) for (int t = 0; t < 16; ++t) out.T[(int64_t)b * 16 + t] = T ? T[t] : d_nan();
+    if (out.n_assoc) out.n_assoc[b] = n_assoc;
+    if (out.status) out.status[b] = status;
 }
 
 #define RANSAC_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
 __global__ void __launch_bounds__(RANSAC_NT) k_ransac(roman_ransac_params_t P, int B, const RansacDesc* __restrict__ probs, const double* __restrict__ pts,
-                                                       int kmax, int32_t* __restrict__ assoc_out, roman_ransac_record_t* __restrict__ rec_out,
-                                                       int32_t* __restrict__ counts_out)
+                                                       int F, int kmax, int32_t* __restrict__ assoc_out, roman_ransac_record_t* __restrict__ rec_out,
+                                                       int32_t* __restrict__ counts_out, RansacSplit split)
 {
     extern __shared__ __attribute__((aligned(16))) double ransac_pts[];   // P (n1 x 3) | Q (n2 x 3)
     __shared__ uint32_t queue[RANSAC_NW][RANSAC_QCAP];          // per wave: survivors of the round, as h - (start of the round)
@@ -6717,12 +6726,13 @@ __global__ void __launch_bounds__(RANSAC_NT) k_ransac(roman_ransac_params_t P, i
     const int n = pd.n1, m = pd.n2;
     roman_ransac_record_t* rec = rec_out + b;
     if (n <= 0 || m <= 0) {
-        if (tid == 0) ransac_record(rec, 0, ROMAN_ST_EMPTY_MAP, 0, 0, -1, 0, 0.0, nullptr);
+        if (tid == 0) ransac_record(rec, split, b, 0, ROMAN_ST_EMPTY_MAP, 0, 0, -1, 0, 0.0, nullptr);
         return;
     }
     double* sP = ransac_pts; double* sQ = ransac_pts + (size_t)n * 3;
-    for (int t = tid; t < n * 3; t += RANSAC_NT) sP[t] = pts[pd.off1 * 3 + t];
-    for (int t = tid; t < m * 3; t += RANSAC_NT) sQ[t] = pts[pd.off2 * 3 + t];
+    // the centres are columns 0-2 of rows of F doubles (F = 3: a packed pool); no other column is read
+    for (int t = tid; t < n * 3; t += RANSAC_NT) sP[t] = pts[(pd.off1 + t / 3) * F + t % 3];
+    for (int t = tid; t < m * 3; t += RANSAC_NT) sQ[t] = pts[(pd.off2 + t / 3) * F + t % 3];
     __syncthreads();
 
     const uint64_t nm = (uint64_t)n * (uint64_t)m;
@@ -6821,7 +6831,7 @@ __global__ void __launch_bounds__(RANSAC_NT) k_ransac(roman_ransac_params_t P, i
     // ---- the winner's inliers and the pose on them ----
     if (bh < 0) {                                               // nothing survived the prune
         __syncthreads();
-        if (tid == 0) ransac_record(rec, 0, ROMAN_ST_INSUFFICIENT, done, 0, -1, 0, 0.0, nullptr);
+        if (tid == 0) ransac_record(rec, split, b, 0, ROMAN_ST_INSUFFICIENT, done, 0, -1, 0, 0.0, nullptr);
         return;
     }
     double T[16];
@@ -6912,7 +6922,7 @@ __global__ void __launch_bounds__(RANSAC_NT) k_ransac(roman_ransac_params_t P, i
             write_pose(To, 3, Hs, m1, m2);
         }
         if (total > kmax) status |= ROMAN_ST_ASSOC_TRUNCATED;
-        ransac_record(rec, total, status, done, scored, bh, bc, bs, To);
+        ransac_record(rec, split, b, total, status, done, scored, bh, bc, bs, To);
     }
 }
 

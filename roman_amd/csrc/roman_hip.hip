@@ -2524,16 +2524,14 @@ static int ransac_check(roman_ctx* c, const roman_ransac_params_t* P, int32_t B,
     return check_batch(c, B, off1, n1, off2, n2, chk);
 }
 
-int roman_ransac_batch_dev(roman_ctx_t* c, const roman_ransac_params_t* rparams, int32_t B,
-                           const double* pts, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
-                           int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out)
+// k_ransac for B checked problems over rows of F doubles, on the context's stream: descriptors through the pinned staging, one launch
+static int enqueue_ransac(roman_ctx* c, const roman_ransac_params_t* rparams, int32_t B, const double* rows, int32_t F,
+                          const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                          int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out, const RansacSplit& split)
 {
-    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, -1, kmax, assoc_out, rec_out);
-    if (rc || B == 0) return rc;
     int maxN = 0; bool any = false;
     for (int b = 0; b < B; ++b) { maxN = std::max(maxN, n1[b] + n2[b]); any = any || (n1[b] > 0 && n2[b] > 0); }
-    if (!pts && any) return fail(c, ROMAN_E_INVALID, "pts is NULL");
+    if (!rows && any) return fail(c, ROMAN_E_INVALID, "pts is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t stream = c->stream;
     RansacDesc* staged = nullptr;
@@ -2541,38 +2539,133 @@ int roman_ransac_batch_dev(roman_ctx_t* c, const roman_ransac_params_t* rparams,
     for (int b = 0; b < B; ++b) staged[b] = RansacDesc{off1[b], off2[b], n1[b], n2[b]};
     HIPCHK(c, c->ransacStage.upload(c->ransacDesc, (size_t)B, stream));
     const size_t lds = sizeof(double) * 3 * (size_t)std::max(maxN, 1);          // both point sets of the largest problem (at most 48 KB)
-    hipLaunchKernelGGL(k_ransac, dim3((unsigned)B), dim3(RANSAC_NT), lds, stream, *rparams, (int)B, c->ransacDesc.as<RansacDesc>(), pts,
-                       (int)kmax, assoc_out, rec_out, counts_out);
+    hipLaunchKernelGGL(k_ransac, dim3((unsigned)B), dim3(RANSAC_NT), lds, stream, *rparams, (int)B, c->ransacDesc.as<RansacDesc>(), rows, (int)F,
+                       (int)kmax, assoc_out, rec_out, counts_out, split);
     HIPCHK(c, hipGetLastError());
     return ROMAN_OK;
+}
+
+int roman_ransac_batch_dev(roman_ctx_t* c, const roman_ransac_params_t* rparams, int32_t B,
+                           const double* pts, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                           int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, -1, kmax, assoc_out, rec_out);
+    if (rc || B == 0) return rc;
+    return enqueue_ransac(c, rparams, B, pts, 3, off1, n1, off2, n2, kmax, assoc_out, rec_out, counts_out, RansacSplit{nullptr, nullptr, nullptr});
 }
 
 int roman_ransac_batch(roman_ctx_t* c, const roman_ransac_params_t* rparams, int32_t B,
                        const double* pts, int64_t n_objects, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
                        int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out)
 {
+    return roman_ransac_lc_batch(c, rparams, B, pts, n_objects, 3, off1, n1, off2, n2, kmax, assoc_out, rec_out, counts_out, nullptr, nullptr, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+}
+
+// --- RANSAC loop closures: k_ransac over strided rows with the tail behind it ([REF roman/align/ransac_reg.py:16-53],
+// [REF roman/align/submap_align.py:160-200], [REF roman/align/results.py:156-198]) ---------------------------------
+// What both forms check before anything is enqueued, and the tail they enqueue (`t`; used only with lc_params).
+static int ransac_lc_check(roman_ctx* c, const roman_ransac_params_t* rparams, int32_t B, int32_t F, const int64_t* off1, const int32_t* n1,
+                           const int64_t* off2, const int32_t* n2, int64_t n_objects, int32_t kmax, const void* assoc_out, const void* rec_out,
+                           double* T_out, int32_t* n_assoc_out, int32_t* status_out, const roman_lc_params_t* lc_params,
+                           const double* T_ref, const int32_t* enable, const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                           roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted, LcTail* t)
+{
+    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, n_objects, kmax, assoc_out, rec_out);
+    if (rc) return rc;
+    if (F < 3) return fail(c, ROMAN_E_INVALID, "F=%d: a row starts with x y z", F);
+    if (!lc_params) return ROMAN_OK;
+    if (B > 0 && (!T_out || !n_assoc_out || !status_out)) return fail(c, ROMAN_E_INVALID, "the tail reads T_out / n_assoc_out / status_out: NULL split output");
+    rc = make_lc_tail(c, lc_params, T_out, n_assoc_out, status_out, T_ref, enable, FL, iL, FR, iR, records, accepted_idx, n_accepted, t);
+    if (rc) return rc;
+    if (lc_params->dim != 3) return fail(c, ROMAN_E_INVALID, "lc_params.dim must be 3 for RANSAC registration (got %d)", lc_params->dim);
+    if (B > 0 && (!records || !accepted_idx)) return fail(c, ROMAN_E_INVALID, "records / accepted_idx is NULL");
+    return ROMAN_OK;
+}
+
+int roman_ransac_lc_batch_dev(roman_ctx_t* c, const roman_ransac_params_t* rparams, int32_t B,
+                              const double* rows, int32_t F, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                              int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out,
+                              double* T_out, int32_t* n_assoc_out, int32_t* status_out,
+                              const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                              const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                              roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    LcTail t;
+    int rc = ransac_lc_check(c, rparams, B, F, off1, n1, off2, n2, -1, kmax, assoc_out, rec_out, T_out, n_assoc_out, status_out, lc_params,
+                             T_ref, enable, FL, iL, FR, iR, records, accepted_idx, n_accepted, &t);
+    if (rc) return rc;
+    if (B > 0) {
+        rc = enqueue_ransac(c, rparams, B, rows, F, off1, n1, off2, n2, kmax, assoc_out, rec_out, counts_out, RansacSplit{T_out, n_assoc_out, status_out});
+        if (rc) return rc;
+    }
+    if (!lc_params) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_lc_tail(c, c->stream, B, t);                  // behind k_ransac on the same stream
+}
+
+int roman_ransac_lc_batch(roman_ctx_t* c, const roman_ransac_params_t* rparams, int32_t B,
+                          const double* rows, int64_t n_objects, int32_t F, const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2,
+                          int32_t kmax, int32_t* assoc_out, roman_ransac_record_t* rec_out, int32_t* counts_out,
+                          double* T_out, int32_t* n_assoc_out, int32_t* status_out,
+                          const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                          const double* FL, int32_t n_left, const int32_t* iL, const double* FR, int32_t n_right, const int32_t* iR,
+                          roman_lc_record_t* records, int32_t* accepted_idx, int32_t* n_accepted)
+{
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (n_objects < 0) return fail(c, ROMAN_E_INVALID, "negative size");
-    int rc = ransac_check(c, rparams, B, off1, n1, off2, n2, n_objects, kmax, assoc_out, rec_out);
-    if (rc || B == 0) return rc;
+    LcTail t;
+    int rc = ransac_lc_check(c, rparams, B, F, off1, n1, off2, n2, n_objects, kmax, assoc_out, rec_out, T_out, n_assoc_out, status_out, lc_params,
+                             T_ref, enable, FL, iL, FR, iR, records, accepted_idx, n_accepted, &t);
+    if (rc) return rc;
+    if (lc_params) {
+        if (n_left < 0 || n_right < 0) return fail(c, ROMAN_E_INVALID, "negative size");
+        for (int b = 0; b < B; ++b) {                            // the device indexes the frame pools with these
+            if (iL && (iL[b] < 0 || iL[b] >= n_left)) return fail(c, ROMAN_E_INVALID, "iL[%d] = %d outside the %d left frames", b, iL[b], n_left);
+            if (iR && (iR[b] < 0 || iR[b] >= n_right)) return fail(c, ROMAN_E_INVALID, "iR[%d] = %d outside the %d right frames", b, iR[b], n_right);
+        }
+    }
+    if (B == 0) { if (lc_params) *n_accepted = 0; return ROMAN_OK; }
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
     c->last.scored = false; c->last.solved = false;            // workspace 0's feature staging is reused: the stepwise problem it held is gone
-    const double* dPts = nullptr;
-    rc = upload_inputs(c, pts, n_objects, 3, 0, nullptr, 0, &dPts);
+    const double* dRows = nullptr;
+    rc = upload_inputs(c, rows, n_objects, F, 0, nullptr, 0, &dRows);
     if (rc) return rc;
-    const size_t rowsPer = (size_t)kmax * 2, nCounts = counts_out ? (size_t)B * (size_t)rparams->max_iteration : 0;
+    const size_t nb = (size_t)B, rowsPer = (size_t)kmax * 2, nCounts = counts_out ? nb * (size_t)rparams->max_iteration : 0;
     HostMirror m(c);
-    const auto rec = m.out(rec_out, sizeof(roman_ransac_record_t) * (size_t)B);
-    const auto rows = m.out(assoc_out, sizeof(int32_t) * (size_t)B * rowsPer);
+    const auto rec = m.out(rec_out, sizeof(roman_ransac_record_t) * nb);
+    const auto arows = m.out(assoc_out, sizeof(int32_t) * nb * rowsPer);
     const auto cnt = m.inout(counts_out, sizeof(int32_t) * nCounts);            // entries beyond n_hyp come back as they were
+    const auto sT = m.out(T_out, T_out ? sizeof(double) * 16 * nb : 0);
+    const auto sN = m.out(n_assoc_out, n_assoc_out ? sizeof(int32_t) * nb : 0);
+    const auto sS = m.out(status_out, status_out ? sizeof(int32_t) * nb : 0);
+    const bool lc = lc_params != nullptr;
+    const auto dRef = m.in(T_ref, lc && T_ref ? sizeof(double) * 16 * nb : 0);
+    const auto dEn = m.in(enable, lc && enable ? sizeof(int32_t) * nb : 0);
+    const auto dFL = m.in(FL, lc && FL ? sizeof(double) * 16 * (size_t)n_left : 0);
+    const auto dIL = m.in(iL, lc && iL ? sizeof(int32_t) * nb : 0);
+    const auto dFR = m.in(FR, lc && FR ? sizeof(double) * 16 * (size_t)n_right : 0);
+    const auto dIR = m.in(iR, lc && iR ? sizeof(int32_t) * nb : 0);
+    const auto lrec = m.out(records, lc ? sizeof(roman_lc_record_t) * nb : 0);
+    const auto lidx = m.out(accepted_idx, lc ? sizeof(int32_t) * nb : 0);
+    const auto lcnt = m.out(n_accepted, lc ? sizeof(int32_t) : 0);
     rc = m.upload();
     if (rc) return rc;
     const int chunk = std::max(1, c->host_chunk);
     for (int lo = 0; lo < B; lo += chunk) {
         const int hi = std::min(B, lo + chunk);
-        rc = roman_ransac_batch_dev(c, rparams, hi - lo, dPts, off1 + lo, n1 + lo, off2 + lo, n2 + lo, kmax,
-                                    rows.dev() + (size_t)lo * rowsPer, rec.dev() + lo, nCounts ? cnt.dev() + (size_t)lo * (size_t)rparams->max_iteration : nullptr);
+        const RansacSplit split{sT.dev() ? sT.dev() + (size_t)lo * 16 : nullptr, sN.dev() ? sN.dev() + lo : nullptr, sS.dev() ? sS.dev() + lo : nullptr};
+        rc = enqueue_ransac(c, rparams, hi - lo, dRows, F, off1 + lo, n1 + lo, off2 + lo, n2 + lo, kmax, arows.dev() ? arows.dev() + (size_t)lo * rowsPer : nullptr,
+                            rec.dev() + lo, nCounts ? cnt.dev() + (size_t)lo * (size_t)rparams->max_iteration : nullptr, split);
+        if (rc) return rc;
+    }
+    if (lc) {                                                    // the tail ONCE over the whole batch, behind the last chunk
+        t.in = LcIn{sT.dev(), sN.dev(), sS.dev(), dRef.dev(), dEn.dev(), dFL.dev(), dIL.dev(), dFR.dev(), dIR.dev()};
+        t.rec = lrec.dev(); t.idx = lidx.dev(); t.cnt = lcnt.dev();
+        rc = enqueue_lc_tail(c, WS.stream, B, t);
         if (rc) return rc;
     }
     return m.download();

@@ -212,6 +212,8 @@ class LoopClosureResult(BatchResult):
     n1_kept: Optional[np.ndarray] = None
     n2_kept: Optional[np.ndarray] = None
     keep: Optional[np.ndarray] = None
+    # ransac_lc_batch only: the (B,) roman_ransac_record_t array (ransac_record_dtype) behind assoc / T / status; `stats` is zeros there
+    ransac_records: Optional[np.ndarray] = None
 
 
 class Context:
@@ -470,6 +472,54 @@ class Context:
         rc = self._lib.roman_ransac_batch_dev(self._h, C.byref(rparams), int(n1.shape[0]), _vp(pts_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
                                               int(kmax), _vp(assoc_out_ptr), _vp(rec_out_ptr), _vp(counts_out_ptr))
         self._check(rc, "roman_ransac_batch_dev")
+
+    def ransac_lc_batch(self, rparams, rows, off1, n1, off2, n2, lc, kmax=None, counts=None):
+        """Host-pointer RANSAC loop closures (roman_ransac_lc_batch): ransac_batch() over `rows` — (n_objects, F)
+        float64 with F >= 3, the centre in columns 0-2 and nothing else read — with the loop-closure tail `lc` (an LcInputs, dim 3)
+        behind it.  -> LoopClosureResult: assoc, T and status as ransac_batch gives them, `stats` zeros, the roman_ransac_record_t
+        array in `ransac_records`."""
+        rows = _f64(rows)
+        if rows.ndim != 2 or rows.shape[1] < 3:
+            raise ValueError("rows must be (n_objects, F) with F >= 3")
+        n_obj, F = rows.shape
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        B = int(n1.shape[0])
+        if kmax is None:
+            kmax = int(max(1, np.max(n1.astype(np.int64) * n2))) if B else 1
+        if counts is True:
+            counts = np.full((B, max(int(rparams.max_iteration), 0)), -2, dtype=np.int32)
+        elif counts is not None:
+            if counts.dtype != np.int32 or not counts.flags.c_contiguous or counts.shape != (B, int(rparams.max_iteration)):
+                raise ValueError("counts must be a C-contiguous (B, max_iteration) int32 array")
+        a_out = np.zeros((B, kmax, 2), dtype=np.int32); rec = np.zeros(B, dtype=ransac_record_dtype())
+        T = np.zeros((B, 16), dtype=np.float64); n_out = np.zeros(B, dtype=np.int32); status = np.zeros(B, dtype=np.int32)
+        records = np.zeros(B, dtype=lc_record_dtype()); idx = np.zeros(max(B, 1), dtype=np.int32); cnt = np.zeros(1, dtype=np.int32)
+        lp = lc.params()
+        T_ref, enable, FL, iL, FR, iR = lc.arrays(B)
+        self._generation += 1
+        rc = self._lib.roman_ransac_lc_batch(self._h, C.byref(rparams), B, _ptr(rows), n_obj, F, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), int(kmax),
+                                             _ptr(a_out), _ptr(rec), _ptr(counts), _ptr(T), _ptr(n_out), _ptr(status),
+                                             C.byref(lp), _ptr(T_ref), _ptr(enable), _ptr(FL), 0 if FL is None else FL.shape[0], _ptr(iL),
+                                             _ptr(FR), 0 if FR is None else FR.shape[0], _ptr(iR), _ptr(records), _ptr(idx), _ptr(cnt))
+        self._check(rc, "roman_ransac_lc_batch")
+        k = np.minimum(n_out, kmax)
+        return LoopClosureResult([a_out[b, :k[b]].copy() for b in range(B)], T.reshape(B, 4, 4).copy(), status, np.zeros(B, dtype=stats_dtype()),
+                                 records, idx[:int(cnt[0])].copy(), ransac_records=rec)
+
+    def ransac_lc_batch_dev(self, rparams, rows_ptr, F, off1, n1, off2, n2, kmax, assoc_out_ptr, rec_out_ptr, T_out_ptr=None, n_assoc_out_ptr=None,
+                            status_out_ptr=None, lc_params=None, records_ptr=None, accepted_idx_ptr=None, n_accepted_ptr=None, counts_out_ptr=None,
+                            T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None, FR_ptr=None, iR_ptr=None):
+        """Device-pointer RANSAC loop closures (roman_ransac_lc_batch_dev): k_ransac over rows of F doubles with the split outputs
+        T / n_assoc / status, and — with lc_params (a RomanLcParams; None: no tail) — the tail behind it on the context's stream.
+        Pointers are integers, metadata arrays host NumPy arrays.  A pure enqueue; complete after sync()."""
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        rc = self._lib.roman_ransac_lc_batch_dev(self._h, C.byref(rparams), int(n1.shape[0]), _vp(rows_ptr), int(F), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                                 int(kmax), _vp(assoc_out_ptr), _vp(rec_out_ptr), _vp(counts_out_ptr), _vp(T_out_ptr), _vp(n_assoc_out_ptr),
+                                                 _vp(status_out_ptr), None if lc_params is None else C.byref(lc_params), _vp(T_ref_ptr), _vp(enable_ptr),
+                                                 _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(accepted_idx_ptr), _vp(n_accepted_ptr))
+        self._check(rc, "roman_ransac_lc_batch_dev")
 
     # ------------------------------------------------------------------ submaps from a whole map
     @staticmethod
