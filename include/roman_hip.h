@@ -1050,6 +1050,49 @@ ROMAN_API int roman_grid_gate_aabb(roman_ctx_t* ctx, const roman_grid_gate_param
                                    int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo,
                                    const double* box0, const double* box1, const double* sim_in);
 
+/*
+ * roman_session_gate_dev: pass 1 [REF roman/align/submap_align.py:93-149] of EVERY robot pair of a multi-robot
+ * session — the loop of [REF demo/demo.py:138-161] — in one launch sequence: roman_grid_gate_dev over a list of grids ("blocks") that
+ * share one set of per-submap arrays.  Every bulk pointer DEVICE; a PURE ENQUEUE on the context's stream.  The small tables travel
+ * twice: on the device (the kernels read them) and as `_host` copies (the library validates them without a read-back).
+ *
+ *   R, sub_off int32[R+1]   robot r owns the global submaps [sub_off[r], sub_off[r+1]); sub_off[0] = 0, S = sub_off[R]
+ *   pos        float64[S*3]; pos_gt float64[S*3] or NULL; has_gt int32[R], read only with pos_gt: a block's distance is between the
+ *              ground-truth centres when BOTH its robots have has_gt set, between pos otherwise [REF :96-99]
+ *   T_w        float64[S*16]; time float64[S] (may be NULL when no block sets self_lc); desc float64[S*desc_dim] or NULL (desc_dim 0)
+ *   nb, blocks int32[nb*4]: (r0, r1, self_lc, reserved = 0): the grid of r0's submaps (rows) against r1's (columns); self_lc is the
+ *              block's single_robot_lc: the time gate into `enable`.  gparams->single_robot_lc is NOT read; every other field of
+ *              gparams holds for all blocks.  A robot pair (r0, r1) may be listed once.
+ *   pair_off   int64[nb+1]: prefix of n0 * n1;  tile_off int64[nb+1]: prefix of n0 * ceil(n1 / 4) — from sub_off and blocks
+ *
+ * Dense outputs (pair_off[nb] entries; block b row-major at pair_off[b]): dist, flags, yaw_deg, sim, T_ij (x16) — per block bit for
+ * bit what roman_grid_gate_dev writes for its two sides.  Compact outputs (capacity pair_off[nb]; slots beyond the total untouched):
+ *   pairs      int32[.][2] GLOBAL submap indices (gi, gj) of the TODO pairs: blocks in list order, row-major within a block
+ *   T_ref, enable   roman_grid_gate_dev's contract; enable = 0 only where the block's self_lc is set and |time[gi] - time[gj]| < lc_time_thresh
+ *   todo_off   int32[nb+1]: block b's TODO pairs are the slots [todo_off[b], todo_off[b+1]); todo_off[nb] is the total
+ * No atomics: two runs agree bit for bit.
+ *
+ * nb == 0 or no pair at all (robots without submaps): ROMAN_OK, todo_off all 0, nothing else written.  Errors: a NULL pointer that
+ * is needed, R < 0, nb < 0, r outside [0, R), sub_off decreasing or not starting at 0, a reserved word not 0, a NaN radius,
+ * desc_dim < 0, a robot pair listed twice, pair_off / tile_off that disagree with sub_off and blocks -> ROMAN_E_INVALID;
+ * radius < 0 -> ROMAN_E_UNSUPPORTED; pair_off[nb] * 16 beyond int32 -> ROMAN_E_TOO_LARGE.
+ */
+ROMAN_API int roman_session_gate_dev(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
+                                     const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                     int32_t nb, const int32_t* blocks, const int32_t* blocks_host,
+                                     const int64_t* pair_off, const int64_t* pair_off_host, const int64_t* tile_off, const int64_t* tile_off_host,
+                                     double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                     int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off);
+
+/* The same with HOST pointers everywhere (each table once).  Synchronous: copies in, runs roman_session_gate_dev, brings every
+   output back with one synchronisation.  The caller's pairs, T_ref and enable go up first: the slots beyond todo_off[nb] come back
+   as they were. */
+ROMAN_API int roman_session_gate(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                                 const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                 int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                                 double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                 int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off);
+
 /* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */
 /* ------------------------------------------------------------------------------------------- */

@@ -29,7 +29,7 @@ import json
 import pickle
 import time
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 from scipy.spatial.transform import Rotation as Rot
@@ -686,6 +686,38 @@ def _ransac_lc_over_pool(torch, ctx, registration, pool, batch, lp, o, tail_ptrs
     return res
 
 
+def _pool_side_host(pool, gt_poses, gt_available, reads, aabb_mode):
+    """The O(S) host block of one side of submap_align_pools / one robot of submap_align_session, over the non-empty submaps of
+    `pool`: centre, the pose the reference transform is built from, time, the edge frames — through the stand-in Submap's own
+    properties, read as often as the pair loop reads them (submap_align_grid does the same).  `reads`: ascending numbers of
+    submaps on the other side; T_w and the edge frames are given after each of them (a deterministic function applied n times: reading on
+    from one entry to the next gives what n reads from the start give).  -> dict(pos (S, 3), pos_gt (S, 3) or None, time (S,),
+    T_oc (S, 4, 4) or None, and per entry of reads: T_w [(S, 4, 4)], frames [((S, 4, 4) left, (S, 4, 4) right)])."""
+    c = pool.centers
+    gt = None if gt_poses is None else np.asarray(gt_poses, dtype=np.float64).reshape(len(c), 4, 4)
+    sms = [Submap(id=int(s), time=float(c.time[s]), segments=(), pose_flu=np.array(c.pose_flu[s], dtype=np.float64),
+                  pose_flu_gt=None if gt is None else gt[s].copy()) for s in pool.nonempty]
+    pos = np.stack([np.array(sm.position) for sm in sms])
+    pos_gt = None if gt is None else np.stack([np.array(sm.position_gt) for sm in sms])
+    # the AABB gate reads the pose once more per submap, in front of the pair loop (segments_as_global_points, by has_gt
+    # [REF roman/map/map.py:138]).  The pools' poses are yaw-only COPIES already, so how often the pair loop flattens them in
+    # place does not matter here: _read_times below stops at the fixed point either way
+    T_oc = None if not aabb_mode else np.stack([np.array(sm.pose_gravity_aligned_gt if sm.has_gt else sm.pose_gravity_aligned, dtype=np.float64) for sm in sms])
+    read = ("pose_gravity_aligned_gt", "pose_flu_gt") if gt_available else ("pose_gravity_aligned", "pose_flu")
+    T_w, frames, done = [], [], 0
+    for n in reads:                                          # (cumulative: the reads of one entry continue those of the entry before)
+        if n > done:
+            vals = [_read_times(sm, *read, n - done) for sm in sms]
+            T_w.append(np.stack([np.array(v, dtype=np.float64) for v in vals]))
+            fr = [_edge_frames(sm) for sm in sms]            # (on a copy of the submap as the reads left it)
+            frames.append((np.stack([f[0] for f in fr]), np.stack([f[1] for f in fr])))
+        else:
+            T_w.append(T_w[-1]); frames.append(frames[-1])
+        done = n
+    times = np.array([sm.time for sm in sms], dtype=np.float64)
+    return dict(pos=pos, pos_gt=pos_gt, T_w=T_w, time=times, T_oc=T_oc, frames=frames)
+
+
 def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, registration=None, gt_poses=(None, None)) -> SubmapAlignResults:
     """submap_align_grid() for two maps whose submaps are ALREADY in HBM (`pools`: two align.submaps.SubmapPool, as
     build_submap_pool leaves them): the same results as submap_align_grid(sm_params, [p.to_submaps(segments) for p in pools]),
@@ -791,21 +823,10 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     other = (n1, n0)
     side, frames = [], []
     for r in range(2):
-        c = p[r].centers
-        gt = None if gt_poses[r] is None else np.asarray(gt_poses[r], dtype=np.float64).reshape(len(c), 4, 4)
-        sms = [Submap(id=int(s), time=float(c.time[s]), segments=(), pose_flu=np.array(c.pose_flu[s], dtype=np.float64),
-                      pose_flu_gt=None if gt is None else gt[s].copy()) for s in keep[r]]
-        pos = np.stack([np.array(sm.position) for sm in sms])
-        pos_gt = None if gt is None else np.stack([np.array(sm.position_gt) for sm in sms])
-        # the AABB gate reads the pose once more per submap, in front of the pair loop (segments_as_global_points, by has_gt
-        # [REF roman/map/map.py:138]).  The pools' poses are yaw-only COPIES already, so how often the pair loop flattens them in
-        # place does not matter here: _read_times below stops at the fixed point either way
-        T_oc = None if not aabb_mode else np.stack([np.array(sm.pose_gravity_aligned_gt if sm.has_gt else sm.pose_gravity_aligned, dtype=np.float64) for sm in sms])
-        read = ("pose_gravity_aligned_gt", "pose_flu_gt") if sm_io.gt_available[r] else ("pose_gravity_aligned", "pose_flu")
-        T_w = np.stack([np.array(_read_times(sm, *read, other[r]), dtype=np.float64) for sm in sms])
-        times = np.array([sm.time for sm in sms], dtype=np.float64)
-        frames.append(np.stack([_edge_frames(sm)[r] for sm in sms]))
-        side.append(dict(pos=up(pos), gt=up(pos_gt), T_w=up(T_w.reshape(-1, 16)), time=up(times), T_oc=None if T_oc is None else up(T_oc.reshape(-1, 16)),
+        hs = _pool_side_host(p[r], gt_poses[r], sm_io.gt_available[r], [other[r]], aabb_mode)
+        frames.append(hs["frames"][0][r])
+        side.append(dict(pos=up(hs["pos"]), gt=up(hs["pos_gt"]), T_w=up(hs["T_w"][0].reshape(-1, 16)), time=up(hs["time"]),
+                         T_oc=None if hs["T_oc"] is None else up(hs["T_oc"].reshape(-1, 16)),
                          desc=p[r].desc_dev[torch.from_numpy(keep[r].astype(np.int64)).to(dev)].contiguous() if d else None))
 
     # ---- pass 1 on the device: one enqueue, one synchronisation, the pair list and the dense matrices back ----
@@ -892,6 +913,219 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     ctx.sync()
     timing_list = [(time.time() - t0) / B] * B
     return M.results(timing_list, _records_into_results(M, o.result(status, sm_params.dim), pairs[:, 0], pairs[:, 1], nearby))
+
+
+def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[SubmapAlignIO] = None, registration=None,
+                         gt_poses=None) -> Dict[Tuple[int, int], SubmapAlignResults]:
+    """The robot-pair loop of the reference's driver [REF demo/demo.py:138-161] in ONE call: `pools` is a list of R
+    device-resident SubmapPool, `robot_pairs` the blocks (r, s) to align — default: every r <= s in the driver's order.  -> {(r, s):
+    SubmapAlignResults}, each equal to what submap_align_pools(p, [pools[r], pools[s]], ...) returns for that block alone with
+    single_robot_lc = (r == s), as [REF demo/demo.py:160] sets it.  sm_params.single_robot_lc is IGNORED.
+
+    gt_poses[r] follows submap_align_pools; a block's sm_io.gt_available is (gt_poses[r] is not None, gt_poses[s] is not None).
+    `sm_io` is shared by all blocks (every result carries a copy with its own gt_available); the caller names the output files
+    when it calls the writers on each result.
+
+    Per robot the O(S) host block runs once per distinct outcome of the pair loop's pose reads (as a rule: once) and goes up
+    once; pass 1 of all blocks is one roman_session_gate_dev, one
+    synchronisation and one read-back; every TODO pair of every block is a problem of ONE batch over the concatenated pools
+    (self blocks lose the segments both submaps hold through one roman_shared_reduce_dev over their problems); one
+    issue_chunked, one join, one roman_lc_tail_dev with the frames tabled over all submaps of the session.
+
+    Not covered — ValueError before any context is made; submap_align_pools per robot pair is the way: force_fill_submaps / no
+    submap_radius, 'stacked_frame_descriptors', a RansacReg, a plugin with a host prefilter, pools of different row width or
+    descriptor length, a self block over a pool without ids_dev, and whatever submap_align_pools refuses for a pool.  Two
+    refusals ask the context itself and so come after it exists, as in submap_align_pools: a context without
+    roman_session_gate_dev, and one without roman_shared_reduce_dev when the list holds a self block."""
+    import torch
+    from ..runtime import session_tables
+    from .pipeline import issue_chunked
+    sm_io = sm_io or SubmapAlignIO()
+    registration = registration or sm_params.get_object_registration()
+    way = " (not in the session call: use submap_align_pools per robot pair)"
+    p = list(pools)
+    R = len(p)
+    gt_poses = [None] * R if gt_poses is None else list(gt_poses)
+    blocks = [(r, s) for r in range(R) for s in range(r, R)] if robot_pairs is None else [(int(r), int(s)) for r, s in robot_pairs]
+    if len(gt_poses) != R:
+        raise ValueError("gt_poses must hold one entry per pool" + way)
+    if any(not (0 <= r < R and 0 <= s < R) for r, s in blocks) or len(set(blocks)) != len(blocks):
+        raise ValueError("robot_pairs must name pools by index, each pair once" + way)
+    if isinstance(registration, RansacReg):
+        raise ValueError("a RansacReg does not go through the batched solver" + way)
+    if sm_params.force_fill_submaps or sm_params.submap_radius is None:
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes" + way)
+    mode = sm_params.submap_descriptor
+    if mode == 'stacked_frame_descriptors':
+        raise ValueError("'stacked_frame_descriptors' needs the similarity of roman_stacked_sim_dev per pair of maps" + way)
+    if mode not in (None, 'mean_semantic', 'mean_frame_descriptor'):
+        raise ValueError(f"submap_descriptor {mode!r} is not one the pools carry" + way)
+    if mode == 'mean_frame_descriptor' and any(q.descriptor_mode != mode for q in p):
+        raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool(frames=...) keeps the frame masks on the device)" + way)
+    if _has_host_prefilter(registration):
+        raise ValueError("the registration plugin prefilters association lists on the host" + way)
+    if R and any(int(q.pool.shape[1]) != int(p[0].pool.shape[1]) for q in p):
+        raise ValueError("the pools have different row widths" + way)
+    d = 0
+    if mode is not None and R:
+        if any(q.desc_dev is None for q in p):
+            raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool keeps the descriptors on the device)" + way)
+        d = int(p[0].desc_dev.shape[1])
+        if any(int(q.desc_dev.shape[1]) != d for q in p):
+            raise ValueError("the pools have descriptors of different lengths" + way)
+    selfs = sorted({r for r, s in blocks if r == s})
+    if any(p[r].ids_dev is None for r in selfs):
+        raise ValueError("a self block drops the segments both submaps hold: its pool must have kept its ids on the device (SubmapPool.ids_dev, "
+                         "as build_submap_pool leaves it)" + way)
+    keep = [q.nonempty for q in p]
+    counts = np.array([len(k) for k in keep], dtype=np.int64)
+    # ---- per robot (O(S), host): the block submap_align_pools runs per side, with the reads of the pair loop it would see.  A
+    # pose read `n` times (n: the partner's submaps) usually sits at a fixed point after a read or two, and the robot then has ONE
+    # set of arrays for all its blocks; where flattening a pose alternates between two neighbouring values, its reference
+    # transform depends on n, and the robot enters the tables once per distinct outcome (a "view": same pool rows, own T_w and
+    # edge frames).  views[v] = (robot, host arrays or None); view_of[(r, n)] = v ----
+    views, view_of = [], {}
+    for r in range(R):
+        reads = sorted({int(counts[s if a == r else a]) for a, s in blocks if r in (a, s)})
+        mine = []
+        live_reads = [n for n in reads if n > 0] if counts[r] else []       # (an empty block: the robot only needs a place in the tables)
+        all_ = _pool_side_host(p[r], gt_poses[r], gt_poses[r] is not None, live_reads, False) if live_reads else None
+        for k, n in enumerate(live_reads):
+            hs = dict(all_, T_w=[all_["T_w"][k]], frames=all_["frames"][k])
+            key = hs["T_w"][0].tobytes() + hs["frames"][0].tobytes() + hs["frames"][1].tobytes()
+            same = [v for v, kk in mine if kk == key]
+            if not same:
+                views.append((r, hs)); mine.append((len(views) - 1, key))
+            view_of[(r, n)] = same[0] if same else len(views) - 1
+        if reads and not mine:                               # only in empty blocks: zeros stand in (never read)
+            views.append((r, None)); mine.append((len(views) - 1, b""))
+        for n in reads:
+            view_of.setdefault((r, n), mine[0][0])
+    vcount = np.array([counts[r] for r, _ in views], dtype=np.int64)
+    vblocks = [(view_of[(r, int(counts[s]))], view_of[(s, int(counts[r]))]) for r, s in blocks]
+
+    # ---- the refusals that need no context are behind us: the tables, the context, the uploads ----
+    def result_of(b, M, timing=(), edges=None):
+        io = copy.copy(sm_io); io.gt_available = (gt_poses[blocks[b][0]] is not None, gt_poses[blocks[b][1]] is not None)
+        M.sm_io = io
+        return M.results(timing, edges)
+    prm = [copy.copy(sm_params) for _ in blocks]
+    for q, (r, s) in zip(prm, blocks):
+        q.single_robot_lc = (r == s)
+    Ms = [_GridResults(prm[b], sm_io, int(counts[r]), int(counts[s])) for b, (r, s) in enumerate(blocks)]
+    sub_off, blk, pair_off, tile_off = session_tables(vcount, [(va, vb, r == s) for (va, vb), (r, s) in zip(vblocks, blocks)])
+    total, nb = int(pair_off[-1]), len(blocks)
+    if total == 0:
+        return {blocks[b]: result_of(b, Ms[b], edges=Ms[b].empty_edges()) for b in range(nb)}
+    ctx = registration._context()
+    if selfs and not hasattr(ctx, "shared_reduce_dev"):      # (these two ask the context itself, as submap_align_pools does)
+        raise ValueError("self blocks need a context with roman_shared_reduce_dev" + way)
+    if not hasattr(ctx, "session_gate_dev"):
+        raise ValueError("the context has no roman_session_gate_dev" + way)
+    dev = p[0].pool.device
+    on_host = dev.type == "cpu"                              # CPU tensors + a stand-in context (tests)
+    wait_torch = (lambda: None) if on_host else (lambda: torch.cuda.current_stream(dev).synchronize())
+    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    lv = [(r, hs) for r, hs in views if counts[r]]           # the views that hold submaps, in table order
+    cat = lambda get, width: np.concatenate([np.zeros((int(counts[r]),) + width) if hs is None else np.asarray(get(hs)).reshape((-1,) + width) for r, hs in lv])
+    any_gt = any(gt_poses[r] is not None for r, _ in lv)
+    pos_gt = None
+    if any_gt:
+        pos_gt = np.concatenate([np.full((int(counts[r]), 3), np.nan) if (hs is None or hs["pos_gt"] is None) else hs["pos_gt"] for r, hs in lv])
+    FLh, FRh = cat(lambda hs: hs["frames"][0], (16,)), cat(lambda hs: hs["frames"][1], (16,))
+    rows_of = {r: torch.from_numpy(keep[r].astype(np.int64)).to(dev) for r in {r for r, _ in lv}} if d else {}
+    t = dict(pos=up(cat(lambda hs: hs["pos"], (3,))), gt=up(pos_gt),
+             has=up(np.array([gt_poses[r] is not None for r, _ in views], dtype=np.int32)) if any_gt else None,
+             T_w=up(cat(lambda hs: hs["T_w"][0], (16,))), time=up(cat(lambda hs: hs["time"], ())), sub_off=up(sub_off), blocks=up(blk),
+             pair_off=up(pair_off), tile_off=up(tile_off), desc=torch.cat([p[r].desc_dev[rows_of[r]] for r, _ in lv]).contiguous() if d else None)
+
+    # ---- pass 1 of all blocks on the device: one enqueue, one synchronisation, one read-back ----
+    f64, i32 = torch.float64, torch.int32
+    g = dict(dist=torch.empty(total, dtype=f64, device=dev), flags=torch.empty(total, dtype=i32, device=dev), yaw=torch.empty(total, dtype=f64, device=dev),
+             sim=torch.empty(total, dtype=f64, device=dev), T_ij=torch.empty((total, 16), dtype=f64, device=dev),
+             pairs=torch.empty((total, 2), dtype=i32, device=dev), T_ref=torch.empty((total, 16), dtype=f64, device=dev),
+             enable=torch.empty(total, dtype=i32, device=dev), todo_off=torch.zeros(nb + 1, dtype=i32, device=dev))
+    gp = grid_gate_params(sm_params.submap_radius, sm_io.skip_distance, d, sm_params.submap_descriptor_thresh if d else 0.0,
+                          False, sm_params.single_robot_lc_time_thresh)
+    wait_torch()                                             # the uploads are in place before the library's stream reads them
+    ctx.session_gate_dev(gp, sub_off, blk, pair_off, tile_off, ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]), ptr(t["tile_off"]),
+                         ptr(t["pos"]), ptr(t["T_w"]), *[g[k].data_ptr() for k in ("dist", "flags", "yaw", "sim", "T_ij", "pairs", "T_ref", "enable", "todo_off")],
+                         time_ptr=ptr(t["time"]), desc_ptr=ptr(t["desc"]), pos_gt_ptr=ptr(t["gt"]), has_gt_ptr=ptr(t["has"]))
+    ctx.sync()
+    todo_off = g["todo_off"].cpu().numpy().astype(np.int64)
+    B = int(todo_off[-1])
+    gpairs = g["pairs"][:B].cpu().numpy().astype(np.int64)
+    h = {k: g[k].cpu().numpy() for k in ("dist", "flags", "yaw", "sim", "T_ij")}
+    nearby, local = [], []
+    for b, (r, s) in enumerate(blocks):
+        n0, n1 = int(counts[r]), int(counts[s])
+        lo, hi = int(pair_off[b]), int(pair_off[b + 1])
+        flags = h["flags"][lo:hi].reshape(n0, n1)
+        near, todo = (flags & _abi.ROMAN_GRID_NEARBY) != 0, (flags & _abi.ROMAN_GRID_TODO) != 0
+        Ms[b].pass1(h["dist"][lo:hi].reshape(n0, n1), near, (flags & _abi.ROMAN_GRID_SKIP) != 0, (flags & _abi.ROMAN_GRID_GATED) != 0,
+                    h["yaw"][lo:hi].reshape(n0, n1), h["sim"][lo:hi].reshape(n0, n1), h["T_ij"][lo:hi].reshape(n0, n1, 4, 4))
+        lp_ = gpairs[todo_off[b]:todo_off[b + 1]] - np.array([sub_off[vblocks[b][0]], sub_off[vblocks[b][1]]], dtype=np.int64)
+        if not np.array_equal(lp_, np.stack(np.nonzero(todo), axis=1)):
+            raise _abi.RomanHipError(f"roman_session_gate_dev: the compact pair list of block {blocks[b]} is not its TODO pairs in row-major order")
+        nearby.append(near); local.append(lp_)
+    if B == 0:
+        return {blocks[b]: result_of(b, Ms[b], edges=Ms[b].empty_edges()) for b in range(nb)}
+
+    # ---- ONE batch over the concatenated pools: offsets and counts per global submap, the problems in compact order ----
+    live = sorted({r for r, _ in lv})                        # every robot's rows once, whatever the number of its views
+    pool = p[live[0]].pool if len(live) == 1 else torch.cat([p[r].pool for r in live], dim=0)
+    row0 = dict(zip(live, np.concatenate([[0], np.cumsum([int(p[r].pool.shape[0]) for r in live])]).astype(np.int64).tolist()))
+    sm_row = np.concatenate([row0[r] + p[r].offsets()[0] for r, _ in lv])       # per GLOBAL submap index (the gate's), as sub_off orders them
+    sm_cnt = np.concatenate([p[r].offsets()[1] for r, _ in lv]).astype(np.int32)
+    rows, F = int(pool.shape[0]), int(pool.shape[1])
+    off1, n1_, off2, n2_ = sm_row[gpairs[:, 0]], sm_cnt[gpairs[:, 0]], sm_row[gpairs[:, 1]], sm_cnt[gpairs[:, 1]]
+    kmax = int(max(1, np.max(np.minimum(n1_, n2_))))         # (of the unreduced sizes: still a bound after the removal)
+    of_self = np.concatenate([np.full(int(todo_off[b + 1] - todo_off[b]), r == s, dtype=bool) for b, (r, s) in enumerate(blocks)])
+    sel = np.nonzero(of_self)[0]
+    if len(sel):
+        # the problems of the self blocks lose the segments both submaps hold: the pools' rows and behind them the gather region of
+        # THESE problems in one allocation, one launch, the kept counts back (the one extra synchronisation)
+        n_slots = int(n1_[sel].sum(dtype=np.int64) + n2_[sel].sum(dtype=np.int64))
+        work = torch.empty((rows + n_slots, F), dtype=torch.float64, device=dev)
+        work[:rows].copy_(pool)
+        ids_dev = torch.cat([p[r].ids_dev if p[r].ids_dev is not None else torch.zeros(int(p[r].pool.shape[0]), dtype=torch.int64, device=dev) for r in live])
+        keep_dev = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev); kept_dev = torch.zeros((len(sel), 2), dtype=torch.int32, device=dev)
+        wait_torch()                                         # the copy of the pools and the ids are in place
+        ctx.shared_reduce_dev(len(sel), F, work.data_ptr(), rows, ids_dev.data_ptr(), np.ascontiguousarray(off1[sel]), np.ascontiguousarray(n1_[sel]),
+                              np.ascontiguousarray(off2[sel]), np.ascontiguousarray(n2_[sel]), keep_dev.data_ptr(), kept_dev.data_ptr())
+        ctx.sync()
+        red = reduced_problems(off1[sel], n1_[sel], off2[sel], n2_[sel], kept_dev.cpu().numpy(), rows)
+        off1, n1_, off2, n2_ = off1.copy(), n1_.copy(), off2.copy(), n2_.copy()
+        off1[sel], n1_[sel], off2[sel], n2_[sel] = red
+        pool, rows = work, rows + n_slots
+    batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), (rows, F)), off1.astype(np.int64), n1_.astype(np.int32), off2.astype(np.int64), n2_.astype(np.int32),
+                           pair_index=gpairs)
+    o = _TailBuffers(torch, dev, B, kmax)
+    FL, FR = up(FLh), up(FRh)
+    iL, iR = g["pairs"][:B, 0].contiguous(), g["pairs"][:B, 1].contiguous()
+    lp = _lc_inputs(sm_params, sm_io, registration).params()
+    wait_torch()                                             # the pool (torch.cat), the cleared outputs and the frames are in place
+    t0 = time.time()
+    status = issue_chunked(ctx, registration._abi_params(), pool, batch, kmax, o.assoc, o.n, o.T, o.status)
+    ctx.join()                                               # the tail below sees the FINAL attempt of every problem only
+    ctx.lc_tail_dev(lp, B, o.T.data_ptr(), o.n.data_ptr(), o.status.data_ptr(), o.records.data_ptr(), o.acc_idx.data_ptr(), o.acc_n.data_ptr(),
+                    T_ref_ptr=g["T_ref"].data_ptr(), enable_ptr=g["enable"].data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
+                    FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr())
+    ctx.sync()
+    per_pair = (time.time() - t0) / B
+    res = o.result(status, sm_params.dim)
+
+    # ---- the records and the accepted list split by todo_off, per block with block-local indices ----
+    out = {}
+    acc = np.asarray(res.accepted, dtype=np.int64)
+    for b in range(nb):
+        lo, hi = int(todo_off[b]), int(todo_off[b + 1])
+        part = LoopClosureResult(res.assoc[lo:hi], res.T[lo:hi], res.status[lo:hi], res.stats[lo:hi], res.records[lo:hi],
+                                 acc[(acc >= lo) & (acc < hi)] - lo)
+        edges = _records_into_results(Ms[b], part, local[b][:, 0], local[b][:, 1], nearby[b]) if hi > lo else Ms[b].empty_edges()
+        out[blocks[b]] = result_of(b, Ms[b], [per_pair] * (hi - lo), edges)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------

@@ -7449,6 +7449,41 @@ __global__ void __launch_bounds__(256) k_grid_norms(int S0, int S1, int d, const
     if (lane == 0) norm[w] = sqrt(s);
 }
 
+// One pair of pass 1 — what k_grid_gate and k_session_gate do once the descriptors' dot product is known: submap i of side a against
+// submap j of side b (indices into the sides' arrays), `gt`: the distance is between the ground-truth centres, `np_`: the product of the
+// two descriptor norms (read with d > 0 only), `p`: the pair's place in the dense outputs.
+template <bool SIM_IN, bool AABB>
+__device__ __forceinline__ void grid_pair(const roman_grid_gate_params_t& P, const GridSide& a, const GridSide& b, int64_t i, int64_t j, bool gt, int d,
+                                          double dot, double np_, int64_t p, const GridOut& out)
+{
+    const double* pa = (gt ? a.pos_gt : a.pos) + 3 * i;
+    const double* pb = (gt ? b.pos_gt : b.pos) + 3 * j;
+    const double dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
+    const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
+    bool nearby;
+    if (AABB) {                                                  // <= and >= as they stand: touching boxes intersect [REF roman/utils.py:167-169]
+        const double* A = a.box + 6 * i;
+        const double* Bx = b.box + 6 * j;
+        nearby = A[0] <= Bx[3] && A[3] >= Bx[0] && A[1] <= Bx[4] && A[4] >= Bx[1] && A[2] <= Bx[5] && A[5] >= Bx[2];
+    } else nearby = dist < 2.0 * P.radius;
+    double Ti[16], T[16];
+    lc_inv_affine(a.T_w + 16 * i, Ti);
+    lc_mul4(Ti, b.T_w + 16 * j, T);
+    const double yaw = nearby ? fabs(atan2(T[4], T[0]) * (180.0 / 3.141592653589793)) : d_nan();    // |np.rad2deg(yaw)|
+    double sim = INFINITY;
+    if (SIM_IN) sim = out.sim[p];
+    else if (d > 0) sim = (np_ <= 1e-9) ? 0.0 : dot / np_;       // np.isclose(norm_prod, 0, atol=1e-9, rtol=0) [REF roman/map/map.py:151-153]
+    const bool skip = dist > P.skip_distance;                    // [REF :136]
+    const bool gated = !skip && sim < P.desc_thresh;
+    const bool todo = !skip && !gated;
+    out.dist[p] = dist; out.yaw_deg[p] = yaw;
+    if (!SIM_IN) out.sim[p] = sim;
+    out.flags[p] = (nearby ? GRID_NEARBY : 0) | (skip ? GRID_SKIP : 0) | (gated ? GRID_GATED : 0) | (todo ? GRID_TODO : 0);
+    double* To = out.T_ij + 16 * p;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) To[t] = T[t];
+}
+
 // SIM_IN (roman_grid_gate_sim*): the similarity of every pair is already in out.sim — read, never written — and no descriptor is touched
 // AABB (roman_grid_gate_aabb*): NEARBY from a.box[i] and b.box[j] (float64[6]: min x y z, max x y z), P.radius is not read
 template <bool SIM_IN, bool AABB>
@@ -7482,37 +7517,8 @@ __global__ void __launch_bounds__(256) k_grid_gate(roman_grid_gate_params_t P, i
     double dot = acc[0];
 #pragma unroll
     for (int t = 1; t < GRID_TJ; ++t) dot = (lane == t) ? acc[t] : dot;
-    const int64_t p = (int64_t)i * S1 + j;
-    const bool gt = a.pos_gt != nullptr && b.pos_gt != nullptr;  // [REF :96-99]
-    const double* pa = (gt ? a.pos_gt : a.pos) + 3 * (int64_t)i;
-    const double* pb = (gt ? b.pos_gt : b.pos) + 3 * (int64_t)j;
-    const double dx = pa[0] - pb[0], dy = pa[1] - pb[1], dz = pa[2] - pb[2];
-    const double dist = sqrt((dx * dx + dy * dy) + dz * dz);
-    bool nearby;
-    if (AABB) {                                                  // <= and >= as they stand: touching boxes intersect [REF roman/utils.py:167-169]
-        const double* A = a.box + 6 * (int64_t)i;
-        const double* Bx = b.box + 6 * (int64_t)j;
-        nearby = A[0] <= Bx[3] && A[3] >= Bx[0] && A[1] <= Bx[4] && A[4] >= Bx[1] && A[2] <= Bx[5] && A[5] >= Bx[2];
-    } else nearby = dist < 2.0 * P.radius;
-    double Ti[16], T[16];
-    lc_inv_affine(a.T_w + 16 * (int64_t)i, Ti);
-    lc_mul4(Ti, b.T_w + 16 * (int64_t)j, T);
-    const double yaw = nearby ? fabs(atan2(T[4], T[0]) * (180.0 / 3.141592653589793)) : d_nan();    // |np.rad2deg(yaw)|
-    double sim = INFINITY;
-    if (SIM_IN) sim = out.sim[p];
-    else if (d > 0) {
-        const double np_ = norm[i] * norm[S0 + j];
-        sim = (np_ <= 1e-9) ? 0.0 : dot / np_;                   // np.isclose(norm_prod, 0, atol=1e-9, rtol=0) [REF roman/map/map.py:151-153]
-    }
-    const bool skip = dist > P.skip_distance;                    // [REF :136]
-    const bool gated = !skip && sim < P.desc_thresh;
-    const bool todo = !skip && !gated;
-    out.dist[p] = dist; out.yaw_deg[p] = yaw;
-    if (!SIM_IN) out.sim[p] = sim;
-    out.flags[p] = (nearby ? GRID_NEARBY : 0) | (skip ? GRID_SKIP : 0) | (gated ? GRID_GATED : 0) | (todo ? GRID_TODO : 0);
-    double* To = out.T_ij + 16 * p;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) To[t] = T[t];
+    const double np_ = (!SIM_IN && d > 0) ? norm[i] * norm[S0 + j] : 0.0;
+    grid_pair<SIM_IN, AABB>(P, a, b, i, j, a.pos_gt != nullptr && b.pos_gt != nullptr /* [REF :96-99] */, d, dot, np_, (int64_t)i * S1 + j, out);
 }
 
 __global__ void __launch_bounds__(1024) k_grid_compact(int B, int S1, const int32_t* __restrict__ flags, int32_t* __restrict__ pairs, int32_t* __restrict__ n_todo)
@@ -7541,6 +7547,160 @@ __global__ void __launch_bounds__(256) k_grid_fill(roman_grid_gate_params_t P, i
     const int i = pairs[2 * s], j = pairs[2 * s + 1];
     T_ref[16 * s + e] = T_ij[16 * ((int64_t)i * S1 + j) + e];
     if (e == 0) enable[s] = (P.single_robot_lc && fabs(time0[i] - time1[j]) < P.lc_time_thresh) ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// pass 1 of a whole multi-robot session (roman_session_gate*): the grids of a LIST of robot pairs ("blocks") over
+// ONE set of per-submap arrays — robot r owns the global submaps [sub_off[r], sub_off[r + 1]) —, in one launch sequence.  Block b is
+// (r0, r1, self_lc, 0); its n0 x n1 grid lies row-major at pair_off[b] of the dense outputs, its tiles at tile_off[b].
+//   k_grid_norms      over all S submaps (S1 = 0);
+//   k_session_gate    k_grid_gate's wave — (block, row i, GRID_TJ consecutive columns), the block by a wave-uniform binary search of
+//                     tile_off —, the same lane layout of the dot product and the same per-pair body (grid_pair): a block's dense
+//                     values are bit for bit what k_grid_gate writes for its two sides;
+//   k_session_count   the TODO flags of 1024 consecutive pairs: ballot + popcount per wave, the 16 wave counts added in LDS;
+//   k_session_scan    one workgroup: the exclusive scan of the workgroup counts, 1024 at a time (block_excl_scan with a carry), and
+//                     todo_off of the blocks that start at the end of the flags (trailing empty blocks, and todo_off[nb]: the total);
+//   k_session_scatter recounts its 1024 flags, adds the scanned base and writes (gi, gj) of every TODO pair at its rank; the thread
+//                     of a block's FIRST flag writes that block's todo_off (and that of the empty blocks in front of it);
+//   k_session_fill    k_grid_fill with global indices: the block of a compact slot by binary search of todo_off, T_ref from the
+//                     block's dense T_ij, enable = 0 only where the block's self_lc is set and the two times are close.
+// No atomics, no spin-waits, no cooperative launch: the order of every sum is fixed, two runs agree bit for bit.
+// ---------------------------------------------------------------------------------------------
+constexpr int SESSION_SCAN = 1024;                               // flags per workgroup of the compaction
+
+struct SessionTab { int nb; const int32_t* sub_off; const int32_t* blocks; const int64_t* pair_off; const int64_t* tile_off; const int32_t* has_gt; };
+
+// the last k in [0, n) with off[k] <= x (off ascending, off[0] <= x): the block that holds x — of several that start at the same place,
+// the last one, the only one that is not empty
+__device__ __forceinline__ int session_find(const int64_t* __restrict__ off, int n, int64_t x)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= x) lo = mid; else hi = mid; }
+    return lo;
+}
+
+__device__ __forceinline__ int session_find(const int32_t* __restrict__ off, int n, int64_t x)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= x) lo = mid; else hi = mid; }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) k_session_gate(roman_grid_gate_params_t P, SessionTab tab, int64_t tiles, GridSide s,
+                                                      const double* __restrict__ norm, GridOut out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (w >= tiles) return;                                      // (wave-uniform, as everything up to the lanes' pairs)
+    const int b = session_find(tab.tile_off, tab.nb, w);
+    const int r0 = tab.blocks[4 * b], r1 = tab.blocks[4 * b + 1];
+    const int base0 = tab.sub_off[r0], base1 = tab.sub_off[r1], n1 = tab.sub_off[r1 + 1] - base1;
+    const int nT = (n1 + GRID_TJ - 1) / GRID_TJ;
+    const int64_t lw = w - tab.tile_off[b];
+    const int i = (int)(lw / nT), j0 = (int)(lw % nT) * GRID_TJ;
+    const int d = P.desc_dim;
+    double acc[GRID_TJ];
+#pragma unroll
+    for (int t = 0; t < GRID_TJ; ++t) acc[t] = 0.0;
+    if (d > 0) {
+        const double* va = s.desc + (int64_t)(base0 + i) * d;
+        const double* vb[GRID_TJ];
+#pragma unroll
+        for (int t = 0; t < GRID_TJ; ++t) vb[t] = s.desc + (int64_t)(base1 + min(j0 + t, n1 - 1)) * d;    // (a tile's tail repeats the block's last row)
+        for (int k = lane; k < d; k += 64) {
+            const double x = va[k];
+#pragma unroll
+            for (int t = 0; t < GRID_TJ; ++t) acc[t] += x * vb[t][k];
+        }
+#pragma unroll
+        for (int t = 0; t < GRID_TJ; ++t) acc[t] = wave_sum_all(acc[t]);
+    }
+    const int j = j0 + lane;
+    if (lane >= GRID_TJ || j >= n1) return;
+    double dot = acc[0];
+#pragma unroll
+    for (int t = 1; t < GRID_TJ; ++t) dot = (lane == t) ? acc[t] : dot;
+    const int64_t gi = base0 + i, gj = base1 + j;
+    const bool gt = s.pos_gt != nullptr && tab.has_gt[r0] != 0 && tab.has_gt[r1] != 0;      // [REF :96-99]
+    const double np_ = d > 0 ? norm[gi] * norm[gj] : 0.0;
+    grid_pair<false, false>(P, s, s, gi, gj, gt, d, dot, np_, tab.pair_off[b] + (int64_t)i * n1 + j, out);
+}
+
+// the TODO flags of this workgroup's SESSION_SCAN pairs: -> (is flag g TODO, TODO flags of the workgroup in front of g, their number in the workgroup)
+__device__ __forceinline__ void session_rank(const int32_t* __restrict__ flags, int64_t total, int64_t g, int* sh, bool& mine, int& rank, int& count)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    mine = g < total && (flags[g] & GRID_TODO) != 0;
+    const unsigned long long m = __ballot(mine);
+    if (lane == 0) sh[w] = __popcll(m);
+    __syncthreads();
+    int base = 0, tot = 0;
+    for (int k = 0; k < SESSION_SCAN / 64; ++k) { const int x = sh[k]; if (k < w) base += x; tot += x; }
+    rank = base + __popcll(m & ((1ull << lane) - 1ull));
+    count = tot;
+}
+
+__global__ void __launch_bounds__(SESSION_SCAN) k_session_count(int64_t total, const int32_t* __restrict__ flags, int32_t* __restrict__ counts)
+{
+    __shared__ int sh[SESSION_SCAN / 64];
+    bool mine; int rank, count;
+    session_rank(flags, total, (int64_t)blockIdx.x * SESSION_SCAN + threadIdx.x, sh, mine, rank, count);
+    if (threadIdx.x == 0) counts[blockIdx.x] = count;
+}
+
+// counts[k] <- the TODO flags in front of workgroup k (in place); todo_off[b] <- the total for every b whose block starts at `total`
+__global__ void __launch_bounds__(SESSION_SCAN) k_session_scan(int nwg, int32_t* __restrict__ counts, SessionTab tab, int64_t total, int32_t* __restrict__ todo_off)
+{
+    __shared__ int shi[17];
+    int carry = 0;
+    for (int k0 = 0; k0 < nwg; k0 += SESSION_SCAN) {             // (uniform trip count: block_excl_scan has barriers)
+        const int k = k0 + (int)threadIdx.x;
+        const int v = k < nwg ? counts[k] : 0;
+        int tot;
+        const int ex = block_excl_scan(v, shi, tot);
+        if (k < nwg) counts[k] = carry + ex;
+        carry += tot;
+    }
+    for (int b = threadIdx.x; b <= tab.nb; b += SESSION_SCAN)
+        if (tab.pair_off[b] == total) todo_off[b] = carry;
+}
+
+__global__ void __launch_bounds__(SESSION_SCAN) k_session_scatter(int64_t total, const int32_t* __restrict__ flags, const int32_t* __restrict__ bases,
+                                                                  SessionTab tab, int32_t* __restrict__ pairs, int32_t* __restrict__ todo_off)
+{
+    __shared__ int sh[SESSION_SCAN / 64];
+    const int64_t g = (int64_t)blockIdx.x * SESSION_SCAN + threadIdx.x;
+    bool mine; int rank, count;
+    session_rank(flags, total, g, sh, mine, rank, count);
+    if (g >= total) return;
+    const int pos = bases[blockIdx.x] + rank;
+    const int b = session_find(tab.pair_off, tab.nb, g);        // (g < total: the block that holds g is not empty)
+    const int64_t first = tab.pair_off[b];
+    if (first == g)                                              // the block's first flag: its rank is the block's todo_off, and that of
+        for (int k = b; k >= 0 && tab.pair_off[k] == g; --k) todo_off[k] = pos;     // the empty blocks listed in front of it
+    if (!mine) return;
+    const int r0 = tab.blocks[4 * b], r1 = tab.blocks[4 * b + 1];
+    const int base1 = tab.sub_off[r1], n1 = tab.sub_off[r1 + 1] - base1;
+    const int64_t l = g - first;
+    pairs[2 * (int64_t)pos] = tab.sub_off[r0] + (int32_t)(l / n1);
+    pairs[2 * (int64_t)pos + 1] = base1 + (int32_t)(l % n1);
+}
+
+__global__ void __launch_bounds__(256) k_session_fill(roman_grid_gate_params_t P, SessionTab tab, const int32_t* __restrict__ todo_off,
+                                                      const int32_t* __restrict__ pairs, const double* __restrict__ T_ij, const double* __restrict__ time,
+                                                      double* __restrict__ T_ref, int32_t* __restrict__ enable)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t s = g >> 4;
+    const int e = (int)(g & 15);
+    if (s >= todo_off[tab.nb]) return;
+    const int b = session_find(todo_off, tab.nb, s);
+    const int r0 = tab.blocks[4 * b], r1 = tab.blocks[4 * b + 1];
+    const int base1 = tab.sub_off[r1], n1 = tab.sub_off[r1 + 1] - base1;
+    const int gi = pairs[2 * s], gj = pairs[2 * s + 1];
+    const int64_t p = tab.pair_off[b] + (int64_t)(gi - tab.sub_off[r0]) * n1 + (gj - base1);
+    T_ref[16 * s + e] = T_ij[16 * p + e];
+    if (e == 0) enable[s] = (tab.blocks[4 * b + 2] && fabs(time[gi] - time[gj]) < P.lc_time_thresh) ? 0 : 1;
 }
 
 // ---------------------------------------------------------------------------------------------

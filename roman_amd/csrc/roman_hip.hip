@@ -182,6 +182,9 @@ struct roman_ctx {
     // pass 1 of a grid (roman_grid_gate*): the descriptor norms of both sides
     DevBuf ggNorm;
 
+    // pass 1 of a session (roman_session_gate*): the TODO counts of the compaction's workgroups, scanned in place
+    DevBuf sgCount;
+
     // frame descriptors (roman_frame_select* / roman_stacked_sim*): the frame norms of both maps, one row band of the frame-cosine
     // matrix, and the column maxima R
     DevBuf ssNorm, ssBand, ssR;
@@ -1450,7 +1453,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     c->shareStage.release(); c->ransacStage.release();
     { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx}; for (DevBuf* b : sm) b->release(); }
     c->smStage.release();
-    c->ggNorm.release();
+    c->ggNorm.release(); c->sgCount.release();
     c->ssNorm.release(); c->ssBand.release(); c->ssR.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
@@ -3041,6 +3044,125 @@ int roman_grid_gate_aabb(roman_ctx_t* c, const roman_grid_gate_params_t* gparams
     return grid_gate_host(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, sim_in ? nullptr : desc0, pos1, pos_gt1, T_w1, time1, sim_in ? nullptr : desc1,
                           dist, flags, yaw_deg, sim_in ? const_cast<double*>(sim_in) /* uploaded, never written */ : sim, T_ij, pairs, T_ref, enable, n_todo,
                           sim_in != nullptr, true, box0, box1);
+}
+
+// --- pass 1 of a multi-robot session: the grids of a list of robot pairs in one launch sequence -------------------
+// The tables are checked on their HOST copies (no read-back): -> *total = pair_off[nb], *tiles = tile_off[nb], *S = sub_off[R].
+static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int32_t R, const int32_t* sub_off, const void* pos, const void* pos_gt,
+                              const void* has_gt, const void* T_w, const void* time, const void* desc, int32_t nb, const int32_t* blocks,
+                              const int64_t* pair_off, const int64_t* tile_off, const void* dist, const void* flags, const void* yaw_deg, const void* sim,
+                              const void* T_ij, const void* pairs, const void* T_ref, const void* enable, const void* todo_off,
+                              int64_t* total, int64_t* tiles, int32_t* S)
+{
+    if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
+    if (R < 0 || nb < 0) return fail(c, ROMAN_E_INVALID, "R < 0 or nb < 0");
+    if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
+        return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
+    if (P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
+    if (P->desc_dim < 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d is negative", P->desc_dim);
+    if (P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: the session gate serves the radius mode only (roman_grid_gate_aabb* per robot pair)", P->radius);
+    if (!sub_off || !pair_off || !tile_off || !todo_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / tile_off / todo_off is NULL");
+    if (sub_off[0] != 0) return fail(c, ROMAN_E_INVALID, "sub_off[0] must be 0");
+    for (int r = 0; r < R; ++r)
+        if (sub_off[r + 1] < sub_off[r]) return fail(c, ROMAN_E_INVALID, "sub_off decreases at robot %d", r);
+    bool self = false;
+    int64_t po = 0, to = 0;
+    std::vector<int64_t> seen;
+    seen.reserve((size_t)nb);
+    if (pair_off[0] != 0 || tile_off[0] != 0) return fail(c, ROMAN_E_INVALID, "pair_off[0] and tile_off[0] must be 0");
+    for (int b = 0; b < nb; ++b) {
+        const int32_t r0 = blocks[4 * b], r1 = blocks[4 * b + 1];
+        if (r0 < 0 || r0 >= R || r1 < 0 || r1 >= R) return fail(c, ROMAN_E_INVALID, "block %d names robot %d / %d outside [0, %d)", b, r0, r1, R);
+        if (blocks[4 * b + 3] != 0) return fail(c, ROMAN_E_INVALID, "block %d: the reserved word must be 0", b);
+        self = self || blocks[4 * b + 2] != 0;
+        seen.push_back((int64_t)r0 * R + r1);
+        const int64_t n0 = sub_off[r0 + 1] - sub_off[r0], n1 = sub_off[r1 + 1] - sub_off[r1];
+        po += n0 * n1; to += n0 * ((n1 + GRID_TJ - 1) / GRID_TJ);
+        if (po > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "the blocks hold more than %d pairs: beyond the index width", INT32_MAX / 16);
+        if (pair_off[b + 1] != po || tile_off[b + 1] != to) return fail(c, ROMAN_E_INVALID, "pair_off / tile_off disagree with sub_off and blocks at block %d", b);
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(c, ROMAN_E_INVALID, "a robot pair is listed twice");
+    *total = po; *tiles = to; *S = sub_off[R];
+    if (po == 0) return ROMAN_OK;
+    if (P->desc_dim > 0 && !desc) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
+    if (!pos || !T_w) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
+    if (pos_gt && !has_gt) return fail(c, ROMAN_E_INVALID, "has_gt is NULL with pos_gt");
+    if (self && !time) return fail(c, ROMAN_E_INVALID, "time is NULL with a self_lc block");
+    if (!dist || !flags || !yaw_deg || !sim || !T_ij || !pairs || !T_ref || !enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
+    return ROMAN_OK;
+}
+
+int roman_session_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
+                           const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                           int32_t nb, const int32_t* blocks, const int32_t* blocks_host,
+                           const int64_t* pair_off, const int64_t* pair_off_host, const int64_t* tile_off, const int64_t* tile_off_host,
+                           double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                           int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
+{
+    // (the arguments are judged first — on host memory only, a NULL context included: fail() then keeps the text for roman_last_error(NULL))
+    if (!sub_off || !pair_off || !tile_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "a table is NULL on the device");
+    int64_t total = 0, tiles = 0; int32_t S = 0;
+    int rc = session_gate_check(c, gparams, R, sub_off_host, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks_host, pair_off_host, tile_off_host,
+                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    if (total == 0) { HIPCHK(c, hipMemsetAsync(todo_off, 0, sizeof(int32_t) * (size_t)(nb + 1), stream)); return ROMAN_OK; }
+    const int d = gparams->desc_dim;
+    const int nwg = (int)((total + SESSION_SCAN - 1) / SESSION_SCAN);
+    HIPCHK(c, c->ggNorm.ensure(sizeof(double) * (size_t)S));                    // scratch first: a failure leaves nothing enqueued
+    HIPCHK(c, c->sgCount.ensure(sizeof(int32_t) * (size_t)nwg));
+    double* dNorm = c->ggNorm.as<double>();
+    int32_t* dCount = c->sgCount.as<int32_t>();
+    if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, stream, (int)S, 0, d, desc, (const double*)nullptr, dNorm);
+    const SessionTab tab{(int)nb, sub_off, blocks, pair_off, tile_off, has_gt};
+    const GridSide s{pos, pos_gt, T_w, time, desc, nullptr};
+    const GridOut out{dist, flags, yaw_deg, sim, T_ij};
+    hipLaunchKernelGGL(k_session_gate, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
+    hipLaunchKernelGGL(k_session_count, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, dCount);
+    hipLaunchKernelGGL(k_session_scan, dim3(1), dim3(SESSION_SCAN), 0, stream, nwg, dCount, tab, total, todo_off);
+    hipLaunchKernelGGL(k_session_scatter, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, (const int32_t*)dCount, tab, pairs, todo_off);
+    hipLaunchKernelGGL(k_session_fill, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, tab, (const int32_t*)todo_off,
+                       (const int32_t*)pairs, (const double*)T_ij, time, T_ref, enable);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_session_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                       const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                       int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                       double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                       int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
+{
+    int64_t total = 0, tiles = 0; int32_t S = 0;
+    int rc = session_gate_check(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks, pair_off, tile_off,
+                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (total == 0) { std::fill(todo_off, todo_off + nb + 1, 0); return ROMAN_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const size_t d = (size_t)gparams->desc_dim, B = (size_t)total, nS = (size_t)S;
+    HostMirror m(c);
+    const auto dSub = m.in(sub_off, 4 * ((size_t)R + 1)), dBlk = m.in(blocks, 16 * (size_t)nb);
+    const auto dPo = m.in(pair_off, 8 * ((size_t)nb + 1)), dTo = m.in(tile_off, 8 * ((size_t)nb + 1));
+    const auto dPos = m.in(pos, 24 * nS), dGt = m.in(pos_gt, pos_gt ? 24 * nS : 0);
+    const auto dHas = m.in(has_gt, pos_gt ? 4 * (size_t)R : 0);
+    const auto dTw = m.in(T_w, 128 * nS), dTime = m.in(time, time ? 8 * nS : 0), dDesc = m.in(desc, 8 * d * nS);
+    const auto dDist = m.out(dist, 8 * B), dYaw = m.out(yaw_deg, 8 * B), dSim = m.out(sim, 8 * B), dTij = m.out(T_ij, 128 * B);
+    const auto dFlags = m.out(flags, 4 * B);
+    // the compact outputs are inout: the slots beyond todo_off[nb] come back as they were
+    const auto dTref = m.inout(T_ref, 128 * B);
+    const auto dPairs = m.inout(pairs, 8 * B), dEn = m.inout(enable, 4 * B), dOff = m.out(todo_off, 4 * ((size_t)nb + 1));
+    rc = m.upload();
+    if (rc) return rc;
+    rc = roman_session_gate_dev(c, gparams, R, dSub.dev(), sub_off, dPos.dev(), dGt.dev(), dHas.dev(), dTw.dev(), dTime.dev(), dDesc.dev(),
+                                nb, dBlk.dev(), blocks, dPo.dev(), pair_off, dTo.dev(), tile_off,
+                                dDist.dev(), dFlags.dev(), dYaw.dev(), dSim.dev(), dTij.dev(), dPairs.dev(), dTref.dev(), dEn.dev(), dOff.dev());
+    if (rc) return rc;
+    return m.download();
 }
 
 // --- frame descriptors of the submaps of a pool ([REF roman/map/map.py:210-242], [REF :155-162]) ------------------

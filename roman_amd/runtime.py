@@ -161,6 +161,41 @@ class GridGateResult:
 
 
 @dataclass
+class SessionGateResult:
+    """Results of one roman_session_gate call over the blocks of a session: block b's dense values lie row-major at pair_off[b]."""
+    dist: np.ndarray       # (total,) float64
+    flags: np.ndarray      # (total,) int32 ROMAN_GRID_* bits
+    yaw_deg: np.ndarray    # (total,) float64, NaN where the pair is not nearby
+    sim: np.ndarray        # (total,) float64 (+inf without descriptors)
+    T_ij: np.ndarray       # (total, 4, 4) float64
+    pairs: np.ndarray      # (total, 2) int32: the first todo_off[-1] rows are the TODO pairs as GLOBAL submap indices; the others as handed in
+    T_ref: np.ndarray      # (total, 4, 4) float64, likewise
+    enable: np.ndarray     # (total,) int32, likewise
+    todo_off: np.ndarray   # (nb + 1,) int32: block b's TODO pairs are the compact slots [todo_off[b], todo_off[b + 1])
+    pair_off: np.ndarray   # (nb + 1,) int64
+
+    def block(self, b, n0, n1):
+        """The dense outputs of block b as (n0, n1) matrices -> dict(dist, flags, yaw_deg, sim, T_ij)."""
+        lo, hi = int(self.pair_off[b]), int(self.pair_off[b + 1])
+        return dict(dist=self.dist[lo:hi].reshape(n0, n1), flags=self.flags[lo:hi].reshape(n0, n1), yaw_deg=self.yaw_deg[lo:hi].reshape(n0, n1),
+                    sim=self.sim[lo:hi].reshape(n0, n1), T_ij=self.T_ij[lo:hi].reshape(n0, n1, 4, 4))
+
+
+def session_tables(counts, blocks):
+    """The small tables of roman_session_gate from the robots' submap counts and the block list [(r0, r1, self_lc), ...] ->
+    (sub_off int32 (R + 1,), blocks int32 (nb, 4), pair_off int64 (nb + 1,), tile_off int64 (nb + 1,))."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    sub_off = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    blk = np.zeros((len(blocks), 4), dtype=np.int32)
+    for b, (r0, r1, self_lc) in enumerate(blocks):
+        blk[b, :3] = (int(r0), int(r1), int(bool(self_lc)))
+    n0, n1 = counts[blk[:, 0]], counts[blk[:, 1]]
+    pair_off = np.concatenate([[0], np.cumsum(n0 * n1)]).astype(np.int64)
+    tile_off = np.concatenate([[0], np.cumsum(n0 * ((n1 + _abi.GRID_TJ - 1) // _abi.GRID_TJ))]).astype(np.int64)
+    return sub_off, blk, pair_off, tile_off
+
+
+@dataclass
 class FrameSelectResult:
     """Results of one roman_frame_select call over the S submaps of a pool and the Nf frames of its map."""
     mask: np.ndarray       # (S, ceil(Nf / 64)) uint64: bit f % 64 of word f / 64
@@ -639,6 +674,58 @@ class Context:
         self._grid_gate_dev("roman_grid_gate_sim_dev", gparams, S0, S1, pos0_ptr, pos_gt0_ptr, T_w0_ptr, time0_ptr,
                             pos1_ptr, pos_gt1_ptr, T_w1_ptr, time1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
                             pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr)
+
+    # ------------------------------------------------------------------ pass 1 of every robot pair of a session
+    def session_gate(self, gparams, sub_off, blocks, pair_off, tile_off, pos, T_w, time=None, desc=None, pos_gt=None, has_gt=None,
+                     pairs=None, T_ref=None, enable=None):
+        """Host-pointer pass 1 over a list of robot pairs (roman_session_gate): the tables as session_tables() gives them (they are
+        passed as they are: the library checks them); pos (S, 3), T_w (S, 4, 4), time (S,), desc (S, desc_dim), pos_gt (S, 3) with
+        has_gt (R,) over ALL submaps of the session.  gparams.single_robot_lc is not read: a block's own self_lc is.  The compact
+        outputs may be handed in, as grid_gate() takes them.  -> SessionGateResult."""
+        sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
+        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
+        R, nb = len(sub_off) - 1, len(blocks)
+        if R < 0 or len(pair_off) != nb + 1 or len(tile_off) != nb + 1:
+            raise ValueError("sub_off must hold R + 1 entries, pair_off and tile_off nb + 1")
+        pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
+        T_w = _f64(T_w).reshape(-1, 16)
+        time = None if time is None else _f64(time).reshape(-1)
+        desc = None if desc is None else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
+        pos_gt = None if pos_gt is None else _f64(pos_gt).reshape(-1, 3)
+        has_gt = None if has_gt is None else np.ascontiguousarray(has_gt, dtype=np.int32).reshape(-1)
+        if T_w.shape[0] != S or (time is not None and time.shape[0] != S) or (pos_gt is not None and pos_gt.shape[0] != S) or \
+                (has_gt is not None and has_gt.shape[0] != R) or int(sub_off[-1]) != S:
+            raise ValueError("the per-submap arrays must hold one entry per submap of the session (sub_off[R]), has_gt one per robot")
+        if desc is not None and gparams.desc_dim > 0 and desc.shape[1] != gparams.desc_dim:
+            raise ValueError("desc must be (S, desc_dim)")
+        B = max(int(pair_off[-1]), 0)
+        pairs = _given(pairs, (B, 2), np.int32, -1); T_ref = _given(T_ref, (B, 4, 4), np.float64, np.nan); enable = _given(enable, (B,), np.int32, -1)
+        dist = np.zeros(B); flags = np.zeros(B, dtype=np.int32); yaw = np.zeros(B); sim = np.zeros(B); T_ij = np.zeros((B, 4, 4))
+        todo_off = np.zeros(nb + 1, dtype=np.int32)
+        self._generation += 1
+        rc = self._lib.roman_session_gate(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
+                                          _ptr(desc), nb, _ptr(blocks), _ptr(pair_off), _ptr(tile_off), _ptr(dist), _ptr(flags), _ptr(yaw), _ptr(sim),
+                                          _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off))
+        self._check(rc, "roman_session_gate")
+        return SessionGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, todo_off, pair_off)
+
+    def session_gate_dev(self, gparams, sub_off, blocks, pair_off, tile_off, sub_off_ptr, blocks_ptr, pair_off_ptr, tile_off_ptr, pos_ptr, T_w_ptr,
+                         dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr, pairs_ptr, T_ref_ptr, enable_ptr, todo_off_ptr,
+                         time_ptr=None, desc_ptr=None, pos_gt_ptr=None, has_gt_ptr=None):
+        """Device-pointer pass 1 over a list of robot pairs (roman_session_gate_dev): the tables as host arrays (session_tables();
+        the library validates these) AND as device addresses of the same values; every other pointer a device address.  A pure
+        enqueue on the context's stream; complete after sync().  pairs_ptr holds GLOBAL submap indices: with frames tabled over
+        all submaps of the session, its two columns are lc_tail_dev's iL and iR."""
+        sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
+        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
+        R, nb = len(sub_off) - 1, len(blocks)
+        if R < 0 or len(pair_off) != nb + 1 or len(tile_off) != nb + 1:
+            raise ValueError("sub_off must hold R + 1 entries, pair_off and tile_off nb + 1")
+        rc = self._lib.roman_session_gate_dev(self._h, C.byref(gparams), R, _vp(sub_off_ptr), _ptr(sub_off), _vp(pos_ptr), _vp(pos_gt_ptr), _vp(has_gt_ptr),
+                                              _vp(T_w_ptr), _vp(time_ptr), _vp(desc_ptr), nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off),
+                                              _vp(tile_off_ptr), _ptr(tile_off), _vp(dist_ptr), _vp(flags_ptr), _vp(yaw_deg_ptr), _vp(sim_ptr), _vp(T_ij_ptr),
+                                              _vp(pairs_ptr), _vp(T_ref_ptr), _vp(enable_ptr), _vp(todo_off_ptr))
+        self._check(rc, "roman_session_gate_dev")
 
     # ------------------------------------------------------------------ force-fill submaps, boxes, the bounding-box gate (DESIGN.md §4.12)
     def submaps_fill(self, point_dim, cap, seg_feats, descs, count, src, seg_ids=None, desc_dim=0, want_pool=True):
