@@ -3683,7 +3683,10 @@ __device__ __forceinline__ double col3(const double (&A)[9], int r3, int c) { re
 
 // Rotation of the Kabsch / Umeyama fit from the d x d cross-covariance H (d = 2 or 3; rows and columns >= d of H are ignored):
 // one-sided Jacobi SVD of H, the two leading singular pairs, the third by cross products (a proper rotation whatever the rank).
-__device__ __forceinline__ void kabsch_rotation(const double (&H)[9], int d, double (&R)[9])
+// `thin` (optional, 8 doubles): where the 3-D fit found rank H <= 1 and completed u1 arbitrarily, thin[0] = 1, thin[1..6] = u1, v1
+// and thin[7] = s1
+// — a caller that still has the points can then settle the turn about the line (wave_pose).
+__device__ __forceinline__ void kabsch_rotation(const double (&H)[9], int d, double (&R)[9], double* thin = nullptr)
 {
     double G[9], V[9];
 #pragma unroll
@@ -3734,6 +3737,12 @@ __device__ __forceinline__ void kabsch_rotation(const double (&H)[9], int d, dou
 #pragma unroll
         for (int r = 0; r < 3; ++r) u2[r] = col3(G, r * 3, i2) / s2;
     } else {                                                            // rank <= 1: complete u1 arbitrarily
+        if (thin != nullptr && s1 > 0.0) {
+            thin[0] = 1.0;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) { thin[1 + r] = u1[r]; thin[4 + r] = v1[r]; }
+            thin[7] = s1;
+        }
         int m = 0;
         if (fabs(u1[1]) < fabs(u1[0])) m = 1;
         if (fabs(u1[2]) < fabs(m == 0 ? u1[0] : u1[1])) m = 2;
@@ -3754,10 +3763,8 @@ __device__ __forceinline__ void kabsch_rotation(const double (&H)[9], int d, dou
 }
 
 // T (row-major (d+1)x(d+1) in the leading entries of 16 doubles) from centred sums.
-__device__ __forceinline__ void write_pose(double (&T)[16], int d, const double (&H)[9], const double (&m1)[3], const double (&m2)[3])
+__device__ __forceinline__ void store_pose(double (&T)[16], int d, const double (&R)[9], const double (&m1)[3], const double (&m2)[3])
 {
-    double R[9];
-    kabsch_rotation(H, d, R);
 #pragma unroll
     for (int t = 0; t < 16; ++t) T[t] = 0.0;
     if (d == 3) {
@@ -3779,6 +3786,59 @@ __device__ __forceinline__ void write_pose(double (&T)[16], int d, const double 
         }
         T[8] = 1.0;
     }
+}
+__device__ __forceinline__ void write_pose(double (&T)[16], int d, const double (&H)[9], const double (&m1)[3], const double (&m2)[3],
+                                           double* thin = nullptr)
+{
+    double R[9];
+    kabsch_rotation(H, d, R, thin);
+    store_pose(T, d, R, m1, m2);
+}
+
+// The turn about the line of a rank-1 fit.  H2 is the cross-covariance of the points with their u1 / v1 components taken out (a
+// needle's cross-section: far below the rounding of H itself, s2 / s1 < 2^-53, yet held by the coordinates).  Its leading singular
+// pair, made orthogonal to (u1, v1), replaces the arbitrary completion.  False — the completion stays — where that pair is no
+// more than rounding: H2 of points on one line is noise of about 2^-104 s1 (the squared rounding of the deflated coordinates; 0.2 to
+// 0.9 of it measured for lines inside +-15 of the origin), a needle of cross-section 1e-9 gives 1e13 times that; the line is drawn
+// at 2^-90 s1.  (Far from the origin the centroids' rounding alone is (c / r)^2 larger and can pass the line: the turn is then set by
+// that noise — as proper and as optimal as the completion.)
+__device__ __forceinline__ bool thin_rotation(const double* thin, const double (&H2)[9], double (&R)[9])
+{
+    double G[9], V[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) { G[e] = H2[e]; V[e] = (e % 4 == 0) ? 1.0 : 0.0; }
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool moved = false;
+        jacobi_pair<0, 1>(G, V, moved);
+        jacobi_pair<0, 2>(G, V, moved);
+        jacobi_pair<1, 2>(G, V, moved);
+        if (!moved) break;
+    }
+    double sg[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sg[c] = sqrt(G[c] * G[c] + G[3 + c] * G[3 + c] + G[6 + c] * G[6 + c]);
+    int j = 0;
+    if (sg[1] > sg[0]) j = 1;
+    if (sg[2] > (j == 0 ? sg[0] : sg[1])) j = 2;
+    const double s = j == 0 ? sg[0] : (j == 1 ? sg[1] : sg[2]);
+    if (!(s > 0x1p-90 * thin[7])) return false;
+    const double u1[3] = {thin[1], thin[2], thin[3]}, v1[3] = {thin[4], thin[5], thin[6]};
+    double u2[3], v2[3], du = 0.0, dv = 0.0, nu = 0.0, nv = 0.0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { u2[r] = col3(G, r * 3, j) / s; v2[r] = col3(V, r * 3, j); du += u1[r] * u2[r]; dv += v1[r] * v2[r]; }
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { u2[r] -= du * u1[r]; v2[r] -= dv * v1[r]; nu += u2[r] * u2[r]; nv += v2[r] * v2[r]; }
+    if (!(nu > 0.25 && nv > 0.25)) return false;                       // (rounding noise along u1 / v1: no direction of its own)
+    nu = sqrt(nu); nv = sqrt(nv);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { u2[r] /= nu; v2[r] /= nv; }
+    const double u3[3] = {u1[1] * u2[2] - u1[2] * u2[1], u1[2] * u2[0] - u1[0] * u2[2], u1[0] * u2[1] - u1[1] * u2[0]};
+    const double v3[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) R[r * 3 + c] = u1[r] * v1[c] + u2[r] * v2[c] + u3[r] * v3[c];
+    return true;
 }
 
 // Centred cross-covariance of the nsel selected correspondences and the pose, by ONE wave (all 64 lanes active): nsel is tens to a
@@ -3829,7 +3889,35 @@ __device__ __forceinline__ void wave_pose(double (&T)[16], int dim, int nsel, in
     }
 #pragma unroll
     for (int e = 0; e < 9; ++e) H[e] = readlane63(wave_sum63(H[e]));
-    write_pose(T, dim, H, m1, m2);
+    double thin[8];
+    thin[0] = 0.0;
+    write_pose(T, dim, H, m1, m2, thin);
+    if (dim == 3 && thin[0] != 0.0) {                           // rank H <= 1 (the same H in every lane: a uniform branch): a third sweep
+        double H2[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        auto add2 = [&](const double (&a)[3], const double (&q)[3]) {  // (a, q: centred)
+            const double pa = a[0] * thin[1] + a[1] * thin[2] + a[2] * thin[3], pq = q[0] * thin[4] + q[1] * thin[5] + q[2] * thin[6];
+            double a2[3], q2[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { a2[c] = a[c] - pa * thin[1 + c]; q2[c] = q[c] - pq * thin[4 + c]; }
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) H2[r * 3 + c] += a2[r] * q2[c];
+        };
+#pragma unroll
+        for (int x = 0; x < KEEP; ++x) if (lane + 64 * x < nsel) add2(ka[x], kq[x]);   // (kept pairs were centred in place)
+        for (int t = lane + 64 * KEEP; t < nsel; t += 64) {
+            double a[3], q[3];
+            fetch(t, a, q);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { a[c] -= m1[c]; q[c] -= m2[c]; }
+            add2(a, q);
+        }
+#pragma unroll
+        for (int e = 0; e < 9; ++e) H2[e] = readlane63(wave_sum63(H2[e]));
+        double R[9];
+        if (thin_rotation(thin, H2, R)) store_pose(T, dim, R, m1, m2);
+    }
 }
 
 // Exact emulation of findIndicesOfkLargest (min-heap on (value,index); strict '<' replacement)
