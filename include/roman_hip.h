@@ -1093,6 +1093,72 @@ ROMAN_API int roman_session_gate(roman_ctx_t* ctx, const roman_grid_gate_params_
                                  double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
                                  int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off);
 
+/*
+ * roman_session_gate_sim_dev: roman_session_gate_dev over a similarity that is ALREADY computed — what
+ * roman_grid_gate_sim_dev is to roman_grid_gate_dev.  The arguments are roman_session_gate_dev's plus a trailing
+ *   sim_in     float64[pair_off[nb]], DEVICE: block b's similarities row-major at pair_off[b] (roman_session_stacked_sim_dev writes them so)
+ * gparams->desc_dim must be 0 (else ROMAN_E_INVALID): desc_thresh gates sim_in, GATED = not skipped and sim_in < desc_thresh, so a
+ * similarity equal to the threshold passes and -inf is gated.  `desc` is not read and `sim` is not written; both may be NULL.
+ * Every other output, per block, is bit for bit what roman_grid_gate_sim_dev writes when given that block's slice of sim_in.
+ * Errors: roman_session_gate_dev's, and sim_in NULL while a pair exists -> ROMAN_E_INVALID.
+ */
+ROMAN_API int roman_session_gate_sim_dev(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
+                                         const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                         int32_t nb, const int32_t* blocks, const int32_t* blocks_host,
+                                         const int64_t* pair_off, const int64_t* pair_off_host, const int64_t* tile_off, const int64_t* tile_off_host,
+                                         double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                         int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* sim_in);
+
+/* The same with HOST pointers everywhere (each table once).  Synchronous; sim_in goes up and is not brought back. */
+ROMAN_API int roman_session_gate_sim(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                                     const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                     int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                                     double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                     int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* sim_in);
+
+/*
+ * roman_session_stacked_sim_dev: roman_stacked_sim_dev for EVERY block of a session in one launch sequence, over
+ * ONE frame table.  Every bulk pointer DEVICE; a PURE ENQUEUE on the context's stream.  The small tables travel twice, as
+ * roman_session_gate_dev's do: on the device (the kernels read them) and as `_host` copies (validated without a read-back, in front
+ * of everything else: every refusal has its code even without a device).
+ *
+ *   d, Nf, desc        float64[Nf][d]: the frame descriptors of the whole session
+ *   mask               uint64 words: the frame masks of all views (roman_frame_select_dev's rows, gathered)
+ *   R, per view r      frame_lo[r], frame_n[r] (int32): the view's frames are the rows [frame_lo[r], frame_lo[r] + frame_n[r]) of desc;
+ *                      mask_off[r] (int64, in words): its masks are uint64[n_r][ceil(frame_n[r] / 64)] at mask + mask_off[r], bit t of a
+ *                      row = frame frame_lo[r] + t; n_r = sub_off[r+1] - sub_off[r].  These are ranges, not prefixes: two views of one
+ *                      robot may name the same frames and the same words — everything is read-only
+ *   sub_off, nb, blocks, pair_off   roman_session_gate_dev's tables; self_lc and the reserved word are validated as there, self_lc
+ *                      is not otherwise read
+ *   sim                float64[pair_off[nb]]: block b row-major at pair_off[b].  Slots outside [0, pair_off[nb]) are untouched
+ *
+ * Per block, sim is BIT FOR BIT what roman_stacked_sim_dev writes for the block's two sides: -inf for an empty mask or a view without
+ * frames, 0 where |a| |b| <= 1e-9.  The norms are computed once per frame of the session.  No floating-point atomics; two runs agree
+ * bit for bit; the result does not depend on roman_ctx_set_stacked_band or on the other blocks of the list.  The frame-cosine
+ * matrices go through the context's band workspace in ROUNDS of at most one row band per block, a round's bands together within
+ * 64 MiB (one band of 32 rows may exceed it; a band height set with roman_ctx_set_stacked_band caps every band).
+ * nb == 0 or no pair at all: ROMAN_OK, nothing written.  A failed workspace allocation: ROMAN_E_NOMEM, nothing enqueued, the
+ * context stays usable.
+ * Errors (ROMAN_E_INVALID): d < 1, Nf < 0, R < 0, nb < 0, a frame range outside [0, Nf], a negative mask_off, a NULL pointer that is
+ * needed, and everything roman_session_gate_dev refuses about sub_off, blocks and pair_off.
+ * ROMAN_E_TOO_LARGE, over the blocks with submaps and frames on both sides (n0 x n1 submaps, Nf0 x Nf1 frames):
+ *   pair_off[nb] * 16 beyond int32 (roman_session_gate_dev's bound);
+ *   sum of n0 * ceil(Nf1 / 256) beyond int32 (the workgroups of one round's column maxima);
+ *   sum of ceil(Nf0 / 32) * ceil(Nf1 / 32) beyond int32 (the tiles of one round, and the number of bands).
+ * Offsets into the frame table, the masks and the workspaces are 64-bit.
+ */
+ROMAN_API int roman_session_stacked_sim_dev(roman_ctx_t* ctx, int32_t d, int32_t Nf, const double* desc, const uint64_t* mask,
+                                            int32_t R, const int32_t* frame_lo, const int32_t* frame_lo_host, const int32_t* frame_n, const int32_t* frame_n_host,
+                                            const int64_t* mask_off, const int64_t* mask_off_host, const int32_t* sub_off, const int32_t* sub_off_host,
+                                            int32_t nb, const int32_t* blocks, const int32_t* blocks_host, const int64_t* pair_off, const int64_t* pair_off_host,
+                                            double* sim);
+
+/* The same with HOST pointers everywhere (each table once).  Synchronous.  mask_words: the words `mask` holds (the call copies them):
+   a view whose masks leave them -> ROMAN_E_INVALID. */
+ROMAN_API int roman_session_stacked_sim(roman_ctx_t* ctx, int32_t d, int32_t Nf, const double* desc, const uint64_t* mask, int64_t mask_words,
+                                        int32_t R, const int32_t* frame_lo, const int32_t* frame_n, const int64_t* mask_off, const int32_t* sub_off,
+                                        int32_t nb, const int32_t* blocks, const int64_t* pair_off, double* sim);
+
 /* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */
 /* ------------------------------------------------------------------------------------------- */

@@ -932,11 +932,17 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     (self blocks lose the segments both submaps hold through one roman_shared_reduce_dev over their problems); one
     issue_chunked, one join, one roman_lc_tail_dev with the frames tabled over all submaps of the session.
 
+    'stacked_frame_descriptors' (pools built with it): every live robot's frame descriptors go ONCE into the
+    session's frame table and the mask rows of its non-empty submaps once into one block of words, whatever number of views the
+    robot has; roman_session_stacked_sim_dev writes the similarity of every pair of every block and roman_session_gate_sim_dev
+    behind it, on the same stream, gates on it.  similarity_mat per block is what the device computed.
+
     Not covered — ValueError before any context is made; submap_align_pools per robot pair is the way: force_fill_submaps / no
-    submap_radius, 'stacked_frame_descriptors', a RansacReg, a plugin with a host prefilter, pools of different row width or
-    descriptor length, a self block over a pool without ids_dev, and whatever submap_align_pools refuses for a pool.  Two
-    refusals ask the context itself and so come after it exists, as in submap_align_pools: a context without
-    roman_session_gate_dev, and one without roman_shared_reduce_dev when the list holds a self block."""
+    submap_radius, a RansacReg, a plugin with a host prefilter, pools of different row width or descriptor length, pools not
+    built with the frame-descriptor mode asked for, a self block over a pool without ids_dev, and whatever submap_align_pools
+    refuses for a pool.  Three refusals ask the context itself and so come after it exists, as in submap_align_pools: a context
+    without roman_session_gate_dev, one without roman_session_stacked_sim_dev for stacked descriptors, and one without
+    roman_shared_reduce_dev when the list holds a self block."""
     import torch
     from ..runtime import session_tables
     from .pipeline import issue_chunked
@@ -956,18 +962,20 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     if sm_params.force_fill_submaps or sm_params.submap_radius is None:
         raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes" + way)
     mode = sm_params.submap_descriptor
-    if mode == 'stacked_frame_descriptors':
-        raise ValueError("'stacked_frame_descriptors' needs the similarity of roman_stacked_sim_dev per pair of maps" + way)
-    if mode not in (None, 'mean_semantic', 'mean_frame_descriptor'):
+    stacked = mode == 'stacked_frame_descriptors'
+    if mode not in (None, 'mean_semantic', 'mean_frame_descriptor', 'stacked_frame_descriptors'):
         raise ValueError(f"submap_descriptor {mode!r} is not one the pools carry" + way)
-    if mode == 'mean_frame_descriptor' and any(q.descriptor_mode != mode for q in p):
+    if mode in ('mean_frame_descriptor', 'stacked_frame_descriptors') and any(q.descriptor_mode != mode for q in p):
         raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool(frames=...) keeps the frame masks on the device)" + way)
     if _has_host_prefilter(registration):
         raise ValueError("the registration plugin prefilters association lists on the host" + way)
     if R and any(int(q.pool.shape[1]) != int(p[0].pool.shape[1]) for q in p):
         raise ValueError("the pools have different row widths" + way)
     d = 0
-    if mode is not None and R:
+    if stacked and R:                                        # (the gate reads a ready similarity: its desc_dim stays 0)
+        if any(int(q.frame_desc_dev.shape[1]) != int(p[0].frame_desc_dev.shape[1]) for q in p):
+            raise ValueError("the pools have frame descriptors of different lengths" + way)
+    elif mode is not None and R:
         if any(q.desc_dev is None for q in p):
             raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool keeps the descriptors on the device)" + way)
         d = int(p[0].desc_dev.shape[1])
@@ -1022,6 +1030,8 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         raise ValueError("self blocks need a context with roman_shared_reduce_dev" + way)
     if not hasattr(ctx, "session_gate_dev"):
         raise ValueError("the context has no roman_session_gate_dev" + way)
+    if stacked and not hasattr(ctx, "session_stacked_sim_dev"):
+        raise ValueError("the context has no roman_session_stacked_sim_dev" + way)
     dev = p[0].pool.device
     on_host = dev.type == "cpu"                              # CPU tensors + a stand-in context (tests)
     wait_torch = (lambda: None) if on_host else (lambda: torch.cuda.current_stream(dev).synchronize())
@@ -1034,11 +1044,26 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     if any_gt:
         pos_gt = np.concatenate([np.full((int(counts[r]), 3), np.nan) if (hs is None or hs["pos_gt"] is None) else hs["pos_gt"] for r, hs in lv])
     FLh, FRh = cat(lambda hs: hs["frames"][0], (16,)), cat(lambda hs: hs["frames"][1], (16,))
-    rows_of = {r: torch.from_numpy(keep[r].astype(np.int64)).to(dev) for r in {r for r, _ in lv}} if d else {}
+    rows_of = {r: torch.from_numpy(keep[r].astype(np.int64)).to(dev) for r in {r for r, _ in lv}} if d or stacked else {}
     t = dict(pos=up(cat(lambda hs: hs["pos"], (3,))), gt=up(pos_gt),
              has=up(np.array([gt_poses[r] is not None for r, _ in views], dtype=np.int32)) if any_gt else None,
              T_w=up(cat(lambda hs: hs["T_w"][0], (16,))), time=up(cat(lambda hs: hs["time"], ())), sub_off=up(sub_off), blocks=up(blk),
              pair_off=up(pair_off), tile_off=up(tile_off), desc=torch.cat([p[r].desc_dev[rows_of[r]] for r, _ in lv]).contiguous() if d else None)
+
+    if stacked:
+        # ONE frame table and ONE block of mask words for the session: every live robot's frame descriptors once and the mask rows of
+        # its non-empty submaps (gathered on the device) once, whatever number of views it has — the views of a robot name the same
+        # frames and the same words
+        live_f = sorted(rows_of)
+        fdesc = p[live_f[0]].frame_desc_dev if len(live_f) == 1 else torch.cat([p[r].frame_desc_dev for r in live_f], dim=0)
+        fmask = torch.cat([p[r].frame_mask[rows_of[r]].reshape(-1) for r in live_f]).contiguous()
+        nfr = {r: int(p[r].frame_desc_dev.shape[0]) for r in live_f}
+        flo = dict(zip(live_f, np.concatenate([[0], np.cumsum([nfr[r] for r in live_f])]).astype(np.int64).tolist()))
+        mof = dict(zip(live_f, np.concatenate([[0], np.cumsum([int(counts[r]) * ((nfr[r] + 63) // 64) for r in live_f])]).astype(np.int64).tolist()))
+        frame_lo = np.array([flo.get(r, 0) for r, _ in views], dtype=np.int32)
+        frame_n = np.array([nfr.get(r, 0) for r, _ in views], dtype=np.int32)
+        mask_off = np.array([mof.get(r, 0) for r, _ in views], dtype=np.int64)
+        t.update(frame_lo=up(frame_lo), frame_n=up(frame_n), mask_off=up(mask_off))
 
     # ---- pass 1 of all blocks on the device: one enqueue, one synchronisation, one read-back ----
     f64, i32 = torch.float64, torch.int32
@@ -1048,10 +1073,17 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
              enable=torch.empty(total, dtype=i32, device=dev), todo_off=torch.zeros(nb + 1, dtype=i32, device=dev))
     gp = grid_gate_params(sm_params.submap_radius, sm_io.skip_distance, d, sm_params.submap_descriptor_thresh if d else 0.0,
                           False, sm_params.single_robot_lc_time_thresh)
+    gate_kw = dict(time_ptr=ptr(t["time"]), desc_ptr=ptr(t["desc"]), pos_gt_ptr=ptr(t["gt"]), has_gt_ptr=ptr(t["has"]))
     wait_torch()                                             # the uploads are in place before the library's stream reads them
+    if stacked:                                              # similarity first, then the gate that reads it: both on the context's stream
+        gp.desc_thresh = float(sm_params.submap_descriptor_thresh)
+        ctx.session_stacked_sim_dev(int(fdesc.shape[1]), int(fdesc.shape[0]), ptr(fdesc), ptr(fmask), frame_lo, frame_n, mask_off, sub_off, blk, pair_off,
+                                    ptr(t["frame_lo"]), ptr(t["frame_n"]), ptr(t["mask_off"]), ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]),
+                                    g["sim"].data_ptr())
+        gate_kw["sim_in_ptr"] = g["sim"].data_ptr()
     ctx.session_gate_dev(gp, sub_off, blk, pair_off, tile_off, ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]), ptr(t["tile_off"]),
                          ptr(t["pos"]), ptr(t["T_w"]), *[g[k].data_ptr() for k in ("dist", "flags", "yaw", "sim", "T_ij", "pairs", "T_ref", "enable", "todo_off")],
-                         time_ptr=ptr(t["time"]), desc_ptr=ptr(t["desc"]), pos_gt_ptr=ptr(t["gt"]), has_gt_ptr=ptr(t["has"]))
+                         **gate_kw)
     ctx.sync()
     todo_off = g["todo_off"].cpu().numpy().astype(np.int64)
     B = int(todo_off[-1])

@@ -7674,6 +7674,8 @@ __device__ __forceinline__ int session_find(const int32_t* __restrict__ off, int
     return lo;
 }
 
+// SIM_IN (roman_session_gate_sim*): the similarity of every pair is already in out.sim — read, never written — and no descriptor is touched
+template <bool SIM_IN>
 __global__ void __launch_bounds__(256) k_session_gate(roman_grid_gate_params_t P, SessionTab tab, int64_t tiles, GridSide s,
                                                       const double* __restrict__ norm, GridOut out)
 {
@@ -7686,7 +7688,7 @@ __global__ void __launch_bounds__(256) k_session_gate(roman_grid_gate_params_t P
     const int nT = (n1 + GRID_TJ - 1) / GRID_TJ;
     const int64_t lw = w - tab.tile_off[b];
     const int i = (int)(lw / nT), j0 = (int)(lw % nT) * GRID_TJ;
-    const int d = P.desc_dim;
+    const int d = SIM_IN ? 0 : P.desc_dim;
     double acc[GRID_TJ];
 #pragma unroll
     for (int t = 0; t < GRID_TJ; ++t) acc[t] = 0.0;
@@ -7710,8 +7712,8 @@ __global__ void __launch_bounds__(256) k_session_gate(roman_grid_gate_params_t P
     for (int t = 1; t < GRID_TJ; ++t) dot = (lane == t) ? acc[t] : dot;
     const int64_t gi = base0 + i, gj = base1 + j;
     const bool gt = s.pos_gt != nullptr && tab.has_gt[r0] != 0 && tab.has_gt[r1] != 0;      // [REF :96-99]
-    const double np_ = d > 0 ? norm[gi] * norm[gj] : 0.0;
-    grid_pair<false, false>(P, s, s, gi, gj, gt, d, dot, np_, tab.pair_off[b] + (int64_t)i * n1 + j, out);
+    const double np_ = (!SIM_IN && d > 0) ? norm[gi] * norm[gj] : 0.0;
+    grid_pair<SIM_IN, false>(P, s, s, gi, gj, gt, d, dot, np_, tab.pair_off[b] + (int64_t)i * n1 + j, out);
 }
 
 // the TODO flags of this workgroup's SESSION_SCAN pairs: -> (is flag g TODO, TODO flags of the workgroup in front of g, their number in the workgroup)
@@ -7897,14 +7899,12 @@ __global__ void __launch_bounds__(256) k_fill_f64(int64_t n, double v, double* _
 
 constexpr int STACK_TILE = 32;                                   // rows and columns of the frame-cosine matrix a wave of k_stacked_band owns
 
-// rows [a0, a0 + H) of map 0 (a0 + H <= Nf0) against the Nf1 frames of map 1 -> Cb[H][Nf1]
-__global__ void __launch_bounds__(256) k_stacked_band(int d, int a0, int H, int Nf1, const double* __restrict__ desc0, const double* __restrict__ desc1,
-                                                      const double* __restrict__ norm0, const double* __restrict__ norm1, double* __restrict__ Cb)
+// One STACK_TILE x STACK_TILE tile (xt, yt) of a band — what a wave of k_stacked_band and of k_session_band does once it knows its
+// tile: rows [a0, a0 + H) of desc0 against the Nf1 rows of desc1 -> Cb[H][Nf1].  The contraction order of an element depends on d
+// alone, never on the tile, the band or the launch: that is what makes a session's block bit for bit roman_stacked_sim_dev's.
+__device__ __forceinline__ void stacked_tile(int d, int a0, int H, int Nf1, const double* desc0, const double* desc1, const double* norm0, const double* norm1,
+                                             double* Cb, int xt, int yt)
 {
-    const int nty = (Nf1 + STACK_TILE - 1) / STACK_TILE, ntx = (H + STACK_TILE - 1) / STACK_TILE;
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= (int64_t)ntx * nty) return;                         // (wave-uniform)
-    const int xt = (int)(w / nty), yt = (int)(w % nty);
     const int lane = threadIdx.x & 63, lr = lane & 15, kq = lane >> 4;
     const double* fa[2]; const double* fb[2]; bool va[2], vb[2];
 #pragma unroll
@@ -7963,12 +7963,21 @@ __global__ void __launch_bounds__(256) k_stacked_band(int d, int a0, int H, int 
     }
 }
 
-// nbx workgroups per submap i; `first`: the band opens R (nothing is read)
-__global__ void __launch_bounds__(256) k_stacked_colmax(int nbx, int W0, int a0, int H, int Nf1, int first, const unsigned long long* __restrict__ mask0,
-                                                        const double* __restrict__ Cb, double* __restrict__ R)
+// rows [a0, a0 + H) of map 0 (a0 + H <= Nf0) against the Nf1 frames of map 1 -> Cb[H][Nf1]
+__global__ void __launch_bounds__(256) k_stacked_band(int d, int a0, int H, int Nf1, const double* __restrict__ desc0, const double* __restrict__ desc1,
+                                                      const double* __restrict__ norm0, const double* __restrict__ norm1, double* __restrict__ Cb)
 {
-    const int i = blockIdx.x / nbx, b = (blockIdx.x % nbx) * 256 + threadIdx.x;
-    if (b >= Nf1) return;
+    const int nty = (Nf1 + STACK_TILE - 1) / STACK_TILE, ntx = (H + STACK_TILE - 1) / STACK_TILE;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= (int64_t)ntx * nty) return;                         // (wave-uniform)
+    stacked_tile(d, a0, H, Nf1, desc0, desc1, norm0, norm1, Cb, (int)(w / nty), (int)(w % nty));
+}
+
+// element (i, b) of R against one band — the owner thread's work in k_stacked_colmax and k_session_colmax; `first`: the band opens R
+// (nothing is read)
+__device__ __forceinline__ void stacked_colmax_one(int i, int b, int W0, int a0, int H, int Nf1, int first, const unsigned long long* mask0, const double* Cb,
+                                                   double* R)
+{
     double m = first ? -INFINITY : R[(int64_t)i * Nf1 + b];
     for (int w = a0 >> 6; w <= (a0 + H - 1) >> 6; ++w) {
         unsigned long long bits = mask0[(int64_t)i * W0 + w];    // (uniform); clipped to the band's frames
@@ -7984,20 +7993,117 @@ __global__ void __launch_bounds__(256) k_stacked_colmax(int nbx, int W0, int a0,
     R[(int64_t)i * Nf1 + b] = m;
 }
 
-__global__ void __launch_bounds__(256) k_stacked_rowmax(int S0, int S1, int W1, int Nf1, const unsigned long long* __restrict__ mask1,
-                                                        const double* __restrict__ R, double* __restrict__ sim)
+// nbx workgroups per submap i
+__global__ void __launch_bounds__(256) k_stacked_colmax(int nbx, int W0, int a0, int H, int Nf1, int first, const unsigned long long* __restrict__ mask0,
+                                                        const double* __restrict__ Cb, double* __restrict__ R)
+{
+    const int i = blockIdx.x / nbx, b = (blockIdx.x % nbx) * 256 + threadIdx.x;
+    if (b >= Nf1) return;
+    stacked_colmax_one(i, b, W0, a0, H, Nf1, first, mask0, Cb, R);
+}
+
+// max over b in mask1[j] of R[i][b], the same bits in every lane of the wave — a pair's work in k_stacked_rowmax and k_session_rowmax
+__device__ __forceinline__ double stacked_rowmax_one(int i, int j, int W1, int Nf1, const unsigned long long* mask1, const double* R)
 {
     const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= (int64_t)S0 * S1) return;                           // (wave-uniform)
-    const int i = (int)(p / S1), j = (int)(p % S1);
     double m = -INFINITY;
     for (int w = 0; w < W1; ++w) {
         const unsigned long long bits = mask1[(int64_t)j * W1 + w];      // (uniform)
         const int b = 64 * w + lane;
         if (((bits >> lane) & 1ull) && b < Nf1) m = fmax(m, R[(int64_t)i * Nf1 + b]);
     }
-    m = wave_max_all(m);
+    return wave_max_all(m);
+}
+
+__global__ void __launch_bounds__(256) k_stacked_rowmax(int S0, int S1, int W1, int Nf1, const unsigned long long* __restrict__ mask1,
+                                                        const double* __restrict__ R, double* __restrict__ sim)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= (int64_t)S0 * S1) return;                           // (wave-uniform)
+    const double m = stacked_rowmax_one((int)(p / S1), (int)(p % S1), W1, Nf1, mask1, R);
+    if (lane == 0) sim[p] = m;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The stacked similarity of every block of a session (roman_session_stacked_sim*): roman_stacked_sim_dev over a LIST
+// of robot pairs that share ONE frame table.  View r names the frames [frame_lo[r], frame_lo[r] + frame_n[r]) of it and the masks
+// uint64[n_r][ceil(frame_n[r] / 64)] at mask + mask_off[r] (bit t: frame frame_lo[r] + t); blocks, sub_off and pair_off are
+// k_session_gate's.  The host cuts every live block (submaps and frames on both sides) into ITEMS — (block, a0, h): the rows
+// [a0, a0 + h) of the block's frame-cosine matrix — and deals them into ROUNDS of at most ONE item per block, whose bands lie side by
+// side in the band workspace.  A round is two launches:
+//   k_session_band    a wave per tile of the round: its item by a wave-uniform binary search of the items' tile prefix (as
+//                     k_session_gate finds its block), then stacked_tile() — k_stacked_band's wave, instruction for instruction;
+//   k_session_colmax  a workgroup per (item, submap i, 256 columns): its item by the workgroup prefix, then stacked_colmax_one().  One
+//                     item per block and round: no two threads of a launch own the same element of R, and the rounds are ordered on
+//                     the stream — a block's R is opened by its first item (a0 == 0) and updated in place by the later ones.
+// Behind the last round:
+//   k_session_rowmax  a wave per pair of pair_off[nb]: its block by binary search of pair_off, then stacked_rowmax_one(); -inf for a
+//                     block with a view without frames (there is no R to read).
+// No atomics, no spin-waits, no cooperative launch; max of doubles is exact and order-free, so how the host cuts the items
+// (roman_ctx_set_stacked_band, the other blocks of the list) changes no bit of the result.
+// ---------------------------------------------------------------------------------------------
+struct SsTab { int nb; const int32_t* sub_off; const int32_t* blocks; const int64_t* pair_off; const int32_t* frame_lo; const int32_t* frame_n; const int64_t* mask_off; };
+
+// rows [a0, a0 + h) of block `block`: its band at band_off of the band workspace (doubles), its block's R at r_off of the R workspace;
+// tile_off / wg_off: the tiles / the column-maximum workgroups of the round's items in front of it
+struct SsItem { int64_t band_off, tile_off, r_off; int32_t wg_off, block, a0, h; };
+static_assert(sizeof(SsItem) == 40, "SsItem travels as five 64-bit words");
+
+// the last k in [0, n) with items[k].tile_off <= x / items[k].wg_off <= x (ascending, items[0] at 0, no item empty)
+__device__ __forceinline__ int ss_find_tile(const SsItem* __restrict__ items, int n, int64_t x)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (items[mid].tile_off <= x) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ int ss_find_wg(const SsItem* __restrict__ items, int n, int x)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (items[mid].wg_off <= x) lo = mid; else hi = mid; }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) k_session_band(int d, SsTab tab, const SsItem* __restrict__ items, int n_items, int64_t tiles,
+                                                      const double* __restrict__ desc, const double* __restrict__ norm, double* __restrict__ band)
+{
+    const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (w >= tiles) return;                                      // (wave-uniform, as everything up to the tile)
+    const SsItem it = items[ss_find_tile(items, n_items, w)];
+    const int r0 = tab.blocks[4 * it.block], r1 = tab.blocks[4 * it.block + 1];
+    const int lo0 = tab.frame_lo[r0], lo1 = tab.frame_lo[r1], Nf1 = tab.frame_n[r1];
+    const int nty = (Nf1 + STACK_TILE - 1) / STACK_TILE;
+    const int64_t lw = w - it.tile_off;
+    stacked_tile(d, it.a0, it.h, Nf1, desc + (int64_t)lo0 * d, desc + (int64_t)lo1 * d, norm + lo0, norm + lo1, band + it.band_off,
+                 (int)(lw / nty), (int)(lw % nty));
+}
+
+__global__ void __launch_bounds__(256) k_session_colmax(SsTab tab, const SsItem* __restrict__ items, int n_items, const unsigned long long* __restrict__ mask,
+                                                        const double* __restrict__ band, double* __restrict__ R)
+{
+    const SsItem it = items[ss_find_wg(items, n_items, (int)blockIdx.x)];
+    const int r0 = tab.blocks[4 * it.block], r1 = tab.blocks[4 * it.block + 1];
+    const int Nf0 = tab.frame_n[r0], Nf1 = tab.frame_n[r1];
+    const int nbx = (Nf1 + 255) / 256;
+    const int lw = (int)blockIdx.x - it.wg_off;
+    const int i = lw / nbx, b = (lw % nbx) * 256 + threadIdx.x;
+    if (b >= Nf1) return;
+    stacked_colmax_one(i, b, (Nf0 + 63) >> 6, it.a0, it.h, Nf1, it.a0 == 0 ? 1 : 0, mask + tab.mask_off[r0], band + it.band_off, R + it.r_off);
+}
+
+// r_off[b]: block b's R in the R workspace (read for a live block only)
+__global__ void __launch_bounds__(256) k_session_rowmax(SsTab tab, const int64_t* __restrict__ r_off, int64_t total, const unsigned long long* __restrict__ mask,
+                                                        const double* __restrict__ R, double* __restrict__ sim)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (p >= total) return;                                      // (wave-uniform)
+    const int b = session_find(tab.pair_off, tab.nb, p);
+    const int r0 = tab.blocks[4 * b], r1 = tab.blocks[4 * b + 1];
+    const int n1 = tab.sub_off[r1 + 1] - tab.sub_off[r1], Nf0 = tab.frame_n[r0], Nf1 = tab.frame_n[r1];
+    const int64_t l = p - tab.pair_off[b];
+    double m = -INFINITY;                                        // a view without frames: the maximum over nothing
+    if (Nf0 > 0 && Nf1 > 0) m = stacked_rowmax_one((int)(l / n1), (int)(l % n1), (Nf1 + 63) >> 6, Nf1, mask + tab.mask_off[r1], R + r_off[b]);
     if (lane == 0) sim[p] = m;
 }
 

@@ -189,6 +189,10 @@ struct roman_ctx {
     // matrix, and the column maxima R
     DevBuf ssNorm, ssBand, ssR;
     int stacked_band = 0;                      // rows per band (roman_ctx_set_stacked_band); 0: automatic
+    // ... of a whole session (roman_session_stacked_sim*): the blocks' R offsets and the items of every round, as 64-bit words
+    // through pinned staging (a pure enqueue)
+    DevBuf ssItems;
+    PinnedStage<int64_t> ssStage;
 
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
@@ -1454,7 +1458,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx}; for (DevBuf* b : sm) b->release(); }
     c->smStage.release();
     c->ggNorm.release(); c->sgCount.release();
-    c->ssNorm.release(); c->ssBand.release(); c->ssR.release();
+    c->ssNorm.release(); c->ssBand.release(); c->ssR.release(); c->ssItems.release(); c->ssStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -3048,20 +3052,11 @@ int roman_grid_gate_aabb(roman_ctx_t* c, const roman_grid_gate_params_t* gparams
 
 // --- pass 1 of a multi-robot session: the grids of a list of robot pairs in one launch sequence -------------------
 // The tables are checked on their HOST copies (no read-back): -> *total = pair_off[nb], *tiles = tile_off[nb], *S = sub_off[R].
-static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int32_t R, const int32_t* sub_off, const void* pos, const void* pos_gt,
-                              const void* has_gt, const void* T_w, const void* time, const void* desc, int32_t nb, const int32_t* blocks,
-                              const int64_t* pair_off, const int64_t* tile_off, const void* dist, const void* flags, const void* yaw_deg, const void* sim,
-                              const void* T_ij, const void* pairs, const void* T_ref, const void* enable, const void* todo_off,
-                              int64_t* total, int64_t* tiles, int32_t* S)
+// sub_off, blocks and pair_off of a session (tile_off too where it is given), R >= 0, nb >= 0 and the pointers that are needed not NULL:
+// -> *total = pair_off[nb], *tiles = the tiles of the gate, *self: a block sets self_lc
+static int session_tables_check(roman_ctx* c, int32_t R, const int32_t* sub_off, int32_t nb, const int32_t* blocks, const int64_t* pair_off,
+                                const int64_t* tile_off, int64_t* total, int64_t* tiles, bool* self_out)
 {
-    if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
-    if (R < 0 || nb < 0) return fail(c, ROMAN_E_INVALID, "R < 0 or nb < 0");
-    if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
-        return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
-    if (P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
-    if (P->desc_dim < 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d is negative", P->desc_dim);
-    if (P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: the session gate serves the radius mode only (roman_grid_gate_aabb* per robot pair)", P->radius);
-    if (!sub_off || !pair_off || !tile_off || !todo_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / tile_off / todo_off is NULL");
     if (sub_off[0] != 0) return fail(c, ROMAN_E_INVALID, "sub_off[0] must be 0");
     for (int r = 0; r < R; ++r)
         if (sub_off[r + 1] < sub_off[r]) return fail(c, ROMAN_E_INVALID, "sub_off decreases at robot %d", r);
@@ -3069,7 +3064,7 @@ static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, i
     int64_t po = 0, to = 0;
     std::vector<int64_t> seen;
     seen.reserve((size_t)nb);
-    if (pair_off[0] != 0 || tile_off[0] != 0) return fail(c, ROMAN_E_INVALID, "pair_off[0] and tile_off[0] must be 0");
+    if (pair_off[0] != 0 || (tile_off && tile_off[0] != 0)) return fail(c, ROMAN_E_INVALID, "pair_off[0] and tile_off[0] must be 0");
     for (int b = 0; b < nb; ++b) {
         const int32_t r0 = blocks[4 * b], r1 = blocks[4 * b + 1];
         if (r0 < 0 || r0 >= R || r1 < 0 || r1 >= R) return fail(c, ROMAN_E_INVALID, "block %d names robot %d / %d outside [0, %d)", b, r0, r1, R);
@@ -3079,17 +3074,79 @@ static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, i
         const int64_t n0 = sub_off[r0 + 1] - sub_off[r0], n1 = sub_off[r1 + 1] - sub_off[r1];
         po += n0 * n1; to += n0 * ((n1 + GRID_TJ - 1) / GRID_TJ);
         if (po > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "the blocks hold more than %d pairs: beyond the index width", INT32_MAX / 16);
-        if (pair_off[b + 1] != po || tile_off[b + 1] != to) return fail(c, ROMAN_E_INVALID, "pair_off / tile_off disagree with sub_off and blocks at block %d", b);
+        if (pair_off[b + 1] != po || (tile_off && tile_off[b + 1] != to)) return fail(c, ROMAN_E_INVALID, "pair_off / tile_off disagree with sub_off and blocks at block %d", b);
     }
     std::sort(seen.begin(), seen.end());
     if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return fail(c, ROMAN_E_INVALID, "a robot pair is listed twice");
-    *total = po; *tiles = to; *S = sub_off[R];
+    *total = po; *tiles = to; *self_out = self;
+    return ROMAN_OK;
+}
+
+// sim_in: `sim` holds every pair's similarity already (roman_session_gate_sim*): desc_dim must be 0
+static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int32_t R, const int32_t* sub_off, const void* pos, const void* pos_gt,
+                              const void* has_gt, const void* T_w, const void* time, const void* desc, int32_t nb, const int32_t* blocks,
+                              const int64_t* pair_off, const int64_t* tile_off, const void* dist, const void* flags, const void* yaw_deg, const void* sim,
+                              const void* T_ij, const void* pairs, const void* T_ref, const void* enable, const void* todo_off,
+                              int64_t* total, int64_t* tiles, int32_t* S, bool sim_in = false)
+{
+    if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
+    if (sim_in && P->desc_dim != 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d: the similarity is given, desc_dim must be 0", P->desc_dim);
+    if (R < 0 || nb < 0) return fail(c, ROMAN_E_INVALID, "R < 0 or nb < 0");
+    if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
+        return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
+    if (P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
+    if (P->desc_dim < 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d is negative", P->desc_dim);
+    if (P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: the session gate serves the radius mode only (roman_grid_gate_aabb* per robot pair)", P->radius);
+    if (!sub_off || !pair_off || !tile_off || !todo_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / tile_off / todo_off is NULL");
+    bool self = false;
+    { int rc = session_tables_check(c, R, sub_off, nb, blocks, pair_off, tile_off, total, tiles, &self); if (rc) return rc; }
+    const int64_t po = *total;
+    *S = sub_off[R];
     if (po == 0) return ROMAN_OK;
     if (P->desc_dim > 0 && !desc) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
     if (!pos || !T_w) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
     if (pos_gt && !has_gt) return fail(c, ROMAN_E_INVALID, "has_gt is NULL with pos_gt");
     if (self && !time) return fail(c, ROMAN_E_INVALID, "time is NULL with a self_lc block");
     if (!dist || !flags || !yaw_deg || !sim || !T_ij || !pairs || !T_ref || !enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
+    return ROMAN_OK;
+}
+
+// the device-pointer session gate; sim_in: `sim` holds every pair's similarity already (roman_session_gate_sim_dev) and is only read
+static int session_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
+                            const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                            int32_t nb, const int32_t* blocks, const int32_t* blocks_host,
+                            const int64_t* pair_off, const int64_t* pair_off_host, const int64_t* tile_off, const int64_t* tile_off_host,
+                            double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                            int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, bool sim_in)
+{
+    // (the arguments are judged first — on host memory only, a NULL context included: fail() then keeps the text for roman_last_error(NULL))
+    if (!sub_off || !pair_off || !tile_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "a table is NULL on the device");
+    int64_t total = 0, tiles = 0; int32_t S = 0;
+    int rc = session_gate_check(c, gparams, R, sub_off_host, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks_host, pair_off_host, tile_off_host,
+                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S, sim_in);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    if (total == 0) { HIPCHK(c, hipMemsetAsync(todo_off, 0, sizeof(int32_t) * (size_t)(nb + 1), stream)); return ROMAN_OK; }
+    const int d = sim_in ? 0 : gparams->desc_dim;
+    const int nwg = (int)((total + SESSION_SCAN - 1) / SESSION_SCAN);
+    HIPCHK(c, c->ggNorm.ensure(sizeof(double) * (size_t)S));                    // scratch first: a failure leaves nothing enqueued
+    HIPCHK(c, c->sgCount.ensure(sizeof(int32_t) * (size_t)nwg));
+    double* dNorm = c->ggNorm.as<double>();
+    int32_t* dCount = c->sgCount.as<int32_t>();
+    if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, stream, (int)S, 0, d, desc, (const double*)nullptr, dNorm);
+    const SessionTab tab{(int)nb, sub_off, blocks, pair_off, tile_off, has_gt};
+    const GridSide s{pos, pos_gt, T_w, time, desc, nullptr};
+    const GridOut out{dist, flags, yaw_deg, sim, T_ij};
+    if (sim_in) hipLaunchKernelGGL(k_session_gate<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
+    else hipLaunchKernelGGL(k_session_gate<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
+    hipLaunchKernelGGL(k_session_count, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, dCount);
+    hipLaunchKernelGGL(k_session_scan, dim3(1), dim3(SESSION_SCAN), 0, stream, nwg, dCount, tab, total, todo_off);
+    hipLaunchKernelGGL(k_session_scatter, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, (const int32_t*)dCount, tab, pairs, todo_off);
+    hipLaunchKernelGGL(k_session_fill, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, tab, (const int32_t*)todo_off,
+                       (const int32_t*)pairs, (const double*)T_ij, time, T_ref, enable);
+    HIPCHK(c, hipGetLastError());
     return ROMAN_OK;
 }
 
@@ -3100,45 +3157,34 @@ int roman_session_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gpara
                            double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
                            int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
 {
-    // (the arguments are judged first — on host memory only, a NULL context included: fail() then keeps the text for roman_last_error(NULL))
-    if (!sub_off || !pair_off || !tile_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "a table is NULL on the device");
-    int64_t total = 0, tiles = 0; int32_t S = 0;
-    int rc = session_gate_check(c, gparams, R, sub_off_host, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks_host, pair_off_host, tile_off_host,
-                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S);
-    if (rc) return rc;
-    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t stream = c->stream;
-    if (total == 0) { HIPCHK(c, hipMemsetAsync(todo_off, 0, sizeof(int32_t) * (size_t)(nb + 1), stream)); return ROMAN_OK; }
-    const int d = gparams->desc_dim;
-    const int nwg = (int)((total + SESSION_SCAN - 1) / SESSION_SCAN);
-    HIPCHK(c, c->ggNorm.ensure(sizeof(double) * (size_t)S));                    // scratch first: a failure leaves nothing enqueued
-    HIPCHK(c, c->sgCount.ensure(sizeof(int32_t) * (size_t)nwg));
-    double* dNorm = c->ggNorm.as<double>();
-    int32_t* dCount = c->sgCount.as<int32_t>();
-    if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, stream, (int)S, 0, d, desc, (const double*)nullptr, dNorm);
-    const SessionTab tab{(int)nb, sub_off, blocks, pair_off, tile_off, has_gt};
-    const GridSide s{pos, pos_gt, T_w, time, desc, nullptr};
-    const GridOut out{dist, flags, yaw_deg, sim, T_ij};
-    hipLaunchKernelGGL(k_session_gate, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
-    hipLaunchKernelGGL(k_session_count, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, dCount);
-    hipLaunchKernelGGL(k_session_scan, dim3(1), dim3(SESSION_SCAN), 0, stream, nwg, dCount, tab, total, todo_off);
-    hipLaunchKernelGGL(k_session_scatter, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, (const int32_t*)dCount, tab, pairs, todo_off);
-    hipLaunchKernelGGL(k_session_fill, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, tab, (const int32_t*)todo_off,
-                       (const int32_t*)pairs, (const double*)T_ij, time, T_ref, enable);
-    HIPCHK(c, hipGetLastError());
-    return ROMAN_OK;
+    return session_gate_dev(c, gparams, R, sub_off, sub_off_host, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks, blocks_host, pair_off, pair_off_host,
+                            tile_off, tile_off_host, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, false);
 }
 
-int roman_session_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
-                       const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
-                       int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
-                       double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                       int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
+// `desc` is not read and `sim` is not written (both may be NULL): the similarity is sim_in
+int roman_session_gate_sim_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
+                               const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                               int32_t nb, const int32_t* blocks, const int32_t* blocks_host,
+                               const int64_t* pair_off, const int64_t* pair_off_host, const int64_t* tile_off, const int64_t* tile_off_host,
+                               double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                               int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* sim_in)
+{
+    (void)desc; (void)sim;
+    return session_gate_dev(c, gparams, R, sub_off, sub_off_host, pos, pos_gt, has_gt, T_w, time, nullptr, nb, blocks, blocks_host, pair_off, pair_off_host,
+                            tile_off, tile_off_host, dist, flags, yaw_deg, const_cast<double*>(sim_in) /* k_session_gate<true> only reads it */, T_ij,
+                            pairs, T_ref, enable, todo_off, true);
+}
+
+// the host-pointer session gate; sim_in: the caller's `sim` goes up and is not brought back
+static int session_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                             const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                             int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                             double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                             int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, bool sim_in)
 {
     int64_t total = 0, tiles = 0; int32_t S = 0;
     int rc = session_gate_check(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks, pair_off, tile_off,
-                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S);
+                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S, sim_in);
     if (rc) return rc;
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (total == 0) { std::fill(todo_off, todo_off + nb + 1, 0); return ROMAN_OK; }
@@ -3151,18 +3197,39 @@ int roman_session_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, 
     const auto dPos = m.in(pos, 24 * nS), dGt = m.in(pos_gt, pos_gt ? 24 * nS : 0);
     const auto dHas = m.in(has_gt, pos_gt ? 4 * (size_t)R : 0);
     const auto dTw = m.in(T_w, 128 * nS), dTime = m.in(time, time ? 8 * nS : 0), dDesc = m.in(desc, 8 * d * nS);
-    const auto dDist = m.out(dist, 8 * B), dYaw = m.out(yaw_deg, 8 * B), dSim = m.out(sim, 8 * B), dTij = m.out(T_ij, 128 * B);
+    const auto dDist = m.out(dist, 8 * B), dYaw = m.out(yaw_deg, 8 * B), dSim = sim_in ? m.in(sim, 8 * B) : m.out(sim, 8 * B), dTij = m.out(T_ij, 128 * B);
     const auto dFlags = m.out(flags, 4 * B);
     // the compact outputs are inout: the slots beyond todo_off[nb] come back as they were
     const auto dTref = m.inout(T_ref, 128 * B);
     const auto dPairs = m.inout(pairs, 8 * B), dEn = m.inout(enable, 4 * B), dOff = m.out(todo_off, 4 * ((size_t)nb + 1));
     rc = m.upload();
     if (rc) return rc;
-    rc = roman_session_gate_dev(c, gparams, R, dSub.dev(), sub_off, dPos.dev(), dGt.dev(), dHas.dev(), dTw.dev(), dTime.dev(), dDesc.dev(),
-                                nb, dBlk.dev(), blocks, dPo.dev(), pair_off, dTo.dev(), tile_off,
-                                dDist.dev(), dFlags.dev(), dYaw.dev(), dSim.dev(), dTij.dev(), dPairs.dev(), dTref.dev(), dEn.dev(), dOff.dev());
+    rc = session_gate_dev(c, gparams, R, dSub.dev(), sub_off, dPos.dev(), dGt.dev(), dHas.dev(), dTw.dev(), dTime.dev(), dDesc.dev(),
+                          nb, dBlk.dev(), blocks, dPo.dev(), pair_off, dTo.dev(), tile_off,
+                          dDist.dev(), dFlags.dev(), dYaw.dev(), dSim.dev(), dTij.dev(), dPairs.dev(), dTref.dev(), dEn.dev(), dOff.dev(), sim_in);
     if (rc) return rc;
     return m.download();
+}
+
+int roman_session_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                       const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                       int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                       double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                       int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
+{
+    return session_gate_host(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks, pair_off, tile_off, dist, flags, yaw_deg, sim, T_ij,
+                             pairs, T_ref, enable, todo_off, false);
+}
+
+int roman_session_gate_sim(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                           const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                           int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                           double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                           int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* sim_in)
+{
+    (void)desc; (void)sim;
+    return session_gate_host(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, nullptr, nb, blocks, pair_off, tile_off, dist, flags, yaw_deg,
+                             const_cast<double*>(sim_in) /* uploaded, never written */, T_ij, pairs, T_ref, enable, todo_off, true);
 }
 
 // --- frame descriptors of the submaps of a pool ([REF roman/map/map.py:210-242], [REF :155-162]) ------------------
@@ -3311,6 +3378,156 @@ int roman_stacked_sim(roman_ctx_t* c, int32_t d, int32_t Nf0, const double* desc
     rc = m.upload();
     if (rc) return rc;
     rc = roman_stacked_sim_dev(c, d, Nf0, d0.dev(), S0, m0.dev(), Nf1, d1.dev(), S1, m1.dev(), dSim.dev());
+    if (rc) return rc;
+    return m.download();
+}
+
+// --- the stacked similarity of every block of a session in one launch sequence -----------------------------------
+// One live block (submaps and frames on both sides) as the host sees it while it cuts the items.
+struct SsLive { int32_t b; int64_t n0, Nf0, Nf1, r_off, a; };
+
+// The tables are checked on their HOST copies (no read-back).  -> *total = pair_off[nb], the live blocks with their R offsets,
+// *r_total: the doubles of all R together
+static int session_stacked_check(roman_ctx* c, int32_t d, int32_t Nf, const void* desc, const void* mask, int32_t R, const int32_t* frame_lo,
+                                 const int32_t* frame_n, const int64_t* mask_off, const int32_t* sub_off, int32_t nb, const int32_t* blocks,
+                                 const int64_t* pair_off, const void* sim, int64_t* total, std::vector<SsLive>* live, int64_t* r_total)
+{
+    if (d < 1) return fail(c, ROMAN_E_INVALID, "d=%d: a frame descriptor has at least one component", d);
+    if (Nf < 0 || R < 0 || nb < 0) return fail(c, ROMAN_E_INVALID, "Nf < 0, R < 0 or nb < 0");
+    if (!sub_off || !pair_off || (nb > 0 && !blocks) || (R > 0 && (!frame_lo || !frame_n || !mask_off)))
+        return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / frame_lo / frame_n / mask_off is NULL");
+    for (int r = 0; r < R; ++r) {
+        if (frame_lo[r] < 0 || frame_n[r] < 0 || (int64_t)frame_lo[r] + frame_n[r] > (int64_t)Nf)
+            return fail(c, ROMAN_E_INVALID, "view %d: the frames [%d, %d + %d) leave the table of %d", r, frame_lo[r], frame_lo[r], frame_n[r], Nf);
+        if (mask_off[r] < 0) return fail(c, ROMAN_E_INVALID, "view %d: mask_off=%lld is negative", r, (long long)mask_off[r]);
+    }
+    int64_t tiles = 0; bool self = false;
+    { int rc = session_tables_check(c, R, sub_off, nb, blocks, pair_off, nullptr, total, &tiles, &self); if (rc) return rc; }
+    if (*total == 0) return ROMAN_OK;
+    int64_t wgs = 0, tl = 0, ro = 0;
+    for (int b = 0; b < nb; ++b) {
+        const int32_t r0 = blocks[4 * b], r1 = blocks[4 * b + 1];
+        const int64_t n0 = sub_off[r0 + 1] - sub_off[r0], n1 = sub_off[r1 + 1] - sub_off[r1], Nf0 = frame_n[r0], Nf1 = frame_n[r1];
+        if (n0 == 0 || n1 == 0 || Nf0 == 0 || Nf1 == 0) continue;
+        live->push_back(SsLive{b, n0, Nf0, Nf1, ro, 0});
+        ro += n0 * Nf1;                                          // (n0 <= INT32_MAX / 16, Nf1 < 2^31, nb < 2^31: far inside int64)
+        wgs += n0 * ((Nf1 + 255) / 256);
+        tl += ((Nf0 + STACK_TILE - 1) / STACK_TILE) * ((Nf1 + STACK_TILE - 1) / STACK_TILE);
+        if (wgs > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "the blocks' submaps x ceil(frames / 256) exceed the launch width of a round");
+        if (tl > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "the blocks' frame-cosine matrices hold more than %d tiles", INT32_MAX);
+    }
+    *r_total = ro;
+    if (!sim) return fail(c, ROMAN_E_INVALID, "sim is NULL");
+    if (!live->empty() && (!desc || !mask)) return fail(c, ROMAN_E_INVALID, "desc / mask is NULL");
+    return ROMAN_OK;
+}
+
+int roman_session_stacked_sim_dev(roman_ctx_t* c, int32_t d, int32_t Nf, const double* desc, const uint64_t* mask,
+                                  int32_t R, const int32_t* frame_lo, const int32_t* frame_lo_host, const int32_t* frame_n, const int32_t* frame_n_host,
+                                  const int64_t* mask_off, const int64_t* mask_off_host, const int32_t* sub_off, const int32_t* sub_off_host,
+                                  int32_t nb, const int32_t* blocks, const int32_t* blocks_host, const int64_t* pair_off, const int64_t* pair_off_host,
+                                  double* sim)
+{
+    // (the arguments are judged first — on host memory only, a NULL context included, as roman_session_gate_dev does)
+    if (!sub_off || !pair_off || (nb > 0 && !blocks) || (R > 0 && (!frame_lo || !frame_n || !mask_off))) return fail(c, ROMAN_E_INVALID, "a table is NULL on the device");
+    int64_t total = 0, r_total = 0;
+    std::vector<SsLive> live;
+    int rc = session_stacked_check(c, d, Nf, desc, mask, R, frame_lo_host, frame_n_host, mask_off_host, sub_off_host, nb, blocks_host, pair_off_host, sim,
+                                   &total, &live, &r_total);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (total == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+
+    // ---- the items, round by round: at most one per block and round, a round's bands side by side within the budget (a forced band
+    // height caps h; the first item of a round takes STACK_TILE rows at least, whatever they cost) ----
+    struct Round { size_t it0, it1; int64_t tiles, wgs; };
+    std::vector<SsItem> items;
+    std::vector<Round> rounds;
+    const int64_t budget = (int64_t)(64 << 20) / 8;
+    int64_t bandMax = 0;
+    for (size_t open = live.size(); open > 0;) {
+        Round rd{items.size(), 0, 0, 0};
+        int64_t used = 0;
+        for (SsLive& L : live) {
+            if (L.a >= L.Nf0) continue;
+            int64_t h = ((budget - used) / L.Nf1) / STACK_TILE * STACK_TILE;
+            if (c->stacked_band > 0) h = std::min<int64_t>(h, c->stacked_band);
+            if (h < STACK_TILE) { if (used > 0) continue; h = STACK_TILE; }     // (no room left in this round: the block waits for the next)
+            h = std::min(h, L.Nf0 - L.a);
+            items.push_back(SsItem{used, rd.tiles, L.r_off, (int32_t)rd.wgs, L.b, (int32_t)L.a, (int32_t)h});
+            used += h * L.Nf1;
+            rd.tiles += ((h + STACK_TILE - 1) / STACK_TILE) * ((L.Nf1 + STACK_TILE - 1) / STACK_TILE);
+            rd.wgs += L.n0 * ((L.Nf1 + 255) / 256);
+            L.a += h;
+            if (L.a >= L.Nf0) --open;
+        }
+        rd.it1 = items.size();
+        bandMax = std::max(bandMax, used);
+        rounds.push_back(rd);
+    }
+
+    // ---- scratch and staging first: a failure leaves nothing enqueued ----
+    const size_t words = (size_t)nb + 5 * items.size();
+    int64_t* staged = nullptr;
+    HIPCHK(c, c->ssStage.stage(words, &staged));
+    HIPCHK(c, c->ssItems.ensure(sizeof(int64_t) * words));
+    HIPCHK(c, c->ssNorm.ensure(sizeof(double) * (size_t)std::max<int32_t>(Nf, 1)));
+    HIPCHK(c, c->ssBand.ensure(sizeof(double) * (size_t)std::max<int64_t>(bandMax, 1)));
+    HIPCHK(c, c->ssR.ensure(sizeof(double) * (size_t)std::max<int64_t>(r_total, 1)));
+    std::fill(staged, staged + nb, (int64_t)0);
+    for (const SsLive& L : live) staged[L.b] = L.r_off;
+    if (!items.empty()) memcpy(staged + nb, items.data(), sizeof(SsItem) * items.size());
+    HIPCHK(c, c->ssStage.upload(c->ssItems, words, stream));
+    const int64_t* dRoff = c->ssItems.as<int64_t>();
+    const SsItem* dItems = reinterpret_cast<const SsItem*>(dRoff + nb);
+    double* const dNorm = c->ssNorm.as<double>();
+    double* const band = c->ssBand.as<double>();
+    double* const Rw = c->ssR.as<double>();
+    const SsTab tab{(int)nb, sub_off, blocks, pair_off, frame_lo, frame_n, mask_off};
+    const unsigned long long* m = reinterpret_cast<const unsigned long long*>(mask);
+    if (!live.empty())                                           // once per frame of the session, whatever number of blocks and views read it
+        hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)(((int64_t)Nf + 3) / 4)), dim3(256), 0, stream, (int)Nf, 0, (int)d, desc, (const double*)nullptr, dNorm);
+    for (const Round& rd : rounds) {                             // rounds ordered on the stream: each updates the blocks' R in place
+        const int n = (int)(rd.it1 - rd.it0);
+        hipLaunchKernelGGL(k_session_band, dim3((unsigned)((rd.tiles + 3) / 4)), dim3(256), 0, stream, (int)d, tab, dItems + rd.it0, n, rd.tiles, desc,
+                           (const double*)dNorm, band);
+        hipLaunchKernelGGL(k_session_colmax, dim3((unsigned)rd.wgs), dim3(256), 0, stream, tab, dItems + rd.it0, n, m, (const double*)band, Rw);
+    }
+    hipLaunchKernelGGL(k_session_rowmax, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, tab, dRoff, total, m, (const double*)Rw, sim);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_session_stacked_sim(roman_ctx_t* c, int32_t d, int32_t Nf, const double* desc, const uint64_t* mask, int64_t mask_words,
+                              int32_t R, const int32_t* frame_lo, const int32_t* frame_n, const int64_t* mask_off, const int32_t* sub_off,
+                              int32_t nb, const int32_t* blocks, const int64_t* pair_off, double* sim)
+{
+    int64_t total = 0, r_total = 0;
+    std::vector<SsLive> live;
+    int rc = session_stacked_check(c, d, Nf, desc, mask, R, frame_lo, frame_n, mask_off, sub_off, nb, blocks, pair_off, sim, &total, &live, &r_total);
+    if (rc) return rc;
+    if (mask_words < 0) return fail(c, ROMAN_E_INVALID, "mask_words=%lld is negative", (long long)mask_words);
+    for (int r = 0; r < R; ++r)                                  // the host twin copies `mask`: every view must lie inside the words it was given
+        if (mask_off[r] + (int64_t)(sub_off[r + 1] - sub_off[r]) * (((int64_t)frame_n[r] + 63) / 64) > mask_words)
+            return fail(c, ROMAN_E_INVALID, "view %d: its masks leave the %lld words of mask", r, (long long)mask_words);
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (total == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    HostMirror m(c);
+    const auto dDesc = m.in(desc, 8 * (size_t)Nf * (size_t)d);
+    const auto dMask = m.in(mask, 8 * (size_t)mask_words);
+    const auto dLo = m.in(frame_lo, 4 * (size_t)R), dN = m.in(frame_n, 4 * (size_t)R);
+    const auto dMo = m.in(mask_off, 8 * (size_t)R);
+    const auto dSub = m.in(sub_off, 4 * ((size_t)R + 1)), dBlk = m.in(blocks, 16 * (size_t)nb);
+    const auto dPo = m.in(pair_off, 8 * ((size_t)nb + 1));
+    const auto dSim = m.out(sim, 8 * (size_t)total);
+    rc = m.upload();
+    if (rc) return rc;
+    rc = roman_session_stacked_sim_dev(c, d, Nf, dDesc.dev(), dMask.dev(), R, dLo.dev(), frame_lo, dN.dev(), frame_n, dMo.dev(), mask_off, dSub.dev(), sub_off,
+                                       nb, dBlk.dev(), blocks, dPo.dev(), pair_off, dSim.dev());
     if (rc) return rc;
     return m.download();
 }

@@ -677,11 +677,12 @@ class Context:
 
     # ------------------------------------------------------------------ pass 1 of every robot pair of a session
     def session_gate(self, gparams, sub_off, blocks, pair_off, tile_off, pos, T_w, time=None, desc=None, pos_gt=None, has_gt=None,
-                     pairs=None, T_ref=None, enable=None):
+                     pairs=None, T_ref=None, enable=None, sim_in=None):
         """Host-pointer pass 1 over a list of robot pairs (roman_session_gate): the tables as session_tables() gives them (they are
         passed as they are: the library checks them); pos (S, 3), T_w (S, 4, 4), time (S,), desc (S, desc_dim), pos_gt (S, 3) with
         has_gt (R,) over ALL submaps of the session.  gparams.single_robot_lc is not read: a block's own self_lc is.  The compact
-        outputs may be handed in, as grid_gate() takes them.  -> SessionGateResult."""
+        outputs may be handed in, as grid_gate() takes them.  sim_in (pair_off[nb],): the similarity of every pair is given
+        (roman_session_gate_sim; gparams.desc_dim must be 0) and comes back as `sim`.  -> SessionGateResult."""
         sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
         pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
         R, nb = len(sub_off) - 1, len(blocks)
@@ -703,6 +704,15 @@ class Context:
         dist = np.zeros(B); flags = np.zeros(B, dtype=np.int32); yaw = np.zeros(B); sim = np.zeros(B); T_ij = np.zeros((B, 4, 4))
         todo_off = np.zeros(nb + 1, dtype=np.int32)
         self._generation += 1
+        if sim_in is not None:
+            sim = _f64(sim_in).reshape(-1).copy()
+            if sim.shape[0] != B:
+                raise ValueError("sim_in must hold pair_off[nb] entries")
+            rc = self._lib.roman_session_gate_sim(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
+                                                  None, nb, _ptr(blocks), _ptr(pair_off), _ptr(tile_off), _ptr(dist), _ptr(flags), _ptr(yaw), None,
+                                                  _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off), _ptr(sim))
+            self._check(rc, "roman_session_gate_sim")
+            return SessionGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, todo_off, pair_off)
         rc = self._lib.roman_session_gate(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
                                           _ptr(desc), nb, _ptr(blocks), _ptr(pair_off), _ptr(tile_off), _ptr(dist), _ptr(flags), _ptr(yaw), _ptr(sim),
                                           _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off))
@@ -711,21 +721,65 @@ class Context:
 
     def session_gate_dev(self, gparams, sub_off, blocks, pair_off, tile_off, sub_off_ptr, blocks_ptr, pair_off_ptr, tile_off_ptr, pos_ptr, T_w_ptr,
                          dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr, pairs_ptr, T_ref_ptr, enable_ptr, todo_off_ptr,
-                         time_ptr=None, desc_ptr=None, pos_gt_ptr=None, has_gt_ptr=None):
+                         time_ptr=None, desc_ptr=None, pos_gt_ptr=None, has_gt_ptr=None, sim_in_ptr=None):
         """Device-pointer pass 1 over a list of robot pairs (roman_session_gate_dev): the tables as host arrays (session_tables();
         the library validates these) AND as device addresses of the same values; every other pointer a device address.  A pure
         enqueue on the context's stream; complete after sync().  pairs_ptr holds GLOBAL submap indices: with frames tabled over
-        all submaps of the session, its two columns are lc_tail_dev's iL and iR."""
+        all submaps of the session, its two columns are lc_tail_dev's iL and iR.  sim_in_ptr: the similarity of every pair is
+        given (roman_session_gate_sim_dev): gparams.desc_dim must be 0, desc_ptr is not read, sim_ptr not written."""
         sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
         pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
         R, nb = len(sub_off) - 1, len(blocks)
         if R < 0 or len(pair_off) != nb + 1 or len(tile_off) != nb + 1:
             raise ValueError("sub_off must hold R + 1 entries, pair_off and tile_off nb + 1")
-        rc = self._lib.roman_session_gate_dev(self._h, C.byref(gparams), R, _vp(sub_off_ptr), _ptr(sub_off), _vp(pos_ptr), _vp(pos_gt_ptr), _vp(has_gt_ptr),
-                                              _vp(T_w_ptr), _vp(time_ptr), _vp(desc_ptr), nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off),
-                                              _vp(tile_off_ptr), _ptr(tile_off), _vp(dist_ptr), _vp(flags_ptr), _vp(yaw_deg_ptr), _vp(sim_ptr), _vp(T_ij_ptr),
-                                              _vp(pairs_ptr), _vp(T_ref_ptr), _vp(enable_ptr), _vp(todo_off_ptr))
-        self._check(rc, "roman_session_gate_dev")
+        args = (self._h, C.byref(gparams), R, _vp(sub_off_ptr), _ptr(sub_off), _vp(pos_ptr), _vp(pos_gt_ptr), _vp(has_gt_ptr),
+                _vp(T_w_ptr), _vp(time_ptr), _vp(desc_ptr), nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off),
+                _vp(tile_off_ptr), _ptr(tile_off), _vp(dist_ptr), _vp(flags_ptr), _vp(yaw_deg_ptr), _vp(sim_ptr), _vp(T_ij_ptr),
+                _vp(pairs_ptr), _vp(T_ref_ptr), _vp(enable_ptr), _vp(todo_off_ptr))
+        if sim_in_ptr is not None:
+            self._check(self._lib.roman_session_gate_sim_dev(*args, _vp(sim_in_ptr)), "roman_session_gate_sim_dev")
+            return
+        self._check(self._lib.roman_session_gate_dev(*args), "roman_session_gate_dev")
+
+    # ------------------------------------------------------------------ the stacked similarity of every block of a session (DESIGN.md §4.15)
+    @staticmethod
+    def _session_stacked_tables(frame_lo, frame_n, mask_off, sub_off, blocks, pair_off):
+        frame_lo = np.ascontiguousarray(frame_lo, dtype=np.int32).reshape(-1); frame_n = np.ascontiguousarray(frame_n, dtype=np.int32).reshape(-1)
+        mask_off = np.ascontiguousarray(mask_off, dtype=np.int64).reshape(-1)
+        sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
+        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1)
+        R, nb = len(sub_off) - 1, len(blocks)
+        if R < 0 or len(pair_off) != nb + 1 or not (len(frame_lo) == len(frame_n) == len(mask_off) == R):
+            raise ValueError("sub_off must hold R + 1 entries, frame_lo, frame_n and mask_off R, pair_off nb + 1")
+        return frame_lo, frame_n, mask_off, sub_off, blocks, pair_off, R, nb
+
+    def session_stacked_sim(self, desc, mask, frame_lo, frame_n, mask_off, sub_off, blocks, pair_off):
+        """Host-pointer stacked similarity of every block of a session (roman_session_stacked_sim): desc (Nf, d) the ONE frame
+        table, mask the uint64 words of all views' frame masks, view r = frames [frame_lo[r], frame_lo[r] + frame_n[r]) with its
+        masks (n_r, ceil(frame_n[r] / 64)) at word mask_off[r]; sub_off, blocks, pair_off as session_tables() gives them.
+        -> sim (pair_off[nb],) float64, block b row-major at pair_off[b]."""
+        desc = _f64(desc)
+        if desc.ndim != 2:
+            raise ValueError("session_stacked_sim needs an (Nf, d) frame table")
+        mask = np.ascontiguousarray(mask, dtype=np.uint64).reshape(-1)
+        frame_lo, frame_n, mask_off, sub_off, blocks, pair_off, R, nb = self._session_stacked_tables(frame_lo, frame_n, mask_off, sub_off, blocks, pair_off)
+        sim = np.zeros(max(int(pair_off[-1]), 0))
+        self._generation += 1
+        rc = self._lib.roman_session_stacked_sim(self._h, desc.shape[1], desc.shape[0], _ptr(desc), _ptr(mask), mask.shape[0], R, _ptr(frame_lo), _ptr(frame_n),
+                                                 _ptr(mask_off), _ptr(sub_off), nb, _ptr(blocks), _ptr(pair_off), _ptr(sim))
+        self._check(rc, "roman_session_stacked_sim")
+        return sim
+
+    def session_stacked_sim_dev(self, d, Nf, desc_ptr, mask_ptr, frame_lo, frame_n, mask_off, sub_off, blocks, pair_off,
+                                frame_lo_ptr, frame_n_ptr, mask_off_ptr, sub_off_ptr, blocks_ptr, pair_off_ptr, sim_ptr):
+        """Device-pointer stacked similarity of every block of a session (roman_session_stacked_sim_dev): the tables as host arrays
+        (the library validates these) AND as device addresses of the same values; desc, mask and sim device addresses.  A pure
+        enqueue on the context's stream: session_gate_dev(..., sim_in_ptr=sim_ptr) behind it reads what it wrote."""
+        frame_lo, frame_n, mask_off, sub_off, blocks, pair_off, R, nb = self._session_stacked_tables(frame_lo, frame_n, mask_off, sub_off, blocks, pair_off)
+        rc = self._lib.roman_session_stacked_sim_dev(self._h, int(d), int(Nf), _vp(desc_ptr), _vp(mask_ptr), R, _vp(frame_lo_ptr), _ptr(frame_lo),
+                                                     _vp(frame_n_ptr), _ptr(frame_n), _vp(mask_off_ptr), _ptr(mask_off), _vp(sub_off_ptr), _ptr(sub_off),
+                                                     nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off), _vp(sim_ptr))
+        self._check(rc, "roman_session_stacked_sim_dev")
 
     # ------------------------------------------------------------------ force-fill submaps, boxes, the bounding-box gate (DESIGN.md §4.12)
     def submaps_fill(self, point_dim, cap, seg_feats, descs, count, src, seg_ids=None, desc_dim=0, want_pool=True):
