@@ -12,7 +12,7 @@
 //     k_upper      every candidate pair kept once, in the row of its endpoint with the smaller POSITION (rank by degree):
 //                  the row's kept candidates as a list of 16-bit live column indices
 //     k_slicegeom  slice widths / bases of the quad layout
-//     k_fill_list  candidate lists -> values, one quad (4 entries per lane = row) at a time, straight into the layout
+//     k_fill_list  candidate lists -> values, one list quad (4 entries) per lane at a time, straight into the layout
 //     k_solve_up   persistent per-problem CLIPPER solve on the upper triangle (pull + push SpMV)
 //   kind 1 (fallback, any L): symmetric sorted SELL-64 in live numbering: k_fill, then k_solve (a workgroup per
 //     problem) or k_solve_wide (cooperative launch: the whole device on one large problem at a time, or teams of compute
@@ -3275,15 +3275,23 @@ __global__ void __launch_bounds__(1024) k_fill(DevParams D, const ProbDesc* __re
 // ---------------------------------------------------------------------------------------------
 // k_fill_list (stream layout): candidates -> values, written straight into the quad layout.  k_upper left every
 // position row's kept candidates as a list of live column indices (ascending, padded to whole quads), so entry e of a
-// row is simply element e of its list.  A wave takes one QUAD of one slice at a time — lane = lane slot = row, 4
-// consecutive entries per lane: one 8-byte list read, four independent evaluation chains (two LDS column lookups, two
-// table gathers, sqrt / exp / cbrt, fusion, affinityeps filter), then one 8-byte column store and two 16-byte value
-// stores that are contiguous over the wave — the layout's own order, no staging image, no barriers inside a work
-// item.  Entries beyond a row's count (slice padding) and filtered entries are written inert (value 0, the lane
-// slot's dummy column with the C-flag).  Work items are groups of consecutive slices of one problem (NG groups per problem): the
-// problem's column tile (objects, z, single score, position of every live association) is staged in LDS once per
-// item, as are the rows of the group (live index, count, list offset); the quads of the group are dealt to the waves
-// round-robin.  Items are ordered so that the groups of one problem run on one XCD (its tables stay in that L2).
+// row is simply element e of its list.  A slice is 64 rows x (longest list, in quads) SLOT quads; a row's list covers
+// only its first slot quads, and at the workload's shapes a third of the (slot quad, row) pairs have no list quad.
+// Only the pairs that have one are evaluated.  Per window of FILL_WIN consecutive slot quads of a work item:
+//   pass 1  lane = row, slot quads dealt to the waves: ballot of the rows whose list reaches the slot quad -> mask, count
+//           and slice of the slot quad in LDS; the other lanes write their slot inert (slice padding: value 0, the lane
+//           slot's dummy column with the C-flag);
+//   scan    one wave: live pairs in front of every slot quad;
+//   pass 2  the live pairs in (slot quad, row) order, 64 consecutive ones per wave step: a lane finds its slot quad in the
+//           prefix table (the wave's first one by bisection, its own by stepping on) and its row as the n-th set bit of
+//           the mask, then: one 8-byte list read, four independent evaluation chains (two LDS column lookups, two table
+//           gathers, sqrt / exp / cbrt, fusion, affinityeps filter), one 8-byte column store and two 16-byte value
+//           stores — the layout's own order, contiguous over the wave wherever the live rows of a slot quad are.
+// Entries beyond a row's count in its last quad and filtered entries are written inert by pass 2.  Every slot is written
+// exactly once, with what the lane = row loop wrote there.  Work items are groups of consecutive slices of one problem (NG
+// groups per problem): the problem's column tile (objects, z, single score, position of every live association) is staged
+// in LDS once per item, as are the rows of the group (live index, count, list offset).  Items are ordered so that the
+// groups of one problem run on one XCD (its tables stay in that L2).
 // ---------------------------------------------------------------------------------------------
 constexpr int FILLS_MAXSPI = STREAM_MAXL / 64;     // slices per work item (group): up to a whole problem
 
@@ -3306,6 +3314,21 @@ __device__ __forceinline__ double fill_value(const DevParams& D, double a, doubl
 }
 
 constexpr uint32_t FILL_ROTATE = 5;      // k_fill_list rotates the list quads of row x by FILL_ROTATE * x (why: at the rotation itself)
+constexpr int FILL_WIN = 256;            // slot quads of a group k_fill_list takes between two barriers (its mask / prefix tables in LDS)
+
+// Index of the n-th set bit (n = 0: the lowest) of the 64-bit mask hi:lo; n < popcount.
+__device__ __forceinline__ uint32_t nth_set_bit(uint32_t lo, uint32_t hi, uint32_t n)
+{
+    uint32_t base = 0, v = lo;
+    const uint32_t c = (uint32_t)__popc(lo);
+    if (n >= c) { n -= c; v = hi; base = 32; }
+#pragma unroll
+    for (int s = 16; s > 0; s >>= 1) {
+        const uint32_t cl = (uint32_t)__popc(v & ((1u << s) - 1u));
+        if (n >= cl) { n -= cl; v >>= s; base += (uint32_t)s; }
+    }
+    return base;
+}
 
 template <bool GRAV, bool FAST, bool OBJ>
 __global__ void __launch_bounds__(1024) k_fill_list(DevParams D, int B, const ProbDesc* __restrict__ probs,
@@ -3321,7 +3344,7 @@ __global__ void __launch_bounds__(1024) k_fill_list(DevParams D, int B, const Pr
                                                     const uint32_t* __restrict__ sliceBase,
                                                     uint16_t* __restrict__ cols, double* __restrict__ vals, int TC, int NG, int SPI /* LDS capacity: slices per group */)
 {
-    // LDS: cS[TC] [OBJ: sO[2*NO] (x, y, z, -) | else GRAV: cZa[TC] cZb[TC]] cI[TC] cJ[TC] | gK gCnt gOff [SPI*64] | gQ[SPI+1] gSB[SPI+1] | cP[TC] (u16)
+    // LDS: cS[TC] [OBJ: sO[2*NO] (x, y, z, -) | else GRAV: cZa[TC] cZb[TC]] cI[TC] cJ[TC] | gK gCnt gOff [SPI*64] | gQ[SPI+1] gSB[SPI+1] | wLo wHi wSl [FILL_WIN] wPre[FILL_WIN+1] | cP[TC] (u16)
     // OBJ: the two distances of an entry are RECOMPUTED from the objects' coordinates (LDS) with k_tables' own operation
     // sequence — the same bits — instead of gathered from the tables: a wave's 64 lanes are 64 different rows, every table
     // gather touched 64 cache lines for 64 doubles (4 GB of L2 -> L1 line traffic per batch of 256 at config 3, the kernel's bound).
@@ -3337,7 +3360,11 @@ __global__ void __launch_bounds__(1024) k_fill_list(DevParams D, int B, const Pr
     uint32_t* gOff = gCnt + SPI * 64;                   //   list offset
     uint32_t* gQ = gOff + SPI * 64;                     // quads in front of every slice of the group (+ total)
     uint32_t* gSB = gQ + SPI + 1;                       // slice bases
-    uint16_t* cP = reinterpret_cast<uint16_t*>(gSB + SPI + 1);
+    uint32_t* wLo = gSB + SPI + 1;                      // window: live-row mask of every slot quad (low, high half)
+    uint32_t* wHi = wLo + FILL_WIN;
+    uint32_t* wSl = wHi + FILL_WIN;                     //   its slice inside the group
+    uint32_t* wPre = wSl + FILL_WIN;                    //   live quads in front of it (+ the total, at [FILL_WIN])
+    uint16_t* cP = reinterpret_cast<uint16_t*>(wPre + FILL_WIN + 1);
     const int tid = threadIdx.x, nt = blockDim.x;
     const int lane = tid & 63, w = tid >> 6, nw = nt >> 6;
     const int nGroups = tot->sliceGroups;
@@ -3393,12 +3420,53 @@ __global__ void __launch_bounds__(1024) k_fill_list(DevParams D, int B, const Pr
         __syncthreads();
         const uint32_t Q = gQ[ns];
         uint32_t upper = 0;
-        int si = 0;
-        for (uint32_t u = (uint32_t)w; u < Q; u += (uint32_t)nw) {
-            while (u >= gQ[si + 1]) ++si;                       // wave-uniform
-            const uint32_t g = u - gQ[si];
+        int si1 = 0;                                            // pass 1's slice (a wave's slot quads only go forward)
+        for (uint32_t u0 = 0; u0 < Q; u0 += (uint32_t)FILL_WIN) {
+            const uint32_t Wn = min((uint32_t)FILL_WIN, Q - u0);
+            if (u0) __syncthreads();                            // every wave is done with the previous window's tables
+            // Pass 1, lane = row, the window's slot quads dealt to the waves: which rows have a list quad for slot quad u
+            // (mask, count); the others' slots are written inert here (slice padding: value 0, the lane slot's dummy column).
+            for (uint32_t ul = (uint32_t)w; ul < Wn; ul += (uint32_t)nw) {
+                const uint32_t u = u0 + ul;
+                while (u >= gQ[si1 + 1]) ++si1;                 // wave-uniform
+                const uint32_t g = u - gQ[si1];
+                const bool live = g < ((gCnt[si1 * 64 + lane] + 3u) >> 2);
+                const unsigned long long m = __ballot(live);
+                if (lane == 0) { wLo[ul] = (uint32_t)m; wHi[ul] = (uint32_t)(m >> 32); wSl[ul] = (uint32_t)si1; wPre[ul] = (uint32_t)__popcll(m); }
+                if (!live) {
+                    const int64_t sb = no + gSB[si1];
+                    const uint32_t inert = ((uint32_t)L + (uint32_t)lane) | 0x8000u, i2 = inert | (inert << 16);
+                    *reinterpret_cast<uint2*>(cols + sb + (int64_t)g * 256 + lane * 4) = make_uint2(i2, i2);
+                    *reinterpret_cast<double2*>(vals + sb + (int64_t)(2 * g) * 128 + lane * 2) = make_double2(0.0, 0.0);
+                    *reinterpret_cast<double2*>(vals + sb + (int64_t)(2 * g + 1) * 128 + lane * 2) = make_double2(0.0, 0.0);
+                }
+            }
+            for (uint32_t ul = Wn + (uint32_t)tid; ul < (uint32_t)FILL_WIN; ul += (uint32_t)nt) wPre[ul] = 0u;
+            __syncthreads();
+            if (w == 0) {                       // counts -> live quads in front of every slot quad, the window's total behind them
+                static_assert(FILL_WIN == 4 * WAVE, "one wave scans the window, four slot quads per lane");
+                uint32_t c[4], s = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { c[j] = wPre[4 * lane + j]; s += c[j]; }
+                uint32_t ex = wave_excl_scan(s, lane);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { wPre[4 * lane + j] = ex; ex += c[j]; }
+                if (lane == WAVE - 1) wPre[FILL_WIN] = ex;
+            }
+            __syncthreads();
+            // Pass 2: the window's live (slot quad, row) pairs, in that order, 64 consecutive ones per wave step.
+            const uint32_t F = wPre[FILL_WIN];
+            for (uint32_t f0 = (uint32_t)uni_i(w) * 64u; f0 < F; f0 += (uint32_t)nt) {
+            uint32_t ul = 0;                                    // wave-uniform: the slot quad of the wave's first pair
+            { uint32_t lo_ = 0, hi_ = Wn - 1u; while (lo_ < hi_) { const uint32_t mid = (lo_ + hi_ + 1u) >> 1; if (wPre[mid] <= f0) lo_ = mid; else hi_ = mid - 1u; } ul = lo_; }
+            const uint32_t f = f0 + (uint32_t)lane;
+            if (f < F) {
+            while (wPre[ul + 1] <= f) ++ul;                     // (every slot quad of a slice has a live row: at most 64 steps; wPre[Wn] = F > f)
+            const int r = (int)nth_set_bit(wLo[ul], wHi[ul], f - wPre[ul]);       // the pair's row: lane slot r of its slice
+            const int si = (int)wSl[ul];
+            const uint32_t g = u0 + ul - gQ[si];
             const int64_t sb = no + gSB[si];                    // first element of the slice (multiple of 256)
-            const int x = si * 64 + lane;
+            const int x = si * 64 + r;
             const uint32_t kraw = gK[x], cnt = gCnt[x];
             // Which list quad goes into slot quad g: the row's quads ROTATED by a row-dependent offset.  The order of a row's
             // entries is free (the solver's sums are exact), and the 64 rows of a slice — lanes of one wave — hold much the same
@@ -3407,19 +3475,17 @@ __global__ void __launch_bounds__(1024) k_fill_list(DevParams D, int B, const Pr
             // Measured (round 4, two boxes, alternating): solver launch in flight 1.41-1.45 -> 1.36-1.37 ms, p50 0.665-0.674 -> 0.640 ms,
             // throughput +0.5-1.5 %, isolated solver launch 1.09-1.11 -> 1.02-1.03 ms.  Starting lane l at l/64 of its row instead, with or
             // without a further rotation inside the quad: 1.04-1.06 ms, p50 0.64-0.65 (same boxes, alternating): the plain one stays.
-            const uint32_t nq = (cnt + 3u) >> 2;
-            uint32_t e0 = g << 2;
-            if (g < nq) e0 = ((g + (uint32_t)x * FILL_ROTATE) % nq) << 2;
-            uint2 qq = make_uint2(0u, 0u);
-            if (e0 < cnt) qq = *reinterpret_cast<const uint2*>(lists + gOff[x] + e0);
-            const int k = (kraw == 0xffffffffu) ? 0 : (int)kraw;
+            const uint32_t nq = (cnt + 3u) >> 2;                // > g: the pair is live
+            const uint32_t e0 = ((g + (uint32_t)x * FILL_ROTATE) % nq) << 2;
+            const uint2 qq = *reinterpret_cast<const uint2*>(lists + gOff[x] + e0);
+            const int k = (int)kraw;
             const double sk = cS[k];
             const double* TAr = TA + (int64_t)cI[k] * pd.n1;
             const double* TBr = TB + (int64_t)cJ[k] * pd.n2;
             const double zak = (GRAV && !OBJ) ? cZa[k] : 0.0, zbk = (GRAV && !OBJ) ? cZb[k] : 0.0;
             dbl2_t oa0 = {0.0, 0.0}, oa1 = {0.0, 0.0}, ob0 = {0.0, 0.0}, ob1 = {0.0, 0.0};
             if (OBJ) { oa0 = sO[2 * cI[k]]; oa1 = sO[2 * cI[k] + 1]; ob0 = sO[2 * (NO + cJ[k])]; ob1 = sO[2 * (NO + cJ[k]) + 1]; }
-            const uint32_t inert = ((uint32_t)L + (uint32_t)lane) | 0x8000u;     // the lane slot's own dummy column
+            const uint32_t inert = ((uint32_t)L + (uint32_t)r) | 0x8000u;        // the lane slot's own dummy column
             uint32_t cw[4]; double vv[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -3446,9 +3512,11 @@ __global__ void __launch_bounds__(1024) k_fill_list(DevParams D, int B, const Pr
                 vv[j] = keep ? v : 0.0;
                 upper += keep ? 1u : 0u;                        // every stored entry is kept once: a strict-upper one
             }
-            *reinterpret_cast<uint2*>(cols + sb + (int64_t)g * 256 + lane * 4) = make_uint2(cw[0] | (cw[1] << 16), cw[2] | (cw[3] << 16));
-            *reinterpret_cast<double2*>(vals + sb + (int64_t)(2 * g) * 128 + lane * 2) = make_double2(vv[0], vv[1]);
-            *reinterpret_cast<double2*>(vals + sb + (int64_t)(2 * g + 1) * 128 + lane * 2) = make_double2(vv[2], vv[3]);
+            *reinterpret_cast<uint2*>(cols + sb + (int64_t)g * 256 + r * 4) = make_uint2(cw[0] | (cw[1] << 16), cw[2] | (cw[3] << 16));
+            *reinterpret_cast<double2*>(vals + sb + (int64_t)(2 * g) * 128 + r * 2) = make_double2(vv[0], vv[1]);
+            *reinterpret_cast<double2*>(vals + sb + (int64_t)(2 * g + 1) * 128 + r * 2) = make_double2(vv[2], vv[3]);
+            }
+            }
         }
         for (int off = 32; off > 0; off >>= 1) upper += __shfl_xor(upper, off);
         if (lane == 0 && upper) atomicAdd(&st[b].nnzUpper, (unsigned long long)upper);

@@ -915,7 +915,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
         // the objects' coordinates in LDS (32 bytes per object) instead of the z columns, when they fit: the fill then
         // recomputes the distances instead of gathering them from the tables
         const int NO = (std::max(maxN, 1) + 1) & ~1;
-        const size_t groupLds = sizeof(uint32_t) * (size_t)(3 * SPI * 64 + 2 * (SPI + 1) + 2);
+        const size_t groupLds = sizeof(uint32_t) * (size_t)(3 * SPI * 64 + 2 * (SPI + 1) + 4 * FILL_WIN + 1 + 2);    // (+ the window's mask / slice / prefix tables)
         const bool obj = (size_t)TCs * (16 + 2) + (size_t)64 * NO + groupLds <= c->lds_max;
         const size_t sliceLds = obj ? (size_t)TCs * (16 + 2) + (size_t)64 * NO + groupLds : (size_t)TCs * (colBytesF + 2) + groupLds;
         if (sliceLds > c->lds_max) return fail(c, ROMAN_E_TOO_LARGE, "internal: stream column tile does not fit the LDS");
