@@ -1075,7 +1075,8 @@ ROMAN_API int roman_grid_gate_aabb(roman_ctx_t* ctx, const roman_grid_gate_param
  * nb == 0 or no pair at all (robots without submaps): ROMAN_OK, todo_off all 0, nothing else written.  Errors: a NULL pointer that
  * is needed, R < 0, nb < 0, r outside [0, R), sub_off decreasing or not starting at 0, a reserved word not 0, a NaN radius,
  * desc_dim < 0, a robot pair listed twice, pair_off / tile_off that disagree with sub_off and blocks -> ROMAN_E_INVALID;
- * radius < 0 -> ROMAN_E_UNSUPPORTED; pair_off[nb] * 16 beyond int32 -> ROMAN_E_TOO_LARGE.
+ * radius < 0 -> ROMAN_E_UNSUPPORTED (the gate without a radius is roman_session_gate_aabb_dev below); pair_off[nb] * 16 beyond int32
+ * -> ROMAN_E_TOO_LARGE.
  */
 ROMAN_API int roman_session_gate_dev(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
                                      const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
@@ -1158,6 +1159,58 @@ ROMAN_API int roman_session_stacked_sim_dev(roman_ctx_t* ctx, int32_t d, int32_t
 ROMAN_API int roman_session_stacked_sim(roman_ctx_t* ctx, int32_t d, int32_t Nf, const double* desc, const uint64_t* mask, int64_t mask_words,
                                         int32_t R, const int32_t* frame_lo, const int32_t* frame_n, const int64_t* mask_off, const int32_t* sub_off,
                                         int32_t nb, const int32_t* blocks, const int64_t* pair_off, double* sim);
+
+/*
+ * roman_session_boxes_dev: roman_submap_boxes_dev — what aabb_intersects [REF roman/utils.py:160-169] reads of
+ * Submap.segments_as_global_points [REF roman/map/map.py:133-139] — over the submap table of a whole session instead of one pool's
+ * slots.  Every pointer DEVICE; a PURE ENQUEUE on the context's stream; one launch, no launch per robot, no gather of rows.
+ *   S          global submaps: the submaps of every VIEW of the session (§4.14), sub_off[R] of roman_session_gate_dev
+ *   pool       float64[.][F], F >= 3: ONE pool, the concatenated pools the batch reads; only the first three columns are read
+ *   row0       int64[S], count int32[S]: submap g holds the rows [row0[g], row0[g] + count[g]) of pool.  Ranges, not prefixes: in
+ *              any order, and two views of one robot name the SAME rows with their own transform — everything but box is read-only.
+ *              The device call trusts both; the host call refuses a negative entry (ROMAN_E_INVALID) and copies the rows they name
+ *   T_odom_center  float64[S][16] row-major 4x4: the pose that takes submap g to the global frame (ground truth or not, as has_gt
+ *              does [REF roman/map/map.py:138]: the caller resolves that)
+ *   box        float64[S][6] = (min x, min y, min z, max x, max y, max z), each component ((r0 x + r1 y) + r2 z) + t without fused
+ *              multiply-adds: for any submap BIT FOR BIT what roman_submap_boxes_dev writes for the same rows and the same
+ *              transform.  count[g] == 0: (+inf, +inf, +inf, -inf, -inf, -inf).  No atomics: two calls agree bit for bit
+ * Inputs must be finite.  S == 0: ROMAN_OK, nothing written.  Errors: S < 0, F < 3, a NULL pointer that is needed -> ROMAN_E_INVALID.
+ */
+ROMAN_API int roman_session_boxes_dev(roman_ctx_t* ctx, int32_t S, int32_t F, const double* pool, const int64_t* row0, const int32_t* count,
+                                      const double* T_odom_center, double* box);
+
+/* The same with HOST pointers everywhere.  Synchronous; `pool` is read up to the last row a submap names. */
+ROMAN_API int roman_session_boxes(roman_ctx_t* ctx, int32_t S, int32_t F, const double* pool, const int64_t* row0, const int32_t* count,
+                                  const double* T_odom_center, double* box);
+
+/*
+ * roman_session_gate_aabb_dev: roman_session_gate_dev with the bounding-box gate [REF roman/align/submap_align.py:101-103]
+ * — what roman_grid_gate_aabb_dev is to roman_grid_gate_dev.  The arguments are roman_session_gate_dev's; then
+ *   box        float64[S][6] over ALL submaps of the session, as roman_session_boxes_dev wrote them.  NEARBY is the six comparisons
+ *              of [REF roman/utils.py:167-169] on box[gi] and box[gj], <= and >= as they stand: touching boxes intersect, an empty
+ *              submap's box intersects nothing.  gparams->radius is NOT read (any value, NaN included)
+ *   sim_in     float64[pair_off[nb]] or NULL.  Given: the similarity of every pair is already there (roman_session_stacked_sim_dev's),
+ *              read as roman_session_gate_sim_dev reads it and never written; gparams->desc_dim must then be 0 (ROMAN_E_INVALID
+ *              otherwise), `desc` is not read and `sim` is not written (both may be NULL)
+ * Per block every output is bit for bit what roman_grid_gate_aabb_dev writes for the block's two sides (pairs after re-basing).
+ * Everything else is roman_session_gate_dev's contract: the tables and their validation, the compact list by a prefix sum (no
+ * atomics), todo_off, the slots beyond todo_off[nb] untouched, the errors — without those of the radius, plus box NULL while a
+ * pair exists -> ROMAN_E_INVALID.
+ */
+ROMAN_API int roman_session_gate_aabb_dev(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
+                                          const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                          int32_t nb, const int32_t* blocks, const int32_t* blocks_host,
+                                          const int64_t* pair_off, const int64_t* pair_off_host, const int64_t* tile_off, const int64_t* tile_off_host,
+                                          double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                          int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* box, const double* sim_in);
+
+/* The same with HOST pointers everywhere (each table once).  Synchronous; box and sim_in go up and are not brought back (sim comes
+   back only without sim_in).  The caller's pairs, T_ref and enable go up first: the slots beyond todo_off[nb] come back as they were. */
+ROMAN_API int roman_session_gate_aabb(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                                      const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                      int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                                      double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                      int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* box, const double* sim_in);
 
 /* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */

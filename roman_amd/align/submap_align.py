@@ -937,12 +937,28 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     robot has; roman_session_stacked_sim_dev writes the similarity of every pair of every block and roman_session_gate_sim_dev
     behind it, on the same stream, gates on it.  similarity_mat per block is what the device computed.
 
-    Not covered — ValueError before any context is made; submap_align_pools per robot pair is the way: force_fill_submaps / no
-    submap_radius, a RansacReg, a plugin with a host prefilter, pools of different row width or descriptor length, pools not
-    built with the frame-descriptor mode asked for, a self block over a pool without ids_dev, and whatever submap_align_pools
-    refuses for a pool.  Three refusals ask the context itself and so come after it exists, as in submap_align_pools: a context
-    without roman_session_gate_dev, one without roman_session_stacked_sim_dev for stacked descriptors, and one without
-    roman_shared_reduce_dev when the list holds a self block."""
+    force_fill_submaps / no submap_radius: the gate is aabb_intersects over segments_as_global_points
+    [REF roman/align/submap_align.py:101-103].  ONE roman_session_boxes_dev reduces every submap of every view to its box, straight
+    from the concatenated pools the batch reads anyway (rows by offset and count, a view's own T_odom_center — the ground-truth
+    pose where gt_poses[r] is given); roman_session_gate_aabb_dev is the gate, behind roman_session_stacked_sim_dev for stacked
+    descriptors — all on the context's stream, with the one synchronisation of the radius mode.  Pools built by
+    build_submap_pool(fill=...) and radius-mode pools are served alike, in one session too.
+
+    A RansacReg (method='ransac'): pass 1 and the shared-segment removal of the self blocks unchanged, then
+    the problems of ALL blocks through one `_ransac_lc_over_pool` (roman_ransac_lc_batch_dev and the tail, chunked by
+    RANSAC_ASSOC_CHUNK_BYTES) in place of issue_chunked, join and the tail.  The seed is one per batch and a problem's result does
+    not depend on its place in it: every block equals submap_align_pools with the same registration.  Both together work too.
+
+    Not covered — ValueError before any context is made; submap_align_pools per robot pair is the way: a plugin with a host
+    prefilter, pools of different row width or descriptor length, pools not built with the frame-descriptor mode asked for, a self
+    block over a pool without ids_dev, and whatever submap_align_pools refuses for a pool — for a RansacReg its four (pools of
+    dim 2, a `cap` above ROMAN_RANSAC_MAX_OBJECTS, host-tensor pools while the registration has no context set, a context without
+    roman_ransac_lc_batch_dev), in its order.  The bounding-box gate over host-tensor pools while the registration has no context
+    set is refused there as well: there is no device the rows could be reduced on.  The other refusals ask the context itself and
+    so come after it exists, as in submap_align_pools: a context without roman_session_gate_dev, one without
+    roman_session_stacked_sim_dev for stacked descriptors, one without roman_shared_reduce_dev when the list holds a self block,
+    and for the bounding-box gate a context without roman_session_boxes_dev / roman_session_gate_aabb_dev, or pools of dim 2
+    (their rows hold no z)."""
     import torch
     from ..runtime import session_tables
     from .pipeline import issue_chunked
@@ -957,10 +973,21 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         raise ValueError("gt_poses must hold one entry per pool" + way)
     if any(not (0 <= r < R and 0 <= s < R) for r, s in blocks) or len(set(blocks)) != len(blocks):
         raise ValueError("robot_pairs must name pools by index, each pair once" + way)
-    if isinstance(registration, RansacReg):
-        raise ValueError("a RansacReg does not go through the batched solver" + way)
-    if sm_params.force_fill_submaps or sm_params.submap_radius is None:
-        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes" + way)
+    ransac = isinstance(registration, RansacReg)
+    no_device = getattr(registration, "_ctx", None) is None and any(q.pool.device.type == "cpu" for q in p)
+    if ransac and R:                                         # (submap_align_pools' four, in its order: in front of everything that makes a HIP context)
+        if any(int(q.table.point_dim) != 3 for q in p):
+            raise ValueError("RansacReg reads x y z from columns 0-2 of a pool row, and pools of dim 2 hold no z" + way)
+        if any(int(q.cap) > _abi.ROMAN_RANSAC_MAX_OBJECTS for q in p):
+            raise ValueError(f"RansacReg serves at most {_abi.ROMAN_RANSAC_MAX_OBJECTS} objects per submap (the pools' cap is larger)" + way)
+        if no_device:
+            raise ValueError("RansacReg has no context set and the pools are host tensors: no device to run on" + way)
+        if not hasattr(registration._context(), "ransac_lc_batch_dev"):
+            raise ValueError("the context has no roman_ransac_lc_batch_dev" + way)
+    aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
+    if aabb_mode and no_device:                              # (the boxes are reduced from the resident rows: as for a RansacReg, host rows need a context of the caller's)
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes of the resident rows: the registration has no context set "
+                         "and the pools are host tensors: no device to run on" + way)
     mode = sm_params.submap_descriptor
     stacked = mode == 'stacked_frame_descriptors'
     if mode not in (None, 'mean_semantic', 'mean_frame_descriptor', 'stacked_frame_descriptors'):
@@ -997,10 +1024,10 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         reads = sorted({int(counts[s if a == r else a]) for a, s in blocks if r in (a, s)})
         mine = []
         live_reads = [n for n in reads if n > 0] if counts[r] else []       # (an empty block: the robot only needs a place in the tables)
-        all_ = _pool_side_host(p[r], gt_poses[r], gt_poses[r] is not None, live_reads, False) if live_reads else None
+        all_ = _pool_side_host(p[r], gt_poses[r], gt_poses[r] is not None, live_reads, aabb_mode) if live_reads else None
         for k, n in enumerate(live_reads):
             hs = dict(all_, T_w=[all_["T_w"][k]], frames=all_["frames"][k])
-            key = hs["T_w"][0].tobytes() + hs["frames"][0].tobytes() + hs["frames"][1].tobytes()
+            key = hs["T_w"][0].tobytes() + hs["frames"][0].tobytes() + hs["frames"][1].tobytes() + (hs["T_oc"].tobytes() if aabb_mode else b"")
             same = [v for v, kk in mine if kk == key]
             if not same:
                 views.append((r, hs)); mine.append((len(views) - 1, key))
@@ -1032,6 +1059,11 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         raise ValueError("the context has no roman_session_gate_dev" + way)
     if stacked and not hasattr(ctx, "session_stacked_sim_dev"):
         raise ValueError("the context has no roman_session_stacked_sim_dev" + way)
+    if aabb_mode and not (hasattr(ctx, "session_boxes_dev") and hasattr(ctx, "session_gate_aabb_dev")):
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes: the context has no roman_session_boxes_dev / "
+                         "roman_session_gate_aabb_dev" + way)
+    if aabb_mode and any(int(q.table.point_dim) != 3 for q in p):
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes, and pools of dim 2: their rows hold no z" + way)
     dev = p[0].pool.device
     on_host = dev.type == "cpu"                              # CPU tensors + a stand-in context (tests)
     wait_torch = (lambda: None) if on_host else (lambda: torch.cuda.current_stream(dev).synchronize())
@@ -1065,8 +1097,23 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         mask_off = np.array([mof.get(r, 0) for r, _ in views], dtype=np.int64)
         t.update(frame_lo=up(frame_lo), frame_n=up(frame_n), mask_off=up(mask_off))
 
+    def concatenated():
+        """ONE pool for the session — every live robot's rows once, whatever the number of its views — and per GLOBAL submap index
+        (the gate's, as sub_off orders them) its first row and its rows -> (pool, sm_row int64, sm_cnt int32)."""
+        live = sorted({r for r, _ in lv})
+        pool = p[live[0]].pool if len(live) == 1 else torch.cat([p[r].pool for r in live], dim=0)
+        row0 = dict(zip(live, np.concatenate([[0], np.cumsum([int(p[r].pool.shape[0]) for r in live])]).astype(np.int64).tolist()))
+        return (pool, np.concatenate([row0[r] + p[r].offsets()[0] for r, _ in lv]).astype(np.int64),
+                np.concatenate([p[r].offsets()[1] for r, _ in lv]).astype(np.int32))
+
     # ---- pass 1 of all blocks on the device: one enqueue, one synchronisation, one read-back ----
     f64, i32 = torch.float64, torch.int32
+    if aabb_mode:
+        # the boxes of every submap of every view from the concatenated pools the batch reads anyway: rows by offset and count, no
+        # gather into slots; a view's own T_odom_center (two views of a robot: the same rows, two box sets)
+        pool, sm_row, sm_cnt = concatenated()
+        t.update(row0=up(sm_row), count=up(sm_cnt), T_oc=up(cat(lambda hs: hs["T_oc"], (16,))),
+                 box=torch.empty((len(sm_cnt), 6), dtype=f64, device=dev))
     g = dict(dist=torch.empty(total, dtype=f64, device=dev), flags=torch.empty(total, dtype=i32, device=dev), yaw=torch.empty(total, dtype=f64, device=dev),
              sim=torch.empty(total, dtype=f64, device=dev), T_ij=torch.empty((total, 16), dtype=f64, device=dev),
              pairs=torch.empty((total, 2), dtype=i32, device=dev), T_ref=torch.empty((total, 16), dtype=f64, device=dev),
@@ -1075,15 +1122,20 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
                           False, sm_params.single_robot_lc_time_thresh)
     gate_kw = dict(time_ptr=ptr(t["time"]), desc_ptr=ptr(t["desc"]), pos_gt_ptr=ptr(t["gt"]), has_gt_ptr=ptr(t["has"]))
     wait_torch()                                             # the uploads are in place before the library's stream reads them
+    if aabb_mode:
+        ctx.session_boxes_dev(len(sm_cnt), int(pool.shape[1]), pool.data_ptr(), ptr(t["row0"]), ptr(t["count"]), ptr(t["T_oc"]), ptr(t["box"]))
     if stacked:                                              # similarity first, then the gate that reads it: both on the context's stream
         gp.desc_thresh = float(sm_params.submap_descriptor_thresh)
         ctx.session_stacked_sim_dev(int(fdesc.shape[1]), int(fdesc.shape[0]), ptr(fdesc), ptr(fmask), frame_lo, frame_n, mask_off, sub_off, blk, pair_off,
                                     ptr(t["frame_lo"]), ptr(t["frame_n"]), ptr(t["mask_off"]), ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]),
                                     g["sim"].data_ptr())
         gate_kw["sim_in_ptr"] = g["sim"].data_ptr()
-    ctx.session_gate_dev(gp, sub_off, blk, pair_off, tile_off, ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]), ptr(t["tile_off"]),
-                         ptr(t["pos"]), ptr(t["T_w"]), *[g[k].data_ptr() for k in ("dist", "flags", "yaw", "sim", "T_ij", "pairs", "T_ref", "enable", "todo_off")],
-                         **gate_kw)
+    gate_args = (gp, sub_off, blk, pair_off, tile_off, ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]), ptr(t["tile_off"]), ptr(t["pos"]), ptr(t["T_w"]),
+                 *[g[k].data_ptr() for k in ("dist", "flags", "yaw", "sim", "T_ij", "pairs", "T_ref", "enable", "todo_off")])
+    if aabb_mode:
+        ctx.session_gate_aabb_dev(*gate_args, ptr(t["box"]), **gate_kw)
+    else:
+        ctx.session_gate_dev(*gate_args, **gate_kw)
     ctx.sync()
     todo_off = g["todo_off"].cpu().numpy().astype(np.int64)
     B = int(todo_off[-1])
@@ -1105,11 +1157,9 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         return {blocks[b]: result_of(b, Ms[b], edges=Ms[b].empty_edges()) for b in range(nb)}
 
     # ---- ONE batch over the concatenated pools: offsets and counts per global submap, the problems in compact order ----
-    live = sorted({r for r, _ in lv})                        # every robot's rows once, whatever the number of its views
-    pool = p[live[0]].pool if len(live) == 1 else torch.cat([p[r].pool for r in live], dim=0)
-    row0 = dict(zip(live, np.concatenate([[0], np.cumsum([int(p[r].pool.shape[0]) for r in live])]).astype(np.int64).tolist()))
-    sm_row = np.concatenate([row0[r] + p[r].offsets()[0] for r, _ in lv])       # per GLOBAL submap index (the gate's), as sub_off orders them
-    sm_cnt = np.concatenate([p[r].offsets()[1] for r, _ in lv]).astype(np.int32)
+    live = sorted({r for r, _ in lv})
+    if not aabb_mode:
+        pool, sm_row, sm_cnt = concatenated()
     rows, F = int(pool.shape[0]), int(pool.shape[1])
     off1, n1_, off2, n2_ = sm_row[gpairs[:, 0]], sm_cnt[gpairs[:, 0]], sm_row[gpairs[:, 1]], sm_cnt[gpairs[:, 1]]
     kmax = int(max(1, np.max(np.minimum(n1_, n2_))))         # (of the unreduced sizes: still a bound after the removal)
@@ -1133,20 +1183,25 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         pool, rows = work, rows + n_slots
     batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), (rows, F)), off1.astype(np.int64), n1_.astype(np.int32), off2.astype(np.int64), n2_.astype(np.int32),
                            pair_index=gpairs)
-    o = _TailBuffers(torch, dev, B, kmax)
+    o = _TailBuffers(torch, dev, B, 0 if ransac else kmax)   # (a RansacReg keeps its association rows in a buffer of its own)
     FL, FR = up(FLh), up(FRh)
     iL, iR = g["pairs"][:B, 0].contiguous(), g["pairs"][:B, 1].contiguous()
     lp = _lc_inputs(sm_params, sm_io, registration).params()
     wait_torch()                                             # the pool (torch.cat), the cleared outputs and the frames are in place
     t0 = time.time()
-    status = issue_chunked(ctx, registration._abi_params(), pool, batch, kmax, o.assoc, o.n, o.T, o.status)
-    ctx.join()                                               # the tail below sees the FINAL attempt of every problem only
-    ctx.lc_tail_dev(lp, B, o.T.data_ptr(), o.n.data_ptr(), o.status.data_ptr(), o.records.data_ptr(), o.acc_idx.data_ptr(), o.acc_n.data_ptr(),
-                    T_ref_ptr=g["T_ref"].data_ptr(), enable_ptr=g["enable"].data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
-                    FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr())
-    ctx.sync()
+    tail_ptrs = dict(T_ref_ptr=g["T_ref"].data_ptr(), enable_ptr=g["enable"].data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
+                     FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr())
+    if ransac:
+        # k_ransac over the rows as they are and the tail behind it, for the problems of ALL blocks: the seed
+        # is one per batch and a problem's draws do not depend on its place in it, so a block equals its own submap_align_pools
+        res = _ransac_lc_over_pool(torch, ctx, registration, pool, batch, lp, o, tail_ptrs, wait_torch)
+    else:
+        status = issue_chunked(ctx, registration._abi_params(), pool, batch, kmax, o.assoc, o.n, o.T, o.status)
+        ctx.join()                                           # the tail below sees the FINAL attempt of every problem only
+        ctx.lc_tail_dev(lp, B, o.T.data_ptr(), o.n.data_ptr(), o.status.data_ptr(), o.records.data_ptr(), o.acc_idx.data_ptr(), o.acc_n.data_ptr(), **tail_ptrs)
+        ctx.sync()
+        res = o.result(status, sm_params.dim)
     per_pair = (time.time() - t0) / B
-    res = o.result(status, sm_params.dim)
 
     # ---- the records and the accepted list split by todo_off, per block with block-local indices ----
     out = {}

@@ -7536,16 +7536,12 @@ __global__ void __launch_bounds__(256) k_submap_desc(int cap, int F, int d, cons
 // T_odom_center — each component ((r0 x + r1 y) + r2 z) + t, k_submap_gather's arithmetic — and reduces them to
 // box[s] = (min x, min y, min z, max x, max y, max z).  Rows beyond 64 are taken in further steps of the same wave; min and max of
 // finite doubles are exact and order-free, so the butterfly's order is free.  An empty submap: (+inf x 3, -inf x 3), never nearby.
-__global__ void __launch_bounds__(256) k_submap_boxes(int S, int F, int cap, const double* __restrict__ pool, const int32_t* __restrict__ count,
-                                                      const double* __restrict__ T_odom_center, double* __restrict__ box)
+// (the wave's work in k_submap_boxes and k_session_boxes: `rows` the submap's first row, `n` its rows, `T` its pose, `out` its box)
+__device__ __forceinline__ void box_of_rows(const double* __restrict__ rows, int n, int F, const double* __restrict__ T, double* __restrict__ out, int lane)
 {
-    const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= S) return;                                          // (wave-uniform)
-    const double* T = T_odom_center + 16 * (int64_t)s;
-    const int n = max(0, min(count[s], cap));                    // (a count outside its slot reads nothing beyond it)
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int r = lane; r < n; r += 64) {
-        const double* p = pool + ((int64_t)s * cap + r) * F;
+        const double* p = rows + (int64_t)r * F;
         const double x = p[0], y = p[1], z = p[2];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -7559,8 +7555,30 @@ __global__ void __launch_bounds__(256) k_submap_boxes(int S, int F, int cap, con
         for (int off = 32; off >= 1; off >>= 1) { lo[c] = fmin(lo[c], __shfl_xor(lo[c], off)); hi[c] = fmax(hi[c], __shfl_xor(hi[c], off)); }
     if (lane < 3) {
         const double l = lane == 0 ? lo[0] : (lane == 1 ? lo[1] : lo[2]), h = lane == 0 ? hi[0] : (lane == 1 ? hi[1] : hi[2]);
-        box[6 * (int64_t)s + lane] = l; box[6 * (int64_t)s + 3 + lane] = h;
+        out[lane] = l; out[3 + lane] = h;
     }
+}
+
+__global__ void __launch_bounds__(256) k_submap_boxes(int S, int F, int cap, const double* __restrict__ pool, const int32_t* __restrict__ count,
+                                                      const double* __restrict__ T_odom_center, double* __restrict__ box)
+{
+    const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= S) return;                                          // (wave-uniform)
+    const int n = max(0, min(count[s], cap));                    // (a count outside its slot reads nothing beyond it)
+    box_of_rows(pool + (int64_t)s * cap * F, n, F, T_odom_center + 16 * (int64_t)s, box + 6 * (int64_t)s, lane);
+}
+
+// The same over the submap table of a SESSION (roman_session_boxes*): one wave per global submap g — a submap of a
+// view (§4.14) — whose rows are [row0[g], row0[g] + count[g]) of the ONE concatenated pool the batch reads anyway: no launch per
+// robot, no gather of the rows into slots.  Two views of one robot name the same rows with their own T_odom_center; everything but
+// `box` is read-only.  Latency-bound (one strided row read per lane: three columns of a row of F doubles); not measured at session
+// scale beyond DESIGN.md §6.16.
+__global__ void __launch_bounds__(256) k_session_boxes(int S, int F, const double* __restrict__ pool, const int64_t* __restrict__ row0,
+                                                       const int32_t* __restrict__ count, const double* __restrict__ T_odom_center, double* __restrict__ box)
+{
+    const int lane = threadIdx.x & 63, g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= S) return;                                          // (wave-uniform)
+    box_of_rows(pool + row0[g] * F, max(0, count[g]), F, T_odom_center + 16 * (int64_t)g, box + 6 * (int64_t)g, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -7742,10 +7760,10 @@ __device__ __forceinline__ int session_find(const int32_t* __restrict__ off, int
     return lo;
 }
 
-// SIM_IN (roman_session_gate_sim*): the similarity of every pair is already in out.sim — read, never written — and no descriptor is touched
-template <bool SIM_IN>
-__global__ void __launch_bounds__(256) k_session_gate(roman_grid_gate_params_t P, SessionTab tab, int64_t tiles, GridSide s,
-                                                      const double* __restrict__ norm, GridOut out)
+// a wave of k_session_gate — SIM_IN and AABB as grid_pair has them
+template <bool SIM_IN, bool AABB>
+__device__ __forceinline__ void session_gate_wave(roman_grid_gate_params_t P, SessionTab tab, int64_t tiles, GridSide s,
+                                                  const double* __restrict__ norm, GridOut out)
 {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -7781,7 +7799,24 @@ __global__ void __launch_bounds__(256) k_session_gate(roman_grid_gate_params_t P
     const int64_t gi = base0 + i, gj = base1 + j;
     const bool gt = s.pos_gt != nullptr && tab.has_gt[r0] != 0 && tab.has_gt[r1] != 0;      // [REF :96-99]
     const double np_ = (!SIM_IN && d > 0) ? norm[gi] * norm[gj] : 0.0;
-    grid_pair<SIM_IN, false>(P, s, s, gi, gj, gt, d, dot, np_, tab.pair_off[b] + (int64_t)i * n1 + j, out);
+    grid_pair<SIM_IN, AABB>(P, s, s, gi, gj, gt, d, dot, np_, tab.pair_off[b] + (int64_t)i * n1 + j, out);
+}
+
+// SIM_IN (roman_session_gate_sim*): the similarity of every pair is already in out.sim — read, never written — and no descriptor is touched
+template <bool SIM_IN>
+__global__ void __launch_bounds__(256) k_session_gate(roman_grid_gate_params_t P, SessionTab tab, int64_t tiles, GridSide s,
+                                                      const double* __restrict__ norm, GridOut out)
+{
+    session_gate_wave<SIM_IN, false>(P, tab, tiles, s, norm, out);
+}
+
+// the second switch k_grid_gate has, as an overload: k_session_gate<SIM_IN> above keeps its name and its launches.  AABB
+// (roman_session_gate_aabb*): NEARBY from s.box[gi] and s.box[gj] (k_session_boxes), P.radius is not read
+template <bool SIM_IN, bool AABB>
+__global__ void __launch_bounds__(256) k_session_gate(roman_grid_gate_params_t P, SessionTab tab, int64_t tiles, GridSide s,
+                                                      const double* __restrict__ norm, GridOut out)
+{
+    session_gate_wave<SIM_IN, AABB>(P, tab, tiles, s, norm, out);
 }
 
 // the TODO flags of this workgroup's SESSION_SCAN pairs: -> (is flag g TODO, TODO flags of the workgroup in front of g, their number in the workgroup)

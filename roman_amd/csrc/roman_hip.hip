@@ -2887,6 +2887,57 @@ int roman_submap_boxes(roman_ctx_t* c, int32_t S, int32_t F, int32_t cap, const 
     return m.download();
 }
 
+// --- the boxes of every submap of a session over the concatenated pools ------------------------------------------
+static int session_boxes_check(roman_ctx* c, int32_t S, int32_t F, const void* pool, const void* row0, const void* count, const void* T_odom_center, const void* box)
+{
+    if (S < 0) return fail(c, ROMAN_E_INVALID, "S < 0");
+    if (F < 3) return fail(c, ROMAN_E_INVALID, "F=%d: a pool row starts with x y z", F);
+    if (S == 0) return ROMAN_OK;
+    if (!pool || !row0 || !count || !T_odom_center || !box) return fail(c, ROMAN_E_INVALID, "NULL pool, row0, count, T_odom_center or box pointer");
+    return ROMAN_OK;
+}
+
+int roman_session_boxes_dev(roman_ctx_t* c, int32_t S, int32_t F, const double* pool, const int64_t* row0, const int32_t* count,
+                            const double* T_odom_center, double* box)
+{
+    int rc = session_boxes_check(c, S, F, pool, row0, count, T_odom_center, box);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (S == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_session_boxes, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, c->stream, (int)S, (int)F, pool, row0, count, T_odom_center, box);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_session_boxes(roman_ctx_t* c, int32_t S, int32_t F, const double* pool, const int64_t* row0, const int32_t* count,
+                        const double* T_odom_center, double* box)
+{
+    int rc = session_boxes_check(c, S, F, pool, row0, count, T_odom_center, box);
+    if (rc) return rc;
+    int64_t rows = 0;                                            // the rows of `pool` the submaps name: what goes up
+    for (int g = 0; g < S; ++g) {
+        if (count[g] < 0 || row0[g] < 0) return fail(c, ROMAN_E_INVALID, "submap %d: row0=%lld, count=%d must not be negative", g, (long long)row0[g], count[g]);
+        if (count[g] > 0) rows = std::max(rows, row0[g] + (int64_t)count[g]);
+    }
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (S == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    HostMirror m(c);
+    const auto dPool = m.in(pool, sizeof(double) * (size_t)rows * (size_t)F);
+    const auto dRow = m.in(row0, sizeof(int64_t) * (size_t)S);
+    const auto cnt = m.in(count, sizeof(int32_t) * (size_t)S);
+    const auto T = m.in(T_odom_center, sizeof(double) * 16 * (size_t)S);
+    const auto dBox = m.out(box, sizeof(double) * 6 * (size_t)S);
+    rc = m.upload();
+    if (rc) return rc;
+    rc = roman_session_boxes_dev(c, S, F, rows ? dPool.dev() : reinterpret_cast<const double*>(dRow.dev()) /* never read: every count is 0 */, dRow.dev(), cnt.dev(),
+                                 T.dev(), dBox.dev());
+    if (rc) return rc;
+    return m.download();
+}
+
 // --- pass 1 of the pair loop over a grid, radius mode ([REF roman/align/submap_align.py:93-149]) -------------------
 static int grid_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int32_t S0, int32_t S1,
                            const void* pos0, const void* T_w0, const void* time0, const void* desc0,
@@ -3087,16 +3138,16 @@ static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, i
                               const void* has_gt, const void* T_w, const void* time, const void* desc, int32_t nb, const int32_t* blocks,
                               const int64_t* pair_off, const int64_t* tile_off, const void* dist, const void* flags, const void* yaw_deg, const void* sim,
                               const void* T_ij, const void* pairs, const void* T_ref, const void* enable, const void* todo_off,
-                              int64_t* total, int64_t* tiles, int32_t* S, bool sim_in = false)
+                              int64_t* total, int64_t* tiles, int32_t* S, bool sim_in = false, bool aabb = false, const void* box = nullptr)
 {
     if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
     if (sim_in && P->desc_dim != 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d: the similarity is given, desc_dim must be 0", P->desc_dim);
     if (R < 0 || nb < 0) return fail(c, ROMAN_E_INVALID, "R < 0 or nb < 0");
     if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
         return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
-    if (P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
+    if (!aabb && P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
     if (P->desc_dim < 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d is negative", P->desc_dim);
-    if (P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: the session gate serves the radius mode only (roman_grid_gate_aabb* per robot pair)", P->radius);
+    if (!aabb && P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: without a radius the gate is the AABB test (roman_session_gate_aabb*)", P->radius);
     if (!sub_off || !pair_off || !tile_off || !todo_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / tile_off / todo_off is NULL");
     bool self = false;
     { int rc = session_tables_check(c, R, sub_off, nb, blocks, pair_off, tile_off, total, tiles, &self); if (rc) return rc; }
@@ -3105,6 +3156,7 @@ static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, i
     if (po == 0) return ROMAN_OK;
     if (P->desc_dim > 0 && !desc) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
     if (!pos || !T_w) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
+    if (aabb && !box) return fail(c, ROMAN_E_INVALID, "box is NULL");
     if (pos_gt && !has_gt) return fail(c, ROMAN_E_INVALID, "has_gt is NULL with pos_gt");
     if (self && !time) return fail(c, ROMAN_E_INVALID, "time is NULL with a self_lc block");
     if (!dist || !flags || !yaw_deg || !sim || !T_ij || !pairs || !T_ref || !enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
@@ -3117,13 +3169,14 @@ static int session_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparam
                             int32_t nb, const int32_t* blocks, const int32_t* blocks_host,
                             const int64_t* pair_off, const int64_t* pair_off_host, const int64_t* tile_off, const int64_t* tile_off_host,
                             double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                            int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, bool sim_in)
+                            int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, bool sim_in,
+                            bool aabb = false, const double* box = nullptr)
 {
     // (the arguments are judged first — on host memory only, a NULL context included: fail() then keeps the text for roman_last_error(NULL))
     if (!sub_off || !pair_off || !tile_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "a table is NULL on the device");
     int64_t total = 0, tiles = 0; int32_t S = 0;
     int rc = session_gate_check(c, gparams, R, sub_off_host, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks_host, pair_off_host, tile_off_host,
-                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S, sim_in);
+                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S, sim_in, aabb, box);
     if (rc) return rc;
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     HIPCHK(c, hipSetDevice(c->device));
@@ -3137,9 +3190,11 @@ static int session_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparam
     int32_t* dCount = c->sgCount.as<int32_t>();
     if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, stream, (int)S, 0, d, desc, (const double*)nullptr, dNorm);
     const SessionTab tab{(int)nb, sub_off, blocks, pair_off, tile_off, has_gt};
-    const GridSide s{pos, pos_gt, T_w, time, desc, nullptr};
+    const GridSide s{pos, pos_gt, T_w, time, desc, box};
     const GridOut out{dist, flags, yaw_deg, sim, T_ij};
-    if (sim_in) hipLaunchKernelGGL(k_session_gate<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
+    if (aabb && sim_in) hipLaunchKernelGGL((k_session_gate<true, true>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
+    else if (aabb) hipLaunchKernelGGL((k_session_gate<false, true>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
+    else if (sim_in) hipLaunchKernelGGL(k_session_gate<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
     else hipLaunchKernelGGL(k_session_gate<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
     hipLaunchKernelGGL(k_session_count, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, dCount);
     hipLaunchKernelGGL(k_session_scan, dim3(1), dim3(SESSION_SCAN), 0, stream, nwg, dCount, tab, total, todo_off);
@@ -3180,11 +3235,12 @@ static int session_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gpara
                              const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
                              int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
                              double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                             int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, bool sim_in)
+                             int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, bool sim_in,
+                             bool aabb = false, const double* box = nullptr)
 {
     int64_t total = 0, tiles = 0; int32_t S = 0;
     int rc = session_gate_check(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks, pair_off, tile_off,
-                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S, sim_in);
+                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S, sim_in, aabb, box);
     if (rc) return rc;
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (total == 0) { std::fill(todo_off, todo_off + nb + 1, 0); return ROMAN_OK; }
@@ -3196,7 +3252,8 @@ static int session_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gpara
     const auto dPo = m.in(pair_off, 8 * ((size_t)nb + 1)), dTo = m.in(tile_off, 8 * ((size_t)nb + 1));
     const auto dPos = m.in(pos, 24 * nS), dGt = m.in(pos_gt, pos_gt ? 24 * nS : 0);
     const auto dHas = m.in(has_gt, pos_gt ? 4 * (size_t)R : 0);
-    const auto dTw = m.in(T_w, 128 * nS), dTime = m.in(time, time ? 8 * nS : 0), dDesc = m.in(desc, 8 * d * nS);
+    const auto dTw = m.in(T_w, 128 * nS), dTime = m.in(time, time ? 8 * nS : 0), dDesc = m.in(desc, desc ? 8 * d * nS : 0);
+    const auto dBox = m.in(box, aabb ? 48 * nS : 0);
     const auto dDist = m.out(dist, 8 * B), dYaw = m.out(yaw_deg, 8 * B), dSim = sim_in ? m.in(sim, 8 * B) : m.out(sim, 8 * B), dTij = m.out(T_ij, 128 * B);
     const auto dFlags = m.out(flags, 4 * B);
     // the compact outputs are inout: the slots beyond todo_off[nb] come back as they were
@@ -3206,7 +3263,8 @@ static int session_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gpara
     if (rc) return rc;
     rc = session_gate_dev(c, gparams, R, dSub.dev(), sub_off, dPos.dev(), dGt.dev(), dHas.dev(), dTw.dev(), dTime.dev(), dDesc.dev(),
                           nb, dBlk.dev(), blocks, dPo.dev(), pair_off, dTo.dev(), tile_off,
-                          dDist.dev(), dFlags.dev(), dYaw.dev(), dSim.dev(), dTij.dev(), dPairs.dev(), dTref.dev(), dEn.dev(), dOff.dev(), sim_in);
+                          dDist.dev(), dFlags.dev(), dYaw.dev(), dSim.dev(), dTij.dev(), dPairs.dev(), dTref.dev(), dEn.dev(), dOff.dev(), sim_in,
+                          aabb, dBox.dev());
     if (rc) return rc;
     return m.download();
 }
@@ -3230,6 +3288,31 @@ int roman_session_gate_sim(roman_ctx_t* c, const roman_grid_gate_params_t* gpara
     (void)desc; (void)sim;
     return session_gate_host(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, nullptr, nb, blocks, pair_off, tile_off, dist, flags, yaw_deg,
                              const_cast<double*>(sim_in) /* uploaded, never written */, T_ij, pairs, T_ref, enable, todo_off, true);
+}
+
+// the AABB gate of a session: NEARBY from the boxes roman_session_boxes_dev wrote; with sim_in the similarity is an
+// input (`desc` is not read, `sim` not written), as roman_grid_gate_aabb* carries both
+int roman_session_gate_aabb_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
+                                const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                int32_t nb, const int32_t* blocks, const int32_t* blocks_host,
+                                const int64_t* pair_off, const int64_t* pair_off_host, const int64_t* tile_off, const int64_t* tile_off_host,
+                                double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* box, const double* sim_in)
+{
+    return session_gate_dev(c, gparams, R, sub_off, sub_off_host, pos, pos_gt, has_gt, T_w, time, sim_in ? nullptr : desc, nb, blocks, blocks_host,
+                            pair_off, pair_off_host, tile_off, tile_off_host, dist, flags, yaw_deg, sim_in ? const_cast<double*>(sim_in) /* only read */ : sim, T_ij,
+                            pairs, T_ref, enable, todo_off, sim_in != nullptr, true, box);
+}
+
+int roman_session_gate_aabb(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                            const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                            int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                            double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                            int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* box, const double* sim_in)
+{
+    return session_gate_host(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, sim_in ? nullptr : desc, nb, blocks, pair_off, tile_off, dist, flags, yaw_deg,
+                             sim_in ? const_cast<double*>(sim_in) /* uploaded, never written */ : sim, T_ij, pairs, T_ref, enable, todo_off,
+                             sim_in != nullptr, true, box);
 }
 
 // --- frame descriptors of the submaps of a pool ([REF roman/map/map.py:210-242], [REF :155-162]) ------------------

@@ -677,12 +677,13 @@ class Context:
 
     # ------------------------------------------------------------------ pass 1 of every robot pair of a session
     def session_gate(self, gparams, sub_off, blocks, pair_off, tile_off, pos, T_w, time=None, desc=None, pos_gt=None, has_gt=None,
-                     pairs=None, T_ref=None, enable=None, sim_in=None):
+                     pairs=None, T_ref=None, enable=None, sim_in=None, box=None):
         """Host-pointer pass 1 over a list of robot pairs (roman_session_gate): the tables as session_tables() gives them (they are
         passed as they are: the library checks them); pos (S, 3), T_w (S, 4, 4), time (S,), desc (S, desc_dim), pos_gt (S, 3) with
         has_gt (R,) over ALL submaps of the session.  gparams.single_robot_lc is not read: a block's own self_lc is.  The compact
         outputs may be handed in, as grid_gate() takes them.  sim_in (pair_off[nb],): the similarity of every pair is given
-        (roman_session_gate_sim; gparams.desc_dim must be 0) and comes back as `sim`.  -> SessionGateResult."""
+        (roman_session_gate_sim; gparams.desc_dim must be 0) and comes back as `sim`.  box (S, 6): the bounding-box gate
+        (roman_session_gate_aabb, DESIGN.md §4.16: session_gate_aabb() below).  -> SessionGateResult."""
         sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
         pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
         R, nb = len(sub_off) - 1, len(blocks)
@@ -708,6 +709,18 @@ class Context:
             sim = _f64(sim_in).reshape(-1).copy()
             if sim.shape[0] != B:
                 raise ValueError("sim_in must hold pair_off[nb] entries")
+        if box is not None:
+            box = _f64(box).reshape(-1, 6)
+            if box.shape[0] != S:
+                raise ValueError("box must hold one row per submap of the session")
+            given = sim_in is not None
+            rc = self._lib.roman_session_gate_aabb(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
+                                                   None if given else _ptr(desc), nb, _ptr(blocks), _ptr(pair_off), _ptr(tile_off), _ptr(dist), _ptr(flags),
+                                                   _ptr(yaw), None if given else _ptr(sim), _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off),
+                                                   _ptr(box), _ptr(sim) if given else None)
+            self._check(rc, "roman_session_gate_aabb")
+            return SessionGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, todo_off, pair_off)
+        if sim_in is not None:
             rc = self._lib.roman_session_gate_sim(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
                                                   None, nb, _ptr(blocks), _ptr(pair_off), _ptr(tile_off), _ptr(dist), _ptr(flags), _ptr(yaw), None,
                                                   _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off), _ptr(sim))
@@ -721,12 +734,13 @@ class Context:
 
     def session_gate_dev(self, gparams, sub_off, blocks, pair_off, tile_off, sub_off_ptr, blocks_ptr, pair_off_ptr, tile_off_ptr, pos_ptr, T_w_ptr,
                          dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr, pairs_ptr, T_ref_ptr, enable_ptr, todo_off_ptr,
-                         time_ptr=None, desc_ptr=None, pos_gt_ptr=None, has_gt_ptr=None, sim_in_ptr=None):
+                         time_ptr=None, desc_ptr=None, pos_gt_ptr=None, has_gt_ptr=None, sim_in_ptr=None, box_ptr=None):
         """Device-pointer pass 1 over a list of robot pairs (roman_session_gate_dev): the tables as host arrays (session_tables();
         the library validates these) AND as device addresses of the same values; every other pointer a device address.  A pure
         enqueue on the context's stream; complete after sync().  pairs_ptr holds GLOBAL submap indices: with frames tabled over
         all submaps of the session, its two columns are lc_tail_dev's iL and iR.  sim_in_ptr: the similarity of every pair is
-        given (roman_session_gate_sim_dev): gparams.desc_dim must be 0, desc_ptr is not read, sim_ptr not written."""
+        given (roman_session_gate_sim_dev): gparams.desc_dim must be 0, desc_ptr is not read, sim_ptr not written.
+        box_ptr: the bounding-box gate (roman_session_gate_aabb_dev, DESIGN.md §4.16: session_gate_aabb_dev() below)."""
         sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
         pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
         R, nb = len(sub_off) - 1, len(blocks)
@@ -736,10 +750,52 @@ class Context:
                 _vp(T_w_ptr), _vp(time_ptr), _vp(desc_ptr), nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off),
                 _vp(tile_off_ptr), _ptr(tile_off), _vp(dist_ptr), _vp(flags_ptr), _vp(yaw_deg_ptr), _vp(sim_ptr), _vp(T_ij_ptr),
                 _vp(pairs_ptr), _vp(T_ref_ptr), _vp(enable_ptr), _vp(todo_off_ptr))
+        if box_ptr is not None:
+            self._check(self._lib.roman_session_gate_aabb_dev(*args, _vp(box_ptr), _vp(sim_in_ptr)), "roman_session_gate_aabb_dev")
+            return
         if sim_in_ptr is not None:
             self._check(self._lib.roman_session_gate_sim_dev(*args, _vp(sim_in_ptr)), "roman_session_gate_sim_dev")
             return
         self._check(self._lib.roman_session_gate_dev(*args), "roman_session_gate_dev")
+
+    # ------------------------------------------------------------------ boxes and the bounding-box gate of a session
+    def session_boxes(self, pool, row0, count, T_odom_center):
+        """Host-pointer boxes of every submap of a session (roman_session_boxes): pool (rows, F) the concatenated pools, submap g
+        its rows [row0[g], row0[g] + count[g]) — in any order, overlapping where two views of a robot name the same rows —,
+        T_odom_center (S, 4, 4) -> (S, 6) float64: min x y z, max x y z in the global frame."""
+        pool = _f64(pool); row0 = np.ascontiguousarray(row0, dtype=np.int64).reshape(-1)
+        count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        S = int(count.shape[0])
+        T = _f64(T_odom_center).reshape(-1, 16)
+        if pool.ndim != 2 or row0.shape[0] != S or T.shape[0] != S:
+            raise ValueError("pool must be (rows, F), row0 and count (S,) and T_odom_center (S, 4, 4)")
+        if S and (count.min() < 0 or row0.min() < 0 or int((row0 + count).max()) > pool.shape[0]):
+            raise ValueError("a submap's rows lie outside the pool")
+        box = np.zeros((S, 6))
+        self._generation += 1
+        rc = self._lib.roman_session_boxes(self._h, S, int(pool.shape[1]), _ptr(pool), _ptr(row0), _ptr(count), _ptr(T), _ptr(box))
+        self._check(rc, "roman_session_boxes")
+        return box
+
+    def session_boxes_dev(self, S, F, pool_ptr, row0_ptr, count_ptr, T_odom_center_ptr, box_ptr):
+        """Device-pointer boxes of every submap of a session (roman_session_boxes_dev): row0 int64[S] and count int32[S] on the
+        device.  A pure enqueue on the context's stream."""
+        rc = self._lib.roman_session_boxes_dev(self._h, int(S), int(F), _vp(pool_ptr), _vp(row0_ptr), _vp(count_ptr), _vp(T_odom_center_ptr), _vp(box_ptr))
+        self._check(rc, "roman_session_boxes_dev")
+
+    def session_gate_aabb(self, gparams, box, sub_off, blocks, pair_off, tile_off, pos, T_w, **kw):
+        """session_gate() with the bounding-box gate (roman_session_gate_aabb): box (S, 6) as session_boxes() gives them;
+        gparams.radius is not read; sim_in as in session_gate().  -> SessionGateResult."""
+        return self.session_gate(gparams, sub_off, blocks, pair_off, tile_off, pos, T_w, box=_f64(box).reshape(-1, 6), **kw)
+
+    def session_gate_aabb_dev(self, gparams, sub_off, blocks, pair_off, tile_off, sub_off_ptr, blocks_ptr, pair_off_ptr, tile_off_ptr, pos_ptr, T_w_ptr,
+                              dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr, pairs_ptr, T_ref_ptr, enable_ptr, todo_off_ptr, box_ptr, **kw):
+        """session_gate_dev() with the bounding-box gate (roman_session_gate_aabb_dev): box_ptr as session_boxes_dev wrote them, over
+        all submaps of the session; with sim_in_ptr the similarity is an input.  A pure enqueue on the context's stream."""
+        if box_ptr is None:
+            raise ValueError("session_gate_aabb_dev needs the boxes")
+        self.session_gate_dev(gparams, sub_off, blocks, pair_off, tile_off, sub_off_ptr, blocks_ptr, pair_off_ptr, tile_off_ptr, pos_ptr, T_w_ptr,
+                              dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr, pairs_ptr, T_ref_ptr, enable_ptr, todo_off_ptr, box_ptr=box_ptr, **kw)
 
     # ------------------------------------------------------------------ the stacked similarity of every block of a session (DESIGN.md §4.15)
     @staticmethod
