@@ -718,6 +718,123 @@ def _pool_side_host(pool, gt_poses, gt_available, reads, aabb_mode):
     return dict(pos=pos, pos_gt=pos_gt, T_w=T_w, time=times, T_oc=T_oc, frames=frames)
 
 
+# ---------------------------------------------------------------------------------------------
+# the stages submap_align_pools and submap_align_session share: refusals, device plumbing, the read-back of pass 1, the
+# shared-segment removal and the registration over resident rows
+# ---------------------------------------------------------------------------------------------
+def _no_device(registration, p):
+    """No context of the caller's and host-tensor pools: nothing a kernel could run on."""
+    return getattr(registration, "_ctx", None) is None and any(q.pool.device.type == "cpu" for q in p)
+
+
+def _ransac_refusals(registration, p, way):
+    """What a RansacReg over the pools `p` is refused for — every check in front of registration._context() makes no HIP context."""
+    if any(int(q.table.point_dim) != 3 for q in p):
+        raise ValueError("RansacReg reads x y z from columns 0-2 of a pool row, and pools of dim 2 hold no z" + way)
+    if any(int(q.cap) > _abi.ROMAN_RANSAC_MAX_OBJECTS for q in p):
+        raise ValueError(f"RansacReg serves at most {_abi.ROMAN_RANSAC_MAX_OBJECTS} objects per submap (the pools' cap is larger)" + way)
+    if _no_device(registration, p):
+        raise ValueError("RansacReg has no context set and the pools are host tensors: no device to run on" + way)
+    if not hasattr(registration._context(), "ransac_lc_batch_dev"):
+        raise ValueError("the context has no roman_ransac_lc_batch_dev" + way)
+
+
+def _descriptor_refusals(registration, p, mode, way):
+    """The descriptor modes the pools `p` do not carry, and a plugin whose host prefilter would need the segment rows back."""
+    if mode not in (None, 'mean_semantic', 'mean_frame_descriptor', 'stacked_frame_descriptors'):
+        raise ValueError(f"submap_descriptor {mode!r} is not one the pools carry" + way)
+    if mode in ('mean_frame_descriptor', 'stacked_frame_descriptors') and any(q.descriptor_mode != mode for q in p):
+        raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool(frames=...) keeps the frame masks on the device)" + way)
+    if _has_host_prefilter(registration):
+        raise ValueError("the registration plugin prefilters association lists on the host" + way)
+
+
+def _descriptor_dim(p, mode, the_pools, way):
+    """-> the length of the submap descriptors the gate contracts: 0 without a descriptor, and for stacked frame descriptors (the
+    gate then reads a ready similarity).  Refuses pools `p` (`the_pools` in the text) that lack them or disagree on the length."""
+    if mode is None or not p:
+        return 0
+    if mode == 'stacked_frame_descriptors':
+        if any(int(q.frame_desc_dev.shape[1]) != int(p[0].frame_desc_dev.shape[1]) for q in p):
+            raise ValueError(f"{the_pools} have frame descriptors of different lengths" + way)
+        return 0
+    if any(q.desc_dev is None for q in p):
+        raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool keeps the descriptors on the device)" + way)
+    d = int(p[0].desc_dev.shape[1])
+    if any(int(q.desc_dev.shape[1]) != d for q in p):
+        raise ValueError(f"{the_pools} have descriptors of different lengths" + way)
+    return d
+
+
+def _plumbing(torch, dev):
+    """-> (wait_torch, up, ptr) for pools on `dev` (CPU tensors: a stand-in context, as the tests use): wait_torch() returns when
+    torch's stream has done what was asked of it — the library's stream may read it then —, up(array or None) -> tensor on `dev`,
+    ptr(tensor or None) -> address."""
+    wait_torch = (lambda: None) if dev.type == "cpu" else (lambda: torch.cuda.current_stream(dev).synchronize())
+    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    return wait_torch, up, ptr
+
+
+def _pass1_block(M, h, lo, hi, n0, n1, compact_pairs, what):
+    """Pass 1 of one (n0, n1) grid as the gate left it at [lo, hi) of its dense outputs `h` (host arrays), into `M`.  `compact_pairs`:
+    the grid's rows of the compact list, grid-local; they must be the TODO pairs in row-major order (`what`: the text of the
+    error otherwise).  -> (nearby, todo), (n0, n1) bool."""
+    cut = lambda k: h[k].reshape(-1)[lo:hi].reshape(n0, n1)
+    flags = cut("flags")
+    nearby, todo = (flags & _abi.ROMAN_GRID_NEARBY) != 0, (flags & _abi.ROMAN_GRID_TODO) != 0
+    M.pass1(cut("dist"), nearby, (flags & _abi.ROMAN_GRID_SKIP) != 0, (flags & _abi.ROMAN_GRID_GATED) != 0, cut("yaw"), cut("sim"),
+            h["T_ij"][lo:hi].reshape(n0, n1, 4, 4))
+    if not np.array_equal(compact_pairs, np.stack(np.nonzero(todo), axis=1)):
+        raise _abi.RomanHipError(what)
+    return nearby, todo
+
+
+def _drop_shared_over_pool(torch, ctx, pool, ids_dev, off1, n1, off2, n2, sel, wait_torch):
+    """The shared-segment removal of [REF roman/align/submap_align.py:108-115] for the problems `sel` of (off1, n1, off2, n2) over
+    the resident rows `pool` (`ids_dev`: one id per row), DESIGN.md §4.11: the pool's rows and behind them the fixed slots of
+    THESE problems' gather region in ONE allocation; mark + gather in one launch; the kept counts back (8 bytes per problem: the
+    one extra synchronisation).  The problems that lost something then read their slots, the others the pool as given.
+    -> (pool with the region, off1, n1, off2, n2)."""
+    rows, F, dev = int(pool.shape[0]), int(pool.shape[1]), pool.device
+    sub = [np.ascontiguousarray(a[sel]) for a in (off1, n1, off2, n2)]
+    n_slots = int(sub[1].sum(dtype=np.int64) + sub[3].sum(dtype=np.int64))
+    work = torch.empty((rows + n_slots, F), dtype=torch.float64, device=dev)
+    work[:rows].copy_(pool)
+    keep_dev = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev); kept_dev = torch.zeros((len(sel), 2), dtype=torch.int32, device=dev)
+    wait_torch()                                             # the copy of the pool and the ids are in place
+    ctx.shared_reduce_dev(len(sel), F, work.data_ptr(), rows, ids_dev.data_ptr(), *sub, keep_dev.data_ptr(), kept_dev.data_ptr())
+    ctx.sync()
+    out = [np.array(a) for a in (off1, n1, off2, n2)]
+    for a, red in zip(out, reduced_problems(*sub, kept_dev.cpu().numpy(), rows)):
+        a[sel] = red
+    return (work, *out)
+
+
+def _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, FL, FR, wait_torch):
+    """The B problems of `batch` over the resident rows `pool`, and the tail behind them with T_ref, enable and the pairs where the
+    gate wrote them (`g`) and the edge frames FL / FR (device tensors, indexed by the pairs): issue_chunked, join and
+    roman_lc_tail_dev — or, for a RansacReg, `_ransac_lc_over_pool`.  -> (runtime.LoopClosureResult, seconds per pair)."""
+    from .pipeline import issue_chunked
+    ransac = isinstance(registration, RansacReg)
+    o = _TailBuffers(torch, pool.device, B, 0 if ransac else kmax)   # (a RansacReg keeps its association rows in a buffer of its own)
+    iL, iR = g["pairs"][:B, 0].contiguous(), g["pairs"][:B, 1].contiguous()
+    lp = _lc_inputs(sm_params, sm_io, registration).params()
+    tail_ptrs = dict(T_ref_ptr=g["T_ref"].data_ptr(), enable_ptr=g["enable"].data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
+                     FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr())
+    wait_torch()                                             # the pool (torch.cat), the cleared outputs and the frames are in place
+    t0 = time.time()
+    if ransac:                                               # k_ransac over the rows as they are, the tail behind it
+        res = _ransac_lc_over_pool(torch, ctx, registration, pool, batch, lp, o, tail_ptrs, wait_torch)
+    else:
+        status = issue_chunked(ctx, registration._abi_params(), pool, batch, kmax, o.assoc, o.n, o.T, o.status)   # re-issues skipped problems, then synchronises:
+        ctx.join()                                           # ... the tail below sees the FINAL attempt of every problem only
+        ctx.lc_tail_dev(lp, B, o.T.data_ptr(), o.n.data_ptr(), o.status.data_ptr(), o.records.data_ptr(), o.acc_idx.data_ptr(), o.acc_n.data_ptr(), **tail_ptrs)
+        ctx.sync()
+        res = o.result(status, sm_params.dim)
+    return res, (time.time() - t0) / B
+
+
 def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, registration=None, gt_poses=(None, None)) -> SubmapAlignResults:
     """submap_align_grid() for two maps whose submaps are ALREADY in HBM (`pools`: two align.submaps.SubmapPool, as
     build_submap_pool leaves them): the same results as submap_align_grid(sm_params, [p.to_submaps(segments) for p in pools]),
@@ -757,42 +874,19 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     masks — every distinct frame pair contracted once — and roman_grid_gate_sim_dev on that similarity.  similarity_mat is what
     the device computed."""
     import torch
-    from .pipeline import issue_chunked
     sm_io = sm_io or SubmapAlignIO()
     registration = registration or sm_params.get_object_registration()
     way = " (not on the device-resident path: use SubmapPool.to_submaps() + submap_align_grid)"
     p = list(pools)
     if len(p) != 2:
         raise ValueError("pools must hold two SubmapPool objects")
-    ransac = isinstance(registration, RansacReg)
-    if ransac:                                               # (every check in front of registration._context(): nothing here makes a HIP context)
-        if any(int(q.table.point_dim) != 3 for q in p):
-            raise ValueError("RansacReg reads x y z from columns 0-2 of a pool row, and pools of dim 2 hold no z" + way)
-        if any(int(q.cap) > _abi.ROMAN_RANSAC_MAX_OBJECTS for q in p):
-            raise ValueError(f"RansacReg serves at most {_abi.ROMAN_RANSAC_MAX_OBJECTS} objects per submap (the pools' cap is larger)" + way)
-        if getattr(registration, "_ctx", None) is None and any(q.pool.device.type == "cpu" for q in p):
-            raise ValueError("RansacReg has no context set and the pools are host tensors: no device to run on" + way)
-        if not hasattr(registration._context(), "ransac_lc_batch_dev"):
-            raise ValueError("the context has no roman_ransac_lc_batch_dev" + way)
+    if isinstance(registration, RansacReg):
+        _ransac_refusals(registration, p, way)
     aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
     mode = sm_params.submap_descriptor
     stacked = mode == 'stacked_frame_descriptors'
-    if mode not in (None, 'mean_semantic', 'mean_frame_descriptor', 'stacked_frame_descriptors'):
-        raise ValueError(f"submap_descriptor {mode!r} is not one the pools carry" + way)
-    if mode in ('mean_frame_descriptor', 'stacked_frame_descriptors') and any(q.descriptor_mode != mode for q in p):
-        raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool(frames=...) keeps the frame masks on the device)" + way)
-    if _has_host_prefilter(registration):
-        raise ValueError("the registration plugin prefilters association lists on the host" + way)
-    d = 0
-    if stacked:
-        if int(p[0].frame_desc_dev.shape[1]) != int(p[1].frame_desc_dev.shape[1]):
-            raise ValueError("the two pools have frame descriptors of different lengths")
-    elif mode is not None:
-        if p[0].desc_dev is None or p[1].desc_dev is None:
-            raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool keeps the descriptors on the device)")
-        d = int(p[0].desc_dev.shape[1])
-        if int(p[1].desc_dev.shape[1]) != d:
-            raise ValueError("the two pools have descriptors of different lengths")
+    _descriptor_refusals(registration, p, mode, way)
+    d = _descriptor_dim(p, mode, "the two pools", "")
     for r in range(2):
         if sm_io.gt_available[r] and gt_poses[r] is None:
             raise ValueError(f"sm_io.gt_available[{r}] is set without gt_poses[{r}]")
@@ -808,10 +902,7 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         raise ValueError("single_robot_lc over submaps that share segment ids needs pools that kept their ids on the device (SubmapPool.ids_dev, "
                          "as build_submap_pool leaves it) and a context with roman_shared_reduce_dev" + way)
     dev = p[0].pool.device
-    on_host = dev.type == "cpu"                              # CPU tensors + a stand-in context (tests)
-    wait_torch = (lambda: None) if on_host else (lambda: torch.cuda.current_stream(dev).synchronize())
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
+    wait_torch, up, ptr = _plumbing(torch, dev)
     keep = [q.nonempty for q in p]                           # [REF roman/map/map.py:341]: the reference drops the empty submaps
     n0, n1 = len(keep[0]), len(keep[1])
     M = _GridResults(sm_params, sm_io, n0, n1)
@@ -864,12 +955,7 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     B = int(g["n_todo"].cpu().numpy()[0])
     pairs = g["pairs"][:B].cpu().numpy().astype(np.int64)
     h = {k: g[k].cpu().numpy() for k in ("dist", "flags", "yaw", "sim", "T_ij")}
-    flags = h["flags"]
-    nearby, todo = (flags & _abi.ROMAN_GRID_NEARBY) != 0, (flags & _abi.ROMAN_GRID_TODO) != 0
-    M.pass1(h["dist"], nearby, (flags & _abi.ROMAN_GRID_SKIP) != 0, (flags & _abi.ROMAN_GRID_GATED) != 0, h["yaw"], h["sim"],
-            h["T_ij"].reshape(n0, n1, 4, 4))
-    if not np.array_equal(pairs, np.stack(np.nonzero(todo), axis=1)):
-        raise _abi.RomanHipError("roman_grid_gate_dev: the compact pair list is not the TODO pairs in row-major order")
+    nearby, todo = _pass1_block(M, h, 0, n0 * n1, n0, n1, pairs, "roman_grid_gate_dev: the compact pair list is not the TODO pairs in row-major order")
     if B == 0:
         return M.results(lc_edges=M.empty_edges())
 
@@ -877,42 +963,12 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     batch, pool = p[0].grid_batch(p[1], mask=todo)
     kmax = batch.kmax()                                      # (of the unreduced sizes: still a bound after the removal)
     if shared:
-        # the pool's rows and behind them the fixed slots of the gather region in ONE allocation; mark + gather in one launch;
-        # the kept counts back (8 bytes per problem: the one extra synchronisation); the problems that lost something then read
-        # their slots, the others the pool as given
-        rows, F = int(pool.shape[0]), int(pool.shape[1])
-        n_slots = int(batch.n1.sum(dtype=np.int64) + batch.n2.sum(dtype=np.int64))
-        work = torch.empty((rows + n_slots, F), dtype=torch.float64, device=dev)
-        work[:rows].copy_(pool)
         ids_dev = p[0].ids_dev if p[0] is p[1] else torch.cat([p[0].ids_dev, p[1].ids_dev])
-        keep_dev = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev); kept_dev = torch.zeros((B, 2), dtype=torch.int32, device=dev)
-        wait_torch()                                         # the copy of the pool and the ids are in place
-        ctx.shared_reduce_dev(B, F, work.data_ptr(), rows, ids_dev.data_ptr(), batch.off1, batch.n1, batch.off2, batch.n2,
-                              keep_dev.data_ptr(), kept_dev.data_ptr())
-        ctx.sync()
-        off1, n1, off2, n2 = reduced_problems(batch.off1, batch.n1, batch.off2, batch.n2, kept_dev.cpu().numpy(), rows)
-        batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), (rows + n_slots, F)), off1, n1, off2, n2, pair_index=batch.pair_index)
-        pool = work
-    o = _TailBuffers(torch, dev, B, 0 if ransac else kmax)   # (a RansacReg keeps its association rows in a buffer of its own)
-    FL, FR = up(frames[0].reshape(-1, 16)), up(frames[1].reshape(-1, 16))
-    iL, iR = g["pairs"][:B, 0].contiguous(), g["pairs"][:B, 1].contiguous()
-    lp = _lc_inputs(sm_params, sm_io, registration).params()
-    wait_torch()                                             # the pool (torch.cat), the cleared outputs and the frames are in place
-    t0 = time.time()
-    if ransac:                                               # k_ransac over the rows as they are, the tail behind it (DESIGN.md §4.13)
-        res = _ransac_lc_over_pool(torch, ctx, registration, pool, batch, lp, o,
-                                   dict(T_ref_ptr=g["T_ref"].data_ptr(), enable_ptr=g["enable"].data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
-                                        FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr()), wait_torch)
-        timing_list = [(time.time() - t0) / B] * B
-        return M.results(timing_list, _records_into_results(M, res, pairs[:, 0], pairs[:, 1], nearby))
-    status = issue_chunked(ctx, registration._abi_params(), pool, batch, kmax, o.assoc, o.n, o.T, o.status)   # re-issues skipped problems, then synchronises:
-    ctx.join()                                               # ... the tail below sees the FINAL attempt of every problem only
-    ctx.lc_tail_dev(lp, B, o.T.data_ptr(), o.n.data_ptr(), o.status.data_ptr(), o.records.data_ptr(), o.acc_idx.data_ptr(), o.acc_n.data_ptr(),
-                    T_ref_ptr=g["T_ref"].data_ptr(), enable_ptr=g["enable"].data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
-                    FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr())
-    ctx.sync()
-    timing_list = [(time.time() - t0) / B] * B
-    return M.results(timing_list, _records_into_results(M, o.result(status, sm_params.dim), pairs[:, 0], pairs[:, 1], nearby))
+        pool, *prob = _drop_shared_over_pool(torch, ctx, pool, ids_dev, batch.off1, batch.n1, batch.off2, batch.n2, np.arange(B), wait_torch)
+        batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), tuple(pool.shape)), *prob, pair_index=batch.pair_index)
+    res, per_pair = _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, up(frames[0].reshape(-1, 16)),
+                                        up(frames[1].reshape(-1, 16)), wait_torch)
+    return M.results([per_pair] * B, _records_into_results(M, res, pairs[:, 0], pairs[:, 1], nearby))
 
 
 def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[SubmapAlignIO] = None, registration=None,
@@ -961,7 +1017,6 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     (their rows hold no z)."""
     import torch
     from ..runtime import session_tables
-    from .pipeline import issue_chunked
     sm_io = sm_io or SubmapAlignIO()
     registration = registration or sm_params.get_object_registration()
     way = " (not in the session call: use submap_align_pools per robot pair)"
@@ -973,41 +1028,18 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         raise ValueError("gt_poses must hold one entry per pool" + way)
     if any(not (0 <= r < R and 0 <= s < R) for r, s in blocks) or len(set(blocks)) != len(blocks):
         raise ValueError("robot_pairs must name pools by index, each pair once" + way)
-    ransac = isinstance(registration, RansacReg)
-    no_device = getattr(registration, "_ctx", None) is None and any(q.pool.device.type == "cpu" for q in p)
-    if ransac and R:                                         # (submap_align_pools' four, in its order: in front of everything that makes a HIP context)
-        if any(int(q.table.point_dim) != 3 for q in p):
-            raise ValueError("RansacReg reads x y z from columns 0-2 of a pool row, and pools of dim 2 hold no z" + way)
-        if any(int(q.cap) > _abi.ROMAN_RANSAC_MAX_OBJECTS for q in p):
-            raise ValueError(f"RansacReg serves at most {_abi.ROMAN_RANSAC_MAX_OBJECTS} objects per submap (the pools' cap is larger)" + way)
-        if no_device:
-            raise ValueError("RansacReg has no context set and the pools are host tensors: no device to run on" + way)
-        if not hasattr(registration._context(), "ransac_lc_batch_dev"):
-            raise ValueError("the context has no roman_ransac_lc_batch_dev" + way)
+    if isinstance(registration, RansacReg) and R:            # (submap_align_pools' four, in its order: in front of everything that makes a HIP context)
+        _ransac_refusals(registration, p, way)
     aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
-    if aabb_mode and no_device:                              # (the boxes are reduced from the resident rows: as for a RansacReg, host rows need a context of the caller's)
+    if aabb_mode and _no_device(registration, p):            # (the boxes are reduced from the resident rows: as for a RansacReg, host rows need a context of the caller's)
         raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes of the resident rows: the registration has no context set "
                          "and the pools are host tensors: no device to run on" + way)
     mode = sm_params.submap_descriptor
     stacked = mode == 'stacked_frame_descriptors'
-    if mode not in (None, 'mean_semantic', 'mean_frame_descriptor', 'stacked_frame_descriptors'):
-        raise ValueError(f"submap_descriptor {mode!r} is not one the pools carry" + way)
-    if mode in ('mean_frame_descriptor', 'stacked_frame_descriptors') and any(q.descriptor_mode != mode for q in p):
-        raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool(frames=...) keeps the frame masks on the device)" + way)
-    if _has_host_prefilter(registration):
-        raise ValueError("the registration plugin prefilters association lists on the host" + way)
+    _descriptor_refusals(registration, p, mode, way)
     if R and any(int(q.pool.shape[1]) != int(p[0].pool.shape[1]) for q in p):
         raise ValueError("the pools have different row widths" + way)
-    d = 0
-    if stacked and R:                                        # (the gate reads a ready similarity: its desc_dim stays 0)
-        if any(int(q.frame_desc_dev.shape[1]) != int(p[0].frame_desc_dev.shape[1]) for q in p):
-            raise ValueError("the pools have frame descriptors of different lengths" + way)
-    elif mode is not None and R:
-        if any(q.desc_dev is None for q in p):
-            raise ValueError(f"submap_descriptor {mode!r} needs pools built with it (build_submap_pool keeps the descriptors on the device)" + way)
-        d = int(p[0].desc_dev.shape[1])
-        if any(int(q.desc_dev.shape[1]) != d for q in p):
-            raise ValueError("the pools have descriptors of different lengths" + way)
+    d = _descriptor_dim(p, mode, "the pools", way)
     selfs = sorted({r for r, s in blocks if r == s})
     if any(p[r].ids_dev is None for r in selfs):
         raise ValueError("a self block drops the segments both submaps hold: its pool must have kept its ids on the device (SubmapPool.ids_dev, "
@@ -1065,10 +1097,7 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     if aabb_mode and any(int(q.table.point_dim) != 3 for q in p):
         raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes, and pools of dim 2: their rows hold no z" + way)
     dev = p[0].pool.device
-    on_host = dev.type == "cpu"                              # CPU tensors + a stand-in context (tests)
-    wait_torch = (lambda: None) if on_host else (lambda: torch.cuda.current_stream(dev).synchronize())
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
+    wait_torch, up, ptr = _plumbing(torch, dev)
     lv = [(r, hs) for r, hs in views if counts[r]]           # the views that hold submaps, in table order
     cat = lambda get, width: np.concatenate([np.zeros((int(counts[r]),) + width) if hs is None else np.asarray(get(hs)).reshape((-1,) + width) for r, hs in lv])
     any_gt = any(gt_poses[r] is not None for r, _ in lv)
@@ -1144,14 +1173,9 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     nearby, local = [], []
     for b, (r, s) in enumerate(blocks):
         n0, n1 = int(counts[r]), int(counts[s])
-        lo, hi = int(pair_off[b]), int(pair_off[b + 1])
-        flags = h["flags"][lo:hi].reshape(n0, n1)
-        near, todo = (flags & _abi.ROMAN_GRID_NEARBY) != 0, (flags & _abi.ROMAN_GRID_TODO) != 0
-        Ms[b].pass1(h["dist"][lo:hi].reshape(n0, n1), near, (flags & _abi.ROMAN_GRID_SKIP) != 0, (flags & _abi.ROMAN_GRID_GATED) != 0,
-                    h["yaw"][lo:hi].reshape(n0, n1), h["sim"][lo:hi].reshape(n0, n1), h["T_ij"][lo:hi].reshape(n0, n1, 4, 4))
         lp_ = gpairs[todo_off[b]:todo_off[b + 1]] - np.array([sub_off[vblocks[b][0]], sub_off[vblocks[b][1]]], dtype=np.int64)
-        if not np.array_equal(lp_, np.stack(np.nonzero(todo), axis=1)):
-            raise _abi.RomanHipError(f"roman_session_gate_dev: the compact pair list of block {blocks[b]} is not its TODO pairs in row-major order")
+        near, _ = _pass1_block(Ms[b], h, int(pair_off[b]), int(pair_off[b + 1]), n0, n1, lp_,
+                               f"roman_session_gate_dev: the compact pair list of block {blocks[b]} is not its TODO pairs in row-major order")
         nearby.append(near); local.append(lp_)
     if B == 0:
         return {blocks[b]: result_of(b, Ms[b], edges=Ms[b].empty_edges()) for b in range(nb)}
@@ -1160,48 +1184,18 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     live = sorted({r for r, _ in lv})
     if not aabb_mode:
         pool, sm_row, sm_cnt = concatenated()
-    rows, F = int(pool.shape[0]), int(pool.shape[1])
-    off1, n1_, off2, n2_ = sm_row[gpairs[:, 0]], sm_cnt[gpairs[:, 0]], sm_row[gpairs[:, 1]], sm_cnt[gpairs[:, 1]]
-    kmax = int(max(1, np.max(np.minimum(n1_, n2_))))         # (of the unreduced sizes: still a bound after the removal)
+    prob = sm_row[gpairs[:, 0]], sm_cnt[gpairs[:, 0]], sm_row[gpairs[:, 1]], sm_cnt[gpairs[:, 1]]
+    kmax = int(max(1, np.max(np.minimum(prob[1], prob[3]))))    # (of the unreduced sizes: still a bound after the removal)
     of_self = np.concatenate([np.full(int(todo_off[b + 1] - todo_off[b]), r == s, dtype=bool) for b, (r, s) in enumerate(blocks)])
     sel = np.nonzero(of_self)[0]
-    if len(sel):
-        # the problems of the self blocks lose the segments both submaps hold: the pools' rows and behind them the gather region of
-        # THESE problems in one allocation, one launch, the kept counts back (the one extra synchronisation)
-        n_slots = int(n1_[sel].sum(dtype=np.int64) + n2_[sel].sum(dtype=np.int64))
-        work = torch.empty((rows + n_slots, F), dtype=torch.float64, device=dev)
-        work[:rows].copy_(pool)
+    if len(sel):                                             # the problems of the self blocks lose the segments both submaps hold
         ids_dev = torch.cat([p[r].ids_dev if p[r].ids_dev is not None else torch.zeros(int(p[r].pool.shape[0]), dtype=torch.int64, device=dev) for r in live])
-        keep_dev = torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev); kept_dev = torch.zeros((len(sel), 2), dtype=torch.int32, device=dev)
-        wait_torch()                                         # the copy of the pools and the ids are in place
-        ctx.shared_reduce_dev(len(sel), F, work.data_ptr(), rows, ids_dev.data_ptr(), np.ascontiguousarray(off1[sel]), np.ascontiguousarray(n1_[sel]),
-                              np.ascontiguousarray(off2[sel]), np.ascontiguousarray(n2_[sel]), keep_dev.data_ptr(), kept_dev.data_ptr())
-        ctx.sync()
-        red = reduced_problems(off1[sel], n1_[sel], off2[sel], n2_[sel], kept_dev.cpu().numpy(), rows)
-        off1, n1_, off2, n2_ = off1.copy(), n1_.copy(), off2.copy(), n2_.copy()
-        off1[sel], n1_[sel], off2[sel], n2_[sel] = red
-        pool, rows = work, rows + n_slots
-    batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), (rows, F)), off1.astype(np.int64), n1_.astype(np.int32), off2.astype(np.int64), n2_.astype(np.int32),
-                           pair_index=gpairs)
-    o = _TailBuffers(torch, dev, B, 0 if ransac else kmax)   # (a RansacReg keeps its association rows in a buffer of its own)
-    FL, FR = up(FLh), up(FRh)
-    iL, iR = g["pairs"][:B, 0].contiguous(), g["pairs"][:B, 1].contiguous()
-    lp = _lc_inputs(sm_params, sm_io, registration).params()
-    wait_torch()                                             # the pool (torch.cat), the cleared outputs and the frames are in place
-    t0 = time.time()
-    tail_ptrs = dict(T_ref_ptr=g["T_ref"].data_ptr(), enable_ptr=g["enable"].data_ptr(), FL_ptr=FL.data_ptr(), iL_ptr=iL.data_ptr(),
-                     FR_ptr=FR.data_ptr(), iR_ptr=iR.data_ptr())
-    if ransac:
-        # k_ransac over the rows as they are and the tail behind it, for the problems of ALL blocks: the seed
-        # is one per batch and a problem's draws do not depend on its place in it, so a block equals its own submap_align_pools
-        res = _ransac_lc_over_pool(torch, ctx, registration, pool, batch, lp, o, tail_ptrs, wait_torch)
-    else:
-        status = issue_chunked(ctx, registration._abi_params(), pool, batch, kmax, o.assoc, o.n, o.T, o.status)
-        ctx.join()                                           # the tail below sees the FINAL attempt of every problem only
-        ctx.lc_tail_dev(lp, B, o.T.data_ptr(), o.n.data_ptr(), o.status.data_ptr(), o.records.data_ptr(), o.acc_idx.data_ptr(), o.acc_n.data_ptr(), **tail_ptrs)
-        ctx.sync()
-        res = o.result(status, sm_params.dim)
-    per_pair = (time.time() - t0) / B
+        pool, *prob = _drop_shared_over_pool(torch, ctx, pool, ids_dev, *prob, sel, wait_torch)
+    batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), tuple(pool.shape)), prob[0].astype(np.int64), prob[1].astype(np.int32), prob[2].astype(np.int64),
+                           prob[3].astype(np.int32), pair_index=gpairs)
+    # for a RansacReg too the problems of ALL blocks go in one batch: the seed is one per batch and a
+    # problem's draws do not depend on its place in it, so a block equals its own submap_align_pools
+    res, per_pair = _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, up(FLh), up(FRh), wait_torch)
 
     # ---- the records and the accepted list split by todo_off, per block with block-local indices ----
     out = {}

@@ -2938,6 +2938,35 @@ int roman_session_boxes(roman_ctx_t* c, int32_t S, int32_t F, const double* pool
     return m.download();
 }
 
+// What the grid gate and the session gate ask of roman_grid_gate_params_t, in front of their own checks.  The caller's check of its
+// counts (`bad_sizes`, with the text `sizes`) is handed in because it has always been the THIRD check, between the given similarity
+// and the reserved words, and a call wrong in two ways keeps its answer.  `aabb_entry`: the entry points that serve a missing radius
+static int gate_params_check(roman_ctx* c, const roman_grid_gate_params_t* P, bool sim_in, bool aabb, const char* aabb_entry, bool bad_sizes, const char* sizes)
+{
+    if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
+    if (sim_in && P->desc_dim != 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d: the similarity is given, desc_dim must be 0", P->desc_dim);
+    if (bad_sizes) return fail(c, ROMAN_E_INVALID, "%s", sizes);
+    if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
+        return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
+    if (!aabb && P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
+    if (P->desc_dim < 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d is negative", P->desc_dim);
+    if (!aabb && P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: without a radius the gate is the AABB test (%s)", P->radius, aabb_entry);
+    return ROMAN_OK;
+}
+
+// the instantiation of a gate kernel for (sim_in, aabb)
+static auto grid_gate_kernel(bool sim_in, bool aabb)
+{
+    return sim_in ? (aabb ? k_grid_gate<true, true> : k_grid_gate<true, false>) : (aabb ? k_grid_gate<false, true> : k_grid_gate<false, false>);
+}
+
+static auto session_gate_kernel(bool sim_in, bool aabb)
+{
+    using Kernel = void (*)(roman_grid_gate_params_t, SessionTab, int64_t, GridSide, const double*, GridOut);
+    const Kernel radius = sim_in ? k_session_gate<true> : k_session_gate<false>, boxes = sim_in ? k_session_gate<true, true> : k_session_gate<false, true>;
+    return aabb ? boxes : radius;
+}
+
 // --- pass 1 of the pair loop over a grid, radius mode ([REF roman/align/submap_align.py:93-149]) -------------------
 static int grid_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int32_t S0, int32_t S1,
                            const void* pos0, const void* T_w0, const void* time0, const void* desc0,
@@ -2946,14 +2975,7 @@ static int grid_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int3
                            const void* pairs, const void* T_ref, const void* enable, const void* n_todo, bool sim_in = false,
                            bool aabb = false, const void* box0 = nullptr, const void* box1 = nullptr)
 {
-    if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
-    if (sim_in && P->desc_dim != 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d: the similarity is given, desc_dim must be 0", P->desc_dim);
-    if (S0 < 0 || S1 < 0) return fail(c, ROMAN_E_INVALID, "S0 < 0 or S1 < 0");
-    if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
-        return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
-    if (!aabb && P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
-    if (P->desc_dim < 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d is negative", P->desc_dim);
-    if (!aabb && P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: without a radius the gate is the AABB test (roman_grid_gate_aabb*)", P->radius);
+    { int rc = gate_params_check(c, P, sim_in, aabb, "roman_grid_gate_aabb*", S0 < 0 || S1 < 0, "S0 < 0 or S1 < 0"); if (rc) return rc; }
     if (!n_todo) return fail(c, ROMAN_E_INVALID, "n_todo is NULL");
     if (S0 == 0 || S1 == 0) return ROMAN_OK;
     if ((int64_t)S0 * S1 > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "S0 * S1 = %lld pairs exceed the index width", (long long)S0 * S1);
@@ -2987,11 +3009,7 @@ static int grid_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, 
     const GridSide a{pos0, pos_gt0, T_w0, time0, desc0, box0}, b{pos1, pos_gt1, T_w1, time1, desc1, box1};
     const GridOut out{dist, flags, yaw_deg, sim, T_ij};
     const int64_t waves = (int64_t)S0 * ((S1 + GRID_TJ - 1) / GRID_TJ);
-    const dim3 gateGrid((unsigned)((waves + 3) / 4));
-    if (aabb && sim_in) hipLaunchKernelGGL((k_grid_gate<true, true>), gateGrid, dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
-    else if (aabb) hipLaunchKernelGGL((k_grid_gate<false, true>), gateGrid, dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
-    else if (sim_in) hipLaunchKernelGGL((k_grid_gate<true, false>), gateGrid, dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
-    else hipLaunchKernelGGL((k_grid_gate<false, false>), gateGrid, dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
+    hipLaunchKernelGGL(grid_gate_kernel(sim_in, aabb), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
     hipLaunchKernelGGL(k_grid_compact, dim3(1), dim3(B > 256 ? 1024 : 256), 0, stream, B, (int)S1, (const int32_t*)flags, pairs, n_todo);
     hipLaunchKernelGGL(k_grid_fill, dim3((unsigned)(((int64_t)B * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, (int)S1, (const int32_t*)n_todo,
                        (const int32_t*)pairs, (const double*)T_ij, time0, time1, T_ref, enable);
@@ -3140,14 +3158,7 @@ static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, i
                               const void* T_ij, const void* pairs, const void* T_ref, const void* enable, const void* todo_off,
                               int64_t* total, int64_t* tiles, int32_t* S, bool sim_in = false, bool aabb = false, const void* box = nullptr)
 {
-    if (!P) return fail(c, ROMAN_E_INVALID, "gparams is NULL");
-    if (sim_in && P->desc_dim != 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d: the similarity is given, desc_dim must be 0", P->desc_dim);
-    if (R < 0 || nb < 0) return fail(c, ROMAN_E_INVALID, "R < 0 or nb < 0");
-    if (P->reserved0 != 0 || P->reserved1 != 0 || P->reserved[0] != 0 || P->reserved[1] != 0)
-        return fail(c, ROMAN_E_INVALID, "roman_grid_gate_params_t reserved words must be 0");
-    if (!aabb && P->radius != P->radius) return fail(c, ROMAN_E_INVALID, "radius is NaN");
-    if (P->desc_dim < 0) return fail(c, ROMAN_E_INVALID, "desc_dim=%d is negative", P->desc_dim);
-    if (!aabb && P->radius < 0.0) return fail(c, ROMAN_E_UNSUPPORTED, "radius=%g: without a radius the gate is the AABB test (roman_session_gate_aabb*)", P->radius);
+    { int rc = gate_params_check(c, P, sim_in, aabb, "roman_session_gate_aabb*", R < 0 || nb < 0, "R < 0 or nb < 0"); if (rc) return rc; }
     if (!sub_off || !pair_off || !tile_off || !todo_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / tile_off / todo_off is NULL");
     bool self = false;
     { int rc = session_tables_check(c, R, sub_off, nb, blocks, pair_off, tile_off, total, tiles, &self); if (rc) return rc; }
@@ -3192,10 +3203,7 @@ static int session_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparam
     const SessionTab tab{(int)nb, sub_off, blocks, pair_off, tile_off, has_gt};
     const GridSide s{pos, pos_gt, T_w, time, desc, box};
     const GridOut out{dist, flags, yaw_deg, sim, T_ij};
-    if (aabb && sim_in) hipLaunchKernelGGL((k_session_gate<true, true>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
-    else if (aabb) hipLaunchKernelGGL((k_session_gate<false, true>), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
-    else if (sim_in) hipLaunchKernelGGL(k_session_gate<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
-    else hipLaunchKernelGGL(k_session_gate<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
+    hipLaunchKernelGGL(session_gate_kernel(sim_in, aabb), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
     hipLaunchKernelGGL(k_session_count, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, dCount);
     hipLaunchKernelGGL(k_session_scan, dim3(1), dim3(SESSION_SCAN), 0, stream, nwg, dCount, tab, total, todo_off);
     hipLaunchKernelGGL(k_session_scatter, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, (const int32_t*)dCount, tab, pairs, todo_off);
