@@ -2967,54 +2967,102 @@ static auto session_gate_kernel(bool sim_in, bool aabb)
     return aabb ? boxes : radius;
 }
 
+// --- the gates' argument blocks: what one gate call works on, under names, from the C entry point to the launch ---------------------
+// An entry point fills one from its own parameters; a host form hands the device form a copy whose arrays are the mirror's.
+// sim_in: out.sim holds every pair's similarity already and is only read, desc is not; aabb: NEARBY from the boxes, the radius is not read
+struct GridGateArgs {
+    int32_t S0, S1;
+    GridSide a, b;
+    GridOut out;
+    int32_t* pairs; double* T_ref; int32_t* enable; int32_t* n_todo;
+    bool sim_in, aabb;
+};
+
+struct SessionGateArgs {
+    int32_t R;
+    SessionTab tab;                                              // the tables on the device, and nb (host forms: only nb and has_gt, in host memory)
+    const int32_t* sub_off; const int32_t* blocks; const int64_t* pair_off; const int64_t* tile_off;    // the tables in host memory: what is checked
+    GridSide s;
+    GridOut out;
+    int32_t* pairs; double* T_ref; int32_t* enable; int32_t* todo_off;
+    bool sim_in, aabb;
+};
+
+// The similarity is given: desc is not read, and `sim` stands where the gate would write it.  The cast is safe: k_grid_gate<true, .>
+// and k_session_gate<true, .> only read out.sim, and a host form uploads it and never brings it back.
+static void gate_sim_given(GridGateArgs& g, const double* sim) { g.sim_in = true; g.a.desc = g.b.desc = nullptr; g.out.sim = const_cast<double*>(sim); }
+static void gate_sim_given(SessionGateArgs& g, const double* sim) { g.sim_in = true; g.s.desc = nullptr; g.out.sim = const_cast<double*>(sim); }
+
 // --- pass 1 of the pair loop over a grid, radius mode ([REF roman/align/submap_align.py:93-149]) -------------------
-static int grid_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int32_t S0, int32_t S1,
-                           const void* pos0, const void* T_w0, const void* time0, const void* desc0,
-                           const void* pos1, const void* T_w1, const void* time1, const void* desc1,
-                           const void* dist, const void* flags, const void* yaw_deg, const void* sim, const void* T_ij,
-                           const void* pairs, const void* T_ref, const void* enable, const void* n_todo, bool sim_in = false,
-                           bool aabb = false, const void* box0 = nullptr, const void* box1 = nullptr)
+static int grid_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, const GridGateArgs& g)
 {
-    { int rc = gate_params_check(c, P, sim_in, aabb, "roman_grid_gate_aabb*", S0 < 0 || S1 < 0, "S0 < 0 or S1 < 0"); if (rc) return rc; }
-    if (!n_todo) return fail(c, ROMAN_E_INVALID, "n_todo is NULL");
-    if (S0 == 0 || S1 == 0) return ROMAN_OK;
-    if ((int64_t)S0 * S1 > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "S0 * S1 = %lld pairs exceed the index width", (long long)S0 * S1);
-    if (P->desc_dim > 0 && (!desc0 || !desc1)) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
-    if (!pos0 || !pos1 || !T_w0 || !T_w1) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
-    if (aabb && (!box0 || !box1)) return fail(c, ROMAN_E_INVALID, "box is NULL");
-    if (P->single_robot_lc && (!time0 || !time1)) return fail(c, ROMAN_E_INVALID, "time is NULL with single_robot_lc");
-    if (!dist || !flags || !yaw_deg || !sim || !T_ij || !pairs || !T_ref || !enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
+    { int rc = gate_params_check(c, P, g.sim_in, g.aabb, "roman_grid_gate_aabb*", g.S0 < 0 || g.S1 < 0, "S0 < 0 or S1 < 0"); if (rc) return rc; }
+    if (!g.n_todo) return fail(c, ROMAN_E_INVALID, "n_todo is NULL");
+    if (g.S0 == 0 || g.S1 == 0) return ROMAN_OK;
+    if ((int64_t)g.S0 * g.S1 > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "S0 * S1 = %lld pairs exceed the index width", (long long)g.S0 * g.S1);
+    if (P->desc_dim > 0 && (!g.a.desc || !g.b.desc)) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
+    if (!g.a.pos || !g.b.pos || !g.a.T_w || !g.b.T_w) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
+    if (g.aabb && (!g.a.box || !g.b.box)) return fail(c, ROMAN_E_INVALID, "box is NULL");
+    if (P->single_robot_lc && (!g.a.time || !g.b.time)) return fail(c, ROMAN_E_INVALID, "time is NULL with single_robot_lc");
+    if (!g.out.dist || !g.out.flags || !g.out.yaw_deg || !g.out.sim || !g.out.T_ij || !g.pairs || !g.T_ref || !g.enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
     return ROMAN_OK;
 }
 
-// the device-pointer gate; sim_in: `sim` holds every pair's similarity already (roman_grid_gate_sim_dev) and is only read
-static int grid_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
-                         const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
-                         const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
-                         double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                         int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo, bool sim_in,
-                         bool aabb = false, const double* box0 = nullptr, const double* box1 = nullptr)
+// the device-pointer gate
+static int grid_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, const GridGateArgs& g)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo, sim_in,
-                             aabb, box0, box1);
+    int rc = grid_gate_check(c, gparams, g);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t stream = c->stream;
-    if (S0 == 0 || S1 == 0) { HIPCHK(c, hipMemsetAsync(n_todo, 0, sizeof(int32_t), stream)); return ROMAN_OK; }
+    const int S0 = g.S0, S1 = g.S1;
+    if (S0 == 0 || S1 == 0) { HIPCHK(c, hipMemsetAsync(g.n_todo, 0, sizeof(int32_t), stream)); return ROMAN_OK; }
     const int d = gparams->desc_dim, B = S0 * S1;
     HIPCHK(c, c->ggNorm.ensure(sizeof(double) * (size_t)(S0 + S1)));            // scratch first: a failure leaves nothing enqueued
     double* dNorm = c->ggNorm.as<double>();
-    if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S0 + S1 + 3) / 4)), dim3(256), 0, stream, (int)S0, (int)S1, d, desc0, desc1, dNorm);
-    const GridSide a{pos0, pos_gt0, T_w0, time0, desc0, box0}, b{pos1, pos_gt1, T_w1, time1, desc1, box1};
-    const GridOut out{dist, flags, yaw_deg, sim, T_ij};
+    if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S0 + S1 + 3) / 4)), dim3(256), 0, stream, S0, S1, d, g.a.desc, g.b.desc, dNorm);
     const int64_t waves = (int64_t)S0 * ((S1 + GRID_TJ - 1) / GRID_TJ);
-    hipLaunchKernelGGL(grid_gate_kernel(sim_in, aabb), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, (int)S0, (int)S1, a, b, (const double*)dNorm, out);
-    hipLaunchKernelGGL(k_grid_compact, dim3(1), dim3(B > 256 ? 1024 : 256), 0, stream, B, (int)S1, (const int32_t*)flags, pairs, n_todo);
-    hipLaunchKernelGGL(k_grid_fill, dim3((unsigned)(((int64_t)B * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, (int)S1, (const int32_t*)n_todo,
-                       (const int32_t*)pairs, (const double*)T_ij, time0, time1, T_ref, enable);
+    hipLaunchKernelGGL(grid_gate_kernel(g.sim_in, g.aabb), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, S0, S1, g.a, g.b, (const double*)dNorm, g.out);
+    hipLaunchKernelGGL(k_grid_compact, dim3(1), dim3(B > 256 ? 1024 : 256), 0, stream, B, S1, (const int32_t*)g.out.flags, g.pairs, g.n_todo);
+    hipLaunchKernelGGL(k_grid_fill, dim3((unsigned)(((int64_t)B * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, S1, (const int32_t*)g.n_todo,
+                       (const int32_t*)g.pairs, (const double*)g.out.T_ij, g.a.time, g.b.time, g.T_ref, g.enable);
     HIPCHK(c, hipGetLastError());
     return ROMAN_OK;
+}
+
+// the host-pointer gate; sim_in: the caller's sim goes up and is not brought back
+static int grid_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gparams, const GridGateArgs& h)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = grid_gate_check(c, gparams, h);
+    if (rc) return rc;
+    if (h.S0 == 0 || h.S1 == 0) { *h.n_todo = 0; return ROMAN_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const size_t d = (size_t)gparams->desc_dim, S0 = (size_t)h.S0, S1 = (size_t)h.S1, B = S0 * S1;
+    HostMirror m(c);
+    const auto in = [&m](const double* p, size_t bytes) { return m.in(p, p ? bytes : 0); };          // an optional array that is absent stays absent
+    const auto aPos = in(h.a.pos, 24 * S0), aGt = in(h.a.pos_gt, 24 * S0), aTw = in(h.a.T_w, 128 * S0), aTime = in(h.a.time, 8 * S0);
+    const auto aDesc = in(h.a.desc, 8 * d * S0), aBox = in(h.a.box, 48 * S0);
+    const auto bPos = in(h.b.pos, 24 * S1), bGt = in(h.b.pos_gt, 24 * S1), bTw = in(h.b.T_w, 128 * S1), bTime = in(h.b.time, 8 * S1);
+    const auto bDesc = in(h.b.desc, 8 * d * S1), bBox = in(h.b.box, 48 * S1);
+    const auto dDist = m.out(h.out.dist, 8 * B), dYaw = m.out(h.out.yaw_deg, 8 * B);
+    const auto dSim = h.sim_in ? m.in(h.out.sim, 8 * B) : m.out(h.out.sim, 8 * B), dTij = m.out(h.out.T_ij, 128 * B);
+    const auto dFlags = m.out(h.out.flags, 4 * B);
+    // the compact outputs are inout: the slots beyond n_todo come back as they were
+    const auto dTref = m.inout(h.T_ref, 128 * B);
+    const auto dPairs = m.inout(h.pairs, 8 * B), dEn = m.inout(h.enable, 4 * B), dCnt = m.out(h.n_todo, 4);
+    rc = m.upload();
+    if (rc) return rc;
+    GridGateArgs g = h;                                          // the same call on the mirror
+    g.a.pos = aPos.dev(); g.a.pos_gt = aGt.dev(); g.a.T_w = aTw.dev(); g.a.time = aTime.dev(); g.a.desc = aDesc.dev(); g.a.box = aBox.dev();
+    g.b.pos = bPos.dev(); g.b.pos_gt = bGt.dev(); g.b.T_w = bTw.dev(); g.b.time = bTime.dev(); g.b.desc = bDesc.dev(); g.b.box = bBox.dev();
+    g.out.dist = dDist.dev(); g.out.flags = dFlags.dev(); g.out.yaw_deg = dYaw.dev(); g.out.sim = dSim.dev(); g.out.T_ij = dTij.dev();
+    g.pairs = dPairs.dev(); g.T_ref = dTref.dev(); g.enable = dEn.dev(); g.n_todo = dCnt.dev();
+    rc = grid_gate_dev(c, gparams, g);
+    if (rc) return rc;
+    return m.download();
 }
 
 int roman_grid_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
@@ -3023,8 +3071,12 @@ int roman_grid_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams,
                         double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
                         int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
 {
-    return grid_gate_dev(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, desc0, pos1, pos_gt1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij,
-                         pairs, T_ref, enable, n_todo, false);
+    GridGateArgs g{};
+    g.S0 = S0; g.S1 = S1; g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.n_todo = n_todo;
+    g.a.pos = pos0; g.a.pos_gt = pos_gt0; g.a.T_w = T_w0; g.a.time = time0; g.a.desc = desc0;
+    g.b.pos = pos1; g.b.pos_gt = pos_gt1; g.b.T_w = T_w1; g.b.time = time1; g.b.desc = desc1;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.sim = sim; g.out.T_ij = T_ij;
+    return grid_gate_dev(c, gparams, g);
 }
 
 int roman_grid_gate_sim_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
@@ -3033,8 +3085,13 @@ int roman_grid_gate_sim_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gpar
                             double* dist, int32_t* flags, double* yaw_deg, const double* sim, double* T_ij,
                             int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
 {
-    return grid_gate_dev(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, nullptr, pos1, pos_gt1, T_w1, time1, nullptr, dist, flags, yaw_deg,
-                         const_cast<double*>(sim) /* k_grid_gate<true, .> only reads it */, T_ij, pairs, T_ref, enable, n_todo, true);
+    GridGateArgs g{};
+    g.S0 = S0; g.S1 = S1; g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.n_todo = n_todo;
+    g.a.pos = pos0; g.a.pos_gt = pos_gt0; g.a.T_w = T_w0; g.a.time = time0;
+    g.b.pos = pos1; g.b.pos_gt = pos_gt1; g.b.T_w = T_w1; g.b.time = time1;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.T_ij = T_ij;
+    gate_sim_given(g, sim);
+    return grid_gate_dev(c, gparams, g);
 }
 
 // the AABB gate: NEARBY from the boxes roman_submap_boxes_dev wrote; with sim_in the similarity is an input
@@ -3045,46 +3102,13 @@ int roman_grid_gate_aabb_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gpa
                              int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo,
                              const double* box0, const double* box1, const double* sim_in)
 {
-    return grid_gate_dev(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, sim_in ? nullptr : desc0, pos1, pos_gt1, T_w1, time1, sim_in ? nullptr : desc1,
-                         dist, flags, yaw_deg, sim_in ? const_cast<double*>(sim_in) /* only read */ : sim, T_ij, pairs, T_ref, enable, n_todo, sim_in != nullptr,
-                         true, box0, box1);
-}
-
-// the host-pointer gate; sim_in: the caller's sim goes up and is not brought back
-static int grid_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
-                          const double* pos0, const double* pos_gt0, const double* T_w0, const double* time0, const double* desc0,
-                          const double* pos1, const double* pos_gt1, const double* T_w1, const double* time1, const double* desc1,
-                          double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                          int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo, bool sim_in,
-                          bool aabb = false, const double* box0 = nullptr, const double* box1 = nullptr)
-{
-    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = grid_gate_check(c, gparams, S0, S1, pos0, T_w0, time0, desc0, pos1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, n_todo, sim_in,
-                             aabb, box0, box1);
-    if (rc) return rc;
-    if (S0 == 0 || S1 == 0) { *n_todo = 0; return ROMAN_OK; }
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    const size_t d = (size_t)gparams->desc_dim, B = (size_t)S0 * (size_t)S1;
-    HostMirror m(c);
-    const double* side[2][6] = {{pos0, pos_gt0, T_w0, time0, desc0, box0}, {pos1, pos_gt1, T_w1, time1, desc1, box1}};
-    const size_t S[2] = {(size_t)S0, (size_t)S1}, per[6] = {3, 3, 16, 1, d, 6};
-    HostMirror::Piece<double> dIn[2][6];
-    for (int r = 0; r < 2; ++r)
-        for (int k = 0; k < 6; ++k) dIn[r][k] = m.in(side[r][k], side[r][k] ? sizeof(double) * per[k] * S[r] : 0);
-    const auto dDist = m.out(dist, 8 * B), dYaw = m.out(yaw_deg, 8 * B), dSim = sim_in ? m.in(sim, 8 * B) : m.out(sim, 8 * B), dTij = m.out(T_ij, 128 * B);
-    const auto dFlags = m.out(flags, 4 * B);
-    // the compact outputs are inout: the slots beyond n_todo come back as they were
-    const auto dTref = m.inout(T_ref, 128 * B);
-    const auto dPairs = m.inout(pairs, 8 * B), dEn = m.inout(enable, 4 * B), dCnt = m.out(n_todo, 4);
-    rc = m.upload();
-    if (rc) return rc;
-    rc = grid_gate_dev(c, gparams, S0, S1, dIn[0][0].dev(), dIn[0][1].dev(), dIn[0][2].dev(), dIn[0][3].dev(), dIn[0][4].dev(),
-                       dIn[1][0].dev(), dIn[1][1].dev(), dIn[1][2].dev(), dIn[1][3].dev(), dIn[1][4].dev(),
-                       dDist.dev(), dFlags.dev(), dYaw.dev(), dSim.dev(), dTij.dev(), dPairs.dev(), dTref.dev(), dEn.dev(), dCnt.dev(), sim_in,
-                       aabb, dIn[0][5].dev(), dIn[1][5].dev());
-    if (rc) return rc;
-    return m.download();
+    GridGateArgs g{};
+    g.S0 = S0; g.S1 = S1; g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.n_todo = n_todo; g.aabb = true;
+    g.a.pos = pos0; g.a.pos_gt = pos_gt0; g.a.T_w = T_w0; g.a.time = time0; g.a.desc = desc0; g.a.box = box0;
+    g.b.pos = pos1; g.b.pos_gt = pos_gt1; g.b.T_w = T_w1; g.b.time = time1; g.b.desc = desc1; g.b.box = box1;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.sim = sim; g.out.T_ij = T_ij;
+    if (sim_in) gate_sim_given(g, sim_in);
+    return grid_gate_dev(c, gparams, g);
 }
 
 int roman_grid_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
@@ -3093,8 +3117,12 @@ int roman_grid_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int
                     double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
                     int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
 {
-    return grid_gate_host(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, desc0, pos1, pos_gt1, T_w1, time1, desc1, dist, flags, yaw_deg, sim, T_ij,
-                          pairs, T_ref, enable, n_todo, false);
+    GridGateArgs g{};
+    g.S0 = S0; g.S1 = S1; g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.n_todo = n_todo;
+    g.a.pos = pos0; g.a.pos_gt = pos_gt0; g.a.T_w = T_w0; g.a.time = time0; g.a.desc = desc0;
+    g.b.pos = pos1; g.b.pos_gt = pos_gt1; g.b.T_w = T_w1; g.b.time = time1; g.b.desc = desc1;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.sim = sim; g.out.T_ij = T_ij;
+    return grid_gate_host(c, gparams, g);
 }
 
 int roman_grid_gate_sim(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
@@ -3103,8 +3131,13 @@ int roman_grid_gate_sim(roman_ctx_t* c, const roman_grid_gate_params_t* gparams,
                         double* dist, int32_t* flags, double* yaw_deg, const double* sim, double* T_ij,
                         int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo)
 {
-    return grid_gate_host(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, nullptr, pos1, pos_gt1, T_w1, time1, nullptr, dist, flags, yaw_deg,
-                          const_cast<double*>(sim) /* uploaded, never written */, T_ij, pairs, T_ref, enable, n_todo, true);
+    GridGateArgs g{};
+    g.S0 = S0; g.S1 = S1; g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.n_todo = n_todo;
+    g.a.pos = pos0; g.a.pos_gt = pos_gt0; g.a.T_w = T_w0; g.a.time = time0;
+    g.b.pos = pos1; g.b.pos_gt = pos_gt1; g.b.T_w = T_w1; g.b.time = time1;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.T_ij = T_ij;
+    gate_sim_given(g, sim);
+    return grid_gate_host(c, gparams, g);
 }
 
 int roman_grid_gate_aabb(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t S0, int32_t S1,
@@ -3114,9 +3147,13 @@ int roman_grid_gate_aabb(roman_ctx_t* c, const roman_grid_gate_params_t* gparams
                          int32_t* pairs, double* T_ref, int32_t* enable, int32_t* n_todo,
                          const double* box0, const double* box1, const double* sim_in)
 {
-    return grid_gate_host(c, gparams, S0, S1, pos0, pos_gt0, T_w0, time0, sim_in ? nullptr : desc0, pos1, pos_gt1, T_w1, time1, sim_in ? nullptr : desc1,
-                          dist, flags, yaw_deg, sim_in ? const_cast<double*>(sim_in) /* uploaded, never written */ : sim, T_ij, pairs, T_ref, enable, n_todo,
-                          sim_in != nullptr, true, box0, box1);
+    GridGateArgs g{};
+    g.S0 = S0; g.S1 = S1; g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.n_todo = n_todo; g.aabb = true;
+    g.a.pos = pos0; g.a.pos_gt = pos_gt0; g.a.T_w = T_w0; g.a.time = time0; g.a.desc = desc0; g.a.box = box0;
+    g.b.pos = pos1; g.b.pos_gt = pos_gt1; g.b.T_w = T_w1; g.b.time = time1; g.b.desc = desc1; g.b.box = box1;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.sim = sim; g.out.T_ij = T_ij;
+    if (sim_in) gate_sim_given(g, sim_in);
+    return grid_gate_host(c, gparams, g);
 }
 
 // --- pass 1 of a multi-robot session: the grids of a list of robot pairs in one launch sequence -------------------
@@ -3151,66 +3188,90 @@ static int session_tables_check(roman_ctx* c, int32_t R, const int32_t* sub_off,
     return ROMAN_OK;
 }
 
-// sim_in: `sim` holds every pair's similarity already (roman_session_gate_sim*): desc_dim must be 0
-static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, int32_t R, const int32_t* sub_off, const void* pos, const void* pos_gt,
-                              const void* has_gt, const void* T_w, const void* time, const void* desc, int32_t nb, const int32_t* blocks,
-                              const int64_t* pair_off, const int64_t* tile_off, const void* dist, const void* flags, const void* yaw_deg, const void* sim,
-                              const void* T_ij, const void* pairs, const void* T_ref, const void* enable, const void* todo_off,
-                              int64_t* total, int64_t* tiles, int32_t* S, bool sim_in = false, bool aabb = false, const void* box = nullptr)
+// the tables are judged on their host copies; what passes has pair_off[nb] pairs, tile_off[nb] tiles and sub_off[R] submaps
+static int session_gate_check(roman_ctx* c, const roman_grid_gate_params_t* P, const SessionGateArgs& g)
 {
-    { int rc = gate_params_check(c, P, sim_in, aabb, "roman_session_gate_aabb*", R < 0 || nb < 0, "R < 0 or nb < 0"); if (rc) return rc; }
-    if (!sub_off || !pair_off || !tile_off || !todo_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / tile_off / todo_off is NULL");
+    const int32_t R = g.R, nb = g.tab.nb;
+    { int rc = gate_params_check(c, P, g.sim_in, g.aabb, "roman_session_gate_aabb*", R < 0 || nb < 0, "R < 0 or nb < 0"); if (rc) return rc; }
+    if (!g.sub_off || !g.pair_off || !g.tile_off || !g.todo_off || (nb > 0 && !g.blocks)) return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / tile_off / todo_off is NULL");
     bool self = false;
-    { int rc = session_tables_check(c, R, sub_off, nb, blocks, pair_off, tile_off, total, tiles, &self); if (rc) return rc; }
-    const int64_t po = *total;
-    *S = sub_off[R];
-    if (po == 0) return ROMAN_OK;
-    if (P->desc_dim > 0 && !desc) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
-    if (!pos || !T_w) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
-    if (aabb && !box) return fail(c, ROMAN_E_INVALID, "box is NULL");
-    if (pos_gt && !has_gt) return fail(c, ROMAN_E_INVALID, "has_gt is NULL with pos_gt");
-    if (self && !time) return fail(c, ROMAN_E_INVALID, "time is NULL with a self_lc block");
-    if (!dist || !flags || !yaw_deg || !sim || !T_ij || !pairs || !T_ref || !enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
+    int64_t total = 0, tiles = 0;
+    { int rc = session_tables_check(c, R, g.sub_off, nb, g.blocks, g.pair_off, g.tile_off, &total, &tiles, &self); if (rc) return rc; }
+    if (total == 0) return ROMAN_OK;
+    if (P->desc_dim > 0 && !g.s.desc) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
+    if (!g.s.pos || !g.s.T_w) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
+    if (g.aabb && !g.s.box) return fail(c, ROMAN_E_INVALID, "box is NULL");
+    if (g.s.pos_gt && !g.tab.has_gt) return fail(c, ROMAN_E_INVALID, "has_gt is NULL with pos_gt");
+    if (self && !g.s.time) return fail(c, ROMAN_E_INVALID, "time is NULL with a self_lc block");
+    if (!g.out.dist || !g.out.flags || !g.out.yaw_deg || !g.out.sim || !g.out.T_ij || !g.pairs || !g.T_ref || !g.enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
     return ROMAN_OK;
 }
 
-// the device-pointer session gate; sim_in: `sim` holds every pair's similarity already (roman_session_gate_sim_dev) and is only read
-static int session_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
-                            const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
-                            int32_t nb, const int32_t* blocks, const int32_t* blocks_host,
-                            const int64_t* pair_off, const int64_t* pair_off_host, const int64_t* tile_off, const int64_t* tile_off_host,
-                            double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                            int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, bool sim_in,
-                            bool aabb = false, const double* box = nullptr)
+// the device-pointer session gate
+static int session_gate_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, const SessionGateArgs& g)
 {
+    const SessionTab& tab = g.tab;
     // (the arguments are judged first — on host memory only, a NULL context included: fail() then keeps the text for roman_last_error(NULL))
-    if (!sub_off || !pair_off || !tile_off || (nb > 0 && !blocks)) return fail(c, ROMAN_E_INVALID, "a table is NULL on the device");
-    int64_t total = 0, tiles = 0; int32_t S = 0;
-    int rc = session_gate_check(c, gparams, R, sub_off_host, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks_host, pair_off_host, tile_off_host,
-                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S, sim_in, aabb, box);
+    if (!tab.sub_off || !tab.pair_off || !tab.tile_off || (tab.nb > 0 && !tab.blocks)) return fail(c, ROMAN_E_INVALID, "a table is NULL on the device");
+    int rc = session_gate_check(c, gparams, g);
     if (rc) return rc;
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t stream = c->stream;
-    if (total == 0) { HIPCHK(c, hipMemsetAsync(todo_off, 0, sizeof(int32_t) * (size_t)(nb + 1), stream)); return ROMAN_OK; }
-    const int d = sim_in ? 0 : gparams->desc_dim;
+    const int64_t total = g.pair_off[tab.nb], tiles = g.tile_off[tab.nb];
+    const int S = g.sub_off[g.R];
+    if (total == 0) { HIPCHK(c, hipMemsetAsync(g.todo_off, 0, sizeof(int32_t) * (size_t)(tab.nb + 1), stream)); return ROMAN_OK; }
+    const int d = g.sim_in ? 0 : gparams->desc_dim;
     const int nwg = (int)((total + SESSION_SCAN - 1) / SESSION_SCAN);
     HIPCHK(c, c->ggNorm.ensure(sizeof(double) * (size_t)S));                    // scratch first: a failure leaves nothing enqueued
     HIPCHK(c, c->sgCount.ensure(sizeof(int32_t) * (size_t)nwg));
     double* dNorm = c->ggNorm.as<double>();
     int32_t* dCount = c->sgCount.as<int32_t>();
-    if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, stream, (int)S, 0, d, desc, (const double*)nullptr, dNorm);
-    const SessionTab tab{(int)nb, sub_off, blocks, pair_off, tile_off, has_gt};
-    const GridSide s{pos, pos_gt, T_w, time, desc, box};
-    const GridOut out{dist, flags, yaw_deg, sim, T_ij};
-    hipLaunchKernelGGL(session_gate_kernel(sim_in, aabb), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, s, (const double*)dNorm, out);
-    hipLaunchKernelGGL(k_session_count, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, dCount);
-    hipLaunchKernelGGL(k_session_scan, dim3(1), dim3(SESSION_SCAN), 0, stream, nwg, dCount, tab, total, todo_off);
-    hipLaunchKernelGGL(k_session_scatter, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)flags, (const int32_t*)dCount, tab, pairs, todo_off);
-    hipLaunchKernelGGL(k_session_fill, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, tab, (const int32_t*)todo_off,
-                       (const int32_t*)pairs, (const double*)T_ij, time, T_ref, enable);
+    if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, stream, S, 0, d, g.s.desc, (const double*)nullptr, dNorm);
+    hipLaunchKernelGGL(session_gate_kernel(g.sim_in, g.aabb), dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, *gparams, tab, tiles, g.s, (const double*)dNorm, g.out);
+    hipLaunchKernelGGL(k_session_count, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)g.out.flags, dCount);
+    hipLaunchKernelGGL(k_session_scan, dim3(1), dim3(SESSION_SCAN), 0, stream, nwg, dCount, tab, total, g.todo_off);
+    hipLaunchKernelGGL(k_session_scatter, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, total, (const int32_t*)g.out.flags, (const int32_t*)dCount, tab, g.pairs, g.todo_off);
+    hipLaunchKernelGGL(k_session_fill, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, tab, (const int32_t*)g.todo_off,
+                       (const int32_t*)g.pairs, (const double*)g.out.T_ij, g.s.time, g.T_ref, g.enable);
     HIPCHK(c, hipGetLastError());
     return ROMAN_OK;
+}
+
+// the host-pointer session gate; sim_in: the caller's `sim` goes up and is not brought back
+static int session_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gparams, const SessionGateArgs& h)
+{
+    int rc = session_gate_check(c, gparams, h);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    const size_t R = (size_t)h.R, nb = (size_t)h.tab.nb, B = (size_t)h.pair_off[nb], nS = (size_t)h.sub_off[R];
+    if (B == 0) { std::fill(h.todo_off, h.todo_off + nb + 1, 0); return ROMAN_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const size_t d = (size_t)gparams->desc_dim;
+    HostMirror m(c);
+    const auto dSub = m.in(h.sub_off, 4 * (R + 1)), dBlk = m.in(h.blocks, 16 * nb);
+    const auto dPo = m.in(h.pair_off, 8 * (nb + 1)), dTo = m.in(h.tile_off, 8 * (nb + 1));
+    const auto dPos = m.in(h.s.pos, 24 * nS), dGt = m.in(h.s.pos_gt, h.s.pos_gt ? 24 * nS : 0);
+    const auto dHas = m.in(h.tab.has_gt, h.s.pos_gt ? 4 * R : 0);
+    const auto dTw = m.in(h.s.T_w, 128 * nS), dTime = m.in(h.s.time, h.s.time ? 8 * nS : 0), dDesc = m.in(h.s.desc, h.s.desc ? 8 * d * nS : 0);
+    const auto dBox = m.in(h.s.box, h.aabb ? 48 * nS : 0);
+    const auto dDist = m.out(h.out.dist, 8 * B), dYaw = m.out(h.out.yaw_deg, 8 * B);
+    const auto dSim = h.sim_in ? m.in(h.out.sim, 8 * B) : m.out(h.out.sim, 8 * B), dTij = m.out(h.out.T_ij, 128 * B);
+    const auto dFlags = m.out(h.out.flags, 4 * B);
+    // the compact outputs are inout: the slots beyond todo_off[nb] come back as they were
+    const auto dTref = m.inout(h.T_ref, 128 * B);
+    const auto dPairs = m.inout(h.pairs, 8 * B), dEn = m.inout(h.enable, 4 * B), dOff = m.out(h.todo_off, 4 * (nb + 1));
+    rc = m.upload();
+    if (rc) return rc;
+    SessionGateArgs g = h;                                       // the same call on the mirror; the host tables stay the caller's
+    g.tab.sub_off = dSub.dev(); g.tab.blocks = dBlk.dev(); g.tab.pair_off = dPo.dev(); g.tab.tile_off = dTo.dev(); g.tab.has_gt = dHas.dev();
+    g.s.pos = dPos.dev(); g.s.pos_gt = dGt.dev(); g.s.T_w = dTw.dev(); g.s.time = dTime.dev(); g.s.desc = dDesc.dev(); g.s.box = dBox.dev();
+    g.out.dist = dDist.dev(); g.out.flags = dFlags.dev(); g.out.yaw_deg = dYaw.dev(); g.out.sim = dSim.dev(); g.out.T_ij = dTij.dev();
+    g.pairs = dPairs.dev(); g.T_ref = dTref.dev(); g.enable = dEn.dev(); g.todo_off = dOff.dev();
+    rc = session_gate_dev(c, gparams, g);
+    if (rc) return rc;
+    return m.download();
 }
 
 int roman_session_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
@@ -3220,8 +3281,13 @@ int roman_session_gate_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gpara
                            double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
                            int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
 {
-    return session_gate_dev(c, gparams, R, sub_off, sub_off_host, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks, blocks_host, pair_off, pair_off_host,
-                            tile_off, tile_off_host, dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, false);
+    SessionGateArgs g{};
+    g.R = R; g.tab.nb = nb; g.tab.sub_off = sub_off; g.tab.blocks = blocks; g.tab.pair_off = pair_off; g.tab.tile_off = tile_off; g.tab.has_gt = has_gt;
+    g.sub_off = sub_off_host; g.blocks = blocks_host; g.pair_off = pair_off_host; g.tile_off = tile_off_host;
+    g.s.pos = pos; g.s.pos_gt = pos_gt; g.s.T_w = T_w; g.s.time = time; g.s.desc = desc;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.sim = sim; g.out.T_ij = T_ij;
+    g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.todo_off = todo_off;
+    return session_gate_dev(c, gparams, g);
 }
 
 // `desc` is not read and `sim` is not written (both may be NULL): the similarity is sim_in
@@ -3233,69 +3299,14 @@ int roman_session_gate_sim_dev(roman_ctx_t* c, const roman_grid_gate_params_t* g
                                int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* sim_in)
 {
     (void)desc; (void)sim;
-    return session_gate_dev(c, gparams, R, sub_off, sub_off_host, pos, pos_gt, has_gt, T_w, time, nullptr, nb, blocks, blocks_host, pair_off, pair_off_host,
-                            tile_off, tile_off_host, dist, flags, yaw_deg, const_cast<double*>(sim_in) /* k_session_gate<true> only reads it */, T_ij,
-                            pairs, T_ref, enable, todo_off, true);
-}
-
-// the host-pointer session gate; sim_in: the caller's `sim` goes up and is not brought back
-static int session_gate_host(roman_ctx* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
-                             const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
-                             int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
-                             double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                             int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, bool sim_in,
-                             bool aabb = false, const double* box = nullptr)
-{
-    int64_t total = 0, tiles = 0; int32_t S = 0;
-    int rc = session_gate_check(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks, pair_off, tile_off,
-                                dist, flags, yaw_deg, sim, T_ij, pairs, T_ref, enable, todo_off, &total, &tiles, &S, sim_in, aabb, box);
-    if (rc) return rc;
-    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    if (total == 0) { std::fill(todo_off, todo_off + nb + 1, 0); return ROMAN_OK; }
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    const size_t d = (size_t)gparams->desc_dim, B = (size_t)total, nS = (size_t)S;
-    HostMirror m(c);
-    const auto dSub = m.in(sub_off, 4 * ((size_t)R + 1)), dBlk = m.in(blocks, 16 * (size_t)nb);
-    const auto dPo = m.in(pair_off, 8 * ((size_t)nb + 1)), dTo = m.in(tile_off, 8 * ((size_t)nb + 1));
-    const auto dPos = m.in(pos, 24 * nS), dGt = m.in(pos_gt, pos_gt ? 24 * nS : 0);
-    const auto dHas = m.in(has_gt, pos_gt ? 4 * (size_t)R : 0);
-    const auto dTw = m.in(T_w, 128 * nS), dTime = m.in(time, time ? 8 * nS : 0), dDesc = m.in(desc, desc ? 8 * d * nS : 0);
-    const auto dBox = m.in(box, aabb ? 48 * nS : 0);
-    const auto dDist = m.out(dist, 8 * B), dYaw = m.out(yaw_deg, 8 * B), dSim = sim_in ? m.in(sim, 8 * B) : m.out(sim, 8 * B), dTij = m.out(T_ij, 128 * B);
-    const auto dFlags = m.out(flags, 4 * B);
-    // the compact outputs are inout: the slots beyond todo_off[nb] come back as they were
-    const auto dTref = m.inout(T_ref, 128 * B);
-    const auto dPairs = m.inout(pairs, 8 * B), dEn = m.inout(enable, 4 * B), dOff = m.out(todo_off, 4 * ((size_t)nb + 1));
-    rc = m.upload();
-    if (rc) return rc;
-    rc = session_gate_dev(c, gparams, R, dSub.dev(), sub_off, dPos.dev(), dGt.dev(), dHas.dev(), dTw.dev(), dTime.dev(), dDesc.dev(),
-                          nb, dBlk.dev(), blocks, dPo.dev(), pair_off, dTo.dev(), tile_off,
-                          dDist.dev(), dFlags.dev(), dYaw.dev(), dSim.dev(), dTij.dev(), dPairs.dev(), dTref.dev(), dEn.dev(), dOff.dev(), sim_in,
-                          aabb, dBox.dev());
-    if (rc) return rc;
-    return m.download();
-}
-
-int roman_session_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
-                       const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
-                       int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
-                       double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                       int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
-{
-    return session_gate_host(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, desc, nb, blocks, pair_off, tile_off, dist, flags, yaw_deg, sim, T_ij,
-                             pairs, T_ref, enable, todo_off, false);
-}
-
-int roman_session_gate_sim(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
-                           const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
-                           int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
-                           double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
-                           int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* sim_in)
-{
-    (void)desc; (void)sim;
-    return session_gate_host(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, nullptr, nb, blocks, pair_off, tile_off, dist, flags, yaw_deg,
-                             const_cast<double*>(sim_in) /* uploaded, never written */, T_ij, pairs, T_ref, enable, todo_off, true);
+    SessionGateArgs g{};
+    g.R = R; g.tab.nb = nb; g.tab.sub_off = sub_off; g.tab.blocks = blocks; g.tab.pair_off = pair_off; g.tab.tile_off = tile_off; g.tab.has_gt = has_gt;
+    g.sub_off = sub_off_host; g.blocks = blocks_host; g.pair_off = pair_off_host; g.tile_off = tile_off_host;
+    g.s.pos = pos; g.s.pos_gt = pos_gt; g.s.T_w = T_w; g.s.time = time;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.T_ij = T_ij;
+    g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.todo_off = todo_off;
+    gate_sim_given(g, sim_in);
+    return session_gate_dev(c, gparams, g);
 }
 
 // the AABB gate of a session: NEARBY from the boxes roman_session_boxes_dev wrote; with sim_in the similarity is an
@@ -3307,9 +3318,44 @@ int roman_session_gate_aabb_dev(roman_ctx_t* c, const roman_grid_gate_params_t* 
                                 double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
                                 int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* box, const double* sim_in)
 {
-    return session_gate_dev(c, gparams, R, sub_off, sub_off_host, pos, pos_gt, has_gt, T_w, time, sim_in ? nullptr : desc, nb, blocks, blocks_host,
-                            pair_off, pair_off_host, tile_off, tile_off_host, dist, flags, yaw_deg, sim_in ? const_cast<double*>(sim_in) /* only read */ : sim, T_ij,
-                            pairs, T_ref, enable, todo_off, sim_in != nullptr, true, box);
+    SessionGateArgs g{};
+    g.R = R; g.tab.nb = nb; g.tab.sub_off = sub_off; g.tab.blocks = blocks; g.tab.pair_off = pair_off; g.tab.tile_off = tile_off; g.tab.has_gt = has_gt;
+    g.sub_off = sub_off_host; g.blocks = blocks_host; g.pair_off = pair_off_host; g.tile_off = tile_off_host;
+    g.s.pos = pos; g.s.pos_gt = pos_gt; g.s.T_w = T_w; g.s.time = time; g.s.desc = desc; g.s.box = box; g.aabb = true;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.sim = sim; g.out.T_ij = T_ij;
+    g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.todo_off = todo_off;
+    if (sim_in) gate_sim_given(g, sim_in);
+    return session_gate_dev(c, gparams, g);
+}
+
+int roman_session_gate(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                       const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                       int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                       double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                       int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
+{
+    SessionGateArgs g{};
+    g.R = R; g.tab.nb = nb; g.tab.has_gt = has_gt; g.sub_off = sub_off; g.blocks = blocks; g.pair_off = pair_off; g.tile_off = tile_off;
+    g.s.pos = pos; g.s.pos_gt = pos_gt; g.s.T_w = T_w; g.s.time = time; g.s.desc = desc;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.sim = sim; g.out.T_ij = T_ij;
+    g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.todo_off = todo_off;
+    return session_gate_host(c, gparams, g);
+}
+
+int roman_session_gate_sim(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                           const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                           int32_t nb, const int32_t* blocks, const int64_t* pair_off, const int64_t* tile_off,
+                           double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                           int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* sim_in)
+{
+    (void)desc; (void)sim;
+    SessionGateArgs g{};
+    g.R = R; g.tab.nb = nb; g.tab.has_gt = has_gt; g.sub_off = sub_off; g.blocks = blocks; g.pair_off = pair_off; g.tile_off = tile_off;
+    g.s.pos = pos; g.s.pos_gt = pos_gt; g.s.T_w = T_w; g.s.time = time;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.T_ij = T_ij;
+    g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.todo_off = todo_off;
+    gate_sim_given(g, sim_in);
+    return session_gate_host(c, gparams, g);
 }
 
 int roman_session_gate_aabb(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
@@ -3318,9 +3364,13 @@ int roman_session_gate_aabb(roman_ctx_t* c, const roman_grid_gate_params_t* gpar
                             double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
                             int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* box, const double* sim_in)
 {
-    return session_gate_host(c, gparams, R, sub_off, pos, pos_gt, has_gt, T_w, time, sim_in ? nullptr : desc, nb, blocks, pair_off, tile_off, dist, flags, yaw_deg,
-                             sim_in ? const_cast<double*>(sim_in) /* uploaded, never written */ : sim, T_ij, pairs, T_ref, enable, todo_off,
-                             sim_in != nullptr, true, box);
+    SessionGateArgs g{};
+    g.R = R; g.tab.nb = nb; g.tab.has_gt = has_gt; g.sub_off = sub_off; g.blocks = blocks; g.pair_off = pair_off; g.tile_off = tile_off;
+    g.s.pos = pos; g.s.pos_gt = pos_gt; g.s.T_w = T_w; g.s.time = time; g.s.desc = desc; g.s.box = box; g.aabb = true;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.sim = sim; g.out.T_ij = T_ij;
+    g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.todo_off = todo_off;
+    if (sim_in) gate_sim_given(g, sim_in);
+    return session_gate_host(c, gparams, g);
 }
 
 // --- frame descriptors of the submaps of a pool ([REF roman/map/map.py:210-242], [REF :155-162]) ------------------

@@ -612,10 +612,11 @@ class Context:
         return self._grid_gate_host("roman_grid_gate", gparams, (pos0, T_w0, time0, desc0, pos_gt0, None), (pos1, T_w1, time1, desc1, pos_gt1, None),
                                     pairs, T_ref, enable)
 
-    def _grid_gate_host(self, fn, gparams, side0, side1, pairs, T_ref, enable, sim_in=None, sim_name="sim_in"):
+    def _grid_gate_host(self, fn, gparams, side0, side1, pairs, T_ref, enable, sim_in=None, sim_name="sim_in", has_desc=True, aabb=False):
         """The host-pointer gate behind grid_gate / grid_gate_sim / grid_gate_aabb: a side is (pos, T_w, time, desc, pos_gt, box);
-        only roman_grid_gate_aabb reads box, and with sim_in (the similarity is an input) desc is not read."""
-        aabb, side = fn == "roman_grid_gate_aabb", []
+        with sim_in (the similarity is an input) desc is not read.  What the entry `fn` carries: has_desc, a desc per side;
+        aabb, the boxes and sim_in behind the outputs (without it a given similarity goes in the sim slot)."""
+        side = []
         for pos, T_w, tm, desc, gt, box in (side0, side1):
             pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
             T_w = _f64(T_w).reshape(-1, 16); box = _f64(box).reshape(-1, 6) if aabb else None
@@ -638,11 +639,10 @@ class Context:
         sim = np.zeros((S0, S1)) if sim_in is None else None
         T_ij = np.zeros((S0, S1, 4, 4)); n_todo = np.zeros(1, dtype=np.int32)
         self._generation += 1
-        # roman_grid_gate_sim takes no desc and the similarity in the sim slot; roman_grid_gate_aabb the boxes and sim_in behind the outputs
-        ins = [_ptr(a) for s in side for a in s[1:(5 if fn == "roman_grid_gate_sim" else 6)]]
+        ins = [_ptr(a) for s in side for a in s[1:(6 if has_desc else 5)]]
         tail = [_ptr(side[0][6]), _ptr(side[1][6]), _ptr(sim_in)] if aabb else []
         rc = getattr(self._lib, fn)(self._h, C.byref(gparams), S0, S1, *ins, _ptr(dist), _ptr(flags), _ptr(yaw),
-                                    _ptr(sim_in if fn == "roman_grid_gate_sim" else sim), _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(n_todo), *tail)
+                                    _ptr(sim if aabb or sim_in is None else sim_in), _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(n_todo), *tail)
         self._check(rc, fn)
         return GridGateResult(dist, flags, yaw, sim if sim_in is None else sim_in, T_ij, pairs, T_ref, enable, int(n_todo[0]))
 
@@ -666,7 +666,7 @@ class Context:
         """grid_gate() on a similarity that is already there (roman_grid_gate_sim): `sim` (S0, S1) is read, never written;
         gparams.desc_dim must be 0.  -> GridGateResult whose sim is the array handed in."""
         return self._grid_gate_host("roman_grid_gate_sim", gparams, (pos0, T_w0, time0, None, pos_gt0, None), (pos1, T_w1, time1, None, pos_gt1, None),
-                                    pairs, T_ref, enable, sim_in=_f64(sim), sim_name="sim")
+                                    pairs, T_ref, enable, sim_in=_f64(sim), sim_name="sim", has_desc=False)
 
     def grid_gate_sim_dev(self, gparams, S0, S1, pos0_ptr, T_w0_ptr, pos1_ptr, T_w1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
                           pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr, time0_ptr=None, time1_ptr=None, pos_gt0_ptr=None, pos_gt1_ptr=None):
@@ -676,6 +676,23 @@ class Context:
                             pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr)
 
     # ------------------------------------------------------------------ pass 1 of every robot pair of a session
+    @staticmethod
+    def _session_gate_tables(sub_off, blocks, pair_off, tile_off):
+        sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
+        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
+        R, nb = len(sub_off) - 1, len(blocks)
+        if R < 0 or len(pair_off) != nb + 1 or len(tile_off) != nb + 1:
+            raise ValueError("sub_off must hold R + 1 entries, pair_off and tile_off nb + 1")
+        return sub_off, blocks, pair_off, tile_off, R, nb
+
+    @staticmethod
+    def _session_gate_entry(box, sim_in):
+        """-> the stem of the C entry that serves (box, sim_in) and what follows its outputs: roman_session_gate_aabb* carries
+        both, given or not; roman_session_gate_sim* the similarity alone."""
+        if box is not None:
+            return "roman_session_gate_aabb", (box, sim_in)
+        return ("roman_session_gate", ()) if sim_in is None else ("roman_session_gate_sim", (sim_in,))
+
     def session_gate(self, gparams, sub_off, blocks, pair_off, tile_off, pos, T_w, time=None, desc=None, pos_gt=None, has_gt=None,
                      pairs=None, T_ref=None, enable=None, sim_in=None, box=None):
         """Host-pointer pass 1 over a list of robot pairs (roman_session_gate): the tables as session_tables() gives them (they are
@@ -684,11 +701,7 @@ class Context:
         outputs may be handed in, as grid_gate() takes them.  sim_in (pair_off[nb],): the similarity of every pair is given
         (roman_session_gate_sim; gparams.desc_dim must be 0) and comes back as `sim`.  box (S, 6): the bounding-box gate
         (roman_session_gate_aabb, DESIGN.md §4.16: session_gate_aabb() below).  -> SessionGateResult."""
-        sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
-        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
-        R, nb = len(sub_off) - 1, len(blocks)
-        if R < 0 or len(pair_off) != nb + 1 or len(tile_off) != nb + 1:
-            raise ValueError("sub_off must hold R + 1 entries, pair_off and tile_off nb + 1")
+        sub_off, blocks, pair_off, tile_off, R, nb = self._session_gate_tables(sub_off, blocks, pair_off, tile_off)
         pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
         T_w = _f64(T_w).reshape(-1, 16)
         time = None if time is None else _f64(time).reshape(-1)
@@ -705,7 +718,8 @@ class Context:
         dist = np.zeros(B); flags = np.zeros(B, dtype=np.int32); yaw = np.zeros(B); sim = np.zeros(B); T_ij = np.zeros((B, 4, 4))
         todo_off = np.zeros(nb + 1, dtype=np.int32)
         self._generation += 1
-        if sim_in is not None:
+        given = sim_in is not None
+        if given:
             sim = _f64(sim_in).reshape(-1).copy()
             if sim.shape[0] != B:
                 raise ValueError("sim_in must hold pair_off[nb] entries")
@@ -713,23 +727,12 @@ class Context:
             box = _f64(box).reshape(-1, 6)
             if box.shape[0] != S:
                 raise ValueError("box must hold one row per submap of the session")
-            given = sim_in is not None
-            rc = self._lib.roman_session_gate_aabb(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
-                                                   None if given else _ptr(desc), nb, _ptr(blocks), _ptr(pair_off), _ptr(tile_off), _ptr(dist), _ptr(flags),
-                                                   _ptr(yaw), None if given else _ptr(sim), _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off),
-                                                   _ptr(box), _ptr(sim) if given else None)
-            self._check(rc, "roman_session_gate_aabb")
-            return SessionGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, todo_off, pair_off)
-        if sim_in is not None:
-            rc = self._lib.roman_session_gate_sim(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
-                                                  None, nb, _ptr(blocks), _ptr(pair_off), _ptr(tile_off), _ptr(dist), _ptr(flags), _ptr(yaw), None,
-                                                  _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off), _ptr(sim))
-            self._check(rc, "roman_session_gate_sim")
-            return SessionGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, todo_off, pair_off)
-        rc = self._lib.roman_session_gate(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
-                                          _ptr(desc), nb, _ptr(blocks), _ptr(pair_off), _ptr(tile_off), _ptr(dist), _ptr(flags), _ptr(yaw), _ptr(sim),
-                                          _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off))
-        self._check(rc, "roman_session_gate")
+        # a given similarity travels behind the outputs: the desc and sim slots are then empty
+        fn, tail = self._session_gate_entry(box, sim if given else None)
+        rc = getattr(self._lib, fn)(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
+                                    None if given else _ptr(desc), nb, _ptr(blocks), _ptr(pair_off), _ptr(tile_off), _ptr(dist), _ptr(flags), _ptr(yaw),
+                                    None if given else _ptr(sim), _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off), *map(_ptr, tail))
+        self._check(rc, fn)
         return SessionGateResult(dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, todo_off, pair_off)
 
     def session_gate_dev(self, gparams, sub_off, blocks, pair_off, tile_off, sub_off_ptr, blocks_ptr, pair_off_ptr, tile_off_ptr, pos_ptr, T_w_ptr,
@@ -741,22 +744,13 @@ class Context:
         all submaps of the session, its two columns are lc_tail_dev's iL and iR.  sim_in_ptr: the similarity of every pair is
         given (roman_session_gate_sim_dev): gparams.desc_dim must be 0, desc_ptr is not read, sim_ptr not written.
         box_ptr: the bounding-box gate (roman_session_gate_aabb_dev, DESIGN.md §4.16: session_gate_aabb_dev() below)."""
-        sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
-        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
-        R, nb = len(sub_off) - 1, len(blocks)
-        if R < 0 or len(pair_off) != nb + 1 or len(tile_off) != nb + 1:
-            raise ValueError("sub_off must hold R + 1 entries, pair_off and tile_off nb + 1")
-        args = (self._h, C.byref(gparams), R, _vp(sub_off_ptr), _ptr(sub_off), _vp(pos_ptr), _vp(pos_gt_ptr), _vp(has_gt_ptr),
-                _vp(T_w_ptr), _vp(time_ptr), _vp(desc_ptr), nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off),
-                _vp(tile_off_ptr), _ptr(tile_off), _vp(dist_ptr), _vp(flags_ptr), _vp(yaw_deg_ptr), _vp(sim_ptr), _vp(T_ij_ptr),
-                _vp(pairs_ptr), _vp(T_ref_ptr), _vp(enable_ptr), _vp(todo_off_ptr))
-        if box_ptr is not None:
-            self._check(self._lib.roman_session_gate_aabb_dev(*args, _vp(box_ptr), _vp(sim_in_ptr)), "roman_session_gate_aabb_dev")
-            return
-        if sim_in_ptr is not None:
-            self._check(self._lib.roman_session_gate_sim_dev(*args, _vp(sim_in_ptr)), "roman_session_gate_sim_dev")
-            return
-        self._check(self._lib.roman_session_gate_dev(*args), "roman_session_gate_dev")
+        sub_off, blocks, pair_off, tile_off, R, nb = self._session_gate_tables(sub_off, blocks, pair_off, tile_off)
+        fn, tail = self._session_gate_entry(box_ptr, sim_in_ptr)
+        rc = getattr(self._lib, fn + "_dev")(self._h, C.byref(gparams), R, _vp(sub_off_ptr), _ptr(sub_off), _vp(pos_ptr), _vp(pos_gt_ptr), _vp(has_gt_ptr),
+                                             _vp(T_w_ptr), _vp(time_ptr), _vp(desc_ptr), nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off),
+                                             _vp(tile_off_ptr), _ptr(tile_off), _vp(dist_ptr), _vp(flags_ptr), _vp(yaw_deg_ptr), _vp(sim_ptr), _vp(T_ij_ptr),
+                                             _vp(pairs_ptr), _vp(T_ref_ptr), _vp(enable_ptr), _vp(todo_off_ptr), *map(_vp, tail))
+        self._check(rc, fn + "_dev")
 
     # ------------------------------------------------------------------ boxes and the bounding-box gate of a session (DESIGN.md §4.16)
     def session_boxes(self, pool, row0, count, T_odom_center):
@@ -902,7 +896,7 @@ class Context:
         is not read.  `sim_in` (S0, S1): the similarity is already there (gparams.desc_dim must be 0); the result's sim is then
         that array.  -> GridGateResult."""
         return self._grid_gate_host("roman_grid_gate_aabb", gparams, (pos0, T_w0, time0, desc0, pos_gt0, box0), (pos1, T_w1, time1, desc1, pos_gt1, box1),
-                                    pairs, T_ref, enable, sim_in=sim_in)
+                                    pairs, T_ref, enable, sim_in=sim_in, aabb=True)
 
     def grid_gate_aabb_dev(self, gparams, S0, S1, pos0_ptr, T_w0_ptr, pos1_ptr, T_w1_ptr, dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr,
                            pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr, box0_ptr=None, box1_ptr=None, sim_in_ptr=None, time0_ptr=None, time1_ptr=None,

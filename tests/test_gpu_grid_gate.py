@@ -195,6 +195,79 @@ def test_two_runs_agree_bit_for_bit_and_the_host_pointer_call_gives_the_same_byt
         hip.free_all()
 
 
+def sides_case(gt, seed=9112):
+    """A 2 x 5 grid (a row spans two waves of GRID_TJ = 4 columns) on which every per-side array differs between the sides: 3-d
+    descriptors, distinct times under the time gate, boxes, a given similarity.  gt (True, True): the distances come from pos_gt
+    and pos is not read; (True, False): they come from pos, and side 0's pos_gt must not be used."""
+    gate = gate_params(3, skip_distance=35.0)
+    a, b = go.clean_grid(seed, 2, 5, 3, gt=gt, **gate)
+    rng = np.random.default_rng(seed + 1)
+    boxes = [np.hstack([s["pos"] - rng.uniform(5.0, 25.0, (len(s["pos"]), 3)), s["pos"] + rng.uniform(5.0, 25.0, (len(s["pos"]), 3))]) for s in (a, b)]
+    return a, b, boxes, rng.uniform(0.2, 0.95, (2, 5)), gate
+
+
+def sides_oracle(a, b, boxes, sim_in, gate, aabb, given):
+    """The NumPy restatement of the entry that serves (aabb, given)."""
+    import _fill_boxes_oracle as fo
+    rest = {k: v for k, v in gate.items() if k != "radius"}
+    if not given:
+        return fo.aabb_gate_oracle(a, b, *boxes, **rest) if aabb else go.grid_gate_oracle(a, b, **gate)
+    o = fo.aabb_gate_oracle(a, b, *boxes, sim_in=sim_in, **rest)
+    if not aabb:                                 # the classes of a given similarity as the box oracle derives them; NEARBY and the yaw by the radius
+        r = go.grid_gate_oracle({**a, "desc": None}, {**b, "desc": None}, **gate)
+        o["flags"] = (o["flags"] & ~go.NEARBY) | (r["flags"] & go.NEARBY); o["yaw_deg"] = r["yaw_deg"]
+    return o
+
+
+@pytest.mark.parametrize("gt", [(True, True), (True, False)], ids=["gt-both", "gt-one"])
+@pytest.mark.parametrize("entry", ["grid_gate", "grid_gate_sim", "grid_gate_aabb", "grid_gate_aabb-sim_in"])
+def test_every_entry_keeps_its_two_sides_apart(ctx, entry, gt):
+    """Each of the six entry points, host and `_dev`, against the oracle on sides_case(): an entry that hands the gate side 1's
+    pos, pos_gt, T_w, time, desc or box for side 0's, sim for sim_in or T_ref for T_ij misses it."""
+    aabb, given = "aabb" in entry, "sim" in entry
+    a, b, boxes, sim_in, gate = sides_case(gt)
+    d = 0 if given else 3
+    P = grid_gate_params(None if aabb else gate["radius"], desc_dim=d, **{k: v for k, v in gate.items() if k != "radius"})
+    o = sides_oracle(a, b, boxes, sim_in, gate, aabb, given)
+    assert 0 < o["n_todo"] < 10 and set(o["enable"].tolist()) == {0, 1} and 0 < ((o["flags"] & go.NEARBY) != 0).sum() < 10, "the case lost its classes"
+    hip = Hip()
+    try:
+        up = lambda x: None if x is None else hip.upload(np.asarray(x, dtype=np.float64).ravel())
+        size = dict(dist=10, flags=10, yaw_deg=10, sim=10, T_ij=160, pairs=20, T_ref=160, enable=10, n_todo=1)
+        out = {k: Guarded(hip, n, DTYPE[k], FILL[k]) for k, n in size.items()}
+        handed = dict(pairs=np.full((10, 2), FILL["pairs"], np.int32), T_ref=np.full((10, 4, 4), FILL["T_ref"]), enable=np.full(10, FILL["enable"], np.int32))
+        pos = (a["pos"], a["T_w"], b["pos"], b["T_w"])
+        kw = dict(time0=a["time"], time1=b["time"], pos_gt0=a["pos_gt"], pos_gt1=b["pos_gt"])
+        if not given:
+            kw.update(desc0=a["desc"], desc1=b["desc"])
+        dev = [up(x) for x in pos] + [out[k].ptr for k in size]
+        dkw = {k + "_ptr": up(v) for k, v in kw.items()}
+        if entry == "grid_gate_sim":                           # the similarity travels in the sim slot and comes back as it went
+            dev[7] = up(sim_in)
+            h = ctx.grid_gate_sim(P, sim_in, *pos, **kw, **handed)
+            ctx.grid_gate_sim_dev(P, 2, 5, *dev, **dkw)
+        elif aabb:
+            h = ctx.grid_gate_aabb(P, boxes[0], boxes[1], *pos, **kw, sim_in=sim_in if given else None, **handed)
+            ctx.grid_gate_aabb_dev(P, 2, 5, *dev, **dkw, box0_ptr=up(boxes[0]), box1_ptr=up(boxes[1]), sim_in_ptr=up(sim_in) if given else None)
+        else:
+            h = ctx.grid_gate(P, *pos, **kw, **handed)
+            ctx.grid_gate_dev(P, 2, 5, *dev, **dkw)
+        ctx.sync()
+        got = {k: v.get() for k, v in out.items()}
+        if given:                                              # an entry that is given the similarity does not write one
+            assert (got["sim"] == FILL["sim"]).all()
+            got["sim"] = hip.download(dev[7], (10,), np.float64) if entry == "grid_gate_sim" else sim_in.ravel()
+        for k in ("dist", "flags", "yaw_deg", "sim"):
+            got[k] = got[k].reshape(2, 5)
+        got["T_ij"] = got["T_ij"].reshape(2, 5, 4, 4); got["pairs"] = got["pairs"].reshape(10, 2); got["T_ref"] = got["T_ref"].reshape(10, 4, 4)
+        check(o, got, f"{entry}_dev {gt}")
+        host = {k: getattr(h, k) for k in size if k != "n_todo"}
+        host["n_todo"] = np.array([h.n_todo])
+        check(o, host, f"{entry} {gt}")
+    finally:
+        hip.free_all()
+
+
 def test_error_codes(ctx):
     gate = gate_params(4)
     a, b = go.clean_grid(5, 3, 4, 4, **gate)

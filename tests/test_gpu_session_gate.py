@@ -10,7 +10,7 @@ import _session as ss
 from _hipmem import Hip
 from roman_amd import _abi
 from roman_amd.runtime import grid_gate_params, session_tables
-from test_gpu_grid_gate import DTYPE, FILL, Guarded, run_dev
+from test_gpu_grid_gate import DTYPE, FILL, Guarded, close, run_dev
 from test_session_abi import check_error_codes
 
 pytestmark = pytest.mark.gpu
@@ -191,6 +191,70 @@ def test_two_runs_agree_bitwise_and_host_pointers_agree_with_device_pointers(ctx
                              has_gt=has_gt, **given)
         for k in ("dist", "flags", "yaw_deg", "sim", "T_ij", "pairs", "T_ref", "enable", "todo_off"):
             assert np.asarray(getattr(h, k)).tobytes() == a[k].tobytes(), k          # (the untouched capacity included: inout)
+    finally:
+        hip.free_all()
+
+
+def check_against_numpy(o, got, tag):
+    """A session result against a NumPy restatement: what tests/test_gpu_grid_gate.check() holds exact is exact here."""
+    n = int(o["todo_off"][-1])
+    assert np.asarray(got["todo_off"]).tolist() == o["todo_off"].tolist(), tag
+    assert np.array_equal(got["flags"], o["flags"]), tag
+    assert np.array_equal(got["pairs"][:n], o["pairs"]) and np.array_equal(got["enable"][:n], o["enable"]), tag
+    for k in ("dist", "sim", "yaw_deg", "T_ij"):
+        assert close(got[k], o[k]), (tag, k)
+    assert close(got["T_ref"][:n], o["T_ref"]), tag
+    assert got["T_ref"][:n].tobytes() == got["T_ij"][(o["flags"] & go.TODO) != 0].tobytes(), (tag, "T_ref is not the pair's T_ij")
+    assert (got["pairs"][n:] == FILL["pairs"]).all() and (got["T_ref"][n:] == FILL["T_ref"]).all() and (got["enable"][n:] == FILL["enable"]).all(), \
+        (tag, "capacity slots beyond the total were written")
+
+
+@pytest.mark.parametrize("entry", ["session_gate", "session_gate_sim", "session_gate_aabb", "session_gate_aabb-sim_in"])
+def test_every_entry_against_the_numpy_restatement(ctx, entry):
+    """Each of the six entry points, host and `_dev`, against tests/_session.py / tests/_session_aabb.py on two robots of 2 and 5
+    submaps, a block (0, 1) and a self block (1, 1), ground truth on robot 0 only (so pos is what is read, never pos_gt): an entry
+    that hands the gate one array for another of its type — pos_gt for pos, sim for sim_in, T_ref for T_ij — misses it."""
+    import _session_aabb as sa
+    import _session_stacked as sst
+    aabb, given = "aabb" in entry, "sim" in entry
+    counts, blocks, has_gt = (2, 5), [(0, 1, False), (1, 1, True)], (1, 0)
+    sides, arr, g = make_session(8700, counts, 3, has_gt, blocks, GATE)
+    rng = np.random.default_rng(8701)
+    box = np.hstack([arr["pos"] - rng.uniform(5.0, 25.0, (7, 3)), arr["pos"] + rng.uniform(5.0, 25.0, (7, 3))])
+    sim_in = rng.uniform(0.2, 0.95, 35)
+    tabs = session_tables(counts, blocks)
+    sub_off, blk, pair_off, _ = tabs
+    rest = {k: g[k] for k in ("skip_distance", "desc_thresh", "lc_time_thresh")}
+    seen = dict(arr, desc=None) if given else arr
+    if aabb:
+        o = sa.session_gate_aabb_oracle(seen, box, sub_off, blk, has_gt, sim_in=sim_in if given else None, pair_off=pair_off, **rest)
+    else:
+        o = ss.session_gate_oracle(seen, sub_off, blk, has_gt, g["radius"], **rest)
+        if given:
+            o = {**o, **sst.gate_from_sim(o, sim_in, sub_off, blk, g["desc_thresh"], arr["time"], g["lc_time_thresh"]), "sim": sim_in}
+    n = int(o["todo_off"][-1])
+    assert 0 < n < 35 and set(o["enable"].tolist()) == {0, 1} and 0 < ((o["flags"] & go.NEARBY) != 0).sum() < 35, "the case lost its classes"
+    P = grid_gate_params(None if aabb else g["radius"], desc_dim=0 if given else 3, single_robot_lc=False, **rest)
+    hip = Hip()
+    try:
+        up = lambda x: hip.upload(np.asarray(x, dtype=np.float64).ravel())
+        out = {k: Guarded(hip, WIDTH[k] * 35, DTYPE[k], FILL[k]) for k in OUT}
+        out["todo_off"] = Guarded(hip, 3, np.int32, -11)
+        ctx.session_gate_dev(P, *tabs, *[hip.upload(t) for t in tabs], up(arr["pos"]), up(arr["T_w"]), *[out[k].ptr for k in OUT], out["todo_off"].ptr,
+                             time_ptr=up(arr["time"]), desc_ptr=None if given else up(arr["desc"]), pos_gt_ptr=up(arr["pos_gt"]),
+                             has_gt_ptr=hip.upload(np.asarray(has_gt, dtype=np.int32)), sim_in_ptr=up(sim_in) if given else None,
+                             box_ptr=up(box) if aabb else None)
+        ctx.sync()
+        got = {k: v.get() for k, v in out.items()}
+        if given:                                              # an entry that is given the similarity does not write one
+            assert (got["sim"] == FILL["sim"]).all()
+            got["sim"] = sim_in
+        got["T_ij"] = got["T_ij"].reshape(35, 4, 4); got["T_ref"] = got["T_ref"].reshape(35, 4, 4); got["pairs"] = got["pairs"].reshape(35, 2)
+        check_against_numpy(o, got, entry + "_dev")
+        handed = dict(pairs=np.full((35, 2), FILL["pairs"], np.int32), T_ref=np.full((35, 4, 4), FILL["T_ref"]), enable=np.full(35, FILL["enable"], np.int32))
+        h = ctx.session_gate(P, *tabs, arr["pos"], arr["T_w"], time=arr["time"], desc=None if given else arr["desc"], pos_gt=arr["pos_gt"], has_gt=has_gt,
+                             sim_in=sim_in if given else None, box=box if aabb else None, **handed)
+        check_against_numpy(o, {k: np.asarray(getattr(h, k)) for k in OUT + ("todo_off",)}, entry)
     finally:
         hip.free_all()
 
