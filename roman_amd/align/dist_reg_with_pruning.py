@@ -1,6 +1,7 @@
 """DistRegWithPruning — `method='clipper+prune'`: prune associations by semantic cosine and shape
 ratios, then plain Euclidean-distance CLIPPER; reject results with roll/pitch above a threshold.
 Mirrors [REF roman/align/dist_reg_with_pruning.py:12-97]."""
+import copy
 from typing import List
 
 import numpy as np
@@ -47,6 +48,18 @@ class DistRegWithPruning(ObjectRegistration):
         self.use_gravity = use_gravity
         self.roll_pitch_thresh = roll_pitch_thresh
         assert not self.use_gravity or self.dim == 3, "Gravity can only be used with 3D points"
+
+    def on_device(self, semantics_dim=None):
+        """-> a copy of this plugin with prune_on_device=True: the same thresholds, dim and gravity check, the caller's context if
+        one is set; `semantics_dim` replaces the copy's descriptor length when given.  The way from the factory's plugin
+        (SubmapAlignParams.get_object_registration(): NumPy prefilter, as the reference) to the one the device-resident path
+        serves: `reg = params.get_object_registration().on_device(d)`, `MapTable.from_segments(reg, segments)`,
+        build_submap_pool, submap_align_pools / submap_align_session(..., registration=reg).  This plugin is left as it is."""
+        reg = copy.copy(self)
+        reg.prune_on_device = True
+        if semantics_dim is not None:
+            reg.semantics_dim = int(semantics_dim)
+        return reg
 
     def _abi_params(self):
         """clipperpy.invariants.EuclideanDistance + default clipperpy.Params,

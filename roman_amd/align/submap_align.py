@@ -37,7 +37,7 @@ from scipy.spatial.transform import Rotation as Rot
 from .. import _abi
 from ..runtime import LcInputs, LoopClosureResult, grid_gate_params, lc_record_dtype, stats_dtype
 from .batch import AlignmentBatch, pack_submaps, run_batch, run_lc_batch, run_lc_batch_ids
-from .dist_reg_with_pruning import _zyx_euler
+from .dist_reg_with_pruning import DistRegWithPruning, _zyx_euler
 from .object_registration import ObjectRegistration
 from .ransac_reg import RansacReg
 
@@ -259,10 +259,20 @@ def _drop_shared(segs_i, segs_j):
     return [s for s in segs_i if s.id not in common], [s for s in segs_j if s.id not in common]
 
 
+def _device_prefilter(registration):
+    """A DistRegWithPruning whose prefilter the device evaluates (prune_on_device: ROMAN_INV_EUCLIDEAN_PRUNED):
+    its `_associations_to_score` gives None for every pair.  A subclass that brings a scorer of its own is not one."""
+    return (isinstance(registration, DistRegWithPruning) and bool(registration.prune_on_device)
+            and type(registration)._associations_to_score is DistRegWithPruning._associations_to_score)
+
+
 def _has_host_prefilter(registration):
-    """A pruning plugin that scores explicit association lists: its host prefilter reads both maps of a pair."""
+    """A pruning plugin that scores explicit association lists: its host prefilter reads both maps of a pair.  Asked of the
+    INSTANCE: a DistRegWithPruning with prune_on_device has none; any other plugin that overrides `_associations_to_score` has."""
     scorer = getattr(type(registration), "_associations_to_score", None)
-    return scorer is not None and scorer is not ObjectRegistration._associations_to_score
+    if scorer is None or scorer is ObjectRegistration._associations_to_score:
+        return False
+    return not _device_prefilter(registration)
 
 
 def _set_association_lists(registration, batch, segs_of):
@@ -470,7 +480,8 @@ def submap_align_grid(sm_params, submaps, sm_io: Optional[SubmapAlignIO] = None,
     per-pair list is the input itself: a registration plugin's host prefilter.  The shared-segment removal of
     `single_robot_lc` ([REF :108-115]) runs on the device too (roman_align_lc_batch_ids: one id per pool row); it stays a
     per-pair host loop only with an injected `compute`, with such a plugin (its prefilter reads the reduced lists) or when
-    an id is not an integer that int64 holds.
+    an id is not an integer that int64 holds.  A DistRegWithPruning with prune_on_device has no host prefilter (the device applies
+    it: `_has_host_prefilter` asks the instance) and takes the batched path, with no association lists.
 
     `compute(registration, AlignmentBatch, runtime.LcInputs) -> runtime.LoopClosureResult` defaults to the HIP path
     (`run_lc_batch`); tests inject a CPU double."""
@@ -739,6 +750,26 @@ def _ransac_refusals(registration, p, way):
         raise ValueError("the context has no roman_ransac_lc_batch_dev" + way)
 
 
+def _prune_refusals(registration, p, way):
+    """What a device-prefilter plugin (DistRegWithPruning.on_device()) over the pools `p` is refused for, in front of anything that
+    makes a HIP context: the cosine stage reads [centre | volume, linearity, planarity, scattering | descriptor] from every row, and
+    rows packed by another registration (another number of shape columns, or method='roman': the same number in another order)
+    would be read as they lie — shape attributes out of descriptor columns, a volume for a linearity — without any error."""
+    d = registration.semantics_dim
+    if d is None:
+        raise ValueError("the device prefilter needs the descriptor length: DistRegWithPruning.on_device(semantics_dim=...) before the pools are built" + way)
+    F = int(registration.dim) + 4 + int(d)
+    if any(int(q.pool.shape[1]) != F for q in p):
+        raise ValueError(f"the device prefilter reads rows of dim + 4 + semantics_dim = {F} columns [centre | volume, linearity, planarity, scattering | "
+                         "descriptor]: build the pools with MapTable.from_segments(registration.on_device(semantics_dim), segments)" + way)
+    if any(int(q.table.desc_dim) != int(d) for q in p):
+        raise ValueError(f"the device prefilter contracts descriptors of semantics_dim = {int(d)}, and a pool's table was packed with another desc_dim" + way)
+    # (method='roman' packs [centre | linearity, planarity, scattering | volume | descriptor]: the same width, another column order)
+    if any(getattr(q.table, "invariant", None) not in (None, _abi.ROMAN_INV_EUCLIDEAN_PRUNED) for q in p):
+        raise ValueError("a pool's table was packed by another registration, with its own column order between centre and descriptor: build the "
+                         "pools with MapTable.from_segments(registration.on_device(semantics_dim), segments)" + way)
+
+
 def _descriptor_refusals(registration, p, mode, way):
     """The descriptor modes the pools `p` do not carry, and a plugin whose host prefilter would need the segment rows back."""
     if mode not in (None, 'mean_semantic', 'mean_frame_descriptor', 'stacked_frame_descriptors'):
@@ -860,8 +891,18 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     build_submap_pool(fill=...) (force-fill slices) and radius-mode pools are served alike.
 
     Not covered — ValueError; SubmapPool.to_submaps() + submap_align_grid is the way: the AABB gate over pools with dim 2 (their
-    rows hold no z) or a context without roman_grid_gate_aabb_dev, registration plugins with a host prefilter, shared ids over
-    pools without `ids_dev`.
+    rows hold no z) or a context without roman_grid_gate_aabb_dev, registration plugins whose prefilter runs on the host (their pool
+    rows hold centres only; for method='clipper+prune' DistRegWithPruning.on_device() gives the plugin that is served, below),
+    shared ids over pools without `ids_dev`.
+
+    method='clipper+prune'  runs with the device-prefilter plugin, `reg = sm_params.get_object_registration()
+    .on_device(semantics_dim)`, over pools built with it (MapTable.from_segments(reg, segments): rows [centre | volume, linearity,
+    planarity, scattering | descriptor]), in every mode above: both gates, every submap descriptor, [pool, pool] self loop closures
+    (the gather region holds the full-width rows).  It is a CLIPPER method like any other here — issue_chunked with
+    ROMAN_INV_EUCLIDEAN_PRUNED, join, the tail with the plugin's roll / pitch check.  Refused for it, before a context is made
+    (`_prune_refusals`, four): semantics_dim unset, pools of another row width than dim + 4 + semantics_dim, a table of another
+    desc_dim, a table packed by another registration (MapTable.invariant: method='roman' rows have the same width and another
+    column order).  The factory's own plugin (prune_on_device=False) keeps its NumPy prefilter and stays refused.
 
     A RansacReg (method='ransac') runs over the same pools — built with ANY registration: roman_ransac_lc_batch_dev
     reads the centre from columns 0-2 of a row and nothing else — with pass 1 and the shared-segment removal unchanged; in place
@@ -882,6 +923,8 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         raise ValueError("pools must hold two SubmapPool objects")
     if isinstance(registration, RansacReg):
         _ransac_refusals(registration, p, way)
+    if _device_prefilter(registration):
+        _prune_refusals(registration, p, way)
     aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
     mode = sm_params.submap_descriptor
     stacked = mode == 'stacked_frame_descriptors'
@@ -1005,8 +1048,14 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     RANSAC_ASSOC_CHUNK_BYTES) in place of issue_chunked, join and the tail.  The seed is one per batch and a problem's result does
     not depend on its place in it: every block equals submap_align_pools with the same registration.  Both together work too.
 
-    Not covered — ValueError before any context is made; submap_align_pools per robot pair is the way: a plugin with a host
-    prefilter, pools of different row width or descriptor length, pools not built with the frame-descriptor mode asked for, a self
+    method='clipper+prune' with the device-prefilter plugin (DistRegWithPruning.on_device()) over pools built
+    with it: a CLIPPER method like any other — the problems of all blocks in the one issue_chunked, self blocks through the one
+    roman_shared_reduce_dev with their full-width rows —, every block equal to submap_align_pools with the same plugin.
+
+    Not covered — ValueError before any context is made; submap_align_pools per robot pair is the way: a plugin whose prefilter
+    runs on the host (DistRegWithPruning.on_device() is the one that is served), for a device-prefilter plugin the four things
+    submap_align_pools refuses for it (semantics_dim unset, row width, desc_dim, a table packed by another registration), pools of
+    different row width or descriptor length, pools not built with the frame-descriptor mode asked for, a self
     block over a pool without ids_dev, and whatever submap_align_pools refuses for a pool — for a RansacReg its four (pools of
     dim 2, a `cap` above ROMAN_RANSAC_MAX_OBJECTS, host-tensor pools while the registration has no context set, a context without
     roman_ransac_lc_batch_dev), in its order.  The bounding-box gate over host-tensor pools while the registration has no context
@@ -1030,6 +1079,8 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         raise ValueError("robot_pairs must name pools by index, each pair once" + way)
     if isinstance(registration, RansacReg) and R:            # (submap_align_pools' four, in its order: in front of everything that makes a HIP context)
         _ransac_refusals(registration, p, way)
+    if _device_prefilter(registration) and R:                # (and its four for a device-prefilter plugin)
+        _prune_refusals(registration, p, way)
     aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
     if aabb_mode and _no_device(registration, p):            # (the boxes are reduced from the resident rows: as for a RansacReg, host rows need a context of the caller's)
         raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes of the resident rows: the registration has no context set "

@@ -147,6 +147,8 @@ class MapTable:
     ids: np.ndarray              # (N,) int64
     point_dim: int               # centre components an output row keeps (the registration's dim)
     desc_dim: int                # trailing descriptor columns (0: none)
+    invariant: Optional[int] = None   # ROMAN_INV_* of the registration that packed the rows (its column order between point and descriptor);
+                                      # None: centres only (a RansacReg) or a table built by other means
 
     @classmethod
     def from_segments(cls, registration, segments):
@@ -163,7 +165,7 @@ class MapTable:
             return cls(feats, times, ids, int(dim), 0)
         P = registration._abi_params()
         d = int(P.cos_feature_dim) if P.invariant != _abi.ROMAN_INV_EUCLIDEAN else 0
-        return cls(feats, times, ids, int(dim), d)
+        return cls(feats, times, ids, int(dim), d, int(P.invariant))
 
     def __len__(self):
         return int(self.feats.shape[0])
