@@ -612,6 +612,67 @@ ROMAN_API int roman_mno_batch(roman_ctx_t* ctx, const roman_params_t* params, in
                               int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
                               roman_mno_solution_t* sol_out, roman_stats_t* stats_out);
 
+/*
+ * roman_mno_lc_tail_dev: the loop-closure tail over K hypotheses per problem — roman_lc_tail_dev for the output of
+ * roman_mno_batch_dev.  What the reference does to a pose before it becomes an edge ([REF roman/align/submap_align.py:160-200],
+ * [REF roman/align/results.py:156-198]) for every solution of mno_clipper [REF roman/align/object_registration.py:57-86], and
+ * the choice among a problem's hypotheses.  All bulk pointers DEVICE; a pure enqueue on the context's stream; at pipeline
+ * depth >= 2 order the batch calls in front of it with roman_ctx_join().
+ *
+ *   sol           roman_mno_solution_t[B][K]: n_assoc, status and T of hypothesis k of problem b
+ *   T_ref, enable, FL, iL, FR, iR   as for roman_lc_tail_dev, PER PROBLEM ([B] entries): the K hypotheses of a problem share them
+ *   records       roman_lc_record_t[B * K]: record b * K + k is, field for field, what roman_lc_tail_dev writes for that pose
+ *                 with the problem's inputs; record.problem = b * K + k
+ *   best          int32[B]: the hypothesis the problem's results come from.  Candidates are the hypotheses whose record has none
+ *                 of ROMAN_LC_FAILED_*, ROMAN_LC_SKIPPED, ROMAN_LC_INTERNAL; the largest n_assoc wins, the lower k among equals;
+ *                 -1 when no hypothesis qualifies (the pair carries the sentinels of [REF roman/align/submap_align.py:179-184]).
+ *                 A candidate need not be accepted (too few associations, enable == 0)
+ *   accepted_idx  int32[B * K] capacity, n_accepted int32[1]: the accepted records as b * K + k, ASCENDING, by prefix sum
+ *   accepted_best_idx  int32[B] capacity, n_accepted_best int32[1]: the problems b whose best hypothesis is accepted, ASCENDING
+ *
+ * ROMAN_E_INVALID (text in roman_last_error; nothing is enqueued): NULL context, B < 0, K outside 1 ... ROMAN_MNO_MAX_SOLUTIONS,
+ * B * K above INT32_MAX, the parameter errors of roman_lc_tail_dev, a frame pool without its index array, NULL n_accepted /
+ * n_accepted_best, and with B > 0 NULL sol / records / best / accepted_idx / accepted_best_idx.  B == 0 is legal: both counts
+ * become 0.  Entries of the lists beyond the counts are not written.
+ */
+ROMAN_API int roman_mno_lc_tail_dev(roman_ctx_t* ctx, const roman_lc_params_t* lc_params, int32_t B, int32_t K,
+                                    const roman_mno_solution_t* sol, const double* T_ref, const int32_t* enable,
+                                    const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                                    roman_lc_record_t* records, int32_t* best, int32_t* accepted_idx, int32_t* n_accepted,
+                                    int32_t* accepted_best_idx, int32_t* n_accepted_best);
+
+/* roman_mno_batch_dev followed by roman_mno_lc_tail_dev over its solutions, enqueued on the SAME stream as that call's rounds
+   (the relation of roman_align_lc_batch_dev to roman_align_batch_dev): [REF roman/align/object_registration.py:57-86] and the
+   tail of [REF roman/align/submap_align.py:160-200] / [REF roman/align/results.py:156-198] in one pure enqueue, complete after
+   roman_ctx_sync().  A problem skipped for workspace has ROMAN_LC_SKIPPED on all K records and best = -1: issue it again. */
+ROMAN_API int roman_mno_lc_batch_dev(roman_ctx_t* ctx, const roman_params_t* params, int32_t B,
+                                     const double* feats, const int64_t* off1, const int32_t* n1,
+                                     const int64_t* off2, const int32_t* n2, int32_t F,
+                                     const int32_t* assoc, const int64_t* assoc_off,
+                                     int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                                     roman_mno_solution_t* sol_out, roman_stats_t* stats_out,
+                                     const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                                     const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                                     roman_lc_record_t* records, int32_t* best, int32_t* accepted_idx, int32_t* n_accepted,
+                                     int32_t* accepted_best_idx, int32_t* n_accepted_best);
+
+/* The same with HOST pointers everywhere (n_left / n_right: submaps in FL / FR): roman_mno_batch with its chunking and
+   re-issues first, THEN the tail over the final device block — a record is never built from a skipped attempt —, then the
+   read-back (the list entries beyond the counts come back unspecified here: the untouched-slot guarantee is the _dev entries').
+   mno_clipper [REF roman/align/object_registration.py:57-86] plus [REF roman/align/submap_align.py:160-200] and
+   [REF roman/align/results.py:156-198] per hypothesis for a caller that holds NumPy arrays. */
+ROMAN_API int roman_mno_lc_batch(roman_ctx_t* ctx, const roman_params_t* params, int32_t B,
+                                 const double* feats, int64_t n_objects,
+                                 const int64_t* off1, const int32_t* n1,
+                                 const int64_t* off2, const int32_t* n2, int32_t F,
+                                 const int32_t* assoc, const int64_t* assoc_off,
+                                 int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                                 roman_mno_solution_t* sol_out, roman_stats_t* stats_out,
+                                 const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                                 const double* FL, int32_t n_left, const int32_t* iL, const double* FR, int32_t n_right, const int32_t* iR,
+                                 roman_lc_record_t* records, int32_t* best, int32_t* accepted_idx, int32_t* n_accepted,
+                                 int32_t* accepted_best_idx, int32_t* n_accepted_best);
+
 /* ------------------------------------------------------------------------------------------- */
 /* RANSAC registration on object centres, batched (method 'ransac')                            */
 /* ------------------------------------------------------------------------------------------- */

@@ -160,6 +160,14 @@ def run_mno_batch(registration, batch: AlignmentBatch, num_solutions=2, ctx=None
                          num_solutions=num_solutions, assoc=batch.assoc, assoc_off=batch.assoc_off, kmax=batch.kmax())
 
 
+def run_mno_lc_batch(registration, batch: AlignmentBatch, lc, num_solutions=2, ctx=None):
+    """One roman_mno_lc_batch call for `batch`: `num_solutions` hypotheses per problem, each through the loop-closure tail `lc`
+    (runtime.LcInputs, per-problem arrays), and the best hypothesis of every problem -> runtime.MnoLoopClosureResult."""
+    ctx = ctx or registration._context()
+    return ctx.mno_lc_batch(registration._abi_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2, lc,
+                            num_solutions=num_solutions, assoc=batch.assoc, assoc_off=batch.assoc_off, kmax=batch.kmax())
+
+
 def align_pairs(registration, pairs, u0=None):
     """register() + T_align() for every (map1, map2) in `pairs`, one device call."""
     return run_batch(registration, batch_from_pairs(registration, pairs), u0=u0)

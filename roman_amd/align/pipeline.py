@@ -283,6 +283,54 @@ def issue_chunked(ctx, P, pool, batch, kmax, a_out, n_out, T_out, st_out, stats_
     return status.copy()
 
 
+def issue_mno_chunked(ctx, P, pool, batch, K, kmax, a_out, sol_out, assoc_dev=None, chunk=None, in_flight=3):
+    """issue_chunked() for the multi-solution call (roman_mno_batch_dev): the problems of `batch` over the resident `pool` as calls
+    of `chunk` problems, `in_flight` at once; problem b writes rows [b*K, (b+1)*K) of `a_out` ((B, K, kmax, 2) int32) and of
+    `sol_out` (B*K roman_mno_solution_t as a uint8 tensor).  A problem skipped for workspace carries ROMAN_ST_WORKSPACE on every
+    solution and is issued again — those only, in runs of consecutive problems — up to MAX_ATTEMPTS times.
+    -> the status of solution 0 of every problem on the host.  Synchronises the context; its pipeline depth is restored.
+    Unlike issue_chunked there is no second attempt with the team mode off for ROMAN_ST_INTERNAL: a solution that carries it is left
+    as it is, and the caller (submap_align._mno_lc_over_pool) raises on its record — on any hypothesis of the problem —, as it does
+    for a problem still skipped after MAX_ATTEMPTS."""
+    from ..runtime import mno_solution_dtype
+    B = len(batch)
+    F = int(pool.shape[1])
+    chunk = default_chunk(B) if chunk is None else max(1, int(chunk))
+    SB = _abi.MNO_SOLUTION_NBYTES
+
+    def issue(lo, hi):
+        ctx.mno_batch_dev(P, pool.data_ptr(), F, batch.off1[lo:hi], batch.n1[lo:hi], batch.off2[lo:hi], batch.n2[lo:hi], K, kmax,
+                          a_out[lo:].data_ptr(), sol_out[lo * K * SB:].data_ptr(),
+                          assoc_ptr=None if assoc_dev is None else assoc_dev.data_ptr(),
+                          assoc_off=None if batch.assoc_off is None else batch.assoc_off[lo:hi + 1])
+
+    status = np.zeros(0, dtype=np.int32)
+    depth_before = getattr(ctx, "pipeline_depth", 1)
+    ctx.set_pipeline(max(1, int(in_flight)))
+    try:
+        for l in range(0, B, chunk):
+            issue(l, min(B, l + chunk))
+            if l == 0:
+                ctx.sync()                                       # the calls behind the first size their pools from what it needed
+        for attempt in range(1, MAX_ATTEMPTS + 1):
+            ctx.sync()
+            sol = np.frombuffer(sol_out.cpu().numpy().tobytes(), dtype=mno_solution_dtype())[:B * K].reshape(B, K)
+            status = sol["status"][:, 0].copy()
+            skipped = np.nonzero((status & _abi.ROMAN_ST_WORKSPACE) != 0)[0]
+            if not len(skipped) or attempt == MAX_ATTEMPTS:
+                break
+            b = 0
+            while b < len(skipped):
+                e = b + 1
+                while e < len(skipped) and skipped[e] == skipped[e - 1] + 1 and e - b < chunk:
+                    e += 1
+                issue(int(skipped[b]), int(skipped[e - 1]) + 1)
+                b = e
+    finally:
+        ctx.set_pipeline(depth_before)
+    return status
+
+
 def align_resident(registration, batch, pool, chunk=None, in_flight=3, device=None, ctx=None, stats=True):
     """ONE batch of any size over a feature pool that is already in HBM (`pool`: the batch's (n_objects, F) float64 matrix as a
     torch tensor on `device`) -> runtime.BatchResult on the host.  On a real context this is ONE library call

@@ -194,6 +194,10 @@ class SubmapAlignResults:
     # submap_align_grid / submap_align_pools only: the loop-closure edges as the device computed them — {'pairs': (K, 2) int (i, j) in loop order,
     # 't': (K, 3), 'q': (K, 4) xyzw}.  loop_closure_edges() and the writers then do no per-pair matrix work.
     lc_edges: Optional[dict] = None
+    # submap_align_pools / submap_align_session with num_solutions=K only: {(i, j): [K tuples (associations, score, T_hat,
+    # n_assoc, flags, edge)]} for every registered pair — every hypothesis of the pair, `edge` = (t (3,), q (4,) xyzw) of an ACCEPTED
+    # hypothesis, else None.  The matrices above and lc_edges come from each pair's best hypothesis.
+    hypotheses: Optional[dict] = None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -234,8 +238,8 @@ class _GridResults:
         self.clipper_num_associations[gated] = 0
         self.clipper_angle_mat[gated & nearby] = np.abs(np.rad2deg(_NO_ESTIMATE[0])); self.clipper_dist_mat[gated & nearby] = _NO_ESTIMATE[1]
 
-    def results(self, timing_list=(), lc_edges=None):
-        return SubmapAlignResults(
+    def results(self, timing_list=(), lc_edges=None, hypotheses=None):
+        return SubmapAlignResults(hypotheses=hypotheses,
             robots_nearby_mat=self.robots_nearby_mat, clipper_angle_mat=self.clipper_angle_mat, clipper_dist_mat=self.clipper_dist_mat,
             clipper_num_associations=self.clipper_num_associations,
             similarity_mat=self.similarity_mat if self.sm_params.submap_descriptor is not None else None,
@@ -750,6 +754,21 @@ def _ransac_refusals(registration, p, way):
         raise ValueError("the context has no roman_ransac_lc_batch_dev" + way)
 
 
+def _mno_refusals(registration, p, pool_pairs, num_solutions, way):
+    """What num_solutions=K over the pools `p` is refused for (`pool_pairs`: the (r, s) to align) — in front of anything that makes a HIP
+    context: a RansacReg builds no affinity matrix to take a second solution from; K outside 1 ... ROMAN_MNO_MAX_SOLUTIONS; a `cap`
+    whose all-to-all list exceeds what roman_mno_batch serves per problem."""
+    if isinstance(registration, RansacReg):
+        raise ValueError("num_solutions needs a CLIPPER method: RansacReg builds no affinity matrix" + way)
+    K = num_solutions
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not (1 <= int(K) <= _abi.ROMAN_MNO_MAX_SOLUTIONS):
+        raise ValueError(f"num_solutions must be an integer in 1 ... {_abi.ROMAN_MNO_MAX_SOLUTIONS} (got {K!r})" + way)
+    for r, s_ in pool_pairs:
+        if int(p[r].cap) * int(p[s_].cap) > _abi.ROMAN_MNO_MAX_ASSOC:
+            raise ValueError(f"num_solutions: submaps of up to {int(p[r].cap)} x {int(p[s_].cap)} objects have an all-to-all list above the "
+                             f"{_abi.ROMAN_MNO_MAX_ASSOC} associations roman_mno_batch serves per problem (ROMAN_MNO_MAX_ASSOC)" + way)
+
+
 def _prune_refusals(registration, p, way):
     """What a device-prefilter plugin (DistRegWithPruning.on_device()) over the pools `p` is refused for, in front of anything that
     makes a HIP context: the cosine stage reads [centre | volume, linearity, planarity, scattering | descriptor] from every row, and
@@ -842,7 +861,55 @@ def _drop_shared_over_pool(torch, ctx, pool, ids_dev, off1, n1, off2, n2, sel, w
     return (work, *out)
 
 
-def _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, FL, FR, wait_torch):
+def _mno_lc_over_pool(torch, ctx, registration, pool, batch, K, kmax, lp, B, tail_ptrs, dim):
+    """num_solutions=K: the K solves of every problem over the resident rows (pipeline.issue_mno_chunked: chunks,
+    skipped problems issued again), join, ONE roman_mno_lc_tail_dev over the final block.  -> runtime.LoopClosureResult whose
+    entry b is problem b's BEST hypothesis (hypothesis 0's record — a failed one, the sentinels — where best = -1) and whose
+    accepted list is accepted_best_idx, with `.hypotheses`: per problem the K tuples of SubmapAlignResults.hypotheses."""
+    from .pipeline import issue_mno_chunked
+    from ..runtime import mno_solution_dtype
+    dev, i32 = pool.device, torch.int32
+    a_out = torch.full((B, K, kmax, 2), -1, dtype=i32, device=dev)
+    sol = torch.zeros(B * K * _abi.MNO_SOLUTION_NBYTES, dtype=torch.uint8, device=dev)
+    rec = torch.zeros(B * K * _abi.LC_RECORD_NBYTES, dtype=torch.uint8, device=dev)
+    best = torch.full((B,), -1, dtype=i32, device=dev)
+    idx = torch.zeros(B * K, dtype=i32, device=dev); cnt = torch.zeros(1, dtype=i32, device=dev)
+    bidx = torch.zeros(B, dtype=i32, device=dev); bcnt = torch.zeros(1, dtype=i32, device=dev)
+    status = issue_mno_chunked(ctx, registration._abi_params(), pool, batch, K, kmax, a_out, sol)   # re-issues skipped problems, then synchronises:
+    ctx.join()                                               # ... the tail below sees the FINAL attempt of every problem only
+    ctx.mno_lc_tail_dev(lp, B, K, sol.data_ptr(), rec.data_ptr(), best.data_ptr(), idx.data_ptr(), cnt.data_ptr(), bidx.data_ptr(), bcnt.data_ptr(),
+                        **tail_ptrs)
+    ctx.sync()
+    s = dim + 1
+    sol_h = np.frombuffer(sol.cpu().numpy().tobytes(), dtype=mno_solution_dtype()).reshape(B, K)
+    rec_h = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=lc_record_dtype()).reshape(B, K).copy()
+    best_h, a_h = best.cpu().numpy(), a_out.cpu().numpy()
+    if np.any(rec_h["flags"] & (_abi.ROMAN_LC_SKIPPED | _abi.ROMAN_LC_INTERNAL)):       # (on ANY hypothesis: the best view below would hide one behind k = 0)
+        raise _abi.RomanHipError("the multi-solution call left hypotheses without a result (ROMAN_LC_SKIPPED / ROMAN_LC_INTERNAL records)")
+    rows = np.minimum(sol_h["n_assoc"], kmax)
+    hyps = []
+    for b in range(B):
+        one = []
+        for k in range(K):
+            r = rec_h[b, k]
+            edge = (r["edge_t"].copy(), r["edge_q"].copy()) if r["flags"] & _abi.ROMAN_LC_ACCEPTED else None
+            one.append((a_h[b, k, :rows[b, k]].copy(), float(sol_h["score"][b, k]), r["T_hat"].copy(), int(r["n_assoc"]), int(r["flags"]), edge))
+        hyps.append(one)
+    pick = np.maximum(best_h, 0)
+    ar = np.arange(B)
+    res = LoopClosureResult([hyps[b][pick[b]][0] for b in range(B)], sol_h["T"][ar, pick][:, :s * s].reshape(B, s, s).copy(), status,
+                            np.zeros(B, dtype=stats_dtype()), rec_h[ar, pick].copy(), bidx.cpu().numpy()[:int(bcnt.cpu().numpy()[0])].copy())
+    res.hypotheses, res.best = hyps, best_h
+    return res
+
+
+def _hypotheses_of(res, ti, tj):
+    """SubmapAlignResults.hypotheses of the registered pairs (ti, tj), or None on the single-solution path."""
+    hyps = getattr(res, "hypotheses", None)
+    return None if hyps is None else {(int(i), int(j)): h for i, j, h in zip(ti, tj, hyps)}
+
+
+def _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, FL, FR, wait_torch, num_solutions=None):
     """The B problems of `batch` over the resident rows `pool`, and the tail behind them with T_ref, enable and the pairs where the
     gate wrote them (`g`) and the edge frames FL / FR (device tensors, indexed by the pairs): issue_chunked, join and
     roman_lc_tail_dev — or, for a RansacReg, `_ransac_lc_over_pool`.  -> (runtime.LoopClosureResult, seconds per pair)."""
@@ -857,6 +924,8 @@ def _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch,
     t0 = time.time()
     if ransac:                                               # k_ransac over the rows as they are, the tail behind it
         res = _ransac_lc_over_pool(torch, ctx, registration, pool, batch, lp, o, tail_ptrs, wait_torch)
+    elif num_solutions is not None:                          # K hypotheses per pair, the tail over all of them, the best of each pair
+        res = _mno_lc_over_pool(torch, ctx, registration, pool, batch, int(num_solutions), kmax, lp, B, tail_ptrs, sm_params.dim)
     else:
         status = issue_chunked(ctx, registration._abi_params(), pool, batch, kmax, o.assoc, o.n, o.T, o.status)   # re-issues skipped problems, then synchronises:
         ctx.join()                                           # ... the tail below sees the FINAL attempt of every problem only
@@ -866,7 +935,8 @@ def _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch,
     return res, (time.time() - t0) / B
 
 
-def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, registration=None, gt_poses=(None, None)) -> SubmapAlignResults:
+def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, registration=None, gt_poses=(None, None),
+                       num_solutions=None) -> SubmapAlignResults:
     """submap_align_grid() for two maps whose submaps are ALREADY in HBM (`pools`: two align.submaps.SubmapPool, as
     build_submap_pool leaves them): the same results as submap_align_grid(sm_params, [p.to_submaps(segments) for p in pools]),
     without a segment row coming back to the host or going up twice.  Pass 1 ([REF roman/align/submap_align.py:93-149])
@@ -913,7 +983,15 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     Frame descriptors need pools built with them (build_submap_pool(frames=...)): 'mean_frame_descriptor' goes
     through the same gate as 'mean_semantic'; 'stacked_frame_descriptors' through roman_stacked_sim_dev over the two pools' frame
     masks — every distinct frame pair contracted once — and roman_grid_gate_sim_dev on that similarity.  similarity_mat is what
-    the device computed."""
+    the device computed.
+
+    num_solutions=K (1 ... 64): every registered pair gets K hypotheses (roman_mno_batch_dev over the resident rows
+    in chunks, skipped problems issued again) and ONE roman_mno_lc_tail_dev runs the tail over all of them.  The result matrices
+    and lc_edges come from each pair's best hypothesis — no failed filter, most associations, the lower k among equals; the
+    reference's sentinels where every hypothesis failed — and `hypotheses` holds all K per pair.  Every hypothesis is a plain-CLIPPER
+    solve over all associations: for a method with single scores (`roman`) hypothesis 0 is in general not register()'s result.
+    Refused before a context is made: a RansacReg, K outside 1 ... 64, a pool `cap` whose all-to-all list exceeds
+    ROMAN_MNO_MAX_ASSOC; after it: a context without roman_mno_lc_tail_dev.  None: the single-solution path, unchanged."""
     import torch
     sm_io = sm_io or SubmapAlignIO()
     registration = registration or sm_params.get_object_registration()
@@ -921,6 +999,8 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     p = list(pools)
     if len(p) != 2:
         raise ValueError("pools must hold two SubmapPool objects")
+    if num_solutions is not None:
+        _mno_refusals(registration, p, [(0, 1)], num_solutions, way)
     if isinstance(registration, RansacReg):
         _ransac_refusals(registration, p, way)
     if _device_prefilter(registration):
@@ -934,6 +1014,8 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         if sm_io.gt_available[r] and gt_poses[r] is None:
             raise ValueError(f"sm_io.gt_available[{r}] is set without gt_poses[{r}]")
     ctx = registration._context()
+    if num_solutions is not None and not hasattr(ctx, "mno_lc_tail_dev"):
+        raise ValueError("the context has no roman_mno_lc_tail_dev" + way)
     if aabb_mode and not (hasattr(ctx, "grid_gate_aabb_dev") and hasattr(ctx, "submap_boxes_dev")):
         raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes" + way)
     if aabb_mode and any(int(q.table.point_dim) != 3 for q in p):
@@ -950,7 +1032,7 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     n0, n1 = len(keep[0]), len(keep[1])
     M = _GridResults(sm_params, sm_io, n0, n1)
     if n0 == 0 or n1 == 0:
-        return M.results(lc_edges=M.empty_edges())
+        return M.results(lc_edges=M.empty_edges(), hypotheses=None if num_solutions is None else {})
 
     # ---- per submap, on the host (O(S)): centre, the pose the reference transform is built from, time, the edge frames —
     # through the stand-in Submap's own properties, read as often as the pair loop reads them (submap_align_grid does the same) ----
@@ -1000,7 +1082,7 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     h = {k: g[k].cpu().numpy() for k in ("dist", "flags", "yaw", "sim", "T_ij")}
     nearby, todo = _pass1_block(M, h, 0, n0 * n1, n0, n1, pairs, "roman_grid_gate_dev: the compact pair list is not the TODO pairs in row-major order")
     if B == 0:
-        return M.results(lc_edges=M.empty_edges())
+        return M.results(lc_edges=M.empty_edges(), hypotheses=None if num_solutions is None else {})
 
     # ---- the hot path over the resident pools: offsets and counts from the pools, the batch in chunks, then the tail ----
     batch, pool = p[0].grid_batch(p[1], mask=todo)
@@ -1010,12 +1092,14 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
         pool, *prob = _drop_shared_over_pool(torch, ctx, pool, ids_dev, batch.off1, batch.n1, batch.off2, batch.n2, np.arange(B), wait_torch)
         batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), tuple(pool.shape)), *prob, pair_index=batch.pair_index)
     res, per_pair = _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, up(frames[0].reshape(-1, 16)),
-                                        up(frames[1].reshape(-1, 16)), wait_torch)
-    return M.results([per_pair] * B, _records_into_results(M, res, pairs[:, 0], pairs[:, 1], nearby))
+                                        up(frames[1].reshape(-1, 16)), wait_torch, num_solutions)
+    out = M.results([per_pair] * B, _records_into_results(M, res, pairs[:, 0], pairs[:, 1], nearby))
+    out.hypotheses = _hypotheses_of(res, pairs[:, 0], pairs[:, 1])
+    return out
 
 
 def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[SubmapAlignIO] = None, registration=None,
-                         gt_poses=None) -> Dict[Tuple[int, int], SubmapAlignResults]:
+                         gt_poses=None, num_solutions=None) -> Dict[Tuple[int, int], SubmapAlignResults]:
     """The robot-pair loop of the reference's driver [REF demo/demo.py:138-161] in ONE call: `pools` is a list of R
     device-resident SubmapPool, `robot_pairs` the blocks (r, s) to align — default: every r <= s in the driver's order.  -> {(r, s):
     SubmapAlignResults}, each equal to what submap_align_pools(p, [pools[r], pools[s]], ...) returns for that block alone with
@@ -1077,6 +1161,8 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         raise ValueError("gt_poses must hold one entry per pool" + way)
     if any(not (0 <= r < R and 0 <= s < R) for r, s in blocks) or len(set(blocks)) != len(blocks):
         raise ValueError("robot_pairs must name pools by index, each pair once" + way)
+    if num_solutions is not None:                            # (submap_align_pools' three for K hypotheses per pair)
+        _mno_refusals(registration, p, blocks, num_solutions, way)
     if isinstance(registration, RansacReg) and R:            # (submap_align_pools' four, in its order: in front of everything that makes a HIP context)
         _ransac_refusals(registration, p, way)
     if _device_prefilter(registration) and R:                # (and its four for a device-prefilter plugin)
@@ -1123,10 +1209,10 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     vblocks = [(view_of[(r, int(counts[s]))], view_of[(s, int(counts[r]))]) for r, s in blocks]
 
     # ---- the refusals that need no context are behind us: the tables, the context, the uploads ----
-    def result_of(b, M, timing=(), edges=None):
+    def result_of(b, M, timing=(), edges=None, hyps=None):
         io = copy.copy(sm_io); io.gt_available = (gt_poses[blocks[b][0]] is not None, gt_poses[blocks[b][1]] is not None)
         M.sm_io = io
-        return M.results(timing, edges)
+        return M.results(timing, edges, hyps if num_solutions is None or hyps is not None else {})
     prm = [copy.copy(sm_params) for _ in blocks]
     for q, (r, s) in zip(prm, blocks):
         q.single_robot_lc = (r == s)
@@ -1136,6 +1222,8 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     if total == 0:
         return {blocks[b]: result_of(b, Ms[b], edges=Ms[b].empty_edges()) for b in range(nb)}
     ctx = registration._context()
+    if num_solutions is not None and not hasattr(ctx, "mno_lc_tail_dev"):
+        raise ValueError("the context has no roman_mno_lc_tail_dev" + way)
     if selfs and not hasattr(ctx, "shared_reduce_dev"):      # (these two ask the context itself, as submap_align_pools does)
         raise ValueError("self blocks need a context with roman_shared_reduce_dev" + way)
     if not hasattr(ctx, "session_gate_dev"):
@@ -1246,7 +1334,7 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
                            prob[3].astype(np.int32), pair_index=gpairs)
     # for a RansacReg too the problems of ALL blocks go in one batch: the seed is one per batch and a
     # problem's draws do not depend on its place in it, so a block equals its own submap_align_pools
-    res, per_pair = _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, up(FLh), up(FRh), wait_torch)
+    res, per_pair = _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, up(FLh), up(FRh), wait_torch, num_solutions)
 
     # ---- the records and the accepted list split by todo_off, per block with block-local indices ----
     out = {}
@@ -1255,8 +1343,10 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         lo, hi = int(todo_off[b]), int(todo_off[b + 1])
         part = LoopClosureResult(res.assoc[lo:hi], res.T[lo:hi], res.status[lo:hi], res.stats[lo:hi], res.records[lo:hi],
                                  acc[(acc >= lo) & (acc < hi)] - lo)
+        if num_solutions is not None:
+            part.hypotheses = res.hypotheses[lo:hi]
         edges = _records_into_results(Ms[b], part, local[b][:, 0], local[b][:, 1], nearby[b]) if hi > lo else Ms[b].empty_edges()
-        out[blocks[b]] = result_of(b, Ms[b], [per_pair] * (hi - lo), edges)
+        out[blocks[b]] = result_of(b, Ms[b], [per_pair] * (hi - lo), edges, _hypotheses_of(part, local[b][:, 0], local[b][:, 1]))
     return out
 
 

@@ -7127,24 +7127,25 @@ __device__ __forceinline__ void lc_inv_affine(const double* A, double* I)
     I[12] = 0.0; I[13] = 0.0; I[14] = 0.0; I[15] = 1.0;
 }
 
-// k_lc_tail: one record per problem.  GATES compare what the host compares — the angles themselves (roll, pitch from atan2 /
+// lc_pose_record: the record of ONE pose — what k_lc_tail does per problem and k_mno_lc_tail per (problem, hypothesis).
+// GATES compare what the host compares — the angles themselves (roll, pitch from atan2 /
 // asin) against the thresholds, the association count against lc_association_thresh — so a decision depends on a library
 // function's last bit exactly where the host's does.
 // Quaternion: the branch rule of scipy's Rotation.from_matrix — the FIRST maximum of (R00, R11, R22, trace) picks the
 // component that is computed as a sum (hence non-negative), the other three follow from it, the vector is normalised and
 // NOT canonicalised (w may be negative): as_quat()'s component order xyzw and sign.
-__global__ void __launch_bounds__(256) k_lc_tail(roman_lc_params_t P, int B, LcIn in, roman_lc_record_t* __restrict__ rec)
+// st, T: the pose's status and its 16 doubles; n_assoc, enable, iL, iR: the pose's ENTRIES of those arrays (enable, iL, iR NULL with
+// their arrays), read only where the host reads them; T_ref: the problem's 16 doubles or NULL; FL, FR: the frame pools or NULL.
+__device__ __forceinline__ void lc_pose_record(const roman_lc_params_t& P, int problem, int st, const double* T, const int32_t* n_assoc,
+                                               const double* T_ref, const int32_t* enable, const double* FL, const int32_t* iL,
+                                               const double* FR, const int32_t* iR, roman_lc_record_t& R)
 {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const int st = in.status[b];
     int flags = 0;
     if (st & ROMAN_ST_WORKSPACE) flags = ROMAN_LC_SKIPPED;
     else if (st & ROMAN_ST_INTERNAL) flags = ROMAN_LC_INTERNAL;
     else if (st & (ROMAN_ST_INSUFFICIENT | ROMAN_ST_EMPTY_MAP)) flags = ROMAN_LC_FAILED_INSUFFICIENT;
     double Th[16];
     if (!flags) {
-        const double* T = in.T + (int64_t)b * 16;
         if (P.dim == 2) {                                        // planar estimate lifted to SE(3), identity in z
 #pragma unroll
             for (int t = 0; t < 16; ++t) Th[t] = (t % 5 == 0) ? 1.0 : 0.0;
@@ -7167,17 +7168,16 @@ __global__ void __launch_bounds__(256) k_lc_tail(roman_lc_params_t P, int B, LcI
             }
         }
     }
-    roman_lc_record_t R;
-    R.problem = b; R.reserved = 0;
+    R.problem = problem; R.reserved = 0;
     double theta = 180.0, dist = 1e6;                            // the sentinels of the except-branch
     int n = 0;
     if (!flags) {
-        n = in.n_assoc[b];
+        n = *n_assoc;
         theta = d_nan(); dist = d_nan();
-        if (in.T_ref) {
+        if (T_ref) {
             double Ti[16], E[16];
             lc_inv_affine(Th, Ti);
-            lc_mul4(Ti, in.T_ref + (int64_t)b * 16, E);
+            lc_mul4(Ti, T_ref, E);
             if (P.dim == 2) { theta = atan2(E[4], E[0]); dist = sqrt(E[3] * E[3] + E[7] * E[7]); }
             else {
                 // rotation magnitude: 2 atan2(|q_xyz|, |q_w|) == atan2(|skew part| / 2, (trace - 1) / 2) on [0, pi]
@@ -7191,14 +7191,14 @@ __global__ void __launch_bounds__(256) k_lc_tail(roman_lc_params_t P, int B, LcI
         for (int t = 0; t < 16; ++t) Th[t] = d_nan();
     }
     const bool countable = !(flags & (ROMAN_LC_SKIPPED | ROMAN_LC_INTERNAL));
-    const bool accepted = countable && n >= P.lc_association_thresh && (!in.enable || in.enable[b] != 0);
+    const bool accepted = countable && n >= P.lc_association_thresh && (!enable || *enable != 0);
     double et[3] = {d_nan(), d_nan(), d_nan()}, eq[4] = {d_nan(), d_nan(), d_nan(), d_nan()};
     if (accepted) {
         flags |= ROMAN_LC_ACCEPTED;
         double A[16], E[16];
         const double* Ep = Th;
-        if (in.FL) { lc_mul4(in.FL + (int64_t)in.iL[b] * 16, Th, A); Ep = A; }
-        if (in.FR) { lc_mul4(Ep, in.FR + (int64_t)in.iR[b] * 16, E); Ep = E; }
+        if (FL) { lc_mul4(FL + (int64_t)*iL * 16, Th, A); Ep = A; }
+        if (FR) { lc_mul4(Ep, FR + (int64_t)*iR * 16, E); Ep = E; }
         et[0] = Ep[3]; et[1] = Ep[7]; et[2] = Ep[11];
         const double m00 = Ep[0], m11 = Ep[5], m22 = Ep[10], tr = m00 + m11 + m22;
         int choice = 0; double best = m00;
@@ -7225,23 +7225,92 @@ __global__ void __launch_bounds__(256) k_lc_tail(roman_lc_params_t P, int B, LcI
     for (int t = 0; t < 3; ++t) R.edge_t[t] = et[t];
 #pragma unroll
     for (int t = 0; t < 4; ++t) R.edge_q[t] = eq[t];
+}
+
+// k_lc_tail: one record per problem, one thread each.
+__global__ void __launch_bounds__(256) k_lc_tail(roman_lc_params_t P, int B, LcIn in, roman_lc_record_t* __restrict__ rec)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    roman_lc_record_t R;
+    lc_pose_record(P, b, in.status[b], in.T + (int64_t)b * 16, in.n_assoc + b, in.T_ref ? in.T_ref + (int64_t)b * 16 : nullptr,
+                   in.enable ? in.enable + b : nullptr, in.FL, in.iL ? in.iL + b : nullptr, in.FR, in.iR ? in.iR + b : nullptr, R);
     rec[b] = R;
 }
 
-// k_lc_compact: the indices of the accepted problems in ascending order and their count.  One workgroup; a thread takes PER
-// consecutive problems and k_rowbase's block scan places them — deterministic, the order of the reference's edge loop.
-__global__ void __launch_bounds__(1024) k_lc_compact(int B, const roman_lc_record_t* __restrict__ rec, int32_t* __restrict__ idx, int32_t* __restrict__ count)
+// lc_compact: the indices b < B with take(b) in ascending order and their count, by one workgroup; a thread takes PER
+// consecutive indices and k_rowbase's block scan places them — deterministic, the order of the reference's edge loop.
+template <typename Take>
+__device__ __forceinline__ void lc_compact(int B, Take take, int32_t* __restrict__ idx, int32_t* __restrict__ count)
 {
     __shared__ int shi[17];
     const int tid = threadIdx.x, nt = blockDim.x;
     const int PER = (B + nt - 1) / nt;
     const int b0 = min(B, tid * PER), b1 = min(B, b0 + PER);
     int mine = 0;
-    for (int b = b0; b < b1; ++b) mine += (rec[b].flags & ROMAN_LC_ACCEPTED) ? 1 : 0;
+    for (int b = b0; b < b1; ++b) mine += take(b) ? 1 : 0;
     int total;
     int pos = block_excl_scan(mine, shi, total);
-    for (int b = b0; b < b1; ++b) if (rec[b].flags & ROMAN_LC_ACCEPTED) idx[pos++] = b;
+    for (int b = b0; b < b1; ++b) if (take(b)) idx[pos++] = b;
     if (tid == 0) *count = total;
+}
+
+// k_lc_compact: the accepted records.
+__global__ void __launch_bounds__(1024) k_lc_compact(int B, const roman_lc_record_t* __restrict__ rec, int32_t* __restrict__ idx, int32_t* __restrict__ count)
+{
+    lc_compact(B, [&](int b) { return (rec[b].flags & ROMAN_LC_ACCEPTED) != 0; }, idx, count);
+}
+
+// ---------------------------------------------------------------------------------------------
+// the tail over K hypotheses per problem (roman_mno_solution_t[B][K]): one wave per problem, lane k builds
+// the record of hypothesis k with lc_pose_record — per (b, k) the arithmetic of k_lc_tail — and the wave picks the problem's
+// best hypothesis: among the records without a FAILED_*, SKIPPED or INTERNAL flag the largest n_assoc, the lowest k among
+// equals; -1 when there is none.  The maximum runs over n_assoc + 1 (0 = no candidate, the neutral element) through the DPP
+// tree of wave_max63, the winner is the first set bit of a ballot: no LDS, no atomics, a pure function of the records.
+// ---------------------------------------------------------------------------------------------
+constexpr int MNO_LC_NT = 256;                                   // four problems per workgroup
+
+__device__ __forceinline__ int wave_max63_i32(int v)            // (of non-negative values; valid in lane 63)
+{
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false));     // quad_perm [1,0,3,2]
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false));     // quad_perm [2,3,0,1]
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x124, 0xf, 0xf, false));    // row_ror:4
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false));    // row_ror:8
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));    // row_bcast:15 -> rows 1,3
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));    // row_bcast:31 -> rows 2,3
+    return v;
+}
+
+__global__ void __launch_bounds__(MNO_LC_NT) k_mno_lc_tail(roman_lc_params_t P, int B, int K, const roman_mno_solution_t* __restrict__ sol,
+                                                            const double* __restrict__ T_ref, const int32_t* __restrict__ enable,
+                                                            const double* __restrict__ FL, const int32_t* __restrict__ iL,
+                                                            const double* __restrict__ FR, const int32_t* __restrict__ iR,
+                                                            roman_lc_record_t* __restrict__ rec, int32_t* __restrict__ best)
+{
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * (MNO_LC_NT / 64) + (threadIdx.x >> 6);        // wave-uniform
+    if (b >= B) return;
+    int key = 0;                                                 // n_assoc + 1 of a candidate, 0 otherwise
+    if (lane < K) {
+        const int64_t r = (int64_t)b * K + lane;
+        const roman_mno_solution_t* s = sol + r;
+        roman_lc_record_t R;
+        lc_pose_record(P, (int)r, s->status, s->T, &s->n_assoc, T_ref ? T_ref + (int64_t)b * 16 : nullptr, enable ? enable + b : nullptr,
+                       FL, iL ? iL + b : nullptr, FR, iR ? iR + b : nullptr, R);
+        rec[r] = R;
+        const int no = ROMAN_LC_FAILED_INSUFFICIENT | ROMAN_LC_FAILED_TILT | ROMAN_LC_FAILED_UPSIDE_DOWN | ROMAN_LC_SKIPPED | ROMAN_LC_INTERNAL;
+        if (!(R.flags & no)) key = max(R.n_assoc, 0) + 1;
+    }
+    const int top = __builtin_amdgcn_readlane(wave_max63_i32(key), 63);
+    const unsigned long long won = __ballot(key == top);
+    if (lane == 0) best[b] = top > 0 ? __ffsll((long long)won) - 1 : -1;
+}
+
+// k_mno_best_compact: the problems whose best hypothesis is accepted, ascending, and their count.
+__global__ void __launch_bounds__(1024) k_mno_best_compact(int B, int K, const roman_lc_record_t* __restrict__ rec, const int32_t* __restrict__ best,
+                                                           int32_t* __restrict__ idx, int32_t* __restrict__ count)
+{
+    lc_compact(B, [&](int b) { const int k = best[b]; return k >= 0 && (rec[(int64_t)b * K + k].flags & ROMAN_LC_ACCEPTED) != 0; }, idx, count);
 }
 
 // ---------------------------------------------------------------------------------------------

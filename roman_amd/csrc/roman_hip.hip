@@ -2433,6 +2433,75 @@ static int mno_check(roman_ctx* c, const roman_params_t* params, int32_t B, cons
     return ROMAN_OK;
 }
 
+// The tail over K hypotheses per problem: switches, device inputs, device outputs.
+struct MnoLcTail {
+    roman_lc_params_t P; const double* T_ref; const int32_t* enable; const double* FL; const int32_t* iL; const double* FR; const int32_t* iR;
+    roman_lc_record_t* rec; int32_t* best; int32_t* idx; int32_t* cnt; int32_t* bidx; int32_t* bcnt;
+};
+
+static int make_mno_lc_tail(roman_ctx* c, const roman_lc_params_t* lp, int32_t B, int32_t K, const double* T_ref, const int32_t* enable,
+                            const double* FL, const int32_t* iL, const double* FR, const int32_t* iR, roman_lc_record_t* records, int32_t* best,
+                            int32_t* accepted_idx, int32_t* n_accepted, int32_t* accepted_best_idx, int32_t* n_accepted_best, MnoLcTail* t)
+{
+    if (B < 0) return fail(c, ROMAN_E_INVALID, "B < 0");
+    if (K < 1 || K > ROMAN_MNO_MAX_SOLUTIONS) return fail(c, ROMAN_E_INVALID, "num_solutions must be 1..%d (got %d)", ROMAN_MNO_MAX_SOLUTIONS, K);
+    if ((int64_t)B * K > INT32_MAX) return fail(c, ROMAN_E_INVALID, "B * num_solutions = %lld records: a record index is an int32", (long long)B * K);
+    const int rc = check_lc_params(c, lp);
+    if (rc) return rc;
+    if (!n_accepted || !n_accepted_best) return fail(c, ROMAN_E_INVALID, "n_accepted / n_accepted_best is NULL");
+    if ((FL != nullptr) != (iL != nullptr) || (FR != nullptr) != (iR != nullptr)) return fail(c, ROMAN_E_INVALID, "a frame pool and its index array come together (FL with iL, FR with iR)");
+    if (B > 0 && (!records || !best)) return fail(c, ROMAN_E_INVALID, "records / best is NULL");
+    if (B > 0 && (!accepted_idx || !accepted_best_idx)) return fail(c, ROMAN_E_INVALID, "accepted_idx / accepted_best_idx is NULL");
+    *t = MnoLcTail{*lp, T_ref, enable, FL, iL, FR, iR, records, best, accepted_idx, n_accepted, accepted_best_idx, n_accepted_best};
+    return ROMAN_OK;
+}
+
+// k_mno_lc_tail, then both lists, behind whatever is queued on `stream`
+static int enqueue_mno_lc_tail(roman_ctx* c, hipStream_t stream, int B, int K, const roman_mno_solution_t* sol, const MnoLcTail& t)
+{
+    if (B > 0) {
+        if (!sol) return fail(c, ROMAN_E_INVALID, "sol is NULL");
+        constexpr int PER = MNO_LC_NT / 64;
+        hipLaunchKernelGGL(k_mno_lc_tail, dim3((unsigned)((B + PER - 1) / PER)), dim3(MNO_LC_NT), 0, stream, t.P, (int)B, (int)K, sol,
+                           t.T_ref, t.enable, t.FL, t.iL, t.FR, t.iR, t.rec, t.best);
+        HIPCHK(c, hipGetLastError());
+    }
+    const int n = B * K;
+    hipLaunchKernelGGL(k_lc_compact, dim3(1), dim3(n > 256 ? 1024 : 256), 0, stream, n, (const roman_lc_record_t*)t.rec, t.idx, t.cnt);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_mno_best_compact, dim3(1), dim3(B > 256 ? 1024 : 256), 0, stream, (int)B, (int)K, (const roman_lc_record_t*)t.rec,
+                       (const int32_t*)t.best, t.bidx, t.bcnt);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+// roman_mno_batch_dev, optionally with the hypothesis tail behind the last round on the same stream
+static int mno_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B, const double* feats, const int64_t* off1, const int32_t* n1,
+                         const int64_t* off2, const int32_t* n2, int32_t F, const int32_t* assoc, const int64_t* assoc_off,
+                         int32_t num_solutions, int32_t kmax, int32_t* assoc_out, roman_mno_solution_t* sol_out, roman_stats_t* stats_out,
+                         const MnoLcTail* tail)
+{
+    BatchCheck chk; chk.assoc = assoc; chk.assoc_off = assoc_off;
+    bool any = false;
+    int rc = mno_check(c, params, B, off1, n1, off2, n2, chk, num_solutions, kmax, assoc_out, sol_out, &any);
+    if (rc) return rc;
+    if (B == 0) {
+        if (tail) { HIPCHK(c, hipSetDevice(c->device)); return enqueue_mno_lc_tail(c, c->stream, 0, num_solutions, nullptr, *tail); }
+        return ROMAN_OK;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    DevParams D;
+    rc = make_dev_params(c, params, F, &D);
+    if (rc) return rc;
+    if (!feats && any) return fail(c, ROMAN_E_INVALID, "feats is NULL");
+    static_assert(STREAM_MAXL == ROMAN_MNO_MAX_ASSOC, "the documented cap is the stream layout's");
+    const BatchIn in{B, feats, off1, n1, off2, n2, F, assoc, assoc_off};
+    return on_next_workspace(c, [&](hipStream_t stream) -> int {
+        const int r = run_mno(c, D, params, in, num_solutions, kmax, assoc_out, sol_out, stats_out);
+        return (!r && tail) ? enqueue_mno_lc_tail(c, stream, B, num_solutions, sol_out, *tail) : r;
+    });
+}
+
 int roman_mno_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
                         const double* feats, const int64_t* off1, const int32_t* n1,
                         const int64_t* off2, const int32_t* n2, int32_t F,
@@ -2441,32 +2510,63 @@ int roman_mno_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
                         roman_mno_solution_t* sol_out, roman_stats_t* stats_out)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    BatchCheck chk; chk.assoc = assoc; chk.assoc_off = assoc_off;
-    bool any = false;
-    int rc = mno_check(c, params, B, off1, n1, off2, n2, chk, num_solutions, kmax, assoc_out, sol_out, &any);
-    if (rc || B == 0) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    DevParams D;
-    rc = make_dev_params(c, params, F, &D);
-    if (rc) return rc;
-    if (!feats && any) return fail(c, ROMAN_E_INVALID, "feats is NULL");
-    static_assert(STREAM_MAXL == ROMAN_MNO_MAX_ASSOC, "the documented cap is the stream layout's");
-    const BatchIn in{B, feats, off1, n1, off2, n2, F, assoc, assoc_off};
-    return on_next_workspace(c, [&](hipStream_t) -> int { return run_mno(c, D, params, in, num_solutions, kmax, assoc_out, sol_out, stats_out); });
+    return mno_batch_dev(c, params, B, feats, off1, n1, off2, n2, F, assoc, assoc_off, num_solutions, kmax, assoc_out, sol_out, stats_out, nullptr);
 }
 
-int roman_mno_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
-                    const double* feats, int64_t n_objects,
-                    const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
-                    const int32_t* assoc, const int64_t* assoc_off,
-                    int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
-                    roman_mno_solution_t* sol_out, roman_stats_t* stats_out)
+// The hypothesis tail on its own, on the context's stream.  At pipeline depth >= 2 the solutions it reads are written on internal
+// streams: the caller orders them in front with roman_ctx_join().
+int roman_mno_lc_tail_dev(roman_ctx_t* c, const roman_lc_params_t* lc_params, int32_t B, int32_t K, const roman_mno_solution_t* sol,
+                          const double* T_ref, const int32_t* enable, const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                          roman_lc_record_t* records, int32_t* best, int32_t* accepted_idx, int32_t* n_accepted,
+                          int32_t* accepted_best_idx, int32_t* n_accepted_best)
 {
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    MnoLcTail t;
+    const int rc = make_mno_lc_tail(c, lc_params, B, K, T_ref, enable, FL, iL, FR, iR, records, best, accepted_idx, n_accepted, accepted_best_idx, n_accepted_best, &t);
+    if (rc) return rc;
+    if (B > 0 && !sol) return fail(c, ROMAN_E_INVALID, "sol is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    return enqueue_mno_lc_tail(c, c->stream, B, K, sol, t);
+}
+
+int roman_mno_lc_batch_dev(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                           const double* feats, const int64_t* off1, const int32_t* n1,
+                           const int64_t* off2, const int32_t* n2, int32_t F,
+                           const int32_t* assoc, const int64_t* assoc_off,
+                           int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                           roman_mno_solution_t* sol_out, roman_stats_t* stats_out,
+                           const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                           const double* FL, const int32_t* iL, const double* FR, const int32_t* iR,
+                           roman_lc_record_t* records, int32_t* best, int32_t* accepted_idx, int32_t* n_accepted,
+                           int32_t* accepted_best_idx, int32_t* n_accepted_best)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    MnoLcTail t;
+    const int rc = make_mno_lc_tail(c, lc_params, B, num_solutions, T_ref, enable, FL, iL, FR, iR, records, best, accepted_idx, n_accepted, accepted_best_idx, n_accepted_best, &t);
+    if (rc) return rc;
+    if (params && lc_params->dim != params->point_dim) return fail(c, ROMAN_E_INVALID, "lc_params.dim (%d) differs from params.point_dim (%d)", lc_params->dim, params->point_dim);
+    return mno_batch_dev(c, params, B, feats, off1, n1, off2, n2, F, assoc, assoc_off, num_solutions, kmax, assoc_out, sol_out, stats_out, &t);
+}
+
+// What roman_mno_lc_batch adds to roman_mno_batch: the tail's host arrays.
+struct MnoLcHost {
+    const roman_lc_params_t* lp; const double* T_ref; const int32_t* enable; const double* FL; int32_t n_left; const int32_t* iL;
+    const double* FR; int32_t n_right; const int32_t* iR; roman_lc_record_t* records; int32_t* best; int32_t* accepted_idx; int32_t* n_accepted;
+    int32_t* accepted_best_idx; int32_t* n_accepted_best;
+};
+
+static int mno_to_host(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                       const double* feats, int64_t n_objects,
+                       const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
+                       const int32_t* assoc, const int64_t* assoc_off,
+                       int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                       roman_mno_solution_t* sol_out, roman_stats_t* stats_out, const MnoLcHost* lc)
+{
     if (n_objects < 0 || F < 0) return fail(c, ROMAN_E_INVALID, "negative size");
     BatchCheck chk; chk.n_objects = n_objects; chk.assoc = assoc; chk.assoc_off = assoc_off; chk.assoc_on_host = true; chk.whole_list = true;
     int rc = mno_check(c, params, B, off1, n1, off2, n2, chk, num_solutions, kmax, assoc_out, sol_out);
-    if (rc || B == 0) return rc;
+    if (rc) return rc;
+    if (B == 0) { if (lc) { *lc->n_accepted = 0; *lc->n_accepted_best = 0; } return ROMAN_OK; }
     const int K = num_solutions;
     HIPCHK(c, hipSetDevice(c->device));
     { int rc0 = use_ws0(c); if (rc0) return rc0; }
@@ -2511,7 +2611,66 @@ int roman_mno_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
     memcpy(sol_out, hs.data(), sizeof(roman_mno_solution_t) * nSol);
     if (stats_out && hipMemcpy(stats_out, dStats, sizeof(roman_stats_t) * nSol, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return fail(c, ROMAN_E_HIP, "statistics read-back failed"); }
     if (rowsPer && hipMemcpy(assoc_out, dAssoc, sizeof(int32_t) * nSol * rowsPer, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return fail(c, ROMAN_E_HIP, "association read-back failed"); }
+    if (lc) {                                                    // the tail ONCE over the final block: no record comes from a skipped attempt
+        const size_t nb = (size_t)B;
+        HostMirror m(c);
+        const auto dRef = m.in(lc->T_ref, lc->T_ref ? sizeof(double) * 16 * nb : 0);
+        const auto dEn = m.in(lc->enable, lc->enable ? sizeof(int32_t) * nb : 0);
+        const auto dFL = m.in(lc->FL, lc->FL ? sizeof(double) * 16 * (size_t)lc->n_left : 0);
+        const auto dIL = m.in(lc->iL, lc->iL ? sizeof(int32_t) * nb : 0);
+        const auto dFR = m.in(lc->FR, lc->FR ? sizeof(double) * 16 * (size_t)lc->n_right : 0);
+        const auto dIR = m.in(lc->iR, lc->iR ? sizeof(int32_t) * nb : 0);
+        const auto lrec = m.out(lc->records, sizeof(roman_lc_record_t) * nSol);
+        const auto lbest = m.out(lc->best, sizeof(int32_t) * nb);
+        const auto lidx = m.out(lc->accepted_idx, sizeof(int32_t) * nSol);
+        const auto lcnt = m.out(lc->n_accepted, sizeof(int32_t));
+        const auto bidx = m.out(lc->accepted_best_idx, sizeof(int32_t) * nb);
+        const auto bcnt = m.out(lc->n_accepted_best, sizeof(int32_t));
+        rc = m.upload();
+        if (rc) return rc;
+        const MnoLcTail t{*lc->lp, dRef.dev(), dEn.dev(), dFL.dev(), dIL.dev(), dFR.dev(), dIR.dev(), lrec.dev(), lbest.dev(), lidx.dev(), lcnt.dev(), bidx.dev(), bcnt.dev()};
+        rc = enqueue_mno_lc_tail(c, WS.stream, B, K, dSol, t);   // (everything in front of it is complete: the loop above ends on a sync)
+        if (rc) return rc;
+        rc = m.download();
+        if (rc) return rc;
+    }
     return scope.close(ROMAN_OK);
+}
+
+int roman_mno_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                    const double* feats, int64_t n_objects,
+                    const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
+                    const int32_t* assoc, const int64_t* assoc_off,
+                    int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                    roman_mno_solution_t* sol_out, roman_stats_t* stats_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    return mno_to_host(c, params, B, feats, n_objects, off1, n1, off2, n2, F, assoc, assoc_off, num_solutions, kmax, assoc_out, sol_out, stats_out, nullptr);
+}
+
+int roman_mno_lc_batch(roman_ctx_t* c, const roman_params_t* params, int32_t B,
+                       const double* feats, int64_t n_objects,
+                       const int64_t* off1, const int32_t* n1, const int64_t* off2, const int32_t* n2, int32_t F,
+                       const int32_t* assoc, const int64_t* assoc_off,
+                       int32_t num_solutions, int32_t kmax, int32_t* assoc_out,
+                       roman_mno_solution_t* sol_out, roman_stats_t* stats_out,
+                       const roman_lc_params_t* lc_params, const double* T_ref, const int32_t* enable,
+                       const double* FL, int32_t n_left, const int32_t* iL, const double* FR, int32_t n_right, const int32_t* iR,
+                       roman_lc_record_t* records, int32_t* best, int32_t* accepted_idx, int32_t* n_accepted,
+                       int32_t* accepted_best_idx, int32_t* n_accepted_best)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    MnoLcTail t;
+    const int rc = make_mno_lc_tail(c, lc_params, B, num_solutions, T_ref, enable, FL, iL, FR, iR, records, best, accepted_idx, n_accepted, accepted_best_idx, n_accepted_best, &t);
+    if (rc) return rc;
+    if (params && lc_params->dim != params->point_dim) return fail(c, ROMAN_E_INVALID, "lc_params.dim (%d) differs from params.point_dim (%d)", lc_params->dim, params->point_dim);
+    if (n_left < 0 || n_right < 0) return fail(c, ROMAN_E_INVALID, "negative size");
+    for (int b = 0; b < B; ++b) {                                // the device indexes the frame pools with these
+        if (iL && (iL[b] < 0 || iL[b] >= n_left)) return fail(c, ROMAN_E_INVALID, "iL[%d] = %d outside the %d left frames", b, iL[b], n_left);
+        if (iR && (iR[b] < 0 || iR[b] >= n_right)) return fail(c, ROMAN_E_INVALID, "iR[%d] = %d outside the %d right frames", b, iR[b], n_right);
+    }
+    const MnoLcHost lc{lc_params, T_ref, enable, FL, n_left, iL, FR, n_right, iR, records, best, accepted_idx, n_accepted, accepted_best_idx, n_accepted_best};
+    return mno_to_host(c, params, B, feats, n_objects, off1, n1, off2, n2, F, assoc, assoc_off, num_solutions, kmax, assoc_out, sol_out, stats_out, &lc);
 }
 
 // --- RANSAC registration on object centres, batched ([REF roman/align/ransac_reg.py:16-53]) ----------------------

@@ -251,6 +251,16 @@ class LoopClosureResult(BatchResult):
     ransac_records: Optional[np.ndarray] = None
 
 
+@dataclass
+class MnoLoopClosureResult(MnoResult):
+    """A multi-solution result with the hypothesis tail behind it (roman_mno_lc_batch)."""
+    n_assoc: np.ndarray        # (B, K) int32: associations of every solution as the solver counted them
+    records: np.ndarray        # (B, K) structured array (lc_record_dtype); records[b, k]["problem"] == b * K + k
+    best: np.ndarray           # (B,) int32: the hypothesis a problem's results come from, -1 when none qualifies
+    accepted: np.ndarray       # (n_accepted,) int32: accepted (b, k) as b * K + k, ascending
+    accepted_best: np.ndarray  # (n_accepted_best,) int32: problems whose best hypothesis is accepted, ascending
+
+
 class Context:
     """One roman_ctx: a HIP device + stream + the library's HBM workspace."""
 
@@ -471,6 +481,71 @@ class Context:
                                            int(F), _vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax), _vp(assoc_out_ptr),
                                            _vp(sol_out_ptr), _vp(stats_out_ptr))
         self._check(rc, "roman_mno_batch_dev")
+
+    def mno_lc_tail_dev(self, lc_params, B, K, sol_ptr, records_ptr, best_ptr, accepted_idx_ptr, n_accepted_ptr, accepted_best_idx_ptr,
+                        n_accepted_best_ptr, T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None, FR_ptr=None, iR_ptr=None):
+        """The tail over K hypotheses per problem on its own (roman_mno_lc_tail_dev): sol_ptr is roman_mno_solution_t[B][K] in HBM,
+        the per-problem inputs are shared by a problem's hypotheses; every pointer a device address (an integer).  A pure enqueue
+        on the context's stream."""
+        rc = self._lib.roman_mno_lc_tail_dev(self._h, C.byref(lc_params), int(B), int(K), _vp(sol_ptr), _vp(T_ref_ptr), _vp(enable_ptr),
+                                             _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(best_ptr),
+                                             _vp(accepted_idx_ptr), _vp(n_accepted_ptr), _vp(accepted_best_idx_ptr), _vp(n_accepted_best_ptr))
+        self._check(rc, "roman_mno_lc_tail_dev")
+
+    def mno_lc_batch_dev(self, params, feats_ptr, F, off1, n1, off2, n2, num_solutions, kmax, assoc_out_ptr, sol_out_ptr, lc_params,
+                         records_ptr, best_ptr, accepted_idx_ptr, n_accepted_ptr, accepted_best_idx_ptr, n_accepted_best_ptr,
+                         stats_out_ptr=None, assoc_ptr=None, assoc_off=None, T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None,
+                         FR_ptr=None, iR_ptr=None):
+        """mno_batch_dev with the hypothesis tail enqueued behind its rounds on the same stream (roman_mno_lc_batch_dev): a pure
+        enqueue, complete after sync()."""
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        if assoc_off is not None:
+            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        self._generation += 1
+        rc = self._lib.roman_mno_lc_batch_dev(self._h, C.byref(params), int(n1.shape[0]), _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                              int(F), _vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax), _vp(assoc_out_ptr),
+                                              _vp(sol_out_ptr), _vp(stats_out_ptr), C.byref(lc_params), _vp(T_ref_ptr), _vp(enable_ptr),
+                                              _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(best_ptr),
+                                              _vp(accepted_idx_ptr), _vp(n_accepted_ptr), _vp(accepted_best_idx_ptr), _vp(n_accepted_best_ptr))
+        self._check(rc, "roman_mno_lc_batch_dev")
+
+    def mno_lc_batch(self, params, feats, off1, n1, off2, n2, lc, num_solutions=2, assoc=None, assoc_off=None, kmax=None):
+        """Host-pointer batched mno_clipper with the hypothesis tail behind it (roman_mno_lc_batch): `lc` is an LcInputs whose
+        per-problem arrays have B entries.  -> MnoLoopClosureResult."""
+        feats = _f64(feats)
+        if feats.ndim != 2:
+            raise ValueError("feats must be (n_objects, F)")
+        n_obj, F = feats.shape
+        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+        B, K = int(n1.shape[0]), int(num_solutions)
+        if assoc is not None:
+            assoc = np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2)
+            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        if kmax is None:
+            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
+        Kc = max(K, 0)
+        a_out = np.zeros((B, Kc, kmax, 2), dtype=np.int32)
+        sol = np.zeros((B, Kc), dtype=mno_solution_dtype())
+        stats = np.zeros((B, Kc), dtype=stats_dtype())
+        records = np.zeros((B, Kc), dtype=lc_record_dtype()); best = np.full(max(B, 1), -1, dtype=np.int32)
+        idx = np.zeros(max(B * Kc, 1), dtype=np.int32); cnt = np.zeros(1, dtype=np.int32)
+        bidx = np.zeros(max(B, 1), dtype=np.int32); bcnt = np.zeros(1, dtype=np.int32)
+        lp = lc.params()
+        T_ref, enable, FL, iL, FR, iR = lc.arrays(B)
+        self._generation += 1
+        rc = self._lib.roman_mno_lc_batch(self._h, C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
+                                          _ptr(assoc), _ptr(assoc_off), K, int(kmax), _ptr(a_out), _ptr(sol), _ptr(stats),
+                                          C.byref(lp), _ptr(T_ref), _ptr(enable), _ptr(FL), 0 if FL is None else FL.shape[0], _ptr(iL),
+                                          _ptr(FR), 0 if FR is None else FR.shape[0], _ptr(iR), _ptr(records), _ptr(best), _ptr(idx), _ptr(cnt),
+                                          _ptr(bidx), _ptr(bcnt))
+        self._check(rc, "roman_mno_lc_batch")
+        s = params.point_dim + 1
+        rows = np.minimum(sol["n_assoc"], kmax)
+        return MnoLoopClosureResult([[a_out[b, k, :rows[b, k]].copy() for k in range(K)] for b in range(B)],
+                                    sol["score"].copy(), sol["T"][:, :, :s * s].reshape(B, K, s, s).copy(), sol["status"].copy(), stats,
+                                    sol["n_assoc"].copy(), records, best[:B].copy(), idx[:int(cnt[0])].copy(), bidx[:int(bcnt[0])].copy())
 
     # ------------------------------------------------------------------ RANSAC registration
     def ransac_batch(self, rparams, pts, off1, n1, off2, n2, kmax=None, counts=None):
