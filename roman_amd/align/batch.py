@@ -11,6 +11,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from .. import _abi
+from ..runtime import default_kmax, ransac_kmax
 from .ransac_reg import RansacReg
 
 
@@ -31,7 +32,7 @@ class AlignmentBatch:
         return int(self.n1.shape[0])
 
     def kmax(self):
-        return int(max(1, np.max(np.minimum(self.n1, self.n2)))) if len(self) else 1
+        return default_kmax(self.n1, self.n2)
 
     def subset(self, lo, hi):
         """Problems [lo, hi) over the same pool (used for sharding across ranks)."""
@@ -119,7 +120,7 @@ def run_ransac_batch(registration, batch: AlignmentBatch, ctx=None, counts=None)
     """One roman_ransac_batch call for `batch` (its pool holds object centres, 3 columns): register() + T_align() of a RansacReg
     ([REF roman/align/ransac_reg.py:16-53]) for every pair -> runtime.RansacResult."""
     ctx = ctx or registration._context()
-    kmax = int(max(1, np.max(batch.n1.astype(np.int64) * batch.n2))) if len(batch) else 1       # every correspondence may be an inlier
+    kmax = ransac_kmax(batch.n1, batch.n2)
     return ctx.ransac_batch(registration._ransac_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2, kmax=kmax, counts=counts)
 
 
@@ -139,7 +140,7 @@ def run_ransac_lc_batch(registration, batch: AlignmentBatch, lc, ctx=None):
     """One roman_ransac_lc_batch call for `batch` — its pool may have any row width F >= 3, the centre in columns 0-2 — with the
     loop-closure tail `lc` (runtime.LcInputs) behind the RANSAC kernel -> runtime.LoopClosureResult."""
     ctx = ctx or registration._context()
-    kmax = int(max(1, np.max(batch.n1.astype(np.int64) * batch.n2))) if len(batch) else 1       # every correspondence may be an inlier
+    kmax = ransac_kmax(batch.n1, batch.n2)
     return ctx.ransac_lc_batch(registration._ransac_params(), batch.feats, batch.off1, batch.n1, batch.off2, batch.n2, lc, kmax=kmax)
 
 

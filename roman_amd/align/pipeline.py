@@ -223,6 +223,18 @@ def default_chunk(B):
     return min(2048, ((-(-B // 2)) + 63) & ~63)
 
 
+def _runs(skipped, chunk):
+    """Ascending problem indices -> (lo, hi) of the maximal runs of consecutive ones, cut into pieces of `chunk` problems at most
+    (what the library's reissue_runs does for the host-pointer calls)."""
+    b = 0
+    while b < len(skipped):
+        e = b + 1
+        while e < len(skipped) and skipped[e] == skipped[e - 1] + 1 and e - b < chunk:
+            e += 1
+        yield int(skipped[b]), int(skipped[e - 1]) + 1
+        b = e
+
+
 def issue_chunked(ctx, P, pool, batch, kmax, a_out, n_out, T_out, st_out, stats_out=None, assoc_dev=None, chunk=None, in_flight=3):
     """The problems of `batch` over the device-resident `pool` as calls of `chunk` problems with `in_flight` of them on the device
     at once; problem b writes row b of the output tensors (torch, on the pool's device).  Problems a call skipped for workspace
@@ -269,13 +281,8 @@ def issue_chunked(ctx, P, pool, batch, kmax, a_out, n_out, T_out, st_out, stats_
             skipped = np.nonzero((status & again) != 0)[0]
             if not len(skipped) or attempt == MAX_ATTEMPTS:
                 break
-            b = 0
-            while b < len(skipped):                                 # runs of consecutive skipped problems, a chunk at most
-                e = b + 1
-                while e < len(skipped) and skipped[e] == skipped[e - 1] + 1 and e - b < chunk:
-                    e += 1
-                issue(int(skipped[b]), int(skipped[e - 1]) + 1)
-                b = e
+            for lo, hi in _runs(skipped, chunk):
+                issue(lo, hi)
     finally:
         ctx.set_pipeline(depth_before)
         if teams_off:
@@ -319,13 +326,8 @@ def issue_mno_chunked(ctx, P, pool, batch, K, kmax, a_out, sol_out, assoc_dev=No
             skipped = np.nonzero((status & _abi.ROMAN_ST_WORKSPACE) != 0)[0]
             if not len(skipped) or attempt == MAX_ATTEMPTS:
                 break
-            b = 0
-            while b < len(skipped):
-                e = b + 1
-                while e < len(skipped) and skipped[e] == skipped[e - 1] + 1 and e - b < chunk:
-                    e += 1
-                issue(int(skipped[b]), int(skipped[e - 1]) + 1)
-                b = e
+            for lo, hi in _runs(skipped, chunk):
+                issue(lo, hi)
     finally:
         ctx.set_pipeline(depth_before)
     return status

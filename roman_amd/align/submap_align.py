@@ -664,10 +664,10 @@ def _ransac_lc_over_pool(torch, ctx, registration, pool, batch, lp, o, tail_ptrs
     the whole batch fits RANSAC_ASSOC_CHUNK_BYTES; otherwise calls without a tail over chunks of problems — one chunk-sized
     association buffer, read back between them — and ONE roman_lc_tail_dev over all problems at the end.
     -> runtime.LoopClosureResult with ransac_records."""
-    from ..runtime import ransac_record_dtype
+    from ..runtime import ransac_kmax, ransac_record_dtype
     B, F, dev = len(batch), int(pool.shape[1]), pool.device
     rp = registration._ransac_params()
-    kmax = int(max(1, np.max(batch.n1.astype(np.int64) * batch.n2)))
+    kmax = ransac_kmax(batch.n1, batch.n2)
     chunk = max(1, int(RANSAC_ASSOC_CHUNK_BYTES // (8 * kmax)))
     nb = _abi.RANSAC_RECORD_NBYTES
     rec = torch.zeros(B * nb, dtype=torch.uint8, device=dev)

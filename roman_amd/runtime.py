@@ -36,6 +36,108 @@ def _given(a, shape, dtype, fill):
     return a
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# What the batch wrappers of Context share ("Python side of the entry points"): a wrapper reads "convert, allocate, call, unpack", and each of
+# these is one of those steps.  tests/test_runtime_marshalling.py holds what reaches the C ABI through them.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _vps(*ptrs):
+    """Device addresses as pointer arguments, in the order given."""
+    return [_vp(p) for p in ptrs]
+
+
+def _problems(off1, n1, off2, n2):
+    """The problem table of a batch call in the C ABI's types -> (off1, n1, off2, n2, B)."""
+    off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
+    n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
+    return off1, n1, off2, n2, int(n1.shape[0])
+
+
+def _pool(feats):
+    """A host feature pool -> (feats float64 (n_objects, F), n_objects, F)."""
+    feats = _f64(feats)
+    if feats.ndim != 2:
+        raise ValueError("feats must be (n_objects, F)")
+    return (feats, *feats.shape)
+
+
+def _assoc_list(assoc, assoc_off):
+    """Explicit association lists of a host-pointer call (absent: both as they are)."""
+    if assoc is None:
+        return assoc, assoc_off
+    return np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2), np.ascontiguousarray(assoc_off, dtype=np.int64)
+
+
+def _assoc_off(assoc_off):
+    """The offsets of association lists that are in HBM (a device-pointer call)."""
+    return None if assoc_off is None else np.ascontiguousarray(assoc_off, dtype=np.int64)
+
+
+def default_kmax(n1, n2):
+    """The association rows a problem of a CLIPPER batch can return: the smaller map of the largest problem (at least 1)."""
+    return int(max(1, np.max(np.minimum(n1, n2)))) if len(n1) else 1
+
+
+def ransac_kmax(n1, n2):
+    """The same for a RANSAC batch: every correspondence may be an inlier."""
+    return int(max(1, np.max(n1.astype(np.int64) * n2))) if len(n1) else 1
+
+
+def _ransac_counts(counts, B, rparams):
+    """The `counts` argument of the RANSAC calls: None, True (a fresh (B, max_iteration) array of -2) or the caller's, checked."""
+    if counts is True:
+        return np.full((B, max(int(rparams.max_iteration), 0)), -2, dtype=np.int32)
+    if counts is not None and (counts.dtype != np.int32 or not counts.flags.c_contiguous or counts.shape != (B, int(rparams.max_iteration))):
+        raise ValueError("counts must be a C-contiguous (B, max_iteration) int32 array")
+    return counts
+
+
+def _solver_out(B, kmax):
+    """The cleared host outputs of a single-solution call -> (assoc_out, n_assoc_out, T_out, status_out, stats_out)."""
+    stats = np.zeros(B, dtype=stats_dtype())
+    assert stats.dtype.itemsize == _abi.STATS_NBYTES
+    return np.zeros((B, kmax, 2), dtype=np.int32), np.zeros(B, dtype=np.int32), np.zeros((B, 16), dtype=np.float64), np.zeros(B, dtype=np.int32), stats
+
+
+def _mno_out(B, K, kmax):
+    """The cleared host outputs of a call with K solutions per problem -> (assoc_out, sol_out, stats_out)."""
+    sol = np.zeros((B, K), dtype=mno_solution_dtype())
+    assert sol.dtype.itemsize == _abi.MNO_SOLUTION_NBYTES
+    return np.zeros((B, K, kmax, 2), dtype=np.int32), sol, np.zeros((B, K), dtype=stats_dtype())
+
+
+def _tail_out(*shape):
+    """The cleared host outputs of the loop-closure tail over (B,) or (B, K) poses -> (records, accepted_idx, n_accepted)."""
+    records = np.zeros(shape, dtype=lc_record_dtype())
+    assert records.dtype.itemsize == _abi.LC_RECORD_NBYTES
+    return records, np.zeros(max(records.size, 1), dtype=np.int32), np.zeros(1, dtype=np.int32)
+
+
+def _mno_best_out(B):
+    """What the hypothesis tail adds per problem -> (best, accepted_best_idx, n_accepted_best)."""
+    return np.full(max(B, 1), -1, dtype=np.int32), np.zeros(max(B, 1), dtype=np.int32), np.zeros(1, dtype=np.int32)
+
+
+def _lc_host_args(lp, arrays):
+    """The tail's inputs of a host-pointer call in the C ABI's order: `lp` an LcInputs.params(), `arrays` its arrays(B) — both
+    held by the caller until the call has returned."""
+    T_ref, enable, FL, iL, FR, iR = arrays
+    return [C.byref(lp), _ptr(T_ref), _ptr(enable), _ptr(FL), 0 if FL is None else FL.shape[0], _ptr(iL),
+            _ptr(FR), 0 if FR is None else FR.shape[0], _ptr(iR)]
+
+
+def _solver_result(a_out, n_out, T, dim):
+    """-> (the association rows of every problem, the (dim+1)^2 poses) out of the cleared-and-filled outputs, as copies."""
+    B, s = T.shape[0], dim + 1
+    return [a_out[b, :n_out[b]].copy() for b in range(B)], T[:, :s * s].reshape(B, s, s).copy()
+
+
+def _mno_result(a_out, sol, K, dim):
+    """-> (assoc[b][k], score, T, status) of a call with K solutions per problem, as copies."""
+    B, s = sol.shape[0], dim + 1
+    return ([[a_out[b, k, :sol["n_assoc"][b, k]].copy() for k in range(K)] for b in range(B)],
+            sol["score"].copy(), sol["T"][:, :, :s * s].reshape(B, K, s, s).copy(), sol["status"].copy())
+
+
 def stats_dtype():
     return np.dtype([("n_assoc_in", np.int32), ("n_live", np.int32), ("nnz_upper", np.int64),
                      ("n_pass", np.int32), ("outer_iters", np.int32), ("inner_iters", np.int32),
@@ -275,6 +377,14 @@ class Context:
         # One context holds ONE stepwise problem (the matrices of the last score()/set_matrix_data()).  Every call
         # that replaces or invalidates it bumps this counter; holders of a problem (the clipperpy shim's CLIPPER
         # objects) remember the value they loaded at and re-send their inputs when it has moved on.
+        # The stepwise problem lives in workspace 0 of the library, and the library forgets it (its `last.scored`) in two places:
+        # on_next_workspace(), which every solver enqueue goes through (align_batch_dev, align_lc_batch_dev, mno_batch_dev,
+        # mno_lc_batch_dev, and the host and resident forms built on them), and every host-pointer call that stages its inputs in
+        # workspace 0 (ransac_batch, ransac_lc_batch, the submap / gate / frame-select calls).  The batch wrappers among these
+        # bump the counter in ONE place, _workspace_call(); the stage calls further down bump it themselves.  The pure enqueues
+        # that only read and write the caller's device buffers through small descriptor stagings of their own — lc_tail_dev,
+        # mno_lc_tail_dev, ransac_batch_dev, ransac_lc_batch_dev, shared_ids_dev, shared_reduce_dev, and the other stage calls'
+        # _dev forms — leave workspace 0 alone and do not bump it (they go through _enqueue()).
         self._generation = 0
         self.pipeline_depth = 1                 # what set_pipeline() last set (callers that change it restore it)
         self.wide_teams = -1                    # what set_wide_teams() last set
@@ -355,71 +465,55 @@ class Context:
             err.code = int(rc)                                   # the ROMAN_E_* code
             raise err
 
+    def _workspace_call(self, fn, *args):
+        """A batch entry that takes a solver workspace or stages in workspace 0: the stepwise problem is gone (see __init__) -> rc."""
+        self._generation += 1
+        return getattr(self._lib, fn)(self._h, *args)
+
+    def _enqueue(self, fn, *args):
+        """A pure enqueue that leaves the workspaces alone: the call and its check."""
+        self._check(getattr(self._lib, fn)(self._h, *args), fn)
+
+    def _finish(self, rc, what, result):
+        """The end of a host-result call of the align family: `result()` — and on ROMAN_E_INTERNAL, where the library copied the
+        outputs back and its message says which problems have none, the same result on the error's `.result`."""
+        if rc == _abi.ROMAN_E_INTERNAL:
+            msg = self._lib.roman_last_error(self._h)
+            err = RomanHipError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
+            err.result = result()
+            raise err
+        self._check(rc, what)
+        return result()
+
     # ------------------------------------------------------------------ batched hot path
     def align_batch(self, params, feats, off1, n1, off2, n2, assoc=None, assoc_off=None, u0=None,
                     kmax=None):
         """Host-pointer batch call (roman_align_batch).  feats: (n_objects, F) float64."""
-        feats = _f64(feats)
-        if feats.ndim != 2:
-            raise ValueError("feats must be (n_objects, F)")
-        n_obj, F = feats.shape
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        B = int(n1.shape[0])
-        if assoc is not None:
-            assoc = np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2)
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        if u0 is not None:
-            u0 = _f64(u0)
+        feats, n_obj, F = _pool(feats)
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        assoc, assoc_off = _assoc_list(assoc, assoc_off)
+        u0 = None if u0 is None else _f64(u0)
         if kmax is None:
-            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
-        dim = params.point_dim
-        a_out = np.zeros((B, kmax, 2), dtype=np.int32)
-        n_out = np.zeros(B, dtype=np.int32)
-        T = np.zeros((B, 16), dtype=np.float64)
-        status = np.zeros(B, dtype=np.int32)
-        stats = np.zeros(B, dtype=stats_dtype())
-        assert stats.dtype.itemsize == _abi.STATS_NBYTES
-        self._generation += 1
-        rc = self._lib.roman_align_batch(self._h, C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1),
-                                         _ptr(off2), _ptr(n2), F, _ptr(assoc), _ptr(assoc_off), _ptr(u0), kmax,
-                                         _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats))
-        s = dim + 1
-        if rc == _abi.ROMAN_E_INTERNAL:                          # outputs were copied: the error says which problems have no result
-            msg = self._lib.roman_last_error(self._h)
-            err = RomanHipError(f"roman_align_batch failed ({rc}): {msg.decode() if msg else ''}")
-            err.result = BatchResult([a_out[b, :n_out[b]].copy() for b in range(B)], T[:, :s * s].reshape(B, s, s).copy(), status, stats)
-            raise err
-        self._check(rc, "roman_align_batch")
-        Ts = T[:, :s * s].reshape(B, s, s).copy()
-        return BatchResult([a_out[b, :n_out[b]].copy() for b in range(B)], Ts, status, stats)
+            kmax = default_kmax(n1, n2)
+        a_out, n_out, T, status, stats = _solver_out(B, kmax)
+        rc = self._workspace_call("roman_align_batch", C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1),
+                                  _ptr(off2), _ptr(n2), F, _ptr(assoc), _ptr(assoc_off), _ptr(u0), kmax,
+                                  _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats))
+        return self._finish(rc, "roman_align_batch", lambda: BatchResult(*_solver_result(a_out, n_out, T, params.point_dim), status, stats))
 
     def align_batch_resident(self, params, feats_ptr, F, off1, n1, off2, n2, kmax=None, assoc_ptr=None, assoc_off=None, u0_ptr=None):
         """Inputs in HBM (device pointers as integers, e.g. torch.Tensor.data_ptr()), results on the host
         (roman_align_batch_resident): -> BatchResult.  Synchronous; the library chunks, pipelines and retries like align_batch(),
         and the whole result comes back with one copy."""
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        B = int(n1.shape[0])
-        if assoc_off is not None:
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        assoc_off = _assoc_off(assoc_off)
         if kmax is None:
-            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
-        a_out = np.empty((B, kmax, 2), dtype=np.int32); n_out = np.empty(B, dtype=np.int32)
-        T = np.empty((B, 16), dtype=np.float64); status = np.empty(B, dtype=np.int32); stats = np.empty(B, dtype=stats_dtype())
-        self._generation += 1
-        rc = self._lib.roman_align_batch_resident(self._h, C.byref(params), B, _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                                  int(F), _vp(assoc_ptr), _ptr(assoc_off), _vp(u0_ptr), int(kmax),
-                                                  _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats))
-        s = params.point_dim + 1
-        res = lambda: BatchResult([a_out[b, :n_out[b]].copy() for b in range(B)], T[:, :s * s].reshape(B, s, s).copy(), status, stats)
-        if rc == _abi.ROMAN_E_INTERNAL:                          # outputs were copied: the error says which problems have no result
-            msg = self._lib.roman_last_error(self._h)
-            err = RomanHipError(f"roman_align_batch_resident failed ({rc}): {msg.decode() if msg else ''}")
-            err.result = res()
-            raise err
-        self._check(rc, "roman_align_batch_resident")
-        return res()
+            kmax = default_kmax(n1, n2)
+        a_out, n_out, T, status, stats = _solver_out(B, kmax)
+        rc = self._workspace_call("roman_align_batch_resident", C.byref(params), B, _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                  int(F), _vp(assoc_ptr), _ptr(assoc_off), _vp(u0_ptr), int(kmax),
+                                  _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats))
+        return self._finish(rc, "roman_align_batch_resident", lambda: BatchResult(*_solver_result(a_out, n_out, T, params.point_dim), status, stats))
 
     def align_batch_dev(self, params, feats_ptr, F, off1, n1, off2, n2, kmax, assoc_out_ptr, n_assoc_out_ptr,
                         T_out_ptr, status_out_ptr, stats_out_ptr=None, assoc_ptr=None, assoc_off=None,
@@ -428,58 +522,38 @@ class Context:
         torch.Tensor.data_ptr()); metadata arrays are host NumPy arrays.  A pure enqueue: nothing is
         waited for or read back; problems that found no workspace come back with ROMAN_ST_WORKSPACE
         (run them again)."""
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        if assoc_off is not None:
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        self._generation += 1
-        rc = self._lib.roman_align_batch_dev(self._h, C.byref(params), int(n1.shape[0]), _vp(feats_ptr), _ptr(off1),
-                                             _ptr(n1), _ptr(off2), _ptr(n2), int(F), _vp(assoc_ptr), _ptr(assoc_off),
-                                             _vp(u0_ptr), int(kmax), _vp(assoc_out_ptr), _vp(n_assoc_out_ptr),
-                                             _vp(T_out_ptr), _vp(status_out_ptr), _vp(stats_out_ptr))
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        assoc_off = _assoc_off(assoc_off)
+        rc = self._workspace_call("roman_align_batch_dev", C.byref(params), B, _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                  int(F), _vp(assoc_ptr), _ptr(assoc_off), _vp(u0_ptr), int(kmax),
+                                  *_vps(assoc_out_ptr, n_assoc_out_ptr, T_out_ptr, status_out_ptr, stats_out_ptr))
         self._check(rc, "roman_align_batch_dev")
 
     # ------------------------------------------------------------------ multi-solution extraction
     def mno_batch(self, params, feats, off1, n1, off2, n2, num_solutions=2, assoc=None, assoc_off=None, kmax=None):
         """Host-pointer batched mno_clipper (roman_mno_batch): `num_solutions` plain-CLIPPER solves per problem with the
         selected block of M zeroed between them, all on the device.  feats: (n_objects, F) float64.  -> MnoResult."""
-        feats = _f64(feats)
-        if feats.ndim != 2:
-            raise ValueError("feats must be (n_objects, F)")
-        n_obj, F = feats.shape
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        B, K = int(n1.shape[0]), int(num_solutions)
-        if assoc is not None:
-            assoc = np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2)
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        feats, n_obj, F = _pool(feats)
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        K = int(num_solutions)
+        assoc, assoc_off = _assoc_list(assoc, assoc_off)
         if kmax is None:
-            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
-        Kc = max(K, 0)
-        a_out = np.zeros((B, Kc, kmax, 2), dtype=np.int32)
-        sol = np.zeros((B, Kc), dtype=mno_solution_dtype())
-        stats = np.zeros((B, Kc), dtype=stats_dtype())
-        assert sol.dtype.itemsize == _abi.MNO_SOLUTION_NBYTES
-        self._generation += 1
-        rc = self._lib.roman_mno_batch(self._h, C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
-                                       _ptr(assoc), _ptr(assoc_off), K, int(kmax), _ptr(a_out), _ptr(sol), _ptr(stats))
+            kmax = default_kmax(n1, n2)
+        a_out, sol, stats = _mno_out(B, max(K, 0), kmax)
+        rc = self._workspace_call("roman_mno_batch", C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
+                                  _ptr(assoc), _ptr(assoc_off), K, int(kmax), _ptr(a_out), _ptr(sol), _ptr(stats))
         self._check(rc, "roman_mno_batch")
-        s = params.point_dim + 1
-        return MnoResult([[a_out[b, k, :sol["n_assoc"][b, k]].copy() for k in range(K)] for b in range(B)],
-                         sol["score"].copy(), sol["T"][:, :, :s * s].reshape(B, K, s, s).copy(), sol["status"].copy(), stats)
+        return MnoResult(*_mno_result(a_out, sol, K, params.point_dim), stats)
 
     def mno_batch_dev(self, params, feats_ptr, F, off1, n1, off2, n2, num_solutions, kmax, assoc_out_ptr, sol_out_ptr,
                       stats_out_ptr=None, assoc_ptr=None, assoc_off=None):
         """Device-pointer batched mno_clipper (roman_mno_batch_dev): pointers are integers, metadata arrays host NumPy arrays.
         A pure enqueue; skipped problems carry ROMAN_ST_WORKSPACE on every solution (issue them again)."""
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        if assoc_off is not None:
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        self._generation += 1
-        rc = self._lib.roman_mno_batch_dev(self._h, C.byref(params), int(n1.shape[0]), _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                           int(F), _vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax), _vp(assoc_out_ptr),
-                                           _vp(sol_out_ptr), _vp(stats_out_ptr))
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        assoc_off = _assoc_off(assoc_off)
+        rc = self._workspace_call("roman_mno_batch_dev", C.byref(params), B, _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                  int(F), _vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax),
+                                  *_vps(assoc_out_ptr, sol_out_ptr, stats_out_ptr))
         self._check(rc, "roman_mno_batch_dev")
 
     def mno_lc_tail_dev(self, lc_params, B, K, sol_ptr, records_ptr, best_ptr, accepted_idx_ptr, n_accepted_ptr, accepted_best_idx_ptr,
@@ -487,10 +561,9 @@ class Context:
         """The tail over K hypotheses per problem on its own (roman_mno_lc_tail_dev): sol_ptr is roman_mno_solution_t[B][K] in HBM,
         the per-problem inputs are shared by a problem's hypotheses; every pointer a device address (an integer).  A pure enqueue
         on the context's stream."""
-        rc = self._lib.roman_mno_lc_tail_dev(self._h, C.byref(lc_params), int(B), int(K), _vp(sol_ptr), _vp(T_ref_ptr), _vp(enable_ptr),
-                                             _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(best_ptr),
-                                             _vp(accepted_idx_ptr), _vp(n_accepted_ptr), _vp(accepted_best_idx_ptr), _vp(n_accepted_best_ptr))
-        self._check(rc, "roman_mno_lc_tail_dev")
+        self._enqueue("roman_mno_lc_tail_dev", C.byref(lc_params), int(B), int(K),
+                      *_vps(sol_ptr, T_ref_ptr, enable_ptr, FL_ptr, iL_ptr, FR_ptr, iR_ptr, records_ptr, best_ptr,
+                            accepted_idx_ptr, n_accepted_ptr, accepted_best_idx_ptr, n_accepted_best_ptr))
 
     def mno_lc_batch_dev(self, params, feats_ptr, F, off1, n1, off2, n2, num_solutions, kmax, assoc_out_ptr, sol_out_ptr, lc_params,
                          records_ptr, best_ptr, accepted_idx_ptr, n_accepted_ptr, accepted_best_idx_ptr, n_accepted_best_ptr,
@@ -498,54 +571,34 @@ class Context:
                          FR_ptr=None, iR_ptr=None):
         """mno_batch_dev with the hypothesis tail enqueued behind its rounds on the same stream (roman_mno_lc_batch_dev): a pure
         enqueue, complete after sync()."""
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        if assoc_off is not None:
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        self._generation += 1
-        rc = self._lib.roman_mno_lc_batch_dev(self._h, C.byref(params), int(n1.shape[0]), _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                              int(F), _vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax), _vp(assoc_out_ptr),
-                                              _vp(sol_out_ptr), _vp(stats_out_ptr), C.byref(lc_params), _vp(T_ref_ptr), _vp(enable_ptr),
-                                              _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(best_ptr),
-                                              _vp(accepted_idx_ptr), _vp(n_accepted_ptr), _vp(accepted_best_idx_ptr), _vp(n_accepted_best_ptr))
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        assoc_off = _assoc_off(assoc_off)
+        rc = self._workspace_call("roman_mno_lc_batch_dev", C.byref(params), B, _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                  int(F), _vp(assoc_ptr), _ptr(assoc_off), int(num_solutions), int(kmax),
+                                  *_vps(assoc_out_ptr, sol_out_ptr, stats_out_ptr), C.byref(lc_params),
+                                  *_vps(T_ref_ptr, enable_ptr, FL_ptr, iL_ptr, FR_ptr, iR_ptr, records_ptr, best_ptr,
+                                        accepted_idx_ptr, n_accepted_ptr, accepted_best_idx_ptr, n_accepted_best_ptr))
         self._check(rc, "roman_mno_lc_batch_dev")
 
     def mno_lc_batch(self, params, feats, off1, n1, off2, n2, lc, num_solutions=2, assoc=None, assoc_off=None, kmax=None):
         """Host-pointer batched mno_clipper with the hypothesis tail behind it (roman_mno_lc_batch): `lc` is an LcInputs whose
         per-problem arrays have B entries.  -> MnoLoopClosureResult."""
-        feats = _f64(feats)
-        if feats.ndim != 2:
-            raise ValueError("feats must be (n_objects, F)")
-        n_obj, F = feats.shape
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        B, K = int(n1.shape[0]), int(num_solutions)
-        if assoc is not None:
-            assoc = np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2)
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
+        feats, n_obj, F = _pool(feats)
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        K = int(num_solutions)
+        assoc, assoc_off = _assoc_list(assoc, assoc_off)
         if kmax is None:
-            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
-        Kc = max(K, 0)
-        a_out = np.zeros((B, Kc, kmax, 2), dtype=np.int32)
-        sol = np.zeros((B, Kc), dtype=mno_solution_dtype())
-        stats = np.zeros((B, Kc), dtype=stats_dtype())
-        records = np.zeros((B, Kc), dtype=lc_record_dtype()); best = np.full(max(B, 1), -1, dtype=np.int32)
-        idx = np.zeros(max(B * Kc, 1), dtype=np.int32); cnt = np.zeros(1, dtype=np.int32)
-        bidx = np.zeros(max(B, 1), dtype=np.int32); bcnt = np.zeros(1, dtype=np.int32)
-        lp = lc.params()
-        T_ref, enable, FL, iL, FR, iR = lc.arrays(B)
-        self._generation += 1
-        rc = self._lib.roman_mno_lc_batch(self._h, C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
-                                          _ptr(assoc), _ptr(assoc_off), K, int(kmax), _ptr(a_out), _ptr(sol), _ptr(stats),
-                                          C.byref(lp), _ptr(T_ref), _ptr(enable), _ptr(FL), 0 if FL is None else FL.shape[0], _ptr(iL),
-                                          _ptr(FR), 0 if FR is None else FR.shape[0], _ptr(iR), _ptr(records), _ptr(best), _ptr(idx), _ptr(cnt),
-                                          _ptr(bidx), _ptr(bcnt))
+            kmax = default_kmax(n1, n2)
+        a_out, sol, stats = _mno_out(B, max(K, 0), kmax)
+        records, idx, cnt = _tail_out(B, max(K, 0))
+        best, bidx, bcnt = _mno_best_out(B)
+        lp, lc_arrays = lc.params(), lc.arrays(B)
+        rc = self._workspace_call("roman_mno_lc_batch", C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
+                                  _ptr(assoc), _ptr(assoc_off), K, int(kmax), _ptr(a_out), _ptr(sol), _ptr(stats),
+                                  *_lc_host_args(lp, lc_arrays), _ptr(records), _ptr(best), _ptr(idx), _ptr(cnt), _ptr(bidx), _ptr(bcnt))
         self._check(rc, "roman_mno_lc_batch")
-        s = params.point_dim + 1
-        rows = np.minimum(sol["n_assoc"], kmax)
-        return MnoLoopClosureResult([[a_out[b, k, :rows[b, k]].copy() for k in range(K)] for b in range(B)],
-                                    sol["score"].copy(), sol["T"][:, :, :s * s].reshape(B, K, s, s).copy(), sol["status"].copy(), stats,
-                                    sol["n_assoc"].copy(), records, best[:B].copy(), idx[:int(cnt[0])].copy(), bidx[:int(bcnt[0])].copy())
+        return MnoLoopClosureResult(*_mno_result(a_out, sol, K, params.point_dim), stats, sol["n_assoc"].copy(), records, best[:B].copy(),
+                                    idx[:int(cnt[0])].copy(), bidx[:int(bcnt[0])].copy())
 
     # ------------------------------------------------------------------ RANSAC registration
     def ransac_batch(self, rparams, pts, off1, n1, off2, n2, kmax=None, counts=None):
@@ -555,21 +608,14 @@ class Context:
         pts = _f64(pts)
         if pts.ndim != 2 or pts.shape[1] != 3:
             raise ValueError("pts must be (n_objects, 3)")
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        B = int(n1.shape[0])
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
         if kmax is None:
-            kmax = int(max(1, np.max(n1.astype(np.int64) * n2))) if B else 1
-        if counts is True:
-            counts = np.full((B, max(int(rparams.max_iteration), 0)), -2, dtype=np.int32)
-        elif counts is not None:
-            if counts.dtype != np.int32 or not counts.flags.c_contiguous or counts.shape != (B, int(rparams.max_iteration)):
-                raise ValueError("counts must be a C-contiguous (B, max_iteration) int32 array")
+            kmax = ransac_kmax(n1, n2)
+        counts = _ransac_counts(counts, B, rparams)
         a_out = np.zeros((B, kmax, 2), dtype=np.int32)
         rec = np.zeros(B, dtype=ransac_record_dtype())
-        self._generation += 1
-        rc = self._lib.roman_ransac_batch(self._h, C.byref(rparams), B, _ptr(pts), pts.shape[0], _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                          int(kmax), _ptr(a_out), _ptr(rec), _ptr(counts))
+        rc = self._workspace_call("roman_ransac_batch", C.byref(rparams), B, _ptr(pts), pts.shape[0], _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                  int(kmax), _ptr(a_out), _ptr(rec), _ptr(counts))
         self._check(rc, "roman_ransac_batch")
         rows = np.minimum(rec["n_assoc"], kmax)
         return RansacResult([a_out[b, :rows[b]].copy() for b in range(B)], rec["T"].reshape(B, 4, 4).copy(), rec["status"].copy(), rec, counts)
@@ -577,11 +623,9 @@ class Context:
     def ransac_batch_dev(self, rparams, pts_ptr, off1, n1, off2, n2, kmax, assoc_out_ptr, rec_out_ptr, counts_out_ptr=None):
         """Device-pointer batched RANSAC registration (roman_ransac_batch_dev): pointers are integers, metadata arrays host
         NumPy arrays.  A pure enqueue on the context's stream; complete after sync()."""
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        rc = self._lib.roman_ransac_batch_dev(self._h, C.byref(rparams), int(n1.shape[0]), _vp(pts_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                              int(kmax), _vp(assoc_out_ptr), _vp(rec_out_ptr), _vp(counts_out_ptr))
-        self._check(rc, "roman_ransac_batch_dev")
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        self._enqueue("roman_ransac_batch_dev", C.byref(rparams), B, _vp(pts_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                      int(kmax), *_vps(assoc_out_ptr, rec_out_ptr, counts_out_ptr))
 
     def ransac_lc_batch(self, rparams, rows, off1, n1, off2, n2, lc, kmax=None, counts=None):
         """Host-pointer RANSAC loop closures (roman_ransac_lc_batch): ransac_batch() over `rows` — (n_objects, F)
@@ -592,30 +636,19 @@ class Context:
         if rows.ndim != 2 or rows.shape[1] < 3:
             raise ValueError("rows must be (n_objects, F) with F >= 3")
         n_obj, F = rows.shape
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        B = int(n1.shape[0])
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
         if kmax is None:
-            kmax = int(max(1, np.max(n1.astype(np.int64) * n2))) if B else 1
-        if counts is True:
-            counts = np.full((B, max(int(rparams.max_iteration), 0)), -2, dtype=np.int32)
-        elif counts is not None:
-            if counts.dtype != np.int32 or not counts.flags.c_contiguous or counts.shape != (B, int(rparams.max_iteration)):
-                raise ValueError("counts must be a C-contiguous (B, max_iteration) int32 array")
-        a_out = np.zeros((B, kmax, 2), dtype=np.int32); rec = np.zeros(B, dtype=ransac_record_dtype())
-        T = np.zeros((B, 16), dtype=np.float64); n_out = np.zeros(B, dtype=np.int32); status = np.zeros(B, dtype=np.int32)
-        records = np.zeros(B, dtype=lc_record_dtype()); idx = np.zeros(max(B, 1), dtype=np.int32); cnt = np.zeros(1, dtype=np.int32)
-        lp = lc.params()
-        T_ref, enable, FL, iL, FR, iR = lc.arrays(B)
-        self._generation += 1
-        rc = self._lib.roman_ransac_lc_batch(self._h, C.byref(rparams), B, _ptr(rows), n_obj, F, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), int(kmax),
-                                             _ptr(a_out), _ptr(rec), _ptr(counts), _ptr(T), _ptr(n_out), _ptr(status),
-                                             C.byref(lp), _ptr(T_ref), _ptr(enable), _ptr(FL), 0 if FL is None else FL.shape[0], _ptr(iL),
-                                             _ptr(FR), 0 if FR is None else FR.shape[0], _ptr(iR), _ptr(records), _ptr(idx), _ptr(cnt))
+            kmax = ransac_kmax(n1, n2)
+        counts = _ransac_counts(counts, B, rparams)
+        a_out, n_out, T, status, stats = _solver_out(B, kmax)    # (no statistics come back: `stats` stays zeros)
+        rec = np.zeros(B, dtype=ransac_record_dtype())
+        records, idx, cnt = _tail_out(B)
+        lp, lc_arrays = lc.params(), lc.arrays(B)
+        rc = self._workspace_call("roman_ransac_lc_batch", C.byref(rparams), B, _ptr(rows), n_obj, F, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                  int(kmax), _ptr(a_out), _ptr(rec), _ptr(counts), _ptr(T), _ptr(n_out), _ptr(status),
+                                  *_lc_host_args(lp, lc_arrays), _ptr(records), _ptr(idx), _ptr(cnt))
         self._check(rc, "roman_ransac_lc_batch")
-        k = np.minimum(n_out, kmax)
-        return LoopClosureResult([a_out[b, :k[b]].copy() for b in range(B)], T.reshape(B, 4, 4).copy(), status, np.zeros(B, dtype=stats_dtype()),
-                                 records, idx[:int(cnt[0])].copy(), ransac_records=rec)
+        return LoopClosureResult(*_solver_result(a_out, n_out, T, 3), status, stats, records, idx[:int(cnt[0])].copy(), ransac_records=rec)
 
     def ransac_lc_batch_dev(self, rparams, rows_ptr, F, off1, n1, off2, n2, kmax, assoc_out_ptr, rec_out_ptr, T_out_ptr=None, n_assoc_out_ptr=None,
                             status_out_ptr=None, lc_params=None, records_ptr=None, accepted_idx_ptr=None, n_accepted_ptr=None, counts_out_ptr=None,
@@ -623,13 +656,11 @@ class Context:
         """Device-pointer RANSAC loop closures (roman_ransac_lc_batch_dev): k_ransac over rows of F doubles with the split outputs
         T / n_assoc / status, and — with lc_params (a RomanLcParams; None: no tail) — the tail behind it on the context's stream.
         Pointers are integers, metadata arrays host NumPy arrays.  A pure enqueue; complete after sync()."""
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        rc = self._lib.roman_ransac_lc_batch_dev(self._h, C.byref(rparams), int(n1.shape[0]), _vp(rows_ptr), int(F), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                                 int(kmax), _vp(assoc_out_ptr), _vp(rec_out_ptr), _vp(counts_out_ptr), _vp(T_out_ptr), _vp(n_assoc_out_ptr),
-                                                 _vp(status_out_ptr), None if lc_params is None else C.byref(lc_params), _vp(T_ref_ptr), _vp(enable_ptr),
-                                                 _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(accepted_idx_ptr), _vp(n_accepted_ptr))
-        self._check(rc, "roman_ransac_lc_batch_dev")
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        self._enqueue("roman_ransac_lc_batch_dev", C.byref(rparams), B, _vp(rows_ptr), int(F), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                      int(kmax), *_vps(assoc_out_ptr, rec_out_ptr, counts_out_ptr, T_out_ptr, n_assoc_out_ptr, status_out_ptr),
+                      None if lc_params is None else C.byref(lc_params),
+                      *_vps(T_ref_ptr, enable_ptr, FL_ptr, iL_ptr, FR_ptr, iR_ptr, records_ptr, accepted_idx_ptr, n_accepted_ptr))
 
     # ------------------------------------------------------------------ submaps from a whole map
     @staticmethod
@@ -1046,128 +1077,79 @@ class Context:
     def align_lc_batch(self, params, feats, off1, n1, off2, n2, lc, assoc=None, assoc_off=None, u0=None, kmax=None):
         """Host-pointer batch call with the loop-closure tail behind it (roman_align_lc_batch): `lc` is an LcInputs.
         -> LoopClosureResult; one read-back brings outputs, records and the accepted list."""
-        feats = _f64(feats)
-        if feats.ndim != 2:
-            raise ValueError("feats must be (n_objects, F)")
-        n_obj, F = feats.shape
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        B = int(n1.shape[0])
-        if assoc is not None:
-            assoc = np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2)
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        if u0 is not None:
-            u0 = _f64(u0)
+        feats, n_obj, F = _pool(feats)
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        assoc, assoc_off = _assoc_list(assoc, assoc_off)
+        u0 = None if u0 is None else _f64(u0)
         if kmax is None:
-            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
-        a_out = np.zeros((B, kmax, 2), dtype=np.int32); n_out = np.zeros(B, dtype=np.int32)
-        T = np.zeros((B, 16), dtype=np.float64); status = np.zeros(B, dtype=np.int32); stats = np.zeros(B, dtype=stats_dtype())
-        records = np.zeros(B, dtype=lc_record_dtype()); idx = np.zeros(max(B, 1), dtype=np.int32); cnt = np.zeros(1, dtype=np.int32)
-        assert records.dtype.itemsize == _abi.LC_RECORD_NBYTES
-        lp = lc.params()
-        T_ref, enable, FL, iL, FR, iR = lc.arrays(B)
-        self._generation += 1
-        rc = self._lib.roman_align_lc_batch(self._h, C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
-                                            _ptr(assoc), _ptr(assoc_off), _ptr(u0), kmax, _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats),
-                                            C.byref(lp), _ptr(T_ref), _ptr(enable), _ptr(FL), 0 if FL is None else FL.shape[0], _ptr(iL),
-                                            _ptr(FR), 0 if FR is None else FR.shape[0], _ptr(iR), _ptr(records), _ptr(idx), _ptr(cnt))
-        s = params.point_dim + 1
-        res = lambda: LoopClosureResult([a_out[b, :n_out[b]].copy() for b in range(B)], T[:, :s * s].reshape(B, s, s).copy(), status, stats,
-                                        records, idx[:int(cnt[0])].copy())
-        if rc == _abi.ROMAN_E_INTERNAL:                          # outputs were copied: the error says which problems have no result
-            msg = self._lib.roman_last_error(self._h)
-            err = RomanHipError(f"roman_align_lc_batch failed ({rc}): {msg.decode() if msg else ''}")
-            err.result = res()
-            raise err
-        self._check(rc, "roman_align_lc_batch")
-        return res()
+            kmax = default_kmax(n1, n2)
+        a_out, n_out, T, status, stats = _solver_out(B, kmax)
+        records, idx, cnt = _tail_out(B)
+        lp, lc_arrays = lc.params(), lc.arrays(B)
+        rc = self._workspace_call("roman_align_lc_batch", C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
+                                  _ptr(assoc), _ptr(assoc_off), _ptr(u0), kmax, _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats),
+                                  *_lc_host_args(lp, lc_arrays), _ptr(records), _ptr(idx), _ptr(cnt))
+        return self._finish(rc, "roman_align_lc_batch", lambda: LoopClosureResult(*_solver_result(a_out, n_out, T, params.point_dim), status, stats,
+                                                                                  records, idx[:int(cnt[0])].copy()))
 
     def align_lc_batch_ids(self, params, feats, ids, off1, n1, off2, n2, lc, assoc=None, assoc_off=None, u0=None, kmax=None, want_keep=True):
         """align_lc_batch() for self loop closures (roman_align_lc_batch_ids): `ids` holds one int64 per row of `feats`; every
         problem first loses the objects whose id occurs on both of its sides — on the device, over the pool that holds every
         submap once.  -> LoopClosureResult with n1_kept, n2_kept (and keep, the kept local indices, unless want_keep is False);
         associations index the reduced maps.  `assoc` must stay None (the library refuses explicit lists together with ids)."""
-        feats = _f64(feats)
-        if feats.ndim != 2:
-            raise ValueError("feats must be (n_objects, F)")
-        n_obj, F = feats.shape
+        feats, n_obj, F = _pool(feats)
         ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
         if ids.shape[0] != n_obj:
             raise ValueError("ids must hold one entry per row of feats")
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        B = int(n1.shape[0])
-        if assoc is not None:
-            assoc = np.ascontiguousarray(assoc, dtype=np.int32).reshape(-1, 2)
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        if u0 is not None:
-            u0 = _f64(u0)
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        assoc, assoc_off = _assoc_list(assoc, assoc_off)
+        u0 = None if u0 is None else _f64(u0)
         if kmax is None:
-            kmax = int(max(1, np.max(np.minimum(n1, n2)))) if B else 1
-        a_out = np.zeros((B, kmax, 2), dtype=np.int32); n_out = np.zeros(B, dtype=np.int32)
-        T = np.zeros((B, 16), dtype=np.float64); status = np.zeros(B, dtype=np.int32); stats = np.zeros(B, dtype=stats_dtype())
-        records = np.zeros(B, dtype=lc_record_dtype()); idx = np.zeros(max(B, 1), dtype=np.int32); cnt = np.zeros(1, dtype=np.int32)
+            kmax = default_kmax(n1, n2)
+        a_out, n_out, T, status, stats = _solver_out(B, kmax)
+        records, idx, cnt = _tail_out(B)
         k1 = np.zeros(B, dtype=np.int32); k2 = np.zeros(B, dtype=np.int32)
         keep = np.full(int(n1.sum(dtype=np.int64) + n2.sum(dtype=np.int64)), -1, dtype=np.int32) if want_keep else None
-        lp = lc.params()
-        T_ref, enable, FL, iL, FR, iR = lc.arrays(B)
-        self._generation += 1
-        rc = self._lib.roman_align_lc_batch_ids(self._h, C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
-                                                _ptr(assoc), _ptr(assoc_off), _ptr(u0), kmax, _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats),
-                                                C.byref(lp), _ptr(T_ref), _ptr(enable), _ptr(FL), 0 if FL is None else FL.shape[0], _ptr(iL),
-                                                _ptr(FR), 0 if FR is None else FR.shape[0], _ptr(iR), _ptr(records), _ptr(idx), _ptr(cnt),
-                                                _ptr(ids), _ptr(k1), _ptr(k2), _ptr(keep))
-        s = params.point_dim + 1
-        res = lambda: LoopClosureResult([a_out[b, :n_out[b]].copy() for b in range(B)], T[:, :s * s].reshape(B, s, s).copy(), status, stats,
-                                        records, idx[:int(cnt[0])].copy(), k1, k2, keep)
-        if rc == _abi.ROMAN_E_INTERNAL:                          # outputs were copied: the error says which problems have no result
-            msg = self._lib.roman_last_error(self._h)
-            err = RomanHipError(f"roman_align_lc_batch_ids failed ({rc}): {msg.decode() if msg else ''}")
-            err.result = res()
-            raise err
-        self._check(rc, "roman_align_lc_batch_ids")
-        return res()
+        lp, lc_arrays = lc.params(), lc.arrays(B)
+        rc = self._workspace_call("roman_align_lc_batch_ids", C.byref(params), B, _ptr(feats), n_obj, _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), F,
+                                  _ptr(assoc), _ptr(assoc_off), _ptr(u0), kmax, _ptr(a_out), _ptr(n_out), _ptr(T), _ptr(status), _ptr(stats),
+                                  *_lc_host_args(lp, lc_arrays), _ptr(records), _ptr(idx), _ptr(cnt), _ptr(ids), _ptr(k1), _ptr(k2), _ptr(keep))
+        return self._finish(rc, "roman_align_lc_batch_ids", lambda: LoopClosureResult(*_solver_result(a_out, n_out, T, params.point_dim), status, stats,
+                                                                                      records, idx[:int(cnt[0])].copy(), k1, k2, keep))
 
     def shared_ids_dev(self, B, ids_ptr, off1, n1, off2, n2, keep_ptr, kept_ptr):
         """The mark step of the shared-segment removal on its own (roman_shared_ids_dev): ids, keep and kept are device addresses
         (integers), the offsets and sizes host arrays.  A pure enqueue on the context's stream; complete after sync()."""
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        rc = self._lib.roman_shared_ids_dev(self._h, int(B), _vp(ids_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), _vp(keep_ptr), _vp(kept_ptr))
-        self._check(rc, "roman_shared_ids_dev")
+        off1, n1, off2, n2, _ = _problems(off1, n1, off2, n2)
+        self._enqueue("roman_shared_ids_dev", int(B), _vp(ids_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2), _vp(keep_ptr), _vp(kept_ptr))
 
     def shared_reduce_dev(self, B, F, feats_ptr, region_row0, ids_ptr, off1, n1, off2, n2, keep_ptr, kept_ptr):
         """Mark and gather of the shared-segment removal in one launch (roman_shared_reduce_dev): feats (the pool's rows, then a
         gather region of sum(n1 + n2) rows from row region_row0 on), ids, keep and kept are device addresses (integers), the
         offsets and sizes host arrays.  A pure enqueue on the context's stream; complete after sync()."""
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        rc = self._lib.roman_shared_reduce_dev(self._h, int(B), int(F), _vp(feats_ptr), int(region_row0), _vp(ids_ptr), _ptr(off1), _ptr(n1),
-                                               _ptr(off2), _ptr(n2), _vp(keep_ptr), _vp(kept_ptr))
-        self._check(rc, "roman_shared_reduce_dev")
+        off1, n1, off2, n2, _ = _problems(off1, n1, off2, n2)
+        self._enqueue("roman_shared_reduce_dev", int(B), int(F), _vp(feats_ptr), int(region_row0), _vp(ids_ptr), _ptr(off1), _ptr(n1),
+                      _ptr(off2), _ptr(n2), _vp(keep_ptr), _vp(kept_ptr))
 
     def lc_tail_dev(self, lc_params, B, T_ptr, n_assoc_ptr, status_ptr, records_ptr, accepted_idx_ptr, n_accepted_ptr,
                     T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None, FR_ptr=None, iR_ptr=None):
         """The tail on its own over batch outputs in HBM (roman_lc_tail_dev): every pointer a device address (an integer, e.g.
         torch.Tensor.data_ptr()); lc_params a RomanLcParams (LcInputs.params()).  A pure enqueue on the context's stream."""
-        rc = self._lib.roman_lc_tail_dev(self._h, C.byref(lc_params), int(B), _vp(T_ptr), _vp(n_assoc_ptr), _vp(status_ptr), _vp(T_ref_ptr), _vp(enable_ptr),
-                                         _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(accepted_idx_ptr), _vp(n_accepted_ptr))
-        self._check(rc, "roman_lc_tail_dev")
+        self._enqueue("roman_lc_tail_dev", C.byref(lc_params), int(B),
+                      *_vps(T_ptr, n_assoc_ptr, status_ptr, T_ref_ptr, enable_ptr, FL_ptr, iL_ptr, FR_ptr, iR_ptr,
+                            records_ptr, accepted_idx_ptr, n_accepted_ptr))
 
     def align_lc_batch_dev(self, params, feats_ptr, F, off1, n1, off2, n2, kmax, assoc_out_ptr, n_assoc_out_ptr, T_out_ptr, status_out_ptr,
                            lc_params, records_ptr, accepted_idx_ptr, n_accepted_ptr, stats_out_ptr=None, assoc_ptr=None, assoc_off=None, u0_ptr=None,
                            T_ref_ptr=None, enable_ptr=None, FL_ptr=None, iL_ptr=None, FR_ptr=None, iR_ptr=None):
         """align_batch_dev with the tail enqueued behind the solver on the same stream (roman_align_lc_batch_dev): a pure enqueue,
         complete after sync()."""
-        off1 = np.ascontiguousarray(off1, dtype=np.int64); off2 = np.ascontiguousarray(off2, dtype=np.int64)
-        n1 = np.ascontiguousarray(n1, dtype=np.int32); n2 = np.ascontiguousarray(n2, dtype=np.int32)
-        if assoc_off is not None:
-            assoc_off = np.ascontiguousarray(assoc_off, dtype=np.int64)
-        self._generation += 1
-        rc = self._lib.roman_align_lc_batch_dev(self._h, C.byref(params), int(n1.shape[0]), _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
-                                                int(F), _vp(assoc_ptr), _ptr(assoc_off), _vp(u0_ptr), int(kmax), _vp(assoc_out_ptr), _vp(n_assoc_out_ptr),
-                                                _vp(T_out_ptr), _vp(status_out_ptr), _vp(stats_out_ptr), C.byref(lc_params), _vp(T_ref_ptr), _vp(enable_ptr),
-                                                _vp(FL_ptr), _vp(iL_ptr), _vp(FR_ptr), _vp(iR_ptr), _vp(records_ptr), _vp(accepted_idx_ptr), _vp(n_accepted_ptr))
+        off1, n1, off2, n2, B = _problems(off1, n1, off2, n2)
+        assoc_off = _assoc_off(assoc_off)
+        rc = self._workspace_call("roman_align_lc_batch_dev", C.byref(params), B, _vp(feats_ptr), _ptr(off1), _ptr(n1), _ptr(off2), _ptr(n2),
+                                  int(F), _vp(assoc_ptr), _ptr(assoc_off), _vp(u0_ptr), int(kmax),
+                                  *_vps(assoc_out_ptr, n_assoc_out_ptr, T_out_ptr, status_out_ptr, stats_out_ptr), C.byref(lc_params),
+                                  *_vps(T_ref_ptr, enable_ptr, FL_ptr, iL_ptr, FR_ptr, iR_ptr, records_ptr, accepted_idx_ptr, n_accepted_ptr))
         self._check(rc, "roman_align_lc_batch_dev")
 
     # ------------------------------------------------------------------ stepwise (clipperpy shim)
