@@ -863,6 +863,41 @@ ROMAN_API int roman_submaps(roman_ctx_t* ctx, const roman_submap_params_t* spara
                             double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status,
                             int32_t desc_dim, double* desc_out);
 
+/*
+ * roman_session_submaps_dev: roman_submaps_dev [REF roman/map/map.py:297-346] for the R maps of a multi-robot
+ * session in ONE launch sequence, straight into the one pool the session's batch reads.  Bulk pointers DEVICE; the offset tables and
+ * the descriptors HOST (the library stages what the device needs).  A PURE ENQUEUE on the context's stream.  One parameter block
+ * serves every map (one `cap`); radius mode only, use_radius = 0 and max_size <= 0 included.
+ *   R, seg_off int64[R+1] HOST: map r owns the segment rows [seg_off[r], seg_off[r+1]) of seg_feats / seg_times / seg_ids, the R map
+ *              tables concatenated in map order (N_r = seg_off[r+1] - seg_off[r]); seg_off[0] = 0
+ *   sub_off    int32[R+1] HOST: map r owns the submaps [sub_off[r], sub_off[r+1]) (S_r of them); sub_off[0] = 0
+ *   descs      roman_submap_desc_t[sub_off[R]] HOST, the maps' centres in map order
+ *   pool, count, src, ids_out, status, desc_dim, desc_out   as for roman_submaps_dev, over all sub_off[R] submaps: submap
+ *              g = sub_off[r] + s owns the pool rows [g*cap, g*cap + count[g]); src holds MAP-LOCAL indices (0 .. N_r - 1)
+ * For every r the slice [sub_off[r], sub_off[r+1]) of count, status and desc_out and the slice [sub_off[r]*cap, sub_off[r+1]*cap) of
+ * pool, src and ids_out are BIT FOR BIT what roman_submaps_dev(ctx, sparams, N_r, F, <map r's tables>, S_r, <its descs>, ...) writes;
+ * rows beyond count[g] and the descriptor of an empty submap are not written.  R == 0, maps with N_r == 0 and maps with S_r == 0 are
+ * legal.  Candidates beyond the first 4096 of a submap go through a scratch the context owns: sum over r of S_r * max(N_r - 4096, 0)
+ * entries of 12 bytes, every submap's slice at an offset the host computes; allocated only when some N_r > 4096.
+ * Errors: those of roman_submaps_dev; R < 0, a NULL offset table with R > 0, seg_off[0] or sub_off[0] not 0, an offset table that
+ * decreases -> ROMAN_E_INVALID; sub_off[R] * cap beyond int32 (or a map of more than 2^31 - 1 rows) -> ROMAN_E_TOO_LARGE; a scratch
+ * allocation that fails -> ROMAN_E_NOMEM, nothing is enqueued and the context stays usable.  The arguments are judged before the
+ * context: with ctx NULL a refused call answers with its own code.
+ */
+ROMAN_API int roman_session_submaps_dev(roman_ctx_t* ctx, const roman_submap_params_t* sparams, int32_t R, int32_t F,
+                                        const int64_t* seg_off, const double* seg_feats, const double* seg_times, const int64_t* seg_ids,
+                                        const int32_t* sub_off, const roman_submap_desc_t* descs,
+                                        double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status,
+                                        int32_t desc_dim, double* desc_out);
+
+/* The same with HOST pointers everywhere.  Synchronous: copies in, runs roman_session_submaps_dev, brings count, src, ids_out,
+   status, desc_out and — pool != NULL — the pool back; what the device call leaves untouched comes back as it was. */
+ROMAN_API int roman_session_submaps(roman_ctx_t* ctx, const roman_submap_params_t* sparams, int32_t R, int32_t F,
+                                    const int64_t* seg_off, const double* seg_feats, const double* seg_times, const int64_t* seg_ids,
+                                    const int32_t* sub_off, const roman_submap_desc_t* descs,
+                                    double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status,
+                                    int32_t desc_dim, double* desc_out);
+
 /* ------------------------------------------------------------------------------------------- */
 /* frame descriptors of the submaps of a pool                                                  */
 /* ------------------------------------------------------------------------------------------- */

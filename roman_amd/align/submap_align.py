@@ -1098,6 +1098,24 @@ def submap_align_pools(sm_params, pools, sm_io: Optional[SubmapAlignIO] = None, 
     return out
 
 
+def _one_storage(torch, parts):
+    """The tensors `parts` as ONE tensor without a copy, where they allow it: each contiguous, all in the same storage, each
+    starting where the one in front of it ends (the pools build_session_pools leaves are such row ranges) -> a
+    view of that storage over all their rows, or None — a gap, another order, separately allocated tensors, a missing one —, and
+    the caller concatenates as before."""
+    if len(parts) < 2 or any(q is None or not q.is_contiguous() for q in parts):
+        return None
+    first = parts[0]
+    base, at, tail = first.untyped_storage().data_ptr(), first.data_ptr(), tuple(first.shape[1:])
+    for q in parts:
+        if q.untyped_storage().data_ptr() != base or q.data_ptr() != at or tuple(q.shape[1:]) != tail or q.dtype != first.dtype:
+            return None
+        at += q.numel() * q.element_size()
+    shape = (sum(int(q.shape[0]) for q in parts),) + tail
+    stride = tuple(int(np.prod(shape[k + 1:], dtype=np.int64)) for k in range(len(shape)))
+    return first.as_strided(shape, stride, first.storage_offset())
+
+
 def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[SubmapAlignIO] = None, registration=None,
                          gt_poses=None, num_solutions=None) -> Dict[Tuple[int, int], SubmapAlignResults]:
     """The robot-pair loop of the reference's driver [REF demo/demo.py:138-161] in ONE call: `pools` is a list of R
@@ -1114,6 +1132,11 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     synchronisation and one read-back; every TODO pair of every block is a problem of ONE batch over the concatenated pools
     (self blocks lose the segments both submaps hold through one roman_shared_reduce_dev over their problems); one
     issue_chunked, one join, one roman_lc_tail_dev with the frames tabled over all submaps of the session.
+
+    Pools that are consecutive row ranges of ONE storage, in list order — what build_session_pools leaves — are
+    read in place: the batch and the shared-segment removal run over a view of that storage, nothing is concatenated, and every
+    block is what it is over separately built pools.  Any other list (separately built pools, a gap, another order) is
+    concatenated as before (`_one_storage`).
 
     'stacked_frame_descriptors' (pools built with it): every live robot's frame descriptors go ONCE into the
     session's frame table and the mask rows of its non-empty submaps once into one block of words, whatever number of views the
@@ -1269,7 +1292,9 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
         """ONE pool for the session — every live robot's rows once, whatever the number of its views — and per GLOBAL submap index
         (the gate's, as sub_off orders them) its first row and its rows -> (pool, sm_row int64, sm_cnt int32)."""
         live = sorted({r for r, _ in lv})
-        pool = p[live[0]].pool if len(live) == 1 else torch.cat([p[r].pool for r in live], dim=0)
+        pool = _one_storage(torch, [p[r].pool for r in live])   # pools of ONE build (build_session_pools): the rows are there already
+        if pool is None:
+            pool = p[live[0]].pool if len(live) == 1 else torch.cat([p[r].pool for r in live], dim=0)
         row0 = dict(zip(live, np.concatenate([[0], np.cumsum([int(p[r].pool.shape[0]) for r in live])]).astype(np.int64).tolist()))
         return (pool, np.concatenate([row0[r] + p[r].offsets()[0] for r, _ in lv]).astype(np.int64),
                 np.concatenate([p[r].offsets()[1] for r, _ in lv]).astype(np.int32))
@@ -1328,7 +1353,9 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     of_self = np.concatenate([np.full(int(todo_off[b + 1] - todo_off[b]), r == s, dtype=bool) for b, (r, s) in enumerate(blocks)])
     sel = np.nonzero(of_self)[0]
     if len(sel):                                             # the problems of the self blocks lose the segments both submaps hold
-        ids_dev = torch.cat([p[r].ids_dev if p[r].ids_dev is not None else torch.zeros(int(p[r].pool.shape[0]), dtype=torch.int64, device=dev) for r in live])
+        ids_dev = _one_storage(torch, [p[r].ids_dev for r in live])
+        if ids_dev is None or int(ids_dev.shape[0]) != int(pool.shape[0]):
+            ids_dev = torch.cat([p[r].ids_dev if p[r].ids_dev is not None else torch.zeros(int(p[r].pool.shape[0]), dtype=torch.int64, device=dev) for r in live])
         pool, *prob = _drop_shared_over_pool(torch, ctx, pool, ids_dev, *prob, sel, wait_torch)
     batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), tuple(pool.shape)), prob[0].astype(np.int64), prob[1].astype(np.int32), prob[2].astype(np.int64),
                            prob[3].astype(np.int32), pair_index=gpairs)

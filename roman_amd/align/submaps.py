@@ -310,6 +310,26 @@ def submap_call_params(table: MapTable, params: SubmapParams, cap=None) -> _abi.
     return P
 
 
+def _descriptor_width(table, params, frames):
+    """What params.submap_descriptor asks of a pool over `table` -> (d: columns of the per-submap descriptor the build writes, 0: none;
+    framed: a frame-descriptor mode; mean_frames: its mean).  The refusals of build_submap_pool for the descriptor."""
+    d = 0
+    if params.submap_descriptor == 'mean_semantic':
+        if table.desc_dim <= 0:
+            raise ValueError("submap_descriptor 'mean_semantic' needs a registration with semantic descriptors")
+        d = table.desc_dim
+    elif params.submap_descriptor in FRAME_MODES:
+        if frames is None:
+            raise ValueError(f"submap_descriptor {params.submap_descriptor!r} needs the map's frames: pass frames=FrameTable.from_map(trajectory, times, descriptors)")
+    elif params.submap_descriptor is not None:
+        raise ValueError(f"unknown submap_descriptor {params.submap_descriptor!r}")
+    framed = params.submap_descriptor in FRAME_MODES
+    mean_frames = params.submap_descriptor == 'mean_frame_descriptor'
+    if mean_frames:
+        d = int(frames.desc.shape[1])
+    return d, framed, mean_frames
+
+
 def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, params, ctx=None, device=None, cap=None,
                       frames: Optional[FrameTable] = None, fill=None) -> SubmapPool:
     """The submaps of `table` around `centers` as a device-resident feature pool: ONE roman_submaps_dev call (membership, prune,
@@ -341,20 +361,7 @@ def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, par
     else:
         P = submap_call_params(table, params, cap)
     S, N, F = len(centers), len(table), int(table.feats.shape[1])
-    d = 0
-    if params.submap_descriptor == 'mean_semantic':
-        if table.desc_dim <= 0:
-            raise ValueError("submap_descriptor 'mean_semantic' needs a registration with semantic descriptors")
-        d = table.desc_dim
-    elif params.submap_descriptor in FRAME_MODES:
-        if frames is None:
-            raise ValueError(f"submap_descriptor {params.submap_descriptor!r} needs the map's frames: pass frames=FrameTable.from_map(trajectory, times, descriptors)")
-    elif params.submap_descriptor is not None:
-        raise ValueError(f"unknown submap_descriptor {params.submap_descriptor!r}")
-    framed = params.submap_descriptor in FRAME_MODES
-    mean_frames = params.submap_descriptor == 'mean_frame_descriptor'
-    if mean_frames:
-        d = int(frames.desc.shape[1])
+    d, framed, mean_frames = _descriptor_width(table, params, frames)
     Fo, rows = P.point_dim + F - 3, S * P.cap
     feats = torch.from_numpy(table.feats).to(dev); times = torch.from_numpy(table.times).to(dev); ids = torch.from_numpy(table.ids).to(dev)
     pool = torch.zeros((rows, Fo), dtype=torch.float64, device=dev)
@@ -402,3 +409,105 @@ def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, par
                       ids_out.cpu().numpy()[:rows].reshape(S, P.cap).copy(), status.cpu().numpy()[:S].copy(),
                       desc.cpu().numpy()[:S, :d].copy() if d else None, centers, table, desc_dev=desc[:S, :d] if d else None,
                       descriptor_mode=params.submap_descriptor, ids_dev=ids_out[:rows], **extra)
+
+
+def build_session_pools(registration, tables, centers, params, ctx=None, device=None, cap=None, frames=None, fill=None) -> List[SubmapPool]:
+    """The submap pools of ALL R robots of a session (one MapTable and one SubmapCenters each) from ONE roman_session_submaps_dev
+    call: the R tables go up once, concatenated in robot order; one launch sequence writes every robot's submaps
+    into ONE pool tensor — and one ids, count, src, status and descriptor tensor —; one synchronisation brings the small arrays
+    back.  Pool r is an ordinary SubmapPool whose `pool`, `ids_dev` and `desc_dev` are row-slice VIEWS of the session's tensors,
+    bit for bit what build_submap_pool(registration, tables[r], centers[r], params, cap=<the session's cap>) gives: grid_batch,
+    to_submaps and submap_align_pools read it unchanged, and submap_align_session over the list runs on the one allocation
+    without concatenating anything.
+
+    One `cap` serves the session: params.max_size, or `cap`, or the largest map's rows.  `frames`: one FrameTable per robot for the
+    frame-descriptor modes — roman_frame_select_dev per robot behind the session call, on the same stream, as in build_submap_pool.
+
+    Refused (ValueError, before anything makes a HIP context): `fill=` or params of the force_fill_submaps mode — that mode slices
+    on the host, build_submap_pool(fill=...) per robot serves it —, tables of different row width, point_dim, desc_dim or
+    invariant, a `centers` or `frames` list whose length is not R, and whatever build_submap_pool refuses per robot."""
+    import torch
+    tables, centers = list(tables), list(centers)
+    R = len(tables)
+    if fill is not None or isinstance(params, FillSubmapParams) or getattr(params, "force_fill_submaps", False):
+        raise ValueError("the session call covers the radius mode: the force_fill_submaps mode orders its slices on the host, use "
+                         "build_submap_pool(fill=...) per robot")
+    if len(centers) != R:
+        raise ValueError("centers must hold one SubmapCenters per table")
+    frames = [None] * R if frames is None else list(frames)
+    if len(frames) != R:
+        raise ValueError("frames must hold one FrameTable per table")
+    layout = lambda t: (int(t.feats.shape[1]), int(t.point_dim), int(t.desc_dim), t.invariant)
+    if any(layout(t) != layout(tables[0]) for t in tables):
+        raise ValueError("the tables differ in row width, point_dim, desc_dim or invariant: one session call packs rows of one layout")
+    widths = [_descriptor_width(t, params, f) for t, f in zip(tables, frames)]       # (build_submap_pool's refusals, per robot)
+    if len({w for w in widths}) > 1:
+        raise ValueError("the robots' frame descriptors differ in length")
+    if cap is None and params.max_size is None:
+        cap = max([len(t) for t in tables] + [1])
+    calls = [submap_call_params(t, params, cap) for t in tables]
+    if R == 0:
+        return []
+    P = calls[0]
+    d, framed, mean_frames = widths[0]
+    ctx = ctx or registration._context()
+    dev = torch.device(device if device is not None else f"cuda:{getattr(ctx, 'device', 0)}")
+    on_host = dev.type == "cpu"                                              # CPU tensors + a stand-in context (tests)
+    F = int(tables[0].feats.shape[1])
+    seg_off = np.concatenate([[0], np.cumsum([len(t) for t in tables])]).astype(np.int64)
+    sub_off = np.concatenate([[0], np.cumsum([len(c) for c in centers])]).astype(np.int32)
+    S, Fo = int(sub_off[-1]), P.point_dim + F - 3
+    rows = S * P.cap
+    # the concatenated table is made ON the device — one tensor, every robot's rows copied straight into their range: joining the
+    # tables on the host first would copy the whole session (hundreds of MB) once more through host memory
+    feats = torch.empty((int(seg_off[-1]), F), dtype=torch.float64, device=dev)
+    for r, t in enumerate(tables):
+        feats[int(seg_off[r]):int(seg_off[r + 1])].copy_(torch.from_numpy(np.ascontiguousarray(t.feats, dtype=np.float64)))
+    times = torch.from_numpy(np.ascontiguousarray(np.concatenate([t.times.reshape(-1, 2) for t in tables], axis=0), dtype=np.float64)).to(dev)
+    ids = torch.from_numpy(np.ascontiguousarray(np.concatenate([t.ids.reshape(-1) for t in tables]), dtype=np.int64)).to(dev)
+    descs = np.concatenate([c.descs() for c in centers])
+    pool = torch.zeros((rows, Fo), dtype=torch.float64, device=dev)
+    count = torch.zeros(max(S, 1), dtype=torch.int32, device=dev); status = torch.zeros(max(S, 1), dtype=torch.int32, device=dev)
+    src = torch.full((max(rows, 1),), -1, dtype=torch.int32, device=dev)
+    ids_out = torch.full((max(rows, 1),), -1, dtype=torch.int64, device=dev)
+    desc = torch.full((max(S, 1), max(d, 1)), float("nan"), dtype=torch.float64, device=dev)
+    ft = []
+    if framed:
+        thin = params.frame_descriptor_dist if params.submap_descriptor == 'stacked_frame_descriptors' else None      # [REF roman/map/map.py:216-226]
+        for r, fr in enumerate(frames):
+            S_r, W = len(centers[r]), (len(fr) + 63) // 64
+            ft.append(dict(W=W, times=torch.from_numpy(fr.times).to(dev), pos=torch.from_numpy(fr.pos).to(dev), desc=torch.from_numpy(fr.desc).to(dev),
+                           mask=torch.zeros((max(S_r, 1), max(W, 1)), dtype=torch.int64, device=dev),
+                           n=torch.zeros(max(S_r, 1), dtype=torch.int32, device=dev), span=torch.zeros((max(S_r, 1), 2), dtype=torch.float64, device=dev)))
+    if not on_host:
+        torch.cuda.current_stream(dev).synchronize()                         # inputs and cleared outputs are in place before the library's stream touches them
+    ctx.session_submaps_dev(P, F, seg_off, feats.data_ptr(), times.data_ptr(), sub_off, descs, pool.data_ptr(), count.data_ptr(), src.data_ptr(),
+                            status.data_ptr(), seg_ids_ptr=ids.data_ptr(), ids_out_ptr=ids_out.data_ptr() if len(ids) else None,     # (no segment at all: no id to write)
+                            desc_dim=0 if framed else d, desc_out_ptr=desc.data_ptr() if d and not framed else None)
+    for r in range(R if framed else 0):                                      # behind it on the same stream: each reads its robot's count and src
+        lo, hi, f = int(sub_off[r]), int(sub_off[r + 1]), ft[r]
+        if hi > lo:
+            ctx.frame_select_dev(frame_select_params(thin, mean_frames), hi - lo, P.cap, count[lo:].data_ptr(), src[lo * P.cap:].data_ptr(), len(tables[r]),
+                                 times[int(seg_off[r]):].data_ptr(), len(frames[r]), f["times"].data_ptr(), f["mask"].data_ptr(), f["n"].data_ptr(),
+                                 f["span"].data_ptr(), frame_pos_ptr=f["pos"].data_ptr(), d=int(frames[r].desc.shape[1]), frame_desc_ptr=f["desc"].data_ptr(),
+                                 mean_ptr=desc[lo:].data_ptr() if mean_frames else None)
+    ctx.sync()
+    count_h, status_h = count.cpu().numpy()[:S].copy(), status.cpu().numpy()[:S].copy()
+    src_h, ids_h = src.cpu().numpy()[:rows].reshape(S, P.cap), ids_out.cpu().numpy()[:rows].reshape(S, P.cap)
+    desc_h = desc.cpu().numpy()[:S, :d] if d else None
+    out = []
+    for r in range(R):
+        lo, hi = int(sub_off[r]), int(sub_off[r + 1])
+        extra = {}
+        if framed:
+            n_h = ft[r]["n"].cpu().numpy()[:hi - lo].copy()
+            bad = np.nonzero((count_h[lo:hi] > 0) & (n_h == 0))[0]
+            if len(bad):
+                raise ValueError(f"submap {int(bad[0])} holds {int(count_h[lo + bad[0]])} segments but no frame of the map lies in its time span: "
+                                 "the reference cannot build its frame descriptor")
+            extra = dict(frames=frames[r], frame_mask=ft[r]["mask"][:hi - lo, :ft[r]["W"]], frame_n=n_h, frame_desc_dev=ft[r]["desc"])
+        out.append(SubmapPool(pool[lo * P.cap:hi * P.cap], int(P.cap), count_h[lo:hi].copy(), src_h[lo:hi].copy(), ids_h[lo:hi].copy(),
+                              status_h[lo:hi].copy(), desc_h[lo:hi].copy() if d else None, centers[r], tables[r],
+                              desc_dev=desc[lo:hi, :d] if d else None, descriptor_mode=params.submap_descriptor,
+                              ids_dev=ids_out[lo * P.cap:hi * P.cap], **extra))
+    return out

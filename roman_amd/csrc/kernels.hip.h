@@ -7468,29 +7468,34 @@ __global__ void __launch_bounds__(256) k_shared_gather(int F, const GatherJob* _
 constexpr int SUBMAP_NT = 256;
 constexpr int SUBMAP_LDS_CAND = 4096;                            // candidates of a submap held in LDS (8 + 4 bytes each)
 
-__global__ void __launch_bounds__(256) k_submap_points(int N, int F, const double* __restrict__ feats, double* __restrict__ pts)
+// (the per-submap bodies below serve k_submap_* and their session forms k_session_submap_* alike — DESIGN.md §4.19 —, as grid_pair()
+// serves k_grid_gate and k_session_gate: one statement of the arithmetic, so the two forms cannot drift apart)
+// centre i of a table of F-double rows into the dense array
+__device__ __forceinline__ void submap_point_one(int64_t i, int F, const double* __restrict__ feats, double* __restrict__ pts)
 {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
     const double* r = feats + i * (int64_t)F;
     pts[3 * i] = r[0]; pts[3 * i + 1] = r[1]; pts[3 * i + 2] = r[2];
 }
 
-__global__ void __launch_bounds__(SUBMAP_NT) k_submap_select(roman_submap_params_t P, int S, int N, const roman_submap_desc_t* __restrict__ descs,
-                                                             const double* __restrict__ pts, const double* __restrict__ times,
-                                                             double* spillKey, int32_t* spillIdx, int64_t spillStride,
-                                                             int32_t* __restrict__ count, int32_t* __restrict__ src, int32_t* __restrict__ status)
+__global__ void __launch_bounds__(256) k_submap_points(int N, int F, const double* __restrict__ feats, double* __restrict__ pts)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    submap_point_one(i, F, feats, pts);
+}
+
+// The workgroup's work for ONE submap: `D` its centre, `pts` / `times` the N centres and times of ITS map (indices 0 .. N - 1 are what
+// src receives), gKey / gIdx its slice of the spill, count / status its two words, `out` its slot of `cap` indices.
+__device__ __forceinline__ void submap_select_one(const roman_submap_params_t& P, const roman_submap_desc_t& D, int N,
+                                                  const double* __restrict__ pts, const double* __restrict__ times,
+                                                  double* gKey, int32_t* gIdx,       // candidates SUBMAP_LDS_CAND, SUBMAP_LDS_CAND + 1, ... of this submap
+                                                  int32_t* __restrict__ count, int32_t* __restrict__ out, int32_t* __restrict__ status)
 {
     __shared__ double keyL[SUBMAP_LDS_CAND];
     __shared__ int32_t idxL[SUBMAP_LDS_CAND];
     __shared__ int wcnt[SUBMAP_NT / 64];
-    const int s = blockIdx.x;
-    if (s >= S) return;
-    const roman_submap_desc_t D = descs[s];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
-    double* const gKey = spillKey + (int64_t)s * spillStride;      // candidates SUBMAP_LDS_CAND, SUBMAP_LDS_CAND + 1, ... of this submap
-    int32_t* const gIdx = spillIdx + (int64_t)s * spillStride;
     const bool ordered = P.max_size > 0;
     int base = 0;
     for (int i0 = 0; i0 < N; i0 += SUBMAP_NT) {                   // (uniform bounds: every barrier below is met by the whole workgroup)
@@ -7533,8 +7538,7 @@ __global__ void __launch_bounds__(SUBMAP_NT) k_submap_select(roman_submap_params
     }
     __syncthreads();                                             // the list is complete (LDS and, at workgroup scope, the spill)
     const int n = base, outN = min(n, P.cap), nL = min(n, SUBMAP_LDS_CAND);
-    if (tid == 0) { count[s] = outN; status[s] = (!ordered && n > P.cap) ? ROMAN_ST_ASSOC_TRUNCATED : ROMAN_ST_OK; }
-    int32_t* const out = src + (int64_t)s * P.cap;
+    if (tid == 0) { *count = outN; *status = (!ordered && n > P.cap) ? ROMAN_ST_ASSOC_TRUNCATED : ROMAN_ST_OK; }
     if (!ordered) {                                              // map order: the list as it stands
         for (int i = tid; i < outN; i += SUBMAP_NT) out[i] = i < SUBMAP_LDS_CAND ? idxL[i] : gIdx[i - SUBMAP_LDS_CAND];
         return;
@@ -7550,6 +7554,47 @@ __global__ void __launch_bounds__(SUBMAP_NT) k_submap_select(roman_submap_params
     }
 }
 
+__global__ void __launch_bounds__(SUBMAP_NT) k_submap_select(roman_submap_params_t P, int S, int N, const roman_submap_desc_t* __restrict__ descs,
+                                                             const double* __restrict__ pts, const double* __restrict__ times,
+                                                             double* spillKey, int32_t* spillIdx, int64_t spillStride,
+                                                             int32_t* __restrict__ count, int32_t* __restrict__ src, int32_t* __restrict__ status)
+{
+    const int s = blockIdx.x;
+    if (s >= S) return;
+    const roman_submap_desc_t D = descs[s];
+    submap_select_one(P, D, N, pts, times, spillKey + (int64_t)s * spillStride, spillIdx + (int64_t)s * spillStride,
+                      count + s, src + (int64_t)s * P.cap, status + s);
+}
+
+// The wave's work for ONE selected row: segment k of the table `feats` (its id in `ids`) into pool row `row`, its centre through T.
+__device__ __forceinline__ void submap_gather_row(int point_dim, int F, const double* __restrict__ T, const unsigned long long* __restrict__ feats,
+                                                  const int64_t* __restrict__ ids, int k, int64_t row,
+                                                  unsigned long long* __restrict__ pool, int64_t* __restrict__ ids_out, int lane)
+{
+    const int Fo = point_dim + F - 3, rest = F - 3;
+    const unsigned long long* in = feats + (int64_t)k * F;
+    unsigned long long* out = pool + row * Fo;
+    if (lane == 0) {
+        const double x = __longlong_as_double((long long)in[0]), y = __longlong_as_double((long long)in[1]), z = __longlong_as_double((long long)in[2]);
+        for (int c = 0; c < point_dim; ++c)
+            out[c] = (unsigned long long)__double_as_longlong(((T[4 * c] * x + T[4 * c + 1] * y) + T[4 * c + 2] * z) + T[4 * c + 3]);
+        if (ids_out) ids_out[row] = ids[k];
+    }
+    const unsigned long long* a = in + 3;
+    unsigned long long* b = out + point_dim;
+    const unsigned oa = (unsigned)(((uintptr_t)a >> 3) & 1u), ob = (unsigned)(((uintptr_t)b >> 3) & 1u);
+    if (oa == ob) {                                              // one 16-byte phase: a leading word when odd, pairs, a trailing word
+        const int head = min((int)oa, rest), pairs = (rest - head) >> 1;
+        if (lane == 0 && head) b[0] = a[0];
+        const ulonglong2* a2 = reinterpret_cast<const ulonglong2*>(a + head);
+        ulonglong2* b2 = reinterpret_cast<ulonglong2*>(b + head);
+        for (int q = lane; q < pairs; q += 64) b2[q] = a2[q];
+        if (lane == 63 && head + 2 * pairs < rest) b[rest - 1] = a[rest - 1];
+    } else {
+        for (int q = lane; q < rest; q += 64) b[q] = a[q];
+    }
+}
+
 // grid (submaps, row groups); a wave per selected row
 __global__ void __launch_bounds__(256) k_submap_gather(int point_dim, int cap, int F, const roman_submap_desc_t* __restrict__ descs,
                                                        const unsigned long long* __restrict__ feats, const int64_t* __restrict__ ids,
@@ -7558,33 +7603,20 @@ __global__ void __launch_bounds__(256) k_submap_gather(int point_dim, int cap, i
 {
     const int s = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = count[s], Fo = point_dim + F - 3, rest = F - 3;
+    const int n = count[s];
     for (int r = blockIdx.y * 4 + wave; r < n; r += 4 * gridDim.y) {
         const int64_t row = (int64_t)s * cap + r;
-        const int k = src[row];
-        const unsigned long long* in = feats + (int64_t)k * F;
-        unsigned long long* out = pool + row * Fo;
-        if (lane == 0) {
-            const double* T = descs[s].T_center_odom;
-            const double x = __longlong_as_double((long long)in[0]), y = __longlong_as_double((long long)in[1]), z = __longlong_as_double((long long)in[2]);
-            for (int c = 0; c < point_dim; ++c)
-                out[c] = (unsigned long long)__double_as_longlong(((T[4 * c] * x + T[4 * c + 1] * y) + T[4 * c + 2] * z) + T[4 * c + 3]);
-            if (ids_out) ids_out[row] = ids[k];
-        }
-        const unsigned long long* a = in + 3;
-        unsigned long long* b = out + point_dim;
-        const unsigned oa = (unsigned)(((uintptr_t)a >> 3) & 1u), ob = (unsigned)(((uintptr_t)b >> 3) & 1u);
-        if (oa == ob) {                                          // one 16-byte phase: a leading word when odd, pairs, a trailing word
-            const int head = min((int)oa, rest), pairs = (rest - head) >> 1;
-            if (lane == 0 && head) b[0] = a[0];
-            const ulonglong2* a2 = reinterpret_cast<const ulonglong2*>(a + head);
-            ulonglong2* b2 = reinterpret_cast<ulonglong2*>(b + head);
-            for (int q = lane; q < pairs; q += 64) b2[q] = a2[q];
-            if (lane == 63 && head + 2 * pairs < rest) b[rest - 1] = a[rest - 1];
-        } else {
-            for (int q = lane; q < rest; q += 64) b[q] = a[q];
-        }
+        submap_gather_row(point_dim, F, descs[s].T_center_odom, feats, ids, src[row], row, pool, ids_out, lane);
     }
+}
+
+// column c of ONE submap's mean_semantic descriptor: the n rows `rows` names of the table `feats`, added in output order
+__device__ __forceinline__ void submap_desc_one(int F, int d, int c, const double* __restrict__ feats, const int32_t* __restrict__ rows, int n,
+                                                double* __restrict__ desc)
+{
+    double acc = 0.0;
+    for (int r = 0; r < n; ++r) acc += feats[(int64_t)rows[r] * F + (F - d) + c];
+    desc[c] = acc / (double)n;
 }
 
 // grid (submaps, column groups): desc_out[s][c] = (sum over the rows of submap s, in output order, of descriptor column c) / count
@@ -7594,10 +7626,71 @@ __global__ void __launch_bounds__(256) k_submap_desc(int cap, int F, int d, cons
     const int s = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
     const int n = count[s];
     if (c >= d || n == 0) return;                                // an empty submap's descriptor is left as it was
-    const int32_t* rows = src + (int64_t)s * cap;
-    double acc = 0.0;
-    for (int r = 0; r < n; ++r) acc += feats[(int64_t)rows[r] * F + (F - d) + c];
-    desc_out[(int64_t)s * d + c] = acc / (double)n;
+    submap_desc_one(F, d, c, feats, src + (int64_t)s * cap, n, desc_out + (int64_t)s * d);
+}
+
+// The same four over the maps of a SESSION (roman_session_submaps*): the R segment tables concatenated in map order,
+// one grid over the submaps of all maps.  A workgroup finds its map through the record the HOST stages per global submap g — the first
+// segment row of its map, the map's rows, the start of the submap's spill slice —: one 24-byte uniform load, no search, and the spill
+// offset (a prefix over S_r * max(N_r - SUBMAP_LDS_CAND, 0)) has no closed form a workgroup could compute anyway.  Everything a
+// workgroup does for its submap is the body above, over ITS map's rows only: src holds map-local indices, and every written byte
+// is what k_submap_* writes for that map alone.
+struct SessionSubmap {
+    int64_t seg0;            // first row of the submap's map in the concatenated tables (seg_off[r])
+    int64_t spill0;          // first entry of the submap's slice of the spill
+    int32_t N;               // rows of the map (seg_off[r + 1] - seg_off[r])
+    int32_t reserved;
+};
+
+__global__ void __launch_bounds__(256) k_session_submap_points(int64_t N, int F, const double* __restrict__ feats, double* __restrict__ pts)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    submap_point_one(i, F, feats, pts);
+}
+
+__global__ void __launch_bounds__(SUBMAP_NT) k_session_submap_select(roman_submap_params_t P, int S, const SessionSubmap* __restrict__ tab,
+                                                                     const roman_submap_desc_t* __restrict__ descs,
+                                                                     const double* __restrict__ pts, const double* __restrict__ times,
+                                                                     double* spillKey, int32_t* spillIdx,
+                                                                     int32_t* __restrict__ count, int32_t* __restrict__ src, int32_t* __restrict__ status)
+{
+    const int g = blockIdx.x;
+    if (g >= S) return;
+    const SessionSubmap M = tab[g];                              // (uniform: the whole workgroup serves one submap of one map)
+    const roman_submap_desc_t D = descs[g];
+    submap_select_one(P, D, M.N, pts + 3 * M.seg0, times + 2 * M.seg0, spillKey + M.spill0, spillIdx + M.spill0,
+                      count + g, src + (int64_t)g * P.cap, status + g);
+}
+
+// grid (submaps of all maps, row groups).  The 16-byte phase is read off the addresses in submap_gather_row: a map's first row sits at
+// seg0 * F * 8 bytes, 8 mod 16 for odd seg0 * F.
+__global__ void __launch_bounds__(256) k_session_submap_gather(int point_dim, int cap, int F, const SessionSubmap* __restrict__ tab,
+                                                               const roman_submap_desc_t* __restrict__ descs,
+                                                               const unsigned long long* __restrict__ feats, const int64_t* __restrict__ ids,
+                                                               const int32_t* __restrict__ count, const int32_t* __restrict__ src,
+                                                               unsigned long long* __restrict__ pool, int64_t* __restrict__ ids_out)
+{
+    const int g = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = count[g];
+    const int64_t seg0 = tab[g].seg0;
+    const unsigned long long* mfeats = feats + seg0 * F;
+    const int64_t* mids = ids ? ids + seg0 : nullptr;
+    for (int r = blockIdx.y * 4 + wave; r < n; r += 4 * gridDim.y) {
+        const int64_t row = (int64_t)g * cap + r;
+        submap_gather_row(point_dim, F, descs[g].T_center_odom, mfeats, mids, src[row], row, pool, ids_out, lane);
+    }
+}
+
+// grid (submaps of all maps, column groups)
+__global__ void __launch_bounds__(256) k_session_submap_desc(int cap, int F, int d, const SessionSubmap* __restrict__ tab, const double* __restrict__ feats,
+                                                             const int32_t* __restrict__ count, const int32_t* __restrict__ src, double* __restrict__ desc_out)
+{
+    const int g = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
+    const int n = count[g];
+    if (c >= d || n == 0) return;                                // an empty submap's descriptor is left as it was
+    submap_desc_one(F, d, c, feats + tab[g].seg0 * F, src + (int64_t)g * cap, n, desc_out + (int64_t)g * d);
 }
 
 // Submap.segments_as_global_points [REF roman/map/map.py:133-139] reduced to what aabb_intersects [REF roman/utils.py:160-169] reads

@@ -178,6 +178,9 @@ struct roman_ctx {
     // the map, and the per-submap spill of candidate lists beyond SUBMAP_LDS_CAND
     DevBuf smDesc, smPts, smSpillKey, smSpillIdx;
     PinnedStage<roman_submap_desc_t> smStage;
+    // ... of a whole session (roman_session_submaps*): one record per global submap — where its map and its spill slice start
+    DevBuf smTab;
+    PinnedStage<SessionSubmap> smTabStage;
 
     // pass 1 of a grid (roman_grid_gate*): the descriptor norms of both sides
     DevBuf ggNorm;
@@ -1456,7 +1459,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     c->hostMirror.release(); c->ransacDesc.release();
     c->shareStage.release(); c->ransacStage.release();
     { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx}; for (DevBuf* b : sm) b->release(); }
-    c->smStage.release();
+    c->smStage.release(); c->smTab.release(); c->smTabStage.release();
     c->ggNorm.release(); c->sgCount.release();
     c->ssNorm.release(); c->ssBand.release(); c->ssR.release(); c->ssItems.release(); c->ssStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
@@ -2923,6 +2926,143 @@ int roman_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t 
                            desc_dim, descOut.dev());
     if (rc) return rc;
     return m.download();
+}
+
+// --- the submaps of every map of a session in one launch sequence -------------------------------------------------
+// What one call works on, under names, from the C entry point to the launch; the host form hands the device form a copy whose bulk
+// arrays are the mirror's.  seg_off, sub_off and descs are HOST memory in both forms.
+struct SessionSubmapsArgs {
+    int32_t R, F;
+    const int64_t* seg_off; const double* seg_feats; const double* seg_times; const int64_t* seg_ids;
+    const int32_t* sub_off; const roman_submap_desc_t* descs;
+    double* pool; int32_t* count; int32_t* src; int64_t* ids_out; int32_t* status;
+    int32_t desc_dim; double* desc_out;
+};
+
+// the offsets first (they size everything else), then roman_submaps_dev's own checks; what passes has *N segment rows and *S submaps
+static int session_submaps_check(roman_ctx* c, const roman_submap_params_t* P, const SessionSubmapsArgs& g, bool pool_needed, int64_t* N, int32_t* S)
+{
+    const int32_t R = g.R;
+    if (R < 0) return fail(c, ROMAN_E_INVALID, "R < 0");
+    if (R > 0 && (!g.seg_off || !g.sub_off)) return fail(c, ROMAN_E_INVALID, "seg_off / sub_off is NULL");
+    if (R > 0 && (g.seg_off[0] != 0 || g.sub_off[0] != 0)) return fail(c, ROMAN_E_INVALID, "seg_off[0] and sub_off[0] must be 0");
+    for (int r = 0; r < R; ++r) {
+        if (g.seg_off[r + 1] < g.seg_off[r]) return fail(c, ROMAN_E_INVALID, "seg_off decreases at map %d", r);
+        if (g.sub_off[r + 1] < g.sub_off[r]) return fail(c, ROMAN_E_INVALID, "sub_off decreases at map %d", r);
+        if (g.seg_off[r + 1] - g.seg_off[r] > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "map %d holds more than %d segments", r, INT32_MAX);
+    }
+    *N = R > 0 ? g.seg_off[R] : 0; *S = R > 0 ? g.sub_off[R] : 0;
+    int rc = submaps_check(c, P, *N > 0 ? 1 : 0, g.F, g.seg_feats, g.seg_times, g.seg_ids, *S, g.descs, g.pool, g.count, g.src, g.ids_out, g.status,
+                           g.desc_dim, g.desc_out, pool_needed);
+    if (rc) return rc;
+    if ((int64_t)*S * P->cap > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "sub_off[R] * cap = %lld rows exceed the index width", (long long)*S * P->cap);
+    return ROMAN_OK;
+}
+
+// the device-pointer call
+static int session_submaps_dev(roman_ctx* c, const roman_submap_params_t* sparams, const SessionSubmapsArgs& g)
+{
+    // (the arguments are judged first — on host memory only, a NULL context included: fail() then keeps the text for roman_last_error(NULL))
+    int64_t N = 0; int32_t S = 0;
+    int rc = session_submaps_check(c, sparams, g, true, &N, &S);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (S == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    // every submap's slice of the spill starts where the slices of the submaps in front of it end
+    int64_t spill = 0; int32_t maxN = 0;
+    for (int r = 0; r < g.R; ++r) {
+        const int64_t n = g.seg_off[r + 1] - g.seg_off[r], over = std::max<int64_t>(n - SUBMAP_LDS_CAND, 0);
+        const int64_t subs = g.sub_off[r + 1] - g.sub_off[r];
+        if (subs) maxN = std::max(maxN, (int32_t)n);
+        if (over && subs > (INT64_MAX / 16 - spill) / over) return fail(c, ROMAN_E_NOMEM, "the candidate scratch of the session exceeds the address space");
+        spill += subs * over;
+    }
+    // scratch and staging first: a failure leaves nothing enqueued
+    if (spill > 0) {
+        HIPCHK(c, c->smSpillKey.ensure(sizeof(double) * (size_t)spill));
+        HIPCHK(c, c->smSpillIdx.ensure(sizeof(int32_t) * (size_t)spill));
+    }
+    HIPCHK(c, c->smPts.ensure(sizeof(double) * 3 * (size_t)std::max<int64_t>(N, 1)));
+    HIPCHK(c, c->smDesc.ensure(sizeof(roman_submap_desc_t) * (size_t)S));
+    HIPCHK(c, c->smTab.ensure(sizeof(SessionSubmap) * (size_t)S));
+    roman_submap_desc_t* staged = nullptr;
+    SessionSubmap* tab = nullptr;
+    HIPCHK(c, c->smStage.stage((size_t)S, &staged));
+    HIPCHK(c, c->smTabStage.stage((size_t)S, &tab));
+    memcpy(staged, g.descs, sizeof(roman_submap_desc_t) * (size_t)S);
+    int64_t at = 0;
+    for (int r = 0; r < g.R; ++r) {
+        const int64_t n = g.seg_off[r + 1] - g.seg_off[r], over = std::max<int64_t>(n - SUBMAP_LDS_CAND, 0);
+        for (int32_t s = g.sub_off[r]; s < g.sub_off[r + 1]; ++s, at += over) tab[s] = SessionSubmap{g.seg_off[r], at, (int32_t)n, 0};
+    }
+    HIPCHK(c, c->smStage.upload(c->smDesc, (size_t)S, stream));
+    HIPCHK(c, c->smTabStage.upload(c->smTab, (size_t)S, stream));
+    const roman_submap_desc_t* dDesc = c->smDesc.as<roman_submap_desc_t>();
+    const SessionSubmap* dTab = c->smTab.as<SessionSubmap>();
+    const int cap = sparams->cap, F = g.F;
+    if (N > 0) hipLaunchKernelGGL(k_session_submap_points, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, N, F, g.seg_feats, c->smPts.as<double>());
+    hipLaunchKernelGGL(k_session_submap_select, dim3((unsigned)S), dim3(SUBMAP_NT), 0, stream, *sparams, (int)S, dTab, dDesc, c->smPts.as<double>(), g.seg_times,
+                       c->smSpillKey.as<double>(), c->smSpillIdx.as<int32_t>(), g.count, g.src, g.status);
+    HIPCHK(c, hipGetLastError());
+    if (maxN > 0) {
+        // as roman_submaps_dev launches them: enough row groups for the largest slot of the largest map, at most 64 per submap
+        const unsigned groups = (unsigned)std::min(64, (std::min(cap, maxN) + 3) / 4);
+        hipLaunchKernelGGL(k_session_submap_gather, dim3((unsigned)S, groups), dim3(256), 0, stream, (int)sparams->point_dim, cap, F, dTab, dDesc,
+                           reinterpret_cast<const unsigned long long*>(g.seg_feats), g.seg_ids, g.count, g.src, reinterpret_cast<unsigned long long*>(g.pool), g.ids_out);
+        if (g.desc_out) hipLaunchKernelGGL(k_session_submap_desc, dim3((unsigned)S, (unsigned)((g.desc_dim + 255) / 256)), dim3(256), 0, stream, cap, F, (int)g.desc_dim,
+                                           dTab, g.seg_feats, g.count, g.src, g.desc_out);
+        HIPCHK(c, hipGetLastError());
+    }
+    return ROMAN_OK;
+}
+
+// the host-pointer call: without a pool the device call still writes one
+static int session_submaps_host(roman_ctx* c, const roman_submap_params_t* sparams, const SessionSubmapsArgs& h)
+{
+    int64_t N = 0; int32_t S = 0;
+    int rc = session_submaps_check(c, sparams, h, false, &N, &S);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (S == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const size_t rows = (size_t)S * (size_t)sparams->cap, bPool = sizeof(double) * rows * (size_t)(sparams->point_dim + h.F - 3);
+    HostMirror m(c);
+    const auto feats = m.in(h.seg_feats, sizeof(double) * (size_t)N * (size_t)h.F);
+    const auto times = m.in(h.seg_times, sizeof(double) * 2 * (size_t)N);
+    const auto ids = m.in(h.seg_ids, h.seg_ids ? sizeof(int64_t) * (size_t)N : 0);
+    const auto dPool = h.pool ? m.inout(h.pool, bPool) : m.room<double>(bPool);
+    const auto idsOut = m.inout(h.ids_out, h.ids_out ? sizeof(int64_t) * rows : 0);
+    const auto descOut = m.inout(h.desc_out, h.desc_out ? sizeof(double) * (size_t)S * (size_t)h.desc_dim : 0);
+    const auto dSrc = m.inout(h.src, sizeof(int32_t) * rows);
+    const auto cnt = m.out(h.count, sizeof(int32_t) * (size_t)S);
+    const auto st = m.out(h.status, sizeof(int32_t) * (size_t)S);
+    rc = m.upload();
+    if (rc) return rc;
+    SessionSubmapsArgs g = h;                                    // the same call on the mirror; offsets and descriptors stay the caller's
+    g.seg_feats = feats.dev(); g.seg_times = times.dev(); g.seg_ids = ids.dev();
+    g.pool = dPool.dev(); g.count = cnt.dev(); g.src = dSrc.dev(); g.ids_out = idsOut.dev(); g.status = st.dev(); g.desc_out = descOut.dev();
+    rc = session_submaps_dev(c, sparams, g);
+    if (rc) return rc;
+    return m.download();
+}
+
+int roman_session_submaps_dev(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
+                              const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
+                              double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
+{
+    const SessionSubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
+    return session_submaps_dev(c, sparams, g);
+}
+
+int roman_session_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
+                          const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
+                          double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
+{
+    const SessionSubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
+    return session_submaps_host(c, sparams, g);
 }
 
 // --- force-fill submaps and the boxes of a pool ([REF roman/map/map.py:264-295], [REF :133-139]) -------------------

@@ -708,6 +708,56 @@ class Context:
                                          _vp(status_ptr), int(desc_dim), _vp(desc_out_ptr))
         self._check(rc, "roman_submaps_dev")
 
+    # ------------------------------------------------------------------ the submaps of every map of a session
+    @staticmethod
+    def _session_offsets(seg_off, sub_off):
+        """The two offset tables of a session of maps in the C ABI's types -> (seg_off int64[R+1], sub_off int32[R+1], R)."""
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1); sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1)
+        if seg_off.shape[0] != sub_off.shape[0] or seg_off.shape[0] < 1:
+            raise ValueError("seg_off and sub_off must both hold R + 1 entries")
+        return seg_off, sub_off, int(seg_off.shape[0]) - 1
+
+    def session_submaps(self, sparams, seg_off, seg_feats, seg_times, sub_off, descs, seg_ids=None, desc_dim=0, want_pool=True,
+                        pool=None, src=None, ids_out=None, desc_out=None):
+        """Host-pointer submaps of the R maps of a session (roman_session_submaps): submaps() for every map in one
+        call.  seg_feats (N, F) / seg_times (N, 2) / seg_ids (N,) are the R map tables concatenated in map order, map r owning the
+        rows [seg_off[r], seg_off[r+1]) and the centres descs[sub_off[r]:sub_off[r+1]]; `src` holds map-local indices.  Output
+        arrays as for submaps().  -> SubmapsResult over all sub_off[R] submaps."""
+        seg_feats = _f64(seg_feats); seg_times = _f64(seg_times)
+        if seg_feats.ndim != 2 or seg_times.shape != (seg_feats.shape[0], 2):
+            raise ValueError("seg_feats must be (N, F) and seg_times (N, 2)")
+        N, F = seg_feats.shape
+        if seg_ids is not None:
+            seg_ids = np.ascontiguousarray(seg_ids, dtype=np.int64).reshape(-1)
+            if seg_ids.shape[0] != N:
+                raise ValueError("seg_ids must hold one entry per segment")
+        seg_off, sub_off, R = self._session_offsets(seg_off, sub_off)
+        descs = self._submap_descs(descs)
+        S = int(descs.shape[0])
+        if int(seg_off[-1]) != N or int(sub_off[-1]) != S:
+            raise ValueError("seg_off[R] must be the rows of seg_feats and sub_off[R] the number of descs")
+        rows, Fo, d = S * max(int(sparams.cap), 0), int(sparams.point_dim) + F - 3, int(desc_dim)
+        pool = _given(pool, (rows, max(Fo, 0)), np.float64, 0.0) if (want_pool or pool is not None) else None
+        src = _given(src, (rows,), np.int32, -1)
+        ids_out = _given(ids_out, (rows,), np.int64, -1) if seg_ids is not None else None
+        desc_out = _given(desc_out, (S, d), np.float64, np.nan) if d > 0 else None
+        count = np.zeros(S, dtype=np.int32); status = np.zeros(S, dtype=np.int32)
+        self._enqueue("roman_session_submaps", C.byref(sparams), R, F, _ptr(seg_off), _ptr(seg_feats), _ptr(seg_times), _ptr(seg_ids), _ptr(sub_off),
+                      _ptr(descs), _ptr(pool), _ptr(count), _ptr(src), _ptr(ids_out), _ptr(status), d, _ptr(desc_out))
+        return SubmapsResult(pool, count, src, ids_out, status, desc_out)
+
+    def session_submaps_dev(self, sparams, F, seg_off, seg_feats_ptr, seg_times_ptr, sub_off, descs, pool_ptr, count_ptr, src_ptr, status_ptr,
+                            seg_ids_ptr=None, ids_out_ptr=None, desc_dim=0, desc_out_ptr=None):
+        """Device-pointer submaps of the R maps of a session (roman_session_submaps_dev): bulk pointers are device addresses
+        (integers); seg_off, sub_off and `descs` (a submap_desc_dtype array over all sub_off[R] centres) are host arrays.  A pure
+        enqueue on the context's stream; complete after sync()."""
+        seg_off, sub_off, R = self._session_offsets(seg_off, sub_off)
+        descs = self._submap_descs(descs)
+        if int(sub_off[-1]) != int(descs.shape[0]):
+            raise ValueError("sub_off[R] must be the number of descs")
+        self._enqueue("roman_session_submaps_dev", C.byref(sparams), R, int(F), _ptr(seg_off), *_vps(seg_feats_ptr, seg_times_ptr, seg_ids_ptr),
+                      _ptr(sub_off), _ptr(descs), *_vps(pool_ptr, count_ptr, src_ptr, ids_out_ptr, status_ptr), int(desc_dim), _vp(desc_out_ptr))
+
     # ------------------------------------------------------------------ pass 1 of a grid of submaps
     def grid_gate(self, gparams, pos0, T_w0, pos1, T_w1, time0=None, time1=None, desc0=None, desc1=None, pos_gt0=None, pos_gt1=None,
                   pairs=None, T_ref=None, enable=None):
