@@ -1308,6 +1308,45 @@ ROMAN_API int roman_session_gate_aabb(roman_ctx_t* ctx, const roman_grid_gate_pa
                                       double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
                                       int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off, const double* box, const double* sim_in);
 
+/*
+ * roman_session_gate_list_dev: pass 1 of a session for an explicit LIST of pairs instead of whole robot-pair
+ * grids — what a session that grows asks for: only the pairs a new or changed submap touches.  R, sub_off, pos, pos_gt, has_gt,
+ * T_w, time, desc, nb, blocks and pair_off are roman_session_gate_dev's, validated as there and in front of everything else (no
+ * tile_off: the list is the work).  Every bulk pointer DEVICE; a PURE ENQUEUE on the context's stream; the small tables and the
+ * list travel twice (device, and `_host` copies the library validates).
+ *
+ *   L, list    int32[L][3]: (b, i, j) — block index, block-local row and column.  Strictly ascending in (b, i, j): no pair twice
+ *   box        float64[S][6] or NULL.  Given: the bounding-box gate, roman_session_gate_aabb_dev's rules; the radius is not read
+ *   sim_in     float64[pair_off[nb]] or NULL.  Given: the similarity of every pair of every block is already there, at the pair's
+ *              DENSE position pair_off[b] + i * n1 + j (roman_session_stacked_sim_dev's layout), gated by roman_session_gate_sim_dev's
+ *              rules: gparams->desc_dim must be 0, equality with the threshold passes; `desc` is not read
+ *
+ * Outputs per LISTED pair (L entries, in list order): dist, flags, yaw_deg, sim, T_ij (x16) — entry l bit for bit what
+ * roman_session_gate_dev (roman_session_gate_sim_dev / _aabb_dev) writes at that pair's dense position over the same tables; with
+ * sim_in, sim[l] is the copy of the pair's entry of sim_in.  Compact outputs (capacity L; slots beyond the total untouched):
+ * pairs (GLOBAL gi, gj), T_ref, enable, and todo_off int32[nb+1] — the TODO pairs in list order, block b's in the slots
+ * [todo_off[b], todo_off[b+1]).  With the full list (every pair of every block) every output equals the whole-grid call's.
+ * No atomics: two runs agree bit for bit.
+ *
+ * L == 0: ROMAN_OK, todo_off all 0, nothing else written.  Errors: roman_session_gate_dev's about its tables and gparams; L < 0, a
+ * NULL list with L > 0, an entry with b outside [0, nb) or (i, j) outside its block, a list not strictly ascending, sim_in with
+ * desc_dim != 0, a NULL output that is needed -> ROMAN_E_INVALID; L * 16 beyond int32 -> ROMAN_E_TOO_LARGE.
+ */
+ROMAN_API int roman_session_gate_list_dev(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
+                                          const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                          int32_t nb, const int32_t* blocks, const int32_t* blocks_host, const int64_t* pair_off, const int64_t* pair_off_host,
+                                          int32_t L, const int32_t* list, const int32_t* list_host, const double* box, const double* sim_in,
+                                          double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                          int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off);
+
+/* The same with HOST pointers everywhere (each table and the list once).  Synchronous; box and sim_in go up and are not brought
+   back.  The caller's pairs, T_ref and enable go up first: the slots beyond todo_off[nb] come back as they were. */
+ROMAN_API int roman_session_gate_list(roman_ctx_t* ctx, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                                      const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                      int32_t nb, const int32_t* blocks, const int64_t* pair_off, int32_t L, const int32_t* list, const double* box, const double* sim_in,
+                                      double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                      int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off);
+
 /* ------------------------------------------------------------------------------------------- */
 /* stepwise surface for the clipperpy-compatible shim (single problem, host pointers)          */
 /* ------------------------------------------------------------------------------------------- */

@@ -1378,6 +1378,375 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
 
 
 # ---------------------------------------------------------------------------------------------
+# a session that GROWS: only the pairs a new or changed submap touches
+# ---------------------------------------------------------------------------------------------
+class SessionAlignState:
+    """What submap_align_session_update keeps between two steps of one session: the call it was made for, per robot the submaps
+    it saw and the bytes of their host-side inputs, and every block's results.  Empty until the first call."""
+
+    def __init__(self):
+        self.key = None              # robot_pairs, method, descriptor mode, gate, ground truth, num_solutions: a state serves ONE kind of call
+        self.n_pool = None           # per robot: the submaps of its pool, empty ones included
+        self.keep = None             # per robot: the pool indices of its non-empty submaps
+        self.seen = None             # per (block, side): uint8 (n, bytes) — the host-side inputs of every non-empty submap as that block read them
+        self.results = None          # {(r, s): SubmapAlignResults} as returned last
+        self.listed = 0              # pairs the last call listed, and what the full grids hold (for the caller's accounting)
+        self.total = 0
+        self.seconds = {}            # the last call's wall time by part: 'host' (the per-robot block, the touched set, the carry-over), 'gate' (uploads,
+                                     # pass 1, its synchronisation and read-back), 'register' (the batch, the tail and the records)
+
+
+_MATRICES = ("robots_nearby_mat", "clipper_angle_mat", "clipper_dist_mat", "clipper_num_associations", "similarity_mat", "submap_yaw_diff_mat",
+             "T_ij_mat", "T_ij_hat_mat")
+
+
+def _carry_over(M, old, old_keep, new_keep):
+    """The stored results `old` of a block into the fresh matrices `M`, re-indexed through the pool indices of the non-empty
+    submaps (old_keep / new_keep: one array per side) -> (edges, hypotheses) re-indexed the same way; a submap that is gone
+    takes its entries with it."""
+    where = [{int(s): k for k, s in enumerate(nk)} for nk in new_keep]
+    to_new = [np.array([where[a].get(int(s), -1) for s in ok], dtype=np.int64) for a, ok in enumerate(old_keep)]
+    src = [np.nonzero(t >= 0)[0] for t in to_new]
+    dst = [t[t >= 0] for t in to_new]
+    appended = all(len(ok) <= len(nk) and np.array_equal(ok, nk[:len(ok)]) for ok, nk in zip(old_keep, new_keep))
+    if appended and len(src[0]) and len(src[1]):             # the usual step: the old grid is the top left corner of the new one
+        a, b = len(old_keep[0]), len(old_keep[1])
+        for name in _MATRICES:
+            if getattr(old, name) is not None:
+                getattr(M, name)[:a, :b] = getattr(old, name)
+        extra = len(new_keep[1]) - b
+        for i in range(a):
+            M.associated_objs_mat[i] = old.associated_objs_mat[i] + [[] for _ in range(extra)]
+    elif len(src[0]) and len(src[1]):
+        for name in _MATRICES:
+            if getattr(old, name) is not None:
+                getattr(M, name)[np.ix_(dst[0], dst[1])] = getattr(old, name)[np.ix_(src[0], src[1])]
+        back = np.full(len(new_keep[1]), -1, dtype=np.int64)        # new column -> old column
+        back[dst[1]] = src[1]
+        back = back.tolist()
+        for i_old, i_new in zip(src[0].tolist(), dst[0].tolist()):
+            row = old.associated_objs_mat[i_old]
+            M.associated_objs_mat[i_new] = [row[j] if j >= 0 else [] for j in back]
+    edges = None
+    if old.lc_edges is not None:
+        pr = np.asarray(old.lc_edges["pairs"], dtype=np.int64).reshape(-1, 2)
+        pr = np.stack([to_new[0][pr[:, 0]], to_new[1][pr[:, 1]]], axis=1) if len(pr) else pr
+        ok = (pr >= 0).all(axis=1)
+        edges = dict(pairs=pr[ok], t=np.asarray(old.lc_edges["t"]).reshape(-1, 3)[ok], q=np.asarray(old.lc_edges["q"]).reshape(-1, 4)[ok])
+    hyps = None
+    if old.hypotheses is not None:
+        hyps = {(int(to_new[0][i]), int(to_new[1][j])): h for (i, j), h in old.hypotheses.items() if to_new[0][i] >= 0 and to_new[1][j] >= 0}
+    return edges, hyps
+
+
+def submap_align_session_update(state, sm_params, pools, touched=None, robot_pairs=None, sm_io: Optional[SubmapAlignIO] = None, registration=None,
+                                gt_poses=None, num_solutions=None) -> Dict[Tuple[int, int], SubmapAlignResults]:
+    """submap_align_session for a session that GROWS: `state` (a SessionAlignState, empty before the first call)
+    keeps every block's results, and a call gates and registers only the pairs with a TOUCHED submap on either side — one
+    roman_session_gate_list_dev over the pair list, one batch over the pools, the shared-segment removal and the tail as in
+    submap_align_session.  -> {(r, s): SubmapAlignResults} over EVERY block, equal to submap_align_session(sm_params, pools, ...)
+    over the same pools (only timing_list differs: it holds the pairs registered in this call).  A first call is the full call.
+
+    Between two calls a pool may only grow by APPENDING submaps: submap s of robot r stays submap s (one that was empty may fill).
+    touched[r] (bool over robot r's pool submaps, or None) flags the submaps whose rows, ids or frames the caller changed — as
+    the last submap of the step before, whose t_hi moves when a successor arrives.  The call adds on its own: every submap beyond
+    the robot's earlier count; every submap that was empty; and every submap whose host-side inputs differ, by bytes, from what the
+    state recorded for ANY block the robot takes part in — centre, ground-truth centre, time, and what depends on the pose as the
+    pair loop leaves it: reference pose, edge frames, the box pose of the bounding-box gate.  The last three can change without
+    the caller's doing: what the pair loop reads of a pose can depend on the partner's number of submaps, so
+    a partner going from an odd to an even count touches every submap of a robot whose poses alternate.  Nothing stale is reused
+    silently: what these rules cannot see is the caller's to flag.
+
+    With 'stacked_frame_descriptors' the similarity is still computed for whole blocks (roman_session_stacked_sim_dev), the gate
+    then reads it at the listed pairs.
+
+    ValueError before any context is made: whatever submap_align_session refuses; a pool that shrank; a `touched` of the wrong
+    length; a state made for other robot_pairs, another method, descriptor mode, gate, ground-truth pattern or num_solutions."""
+    import torch
+    from ..runtime import session_pair_list, session_tables
+    marks = [time.perf_counter()]
+    sm_io = sm_io or SubmapAlignIO()
+    registration = registration or sm_params.get_object_registration()
+    way = " (not in the session call: use submap_align_pools per robot pair)"
+    p = list(pools)
+    R = len(p)
+    gt_poses = [None] * R if gt_poses is None else list(gt_poses)
+    blocks = [(r, s) for r in range(R) for s in range(r, R)] if robot_pairs is None else [(int(r), int(s)) for r, s in robot_pairs]
+    if len(gt_poses) != R:
+        raise ValueError("gt_poses must hold one entry per pool" + way)
+    if any(not (0 <= r < R and 0 <= s < R) for r, s in blocks) or len(set(blocks)) != len(blocks):
+        raise ValueError("robot_pairs must name pools by index, each pair once" + way)
+    if num_solutions is not None:
+        _mno_refusals(registration, p, blocks, num_solutions, way)
+    if isinstance(registration, RansacReg) and R:
+        _ransac_refusals(registration, p, way)
+    if _device_prefilter(registration) and R:
+        _prune_refusals(registration, p, way)
+    aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
+    if aabb_mode and _no_device(registration, p):
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes of the resident rows: the registration has no context set "
+                         "and the pools are host tensors: no device to run on" + way)
+    mode = sm_params.submap_descriptor
+    stacked = mode == 'stacked_frame_descriptors'
+    _descriptor_refusals(registration, p, mode, way)
+    if R and any(int(q.pool.shape[1]) != int(p[0].pool.shape[1]) for q in p):
+        raise ValueError("the pools have different row widths" + way)
+    d = _descriptor_dim(p, mode, "the pools", way)
+    selfs = sorted({r for r, s in blocks if r == s})
+    if any(p[r].ids_dev is None for r in selfs):
+        raise ValueError("a self block drops the segments both submaps hold: its pool must have kept its ids on the device (SubmapPool.ids_dev, "
+                         "as build_submap_pool leaves it)" + way)
+    # ---- what only a growing session can get wrong ----
+    key = (tuple(blocks), type(registration).__name__, getattr(sm_params, "method", None), mode, aabb_mode, tuple(g is not None for g in gt_poses),
+           num_solutions, int(d))
+    if state.key is not None and state.key != key:
+        raise ValueError("the state was made by a call with other robot_pairs, another method, descriptor mode, gate, ground-truth pattern or "
+                         "num_solutions: a SessionAlignState serves one kind of call")
+    n_pool = [len(q.count) for q in p]
+    if state.key is not None and any(n < m for n, m in zip(n_pool, state.n_pool)):
+        raise ValueError("a pool shrank: between two calls pools may only grow by appending submaps")
+    touched = [None] * R if touched is None else list(touched)
+    if len(touched) != R or any(t is not None and np.asarray(t).reshape(-1).shape[0] != n for t, n in zip(touched, n_pool)):
+        raise ValueError("touched must hold one entry per pool, each None or one flag per submap of that pool")
+
+    keep = [q.nonempty for q in p]
+    counts = np.array([len(k) for k in keep], dtype=np.int64)
+    # ---- per robot (O(S), host): views exactly as submap_align_session cuts them ----
+    views, view_of = [], {}
+    for r in range(R):
+        reads = sorted({int(counts[s if a == r else a]) for a, s in blocks if r in (a, s)})
+        mine = []
+        live_reads = [n for n in reads if n > 0] if counts[r] else []
+        all_ = _pool_side_host(p[r], gt_poses[r], gt_poses[r] is not None, live_reads, aabb_mode) if live_reads else None
+        for k, n in enumerate(live_reads):
+            hs = dict(all_, T_w=[all_["T_w"][k]], frames=all_["frames"][k])
+            vkey = hs["T_w"][0].tobytes() + hs["frames"][0].tobytes() + hs["frames"][1].tobytes() + (hs["T_oc"].tobytes() if aabb_mode else b"")
+            same = [v for v, kk in mine if kk == vkey]
+            if not same:
+                views.append((r, hs)); mine.append((len(views) - 1, vkey))
+            view_of[(r, n)] = same[0] if same else len(views) - 1
+        if reads and not mine:
+            views.append((r, None)); mine.append((len(views) - 1, b""))
+        for n in reads:
+            view_of.setdefault((r, n), mine[0][0])
+    vcount = np.array([counts[r] for r, _ in views], dtype=np.int64)
+    vblocks = [(view_of[(r, int(counts[s]))], view_of[(s, int(counts[r]))]) for r, s in blocks]
+
+    # ---- the touched set: the caller's flags, what is new, and what differs from the bytes the state recorded ----
+    def rows_of_view(v):
+        """-> (uint8 (n, a) of what does not depend on the reads, uint8 (n, b) of what does) per non-empty submap of view v."""
+        r, hs = views[v]
+        n = int(counts[r])
+        if hs is None:
+            return np.zeros((n, 0), np.uint8), np.zeros((n, 0), np.uint8)
+        as_bytes = lambda parts: np.concatenate([np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(n, -1)).view(np.uint8) for a in parts], axis=1)
+        fixed = [hs["pos"], hs["time"]] + ([hs["pos_gt"]] if hs["pos_gt"] is not None else [])
+        return as_bytes(fixed), as_bytes([hs["T_w"][0], hs["frames"][0], hs["frames"][1]] + ([hs["T_oc"]] if aabb_mode else []))
+    seen = {(b, a): rows_of_view(vblocks[b][a]) for b in range(len(blocks)) for a in range(2)}
+    flag = [np.zeros(n, dtype=bool) if t is None else np.asarray(t, dtype=bool).reshape(-1).copy() for t, n in zip(touched, n_pool)]
+    first = state.key is None
+    for r in range(R):
+        if first:
+            flag[r][:] = True
+            continue
+        flag[r][state.n_pool[r]:] = True
+        flag[r][np.setdiff1d(keep[r], state.keep[r])] = True     # (it was empty)
+    if not first:
+        for (b, a), (fixed, posed) in seen.items():
+            r = blocks[b][a]
+            was_fixed, was_posed = state.seen[(b, a)]
+            common, at_new, at_old = np.intersect1d(keep[r], state.keep[r], return_indices=True)
+            if not len(common) or not fixed.shape[1] or not was_fixed.shape[1]:
+                if len(common) and fixed.shape[1] != was_fixed.shape[1]:
+                    flag[r][:] = True                            # (the block had no pair before, or has none now: nothing recorded to compare with)
+                continue
+            flag[r][common[(fixed[at_new] != was_fixed[at_old]).any(axis=1)]] = True
+            flag[r][common[(posed[at_new] != was_posed[at_old]).any(axis=1)]] = True      # (it is read with another pose, in this block at least)
+    local_flag = [flag[r][keep[r]] for r in range(R)]
+
+    def result_of(b, M, timing=(), edges=None, hyps=None):
+        io = copy.copy(sm_io); io.gt_available = (gt_poses[blocks[b][0]] is not None, gt_poses[blocks[b][1]] is not None)
+        M.sm_io = io
+        return M.results(timing, edges, hyps if num_solutions is None or hyps is not None else {})
+    prm = [copy.copy(sm_params) for _ in blocks]
+    for q, (r, s) in zip(prm, blocks):
+        q.single_robot_lc = (r == s)
+    nb = len(blocks)
+    Ms = [_GridResults(prm[b], sm_io, int(counts[r]), int(counts[s])) for b, (r, s) in enumerate(blocks)]
+    old = []                                                     # per block: the stored results re-indexed into Ms[b] -> (edges, hypotheses)
+    for b, (r, s) in enumerate(blocks):
+        if first:
+            old.append((Ms[b].empty_edges(), None if num_solutions is None else {}))
+        else:
+            e, hy = _carry_over(Ms[b], state.results[blocks[b]], (state.keep[r], state.keep[s]), (keep[r], keep[s]))
+            old.append(((e if e is not None else Ms[b].empty_edges()) if Ms[b].device_edges else None, hy))
+    sub_off, blk, pair_off, tile_off = session_tables(vcount, [(va, vb, r == s) for (va, vb), (r, s) in zip(vblocks, blocks)])
+    lst = session_pair_list(vcount, vblocks, [local_flag[r] for r, _ in views])
+    total, L = int(pair_off[-1]), len(lst)
+    cut = np.searchsorted(lst[:, 0], np.arange(nb + 1))          # block b's entries are lst[cut[b]:cut[b + 1]]
+
+    def remember(out):
+        state.key, state.n_pool, state.keep, state.seen, state.results, state.listed, state.total = key, n_pool, keep, seen, out, L, total
+        marks.append(time.perf_counter())
+        state.seconds = dict(zip(("host", "gate", "register"), np.diff(marks).tolist()))
+        return out
+
+    def merged(b, fresh_M=None, ti=None, tj=None, fresh_edges=None, fresh_hyps=None, timing=()):
+        """Block b: the carried-over entries, and over them what this call computed for its listed pairs."""
+        M, (edges, hyps) = Ms[b], old[b]
+        li, lj = lst[cut[b]:cut[b + 1], 1].astype(np.int64), lst[cut[b]:cut[b + 1], 2].astype(np.int64)
+        if fresh_M is not None:                                  # (a grid of one column: row k is the block's k-th listed pair)
+            for name in _MATRICES:
+                getattr(M, name)[li, lj] = getattr(fresh_M, name)[:, 0]
+            for k, (i, j) in enumerate(zip(li.tolist(), lj.tolist())):
+                M.associated_objs_mat[i][j] = fresh_M.associated_objs_mat[k][0]
+        n1 = max(int(counts[blocks[b][1]]), 1)
+        was_listed = np.zeros(int(counts[blocks[b][0]]) * n1 + 1, dtype=bool)
+        was_listed[li * n1 + lj] = True
+        if M.device_edges:
+            kept = ~was_listed[edges["pairs"][:, 0] * n1 + edges["pairs"][:, 1]] if len(edges["pairs"]) else np.zeros(0, dtype=bool)
+            parts = [dict(pairs=edges["pairs"][kept], t=edges["t"][kept], q=edges["q"][kept])] + ([fresh_edges] if fresh_edges is not None else [])
+            pr = np.concatenate([np.asarray(e["pairs"], dtype=np.int64).reshape(-1, 2) for e in parts])
+            order = np.lexsort((pr[:, 1], pr[:, 0]))             # loop order: row-major
+            edges = dict(pairs=pr[order], t=np.concatenate([np.asarray(e["t"]).reshape(-1, 3) for e in parts])[order],
+                         q=np.concatenate([np.asarray(e["q"]).reshape(-1, 4) for e in parts])[order])
+        else:
+            edges = None
+        if hyps is not None:
+            hyps = {k: v for k, v in hyps.items() if not was_listed[k[0] * n1 + k[1]]}
+            hyps.update(fresh_hyps or {})
+            hyps = dict(sorted(hyps.items()))
+        return result_of(b, M, timing, edges, hyps)
+
+    if L == 0:                                                   # nothing touched (or no pair at all): the stored results, re-indexed; no context is made
+        return remember({blocks[b]: merged(b) for b in range(nb)})
+    marks.append(time.perf_counter())
+    ctx = registration._context()
+    if num_solutions is not None and not hasattr(ctx, "mno_lc_tail_dev"):
+        raise ValueError("the context has no roman_mno_lc_tail_dev" + way)
+    if selfs and not hasattr(ctx, "shared_reduce_dev"):
+        raise ValueError("self blocks need a context with roman_shared_reduce_dev" + way)
+    if not hasattr(ctx, "session_gate_list_dev"):
+        raise ValueError("the context has no roman_session_gate_list_dev" + way)
+    if stacked and not hasattr(ctx, "session_stacked_sim_dev"):
+        raise ValueError("the context has no roman_session_stacked_sim_dev" + way)
+    if aabb_mode and not hasattr(ctx, "session_boxes_dev"):
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes: the context has no roman_session_boxes_dev" + way)
+    if aabb_mode and any(int(q.table.point_dim) != 3 for q in p):
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes, and pools of dim 2: their rows hold no z" + way)
+    dev = p[0].pool.device
+    wait_torch, up, ptr = _plumbing(torch, dev)
+    lv = [(r, hs) for r, hs in views if counts[r]]
+    cat = lambda get, width: np.concatenate([np.zeros((int(counts[r]),) + width) if hs is None else np.asarray(get(hs)).reshape((-1,) + width) for r, hs in lv])
+    any_gt = any(gt_poses[r] is not None for r, _ in lv)
+    pos_gt = None
+    if any_gt:
+        pos_gt = np.concatenate([np.full((int(counts[r]), 3), np.nan) if (hs is None or hs["pos_gt"] is None) else hs["pos_gt"] for r, hs in lv])
+    FLh, FRh = cat(lambda hs: hs["frames"][0], (16,)), cat(lambda hs: hs["frames"][1], (16,))
+    rows_of = {r: torch.from_numpy(keep[r].astype(np.int64)).to(dev) for r in {r for r, _ in lv}} if d or stacked else {}
+    t = dict(pos=up(cat(lambda hs: hs["pos"], (3,))), gt=up(pos_gt),
+             has=up(np.array([gt_poses[r] is not None for r, _ in views], dtype=np.int32)) if any_gt else None,
+             T_w=up(cat(lambda hs: hs["T_w"][0], (16,))), time=up(cat(lambda hs: hs["time"], ())), sub_off=up(sub_off), blocks=up(blk),
+             pair_off=up(pair_off), list=up(lst), desc=torch.cat([p[r].desc_dev[rows_of[r]] for r, _ in lv]).contiguous() if d else None)
+    live = sorted({r for r, _ in lv})
+    pool = _one_storage(torch, [p[r].pool for r in live])        # pools of ONE build (build_session_pools): the rows are there already
+    if pool is None:
+        pool = p[live[0]].pool if len(live) == 1 else torch.cat([p[r].pool for r in live], dim=0)
+    row0 = dict(zip(live, np.concatenate([[0], np.cumsum([int(p[r].pool.shape[0]) for r in live])]).astype(np.int64).tolist()))
+    sm_row = np.concatenate([row0[r] + p[r].offsets()[0] for r, _ in lv]).astype(np.int64)
+    sm_cnt = np.concatenate([p[r].offsets()[1] for r, _ in lv]).astype(np.int32)
+
+    # ---- pass 1 of the listed pairs on the device: one enqueue, one synchronisation, one read-back ----
+    f64, i32 = torch.float64, torch.int32
+    g = dict(dist=torch.empty(L, dtype=f64, device=dev), flags=torch.empty(L, dtype=i32, device=dev), yaw=torch.empty(L, dtype=f64, device=dev),
+             sim=torch.empty(L, dtype=f64, device=dev), T_ij=torch.empty((L, 16), dtype=f64, device=dev),
+             pairs=torch.empty((L, 2), dtype=i32, device=dev), T_ref=torch.empty((L, 16), dtype=f64, device=dev),
+             enable=torch.empty(L, dtype=i32, device=dev), todo_off=torch.zeros(nb + 1, dtype=i32, device=dev))
+    gp = grid_gate_params(sm_params.submap_radius, sm_io.skip_distance, d, sm_params.submap_descriptor_thresh if d else 0.0,
+                          False, sm_params.single_robot_lc_time_thresh)
+    gate_kw = dict(time_ptr=ptr(t["time"]), desc_ptr=ptr(t["desc"]), pos_gt_ptr=ptr(t["gt"]), has_gt_ptr=ptr(t["has"]))
+    if aabb_mode:
+        t.update(row0=up(sm_row), count=up(sm_cnt), T_oc=up(cat(lambda hs: hs["T_oc"], (16,))), box=torch.empty((len(sm_cnt), 6), dtype=f64, device=dev))
+    if stacked:
+        live_f = sorted(rows_of)
+        fdesc = p[live_f[0]].frame_desc_dev if len(live_f) == 1 else torch.cat([p[r].frame_desc_dev for r in live_f], dim=0)
+        fmask = torch.cat([p[r].frame_mask[rows_of[r]].reshape(-1) for r in live_f]).contiguous()
+        nfr = {r: int(p[r].frame_desc_dev.shape[0]) for r in live_f}
+        flo = dict(zip(live_f, np.concatenate([[0], np.cumsum([nfr[r] for r in live_f])]).astype(np.int64).tolist()))
+        mof = dict(zip(live_f, np.concatenate([[0], np.cumsum([int(counts[r]) * ((nfr[r] + 63) // 64) for r in live_f])]).astype(np.int64).tolist()))
+        frame_lo = np.array([flo.get(r, 0) for r, _ in views], dtype=np.int32)
+        frame_n = np.array([nfr.get(r, 0) for r, _ in views], dtype=np.int32)
+        mask_off = np.array([mof.get(r, 0) for r, _ in views], dtype=np.int64)
+        t.update(frame_lo=up(frame_lo), frame_n=up(frame_n), mask_off=up(mask_off), dense_sim=torch.empty(total, dtype=f64, device=dev))
+    wait_torch()                                             # the uploads are in place before the library's stream reads them
+    if aabb_mode:
+        ctx.session_boxes_dev(len(sm_cnt), int(pool.shape[1]), pool.data_ptr(), ptr(t["row0"]), ptr(t["count"]), ptr(t["T_oc"]), ptr(t["box"]))
+        gate_kw["box_ptr"] = ptr(t["box"])
+    if stacked:                                              # the similarity of the WHOLE blocks, then the gate that reads it at the listed pairs
+        gp.desc_thresh = float(sm_params.submap_descriptor_thresh)
+        ctx.session_stacked_sim_dev(int(fdesc.shape[1]), int(fdesc.shape[0]), ptr(fdesc), ptr(fmask), frame_lo, frame_n, mask_off, sub_off, blk, pair_off,
+                                    ptr(t["frame_lo"]), ptr(t["frame_n"]), ptr(t["mask_off"]), ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]),
+                                    t["dense_sim"].data_ptr())
+        gate_kw["sim_in_ptr"] = t["dense_sim"].data_ptr()
+    ctx.session_gate_list_dev(gp, sub_off, blk, pair_off, lst, ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]), ptr(t["list"]), ptr(t["pos"]), ptr(t["T_w"]),
+                              *[g[k].data_ptr() for k in ("dist", "flags", "yaw", "sim", "T_ij", "pairs", "T_ref", "enable", "todo_off")], **gate_kw)
+    ctx.sync()
+    todo_off = g["todo_off"].cpu().numpy().astype(np.int64)
+    B = int(todo_off[-1])
+    gpairs = g["pairs"][:B].cpu().numpy().astype(np.int64)
+    h = {k: g[k].cpu().numpy() for k in ("dist", "flags", "yaw", "sim", "T_ij")}
+    fresh, nearby, local, at = [], [], [], []                   # at[b]: the rows of fresh[b] that were registered
+    for b, (r, s) in enumerate(blocks):                          # a block's listed entries as a grid of one column, then pass 1 as ever
+        n1 = int(counts[s])
+        lo, hi = int(cut[b]), int(cut[b + 1])
+        lp_ = gpairs[todo_off[b]:todo_off[b + 1]] - np.array([sub_off[vblocks[b][0]], sub_off[vblocks[b][1]]], dtype=np.int64)
+        if hi == lo:                                             # nothing of this block is listed: it is carried over as it is
+            fresh.append(None); nearby.append(None); local.append(np.zeros((0, 2), dtype=np.int64)); at.append(np.zeros(0, dtype=np.int64))
+            continue
+        F = _GridResults(prm[b], sm_io, hi - lo, 1)
+        flags = h["flags"][lo:hi].reshape(-1, 1)
+        near, todo = (flags & _abi.ROMAN_GRID_NEARBY) != 0, (flags & _abi.ROMAN_GRID_TODO) != 0
+        F.pass1(h["dist"][lo:hi].reshape(-1, 1), near, (flags & _abi.ROMAN_GRID_SKIP) != 0, (flags & _abi.ROMAN_GRID_GATED) != 0,
+                h["yaw"][lo:hi].reshape(-1, 1), h["sim"][lo:hi].reshape(-1, 1), h["T_ij"][lo:hi].reshape(-1, 1, 4, 4))
+        k = np.nonzero(todo[:, 0])[0]                            # the listed entries that are TODO: the block's compact slots, in this order
+        if not np.array_equal(lp_, lst[lo:hi, 1:][k].astype(np.int64)):
+            raise _abi.RomanHipError(f"roman_session_gate_list_dev: the compact pair list of block {blocks[b]} is not its listed TODO pairs in list order")
+        fresh.append(F); nearby.append(near); local.append(lp_); at.append(k)
+    marks.append(time.perf_counter())
+    if B == 0:
+        return remember({blocks[b]: merged(b, fresh[b]) for b in range(nb)})
+
+    # ---- ONE batch over the pools: the problems in compact order, as in submap_align_session ----
+    prob = sm_row[gpairs[:, 0]], sm_cnt[gpairs[:, 0]], sm_row[gpairs[:, 1]], sm_cnt[gpairs[:, 1]]
+    kmax = int(max(1, np.max(np.minimum(prob[1], prob[3]))))
+    of_self = np.concatenate([np.full(int(todo_off[b + 1] - todo_off[b]), r == s, dtype=bool) for b, (r, s) in enumerate(blocks)])
+    sel = np.nonzero(of_self)[0]
+    if len(sel):
+        ids_dev = _one_storage(torch, [p[r].ids_dev for r in live])
+        if ids_dev is None or int(ids_dev.shape[0]) != int(pool.shape[0]):
+            ids_dev = torch.cat([p[r].ids_dev if p[r].ids_dev is not None else torch.zeros(int(p[r].pool.shape[0]), dtype=torch.int64, device=dev) for r in live])
+        pool, *prob = _drop_shared_over_pool(torch, ctx, pool, ids_dev, *prob, sel, wait_torch)
+    batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), tuple(pool.shape)), prob[0].astype(np.int64), prob[1].astype(np.int32), prob[2].astype(np.int64),
+                           prob[3].astype(np.int32), pair_index=gpairs)
+    res, per_pair = _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, up(FLh), up(FRh), wait_torch, num_solutions)
+    out = {}
+    acc = np.asarray(res.accepted, dtype=np.int64)
+    for b in range(nb):
+        lo, hi = int(todo_off[b]), int(todo_off[b + 1])
+        part = LoopClosureResult(res.assoc[lo:hi], res.T[lo:hi], res.status[lo:hi], res.stats[lo:hi], res.records[lo:hi],
+                                 acc[(acc >= lo) & (acc < hi)] - lo)
+        if num_solutions is not None:
+            part.hypotheses = res.hypotheses[lo:hi]
+        edges = Ms[b].empty_edges()
+        if hi > lo:
+            edges = _records_into_results(fresh[b], part, at[b], np.zeros(hi - lo, dtype=np.int64), nearby[b])
+            if edges is not None:                                # (row of the one-column grid -> the pair it stands for)
+                edges["pairs"] = lst[int(cut[b]):int(cut[b + 1]), 1:][edges["pairs"][:, 0]].astype(np.int64).reshape(-1, 2)
+        out[blocks[b]] = merged(b, fresh[b], fresh_edges=edges, fresh_hyps=_hypotheses_of(part, local[b][:, 0], local[b][:, 1]), timing=[per_pair] * (hi - lo))
+    return remember(out)
+
+
+# ---------------------------------------------------------------------------------------------
 # writers (row f3): the wire formats g2o_file_fusion / Kimera-RPGO consume
 # ---------------------------------------------------------------------------------------------
 def nearest_index(times, t):

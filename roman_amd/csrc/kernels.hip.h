@@ -8003,10 +8003,9 @@ __global__ void __launch_bounds__(SESSION_SCAN) k_session_count(int64_t total, c
     if (threadIdx.x == 0) counts[blockIdx.x] = count;
 }
 
-// counts[k] <- the TODO flags in front of workgroup k (in place); todo_off[b] <- the total for every b whose block starts at `total`
-__global__ void __launch_bounds__(SESSION_SCAN) k_session_scan(int nwg, int32_t* __restrict__ counts, SessionTab tab, int64_t total, int32_t* __restrict__ todo_off)
+// counts[k] <- the TODO flags in front of workgroup k (in place) -> their total: the scan of k_session_scan and k_session_list_scan
+__device__ __forceinline__ int session_scan_counts(int nwg, int32_t* __restrict__ counts, int* shi)
 {
-    __shared__ int shi[17];
     int carry = 0;
     for (int k0 = 0; k0 < nwg; k0 += SESSION_SCAN) {             // (uniform trip count: block_excl_scan has barriers)
         const int k = k0 + (int)threadIdx.x;
@@ -8016,6 +8015,14 @@ __global__ void __launch_bounds__(SESSION_SCAN) k_session_scan(int nwg, int32_t*
         if (k < nwg) counts[k] = carry + ex;
         carry += tot;
     }
+    return carry;
+}
+
+// the scan; todo_off[b] <- the total for every b whose block starts at `total`
+__global__ void __launch_bounds__(SESSION_SCAN) k_session_scan(int nwg, int32_t* __restrict__ counts, SessionTab tab, int64_t total, int32_t* __restrict__ todo_off)
+{
+    __shared__ int shi[17];
+    const int carry = session_scan_counts(nwg, counts, shi);
     for (int b = threadIdx.x; b <= tab.nb; b += SESSION_SCAN)
         if (tab.pair_off[b] == total) todo_off[b] = carry;
 }
@@ -8056,6 +8063,118 @@ __global__ void __launch_bounds__(256) k_session_fill(roman_grid_gate_params_t P
     const int64_t p = tab.pair_off[b] + (int64_t)(gi - tab.sub_off[r0]) * n1 + (gj - base1);
     T_ref[16 * s + e] = T_ij[16 * p + e];
     if (e == 0) enable[s] = (tab.blocks[4 * b + 2] && fabs(time[gi] - time[gj]) < P.lc_time_thresh) ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// pass 1 of a session over an explicit PAIR LIST (roman_session_gate_list*): the tables and per-submap arrays of
+// roman_session_gate*, and `list` int32[L][3] — (block, block-local row i, block-local column j), strictly ascending.  The outputs
+// are per LIST ENTRY (L of each), entry l bit for bit what k_session_gate writes at pair_off[b] + i * n1 + j.
+//   k_grid_norms           over all S submaps, as for the whole grids;
+//   k_session_gate_list    a wave per GRID_TJ consecutive list entries.  The entries may lie in different rows and blocks, so
+//                          nothing of a row is shared across them: each sum walks its own two descriptors, lane l the components
+//                          l, l + 64, ... in k_session_gate's order, and wave_sum_all adds the 64 partial sums — the bits of the
+//                          whole-grid kernels.  The entries are read through wave-uniform (scalar) loads; lane t then finishes
+//                          entry 4 w + t through grid_pair() with the entry's index as its place in the outputs.  With SIM_IN the
+//                          similarity is read at the pair's DENSE position of sim_in and copied to sim[l];
+//   k_session_count        the TODO flags of 1024 consecutive entries, as it stands;
+//   k_session_list_scan    k_session_scan with the blocks behind the last listed one in place of those that start at `total`;
+//   k_session_list_scatter recounts, writes (gi, gj) of every TODO entry at its rank and its entry index into `src`; the thread of
+//                          the first entry of a block writes that block's todo_off and that of the blocks without an entry in
+//                          front of it — the block of an entry is list[l][0], no search;
+//   k_session_list_fill    k_session_fill with the source entry from `src` instead of the dense position.
+// No atomics, no spin-waits, no cooperative launch: two runs agree bit for bit.
+// ---------------------------------------------------------------------------------------------
+template <bool SIM_IN, bool AABB>
+__global__ void __launch_bounds__(256) k_session_gate_list(roman_grid_gate_params_t P, SessionTab tab, int L, const int32_t* __restrict__ list,
+                                                           GridSide s, const double* __restrict__ norm, const double* __restrict__ sim_in, GridOut out)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t l0 = w * GRID_TJ;
+    if (l0 >= L) return;                                         // (wave-uniform, as everything up to the lanes' entries)
+    const int d = SIM_IN ? 0 : P.desc_dim;
+    double acc[GRID_TJ];
+#pragma unroll
+    for (int t = 0; t < GRID_TJ; ++t) acc[t] = 0.0;
+    if (d > 0) {
+        const double* va[GRID_TJ];
+        const double* vb[GRID_TJ];
+#pragma unroll
+        for (int t = 0; t < GRID_TJ; ++t) {                      // (the last wave's tail repeats the last entry: in bounds, never stored)
+            const int32_t* e = list + 3 * min(l0 + t, (int64_t)L - 1);
+            const int b = e[0];
+            va[t] = s.desc + (int64_t)(tab.sub_off[tab.blocks[4 * b]] + e[1]) * d;
+            vb[t] = s.desc + (int64_t)(tab.sub_off[tab.blocks[4 * b + 1]] + e[2]) * d;
+        }
+        for (int k = lane; k < d; k += 64) {
+#pragma unroll
+            for (int t = 0; t < GRID_TJ; ++t) acc[t] += va[t][k] * vb[t][k];
+        }
+#pragma unroll
+        for (int t = 0; t < GRID_TJ; ++t) acc[t] = wave_sum_all(acc[t]);
+    }
+    const int64_t l = l0 + lane;
+    if (lane >= GRID_TJ || l >= L) return;
+    double dot = acc[0];
+#pragma unroll
+    for (int t = 1; t < GRID_TJ; ++t) dot = (lane == t) ? acc[t] : dot;
+    const int b = list[3 * l], i = list[3 * l + 1], j = list[3 * l + 2];
+    const int r0 = tab.blocks[4 * b], r1 = tab.blocks[4 * b + 1];
+    const int base1 = tab.sub_off[r1], n1 = tab.sub_off[r1 + 1] - base1;
+    const int64_t gi = tab.sub_off[r0] + i, gj = base1 + j;
+    const bool gt = s.pos_gt != nullptr && tab.has_gt[r0] != 0 && tab.has_gt[r1] != 0;      // [REF :96-99]
+    const double np_ = (!SIM_IN && d > 0) ? norm[gi] * norm[gj] : 0.0;
+    GridOut o = out;
+    if (SIM_IN) {                                                // grid_pair reads o.sim[l]: the pair's dense similarity, and sim[l] gets its copy
+        const double* at = sim_in + (tab.pair_off[b] + (int64_t)i * n1 + j);
+        out.sim[l] = *at;
+        o.sim = const_cast<double*>(at) - l;
+    }
+    grid_pair<SIM_IN, AABB>(P, s, s, gi, gj, gt, d, dot, np_, l, o);
+}
+
+// todo_off[b] <- the total for every block behind the last listed one, and for nb
+__global__ void __launch_bounds__(SESSION_SCAN) k_session_list_scan(int nwg, int32_t* __restrict__ counts, int nb, int L, const int32_t* __restrict__ list,
+                                                                    int32_t* __restrict__ todo_off)
+{
+    __shared__ int shi[17];
+    const int carry = session_scan_counts(nwg, counts, shi);
+    for (int b = list[3 * ((int64_t)L - 1)] + 1 + (int)threadIdx.x; b <= nb; b += SESSION_SCAN) todo_off[b] = carry;
+}
+
+__global__ void __launch_bounds__(SESSION_SCAN) k_session_list_scatter(int L, const int32_t* __restrict__ flags, const int32_t* __restrict__ bases, SessionTab tab,
+                                                                       const int32_t* __restrict__ list, int32_t* __restrict__ pairs, int32_t* __restrict__ src,
+                                                                       int32_t* __restrict__ todo_off)
+{
+    __shared__ int sh[SESSION_SCAN / 64];
+    const int64_t l = (int64_t)blockIdx.x * SESSION_SCAN + threadIdx.x;
+    bool mine; int rank, count;
+    session_rank(flags, L, l, sh, mine, rank, count);
+    if (l >= L) return;
+    const int pos = bases[blockIdx.x] + rank;
+    const int b = list[3 * l], before = l > 0 ? list[3 * (l - 1)] : -1;
+    for (int k = b; k > before; --k) todo_off[k] = pos;         // the block's first entry: its rank is the block's todo_off, and that of
+    if (!mine) return;                                           // the blocks without an entry in front of it
+    pairs[2 * (int64_t)pos] = tab.sub_off[tab.blocks[4 * b]] + list[3 * l + 1];
+    pairs[2 * (int64_t)pos + 1] = tab.sub_off[tab.blocks[4 * b + 1]] + list[3 * l + 2];
+    src[pos] = (int32_t)l;
+}
+
+__global__ void __launch_bounds__(256) k_session_list_fill(roman_grid_gate_params_t P, SessionTab tab, const int32_t* __restrict__ todo_off,
+                                                           const int32_t* __restrict__ pairs, const int32_t* __restrict__ src, const int32_t* __restrict__ list,
+                                                           const double* __restrict__ T_ij, const double* __restrict__ time,
+                                                           double* __restrict__ T_ref, int32_t* __restrict__ enable)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t s = g >> 4;
+    const int e = (int)(g & 15);
+    if (s >= todo_off[tab.nb]) return;
+    const int64_t l = src[s];
+    T_ref[16 * s + e] = T_ij[16 * l + e];
+    if (e == 0) {
+        const int gi = pairs[2 * s], gj = pairs[2 * s + 1];
+        enable[s] = (tab.blocks[4 * list[3 * l] + 2] && fabs(time[gi] - time[gj]) < P.lc_time_thresh) ? 0 : 1;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

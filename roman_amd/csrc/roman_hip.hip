@@ -3672,6 +3672,152 @@ int roman_session_gate_aabb(roman_ctx_t* c, const roman_grid_gate_params_t* gpar
     return session_gate_host(c, gparams, g);
 }
 
+// --- pass 1 of a session over an explicit pair list ---------------------------------------------------------------
+// SessionGateArgs as the whole-grid calls fill them (no tile_off: the list is the work), and the list: on the device (host forms:
+// NULL), in host memory (what is checked), and the similarity of every pair of every block where it is given.
+struct SessionListArgs {
+    SessionGateArgs g;
+    int32_t L; const int32_t* list; const int32_t* list_host;
+    const double* sim_in;
+};
+
+static auto session_gate_list_kernel(bool sim_in, bool aabb)
+{
+    return sim_in ? (aabb ? k_session_gate_list<true, true> : k_session_gate_list<true, false>)
+                  : (aabb ? k_session_gate_list<false, true> : k_session_gate_list<false, false>);
+}
+
+// the tables first (session_tables_check, as the whole-grid calls judge them), then the list on its host copy
+static int session_gate_list_check(roman_ctx* c, const roman_grid_gate_params_t* P, const SessionListArgs& a)
+{
+    const SessionGateArgs& g = a.g;
+    const int32_t R = g.R, nb = g.tab.nb, L = a.L;
+    { int rc = gate_params_check(c, P, g.sim_in, g.aabb, "roman_session_gate_list* with box", R < 0 || nb < 0 || L < 0, "R < 0, nb < 0 or L < 0"); if (rc) return rc; }
+    if (!g.sub_off || !g.pair_off || !g.todo_off || (nb > 0 && !g.blocks)) return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / todo_off is NULL");
+    bool self = false;
+    int64_t total = 0, tiles = 0;
+    { int rc = session_tables_check(c, R, g.sub_off, nb, g.blocks, g.pair_off, nullptr, &total, &tiles, &self); if (rc) return rc; }
+    if (L == 0) return ROMAN_OK;
+    if ((int64_t)L > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "L = %d pairs: L * 16 exceeds the index width", L);
+    if (!a.list_host) return fail(c, ROMAN_E_INVALID, "list is NULL with L=%d", L);
+    for (int64_t l = 0; l < L; ++l) {
+        const int32_t* e = a.list_host + 3 * l;
+        if (e[0] < 0 || e[0] >= nb) return fail(c, ROMAN_E_INVALID, "list entry %lld names block %d outside [0, %d)", (long long)l, e[0], nb);
+        const int32_t r0 = g.blocks[4 * e[0]], r1 = g.blocks[4 * e[0] + 1];
+        const int32_t n0 = g.sub_off[r0 + 1] - g.sub_off[r0], n1 = g.sub_off[r1 + 1] - g.sub_off[r1];
+        if (e[1] < 0 || e[1] >= n0 || e[2] < 0 || e[2] >= n1)
+            return fail(c, ROMAN_E_INVALID, "list entry %lld: pair (%d, %d) lies outside the %d x %d grid of block %d", (long long)l, e[1], e[2], n0, n1, e[0]);
+        if (l > 0 && !std::lexicographical_compare(e - 3, e, e, e + 3))
+            return fail(c, ROMAN_E_INVALID, "the list is not strictly ascending in (block, i, j) at entry %lld", (long long)l);
+    }
+    if (P->desc_dim > 0 && !g.s.desc) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
+    if (!g.s.pos || !g.s.T_w) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
+    if (g.s.pos_gt && !g.tab.has_gt) return fail(c, ROMAN_E_INVALID, "has_gt is NULL with pos_gt");
+    if (self && !g.s.time) return fail(c, ROMAN_E_INVALID, "time is NULL with a self_lc block");
+    if (!g.out.dist || !g.out.flags || !g.out.yaw_deg || !g.out.sim || !g.out.T_ij || !g.pairs || !g.T_ref || !g.enable) return fail(c, ROMAN_E_INVALID, "NULL output pointer");
+    return ROMAN_OK;
+}
+
+// the device-pointer list gate
+static int session_gate_list_dev(roman_ctx* c, const roman_grid_gate_params_t* gparams, const SessionListArgs& a)
+{
+    const SessionGateArgs& g = a.g;
+    const SessionTab& tab = g.tab;
+    // (the arguments are judged first — on host memory only, a NULL context included)
+    if (!tab.sub_off || !tab.pair_off || (tab.nb > 0 && !tab.blocks) || (a.L > 0 && !a.list)) return fail(c, ROMAN_E_INVALID, "a table or the list is NULL on the device");
+    int rc = session_gate_list_check(c, gparams, a);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    const int L = a.L, S = g.sub_off[g.R];
+    if (L == 0) { HIPCHK(c, hipMemsetAsync(g.todo_off, 0, sizeof(int32_t) * (size_t)(tab.nb + 1), stream)); return ROMAN_OK; }
+    const int d = g.sim_in ? 0 : gparams->desc_dim;
+    const int nwg = (L + SESSION_SCAN - 1) / SESSION_SCAN;
+    HIPCHK(c, c->ggNorm.ensure(sizeof(double) * (size_t)S));                    // scratch first: a failure leaves nothing enqueued
+    HIPCHK(c, c->sgCount.ensure(sizeof(int32_t) * ((size_t)nwg + (size_t)L)));  // the workgroup counts, then the source entry of every compact slot
+    double* dNorm = c->ggNorm.as<double>();
+    int32_t* dCount = c->sgCount.as<int32_t>();
+    int32_t* dSrc = dCount + nwg;
+    const int waves = (L + GRID_TJ - 1) / GRID_TJ;
+    if (d > 0) hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, stream, S, 0, d, g.s.desc, (const double*)nullptr, dNorm);
+    hipLaunchKernelGGL(session_gate_list_kernel(g.sim_in, g.aabb), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, *gparams, tab, L, a.list, g.s,
+                       (const double*)dNorm, a.sim_in, g.out);
+    hipLaunchKernelGGL(k_session_count, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, (int64_t)L, (const int32_t*)g.out.flags, dCount);
+    hipLaunchKernelGGL(k_session_list_scan, dim3(1), dim3(SESSION_SCAN), 0, stream, nwg, dCount, tab.nb, L, a.list, g.todo_off);
+    hipLaunchKernelGGL(k_session_list_scatter, dim3((unsigned)nwg), dim3(SESSION_SCAN), 0, stream, L, (const int32_t*)g.out.flags, (const int32_t*)dCount, tab, a.list,
+                       g.pairs, dSrc, g.todo_off);
+    hipLaunchKernelGGL(k_session_list_fill, dim3((unsigned)(((int64_t)L * 16 + 255) / 256)), dim3(256), 0, stream, *gparams, tab, (const int32_t*)g.todo_off,
+                       (const int32_t*)g.pairs, (const int32_t*)dSrc, a.list, (const double*)g.out.T_ij, g.s.time, g.T_ref, g.enable);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_session_gate_list_dev(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off, const int32_t* sub_off_host,
+                                const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                                int32_t nb, const int32_t* blocks, const int32_t* blocks_host, const int64_t* pair_off, const int64_t* pair_off_host,
+                                int32_t L, const int32_t* list, const int32_t* list_host, const double* box, const double* sim_in,
+                                double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                                int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
+{
+    SessionListArgs a{};
+    SessionGateArgs& g = a.g;
+    g.R = R; g.tab.nb = nb; g.tab.sub_off = sub_off; g.tab.blocks = blocks; g.tab.pair_off = pair_off; g.tab.has_gt = has_gt;
+    g.sub_off = sub_off_host; g.blocks = blocks_host; g.pair_off = pair_off_host;
+    g.s.pos = pos; g.s.pos_gt = pos_gt; g.s.T_w = T_w; g.s.time = time; g.s.desc = sim_in ? nullptr : desc; g.s.box = box; g.aabb = box != nullptr;
+    g.out.dist = dist; g.out.flags = flags; g.out.yaw_deg = yaw_deg; g.out.sim = sim; g.out.T_ij = T_ij;
+    g.pairs = pairs; g.T_ref = T_ref; g.enable = enable; g.todo_off = todo_off; g.sim_in = sim_in != nullptr;
+    a.L = L; a.list = list; a.list_host = list_host; a.sim_in = sim_in;
+    return session_gate_list_dev(c, gparams, a);
+}
+
+// the host-pointer list gate: everything goes up, sim_in included, and every output comes back with one synchronisation
+int roman_session_gate_list(roman_ctx_t* c, const roman_grid_gate_params_t* gparams, int32_t R, const int32_t* sub_off,
+                            const double* pos, const double* pos_gt, const int32_t* has_gt, const double* T_w, const double* time, const double* desc,
+                            int32_t nb, const int32_t* blocks, const int64_t* pair_off, int32_t L, const int32_t* list, const double* box, const double* sim_in,
+                            double* dist, int32_t* flags, double* yaw_deg, double* sim, double* T_ij,
+                            int32_t* pairs, double* T_ref, int32_t* enable, int32_t* todo_off)
+{
+    SessionListArgs h{};
+    h.g.R = R; h.g.tab.nb = nb; h.g.tab.has_gt = has_gt; h.g.sub_off = sub_off; h.g.blocks = blocks; h.g.pair_off = pair_off;
+    h.g.s.pos = pos; h.g.s.pos_gt = pos_gt; h.g.s.T_w = T_w; h.g.s.time = time; h.g.s.desc = sim_in ? nullptr : desc; h.g.s.box = box; h.g.aabb = box != nullptr;
+    h.g.out.dist = dist; h.g.out.flags = flags; h.g.out.yaw_deg = yaw_deg; h.g.out.sim = sim; h.g.out.T_ij = T_ij;
+    h.g.pairs = pairs; h.g.T_ref = T_ref; h.g.enable = enable; h.g.todo_off = todo_off; h.g.sim_in = sim_in != nullptr;
+    h.L = L; h.list_host = list; h.sim_in = sim_in;
+    int rc = session_gate_list_check(c, gparams, h);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    const size_t nR = (size_t)R, nB = (size_t)nb, B = (size_t)pair_off[nb], nS = (size_t)sub_off[R], nL = (size_t)L;
+    if (L == 0) { std::fill(todo_off, todo_off + nB + 1, 0); return ROMAN_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const size_t d = sim_in ? 0 : (size_t)gparams->desc_dim;
+    HostMirror m(c);
+    const auto dSub = m.in(sub_off, 4 * (nR + 1)), dBlk = m.in(blocks, 16 * nB), dList = m.in(list, 12 * nL);
+    const auto dPo = m.in(pair_off, 8 * (nB + 1));
+    const auto dPos = m.in(pos, 24 * nS), dGt = m.in(pos_gt, pos_gt ? 24 * nS : 0);
+    const auto dHas = m.in(has_gt, pos_gt ? 4 * nR : 0);
+    const auto dTw = m.in(T_w, 128 * nS), dTime = m.in(time, time ? 8 * nS : 0), dDesc = m.in(h.g.s.desc, h.g.s.desc ? 8 * d * nS : 0);
+    const auto dBox = m.in(box, box ? 48 * nS : 0), dSin = m.in(sim_in, sim_in ? 8 * B : 0);
+    const auto dDist = m.out(dist, 8 * nL), dYaw = m.out(yaw_deg, 8 * nL), dSim = m.out(sim, 8 * nL), dTij = m.out(T_ij, 128 * nL);
+    const auto dFlags = m.out(flags, 4 * nL);
+    // the compact outputs are inout: the slots beyond todo_off[nb] come back as they were
+    const auto dTref = m.inout(T_ref, 128 * nL);
+    const auto dPairs = m.inout(pairs, 8 * nL), dEn = m.inout(enable, 4 * nL), dOff = m.out(todo_off, 4 * (nB + 1));
+    rc = m.upload();
+    if (rc) return rc;
+    SessionListArgs a = h;                                       // the same call on the mirror; the host tables stay the caller's
+    SessionGateArgs& g = a.g;
+    g.tab.sub_off = dSub.dev(); g.tab.blocks = dBlk.dev(); g.tab.pair_off = dPo.dev(); g.tab.has_gt = dHas.dev();
+    g.s.pos = dPos.dev(); g.s.pos_gt = dGt.dev(); g.s.T_w = dTw.dev(); g.s.time = dTime.dev(); g.s.desc = dDesc.dev(); g.s.box = dBox.dev();
+    g.out.dist = dDist.dev(); g.out.flags = dFlags.dev(); g.out.yaw_deg = dYaw.dev(); g.out.sim = dSim.dev(); g.out.T_ij = dTij.dev();
+    g.pairs = dPairs.dev(); g.T_ref = dTref.dev(); g.enable = dEn.dev(); g.todo_off = dOff.dev();
+    a.list = dList.dev(); a.sim_in = dSin.dev();
+    rc = session_gate_list_dev(c, gparams, a);
+    if (rc) return rc;
+    return m.download();
+}
+
 // --- frame descriptors of the submaps of a pool ([REF roman/map/map.py:210-242], [REF :155-162]) ------------------
 static int frame_select_check(roman_ctx* c, const roman_frame_select_params_t* P, int32_t S, int32_t cap, const void* count, const void* src,
                               int32_t N, const void* seg_times, int32_t Nf, const void* frame_times, const void* frame_pos, int32_t d,

@@ -297,6 +297,36 @@ def session_tables(counts, blocks):
     return sub_off, blk, pair_off, tile_off
 
 
+def session_pair_list(counts, blocks, touched):
+    """The pair list of roman_session_gate_list from the robots' submap counts, the block list [(r0, r1, ...), ...] and one bool
+    array per robot: every pair (i, j) of every block with submap i of r0 touched or submap j of r1 touched -> int32 (L, 3) rows
+    (b, i, j), strictly ascending.  touched[r] None: none of robot r's submaps."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    flag = [np.zeros(int(n), dtype=bool) if t is None else np.asarray(t, dtype=bool).reshape(-1) for n, t in zip(counts, touched)]
+    if len(flag) != len(counts) or any(len(f) != n for f, n in zip(flag, counts)):
+        raise ValueError("touched must hold one flag per submap of every robot")
+    rows = []
+    for b, blk in enumerate(blocks):
+        i, j = np.nonzero(flag[int(blk[0])][:, None] | flag[int(blk[1])][None, :])       # (row-major: ascending in (i, j))
+        rows.append(np.stack([np.full(len(i), b, dtype=np.int64), i, j], axis=1))
+    return (np.concatenate(rows) if rows else np.zeros((0, 3))).astype(np.int32).reshape(-1, 3)
+
+
+@dataclass
+class SessionGateListResult:
+    """Results of one roman_session_gate_list call: entry l belongs to the pair list[l] = (block, i, j)."""
+    list: np.ndarray       # (L, 3) int32
+    dist: np.ndarray       # (L,) float64
+    flags: np.ndarray      # (L,) int32 ROMAN_GRID_* bits
+    yaw_deg: np.ndarray    # (L,) float64, NaN where the pair is not nearby
+    sim: np.ndarray        # (L,) float64 (+inf without descriptors; with sim_in the pair's entry of it)
+    T_ij: np.ndarray       # (L, 4, 4) float64
+    pairs: np.ndarray      # (L, 2) int32: the first todo_off[-1] rows are the TODO pairs as GLOBAL submap indices; the others as handed in
+    T_ref: np.ndarray      # (L, 4, 4) float64, likewise
+    enable: np.ndarray     # (L,) int32, likewise
+    todo_off: np.ndarray   # (nb + 1,) int32: block b's TODO pairs are the compact slots [todo_off[b], todo_off[b + 1])
+
+
 @dataclass
 class FrameSelectResult:
     """Results of one roman_frame_select call over the S submaps of a pool and the Nf frames of its map."""
@@ -946,6 +976,68 @@ class Context:
             raise ValueError("session_gate_aabb_dev needs the boxes")
         self.session_gate_dev(gparams, sub_off, blocks, pair_off, tile_off, sub_off_ptr, blocks_ptr, pair_off_ptr, tile_off_ptr, pos_ptr, T_w_ptr,
                               dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr, pairs_ptr, T_ref_ptr, enable_ptr, todo_off_ptr, box_ptr=box_ptr, **kw)
+
+    # ------------------------------------------------------------------ pass 1 of a session over an explicit pair list
+    @staticmethod
+    def _session_list_tables(sub_off, blocks, pair_off, pair_list):
+        sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
+        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); pair_list = np.ascontiguousarray(pair_list, dtype=np.int32).reshape(-1, 3)
+        R, nb = len(sub_off) - 1, len(blocks)
+        if R < 0 or len(pair_off) != nb + 1:
+            raise ValueError("sub_off must hold R + 1 entries, pair_off nb + 1")
+        return sub_off, blocks, pair_off, pair_list, R, nb
+
+    def session_gate_list(self, gparams, sub_off, blocks, pair_off, pair_list, pos, T_w, time=None, desc=None, pos_gt=None, has_gt=None,
+                          pairs=None, T_ref=None, enable=None, sim_in=None, box=None):
+        """Host-pointer pass 1 over a pair list (roman_session_gate_list): the tables as session_tables() gives them (without
+        tile_off), pair_list (L, 3) rows (block, i, j) as session_pair_list() cuts them — both passed as they are: the library
+        checks them; the per-submap arrays as session_gate() takes them.  sim_in (pair_off[nb],): the similarity of every pair
+        of every block, dense; box (S, 6): the bounding-box gate.  The compact outputs may be handed in.  -> SessionGateListResult."""
+        sub_off, blocks, pair_off, pair_list, R, nb = self._session_list_tables(sub_off, blocks, pair_off, pair_list)
+        pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
+        T_w = _f64(T_w).reshape(-1, 16)
+        time = None if time is None else _f64(time).reshape(-1)
+        desc = None if desc is None or sim_in is not None else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
+        pos_gt = None if pos_gt is None else _f64(pos_gt).reshape(-1, 3)
+        has_gt = None if has_gt is None else np.ascontiguousarray(has_gt, dtype=np.int32).reshape(-1)
+        if T_w.shape[0] != S or (time is not None and time.shape[0] != S) or (pos_gt is not None and pos_gt.shape[0] != S) or \
+                (has_gt is not None and has_gt.shape[0] != R) or int(sub_off[-1]) != S:
+            raise ValueError("the per-submap arrays must hold one entry per submap of the session (sub_off[R]), has_gt one per robot")
+        if desc is not None and gparams.desc_dim > 0 and desc.shape[1] != gparams.desc_dim:
+            raise ValueError("desc must be (S, desc_dim)")
+        if sim_in is not None:
+            sim_in = _f64(sim_in).reshape(-1)
+            if sim_in.shape[0] != max(int(pair_off[-1]), 0):
+                raise ValueError("sim_in must hold pair_off[nb] entries")
+        if box is not None:
+            box = _f64(box).reshape(-1, 6)
+            if box.shape[0] != S:
+                raise ValueError("box must hold one row per submap of the session")
+        L = len(pair_list)
+        pairs = _given(pairs, (L, 2), np.int32, -1); T_ref = _given(T_ref, (L, 4, 4), np.float64, np.nan); enable = _given(enable, (L,), np.int32, -1)
+        dist = np.zeros(L); flags = np.zeros(L, dtype=np.int32); yaw = np.zeros(L); sim = np.zeros(L); T_ij = np.zeros((L, 4, 4))
+        todo_off = np.zeros(nb + 1, dtype=np.int32)
+        self._generation += 1
+        rc = self._lib.roman_session_gate_list(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
+                                               _ptr(desc), nb, _ptr(blocks), _ptr(pair_off), L, _ptr(pair_list), _ptr(box), _ptr(sim_in), _ptr(dist), _ptr(flags),
+                                               _ptr(yaw), _ptr(sim), _ptr(T_ij), _ptr(pairs), _ptr(T_ref), _ptr(enable), _ptr(todo_off))
+        self._check(rc, "roman_session_gate_list")
+        return SessionGateListResult(pair_list, dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, todo_off)
+
+    def session_gate_list_dev(self, gparams, sub_off, blocks, pair_off, pair_list, sub_off_ptr, blocks_ptr, pair_off_ptr, list_ptr, pos_ptr, T_w_ptr,
+                              dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr, pairs_ptr, T_ref_ptr, enable_ptr, todo_off_ptr,
+                              time_ptr=None, desc_ptr=None, pos_gt_ptr=None, has_gt_ptr=None, sim_in_ptr=None, box_ptr=None):
+        """Device-pointer pass 1 over a pair list (roman_session_gate_list_dev): the tables and the list as host arrays (the library
+        validates these) AND as device addresses of the same values; every other pointer a device address.  The dense outputs
+        hold L entries, in list order; the compact ones have capacity L.  sim_in_ptr: the similarity of every pair of every
+        block at its dense position (what session_stacked_sim_dev writes); box_ptr: the bounding-box gate.  A pure enqueue on
+        the context's stream; complete after sync()."""
+        sub_off, blocks, pair_off, pair_list, R, nb = self._session_list_tables(sub_off, blocks, pair_off, pair_list)
+        rc = self._lib.roman_session_gate_list_dev(self._h, C.byref(gparams), R, _vp(sub_off_ptr), _ptr(sub_off), _vp(pos_ptr), _vp(pos_gt_ptr), _vp(has_gt_ptr),
+                                                   _vp(T_w_ptr), _vp(time_ptr), _vp(desc_ptr), nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off),
+                                                   len(pair_list), _vp(list_ptr), _ptr(pair_list), _vp(box_ptr), _vp(sim_in_ptr), _vp(dist_ptr), _vp(flags_ptr),
+                                                   _vp(yaw_deg_ptr), _vp(sim_ptr), _vp(T_ij_ptr), _vp(pairs_ptr), _vp(T_ref_ptr), _vp(enable_ptr), _vp(todo_off_ptr))
+        self._check(rc, "roman_session_gate_list_dev")
 
     # ------------------------------------------------------------------ the stacked similarity of every block of a session (DESIGN.md §4.15)
     @staticmethod
