@@ -29,6 +29,7 @@ import json
 import pickle
 import time
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -735,7 +736,10 @@ def _pool_side_host(pool, gt_poses, gt_available, reads, aabb_mode):
 
 # ---------------------------------------------------------------------------------------------
 # the stages submap_align_pools and submap_align_session share: refusals, device plumbing, the read-back of pass 1, the
-# shared-segment removal and the registration over resident rows
+# shared-segment removal and the registration over resident rows.  submap_align_session and submap_align_session_update share
+# every stage of a session call but the gate and its read-back, further down: _session_setup (arguments and early refusals),
+# _session_views, _session_block_results, _session_context (the refusals that ask the context), _session_uploads, _session_pool,
+# _session_pass1_front (boxes and stacked similarity in front of the gate) and _session_register (all blocks in one batch)
 # ---------------------------------------------------------------------------------------------
 def _no_device(registration, p):
     """No context of the caller's and host-tensor pools: nothing a kernel could run on."""
@@ -1116,6 +1120,235 @@ def _one_storage(torch, parts):
     return first.as_strided(shape, stride, first.storage_offset())
 
 
+def _session_setup(sm_params, pools, robot_pairs, sm_io, registration, gt_poses, num_solutions):
+    """The arguments of a session call made whole, and every refusal that needs no context, in submap_align_session's order
+    -> the record every later stage reads: the arguments (sm_io and registration defaulted), p (the pools), R, gt_poses (R
+    entries), blocks, aabb_mode, mode, stacked, d (the gate's descriptor length), selfs (the robots with a self block), keep and
+    counts (per robot: the pool indices of its non-empty submaps, and how many) and way (the tail of every refusal)."""
+    sm_io = sm_io or SubmapAlignIO()
+    registration = registration or sm_params.get_object_registration()
+    way = " (not in the session call: use submap_align_pools per robot pair)"
+    p = list(pools)
+    R = len(p)
+    gt_poses = [None] * R if gt_poses is None else list(gt_poses)
+    blocks = [(r, s) for r in range(R) for s in range(r, R)] if robot_pairs is None else [(int(r), int(s)) for r, s in robot_pairs]
+    if len(gt_poses) != R:
+        raise ValueError("gt_poses must hold one entry per pool" + way)
+    if any(not (0 <= r < R and 0 <= s < R) for r, s in blocks) or len(set(blocks)) != len(blocks):
+        raise ValueError("robot_pairs must name pools by index, each pair once" + way)
+    if num_solutions is not None:                            # (submap_align_pools' three for K hypotheses per pair, DESIGN.md §4.18)
+        _mno_refusals(registration, p, blocks, num_solutions, way)
+    if isinstance(registration, RansacReg) and R:            # (submap_align_pools' four, in its order: in front of everything that makes a HIP context)
+        _ransac_refusals(registration, p, way)
+    if _device_prefilter(registration) and R:                # (and its four for a device-prefilter plugin)
+        _prune_refusals(registration, p, way)
+    aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
+    if aabb_mode and _no_device(registration, p):            # (the boxes are reduced from the resident rows: as for a RansacReg, host rows need a context of the caller's)
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes of the resident rows: the registration has no context set "
+                         "and the pools are host tensors: no device to run on" + way)
+    mode = sm_params.submap_descriptor
+    _descriptor_refusals(registration, p, mode, way)
+    if R and any(int(q.pool.shape[1]) != int(p[0].pool.shape[1]) for q in p):
+        raise ValueError("the pools have different row widths" + way)
+    d = _descriptor_dim(p, mode, "the pools", way)
+    selfs = sorted({r for r, s in blocks if r == s})
+    if any(p[r].ids_dev is None for r in selfs):
+        raise ValueError("a self block drops the segments both submaps hold: its pool must have kept its ids on the device (SubmapPool.ids_dev, "
+                         "as build_submap_pool leaves it)" + way)
+    keep = [q.nonempty for q in p]
+    return SimpleNamespace(sm_params=sm_params, sm_io=sm_io, registration=registration, num_solutions=num_solutions, p=p, R=R, gt_poses=gt_poses,
+                           blocks=blocks, aabb_mode=aabb_mode, mode=mode, stacked=mode == 'stacked_frame_descriptors', d=d, selfs=selfs, keep=keep,
+                           counts=np.array([len(k) for k in keep], dtype=np.int64), way=way)
+
+
+def _session_views(s):
+    """Per robot (O(S), host): the block submap_align_pools runs per side, with the reads of the pair loop it would see.  A pose
+    read `n` times (n: the partner's submaps) usually sits at a fixed point after a read or two, and the robot then has ONE set of
+    arrays for all its blocks; where flattening a pose alternates between two neighbouring values, its reference transform
+    depends on n, and the robot enters the tables once per distinct outcome (a "view": same pool rows, own T_w and edge frames,
+    own T_oc in bounding-box mode).  -> views [(robot, host arrays or None)], vblocks (per block: its two views), vcount (per
+    view: its submaps) and runtime.session_tables over them (sub_off, blocks, pair_off, tile_off)."""
+    from ..runtime import session_tables
+    p, blocks, counts = s.p, s.blocks, s.counts
+    views, view_of = [], {}
+    for r in range(s.R):
+        reads = sorted({int(counts[b if a == r else a]) for a, b in blocks if r in (a, b)})
+        mine = []
+        live_reads = [n for n in reads if n > 0] if counts[r] else []       # (an empty block: the robot only needs a place in the tables)
+        all_ = _pool_side_host(p[r], s.gt_poses[r], s.gt_poses[r] is not None, live_reads, s.aabb_mode) if live_reads else None
+        for k, n in enumerate(live_reads):
+            hs = dict(all_, T_w=[all_["T_w"][k]], frames=all_["frames"][k])
+            key = hs["T_w"][0].tobytes() + hs["frames"][0].tobytes() + hs["frames"][1].tobytes() + (hs["T_oc"].tobytes() if s.aabb_mode else b"")
+            same = [v for v, kk in mine if kk == key]
+            if not same:
+                views.append((r, hs)); mine.append((len(views) - 1, key))
+            view_of[(r, n)] = same[0] if same else len(views) - 1
+        if reads and not mine:                               # only in empty blocks: zeros stand in (never read)
+            views.append((r, None)); mine.append((len(views) - 1, b""))
+        for n in reads:
+            view_of.setdefault((r, n), mine[0][0])
+    vcount = np.array([counts[r] for r, _ in views], dtype=np.int64)
+    vblocks = [(view_of[(a, int(counts[b]))], view_of[(b, int(counts[a]))]) for a, b in blocks]
+    return views, vblocks, vcount, session_tables(vcount, [(va, vb, a == b) for (va, vb), (a, b) in zip(vblocks, blocks)])
+
+
+def _session_block_results(s):
+    """-> prm (per block: the parameters with its own single_robot_lc), Ms (its fresh _GridResults over the non-empty submaps) and
+    result_of(b, M, timing, edges, hyps): block b's SubmapAlignResults out of M, with its own gt_available."""
+    def result_of(b, M, timing=(), edges=None, hyps=None):
+        io = copy.copy(s.sm_io); io.gt_available = (s.gt_poses[s.blocks[b][0]] is not None, s.gt_poses[s.blocks[b][1]] is not None)
+        M.sm_io = io
+        return M.results(timing, edges, hyps if s.num_solutions is None or hyps is not None else {})
+    prm = [copy.copy(s.sm_params) for _ in s.blocks]
+    for q, (a, b) in zip(prm, s.blocks):
+        q.single_robot_lc = (a == b)
+    return prm, [_GridResults(prm[k], s.sm_io, int(s.counts[a]), int(s.counts[b])) for k, (a, b) in enumerate(s.blocks)], result_of
+
+
+def _session_context(s, gate_entry):
+    """The registration's context, and the refusals that ask the context itself (as submap_align_pools does, they come once it
+    exists).  `gate_entry`: the gate the caller enqueues, 'session_gate_dev' (with session_gate_aabb_dev beside it for the
+    bounding-box gate) or 'session_gate_list_dev' (which serves the boxes itself).  -> the context."""
+    ctx, way = s.registration._context(), s.way
+    if s.num_solutions is not None and not hasattr(ctx, "mno_lc_tail_dev"):
+        raise ValueError("the context has no roman_mno_lc_tail_dev" + way)
+    if s.selfs and not hasattr(ctx, "shared_reduce_dev"):
+        raise ValueError("self blocks need a context with roman_shared_reduce_dev" + way)
+    if not hasattr(ctx, gate_entry):
+        raise ValueError(f"the context has no roman_{gate_entry}" + way)
+    if s.stacked and not hasattr(ctx, "session_stacked_sim_dev"):
+        raise ValueError("the context has no roman_session_stacked_sim_dev" + way)
+    box_calls = ["session_boxes_dev"] + (["session_gate_aabb_dev"] if gate_entry == "session_gate_dev" else [])
+    if s.aabb_mode and not all(hasattr(ctx, name) for name in box_calls):
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes: the context has no " +
+                         " / ".join("roman_" + name for name in box_calls) + way)
+    if s.aabb_mode and any(int(q.table.point_dim) != 3 for q in s.p):
+        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes, and pools of dim 2: their rows hold no z" + way)
+    return ctx
+
+
+def _session_uploads(torch, s, views, sub_off, blk, pair_off):
+    """The session-wide arrays of the gate on the pools' device -> a record: dev, wait_torch / up / ptr (`_plumbing`), lv (the views
+    that hold submaps, in table order), cat(get, width) (a host array per view, concatenated over lv), FLh / FRh (the edge frames
+    over all submaps, host), rows_of (per live robot: its non-empty submaps as a device index) and t, the device tables by name
+    (the caller adds the one its own gate reads: tile_off or list).  Stacked descriptors: ONE frame table (fdesc) and ONE block
+    of mask words (fmask) for the session — every live robot's frame descriptors once and the mask rows of its non-empty submaps
+    (gathered on the device) once, whatever number of views it has: the views of a robot name the same frames and the same
+    words — with frame_lo, frame_n, mask_off per view, host here and device in t."""
+    p, counts, gt_poses = s.p, s.counts, s.gt_poses
+    dev = p[0].pool.device
+    wait_torch, up, ptr = _plumbing(torch, dev)
+    lv = [(r, hs) for r, hs in views if counts[r]]
+    cat = lambda get, width: np.concatenate([np.zeros((int(counts[r]),) + width) if hs is None else np.asarray(get(hs)).reshape((-1,) + width) for r, hs in lv])
+    any_gt = any(gt_poses[r] is not None for r, _ in lv)
+    pos_gt = None
+    if any_gt:
+        pos_gt = np.concatenate([np.full((int(counts[r]), 3), np.nan) if (hs is None or hs["pos_gt"] is None) else hs["pos_gt"] for r, hs in lv])
+    rows_of = {r: torch.from_numpy(s.keep[r].astype(np.int64)).to(dev) for r in {r for r, _ in lv}} if s.d or s.stacked else {}
+    t = dict(pos=up(cat(lambda hs: hs["pos"], (3,))), gt=up(pos_gt),
+             has=up(np.array([gt_poses[r] is not None for r, _ in views], dtype=np.int32)) if any_gt else None,
+             T_w=up(cat(lambda hs: hs["T_w"][0], (16,))), time=up(cat(lambda hs: hs["time"], ())), sub_off=up(sub_off), blocks=up(blk),
+             pair_off=up(pair_off), desc=torch.cat([p[r].desc_dev[rows_of[r]] for r, _ in lv]).contiguous() if s.d else None)
+    u = SimpleNamespace(dev=dev, wait_torch=wait_torch, up=up, ptr=ptr, lv=lv, cat=cat, FLh=cat(lambda hs: hs["frames"][0], (16,)),
+                        FRh=cat(lambda hs: hs["frames"][1], (16,)), rows_of=rows_of, t=t)
+    if s.stacked:
+        live_f = sorted(rows_of)
+        u.fdesc = p[live_f[0]].frame_desc_dev if len(live_f) == 1 else torch.cat([p[r].frame_desc_dev for r in live_f], dim=0)
+        u.fmask = torch.cat([p[r].frame_mask[rows_of[r]].reshape(-1) for r in live_f]).contiguous()
+        nfr = {r: int(p[r].frame_desc_dev.shape[0]) for r in live_f}
+        flo = dict(zip(live_f, np.concatenate([[0], np.cumsum([nfr[r] for r in live_f])]).astype(np.int64).tolist()))
+        mof = dict(zip(live_f, np.concatenate([[0], np.cumsum([int(counts[r]) * ((nfr[r] + 63) // 64) for r in live_f])]).astype(np.int64).tolist()))
+        u.frame_lo = np.array([flo.get(r, 0) for r, _ in views], dtype=np.int32)
+        u.frame_n = np.array([nfr.get(r, 0) for r, _ in views], dtype=np.int32)
+        u.mask_off = np.array([mof.get(r, 0) for r, _ in views], dtype=np.int64)
+        t.update(frame_lo=up(u.frame_lo), frame_n=up(u.frame_n), mask_off=up(u.mask_off))
+    return u
+
+
+def _session_pool(torch, s, lv):
+    """ONE pool for the session — every live robot's rows once, whatever the number of its views (lv: the views that hold
+    submaps) — and per GLOBAL submap index (the gate's, as sub_off orders them) its first row and its rows
+    -> (pool, sm_row int64, sm_cnt int32).  Pools of ONE build (build_session_pools) are read in place (`_one_storage`); any other
+    list is concatenated: a copy of every row, so a caller that may not need the pool asks late."""
+    p = s.p
+    live = sorted({r for r, _ in lv})
+    pool = _one_storage(torch, [p[r].pool for r in live])
+    if pool is None:
+        pool = p[live[0]].pool if len(live) == 1 else torch.cat([p[r].pool for r in live], dim=0)
+    row0 = dict(zip(live, np.concatenate([[0], np.cumsum([int(p[r].pool.shape[0]) for r in live])]).astype(np.int64).tolist()))
+    return (pool, np.concatenate([row0[r] + p[r].offsets()[0] for r, _ in lv]).astype(np.int64),
+            np.concatenate([p[r].offsets()[1] for r, _ in lv]).astype(np.int32))
+
+
+def _session_pass1_front(torch, ctx, s, u, sub_off, blk, pair_off, n_out, one_pool, sim_total=None):
+    """What pass 1 of a session enqueues in front of its gate -> (g, gp, gate_kw): g the gate's output buffers, `n_out` entries each
+    (todo_off: one per block and one), gp its parameters, gate_kw its optional pointers.  Behind wait_torch(), on the context's
+    stream: for the bounding-box gate ONE session_boxes_dev over `one_pool` (`_session_pool`'s: rows by offset and count, no
+    gather into slots; a view's own T_odom_center — two views of a robot: the same rows, two box sets) into t["box"]; for
+    stacked descriptors session_stacked_sim_dev over whole blocks — into g["sim"], or with `sim_total` into a dense buffer of
+    that many entries, t["dense_sim"] —, which gate_kw hands to the gate as sim_in_ptr."""
+    f64, i32 = torch.float64, torch.int32
+    sm_params, t, up, ptr, dev, n = s.sm_params, u.t, u.up, u.ptr, u.dev, n_out
+    if s.aabb_mode:
+        pool, sm_row, sm_cnt = one_pool
+        t.update(row0=up(sm_row), count=up(sm_cnt), T_oc=up(u.cat(lambda hs: hs["T_oc"], (16,))), box=torch.empty((len(sm_cnt), 6), dtype=f64, device=dev))
+    g = dict(dist=torch.empty(n, dtype=f64, device=dev), flags=torch.empty(n, dtype=i32, device=dev), yaw=torch.empty(n, dtype=f64, device=dev),
+             sim=torch.empty(n, dtype=f64, device=dev), T_ij=torch.empty((n, 16), dtype=f64, device=dev),
+             pairs=torch.empty((n, 2), dtype=i32, device=dev), T_ref=torch.empty((n, 16), dtype=f64, device=dev),
+             enable=torch.empty(n, dtype=i32, device=dev), todo_off=torch.zeros(len(s.blocks) + 1, dtype=i32, device=dev))
+    gp = grid_gate_params(sm_params.submap_radius, s.sm_io.skip_distance, s.d, sm_params.submap_descriptor_thresh if s.d else 0.0,
+                          False, sm_params.single_robot_lc_time_thresh)
+    gate_kw = dict(time_ptr=ptr(t["time"]), desc_ptr=ptr(t["desc"]), pos_gt_ptr=ptr(t["gt"]), has_gt_ptr=ptr(t["has"]))
+    if s.stacked and sim_total is not None:
+        t["dense_sim"] = torch.empty(sim_total, dtype=f64, device=dev)
+    u.wait_torch()                                           # the uploads are in place before the library's stream reads them
+    if s.aabb_mode:
+        ctx.session_boxes_dev(len(sm_cnt), int(pool.shape[1]), pool.data_ptr(), ptr(t["row0"]), ptr(t["count"]), ptr(t["T_oc"]), ptr(t["box"]))
+    if s.stacked:                                            # similarity first, then the gate that reads it: both on the context's stream
+        gp.desc_thresh = float(sm_params.submap_descriptor_thresh)
+        sim = (g["sim"] if sim_total is None else t["dense_sim"]).data_ptr()
+        ctx.session_stacked_sim_dev(int(u.fdesc.shape[1]), int(u.fdesc.shape[0]), ptr(u.fdesc), ptr(u.fmask), u.frame_lo, u.frame_n, u.mask_off, sub_off, blk,
+                                    pair_off, ptr(t["frame_lo"]), ptr(t["frame_n"]), ptr(t["mask_off"]), ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]),
+                                    sim)
+        gate_kw["sim_in_ptr"] = sim
+    return g, gp, gate_kw
+
+
+def _session_register(torch, ctx, s, u, gpairs, todo_off, one_pool, g):
+    """Every TODO pair of every block as a problem of ONE batch over `one_pool` (`_session_pool`'s), in the compact order pass 1
+    left in g: `gpairs` (B, 2) global submap indices, block b's at [todo_off[b], todo_off[b + 1]).  The problems of the self
+    blocks lose the segments both submaps hold; then `_register_over_pool`.  For a RansacReg too the problems of ALL blocks go
+    in one batch: the seed is one per batch and a problem's draws do not depend on its place in it,
+    so a block equals its own submap_align_pools.  -> (parts, per_pair): one LoopClosureResult per block, its accepted indices
+    block-local, with `hypotheses` when num_solutions is set."""
+    p = s.p
+    pool, sm_row, sm_cnt = one_pool
+    prob = sm_row[gpairs[:, 0]], sm_cnt[gpairs[:, 0]], sm_row[gpairs[:, 1]], sm_cnt[gpairs[:, 1]]
+    kmax = int(max(1, np.max(np.minimum(prob[1], prob[3]))))    # (of the unreduced sizes: still a bound after the removal)
+    of_self = np.concatenate([np.full(int(todo_off[b + 1] - todo_off[b]), a == c, dtype=bool) for b, (a, c) in enumerate(s.blocks)])
+    sel = np.nonzero(of_self)[0]
+    if len(sel):
+        live = sorted({r for r, _ in u.lv})
+        ids_dev = _one_storage(torch, [p[r].ids_dev for r in live])
+        if ids_dev is None or int(ids_dev.shape[0]) != int(pool.shape[0]):
+            ids_dev = torch.cat([p[r].ids_dev if p[r].ids_dev is not None else torch.zeros(int(p[r].pool.shape[0]), dtype=torch.int64, device=u.dev) for r in live])
+        pool, *prob = _drop_shared_over_pool(torch, ctx, pool, ids_dev, *prob, sel, u.wait_torch)
+    batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), tuple(pool.shape)), prob[0].astype(np.int64), prob[1].astype(np.int32), prob[2].astype(np.int64),
+                           prob[3].astype(np.int32), pair_index=gpairs)
+    res, per_pair = _register_over_pool(torch, ctx, s.registration, s.sm_params, s.sm_io, pool, batch, kmax, g, len(gpairs), u.up(u.FLh), u.up(u.FRh),
+                                        u.wait_torch, s.num_solutions)
+    parts = []
+    acc = np.asarray(res.accepted, dtype=np.int64)
+    for b in range(len(s.blocks)):
+        lo, hi = int(todo_off[b]), int(todo_off[b + 1])
+        part = LoopClosureResult(res.assoc[lo:hi], res.T[lo:hi], res.status[lo:hi], res.stats[lo:hi], res.records[lo:hi],
+                                 acc[(acc >= lo) & (acc < hi)] - lo)
+        if s.num_solutions is not None:
+            part.hypotheses = res.hypotheses[lo:hi]
+        parts.append(part)
+    return parts, per_pair
+
+
 def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[SubmapAlignIO] = None, registration=None,
                          gt_poses=None, num_solutions=None) -> Dict[Tuple[int, int], SubmapAlignResults]:
     """The robot-pair loop of the reference's driver [REF demo/demo.py:138-161] in ONE call: `pools` is a list of R
@@ -1172,160 +1405,26 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     and for the bounding-box gate a context without roman_session_boxes_dev / roman_session_gate_aabb_dev, or pools of dim 2
     (their rows hold no z)."""
     import torch
-    from ..runtime import session_tables
-    sm_io = sm_io or SubmapAlignIO()
-    registration = registration or sm_params.get_object_registration()
-    way = " (not in the session call: use submap_align_pools per robot pair)"
-    p = list(pools)
-    R = len(p)
-    gt_poses = [None] * R if gt_poses is None else list(gt_poses)
-    blocks = [(r, s) for r in range(R) for s in range(r, R)] if robot_pairs is None else [(int(r), int(s)) for r, s in robot_pairs]
-    if len(gt_poses) != R:
-        raise ValueError("gt_poses must hold one entry per pool" + way)
-    if any(not (0 <= r < R and 0 <= s < R) for r, s in blocks) or len(set(blocks)) != len(blocks):
-        raise ValueError("robot_pairs must name pools by index, each pair once" + way)
-    if num_solutions is not None:                            # (submap_align_pools' three for K hypotheses per pair, DESIGN.md §4.18)
-        _mno_refusals(registration, p, blocks, num_solutions, way)
-    if isinstance(registration, RansacReg) and R:            # (submap_align_pools' four, in its order: in front of everything that makes a HIP context)
-        _ransac_refusals(registration, p, way)
-    if _device_prefilter(registration) and R:                # (and its four for a device-prefilter plugin)
-        _prune_refusals(registration, p, way)
-    aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
-    if aabb_mode and _no_device(registration, p):            # (the boxes are reduced from the resident rows: as for a RansacReg, host rows need a context of the caller's)
-        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes of the resident rows: the registration has no context set "
-                         "and the pools are host tensors: no device to run on" + way)
-    mode = sm_params.submap_descriptor
-    stacked = mode == 'stacked_frame_descriptors'
-    _descriptor_refusals(registration, p, mode, way)
-    if R and any(int(q.pool.shape[1]) != int(p[0].pool.shape[1]) for q in p):
-        raise ValueError("the pools have different row widths" + way)
-    d = _descriptor_dim(p, mode, "the pools", way)
-    selfs = sorted({r for r, s in blocks if r == s})
-    if any(p[r].ids_dev is None for r in selfs):
-        raise ValueError("a self block drops the segments both submaps hold: its pool must have kept its ids on the device (SubmapPool.ids_dev, "
-                         "as build_submap_pool leaves it)" + way)
-    keep = [q.nonempty for q in p]
-    counts = np.array([len(k) for k in keep], dtype=np.int64)
-    # ---- per robot (O(S), host): the block submap_align_pools runs per side, with the reads of the pair loop it would see.  A
-    # pose read `n` times (n: the partner's submaps) usually sits at a fixed point after a read or two, and the robot then has ONE
-    # set of arrays for all its blocks; where flattening a pose alternates between two neighbouring values, its reference
-    # transform depends on n, and the robot enters the tables once per distinct outcome (a "view": same pool rows, own T_w and
-    # edge frames).  views[v] = (robot, host arrays or None); view_of[(r, n)] = v ----
-    views, view_of = [], {}
-    for r in range(R):
-        reads = sorted({int(counts[s if a == r else a]) for a, s in blocks if r in (a, s)})
-        mine = []
-        live_reads = [n for n in reads if n > 0] if counts[r] else []       # (an empty block: the robot only needs a place in the tables)
-        all_ = _pool_side_host(p[r], gt_poses[r], gt_poses[r] is not None, live_reads, aabb_mode) if live_reads else None
-        for k, n in enumerate(live_reads):
-            hs = dict(all_, T_w=[all_["T_w"][k]], frames=all_["frames"][k])
-            key = hs["T_w"][0].tobytes() + hs["frames"][0].tobytes() + hs["frames"][1].tobytes() + (hs["T_oc"].tobytes() if aabb_mode else b"")
-            same = [v for v, kk in mine if kk == key]
-            if not same:
-                views.append((r, hs)); mine.append((len(views) - 1, key))
-            view_of[(r, n)] = same[0] if same else len(views) - 1
-        if reads and not mine:                               # only in empty blocks: zeros stand in (never read)
-            views.append((r, None)); mine.append((len(views) - 1, b""))
-        for n in reads:
-            view_of.setdefault((r, n), mine[0][0])
-    vcount = np.array([counts[r] for r, _ in views], dtype=np.int64)
-    vblocks = [(view_of[(r, int(counts[s]))], view_of[(s, int(counts[r]))]) for r, s in blocks]
-
+    sess = _session_setup(sm_params, pools, robot_pairs, sm_io, registration, gt_poses, num_solutions)
+    blocks, counts = sess.blocks, sess.counts
+    views, vblocks, _, (sub_off, blk, pair_off, tile_off) = _session_views(sess)
     # ---- the refusals that need no context are behind us: the tables, the context, the uploads ----
-    def result_of(b, M, timing=(), edges=None, hyps=None):
-        io = copy.copy(sm_io); io.gt_available = (gt_poses[blocks[b][0]] is not None, gt_poses[blocks[b][1]] is not None)
-        M.sm_io = io
-        return M.results(timing, edges, hyps if num_solutions is None or hyps is not None else {})
-    prm = [copy.copy(sm_params) for _ in blocks]
-    for q, (r, s) in zip(prm, blocks):
-        q.single_robot_lc = (r == s)
-    Ms = [_GridResults(prm[b], sm_io, int(counts[r]), int(counts[s])) for b, (r, s) in enumerate(blocks)]
-    sub_off, blk, pair_off, tile_off = session_tables(vcount, [(va, vb, r == s) for (va, vb), (r, s) in zip(vblocks, blocks)])
+    _, Ms, result_of = _session_block_results(sess)
     total, nb = int(pair_off[-1]), len(blocks)
     if total == 0:
         return {blocks[b]: result_of(b, Ms[b], edges=Ms[b].empty_edges()) for b in range(nb)}
-    ctx = registration._context()
-    if num_solutions is not None and not hasattr(ctx, "mno_lc_tail_dev"):
-        raise ValueError("the context has no roman_mno_lc_tail_dev" + way)
-    if selfs and not hasattr(ctx, "shared_reduce_dev"):      # (these two ask the context itself, as submap_align_pools does)
-        raise ValueError("self blocks need a context with roman_shared_reduce_dev" + way)
-    if not hasattr(ctx, "session_gate_dev"):
-        raise ValueError("the context has no roman_session_gate_dev" + way)
-    if stacked and not hasattr(ctx, "session_stacked_sim_dev"):
-        raise ValueError("the context has no roman_session_stacked_sim_dev" + way)
-    if aabb_mode and not (hasattr(ctx, "session_boxes_dev") and hasattr(ctx, "session_gate_aabb_dev")):
-        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes: the context has no roman_session_boxes_dev / "
-                         "roman_session_gate_aabb_dev" + way)
-    if aabb_mode and any(int(q.table.point_dim) != 3 for q in p):
-        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes, and pools of dim 2: their rows hold no z" + way)
-    dev = p[0].pool.device
-    wait_torch, up, ptr = _plumbing(torch, dev)
-    lv = [(r, hs) for r, hs in views if counts[r]]           # the views that hold submaps, in table order
-    cat = lambda get, width: np.concatenate([np.zeros((int(counts[r]),) + width) if hs is None else np.asarray(get(hs)).reshape((-1,) + width) for r, hs in lv])
-    any_gt = any(gt_poses[r] is not None for r, _ in lv)
-    pos_gt = None
-    if any_gt:
-        pos_gt = np.concatenate([np.full((int(counts[r]), 3), np.nan) if (hs is None or hs["pos_gt"] is None) else hs["pos_gt"] for r, hs in lv])
-    FLh, FRh = cat(lambda hs: hs["frames"][0], (16,)), cat(lambda hs: hs["frames"][1], (16,))
-    rows_of = {r: torch.from_numpy(keep[r].astype(np.int64)).to(dev) for r in {r for r, _ in lv}} if d or stacked else {}
-    t = dict(pos=up(cat(lambda hs: hs["pos"], (3,))), gt=up(pos_gt),
-             has=up(np.array([gt_poses[r] is not None for r, _ in views], dtype=np.int32)) if any_gt else None,
-             T_w=up(cat(lambda hs: hs["T_w"][0], (16,))), time=up(cat(lambda hs: hs["time"], ())), sub_off=up(sub_off), blocks=up(blk),
-             pair_off=up(pair_off), tile_off=up(tile_off), desc=torch.cat([p[r].desc_dev[rows_of[r]] for r, _ in lv]).contiguous() if d else None)
+    ctx = _session_context(sess, "session_gate_dev")
+    u = _session_uploads(torch, sess, views, sub_off, blk, pair_off)
+    t, ptr = u.t, u.ptr
+    t["tile_off"] = u.up(tile_off)
 
-    if stacked:
-        # ONE frame table and ONE block of mask words for the session: every live robot's frame descriptors once and the mask rows of
-        # its non-empty submaps (gathered on the device) once, whatever number of views it has — the views of a robot name the same
-        # frames and the same words
-        live_f = sorted(rows_of)
-        fdesc = p[live_f[0]].frame_desc_dev if len(live_f) == 1 else torch.cat([p[r].frame_desc_dev for r in live_f], dim=0)
-        fmask = torch.cat([p[r].frame_mask[rows_of[r]].reshape(-1) for r in live_f]).contiguous()
-        nfr = {r: int(p[r].frame_desc_dev.shape[0]) for r in live_f}
-        flo = dict(zip(live_f, np.concatenate([[0], np.cumsum([nfr[r] for r in live_f])]).astype(np.int64).tolist()))
-        mof = dict(zip(live_f, np.concatenate([[0], np.cumsum([int(counts[r]) * ((nfr[r] + 63) // 64) for r in live_f])]).astype(np.int64).tolist()))
-        frame_lo = np.array([flo.get(r, 0) for r, _ in views], dtype=np.int32)
-        frame_n = np.array([nfr.get(r, 0) for r, _ in views], dtype=np.int32)
-        mask_off = np.array([mof.get(r, 0) for r, _ in views], dtype=np.int64)
-        t.update(frame_lo=up(frame_lo), frame_n=up(frame_n), mask_off=up(mask_off))
-
-    def concatenated():
-        """ONE pool for the session — every live robot's rows once, whatever the number of its views — and per GLOBAL submap index
-        (the gate's, as sub_off orders them) its first row and its rows -> (pool, sm_row int64, sm_cnt int32)."""
-        live = sorted({r for r, _ in lv})
-        pool = _one_storage(torch, [p[r].pool for r in live])   # pools of ONE build (build_session_pools): the rows are there already
-        if pool is None:
-            pool = p[live[0]].pool if len(live) == 1 else torch.cat([p[r].pool for r in live], dim=0)
-        row0 = dict(zip(live, np.concatenate([[0], np.cumsum([int(p[r].pool.shape[0]) for r in live])]).astype(np.int64).tolist()))
-        return (pool, np.concatenate([row0[r] + p[r].offsets()[0] for r, _ in lv]).astype(np.int64),
-                np.concatenate([p[r].offsets()[1] for r, _ in lv]).astype(np.int32))
-
-    # ---- pass 1 of all blocks on the device: one enqueue, one synchronisation, one read-back ----
-    f64, i32 = torch.float64, torch.int32
-    if aabb_mode:
-        # the boxes of every submap of every view from the concatenated pools the batch reads anyway: rows by offset and count, no
-        # gather into slots; a view's own T_odom_center (two views of a robot: the same rows, two box sets)
-        pool, sm_row, sm_cnt = concatenated()
-        t.update(row0=up(sm_row), count=up(sm_cnt), T_oc=up(cat(lambda hs: hs["T_oc"], (16,))),
-                 box=torch.empty((len(sm_cnt), 6), dtype=f64, device=dev))
-    g = dict(dist=torch.empty(total, dtype=f64, device=dev), flags=torch.empty(total, dtype=i32, device=dev), yaw=torch.empty(total, dtype=f64, device=dev),
-             sim=torch.empty(total, dtype=f64, device=dev), T_ij=torch.empty((total, 16), dtype=f64, device=dev),
-             pairs=torch.empty((total, 2), dtype=i32, device=dev), T_ref=torch.empty((total, 16), dtype=f64, device=dev),
-             enable=torch.empty(total, dtype=i32, device=dev), todo_off=torch.zeros(nb + 1, dtype=i32, device=dev))
-    gp = grid_gate_params(sm_params.submap_radius, sm_io.skip_distance, d, sm_params.submap_descriptor_thresh if d else 0.0,
-                          False, sm_params.single_robot_lc_time_thresh)
-    gate_kw = dict(time_ptr=ptr(t["time"]), desc_ptr=ptr(t["desc"]), pos_gt_ptr=ptr(t["gt"]), has_gt_ptr=ptr(t["has"]))
-    wait_torch()                                             # the uploads are in place before the library's stream reads them
-    if aabb_mode:
-        ctx.session_boxes_dev(len(sm_cnt), int(pool.shape[1]), pool.data_ptr(), ptr(t["row0"]), ptr(t["count"]), ptr(t["T_oc"]), ptr(t["box"]))
-    if stacked:                                              # similarity first, then the gate that reads it: both on the context's stream
-        gp.desc_thresh = float(sm_params.submap_descriptor_thresh)
-        ctx.session_stacked_sim_dev(int(fdesc.shape[1]), int(fdesc.shape[0]), ptr(fdesc), ptr(fmask), frame_lo, frame_n, mask_off, sub_off, blk, pair_off,
-                                    ptr(t["frame_lo"]), ptr(t["frame_n"]), ptr(t["mask_off"]), ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]),
-                                    g["sim"].data_ptr())
-        gate_kw["sim_in_ptr"] = g["sim"].data_ptr()
+    # ---- pass 1 of all blocks on the device: one enqueue, one synchronisation, one read-back.  The bounding-box gate reads the
+    # ONE pool now; the radius gate leaves it until a pair is TODO (a list of separately built pools is copied into it) ----
+    one_pool = _session_pool(torch, sess, u.lv) if sess.aabb_mode else None
+    g, gp, gate_kw = _session_pass1_front(torch, ctx, sess, u, sub_off, blk, pair_off, total, one_pool)
     gate_args = (gp, sub_off, blk, pair_off, tile_off, ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]), ptr(t["tile_off"]), ptr(t["pos"]), ptr(t["T_w"]),
                  *[g[k].data_ptr() for k in ("dist", "flags", "yaw", "sim", "T_ij", "pairs", "T_ref", "enable", "todo_off")])
-    if aabb_mode:
+    if sess.aabb_mode:
         ctx.session_gate_aabb_dev(*gate_args, ptr(t["box"]), **gate_kw)
     else:
         ctx.session_gate_dev(*gate_args, **gate_kw)
@@ -1344,36 +1443,13 @@ def submap_align_session(sm_params, pools, robot_pairs=None, sm_io: Optional[Sub
     if B == 0:
         return {blocks[b]: result_of(b, Ms[b], edges=Ms[b].empty_edges()) for b in range(nb)}
 
-    # ---- ONE batch over the concatenated pools: offsets and counts per global submap, the problems in compact order ----
-    live = sorted({r for r, _ in lv})
-    if not aabb_mode:
-        pool, sm_row, sm_cnt = concatenated()
-    prob = sm_row[gpairs[:, 0]], sm_cnt[gpairs[:, 0]], sm_row[gpairs[:, 1]], sm_cnt[gpairs[:, 1]]
-    kmax = int(max(1, np.max(np.minimum(prob[1], prob[3]))))    # (of the unreduced sizes: still a bound after the removal)
-    of_self = np.concatenate([np.full(int(todo_off[b + 1] - todo_off[b]), r == s, dtype=bool) for b, (r, s) in enumerate(blocks)])
-    sel = np.nonzero(of_self)[0]
-    if len(sel):                                             # the problems of the self blocks lose the segments both submaps hold
-        ids_dev = _one_storage(torch, [p[r].ids_dev for r in live])
-        if ids_dev is None or int(ids_dev.shape[0]) != int(pool.shape[0]):
-            ids_dev = torch.cat([p[r].ids_dev if p[r].ids_dev is not None else torch.zeros(int(p[r].pool.shape[0]), dtype=torch.int64, device=dev) for r in live])
-        pool, *prob = _drop_shared_over_pool(torch, ctx, pool, ids_dev, *prob, sel, wait_torch)
-    batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), tuple(pool.shape)), prob[0].astype(np.int64), prob[1].astype(np.int32), prob[2].astype(np.int64),
-                           prob[3].astype(np.int32), pair_index=gpairs)
-    # for a RansacReg too the problems of ALL blocks go in one batch: the seed is one per batch and a
-    # problem's draws do not depend on its place in it, so a block equals its own submap_align_pools
-    res, per_pair = _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, up(FLh), up(FRh), wait_torch, num_solutions)
-
-    # ---- the records and the accepted list split by todo_off, per block with block-local indices ----
+    # ---- ONE batch over the ONE pool, then the records and the accepted list per block, with block-local indices ----
+    parts, per_pair = _session_register(torch, ctx, sess, u, gpairs, todo_off, one_pool or _session_pool(torch, sess, u.lv), g)
     out = {}
-    acc = np.asarray(res.accepted, dtype=np.int64)
-    for b in range(nb):
-        lo, hi = int(todo_off[b]), int(todo_off[b + 1])
-        part = LoopClosureResult(res.assoc[lo:hi], res.T[lo:hi], res.status[lo:hi], res.stats[lo:hi], res.records[lo:hi],
-                                 acc[(acc >= lo) & (acc < hi)] - lo)
-        if num_solutions is not None:
-            part.hypotheses = res.hypotheses[lo:hi]
-        edges = _records_into_results(Ms[b], part, local[b][:, 0], local[b][:, 1], nearby[b]) if hi > lo else Ms[b].empty_edges()
-        out[blocks[b]] = result_of(b, Ms[b], [per_pair] * (hi - lo), edges, _hypotheses_of(part, local[b][:, 0], local[b][:, 1]))
+    for b, part in enumerate(parts):
+        ti, tj = local[b][:, 0], local[b][:, 1]
+        edges = _records_into_results(Ms[b], part, ti, tj, nearby[b]) if len(ti) else Ms[b].empty_edges()
+        out[blocks[b]] = result_of(b, Ms[b], [per_pair] * len(ti), edges, _hypotheses_of(part, ti, tj))
     return out
 
 
@@ -1463,42 +1539,13 @@ def submap_align_session_update(state, sm_params, pools, touched=None, robot_pai
     ValueError before any context is made: whatever submap_align_session refuses; a pool that shrank; a `touched` of the wrong
     length; a state made for other robot_pairs, another method, descriptor mode, gate, ground-truth pattern or num_solutions."""
     import torch
-    from ..runtime import session_pair_list, session_tables
+    from ..runtime import session_pair_list
     marks = [time.perf_counter()]
-    sm_io = sm_io or SubmapAlignIO()
-    registration = registration or sm_params.get_object_registration()
-    way = " (not in the session call: use submap_align_pools per robot pair)"
-    p = list(pools)
-    R = len(p)
-    gt_poses = [None] * R if gt_poses is None else list(gt_poses)
-    blocks = [(r, s) for r in range(R) for s in range(r, R)] if robot_pairs is None else [(int(r), int(s)) for r, s in robot_pairs]
-    if len(gt_poses) != R:
-        raise ValueError("gt_poses must hold one entry per pool" + way)
-    if any(not (0 <= r < R and 0 <= s < R) for r, s in blocks) or len(set(blocks)) != len(blocks):
-        raise ValueError("robot_pairs must name pools by index, each pair once" + way)
-    if num_solutions is not None:
-        _mno_refusals(registration, p, blocks, num_solutions, way)
-    if isinstance(registration, RansacReg) and R:
-        _ransac_refusals(registration, p, way)
-    if _device_prefilter(registration) and R:
-        _prune_refusals(registration, p, way)
-    aabb_mode = bool(sm_params.force_fill_submaps or sm_params.submap_radius is None)
-    if aabb_mode and _no_device(registration, p):
-        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes of the resident rows: the registration has no context set "
-                         "and the pools are host tensors: no device to run on" + way)
-    mode = sm_params.submap_descriptor
-    stacked = mode == 'stacked_frame_descriptors'
-    _descriptor_refusals(registration, p, mode, way)
-    if R and any(int(q.pool.shape[1]) != int(p[0].pool.shape[1]) for q in p):
-        raise ValueError("the pools have different row widths" + way)
-    d = _descriptor_dim(p, mode, "the pools", way)
-    selfs = sorted({r for r, s in blocks if r == s})
-    if any(p[r].ids_dev is None for r in selfs):
-        raise ValueError("a self block drops the segments both submaps hold: its pool must have kept its ids on the device (SubmapPool.ids_dev, "
-                         "as build_submap_pool leaves it)" + way)
+    sess = _session_setup(sm_params, pools, robot_pairs, sm_io, registration, gt_poses, num_solutions)
+    p, R, blocks, gt_poses, keep, counts, aabb_mode = sess.p, sess.R, sess.blocks, sess.gt_poses, sess.keep, sess.counts, sess.aabb_mode
     # ---- what only a growing session can get wrong ----
-    key = (tuple(blocks), type(registration).__name__, getattr(sm_params, "method", None), mode, aabb_mode, tuple(g is not None for g in gt_poses),
-           num_solutions, int(d))
+    key = (tuple(blocks), type(sess.registration).__name__, getattr(sm_params, "method", None), sess.mode, aabb_mode, tuple(g is not None for g in gt_poses),
+           num_solutions, int(sess.d))
     if state.key is not None and state.key != key:
         raise ValueError("the state was made by a call with other robot_pairs, another method, descriptor mode, gate, ground-truth pattern or "
                          "num_solutions: a SessionAlignState serves one kind of call")
@@ -1509,28 +1556,7 @@ def submap_align_session_update(state, sm_params, pools, touched=None, robot_pai
     if len(touched) != R or any(t is not None and np.asarray(t).reshape(-1).shape[0] != n for t, n in zip(touched, n_pool)):
         raise ValueError("touched must hold one entry per pool, each None or one flag per submap of that pool")
 
-    keep = [q.nonempty for q in p]
-    counts = np.array([len(k) for k in keep], dtype=np.int64)
-    # ---- per robot (O(S), host): views exactly as submap_align_session cuts them ----
-    views, view_of = [], {}
-    for r in range(R):
-        reads = sorted({int(counts[s if a == r else a]) for a, s in blocks if r in (a, s)})
-        mine = []
-        live_reads = [n for n in reads if n > 0] if counts[r] else []
-        all_ = _pool_side_host(p[r], gt_poses[r], gt_poses[r] is not None, live_reads, aabb_mode) if live_reads else None
-        for k, n in enumerate(live_reads):
-            hs = dict(all_, T_w=[all_["T_w"][k]], frames=all_["frames"][k])
-            vkey = hs["T_w"][0].tobytes() + hs["frames"][0].tobytes() + hs["frames"][1].tobytes() + (hs["T_oc"].tobytes() if aabb_mode else b"")
-            same = [v for v, kk in mine if kk == vkey]
-            if not same:
-                views.append((r, hs)); mine.append((len(views) - 1, vkey))
-            view_of[(r, n)] = same[0] if same else len(views) - 1
-        if reads and not mine:
-            views.append((r, None)); mine.append((len(views) - 1, b""))
-        for n in reads:
-            view_of.setdefault((r, n), mine[0][0])
-    vcount = np.array([counts[r] for r, _ in views], dtype=np.int64)
-    vblocks = [(view_of[(r, int(counts[s]))], view_of[(s, int(counts[r]))]) for r, s in blocks]
+    views, vblocks, vcount, (sub_off, blk, pair_off, _) = _session_views(sess)      # (cut exactly as submap_align_session cuts them)
 
     # ---- the touched set: the caller's flags, what is new, and what differs from the bytes the state recorded ----
     def rows_of_view(v):
@@ -1564,15 +1590,8 @@ def submap_align_session_update(state, sm_params, pools, touched=None, robot_pai
             flag[r][common[(posed[at_new] != was_posed[at_old]).any(axis=1)]] = True      # (it is read with another pose, in this block at least)
     local_flag = [flag[r][keep[r]] for r in range(R)]
 
-    def result_of(b, M, timing=(), edges=None, hyps=None):
-        io = copy.copy(sm_io); io.gt_available = (gt_poses[blocks[b][0]] is not None, gt_poses[blocks[b][1]] is not None)
-        M.sm_io = io
-        return M.results(timing, edges, hyps if num_solutions is None or hyps is not None else {})
-    prm = [copy.copy(sm_params) for _ in blocks]
-    for q, (r, s) in zip(prm, blocks):
-        q.single_robot_lc = (r == s)
+    prm, Ms, result_of = _session_block_results(sess)
     nb = len(blocks)
-    Ms = [_GridResults(prm[b], sm_io, int(counts[r]), int(counts[s])) for b, (r, s) in enumerate(blocks)]
     old = []                                                     # per block: the stored results re-indexed into Ms[b] -> (edges, hypotheses)
     for b, (r, s) in enumerate(blocks):
         if first:
@@ -1580,7 +1599,6 @@ def submap_align_session_update(state, sm_params, pools, touched=None, robot_pai
         else:
             e, hy = _carry_over(Ms[b], state.results[blocks[b]], (state.keep[r], state.keep[s]), (keep[r], keep[s]))
             old.append(((e if e is not None else Ms[b].empty_edges()) if Ms[b].device_edges else None, hy))
-    sub_off, blk, pair_off, tile_off = session_tables(vcount, [(va, vb, r == s) for (va, vb), (r, s) in zip(vblocks, blocks)])
     lst = session_pair_list(vcount, vblocks, [local_flag[r] for r, _ in views])
     total, L = int(pair_off[-1]), len(lst)
     cut = np.searchsorted(lst[:, 0], np.arange(nb + 1))          # block b's entries are lst[cut[b]:cut[b + 1]]
@@ -1621,73 +1639,17 @@ def submap_align_session_update(state, sm_params, pools, touched=None, robot_pai
     if L == 0:                                                   # nothing touched (or no pair at all): the stored results, re-indexed; no context is made
         return remember({blocks[b]: merged(b) for b in range(nb)})
     marks.append(time.perf_counter())
-    ctx = registration._context()
-    if num_solutions is not None and not hasattr(ctx, "mno_lc_tail_dev"):
-        raise ValueError("the context has no roman_mno_lc_tail_dev" + way)
-    if selfs and not hasattr(ctx, "shared_reduce_dev"):
-        raise ValueError("self blocks need a context with roman_shared_reduce_dev" + way)
-    if not hasattr(ctx, "session_gate_list_dev"):
-        raise ValueError("the context has no roman_session_gate_list_dev" + way)
-    if stacked and not hasattr(ctx, "session_stacked_sim_dev"):
-        raise ValueError("the context has no roman_session_stacked_sim_dev" + way)
-    if aabb_mode and not hasattr(ctx, "session_boxes_dev"):
-        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes: the context has no roman_session_boxes_dev" + way)
-    if aabb_mode and any(int(q.table.point_dim) != 3 for q in p):
-        raise ValueError("force_fill_submaps / submap_radius None gate pairs on bounding boxes, and pools of dim 2: their rows hold no z" + way)
-    dev = p[0].pool.device
-    wait_torch, up, ptr = _plumbing(torch, dev)
-    lv = [(r, hs) for r, hs in views if counts[r]]
-    cat = lambda get, width: np.concatenate([np.zeros((int(counts[r]),) + width) if hs is None else np.asarray(get(hs)).reshape((-1,) + width) for r, hs in lv])
-    any_gt = any(gt_poses[r] is not None for r, _ in lv)
-    pos_gt = None
-    if any_gt:
-        pos_gt = np.concatenate([np.full((int(counts[r]), 3), np.nan) if (hs is None or hs["pos_gt"] is None) else hs["pos_gt"] for r, hs in lv])
-    FLh, FRh = cat(lambda hs: hs["frames"][0], (16,)), cat(lambda hs: hs["frames"][1], (16,))
-    rows_of = {r: torch.from_numpy(keep[r].astype(np.int64)).to(dev) for r in {r for r, _ in lv}} if d or stacked else {}
-    t = dict(pos=up(cat(lambda hs: hs["pos"], (3,))), gt=up(pos_gt),
-             has=up(np.array([gt_poses[r] is not None for r, _ in views], dtype=np.int32)) if any_gt else None,
-             T_w=up(cat(lambda hs: hs["T_w"][0], (16,))), time=up(cat(lambda hs: hs["time"], ())), sub_off=up(sub_off), blocks=up(blk),
-             pair_off=up(pair_off), list=up(lst), desc=torch.cat([p[r].desc_dev[rows_of[r]] for r, _ in lv]).contiguous() if d else None)
-    live = sorted({r for r, _ in lv})
-    pool = _one_storage(torch, [p[r].pool for r in live])        # pools of ONE build (build_session_pools): the rows are there already
-    if pool is None:
-        pool = p[live[0]].pool if len(live) == 1 else torch.cat([p[r].pool for r in live], dim=0)
-    row0 = dict(zip(live, np.concatenate([[0], np.cumsum([int(p[r].pool.shape[0]) for r in live])]).astype(np.int64).tolist()))
-    sm_row = np.concatenate([row0[r] + p[r].offsets()[0] for r, _ in lv]).astype(np.int64)
-    sm_cnt = np.concatenate([p[r].offsets()[1] for r, _ in lv]).astype(np.int32)
+    ctx = _session_context(sess, "session_gate_list_dev")
+    u = _session_uploads(torch, sess, views, sub_off, blk, pair_off)
+    t, ptr = u.t, u.ptr
+    t["list"] = u.up(lst)
 
-    # ---- pass 1 of the listed pairs on the device: one enqueue, one synchronisation, one read-back ----
-    f64, i32 = torch.float64, torch.int32
-    g = dict(dist=torch.empty(L, dtype=f64, device=dev), flags=torch.empty(L, dtype=i32, device=dev), yaw=torch.empty(L, dtype=f64, device=dev),
-             sim=torch.empty(L, dtype=f64, device=dev), T_ij=torch.empty((L, 16), dtype=f64, device=dev),
-             pairs=torch.empty((L, 2), dtype=i32, device=dev), T_ref=torch.empty((L, 16), dtype=f64, device=dev),
-             enable=torch.empty(L, dtype=i32, device=dev), todo_off=torch.zeros(nb + 1, dtype=i32, device=dev))
-    gp = grid_gate_params(sm_params.submap_radius, sm_io.skip_distance, d, sm_params.submap_descriptor_thresh if d else 0.0,
-                          False, sm_params.single_robot_lc_time_thresh)
-    gate_kw = dict(time_ptr=ptr(t["time"]), desc_ptr=ptr(t["desc"]), pos_gt_ptr=ptr(t["gt"]), has_gt_ptr=ptr(t["has"]))
+    # ---- pass 1 of the listed pairs on the device: one enqueue, one synchronisation, one read-back.  With stacked descriptors the
+    # similarity of the WHOLE blocks, then the gate that reads it at the listed pairs ----
+    one_pool = _session_pool(torch, sess, u.lv)
+    g, gp, gate_kw = _session_pass1_front(torch, ctx, sess, u, sub_off, blk, pair_off, L, one_pool, sim_total=total)
     if aabb_mode:
-        t.update(row0=up(sm_row), count=up(sm_cnt), T_oc=up(cat(lambda hs: hs["T_oc"], (16,))), box=torch.empty((len(sm_cnt), 6), dtype=f64, device=dev))
-    if stacked:
-        live_f = sorted(rows_of)
-        fdesc = p[live_f[0]].frame_desc_dev if len(live_f) == 1 else torch.cat([p[r].frame_desc_dev for r in live_f], dim=0)
-        fmask = torch.cat([p[r].frame_mask[rows_of[r]].reshape(-1) for r in live_f]).contiguous()
-        nfr = {r: int(p[r].frame_desc_dev.shape[0]) for r in live_f}
-        flo = dict(zip(live_f, np.concatenate([[0], np.cumsum([nfr[r] for r in live_f])]).astype(np.int64).tolist()))
-        mof = dict(zip(live_f, np.concatenate([[0], np.cumsum([int(counts[r]) * ((nfr[r] + 63) // 64) for r in live_f])]).astype(np.int64).tolist()))
-        frame_lo = np.array([flo.get(r, 0) for r, _ in views], dtype=np.int32)
-        frame_n = np.array([nfr.get(r, 0) for r, _ in views], dtype=np.int32)
-        mask_off = np.array([mof.get(r, 0) for r, _ in views], dtype=np.int64)
-        t.update(frame_lo=up(frame_lo), frame_n=up(frame_n), mask_off=up(mask_off), dense_sim=torch.empty(total, dtype=f64, device=dev))
-    wait_torch()                                             # the uploads are in place before the library's stream reads them
-    if aabb_mode:
-        ctx.session_boxes_dev(len(sm_cnt), int(pool.shape[1]), pool.data_ptr(), ptr(t["row0"]), ptr(t["count"]), ptr(t["T_oc"]), ptr(t["box"]))
         gate_kw["box_ptr"] = ptr(t["box"])
-    if stacked:                                              # the similarity of the WHOLE blocks, then the gate that reads it at the listed pairs
-        gp.desc_thresh = float(sm_params.submap_descriptor_thresh)
-        ctx.session_stacked_sim_dev(int(fdesc.shape[1]), int(fdesc.shape[0]), ptr(fdesc), ptr(fmask), frame_lo, frame_n, mask_off, sub_off, blk, pair_off,
-                                    ptr(t["frame_lo"]), ptr(t["frame_n"]), ptr(t["mask_off"]), ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]),
-                                    t["dense_sim"].data_ptr())
-        gate_kw["sim_in_ptr"] = t["dense_sim"].data_ptr()
     ctx.session_gate_list_dev(gp, sub_off, blk, pair_off, lst, ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]), ptr(t["list"]), ptr(t["pos"]), ptr(t["T_w"]),
                               *[g[k].data_ptr() for k in ("dist", "flags", "yaw", "sim", "T_ij", "pairs", "T_ref", "enable", "todo_off")], **gate_kw)
     ctx.sync()
@@ -1703,7 +1665,7 @@ def submap_align_session_update(state, sm_params, pools, touched=None, robot_pai
         if hi == lo:                                             # nothing of this block is listed: it is carried over as it is
             fresh.append(None); nearby.append(None); local.append(np.zeros((0, 2), dtype=np.int64)); at.append(np.zeros(0, dtype=np.int64))
             continue
-        F = _GridResults(prm[b], sm_io, hi - lo, 1)
+        F = _GridResults(prm[b], sess.sm_io, hi - lo, 1)
         flags = h["flags"][lo:hi].reshape(-1, 1)
         near, todo = (flags & _abi.ROMAN_GRID_NEARBY) != 0, (flags & _abi.ROMAN_GRID_TODO) != 0
         F.pass1(h["dist"][lo:hi].reshape(-1, 1), near, (flags & _abi.ROMAN_GRID_SKIP) != 0, (flags & _abi.ROMAN_GRID_GATED) != 0,
@@ -1716,33 +1678,17 @@ def submap_align_session_update(state, sm_params, pools, touched=None, robot_pai
     if B == 0:
         return remember({blocks[b]: merged(b, fresh[b]) for b in range(nb)})
 
-    # ---- ONE batch over the pools: the problems in compact order, as in submap_align_session ----
-    prob = sm_row[gpairs[:, 0]], sm_cnt[gpairs[:, 0]], sm_row[gpairs[:, 1]], sm_cnt[gpairs[:, 1]]
-    kmax = int(max(1, np.max(np.minimum(prob[1], prob[3]))))
-    of_self = np.concatenate([np.full(int(todo_off[b + 1] - todo_off[b]), r == s, dtype=bool) for b, (r, s) in enumerate(blocks)])
-    sel = np.nonzero(of_self)[0]
-    if len(sel):
-        ids_dev = _one_storage(torch, [p[r].ids_dev for r in live])
-        if ids_dev is None or int(ids_dev.shape[0]) != int(pool.shape[0]):
-            ids_dev = torch.cat([p[r].ids_dev if p[r].ids_dev is not None else torch.zeros(int(p[r].pool.shape[0]), dtype=torch.int64, device=dev) for r in live])
-        pool, *prob = _drop_shared_over_pool(torch, ctx, pool, ids_dev, *prob, sel, wait_torch)
-    batch = AlignmentBatch(np.broadcast_to(np.float64(0.0), tuple(pool.shape)), prob[0].astype(np.int64), prob[1].astype(np.int32), prob[2].astype(np.int64),
-                           prob[3].astype(np.int32), pair_index=gpairs)
-    res, per_pair = _register_over_pool(torch, ctx, registration, sm_params, sm_io, pool, batch, kmax, g, B, up(FLh), up(FRh), wait_torch, num_solutions)
+    # ---- ONE batch over the ONE pool, as in submap_align_session; a block's records into its one-column grid ----
+    parts, per_pair = _session_register(torch, ctx, sess, u, gpairs, todo_off, one_pool, g)
     out = {}
-    acc = np.asarray(res.accepted, dtype=np.int64)
-    for b in range(nb):
-        lo, hi = int(todo_off[b]), int(todo_off[b + 1])
-        part = LoopClosureResult(res.assoc[lo:hi], res.T[lo:hi], res.status[lo:hi], res.stats[lo:hi], res.records[lo:hi],
-                                 acc[(acc >= lo) & (acc < hi)] - lo)
-        if num_solutions is not None:
-            part.hypotheses = res.hypotheses[lo:hi]
+    for b, part in enumerate(parts):
+        n = len(at[b])
         edges = Ms[b].empty_edges()
-        if hi > lo:
-            edges = _records_into_results(fresh[b], part, at[b], np.zeros(hi - lo, dtype=np.int64), nearby[b])
+        if n:
+            edges = _records_into_results(fresh[b], part, at[b], np.zeros(n, dtype=np.int64), nearby[b])
             if edges is not None:                                # (row of the one-column grid -> the pair it stands for)
                 edges["pairs"] = lst[int(cut[b]):int(cut[b + 1]), 1:][edges["pairs"][:, 0]].astype(np.int64).reshape(-1, 2)
-        out[blocks[b]] = merged(b, fresh[b], fresh_edges=edges, fresh_hyps=_hypotheses_of(part, local[b][:, 0], local[b][:, 1]), timing=[per_pair] * (hi - lo))
+        out[blocks[b]] = merged(b, fresh[b], fresh_edges=edges, fresh_hyps=_hypotheses_of(part, local[b][:, 0], local[b][:, 1]), timing=[per_pair] * n)
     return remember(out)
 
 

@@ -862,14 +862,45 @@ class Context:
                             pairs_ptr, T_ref_ptr, enable_ptr, n_todo_ptr)
 
     # ------------------------------------------------------------------ pass 1 of every robot pair of a session
+    _TILE_OFF = (np.int64, (-1,), " and tile_off")           # the last table of the tile gate: one entry per block and one
+    _PAIR_LIST = (np.int32, (-1, 3), None)                   # ... and of the list gate: of any length
+
     @staticmethod
-    def _session_gate_tables(sub_off, blocks, pair_off, tile_off):
+    def _session_gate_tables(sub_off, blocks, pair_off, last, dtype, shape, per_block):
+        """The tables of a session gate as the C entries take them; `last`: tile_off or the pair list, of `dtype` and `shape`, and
+        with `per_block` (its name in the refusal) of nb + 1 entries.  -> (sub_off, blocks, pair_off, last, R, nb)."""
         sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
-        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); tile_off = np.ascontiguousarray(tile_off, dtype=np.int64).reshape(-1)
+        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); last = np.ascontiguousarray(last, dtype=dtype).reshape(shape)
         R, nb = len(sub_off) - 1, len(blocks)
-        if R < 0 or len(pair_off) != nb + 1 or len(tile_off) != nb + 1:
-            raise ValueError("sub_off must hold R + 1 entries, pair_off and tile_off nb + 1")
-        return sub_off, blocks, pair_off, tile_off, R, nb
+        if R < 0 or len(pair_off) != nb + 1 or (per_block and len(last) != nb + 1):
+            raise ValueError(f"sub_off must hold R + 1 entries, pair_off{per_block or ''} nb + 1")
+        return sub_off, blocks, pair_off, last, R, nb
+
+    @staticmethod
+    def _session_gate_arrays(gparams, sub_off, pos, T_w, time, desc, pos_gt, has_gt, box, sim_in, n_sim):
+        """The per-submap arrays of a session gate, contiguous and checked against the tables: one entry per submap of the session
+        (sub_off[R]), has_gt one per robot, sim_in `n_sim` entries -> (pos, T_w, time, desc, pos_gt, has_gt, box, sim_in)."""
+        R = len(sub_off) - 1
+        pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
+        T_w = _f64(T_w).reshape(-1, 16)
+        time = None if time is None else _f64(time).reshape(-1)
+        desc = None if desc is None else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
+        pos_gt = None if pos_gt is None else _f64(pos_gt).reshape(-1, 3)
+        has_gt = None if has_gt is None else np.ascontiguousarray(has_gt, dtype=np.int32).reshape(-1)
+        if T_w.shape[0] != S or (time is not None and time.shape[0] != S) or (pos_gt is not None and pos_gt.shape[0] != S) or \
+                (has_gt is not None and has_gt.shape[0] != R) or int(sub_off[-1]) != S:
+            raise ValueError("the per-submap arrays must hold one entry per submap of the session (sub_off[R]), has_gt one per robot")
+        if desc is not None and gparams.desc_dim > 0 and desc.shape[1] != gparams.desc_dim:
+            raise ValueError("desc must be (S, desc_dim)")
+        if sim_in is not None:
+            sim_in = _f64(sim_in).reshape(-1)
+            if sim_in.shape[0] != n_sim:
+                raise ValueError("sim_in must hold pair_off[nb] entries")
+        if box is not None:
+            box = _f64(box).reshape(-1, 6)
+            if box.shape[0] != S:
+                raise ValueError("box must hold one row per submap of the session")
+        return pos, T_w, time, desc, pos_gt, has_gt, box, sim_in
 
     @staticmethod
     def _session_gate_entry(box, sim_in):
@@ -887,32 +918,15 @@ class Context:
         outputs may be handed in, as grid_gate() takes them.  sim_in (pair_off[nb],): the similarity of every pair is given
         (roman_session_gate_sim; gparams.desc_dim must be 0) and comes back as `sim`.  box (S, 6): the bounding-box gate
         (roman_session_gate_aabb, DESIGN.md §4.16: session_gate_aabb() below).  -> SessionGateResult."""
-        sub_off, blocks, pair_off, tile_off, R, nb = self._session_gate_tables(sub_off, blocks, pair_off, tile_off)
-        pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
-        T_w = _f64(T_w).reshape(-1, 16)
-        time = None if time is None else _f64(time).reshape(-1)
-        desc = None if desc is None else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
-        pos_gt = None if pos_gt is None else _f64(pos_gt).reshape(-1, 3)
-        has_gt = None if has_gt is None else np.ascontiguousarray(has_gt, dtype=np.int32).reshape(-1)
-        if T_w.shape[0] != S or (time is not None and time.shape[0] != S) or (pos_gt is not None and pos_gt.shape[0] != S) or \
-                (has_gt is not None and has_gt.shape[0] != R) or int(sub_off[-1]) != S:
-            raise ValueError("the per-submap arrays must hold one entry per submap of the session (sub_off[R]), has_gt one per robot")
-        if desc is not None and gparams.desc_dim > 0 and desc.shape[1] != gparams.desc_dim:
-            raise ValueError("desc must be (S, desc_dim)")
+        sub_off, blocks, pair_off, tile_off, R, nb = self._session_gate_tables(sub_off, blocks, pair_off, tile_off, *self._TILE_OFF)
         B = max(int(pair_off[-1]), 0)
+        pos, T_w, time, desc, pos_gt, has_gt, box, sim_in = self._session_gate_arrays(gparams, sub_off, pos, T_w, time, desc, pos_gt, has_gt, box, sim_in, B)
         pairs = _given(pairs, (B, 2), np.int32, -1); T_ref = _given(T_ref, (B, 4, 4), np.float64, np.nan); enable = _given(enable, (B,), np.int32, -1)
-        dist = np.zeros(B); flags = np.zeros(B, dtype=np.int32); yaw = np.zeros(B); sim = np.zeros(B); T_ij = np.zeros((B, 4, 4))
+        dist = np.zeros(B); flags = np.zeros(B, dtype=np.int32); yaw = np.zeros(B); T_ij = np.zeros((B, 4, 4))
         todo_off = np.zeros(nb + 1, dtype=np.int32)
         self._generation += 1
         given = sim_in is not None
-        if given:
-            sim = _f64(sim_in).reshape(-1).copy()
-            if sim.shape[0] != B:
-                raise ValueError("sim_in must hold pair_off[nb] entries")
-        if box is not None:
-            box = _f64(box).reshape(-1, 6)
-            if box.shape[0] != S:
-                raise ValueError("box must hold one row per submap of the session")
+        sim = sim_in.copy() if given else np.zeros(B)        # (a given similarity comes back as `sim`)
         # a given similarity travels behind the outputs: the desc and sim slots are then empty
         fn, tail = self._session_gate_entry(box, sim if given else None)
         rc = getattr(self._lib, fn)(self._h, C.byref(gparams), R, _ptr(sub_off), _ptr(pos), _ptr(pos_gt), _ptr(has_gt), _ptr(T_w), _ptr(time),
@@ -930,7 +944,7 @@ class Context:
         all submaps of the session, its two columns are lc_tail_dev's iL and iR.  sim_in_ptr: the similarity of every pair is
         given (roman_session_gate_sim_dev): gparams.desc_dim must be 0, desc_ptr is not read, sim_ptr not written.
         box_ptr: the bounding-box gate (roman_session_gate_aabb_dev, DESIGN.md §4.16: session_gate_aabb_dev() below)."""
-        sub_off, blocks, pair_off, tile_off, R, nb = self._session_gate_tables(sub_off, blocks, pair_off, tile_off)
+        sub_off, blocks, pair_off, tile_off, R, nb = self._session_gate_tables(sub_off, blocks, pair_off, tile_off, *self._TILE_OFF)
         fn, tail = self._session_gate_entry(box_ptr, sim_in_ptr)
         rc = getattr(self._lib, fn + "_dev")(self._h, C.byref(gparams), R, _vp(sub_off_ptr), _ptr(sub_off), _vp(pos_ptr), _vp(pos_gt_ptr), _vp(has_gt_ptr),
                                              _vp(T_w_ptr), _vp(time_ptr), _vp(desc_ptr), nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off),
@@ -978,41 +992,15 @@ class Context:
                               dist_ptr, flags_ptr, yaw_deg_ptr, sim_ptr, T_ij_ptr, pairs_ptr, T_ref_ptr, enable_ptr, todo_off_ptr, box_ptr=box_ptr, **kw)
 
     # ------------------------------------------------------------------ pass 1 of a session over an explicit pair list
-    @staticmethod
-    def _session_list_tables(sub_off, blocks, pair_off, pair_list):
-        sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1); blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 4)
-        pair_off = np.ascontiguousarray(pair_off, dtype=np.int64).reshape(-1); pair_list = np.ascontiguousarray(pair_list, dtype=np.int32).reshape(-1, 3)
-        R, nb = len(sub_off) - 1, len(blocks)
-        if R < 0 or len(pair_off) != nb + 1:
-            raise ValueError("sub_off must hold R + 1 entries, pair_off nb + 1")
-        return sub_off, blocks, pair_off, pair_list, R, nb
-
     def session_gate_list(self, gparams, sub_off, blocks, pair_off, pair_list, pos, T_w, time=None, desc=None, pos_gt=None, has_gt=None,
                           pairs=None, T_ref=None, enable=None, sim_in=None, box=None):
         """Host-pointer pass 1 over a pair list (roman_session_gate_list): the tables as session_tables() gives them (without
         tile_off), pair_list (L, 3) rows (block, i, j) as session_pair_list() cuts them — both passed as they are: the library
         checks them; the per-submap arrays as session_gate() takes them.  sim_in (pair_off[nb],): the similarity of every pair
         of every block, dense; box (S, 6): the bounding-box gate.  The compact outputs may be handed in.  -> SessionGateListResult."""
-        sub_off, blocks, pair_off, pair_list, R, nb = self._session_list_tables(sub_off, blocks, pair_off, pair_list)
-        pos = _f64(pos).reshape(-1, 3); S = pos.shape[0]
-        T_w = _f64(T_w).reshape(-1, 16)
-        time = None if time is None else _f64(time).reshape(-1)
-        desc = None if desc is None or sim_in is not None else (_f64(desc).reshape(S, -1) if S else np.zeros((0, max(int(gparams.desc_dim), 0))))
-        pos_gt = None if pos_gt is None else _f64(pos_gt).reshape(-1, 3)
-        has_gt = None if has_gt is None else np.ascontiguousarray(has_gt, dtype=np.int32).reshape(-1)
-        if T_w.shape[0] != S or (time is not None and time.shape[0] != S) or (pos_gt is not None and pos_gt.shape[0] != S) or \
-                (has_gt is not None and has_gt.shape[0] != R) or int(sub_off[-1]) != S:
-            raise ValueError("the per-submap arrays must hold one entry per submap of the session (sub_off[R]), has_gt one per robot")
-        if desc is not None and gparams.desc_dim > 0 and desc.shape[1] != gparams.desc_dim:
-            raise ValueError("desc must be (S, desc_dim)")
-        if sim_in is not None:
-            sim_in = _f64(sim_in).reshape(-1)
-            if sim_in.shape[0] != max(int(pair_off[-1]), 0):
-                raise ValueError("sim_in must hold pair_off[nb] entries")
-        if box is not None:
-            box = _f64(box).reshape(-1, 6)
-            if box.shape[0] != S:
-                raise ValueError("box must hold one row per submap of the session")
+        sub_off, blocks, pair_off, pair_list, R, nb = self._session_gate_tables(sub_off, blocks, pair_off, pair_list, *self._PAIR_LIST)
+        pos, T_w, time, desc, pos_gt, has_gt, box, sim_in = self._session_gate_arrays(
+            gparams, sub_off, pos, T_w, time, None if sim_in is not None else desc, pos_gt, has_gt, box, sim_in, max(int(pair_off[-1]), 0))
         L = len(pair_list)
         pairs = _given(pairs, (L, 2), np.int32, -1); T_ref = _given(T_ref, (L, 4, 4), np.float64, np.nan); enable = _given(enable, (L,), np.int32, -1)
         dist = np.zeros(L); flags = np.zeros(L, dtype=np.int32); yaw = np.zeros(L); sim = np.zeros(L); T_ij = np.zeros((L, 4, 4))
@@ -1032,7 +1020,7 @@ class Context:
         hold L entries, in list order; the compact ones have capacity L.  sim_in_ptr: the similarity of every pair of every
         block at its dense position (what session_stacked_sim_dev writes); box_ptr: the bounding-box gate.  A pure enqueue on
         the context's stream; complete after sync()."""
-        sub_off, blocks, pair_off, pair_list, R, nb = self._session_list_tables(sub_off, blocks, pair_off, pair_list)
+        sub_off, blocks, pair_off, pair_list, R, nb = self._session_gate_tables(sub_off, blocks, pair_off, pair_list, *self._PAIR_LIST)
         rc = self._lib.roman_session_gate_list_dev(self._h, C.byref(gparams), R, _vp(sub_off_ptr), _ptr(sub_off), _vp(pos_ptr), _vp(pos_gt_ptr), _vp(has_gt_ptr),
                                                    _vp(T_w_ptr), _vp(time_ptr), _vp(desc_ptr), nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off),
                                                    len(pair_list), _vp(list_ptr), _ptr(pair_list), _vp(box_ptr), _vp(sim_in_ptr), _vp(dist_ptr), _vp(flags_ptr),

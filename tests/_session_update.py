@@ -2,26 +2,32 @@
 
 `SessionUpdateStubContext` adds roman_session_gate_list_dev to tests/_session.SessionStubContext: the whole-grid oracle of
 tests/_session.py (tests/_grid_gate_oracle.py per block) read at the listed pairs, the compact list in list order.  It records
-every list it is handed.  `pool_prefix()` cuts a pool back to its first k submaps — a session at an earlier step —, `equal()`
-compares two results of one block entry by entry (everything but timing_list)."""
+every list it is handed.  With boxes or a given similarity the whole-grid oracle is the one of tests/_session_aabb.py or of
+tests/_session_stacked.py (`SessionUpdateAabbStubContext`, `SessionUpdateStackedStubContext`).  `pool_prefix()` cuts a pool
+back to its first k submaps — a session at an earlier step —, `equal()` compares two results of one block entry by entry
+(everything but timing_list)."""
 import dataclasses
 
 import numpy as np
 
 import _grid_gate_oracle as go
 import _session as ss
+import _session_aabb as sx
+import _session_stacked as sst
 from _stub_context import _view
 
 
-class SessionUpdateStubContext(ss.SessionStubContext):
-    def __init__(self, dim=3):
-        super().__init__(dim)
+class ListGateCalls:
+    """roman_session_gate_list_dev for any stand-in context: mixed in IN FRONT of the context that serves the rest of the mode."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
         self.lists, self.totals = [], []
 
     def session_gate_list_dev(self, gp, sub_off, blocks, pair_off, pair_list, sub_off_ptr, blocks_ptr, pair_off_ptr, list_ptr, pos, T_w,
                               dist, flags, yaw, sim, T_ij, pairs, T_ref, enable, todo_off, time_ptr=None, desc_ptr=None, pos_gt_ptr=None, has_gt_ptr=None,
                               sim_in_ptr=None, box_ptr=None):
-        assert sim_in_ptr is None and box_ptr is None, "the stand-in serves the radius gate"
+        assert sim_in_ptr is None or gp.desc_dim == 0, "with a given similarity desc_dim must be 0"
         self.order.append("session_gate_list")
         R, nb, S, d, L = len(sub_off) - 1, len(blocks), int(sub_off[-1]), int(gp.desc_dim), len(pair_list)
         want = ss.tables(np.diff(sub_off).tolist(), [tuple(b[:3]) for b in np.asarray(blocks).tolist()])
@@ -37,8 +43,18 @@ class SessionUpdateStubContext(ss.SessionStubContext):
                    T_w=_view(T_w, (S, 4, 4), np.float64), time=_view(time_ptr, (S,), np.float64) if time_ptr else None,
                    desc=_view(desc_ptr, (S, d), np.float64) if d else None)
         has_gt = _view(has_gt_ptr, (R,), np.int32) if has_gt_ptr else np.zeros(R, np.int32)
-        o = ss.session_gate_oracle(arr, sub_off, blocks, has_gt, gp.radius, gp.skip_distance, gp.desc_thresh, gp.lc_time_thresh)
-        blk = np.asarray(blocks).reshape(-1, 4)
+        given = _view(sim_in_ptr, (int(pair_off[-1]),), np.float64).copy() if sim_in_ptr else None
+        if box_ptr:                                          # the whole-grid oracle of tests/_session_aabb.py
+            o = sx.session_gate_aabb_oracle(arr, _view(box_ptr, (S, 6), np.float64), sub_off, blocks, has_gt, gp.skip_distance, gp.desc_thresh,
+                                            gp.lc_time_thresh, sim_in=given, pair_off=pair_off)
+        elif given is not None:                              # tests/_session_stacked.py: the gate without descriptors, its classes from the similarity
+            o = ss.session_gate_oracle(arr, sub_off, blocks, has_gt, gp.radius, gp.skip_distance, 0.0, gp.lc_time_thresh)
+            o["flags"] = sst.gate_from_sim(o, given, sub_off, blocks, gp.desc_thresh, arr["time"] if time_ptr else np.zeros(S), gp.lc_time_thresh)["flags"]
+        else:
+            o = ss.session_gate_oracle(arr, sub_off, blocks, has_gt, gp.radius, gp.skip_distance, gp.desc_thresh, gp.lc_time_thresh)
+        if given is not None:                                # (sim[l] is the pair's entry of sim_in)
+            o["sim"] = given
+        blk =np.asarray(blocks).reshape(-1, 4)
         b, i, j = (lst[:, k].astype(np.int64) for k in range(3))
         n1 = np.diff(sub_off)[blk[:, 1]].astype(np.int64)
         idx = pair_off[b] + i * n1[b] + j
@@ -59,9 +75,21 @@ class SessionUpdateStubContext(ss.SessionStubContext):
         _view(todo_off, (nb + 1,), np.int32)[:] = np.concatenate([[0], np.cumsum(np.bincount(b[todo], minlength=nb))])
 
 
+class SessionUpdateStubContext(ListGateCalls, ss.SessionStubContext):
+    """The radius gate."""
+
+
+class SessionUpdateAabbStubContext(ListGateCalls, sx.SessionAabbStubContext):
+    """The bounding-box gate: roman_session_boxes_dev in front of the list gate, which reads the boxes."""
+
+
+class SessionUpdateStackedStubContext(ListGateCalls, sst.SessionStackedStubContext):
+    """Stacked frame descriptors: roman_session_stacked_sim_dev over whole blocks in front of the list gate, which reads it."""
+
+
 def pool_prefix(pool, k, blank=()):
-    """The first k submaps of `pool` as a pool of its own (rows, counts, ids, centres, descriptors); `blank`: submaps that hold
-    nothing yet (count 0)."""
+    """The first k submaps of `pool` as a pool of its own (rows, counts, ids, centres, descriptors, frame masks and counts — the
+    frame table is the map's, one row per frame, and stays whole); `blank`: submaps that hold nothing yet (count 0)."""
     c = pool.centers
     cen = dataclasses.replace(c, **{f.name: getattr(c, f.name)[:k] for f in dataclasses.fields(c)})
     count = pool.count[:k].copy()

@@ -84,6 +84,51 @@ def test_update_equals_the_full_session_call_after_every_step(desc, gt_on):
         su.equal(again[key], want[key], sim_atol=1e-12)
 
 
+@pytest.mark.parametrize("mode", ["aabb", "stacked"])
+def test_update_equals_the_full_session_call_behind_boxes_and_stacked_similarity(mode):
+    """The bounding-box gate (the pools of tests/test_session_aabb_cpu.py: robots 0 and 2 force-filled, robot 1 cut by radius, a
+    descriptor, ground truth on robot 0) and stacked frame descriptors (the pools of tests/test_session_stacked_cpu.py): a full
+    first call over every robot's submaps but the last, then one appending step — after each, every block equals
+    submap_align_session on the same stand-in, and the call the mode needs comes first on the context."""
+    import test_session_aabb_cpu as ta
+    import test_session_stacked_cpu as ts
+    io = sa.SubmapAlignIO(lc_association_thresh=4, skip_distance=45.0)
+    base = dict(method="roman", semantics_dim=D, submap_radius=15.0, submap_descriptor_thresh=0.8, single_robot_lc=True, single_robot_lc_time_thresh=40.0)
+    if mode == "aabb":
+        reg, final = make_pools('mean_semantic', 3)
+        for r in (0, 2):
+            final[r] = ta.fill_pool(reg, r, 'mean_semantic')
+        p = SubmapAlignParams(**base, force_fill_submaps=True, submap_descriptor='mean_semantic')
+        stand_in, first_call, gt_final = su.SessionUpdateAabbStubContext, "session_boxes", [gt_for(final[0], 70), None, None]
+    else:
+        reg, final = ts.make_pools(3)
+        p = SubmapAlignParams(**base, submap_descriptor=ts.MODE, frame_descriptor_dist=10.0)
+        stand_in, first_call, gt_final = su.SessionUpdateStackedStubContext, "session_stacked_sim", [None] * 3
+    blocks = [(r, s) for r in range(3) for s in range(r, 3)]
+    state = sa.SessionAlignState()
+    aligned, decided = 0, False
+    for step in range(2):
+        pools = [su.pool_prefix(q, len(q.count) - 1 + step) for q in final]
+        gt = [None if g is None else g[:len(q.count)] for g, q in zip(gt_final, pools)]
+        calls = []
+        for call in (lambda: sa.submap_align_session_update(state, p, pools, None, None, io, registration=reg, gt_poses=gt),
+                     lambda: sa.submap_align_session(p, pools, None, io, registration=reg, gt_poses=gt)):
+            ctx = stand_in(); reg.set_context(ctx)
+            ctx.n_objects = int(sum(q.pool.shape[0] for q in pools if len(q.nonempty)))
+            calls.append((ctx, call()))
+        (ctx, got), (full_ctx, want) = calls
+        assert list(got) == list(want) == blocks
+        for key in blocks:
+            su.equal(got[key], want[key], sim_atol=1e-12)
+            aligned += int((want[key].clipper_num_associations >= 4).sum())
+        decided = decided or ts.gated_and_todo(want, 0.8)
+        assert ctx.order[0] == full_ctx.order[0] == first_call and ctx.order[1] == "session_gate_list"
+        assert ctx.session_gates == 0 and getattr(ctx, "session_aabb_gates", 0) == 0
+        assert len(ctx.lists) == 1 and (len(ctx.lists[0]) == ctx.totals[0]) == (step == 0), step      # the step lists the pairs of the new submaps only
+    assert aligned >= 4, "hardly a pair aligned: the comparison would show nothing"
+    assert decided, "no block holds a GATED and a TODO pair: the similarity decides nothing"
+
+
 def test_a_partner_going_from_odd_to_even_touches_the_whole_alternating_robot():
     """Robot 0's poses alternate under flattening (tests/test_session_cpu.py): when robot 1 grows from one submap to two, the pose
     robot 0's submaps are read with changes although none of its inputs did — all of robot 0 is listed again, in every block."""
