@@ -1844,7 +1844,8 @@ __device__ __forceinline__ void count_rows_lds(const DevParams& D, const ProbDes
 // four rows' bins of one table column are ONE 8-byte LDS word: two 8-byte gathers per 64 columns serve 256 pair tests.  Bins are
 // epsilon / 32 wide (15 bits; NaN entries and everything beyond the range share the last bin), compared as packed 16-bit halves;
 // the survivors (~6 % of the columns) are compacted into a per-wave LDS queue, and the EXISTING exact f64 gate runs on the queue,
-// 64 candidates at a time with every lane busy, its operands fetched from the tables in memory (L2) for those few; a passing
+// 64 candidates at a time with every lane busy, its two table entries fetched from memory (L2) for those few and the two heights
+// of the z gate from a per-object table in LDS (n1 + 1 + n2 doubles per workgroup, indexed like the bin table); a passing
 // candidate sets its bit in the row's mask words in LDS (ds_or_b64), which go out coalesced at the end of the rows.
 // The prefilter is a superset of the gate by construction: q(x) = trunc(min(x * invw, 32767)) is monotone, so |a - b| <= eps'
 // gives |q(a) - q(b)| <= ceil(eps' * invw + rounding) <= 32 + 1; pre_K is 34.  A false positive (the last bin's far / NaN pairs
@@ -1855,7 +1856,7 @@ __device__ __forceinline__ void count_rows_lds(const DevParams& D, const ProbDes
 constexpr int PRE_NR = 4;                 // rows a wave sweeps together (their bins share an LDS word)
 constexpr int PRE_COLPAD = 128;           // sentinel columns behind the column tile (a sweep starts at the rows' own 64-column block and advances by 128)
 constexpr int PRE_QCAP = 640;             // queue entries: the exact gate runs while 256 are waiting; a window's candidates go in at once when they fit (else 64 at a time)
-constexpr int PRE_WAVES = 16;             // waves per workgroup of the prefiltered sweep (118 registers per lane: no spills; 12 waves measured 7 % slower)
+constexpr int PRE_WAVES = 16;             // waves per workgroup of the prefiltered sweep (127 registers per lane: no spills; 12 waves measured 7 % slower)
 // per-wave LDS of the prefiltered sweep: PRE_NR mask rows (TC / 64 words), the packed bin table (n1 + 1 + n2 entries of 8 bytes, ldsPerRow
 // rounded), the queue (16-bit entries), the rows' own data (4 x 32 bytes)
 __host__ __device__ constexpr int count_pre_wave_bytes(int ldsPerRow, int TC)
@@ -1876,6 +1877,7 @@ __device__ __forceinline__ void count_rows_pre(const DevParams& D, const ProbDes
                                                PreRow* rowinfo,
                                                unsigned long long* __restrict__ mbase,
                                                const double* __restrict__ gZa, const double* __restrict__ gZb,
+                                               const double* zT /* LDS, or NULL (no room: gZa / gZb serve instead): the objects' heights, indexed like the packed bin table */,
                                                uint32_t* degS /* LDS, or NULL: the full degree of every live row, counted as the pairs pass (whole problems only) */)
 {
     constexpr int NR = PRE_NR;
@@ -1888,8 +1890,14 @@ __device__ __forceinline__ void count_rows_pre(const DevParams& D, const ProbDes
     uint2 ra[NR], rb[NR];
     int pi[NR], pj[NR];                                         // objects of the rows whose bin rows are in ra / rb
     double pzi = 0.0, pzj = 0.0;                                // lane x < NR: the heights of row x's two objects
+    auto fetch_z = [&](int r_) {                                // (the live row's own entries of the pools are its objects' heights: the same bits either way)
+        if (!GM) return;
+        const int kz_ = row0 + min(r_ + min(lane, NR - 1), nrows - 1);
+        if (zT != nullptr) { const uint32_t pk_ = cIJ[kz_]; pzi = zT[pk_ & 0xffffu]; pzj = zT[pk_ >> 16]; }
+        else { pzi = gZa[kz_]; pzj = gZb[kz_]; }
+    };
     auto fetch_tab = [&](int r_) {
-        if (GM) { const int kz_ = row0 + min(r_ + min(lane, NR - 1), nrows - 1); pzi = gZa[kz_]; pzj = gZb[kz_]; }
+        fetch_z(r_);
 #pragma unroll
         for (int x = 0; x < NR; ++x) {
             const int k_ = row0 + min(r_ + x, nrows - 1);
@@ -1919,22 +1927,29 @@ __device__ __forceinline__ void count_rows_pre(const DevParams& D, const ProbDes
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
     // The exact gate over up to 256 queue entries starting at `base`: four candidates per lane, the operands of all four requested
-    // (tables and heights from memory: L2) before the first is used — a single chain's round trip would otherwise be all a wave does
+    // (table entries from memory: L2; heights from the per-object table in LDS, or from memory where the launch had no room for it)
+    // before the first is used — a single chain's round trip would otherwise be all a wave does
     auto consume = [&](uint32_t base, uint32_t n) {
         constexpr int CH = 4;
         uint32_t e[CH]; double a[CH], bb[CH], za[CH], zb[CH];
+        auto gather = [&](auto zlds_) {
 #pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const uint32_t idx = (uint32_t)(c * WAVE + lane);
-            e[c] = idx < n ? (uint32_t)queue[base + idx] : 0xffffu;     // (0x3fff: a column beyond every live set: inactive below)
-            const uint32_t qq = e[c] & 0x3fffu;
-            const bool act = (int)qq < L;                       // (a sentinel column can only get here through the last bin)
-            const uint32_t pk = cIJ[act ? qq : 0u];
-            const PreRow* ri = rowinfo + (e[c] >> 14);
-            a[c] = TA[ri->rowA + (pk & 0xffffu)];               // (32-bit element offsets: maps of at most 32767 objects take this sweep)
-            bb[c] = TB[ri->rowB + (pk >> 16)];                  // (rowB is short of the row's start by n1 + 1: the packed index carries it)
-            if (GM) { za[c] = gZa[act ? qq : 0u]; zb[c] = gZb[act ? qq : 0u]; }
-        }
+            for (int c = 0; c < CH; ++c) {
+                const uint32_t idx = (uint32_t)(c * WAVE + lane);
+                e[c] = idx < n ? (uint32_t)queue[base + idx] : 0xffffu;     // (0x3fff: a column beyond every live set: inactive below)
+                const uint32_t qq = e[c] & 0x3fffu;
+                const bool act = (int)qq < L;                   // (a sentinel column can only get here through the last bin)
+                const uint32_t pk = cIJ[act ? qq : 0u];
+                const PreRow* ri = rowinfo + (e[c] >> 14);
+                a[c] = TA[ri->rowA + (pk & 0xffffu)];           // (32-bit element offsets: maps of at most 32767 objects take this sweep)
+                bb[c] = TB[ri->rowB + (pk >> 16)];              // (rowB is short of the row's start by n1 + 1: the packed index carries it)
+                if (GM) {
+                    if (decltype(zlds_)::value) { za[c] = zT[pk & 0xffffu]; zb[c] = zT[pk >> 16]; }
+                    else { za[c] = gZa[act ? qq : 0u]; zb[c] = gZb[act ? qq : 0u]; }
+                }
+            }
+        };
+        if (GM && zT != nullptr) gather(std::true_type()); else gather(std::false_type());      // (wave-uniform: the launch's choice)
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             const uint32_t qq = e[c] & 0x3fffu, x = e[c] >> 14;
@@ -2012,7 +2027,7 @@ __device__ __forceinline__ void count_rows_pre(const DevParams& D, const ProbDes
                 pi[x] = __builtin_amdgcn_readfirstlane((int)(pk_ & 0xffffu)); pj[x] = __builtin_amdgcn_readfirstlane((int)(pk_ >> 16) - (n1 + 1));
             }
         }
-        if (!pre && GM) { const int kz_ = row0 + min(r + min(lane, NR - 1), nrows - 1); pzi = gZa[kz_]; pzj = gZb[kz_]; }
+        if (!pre) fetch_z(r);
         if (lane < NR) {                                        // the rows' own objects and heights, for the exact gate
             int i_ = pi[0], j_ = pj[0];
 #pragma unroll
@@ -2155,10 +2170,12 @@ __global__ void __launch_bounds__(PRE ? PRE_WAVES * 64 : 1024) k_count(DevParams
                                                 unsigned long long* __restrict__ maskPool,
                                                 uint32_t* __restrict__ prefPool,
                                                 int TC /* LDS column tile (multiple of 256) */, int ldsPerWave /* doubles: NR table slices */, int RPB,
-                                                const uint16_t* __restrict__ qtabPool /* PRE: the tables as bins (k_tables) */)
+                                                const uint16_t* __restrict__ qtabPool /* PRE: the tables as bins (k_tables) */,
+                                                int zLds /* PRE, GM: the launch's LDS holds the height table (0: the exact gate reads lza / lzb) */)
 {
     // LDS: [GM: cZZ[TC]] cIJ[TC] | per wave NR table slices (n1 + 1 + n2 doubles each)
-    // PRE (NR is ignored: PRE_NR rows per wave; ldsPerWave = entries of the packed bin table): cIJ[TC] | per wave count_pre_wave_bytes()
+    // PRE (NR is ignored: PRE_NR rows per wave; ldsPerWave = entries of the packed bin table): cIJ[TC + PRE_COLPAD] | counter | [whole
+    // problems: degL[TC]] | [zLds: zT[ldsPerWave]] | per wave count_pre_wave_bytes()
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double2* cZZ = reinterpret_cast<double2*>(smem);
     uint32_t* cIJ = reinterpret_cast<uint32_t*>(cZZ + ((GM && !PRE) ? TC : 0));
@@ -2170,7 +2187,10 @@ __global__ void __launch_bounds__(PRE ? PRE_WAVES * 64 : 1024) k_count(DevParams
     const int preBytes = PRE ? count_pre_wave_bytes(ldsPerWave, TC) : 0;
     uint32_t* qctr = cIJ + TC + PRE_COLPAD;                      // (PRE) the rows' hand-out counter, 16 bytes
     uint32_t* degL = cIJ + TC + PRE_COLPAD + 4;                  // (PRE, whole problems) TC row degrees
-    unsigned char* pw = reinterpret_cast<unsigned char*>(cIJ + TC + PRE_COLPAD + 4 + ((PRE && RPB < 0) ? TC : 0)) + (size_t)w * preBytes;
+    // (PRE with the z gate, when the launch has the room: zLds != 0) the objects' heights, ldsPerWave doubles indexed like the packed bin table
+    double* zT = reinterpret_cast<double*>(cIJ + TC + PRE_COLPAD + 4 + ((PRE && RPB < 0) ? TC : 0));
+    const bool zInLds = PRE && GM && zLds != 0;
+    unsigned char* pw = reinterpret_cast<unsigned char*>(zT + (zInLds ? ldsPerWave : 0)) + (size_t)w * preBytes;
     unsigned long long* rmask = reinterpret_cast<unsigned long long*>(pw);
     uint2* qT = reinterpret_cast<uint2*>(rmask + PRE_NR * (TC >> 6));
     uint16_t* queue = reinterpret_cast<uint16_t*>(qT + ldsPerWave);
@@ -2209,14 +2229,18 @@ __global__ void __launch_bounds__(PRE ? PRE_WAVES * 64 : 1024) k_count(DevParams
                 const bool v = q < L;
                 cIJ[q] = v ? ((uint32_t)li[lo + q] | ((uint32_t)(pd.n1 + 1 + lj[lo + q]) << 16)) : ((uint32_t)pd.n1 | ((uint32_t)(pd.n1 + 1) << 16));
                 if (GM && !PRE) cZZ[q] = v ? make_double2(lza[lo + q], lzb[lo + q]) : make_double2(0.0, 0.0);
+                // (PRE) the heights per OBJECT: every live column writes its two objects' entries — columns that share an object store
+                // the same bits (k_live copied them from the object's features), and an object of no live column is never looked up
+                if (zInLds && v) { zT[li[lo + q]] = lza[lo + q]; zT[pd.n1 + 1 + lj[lo + q]] = lzb[lo + q]; }
             }
+            if (zInLds && tid == 0) zT[pd.n1] = 0.0;             // (the sentinel columns' entry)
             if (PRE && tid == 0) *qctr = 0u;
             if (PRE && whole) for (int q = tid; q < L; q += nt) degL[q] = 0u;
             __syncthreads();
             if (PRE) {
                 count_rows_pre<GM>(D, pd, L, it.row0, nrows, qctr, lane, cIJ, TA, TB,
                                    qtabPool + 4 * (int64_t)pd.qtabOff4, qtabPool + 4 * (int64_t)pd.qtabOff4 + (int64_t)pd.n1 * ((pd.n1 + 3) & ~3),
-                                   qT, queue, rmask, TC >> 6, rowinfo, maskPool + mo, lza + lo, lzb + lo, whole ? degL : nullptr);
+                                   qT, queue, rmask, TC >> 6, rowinfo, maskPool + mo, lza + lo, lzb + lo, zInLds ? zT : nullptr, whole ? degL : nullptr);
                 if (whole) {                                    // the problem's degrees, for k_lists (live order)
                     __syncthreads();
                     for (int q = tid; q < L; q += nt) rowCnt[lo + q] = degL[q];

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.hip.h"
@@ -739,7 +740,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     const size_t pairLds = tabLds + (size_t)TCc * colBytesC;
     const int pairGrid = c->num_cu * std::max(1, std::min(2048 / (wpb * 64), (int)(c->lds_max / pairLds)));
     // The one-tile sweep with candidate generation in front of the exact gate (count_rows_pre, round 6): column tile without the z
-    // pairs (the exact gate reads them from memory for the ~6 % of the columns that reach it) + per wave the table slices, their
+    // pairs (the exact gate reads them per object: from a table in LDS sized at the launch, or from memory) + per wave the table slices, their
     // 16-bit bin slices, the candidate queue and the rows' mask words.  Taken when the whole expected live set fits its tile;
     // ROMAN_COUNT_PRE=0 / 1 in the environment forces the plain sweep / the prefilter where it fits (A/B and tests: read per call).
     int preNR = 0, preWpb = 0, preTC = 0; size_t preLds = 0;
@@ -815,15 +816,25 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
             const char* wholeEnv = getenv("ROMAN_COUNT_WHOLE");
             const bool wholeP = usePre && (wholeEnv ? wholeEnv[0] != '0' : B >= c->num_cu) && preLds + (size_t)preTC * 4 <= c->lds_max;
             if (wholeP) degGiven = 1;                            // k_count counts the degrees as the pairs pass: k_lists skips its degree sweep
-            HIPCHK(c, dyn_lds(c, kc, ldsK + (wholeP ? (size_t)preTC * 4 : 0)));
+            // (the prefiltered sweep's exact gate takes the heights of a candidate's two objects from a per-object table in LDS, one
+            //  double per entry of the packed bin table, where that fits without costing a resident workgroup; from memory otherwise:
+            //  ROMAN_COUNT_ZLDS=0 forces the memory path, which maps near the LDS limit take — tests)
+            size_t ldsLaunch = ldsK + (wholeP ? (size_t)preTC * 4 : 0);
+            const size_t zBytes = (size_t)preRow * sizeof(double);
+            const char* zEnv = getenv("ROMAN_COUNT_ZLDS");
+            const bool zLds = usePre && D.gmode != 0 && !(zEnv && zEnv[0] == '0') && ldsLaunch + zBytes <= c->lds_max &&
+                              c->lds_max / (ldsLaunch + zBytes) >= std::min<size_t>(gridK / c->num_cu, c->lds_max / ldsLaunch);
+            if (zLds) ldsLaunch += zBytes;
+            HIPCHK(c, dyn_lds(c, kc, ldsLaunch));
             DevParams a_D = D; const ProbDesc* a_dP = dP; const ProbState* a_dS = dS; const BatchTotals* a_dT = dT; const ItemDesc* a_items = WS.items.as<ItemDesc>();
             const double* a_tab = WS.tabPool.as<double>(); const int32_t* a_li = LP.li; const int32_t* a_lj = LP.lj; const double* a_za = LP.lza; const double* a_zb = LP.lzb;
             uint32_t* a_rc = WS.rowCnt.as<uint32_t>(); unsigned long long* a_mask = WS.maskPool.as<unsigned long long>(); uint32_t* a_pref = WS.prefPool.as<uint32_t>();
             int a_TC = usePre ? preTC : TCc, a_lpw = usePre ? preRow : ldsPerWave;
             int a_RPB = wholeP ? -B : RPB;
             const uint16_t* a_qtab = WS.qtabPool.as<uint16_t>();
-            void* args[] = {&a_D, &a_dP, &a_dS, &a_dT, &a_items, &a_tab, &a_li, &a_lj, &a_za, &a_zb, &a_rc, &a_mask, &a_pref, &a_TC, &a_lpw, &a_RPB, &a_qtab};
-            HIPCHK(c, hipLaunchKernel(kc, dim3(gridK), dim3(wpbK * 64), args, ldsK + (wholeP ? (size_t)preTC * 4 : 0), WS.stream));
+            int a_zLds = zLds ? 1 : 0;
+            void* args[] = {&a_D, &a_dP, &a_dS, &a_dT, &a_items, &a_tab, &a_li, &a_lj, &a_za, &a_zb, &a_rc, &a_mask, &a_pref, &a_TC, &a_lpw, &a_RPB, &a_qtab, &a_zLds};
+            HIPCHK(c, hipLaunchKernel(kc, dim3(gridK), dim3(wpbK * 64), args, ldsLaunch, WS.stream));
         }
     DBG(c, "k_count");
         // Stream-layout problems (kind 0) go from the upper blocks straight to positions and kept-candidate lists in ONE kernel, one
