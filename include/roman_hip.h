@@ -898,6 +898,44 @@ ROMAN_API int roman_session_submaps(roman_ctx_t* ctx, const roman_submap_params_
                                     double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status,
                                     int32_t desc_dim, double* desc_out);
 
+/*
+ * roman_session_submaps_list_dev: roman_session_submaps_dev [REF roman/map/map.py:297-346] for the L LISTED submaps
+ * of a session that grows, rebuilt IN PLACE in outputs that stay in HBM between steps, with a report of which slots changed.  The
+ * first 17 arguments are those of roman_session_submaps_dev, over the whole session as it stands now; then
+ *   L, list    int32[L] HOST: global submap indices g, strictly ascending, each in [0, sub_off[R])
+ *   changed    int32[L] DEVICE or NULL
+ * A PURE ENQUEUE on the context's stream.
+ * LISTED slots: count[g], status[g], the rows [0, count[g]) of pool, src and ids_out and the desc_out row hold bit for bit what
+ * roman_session_submaps_dev writes there for the same inputs (the same per-submap code).  A submap may shrink, so a listed slot is
+ * left WHOLE: its rows [count[g], cap) are set to pool 0.0, src -1, ids_out -1 — the values roman_amd's build_session_pools clears its
+ * tensors to —, and the desc_out row of an EMPTY listed submap is set to NaN (0x7ff8000000000000) in every column.
+ * UNLISTED slots: not one byte is written (or read).
+ * changed[l] = 1 when any byte of slot list[l] — count, status, the cap rows of src, ids_out and pool, the desc_out row — differs from
+ * what the slot held when the call began, else 0; every flag is one workgroup's reduction and one store, independent of any order.
+ * With changed NULL nothing is compared (and the old contents are not read).
+ * Candidates beyond the first 4096 of a submap take scratch for the LISTED submaps of maps with N_r > 4096 only.  Every allocation
+ * and staging is made before the first copy: a failure -> ROMAN_E_NOMEM, nothing is enqueued and the context stays usable.
+ * L == 0 is legal and touches nothing; R == 0, maps without rows and maps without centres stay legal.
+ * Errors (judged on host memory before the context): those of roman_session_submaps_dev; L < 0, a NULL list with L > 0, an entry
+ * outside [0, sub_off[R]), a list that is not strictly ascending -> ROMAN_E_INVALID.
+ */
+ROMAN_API int roman_session_submaps_list_dev(roman_ctx_t* ctx, const roman_submap_params_t* sparams, int32_t R, int32_t F,
+                                             const int64_t* seg_off, const double* seg_feats, const double* seg_times, const int64_t* seg_ids,
+                                             const int32_t* sub_off, const roman_submap_desc_t* descs,
+                                             double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status,
+                                             int32_t desc_dim, double* desc_out,
+                                             int32_t L, const int32_t* list, int32_t* changed);
+
+/* The same with HOST pointers everywhere [REF roman/map/map.py:297-346].  Synchronous: the caller's CURRENT pool, count, src, ids_out,
+   status and desc_out go up first (pool is needed here: it is what `changed` compares with), roman_session_submaps_list_dev runs, and
+   everything comes back, `changed` (int32[L] or NULL) included: an unlisted slot comes back as it was. */
+ROMAN_API int roman_session_submaps_list(roman_ctx_t* ctx, const roman_submap_params_t* sparams, int32_t R, int32_t F,
+                                         const int64_t* seg_off, const double* seg_feats, const double* seg_times, const int64_t* seg_ids,
+                                         const int32_t* sub_off, const roman_submap_desc_t* descs,
+                                         double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status,
+                                         int32_t desc_dim, double* desc_out,
+                                         int32_t L, const int32_t* list, int32_t* changed);
+
 /* ------------------------------------------------------------------------------------------- */
 /* frame descriptors of the submaps of a pool                                                  */
 /* ------------------------------------------------------------------------------------------- */

@@ -411,22 +411,9 @@ def build_submap_pool(registration, table: MapTable, centers: SubmapCenters, par
                       descriptor_mode=params.submap_descriptor, ids_dev=ids_out[:rows], **extra)
 
 
-def build_session_pools(registration, tables, centers, params, ctx=None, device=None, cap=None, frames=None, fill=None) -> List[SubmapPool]:
-    """The submap pools of ALL R robots of a session (one MapTable and one SubmapCenters each) from ONE roman_session_submaps_dev
-    call (DESIGN.md §4.19): the R tables go up once, concatenated in robot order; one launch sequence writes every robot's submaps
-    into ONE pool tensor — and one ids, count, src, status and descriptor tensor —; one synchronisation brings the small arrays
-    back.  Pool r is an ordinary SubmapPool whose `pool`, `ids_dev` and `desc_dev` are row-slice VIEWS of the session's tensors,
-    bit for bit what build_submap_pool(registration, tables[r], centers[r], params, cap=<the session's cap>) gives: grid_batch,
-    to_submaps and submap_align_pools read it unchanged, and submap_align_session over the list runs on the one allocation
-    without concatenating anything.
-
-    One `cap` serves the session: params.max_size, or `cap`, or the largest map's rows.  `frames`: one FrameTable per robot for the
-    frame-descriptor modes — roman_frame_select_dev per robot behind the session call, on the same stream, as in build_submap_pool.
-
-    Refused (ValueError, before anything makes a HIP context): `fill=` or params of the force_fill_submaps mode — that mode slices
-    on the host, build_submap_pool(fill=...) per robot serves it —, tables of different row width, point_dim, desc_dim or
-    invariant, a `centers` or `frames` list whose length is not R, and whatever build_submap_pool refuses per robot."""
-    import torch
+def _session_refusals(tables, centers, params, cap, frames, fill):
+    """What build_session_pools refuses before anything makes a HIP context (its docstring) -> (tables, centers, frames as lists, the
+    session's roman_submap_params_t or None for R == 0, (d, framed, mean_frames) of _descriptor_width)."""
     tables, centers = list(tables), list(centers)
     R = len(tables)
     if fill is not None or isinstance(params, FillSubmapParams) or getattr(params, "force_fill_submaps", False):
@@ -447,9 +434,74 @@ def build_session_pools(registration, tables, centers, params, ctx=None, device=
         cap = max([len(t) for t in tables] + [1])
     calls = [submap_call_params(t, params, cap) for t in tables]
     if R == 0:
+        return tables, centers, frames, None, (0, False, False)
+    return tables, centers, frames, calls[0], widths[0]
+
+
+def _session_pool_views(tables, centers, frames, params, P, sub_off, d, framed, pool, ids_out, desc, count_h, status_h, src_h, ids_h, desc_h, ft):
+    """The R SubmapPools over the session's tensors: pool r's `pool`, `ids_dev` and `desc_dev` are row-slice views, its host fields
+    copies of its slices of the arrays read back (ft: per robot the frame-select tensors of the frame-descriptor modes)."""
+    out = []
+    for r in range(len(tables)):
+        lo, hi = int(sub_off[r]), int(sub_off[r + 1])
+        extra = {}
+        if framed:
+            n_h = ft[r]["n"].cpu().numpy()[:hi - lo].copy()
+            bad = np.nonzero((count_h[lo:hi] > 0) & (n_h == 0))[0]
+            if len(bad):
+                raise ValueError(f"submap {int(bad[0])} holds {int(count_h[lo + bad[0]])} segments but no frame of the map lies in its time span: "
+                                 "the reference cannot build its frame descriptor")
+            extra = dict(frames=frames[r], frame_mask=ft[r]["mask"][:hi - lo, :ft[r]["W"]], frame_n=n_h, frame_desc_dev=ft[r]["desc"])
+        out.append(SubmapPool(pool[lo * P.cap:hi * P.cap], int(P.cap), count_h[lo:hi].copy(), src_h[lo:hi].copy(), ids_h[lo:hi].copy(),
+                              status_h[lo:hi].copy(), desc_h[lo:hi].copy() if d else None, centers[r], tables[r],
+                              desc_dev=desc[lo:hi, :d] if d else None, descriptor_mode=params.submap_descriptor,
+                              ids_dev=ids_out[lo * P.cap:hi * P.cap], **extra))
+    return out
+
+
+def _frame_tensors(torch, dev, frames, centers):
+    """Per robot the frame table on the device and cleared frame-select outputs (the frame-descriptor modes of the session builds)."""
+    ft = []
+    for r, fr in enumerate(frames):
+        S_r, W = len(centers[r]), (len(fr) + 63) // 64
+        ft.append(dict(W=W, times=torch.from_numpy(fr.times).to(dev), pos=torch.from_numpy(fr.pos).to(dev), desc=torch.from_numpy(fr.desc).to(dev),
+                       mask=torch.zeros((max(S_r, 1), max(W, 1)), dtype=torch.int64, device=dev),
+                       n=torch.zeros(max(S_r, 1), dtype=torch.int32, device=dev), span=torch.zeros((max(S_r, 1), 2), dtype=torch.float64, device=dev)))
+    return ft
+
+
+def _frame_select_robots(ctx, params, P, tables, frames, seg_off, sub_off, mean_frames, count, src, times, desc, ft):
+    """roman_frame_select_dev per robot behind a session build, on the same stream: each reads its robot's count and src."""
+    thin = params.frame_descriptor_dist if params.submap_descriptor == 'stacked_frame_descriptors' else None      # [REF roman/map/map.py:216-226]
+    for r in range(len(tables)):
+        lo, hi, f = int(sub_off[r]), int(sub_off[r + 1]), ft[r]
+        if hi > lo:
+            ctx.frame_select_dev(frame_select_params(thin, mean_frames), hi - lo, P.cap, count[lo:].data_ptr(), src[lo * P.cap:].data_ptr(), len(tables[r]),
+                                 times[int(seg_off[r]):].data_ptr(), len(frames[r]), f["times"].data_ptr(), f["mask"].data_ptr(), f["n"].data_ptr(),
+                                 f["span"].data_ptr(), frame_pos_ptr=f["pos"].data_ptr(), d=int(frames[r].desc.shape[1]), frame_desc_ptr=f["desc"].data_ptr(),
+                                 mean_ptr=desc[lo:].data_ptr() if mean_frames else None)
+
+
+def build_session_pools(registration, tables, centers, params, ctx=None, device=None, cap=None, frames=None, fill=None) -> List[SubmapPool]:
+    """The submap pools of ALL R robots of a session (one MapTable and one SubmapCenters each) from ONE roman_session_submaps_dev
+    call (DESIGN.md §4.19): the R tables go up once, concatenated in robot order; one launch sequence writes every robot's submaps
+    into ONE pool tensor — and one ids, count, src, status and descriptor tensor —; one synchronisation brings the small arrays
+    back.  Pool r is an ordinary SubmapPool whose `pool`, `ids_dev` and `desc_dev` are row-slice VIEWS of the session's tensors,
+    bit for bit what build_submap_pool(registration, tables[r], centers[r], params, cap=<the session's cap>) gives: grid_batch,
+    to_submaps and submap_align_pools read it unchanged, and submap_align_session over the list runs on the one allocation
+    without concatenating anything.
+
+    One `cap` serves the session: params.max_size, or `cap`, or the largest map's rows.  `frames`: one FrameTable per robot for the
+    frame-descriptor modes — roman_frame_select_dev per robot behind the session call, on the same stream, as in build_submap_pool.
+
+    Refused (ValueError, before anything makes a HIP context): `fill=` or params of the force_fill_submaps mode — that mode slices
+    on the host, build_submap_pool(fill=...) per robot serves it —, tables of different row width, point_dim, desc_dim or
+    invariant, a `centers` or `frames` list whose length is not R, and whatever build_submap_pool refuses per robot."""
+    import torch
+    tables, centers, frames, P, (d, framed, mean_frames) = _session_refusals(tables, centers, params, cap, frames, fill)
+    R = len(tables)
+    if R == 0:
         return []
-    P = calls[0]
-    d, framed, mean_frames = widths[0]
     ctx = ctx or registration._context()
     dev = torch.device(device if device is not None else f"cuda:{getattr(ctx, 'device', 0)}")
     on_host = dev.type == "cpu"                                              # CPU tensors + a stand-in context (tests)
@@ -471,43 +523,223 @@ def build_session_pools(registration, tables, centers, params, ctx=None, device=
     src = torch.full((max(rows, 1),), -1, dtype=torch.int32, device=dev)
     ids_out = torch.full((max(rows, 1),), -1, dtype=torch.int64, device=dev)
     desc = torch.full((max(S, 1), max(d, 1)), float("nan"), dtype=torch.float64, device=dev)
-    ft = []
-    if framed:
-        thin = params.frame_descriptor_dist if params.submap_descriptor == 'stacked_frame_descriptors' else None      # [REF roman/map/map.py:216-226]
-        for r, fr in enumerate(frames):
-            S_r, W = len(centers[r]), (len(fr) + 63) // 64
-            ft.append(dict(W=W, times=torch.from_numpy(fr.times).to(dev), pos=torch.from_numpy(fr.pos).to(dev), desc=torch.from_numpy(fr.desc).to(dev),
-                           mask=torch.zeros((max(S_r, 1), max(W, 1)), dtype=torch.int64, device=dev),
-                           n=torch.zeros(max(S_r, 1), dtype=torch.int32, device=dev), span=torch.zeros((max(S_r, 1), 2), dtype=torch.float64, device=dev)))
+    ft = _frame_tensors(torch, dev, frames, centers) if framed else []
     if not on_host:
         torch.cuda.current_stream(dev).synchronize()                         # inputs and cleared outputs are in place before the library's stream touches them
     ctx.session_submaps_dev(P, F, seg_off, feats.data_ptr(), times.data_ptr(), sub_off, descs, pool.data_ptr(), count.data_ptr(), src.data_ptr(),
                             status.data_ptr(), seg_ids_ptr=ids.data_ptr(), ids_out_ptr=ids_out.data_ptr() if len(ids) else None,     # (no segment at all: no id to write)
                             desc_dim=0 if framed else d, desc_out_ptr=desc.data_ptr() if d and not framed else None)
-    for r in range(R if framed else 0):                                      # behind it on the same stream: each reads its robot's count and src
-        lo, hi, f = int(sub_off[r]), int(sub_off[r + 1]), ft[r]
-        if hi > lo:
-            ctx.frame_select_dev(frame_select_params(thin, mean_frames), hi - lo, P.cap, count[lo:].data_ptr(), src[lo * P.cap:].data_ptr(), len(tables[r]),
-                                 times[int(seg_off[r]):].data_ptr(), len(frames[r]), f["times"].data_ptr(), f["mask"].data_ptr(), f["n"].data_ptr(),
-                                 f["span"].data_ptr(), frame_pos_ptr=f["pos"].data_ptr(), d=int(frames[r].desc.shape[1]), frame_desc_ptr=f["desc"].data_ptr(),
-                                 mean_ptr=desc[lo:].data_ptr() if mean_frames else None)
+    if framed:                                                               # behind it on the same stream: each reads its robot's count and src
+        _frame_select_robots(ctx, params, P, tables, frames, seg_off, sub_off, mean_frames, count, src, times, desc, ft)
     ctx.sync()
     count_h, status_h = count.cpu().numpy()[:S].copy(), status.cpu().numpy()[:S].copy()
     src_h, ids_h = src.cpu().numpy()[:rows].reshape(S, P.cap), ids_out.cpu().numpy()[:rows].reshape(S, P.cap)
     desc_h = desc.cpu().numpy()[:S, :d] if d else None
-    out = []
+    return _session_pool_views(tables, centers, frames, params, P, sub_off, d, framed, pool, ids_out, desc, count_h, status_h, src_h, ids_h, desc_h, ft)
+
+
+# ---------------------------------------------------------------------------------------------
+# a session that GROWS: the tables and the pools stay in HBM, a step builds the new and the changed submaps only
+# ---------------------------------------------------------------------------------------------
+GROWTH = 1.5                     # capacity of the session's tensors over the need, when they have to be made anew
+
+# the session's tensors: name -> (rows per unit: 1, or 'cap' for the slot tensors; unit: 'seg' table rows or 'sub' submaps; the value a fresh one holds)
+_SESSION_TENSORS = dict(feats=(1, 'seg', 0.0), times=(1, 'seg', 0.0), ids=(1, 'seg', 0),
+                        pool=('cap', 'sub', 0.0), src=('cap', 'sub', -1), ids_out=('cap', 'sub', -1), count=(1, 'sub', 0), status=(1, 'sub', 0),
+                        desc=(1, 'sub', float("nan")))
+
+
+class SessionPoolsState:
+    """What grow_session_pools keeps between two steps of one session: the device tensors of the tables (feats, times, ids) and of
+    the outputs (pool, src, ids_out, count, status, desc) — each with room beyond the need, every robot's range next to the one in
+    front of it —, per robot the rows and submaps it held and its centre records as bytes, and `src` / `count` on the host."""
+
+    def __init__(self):
+        self.key = None              # robots, cap, row layout, submap_descriptor: a state serves ONE session
+        self.t = {}                  # name -> torch tensor (see _SESSION_TENSORS)
+        self.n_rows = None           # per robot: rows of its table
+        self.n_sub = None            # per robot: its submaps
+        self.descs = None            # per robot: uint8 (S_r, sizeof(roman_submap_desc_t)) as the last call staged them
+        self.count_h = None          # (S,) int32 and (S, cap) int32 over the whole session, as read back last
+        self.src_h = None
+        self.frame = None            # the frame-descriptor modes, per robot: dict(mask, n, mean) device tensors of the last call
+        self.listed = 0              # submaps the last call rebuilt, of `total`
+        self.total = 0
+        self.seconds = {}            # the last call's wall time by part: 'upload' (host rules, moves and table rows), 'device' (the call to its
+                                     # synchronisation), 'readback'
+
+
+def _moved(torch, t, old_off, old_len, new_off, total, per, fill):
+    """Tensor `t` with robot r's range of old_len[r] units (of `per` rows each) moved from unit old_off[r] to new_off[r] >= old_off[r]:
+    in place from the last robot backwards while `total` units fit, else into a tensor GROWTH times the need (filled with `fill`)."""
+    if total * per > int(t.shape[0]):
+        new = torch.full((max(int(total * per * GROWTH), 1),) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)
+        for o, n, k in zip(old_off, new_off, old_len):
+            if k:
+                new[n * per:(n + k) * per].copy_(t[o * per:(o + k) * per])
+        return new
+    for o, n, k in reversed(list(zip(old_off, new_off, old_len))):
+        if k and n != o:
+            t[n * per:(n + k) * per] = t[o * per:(o + k) * per].clone()          # (the ranges may overlap)
+    return t
+
+
+def grow_session_pools(state, registration, tables, centers, params, ctx=None, device=None, cap=None, frames=None, changed_rows=None, rebuild=None):
+    """build_session_pools for a session that GROWS -> (pools, touched, state).  `state` (a SessionPoolsState, or
+    None before the first call) keeps the session's tables and pools in HBM; a call uploads only the appended and the rewritten
+    table rows, rebuilds only the submaps that are new or can have changed — ONE roman_session_submaps_list_dev call, one
+    synchronisation, one read-back of the small arrays — and learns from the device which slots really changed.  The pools equal,
+    field by field and byte for byte, build_session_pools(registration, tables, centers, params, cap=<the state's cap>) over the same
+    inputs, views of one storage in robot order; touched[r] (bool per submap of robot r) is the `touched` argument of
+    submap_align_session_update: the new submaps and the rebuilt old ones of which a byte changed (in the frame-descriptor modes
+    also those whose frame mask, frame count or mean changed).  The pools of an earlier step are views of the same storage: they are
+    not to be read after the next call.
+
+    Between two calls a table may grow by APPENDED rows (found from the lengths) and have rows rewritten in place, which the caller
+    names in changed_rows[r] (indices, or None); centres may only be appended, an old centre's record may change (t_hi of the former
+    last submap does).  Rebuilt are: every new submap; every old one whose roman_submap_desc_t bytes differ from the recorded ones;
+    every old submap s of robot r for which an appended or named row k was a member (k in src[s, :count[s]]) or passes the time window
+    with its new times, NOT (first_seen > t_hi[s] OR last_seen < t_lo[s]); and whatever rebuild[r] names (rebuild='all': everything).
+
+    ValueError before a context is made: whatever build_session_pools refuses (the force-fill mode included); a robot count, cap,
+    row layout or submap_descriptor other than the state's; a table or centre list that shrank; changed_rows out of range."""
+    import time
+    import torch
+    marks = [time.perf_counter()]
+    tables, centers, frames, P, (d, framed, mean_frames) = _session_refusals(tables, centers, params, cap, frames, None)
+    R = len(tables)
+    state = SessionPoolsState() if state is None else state
+    layout = None if R == 0 else (int(tables[0].feats.shape[1]), int(tables[0].point_dim), int(tables[0].desc_dim), tables[0].invariant)
+    key = (R, None if P is None else int(P.cap), layout, params.submap_descriptor, int(d))
+    if state.key is not None and state.key != key:
+        raise ValueError("the state was made for another robot count, cap, row layout or submap_descriptor: a SessionPoolsState serves one session")
+    first = state.key is None
+    old_rows, old_sub = ([0] * R, [0] * R) if first else (state.n_rows, state.n_sub)
+    n_rows, n_sub = [len(t) for t in tables], [len(c) for c in centers]
+    if any(n < m for n, m in zip(n_rows, old_rows)) or any(n < m for n, m in zip(n_sub, old_sub)):
+        raise ValueError("a table or a centre list shrank: between two calls rows and centres may only be appended")
+    changed_rows = [None] * R if changed_rows is None else list(changed_rows)
+    if len(changed_rows) != R:
+        raise ValueError("changed_rows must hold one entry per table, each None or the indices of the rewritten rows")
+    named = []
+    for r, rows in enumerate(changed_rows):
+        rows = np.zeros(0, dtype=np.int64) if rows is None else np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))
+        if len(rows) and (rows[0] < 0 or rows[-1] >= n_rows[r]):
+            raise ValueError(f"changed_rows[{r}] names a row outside the table's {n_rows[r]} rows")
+        named.append(rows[rows < old_rows[r]])                               # (a named row beyond the old length is an appended one)
+    if not (rebuild is None or isinstance(rebuild, str) and rebuild == 'all'):
+        rebuild = list(rebuild)
+        if len(rebuild) != R or any(x is not None and len(np.asarray(x).reshape(-1)) and
+                                    (np.min(x) < 0 or np.max(x) >= n) for x, n in zip(rebuild, n_sub)):
+            raise ValueError("rebuild must be None, 'all', or one entry per robot, each None or submap indices of that robot")
+    if R == 0:
+        return [], [], state
+
+    # ---- the list: every rule is a necessary condition for a slot to change, so what is left out cannot have (DESIGN.md §4.21) ----
+    seg_off = np.concatenate([[0], np.cumsum(n_rows)]).astype(np.int64)
+    sub_off = np.concatenate([[0], np.cumsum(n_sub)]).astype(np.int32)
+    old_seg_off, old_sub_off = np.concatenate([[0], np.cumsum(old_rows)]).astype(np.int64), np.concatenate([[0], np.cumsum(old_sub)]).astype(np.int64)
+    descs_r = [c.descs() for c in centers]
+    desc_bytes = [np.ascontiguousarray(x).view(np.uint8).reshape(len(x), -1).copy() for x in descs_r]
+    listed = []
     for r in range(R):
-        lo, hi = int(sub_off[r]), int(sub_off[r + 1])
-        extra = {}
-        if framed:
-            n_h = ft[r]["n"].cpu().numpy()[:hi - lo].copy()
-            bad = np.nonzero((count_h[lo:hi] > 0) & (n_h == 0))[0]
-            if len(bad):
-                raise ValueError(f"submap {int(bad[0])} holds {int(count_h[lo + bad[0]])} segments but no frame of the map lies in its time span: "
-                                 "the reference cannot build its frame descriptor")
-            extra = dict(frames=frames[r], frame_mask=ft[r]["mask"][:hi - lo, :ft[r]["W"]], frame_n=n_h, frame_desc_dev=ft[r]["desc"])
-        out.append(SubmapPool(pool[lo * P.cap:hi * P.cap], int(P.cap), count_h[lo:hi].copy(), src_h[lo:hi].copy(), ids_h[lo:hi].copy(),
-                              status_h[lo:hi].copy(), desc_h[lo:hi].copy() if d else None, centers[r], tables[r],
-                              desc_dev=desc[lo:hi, :d] if d else None, descriptor_mode=params.submap_descriptor,
-                              ids_dev=ids_out[lo * P.cap:hi * P.cap], **extra))
-    return out
+        flag = np.zeros(n_sub[r], dtype=bool)
+        flag[old_sub[r]:] = True
+        k_old = old_sub[r]
+        if rebuild is not None:
+            if isinstance(rebuild, str):
+                flag[:] = True
+            elif rebuild[r] is not None:
+                flag[np.asarray(rebuild[r], dtype=np.int64).reshape(-1)] = True
+        if k_old:
+            flag[:k_old] |= (desc_bytes[r][:k_old] != state.descs[r]).any(axis=1)
+            rows = np.concatenate([named[r], np.arange(old_rows[r], n_rows[r], dtype=np.int64)])
+            if len(rows):
+                tm = np.asarray(tables[r].times, dtype=np.float64).reshape(-1, 2)[rows]
+                dd = descs_r[r][:k_old]
+                flag[:k_old] |= (~((tm[None, :, 0] > dd["t_hi"][:, None]) | (tm[None, :, 1] < dd["t_lo"][:, None]))).any(axis=1)
+                if len(named[r]):
+                    lo = int(old_sub_off[r])
+                    src_r, cnt_r = state.src_h[lo:lo + k_old], state.count_h[lo:lo + k_old]
+                    member = np.isin(src_r, named[r]) & (np.arange(src_r.shape[1])[None, :] < cnt_r[:, None])
+                    flag[:k_old] |= member.any(axis=1)
+        listed.append(flag)
+    lst = np.concatenate([int(sub_off[r]) + np.nonzero(f)[0] for r, f in enumerate(listed)]).astype(np.int32)
+
+    # ---- the device: capacity, every robot's range next to the one in front of it, the new table rows ----
+    ctx = ctx or registration._context()
+    dev = torch.device(device if device is not None else f"cuda:{getattr(ctx, 'device', 0)}")
+    on_host = dev.type == "cpu"                                              # CPU tensors + a stand-in context (tests)
+    F, capn = layout[0], int(P.cap)
+    Fo, S, N = P.point_dim + F - 3, int(sub_off[-1]), int(seg_off[-1])
+    shapes = dict(feats=((F,), torch.float64), times=((2,), torch.float64), ids=((), torch.int64), pool=((Fo,), torch.float64), src=((), torch.int32),
+                  ids_out=((), torch.int64), count=((), torch.int32), status=((), torch.int32), desc=((max(d, 1),), torch.float64))
+    t = state.t
+    for name, (per, unit, fill) in _SESSION_TENSORS.items():
+        per = capn if per == 'cap' else 1
+        if first:
+            t[name] = torch.full((0,) + shapes[name][0], fill, dtype=shapes[name][1], device=dev)
+        o_off, n_off, o_len, total = (old_seg_off, seg_off, old_rows, max(N, 1)) if unit == 'seg' else (old_sub_off, sub_off, old_sub, max(S, 1))
+        t[name] = _moved(torch, t[name], [int(x) for x in o_off[:-1]], o_len, [int(x) for x in n_off[:-1]], total, per, fill)
+        if unit == 'sub':                                                    # a new slot starts as a fresh build's does
+            for r in range(R):
+                t[name][(int(sub_off[r]) + old_sub[r]) * per:int(sub_off[r + 1]) * per] = fill
+    for r, tb in enumerate(tables):
+        lo = int(seg_off[r])
+        for name, a, dt in (("feats", tb.feats, np.float64), ("times", tb.times.reshape(-1, 2), np.float64), ("ids", tb.ids.reshape(-1), np.int64)):
+            if n_rows[r] > old_rows[r]:
+                t[name][lo + old_rows[r]:lo + n_rows[r]].copy_(torch.from_numpy(np.ascontiguousarray(a[old_rows[r]:], dtype=dt)))
+            if len(named[r]):
+                t[name][torch.from_numpy(named[r] + lo).to(dev)] = torch.from_numpy(np.ascontiguousarray(a[named[r]], dtype=dt)).to(dev)
+    changed = torch.zeros(max(len(lst), 1), dtype=torch.int32, device=dev)
+    ft, before = [], None
+    if framed:
+        ft = _frame_tensors(torch, dev, frames, centers)
+        before = [None if first or not old_sub[r] else dict(state.frame[r], mean=t["desc"][int(sub_off[r]):int(sub_off[r]) + old_sub[r]].clone())
+                  for r in range(R)]
+        if mean_frames:                                                      # frame_select_dev writes the mean of every non-empty submap again and leaves
+            t["desc"][:S] = float("nan")                                     # an empty one's row alone: NaN there, as in a fresh build
+    if not on_host:
+        torch.cuda.current_stream(dev).synchronize()                         # moves, uploads and cleared slots are in place before the library's stream touches them
+    marks.append(time.perf_counter())
+    descs = np.concatenate(descs_r)
+    ctx.session_submaps_list_dev(P, F, seg_off, t["feats"].data_ptr(), t["times"].data_ptr(), sub_off, descs, lst, t["pool"].data_ptr(), t["count"].data_ptr(),
+                                 t["src"].data_ptr(), t["status"].data_ptr(), seg_ids_ptr=t["ids"].data_ptr(), ids_out_ptr=t["ids_out"].data_ptr() if N else None,
+                                 desc_dim=0 if framed else d, desc_out_ptr=t["desc"].data_ptr() if d and not framed else None,
+                                 changed_ptr=changed.data_ptr())
+    if framed:                                                               # behind it on the same stream, over every submap of a robot as in build_session_pools
+        _frame_select_robots(ctx, params, P, tables, frames, seg_off, sub_off, mean_frames, t["count"], t["src"], t["times"], t["desc"], ft)
+    ctx.sync()
+    marks.append(time.perf_counter())
+
+    # ---- one read-back of the small arrays ----
+    rows = S * capn
+    count_h, status_h = t["count"].cpu().numpy()[:S].copy(), t["status"].cpu().numpy()[:S].copy()
+    src_h, ids_h = t["src"].cpu().numpy()[:rows].reshape(S, capn).copy(), t["ids_out"].cpu().numpy()[:rows].reshape(S, capn).copy()
+    desc_h = t["desc"].cpu().numpy()[:S, :d] if d else None
+    changed_h = changed.cpu().numpy()[:len(lst)]
+    touched = []
+    for r in range(R):
+        flag = np.zeros(n_sub[r], dtype=bool)
+        flag[old_sub[r]:] = True
+        mine = (lst >= sub_off[r]) & (lst < sub_off[r + 1])
+        flag[lst[mine][changed_h[mine] != 0] - int(sub_off[r])] = True
+        if framed and before[r] is not None:                                 # what frame_select_dev left for the old submaps against the last call's, on the device
+            k, f, b = old_sub[r], ft[r], before[r]
+            W = max(int(f["mask"].shape[1]), int(b["mask"].shape[1]))
+            wide = lambda m: torch.nn.functional.pad(m[:k], (0, W - int(m.shape[1])))
+            differs = (wide(f["mask"]) != wide(b["mask"])).any(dim=1) | (f["n"][:k] != b["n"][:k])
+            if mean_frames:
+                now = t["desc"][int(sub_off[r]):int(sub_off[r]) + k]
+                differs |= (now.contiguous().view(torch.int64) != b["mean"].contiguous().view(torch.int64)).any(dim=1)
+            flag[:k] |= differs.cpu().numpy()
+        touched.append(flag)
+    pools = _session_pool_views(tables, centers, frames, params, P, sub_off, d, framed, t["pool"], t["ids_out"], t["desc"], count_h, status_h, src_h, ids_h,
+                                desc_h, ft)
+    state.key, state.n_rows, state.n_sub, state.descs = key, n_rows, n_sub, desc_bytes
+    state.count_h, state.src_h = count_h, src_h
+    state.frame = [dict(mask=f["mask"], n=f["n"]) for f in ft] if framed else None
+    state.listed, state.total = int(len(lst)), S
+    marks.append(time.perf_counter())
+    state.seconds = dict(upload=marks[1] - marks[0], device=marks[2] - marks[1], readback=marks[3] - marks[2])
+    return pools, touched, state

@@ -7590,33 +7590,47 @@ __global__ void __launch_bounds__(SUBMAP_NT) k_submap_select(roman_submap_params
                       count + s, src + (int64_t)s * P.cap, status + s);
 }
 
+// One word (or 16-byte pair) of an output slot.  CMP (the list forms): the OLD value is read before the new one is
+// stored and `diff` learns whether a bit of it changes; without CMP this is the plain store it replaces.
+__device__ __forceinline__ bool slot_differs(const ulonglong2 a, const ulonglong2 b) { return a.x != b.x || a.y != b.y; }
+template <typename T> __device__ __forceinline__ bool slot_differs(const T a, const T b) { return a != b; }
+template <bool CMP, typename T> __device__ __forceinline__ void slot_put(T* p, const T v, bool& diff)
+{
+    if constexpr (CMP) { const T was = *p; diff = diff || slot_differs(was, v); }
+    *p = v;
+}
+
 // The wave's work for ONE selected row: segment k of the table `feats` (its id in `ids`) into pool row `row`, its centre through T.
-__device__ __forceinline__ void submap_gather_row(int point_dim, int F, const double* __restrict__ T, const unsigned long long* __restrict__ feats,
+// -> CMP: whether a bit of the row (or of its id) changed, per lane; otherwise false.
+template <bool CMP = false>
+__device__ __forceinline__ bool submap_gather_row(int point_dim, int F, const double* __restrict__ T, const unsigned long long* __restrict__ feats,
                                                   const int64_t* __restrict__ ids, int k, int64_t row,
                                                   unsigned long long* __restrict__ pool, int64_t* __restrict__ ids_out, int lane)
 {
     const int Fo = point_dim + F - 3, rest = F - 3;
     const unsigned long long* in = feats + (int64_t)k * F;
     unsigned long long* out = pool + row * Fo;
+    bool diff = false;
     if (lane == 0) {
         const double x = __longlong_as_double((long long)in[0]), y = __longlong_as_double((long long)in[1]), z = __longlong_as_double((long long)in[2]);
         for (int c = 0; c < point_dim; ++c)
-            out[c] = (unsigned long long)__double_as_longlong(((T[4 * c] * x + T[4 * c + 1] * y) + T[4 * c + 2] * z) + T[4 * c + 3]);
-        if (ids_out) ids_out[row] = ids[k];
+            slot_put<CMP>(out + c, (unsigned long long)__double_as_longlong(((T[4 * c] * x + T[4 * c + 1] * y) + T[4 * c + 2] * z) + T[4 * c + 3]), diff);
+        if (ids_out) slot_put<CMP>(ids_out + row, ids[k], diff);
     }
     const unsigned long long* a = in + 3;
     unsigned long long* b = out + point_dim;
     const unsigned oa = (unsigned)(((uintptr_t)a >> 3) & 1u), ob = (unsigned)(((uintptr_t)b >> 3) & 1u);
     if (oa == ob) {                                              // one 16-byte phase: a leading word when odd, pairs, a trailing word
         const int head = min((int)oa, rest), pairs = (rest - head) >> 1;
-        if (lane == 0 && head) b[0] = a[0];
+        if (lane == 0 && head) slot_put<CMP>(b, a[0], diff);
         const ulonglong2* a2 = reinterpret_cast<const ulonglong2*>(a + head);
         ulonglong2* b2 = reinterpret_cast<ulonglong2*>(b + head);
-        for (int q = lane; q < pairs; q += 64) b2[q] = a2[q];
-        if (lane == 63 && head + 2 * pairs < rest) b[rest - 1] = a[rest - 1];
+        for (int q = lane; q < pairs; q += 64) slot_put<CMP>(b2 + q, a2[q], diff);
+        if (lane == 63 && head + 2 * pairs < rest) slot_put<CMP>(b + rest - 1, a[rest - 1], diff);
     } else {
-        for (int q = lane; q < rest; q += 64) b[q] = a[q];
+        for (int q = lane; q < rest; q += 64) slot_put<CMP>(b + q, a[q], diff);
     }
+    return diff;
 }
 
 // grid (submaps, row groups); a wave per selected row
@@ -7635,12 +7649,17 @@ __global__ void __launch_bounds__(256) k_submap_gather(int point_dim, int cap, i
 }
 
 // column c of ONE submap's mean_semantic descriptor: the n rows `rows` names of the table `feats`, added in output order
-__device__ __forceinline__ void submap_desc_one(int F, int d, int c, const double* __restrict__ feats, const int32_t* __restrict__ rows, int n,
-                                                double* __restrict__ desc)
+__device__ __forceinline__ double submap_desc_col(int F, int d, int c, const double* __restrict__ feats, const int32_t* __restrict__ rows, int n)
 {
     double acc = 0.0;
     for (int r = 0; r < n; ++r) acc += feats[(int64_t)rows[r] * F + (F - d) + c];
-    desc[c] = acc / (double)n;
+    return acc / (double)n;
+}
+
+__device__ __forceinline__ void submap_desc_one(int F, int d, int c, const double* __restrict__ feats, const int32_t* __restrict__ rows, int n,
+                                                double* __restrict__ desc)
+{
+    desc[c] = submap_desc_col(F, d, c, feats, rows, n);
 }
 
 // grid (submaps, column groups): desc_out[s][c] = (sum over the rows of submap s, in output order, of descriptor column c) / count
@@ -7663,7 +7682,8 @@ struct SessionSubmap {
     int64_t seg0;            // first row of the submap's map in the concatenated tables (seg_off[r])
     int64_t spill0;          // first entry of the submap's slice of the spill
     int32_t N;               // rows of the map (seg_off[r + 1] - seg_off[r])
-    int32_t reserved;
+    int32_t slot;            // the global submap index g the record serves: its place in every output (the list forms read it: their grid runs
+                             // over the listed submaps, not over the slots)
 };
 
 __global__ void __launch_bounds__(256) k_session_submap_points(int64_t N, int F, const double* __restrict__ feats, double* __restrict__ pts)
@@ -7715,6 +7735,84 @@ __global__ void __launch_bounds__(256) k_session_submap_desc(int cap, int F, int
     const int n = count[g];
     if (c >= d || n == 0) return;                                // an empty submap's descriptor is left as it was
     submap_desc_one(F, d, c, feats + tab[g].seg0 * F, src + (int64_t)g * cap, n, desc_out + (int64_t)g * d);
+}
+
+// The LIST forms (roman_session_submaps_list*): only the L listed submaps of the session are rebuilt, each WHOLE —
+// a submap may shrink —, and the call reports which slots changed.  `tab` and `descs` hold the L LISTED submaps' records (tab[l].slot
+// is the global index g), the grids run over L.  The select writes count, status and the ordered indices of listed submap l into a
+// scratch of the context (newCount[l], newStatus[l], newSrc[l * cap ..]) through the unchanged submap_select_one; the store kernel
+// then writes slot g from there.  The dense centres come from k_session_submap_points over the maps that have a listed submap.
+__global__ void __launch_bounds__(SUBMAP_NT) k_session_submap_select_list(roman_submap_params_t P, int L, const SessionSubmap* __restrict__ tab,
+                                                                          const roman_submap_desc_t* __restrict__ descs,
+                                                                          const double* __restrict__ pts, const double* __restrict__ times,
+                                                                          double* spillKey, int32_t* spillIdx,
+                                                                          int32_t* __restrict__ newCount, int32_t* __restrict__ newSrc, int32_t* __restrict__ newStatus)
+{
+    const int l = blockIdx.x;
+    if (l >= L) return;
+    const SessionSubmap M = tab[l];
+    const roman_submap_desc_t D = descs[l];
+    submap_select_one(P, D, M.N, pts + 3 * M.seg0, times + 2 * M.seg0, spillKey + M.spill0, spillIdx + M.spill0,
+                      newCount + l, newSrc + (int64_t)l * P.cap, newStatus + l);
+}
+
+// The wave's work for ONE row of a listed slot beyond its count: the values the Python layer clears its tensors to (pool 0.0, id -1),
+// with submap_gather_row's 16-byte phase logic on the destination: a leading word when the row starts odd, pairs, a trailing word.
+template <bool CMP>
+__device__ __forceinline__ bool submap_clear_row(int Fo, int64_t row, unsigned long long* __restrict__ pool, int64_t* __restrict__ ids_out, int lane)
+{
+    unsigned long long* b = pool + row * Fo;
+    bool diff = false;
+    if (lane == 0 && ids_out) slot_put<CMP>(ids_out + row, (int64_t)-1, diff);
+    const unsigned ob = (unsigned)(((uintptr_t)b >> 3) & 1u);
+    const int head = min((int)ob, Fo), pairs = (Fo - head) >> 1;
+    if (lane == 0 && head) slot_put<CMP>(b, 0ull, diff);
+    ulonglong2* b2 = reinterpret_cast<ulonglong2*>(b + head);
+    for (int q = lane; q < pairs; q += 64) slot_put<CMP>(b2 + q, make_ulonglong2(0ull, 0ull), diff);
+    if (lane == 63 && head + 2 * pairs < Fo) slot_put<CMP>(b + Fo - 1, 0ull, diff);
+    return diff;
+}
+
+// One workgroup per listed submap writes its WHOLE slot: count and status, the `cap` indices of src (-1 beyond the count), the rows
+// [0, count) through submap_gather_row (a wave per row), the rows [count, cap) through submap_clear_row, and the mean_semantic row
+// through submap_desc_col (all NaN for an empty submap) — every byte by exactly one thread, which with CMP reads the old value right
+// before it stores the new one.  changed[l]: whether any thread saw a difference — one __syncthreads_or and one plain store, so the
+// flag does not depend on any order.  Nothing of an unlisted slot is read or written.
+template <bool CMP>
+__global__ void __launch_bounds__(256) k_session_submap_store_list(int point_dim, int cap, int F, int d, const SessionSubmap* __restrict__ tab,
+                                                                   const roman_submap_desc_t* __restrict__ descs,
+                                                                   const unsigned long long* __restrict__ feats, const int64_t* __restrict__ ids,
+                                                                   const int32_t* __restrict__ newCount, const int32_t* __restrict__ newSrc,
+                                                                   const int32_t* __restrict__ newStatus,
+                                                                   unsigned long long* __restrict__ pool, int32_t* __restrict__ count, int32_t* __restrict__ src,
+                                                                   int64_t* __restrict__ ids_out, int32_t* __restrict__ status,
+                                                                   unsigned long long* __restrict__ desc_out, int32_t* __restrict__ changed)
+{
+    const int l = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SessionSubmap M = tab[l];                              // (uniform)
+    const int g = M.slot, n = newCount[l];
+    const int32_t* rows = newSrc + (int64_t)l * cap;
+    const unsigned long long* mfeats = feats + M.seg0 * F;
+    const int64_t* mids = ids ? ids + M.seg0 : nullptr;
+    bool diff = false;
+    if (tid == 0) { slot_put<CMP>(count + g, (int32_t)n, diff); slot_put<CMP>(status + g, newStatus[l], diff); }
+    for (int i = tid; i < cap; i += 256) slot_put<CMP>(src + (int64_t)g * cap + i, i < n ? rows[i] : (int32_t)-1, diff);
+    for (int r = wave; r < cap; r += 4) {                        // (r is uniform over the wave)
+        const int64_t row = (int64_t)g * cap + r;
+        const bool x = r < n ? submap_gather_row<CMP>(point_dim, F, descs[l].T_center_odom, mfeats, mids, rows[r], row, pool, ids_out, lane)
+                             : submap_clear_row<CMP>(point_dim + F - 3, row, pool, ids_out, lane);
+        diff = diff || x;
+    }
+    if (desc_out)
+        for (int c = tid; c < d; c += 256) {
+            const unsigned long long v = n ? (unsigned long long)__double_as_longlong(submap_desc_col(F, d, c, reinterpret_cast<const double*>(mfeats), rows, n))
+                                           : 0x7ff8000000000000ull;                  // the quiet NaN the Python layer fills its descriptors with
+            slot_put<CMP>(desc_out + (int64_t)g * d + c, v, diff);
+        }
+    if constexpr (CMP) {
+        const int any = __syncthreads_or(diff ? 1 : 0);
+        if (tid == 0) changed[l] = any ? 1 : 0;
+    }
 }
 
 // Submap.segments_as_global_points [REF roman/map/map.py:133-139] reduced to what aabb_intersects [REF roman/utils.py:160-169] reads

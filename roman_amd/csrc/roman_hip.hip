@@ -182,6 +182,8 @@ struct roman_ctx {
     // ... of a whole session (roman_session_submaps*): one record per global submap — where its map and its spill slice start
     DevBuf smTab;
     PinnedStage<SessionSubmap> smTabStage;
+    DevBuf smListOut;       // the list form's select output: src int32[L * cap], count int32[L], status int32[L] of the listed submaps
+
 
     // pass 1 of a grid (roman_grid_gate*): the descriptor norms of both sides
     DevBuf ggNorm;
@@ -1470,7 +1472,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     c->hostMirror.release(); c->ransacDesc.release();
     c->shareStage.release(); c->ransacStage.release();
     { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx}; for (DevBuf* b : sm) b->release(); }
-    c->smStage.release(); c->smTab.release(); c->smTabStage.release();
+    c->smStage.release(); c->smTab.release(); c->smTabStage.release(); c->smListOut.release();
     c->ggNorm.release(); c->sgCount.release();
     c->ssNorm.release(); c->ssBand.release(); c->ssR.release(); c->ssItems.release(); c->ssStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
@@ -3006,7 +3008,7 @@ static int session_submaps_dev(roman_ctx* c, const roman_submap_params_t* sparam
     int64_t at = 0;
     for (int r = 0; r < g.R; ++r) {
         const int64_t n = g.seg_off[r + 1] - g.seg_off[r], over = std::max<int64_t>(n - SUBMAP_LDS_CAND, 0);
-        for (int32_t s = g.sub_off[r]; s < g.sub_off[r + 1]; ++s, at += over) tab[s] = SessionSubmap{g.seg_off[r], at, (int32_t)n, 0};
+        for (int32_t s = g.sub_off[r]; s < g.sub_off[r + 1]; ++s, at += over) tab[s] = SessionSubmap{g.seg_off[r], at, (int32_t)n, s};
     }
     HIPCHK(c, c->smStage.upload(c->smDesc, (size_t)S, stream));
     HIPCHK(c, c->smTabStage.upload(c->smTab, (size_t)S, stream));
@@ -3074,6 +3076,142 @@ int roman_session_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, 
 {
     const SessionSubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
     return session_submaps_host(c, sparams, g);
+}
+
+// --- the LISTED submaps of a session, rebuilt in place -------------------------------------------------------------
+// the list is judged behind the session's own checks, on host memory, before the context
+static int session_list_check(roman_ctx* c, int32_t S, int32_t L, const int32_t* list)
+{
+    if (L < 0) return fail(c, ROMAN_E_INVALID, "L < 0");
+    if (L > 0 && !list) return fail(c, ROMAN_E_INVALID, "list is NULL");
+    for (int32_t l = 0; l < L; ++l) {
+        if (list[l] < 0 || list[l] >= S) return fail(c, ROMAN_E_INVALID, "list[%d] = %d outside the %d submaps of the session", l, list[l], S);
+        if (l > 0 && list[l] <= list[l - 1]) return fail(c, ROMAN_E_INVALID, "list is not strictly ascending at entry %d", l);
+    }
+    return ROMAN_OK;
+}
+
+static int session_submaps_list_dev(roman_ctx* c, const roman_submap_params_t* sparams, const SessionSubmapsArgs& g, int32_t L, const int32_t* list,
+                                    int32_t* changed)
+{
+    int64_t N = 0; int32_t S = 0;
+    int rc = session_submaps_check(c, sparams, g, true, &N, &S);
+    if (rc) return rc;
+    rc = session_list_check(c, S, L, list);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (L == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    const int cap = sparams->cap, F = g.F;
+    // scratch slices for the LISTED submaps of the maps beyond SUBMAP_LDS_CAND only, each where the slices of the listed ones in front end
+    int64_t spill = 0;
+    for (int r = 0, l = 0; r < g.R && l < L; ++r) {
+        const int64_t n = g.seg_off[r + 1] - g.seg_off[r], over = std::max<int64_t>(n - SUBMAP_LDS_CAND, 0);
+        int64_t subs = 0;
+        for (; l < L && list[l] < g.sub_off[r + 1]; ++l) ++subs;
+        if (over && subs > (INT64_MAX / 16 - spill) / over) return fail(c, ROMAN_E_NOMEM, "the candidate scratch of the listed submaps exceeds the address space");
+        spill += subs * over;
+    }
+    // scratch and staging first: a failure leaves nothing enqueued
+    if (spill > 0) {
+        HIPCHK(c, c->smSpillKey.ensure(sizeof(double) * (size_t)spill));
+        HIPCHK(c, c->smSpillIdx.ensure(sizeof(int32_t) * (size_t)spill));
+    }
+    HIPCHK(c, c->smPts.ensure(sizeof(double) * 3 * (size_t)std::max<int64_t>(N, 1)));
+    HIPCHK(c, c->smDesc.ensure(sizeof(roman_submap_desc_t) * (size_t)L));
+    HIPCHK(c, c->smTab.ensure(sizeof(SessionSubmap) * (size_t)L));
+    HIPCHK(c, c->smListOut.ensure(sizeof(int32_t) * ((size_t)L * (size_t)cap + 2 * (size_t)L)));
+    roman_submap_desc_t* staged = nullptr;
+    SessionSubmap* tab = nullptr;
+    HIPCHK(c, c->smStage.stage((size_t)L, &staged));
+    HIPCHK(c, c->smTabStage.stage((size_t)L, &tab));
+    int64_t at = 0;
+    for (int r = 0, l = 0; r < g.R && l < L; ++r) {
+        const int64_t n = g.seg_off[r + 1] - g.seg_off[r], over = std::max<int64_t>(n - SUBMAP_LDS_CAND, 0);
+        for (; l < L && list[l] < g.sub_off[r + 1]; ++l, at += over) {
+            staged[l] = g.descs[list[l]];
+            tab[l] = SessionSubmap{g.seg_off[r], at, (int32_t)n, list[l]};
+        }
+    }
+    HIPCHK(c, c->smStage.upload(c->smDesc, (size_t)L, stream));
+    HIPCHK(c, c->smTabStage.upload(c->smTab, (size_t)L, stream));
+    const roman_submap_desc_t* dDesc = c->smDesc.as<roman_submap_desc_t>();
+    const SessionSubmap* dTab = c->smTab.as<SessionSubmap>();
+    int32_t* newSrc = c->smListOut.as<int32_t>();
+    int32_t* newCount = newSrc + (size_t)L * (size_t)cap;
+    int32_t* newStatus = newCount + L;
+    // the dense centres of the maps that have a listed submap, each map's rows at their place in the session's array
+    for (int r = 0, l = 0; r < g.R && l < L; ++r) {
+        const int64_t n = g.seg_off[r + 1] - g.seg_off[r];
+        const int l0 = l;
+        while (l < L && list[l] < g.sub_off[r + 1]) ++l;
+        if (l > l0 && n > 0)
+            hipLaunchKernelGGL(k_session_submap_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, F, g.seg_feats + g.seg_off[r] * F,
+                               c->smPts.as<double>() + 3 * g.seg_off[r]);
+    }
+    hipLaunchKernelGGL(k_session_submap_select_list, dim3((unsigned)L), dim3(SUBMAP_NT), 0, stream, *sparams, (int)L, dTab, dDesc, c->smPts.as<double>(), g.seg_times,
+                       c->smSpillKey.as<double>(), c->smSpillIdx.as<int32_t>(), newCount, newSrc, newStatus);
+    HIPCHK(c, hipGetLastError());
+    const auto store = changed ? k_session_submap_store_list<true> : k_session_submap_store_list<false>;
+    hipLaunchKernelGGL(store, dim3((unsigned)L), dim3(256), 0, stream, (int)sparams->point_dim, cap, F, (int)g.desc_dim, dTab, dDesc,
+                       reinterpret_cast<const unsigned long long*>(g.seg_feats), g.seg_ids, newCount, newSrc, newStatus,
+                       reinterpret_cast<unsigned long long*>(g.pool), g.count, g.src, g.ids_out, g.status, reinterpret_cast<unsigned long long*>(g.desc_out), changed);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+// the host-pointer call: the caller's current outputs go up first (an unlisted slot comes back as it was, and `changed` compares with them)
+static int session_submaps_list_host(roman_ctx* c, const roman_submap_params_t* sparams, const SessionSubmapsArgs& h, int32_t L, const int32_t* list,
+                                     int32_t* changed)
+{
+    int64_t N = 0; int32_t S = 0;
+    int rc = session_submaps_check(c, sparams, h, true, &N, &S);
+    if (rc) return rc;
+    rc = session_list_check(c, S, L, list);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (L == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const size_t rows = (size_t)S * (size_t)sparams->cap, bPool = sizeof(double) * rows * (size_t)(sparams->point_dim + h.F - 3);
+    HostMirror m(c);
+    const auto feats = m.in(h.seg_feats, sizeof(double) * (size_t)N * (size_t)h.F);
+    const auto times = m.in(h.seg_times, sizeof(double) * 2 * (size_t)N);
+    const auto ids = m.in(h.seg_ids, h.seg_ids ? sizeof(int64_t) * (size_t)N : 0);
+    const auto dPool = m.inout(h.pool, bPool);
+    const auto idsOut = m.inout(h.ids_out, h.ids_out ? sizeof(int64_t) * rows : 0);
+    const auto descOut = m.inout(h.desc_out, h.desc_out ? sizeof(double) * (size_t)S * (size_t)h.desc_dim : 0);
+    const auto dSrc = m.inout(h.src, sizeof(int32_t) * rows);
+    const auto cnt = m.inout(h.count, sizeof(int32_t) * (size_t)S);
+    const auto st = m.inout(h.status, sizeof(int32_t) * (size_t)S);
+    const auto chg = m.out(changed, changed ? sizeof(int32_t) * (size_t)L : 0);
+    rc = m.upload();
+    if (rc) return rc;
+    SessionSubmapsArgs g = h;
+    g.seg_feats = feats.dev(); g.seg_times = times.dev(); g.seg_ids = ids.dev();
+    g.pool = dPool.dev(); g.count = cnt.dev(); g.src = dSrc.dev(); g.ids_out = idsOut.dev(); g.status = st.dev(); g.desc_out = descOut.dev();
+    rc = session_submaps_list_dev(c, sparams, g, L, list, chg.dev());
+    if (rc) return rc;
+    return m.download();
+}
+
+int roman_session_submaps_list_dev(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
+                                   const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
+                                   double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out,
+                                   int32_t L, const int32_t* list, int32_t* changed)
+{
+    const SessionSubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
+    return session_submaps_list_dev(c, sparams, g, L, list, changed);
+}
+
+int roman_session_submaps_list(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
+                               const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
+                               double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out,
+                               int32_t L, const int32_t* list, int32_t* changed)
+{
+    const SessionSubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
+    return session_submaps_list_host(c, sparams, g, L, list, changed);
 }
 
 // --- force-fill submaps and the boxes of a pool ([REF roman/map/map.py:264-295], [REF :133-139]) -------------------

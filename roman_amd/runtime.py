@@ -788,6 +788,59 @@ class Context:
         self._enqueue("roman_session_submaps_dev", C.byref(sparams), R, int(F), _ptr(seg_off), *_vps(seg_feats_ptr, seg_times_ptr, seg_ids_ptr),
                       _ptr(sub_off), _ptr(descs), *_vps(pool_ptr, count_ptr, src_ptr, ids_out_ptr, status_ptr), int(desc_dim), _vp(desc_out_ptr))
 
+    @staticmethod
+    def _submap_list(lst):
+        """The listed submaps of a session in the C ABI's type -> int32[L] (strictly ascending is the library's to judge)."""
+        return np.ascontiguousarray(lst, dtype=np.int32).reshape(-1)
+
+    def session_submaps_list(self, sparams, seg_off, seg_feats, seg_times, sub_off, descs, lst, pool, count, src, status, seg_ids=None, ids_out=None,
+                             desc_dim=0, desc_out=None, want_changed=True):
+        """Host-pointer rebuild of the LISTED submaps of a session in place (roman_session_submaps_list): the tables as
+        for session_submaps(); `lst` the global submap indices, strictly ascending; pool, count, src, status (and ids_out, desc_out) the
+        session's CURRENT outputs (C-contiguous, the C ABI's shapes and types), which the call changes in the listed slots only.
+        -> (SubmapsResult over the caller's arrays, changed int32[L] or None)."""
+        seg_feats = _f64(seg_feats); seg_times = _f64(seg_times)
+        if seg_feats.ndim != 2 or seg_times.shape != (seg_feats.shape[0], 2):
+            raise ValueError("seg_feats must be (N, F) and seg_times (N, 2)")
+        N, F = seg_feats.shape
+        if seg_ids is not None:
+            seg_ids = np.ascontiguousarray(seg_ids, dtype=np.int64).reshape(-1)
+            if seg_ids.shape[0] != N:
+                raise ValueError("seg_ids must hold one entry per segment")
+        seg_off, sub_off, R = self._session_offsets(seg_off, sub_off)
+        descs = self._submap_descs(descs)
+        S = int(descs.shape[0])
+        if int(seg_off[-1]) != N or int(sub_off[-1]) != S:
+            raise ValueError("seg_off[R] must be the rows of seg_feats and sub_off[R] the number of descs")
+        rows, Fo, d = S * max(int(sparams.cap), 0), int(sparams.point_dim) + F - 3, int(desc_dim)
+        for a, shape, dt in ((pool, (rows, max(Fo, 0)), np.float64), (count, (S,), np.int32), (src, (rows,), np.int32), (status, (S,), np.int32)):
+            if a is None:
+                raise ValueError("pool, count, src and status are the session's current outputs: all are needed")
+            _given(a, shape, dt, 0)
+        if ids_out is not None:
+            _given(ids_out, (rows,), np.int64, 0)
+        if desc_out is not None:
+            _given(desc_out, (S, d), np.float64, 0)
+        lst = self._submap_list(lst)
+        changed = np.zeros(len(lst), dtype=np.int32) if want_changed else None
+        self._enqueue("roman_session_submaps_list", C.byref(sparams), R, F, _ptr(seg_off), _ptr(seg_feats), _ptr(seg_times), _ptr(seg_ids), _ptr(sub_off),
+                      _ptr(descs), _ptr(pool), _ptr(count), _ptr(src), _ptr(ids_out), _ptr(status), d, _ptr(desc_out), int(len(lst)), _ptr(lst), _ptr(changed))
+        return SubmapsResult(pool, count, src, ids_out, status, desc_out), changed
+
+    def session_submaps_list_dev(self, sparams, F, seg_off, seg_feats_ptr, seg_times_ptr, sub_off, descs, lst, pool_ptr, count_ptr, src_ptr, status_ptr,
+                                 seg_ids_ptr=None, ids_out_ptr=None, desc_dim=0, desc_out_ptr=None, changed_ptr=None):
+        """Device-pointer rebuild of the LISTED submaps of a session in place (roman_session_submaps_list_dev): the arguments of
+        session_submaps_dev over the whole session, `lst` the global submap indices (host, strictly ascending) and `changed_ptr` a
+        device int32[L] or None.  A pure enqueue on the context's stream; complete after sync()."""
+        seg_off, sub_off, R = self._session_offsets(seg_off, sub_off)
+        descs = self._submap_descs(descs)
+        if int(sub_off[-1]) != int(descs.shape[0]):
+            raise ValueError("sub_off[R] must be the number of descs")
+        lst = self._submap_list(lst)
+        self._enqueue("roman_session_submaps_list_dev", C.byref(sparams), R, int(F), _ptr(seg_off), *_vps(seg_feats_ptr, seg_times_ptr, seg_ids_ptr),
+                      _ptr(sub_off), _ptr(descs), *_vps(pool_ptr, count_ptr, src_ptr, ids_out_ptr, status_ptr), int(desc_dim), _vp(desc_out_ptr),
+                      int(len(lst)), _ptr(lst), _vp(changed_ptr))
+
     # ------------------------------------------------------------------ pass 1 of a grid of submaps
     def grid_gate(self, gparams, pos0, T_w0, pos1, T_w1, time0=None, time1=None, desc0=None, desc1=None, pos_gt0=None, pos_gt1=None,
                   pairs=None, T_ref=None, enable=None):
