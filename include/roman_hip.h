@@ -1295,6 +1295,41 @@ ROMAN_API int roman_session_stacked_sim(roman_ctx_t* ctx, int32_t d, int32_t Nf,
                                         int32_t nb, const int32_t* blocks, const int64_t* pair_off, double* sim);
 
 /*
+ * roman_session_stacked_sim_list_dev: roman_session_stacked_sim_dev for an explicit LIST of pairs — what a session
+ * that grows asks for: the similarity of the pairs a new or changed submap touches, not of whole blocks.  The arguments up to
+ * pair_off_host are roman_session_stacked_sim_dev's.  Every bulk pointer DEVICE; a PURE ENQUEUE on the context's stream (the norms of
+ * the frame table, then one wave per listed pair); the small tables and the list travel twice (device, and `_host` copies).
+ *
+ *   L, list    int32[L][3]: (b, i, j) — roman_session_gate_list_dev's list, strictly ascending, validated by the same code
+ *   sim        float64[pair_off[nb]] in the DENSE layout: for each listed pair the call writes sim[pair_off[b] + i * n1 + j], BIT FOR
+ *              BIT what roman_session_stacked_sim_dev writes there over the same tables (-inf for an empty mask or a view without
+ *              frames, 0 where |a| |b| <= 1e-9).  No other element of sim is read or written:
+ *              roman_session_gate_list_dev(..., sim_in = sim) follows on the same stream
+ *
+ * No atomics, no band workspace; two runs agree bit for bit; a pair's result does not depend on which other pairs are listed.  A
+ * mask may select any number of frames.  L == 0: ROMAN_OK, nothing written.  A failed allocation of the norms: ROMAN_E_NOMEM,
+ * nothing enqueued, the context stays usable.
+ * Errors, judged on host memory in front of everything else (a NULL context included), in this order: what
+ * roman_session_gate_dev refuses about sub_off, blocks and pair_off; d < 1, a frame range outside [0, Nf], a negative mask_off, a
+ * NULL desc / mask that is needed; then L < 0, a NULL list with L > 0, an entry with b outside [0, nb) or (i, j) outside its
+ * block, a list not strictly ascending, a NULL sim with L > 0 -> ROMAN_E_INVALID.  The `_host` copies are judged in front of the
+ * device pointers: a NULL device table or device list is refused (ROMAN_E_INVALID) behind all of the above.
+ * desc and mask are needed — and read — only while a block has submaps and frames on BOTH sides.  Without such a block both may
+ * be NULL whatever Nf and L are: every listed pair is -inf, the norms are not computed and neither pointer is touched.
+ */
+ROMAN_API int roman_session_stacked_sim_list_dev(roman_ctx_t* ctx, int32_t d, int32_t Nf, const double* desc, const uint64_t* mask,
+                                                 int32_t R, const int32_t* frame_lo, const int32_t* frame_lo_host, const int32_t* frame_n, const int32_t* frame_n_host,
+                                                 const int64_t* mask_off, const int64_t* mask_off_host, const int32_t* sub_off, const int32_t* sub_off_host,
+                                                 int32_t nb, const int32_t* blocks, const int32_t* blocks_host, const int64_t* pair_off, const int64_t* pair_off_host,
+                                                 int32_t L, const int32_t* list, const int32_t* list_host, double* sim);
+
+/* The same with HOST pointers everywhere (each table and the list once).  Synchronous.  The caller's sim goes up first: the entries
+   that are not listed come back as they were.  mask_words as roman_session_stacked_sim takes it. */
+ROMAN_API int roman_session_stacked_sim_list(roman_ctx_t* ctx, int32_t d, int32_t Nf, const double* desc, const uint64_t* mask, int64_t mask_words,
+                                             int32_t R, const int32_t* frame_lo, const int32_t* frame_n, const int64_t* mask_off, const int32_t* sub_off,
+                                             int32_t nb, const int32_t* blocks, const int64_t* pair_off, int32_t L, const int32_t* list, double* sim);
+
+/*
  * roman_session_boxes_dev: roman_submap_boxes_dev — what aabb_intersects [REF roman/utils.py:160-169] reads of
  * Submap.segments_as_global_points [REF roman/map/map.py:133-139] — over the submap table of a whole session instead of one pool's
  * slots.  Every pointer DEVICE; a PURE ENQUEUE on the context's stream; one launch, no launch per robot, no gather of rows.

@@ -1280,13 +1280,16 @@ def _session_pool(torch, s, lv):
             np.concatenate([p[r].offsets()[1] for r, _ in lv]).astype(np.int32))
 
 
-def _session_pass1_front(torch, ctx, s, u, sub_off, blk, pair_off, n_out, one_pool, sim_total=None):
+def _session_pass1_front(torch, ctx, s, u, sub_off, blk, pair_off, n_out, one_pool, sim_total=None, lst=None):
     """What pass 1 of a session enqueues in front of its gate -> (g, gp, gate_kw): g the gate's output buffers, `n_out` entries each
     (todo_off: one per block and one), gp its parameters, gate_kw its optional pointers.  Behind wait_torch(), on the context's
     stream: for the bounding-box gate ONE session_boxes_dev over `one_pool` (`_session_pool`'s: rows by offset and count, no
     gather into slots; a view's own T_odom_center — two views of a robot: the same rows, two box sets) into t["box"]; for
     stacked descriptors session_stacked_sim_dev over whole blocks — into g["sim"], or with `sim_total` into a dense buffer of
-    that many entries, t["dense_sim"] —, which gate_kw hands to the gate as sim_in_ptr."""
+    that many entries, t["dense_sim"] —, which gate_kw hands to the gate as sim_in_ptr.  `lst` (with sim_total; t["list"] is its
+    device copy): the pairs the gate will read.  Where the list leaves a pair out and the context has
+    session_stacked_sim_list_dev, ONE such call writes the listed entries of t["dense_sim"] and nothing else (DESIGN.md §4.22);
+    a full list, a first call and a context without the entry take the whole-block call."""
     f64, i32 = torch.float64, torch.int32
     sm_params, t, up, ptr, dev, n = s.sm_params, u.t, u.up, u.ptr, u.dev, n_out
     if s.aabb_mode:
@@ -1307,9 +1310,12 @@ def _session_pass1_front(torch, ctx, s, u, sub_off, blk, pair_off, n_out, one_po
     if s.stacked:                                            # similarity first, then the gate that reads it: both on the context's stream
         gp.desc_thresh = float(sm_params.submap_descriptor_thresh)
         sim = (g["sim"] if sim_total is None else t["dense_sim"]).data_ptr()
-        ctx.session_stacked_sim_dev(int(u.fdesc.shape[1]), int(u.fdesc.shape[0]), ptr(u.fdesc), ptr(u.fmask), u.frame_lo, u.frame_n, u.mask_off, sub_off, blk,
-                                    pair_off, ptr(t["frame_lo"]), ptr(t["frame_n"]), ptr(t["mask_off"]), ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]),
-                                    sim)
+        tables = (u.frame_lo, u.frame_n, u.mask_off, sub_off, blk, pair_off)
+        table_ptrs = [ptr(t[k]) for k in ("frame_lo", "frame_n", "mask_off", "sub_off", "blocks", "pair_off")]
+        if sim_total is not None and lst is not None and len(lst) < sim_total and hasattr(ctx, "session_stacked_sim_list_dev"):
+            ctx.session_stacked_sim_list_dev(int(u.fdesc.shape[1]), int(u.fdesc.shape[0]), ptr(u.fdesc), ptr(u.fmask), *tables, lst, *table_ptrs, ptr(t["list"]), sim)
+        else:
+            ctx.session_stacked_sim_dev(int(u.fdesc.shape[1]), int(u.fdesc.shape[0]), ptr(u.fdesc), ptr(u.fmask), *tables, *table_ptrs, sim)
         gate_kw["sim_in_ptr"] = sim
     return g, gp, gate_kw
 
@@ -1533,8 +1539,9 @@ def submap_align_session_update(state, sm_params, pools, touched=None, robot_pai
     a partner going from an odd to an even count touches every submap of a robot whose poses alternate.  Nothing stale is reused
     silently: what these rules cannot see is the caller's to flag.
 
-    With 'stacked_frame_descriptors' the similarity is still computed for whole blocks (roman_session_stacked_sim_dev), the gate
-    then reads it at the listed pairs.
+    With 'stacked_frame_descriptors' the similarity too follows the list: one roman_session_stacked_sim_list_dev
+    writes the listed pairs' entries, the gate reads them there.  A call that lists every pair of every block (the first one),
+    and a context without that entry, compute the whole blocks with roman_session_stacked_sim_dev as before.
 
     ValueError before any context is made: whatever submap_align_session refuses; a pool that shrank; a `touched` of the wrong
     length; a state made for other robot_pairs, another method, descriptor mode, gate, ground-truth pattern or num_solutions."""
@@ -1645,9 +1652,9 @@ def submap_align_session_update(state, sm_params, pools, touched=None, robot_pai
     t["list"] = u.up(lst)
 
     # ---- pass 1 of the listed pairs on the device: one enqueue, one synchronisation, one read-back.  With stacked descriptors the
-    # similarity of the WHOLE blocks, then the gate that reads it at the listed pairs ----
+    # similarity of the listed pairs (of the whole blocks where everything is listed), then the gate that reads it there ----
     one_pool = _session_pool(torch, sess, u.lv)
-    g, gp, gate_kw = _session_pass1_front(torch, ctx, sess, u, sub_off, blk, pair_off, L, one_pool, sim_total=total)
+    g, gp, gate_kw = _session_pass1_front(torch, ctx, sess, u, sub_off, blk, pair_off, L, one_pool, sim_total=total, lst=lst)
     if aabb_mode:
         gate_kw["box_ptr"] = ptr(t["box"])
     ctx.session_gate_list_dev(gp, sub_off, blk, pair_off, lst, ptr(t["sub_off"]), ptr(t["blocks"]), ptr(t["pair_off"]), ptr(t["list"]), ptr(t["pos"]), ptr(t["T_w"]),

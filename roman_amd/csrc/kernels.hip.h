@@ -8408,6 +8408,7 @@ constexpr int STACK_TILE = 32;                                   // rows and col
 // One STACK_TILE x STACK_TILE tile (xt, yt) of a band — what a wave of k_stacked_band and of k_session_band does once it knows its
 // tile: rows [a0, a0 + H) of desc0 against the Nf1 rows of desc1 -> Cb[H][Nf1].  The contraction order of an element depends on d
 // alone, never on the tile, the band or the launch: that is what makes a session's block bit for bit roman_stacked_sim_dev's.
+// (stacked_contract(), k_session_stacked_list's, is a copy of the contraction loop below: a change here must be made there too.)
 __device__ __forceinline__ void stacked_tile(int d, int a0, int H, int Nf1, const double* desc0, const double* desc1, const double* norm0, const double* norm1,
                                              double* Cb, int xt, int yt)
 {
@@ -8611,6 +8612,161 @@ __global__ void __launch_bounds__(256) k_session_rowmax(SsTab tab, const int64_t
     double m = -INFINITY;                                        // a view without frames: the maximum over nothing
     if (Nf0 > 0 && Nf1 > 0) m = stacked_rowmax_one((int)(l / n1), (int)(l % n1), (Nf1 + 63) >> 6, Nf1, mask + tab.mask_off[r1], R + r_off[b]);
     if (lane == 0) sim[p] = m;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The stacked similarity of a LIST of pairs of a session (roman_session_stacked_sim_list*): what a growing session
+// asks for — only the pairs a new or changed submap touches.  k_grid_norms over the frame table, then
+//   k_session_stacked_list  ONE WAVE per listed pair (b, i, j): the entry, its block, the two views and their frame ranges through
+//                     scalar loads.  The wave walks the selected frames of mask0[i] in chunks of STACK_TILE (tile rows) and inside
+//                     that those of mask1[j] (tile columns); lane (lr, kq) finds the frames of rank 16 h + lr of a chunk by a
+//                     wave-uniform walk over the mask words with a running popcount (ss_gather), and the tile is
+//                     stacked_contract() over those rows — stacked_tile()'s operations, the row addresses gathered.  The epilogue
+//                     divides by the norms as stacked_tile() does and keeps a per-lane maximum; a butterfly, lane 0 stores at the
+//                     pair's DENSE position.
+// An element's bits depend on d alone (not on its place in a tile), and fmax over one set of doubles does not depend on the order
+// (NaN ignored on both sides): the maximum of a pair equals roman_session_stacked_sim_dev's column-then-row maximum bit for bit.
+// Nothing is sized by the number of selected frames.  No atomics, no LDS, no scratch.
+// ---------------------------------------------------------------------------------------------
+// The contraction of one STACK_TILE x STACK_TILE tile over GATHERED rows: lane (lr, kq) holds the rows fa[h] / fb[h] (h = 0, 1: tile
+// row / column 16 h + lr, already advanced by 4 kq), va / vb say which of them exist (the others are multiplied as 0).  A SIBLING COPY
+// of stacked_tile()'s loop, operation for operation — 2 x 2 blocks of v_mfma_f64_16x16x4, chunks of 16 ascending, step t contracts
+// k = 16 c + 4 kq + t, the same 32-byte loads, zero-fill and ragged tail — so the order of an element's sum depends on d alone, not
+// on where its row and column sit in the tile nor on where the rows come from.  (One function for both was tried: it cost
+// k_stacked_band two VGPRs and k_session_band a wave of occupancy; a change to one loop must be made in the other.)
+__device__ __forceinline__ void stacked_contract(int d, int kq, const double* const (&fa)[2], const double* const (&fb)[2], const bool (&va)[2],
+                                                 const bool (&vb)[2], double4_t (&acc)[2][2])
+{
+#pragma unroll
+    for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[x][y] = double4_t{0.0, 0.0, 0.0, 0.0};
+    const int nfull = d >> 4;
+    for (int c = 0; c < nfull; ++c) {
+        d4u_t ra[2], rb[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) { ra[h] = *reinterpret_cast<const d4u_t*>(fa[h] + 16 * c); rb[h] = *reinterpret_cast<const d4u_t*>(fb[h] + 16 * c); }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 2; ++y)
+                    acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[x] ? ra[x].v[t] : 0.0, vb[y] ? rb[y].v[t] : 0.0, acc[x][y], 0, 0, 0);
+    }
+    const int k0 = 16 * nfull;
+    if (k0 < d) {                                                // ragged tail of the descriptor (< 16 elements)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const bool vk = k0 + 4 * kq + t < d;
+            double av[2], bv[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) { av[h] = (va[h] && vk) ? fa[h][k0 + t] : 0.0; bv[h] = (vb[h] && vk) ? fb[h][k0 + t] : 0.0; }
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 2; ++y) acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[x], bv[y], acc[x][y], 0, 0, 0);
+        }
+    }
+}
+
+// position of the k-th set bit of x (k < popcount(x)): six halvings, no loop over the bits
+__device__ __forceinline__ int ss_nth_bit(unsigned long long x, int k)
+{
+    int pos = 0;
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        const int c = __popcll(x & ((1ull << s) - 1ull));
+        if (k >= c) { k -= c; x >>= s; pos += s; }
+    }
+    return pos;
+}
+
+// Where a walk over a mask row stands (wave-uniform): word w, and the set bits of the words in front of it
+struct SsCursor { int w, cnt; };
+
+// The frames of rank base + 16 h + lr (h = 0, 1) among the set bits of the mask row `m` (W words, bits at Nf and beyond ignored)
+// -> idx[h], or -1 where the row selects fewer; returns the selected frames of rank >= base that the chunk holds (0 ..
+// STACK_TILE).  `cur` never passes a word that still holds a frame of rank >= base, and is left at the first word the next chunk
+// (base + STACK_TILE) needs: chunks are asked for in ascending order.
+__device__ __forceinline__ int ss_gather(const unsigned long long* __restrict__ m, int W, int Nf, int base, int lr, SsCursor& cur, int (&idx)[2])
+{
+    idx[0] = -1; idx[1] = -1;
+    int w = cur.w, cnt = cur.cnt;
+    while (w < W && cnt < base + STACK_TILE) {                   // (uniform)
+        unsigned long long bits = m[w];
+        if (64 * w + 64 > Nf) bits &= (1ull << (Nf - 64 * w)) - 1ull;       // (the last word: 0 < Nf - 64 w < 64)
+        const int pc = __popcll(bits);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int k = base + 16 * h + lr - cnt;
+            if (k >= 0 && k < pc) idx[h] = 64 * w + ss_nth_bit(bits, k);
+        }
+        if (cnt + pc > base + STACK_TILE) break;                 // the word holds frames of the next chunk: the cursor stays in front of it
+        cnt += pc; ++w;
+        cur.w = w; cur.cnt = cnt;
+    }
+    if (w < W) return STACK_TILE;                                // (left by the break, or by a full chunk: cnt >= base + STACK_TILE)
+    return min(max(cnt - base, 0), STACK_TILE);
+}
+
+__global__ void __launch_bounds__(256) k_session_stacked_list(int d, SsTab tab, int L, const int32_t* __restrict__ list, const double* __restrict__ desc,
+                                                              const double* __restrict__ norm, const unsigned long long* __restrict__ mask,
+                                                              double* __restrict__ sim)
+{
+    const int lane = threadIdx.x & 63, lr = lane & 15, kq = lane >> 4;
+    const int64_t l = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (l >= L) return;                                          // (wave-uniform, as everything but the gathered rows)
+    const int b = list[3 * l], i = list[3 * l + 1], j = list[3 * l + 2];
+    const int r0 = tab.blocks[4 * b], r1 = tab.blocks[4 * b + 1];
+    const int n1 = tab.sub_off[r1 + 1] - tab.sub_off[r1];
+    const int lo0 = tab.frame_lo[r0], lo1 = tab.frame_lo[r1], Nf0 = tab.frame_n[r0], Nf1 = tab.frame_n[r1];
+    const int W0 = (Nf0 + 63) >> 6, W1 = (Nf1 + 63) >> 6;
+    const unsigned long long* m0 = mask + tab.mask_off[r0] + (int64_t)i * W0;
+    const unsigned long long* m1 = mask + tab.mask_off[r1] + (int64_t)j * W1;
+    const double* desc0 = desc + (int64_t)lo0 * d; const double* desc1 = desc + (int64_t)lo1 * d;
+    const double* norm0 = norm + lo0; const double* norm1 = norm + lo1;
+    double best = -INFINITY;                                     // an empty mask, a view without frames: the maximum over nothing
+    if (Nf0 > 0 && Nf1 > 0) {
+        SsCursor c0{0, 0};
+        for (int bx = 0;; bx += STACK_TILE) {                    // tile rows: the next STACK_TILE selected frames of mask0[i]
+            int ia[2];
+            const int nx = ss_gather(m0, W0, Nf0, bx, lr, c0, ia);
+            if (nx == 0) break;
+            const double* fa[2]; bool va[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) { va[h] = ia[h] >= 0; fa[h] = desc0 + (int64_t)(va[h] ? ia[h] : 0) * d + 4 * kq; }   // (an invalid row reads the view's first frame)
+            SsCursor c1{0, 0};
+            for (int by = 0;; by += STACK_TILE) {                // tile columns: the same over mask1[j]
+                int jb[2];
+                const int ny = ss_gather(m1, W1, Nf1, by, lr, c1, jb);
+                if (ny == 0) break;
+                const double* fb[2]; bool vb[2];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) { vb[h] = jb[h] >= 0; fb[h] = desc1 + (int64_t)(vb[h] ? jb[h] : 0) * d + 4 * kq; }
+                double4_t acc[2][2];
+                stacked_contract(d, kq, fa, fb, va, vb, acc);
+#pragma unroll
+                for (int y = 0; y < 2; ++y) {
+                    const double nb = vb[y] ? norm1[jb[y]] : 0.0;
+#pragma unroll
+                    for (int x = 0; x < 2; ++x)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int row = __shfl(ia[x], kq + 4 * r);      // tile row 16 x + kq + 4 r: the lane with that lr holds its frame
+                            if (row >= 0 && vb[y]) {
+                                const double np_ = norm0[row] * nb;
+                                best = fmax(best, (np_ <= 1e-9) ? 0.0 : acc[x][y][r] / np_);       // [REF roman/map/map.py:159-161]
+                            }
+                        }
+                }
+                if (ny < STACK_TILE) break;
+            }
+            if (nx < STACK_TILE) break;
+        }
+    }
+    best = wave_max_all(best);
+    if (lane == 0) sim[tab.pair_off[b] + (int64_t)i * n1 + j] = best;
 }
 
 // elementwise math probe for tests

@@ -3836,6 +3836,25 @@ static auto session_gate_list_kernel(bool sim_in, bool aabb)
                   : (aabb ? k_session_gate_list<false, true> : k_session_gate_list<false, false>);
 }
 
+// A pair list (L > 0 entries (b, i, j)) on its host copy, against tables that passed session_tables_check — what
+// roman_session_gate_list* and roman_session_stacked_sim_list* refuse about it
+static int session_pair_list_check(roman_ctx* c, const int32_t* sub_off, int32_t nb, const int32_t* blocks, int32_t L, const int32_t* list_host)
+{
+    if ((int64_t)L > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "L = %d pairs: L * 16 exceeds the index width", L);
+    if (!list_host) return fail(c, ROMAN_E_INVALID, "list is NULL with L=%d", L);
+    for (int64_t l = 0; l < L; ++l) {
+        const int32_t* e = list_host + 3 * l;
+        if (e[0] < 0 || e[0] >= nb) return fail(c, ROMAN_E_INVALID, "list entry %lld names block %d outside [0, %d)", (long long)l, e[0], nb);
+        const int32_t r0 = blocks[4 * e[0]], r1 = blocks[4 * e[0] + 1];
+        const int32_t n0 = sub_off[r0 + 1] - sub_off[r0], n1 = sub_off[r1 + 1] - sub_off[r1];
+        if (e[1] < 0 || e[1] >= n0 || e[2] < 0 || e[2] >= n1)
+            return fail(c, ROMAN_E_INVALID, "list entry %lld: pair (%d, %d) lies outside the %d x %d grid of block %d", (long long)l, e[1], e[2], n0, n1, e[0]);
+        if (l > 0 && !std::lexicographical_compare(e - 3, e, e, e + 3))
+            return fail(c, ROMAN_E_INVALID, "the list is not strictly ascending in (block, i, j) at entry %lld", (long long)l);
+    }
+    return ROMAN_OK;
+}
+
 // the tables first (session_tables_check, as the whole-grid calls judge them), then the list on its host copy
 static int session_gate_list_check(roman_ctx* c, const roman_grid_gate_params_t* P, const SessionListArgs& a)
 {
@@ -3847,18 +3866,7 @@ static int session_gate_list_check(roman_ctx* c, const roman_grid_gate_params_t*
     int64_t total = 0, tiles = 0;
     { int rc = session_tables_check(c, R, g.sub_off, nb, g.blocks, g.pair_off, nullptr, &total, &tiles, &self); if (rc) return rc; }
     if (L == 0) return ROMAN_OK;
-    if ((int64_t)L > (int64_t)(INT32_MAX / 16)) return fail(c, ROMAN_E_TOO_LARGE, "L = %d pairs: L * 16 exceeds the index width", L);
-    if (!a.list_host) return fail(c, ROMAN_E_INVALID, "list is NULL with L=%d", L);
-    for (int64_t l = 0; l < L; ++l) {
-        const int32_t* e = a.list_host + 3 * l;
-        if (e[0] < 0 || e[0] >= nb) return fail(c, ROMAN_E_INVALID, "list entry %lld names block %d outside [0, %d)", (long long)l, e[0], nb);
-        const int32_t r0 = g.blocks[4 * e[0]], r1 = g.blocks[4 * e[0] + 1];
-        const int32_t n0 = g.sub_off[r0 + 1] - g.sub_off[r0], n1 = g.sub_off[r1 + 1] - g.sub_off[r1];
-        if (e[1] < 0 || e[1] >= n0 || e[2] < 0 || e[2] >= n1)
-            return fail(c, ROMAN_E_INVALID, "list entry %lld: pair (%d, %d) lies outside the %d x %d grid of block %d", (long long)l, e[1], e[2], n0, n1, e[0]);
-        if (l > 0 && !std::lexicographical_compare(e - 3, e, e, e + 3))
-            return fail(c, ROMAN_E_INVALID, "the list is not strictly ascending in (block, i, j) at entry %lld", (long long)l);
-    }
+    { int rc = session_pair_list_check(c, g.sub_off, nb, g.blocks, L, a.list_host); if (rc) return rc; }
     if (P->desc_dim > 0 && !g.s.desc) return fail(c, ROMAN_E_INVALID, "desc is NULL with desc_dim=%d", P->desc_dim);
     if (!g.s.pos || !g.s.T_w) return fail(c, ROMAN_E_INVALID, "pos / T_w is NULL");
     if (g.s.pos_gt && !g.tab.has_gt) return fail(c, ROMAN_E_INVALID, "has_gt is NULL with pos_gt");
@@ -4121,6 +4129,17 @@ int roman_stacked_sim(roman_ctx_t* c, int32_t d, int32_t Nf0, const double* desc
 // One live block (submaps and frames on both sides) as the host sees it while it cuts the items.
 struct SsLive { int32_t b; int64_t n0, Nf0, Nf1, r_off, a; };
 
+// every view's frames inside the table of Nf frames, no negative mask offset
+static int session_views_check(roman_ctx* c, int32_t Nf, int32_t R, const int32_t* frame_lo, const int32_t* frame_n, const int64_t* mask_off)
+{
+    for (int r = 0; r < R; ++r) {
+        if (frame_lo[r] < 0 || frame_n[r] < 0 || (int64_t)frame_lo[r] + frame_n[r] > (int64_t)Nf)
+            return fail(c, ROMAN_E_INVALID, "view %d: the frames [%d, %d + %d) leave the table of %d", r, frame_lo[r], frame_lo[r], frame_n[r], Nf);
+        if (mask_off[r] < 0) return fail(c, ROMAN_E_INVALID, "view %d: mask_off=%lld is negative", r, (long long)mask_off[r]);
+    }
+    return ROMAN_OK;
+}
+
 // The tables are checked on their HOST copies (no read-back).  -> *total = pair_off[nb], the live blocks with their R offsets,
 // *r_total: the doubles of all R together
 static int session_stacked_check(roman_ctx* c, int32_t d, int32_t Nf, const void* desc, const void* mask, int32_t R, const int32_t* frame_lo,
@@ -4131,11 +4150,7 @@ static int session_stacked_check(roman_ctx* c, int32_t d, int32_t Nf, const void
     if (Nf < 0 || R < 0 || nb < 0) return fail(c, ROMAN_E_INVALID, "Nf < 0, R < 0 or nb < 0");
     if (!sub_off || !pair_off || (nb > 0 && !blocks) || (R > 0 && (!frame_lo || !frame_n || !mask_off)))
         return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / frame_lo / frame_n / mask_off is NULL");
-    for (int r = 0; r < R; ++r) {
-        if (frame_lo[r] < 0 || frame_n[r] < 0 || (int64_t)frame_lo[r] + frame_n[r] > (int64_t)Nf)
-            return fail(c, ROMAN_E_INVALID, "view %d: the frames [%d, %d + %d) leave the table of %d", r, frame_lo[r], frame_lo[r], frame_n[r], Nf);
-        if (mask_off[r] < 0) return fail(c, ROMAN_E_INVALID, "view %d: mask_off=%lld is negative", r, (long long)mask_off[r]);
-    }
+    { int rc = session_views_check(c, Nf, R, frame_lo, frame_n, mask_off); if (rc) return rc; }
     int64_t tiles = 0; bool self = false;
     { int rc = session_tables_check(c, R, sub_off, nb, blocks, pair_off, nullptr, total, &tiles, &self); if (rc) return rc; }
     if (*total == 0) return ROMAN_OK;
@@ -4263,6 +4278,97 @@ int roman_session_stacked_sim(roman_ctx_t* c, int32_t d, int32_t Nf, const doubl
     if (rc) return rc;
     rc = roman_session_stacked_sim_dev(c, d, Nf, dDesc.dev(), dMask.dev(), R, dLo.dev(), frame_lo, dN.dev(), frame_n, dMo.dev(), mask_off, dSub.dev(), sub_off,
                                        nb, dBlk.dev(), blocks, dPo.dev(), pair_off, dSim.dev());
+    if (rc) return rc;
+    return m.download();
+}
+
+// --- the stacked similarity of a list of pairs of a session -------------------------------------------------------
+// On host memory, in front of everything else: the tables (session_tables_check), then what roman_session_stacked_sim_dev refuses
+// about d, the views and the pointers it needs, then the list as roman_session_gate_list_dev judges it, then sim.
+// -> *live_out: a block has submaps and frames on both sides (only then are desc and mask read, by any kernel)
+static int session_stacked_list_check(roman_ctx* c, int32_t d, int32_t Nf, const void* desc, const void* mask, int32_t R, const int32_t* frame_lo,
+                                      const int32_t* frame_n, const int64_t* mask_off, const int32_t* sub_off, int32_t nb, const int32_t* blocks,
+                                      const int64_t* pair_off, int32_t L, const int32_t* list_host, const void* sim, bool* live_out)
+{
+    if (Nf < 0 || R < 0 || nb < 0) return fail(c, ROMAN_E_INVALID, "Nf < 0, R < 0 or nb < 0");
+    if (!sub_off || !pair_off || (nb > 0 && !blocks) || (R > 0 && (!frame_lo || !frame_n || !mask_off)))
+        return fail(c, ROMAN_E_INVALID, "sub_off / blocks / pair_off / frame_lo / frame_n / mask_off is NULL");
+    int64_t total = 0, tiles = 0; bool self = false;
+    { int rc = session_tables_check(c, R, sub_off, nb, blocks, pair_off, nullptr, &total, &tiles, &self); if (rc) return rc; }
+    if (d < 1) return fail(c, ROMAN_E_INVALID, "d=%d: a frame descriptor has at least one component", d);
+    { int rc = session_views_check(c, Nf, R, frame_lo, frame_n, mask_off); if (rc) return rc; }
+    bool live = false;                                           // a block with submaps and frames on both sides: desc and mask are read
+    for (int b = 0; b < nb && !live; ++b) {
+        const int32_t r0 = blocks[4 * b], r1 = blocks[4 * b + 1];
+        live = sub_off[r0 + 1] > sub_off[r0] && sub_off[r1 + 1] > sub_off[r1] && frame_n[r0] > 0 && frame_n[r1] > 0;
+    }
+    *live_out = live;
+    if (live && (!desc || !mask)) return fail(c, ROMAN_E_INVALID, "desc / mask is NULL");
+    if (L < 0) return fail(c, ROMAN_E_INVALID, "L=%d is negative", L);
+    if (L == 0) return ROMAN_OK;
+    { int rc = session_pair_list_check(c, sub_off, nb, blocks, L, list_host); if (rc) return rc; }
+    if (!sim) return fail(c, ROMAN_E_INVALID, "sim is NULL with L=%d", L);
+    return ROMAN_OK;
+}
+
+int roman_session_stacked_sim_list_dev(roman_ctx_t* c, int32_t d, int32_t Nf, const double* desc, const uint64_t* mask,
+                                       int32_t R, const int32_t* frame_lo, const int32_t* frame_lo_host, const int32_t* frame_n, const int32_t* frame_n_host,
+                                       const int64_t* mask_off, const int64_t* mask_off_host, const int32_t* sub_off, const int32_t* sub_off_host,
+                                       int32_t nb, const int32_t* blocks, const int32_t* blocks_host, const int64_t* pair_off, const int64_t* pair_off_host,
+                                       int32_t L, const int32_t* list, const int32_t* list_host, double* sim)
+{
+    // (the arguments are judged first — on host memory only, a NULL context included — and the host copies in front of the device
+    // pointers: the stated order of the refusals holds whatever the device pointers are)
+    bool live = false;
+    int rc = session_stacked_list_check(c, d, Nf, desc, mask, R, frame_lo_host, frame_n_host, mask_off_host, sub_off_host, nb, blocks_host, pair_off_host,
+                                        L, list_host, sim, &live);
+    if (rc) return rc;
+    if (!sub_off || !pair_off || (nb > 0 && !blocks) || (R > 0 && (!frame_lo || !frame_n || !mask_off)) || (L > 0 && !list))
+        return fail(c, ROMAN_E_INVALID, "a table or the list is NULL on the device");
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (L == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    HIPCHK(c, c->ssNorm.ensure(sizeof(double) * (size_t)std::max<int32_t>(Nf, 1)));     // scratch first: a failure leaves nothing enqueued
+    double* const dNorm = c->ssNorm.as<double>();
+    const SsTab tab{(int)nb, sub_off, blocks, pair_off, frame_lo, frame_n, mask_off};
+    if (live)                                                    // once per frame of the session, over the frame table as it stands; without a
+                                                                 // live block no pair reads a frame, and desc may be NULL
+        hipLaunchKernelGGL(k_grid_norms, dim3((unsigned)(((int64_t)Nf + 3) / 4)), dim3(256), 0, stream, (int)Nf, 0, (int)d, desc, (const double*)nullptr, dNorm);
+    hipLaunchKernelGGL(k_session_stacked_list, dim3((unsigned)(((int64_t)L + 3) / 4)), dim3(256), 0, stream, (int)d, tab, (int)L, list, desc, (const double*)dNorm,
+                       reinterpret_cast<const unsigned long long*>(mask), sim);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_session_stacked_sim_list(roman_ctx_t* c, int32_t d, int32_t Nf, const double* desc, const uint64_t* mask, int64_t mask_words,
+                                   int32_t R, const int32_t* frame_lo, const int32_t* frame_n, const int64_t* mask_off, const int32_t* sub_off,
+                                   int32_t nb, const int32_t* blocks, const int64_t* pair_off, int32_t L, const int32_t* list, double* sim)
+{
+    bool live = false;
+    int rc = session_stacked_list_check(c, d, Nf, desc, mask, R, frame_lo, frame_n, mask_off, sub_off, nb, blocks, pair_off, L, list, sim, &live);
+    if (rc) return rc;
+    if (mask_words < 0) return fail(c, ROMAN_E_INVALID, "mask_words=%lld is negative", (long long)mask_words);
+    for (int r = 0; r < R; ++r)                                  // the host twin copies `mask`: every view must lie inside the words it was given
+        if (mask_off[r] + (int64_t)(sub_off[r + 1] - sub_off[r]) * (((int64_t)frame_n[r] + 63) / 64) > mask_words)
+            return fail(c, ROMAN_E_INVALID, "view %d: its masks leave the %lld words of mask", r, (long long)mask_words);
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (L == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    HostMirror m(c);
+    // (without a live block desc and mask are not read and may be NULL: nothing of them goes up)
+    const auto dDesc = m.in(desc, live ? 8 * (size_t)Nf * (size_t)d : 0);
+    const auto dMask = m.in(mask, live ? 8 * (size_t)mask_words : 0);
+    const auto dLo = m.in(frame_lo, 4 * (size_t)R), dN = m.in(frame_n, 4 * (size_t)R);
+    const auto dMo = m.in(mask_off, 8 * (size_t)R);
+    const auto dSub = m.in(sub_off, 4 * ((size_t)R + 1)), dBlk = m.in(blocks, 16 * (size_t)nb), dList = m.in(list, 12 * (size_t)L);
+    const auto dPo = m.in(pair_off, 8 * ((size_t)nb + 1));
+    const auto dSim = m.inout(sim, 8 * (size_t)pair_off[nb]);    // the caller's sim goes up first: the unlisted entries come back as they were
+    rc = m.upload();
+    if (rc) return rc;
+    rc = roman_session_stacked_sim_list_dev(c, d, Nf, dDesc.dev(), dMask.dev(), R, dLo.dev(), frame_lo, dN.dev(), frame_n, dMo.dev(), mask_off, dSub.dev(), sub_off,
+                                            nb, dBlk.dev(), blocks, dPo.dev(), pair_off, L, dList.dev(), list, dSim.dev());
     if (rc) return rc;
     return m.download();
 }

@@ -1120,6 +1120,40 @@ class Context:
                                                      nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off), _vp(sim_ptr))
         self._check(rc, "roman_session_stacked_sim_dev")
 
+    # ------------------------------------------------------------------ ... and of a list of its pairs
+    def session_stacked_sim_list(self, desc, mask, frame_lo, frame_n, mask_off, sub_off, blocks, pair_off, pair_list, sim=None):
+        """Host-pointer stacked similarity of a LIST of pairs of a session (roman_session_stacked_sim_list): session_stacked_sim()'s
+        arguments, then pair_list (L, 3) int32 rows (b, i, j) as session_pair_list() builds them, strictly ascending.  `sim`
+        (pair_off[nb],): the dense array the listed entries are written into — the others come back as they were; None: NaN.
+        -> sim (pair_off[nb],) float64: a listed pair at pair_off[b] + i * n1 + j, bit for bit session_stacked_sim()'s entry."""
+        desc = _f64(desc)
+        if desc.ndim != 2:
+            raise ValueError("session_stacked_sim_list needs an (Nf, d) frame table")
+        mask = np.ascontiguousarray(mask, dtype=np.uint64).reshape(-1)
+        frame_lo, frame_n, mask_off, sub_off, blocks, pair_off, R, nb = self._session_stacked_tables(frame_lo, frame_n, mask_off, sub_off, blocks, pair_off)
+        pair_list = np.ascontiguousarray(pair_list, dtype=np.int32).reshape(-1, 3)
+        sim = _given(sim, (max(int(pair_off[-1]), 0),), np.float64, np.nan)
+        self._generation += 1
+        rc = self._lib.roman_session_stacked_sim_list(self._h, desc.shape[1], desc.shape[0], _ptr(desc), _ptr(mask), mask.shape[0], R, _ptr(frame_lo),
+                                                      _ptr(frame_n), _ptr(mask_off), _ptr(sub_off), nb, _ptr(blocks), _ptr(pair_off), len(pair_list),
+                                                      _ptr(pair_list), _ptr(sim))
+        self._check(rc, "roman_session_stacked_sim_list")
+        return sim
+
+    def session_stacked_sim_list_dev(self, d, Nf, desc_ptr, mask_ptr, frame_lo, frame_n, mask_off, sub_off, blocks, pair_off, pair_list,
+                                     frame_lo_ptr, frame_n_ptr, mask_off_ptr, sub_off_ptr, blocks_ptr, pair_off_ptr, list_ptr, sim_ptr):
+        """Device-pointer stacked similarity of a list of pairs (roman_session_stacked_sim_list_dev): session_stacked_sim_dev()'s
+        arguments with the list as a host array (validated) AND as a device address, as session_gate_list_dev takes it.  Writes
+        the listed pairs' entries of the DENSE array at sim_ptr and nothing else.  A pure enqueue on the context's stream:
+        session_gate_list_dev(..., sim_in_ptr=sim_ptr) behind it reads what it wrote."""
+        frame_lo, frame_n, mask_off, sub_off, blocks, pair_off, R, nb = self._session_stacked_tables(frame_lo, frame_n, mask_off, sub_off, blocks, pair_off)
+        pair_list = np.ascontiguousarray(pair_list, dtype=np.int32).reshape(-1, 3)
+        rc = self._lib.roman_session_stacked_sim_list_dev(self._h, int(d), int(Nf), _vp(desc_ptr), _vp(mask_ptr), R, _vp(frame_lo_ptr), _ptr(frame_lo),
+                                                          _vp(frame_n_ptr), _ptr(frame_n), _vp(mask_off_ptr), _ptr(mask_off), _vp(sub_off_ptr), _ptr(sub_off),
+                                                          nb, _vp(blocks_ptr), _ptr(blocks), _vp(pair_off_ptr), _ptr(pair_off), len(pair_list), _vp(list_ptr),
+                                                          _ptr(pair_list), _vp(sim_ptr))
+        self._check(rc, "roman_session_stacked_sim_list_dev")
+
     # ------------------------------------------------------------------ force-fill submaps, boxes, the bounding-box gate (DESIGN.md §4.12)
     def submaps_fill(self, point_dim, cap, seg_feats, descs, count, src, seg_ids=None, desc_dim=0, want_pool=True):
         """Host-pointer gather of force-fill submaps (roman_submaps_fill, [REF roman/map/map.py:264-295]): `src` (S, cap) holds the
