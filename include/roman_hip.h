@@ -980,6 +980,61 @@ ROMAN_API int roman_frame_select(roman_ctx_t* ctx, const roman_frame_select_para
                                  int32_t Nf, const double* frame_times, const double* frame_pos, int32_t d, const double* frame_desc,
                                  uint64_t* mask, int32_t* n_sel, double* span, double* mean);
 
+/* One robot of a session whose frame tables stay in HBM (roman_session_frame_select_list*): its ranges of the session's tensors. */
+typedef struct roman_session_frame_robot {
+    int64_t seg0;            /* first row of its segment table in seg_times                                                        */
+    int64_t mask_off;        /* word offset of its first mask row in `mask`                                                        */
+    int32_t n_seg;           /* rows of its segment table (src holds indices < n_seg, local to the robot)                          */
+    int32_t sub0;            /* its first global slot                                                                              */
+    int32_t n_sub;           /* its slots: [sub0, sub0 + n_sub)                                                                    */
+    int32_t frame0;          /* its first frame in frame_times / frame_pos / frame_desc                                            */
+    int32_t n_frames;        /* Nf_r                                                                                               */
+    int32_t mask_words;      /* words per mask row, a CAPACITY: >= ceil(Nf_r / 64)                                                 */
+    int32_t reserved[2];     /* must be 0                                                                                          */
+} roman_session_frame_robot_t;
+
+/*
+ * roman_session_frame_select_list_dev: roman_frame_select_dev [REF roman/map/map.py:210-242] for the L LISTED slots
+ * of a session that grows, IN PLACE in outputs that stay in HBM between steps, with a report of which slots changed.  Bulk pointers
+ * DEVICE; `robots` and `list` HOST (the library stages them); a PURE ENQUEUE on the context's stream.
+ *   robots     roman_session_frame_robot_t[R]: segment rows, slots, frames and mask rows of every robot; each kind of range
+ *              ascending and disjoint over the robots (robot r + 1 starts at or behind the end of robot r)
+ *   count      int32[S], src int32[S*cap], by GLOBAL slot, as roman_session_submaps[_list]_dev wrote them (src local to the robot)
+ *   seg_times  float64[..][2], frame_times float64[..], frame_pos float64[..][3] (thin), frame_desc float64[..][d] (want_mean): the
+ *              session's tables, robot r's rows at seg0 / frame0
+ *   L, list    int32[L] global slots, strictly ascending, each inside a robot's [sub0, sub0 + n_sub)
+ * Per LISTED slot g of robot r the rule is roman_frame_select_dev's, over that robot's segment rows and its Nf_r frames [REF
+ * roman/map/map.py:210-242]: span, candidates (lo <= t <= hi), thinning in ascending index with sqrt((dx^2 + dy^2) + dz^2) and no
+ * fused multiply-adds, the mean in ascending frame index — the same per-submap code, bit for bit.
+ *   mask       uint64: row of slot g at mask_off_r + (g - sub0_r) * mask_words_r; ALL mask_words_r words of a listed row are written,
+ *              zero beyond the frames
+ *   n_sel      int32[S], span float64[S][2], mean float64[S][d] (want_mean), by global slot
+ *   changed    int32[L]: 1 when a mask word, n_sel or (want_mean) 64 bits of a mean column — NaN by its bits — of slot list[l]
+ *              differs from what the slot held when the call began, else 0; always written
+ * UNLISTED slots: not one byte is written.  L == 0, R == 0 and Nf_r == 0 are legal.
+ * Errors, in this order, judged on host memory before the context: what roman_frame_select_dev refuses of fparams, cap and d
+ * (fparams NULL, d < 0, cap < 1, reserved words, thin_dist, want_mean with d < 1); R < 0, robots NULL with R > 0; per robot a
+ * reserved word not 0, a negative size or offset, mask_words_r < ceil(Nf_r / 64), ranges not ascending and disjoint; L < 0, list NULL
+ * with L > 0, an entry outside every robot's slots, a list not strictly ascending -> ROMAN_E_INVALID; slots * cap beyond the index
+ * width -> ROMAN_E_TOO_LARGE; then (L > 0) a NULL pointer that is needed -> ROMAN_E_INVALID; then the context.
+ */
+ROMAN_API int roman_session_frame_select_list_dev(roman_ctx_t* ctx, const roman_frame_select_params_t* fparams, int32_t R,
+                                                  const roman_session_frame_robot_t* robots, int32_t cap,
+                                                  const int32_t* count, const int32_t* src, const double* seg_times,
+                                                  const double* frame_times, const double* frame_pos, int32_t d, const double* frame_desc,
+                                                  int32_t L, const int32_t* list,
+                                                  uint64_t* mask, int32_t* n_sel, double* span, double* mean, int32_t* changed);
+
+/* The same with HOST pointers everywhere.  Synchronous: the tables go up over the extent the robots' ranges span, the caller's CURRENT
+   mask, n_sel, span and mean go up too (`changed` compares with them, and an unlisted slot comes back as it was),
+   roman_session_frame_select_list_dev runs, and mask, n_sel, span, mean and changed come back. */
+ROMAN_API int roman_session_frame_select_list(roman_ctx_t* ctx, const roman_frame_select_params_t* fparams, int32_t R,
+                                              const roman_session_frame_robot_t* robots, int32_t cap,
+                                              const int32_t* count, const int32_t* src, const double* seg_times,
+                                              const double* frame_times, const double* frame_pos, int32_t d, const double* frame_desc,
+                                              int32_t L, const int32_t* list,
+                                              uint64_t* mask, int32_t* n_sel, double* span, double* mean, int32_t* changed);
+
 /*
  * roman_stacked_sim_dev: Submap.similarity for 2-D (stacked) descriptors [REF roman/map/map.py:155-162] for every pair of an
  * S0 x S1 grid, from the two maps' frame tables and the masks roman_frame_select_dev wrote.  Every pointer DEVICE; a PURE ENQUEUE

@@ -255,6 +255,21 @@ class RomanFrameSelectParams(C.Structure):
     ]
 
 
+class RomanSessionFrameRobot(C.Structure):
+    """roman_session_frame_robot_t"""
+    _fields_ = [
+        ("seg0", C.c_int64),
+        ("mask_off", C.c_int64),
+        ("n_seg", C.c_int32),
+        ("sub0", C.c_int32),
+        ("n_sub", C.c_int32),
+        ("frame0", C.c_int32),
+        ("n_frames", C.c_int32),
+        ("mask_words", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
 # flag bits of roman_grid_gate's flags[]
 ROMAN_GRID_NEARBY = 1
 ROMAN_GRID_SKIP = 2
@@ -273,6 +288,7 @@ SUBMAP_PARAMS_NBYTES = C.sizeof(RomanSubmapParams)
 SUBMAP_DESC_NBYTES = C.sizeof(RomanSubmapDesc)
 GRID_GATE_PARAMS_NBYTES = C.sizeof(RomanGridGateParams)
 FRAME_SELECT_PARAMS_NBYTES = C.sizeof(RomanFrameSelectParams)
+SESSION_FRAME_ROBOT_NBYTES = C.sizeof(RomanSessionFrameRobot)
 STACKED_BAND_MIN = 32       # the smallest row band of roman_stacked_sim* (kernels.hip.h STACK_TILE)
 LC_PARAMS_NBYTES = C.sizeof(RomanLcParams)
 LC_RECORD_NBYTES = C.sizeof(RomanLcRecord)
@@ -384,6 +400,8 @@ def load_library():
         "roman_session_gate_list": (C.c_int, [ctxp, P(RomanGridGateParams), i32] + [vp] * 7 + [i32] + [vp] * 2 + [i32] + [vp] * 12),
         "roman_frame_select_dev": (C.c_int, [ctxp, P(RomanFrameSelectParams), i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
         "roman_frame_select": (C.c_int, [ctxp, P(RomanFrameSelectParams), i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "roman_session_frame_select_list_dev": (C.c_int, [ctxp, P(RomanFrameSelectParams), i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32] + [vp] * 6),
+        "roman_session_frame_select_list": (C.c_int, [ctxp, P(RomanFrameSelectParams), i32, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32] + [vp] * 6),
         "roman_stacked_sim_dev": (C.c_int, [ctxp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
         "roman_stacked_sim": (C.c_int, [ctxp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
         "roman_ctx_set_stacked_band": (C.c_int, [ctxp, i32]),
@@ -421,7 +439,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_shared_reduce_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_mno_lc_tail_dev", "roman_mno_lc_batch_dev", "roman_mno_lc_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ransac_lc_batch_dev", "roman_ransac_lc_batch", "roman_submaps_dev", "roman_submaps", "roman_session_submaps_dev", "roman_session_submaps", "roman_session_submaps_list_dev", "roman_session_submaps_list", "roman_grid_gate_dev", "roman_grid_gate", "roman_grid_gate_sim_dev", "roman_grid_gate_sim", "roman_submaps_fill_dev", "roman_submaps_fill", "roman_submap_boxes_dev", "roman_submap_boxes", "roman_grid_gate_aabb_dev", "roman_grid_gate_aabb", "roman_session_gate_dev", "roman_session_gate", "roman_session_gate_sim_dev", "roman_session_gate_sim", "roman_session_stacked_sim_dev", "roman_session_stacked_sim", "roman_session_stacked_sim_list_dev", "roman_session_stacked_sim_list", "roman_session_boxes_dev", "roman_session_boxes", "roman_session_gate_aabb_dev", "roman_session_gate_aabb", "roman_session_gate_list_dev", "roman_session_gate_list", "roman_frame_select_dev", "roman_frame_select", "roman_stacked_sim_dev", "roman_stacked_sim", "roman_ctx_set_stacked_band", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_shared_reduce_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_mno_lc_tail_dev", "roman_mno_lc_batch_dev", "roman_mno_lc_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ransac_lc_batch_dev", "roman_ransac_lc_batch", "roman_submaps_dev", "roman_submaps", "roman_session_submaps_dev", "roman_session_submaps", "roman_session_submaps_list_dev", "roman_session_submaps_list", "roman_grid_gate_dev", "roman_grid_gate", "roman_grid_gate_sim_dev", "roman_grid_gate_sim", "roman_submaps_fill_dev", "roman_submaps_fill", "roman_submap_boxes_dev", "roman_submap_boxes", "roman_grid_gate_aabb_dev", "roman_grid_gate_aabb", "roman_session_gate_dev", "roman_session_gate", "roman_session_gate_sim_dev", "roman_session_gate_sim", "roman_session_stacked_sim_dev", "roman_session_stacked_sim", "roman_session_stacked_sim_list_dev", "roman_session_stacked_sim_list", "roman_session_boxes_dev", "roman_session_boxes", "roman_session_gate_aabb_dev", "roman_session_gate_aabb", "roman_session_gate_list_dev", "roman_session_gate_list", "roman_frame_select_dev", "roman_frame_select", "roman_session_frame_select_list_dev", "roman_session_frame_select_list", "roman_stacked_sim_dev", "roman_stacked_sim", "roman_ctx_set_stacked_band", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

@@ -1253,7 +1253,9 @@ def _session_uploads(torch, s, views, sub_off, blk, pair_off):
                         FRh=cat(lambda hs: hs["frames"][1], (16,)), rows_of=rows_of, t=t)
     if s.stacked:
         live_f = sorted(rows_of)
-        u.fdesc = p[live_f[0]].frame_desc_dev if len(live_f) == 1 else torch.cat([p[r].frame_desc_dev for r in live_f], dim=0)
+        u.fdesc = _one_storage(torch, [p[r].frame_desc_dev for r in live_f])       # (grow_session_pools' frame tables are row ranges of one storage, §4.23)
+        if u.fdesc is None:
+            u.fdesc = p[live_f[0]].frame_desc_dev if len(live_f) == 1 else torch.cat([p[r].frame_desc_dev for r in live_f], dim=0)
         u.fmask = torch.cat([p[r].frame_mask[rows_of[r]].reshape(-1) for r in live_f]).contiguous()
         nfr = {r: int(p[r].frame_desc_dev.shape[0]) for r in live_f}
         flo = dict(zip(live_f, np.concatenate([[0], np.cumsum([nfr[r] for r in live_f])]).astype(np.int64).tolist()))

@@ -23,7 +23,7 @@ from typing import List, Optional
 import numpy as np
 
 from .. import _abi
-from ..runtime import frame_select_params, mask_indices, submap_desc_dtype
+from ..runtime import frame_select_params, mask_indices, session_frame_robots, submap_desc_dtype
 from .batch import AlignmentBatch
 from .ransac_reg import RansacReg
 from .submap_align import Submap, transform_rm_roll_pitch
@@ -446,7 +446,7 @@ def _session_pool_views(tables, centers, frames, params, P, sub_off, d, framed, 
         lo, hi = int(sub_off[r]), int(sub_off[r + 1])
         extra = {}
         if framed:
-            n_h = ft[r]["n"].cpu().numpy()[:hi - lo].copy()
+            n_h = (ft[r]["n_h"] if "n_h" in ft[r] else ft[r]["n"].cpu().numpy())[:hi - lo].copy()
             bad = np.nonzero((count_h[lo:hi] > 0) & (n_h == 0))[0]
             if len(bad):
                 raise ValueError(f"submap {int(bad[0])} holds {int(count_h[lo + bad[0]])} segments but no frame of the map lies in its time span: "
@@ -547,12 +547,18 @@ GROWTH = 1.5                     # capacity of the session's tensors over the ne
 _SESSION_TENSORS = dict(feats=(1, 'seg', 0.0), times=(1, 'seg', 0.0), ids=(1, 'seg', 0),
                         pool=('cap', 'sub', 0.0), src=('cap', 'sub', -1), ids_out=('cap', 'sub', -1), count=(1, 'sub', 0), status=(1, 'sub', 0),
                         desc=(1, 'sub', float("nan")))
+# ... and of the frame-descriptor modes over a context that selects by list: unit 'frm' frames.  The mask words are
+# held apart (`_moved_mask`): a robot's range there is its submaps times its own word capacity
+_SESSION_FRAME_TENSORS = dict(f_times=(1, 'frm', 0.0), f_pos=(1, 'frm', 0.0), f_desc=(1, 'frm', 0.0), f_n=(1, 'sub', 0), f_span=(1, 'sub', 0.0))
 
 
 class SessionPoolsState:
     """What grow_session_pools keeps between two steps of one session: the device tensors of the tables (feats, times, ids) and of
     the outputs (pool, src, ids_out, count, status, desc) — each with room beyond the need, every robot's range next to the one in
-    front of it —, per robot the rows and submaps it held and its centre records as bytes, and `src` / `count` on the host."""
+    front of it —, per robot the rows and submaps it held and its centre records as bytes, and `src` / `count` on the host.  In the
+    frame-descriptor modes over a context with session_frame_select_list_dev also the session's frame tensors —
+    f_times, f_pos, f_desc by frame, f_n and f_span by submap, f_mask in rows of a per-robot word capacity —, per robot its frames
+    and that capacity, and `span` on the host."""
 
     def __init__(self):
         self.key = None              # robots, cap, row layout, submap_descriptor: a state serves ONE session
@@ -563,8 +569,14 @@ class SessionPoolsState:
         self.count_h = None          # (S,) int32 and (S, cap) int32 over the whole session, as read back last
         self.src_h = None
         self.frame = None            # the frame-descriptor modes, per robot: dict(mask, n, mean) device tensors of the last call
+        self.n_frames = None         # §4.23, per robot: frames of its table, and the words a mask row of it has room for
+        self.mask_words = None
+        self.span_h = None           # (S, 2) float64 over the whole session, as read back last
+        self.frames_uploaded = 0     # frames the last call uploaded, and slots it listed for the frame selection (of `total`)
+        self.frames_listed = 0
         self.listed = 0              # submaps the last call rebuilt, of `total`
         self.total = 0
+        self.unfinished = False      # a call moved the session's tensors and raised before it recorded the new layout: the state serves no further call
         self.seconds = {}            # the last call's wall time by part: 'upload' (host rules, moves and table rows), 'device' (the call to its
                                      # synchronisation), 'readback'
 
@@ -584,7 +596,80 @@ def _moved(torch, t, old_off, old_len, new_off, total, per, fill):
     return t
 
 
-def grow_session_pools(state, registration, tables, centers, params, ctx=None, device=None, cap=None, frames=None, changed_rows=None, rebuild=None):
+def _grow_frames(torch, dev, state, frames, frames_changed, first, listed, n_rows, n_sub, old_sub, n_frames, sub_off, old_sub_off):
+    """The frame half of a growing step before its device call: the frame list — every rule is a necessary
+    condition for a slot's selection to change —, the session's frame tensors moved and grown, the appended frames uploaded
+    -> (per robot the views _session_pool_views reads, the list, the robots' records, the cleared `changed` of the list, the mask
+    word capacities, the frames uploaded).  The caller records n_frames, mask_words, frames_uploaded and span_h in the state with
+    the rest of the new layout, when the call has ended."""
+    R, t = len(frames), state.t
+    d = int(frames[0].desc.shape[1])
+    if any(int(f.desc.shape[1]) != d for f in frames):
+        raise ValueError("the robots' frame descriptors differ in length")
+    fresh = state.n_frames is None                                           # no frame tensor yet (a first call, or the steps so far ran without the entry)
+    old_nf, old_mw = ([0] * R, [0] * R) if fresh else (state.n_frames, state.mask_words)
+    whole = [fresh or frames_changed[r] for r in range(R)]
+    flagged = []
+    for r in range(R):
+        flag = listed[r].copy()                                              # a rebuilt slot: its rows, so its span, may differ
+        k = 0 if first else old_sub[r]
+        if whole[r]:
+            flag[:] = True
+        elif k and n_frames[r] > old_nf[r]:                                  # an old slot gains a candidate only when an appended frame's time lies in its span
+            ta = np.asarray(frames[r].times, dtype=np.float64).reshape(-1)[old_nf[r]:]
+            sp = state.span_h[int(old_sub_off[r]):int(old_sub_off[r]) + k]
+            flag[:k] |= ((ta[None, :] >= sp[:, :1]) & (ta[None, :] <= sp[:, 1:])).any(axis=1)
+        flagged.append(flag)
+    flst = np.concatenate([int(sub_off[r]) + np.nonzero(f)[0] for r, f in enumerate(flagged)]).astype(np.int32)
+    # capacity: the frame tensors as the session's other tensors; a mask row's words grow when ceil(Nf_r / 64) exceeds them
+    words = [(n + 63) // 64 for n in n_frames]
+    mw = [m if w <= m else int(np.ceil(w * GROWTH)) for w, m in zip(words, old_mw)]
+    off = lambda n: [int(x) for x in np.concatenate([[0], np.cumsum(n)])]
+    frame_off, old_frame_off = off(n_frames), off(old_nf)
+    k_old = [0] * R if (first or fresh) else list(old_sub)
+    mask_off, old_mask_off = off([k * w for k, w in zip(n_sub, mw)]), off([k * w for k, w in zip(k_old, old_mw)])
+    S, NF = int(sub_off[-1]), frame_off[-1]
+    shapes = dict(f_times=((), torch.float64), f_pos=((3,), torch.float64), f_desc=((d,), torch.float64), f_n=((), torch.int32), f_span=((2,), torch.float64))
+    for name, (per, unit, fill) in _SESSION_FRAME_TENSORS.items():
+        if fresh:
+            t[name] = torch.full((0,) + shapes[name][0], fill, dtype=shapes[name][1], device=dev)
+        o_off, n_off, o_len, total = (old_frame_off, frame_off, old_nf, max(NF, 1)) if unit == 'frm' else ([int(x) for x in old_sub_off], [int(x) for x in sub_off], k_old, max(S, 1))
+        t[name] = _moved(torch, t[name], o_off[:-1], o_len, n_off[:-1], total, per, fill)
+    if fresh:
+        t["f_mask"] = torch.zeros((0,), dtype=torch.int64, device=dev)
+    t["f_mask"] = _moved_mask(torch, t["f_mask"], old_mask_off[:-1], k_old, old_mw, mask_off[:-1], mw, max(mask_off[-1], 1))
+    uploaded = 0
+    for r, fr in enumerate(frames):
+        a = 0 if whole[r] else old_nf[r]
+        if n_frames[r] > a:
+            lo = frame_off[r]
+            for name, arr in (("f_times", fr.times.reshape(-1)), ("f_pos", fr.pos.reshape(-1, 3)), ("f_desc", fr.desc.reshape(n_frames[r], -1))):
+                t[name][lo + a:lo + n_frames[r]].copy_(torch.from_numpy(np.ascontiguousarray(arr[a:], dtype=np.float64)))
+            uploaded += n_frames[r] - a
+    ft = []
+    for r in range(R):
+        lo, hi = int(sub_off[r]), int(sub_off[r + 1])
+        ft.append(dict(W=words[r], n=t["f_n"][lo:hi], mask=t["f_mask"][mask_off[r]:mask_off[r + 1]].view(hi - lo, mw[r]),
+                       desc=t["f_desc"][frame_off[r]:frame_off[r + 1]]))
+    robots = session_frame_robots(n_rows, n_sub, n_frames, mw)
+    return ft, flst, robots, torch.zeros(max(len(flst), 1), dtype=torch.int32, device=dev), mw, uploaded
+
+
+def _moved_mask(torch, t, old_off, old_sub, old_words, new_off, new_words, total):
+    """The mask words `t` with robot r's old_sub[r] rows of old_words[r] words moved from word old_off[r] to new_off[r] and laid out
+    in rows of new_words[r] >= old_words[r] words: `_moved` while every robot keeps its row length; else into a tensor GROWTH times
+    the need, old rows copied to the new stride on the device, new words zero."""
+    if list(old_words) == list(new_words):
+        return _moved(torch, t, old_off, [k * w for k, w in zip(old_sub, old_words)], new_off, total, 1, 0)
+    new = torch.zeros((max(int(total * GROWTH), 1),), dtype=t.dtype, device=t.device)
+    for o, n, k, wo, wn in zip(old_off, new_off, old_sub, old_words, new_words):
+        if k and wo:
+            new[n:n + k * wn].view(k, wn)[:, :wo].copy_(t[o:o + k * wo].view(k, wo))
+    return new
+
+
+def grow_session_pools(state, registration, tables, centers, params, ctx=None, device=None, cap=None, frames=None, changed_rows=None, rebuild=None,
+                       frames_changed=None):
     """build_session_pools for a session that GROWS -> (pools, touched, state).  `state` (a SessionPoolsState, or
     None before the first call) keeps the session's tables and pools in HBM; a call uploads only the appended and the rewritten
     table rows, rebuilds only the submaps that are new or can have changed — ONE roman_session_submaps_list_dev call, one
@@ -601,8 +686,20 @@ def grow_session_pools(state, registration, tables, centers, params, ctx=None, d
     every old submap s of robot r for which an appended or named row k was a member (k in src[s, :count[s]]) or passes the time window
     with its new times, NOT (first_seen > t_hi[s] OR last_seen < t_lo[s]); and whatever rebuild[r] names (rebuild='all': everything).
 
+    The frame-descriptor modes over a context with session_frame_select_list_dev: the frame tables stay in HBM
+    too.  A frame table may only grow by APPENDED frames (found from the lengths; only they go up) unless frames_changed[r] (one
+    bool per robot, default none) says that robot r's table was rewritten: it goes up whole and all its submaps are reselected.
+    ONE session_frame_select_list_dev call behind the rebuild reselects the rebuilt submaps, every old one whose recorded span
+    holds an appended frame's time, and those of a frames_changed robot; `touched` is the union of what the two calls report as
+    changed.  pool.frame_mask and pool.frame_desc_dev are strided views of the session's tensors.  state.frames_uploaded and
+    state.frames_listed count what the call moved and reselected.  A context without that entry reselects per robot as
+    build_session_pools does.
+
     ValueError before a context is made: whatever build_session_pools refuses (the force-fill mode included); a robot count, cap,
-    row layout or submap_descriptor other than the state's; a table or centre list that shrank; changed_rows out of range."""
+    row layout or submap_descriptor other than the state's; a table, centre list or frame table that shrank; changed_rows out of
+    range; a frames_changed that does not hold one entry per robot; a state whose last call raised after it had begun to move the
+    session's tensors (state.unfinished: the new layout is recorded in one place, at the end of a call).  ValueError with the
+    context, before anything moves: a state with resident frame tables and a context without session_frame_select_list_dev."""
     import time
     import torch
     marks = [time.perf_counter()]
@@ -611,6 +708,9 @@ def grow_session_pools(state, registration, tables, centers, params, ctx=None, d
     state = SessionPoolsState() if state is None else state
     layout = None if R == 0 else (int(tables[0].feats.shape[1]), int(tables[0].point_dim), int(tables[0].desc_dim), tables[0].invariant)
     key = (R, None if P is None else int(P.cap), layout, params.submap_descriptor, int(d))
+    if state.unfinished:
+        raise ValueError("the state's last call raised after it had begun to move the session's tensors: they no longer match what the "
+                         "state records, begin again with a new state")
     if state.key is not None and state.key != key:
         raise ValueError("the state was made for another robot count, cap, row layout or submap_descriptor: a SessionPoolsState serves one session")
     first = state.key is None
@@ -632,6 +732,12 @@ def grow_session_pools(state, registration, tables, centers, params, ctx=None, d
         if len(rebuild) != R or any(x is not None and len(np.asarray(x).reshape(-1)) and
                                     (np.min(x) < 0 or np.max(x) >= n) for x, n in zip(rebuild, n_sub)):
             raise ValueError("rebuild must be None, 'all', or one entry per robot, each None or submap indices of that robot")
+    frames_changed = [False] * R if frames_changed is None else [bool(x) for x in frames_changed]
+    if len(frames_changed) != R:
+        raise ValueError("frames_changed must hold one bool per table")
+    n_frames = [len(f) for f in frames] if framed else [0] * R
+    if framed and state.n_frames is not None and any(n < m for n, m in zip(n_frames, state.n_frames)):
+        raise ValueError("a frame table shrank: between two calls frames may only be appended")
     if R == 0:
         return [], [], state
 
@@ -640,7 +746,7 @@ def grow_session_pools(state, registration, tables, centers, params, ctx=None, d
     sub_off = np.concatenate([[0], np.cumsum(n_sub)]).astype(np.int32)
     old_seg_off, old_sub_off = np.concatenate([[0], np.cumsum(old_rows)]).astype(np.int64), np.concatenate([[0], np.cumsum(old_sub)]).astype(np.int64)
     descs_r = [c.descs() for c in centers]
-    desc_bytes = [np.ascontiguousarray(x).view(np.uint8).reshape(len(x), -1).copy() for x in descs_r]
+    desc_bytes = [np.ascontiguousarray(x).view(np.uint8).reshape(len(x), x.dtype.itemsize).copy() for x in descs_r]       # (a robot without submaps: (0, bytes))
     listed = []
     for r in range(R):
         flag = np.zeros(n_sub[r], dtype=bool)
@@ -670,6 +776,11 @@ def grow_session_pools(state, registration, tables, centers, params, ctx=None, d
     ctx = ctx or registration._context()
     dev = torch.device(device if device is not None else f"cuda:{getattr(ctx, 'device', 0)}")
     on_host = dev.type == "cpu"                                              # CPU tensors + a stand-in context (tests)
+    resident = framed and hasattr(ctx, "session_frame_select_list_dev")     # the frame tables stay in HBM too
+    if framed and not resident and state.n_frames is not None:
+        raise ValueError("the state keeps the session's frame tables on the device (DESIGN.md §4.23) and this context has no "
+                         "session_frame_select_list_dev: a session stays with the kind of context it began with")
+    state.unfinished = True                                                  # from here the session's tensors move; cleared when the new layout is recorded
     F, capn = layout[0], int(P.cap)
     Fo, S, N = P.point_dim + F - 3, int(sub_off[-1]), int(seg_off[-1])
     shapes = dict(feats=((F,), torch.float64), times=((2,), torch.float64), ids=((), torch.int64), pool=((Fo,), torch.float64), src=((), torch.int32),
@@ -692,8 +803,11 @@ def grow_session_pools(state, registration, tables, centers, params, ctx=None, d
             if len(named[r]):
                 t[name][torch.from_numpy(named[r] + lo).to(dev)] = torch.from_numpy(np.ascontiguousarray(a[named[r]], dtype=dt)).to(dev)
     changed = torch.zeros(max(len(lst), 1), dtype=torch.int32, device=dev)
-    ft, before = [], None
-    if framed:
+    ft, before, flst = [], None, lst
+    if resident:
+        ft, flst, robots, fchanged, mask_words, uploaded = _grow_frames(torch, dev, state, frames, frames_changed, first, listed, n_rows, n_sub, old_sub, n_frames, sub_off,
+                                                  old_sub_off)
+    elif framed:
         ft = _frame_tensors(torch, dev, frames, centers)
         before = [None if first or not old_sub[r] else dict(state.frame[r], mean=t["desc"][int(sub_off[r]):int(sub_off[r]) + old_sub[r]].clone())
                   for r in range(R)]
@@ -707,7 +821,13 @@ def grow_session_pools(state, registration, tables, centers, params, ctx=None, d
                                  t["src"].data_ptr(), t["status"].data_ptr(), seg_ids_ptr=t["ids"].data_ptr(), ids_out_ptr=t["ids_out"].data_ptr() if N else None,
                                  desc_dim=0 if framed else d, desc_out_ptr=t["desc"].data_ptr() if d and not framed else None,
                                  changed_ptr=changed.data_ptr())
-    if framed:                                                               # behind it on the same stream, over every submap of a robot as in build_session_pools
+    if resident:                                                             # ONE call behind it on the same stream: it reads the count and src of the slots just rebuilt
+        thin = params.frame_descriptor_dist if params.submap_descriptor == 'stacked_frame_descriptors' else None      # [REF roman/map/map.py:216-226]
+        ctx.session_frame_select_list_dev(frame_select_params(thin, mean_frames), robots, capn, t["count"].data_ptr(), t["src"].data_ptr(), t["times"].data_ptr(),
+                                          t["f_times"].data_ptr(), flst, t["f_mask"].data_ptr(), t["f_n"].data_ptr(), t["f_span"].data_ptr(), fchanged.data_ptr(),
+                                          frame_pos_ptr=t["f_pos"].data_ptr(), d=int(t["f_desc"].shape[1]), frame_desc_ptr=t["f_desc"].data_ptr(),
+                                          mean_ptr=t["desc"].data_ptr() if mean_frames else None)
+    elif framed:                                                             # behind it on the same stream, over every submap of a robot as in build_session_pools
         _frame_select_robots(ctx, params, P, tables, frames, seg_off, sub_off, mean_frames, t["count"], t["src"], t["times"], t["desc"], ft)
     ctx.sync()
     marks.append(time.perf_counter())
@@ -718,13 +838,18 @@ def grow_session_pools(state, registration, tables, centers, params, ctx=None, d
     src_h, ids_h = t["src"].cpu().numpy()[:rows].reshape(S, capn).copy(), t["ids_out"].cpu().numpy()[:rows].reshape(S, capn).copy()
     desc_h = t["desc"].cpu().numpy()[:S, :d] if d else None
     changed_h = changed.cpu().numpy()[:len(lst)]
+    differs_h = np.zeros(S, dtype=bool)                                      # by global slot: what the device reports as changed
+    differs_h[lst[changed_h != 0]] = True
+    if resident:
+        differs_h[flst[fchanged.cpu().numpy()[:len(flst)] != 0]] = True
+        span_h, fn_h = t["f_span"][:S].cpu().numpy(), t["f_n"][:S].cpu().numpy()
+        for r in range(R):                                                   # (read back once, sliced on the host)
+            ft[r]["n_h"] = fn_h[int(sub_off[r]):int(sub_off[r + 1])]
     touched = []
     for r in range(R):
-        flag = np.zeros(n_sub[r], dtype=bool)
+        flag = differs_h[int(sub_off[r]):int(sub_off[r + 1])].copy()
         flag[old_sub[r]:] = True
-        mine = (lst >= sub_off[r]) & (lst < sub_off[r + 1])
-        flag[lst[mine][changed_h[mine] != 0] - int(sub_off[r])] = True
-        if framed and before[r] is not None:                                 # what frame_select_dev left for the old submaps against the last call's, on the device
+        if before is not None and before[r] is not None:                                 # what frame_select_dev left for the old submaps against the last call's, on the device
             k, f, b = old_sub[r], ft[r], before[r]
             W = max(int(f["mask"].shape[1]), int(b["mask"].shape[1]))
             wide = lambda m: torch.nn.functional.pad(m[:k], (0, W - int(m.shape[1])))
@@ -738,8 +863,12 @@ def grow_session_pools(state, registration, tables, centers, params, ctx=None, d
                                 desc_h, ft)
     state.key, state.n_rows, state.n_sub, state.descs = key, n_rows, n_sub, desc_bytes
     state.count_h, state.src_h = count_h, src_h
-    state.frame = [dict(mask=f["mask"], n=f["n"]) for f in ft] if framed else None
+    state.frame = [dict(mask=f["mask"], n=f["n"]) for f in ft] if framed and not resident else None
     state.listed, state.total = int(len(lst)), S
+    state.frames_listed = int(len(flst)) if resident else (S if framed else 0)
+    if resident:
+        state.n_frames, state.mask_words, state.frames_uploaded, state.span_h = list(n_frames), mask_words, uploaded, span_h
+    state.unfinished = False
     marks.append(time.perf_counter())
     state.seconds = dict(upload=marks[1] - marks[0], device=marks[2] - marks[1], readback=marks[3] - marks[2])
     return pools, touched, state

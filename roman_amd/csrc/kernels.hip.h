@@ -8330,25 +8330,27 @@ __device__ __forceinline__ double wave_max_all(double v)
     return v;
 }
 
-__global__ void __launch_bounds__(256) k_frame_select(roman_frame_select_params_t P, int S, int cap, const int32_t* __restrict__ count,
-                                                      const int32_t* __restrict__ src, int N, const double* __restrict__ seg_times,
-                                                      int Nf, const double* __restrict__ frame_times, const double* __restrict__ frame_pos,
-                                                      unsigned long long* __restrict__ mask, int32_t* __restrict__ n_sel, double* __restrict__ span)
+// One submap's selection by ONE WAVE — what a wave of k_frame_select and of k_session_frame_select_list does once it knows its submap:
+// n rows of `src` (indices into the N rows of seg_times), the Nf frames, and `words` mask words at `mask` (words >= ceil(Nf / 64):
+// whatever lies beyond the frames is written as zero).  CMP: lane 0 compares every word and the count with what the slot held
+// before it stores them -> whether one differs (lane 0's value; false without CMP).
+template <bool CMP>
+__device__ __forceinline__ bool frame_select_submap(const roman_frame_select_params_t& P, int lane, int n, const int32_t* __restrict__ src, int N,
+                                                    const double* __restrict__ seg_times, int Nf, const double* __restrict__ frame_times,
+                                                    const double* __restrict__ frame_pos, int words, unsigned long long* __restrict__ mask,
+                                                    int32_t* __restrict__ n_sel, double* __restrict__ span)
 {
-    const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= S) return;                                          // (wave-uniform)
-    const int n = min(count[s], cap), W = (Nf + 63) >> 6;
     double lo = INFINITY, hi = -INFINITY;
     for (int r = lane; r < n; r += 64) {
-        const int64_t k = src[(int64_t)s * cap + r];
+        const int64_t k = src[r];
         if (k < 0 || k >= N) continue;                           // (not what roman_submaps_dev writes: never read out of the table)
         lo = fmin(lo, seg_times[2 * k]); hi = fmax(hi, seg_times[2 * k + 1]);
     }
     lo = wave_min_all(lo); hi = wave_max_all(hi);
     double lx = 0.0, ly = 0.0, lz = 0.0;                         // the last selected candidate (uniform)
-    bool have = false;
+    bool have = false, differs = false;
     int total = 0;
-    for (int w = 0; w < W; ++w) {
+    for (int w = 0; w < words; ++w) {
         const int f = 64 * w + lane;
         bool cand = false;
         double px = 0.0, py = 0.0, pz = 0.0;
@@ -8372,10 +8374,84 @@ __global__ void __launch_bounds__(256) k_frame_select(roman_frame_select_params_
                 if (take) { sel |= 1ull << t; lx = x; ly = y; lz = z; have = true; }
             }
         }
-        if (lane == 0) mask[(int64_t)s * W + w] = sel;
+        if (lane == 0) {
+            if (CMP) differs |= mask[w] != sel;
+            mask[w] = sel;
+        }
         total += __popcll(sel);
     }
-    if (lane == 0) { n_sel[s] = total; span[2 * (int64_t)s] = lo; span[2 * (int64_t)s + 1] = hi; }
+    if (lane == 0) {
+        if (CMP) differs |= *n_sel != total;
+        *n_sel = total; span[0] = lo; span[1] = hi;
+    }
+    return differs;
+}
+
+__global__ void __launch_bounds__(256) k_frame_select(roman_frame_select_params_t P, int S, int cap, const int32_t* __restrict__ count,
+                                                      const int32_t* __restrict__ src, int N, const double* __restrict__ seg_times,
+                                                      int Nf, const double* __restrict__ frame_times, const double* __restrict__ frame_pos,
+                                                      unsigned long long* __restrict__ mask, int32_t* __restrict__ n_sel, double* __restrict__ span)
+{
+    const int lane = threadIdx.x & 63, s = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (s >= S) return;                                          // (wave-uniform)
+    const int W = (Nf + 63) >> 6;
+    frame_select_submap<false>(P, lane, min(count[s], cap), src + (int64_t)s * cap, N, seg_times, Nf, frame_times, frame_pos, W, mask + (int64_t)s * W,
+                               n_sel + s, span + 2 * (int64_t)s);
+}
+
+// One robot of a session's frame tensors (roman_session_frame_robot_t as the library stages it): its ranges of the session's tables.
+struct SessionFrameRobot {
+    int64_t seg0;            // first row of its segment table
+    int64_t mask_off;        // word offset of its first mask row
+    int32_t n_seg, sub0, n_sub, frame0, n_frames, mask_words;
+    int32_t reserved[2];
+};
+static_assert(sizeof(SessionFrameRobot) == sizeof(roman_session_frame_robot_t), "the staged record is the C ABI's");
+
+// the robot that holds global slot g: the last one whose first slot is <= g (robots without submaps share their first slot with the
+// robot behind them, which is the one found).  R >= 1 and g inside the session are the host's to check.
+__device__ __forceinline__ int session_frame_robot(const SessionFrameRobot* __restrict__ robots, int R, int g)
+{
+    int lo = 0, hi = R - 1;
+    while (lo < hi) {                                            // (uniform)
+        const int mid = (lo + hi + 1) >> 1;
+        if (robots[mid].sub0 <= g) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// ONE WAVE per LISTED slot, four per workgroup: k_frame_select's body over the robot's ranges of the session's
+// tensors, all mask_words of the row written, changed[l] = a word or the count differs from what the slot held.
+__global__ void __launch_bounds__(256) k_session_frame_select_list(roman_frame_select_params_t P, int L, int R, const int32_t* __restrict__ list,
+                                                                   const SessionFrameRobot* __restrict__ robots, int cap,
+                                                                   const int32_t* __restrict__ count, const int32_t* __restrict__ src,
+                                                                   const double* __restrict__ seg_times, const double* __restrict__ frame_times,
+                                                                   const double* __restrict__ frame_pos, unsigned long long* __restrict__ mask,
+                                                                   int32_t* __restrict__ n_sel, double* __restrict__ span, int32_t* __restrict__ changed)
+{
+    const int lane = threadIdx.x & 63, l = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (l >= L) return;                                          // (wave-uniform)
+    const int g = list[l];
+    const SessionFrameRobot rb = robots[session_frame_robot(robots, R, g)];
+    const bool differs = frame_select_submap<true>(P, lane, min(count[g], cap), src + (int64_t)g * cap, rb.n_seg, seg_times + 2 * rb.seg0, rb.n_frames,
+                                                   frame_times + rb.frame0, frame_pos ? frame_pos + 3 * (int64_t)rb.frame0 : nullptr, rb.mask_words,
+                                                   mask + rb.mask_off + (int64_t)(g - rb.sub0) * rb.mask_words, n_sel + g, span + 2 * (int64_t)g);
+    if (lane == 0) changed[l] = differs ? 1 : 0;
+}
+
+// column c of the selected rows of one submap, added in ascending frame index
+__device__ __forceinline__ double frame_column_sum(int words, int d, int c, const double* __restrict__ frame_desc, const unsigned long long* __restrict__ mask)
+{
+    double acc = 0.0;
+    for (int w = 0; w < words; ++w) {
+        unsigned long long bits = mask[w];                       // (uniform)
+        while (bits) {
+            const int t = __ffsll((long long)bits) - 1;
+            bits &= bits - 1ull;
+            acc += frame_desc[(int64_t)(64 * w + t) * d + c];
+        }
+    }
+    return acc;
 }
 
 // grid (submaps, column groups): mean[s][c] = (sum over the selected frames of submap s, ascending, of column c) / n_sel
@@ -8385,16 +8461,26 @@ __global__ void __launch_bounds__(256) k_frame_mean(int Nf, int d, const double*
     const int s = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
     if (c >= d) return;
     const int W = (Nf + 63) >> 6;
-    double acc = 0.0;
-    for (int w = 0; w < W; ++w) {
-        unsigned long long bits = mask[(int64_t)s * W + w];      // (uniform)
-        while (bits) {
-            const int t = __ffsll((long long)bits) - 1;
-            bits &= bits - 1ull;
-            acc += frame_desc[(int64_t)(64 * w + t) * d + c];
-        }
-    }
-    mean[(int64_t)s * d + c] = acc / (double)n_sel[s];          // 0 / 0 = NaN for a submap that selects nothing, as NumPy gives
+    mean[(int64_t)s * d + c] = frame_column_sum(W, d, c, frame_desc, mask + (int64_t)s * W) / (double)n_sel[s];   // 0 / 0 = NaN for a submap that selects nothing, as NumPy gives
+}
+
+// grid (LISTED slots, column groups), behind k_session_frame_select_list on the same stream: the mean row of every listed slot in
+// k_frame_mean's order.  A thread compares its column's old 64 bits with the new ones (NaN by bits) and stores 1 into changed[l]
+// only when they differ: every writer stores the same value, no atomic.
+__global__ void __launch_bounds__(256) k_session_frame_mean_list(int R, const int32_t* __restrict__ list, const SessionFrameRobot* __restrict__ robots, int d,
+                                                                 const double* __restrict__ frame_desc, const unsigned long long* __restrict__ mask,
+                                                                 const int32_t* __restrict__ n_sel, double* __restrict__ mean, int32_t* __restrict__ changed)
+{
+    const int l = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
+    if (c >= d) return;
+    const int g = list[l];
+    const SessionFrameRobot rb = robots[session_frame_robot(robots, R, g)];
+    // (a robot without frames selects nothing: its descriptor rows are never read)
+    const double v = frame_column_sum((rb.n_frames + 63) >> 6, d, c, frame_desc + (int64_t)rb.frame0 * d,
+                                      mask + rb.mask_off + (int64_t)(g - rb.sub0) * rb.mask_words) / (double)n_sel[g];
+    double* out = mean + (int64_t)g * d + c;
+    if (__double_as_longlong(*out) != __double_as_longlong(v)) changed[l] = 1;
+    *out = v;
 }
 
 __global__ void __launch_bounds__(256) k_fill_f64(int64_t n, double v, double* __restrict__ out)

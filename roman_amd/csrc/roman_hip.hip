@@ -199,6 +199,10 @@ struct roman_ctx {
     // through pinned staging (a pure enqueue)
     DevBuf ssItems;
     PinnedStage<int64_t> ssStage;
+    // the listed slots of a session's resident frame tables (roman_session_frame_select_list*): the robots' records and the list
+    // behind them, as 64-bit words through pinned staging (a pure enqueue)
+    DevBuf sfTab;
+    PinnedStage<int64_t> sfStage;
 
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
@@ -1475,6 +1479,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     c->smStage.release(); c->smTab.release(); c->smTabStage.release(); c->smListOut.release();
     c->ggNorm.release(); c->sgCount.release();
     c->ssNorm.release(); c->ssBand.release(); c->ssR.release(); c->ssItems.release(); c->ssStage.release();
+    c->sfTab.release(); c->sfStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -4042,6 +4047,140 @@ int roman_frame_select(roman_ctx_t* c, const roman_frame_select_params_t* fparam
                                 dMask.dev(), sel.dev(), dSpan.dev(), dMean.dev());
     if (rc) return rc;
     return m.download();
+}
+
+// --- the LISTED slots of a session whose frame tables stay in HBM ---------------------------------------------------
+// What one call works on, under names; the host form hands the device form a copy whose bulk arrays are the mirror's.  robots and list
+// are HOST memory in both forms.
+struct SessionFrameArgs {
+    int32_t R; const roman_session_frame_robot_t* robots; int32_t cap;
+    const int32_t* count; const int32_t* src; const double* seg_times; const double* frame_times; const double* frame_pos;
+    int32_t d; const double* frame_desc; int32_t L; const int32_t* list;
+    uint64_t* mask; int32_t* n_sel; double* span; double* mean; int32_t* changed;
+};
+// the extents the robots' ranges span: segment rows, slots, frames, mask words
+struct SessionFrameExtent { int64_t seg = 0, sub = 0, frames = 0, words = 0; };
+
+// the header's order: the parameter block (frame_select_check's own), the robots, the list, the sizes, the pointers
+static int session_frame_check(roman_ctx* c, const roman_frame_select_params_t* P, const SessionFrameArgs& g, SessionFrameExtent* x)
+{
+    int rc = frame_select_check(c, P, 0, g.cap, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, g.d, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (g.R < 0) return fail(c, ROMAN_E_INVALID, "R < 0");
+    if (g.R > 0 && !g.robots) return fail(c, ROMAN_E_INVALID, "robots is NULL");
+    SessionFrameExtent e;
+    for (int r = 0; r < g.R; ++r) {
+        const roman_session_frame_robot_t& b = g.robots[r];
+        if (b.reserved[0] != 0 || b.reserved[1] != 0) return fail(c, ROMAN_E_INVALID, "roman_session_frame_robot_t reserved words must be 0 (robot %d)", r);
+        if (b.seg0 < 0 || b.mask_off < 0 || b.n_seg < 0 || b.sub0 < 0 || b.n_sub < 0 || b.frame0 < 0 || b.n_frames < 0 || b.mask_words < 0)
+            return fail(c, ROMAN_E_INVALID, "robot %d holds a negative size or offset", r);
+        if ((int64_t)b.mask_words < ((int64_t)b.n_frames + 63) / 64)
+            return fail(c, ROMAN_E_INVALID, "robot %d: mask_words=%d is less than the %lld words of its %d frames", r, b.mask_words,
+                        (long long)(((int64_t)b.n_frames + 63) / 64), b.n_frames);
+        if (b.seg0 < e.seg || b.sub0 < e.sub || b.frame0 < e.frames || b.mask_off < e.words)
+            return fail(c, ROMAN_E_INVALID, "the ranges of robot %d are not ascending and disjoint", r);
+        e.seg = b.seg0 + b.n_seg; e.sub = (int64_t)b.sub0 + b.n_sub; e.frames = (int64_t)b.frame0 + b.n_frames;
+        e.words = b.mask_off + (int64_t)b.n_sub * b.mask_words;
+    }
+    if (g.L < 0) return fail(c, ROMAN_E_INVALID, "L < 0");
+    if (g.L > 0 && !g.list) return fail(c, ROMAN_E_INVALID, "list is NULL");
+    for (int32_t l = 0, r = 0; l < g.L; ++l) {
+        const int32_t s = g.list[l];
+        if (s < 0 || s >= e.sub) return fail(c, ROMAN_E_INVALID, "list[%d] = %d outside the %lld slots of the session", l, s, (long long)e.sub);
+        if (l > 0 && s <= g.list[l - 1]) return fail(c, ROMAN_E_INVALID, "list is not strictly ascending at entry %d", l);
+        while ((int64_t)s >= (int64_t)g.robots[r].sub0 + g.robots[r].n_sub) ++r;                 // (s < e.sub: a robot ends behind it)
+        if (s < g.robots[r].sub0) return fail(c, ROMAN_E_INVALID, "list[%d] = %d lies between the slots of two robots", l, s);
+    }
+    if (e.sub > (int64_t)INT32_MAX || e.frames > (int64_t)INT32_MAX || e.sub * g.cap > (int64_t)INT32_MAX)
+        return fail(c, ROMAN_E_TOO_LARGE, "%lld slots of %d rows or %lld frames exceed the index width", (long long)e.sub, g.cap, (long long)e.frames);
+    *x = e;
+    if (g.L == 0) return ROMAN_OK;
+    if (!g.count || !g.src || !g.n_sel || !g.span || !g.changed || (e.words > 0 && !g.mask) || (P->want_mean && !g.mean))
+        return fail(c, ROMAN_E_INVALID, "NULL count, src or output pointer");
+    if (e.seg > 0 && !g.seg_times) return fail(c, ROMAN_E_INVALID, "seg_times is NULL");
+    if (e.frames > 0 && (!g.frame_times || (P->thin && !g.frame_pos) || (P->want_mean && !g.frame_desc)))
+        return fail(c, ROMAN_E_INVALID, "frame_times / frame_pos / frame_desc is NULL");
+    return ROMAN_OK;
+}
+
+static int session_frame_select_list_dev(roman_ctx* c, const roman_frame_select_params_t* fparams, const SessionFrameArgs& g)
+{
+    SessionFrameExtent x;
+    int rc = session_frame_check(c, fparams, g, &x);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (g.L == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    // the robots' records and the list behind them as ONE staged block of 64-bit words: a pure enqueue
+    constexpr size_t RW = sizeof(SessionFrameRobot) / sizeof(int64_t);
+    const size_t words = RW * (size_t)g.R + ((size_t)g.L + 1) / 2;
+    int64_t* staged = nullptr;
+    HIPCHK(c, c->sfTab.ensure(sizeof(int64_t) * words));
+    HIPCHK(c, c->sfStage.stage(words, &staged));
+    memcpy(staged, g.robots, sizeof(SessionFrameRobot) * (size_t)g.R);
+    staged[words - 1] = 0;
+    memcpy(staged + RW * (size_t)g.R, g.list, sizeof(int32_t) * (size_t)g.L);
+    HIPCHK(c, c->sfStage.upload(c->sfTab, words, stream));
+    const SessionFrameRobot* dRobots = c->sfTab.as<SessionFrameRobot>();
+    const int32_t* dList = reinterpret_cast<const int32_t*>(c->sfTab.as<int64_t>() + RW * (size_t)g.R);
+    hipLaunchKernelGGL(k_session_frame_select_list, dim3((unsigned)((g.L + 3) / 4)), dim3(256), 0, stream, *fparams, (int)g.L, (int)g.R, dList, dRobots, (int)g.cap,
+                       g.count, g.src, g.seg_times, g.frame_times, g.frame_pos, reinterpret_cast<unsigned long long*>(g.mask), g.n_sel, g.span, g.changed);
+    if (fparams->want_mean)
+        hipLaunchKernelGGL(k_session_frame_mean_list, dim3((unsigned)g.L, (unsigned)((g.d + 255) / 256)), dim3(256), 0, stream, (int)g.R, dList, dRobots, (int)g.d,
+                           g.frame_desc, reinterpret_cast<const unsigned long long*>(g.mask), (const int32_t*)g.n_sel, g.mean, g.changed);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+static int session_frame_select_list_host(roman_ctx* c, const roman_frame_select_params_t* fparams, const SessionFrameArgs& h)
+{
+    SessionFrameExtent x;
+    int rc = session_frame_check(c, fparams, h, &x);
+    if (rc) return rc;
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (h.L == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const bool thin = fparams->thin != 0, wm = fparams->want_mean != 0;
+    HostMirror m(c);
+    const auto cnt = m.in(h.count, 4 * (size_t)x.sub);
+    const auto dSrc = m.in(h.src, 4 * (size_t)x.sub * (size_t)h.cap);
+    const auto seg = m.in(h.seg_times, 16 * (size_t)x.seg);
+    const auto ft = m.in(h.frame_times, 8 * (size_t)x.frames);
+    const auto fp = m.in(h.frame_pos, thin ? 24 * (size_t)x.frames : 0);
+    const auto fd = m.in(h.frame_desc, wm ? 8 * (size_t)x.frames * (size_t)h.d : 0);
+    const auto dMask = m.inout(h.mask, 8 * (size_t)x.words);
+    const auto sel = m.inout(h.n_sel, 4 * (size_t)x.sub);
+    const auto dSpan = m.inout(h.span, 16 * (size_t)x.sub);
+    const auto dMean = m.inout(h.mean, wm ? 8 * (size_t)x.sub * (size_t)h.d : 0);
+    const auto chg = m.out(h.changed, 4 * (size_t)h.L);
+    rc = m.upload();
+    if (rc) return rc;
+    SessionFrameArgs g = h;
+    g.count = cnt.dev(); g.src = dSrc.dev(); g.seg_times = seg.dev(); g.frame_times = ft.dev(); g.frame_pos = fp.dev(); g.frame_desc = fd.dev();
+    g.mask = dMask.dev(); g.n_sel = sel.dev(); g.span = dSpan.dev(); g.mean = dMean.dev(); g.changed = chg.dev();
+    rc = session_frame_select_list_dev(c, fparams, g);
+    if (rc) return rc;
+    return m.download();
+}
+
+int roman_session_frame_select_list_dev(roman_ctx_t* c, const roman_frame_select_params_t* fparams, int32_t R, const roman_session_frame_robot_t* robots,
+                                        int32_t cap, const int32_t* count, const int32_t* src, const double* seg_times, const double* frame_times,
+                                        const double* frame_pos, int32_t d, const double* frame_desc, int32_t L, const int32_t* list,
+                                        uint64_t* mask, int32_t* n_sel, double* span, double* mean, int32_t* changed)
+{
+    const SessionFrameArgs g{R, robots, cap, count, src, seg_times, frame_times, frame_pos, d, frame_desc, L, list, mask, n_sel, span, mean, changed};
+    return session_frame_select_list_dev(c, fparams, g);
+}
+
+int roman_session_frame_select_list(roman_ctx_t* c, const roman_frame_select_params_t* fparams, int32_t R, const roman_session_frame_robot_t* robots,
+                                    int32_t cap, const int32_t* count, const int32_t* src, const double* seg_times, const double* frame_times,
+                                    const double* frame_pos, int32_t d, const double* frame_desc, int32_t L, const int32_t* list,
+                                    uint64_t* mask, int32_t* n_sel, double* span, double* mean, int32_t* changed)
+{
+    const SessionFrameArgs g{R, robots, cap, count, src, seg_times, frame_times, frame_pos, d, frame_desc, L, list, mask, n_sel, span, mean, changed};
+    return session_frame_select_list_host(c, fparams, g);
 }
 
 static int stacked_sim_check(roman_ctx* c, int32_t d, int32_t Nf0, const void* desc0, int32_t S0, const void* mask0,

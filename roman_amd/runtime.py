@@ -356,6 +356,24 @@ def frame_select_params(thin_dist=None, want_mean=False):
     return P
 
 
+def session_frame_robot_dtype():
+    """roman_session_frame_robot_t as a structured dtype."""
+    return np.dtype([("seg0", np.int64), ("mask_off", np.int64), ("n_seg", np.int32), ("sub0", np.int32), ("n_sub", np.int32), ("frame0", np.int32),
+                     ("n_frames", np.int32), ("mask_words", np.int32), ("reserved", np.int32, (2,))])
+
+
+def session_frame_robots(n_seg, n_sub, n_frames, mask_words=None):
+    """The robots' records of a session whose tables hold every robot's range next to the one in front of it -> a
+    session_frame_robot_dtype array (mask_words: per robot, default ceil(Nf_r / 64))."""
+    n_seg, n_sub, n_frames = (np.asarray(x, dtype=np.int64).reshape(-1) for x in (n_seg, n_sub, n_frames))
+    words = (n_frames + 63) // 64 if mask_words is None else np.asarray(mask_words, dtype=np.int64).reshape(-1)
+    first = lambda n: np.concatenate([[0], np.cumsum(n)[:-1]]) if len(n) else n
+    rec = np.zeros(len(n_seg), dtype=session_frame_robot_dtype())
+    rec["seg0"], rec["n_seg"], rec["sub0"], rec["n_sub"] = first(n_seg), n_seg, first(n_sub), n_sub
+    rec["frame0"], rec["n_frames"], rec["mask_words"], rec["mask_off"] = first(n_frames), n_frames, words, first(n_sub * words)
+    return rec
+
+
 def grid_gate_params(radius, skip_distance=np.inf, desc_dim=0, desc_thresh=0.0, single_robot_lc=False, lc_time_thresh=0.0):
     """-> roman_grid_gate_params_t (a missing radius — None — is passed as -1: roman_grid_gate* answers ROMAN_E_UNSUPPORTED,
     roman_grid_gate_aabb* does not read it)."""
@@ -1261,6 +1279,53 @@ class Context:
                                               int(Nf), _vp(frame_times_ptr), _vp(frame_pos_ptr), int(d), _vp(frame_desc_ptr),
                                               _vp(mask_ptr), _vp(n_sel_ptr), _vp(span_ptr), _vp(mean_ptr))
         self._check(rc, "roman_frame_select_dev")
+
+    @staticmethod
+    def _frame_robots(robots):
+        robots = np.ascontiguousarray(robots, dtype=session_frame_robot_dtype()).reshape(-1)
+        assert robots.dtype.itemsize == _abi.SESSION_FRAME_ROBOT_NBYTES
+        return robots
+
+    def session_frame_select_list(self, fparams, robots, count, src, seg_times, frame_times, lst, mask, n_sel, span, frame_pos=None, frame_desc=None,
+                                  mean=None):
+        """Host-pointer frame selection of the LISTED slots of a session in place (roman_session_frame_select_list):
+        `robots` a session_frame_robot_dtype array; count (S,) and src (S, cap) by global slot; seg_times, frame_times, frame_pos,
+        frame_desc the session's tables; mask (uint64 words), n_sel (S,), span (S, 2) and mean (S, d) the session's CURRENT outputs
+        (C-contiguous), which the call changes in the listed slots only.  -> changed int32[L]."""
+        robots = self._frame_robots(robots)
+        count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1); S = count.shape[0]
+        src = np.ascontiguousarray(src, dtype=np.int32)
+        if src.ndim != 2 or src.shape[0] != S or src.shape[1] < 1:
+            raise ValueError("src must be (S, cap)")
+        seg_times = _f64(seg_times).reshape(-1, 2); frame_times = _f64(frame_times).reshape(-1); Nf = frame_times.shape[0]
+        frame_pos = None if frame_pos is None else _f64(frame_pos).reshape(Nf, 3)
+        frame_desc = None if frame_desc is None else _f64(frame_desc).reshape(Nf, -1)
+        d = 0 if frame_desc is None else frame_desc.shape[1]
+        ends = lambda a, n, per=1: int(max([0] + [int(x) + int(y) * int(z) for x, y, z in zip(robots[a], robots[n], np.broadcast_to(per, robots[n].shape))]))
+        if ends("seg0", "n_seg") > seg_times.shape[0] or ends("sub0", "n_sub") > S or ends("frame0", "n_frames") > Nf:
+            raise ValueError("a robot's range reaches beyond the session's tables")
+        _given(mask, (ends("mask_off", "n_sub", robots["mask_words"]),), np.uint64, 0)
+        _given(n_sel, (S,), np.int32, 0); _given(span, (S, 2), np.float64, 0)
+        if fparams.want_mean:
+            _given(mean, (S, d), np.float64, 0)
+        lst = self._submap_list(lst)
+        changed = np.zeros(len(lst), dtype=np.int32)
+        self._generation += 1
+        rc = self._lib.roman_session_frame_select_list(self._h, C.byref(fparams), len(robots), _ptr(robots), src.shape[1], _ptr(count), _ptr(src),
+                                                       _ptr(seg_times), _ptr(frame_times), _ptr(frame_pos), d, _ptr(frame_desc), len(lst), _ptr(lst),
+                                                       _ptr(mask), _ptr(n_sel), _ptr(span), _ptr(mean) if fparams.want_mean else None, _ptr(changed))
+        self._check(rc, "roman_session_frame_select_list")
+        return changed
+
+    def session_frame_select_list_dev(self, fparams, robots, cap, count_ptr, src_ptr, seg_times_ptr, frame_times_ptr, lst, mask_ptr, n_sel_ptr, span_ptr,
+                                      changed_ptr, frame_pos_ptr=None, d=0, frame_desc_ptr=None, mean_ptr=None):
+        """Device-pointer frame selection of the LISTED slots of a session in place (roman_session_frame_select_list_dev): `robots` (a
+        session_frame_robot_dtype array) and `lst` (global slots, strictly ascending) are host arrays, everything else a device
+        address.  A pure enqueue on the context's stream, behind session_submaps_list_dev."""
+        robots = self._frame_robots(robots)
+        lst = self._submap_list(lst)
+        self._enqueue("roman_session_frame_select_list_dev", C.byref(fparams), len(robots), _ptr(robots), int(cap), *_vps(count_ptr, src_ptr, seg_times_ptr,
+                      frame_times_ptr, frame_pos_ptr), int(d), _vp(frame_desc_ptr), int(len(lst)), _ptr(lst), *_vps(mask_ptr, n_sel_ptr, span_ptr, mean_ptr, changed_ptr))
 
     def stacked_sim(self, desc0, mask0, desc1, mask1):
         """Host-pointer stacked similarity of a grid (roman_stacked_sim, [REF roman/map/map.py:155-162]): desc_r (Nf_r, d) the
