@@ -1408,6 +1408,67 @@ ROMAN_API int roman_session_boxes(roman_ctx_t* ctx, int32_t S, int32_t F, const 
                                   const double* T_odom_center, double* box);
 
 /*
+ * roman_segment_shapes_dev: the segment table of a map from the segments' POINT CLOUDS — what the reference computes
+ * per segment in a Python loop before anything else: submaps_from_roman_map calls set_center_ref on every segment and then
+ * roman_map.minimal_data() [REF roman/map/map.py:258-262], which reads center, volume, linearity, planarity, scattering and extent of
+ * every Segment [REF roman/object/segment.py:496-508].  Bulk data on the DEVICE; a PURE ENQUEUE on the context's stream.
+ *   points        float64[P][3], odom frame: the clouds of all segments one behind the other, P = seg_off_host[N]
+ *   seg_off_dev   int64[N + 1] on the device, seg_off_host the same numbers on the HOST (the launch is sized from them; reading the
+ *                 device copy would cost a synchronisation): ascending, [0] == 0; segment i owns the rows [seg_off[i], seg_off[i + 1])
+ *   params        roman_segment_shape_params_t below
+ *   out           float64[N][out_stride]: row i receives, at the columns the block names and NOWHERE else,
+ *                   col_center + 0..2   the centre.  ROMAN_CENTER_MEAN: the mean [REF roman/object/segment.py:271-272].
+ *                                       ROMAN_CENTER_BOTTOM_MIDDLE: np.median of x and of y — for an even count (a + b) * 0.5 of the two
+ *                                       middle order statistics — and the minimum of z [REF :267-270]: a selection, EXACT (a median that is a zero
+ *                                       is +0.0, as np.median's mean step gives it; the minimum orders -0.0 below +0.0)
+ *                   col_pca + 0..2      linearity (e0 - e1) / e0, planarity (e1 - e2) / e0, scattering e2 / e0 [REF :445-472] of the
+ *                                       eigenvalues e0 >= e1 >= e2 (absolute values: the singular values of [REF :441]) of the 3 x 3
+ *                                       population covariance, taken about the mean in the CENTRED form sum (x - m)(x - m)' / n.
+ *                                       (open3d's compute_mean_and_covariance [REF :430] uses E[xx'] - mm', which cancels digits away
+ *                                       far from the origin: DESIGN.md §2.)  A zero covariance gives 0 / 0 = NaN, nothing is clamped
+ *                   col_extent + 0..2   the side lengths of the box of the points in the eigenframe of that covariance, ASCENDING
+ *                                       (every consumer reads sorted(extent)); col_volume their product [REF :244-263].  n <= 4: 0
+ *                                       [REF :253, :260].  UNPINNED against open3d's create_from_points
+ *   status        int32[N]: ROMAN_SEG_* flags below
+ * Sums run in a fixed order (no floating-point atomics): two calls give the same bits, and a segment's row depends on its own
+ * points only — not on its place in the list.  A segment of fewer than ROMAN_SEG_BLOCK_MIN points is one wave's, the others take a
+ * workgroup each; the two paths agree within the rounding bound of DESIGN.md §4.24, each is deterministic on its own.
+ * The contents of device arrays are not validated: seg_off_dev must hold what seg_off_host holds; non-finite points give
+ * unspecified values for their own segment and for no other.  N == 0: ROMAN_OK, nothing enqueued.
+ * Errors (ROMAN_E_INVALID, nothing enqueued): NULL ctx, params, seg_off_dev (N > 0) or seg_off_host; N < 0; seg_off_host[0] != 0 or
+ * descending; an unknown center_ref; out_stride < 1; col_center < 0 or another column < -1; a written column range that leaves
+ * out_stride; two written ranges that overlap; non-zero reserved words; NULL points with P > 0; NULL out / status with N > 0.
+ * A segment of more than INT32_MAX points: ROMAN_E_TOO_LARGE.
+ */
+#define ROMAN_CENTER_MEAN           0
+#define ROMAN_CENTER_BOTTOM_MIDDLE  1
+#define ROMAN_SEG_EMPTY        1   /* n == 0: the named columns of the row are zeros (ROMAN_SEG_FEW_POINTS is set as well) */
+#define ROMAN_SEG_FEW_POINTS   2   /* n <= 4: no box, extent and volume are 0 [REF roman/object/segment.py:253, :260]          */
+#define ROMAN_SEG_DEGENERATE   4   /* e0 == 0 (one point, or all points equal): the three ratios are NaN                     */
+#define ROMAN_SEG_BLOCK_MIN  768   /* points from which a segment takes a workgroup instead of a wave (roman_ctx_set_segment_block_min) */
+typedef struct roman_segment_shape_params {
+    int32_t center_ref;            /* ROMAN_CENTER_MEAN / ROMAN_CENTER_BOTTOM_MIDDLE */
+    int32_t out_stride;            /* doubles per row of `out` */
+    int32_t col_center;            /* first of 3 columns */
+    int32_t col_pca;               /* first of 3 columns, or -1: not written */
+    int32_t col_volume;            /* 1 column, or -1 */
+    int32_t col_extent;            /* first of 3 columns, or -1 */
+    int32_t reserved[2];           /* must be 0 */
+} roman_segment_shape_params_t;
+ROMAN_API int roman_segment_shapes_dev(roman_ctx_t* ctx, const double* points, const int64_t* seg_off_dev, const int64_t* seg_off_host, int32_t N,
+                                       const roman_segment_shape_params_t* params, double* out, int32_t* status);
+
+/* The same with HOST pointers everywhere.  Synchronous; `out` goes up first, so the columns that are not named come back as they were. */
+ROMAN_API int roman_segment_shapes(roman_ctx_t* ctx, const double* points, const int64_t* seg_off, int32_t N,
+                                   const roman_segment_shape_params_t* params, double* out, int32_t* status);
+
+/* Measurement only: the point count from which roman_segment_shapes* hands a segment to a workgroup (0: ROMAN_SEG_BLOCK_MIN again).
+   It changes which path a segment takes and with it the order of its sums: the rows of a context set to another value agree with
+   those of the default within the bound of DESIGN.md §4.24, NOT bit for bit, and the depth D of that bound is then the one of the
+   path taken.  Every documented figure and every test assumes the default. */
+ROMAN_API int roman_ctx_set_segment_block_min(roman_ctx_t* ctx, int32_t n);
+
+/*
  * roman_session_gate_aabb_dev: roman_session_gate_dev with the bounding-box gate [REF roman/align/submap_align.py:101-103]
  * — what roman_grid_gate_aabb_dev is to roman_grid_gate_dev.  The arguments are roman_session_gate_dev's; then
  *   box        float64[S][6] over ALL submaps of the session, as roman_session_boxes_dev wrote them.  NEARBY is the six comparisons

@@ -270,6 +270,28 @@ class RomanSessionFrameRobot(C.Structure):
     ]
 
 
+class RomanSegmentShapeParams(C.Structure):
+    """roman_segment_shape_params_t"""
+    _fields_ = [
+        ("center_ref", C.c_int32),
+        ("out_stride", C.c_int32),
+        ("col_center", C.c_int32),
+        ("col_pca", C.c_int32),
+        ("col_volume", C.c_int32),
+        ("col_extent", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+ROMAN_CENTER_MEAN = 0
+ROMAN_CENTER_BOTTOM_MIDDLE = 1
+CENTER_REFS = {"mean": ROMAN_CENTER_MEAN, "bottom_middle": ROMAN_CENTER_BOTTOM_MIDDLE}     # the strings of [REF roman/object/segment.py:266-274]
+# flag bits of roman_segment_shapes' status[]
+ROMAN_SEG_EMPTY = 1
+ROMAN_SEG_FEW_POINTS = 2
+ROMAN_SEG_DEGENERATE = 4
+ROMAN_SEG_BLOCK_MIN = 768   # points from which a segment takes a workgroup instead of a wave (kernels.hip.h SEG_BLOCK_MIN)
+
 # flag bits of roman_grid_gate's flags[]
 ROMAN_GRID_NEARBY = 1
 ROMAN_GRID_SKIP = 2
@@ -289,6 +311,7 @@ SUBMAP_DESC_NBYTES = C.sizeof(RomanSubmapDesc)
 GRID_GATE_PARAMS_NBYTES = C.sizeof(RomanGridGateParams)
 FRAME_SELECT_PARAMS_NBYTES = C.sizeof(RomanFrameSelectParams)
 SESSION_FRAME_ROBOT_NBYTES = C.sizeof(RomanSessionFrameRobot)
+SEGMENT_SHAPE_PARAMS_NBYTES = C.sizeof(RomanSegmentShapeParams)
 STACKED_BAND_MIN = 32       # the smallest row band of roman_stacked_sim* (kernels.hip.h STACK_TILE)
 LC_PARAMS_NBYTES = C.sizeof(RomanLcParams)
 LC_RECORD_NBYTES = C.sizeof(RomanLcRecord)
@@ -405,6 +428,9 @@ def load_library():
         "roman_stacked_sim_dev": (C.c_int, [ctxp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
         "roman_stacked_sim": (C.c_int, [ctxp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp]),
         "roman_ctx_set_stacked_band": (C.c_int, [ctxp, i32]),
+        "roman_segment_shapes_dev": (C.c_int, [ctxp, vp, vp, vp, i32, P(RomanSegmentShapeParams), vp, vp]),
+        "roman_segment_shapes": (C.c_int, [ctxp, vp, vp, i32, P(RomanSegmentShapeParams), vp, vp]),
+        "roman_ctx_set_segment_block_min": (C.c_int, [ctxp, i32]),
         "roman_ctx_has_history": (C.c_int, [ctxp, P(RomanParams), i32, P(i32)]),
         "roman_ctx_cosine_screen_stats": (C.c_int, [ctxp, P(C.c_int64), P(C.c_int64), P(C.c_double)]),
         "roman_create_all_to_all": (C.c_int, [i32, i32, vp]),
@@ -439,7 +465,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_shared_reduce_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_mno_lc_tail_dev", "roman_mno_lc_batch_dev", "roman_mno_lc_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ransac_lc_batch_dev", "roman_ransac_lc_batch", "roman_submaps_dev", "roman_submaps", "roman_session_submaps_dev", "roman_session_submaps", "roman_session_submaps_list_dev", "roman_session_submaps_list", "roman_grid_gate_dev", "roman_grid_gate", "roman_grid_gate_sim_dev", "roman_grid_gate_sim", "roman_submaps_fill_dev", "roman_submaps_fill", "roman_submap_boxes_dev", "roman_submap_boxes", "roman_grid_gate_aabb_dev", "roman_grid_gate_aabb", "roman_session_gate_dev", "roman_session_gate", "roman_session_gate_sim_dev", "roman_session_gate_sim", "roman_session_stacked_sim_dev", "roman_session_stacked_sim", "roman_session_stacked_sim_list_dev", "roman_session_stacked_sim_list", "roman_session_boxes_dev", "roman_session_boxes", "roman_session_gate_aabb_dev", "roman_session_gate_aabb", "roman_session_gate_list_dev", "roman_session_gate_list", "roman_frame_select_dev", "roman_frame_select", "roman_session_frame_select_list_dev", "roman_session_frame_select_list", "roman_stacked_sim_dev", "roman_stacked_sim", "roman_ctx_set_stacked_band", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_shared_reduce_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_mno_lc_tail_dev", "roman_mno_lc_batch_dev", "roman_mno_lc_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ransac_lc_batch_dev", "roman_ransac_lc_batch", "roman_submaps_dev", "roman_submaps", "roman_session_submaps_dev", "roman_session_submaps", "roman_session_submaps_list_dev", "roman_session_submaps_list", "roman_grid_gate_dev", "roman_grid_gate", "roman_grid_gate_sim_dev", "roman_grid_gate_sim", "roman_submaps_fill_dev", "roman_submaps_fill", "roman_submap_boxes_dev", "roman_submap_boxes", "roman_grid_gate_aabb_dev", "roman_grid_gate_aabb", "roman_session_gate_dev", "roman_session_gate", "roman_session_gate_sim_dev", "roman_session_gate_sim", "roman_session_stacked_sim_dev", "roman_session_stacked_sim", "roman_session_stacked_sim_list_dev", "roman_session_stacked_sim_list", "roman_session_boxes_dev", "roman_session_boxes", "roman_session_gate_aabb_dev", "roman_session_gate_aabb", "roman_session_gate_list_dev", "roman_session_gate_list", "roman_frame_select_dev", "roman_frame_select", "roman_session_frame_select_list_dev", "roman_session_frame_select_list", "roman_stacked_sim_dev", "roman_stacked_sim", "roman_ctx_set_stacked_band", "roman_segment_shapes_dev", "roman_segment_shapes", "roman_ctx_set_segment_block_min", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

@@ -13,3 +13,4 @@ from .ransac_reg import RansacReg  # noqa: F401
 from .submap_align_params import SubmapAlignParams  # noqa: F401
 from .batch import AlignmentBatch, align_pairs, all_pairs_problems  # noqa: F401
 from .submap_align import Submap, SubmapAlignIO, SubmapAlignResults  # noqa: F401  (the loop: roman_amd.align.submap_align.submap_align)
+from .segment_clouds import MinimalSegment, SegmentClouds  # noqa: F401  (tables from point clouds: MapTable.from_point_clouds)

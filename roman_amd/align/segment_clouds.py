@@ -1,0 +1,201 @@
+"""Segment tables from point clouds.
+
+A pickled ROMANMap holds full `Segment`s, each with its point cloud, and the first thing the reference's `submaps_from_roman_map`
+does with them is `set_center_ref` on every segment and `roman_map.minimal_data()` [REF roman/map/map.py:258-262]: per segment
+the centre, the three shape ratios, the box's extent and volume, from the points [REF roman/object/segment.py:496-508] — a Python
+loop with an open3d and an `np.linalg.svd` call per segment.  Here the clouds of a map are ONE array (`SegmentClouds`), one device
+call (roman_segment_shapes_dev) writes the centre and shape columns of the `MapTable` of any registration
+(`MapTable.from_point_clouds`), and `MinimalSegment` records over the table's rows serve the host-side callers that read
+attributes (`SubmapPool.to_submaps`, `submap_align_grid`, the writers).
+
+torch is used for device memory only; nothing numerical happens here.
+"""
+from dataclasses import dataclass
+from typing import List, Optional
+
+import numpy as np
+
+from .. import _abi
+from ..runtime import segment_shape_params
+from .ransac_reg import RansacReg
+
+
+class MinimalSegment:
+    """The attribute contract of SegmentMinimalData [REF roman/object/segment.py:19-59] over one row of values: id, center (3, 1),
+    volume, linearity, planarity, scattering, extent (3,), semantic_descriptor, first_seen, last_seen, reference_time()."""
+    __slots__ = ("id", "centroid", "volume", "linearity", "planarity", "scattering", "extent", "semantic_descriptor", "first_seen", "last_seen")
+
+    def __init__(self, id, center, volume, linearity, planarity, scattering, extent, semantic_descriptor, first_seen, last_seen):
+        self.id = int(id)
+        self.centroid = np.asarray(center, dtype=np.float64).reshape(-1, 1)
+        self.volume, self.linearity, self.planarity, self.scattering = float(volume), float(linearity), float(planarity), float(scattering)
+        self.extent = np.asarray(extent, dtype=np.float64).reshape(-1)
+        self.semantic_descriptor = semantic_descriptor
+        self.first_seen, self.last_seen = float(first_seen), float(last_seen)
+
+    @property
+    def center(self):
+        return self.centroid
+
+    def reference_time(self, use_avg_time=True):
+        """[REF roman/object/segment.py:57-59]"""
+        return (self.first_seen + self.last_seen) / 2.0 if use_avg_time else self.first_seen
+
+
+@dataclass
+class ShapeColumns:
+    """Where the rows of a registration's MapTable hold what the device writes: first column of the centre (always 0), of the three
+    ratios, of the volume, of the extent (-1: the rows do not hold it), the row width and the descriptor's width behind it."""
+    stride: int
+    center: int = 0
+    pca: int = -1
+    volume: int = -1
+    extent: int = -1
+    desc_dim: int = 0
+
+    def params(self, center_ref="mean"):
+        return segment_shape_params(center_ref, self.stride, self.center, self.pca, self.volume, self.extent)
+
+
+def shape_columns(registration, desc_dim=None) -> ShapeColumns:
+    """The column map of `MapTable.from_segments(registration, ...)`'s rows: [x y z | registration.pack's columns behind the point].
+    ROMANRegistration: pca(3), volume(1), sorted extent(3), descriptor, each if enabled [REF roman/align/roman_registration.py:98-108];
+    DistRegWithPruning.on_device(): volume, linearity, planarity, scattering, descriptor; the host-prefilter DistRegWithPruning and
+    RansacReg: centres only.  desc_dim: the descriptor width of a device-prefilter plugin that has not seen one yet."""
+    from .dist_reg_with_pruning import DistRegWithPruning
+    from .roman_registration import ROMANRegistration
+    if isinstance(registration, RansacReg):
+        return ShapeColumns(3)
+    if isinstance(registration, DistRegWithPruning):
+        if not registration.prune_on_device:
+            return ShapeColumns(3)
+        d = registration.semantics_dim if registration.semantics_dim is not None else desc_dim
+        if d is None:
+            raise ValueError("prune_on_device needs semantics_dim (or clouds with descriptors)")
+        return ShapeColumns(7 + int(d), volume=3, pca=4, desc_dim=int(d))
+    if isinstance(registration, ROMANRegistration):
+        cols, c = ShapeColumns(0), 3
+        if registration.pca:
+            cols.pca, c = c, c + 3
+        if registration.volume:
+            cols.volume, c = c, c + 1
+        if registration.extent:
+            cols.extent, c = c, c + 3
+        cols.desc_dim = int(registration._abi_params().cos_feature_dim)
+        cols.stride = c + cols.desc_dim
+        return cols
+    raise ValueError(f"no column map for a {type(registration).__name__}")
+
+
+@dataclass
+class SegmentClouds:
+    """The segments of a whole map with their point clouds, in map order, odom frame."""
+    points: np.ndarray                    # (P, 3) float64: all clouds one behind the other
+    seg_off: np.ndarray                   # (N + 1,) int64 ascending: segment i owns the rows [seg_off[i], seg_off[i + 1])
+    ids: np.ndarray                       # (N,) int64
+    times: np.ndarray                     # (N, 2) first_seen, last_seen
+    descriptors: Optional[np.ndarray] = None   # (N, d) semantic descriptors, or None
+
+    @classmethod
+    def from_segments(cls, segments):
+        """Reads .points, .id, .first_seen, .last_seen and .semantic_descriptor of reference-style Segments
+        [REF roman/object/segment.py:61-94].  A segment whose points is None holds no point.  The descriptors are kept when every
+        segment has one."""
+        n = len(segments)
+        clouds = [np.zeros((0, 3)) if s.points is None else np.asarray(s.points, dtype=np.float64).reshape(-1, 3) for s in segments]
+        seg_off = np.zeros(n + 1, dtype=np.int64)
+        if n:
+            seg_off[1:] = np.cumsum([len(c) for c in clouds])
+        points = np.ascontiguousarray(np.vstack(clouds)) if n else np.zeros((0, 3))
+        ids = np.array([s.id for s in segments], dtype=np.int64).reshape(n)
+        times = np.array([[s.first_seen, s.last_seen] for s in segments], dtype=np.float64).reshape(n, 2)
+        desc = None
+        if n and all(getattr(s, "semantic_descriptor", None) is not None for s in segments):
+            desc = np.ascontiguousarray(np.stack([np.asarray(s.semantic_descriptor, dtype=np.float64).reshape(-1) for s in segments]))
+        return cls(points, seg_off, ids, times, desc)
+
+    def __len__(self):
+        return int(np.asarray(self.seg_off).shape[0]) - 1
+
+    def minimal_segments(self, table) -> List[MinimalSegment]:
+        """One MinimalSegment per row of `table` (a MapTable.from_point_clouds of these clouds): the centre and whichever shape
+        attributes the table's registration keeps (NaN for the others), this object's descriptors, times and ids."""
+        cols = getattr(table, "shape_cols", None)
+        if cols is None or len(table) != len(self):
+            raise ValueError("the table was not built from these clouds (MapTable.from_point_clouds)")
+        f, nan = table.feats, float("nan")
+        out = []
+        for i in range(len(self)):
+            pca = f[i, cols.pca:cols.pca + 3] if cols.pca >= 0 else (nan, nan, nan)
+            out.append(MinimalSegment(self.ids[i], f[i, :3], f[i, cols.volume] if cols.volume >= 0 else nan, pca[0], pca[1], pca[2],
+                                      f[i, cols.extent:cols.extent + 3] if cols.extent >= 0 else np.full(3, nan),
+                                      None if self.descriptors is None else self.descriptors[i], self.times[i, 0], self.times[i, 1]))
+        return out
+
+
+def _refusals(registration, clouds, center_ref, volume, extent):
+    """What from_point_clouds refuses before any context is made -> (points, seg_off, N, the column map, descriptors or None)."""
+    if center_ref not in _abi.CENTER_REFS:
+        raise ValueError(f"center_ref must be one of {sorted(_abi.CENTER_REFS)} (got {center_ref!r})")
+    try:
+        points = np.ascontiguousarray(clouds.points, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"points must be convertible to float64: {e}") from None
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (P, 3) (got {points.shape})")
+    seg_off = np.ascontiguousarray(clouds.seg_off, dtype=np.int64).reshape(-1)
+    if seg_off.shape[0] < 1 or seg_off[0] != 0 or np.any(np.diff(seg_off) < 0):
+        raise ValueError("seg_off must ascend from 0")
+    if int(seg_off[-1]) != points.shape[0]:
+        raise ValueError(f"seg_off ends at {int(seg_off[-1])}, the clouds hold {points.shape[0]} points")
+    N = int(seg_off.shape[0]) - 1
+    ids = np.asarray(clouds.ids).reshape(-1); times = np.asarray(clouds.times)
+    if ids.shape[0] != N or times.shape != (N, 2):
+        raise ValueError("ids must be (N,) and times (N, 2)")
+    desc = None if clouds.descriptors is None else np.ascontiguousarray(clouds.descriptors, dtype=np.float64)
+    cols = shape_columns(registration, None if desc is None or desc.ndim != 2 else int(desc.shape[1]))
+    if cols.desc_dim > 0:
+        if desc is None:
+            raise ValueError(f"the registration reads descriptors of {cols.desc_dim} columns: the clouds hold none")
+        if desc.shape != (N, cols.desc_dim):
+            raise ValueError(f"descriptors must be ({N}, {cols.desc_dim}) for this registration (got {desc.shape})")
+    if volume is not None and np.shape(volume) != (N,):
+        raise ValueError(f"volume must be ({N},)")
+    if extent is not None and np.shape(extent) != (N, 3):
+        raise ValueError(f"extent must be ({N}, 3)")
+    return points, seg_off, N, cols, desc
+
+
+def table_from_point_clouds(cls, registration, clouds, center_ref="mean", ctx=None, device=None, volume=None, extent=None):
+    """MapTable.from_point_clouds (its docstring)."""
+    points, seg_off, N, cols, desc = _refusals(registration, clouds, center_ref, volume, extent)
+    if getattr(registration, "prune_on_device", False) and registration.semantics_dim is None:
+        registration.semantics_dim = cols.desc_dim                           # as the plugin's pack() takes it from the first object packed
+    import torch
+    ctx = ctx or registration._context()
+    dev = torch.device(device if device is not None else f"cuda:{getattr(ctx, 'device', 0)}")
+    feats_h = np.zeros((N, cols.stride), dtype=np.float64)
+    if cols.desc_dim:                                                        # the descriptor columns are the host's, as today
+        feats_h[:, cols.stride - cols.desc_dim:] = desc
+    feats = torch.from_numpy(feats_h).to(dev)
+    pts = torch.from_numpy(points).to(dev); off = torch.from_numpy(seg_off).to(dev)
+    status = torch.zeros(max(N, 1), dtype=torch.int32, device=dev)
+    if dev.type != "cpu":
+        torch.cuda.current_stream(dev).synchronize()                         # inputs are in place before the library's stream touches them
+    ctx.segment_shapes_dev(pts.data_ptr(), off.data_ptr(), seg_off, cols.params(center_ref), feats.data_ptr(), status.data_ptr())
+    ctx.sync()
+    feats_h = np.ascontiguousarray(feats.cpu().numpy())
+    if volume is not None and cols.volume >= 0:                              # the caller's numbers (open3d's, say) in place of the device's
+        feats_h[:, cols.volume] = np.asarray(volume, dtype=np.float64)
+    if extent is not None and cols.extent >= 0:
+        feats_h[:, cols.extent:cols.extent + 3] = np.sort(np.asarray(extent, dtype=np.float64), axis=1)
+    times = np.ascontiguousarray(clouds.times, dtype=np.float64).reshape(N, 2)
+    ids = np.ascontiguousarray(clouds.ids, dtype=np.int64).reshape(N)
+    if isinstance(registration, RansacReg):
+        table = cls(feats_h, times, ids, int(registration.dim), 0)
+    else:
+        P = registration._abi_params()
+        d = int(P.cos_feature_dim) if P.invariant != _abi.ROMAN_INV_EUCLIDEAN else 0
+        table = cls(feats_h, times, ids, int(registration.dim), d, int(P.invariant))
+    table.shape_cols, table.shape_status = cols, status.cpu().numpy()[:N].copy()
+    return table

@@ -149,6 +149,22 @@ class MapTable:
     desc_dim: int                # trailing descriptor columns (0: none)
     invariant: Optional[int] = None   # ROMAN_INV_* of the registration that packed the rows (its column order between point and descriptor);
                                       # None: centres only (a RansacReg) or a table built by other means
+    shape_cols: Optional[object] = None    # from_point_clouds only: the segment_clouds.ShapeColumns the device wrote (clouds.minimal_segments reads it)
+    shape_status: Optional[np.ndarray] = None   # from_point_clouds only: (N,) int32 ROMAN_SEG_* flags of every segment
+
+    @classmethod
+    def from_point_clouds(cls, registration, clouds, center_ref='mean', ctx=None, device=None, volume=None, extent=None):
+        """The table of `from_segments(registration, ...)` — same layout, same point_dim, desc_dim and invariant — from the segments'
+        POINT CLOUDS (a segment_clouds.SegmentClouds): ONE roman_segment_shapes_dev call writes the centre (center_ref 'mean' or
+        'bottom_middle' [REF roman/object/segment.py:266-274]; the reference's SubmapParams holds it and from_submap_align_params never
+        sets it, so it is an argument here) and whichever of the ratios, volume and extent the registration's rows hold, at the
+        columns `registration.pack` puts them; the descriptor columns, times and ids are the host's.  This replaces the reference's
+        per-segment loop of set_center_ref + minimal_data() [REF roman/map/map.py:258-262].  `volume` (N,) / `extent` (N, 3) given:
+        they replace the device's columns (the box is UNPINNED against open3d, DESIGN.md §2: a caller with open3d keeps its numbers).
+        Refused with ValueError before any context is made: seg_off not ascending from 0 or not ending at P, points not (P, 3)
+        float64-convertible, descriptors missing or of another width than the registration reads, volume / extent of the wrong shape."""
+        from .segment_clouds import table_from_point_clouds
+        return table_from_point_clouds(cls, registration, clouds, center_ref, ctx, device, volume, extent)
 
     @classmethod
     def from_segments(cls, registration, segments):

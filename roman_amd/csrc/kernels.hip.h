@@ -8876,4 +8876,329 @@ __global__ void k_debug_math(int kind, const double* __restrict__ a, const doubl
     out[i] = r;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Segment tables from point clouds: per segment the centre, the three shape ratios of the centred covariance's
+// eigenvalues, and extent and volume of the box in its eigenframe — what Segment.minimal_data() computes per segment on the host
+// [REF roman/object/segment.py:496-508].  A TEAM of NW waves takes one segment: one wave (k_seg_shapes_wave, four segments per
+// workgroup) for a segment of fewer than `block_min` points, the four waves of a workgroup (k_seg_shapes_block) for the others.
+// Every sweep reads the cloud as a flat stream of doubles into LDS (coalesced: 24-byte points are not 16-byte aligned), and thread t
+// of the team then takes point t of the chunk from there.
+//
+// Sums run in a FIXED order: thread t of the team adds the points t, t + 64 NW, t + 128 NW, ... of its segment one after the other,
+// the 64 lanes of a wave are combined by wave_sum63's tree (6 levels), and the NW waves' sums are added in wave order.  No floating
+// point atomics; nothing depends on how waves are scheduled.  The depth of a sum over n terms is ceil(n / (64 NW)) - 1 + 6 + NW - 1.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int SEG_BLOCK_MIN = 768;           // ROMAN_SEG_BLOCK_MIN: points from which a segment goes to a workgroup (profiles/segment_shapes/README.md)
+constexpr int SEG_ST_EMPTY = 1, SEG_ST_FEW_POINTS = 2, SEG_ST_DEGENERATE = 4;     // ROMAN_SEG_* of include/roman_hip.h
+
+struct SegShapeArgs {
+    const double* pts;                       // (P, 3)
+    const int64_t* seg_off;                  // [N + 1]
+    const int32_t* items;                    // the host-cut list: the segments of the wave kernel, then those of the workgroup kernel
+    double* out; int32_t* status;
+    int center_ref, stride, col_center, col_pca, col_volume, col_extent;
+};
+
+template <int NW> struct SegLds {
+    double stage[3 * 64 * NW];               // one chunk of 64 NW points, as it lies in memory
+    double red[NW * 6];                      // the waves' partial results of a team reduction
+    unsigned long long zkey[NW];
+    unsigned int hist[4][256];               // radix select: one histogram per (coordinate, order statistic)
+    unsigned long long pre[4];               // ... the key bits found so far
+    unsigned int rk[4];                      // ... the rank that is left inside the group of keys that share them
+};
+
+// the order-preserving 64-bit key of a double: negative values with every bit flipped, the others with the sign bit set
+// (-inf < ... < -0.0 < +0.0 < ... < +inf as unsigned integers), and back
+__device__ __forceinline__ unsigned long long seg_key(double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double seg_unkey(unsigned long long k)
+{
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+template <int NW> __device__ __forceinline__ void seg_sync()
+{
+    if (NW == 1) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
+    else __syncthreads();
+}
+
+// One sweep over the n points from row p0 on: f(x, y, z) for every point, in the fixed thread assignment above.  Every thread of
+// the team makes every trip of the chunk loop (it holds the team's barriers); ends behind a barrier.
+template <int NW, typename F>
+__device__ __forceinline__ void seg_sweep(const double* __restrict__ pts, int64_t p0, int64_t n, double* stage, int tid, F f)
+{
+    constexpr int NT = 64 * NW;
+    for (int64_t c0 = 0; c0 < n; c0 += NT) {
+        const int m = n - c0 < (int64_t)NT ? (int)(n - c0) : NT;
+        const double* src = pts + 3 * (p0 + c0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const int e = tid + k * NT; if (e < 3 * m) stage[e] = src[e]; }
+        seg_sync<NW>();
+        if (tid < m) f(stage[3 * tid], stage[3 * tid + 1], stage[3 * tid + 2]);
+        seg_sync<NW>();
+    }
+}
+
+// the team's sum of K values per thread, in the fixed order, on every thread
+template <int NW, int K> __device__ __forceinline__ void seg_team_sum(double (&v)[K], double* red, int tid)
+{
+    static_assert(K <= 6, "SegLds::red holds six values per wave");
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = readlane63(wave_sum63(v[k]));
+    if (NW == 1) return;
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[(tid >> 6) * K + k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) { double s = red[k]; for (int w = 1; w < NW; ++w) s += red[w * K + k]; v[k] = s; }
+    __syncthreads();
+}
+
+// the team's minima of lo[3] and maxima of hi[3] (order does not matter to either), on every thread
+template <int NW> __device__ __forceinline__ void seg_team_minmax(double (&lo)[3], double (&hi)[3], double* red, int tid)
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        for (int off = 32; off > 0; off >>= 1) { lo[k] = fmin(lo[k], __shfl_xor(lo[k], off)); hi[k] = fmax(hi[k], __shfl_xor(hi[k], off)); }
+    if (NW == 1) return;
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { red[(tid >> 6) * 6 + k] = lo[k]; red[(tid >> 6) * 6 + 3 + k] = hi[k]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        for (int w = 0; w < NW; ++w) { lo[k] = fmin(lo[k], red[w * 6 + k]); hi[k] = fmax(hi[k], red[w * 6 + 3 + k]); }
+    __syncthreads();
+}
+
+// Two-sided Jacobi rotation that annihilates A[P][Q] of the symmetric 3 x 3 matrix A; V accumulates the rotations (its columns are
+// the eigenvectors).  Indexed at compile time, as jacobi_pair above: A and V stay in registers.
+template <int P, int Q> __device__ __forceinline__ void seg_jacobi_rotate(double (&A)[9], double (&V)[9])
+{
+    constexpr int R = 3 - P - Q;
+    const double apq = A[P * 3 + Q];
+    if (apq == 0.0) return;
+    const double app = A[P * 3 + P], aqq = A[Q * 3 + Q];
+    const double a2 = aqq - app, b2 = 2.0 * apq;                // t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), theta = a2 / b2
+    const double t = (((a2 >= 0.0) == (b2 >= 0.0)) ? fabs(b2) : -fabs(b2)) / (fabs(a2) + sqrt(a2 * a2 + b2 * b2));
+    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+    A[P * 3 + P] = app - t * apq; A[Q * 3 + Q] = aqq + t * apq;
+    A[P * 3 + Q] = 0.0; A[Q * 3 + P] = 0.0;
+    const double arp = A[R * 3 + P], arq = A[R * 3 + Q];
+    A[R * 3 + P] = A[P * 3 + R] = c * arp - s * arq;
+    A[R * 3 + Q] = A[Q * 3 + R] = s * arp + c * arq;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double vp = V[r * 3 + P], vq = V[r * 3 + Q];
+        V[r * 3 + P] = c * vp - s * vq; V[r * 3 + Q] = s * vp + c * vq;
+    }
+}
+
+// sorts (|e|, column of V) pairs so that e[I] >= e[J]
+template <int I, int J> __device__ __forceinline__ void seg_order(double (&e)[3], double (&V)[9])
+{
+    if (e[I] >= e[J]) return;
+    const double t = e[I]; e[I] = e[J]; e[J] = t;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { const double v = V[r * 3 + I]; V[r * 3 + I] = V[r * 3 + J]; V[r * 3 + J] = v; }
+}
+
+// the bin of the 256-bin histogram h that holds rank r (0-based, r < the histogram's total), and the rank left inside it
+__device__ __forceinline__ void seg_find_bin(const unsigned int* h, unsigned int r, int lane, int& bin, unsigned int& rnew)
+{
+    const unsigned int c0 = h[4 * lane], c1 = h[4 * lane + 1], c2 = h[4 * lane + 2], c3 = h[4 * lane + 3];
+    const unsigned int s = c0 + c1 + c2 + c3;
+    unsigned int incl = s;
+    for (int off = 1; off < 64; off <<= 1) { const unsigned int t = (unsigned int)__shfl_up((int)incl, off); if (lane >= off) incl += t; }
+    unsigned int e = incl - s;
+    const bool hit = r >= e && r < incl;
+    int b = 4 * lane;
+    if (hit) {
+        if (r >= e + c0) { e += c0; ++b; if (r >= e + c1) { e += c1; ++b; if (r >= e + c2) { e += c2; ++b; } } }
+    }
+    const unsigned long long m = __ballot(hit);
+    const int src = m ? (int)__ffsll((long long)m) - 1 : 0;
+    bin = __shfl(b, src); rnew = (unsigned int)__shfl((int)(r - e), src);
+}
+
+// Radix select over the keys of x and of y, eight passes of eight bits from the top: the order statistics (n - 1) / 2 and n / 2 of
+// either coordinate -> their keys in L.pre[0..3] (x low, x high, y low, y high).  Integer LDS histograms only, so the result is
+// exact and any n is served with the same 4 KB.
+template <int NW>
+__device__ __forceinline__ void seg_select_medians(const double* __restrict__ pts, int64_t p0, int64_t n, SegLds<NW>& L, int tid)
+{
+    constexpr int NT = 64 * NW;
+    const int lane = tid & 63, wave = tid >> 6;
+    if (tid < 4) { L.pre[tid] = 0ull; L.rk[tid] = (unsigned int)((tid & 1) ? n / 2 : (n - 1) / 2); }
+    for (int d = 0; d < 8; ++d) {
+        const int shift = 56 - 8 * d;
+        const unsigned long long mask = d == 0 ? 0ull : (~0ull << (shift + 8));
+        for (int i = tid; i < 4 * 256; i += NT) (&L.hist[0][0])[i] = 0u;
+        seg_sync<NW>();
+        const unsigned long long pre0 = L.pre[0], pre1 = L.pre[1], pre2 = L.pre[2], pre3 = L.pre[3];
+        seg_sweep<NW>(pts, p0, n, L.stage, tid, [&](double x, double y, double) {
+            const unsigned long long kx = seg_key(x), ky = seg_key(y);
+            const unsigned int bx = (unsigned int)(kx >> shift) & 255u, by = (unsigned int)(ky >> shift) & 255u;
+            if ((kx & mask) == pre0) atomicAdd(&L.hist[0][bx], 1u);
+            if ((kx & mask) == pre1) atomicAdd(&L.hist[1][bx], 1u);
+            if ((ky & mask) == pre2) atomicAdd(&L.hist[2][by], 1u);
+            if ((ky & mask) == pre3) atomicAdd(&L.hist[3][by], 1u);
+        });
+        for (int q = (NW == 1 ? 0 : wave); q < 4; q += (NW == 1 ? 1 : NW)) {
+            int bin; unsigned int rnew;
+            seg_find_bin(L.hist[q], L.rk[q], lane, bin, rnew);
+            if (lane == 0) { L.pre[q] |= (unsigned long long)bin << shift; L.rk[q] = rnew; }
+        }
+        seg_sync<NW>();
+    }
+}
+
+template <int NW>
+__device__ __forceinline__ void seg_shape_team(const SegShapeArgs& A, int s, SegLds<NW>& L, int tid)
+{
+    const int64_t p0 = A.seg_off[s], n = A.seg_off[s + 1] - p0;
+    double* const row = A.out + (int64_t)s * A.stride;
+    if (n <= 0) {                                                // an empty segment: a zero row
+        if (tid == 0) {
+            for (int k = 0; k < 3; ++k) {
+                row[A.col_center + k] = 0.0;
+                if (A.col_pca >= 0) row[A.col_pca + k] = 0.0;
+                if (A.col_extent >= 0) row[A.col_extent + k] = 0.0;
+            }
+            if (A.col_volume >= 0) row[A.col_volume] = 0.0;
+            A.status[s] = SEG_ST_EMPTY | SEG_ST_FEW_POINTS;
+        }
+        return;
+    }
+
+    // ---- sweep 1: the mean, the smallest z by its key, and whether any point differs from the first ----
+    double sum[3] = {0.0, 0.0, 0.0};
+    unsigned long long zk = ~0ull;
+    const double f0 = A.pts[3 * p0], f1 = A.pts[3 * p0 + 1], f2 = A.pts[3 * p0 + 2];
+    int differs = 0;
+    seg_sweep<NW>(A.pts, p0, n, L.stage, tid, [&](double x, double y, double z) {
+        sum[0] += x; sum[1] += y; sum[2] += z;
+        const unsigned long long k = seg_key(z); zk = k < zk ? k : zk;
+        differs |= (int)(x != f0) | (int)(y != f1) | (int)(z != f2);
+    });
+    seg_team_sum<NW, 3>(sum, L.red, tid);
+    differs = NW == 1 ? __any(differs) : __syncthreads_or(differs);
+    // (n equal points: their mean is that point, exactly — a rounded sum / n may miss it by an ulp, and the covariance of a point
+    // cloud without extent is exactly zero, as it is in exact arithmetic)
+    const double mean[3] = {differs ? sum[0] / (double)n : f0, differs ? sum[1] / (double)n : f1, differs ? sum[2] / (double)n : f2};
+
+    // ---- sweep 2: the centred covariance (xx xy xz yy yz zz) ----
+    double cs[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    seg_sweep<NW>(A.pts, p0, n, L.stage, tid, [&](double x, double y, double z) {
+        const double dx = x - mean[0], dy = y - mean[1], dz = z - mean[2];
+        cs[0] += dx * dx; cs[1] += dx * dy; cs[2] += dx * dz; cs[3] += dy * dy; cs[4] += dy * dz; cs[5] += dz * dz;
+    });
+    seg_team_sum<NW, 6>(cs, L.red, tid);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) cs[k] /= (double)n;
+
+    // ---- eigen-decomposition in registers, the same on every thread.  The matrix is first scaled by a power of two so that its
+    // largest entry lies in [1, 2): exact, the ratios do not see it, and the squares a rotation forms (a2 * a2 + b2 * b2) can then
+    // neither underflow nor overflow, however small or large the cloud (an unscaled covariance below 1e-154 would give 0 / 0 there).
+    // Cyclic Jacobi: the off-diagonal part shrinks quadratically from sweep to sweep (1e-3, 1e-6, 1e-12, 1e-24 of the diagonal) and a
+    // rotation sets its own entry to an exact 0, so the loop ends either by the test below — 1e-18 is deliberately below the
+    // rounding unit: one sweep past working precision, so that the eigenvectors are converged as well — or by three exact zeros;
+    // twelve sweeps are a cap for inputs that are not finite, not a count ----
+    {
+        double mx = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) mx = fmax(mx, fabs(cs[k]));
+        if (mx > 0.0 && mx < INFINITY) {
+            const int ex = ilogb(mx);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) cs[k] = scalbn(cs[k], -ex);
+        }
+    }
+    double C[9] = {cs[0], cs[1], cs[2], cs[1], cs[3], cs[4], cs[2], cs[4], cs[5]};
+    double V[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < 12; ++sweep) {
+        const double off = fabs(C[1]) + fabs(C[2]) + fabs(C[5]), dia = fabs(C[0]) + fabs(C[4]) + fabs(C[8]);
+        if (off <= 1e-18 * dia) break;
+        seg_jacobi_rotate<0, 1>(C, V);
+        seg_jacobi_rotate<0, 2>(C, V);
+        seg_jacobi_rotate<1, 2>(C, V);
+    }
+    double e[3] = {fabs(C[0]), fabs(C[4]), fabs(C[8])};         // singular values, as np.linalg.svd gives them [REF roman/object/segment.py:441]
+    seg_order<0, 1>(e, V); seg_order<0, 2>(e, V); seg_order<1, 2>(e, V);
+    int st = 0;
+    if (n <= 4) st |= SEG_ST_FEW_POINTS;
+    if (e[0] == 0.0) st |= SEG_ST_DEGENERATE;
+
+    // ---- sweep 3: the box in the eigenframe [REF roman/object/segment.py:244-263] ----
+    double ext[3] = {0.0, 0.0, 0.0};
+    if (n > 4 && A.col_volume + A.col_extent > -2) {
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        seg_sweep<NW>(A.pts, p0, n, L.stage, tid, [&](double x, double y, double z) {
+            const double dx = x - mean[0], dy = y - mean[1], dz = z - mean[2];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double p = (dx * V[k] + dy * V[3 + k]) + dz * V[6 + k];
+                lo[k] = fmin(lo[k], p); hi[k] = fmax(hi[k], p);
+            }
+        });
+        seg_team_minmax<NW>(lo, hi, L.red, tid);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ext[k] = hi[k] - lo[k];
+        if (ext[0] > ext[1]) { const double t = ext[0]; ext[0] = ext[1]; ext[1] = t; }      // ascending: every consumer reads sorted(extent)
+        if (ext[1] > ext[2]) { const double t = ext[1]; ext[1] = ext[2]; ext[2] = t; }
+        if (ext[0] > ext[1]) { const double t = ext[0]; ext[0] = ext[1]; ext[1] = t; }
+    }
+
+    // ---- the centre ----
+    double cen[3] = {mean[0], mean[1], mean[2]};
+    if (A.center_ref == 1) {                                     // bottom_middle [REF roman/object/segment.py:267-270]
+        for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(zk, off); zk = o < zk ? o : zk; }
+        if (NW > 1) {
+            if ((tid & 63) == 0) L.zkey[tid >> 6] = zk;
+            __syncthreads();
+            for (int w = 0; w < NW; ++w) zk = L.zkey[w] < zk ? L.zkey[w] : zk;
+        }
+        seg_select_medians<NW>(A.pts, p0, n, L, tid);
+        const double xa = seg_unkey(L.pre[0]), xb = seg_unkey(L.pre[1]), ya = seg_unkey(L.pre[2]), yb = seg_unkey(L.pre[3]);
+        // np.median ends in a mean of the one or two middle values, a sum that starts from +0.0: a median that is a zero is +0.0
+        cen[0] = (n & 1) ? 0.0 + xa : ((0.0 + xa) + xb) * 0.5;
+        cen[1] = (n & 1) ? 0.0 + ya : ((0.0 + ya) + yb) * 0.5;
+        cen[2] = seg_unkey(zk);
+    }
+
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) row[A.col_center + k] = cen[k];
+        if (A.col_pca >= 0) {                                    // [REF roman/object/segment.py:445-472]; 0 / 0 = NaN stays NaN
+            row[A.col_pca] = (e[0] - e[1]) / e[0]; row[A.col_pca + 1] = (e[1] - e[2]) / e[0]; row[A.col_pca + 2] = e[2] / e[0];
+        }
+        if (A.col_volume >= 0) row[A.col_volume] = (ext[0] * ext[1]) * ext[2];
+        if (A.col_extent >= 0) { row[A.col_extent] = ext[0]; row[A.col_extent + 1] = ext[1]; row[A.col_extent + 2] = ext[2]; }
+        A.status[s] = st;
+    }
+}
+
+// one wave per listed segment, four to a workgroup; the waves never meet at a workgroup barrier
+__global__ void __launch_bounds__(256) k_seg_shapes_wave(SegShapeArgs A, int n_items)
+{
+    __shared__ SegLds<1> L[4];
+    const int wave = (int)threadIdx.x >> 6, it = (int)blockIdx.x * 4 + wave;
+    if (it >= n_items) return;
+    seg_shape_team<1>(A, A.items[it], L[wave], (int)threadIdx.x & 63);
+}
+
+// one workgroup per listed segment, from item `first` of the list on
+__global__ void __launch_bounds__(256) k_seg_shapes_block(SegShapeArgs A, int first)
+{
+    __shared__ SegLds<4> L;
+    seg_shape_team<4>(A, A.items[first + (int)blockIdx.x], L, (int)threadIdx.x);
+}
+
 }  // namespace roman

@@ -203,6 +203,10 @@ struct roman_ctx {
     // behind them, as 64-bit words through pinned staging (a pure enqueue)
     DevBuf sfTab;
     PinnedStage<int64_t> sfStage;
+    // segment shapes from point clouds (roman_segment_shapes*): the host-cut segment list through pinned staging (a pure enqueue)
+    DevBuf segItems;
+    PinnedStage<int32_t> segStage;
+    int seg_block_min = SEG_BLOCK_MIN;         // points from which a segment takes a workgroup (roman_ctx_set_segment_block_min)
 
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
@@ -1480,6 +1484,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     c->ggNorm.release(); c->sgCount.release();
     c->ssNorm.release(); c->ssBand.release(); c->ssR.release(); c->ssItems.release(); c->ssStage.release();
     c->sfTab.release(); c->sfStage.release();
+    c->segItems.release(); c->segStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -3389,6 +3394,97 @@ int roman_session_boxes(roman_ctx_t* c, int32_t S, int32_t F, const double* pool
                                  T.dev(), dBox.dev());
     if (rc) return rc;
     return m.download();
+}
+
+// --- segment tables from point clouds ------------------------------------------------------------------------------
+static_assert(SEG_BLOCK_MIN == ROMAN_SEG_BLOCK_MIN && SEG_ST_EMPTY == ROMAN_SEG_EMPTY && SEG_ST_FEW_POINTS == ROMAN_SEG_FEW_POINTS &&
+              SEG_ST_DEGENERATE == ROMAN_SEG_DEGENERATE, "kernels.hip.h and roman_hip.h name the same numbers");
+static_assert(sizeof(roman_segment_shape_params_t) == 32, "roman_segment_shape_params_t is eight int32 words");
+
+// everything roman_segment_shapes* judge on host memory -> *P_out: the rows of `points`
+static int segment_shapes_check(roman_ctx* c, const void* points, const int64_t* seg_off, int32_t N, const roman_segment_shape_params_t* P,
+                                const void* out, const void* status, int64_t* P_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (!P) return fail(c, ROMAN_E_INVALID, "params is NULL");
+    if (!seg_off) return fail(c, ROMAN_E_INVALID, "seg_off is NULL");
+    if (N < 0) return fail(c, ROMAN_E_INVALID, "N < 0");
+    if (seg_off[0] != 0) return fail(c, ROMAN_E_INVALID, "seg_off[0] = %lld: the first segment starts at row 0", (long long)seg_off[0]);
+    for (int32_t i = 0; i < N; ++i) {
+        if (seg_off[i + 1] < seg_off[i]) return fail(c, ROMAN_E_INVALID, "seg_off descends at segment %d", i);
+        if (seg_off[i + 1] - seg_off[i] > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "segment %d holds more than %d points", i, INT32_MAX);
+    }
+    if (P->center_ref != ROMAN_CENTER_MEAN && P->center_ref != ROMAN_CENTER_BOTTOM_MIDDLE) return fail(c, ROMAN_E_INVALID, "unknown center_ref %d", P->center_ref);
+    if (P->out_stride < 1) return fail(c, ROMAN_E_INVALID, "out_stride must be >= 1 (got %d)", P->out_stride);
+    if (P->col_center < 0) return fail(c, ROMAN_E_INVALID, "col_center = %d: the centre is always written", P->col_center);
+    if (P->col_pca < -1 || P->col_volume < -1 || P->col_extent < -1) return fail(c, ROMAN_E_INVALID, "a column is < -1 (-1: not written)");
+    const int32_t col[4] = {P->col_center, P->col_pca, P->col_volume, P->col_extent}, width[4] = {3, 3, 1, 3};
+    for (int a = 0; a < 4; ++a) {
+        if (col[a] < 0) continue;
+        if ((int64_t)col[a] + width[a] > (int64_t)P->out_stride) return fail(c, ROMAN_E_INVALID, "columns %d..%d leave out_stride = %d", col[a], col[a] + width[a] - 1, P->out_stride);
+        for (int b = 0; b < a; ++b)
+            if (col[b] >= 0 && col[a] < col[b] + width[b] && col[b] < col[a] + width[a])
+                return fail(c, ROMAN_E_INVALID, "the written columns from %d and from %d overlap", col[b], col[a]);
+    }
+    if (P->reserved[0] || P->reserved[1]) return fail(c, ROMAN_E_INVALID, "reserved words of roman_segment_shape_params_t must be 0");
+    *P_out = seg_off[N];
+    if (*P_out > 0 && !points) return fail(c, ROMAN_E_INVALID, "points is NULL");
+    if (N > 0 && (!out || !status)) return fail(c, ROMAN_E_INVALID, "out / status is NULL");
+    return ROMAN_OK;
+}
+
+int roman_segment_shapes_dev(roman_ctx_t* c, const double* points, const int64_t* seg_off_dev, const int64_t* seg_off_host, int32_t N,
+                             const roman_segment_shape_params_t* params, double* out, int32_t* status)
+{
+    int64_t P = 0;
+    int rc = segment_shapes_check(c, points, seg_off_host, N, params, out, status, &P);
+    if (rc) return rc;
+    if (N > 0 && !seg_off_dev) return fail(c, ROMAN_E_INVALID, "seg_off is NULL on the device");
+    if (N == 0) return ROMAN_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    // ---- the list, cut on the host: the segments one wave serves, then those that take a workgroup (each in map order) ----
+    int32_t* items = nullptr;
+    HIPCHK(c, c->segStage.stage((size_t)N, &items));
+    int32_t nShort = 0;
+    for (int32_t i = 0; i < N; ++i) if (seg_off_host[i + 1] - seg_off_host[i] < (int64_t)c->seg_block_min) items[nShort++] = i;
+    int32_t nLong = 0;
+    for (int32_t i = 0; i < N; ++i) if (seg_off_host[i + 1] - seg_off_host[i] >= (int64_t)c->seg_block_min) items[nShort + nLong++] = i;
+    HIPCHK(c, c->segStage.upload(c->segItems, (size_t)N, c->stream));
+    const SegShapeArgs A{points, seg_off_dev, c->segItems.as<int32_t>(), out, status, (int)params->center_ref, (int)params->out_stride,
+                         (int)params->col_center, (int)params->col_pca, (int)params->col_volume, (int)params->col_extent};
+    if (nShort) hipLaunchKernelGGL(k_seg_shapes_wave, dim3((unsigned)((nShort + 3) / 4)), dim3(256), 0, c->stream, A, (int)nShort);
+    if (nLong) hipLaunchKernelGGL(k_seg_shapes_block, dim3((unsigned)nLong), dim3(256), 0, c->stream, A, (int)nShort);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_segment_shapes(roman_ctx_t* c, const double* points, const int64_t* seg_off, int32_t N, const roman_segment_shape_params_t* params,
+                         double* out, int32_t* status)
+{
+    int64_t P = 0;
+    int rc = segment_shapes_check(c, points, seg_off, N, params, out, status, &P);
+    if (rc || N == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    HostMirror m(c);
+    const auto dPts = m.in(points, sizeof(double) * 3 * (size_t)P);
+    const auto dOff = m.in(seg_off, sizeof(int64_t) * ((size_t)N + 1));
+    const auto dOut = m.inout(out, sizeof(double) * (size_t)N * (size_t)params->out_stride);
+    const auto dSt = m.out(status, sizeof(int32_t) * (size_t)N);
+    rc = m.upload();
+    if (rc) return rc;
+    rc = roman_segment_shapes_dev(c, P ? dPts.dev() : reinterpret_cast<const double*>(dOff.dev()) /* never read: every segment is empty */, dOff.dev(),
+                                  seg_off, N, params, dOut.dev(), dSt.dev());
+    if (rc) return rc;
+    return m.download();
+}
+
+int roman_ctx_set_segment_block_min(roman_ctx_t* c, int32_t n)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    if (n < 0) return fail(c, ROMAN_E_INVALID, "n must be >= 0 (0: the default)");
+    c->seg_block_min = n ? n : SEG_BLOCK_MIN;
+    return ROMAN_OK;
 }
 
 // What the grid gate and the session gate ask of roman_grid_gate_params_t, in front of their own checks.  The caller's check of its

@@ -356,6 +356,30 @@ def frame_select_params(thin_dist=None, want_mean=False):
     return P
 
 
+def segment_shape_params(center_ref="mean", out_stride=3, col_center=0, col_pca=-1, col_volume=-1, col_extent=-1):
+    """-> roman_segment_shape_params_t.  center_ref: 'mean' / 'bottom_middle' [REF roman/object/segment.py:266-274] or a
+    ROMAN_CENTER_* number; a column of -1 is not written."""
+    P = _abi.RomanSegmentShapeParams()
+    if isinstance(center_ref, str):
+        if center_ref not in _abi.CENTER_REFS:
+            raise ValueError(f"center_ref must be one of {sorted(_abi.CENTER_REFS)} (got {center_ref!r})")
+        center_ref = _abi.CENTER_REFS[center_ref]
+    P.center_ref, P.out_stride = int(center_ref), int(out_stride)
+    P.col_center, P.col_pca, P.col_volume, P.col_extent = int(col_center), int(col_pca), int(col_volume), int(col_extent)
+    return P
+
+
+def _segment_clouds(points, seg_off):
+    """The clouds of a host-pointer call in the C ABI's types -> (points float64 (P, 3), seg_off int64 (N + 1,), N)."""
+    points = _f64(points)
+    seg_off = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError("points must be (P, 3)")
+    if seg_off.shape[0] < 1 or int(seg_off[-1]) != points.shape[0]:
+        raise ValueError("seg_off must hold N + 1 offsets and end at the number of points")
+    return points, seg_off, int(seg_off.shape[0]) - 1
+
+
 def session_frame_robot_dtype():
     """roman_session_frame_robot_t as a structured dtype."""
     return np.dtype([("seg0", np.int64), ("mask_off", np.int64), ("n_seg", np.int32), ("sub0", np.int32), ("n_sub", np.int32), ("frame0", np.int32),
@@ -1230,6 +1254,33 @@ class Context:
         """Device-pointer boxes of the submaps of a pool (roman_submap_boxes_dev): a pure enqueue on the context's stream."""
         rc = self._lib.roman_submap_boxes_dev(self._h, int(S), int(F), int(cap), _vp(pool_ptr), _vp(count_ptr), _vp(T_odom_center_ptr), _vp(box_ptr))
         self._check(rc, "roman_submap_boxes_dev")
+
+    # ------------------------------------------------------------------ segment tables from point clouds (DESIGN.md §4.24)
+    def segment_shapes(self, points, seg_off, sparams, out=None):
+        """Host-pointer centre and shape features of every segment of a map from its points (roman_segment_shapes): points (P, 3),
+        seg_off (N + 1,) ascending from 0 to P, sparams a segment_shape_params() block.  `out` (N, sparams.out_stride) float64: the
+        caller's table — the columns the block does not name come back as they were — or None for a fresh table of zeros.
+        -> (out, status (N,) int32 of ROMAN_SEG_* flags)."""
+        points, seg_off, N = _segment_clouds(points, seg_off)
+        out = _given(out, (N, int(sparams.out_stride)), np.float64, 0.0)
+        status = np.zeros(N, dtype=np.int32)
+        self._generation += 1
+        rc = self._lib.roman_segment_shapes(self._h, _ptr(points), _ptr(seg_off), N, C.byref(sparams), _ptr(out), _ptr(status))
+        self._check(rc, "roman_segment_shapes")
+        return out, status
+
+    def segment_shapes_dev(self, points_ptr, seg_off_ptr, seg_off, sparams, out_ptr, status_ptr):
+        """Device-pointer form (roman_segment_shapes_dev): points, seg_off, out and status on the device, `seg_off` the same offsets
+        on the host (the launch is sized from them).  A pure enqueue on the context's stream."""
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1)
+        if seg_off.shape[0] < 1:
+            raise ValueError("seg_off must hold N + 1 offsets")
+        self._enqueue("roman_segment_shapes_dev", _vp(points_ptr), _vp(seg_off_ptr), _ptr(seg_off), int(seg_off.shape[0]) - 1, C.byref(sparams),
+                      _vp(out_ptr), _vp(status_ptr))
+
+    def set_segment_block_min(self, n=0):
+        """Measurement only (roman_ctx_set_segment_block_min): the point count from which a segment takes a workgroup; 0: the default."""
+        self._check(self._lib.roman_ctx_set_segment_block_min(self._h, int(n)), "roman_ctx_set_segment_block_min")
 
     def grid_gate_aabb(self, gparams, box0, box1, pos0, T_w0, pos1, T_w1, time0=None, time1=None, desc0=None, desc1=None, pos_gt0=None, pos_gt1=None,
                        sim_in=None, pairs=None, T_ref=None, enable=None):
