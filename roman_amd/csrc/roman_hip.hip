@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "kernels.hip.h"
+#include "switches.h"
 
 using namespace roman;
 
@@ -345,8 +346,7 @@ struct StageTimer {
 // ROMAN_DEBUG=1: synchronise after every launch and say which one it was (locating a kernel that does not return)
 int dbg_stage(roman_ctx* c, const char* what)
 {
-    static const bool dbg = getenv("ROMAN_DEBUG") != nullptr;
-    if (!dbg) return ROMAN_OK;
+    if (!switches_once().debug) return ROMAN_OK;
     const hipError_t e = hipStreamSynchronize(WS.stream);
     fprintf(stderr, "[roman] %-14s %s\n", what, e == hipSuccess ? "ok" : hipGetErrorString(e));
     fflush(stderr);
@@ -392,7 +392,7 @@ void harvest_totals(roman_ctx* c, bool wait)
     }
 }
 
-void estimate_sizes(roman_ctx* c, const DevParams& D, const roman_params_t* params, int32_t F, const std::vector<ProbDesc>& hd, Sizing* S)
+void estimate_sizes(roman_ctx* c, const Switches& sw, const DevParams& D, const roman_params_t* params, int32_t F, const std::vector<ProbDesc>& hd, Sizing* S)
 {
     roman_ctx::Hist& H = c->hist;
     if (!H.tagged || H.F != F || memcmp(&H.params, params, sizeof(roman_params_t)) != 0) {   // other parameters: other ratios
@@ -422,10 +422,8 @@ void estimate_sizes(roman_ctx* c, const DevParams& D, const roman_params_t* para
     }
     S->capMaskWords = std::max<long long>(S->capMaskWords, 64);
     // tests: force the first attempt of a batch to overflow (exercises the skip / retry path)
-    const char* tcap = getenv("ROMAN_TEST_CAPNNZ");            // (read per call: a test sets it for some of its contexts)
-    if (tcap && !H.valid) S->capNnz = atoll(tcap);
-    const char* tlist = getenv("ROMAN_TEST_CAPLIST");          // ... or its list pool too small (k_lists' overflow: kind 2)
-    if (tlist && !H.valid) S->capList = atoll(tlist);
+    if (sw.test_capnnz_set && !H.valid) S->capNnz = sw.test_capnnz;
+    if (sw.test_caplist_set && !H.valid) S->capList = sw.test_caplist;   // ... or its list pool too small (k_lists' overflow: kind 2)
 }
 
 int may_fallback(const DevParams& D, const std::vector<ProbDesc>& hd);
@@ -487,14 +485,13 @@ static hipError_t launch_cos_flagged(roman_ctx* c, hipStream_t stream, const Dev
     return hipGetLastError();
 }
 // When: the score is the gated one (single scores on, not the pruned prefilter's raw products, cosine_max > cosine_min), maps of at most
-// CSEL_MAXN objects, and a batch that gives most compute units a problem.  ROMAN_COS_SEL=0 never, =1 whenever the results allow it (tests).
-static bool cos_sel_applies(const roman_ctx* c, const DevParams& D, int B, int maxN1, int maxN2, int64_t poolRows)
+// CSEL_MAXN objects, and a batch that gives most compute units a problem.  sw.cos_sel: never / whenever the results allow it (tests).
+static bool cos_sel_applies(const roman_ctx* c, const Switches& sw, const DevParams& D, int B, int maxN1, int maxN2, int64_t poolRows)
 {
     if (!D.single || D.pruned || !(D.p.cosine_max > D.p.cosine_min) || !std::isfinite(D.p.cosine_min) || !std::isfinite(D.p.cosine_max)) return false;
     if (maxN1 > CSEL_MAXN || maxN2 > CSEL_MAXN || maxN1 <= 0 || maxN2 <= 0) return false;
     if (poolRows * (int64_t)D.F * 8 >= (1LL << 32)) return false;         // (the exact pass addresses a row by a 32-bit byte offset into the pool)
-    const char* env = getenv("ROMAN_COS_SEL");
-    if (env && env[0]) return env[0] == '1';
+    if (sw.cos_sel != CHOICE_LIB) return sw.cos_sel == 1;
     // by itself: a batch that gives at least half the compute units a problem (one workgroup per problem; smaller batches keep the dense
     // kernels' many workgroups per problem), descriptors long enough for the two sweeps to pay, and no history of this parameter block
     // that says the screen rules out too little (a quarter of the latest screened batch left to the dense kernel: the dense kernel
@@ -510,26 +507,17 @@ static bool cos_sel_applies(const roman_ctx* c, const DevParams& D, int B, int m
 
 // ---- the launch sequence of one batch (score + solve), on workspace c->cur and its stream; never waits -------------
 
-// Positions of the stream layout: rows of one degree at most for the sort-free placement (place_keys(), kernels.hip.h); beyond, the
-// bitonic sort.  ROMAN_SORT_EQMAX=n sets it (0: always the sort — A/B, tests; read per call).
-static int sort_eq_max()
-{
-    const char* e = getenv("ROMAN_SORT_EQMAX");
-    return (e && e[0]) ? std::max(0, atoi(e)) : 512;
-}
-
 // Cosine matrices of B problems: k_cos_tile (64x64 tile per workgroup, operands through LDS) by default, k_cos_deal (80x80 tiles, blocks
 // dealt evenly to the waves) for batches of mid-size maps, k_cos_wave (one wave per problem) or k_cos_block (one wave per block) for
 // maps of at most 48 objects, k_cos_block again for a few problems of larger maps.
-static hipError_t launch_cos(roman_ctx* c, hipStream_t stream, const DevParams& D, int B, int maxN1, int maxN2, const ProbDesc* dP, const double* feats, double* cosPool)
+static hipError_t launch_cos(roman_ctx* c, const Switches& sw, hipStream_t stream, const DevParams& D, int B, int maxN1, int maxN2, const ProbDesc* dP, const double* feats, double* cosPool)
 {
     {   // a batch with at least two workgroups per compute unit of 5 x 5-block tiles: k_cos_deal (blocks dealt evenly to the waves).
-        // ROMAN_COS_DEAL=0 never, =1 always (A/B, tests; read per call)
-        const char* dealEnv = getenv("ROMAN_COS_DEAL");
+        // sw.cos_deal: never / always (A/B, tests)
         constexpr int TD = 5;
         using CD = CosDeal<TD>;
         const int Gd = CD::tiles(maxN1) * CD::tiles(maxN2);
-        const bool deal = (dealEnv && dealEnv[0]) ? dealEnv[0] == '1' : ((maxN1 > 16 * COSW_NB || maxN2 > 16 * COSW_NB) && (int64_t)Gd * B >= 2 * (int64_t)c->num_cu);
+        const bool deal = sw.cos_deal != CHOICE_LIB ? sw.cos_deal == 1 : ((maxN1 > 16 * COSW_NB || maxN2 > 16 * COSW_NB) && (int64_t)Gd * B >= 2 * (int64_t)c->num_cu);
         if (deal) {
             const hipError_t e = dyn_lds(c, reinterpret_cast<const void*>(k_cos_deal<TD, 0>), (size_t)CD::LDS);
             if (e != hipSuccess) return e;
@@ -541,9 +529,8 @@ static hipError_t launch_cos(roman_ctx* c, hipStream_t stream, const DevParams& 
         // the reference's demo scale: one wave per problem, no LDS, no barrier (k_cos_wave); up to two problems per compute unit (a
         // serial caller's one pair per call, a small batch): one wave per 16 x 16 block (k_cos_block: 31 against 80 us for one pair,
         // 75 against 127 for 256, 114 against 135 for 512, 196 against 152 for 1024 — tools/gpu_cos_block_sweep.py).
-        // ROMAN_COS_BLOCK=0 never, =1 always (A/B, tests; read per call)
-        const char* blockEnv = getenv("ROMAN_COS_BLOCK");
-        const bool perBlock = (blockEnv && blockEnv[0]) ? blockEnv[0] == '1' : B <= 2 * c->num_cu;
+        // sw.cos_block: never / always (A/B, tests)
+        const bool perBlock = sw.cos_block != CHOICE_LIB ? sw.cos_block == 1 : B <= 2 * c->num_cu;
         const int nbx = (maxN1 + 15) / 16, nby = (maxN2 + 15) / 16;
         if (perBlock) hipLaunchKernelGGL(k_cos_block, dim3((unsigned)((B * nbx * nby + 3) / 4)), dim3(256), 0, stream, D, B, nbx, nby, dP, feats, cosPool);
         else hipLaunchKernelGGL(k_cos_wave, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, D, B, dP, feats, cosPool);
@@ -552,10 +539,9 @@ static hipError_t launch_cos(roman_ctx* c, hipStream_t stream, const DevParams& 
     {
         // a few problems of larger maps (the single-pair call: 200 x 200 objects = 169 blocks): one wave per 16 x 16 block as well, eight
         // chunks of loads in flight per wave — the tile kernel below gives such a call sixteen workgroups with two stages in flight
-        // (29 us; the contraction over the descriptor is serial either way).  Up to eight waves per compute unit; ROMAN_COS_BLOCK=0: never
-        const char* blockEnv = getenv("ROMAN_COS_BLOCK");
+        // (29 us; the contraction over the descriptor is serial either way).  Up to eight waves per compute unit; !sw.cos_block_large: never
         const int nbx = (maxN1 + 15) / 16, nby = (maxN2 + 15) / 16;
-        if (!(blockEnv && blockEnv[0] == '0') && (int64_t)B * nbx * nby <= 8 * (int64_t)c->num_cu) {
+        if (sw.cos_block_large && (int64_t)B * nbx * nby <= 8 * (int64_t)c->num_cu) {
             hipLaunchKernelGGL(k_cos_block, dim3((unsigned)((B * nbx * nby + 3) / 4)), dim3(256), 0, stream, D, B, nbx, nby, dP, feats, cosPool);
             return hipGetLastError();
         }
@@ -577,6 +563,7 @@ static hipError_t launch_cos(roman_ctx* c, hipStream_t stream, const DevParams& 
 int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* params, const BatchIn& in, std::vector<ProbDesc>& hd, DevParams* Dout,
                   const BatchOut* smallOut = nullptr, const double* smallU0 = nullptr, bool mno = false /* roman_mno_batch*: every problem in the stream layout */)
 {
+    const Switches sw = read_switches();
     const int B = in.B;
     hd.assign(B, ProbDesc{});
     int64_t sumA = 0, sumCos = 0, sumTab = 0, sumQ4 = 0;
@@ -615,7 +602,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     const bool cosOn = D.p.cos_feature_dim > 0;
 
     Sizing SZ;
-    estimate_sizes(c, D, params, in.F, hd, &SZ);
+    estimate_sizes(c, sw, D, params, in.F, hd, &SZ);
     // a workspace never shrinks: keep what earlier (larger) batches made it hold
     SZ.capMaskWords = std::max(SZ.capMaskWords, WS.capMaskWords); SZ.capNnz = std::max(SZ.capNnz, WS.capNnz); SZ.capList = std::max(SZ.capList, WS.capList);
     // stream layout: as many live associations as the LDS tiles of this launch are sized for
@@ -632,17 +619,16 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     {   // Which solver takes the fallback problems: few (large) ones -> k_solve_wide, every compute unit on one problem at a
         // time; many -> k_solve, one workgroup per problem.  Decided here because the fill writes 16-bit column labels for
         // the wide solver when every position fits (10 instead of 12 bytes per entry of the stream it is bound by).
-        static const char* wideEnv = getenv("ROMAN_WIDE");      // "0": never, "1": whenever a fallback problem can exist
+        // (sw.wide: never / whenever a fallback problem can exist)
         const int mayFb = may_fallback(D, hd);
         // (many fallback problems: the teams take them when their live sets are KNOWN to be large — every association live (no single
         //  scores to remove any), or this parameter block's history says so; the first call of a gated method, whose live sets are a
         //  guess, keeps k_solve as its catch-all: no cooperative launch on the headline path)
         const bool bigLiveSets = !(D.single && !D.keep_all) || c->hist.valid;
         D.wide = (c->coop_ok && mayFb > 0 && D.p.maxiniters >= 1 && D.p.maxlsiters >= 1 && maxA <= (int64_t)WIDE_KW * c->num_cu * WIDE_NW * 64 &&
-                  (wideEnv ? wideEnv[0] == '1' : (mayFb <= std::max(1, c->num_cu / 4) || (bigLiveSets && SZ.expectMaxL >= 4608)))) ? 1 : 0;   // (several: teams of compute units, one problem each;
+                  (sw.wide != CHOICE_LIB ? sw.wide == 1 : (mayFb <= std::max(1, c->num_cu / 4) || (bigLiveSets && SZ.expectMaxL >= 4608)))) ? 1 : 0;   // (several: teams of compute units, one problem each;
                   // measured, solve stage: 128 x L = 3 600 k_solve 10.7 ms / teams 12.9; 128 x L = 4 900 29 / ~24; 128 x L = 6 400 41.6 / 31.3; 96 x L = 10 000 118 / 63)
-        const char* i16Env = getenv("ROMAN_WIDE_IDX16");         // "0": 32-bit labels always (read per call: tests)
-        D.idx16 = (D.wide && maxA <= 65534 && !(i16Env && i16Env[0] == '0')) ? 1 : 0;
+        D.idx16 = (D.wide && maxA <= 65534 && sw.wide_idx16) ? 1 : 0;                 // (!sw.wide_idx16: 32-bit labels always — tests)
     }
     *Dout = D;
 
@@ -687,7 +673,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     StageTimer t0(c, ROMAN_STAGE_SINGLE);
     bool cosScreen = false, cosLive = false;           // cosLive: k_cos_live has scored the problems it did not flag, k_live takes the flagged ones
     if (cosOn && maxN1 > 0 && maxN2 > 0) {
-        cosScreen = cos_sel_applies(c, D, B, maxN1, maxN2, poolRows);
+        cosScreen = cos_sel_applies(c, sw, D, B, maxN1, maxN2, poolRows);
         ++(cosScreen ? c->cosScreenBatches : c->cosDenseBatches);
         if (cosScreen) {
             HIPCHK(c, WS.cosDense.ensure(sizeof(int32_t) * (size_t)B));
@@ -697,7 +683,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
             else
                 HIPCHK(c, launch_cos_sel(c, WS.stream, D, B, maxN1, maxN2, dP, in.feats, WS.cosPool.as<double>(), WS.cosDense.as<int32_t>(), false));
         } else
-        HIPCHK(c, launch_cos(c, WS.stream, D, B, maxN1, maxN2, dP, in.feats, WS.cosPool.as<double>()));
+        HIPCHK(c, launch_cos(c, sw, WS.stream, D, B, maxN1, maxN2, dP, in.feats, WS.cosPool.as<double>()));
     DBG(c, "k_cos");
     }
     if (maxTab > 0) {
@@ -752,12 +738,11 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     // The one-tile sweep with candidate generation in front of the exact gate (count_rows_pre, round 6): column tile without the z
     // pairs (the exact gate reads them per object: from a table in LDS sized at the launch, or from memory) + per wave the table slices, their
     // 16-bit bin slices, the candidate queue and the rows' mask words.  Taken when the whole expected live set fits its tile;
-    // ROMAN_COUNT_PRE=0 / 1 in the environment forces the plain sweep / the prefilter where it fits (A/B and tests: read per call).
+    // sw.count_pre forces the plain sweep / the prefilter where it fits (A/B and tests).
     int preNR = 0, preWpb = 0, preTC = 0; size_t preLds = 0;
     const int preRow = (2 * std::max(maxN, 1) + 1 + 3) & ~3;                 // entries of the packed bin table (n1 + sentinel + n2)
     {
-        const char* preEnv = getenv("ROMAN_COUNT_PRE");
-        const bool want = (preEnv ? preEnv[0] != '0' : true) && D.pre_invw > 0.0 && std::isfinite(D.pre_invw) && Lneed <= (preEnv ? 16000 : 4096) && maxN <= 32767;   // (live sets beyond the stream layout's: measured slower there — 64 x L = 10 000: 5.8 against 4.0 ms with the tiled plain sweep; forced on by ROMAN_COUNT_PRE=1 up to 16 000)
+        const bool want = sw.count_pre != 0 && D.pre_invw > 0.0 && std::isfinite(D.pre_invw) && Lneed <= (sw.count_pre != CHOICE_LIB ? 16000 : 4096) && maxN <= 32767;   // (live sets beyond the stream layout's: measured slower there — 64 x L = 10 000: 5.8 against 4.0 ms with the tiled plain sweep; forced on by ROMAN_COUNT_PRE=1 up to 16 000)
         if (want) {
             const int tc = Lneed;
             for (int wp = PRE_WAVES; wp >= 8; wp -= 4) {
@@ -770,8 +755,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     StageTimer t1(c, ROMAN_STAGE_COUNT_PASS);                  // (the stage also holds k_small: at the demo scale it IS the rest of the alignment)
     {   // demo-scale problems: finished here, in one kernel (k_small); launched when such problems have been seen with this
         // parameter block (or, with no history yet, when the association lists are short enough to make them likely)
-        static const char* fusedEnv = getenv("ROMAN_SMALL_FUSED");     // "0": never (A/B)
-        const bool want = smallOut != nullptr && !(fusedEnv && fusedEnv[0] == '0') && D.p.maxiniters >= 1 && D.p.maxlsiters >= 1 && maxTab > 0 &&
+        const bool want = smallOut != nullptr && sw.small_fused /* off: never (A/B) */ && D.p.maxiniters >= 1 && D.p.maxlsiters >= 1 && maxTab > 0 &&
                           (c->hist.valid ? c->hist.smallSeen : maxA <= 16 * SMALL_MAXL);
         if (want) {
             SolveOut O;
@@ -790,8 +774,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
             // Every problem of this parameter block has so far been finished by k_small: the general kernels (twelve launches
             // that would find nothing to do: ~0.25 ms per call of 4096 problems) are left out.  A problem k_small leaves behind
             // is then skipped like a workspace overflow (ROMAN_ST_WORKSPACE) and the history remembers that they are needed.
-            static const char* onlyEnv = getenv("ROMAN_SMALL_ONLY");   // "0": never leave them out
-            D.small_only = (c->hist.valid && !c->hist.generalSeen && !(onlyEnv && onlyEnv[0] == '0')) ? 1 : 0;
+            D.small_only = (c->hist.valid && !c->hist.generalSeen && sw.small_only /* off: never leave them out */) ? 1 : 0;
             Dout->small_only = D.small_only;
         }
     }
@@ -822,17 +805,15 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
             const int wpbK = usePre ? preWpb : wpb;
             const int gridK = usePre ? c->num_cu * std::max(1, std::min(2048 / (wpbK * 64), (int)(c->lds_max / ldsK))) : pairGrid;
             // (the prefiltered sweep of a batch with at least a problem per compute unit takes whole problems as work items: RPB = -B;
-            //  ROMAN_COUNT_WHOLE=0 / 1 forces the row blocks / whole problems; + the rows' degrees in LDS then)
-            const char* wholeEnv = getenv("ROMAN_COUNT_WHOLE");
-            const bool wholeP = usePre && (wholeEnv ? wholeEnv[0] != '0' : B >= c->num_cu) && preLds + (size_t)preTC * 4 <= c->lds_max;
+            //  sw.count_whole forces the row blocks / whole problems; + the rows' degrees in LDS then)
+            const bool wholeP = usePre && (sw.count_whole != CHOICE_LIB ? sw.count_whole == 1 : B >= c->num_cu) && preLds + (size_t)preTC * 4 <= c->lds_max;
             if (wholeP) degGiven = 1;                            // k_count counts the degrees as the pairs pass: k_lists skips its degree sweep
             // (the prefiltered sweep's exact gate takes the heights of a candidate's two objects from a per-object table in LDS, one
             //  double per entry of the packed bin table, where that fits without costing a resident workgroup; from memory otherwise:
-            //  ROMAN_COUNT_ZLDS=0 forces the memory path, which maps near the LDS limit take — tests)
+            //  !sw.count_zlds forces the memory path, which maps near the LDS limit take — tests)
             size_t ldsLaunch = ldsK + (wholeP ? (size_t)preTC * 4 : 0);
             const size_t zBytes = (size_t)preRow * sizeof(double);
-            const char* zEnv = getenv("ROMAN_COUNT_ZLDS");
-            const bool zLds = usePre && D.gmode != 0 && !(zEnv && zEnv[0] == '0') && ldsLaunch + zBytes <= c->lds_max &&
+            const bool zLds = usePre && D.gmode != 0 && sw.count_zlds && ldsLaunch + zBytes <= c->lds_max &&
                               c->lds_max / (ldsLaunch + zBytes) >= std::min<size_t>(gridK / c->num_cu, c->lds_max / ldsLaunch);
             if (zLds) ldsLaunch += zBytes;
             HIPCHK(c, dyn_lds(c, kc, ldsLaunch));
@@ -849,15 +830,14 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
     DBG(c, "k_count");
         // Stream-layout problems (kind 0) go from the upper blocks straight to positions and kept-candidate lists in ONE kernel, one
         // workgroup per problem (k_lists, round 5); the symmetric matrix and its four kernels remain for the fallback layout's
-        // problems — launched only when such problems can occur — and, with ROMAN_LISTS=0 in the environment, for everything (A/B).
+        // problems — launched only when such problems can occur — and, with sw.lists forced off, for everything (A/B).
         // (a handful of problems — the single-pair call — keep the four kernels: they spread ONE problem over the device, k_lists
         //  gives it one compute unit: 0.59 against 0.66 ms for B = 1)
-        const char* listsEnv = getenv("ROMAN_LISTS");           // "0": never, "1": always (A/B and tests: read per call)
-        const int fusedLists = listsEnv ? (listsEnv[0] == '0' ? 0 : 1) : (B >= std::max(8, c->num_cu / 8) ? 1 : 0);
+        const int fusedLists = sw.lists != CHOICE_LIB ? sw.lists : (B >= std::max(8, c->num_cu / 8) ? 1 : 0);      // (sw.lists: never / always — A/B and tests)
         if (fusedLists) {
             // The LDS the kernel leaves (~83 KB of 160: one workgroup per compute unit either way, by its registers) holds the window of
             // list entries it builds in place and writes out in whole quads; entries beyond it are stored where they go, one at a time.
-            // ROMAN_LISTS_LDS=n: a window of n bytes instead (0: none — every entry stored on its own, A/B).
+            // sw.lists_lds = n: a window of n bytes instead (0: none — every entry stored on its own, A/B).
             // Probe of round 6: behind the prefiltered k_count with whole problems as work items k_lists takes 162-165 us in some
             // processes and 192-210 us in others (every launch of a process alike; identical instruction and byte counters,
             // SQ_WAIT_INST_ANY 122 M -> 190-220 M wave-cycles; behind the plain sweep or row-block work items always 160-169 us).  NOT the
@@ -869,13 +849,12 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
                 HIPCHK(c, hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_lists)));
                 listsStatic = std::max<size_t>(fa.sharedSizeBytes, 1);
             }
-            const char* llEnv = getenv("ROMAN_LISTS_LDS");
             const size_t room = c->lds_max > listsStatic ? c->lds_max - listsStatic : 0;
-            const size_t winBytes = std::min(room, llEnv ? (size_t)std::max(0, atoi(llEnv)) : room) & ~(size_t)15;
+            const size_t winBytes = std::min(room, sw.lists_lds >= 0 ? (size_t)sw.lists_lds : room) & ~(size_t)15;
             if (winBytes) HIPCHK(c, dyn_lds(c, reinterpret_cast<const void*>(k_lists), winBytes));
             hipLaunchKernelGGL(k_lists, dim3((unsigned)std::max(1, std::min(B, 2 * c->num_cu))), dim3(LISTS_NT), winBytes, WS.stream, B, dP, dS, dT,
                                WS.maskPool.as<unsigned long long>(), WS.listPool.as<uint16_t>(), WS.listOff.as<uint32_t>(),
-                               WS.rowCnt.as<uint32_t>(), WS.perm.as<uint32_t>(), WS.rowPos.as<uint32_t>(), LP, PP, (long long)SZ.capList, sort_eq_max(), degGiven,
+                               WS.rowCnt.as<uint32_t>(), WS.perm.as<uint32_t>(), WS.rowPos.as<uint32_t>(), LP, PP, (long long)SZ.capList, sw.sort_eq_max, degGiven,
                                (int)(winBytes / sizeof(uint16_t)));
     DBG(c, "k_lists");
         }
@@ -896,7 +875,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
         int sortThr = 1024;
         if (!D.allow_fallback) { int N2 = 64; while (N2 < expL) N2 <<= 1; sortThr = std::max(64, std::min(1024, N2 / 2)); }
         hipLaunchKernelGGL(k_rowsort, dim3(B), dim3(sortThr), 0, WS.stream, dP, dS, dT, WS.rowCnt.as<uint32_t>(), WS.rowPos.as<uint32_t>(), WS.perm.as<uint32_t>(),
-                           WS.sliceWidth.as<uint32_t>(), WS.sliceBase.as<uint32_t>(), WS.listOff.as<uint32_t>(), SZ.capList, fusedLists, sort_eq_max());
+                           WS.sliceWidth.as<uint32_t>(), WS.sliceBase.as<uint32_t>(), WS.listOff.as<uint32_t>(), SZ.capList, fusedLists, sw.sort_eq_max);
     DBG(c, "k_rowsort");
         if (!fusedLists) {
         // small live sets (the reference's demo scale): a work item is a whole problem of a few dozen rows — more, smaller
@@ -997,6 +976,7 @@ int enqueue_score(roman_ctx* c, const DevParams& Din, const roman_params_t* para
 int enqueue_solve(roman_ctx* c, const DevParams& D, int B, int64_t sumA, int64_t maxA /* longest association list */, const double* feats, const int32_t* assoc,
                   const double* u0, bool hascz, int mayFallback /* problems that can be of the fallback kind */, const BatchOut& out)
 {
+    const Switches sw = read_switches();
     const size_t R1 = (size_t)std::max<int64_t>(sumA, 1);
     SolveOut O;
     { int rc_ = make_solve_out(c, B, sumA, out, &O); if (rc_) return rc_; }
@@ -1028,8 +1008,7 @@ int enqueue_solve(roman_ctx* c, const DevParams& D, int B, int64_t sumA, int64_t
     // instantiation; it is launched when such problems have been seen with this parameter block (or, with no history
     // yet, when the association lists are short enough to make them likely).  The general launch takes the rest — and
     // everything when the small one is not part of the batch.
-    static const char* smallEnv = getenv("ROMAN_SMALL");        // "0": never
-    const bool small = !(smallEnv && smallEnv[0] == '0') && D.p.maxiniters >= 1 && D.p.maxlsiters >= 1 &&
+    const bool small = sw.small /* off: never */ && D.p.maxiniters >= 1 && D.p.maxlsiters >= 1 &&
                        (c->hist.valid ? c->hist.smallSeen : maxA <= 16 * SMALL_MAXL);
     const int Lc1 = SMALL_MAXL + 64;
     const size_t ldsUp1 = (size_t)3 * 8 * Lc1 + sizeof(double) * red_doubles(1) + sizeof(uint32_t) * (ST_MAXSL + 2) + sizeof(int) * 8 + 16 + (size_t)COO_CAP * 12;
@@ -1085,9 +1064,9 @@ int enqueue_solve(roman_ctx* c, const DevParams& D, int B, int64_t sumA, int64_t
                     // smaller after all, its problems keep their ROMAN_ST_INTERNAL records and run again on the whole device (align_chunked)
                     if (a_teams == 2 && mayFallback > 18 && G == c->num_cu && maxA <= (int64_t)WIDE_KW * (perXcd / 3) * WIDE_NW * 64) a_teams = 3;
                 }
-                const char* teamEnv = getenv("ROMAN_WIDE_TEAMS");          // experiments / tests: 0 never, 1 / 2 / 4 teams per XCD whenever the live sets fit (read per call)
-                const int forced = teamEnv ? atoi(teamEnv) : c->wide_teams;
-                if (teamEnv || c->wide_teams >= 0) a_teams = (forced >= 1 && forced <= 4 && mayFallback >= 1 && maxA <= cap(forced)) ? forced : 0;
+                // sw.wide_teams (experiments / tests; before roman_ctx_set_wide_teams): 0 never, 1 / 2 / 4 teams per XCD whenever the live sets fit
+                const int forced = sw.wide_teams_set ? sw.wide_teams : c->wide_teams;
+                if (sw.wide_teams_set || c->wide_teams >= 0) a_teams = (forced >= 1 && forced <= 4 && mayFallback >= 1 && maxA <= cap(forced)) ? forced : 0;
             }
             if (a_teams) c->teams_launched = true;
             const int nTeams = a_teams ? 8 * a_teams : 1;       // (teams are numbered XCC_ID * teams-per-XCD + sub-team: 8 XCC ids whatever the partition)
@@ -1096,9 +1075,9 @@ int enqueue_solve(roman_ctx* c, const DevParams& D, int B, int64_t sumA, int64_t
             // an instantiation of its own, k_solve_wide<uint16_t, true>): taken where it was measured faster than the plain kernel — TEAMS on live
             // sets of at least 8 000 associations (break-even ~7 700: L = 7 225 19.1 -> 19.9, L = 8 100 25.8 -> 24.9, L = 9 025 30.0 -> 27.7; 64 x L = 10 000: 39.7 -> 36.6 ms of solve, 96 x: 55.8 -> 52.6, 24 x: 15.9 -> 14.4; L = 8 100:
             // 26.6 -> 25.8) —, not below (L = 4 900: 10.0 -> 12.2, L = 6 400: 27.5 -> 31.3: its passes outside the copy cost more registers and a
-            // longer collect) and not with the whole device on one problem (n = m = 200: 22.8 -> 22.4).  ROMAN_WIDE_UPPER=0 / 1 forces either.
+            // longer collect) and not with the whole device on one problem (n = m = 200: 22.8 -> 22.4).  sw.wide_upper forces either.
             int a_ucfg = (D.idx16 && a_teams > 0 && maxA >= 8000) ? 1 : 0;
-            { const char* e_ = getenv("ROMAN_WIDE_UPPER"); if (e_ && e_[0]) a_ucfg = (D.idx16 && e_[0] != '0') ? 1 : 0; }
+            if (sw.wide_upper != CHOICE_LIB) a_ucfg = (D.idx16 && sw.wide_upper == 1) ? 1 : 0;
             long long a_partStride = (long long)(((size_t)NWGt * WIDE_MAXCH + (size_t)(a_ucfg ? WIDE_MAXBLK : 1) * ((size_t)(maxA + 63) / 64) + 4) * 64 * 2);   // pieces: chunks + slices (per column block of the half copy)
             HIPCHK(c, WS.widePart.ensure(sizeof(double) * (size_t)a_partStride * (size_t)nTeams));
             HIPCHK(c, WS.wideSlots.ensure(sizeof(double) * 2 * (size_t)G * WIDE_NRED * (size_t)nTeams));
@@ -1124,9 +1103,9 @@ int enqueue_solve(roman_ctx* c, const DevParams& D, int B, int64_t sumA, int64_t
             if (a_xcap < 0) a_xcap = 0;
             const size_t wideLds = sizeof(double) * (size_t)a_xcap + (size_t)wideFixed;
             // Column compaction (kernels.hip.h, k_solve_wide): a mirror of the matrix pools holds the compacted copy.
-            // ROMAN_WIDE_COMPACT=0 turns it off; =0xWWTTCC sets passes per window / threshold (x/256) / compactions allowed per problem.
+            // sw.wide_compact = 0 turns it off; = 0xWWTTCC sets passes per window / threshold (x/256) / compactions allowed per problem.
             int a_ccfg = 6 | (128 << 8) | (4 << 16);
-            { const char* e_ = getenv("ROMAN_WIDE_COMPACT"); if (e_ && e_[0]) a_ccfg = (int)strtol(e_, nullptr, 0); }
+            if (sw.wide_compact_set) a_ccfg = sw.wide_compact;
             // the pushed sums of the half copy's column blocks (one slot per workgroup of a team) and its slice widths
             int a_ySlots = NWGt / WIDE_NW;
             int a_ycap = a_ucfg ? ((a_xcap / 3) & ~63) : 0;
@@ -1246,9 +1225,8 @@ int run_batch(roman_ctx* c, const DevParams& D0, const roman_params_t* params, c
 bool batch_overflowed(roman_ctx* c)
 {
     harvest_totals(c, true);
-    static const bool dbg = getenv("ROMAN_DEBUG") != nullptr;
     const BatchTotals& t = *WS.pinnedTotals;
-    if (dbg) fprintf(stderr, "[roman] batch totals: R=%d maxL=%d items=%d maskWords need %lld cap %lld, nnz need %lld cap %lld, list need %llu cap %lld, overflow=%d sliceGroups=%d\n",
+    if (switches_once().debug) fprintf(stderr, "[roman] batch totals: R=%d maxL=%d items=%d maskWords need %lld cap %lld, nnz need %lld cap %lld, list need %llu cap %lld, overflow=%d sliceGroups=%d\n",
                      t.R, t.maxL, t.items, (long long)t.needMaskWords, WS.capMaskWords, (long long)t.needNnz, WS.capNnz, t.listTop, WS.capList, t.overflow, t.sliceGroups);
     return t.overflow > 0;
 }
@@ -1410,11 +1388,12 @@ int roman_ctx_create(roman_ctx_t** out, int device, void* stream)
     roman_ctx* c = new (std::nothrow) roman_ctx();
     if (!c) return fail(nullptr, ROMAN_E_NOMEM, "out of host memory");
     c->device = device;
+    const Switches sw = read_switches();
     c->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     {   // XCDs of this device (8 on an MI355X in SPX mode, 1 in CPX mode): the team mode of k_solve_wide sizes a team's buffers from it
         int nx = 0;
         if (hipDeviceGetAttribute(&nx, hipDeviceAttributeNumberOfXccs, device) != hipSuccess || nx < 1 || nx > 8) { (void)hipGetLastError(); nx = 8; }
-        if (const char* e = getenv("ROMAN_NUM_XCC")) { const int v = atoi(e); if (v >= 1 && v <= 64) nx = v; }   // test hook: a host-side count that does not match the device's
+        if (sw.num_xcc) nx = sw.num_xcc;                           // test hook: a host-side count that does not match the device's
         c->num_xcc = nx;
     }
     c->lds_max = prop.sharedMemPerBlock >= 163840 ? (size_t)(160 * 1024 - 256) : (size_t)prop.sharedMemPerBlock;
@@ -1436,7 +1415,7 @@ int roman_ctx_create(roman_ctx_t** out, int device, void* stream)
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || khz <= 0) { (void)hipGetLastError(); khz = 100000; }
         double ms = 4000.0;
-        if (const char* e = getenv("ROMAN_WIDE_SPIN_MS")) { const double v = atof(e); if (v >= 0.0) ms = v; }   // test hook (0: the first unsuccessful poll of a wait is a timeout)
+        if (sw.wide_spin_ms >= 0.0) ms = sw.wide_spin_ms;          // test hook (0: the first unsuccessful poll of a wait is a timeout)
         c->spin_ticks = (unsigned long long)((double)khz * ms);
     }
     if (stream) { c->stream = (hipStream_t)stream; c->own_stream = false; }
@@ -4772,7 +4751,7 @@ int roman_set_matrix_data(roman_ctx_t* c, const roman_params_t* params, const do
         hipLaunchKernelGGL(k_rowprefix, dim3(c->num_cu * 2), dim3(1024), 0, WS.stream, dP, dS, dT, WS.items.as<ItemDesc>(),
                            WS.maskPool.as<unsigned long long>(), WS.prefPool.as<uint32_t>(), WS.rowCnt.as<uint32_t>(), RPB, 0);
         hipLaunchKernelGGL(k_rowsort, dim3(1), dim3(1024), 0, WS.stream, dP, dS, dT, WS.rowCnt.as<uint32_t>(), WS.rowPos.as<uint32_t>(), WS.perm.as<uint32_t>(),
-                           WS.sliceWidth.as<uint32_t>(), WS.sliceBase.as<uint32_t>(), WS.listOff.as<uint32_t>(), capList, 0, sort_eq_max());
+                           WS.sliceWidth.as<uint32_t>(), WS.sliceBase.as<uint32_t>(), WS.listOff.as<uint32_t>(), capList, 0, read_switches().sort_eq_max);
         if (up) {
             hipLaunchKernelGGL(k_upper, dim3(c->num_cu * 2), dim3(1024), 0, WS.stream, dP, dS, dT, WS.items.as<ItemDesc>(),
                                WS.maskPool.as<unsigned long long>(), WS.listPool.as<uint16_t>(), WS.listOff.as<uint32_t>(),
@@ -4984,13 +4963,13 @@ int roman_debug_cosine(roman_ctx_t* c, const roman_params_t* params, const doubl
     HIPCHK(c, WS.probs.ensure(sizeof(ProbDesc)));
     HIPCHK(c, WS.cosPool.ensure(sizeof(double) * (size_t)n1 * n2));
     HIPCHK(c, hipMemcpyAsync(WS.probs.p, &pd, sizeof(pd), hipMemcpyHostToDevice, WS.stream));
-    // ROMAN_COS_SEL=approx / gated (tests): k_cos_sel's screen matrix / k_cos_sel's matrix (exact where cos >= cosine_min - 2^-6, the screen elsewhere)
-    const char* selEnv = getenv("ROMAN_COS_SEL");
-    if (selEnv && (!strcmp(selEnv, "approx") || !strcmp(selEnv, "gated")) && n1 <= CSEL_MAXN && n2 <= CSEL_MAXN) {
+    // sw.cos_sel_matrix approx / gated (tests): k_cos_sel's screen matrix / k_cos_sel's matrix (exact where cos >= cosine_min - 2^-6, the screen elsewhere)
+    const Switches sw = read_switches();
+    if (sw.cos_sel_matrix && n1 <= CSEL_MAXN && n2 <= CSEL_MAXN) {
         HIPCHK(c, WS.cosDense.ensure(sizeof(int32_t)));
-        HIPCHK(c, launch_cos_sel(c, WS.stream, D, 1, n1, n2, WS.probs.as<ProbDesc>(), WS.hFeats.as<double>(), WS.cosPool.as<double>(), WS.cosDense.as<int32_t>(), selEnv[0] == 'a'));
+        HIPCHK(c, launch_cos_sel(c, WS.stream, D, 1, n1, n2, WS.probs.as<ProbDesc>(), WS.hFeats.as<double>(), WS.cosPool.as<double>(), WS.cosDense.as<int32_t>(), sw.cos_sel_matrix == COS_SEL_APPROX));
     } else
-    HIPCHK(c, launch_cos(c, WS.stream, D, 1, n1, n2, WS.probs.as<ProbDesc>(), WS.hFeats.as<double>(), WS.cosPool.as<double>()));
+    HIPCHK(c, launch_cos(c, sw, WS.stream, D, 1, n1, n2, WS.probs.as<ProbDesc>(), WS.hFeats.as<double>(), WS.cosPool.as<double>()));
     HIPCHK(c, hipMemcpyAsync(out, WS.cosPool.p, sizeof(double) * (size_t)n1 * n2, hipMemcpyDeviceToHost, WS.stream));
     HIPCHK(c, hipStreamSynchronize(WS.stream));
     c->last.scored = false; c->last.solved = false;
