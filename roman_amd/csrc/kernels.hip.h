@@ -7492,8 +7492,20 @@ __global__ void __launch_bounds__(256) k_shared_gather(int F, const GatherJob* _
 constexpr int SUBMAP_NT = 256;
 constexpr int SUBMAP_LDS_CAND = 4096;                            // candidates of a submap held in LDS (8 + 4 bytes each)
 
-// (the per-submap bodies below serve k_submap_* and their session forms k_session_submap_* alike — DESIGN.md §4.19 —, as grid_pair()
-// serves k_grid_gate and k_session_gate: one statement of the arithmetic, so the two forms cannot drift apart)
+// ONE kernel set serves every form: a single map is a session of one map.  The R segment tables
+// lie concatenated in map order, and the HOST stages one record per LAUNCHED submap — its centre, the first segment row of its map, the
+// map's rows, the start of its spill slice, its output slot —: one uniform load, no search, and the spill offset (a prefix over
+// S_r * max(N_r - SUBMAP_LDS_CAND, 0)) has no closed form a workgroup could compute anyway.  Everything a workgroup does for its
+// submap runs over ITS map's rows only: src holds map-local indices.
+struct SubmapJob {
+    roman_submap_desc_t D;   // the centre as the caller prepared it
+    int64_t seg0;            // first row of the submap's map in the concatenated tables (seg_off[r]; 0 for a single map)
+    int64_t spill0;          // first entry of the submap's slice of the spill
+    int32_t N;               // rows of the map (seg_off[r + 1] - seg_off[r])
+    int32_t slot;            // the global submap index g the record serves: its place in every output (the list forms read it: their grid runs
+                             // over the listed submaps, not over the slots; everywhere else job b serves slot b)
+};
+
 // centre i of a table of F-double rows into the dense array
 __device__ __forceinline__ void submap_point_one(int64_t i, int F, const double* __restrict__ feats, double* __restrict__ pts)
 {
@@ -7501,7 +7513,7 @@ __device__ __forceinline__ void submap_point_one(int64_t i, int F, const double*
     pts[3 * i] = r[0]; pts[3 * i + 1] = r[1]; pts[3 * i + 2] = r[2];
 }
 
-__global__ void __launch_bounds__(256) k_submap_points(int N, int F, const double* __restrict__ feats, double* __restrict__ pts)
+__global__ void __launch_bounds__(256) k_submap_points(int64_t N, int F, const double* __restrict__ feats, double* __restrict__ pts)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
@@ -7578,16 +7590,18 @@ __device__ __forceinline__ void submap_select_one(const roman_submap_params_t& P
     }
 }
 
-__global__ void __launch_bounds__(SUBMAP_NT) k_submap_select(roman_submap_params_t P, int S, int N, const roman_submap_desc_t* __restrict__ descs,
+// Workgroup b serves job b and writes count[b], src[b * cap ..] and status[b]: the caller's arrays where job b is slot b, a scratch of
+// the context in the list forms, whose k_submap_store_list then writes slot jobs[b].slot from there.
+__global__ void __launch_bounds__(SUBMAP_NT) k_submap_select(roman_submap_params_t P, int n, const SubmapJob* __restrict__ jobs,
                                                              const double* __restrict__ pts, const double* __restrict__ times,
-                                                             double* spillKey, int32_t* spillIdx, int64_t spillStride,
+                                                             double* spillKey, int32_t* spillIdx,
                                                              int32_t* __restrict__ count, int32_t* __restrict__ src, int32_t* __restrict__ status)
 {
-    const int s = blockIdx.x;
-    if (s >= S) return;
-    const roman_submap_desc_t D = descs[s];
-    submap_select_one(P, D, N, pts, times, spillKey + (int64_t)s * spillStride, spillIdx + (int64_t)s * spillStride,
-                      count + s, src + (int64_t)s * P.cap, status + s);
+    const int b = blockIdx.x;
+    if (b >= n) return;
+    const SubmapJob J = jobs[b];                                 // (uniform: the whole workgroup serves one submap of one map)
+    submap_select_one(P, J.D, J.N, pts + 3 * J.seg0, times + 2 * J.seg0, spillKey + J.spill0, spillIdx + J.spill0,
+                      count + b, src + (int64_t)b * P.cap, status + b);
 }
 
 // One word (or 16-byte pair) of an output slot.  CMP (the list forms): the OLD value is read before the new one is
@@ -7633,18 +7647,22 @@ __device__ __forceinline__ bool submap_gather_row(int point_dim, int F, const do
     return diff;
 }
 
-// grid (submaps, row groups); a wave per selected row
-__global__ void __launch_bounds__(256) k_submap_gather(int point_dim, int cap, int F, const roman_submap_desc_t* __restrict__ descs,
+// grid (submaps of all maps, row groups); a wave per selected row.  The 16-byte phase is read off the addresses in submap_gather_row:
+// a map's first row sits at seg0 * F * 8 bytes, 8 mod 16 for odd seg0 * F.
+__global__ void __launch_bounds__(256) k_submap_gather(int point_dim, int cap, int F, const SubmapJob* __restrict__ jobs,
                                                        const unsigned long long* __restrict__ feats, const int64_t* __restrict__ ids,
                                                        const int32_t* __restrict__ count, const int32_t* __restrict__ src,
                                                        unsigned long long* __restrict__ pool, int64_t* __restrict__ ids_out)
 {
-    const int s = blockIdx.x;
+    const int g = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = count[s];
+    const int n = count[g];
+    const int64_t seg0 = jobs[g].seg0;
+    const unsigned long long* mfeats = feats + seg0 * F;
+    const int64_t* mids = ids ? ids + seg0 : nullptr;
     for (int r = blockIdx.y * 4 + wave; r < n; r += 4 * gridDim.y) {
-        const int64_t row = (int64_t)s * cap + r;
-        submap_gather_row(point_dim, F, descs[s].T_center_odom, feats, ids, src[row], row, pool, ids_out, lane);
+        const int64_t row = (int64_t)g * cap + r;
+        submap_gather_row(point_dim, F, jobs[g].D.T_center_odom, mfeats, mids, src[row], row, pool, ids_out, lane);
     }
 }
 
@@ -7662,100 +7680,21 @@ __device__ __forceinline__ void submap_desc_one(int F, int d, int c, const doubl
     desc[c] = submap_desc_col(F, d, c, feats, rows, n);
 }
 
-// grid (submaps, column groups): desc_out[s][c] = (sum over the rows of submap s, in output order, of descriptor column c) / count
-__global__ void __launch_bounds__(256) k_submap_desc(int cap, int F, int d, const double* __restrict__ feats, const int32_t* __restrict__ count,
-                                                     const int32_t* __restrict__ src, double* __restrict__ desc_out)
-{
-    const int s = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
-    const int n = count[s];
-    if (c >= d || n == 0) return;                                // an empty submap's descriptor is left as it was
-    submap_desc_one(F, d, c, feats, src + (int64_t)s * cap, n, desc_out + (int64_t)s * d);
-}
-
-// The same four over the maps of a SESSION (roman_session_submaps*): the R segment tables concatenated in map order,
-// one grid over the submaps of all maps.  A workgroup finds its map through the record the HOST stages per global submap g — the first
-// segment row of its map, the map's rows, the start of the submap's spill slice —: one 24-byte uniform load, no search, and the spill
-// offset (a prefix over S_r * max(N_r - SUBMAP_LDS_CAND, 0)) has no closed form a workgroup could compute anyway.  Everything a
-// workgroup does for its submap is the body above, over ITS map's rows only: src holds map-local indices, and every written byte
-// is what k_submap_* writes for that map alone.
-struct SessionSubmap {
-    int64_t seg0;            // first row of the submap's map in the concatenated tables (seg_off[r])
-    int64_t spill0;          // first entry of the submap's slice of the spill
-    int32_t N;               // rows of the map (seg_off[r + 1] - seg_off[r])
-    int32_t slot;            // the global submap index g the record serves: its place in every output (the list forms read it: their grid runs
-                             // over the listed submaps, not over the slots)
-};
-
-__global__ void __launch_bounds__(256) k_session_submap_points(int64_t N, int F, const double* __restrict__ feats, double* __restrict__ pts)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
-    submap_point_one(i, F, feats, pts);
-}
-
-__global__ void __launch_bounds__(SUBMAP_NT) k_session_submap_select(roman_submap_params_t P, int S, const SessionSubmap* __restrict__ tab,
-                                                                     const roman_submap_desc_t* __restrict__ descs,
-                                                                     const double* __restrict__ pts, const double* __restrict__ times,
-                                                                     double* spillKey, int32_t* spillIdx,
-                                                                     int32_t* __restrict__ count, int32_t* __restrict__ src, int32_t* __restrict__ status)
-{
-    const int g = blockIdx.x;
-    if (g >= S) return;
-    const SessionSubmap M = tab[g];                              // (uniform: the whole workgroup serves one submap of one map)
-    const roman_submap_desc_t D = descs[g];
-    submap_select_one(P, D, M.N, pts + 3 * M.seg0, times + 2 * M.seg0, spillKey + M.spill0, spillIdx + M.spill0,
-                      count + g, src + (int64_t)g * P.cap, status + g);
-}
-
-// grid (submaps of all maps, row groups).  The 16-byte phase is read off the addresses in submap_gather_row: a map's first row sits at
-// seg0 * F * 8 bytes, 8 mod 16 for odd seg0 * F.
-__global__ void __launch_bounds__(256) k_session_submap_gather(int point_dim, int cap, int F, const SessionSubmap* __restrict__ tab,
-                                                               const roman_submap_desc_t* __restrict__ descs,
-                                                               const unsigned long long* __restrict__ feats, const int64_t* __restrict__ ids,
-                                                               const int32_t* __restrict__ count, const int32_t* __restrict__ src,
-                                                               unsigned long long* __restrict__ pool, int64_t* __restrict__ ids_out)
-{
-    const int g = blockIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = count[g];
-    const int64_t seg0 = tab[g].seg0;
-    const unsigned long long* mfeats = feats + seg0 * F;
-    const int64_t* mids = ids ? ids + seg0 : nullptr;
-    for (int r = blockIdx.y * 4 + wave; r < n; r += 4 * gridDim.y) {
-        const int64_t row = (int64_t)g * cap + r;
-        submap_gather_row(point_dim, F, descs[g].T_center_odom, mfeats, mids, src[row], row, pool, ids_out, lane);
-    }
-}
-
-// grid (submaps of all maps, column groups)
-__global__ void __launch_bounds__(256) k_session_submap_desc(int cap, int F, int d, const SessionSubmap* __restrict__ tab, const double* __restrict__ feats,
-                                                             const int32_t* __restrict__ count, const int32_t* __restrict__ src, double* __restrict__ desc_out)
+// grid (submaps of all maps, column groups): desc_out[g][c] = (sum over the rows of submap g, in output order, of descriptor column c) / count
+__global__ void __launch_bounds__(256) k_submap_desc(int cap, int F, int d, const SubmapJob* __restrict__ jobs, const double* __restrict__ feats,
+                                                     const int32_t* __restrict__ count, const int32_t* __restrict__ src, double* __restrict__ desc_out)
 {
     const int g = blockIdx.x, c = blockIdx.y * blockDim.x + threadIdx.x;
     const int n = count[g];
     if (c >= d || n == 0) return;                                // an empty submap's descriptor is left as it was
-    submap_desc_one(F, d, c, feats + tab[g].seg0 * F, src + (int64_t)g * cap, n, desc_out + (int64_t)g * d);
+    submap_desc_one(F, d, c, feats + jobs[g].seg0 * F, src + (int64_t)g * cap, n, desc_out + (int64_t)g * d);
 }
 
 // The LIST forms (roman_session_submaps_list*): only the L listed submaps of the session are rebuilt, each WHOLE —
-// a submap may shrink —, and the call reports which slots changed.  `tab` and `descs` hold the L LISTED submaps' records (tab[l].slot
-// is the global index g), the grids run over L.  The select writes count, status and the ordered indices of listed submap l into a
-// scratch of the context (newCount[l], newStatus[l], newSrc[l * cap ..]) through the unchanged submap_select_one; the store kernel
-// then writes slot g from there.  The dense centres come from k_session_submap_points over the maps that have a listed submap.
-__global__ void __launch_bounds__(SUBMAP_NT) k_session_submap_select_list(roman_submap_params_t P, int L, const SessionSubmap* __restrict__ tab,
-                                                                          const roman_submap_desc_t* __restrict__ descs,
-                                                                          const double* __restrict__ pts, const double* __restrict__ times,
-                                                                          double* spillKey, int32_t* spillIdx,
-                                                                          int32_t* __restrict__ newCount, int32_t* __restrict__ newSrc, int32_t* __restrict__ newStatus)
-{
-    const int l = blockIdx.x;
-    if (l >= L) return;
-    const SessionSubmap M = tab[l];
-    const roman_submap_desc_t D = descs[l];
-    submap_select_one(P, D, M.N, pts + 3 * M.seg0, times + 2 * M.seg0, spillKey + M.spill0, spillIdx + M.spill0,
-                      newCount + l, newSrc + (int64_t)l * P.cap, newStatus + l);
-}
-
+// a submap may shrink —, and the call reports which slots changed.  `jobs` holds the L LISTED submaps' records (jobs[l].slot is the
+// global index g), the grids run over L.  k_submap_select writes count, status and the ordered indices of listed submap l into a
+// scratch of the context (newCount[l], newStatus[l], newSrc[l * cap ..]); the store kernel then writes slot g from there.  The dense
+// centres come from k_submap_points over the maps that have a listed submap.
 // The wave's work for ONE row of a listed slot beyond its count: the values the Python layer clears its tensors to (pool 0.0, id -1),
 // with submap_gather_row's 16-byte phase logic on the destination: a leading word when the row starts odd, pairs, a trailing word.
 template <bool CMP>
@@ -7779,27 +7718,26 @@ __device__ __forceinline__ bool submap_clear_row(int Fo, int64_t row, unsigned l
 // before it stores the new one.  changed[l]: whether any thread saw a difference — one __syncthreads_or and one plain store, so the
 // flag does not depend on any order.  Nothing of an unlisted slot is read or written.
 template <bool CMP>
-__global__ void __launch_bounds__(256) k_session_submap_store_list(int point_dim, int cap, int F, int d, const SessionSubmap* __restrict__ tab,
-                                                                   const roman_submap_desc_t* __restrict__ descs,
-                                                                   const unsigned long long* __restrict__ feats, const int64_t* __restrict__ ids,
-                                                                   const int32_t* __restrict__ newCount, const int32_t* __restrict__ newSrc,
-                                                                   const int32_t* __restrict__ newStatus,
-                                                                   unsigned long long* __restrict__ pool, int32_t* __restrict__ count, int32_t* __restrict__ src,
-                                                                   int64_t* __restrict__ ids_out, int32_t* __restrict__ status,
-                                                                   unsigned long long* __restrict__ desc_out, int32_t* __restrict__ changed)
+__global__ void __launch_bounds__(256) k_submap_store_list(int point_dim, int cap, int F, int d, const SubmapJob* __restrict__ jobs,
+                                                           const unsigned long long* __restrict__ feats, const int64_t* __restrict__ ids,
+                                                           const int32_t* __restrict__ newCount, const int32_t* __restrict__ newSrc,
+                                                           const int32_t* __restrict__ newStatus,
+                                                           unsigned long long* __restrict__ pool, int32_t* __restrict__ count, int32_t* __restrict__ src,
+                                                           int64_t* __restrict__ ids_out, int32_t* __restrict__ status,
+                                                           unsigned long long* __restrict__ desc_out, int32_t* __restrict__ changed)
 {
     const int l = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const SessionSubmap M = tab[l];                              // (uniform)
-    const int g = M.slot, n = newCount[l];
+    const int64_t seg0 = jobs[l].seg0;                           // (uniform)
+    const int g = jobs[l].slot, n = newCount[l];
     const int32_t* rows = newSrc + (int64_t)l * cap;
-    const unsigned long long* mfeats = feats + M.seg0 * F;
-    const int64_t* mids = ids ? ids + M.seg0 : nullptr;
+    const unsigned long long* mfeats = feats + seg0 * F;
+    const int64_t* mids = ids ? ids + seg0 : nullptr;
     bool diff = false;
     if (tid == 0) { slot_put<CMP>(count + g, (int32_t)n, diff); slot_put<CMP>(status + g, newStatus[l], diff); }
     for (int i = tid; i < cap; i += 256) slot_put<CMP>(src + (int64_t)g * cap + i, i < n ? rows[i] : (int32_t)-1, diff);
     for (int r = wave; r < cap; r += 4) {                        // (r is uniform over the wave)
         const int64_t row = (int64_t)g * cap + r;
-        const bool x = r < n ? submap_gather_row<CMP>(point_dim, F, descs[l].T_center_odom, mfeats, mids, rows[r], row, pool, ids_out, lane)
+        const bool x = r < n ? submap_gather_row<CMP>(point_dim, F, jobs[l].D.T_center_odom, mfeats, mids, rows[r], row, pool, ids_out, lane)
                              : submap_clear_row<CMP>(point_dim + F - 3, row, pool, ids_out, lane);
         diff = diff || x;
     }

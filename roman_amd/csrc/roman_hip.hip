@@ -176,14 +176,12 @@ struct roman_ctx {
     DevBuf ransacDesc;
     PinnedStage<RansacDesc> ransacStage;
 
-    // submaps from a whole map (roman_submaps*): the submap descriptors through pinned staging (a pure enqueue), the dense centres of
-    // the map, and the per-submap spill of candidate lists beyond SUBMAP_LDS_CAND
-    DevBuf smDesc, smPts, smSpillKey, smSpillIdx;
-    PinnedStage<roman_submap_desc_t> smStage;
-    // ... of a whole session (roman_session_submaps*): one record per global submap — where its map and its spill slice start
-    DevBuf smTab;
-    PinnedStage<SessionSubmap> smTabStage;
-    DevBuf smListOut;       // the list form's select output: src int32[L * cap], count int32[L], status int32[L] of the listed submaps
+    // submaps from whole maps (roman_submaps*, roman_submaps_fill*, roman_session_submaps*): one record per launched submap — its
+    // centre, where its map and its spill slice start — through pinned staging (a pure enqueue), the dense centres of the maps, and
+    // the per-submap spill of candidate lists beyond SUBMAP_LDS_CAND
+    DevBuf smJobs, smPts, smSpillKey, smSpillIdx;
+    PinnedStage<SubmapJob> smStage;
+    DevBuf smListOut;      // the list form's select output: src int32[L * cap], count int32[L], status int32[L] of the listed submaps
 
 
     // pass 1 of a grid (roman_grid_gate*): the descriptor norms of both sides
@@ -1458,8 +1456,8 @@ int roman_ctx_destroy(roman_ctx_t* c)
     { DevBuf* share[] = {&c->shareDesc, &c->shareIds, &c->shareKeep, &c->shareKept, &c->shareJobs}; for (DevBuf* b : share) b->release(); }
     c->hostMirror.release(); c->ransacDesc.release();
     c->shareStage.release(); c->ransacStage.release();
-    { DevBuf* sm[] = {&c->smDesc, &c->smPts, &c->smSpillKey, &c->smSpillIdx}; for (DevBuf* b : sm) b->release(); }
-    c->smStage.release(); c->smTab.release(); c->smTabStage.release(); c->smListOut.release();
+    { DevBuf* sm[] = {&c->smJobs, &c->smPts, &c->smSpillKey, &c->smSpillIdx, &c->smListOut}; for (DevBuf* b : sm) b->release(); }
+    c->smStage.release();
     c->ggNorm.release(); c->sgCount.release();
     c->ssNorm.release(); c->ssBand.release(); c->ssR.release(); c->ssItems.release(); c->ssStage.release();
     c->sfTab.release(); c->sfStage.release();
@@ -1702,6 +1700,7 @@ struct HostMirror {
     template <typename T> Piece<T> out(T* h, size_t b) { return Piece<T>{this, add(h, b, DOWN)}; }
     template <typename T> Piece<T> inout(T* h, size_t b) { return Piece<T>{this, add(h, b, UP | DOWN)}; }
     template <typename T> Piece<T> room(size_t b) { return Piece<T>{this, add(nullptr, b, 0)}; }
+    template <typename T> Piece<T> piece(T* h, size_t b, unsigned d) { return Piece<T>{this, add(h, b, d)}; }   // the direction as data
     // the block on the device, and the in and inout pieces on their way into it
     int upload() {
         if (n > CAP) return fail(c, ROMAN_E_INTERNAL, "a host-pointer call declares more than %d arrays", CAP);
@@ -2864,85 +2863,26 @@ static int submaps_check(roman_ctx* c, const roman_submap_params_t* P, int32_t N
     return ROMAN_OK;
 }
 
-int roman_submaps_dev(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t N, int32_t F,
-                      const double* seg_feats, const double* seg_times, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
-                      double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
-{
-    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = submaps_check(c, sparams, N, F, seg_feats, seg_times, seg_ids, S, descs, pool, count, src, ids_out, status, desc_dim, desc_out, true);
-    if (rc || S == 0) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t stream = c->stream;
-    // scratch first: a failure leaves nothing enqueued
-    const int64_t spill = std::max<int64_t>((int64_t)N - SUBMAP_LDS_CAND, 0);
-    HIPCHK(c, c->smSpillKey.ensure(sizeof(double) * (size_t)std::max<int64_t>(spill * S, 1)));
-    HIPCHK(c, c->smSpillIdx.ensure(sizeof(int32_t) * (size_t)std::max<int64_t>(spill * S, 1)));
-    HIPCHK(c, c->smPts.ensure(sizeof(double) * 3 * (size_t)std::max(N, 1)));
-    roman_submap_desc_t* staged = nullptr;
-    HIPCHK(c, c->smStage.stage((size_t)S, &staged));
-    memcpy(staged, descs, sizeof(roman_submap_desc_t) * (size_t)S);
-    HIPCHK(c, c->smStage.upload(c->smDesc, (size_t)S, stream));
-    const roman_submap_desc_t* dDesc = c->smDesc.as<roman_submap_desc_t>();
-    if (N > 0) hipLaunchKernelGGL(k_submap_points, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, (int)N, (int)F, seg_feats, c->smPts.as<double>());
-    hipLaunchKernelGGL(k_submap_select, dim3((unsigned)S), dim3(SUBMAP_NT), 0, stream, *sparams, (int)S, (int)N, dDesc, c->smPts.as<double>(), seg_times,
-                       c->smSpillKey.as<double>(), c->smSpillIdx.as<int32_t>(), spill, count, src, status);
-    HIPCHK(c, hipGetLastError());
-    if (N > 0) {
-        // a wave per row, four rows per workgroup and pass: enough row groups for the largest slot, at most 64 per submap
-        const unsigned groups = (unsigned)std::min(64, (std::min(sparams->cap, N) + 3) / 4);
-        hipLaunchKernelGGL(k_submap_gather, dim3((unsigned)S, groups), dim3(256), 0, stream, (int)sparams->point_dim, (int)sparams->cap, (int)F, dDesc,
-                           reinterpret_cast<const unsigned long long*>(seg_feats), seg_ids, count, src, reinterpret_cast<unsigned long long*>(pool), ids_out);
-        if (desc_out) hipLaunchKernelGGL(k_submap_desc, dim3((unsigned)S, (unsigned)((desc_dim + 255) / 256)), dim3(256), 0, stream, (int)sparams->cap, (int)F, (int)desc_dim,
-                                         seg_feats, count, src, desc_out);
-        HIPCHK(c, hipGetLastError());
-    }
-    return ROMAN_OK;
-}
-
-int roman_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t N, int32_t F,
-                  const double* seg_feats, const double* seg_times, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
-                  double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
-{
-    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    int rc = submaps_check(c, sparams, N, F, seg_feats, seg_times, seg_ids, S, descs, pool, count, src, ids_out, status, desc_dim, desc_out, false);
-    if (rc || S == 0) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    c->last.scored = false; c->last.solved = false;            // workspace 0's feature staging is reused: the stepwise problem it held is gone
-    const double* dFeats = nullptr;
-    rc = upload_inputs(c, seg_feats, N, F, 0, nullptr, 0, &dFeats);
-    if (rc) return rc;
-    const size_t rows = (size_t)S * (size_t)sparams->cap, bPool = sizeof(double) * rows * (size_t)(sparams->point_dim + F - 3);
-    HostMirror m(c);
-    const auto times = m.in(seg_times, sizeof(double) * 2 * (size_t)N);
-    const auto ids = m.in(seg_ids, seg_ids ? sizeof(int64_t) * (size_t)N : 0);
-    const auto dPool = pool ? m.inout(pool, bPool) : m.room<double>(bPool);     // without a pool the device call still writes one
-    const auto idsOut = m.inout(ids_out, ids_out ? sizeof(int64_t) * rows : 0);
-    const auto descOut = m.inout(desc_out, desc_out ? sizeof(double) * (size_t)S * (size_t)desc_dim : 0);
-    const auto dSrc = m.inout(src, sizeof(int32_t) * rows);
-    const auto cnt = m.out(count, sizeof(int32_t) * (size_t)S);
-    const auto st = m.out(status, sizeof(int32_t) * (size_t)S);
-    rc = m.upload();
-    if (rc) return rc;
-    rc = roman_submaps_dev(c, sparams, N, F, dFeats, times.dev(), ids.dev(), S, descs, dPool.dev(), cnt.dev(), dSrc.dev(), idsOut.dev(), st.dev(),
-                           desc_dim, descOut.dev());
-    if (rc) return rc;
-    return m.download();
-}
-
 // --- the submaps of every map of a session in one launch sequence -------------------------------------------------
-// What one call works on, under names, from the C entry point to the launch; the host form hands the device form a copy whose bulk
-// arrays are the mirror's.  seg_off, sub_off and descs are HOST memory in both forms.
-struct SessionSubmapsArgs {
+// What one call of ANY form works on, under names, from the C entry point to the launch: a single map is a session of one map (its two
+// offset tables on the entry point's stack).  The host forms hand the launch a copy whose bulk arrays are the mirror's; seg_off,
+// sub_off, descs and list are HOST memory in every form.  What tells the forms apart is data:
+//   listed  only the L submaps of `list` are rebuilt, whole, in place; `changed` (or NULL) learns which slots differ
+//   fill    count and src are the CALLER's lists: nothing is selected, seg_times and status are not read
+struct SubmapsArgs {
     int32_t R, F;
     const int64_t* seg_off; const double* seg_feats; const double* seg_times; const int64_t* seg_ids;
     const int32_t* sub_off; const roman_submap_desc_t* descs;
     double* pool; int32_t* count; int32_t* src; int64_t* ids_out; int32_t* status;
     int32_t desc_dim; double* desc_out;
+    bool listed; int32_t L; const int32_t* list; int32_t* changed;
+    bool fill;
 };
 
-// the offsets first (they size everything else), then roman_submaps_dev's own checks; what passes has *N segment rows and *S submaps
-static int session_submaps_check(roman_ctx* c, const roman_submap_params_t* P, const SessionSubmapsArgs& g, bool pool_needed, int64_t* N, int32_t* S)
+// The checks of the session entry points, on host memory only, a NULL context included (fail() then keeps the text for
+// roman_last_error(NULL)): the offsets first (they size everything else), then roman_submaps_dev's own checks, the list (DESIGN.md
+// §4.21) behind them, the context last.  What passes has *n submaps to launch; 0: the call is empty.
+static int session_submaps_check(roman_ctx* c, const roman_submap_params_t* P, const SubmapsArgs& g, bool pool_needed, int32_t* n)
 {
     const int32_t R = g.R;
     if (R < 0) return fail(c, ROMAN_E_INVALID, "R < 0");
@@ -2953,254 +2893,23 @@ static int session_submaps_check(roman_ctx* c, const roman_submap_params_t* P, c
         if (g.sub_off[r + 1] < g.sub_off[r]) return fail(c, ROMAN_E_INVALID, "sub_off decreases at map %d", r);
         if (g.seg_off[r + 1] - g.seg_off[r] > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "map %d holds more than %d segments", r, INT32_MAX);
     }
-    *N = R > 0 ? g.seg_off[R] : 0; *S = R > 0 ? g.sub_off[R] : 0;
-    int rc = submaps_check(c, P, *N > 0 ? 1 : 0, g.F, g.seg_feats, g.seg_times, g.seg_ids, *S, g.descs, g.pool, g.count, g.src, g.ids_out, g.status,
+    const int64_t N = R > 0 ? g.seg_off[R] : 0;
+    const int32_t S = R > 0 ? g.sub_off[R] : 0;
+    int rc = submaps_check(c, P, N > 0 ? 1 : 0, g.F, g.seg_feats, g.seg_times, g.seg_ids, S, g.descs, g.pool, g.count, g.src, g.ids_out, g.status,
                            g.desc_dim, g.desc_out, pool_needed);
     if (rc) return rc;
-    if ((int64_t)*S * P->cap > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "sub_off[R] * cap = %lld rows exceed the index width", (long long)*S * P->cap);
-    return ROMAN_OK;
-}
-
-// the device-pointer call
-static int session_submaps_dev(roman_ctx* c, const roman_submap_params_t* sparams, const SessionSubmapsArgs& g)
-{
-    // (the arguments are judged first — on host memory only, a NULL context included: fail() then keeps the text for roman_last_error(NULL))
-    int64_t N = 0; int32_t S = 0;
-    int rc = session_submaps_check(c, sparams, g, true, &N, &S);
-    if (rc) return rc;
-    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    if (S == 0) return ROMAN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t stream = c->stream;
-    // every submap's slice of the spill starts where the slices of the submaps in front of it end
-    int64_t spill = 0; int32_t maxN = 0;
-    for (int r = 0; r < g.R; ++r) {
-        const int64_t n = g.seg_off[r + 1] - g.seg_off[r], over = std::max<int64_t>(n - SUBMAP_LDS_CAND, 0);
-        const int64_t subs = g.sub_off[r + 1] - g.sub_off[r];
-        if (subs) maxN = std::max(maxN, (int32_t)n);
-        if (over && subs > (INT64_MAX / 16 - spill) / over) return fail(c, ROMAN_E_NOMEM, "the candidate scratch of the session exceeds the address space");
-        spill += subs * over;
-    }
-    // scratch and staging first: a failure leaves nothing enqueued
-    if (spill > 0) {
-        HIPCHK(c, c->smSpillKey.ensure(sizeof(double) * (size_t)spill));
-        HIPCHK(c, c->smSpillIdx.ensure(sizeof(int32_t) * (size_t)spill));
-    }
-    HIPCHK(c, c->smPts.ensure(sizeof(double) * 3 * (size_t)std::max<int64_t>(N, 1)));
-    HIPCHK(c, c->smDesc.ensure(sizeof(roman_submap_desc_t) * (size_t)S));
-    HIPCHK(c, c->smTab.ensure(sizeof(SessionSubmap) * (size_t)S));
-    roman_submap_desc_t* staged = nullptr;
-    SessionSubmap* tab = nullptr;
-    HIPCHK(c, c->smStage.stage((size_t)S, &staged));
-    HIPCHK(c, c->smTabStage.stage((size_t)S, &tab));
-    memcpy(staged, g.descs, sizeof(roman_submap_desc_t) * (size_t)S);
-    int64_t at = 0;
-    for (int r = 0; r < g.R; ++r) {
-        const int64_t n = g.seg_off[r + 1] - g.seg_off[r], over = std::max<int64_t>(n - SUBMAP_LDS_CAND, 0);
-        for (int32_t s = g.sub_off[r]; s < g.sub_off[r + 1]; ++s, at += over) tab[s] = SessionSubmap{g.seg_off[r], at, (int32_t)n, s};
-    }
-    HIPCHK(c, c->smStage.upload(c->smDesc, (size_t)S, stream));
-    HIPCHK(c, c->smTabStage.upload(c->smTab, (size_t)S, stream));
-    const roman_submap_desc_t* dDesc = c->smDesc.as<roman_submap_desc_t>();
-    const SessionSubmap* dTab = c->smTab.as<SessionSubmap>();
-    const int cap = sparams->cap, F = g.F;
-    if (N > 0) hipLaunchKernelGGL(k_session_submap_points, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, N, F, g.seg_feats, c->smPts.as<double>());
-    hipLaunchKernelGGL(k_session_submap_select, dim3((unsigned)S), dim3(SUBMAP_NT), 0, stream, *sparams, (int)S, dTab, dDesc, c->smPts.as<double>(), g.seg_times,
-                       c->smSpillKey.as<double>(), c->smSpillIdx.as<int32_t>(), g.count, g.src, g.status);
-    HIPCHK(c, hipGetLastError());
-    if (maxN > 0) {
-        // as roman_submaps_dev launches them: enough row groups for the largest slot of the largest map, at most 64 per submap
-        const unsigned groups = (unsigned)std::min(64, (std::min(cap, maxN) + 3) / 4);
-        hipLaunchKernelGGL(k_session_submap_gather, dim3((unsigned)S, groups), dim3(256), 0, stream, (int)sparams->point_dim, cap, F, dTab, dDesc,
-                           reinterpret_cast<const unsigned long long*>(g.seg_feats), g.seg_ids, g.count, g.src, reinterpret_cast<unsigned long long*>(g.pool), g.ids_out);
-        if (g.desc_out) hipLaunchKernelGGL(k_session_submap_desc, dim3((unsigned)S, (unsigned)((g.desc_dim + 255) / 256)), dim3(256), 0, stream, cap, F, (int)g.desc_dim,
-                                           dTab, g.seg_feats, g.count, g.src, g.desc_out);
-        HIPCHK(c, hipGetLastError());
-    }
-    return ROMAN_OK;
-}
-
-// the host-pointer call: without a pool the device call still writes one
-static int session_submaps_host(roman_ctx* c, const roman_submap_params_t* sparams, const SessionSubmapsArgs& h)
-{
-    int64_t N = 0; int32_t S = 0;
-    int rc = session_submaps_check(c, sparams, h, false, &N, &S);
-    if (rc) return rc;
-    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    if (S == 0) return ROMAN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    const size_t rows = (size_t)S * (size_t)sparams->cap, bPool = sizeof(double) * rows * (size_t)(sparams->point_dim + h.F - 3);
-    HostMirror m(c);
-    const auto feats = m.in(h.seg_feats, sizeof(double) * (size_t)N * (size_t)h.F);
-    const auto times = m.in(h.seg_times, sizeof(double) * 2 * (size_t)N);
-    const auto ids = m.in(h.seg_ids, h.seg_ids ? sizeof(int64_t) * (size_t)N : 0);
-    const auto dPool = h.pool ? m.inout(h.pool, bPool) : m.room<double>(bPool);
-    const auto idsOut = m.inout(h.ids_out, h.ids_out ? sizeof(int64_t) * rows : 0);
-    const auto descOut = m.inout(h.desc_out, h.desc_out ? sizeof(double) * (size_t)S * (size_t)h.desc_dim : 0);
-    const auto dSrc = m.inout(h.src, sizeof(int32_t) * rows);
-    const auto cnt = m.out(h.count, sizeof(int32_t) * (size_t)S);
-    const auto st = m.out(h.status, sizeof(int32_t) * (size_t)S);
-    rc = m.upload();
-    if (rc) return rc;
-    SessionSubmapsArgs g = h;                                    // the same call on the mirror; offsets and descriptors stay the caller's
-    g.seg_feats = feats.dev(); g.seg_times = times.dev(); g.seg_ids = ids.dev();
-    g.pool = dPool.dev(); g.count = cnt.dev(); g.src = dSrc.dev(); g.ids_out = idsOut.dev(); g.status = st.dev(); g.desc_out = descOut.dev();
-    rc = session_submaps_dev(c, sparams, g);
-    if (rc) return rc;
-    return m.download();
-}
-
-int roman_session_submaps_dev(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
-                              const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
-                              double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
-{
-    const SessionSubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
-    return session_submaps_dev(c, sparams, g);
-}
-
-int roman_session_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
-                          const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
-                          double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
-{
-    const SessionSubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
-    return session_submaps_host(c, sparams, g);
-}
-
-// --- the LISTED submaps of a session, rebuilt in place -------------------------------------------------------------
-// the list is judged behind the session's own checks, on host memory, before the context
-static int session_list_check(roman_ctx* c, int32_t S, int32_t L, const int32_t* list)
-{
-    if (L < 0) return fail(c, ROMAN_E_INVALID, "L < 0");
-    if (L > 0 && !list) return fail(c, ROMAN_E_INVALID, "list is NULL");
-    for (int32_t l = 0; l < L; ++l) {
-        if (list[l] < 0 || list[l] >= S) return fail(c, ROMAN_E_INVALID, "list[%d] = %d outside the %d submaps of the session", l, list[l], S);
-        if (l > 0 && list[l] <= list[l - 1]) return fail(c, ROMAN_E_INVALID, "list is not strictly ascending at entry %d", l);
-    }
-    return ROMAN_OK;
-}
-
-static int session_submaps_list_dev(roman_ctx* c, const roman_submap_params_t* sparams, const SessionSubmapsArgs& g, int32_t L, const int32_t* list,
-                                    int32_t* changed)
-{
-    int64_t N = 0; int32_t S = 0;
-    int rc = session_submaps_check(c, sparams, g, true, &N, &S);
-    if (rc) return rc;
-    rc = session_list_check(c, S, L, list);
-    if (rc) return rc;
-    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    if (L == 0) return ROMAN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t stream = c->stream;
-    const int cap = sparams->cap, F = g.F;
-    // scratch slices for the LISTED submaps of the maps beyond SUBMAP_LDS_CAND only, each where the slices of the listed ones in front end
-    int64_t spill = 0;
-    for (int r = 0, l = 0; r < g.R && l < L; ++r) {
-        const int64_t n = g.seg_off[r + 1] - g.seg_off[r], over = std::max<int64_t>(n - SUBMAP_LDS_CAND, 0);
-        int64_t subs = 0;
-        for (; l < L && list[l] < g.sub_off[r + 1]; ++l) ++subs;
-        if (over && subs > (INT64_MAX / 16 - spill) / over) return fail(c, ROMAN_E_NOMEM, "the candidate scratch of the listed submaps exceeds the address space");
-        spill += subs * over;
-    }
-    // scratch and staging first: a failure leaves nothing enqueued
-    if (spill > 0) {
-        HIPCHK(c, c->smSpillKey.ensure(sizeof(double) * (size_t)spill));
-        HIPCHK(c, c->smSpillIdx.ensure(sizeof(int32_t) * (size_t)spill));
-    }
-    HIPCHK(c, c->smPts.ensure(sizeof(double) * 3 * (size_t)std::max<int64_t>(N, 1)));
-    HIPCHK(c, c->smDesc.ensure(sizeof(roman_submap_desc_t) * (size_t)L));
-    HIPCHK(c, c->smTab.ensure(sizeof(SessionSubmap) * (size_t)L));
-    HIPCHK(c, c->smListOut.ensure(sizeof(int32_t) * ((size_t)L * (size_t)cap + 2 * (size_t)L)));
-    roman_submap_desc_t* staged = nullptr;
-    SessionSubmap* tab = nullptr;
-    HIPCHK(c, c->smStage.stage((size_t)L, &staged));
-    HIPCHK(c, c->smTabStage.stage((size_t)L, &tab));
-    int64_t at = 0;
-    for (int r = 0, l = 0; r < g.R && l < L; ++r) {
-        const int64_t n = g.seg_off[r + 1] - g.seg_off[r], over = std::max<int64_t>(n - SUBMAP_LDS_CAND, 0);
-        for (; l < L && list[l] < g.sub_off[r + 1]; ++l, at += over) {
-            staged[l] = g.descs[list[l]];
-            tab[l] = SessionSubmap{g.seg_off[r], at, (int32_t)n, list[l]};
+    if ((int64_t)S * P->cap > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "sub_off[R] * cap = %lld rows exceed the index width", (long long)S * P->cap);
+    if (g.listed) {
+        if (g.L < 0) return fail(c, ROMAN_E_INVALID, "L < 0");
+        if (g.L > 0 && !g.list) return fail(c, ROMAN_E_INVALID, "list is NULL");
+        for (int32_t l = 0; l < g.L; ++l) {
+            if (g.list[l] < 0 || g.list[l] >= S) return fail(c, ROMAN_E_INVALID, "list[%d] = %d outside the %d submaps of the session", l, g.list[l], S);
+            if (l > 0 && g.list[l] <= g.list[l - 1]) return fail(c, ROMAN_E_INVALID, "list is not strictly ascending at entry %d", l);
         }
     }
-    HIPCHK(c, c->smStage.upload(c->smDesc, (size_t)L, stream));
-    HIPCHK(c, c->smTabStage.upload(c->smTab, (size_t)L, stream));
-    const roman_submap_desc_t* dDesc = c->smDesc.as<roman_submap_desc_t>();
-    const SessionSubmap* dTab = c->smTab.as<SessionSubmap>();
-    int32_t* newSrc = c->smListOut.as<int32_t>();
-    int32_t* newCount = newSrc + (size_t)L * (size_t)cap;
-    int32_t* newStatus = newCount + L;
-    // the dense centres of the maps that have a listed submap, each map's rows at their place in the session's array
-    for (int r = 0, l = 0; r < g.R && l < L; ++r) {
-        const int64_t n = g.seg_off[r + 1] - g.seg_off[r];
-        const int l0 = l;
-        while (l < L && list[l] < g.sub_off[r + 1]) ++l;
-        if (l > l0 && n > 0)
-            hipLaunchKernelGGL(k_session_submap_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, F, g.seg_feats + g.seg_off[r] * F,
-                               c->smPts.as<double>() + 3 * g.seg_off[r]);
-    }
-    hipLaunchKernelGGL(k_session_submap_select_list, dim3((unsigned)L), dim3(SUBMAP_NT), 0, stream, *sparams, (int)L, dTab, dDesc, c->smPts.as<double>(), g.seg_times,
-                       c->smSpillKey.as<double>(), c->smSpillIdx.as<int32_t>(), newCount, newSrc, newStatus);
-    HIPCHK(c, hipGetLastError());
-    const auto store = changed ? k_session_submap_store_list<true> : k_session_submap_store_list<false>;
-    hipLaunchKernelGGL(store, dim3((unsigned)L), dim3(256), 0, stream, (int)sparams->point_dim, cap, F, (int)g.desc_dim, dTab, dDesc,
-                       reinterpret_cast<const unsigned long long*>(g.seg_feats), g.seg_ids, newCount, newSrc, newStatus,
-                       reinterpret_cast<unsigned long long*>(g.pool), g.count, g.src, g.ids_out, g.status, reinterpret_cast<unsigned long long*>(g.desc_out), changed);
-    HIPCHK(c, hipGetLastError());
-    return ROMAN_OK;
-}
-
-// the host-pointer call: the caller's current outputs go up first (an unlisted slot comes back as it was, and `changed` compares with them)
-static int session_submaps_list_host(roman_ctx* c, const roman_submap_params_t* sparams, const SessionSubmapsArgs& h, int32_t L, const int32_t* list,
-                                     int32_t* changed)
-{
-    int64_t N = 0; int32_t S = 0;
-    int rc = session_submaps_check(c, sparams, h, true, &N, &S);
-    if (rc) return rc;
-    rc = session_list_check(c, S, L, list);
-    if (rc) return rc;
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
-    if (L == 0) return ROMAN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    const size_t rows = (size_t)S * (size_t)sparams->cap, bPool = sizeof(double) * rows * (size_t)(sparams->point_dim + h.F - 3);
-    HostMirror m(c);
-    const auto feats = m.in(h.seg_feats, sizeof(double) * (size_t)N * (size_t)h.F);
-    const auto times = m.in(h.seg_times, sizeof(double) * 2 * (size_t)N);
-    const auto ids = m.in(h.seg_ids, h.seg_ids ? sizeof(int64_t) * (size_t)N : 0);
-    const auto dPool = m.inout(h.pool, bPool);
-    const auto idsOut = m.inout(h.ids_out, h.ids_out ? sizeof(int64_t) * rows : 0);
-    const auto descOut = m.inout(h.desc_out, h.desc_out ? sizeof(double) * (size_t)S * (size_t)h.desc_dim : 0);
-    const auto dSrc = m.inout(h.src, sizeof(int32_t) * rows);
-    const auto cnt = m.inout(h.count, sizeof(int32_t) * (size_t)S);
-    const auto st = m.inout(h.status, sizeof(int32_t) * (size_t)S);
-    const auto chg = m.out(changed, changed ? sizeof(int32_t) * (size_t)L : 0);
-    rc = m.upload();
-    if (rc) return rc;
-    SessionSubmapsArgs g = h;
-    g.seg_feats = feats.dev(); g.seg_times = times.dev(); g.seg_ids = ids.dev();
-    g.pool = dPool.dev(); g.count = cnt.dev(); g.src = dSrc.dev(); g.ids_out = idsOut.dev(); g.status = st.dev(); g.desc_out = descOut.dev();
-    rc = session_submaps_list_dev(c, sparams, g, L, list, chg.dev());
-    if (rc) return rc;
-    return m.download();
-}
-
-int roman_session_submaps_list_dev(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
-                                   const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
-                                   double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out,
-                                   int32_t L, const int32_t* list, int32_t* changed)
-{
-    const SessionSubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
-    return session_submaps_list_dev(c, sparams, g, L, list, changed);
-}
-
-int roman_session_submaps_list(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
-                               const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
-                               double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out,
-                               int32_t L, const int32_t* list, int32_t* changed)
-{
-    const SessionSubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
-    return session_submaps_list_host(c, sparams, g, L, list, changed);
+    *n = g.listed ? g.L : S;
+    return ROMAN_OK;
 }
 
 // --- force-fill submaps and the boxes of a pool ([REF roman/map/map.py:264-295], [REF :133-139]) -------------------
@@ -3221,6 +2930,208 @@ static int submaps_fill_check(roman_ctx* c, int32_t point_dim, int32_t cap, int3
     return ROMAN_OK;
 }
 
+// --- one path under every form: the job table, the launches, the host-pointer mirror --------------------------------------------------
+// The staged job table of one call: its device copy, the staging it went up from, its records, the largest map that has one.
+struct SubmapJobs { const SubmapJob* dev; const SubmapJob* host; int32_t n, maxN; };
+
+// One record per LAUNCHED submap — all sub_off[R] of them, or the L of `list` (strictly ascending) —, each with its map's rows and its
+// slice of the spill, which starts where the slices of the launched submaps in front of it end (`select`: the call selects, so it needs
+// the spill and the dense centres at all).  Every scratch is had before the table goes up: a failure leaves nothing enqueued.
+static int submaps_stage(roman_ctx* c, int32_t R, const int64_t* seg_off, const int32_t* sub_off, const roman_submap_desc_t* descs,
+                         int32_t L, const int32_t* list, bool select, SubmapJobs* out)
+{
+    const int32_t n = list ? L : sub_off[R];
+    SubmapJob* jobs = nullptr;
+    HIPCHK(c, c->smStage.stage((size_t)n, &jobs));
+    int64_t spill = 0; int32_t maxN = 0;
+    for (int32_t r = 0, j = 0; r < R && j < n; ++r) {
+        const int64_t rows = seg_off[r + 1] - seg_off[r], over = select ? std::max<int64_t>(rows - SUBMAP_LDS_CAND, 0) : 0;
+        int32_t j1 = j;                                          // the launched submaps of map r: jobs [j, j1)
+        if (!list) j1 = sub_off[r + 1]; else while (j1 < n && list[j1] < sub_off[r + 1]) ++j1;
+        if (j1 == j) continue;
+        maxN = std::max(maxN, (int32_t)rows);
+        if (over && j1 - j > (INT64_MAX / 16 - spill) / over)
+            return fail(c, ROMAN_E_NOMEM, "the candidate scratch of the %s exceeds the address space", list ? "listed submaps" : "session");
+        for (; j < j1; ++j, spill += over) {
+            const int32_t g = list ? list[j] : j;
+            jobs[j] = SubmapJob{descs[g], seg_off[r], spill, (int32_t)rows, g};
+        }
+    }
+    if (spill > 0) {
+        HIPCHK(c, c->smSpillKey.ensure(sizeof(double) * (size_t)spill));
+        HIPCHK(c, c->smSpillIdx.ensure(sizeof(int32_t) * (size_t)spill));
+    }
+    if (select) HIPCHK(c, c->smPts.ensure(sizeof(double) * 3 * (size_t)std::max<int64_t>(seg_off[R], 1)));
+    HIPCHK(c, c->smStage.upload(c->smJobs, (size_t)n, c->stream));
+    *out = SubmapJobs{c->smJobs.as<SubmapJob>(), jobs, n, maxN};
+    return ROMAN_OK;
+}
+
+// The device-pointer call of every form, behind its entry point's checks: there is a submap to launch.
+static int submaps_launch(roman_ctx* c, const roman_submap_params_t* P, const SubmapsArgs& g)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t stream = c->stream;
+    const int cap = P->cap, F = g.F, d = g.desc_dim;
+    const auto feats = reinterpret_cast<const unsigned long long*>(g.seg_feats);
+    if (g.listed) HIPCHK(c, c->smListOut.ensure(sizeof(int32_t) * ((size_t)g.L * (size_t)cap + 2 * (size_t)g.L)));
+    SubmapJobs J;
+    int rc = submaps_stage(c, g.R, g.seg_off, g.sub_off, g.descs, g.L, g.listed ? g.list : nullptr, !g.fill, &J);
+    if (rc) return rc;
+    // what the select writes: the caller's arrays, or — the list form, whose store kernel compares before it writes — the context's scratch
+    int32_t* src = g.listed ? c->smListOut.as<int32_t>() : g.src;
+    int32_t* count = g.listed ? src + (size_t)J.n * (size_t)cap : g.count;
+    int32_t* status = g.listed ? count + J.n : g.status;
+    if (!g.fill) {
+        // the dense centres: of the whole session at once, or — the list form — of the maps that have a listed submap, each map's rows
+        // at their place in the session's array (the records of one map lie together; maps without rows launch nothing)
+        double* pts = c->smPts.as<double>();
+        const int64_t N = g.seg_off[g.R];
+        if (!g.listed && N > 0) hipLaunchKernelGGL(k_submap_points, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, N, F, g.seg_feats, pts);
+        for (int32_t l = 0; g.listed && l < J.n; ++l) {
+            const SubmapJob& a = J.host[l];
+            if (a.N > 0 && (l == 0 || J.host[l - 1].seg0 != a.seg0 || J.host[l - 1].N != a.N))
+                hipLaunchKernelGGL(k_submap_points, dim3((unsigned)(((int64_t)a.N + 255) / 256)), dim3(256), 0, stream, (int64_t)a.N, F,
+                                   g.seg_feats + a.seg0 * F, pts + 3 * a.seg0);
+        }
+        hipLaunchKernelGGL(k_submap_select, dim3((unsigned)J.n), dim3(SUBMAP_NT), 0, stream, *P, (int)J.n, J.dev, pts, g.seg_times,
+                           c->smSpillKey.as<double>(), c->smSpillIdx.as<int32_t>(), count, src, status);
+        HIPCHK(c, hipGetLastError());
+    }
+    if (g.listed) {
+        const auto store = g.changed ? k_submap_store_list<true> : k_submap_store_list<false>;
+        hipLaunchKernelGGL(store, dim3((unsigned)J.n), dim3(256), 0, stream, (int)P->point_dim, cap, F, d, J.dev, feats, g.seg_ids, count, src, status,
+                           reinterpret_cast<unsigned long long*>(g.pool), g.count, g.src, g.ids_out, g.status, reinterpret_cast<unsigned long long*>(g.desc_out),
+                           g.changed);
+    } else if (J.maxN > 0) {
+        // a wave per row, four rows per workgroup and pass: enough row groups for the largest slot of the largest map, at most 64 per submap
+        const unsigned groups = (unsigned)std::min(64, (std::min(cap, J.maxN) + 3) / 4);
+        hipLaunchKernelGGL(k_submap_gather, dim3((unsigned)J.n, groups), dim3(256), 0, stream, (int)P->point_dim, cap, F, J.dev, feats, g.seg_ids, count, src,
+                           reinterpret_cast<unsigned long long*>(g.pool), g.ids_out);
+        if (g.desc_out) hipLaunchKernelGGL(k_submap_desc, dim3((unsigned)J.n, (unsigned)((d + 255) / 256)), dim3(256), 0, stream, cap, F, d, J.dev, g.seg_feats,
+                                           count, src, g.desc_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+// The host-pointer call of every form: the bulk arrays as one block of the mirror, submaps_launch() on it, the outputs back.  The
+// caller's src, ids_out, desc_out and pool go up first: what the launch leaves untouched comes back as it was, and without a pool the
+// launch still writes one.  count and status are written whole — but the list form changes the listed slots only (and `changed`
+// compares with what was there), and a fill call only reads the caller's count and src.
+static int submaps_mirror(roman_ctx* c, const roman_submap_params_t* P, const SubmapsArgs& h)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const size_t N = (size_t)h.seg_off[h.R], S = (size_t)h.sub_off[h.R];
+    const size_t rows = S * (size_t)P->cap, bPool = sizeof(double) * rows * (size_t)(P->point_dim + h.F - 3);
+    const unsigned lists = h.fill ? HostMirror::UP : HostMirror::UP | HostMirror::DOWN;
+    const unsigned words = h.fill ? HostMirror::UP : h.listed ? HostMirror::UP | HostMirror::DOWN : HostMirror::DOWN;
+    HostMirror m(c);
+    const auto feats = m.in(h.seg_feats, sizeof(double) * N * (size_t)h.F);
+    const auto times = m.in(h.seg_times, h.fill ? 0 : sizeof(double) * 2 * N);
+    const auto ids = m.in(h.seg_ids, h.seg_ids ? sizeof(int64_t) * N : 0);
+    const auto dPool = h.pool ? m.inout(h.pool, bPool) : m.room<double>(bPool);
+    const auto idsOut = m.inout(h.ids_out, h.ids_out ? sizeof(int64_t) * rows : 0);
+    const auto descOut = m.inout(h.desc_out, h.desc_out ? sizeof(double) * S * (size_t)h.desc_dim : 0);
+    const auto dSrc = m.piece(h.src, sizeof(int32_t) * rows, lists);
+    const auto cnt = m.piece(h.count, sizeof(int32_t) * S, words);
+    const auto st = m.piece(h.status, h.status ? sizeof(int32_t) * S : 0, words);
+    const auto chg = m.out(h.changed, h.changed ? sizeof(int32_t) * (size_t)h.L : 0);
+    int rc = m.upload();
+    if (rc) return rc;
+    SubmapsArgs g = h;                                           // the same call on the mirror; offsets, descriptors and list stay the caller's
+    g.seg_feats = feats.dev(); g.seg_times = times.dev(); g.seg_ids = ids.dev();
+    g.pool = dPool.dev(); g.count = cnt.dev(); g.src = dSrc.dev(); g.ids_out = idsOut.dev(); g.status = st.dev(); g.desc_out = descOut.dev();
+    g.changed = chg.dev();
+    rc = submaps_launch(c, P, g);
+    if (rc) return rc;
+    return m.download();
+}
+
+// --- the entry points: each its own checks, then the argument block and the one path ------------------------------------------------
+int roman_submaps_dev(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t N, int32_t F,
+                      const double* seg_feats, const double* seg_times, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
+                      double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = submaps_check(c, sparams, N, F, seg_feats, seg_times, seg_ids, S, descs, pool, count, src, ids_out, status, desc_dim, desc_out, true);
+    if (rc || S == 0) return rc;
+    const int64_t seg_off[2] = {0, N}; const int32_t sub_off[2] = {0, S};
+    const SubmapsArgs g{1, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
+    return submaps_launch(c, sparams, g);
+}
+
+int roman_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t N, int32_t F,
+                  const double* seg_feats, const double* seg_times, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
+                  double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    int rc = submaps_check(c, sparams, N, F, seg_feats, seg_times, seg_ids, S, descs, pool, count, src, ids_out, status, desc_dim, desc_out, false);
+    if (rc || S == 0) return rc;
+    const int64_t seg_off[2] = {0, N}; const int32_t sub_off[2] = {0, S};
+    const SubmapsArgs h{1, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
+    return submaps_mirror(c, sparams, h);
+}
+
+int roman_session_submaps_dev(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
+                              const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
+                              double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
+{
+    const SubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
+    int32_t n = 0;
+    const int rc = session_submaps_check(c, sparams, g, true, &n);
+    return rc || n == 0 ? rc : submaps_launch(c, sparams, g);
+}
+
+int roman_session_submaps(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
+                          const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
+                          double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out)
+{
+    const SubmapsArgs h{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out};
+    int32_t n = 0;
+    const int rc = session_submaps_check(c, sparams, h, false, &n);
+    return rc || n == 0 ? rc : submaps_mirror(c, sparams, h);
+}
+
+int roman_session_submaps_list_dev(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
+                                   const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
+                                   double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out,
+                                   int32_t L, const int32_t* list, int32_t* changed)
+{
+    const SubmapsArgs g{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out,
+                        true, L, list, changed};
+    int32_t n = 0;
+    const int rc = session_submaps_check(c, sparams, g, true, &n);
+    return rc || n == 0 ? rc : submaps_launch(c, sparams, g);
+}
+
+int roman_session_submaps_list(roman_ctx_t* c, const roman_submap_params_t* sparams, int32_t R, int32_t F, const int64_t* seg_off,
+                               const double* seg_feats, const double* seg_times, const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs,
+                               double* pool, int32_t* count, int32_t* src, int64_t* ids_out, int32_t* status, int32_t desc_dim, double* desc_out,
+                               int32_t L, const int32_t* list, int32_t* changed)
+{
+    const SubmapsArgs h{R, F, seg_off, seg_feats, seg_times, seg_ids, sub_off, descs, pool, count, src, ids_out, status, desc_dim, desc_out,
+                        true, L, list, changed};
+    int32_t n = 0;
+    const int rc = session_submaps_check(c, sparams, h, true, &n);
+    return rc || n == 0 ? rc : submaps_mirror(c, sparams, h);
+}
+
+// The fill forms' argument block: the caller's lists stand where the select's outputs do (nothing writes them), and of the parameters
+// only point_dim and cap exist.
+static SubmapsArgs submaps_fill_args(roman_submap_params_t* P, int32_t point_dim, int32_t cap, int32_t F, const int64_t* seg_off, const double* seg_feats,
+                                     const int64_t* seg_ids, const int32_t* sub_off, const roman_submap_desc_t* descs, const int32_t* count,
+                                     const int32_t* src, double* pool, int64_t* ids_out, int32_t desc_dim, double* desc_out)
+{
+    *P = roman_submap_params_t{};
+    P->point_dim = point_dim; P->cap = cap;
+    SubmapsArgs g{1, F, seg_off, seg_feats, nullptr, seg_ids, sub_off, descs, pool, const_cast<int32_t*>(count), const_cast<int32_t*>(src), ids_out, nullptr,
+                  desc_dim, desc_out};
+    g.fill = true;
+    return g;
+}
+
 int roman_submaps_fill_dev(roman_ctx_t* c, int32_t point_dim, int32_t cap, int32_t N, int32_t F,
                            const double* seg_feats, const int64_t* seg_ids, int32_t S, const roman_submap_desc_t* descs,
                            const int32_t* count, const int32_t* src, double* pool, int64_t* ids_out, int32_t desc_dim, double* desc_out)
@@ -3228,21 +3139,10 @@ int roman_submaps_fill_dev(roman_ctx_t* c, int32_t point_dim, int32_t cap, int32
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     int rc = submaps_fill_check(c, point_dim, cap, N, F, seg_feats, seg_ids, S, descs, count, src, pool, ids_out, desc_dim, desc_out, true);
     if (rc || S == 0 || N == 0) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t stream = c->stream;
-    roman_submap_desc_t* staged = nullptr;
-    HIPCHK(c, c->smStage.stage((size_t)S, &staged));
-    memcpy(staged, descs, sizeof(roman_submap_desc_t) * (size_t)S);
-    HIPCHK(c, c->smStage.upload(c->smDesc, (size_t)S, stream));
-    const roman_submap_desc_t* dDesc = c->smDesc.as<roman_submap_desc_t>();
-    // the gather half of roman_submaps_dev, launched as there
-    const unsigned groups = (unsigned)std::min(64, (std::min(cap, N) + 3) / 4);
-    hipLaunchKernelGGL(k_submap_gather, dim3((unsigned)S, groups), dim3(256), 0, stream, (int)point_dim, (int)cap, (int)F, dDesc,
-                       reinterpret_cast<const unsigned long long*>(seg_feats), seg_ids, count, src, reinterpret_cast<unsigned long long*>(pool), ids_out);
-    if (desc_out) hipLaunchKernelGGL(k_submap_desc, dim3((unsigned)S, (unsigned)((desc_dim + 255) / 256)), dim3(256), 0, stream, (int)cap, (int)F, (int)desc_dim,
-                                     seg_feats, count, src, desc_out);
-    HIPCHK(c, hipGetLastError());
-    return ROMAN_OK;
+    const int64_t seg_off[2] = {0, N}; const int32_t sub_off[2] = {0, S};
+    roman_submap_params_t P;
+    const SubmapsArgs g = submaps_fill_args(&P, point_dim, cap, F, seg_off, seg_feats, seg_ids, sub_off, descs, count, src, pool, ids_out, desc_dim, desc_out);
+    return submaps_launch(c, &P, g);
 }
 
 int roman_submaps_fill(roman_ctx_t* c, int32_t point_dim, int32_t cap, int32_t N, int32_t F,
@@ -3261,25 +3161,10 @@ int roman_submaps_fill(roman_ctx_t* c, int32_t point_dim, int32_t cap, int32_t N
         }
     }
     if (N == 0) return ROMAN_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rc0 = use_ws0(c); if (rc0) return rc0; }
-    c->last.scored = false; c->last.solved = false;            // workspace 0's feature staging is reused: the stepwise problem it held is gone
-    const double* dFeats = nullptr;
-    rc = upload_inputs(c, seg_feats, N, F, 0, nullptr, 0, &dFeats);
-    if (rc) return rc;
-    const size_t rows = (size_t)S * (size_t)cap, bPool = sizeof(double) * rows * (size_t)(point_dim + F - 3);
-    HostMirror m(c);
-    const auto ids = m.in(seg_ids, seg_ids ? sizeof(int64_t) * (size_t)N : 0);
-    const auto dPool = pool ? m.inout(pool, bPool) : m.room<double>(bPool);     // without a pool the device call still writes one
-    const auto idsOut = m.inout(ids_out, ids_out ? sizeof(int64_t) * rows : 0);
-    const auto descOut = m.inout(desc_out, desc_out ? sizeof(double) * (size_t)S * (size_t)desc_dim : 0);
-    const auto dSrc = m.in(src, sizeof(int32_t) * rows);
-    const auto cnt = m.in(count, sizeof(int32_t) * (size_t)S);
-    rc = m.upload();
-    if (rc) return rc;
-    rc = roman_submaps_fill_dev(c, point_dim, cap, N, F, dFeats, ids.dev(), S, descs, cnt.dev(), dSrc.dev(), dPool.dev(), idsOut.dev(), desc_dim, descOut.dev());
-    if (rc) return rc;
-    return m.download();
+    const int64_t seg_off[2] = {0, N}; const int32_t sub_off[2] = {0, S};
+    roman_submap_params_t P;
+    const SubmapsArgs h = submaps_fill_args(&P, point_dim, cap, F, seg_off, seg_feats, seg_ids, sub_off, descs, count, src, pool, ids_out, desc_dim, desc_out);
+    return submaps_mirror(c, &P, h);
 }
 
 static int submap_boxes_check(roman_ctx* c, int32_t S, int32_t F, int32_t cap, const void* pool, const void* count, const void* T_odom_center, const void* box)

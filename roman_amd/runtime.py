@@ -6,6 +6,7 @@ without a gfx950 device raises RomanHipError.
 """
 import ctypes as C
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -452,7 +453,8 @@ class Context:
         # The stepwise problem lives in workspace 0 of the library, and the library forgets it (its `last.scored`) in two places:
         # on_next_workspace(), which every solver enqueue goes through (align_batch_dev, align_lc_batch_dev, mno_batch_dev,
         # mno_lc_batch_dev, and the host and resident forms built on them), and every host-pointer call that stages its inputs in
-        # workspace 0 (ransac_batch, ransac_lc_batch, the submap / gate / frame-select calls).  The batch wrappers among these
+        # workspace 0 (ransac_batch, ransac_lc_batch, the gate / frame-select calls; submaps() and submaps_fill() bump the counter too,
+        # although their map table travels through the host mirror: a holder then re-sends once more than it must).  The batch wrappers among these
         # bump the counter in ONE place, _workspace_call(); the stage calls further down bump it themselves.  The pure enqueues
         # that only read and write the caller's device buffers through small descriptor stagings of their own — lc_tail_dev,
         # mno_lc_tail_dev, ransac_batch_dev, ransac_lc_batch_dev, shared_ids_dev, shared_reduce_dev, and the other stage calls'
@@ -734,20 +736,32 @@ class Context:
                       None if lc_params is None else C.byref(lc_params),
                       *_vps(T_ref_ptr, enable_ptr, FL_ptr, iL_ptr, FR_ptr, iR_ptr, records_ptr, accepted_idx_ptr, n_accepted_ptr))
 
-    # ------------------------------------------------------------------ submaps from a whole map
+    # ------------------------------------------------------------------ submaps from a whole map, and from every map of a session
     @staticmethod
     def _submap_descs(descs):
         descs = np.ascontiguousarray(descs, dtype=submap_desc_dtype()).reshape(-1)
         assert descs.dtype.itemsize == _abi.SUBMAP_DESC_NBYTES
         return descs
 
-    def submaps(self, sparams, seg_feats, seg_times, descs, seg_ids=None, desc_dim=0, want_pool=True,
-                pool=None, src=None, ids_out=None, desc_out=None):
-        """Host-pointer submap extraction (roman_submaps): the radius mode of submaps_from_roman_map [REF roman/map/map.py:297-346]
-        for the S centres in `descs` (a submap_desc_dtype array) over the map table seg_feats (N, F) / seg_times (N, 2) /
-        seg_ids (N,).  sparams: a RomanSubmapParams.  Output arrays may be handed in (C-contiguous, the C ABI's shapes and
-        types): what the call leaves untouched comes back as it was; fresh ones are filled with 0 (pool), -1 (src, ids) and
-        NaN (descriptors).  -> SubmapsResult."""
+    @staticmethod
+    def _session_tables(seg_off, sub_off, descs, N=None):
+        """The two offset tables and the centres of a session of maps in the C ABI's types, sub_off[R] checked against the centres and
+        — with N, the host forms — seg_off[R] against the rows -> (seg_off int64[R+1], sub_off int32[R+1], R, descs)."""
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1); sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1)
+        if seg_off.shape[0] != sub_off.shape[0] or seg_off.shape[0] < 1:
+            raise ValueError("seg_off and sub_off must both hold R + 1 entries")
+        descs = Context._submap_descs(descs)
+        if N is None and int(sub_off[-1]) != int(descs.shape[0]):
+            raise ValueError("sub_off[R] must be the number of descs")
+        if N is not None and (int(seg_off[-1]) != N or int(sub_off[-1]) != int(descs.shape[0])):
+            raise ValueError("seg_off[R] must be the rows of seg_feats and sub_off[R] the number of descs")
+        return seg_off, sub_off, int(seg_off.shape[0]) - 1, descs
+
+    @staticmethod
+    def _map_tables(sparams, seg_feats, seg_times, seg_ids, descs, desc_dim, seg_off=None, sub_off=None):
+        """The map tables of a host-pointer submaps call in the C ABI's types, checked against each other, with the sizes that follow
+        from them: seg_feats (N, F), seg_times (N, 2), seg_ids (N,) or None, descs (S,), the offsets of a session (None: one map),
+        rows = S * cap, Fo the columns of a pool row, d = desc_dim."""
         seg_feats = _f64(seg_feats); seg_times = _f64(seg_times)
         if seg_feats.ndim != 2 or seg_times.shape != (seg_feats.shape[0], 2):
             raise ValueError("seg_feats must be (N, F) and seg_times (N, 2)")
@@ -756,17 +770,44 @@ class Context:
             seg_ids = np.ascontiguousarray(seg_ids, dtype=np.int64).reshape(-1)
             if seg_ids.shape[0] != N:
                 raise ValueError("seg_ids must hold one entry per segment")
-        descs = self._submap_descs(descs)
-        S, rows, Fo = int(descs.shape[0]), int(descs.shape[0]) * max(int(sparams.cap), 0), int(sparams.point_dim) + F - 3
-        d = int(desc_dim)
-        pool = _given(pool, (rows, max(Fo, 0)), np.float64, 0.0) if (want_pool or pool is not None) else None
-        src = _given(src, (rows,), np.int32, -1)
-        ids_out = _given(ids_out, (rows,), np.int64, -1) if seg_ids is not None else None
-        desc_out = _given(desc_out, (S, d), np.float64, np.nan) if d > 0 else None
-        count = np.zeros(S, dtype=np.int32); status = np.zeros(S, dtype=np.int32)
+        R = None
+        if seg_off is None:
+            descs = Context._submap_descs(descs)
+        else:
+            seg_off, sub_off, R, descs = Context._session_tables(seg_off, sub_off, descs, N)
+        S = int(descs.shape[0])
+        return SimpleNamespace(seg_feats=seg_feats, seg_times=seg_times, seg_ids=seg_ids, descs=descs, seg_off=seg_off, sub_off=sub_off, R=R, N=N, F=F, S=S,
+                               rows=S * max(int(sparams.cap), 0), Fo=int(sparams.point_dim) + F - 3, d=int(desc_dim))
+
+    @staticmethod
+    def _submap_outputs(t, pool, count, src, ids_out, status, desc_out, want_pool=True, in_place=False):
+        """The output arrays of a host-pointer submaps call over the tables `t`: the caller's (C-contiguous, the C ABI's shapes and types),
+        checked, or fresh ones filled with 0 (pool, count, status), -1 (src, ids) and NaN (descriptors).  in_place (the list form): they
+        are the session's current outputs — the four that must exist do, and ids and descriptors are there when they were handed in.
+        -> pool, count, src, ids_out, status, desc_out."""
+        if in_place and any(a is None for a in (pool, count, src, status)):
+            raise ValueError("pool, count, src and status are the session's current outputs: all are needed")
+        has_ids, has_desc = (ids_out is not None, desc_out is not None) if in_place else (t.seg_ids is not None, t.d > 0)
+        pool = _given(pool, (t.rows, max(t.Fo, 0)), np.float64, 0.0) if (want_pool or pool is not None) else None
+        count = _given(count, (t.S,), np.int32, 0)
+        src = _given(src, (t.rows,), np.int32, -1)
+        status = _given(status, (t.S,), np.int32, 0)
+        ids_out = _given(ids_out, (t.rows,), np.int64, -1) if has_ids else None
+        desc_out = _given(desc_out, (t.S, t.d), np.float64, np.nan) if has_desc else None
+        return pool, count, src, ids_out, status, desc_out
+
+    def submaps(self, sparams, seg_feats, seg_times, descs, seg_ids=None, desc_dim=0, want_pool=True,
+                pool=None, src=None, ids_out=None, desc_out=None):
+        """Host-pointer submap extraction (roman_submaps): the radius mode of submaps_from_roman_map [REF roman/map/map.py:297-346]
+        for the S centres in `descs` (a submap_desc_dtype array) over the map table seg_feats (N, F) / seg_times (N, 2) /
+        seg_ids (N,).  sparams: a RomanSubmapParams.  Output arrays may be handed in (C-contiguous, the C ABI's shapes and
+        types): what the call leaves untouched comes back as it was; fresh ones are filled with 0 (pool), -1 (src, ids) and
+        NaN (descriptors).  -> SubmapsResult."""
+        t = self._map_tables(sparams, seg_feats, seg_times, seg_ids, descs, desc_dim)
+        pool, count, src, ids_out, status, desc_out = self._submap_outputs(t, pool, None, src, ids_out, None, desc_out, want_pool)
         self._generation += 1
-        rc = self._lib.roman_submaps(self._h, C.byref(sparams), N, F, _ptr(seg_feats), _ptr(seg_times), _ptr(seg_ids), S, _ptr(descs),
-                                     _ptr(pool), _ptr(count), _ptr(src), _ptr(ids_out), _ptr(status), d, _ptr(desc_out))
+        rc = self._lib.roman_submaps(self._h, C.byref(sparams), t.N, t.F, _ptr(t.seg_feats), _ptr(t.seg_times), _ptr(t.seg_ids), t.S, _ptr(t.descs),
+                                     _ptr(pool), _ptr(count), _ptr(src), _ptr(ids_out), _ptr(status), t.d, _ptr(desc_out))
         self._check(rc, "roman_submaps")
         return SubmapsResult(pool, count, src, ids_out, status, desc_out)
 
@@ -780,42 +821,16 @@ class Context:
                                          _vp(status_ptr), int(desc_dim), _vp(desc_out_ptr))
         self._check(rc, "roman_submaps_dev")
 
-    # ------------------------------------------------------------------ the submaps of every map of a session
-    @staticmethod
-    def _session_offsets(seg_off, sub_off):
-        """The two offset tables of a session of maps in the C ABI's types -> (seg_off int64[R+1], sub_off int32[R+1], R)."""
-        seg_off = np.ascontiguousarray(seg_off, dtype=np.int64).reshape(-1); sub_off = np.ascontiguousarray(sub_off, dtype=np.int32).reshape(-1)
-        if seg_off.shape[0] != sub_off.shape[0] or seg_off.shape[0] < 1:
-            raise ValueError("seg_off and sub_off must both hold R + 1 entries")
-        return seg_off, sub_off, int(seg_off.shape[0]) - 1
-
     def session_submaps(self, sparams, seg_off, seg_feats, seg_times, sub_off, descs, seg_ids=None, desc_dim=0, want_pool=True,
                         pool=None, src=None, ids_out=None, desc_out=None):
         """Host-pointer submaps of the R maps of a session (roman_session_submaps): submaps() for every map in one
         call.  seg_feats (N, F) / seg_times (N, 2) / seg_ids (N,) are the R map tables concatenated in map order, map r owning the
         rows [seg_off[r], seg_off[r+1]) and the centres descs[sub_off[r]:sub_off[r+1]]; `src` holds map-local indices.  Output
         arrays as for submaps().  -> SubmapsResult over all sub_off[R] submaps."""
-        seg_feats = _f64(seg_feats); seg_times = _f64(seg_times)
-        if seg_feats.ndim != 2 or seg_times.shape != (seg_feats.shape[0], 2):
-            raise ValueError("seg_feats must be (N, F) and seg_times (N, 2)")
-        N, F = seg_feats.shape
-        if seg_ids is not None:
-            seg_ids = np.ascontiguousarray(seg_ids, dtype=np.int64).reshape(-1)
-            if seg_ids.shape[0] != N:
-                raise ValueError("seg_ids must hold one entry per segment")
-        seg_off, sub_off, R = self._session_offsets(seg_off, sub_off)
-        descs = self._submap_descs(descs)
-        S = int(descs.shape[0])
-        if int(seg_off[-1]) != N or int(sub_off[-1]) != S:
-            raise ValueError("seg_off[R] must be the rows of seg_feats and sub_off[R] the number of descs")
-        rows, Fo, d = S * max(int(sparams.cap), 0), int(sparams.point_dim) + F - 3, int(desc_dim)
-        pool = _given(pool, (rows, max(Fo, 0)), np.float64, 0.0) if (want_pool or pool is not None) else None
-        src = _given(src, (rows,), np.int32, -1)
-        ids_out = _given(ids_out, (rows,), np.int64, -1) if seg_ids is not None else None
-        desc_out = _given(desc_out, (S, d), np.float64, np.nan) if d > 0 else None
-        count = np.zeros(S, dtype=np.int32); status = np.zeros(S, dtype=np.int32)
-        self._enqueue("roman_session_submaps", C.byref(sparams), R, F, _ptr(seg_off), _ptr(seg_feats), _ptr(seg_times), _ptr(seg_ids), _ptr(sub_off),
-                      _ptr(descs), _ptr(pool), _ptr(count), _ptr(src), _ptr(ids_out), _ptr(status), d, _ptr(desc_out))
+        t = self._map_tables(sparams, seg_feats, seg_times, seg_ids, descs, desc_dim, seg_off, sub_off)
+        pool, count, src, ids_out, status, desc_out = self._submap_outputs(t, pool, None, src, ids_out, None, desc_out, want_pool)
+        self._enqueue("roman_session_submaps", C.byref(sparams), t.R, t.F, _ptr(t.seg_off), _ptr(t.seg_feats), _ptr(t.seg_times), _ptr(t.seg_ids),
+                      _ptr(t.sub_off), _ptr(t.descs), _ptr(pool), _ptr(count), _ptr(src), _ptr(ids_out), _ptr(status), t.d, _ptr(desc_out))
         return SubmapsResult(pool, count, src, ids_out, status, desc_out)
 
     def session_submaps_dev(self, sparams, F, seg_off, seg_feats_ptr, seg_times_ptr, sub_off, descs, pool_ptr, count_ptr, src_ptr, status_ptr,
@@ -823,10 +838,7 @@ class Context:
         """Device-pointer submaps of the R maps of a session (roman_session_submaps_dev): bulk pointers are device addresses
         (integers); seg_off, sub_off and `descs` (a submap_desc_dtype array over all sub_off[R] centres) are host arrays.  A pure
         enqueue on the context's stream; complete after sync()."""
-        seg_off, sub_off, R = self._session_offsets(seg_off, sub_off)
-        descs = self._submap_descs(descs)
-        if int(sub_off[-1]) != int(descs.shape[0]):
-            raise ValueError("sub_off[R] must be the number of descs")
+        seg_off, sub_off, R, descs = self._session_tables(seg_off, sub_off, descs)
         self._enqueue("roman_session_submaps_dev", C.byref(sparams), R, int(F), _ptr(seg_off), *_vps(seg_feats_ptr, seg_times_ptr, seg_ids_ptr),
                       _ptr(sub_off), _ptr(descs), *_vps(pool_ptr, count_ptr, src_ptr, ids_out_ptr, status_ptr), int(desc_dim), _vp(desc_out_ptr))
 
@@ -841,32 +853,13 @@ class Context:
         for session_submaps(); `lst` the global submap indices, strictly ascending; pool, count, src, status (and ids_out, desc_out) the
         session's CURRENT outputs (C-contiguous, the C ABI's shapes and types), which the call changes in the listed slots only.
         -> (SubmapsResult over the caller's arrays, changed int32[L] or None)."""
-        seg_feats = _f64(seg_feats); seg_times = _f64(seg_times)
-        if seg_feats.ndim != 2 or seg_times.shape != (seg_feats.shape[0], 2):
-            raise ValueError("seg_feats must be (N, F) and seg_times (N, 2)")
-        N, F = seg_feats.shape
-        if seg_ids is not None:
-            seg_ids = np.ascontiguousarray(seg_ids, dtype=np.int64).reshape(-1)
-            if seg_ids.shape[0] != N:
-                raise ValueError("seg_ids must hold one entry per segment")
-        seg_off, sub_off, R = self._session_offsets(seg_off, sub_off)
-        descs = self._submap_descs(descs)
-        S = int(descs.shape[0])
-        if int(seg_off[-1]) != N or int(sub_off[-1]) != S:
-            raise ValueError("seg_off[R] must be the rows of seg_feats and sub_off[R] the number of descs")
-        rows, Fo, d = S * max(int(sparams.cap), 0), int(sparams.point_dim) + F - 3, int(desc_dim)
-        for a, shape, dt in ((pool, (rows, max(Fo, 0)), np.float64), (count, (S,), np.int32), (src, (rows,), np.int32), (status, (S,), np.int32)):
-            if a is None:
-                raise ValueError("pool, count, src and status are the session's current outputs: all are needed")
-            _given(a, shape, dt, 0)
-        if ids_out is not None:
-            _given(ids_out, (rows,), np.int64, 0)
-        if desc_out is not None:
-            _given(desc_out, (S, d), np.float64, 0)
+        t = self._map_tables(sparams, seg_feats, seg_times, seg_ids, descs, desc_dim, seg_off, sub_off)
+        self._submap_outputs(t, pool, count, src, ids_out, status, desc_out, in_place=True)
         lst = self._submap_list(lst)
         changed = np.zeros(len(lst), dtype=np.int32) if want_changed else None
-        self._enqueue("roman_session_submaps_list", C.byref(sparams), R, F, _ptr(seg_off), _ptr(seg_feats), _ptr(seg_times), _ptr(seg_ids), _ptr(sub_off),
-                      _ptr(descs), _ptr(pool), _ptr(count), _ptr(src), _ptr(ids_out), _ptr(status), d, _ptr(desc_out), int(len(lst)), _ptr(lst), _ptr(changed))
+        self._enqueue("roman_session_submaps_list", C.byref(sparams), t.R, t.F, _ptr(t.seg_off), _ptr(t.seg_feats), _ptr(t.seg_times), _ptr(t.seg_ids),
+                      _ptr(t.sub_off), _ptr(t.descs), _ptr(pool), _ptr(count), _ptr(src), _ptr(ids_out), _ptr(status), t.d, _ptr(desc_out),
+                      int(len(lst)), _ptr(lst), _ptr(changed))
         return SubmapsResult(pool, count, src, ids_out, status, desc_out), changed
 
     def session_submaps_list_dev(self, sparams, F, seg_off, seg_feats_ptr, seg_times_ptr, sub_off, descs, lst, pool_ptr, count_ptr, src_ptr, status_ptr,
@@ -874,10 +867,7 @@ class Context:
         """Device-pointer rebuild of the LISTED submaps of a session in place (roman_session_submaps_list_dev): the arguments of
         session_submaps_dev over the whole session, `lst` the global submap indices (host, strictly ascending) and `changed_ptr` a
         device int32[L] or None.  A pure enqueue on the context's stream; complete after sync()."""
-        seg_off, sub_off, R = self._session_offsets(seg_off, sub_off)
-        descs = self._submap_descs(descs)
-        if int(sub_off[-1]) != int(descs.shape[0]):
-            raise ValueError("sub_off[R] must be the number of descs")
+        seg_off, sub_off, R, descs = self._session_tables(seg_off, sub_off, descs)
         lst = self._submap_list(lst)
         self._enqueue("roman_session_submaps_list_dev", C.byref(sparams), R, int(F), _ptr(seg_off), *_vps(seg_feats_ptr, seg_times_ptr, seg_ids_ptr),
                       _ptr(sub_off), _ptr(descs), *_vps(pool_ptr, count_ptr, src_ptr, ids_out_ptr, status_ptr), int(desc_dim), _vp(desc_out_ptr),

@@ -35,7 +35,7 @@ def test_entry_points_exported_and_declared():
         assert args[17] == "int32_t L" and args[18] == "const int32_t* list" and args[19] == "int32_t* changed"
         assert "[REF roman/map/map.py:297-346]" in src[max(0, at - 3500):at] and "§4.21" in src[max(0, at - 6000):at], s
     kern = open(os.path.join(ROOT, "roman_amd", "csrc", "kernels.hip.h")).read()
-    for k in ("k_session_submap_select_list", "k_session_submap_store_list"):
+    for k in ("k_submap_select", "k_submap_store_list"):
         assert f" {k}(" in kern, k
 
 

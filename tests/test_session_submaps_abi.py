@@ -34,7 +34,7 @@ def test_entry_points_exported_and_declared():
     at = src.index("ROMAN_API int roman_session_submaps_dev(")
     assert "[REF roman/map/map.py:297-346]" in src[max(0, at - 4000):at] and "§4.19" in src[max(0, at - 4000):at]
     kern = open(os.path.join(ROOT, "roman_amd", "csrc", "kernels.hip.h")).read()
-    for k in ("k_session_submap_points", "k_session_submap_select", "k_session_submap_gather", "k_session_submap_desc"):
+    for k in ("k_submap_points", "k_submap_select", "k_submap_gather", "k_submap_desc"):
         assert f" {k}(" in kern, k
 
 
