@@ -1469,6 +1469,71 @@ ROMAN_API int roman_segment_shapes(roman_ctx_t* ctx, const double* points, const
 ROMAN_API int roman_ctx_set_segment_block_min(roman_ctx_t* ctx, int32_t n);
 
 /*
+ * roman_assoc_scores_dev: the scores of the mapper's per-frame data association — what global_nearest_neighbor
+ * computes in its pair loop [REF roman/map/global_nearest_neighbor.py:23-36] for every (segment, observation) pair of a frame
+ * [REF roman/map/mapper.py:65-68] and merge() again for every pair of segments [REF roman/map/mapper.py:276-299]: the voxel IoU or
+ * IoM of the two point clouds, VoxelGrid.iou over VoxelGrid.from_points [REF roman/map/voxel_grid.py:32-103], optionally the cosine
+ * of their descriptors [REF roman/map/mapper.py:204-212], and the score.  Bulk data on the DEVICE; a PURE ENQUEUE on the context's
+ * stream: no synchronisation, no read-back.  All workspace is sized from cloud_off_host: P keys twice and one record per cloud.
+ *   points          float64[P][3]: N1 + N2 clouds one behind the other (self mode: N1), P = cloud_off_host[number of clouds]
+ *   cloud_off_dev   int64[clouds + 1] on the device, cloud_off_host the same numbers on the HOST: ascending, [0] == 0 (the
+ *                   contract of roman_segment_shapes_dev's seg_off).  The first N1 clouds are the ROWS of the outputs, the next
+ *                   N2 the COLUMNS
+ *   N2              >= 0, or -1: SELF mode, the N1 clouds against themselves (N1 x N1, every ordered pair is computed)
+ *   desc, d         float64[clouds][d] descriptors, read when params->semantic is 1; NULL with d == 0: no cloud has one, and the
+ *                   cosine of every pair is 1.0 [REF roman/map/mapper.py:208-209]
+ *   n_vox           int32[clouds] or NULL: occupied voxels of every cloud
+ *   status          int32[clouds]: ROMAN_ASSOC_OK; ROMAN_ASSOC_EMPTY: no point; ROMAN_ASSOC_RANGE: a coordinate is not finite or a
+ *                   voxel key needs more than 21 bits on an axis (|coordinate| / voxel_size beyond 2^20).  An EMPTY or RANGE cloud
+ *                   has no voxel: n_vox 0 and geo 0.0 against everything.  (The reference's from_points raises on an empty cloud and
+ *                   the mapper never passes one: this rule is this library's.)
+ *   inter           int32[N1 * N2] or NULL: voxels both clouds hold inside the intersection of their integer boxes
+ *   geo             float64[N1 * N2]: IoU inter / (va + vb - inter) or IoM inter / min(va, vb) of the volumes n_vox * voxel_size**3,
+ *                   0.0 for a zero denominator, in the reference's operation order: bit for bit what the reference's arithmetic
+ *                   gives.  One line is UNPINNED: the grid index of a point, open3d's VoxelGrid.create_from_point_cloud, is
+ *                   restated by open3d's documented rule (origin = min_bound - voxel_size / 2, index = floor((p - origin) /
+ *                   voxel_size)) and has not been compared with a real open3d
+ *   sem             float64[N1 * N2] or NULL: the cosine; written only when params->semantic is 1.  A zero descriptor gives NaN
+ *   score           float64[N1 * N2]: 1e9 where a similarity is below its range[0]; otherwise -geo (one criterion) or
+ *                   -sqrt(((geo - g0) / (g1 - g0)) * ((sem - s0) / (s1 - s0))) (two; the reference writes np.power(x, 1 / 2), this
+ *                   is the correctly rounded square root).  Comparisons are IEEE: a NaN similarity gives a NaN score
+ * Integer counts and a fixed summation order: two calls give the same bits.  N1 == 0 or N2 == 0: ROMAN_OK, nothing written.
+ * Errors (ROMAN_E_INVALID with a roman_last_error text, nothing enqueued): NULL params; voxel_size not finite or <= 0; an unknown
+ * geometric method; semantic not 0 / 1; range[1] == range[0] or a NaN in a range that is in use; N1 < 0,
+ * N2 < -1; NULL cloud_off_host, [0] != 0 or descending; d < 0; NULL desc with d > 0, or desc with d == 0, when semantic is 1; NULL
+ * points with P > 0; NULL geo / score / status with N1, N2 != 0; NULL ctx; NULL cloud_off_dev.  More than INT32_MAX points in a
+ * cloud, more than 2^30 pairs or 2^30 clouds: ROMAN_E_TOO_LARGE.
+ */
+#define ROMAN_ASSOC_IOU   0
+#define ROMAN_ASSOC_IOM   1
+#define ROMAN_ASSOC_OK    0
+#define ROMAN_ASSOC_EMPTY 1
+#define ROMAN_ASSOC_RANGE 2
+#define ROMAN_ASSOC_WAVE_MAX  256   /* a cloud of at most so many points is sorted by one wave (roman_ctx_set_assoc_cuts)            */
+#define ROMAN_ASSOC_LDS_MAX  8192   /* ... of at most so many by one workgroup in LDS; longer clouds merge through a global ping-pong */
+typedef struct roman_assoc_params {
+    double  voxel_size;        /* > 0, finite (iou_voxel_size) */
+    int32_t geometric;         /* ROMAN_ASSOC_IOU | ROMAN_ASSOC_IOM */
+    int32_t semantic;          /* 0: none, 1: cosine over `desc` */
+    double  geo_range[2];      /* threshold, maximum (geometric_score_range) */
+    double  sem_range[2];      /* (semantic_score_range); read when semantic is 1 */
+} roman_assoc_params_t;
+ROMAN_API int roman_assoc_scores_dev(roman_ctx_t* ctx, const roman_assoc_params_t* params, const double* points, const int64_t* cloud_off_dev,
+                                     const int64_t* cloud_off_host, int32_t N1, int32_t N2, const double* desc, int32_t d,
+                                     int32_t* n_vox, int32_t* inter, double* geo, double* sem, double* score, int32_t* status);
+
+/* The same with HOST pointers everywhere.  Synchronous. */
+ROMAN_API int roman_assoc_scores(roman_ctx_t* ctx, const roman_assoc_params_t* params, const double* points, const int64_t* cloud_off,
+                                 int32_t N1, int32_t N2, const double* desc, int32_t d,
+                                 int32_t* n_vox, int32_t* inter, double* geo, double* sem, double* score, int32_t* status);
+
+/* Measurement only: the two point counts at which roman_assoc_scores* changes the kernel that sorts a cloud's keys — up to wave_max
+   one wave, up to lds_max one workgroup in LDS, beyond it one workgroup that sorts chunks of lds_max keys and merges them in global
+   memory.  0: the default again (ROMAN_ASSOC_WAVE_MAX, ROMAN_ASSOC_LDS_MAX); wave_max <= 512, wave_max <= lds_max, 2 <= lds_max <= 8192.
+   Every path gives the same sorted keys, so results do not depend on the cuts. */
+ROMAN_API int roman_ctx_set_assoc_cuts(roman_ctx_t* ctx, int32_t wave_max, int32_t lds_max);
+
+/*
  * roman_session_gate_aabb_dev: roman_session_gate_dev with the bounding-box gate [REF roman/align/submap_align.py:101-103]
  * — what roman_grid_gate_aabb_dev is to roman_grid_gate_dev.  The arguments are roman_session_gate_dev's; then
  *   box        float64[S][6] over ALL submaps of the session, as roman_session_boxes_dev wrote them.  NEARBY is the six comparisons

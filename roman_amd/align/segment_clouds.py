@@ -114,6 +114,26 @@ class SegmentClouds:
             desc = np.ascontiguousarray(np.stack([np.asarray(s.semantic_descriptor, dtype=np.float64).reshape(-1) for s in segments]))
         return cls(points, seg_off, ids, times, desc)
 
+    @classmethod
+    def from_observations(cls, observations):
+        """The clouds of a frame's observations for the data association (roman_amd.map.association): reads
+        .transformed_points — the cloud in the world frame, what Observation.get_voxel_grid voxelises
+        [REF roman/map/observation.py:38-51] — .semantic_descriptor and, where present, .time of reference-style Observations.
+        An observation whose points are None holds no point; the descriptors are kept when every observation has one; ids are the
+        positions in the list."""
+        n = len(observations)
+        clouds = [np.zeros((0, 3)) if o.transformed_points is None else np.asarray(o.transformed_points, dtype=np.float64).reshape(-1, 3)
+                  for o in observations]
+        seg_off = np.zeros(n + 1, dtype=np.int64)
+        if n:
+            seg_off[1:] = np.cumsum([len(c) for c in clouds])
+        points = np.ascontiguousarray(np.vstack(clouds)) if n else np.zeros((0, 3))
+        times = np.array([[getattr(o, "time", 0.0)] * 2 for o in observations], dtype=np.float64).reshape(n, 2)
+        desc = None
+        if n and all(getattr(o, "semantic_descriptor", None) is not None for o in observations):
+            desc = np.ascontiguousarray(np.stack([np.asarray(o.semantic_descriptor, dtype=np.float64).reshape(-1) for o in observations]))
+        return cls(points, seg_off, np.arange(n, dtype=np.int64), times, desc)
+
     def __len__(self):
         return int(np.asarray(self.seg_off).shape[0]) - 1
 

@@ -9139,4 +9139,346 @@ __global__ void __launch_bounds__(256) k_seg_shapes_block(SegShapeArgs A, int fi
     seg_shape_team<4>(A, A.items[first + (int)blockIdx.x], L, (int)threadIdx.x);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Frame data association: voxel IoU / IoM of every (row cloud, column cloud) pair, the cosine of their
+// descriptors and the score global_nearest_neighbor puts in front of the Hungarian solve [REF roman/map/global_nearest_neighbor.py:
+// 23-36] over VoxelGrid.iou [REF roman/map/voxel_grid.py:32-103].  Integer set operations throughout:
+//   1. per cloud the box (float corners as the reference forms them, their TRUNCATED integers) and one 64-bit key per point,
+//      three biased 21-bit axes of min_corner_int + grid_index, x the most significant;
+//   2. per cloud the keys sorted ascending without duplicates in the cloud's slice of the key workspace, their number = n_vox.
+//      A TEAM takes one cloud: one wave (k_assoc_keys_wave, four clouds per workgroup, a bitonic sort in ASSOC_WAVE_CAP keys of
+//      LDS), a workgroup sorting in ASSOC_LDS_CAP keys of LDS (k_assoc_keys_block<false>), or a workgroup that sorts LDS-sized
+//      chunks and merges them through a global ping-pong of the cloud's own size (k_assoc_keys_block<true>);
+//   3. per pair one wave (k_assoc_pairs): the reference's float test on the corners, then the lanes walk the shorter key list,
+//      reject keys outside [lo, hi) and binary-search the longer one; ballots sum the hits.
+// Counts are integers, so inter, n_vox and geo do not depend on any order; the cosine's sum has a fixed lane order and a fixed
+// butterfly.  No atomics anywhere.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int ASSOC_ST_OK = 0, ASSOC_ST_EMPTY = 1, ASSOC_ST_RANGE = 2;          // ROMAN_ASSOC_OK / _EMPTY / _RANGE
+constexpr int ASSOC_WAVE_CAP = 512;          // keys of LDS one wave sorts in
+constexpr int ASSOC_LDS_CAP = 8192;          // keys of LDS a workgroup sorts in (64 KB)
+constexpr int ASSOC_WAVE_MAX = 256;          // ROMAN_ASSOC_WAVE_MAX: a cloud of at most so many points is one wave's (profiles/assoc_scores/README.md)
+constexpr int ASSOC_LDS_MAX = ASSOC_LDS_CAP; // ROMAN_ASSOC_LDS_MAX: ... of at most so many is sorted in LDS alone
+constexpr long long ASSOC_KEY_BIAS = 1ll << 20;
+constexpr unsigned long long ASSOC_KEY_PAD = ~0ull;                            // sorts behind every key (a key has 63 bits)
+
+struct AssocCloud {                          // what stage 3 reads of a cloud
+    double minc[3], maxc[3];                 // min_corner, max_corner [REF roman/map/voxel_grid.py:90-91]
+    int32_t mci[3], maxci[3];                // min_corner_int, max_corner_int [REF :25-30]
+    int32_t n, status;                       // distinct keys; ASSOC_ST_*
+};
+
+struct AssocKeyArgs {
+    const double* pts;                       // (P, 3)
+    const int64_t* off;                      // [NC + 1]
+    const int32_t* items;                    // the host-cut list: the clouds of the wave kernel, of the LDS kernel, of the merge kernel
+    unsigned long long* keys;                // [P]: cloud c's sorted distinct keys from off[c] on
+    unsigned long long* scratch;             // [P]: the merge kernel's other half
+    AssocCloud* rec; int32_t* n_vox; int32_t* status;
+    double vs; int chunk;                    // voxel size; keys per LDS-sorted chunk of the merge kernel (<= ASSOC_LDS_CAP)
+};
+
+template <int NW, int CAP> struct AssocLds {
+    double stage[3 * 64 * NW];
+    double red[NW * 6];
+    int cnt[NW];
+    unsigned long long k[CAP];
+};
+
+struct AssocBox { double minc[3], maxc[3], origin[3]; long long mci[3], maxci[3]; bool fits; };
+
+// The box of a cloud from its coordinate minima and maxima, in the oracle's operation order (tests/_voxel_oracle.py; the library
+// is built with -ffp-contract=off and these are IEEE divisions: the truncation cases depend on the last bit).  fits: every key
+// axis + 2^20 is in [0, 2^21).
+__device__ __forceinline__ void assoc_box(const double (&mn)[3], const double (&mx)[3], bool finite, double vs, AssocBox& B)
+{
+#pragma clang fp contract(off)
+    B.fits = finite;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        B.minc[k] = floor(mn[k] / vs) * vs;
+        B.maxc[k] = ceil(mx[k] / vs) * vs;
+        B.origin[k] = mn[k] - vs * 0.5;       // UNPINNED: open3d's documented rule for VoxelGrid.create_from_point_cloud
+        const double t = trunc(B.minc[k] / vs), top = t + floor((mx[k] - B.origin[k]) / vs);
+        B.fits = B.fits && t >= -(double)ASSOC_KEY_BIAS && top <= (double)(ASSOC_KEY_BIAS - 1);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        B.mci[k] = B.fits ? (long long)(B.minc[k] / vs) : 0ll;                  // astype(int64): toward zero
+        B.maxci[k] = B.fits ? (long long)(B.maxc[k] / vs) : 0ll;
+    }
+}
+
+__device__ __forceinline__ unsigned long long assoc_key(double x, double y, double z, const AssocBox& B, double vs)
+{
+#pragma clang fp contract(off)
+    const long long kx = B.mci[0] + (long long)floor((x - B.origin[0]) / vs) + ASSOC_KEY_BIAS;
+    const long long ky = B.mci[1] + (long long)floor((y - B.origin[1]) / vs) + ASSOC_KEY_BIAS;
+    const long long kz = B.mci[2] + (long long)floor((z - B.origin[2]) / vs) + ASSOC_KEY_BIAS;
+    return ((unsigned long long)kx << 42) | ((unsigned long long)ky << 21) | (unsigned long long)kz;
+}
+
+// seg_sweep with the point's index inside the swept range: f(i, x, y, z)
+template <int NW, typename F>
+__device__ __forceinline__ void assoc_sweep(const double* __restrict__ pts, int64_t p0, int64_t n, double* stage, int tid, F f)
+{
+    constexpr int NT = 64 * NW;
+    for (int64_t c0 = 0; c0 < n; c0 += NT) {
+        const int m = n - c0 < (int64_t)NT ? (int)(n - c0) : NT;
+        const double* src = pts + 3 * (p0 + c0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const int e = tid + k * NT; if (e < 3 * m) stage[e] = src[e]; }
+        seg_sync<NW>();
+        if (tid < m) f(c0 + tid, stage[3 * tid], stage[3 * tid + 1], stage[3 * tid + 2]);
+        seg_sync<NW>();
+    }
+}
+
+// the m keys of k (m a power of two, in LDS) ascending; ends behind a barrier
+template <int NW> __device__ __forceinline__ void assoc_bitonic(unsigned long long* k, int m, int tid)
+{
+    constexpr int NT = 64 * NW;
+    for (int size = 2; size <= m; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < (m >> 1); t += NT) {
+                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                const unsigned long long a = k[i], b = k[j];
+                if ((a > b) == ((i & size) == 0)) { k[i] = b; k[j] = a; }
+            }
+            seg_sync<NW>();
+        }
+}
+
+// the distinct keys of the ascending src[0..n) -> dst, in order; returns their number on every thread
+template <int NW>
+__device__ __forceinline__ int assoc_unique(const unsigned long long* src, int64_t n, unsigned long long* __restrict__ dst, int* cnt, int tid)
+{
+    constexpr int NT = 64 * NW;
+    const int lane = tid & 63, wave = tid >> 6;
+    int base = 0;
+    for (int64_t c0 = 0; c0 < n; c0 += NT) {
+        const int64_t i = c0 + tid;
+        unsigned long long v = 0ull;
+        bool first = false;
+        if (i < n) { v = src[i]; first = i == 0 || src[i - 1] != v; }
+        const unsigned long long m = __ballot(first);
+        int before = __popcll(m & ((1ull << lane) - 1ull)), total = __popcll(m);
+        if (NW > 1) {
+            if (lane == 0) cnt[wave] = total;
+            __syncthreads();
+            total = 0;
+            for (int w = 0; w < NW; ++w) { const int c = cnt[w]; if (w < wave) before += c; total += c; }
+            __syncthreads();
+        }
+        if (first) dst[base + before] = v;
+        base += total;
+    }
+    return base;
+}
+
+// what the first sweep over a cloud leaves: the box, and the record of a cloud without voxels (returns false for those)
+template <int NW>
+__device__ __forceinline__ bool assoc_cloud_box(const AssocKeyArgs& A, int c, int64_t p0, int64_t n, double* stage, double* red, int tid, AssocBox& B)
+{
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    int bad = 0;
+    assoc_sweep<NW>(A.pts, p0, n, stage, tid, [&](int64_t, double x, double y, double z) {
+        lo[0] = fmin(lo[0], x); lo[1] = fmin(lo[1], y); lo[2] = fmin(lo[2], z);
+        hi[0] = fmax(hi[0], x); hi[1] = fmax(hi[1], y); hi[2] = fmax(hi[2], z);
+        bad |= (int)!(fabs(x) < INFINITY) | (int)!(fabs(y) < INFINITY) | (int)!(fabs(z) < INFINITY);
+    });
+    seg_team_minmax<NW>(lo, hi, red, tid);
+    bad = NW == 1 ? __any(bad) : __syncthreads_or(bad);
+    if (n > 0) assoc_box(lo, hi, !bad, A.vs, B); else B.fits = false;
+    if (B.fits) return true;
+    if (tid == 0) {
+        AssocCloud R = {};
+        R.status = n > 0 ? ASSOC_ST_RANGE : ASSOC_ST_EMPTY;
+        A.rec[c] = R; A.status[c] = R.status;
+        if (A.n_vox) A.n_vox[c] = 0;
+    }
+    return false;
+}
+
+__device__ __forceinline__ void assoc_cloud_done(const AssocKeyArgs& A, int c, const AssocBox& B, int n_keys)
+{
+    AssocCloud R;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { R.minc[k] = B.minc[k]; R.maxc[k] = B.maxc[k]; R.mci[k] = (int32_t)B.mci[k]; R.maxci[k] = (int32_t)B.maxci[k]; }
+    R.n = n_keys; R.status = ASSOC_ST_OK;
+    A.rec[c] = R; A.status[c] = ASSOC_ST_OK;
+    if (A.n_vox) A.n_vox[c] = n_keys;
+}
+
+__device__ __forceinline__ int assoc_pow2(int n) { int m = 2; while (m < n) m <<= 1; return m; }
+
+// the keys of the points [p0, p0 + len) sorted in L.k (len <= CAP; the padding behind them sorts last)
+template <int NW, int CAP>
+__device__ __forceinline__ void assoc_sort_chunk(const AssocKeyArgs& A, const AssocBox& B, int64_t p0, int len, AssocLds<NW, CAP>& L, int tid)
+{
+    const int m = assoc_pow2(len);
+    for (int i = len + tid; i < m; i += 64 * NW) L.k[i] = ASSOC_KEY_PAD;
+    assoc_sweep<NW>(A.pts, p0, len, L.stage, tid, [&](int64_t i, double x, double y, double z) { L.k[i] = assoc_key(x, y, z, B, A.vs); });
+    assoc_bitonic<NW>(L.k, m, tid);
+}
+
+// a cloud of at most CAP points: box, keys, sort and compaction without leaving LDS
+template <int NW, int CAP>
+__device__ __forceinline__ void assoc_cloud_lds(const AssocKeyArgs& A, int c, AssocLds<NW, CAP>& L, int tid)
+{
+    const int64_t p0 = A.off[c], n = A.off[c + 1] - p0;
+    AssocBox B;
+    if (!assoc_cloud_box<NW>(A, c, p0, n, L.stage, L.red, tid, B)) return;
+    assoc_sort_chunk<NW, CAP>(A, B, p0, (int)n, L, tid);
+    const int nk = assoc_unique<NW>(L.k, n, A.keys + p0, L.cnt, tid);
+    if (tid == 0) assoc_cloud_done(A, c, B, nk);
+}
+
+// one wave per listed cloud of at most ASSOC_WAVE_CAP points, four to a workgroup; the waves never meet at a workgroup barrier
+__global__ void __launch_bounds__(256) k_assoc_keys_wave(AssocKeyArgs A, int n_items)
+{
+    __shared__ AssocLds<1, ASSOC_WAVE_CAP> L[4];
+    const int wave = (int)threadIdx.x >> 6, it = (int)blockIdx.x * 4 + wave;
+    if (it >= n_items) return;
+    assoc_cloud_lds<1, ASSOC_WAVE_CAP>(A, A.items[it], L[wave], (int)threadIdx.x & 63);
+}
+
+// One workgroup per listed cloud, from item `first` on.  MERGE false: at most ASSOC_LDS_CAP points, sorted in LDS.  MERGE true:
+// any number — chunks of A.chunk keys are sorted in LDS and written to one half of the ping-pong (the cloud's slices of A.keys and
+// A.scratch), then runs are merged pairwise, every element finding its place by a binary search in the sibling run (stable: lower
+// bound for the left run's elements, upper bound for the right's), until one run is left.  The first half is chosen so that the
+// last pass ends in A.scratch; the compaction writes A.keys.  Every write stays inside the cloud's own n elements.
+template <bool MERGE>
+__global__ void __launch_bounds__(256) k_assoc_keys_block(AssocKeyArgs A, int first)
+{
+    __shared__ AssocLds<4, ASSOC_LDS_CAP> L;
+    const int tid = (int)threadIdx.x, c = A.items[first + (int)blockIdx.x];
+    if (!MERGE) { assoc_cloud_lds<4, ASSOC_LDS_CAP>(A, c, L, tid); return; }
+    const int64_t p0 = A.off[c], n = A.off[c + 1] - p0;
+    AssocBox B;
+    if (!assoc_cloud_box<4>(A, c, p0, n, L.stage, L.red, tid, B)) return;
+    const int64_t chunk = A.chunk;
+    int passes = 0;
+    for (int64_t w = chunk; w < n; w <<= 1) ++passes;
+    unsigned long long* src = (passes & 1) ? A.keys + p0 : A.scratch + p0;
+    unsigned long long* dst = (passes & 1) ? A.scratch + p0 : A.keys + p0;
+    for (int64_t c0 = 0; c0 < n; c0 += chunk) {
+        const int len = n - c0 < chunk ? (int)(n - c0) : (int)chunk;
+        assoc_sort_chunk<4, ASSOC_LDS_CAP>(A, B, p0 + c0, len, L, tid);
+        for (int i = tid; i < len; i += 256) src[c0 + i] = L.k[i];
+        __syncthreads();
+    }
+    for (int64_t w = chunk; w < n; w <<= 1) {
+        for (int64_t i = tid; i < n; i += 256) {
+            const int64_t base = i / (2 * w) * (2 * w), mid = base + w < n ? base + w : n, end = base + 2 * w < n ? base + 2 * w : n;
+            const unsigned long long v = src[i];
+            const bool left = i < mid;
+            int64_t lo = left ? mid : base, hi = left ? end : mid;              // the sibling run
+            const int64_t s0 = lo;
+            while (lo < hi) {
+                const int64_t m = (lo + hi) >> 1;
+                const unsigned long long o = src[m];
+                if (left ? o < v : o <= v) lo = m + 1; else hi = m;
+            }
+            dst[base + (i - (left ? base : mid)) + (lo - s0)] = v;
+        }
+        __syncthreads();
+        unsigned long long* t = src; src = dst; dst = t;
+    }
+    const int nk = assoc_unique<4>(src, n, A.keys + p0, L.cnt, tid);            // src is A.scratch here
+    if (tid == 0) assoc_cloud_done(A, c, B, nk);
+}
+
+// the Euclidean norm of every descriptor: one wave per row, lane l adds the squares of columns l, l + 64, ... in order, then a
+// fixed butterfly
+__device__ __forceinline__ double assoc_butterfly(double v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__global__ void __launch_bounds__(256) k_assoc_norms(const double* __restrict__ desc, int d, int rows, double* __restrict__ norm)
+{
+    const int lane = (int)threadIdx.x & 63, r = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (r >= rows) return;
+    const double* v = desc + (int64_t)r * d;
+    double s = 0.0;
+    for (int k = lane; k < d; k += 64) s += v[k] * v[k];
+    s = assoc_butterfly(s);
+    if (lane == 0) norm[r] = sqrt(s);
+}
+
+struct AssocPairArgs {
+    const AssocCloud* rec; const unsigned long long* keys; const int64_t* off;
+    const double* desc; const double* norm; int d;        // d == 0: no descriptors, the cosine is 1.0 [REF roman/map/mapper.py:208-209]
+    int N1, N2, col0;                                     // columns are the clouds col0 .. col0 + N2 - 1 (self mode: col0 == 0)
+    int iom, semantic;
+    double vs3, glo, ghi, slo, shi;                       // voxel_size**3; the two score ranges
+    int32_t* inter; double* geo; double* sem; double* score;
+};
+
+// one wave per (row, column), four to a workgroup
+__global__ void __launch_bounds__(256) k_assoc_pairs(AssocPairArgs A)
+{
+#pragma clang fp contract(off)
+    const int lane = (int)threadIdx.x & 63;
+    const int64_t p = (int64_t)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (p >= (int64_t)A.N1 * A.N2) return;
+    const int i = (int)(p / A.N2), j = A.col0 + (int)(p % A.N2);
+    const AssocCloud a = A.rec[i], b = A.rec[j];
+    int cnt = 0;
+    if (a.n > 0 && b.n > 0) {
+        bool open = true;                                  // np.any(min_corner >= max_corner) -> 0.0 [REF roman/map/voxel_grid.py:35-40]
+        long long lo[3], hi[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            open = open && !(fmax(a.minc[k], b.minc[k]) >= fmin(a.maxc[k], b.maxc[k]));
+            lo[k] = (a.mci[k] > b.mci[k] ? a.mci[k] : b.mci[k]) + ASSOC_KEY_BIAS;
+            hi[k] = (a.maxci[k] < b.maxci[k] ? a.maxci[k] : b.maxci[k]) + ASSOC_KEY_BIAS;
+            open = open && lo[k] < hi[k];
+        }
+        if (open) {
+            const bool a_short = a.n <= b.n;
+            const unsigned long long* S = A.keys + A.off[a_short ? i : j];
+            const unsigned long long* Lk = A.keys + A.off[a_short ? j : i];
+            const int nS = a_short ? a.n : b.n, nL = a_short ? b.n : a.n;
+            for (int s0 = 0; s0 < nS; s0 += 64) {
+                bool hit = false;
+                if (s0 + lane < nS) {
+                    const unsigned long long v = S[s0 + lane];
+                    const long long x = (long long)(v >> 42), y = (long long)((v >> 21) & 0x1fffffull), z = (long long)(v & 0x1fffffull);
+                    if (x >= lo[0] && x < hi[0] && y >= lo[1] && y < hi[1] && z >= lo[2] && z < hi[2]) {
+                        int l = 0, h = nL;
+                        while (l < h) { const int m = (l + h) >> 1; if (Lk[m] < v) l = m + 1; else h = m; }
+                        hit = l < nL && Lk[l] == v;
+                    }
+                }
+                cnt += __popcll(__ballot(hit));
+            }
+        }
+    }
+    // volume = num_occupied * vs**3, intersection = count * vs**3, then [REF roman/map/voxel_grid.py:75-83] in its order
+    const double va = (double)a.n * A.vs3, vb = (double)b.n * A.vs3, iv = (double)cnt * A.vs3;
+    double geo;
+    if (A.iom) { const double m = fmin(va, vb); geo = m == 0.0 ? 0.0 : iv / m; }
+    else { const double den = va + vb - iv; geo = den == 0.0 ? 0.0 : iv / den; }
+    double sem = 1.0;
+    if (A.semantic && A.d > 0) {
+        const double* u = A.desc + (int64_t)i * A.d;
+        const double* w = A.desc + (int64_t)j * A.d;
+        double s = 0.0;
+        for (int k = lane; k < A.d; k += 64) s += u[k] * w[k];
+        sem = assoc_butterfly(s) / (A.norm[i] * A.norm[j]);
+    }
+    // [REF roman/map/global_nearest_neighbor.py:27-36]: IEEE comparisons, so a NaN similarity is not below its threshold
+    double score;
+    if (geo < A.glo || (A.semantic && sem < A.slo)) score = 1e9;
+    else if (!A.semantic) score = -geo;
+    else score = -sqrt(((geo - A.glo) / (A.ghi - A.glo)) * ((sem - A.slo) / (A.shi - A.slo)));
+    if (lane == 0) {
+        if (A.inter) A.inter[p] = cnt;
+        A.geo[p] = geo; A.score[p] = score;
+        if (A.semantic && A.sem) A.sem[p] = sem;
+    }
+}
+
 }  // namespace roman

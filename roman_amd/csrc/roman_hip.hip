@@ -206,6 +206,11 @@ struct roman_ctx {
     DevBuf segItems;
     PinnedStage<int32_t> segStage;
     int seg_block_min = SEG_BLOCK_MIN;         // points from which a segment takes a workgroup (roman_ctx_set_segment_block_min)
+    // association scores (roman_assoc_scores*): the key workspace and its merge half (P keys each), one record and one descriptor
+    // norm per cloud, and the host-cut cloud list through pinned staging (a pure enqueue)
+    DevBuf asKeys, asScratch, asRec, asNorm, asItems;
+    PinnedStage<int32_t> asStage;
+    int assoc_wave_max = ASSOC_WAVE_MAX, assoc_lds_max = ASSOC_LDS_MAX;   // the two path cuts (roman_ctx_set_assoc_cuts)
 
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
@@ -1462,6 +1467,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     c->ssNorm.release(); c->ssBand.release(); c->ssR.release(); c->ssItems.release(); c->ssStage.release();
     c->sfTab.release(); c->sfStage.release();
     c->segItems.release(); c->segStage.release();
+    c->asKeys.release(); c->asScratch.release(); c->asRec.release(); c->asNorm.release(); c->asItems.release(); c->asStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -3265,6 +3271,17 @@ static_assert(SEG_BLOCK_MIN == ROMAN_SEG_BLOCK_MIN && SEG_ST_EMPTY == ROMAN_SEG_
               SEG_ST_DEGENERATE == ROMAN_SEG_DEGENERATE, "kernels.hip.h and roman_hip.h name the same numbers");
 static_assert(sizeof(roman_segment_shape_params_t) == 32, "roman_segment_shape_params_t is eight int32 words");
 
+// the offsets of N point clouds stored one behind the other (seg_off of roman_segment_shapes*, cloud_off of roman_assoc_scores*)
+static int cloud_offsets_check(roman_ctx* c, const int64_t* off, int64_t N, const char* name, const char* item)
+{
+    if (off[0] != 0) return fail(c, ROMAN_E_INVALID, "%s[0] = %lld: the first %s starts at row 0", name, (long long)off[0], item);
+    for (int64_t i = 0; i < N; ++i) {
+        if (off[i + 1] < off[i]) return fail(c, ROMAN_E_INVALID, "%s descends at %s %lld", name, item, (long long)i);
+        if (off[i + 1] - off[i] > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "%s %lld holds more than %d points", item, (long long)i, INT32_MAX);
+    }
+    return ROMAN_OK;
+}
+
 // everything roman_segment_shapes* judge on host memory -> *P_out: the rows of `points`
 static int segment_shapes_check(roman_ctx* c, const void* points, const int64_t* seg_off, int32_t N, const roman_segment_shape_params_t* P,
                                 const void* out, const void* status, int64_t* P_out)
@@ -3273,11 +3290,7 @@ static int segment_shapes_check(roman_ctx* c, const void* points, const int64_t*
     if (!P) return fail(c, ROMAN_E_INVALID, "params is NULL");
     if (!seg_off) return fail(c, ROMAN_E_INVALID, "seg_off is NULL");
     if (N < 0) return fail(c, ROMAN_E_INVALID, "N < 0");
-    if (seg_off[0] != 0) return fail(c, ROMAN_E_INVALID, "seg_off[0] = %lld: the first segment starts at row 0", (long long)seg_off[0]);
-    for (int32_t i = 0; i < N; ++i) {
-        if (seg_off[i + 1] < seg_off[i]) return fail(c, ROMAN_E_INVALID, "seg_off descends at segment %d", i);
-        if (seg_off[i + 1] - seg_off[i] > (int64_t)INT32_MAX) return fail(c, ROMAN_E_TOO_LARGE, "segment %d holds more than %d points", i, INT32_MAX);
-    }
+    { const int rc = cloud_offsets_check(c, seg_off, N, "seg_off", "segment"); if (rc) return rc; }
     if (P->center_ref != ROMAN_CENTER_MEAN && P->center_ref != ROMAN_CENTER_BOTTOM_MIDDLE) return fail(c, ROMAN_E_INVALID, "unknown center_ref %d", P->center_ref);
     if (P->out_stride < 1) return fail(c, ROMAN_E_INVALID, "out_stride must be >= 1 (got %d)", P->out_stride);
     if (P->col_center < 0) return fail(c, ROMAN_E_INVALID, "col_center = %d: the centre is always written", P->col_center);
@@ -3348,6 +3361,126 @@ int roman_ctx_set_segment_block_min(roman_ctx_t* c, int32_t n)
     if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
     if (n < 0) return fail(c, ROMAN_E_INVALID, "n must be >= 0 (0: the default)");
     c->seg_block_min = n ? n : SEG_BLOCK_MIN;
+    return ROMAN_OK;
+}
+
+// --- frame data association: voxel IoU / IoM, cosine and score of every cloud pair ---------------------------------
+static_assert(ASSOC_ST_OK == ROMAN_ASSOC_OK && ASSOC_ST_EMPTY == ROMAN_ASSOC_EMPTY && ASSOC_ST_RANGE == ROMAN_ASSOC_RANGE &&
+              ASSOC_WAVE_MAX == ROMAN_ASSOC_WAVE_MAX && ASSOC_LDS_MAX == ROMAN_ASSOC_LDS_MAX, "kernels.hip.h and roman_hip.h name the same numbers");
+static_assert(sizeof(roman_assoc_params_t) == 48, "roman_assoc_params_t: a double, two int32 words, four doubles");
+static_assert(ASSOC_WAVE_MAX <= ASSOC_WAVE_CAP && ASSOC_LDS_MAX <= ASSOC_LDS_CAP, "a cut cannot exceed the LDS its kernel sorts in");
+
+struct AssocSizes { int64_t P; int32_t clouds, cols, col0; };
+
+// Everything roman_assoc_scores* judge on host memory.  The argument checks come first and the context last, so that each of them
+// answers without a device (a NULL context then leaves the text with roman_last_error(NULL)).
+static int assoc_check(roman_ctx* c, const roman_assoc_params_t* P, const void* points, const int64_t* cloud_off, int32_t N1, int32_t N2,
+                       const void* desc, int32_t d, const void* geo, const void* score, const void* status, AssocSizes* Z)
+{
+    if (!P) return fail(c, ROMAN_E_INVALID, "params is NULL");
+    if (!(P->voxel_size > 0.0) || !std::isfinite(P->voxel_size)) return fail(c, ROMAN_E_INVALID, "voxel_size must be finite and > 0 (got %g)", P->voxel_size);
+    if (P->geometric != ROMAN_ASSOC_IOU && P->geometric != ROMAN_ASSOC_IOM) return fail(c, ROMAN_E_INVALID, "unknown geometric method %d", P->geometric);
+    if (P->semantic != 0 && P->semantic != 1) return fail(c, ROMAN_E_INVALID, "semantic must be 0 or 1 (got %d)", P->semantic);
+    if (!(P->geo_range[1] != P->geo_range[0]) || P->geo_range[0] != P->geo_range[0])
+        return fail(c, ROMAN_E_INVALID, "geo_range = (%g, %g): threshold and maximum must differ", P->geo_range[0], P->geo_range[1]);
+    if (P->semantic && (!(P->sem_range[1] != P->sem_range[0]) || P->sem_range[0] != P->sem_range[0]))
+        return fail(c, ROMAN_E_INVALID, "sem_range = (%g, %g): threshold and maximum must differ", P->sem_range[0], P->sem_range[1]);
+    if (N1 < 0 || N2 < -1) return fail(c, ROMAN_E_INVALID, "N1 = %d, N2 = %d: N1 >= 0 and N2 >= 0, or N2 == -1 for self mode", N1, N2);
+    if (N1 > (1 << 30) || N2 > (1 << 30) - N1) return fail(c, ROMAN_E_TOO_LARGE, "more than 2^30 clouds");
+    Z->clouds = N2 < 0 ? N1 : N1 + N2; Z->cols = N2 < 0 ? N1 : N2; Z->col0 = N2 < 0 ? 0 : N1;
+    if ((int64_t)N1 * Z->cols > (int64_t)(1 << 30)) return fail(c, ROMAN_E_TOO_LARGE, "%d x %d: more than 2^30 pairs", N1, Z->cols);
+    if (!cloud_off) return fail(c, ROMAN_E_INVALID, "cloud_off is NULL");
+    { const int rc = cloud_offsets_check(c, cloud_off, Z->clouds, "cloud_off", "cloud"); if (rc) return rc; }
+    Z->P = cloud_off[Z->clouds];
+    if (d < 0) return fail(c, ROMAN_E_INVALID, "d < 0");
+    if (P->semantic && d > 0 && !desc && Z->clouds > 0) return fail(c, ROMAN_E_INVALID, "desc is NULL with d = %d", d);
+    if (P->semantic && d == 0 && desc) return fail(c, ROMAN_E_INVALID, "desc is given with d = 0");
+    if (Z->P > 0 && !points) return fail(c, ROMAN_E_INVALID, "points is NULL");
+    if (N1 > 0 && Z->cols > 0 && (!geo || !score || !status)) return fail(c, ROMAN_E_INVALID, "geo / score / status is NULL");
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    return ROMAN_OK;
+}
+
+int roman_assoc_scores_dev(roman_ctx_t* c, const roman_assoc_params_t* params, const double* points, const int64_t* cloud_off_dev,
+                           const int64_t* cloud_off_host, int32_t N1, int32_t N2, const double* desc, int32_t d,
+                           int32_t* n_vox, int32_t* inter, double* geo, double* sem, double* score, int32_t* status)
+{
+    AssocSizes Z{};
+    int rc = assoc_check(c, params, points, cloud_off_host, N1, N2, desc, d, geo, score, status, &Z);
+    if (rc) return rc;
+    if (N1 == 0 || Z.cols == 0) return ROMAN_OK;
+    if (!cloud_off_dev) return fail(c, ROMAN_E_INVALID, "cloud_off is NULL on the device");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int32_t NC = Z.clouds;
+    const bool cosine = params->semantic && d > 0;
+    // ---- the workspace, from the host offsets alone ----
+    HIPCHK(c, c->asKeys.ensure(sizeof(unsigned long long) * (size_t)std::max<int64_t>(Z.P, 1)));
+    HIPCHK(c, c->asRec.ensure(sizeof(AssocCloud) * (size_t)NC));
+    if (cosine) HIPCHK(c, c->asNorm.ensure(sizeof(double) * (size_t)NC));
+    // ---- the list, cut on the host: the clouds of one wave, of a workgroup sorting in LDS, of a workgroup that merges ----
+    const int64_t cutW = c->assoc_wave_max, cutL = c->assoc_lds_max;
+    int32_t* items = nullptr;
+    HIPCHK(c, c->asStage.stage((size_t)NC, &items));
+    int32_t nW = 0, nL = 0, nM = 0;
+    int64_t longest = 0;
+    for (int32_t i = 0; i < NC; ++i) if (cloud_off_host[i + 1] - cloud_off_host[i] <= cutW) items[nW++] = i;
+    for (int32_t i = 0; i < NC; ++i) { const int64_t n = cloud_off_host[i + 1] - cloud_off_host[i]; if (n > cutW && n <= cutL) items[nW + nL++] = i; }
+    for (int32_t i = 0; i < NC; ++i) { const int64_t n = cloud_off_host[i + 1] - cloud_off_host[i]; if (n > cutL) { items[nW + nL + nM++] = i; longest = std::max(longest, n); } }
+    if (nM) HIPCHK(c, c->asScratch.ensure(sizeof(unsigned long long) * (size_t)Z.P));
+    HIPCHK(c, c->asStage.upload(c->asItems, (size_t)NC, c->stream));
+    const AssocKeyArgs K{points, cloud_off_dev, c->asItems.as<int32_t>(), c->asKeys.as<unsigned long long>(), c->asScratch.as<unsigned long long>(),
+                         c->asRec.as<AssocCloud>(), n_vox, status, params->voxel_size, (int)cutL};
+    if (nW) hipLaunchKernelGGL(k_assoc_keys_wave, dim3((unsigned)((nW + 3) / 4)), dim3(256), 0, c->stream, K, (int)nW);
+    if (nL) hipLaunchKernelGGL(k_assoc_keys_block<false>, dim3((unsigned)nL), dim3(256), 0, c->stream, K, (int)nW);
+    if (nM) hipLaunchKernelGGL(k_assoc_keys_block<true>, dim3((unsigned)nM), dim3(256), 0, c->stream, K, (int)(nW + nL));
+    if (cosine) hipLaunchKernelGGL(k_assoc_norms, dim3((unsigned)((NC + 3) / 4)), dim3(256), 0, c->stream, desc, (int)d, (int)NC, c->asNorm.as<double>());
+    const AssocPairArgs A{c->asRec.as<AssocCloud>(), c->asKeys.as<unsigned long long>(), cloud_off_dev, cosine ? desc : nullptr, c->asNorm.as<double>(),
+                          cosine ? (int)d : 0, (int)N1, (int)Z.cols, (int)Z.col0, params->geometric == ROMAN_ASSOC_IOM ? 1 : 0, (int)params->semantic,
+                          std::pow(params->voxel_size, 3.0) /* voxel_size**3 as Python's float power gives it */,
+                          params->geo_range[0], params->geo_range[1], params->sem_range[0], params->sem_range[1], inter, geo, sem, score};
+    const int64_t pairs = (int64_t)N1 * Z.cols;
+    hipLaunchKernelGGL(k_assoc_pairs, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, c->stream, A);
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_assoc_scores(roman_ctx_t* c, const roman_assoc_params_t* params, const double* points, const int64_t* cloud_off,
+                       int32_t N1, int32_t N2, const double* desc, int32_t d,
+                       int32_t* n_vox, int32_t* inter, double* geo, double* sem, double* score, int32_t* status)
+{
+    AssocSizes Z{};
+    int rc = assoc_check(c, params, points, cloud_off, N1, N2, desc, d, geo, score, status, &Z);
+    if (rc || N1 == 0 || Z.cols == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const size_t NC = (size_t)Z.clouds, pairs = (size_t)N1 * (size_t)Z.cols;
+    const bool cosine = params->semantic && d > 0;
+    HostMirror m(c);
+    const auto dPts = m.in(points, sizeof(double) * 3 * (size_t)Z.P);
+    const auto dOff = m.in(cloud_off, sizeof(int64_t) * (NC + 1));
+    const auto dDesc = m.in(desc, cosine ? sizeof(double) * NC * (size_t)d : 0);
+    const auto dNv = m.out(n_vox, n_vox ? sizeof(int32_t) * NC : 0);
+    const auto dSt = m.out(status, sizeof(int32_t) * NC);
+    const auto dIn = m.out(inter, inter ? sizeof(int32_t) * pairs : 0);
+    const auto dGeo = m.out(geo, sizeof(double) * pairs);
+    const auto dSem = m.out(sem, (sem && params->semantic) ? sizeof(double) * pairs : 0);
+    const auto dSc = m.out(score, sizeof(double) * pairs);
+    rc = m.upload();
+    if (rc) return rc;
+    rc = roman_assoc_scores_dev(c, params, Z.P ? dPts.dev() : reinterpret_cast<const double*>(dOff.dev()) /* never read: every cloud is empty */, dOff.dev(),
+                                cloud_off, N1, N2, dDesc.dev(), cosine ? d : 0, dNv.dev(), dIn.dev(), dGeo.dev(), dSem.dev(), dSc.dev(), dSt.dev());
+    if (rc) return rc;
+    return m.download();
+}
+
+int roman_ctx_set_assoc_cuts(roman_ctx_t* c, int32_t wave_max, int32_t lds_max)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    const int w = wave_max ? wave_max : ASSOC_WAVE_MAX, l = lds_max ? lds_max : ASSOC_LDS_MAX;
+    if (wave_max < 0 || lds_max < 0 || w > ASSOC_WAVE_CAP || l > ASSOC_LDS_CAP || l < 2 || w > l)
+        return fail(c, ROMAN_E_INVALID, "wave_max = %d, lds_max = %d: 0 <= wave_max <= %d, wave_max <= lds_max, 2 <= lds_max <= %d (0: the default)",
+                    wave_max, lds_max, ASSOC_WAVE_CAP, ASSOC_LDS_CAP);
+    c->assoc_wave_max = w; c->assoc_lds_max = l;
     return ROMAN_OK;
 }
 

@@ -381,6 +381,49 @@ def _segment_clouds(points, seg_off):
     return points, seg_off, int(seg_off.shape[0]) - 1
 
 
+def assoc_params(voxel_size=0.2, geometric="iou", semantic=False, geo_range=(0.25, 1.0), sem_range=(0.8, 1.0)):
+    """-> roman_assoc_params_t; the defaults are MapperParams' [REF roman/params/mapper_params.py:58-72].  geometric: 'iou' / 'iom'
+    or a ROMAN_ASSOC_* number ('chamfer' is not covered: ValueError); semantic: whether the cosine of the descriptors is the
+    second criterion."""
+    P = _abi.RomanAssocParams()
+    if isinstance(geometric, str):
+        if geometric not in _abi.ASSOC_GEOMETRIC:
+            raise ValueError(f"geometric must be one of {sorted(_abi.ASSOC_GEOMETRIC)} (got {geometric!r})")
+        geometric = _abi.ASSOC_GEOMETRIC[geometric]
+    P.voxel_size, P.geometric, P.semantic = float(voxel_size), int(geometric), int(bool(semantic))
+    P.geo_range[0], P.geo_range[1] = (float(x) for x in geo_range)
+    P.sem_range[0], P.sem_range[1] = (float(x) for x in sem_range)
+    return P
+
+
+@dataclass
+class AssocScores:
+    """What roman_assoc_scores* writes: geo, sem (None without the cosine), score (N1, N2) float64; inter (N1, N2) int32;
+    n_vox and status (clouds,) int32, the row clouds first."""
+    geo: np.ndarray
+    sem: Optional[np.ndarray]
+    score: np.ndarray
+    n_vox: Optional[np.ndarray]
+    inter: Optional[np.ndarray]
+    status: np.ndarray
+
+
+def _assoc_sizes(clouds, N1, N2, desc):
+    """The counts and descriptors of an association call, checked -> (N1, N2, columns, desc float64 (clouds, d) or None, d)."""
+    N1, N2 = int(N1), int(N2)
+    if N1 < 0 or N2 < -1 or (N1 if N2 < 0 else N1 + N2) != clouds:
+        raise ValueError(f"cloud_off holds {clouds} clouds: N1 + N2 must be that (N2 = -1: self mode, N1 alone)")
+    d = 0
+    if desc is not None:
+        desc = _f64(desc)
+        if desc.ndim != 2 or desc.shape[0] != clouds:
+            raise ValueError(f"desc must be ({clouds}, d)")
+        d = int(desc.shape[1])
+        if d == 0:
+            desc = None
+    return N1, N2, (N1 if N2 < 0 else N2), desc, d
+
+
 def session_frame_robot_dtype():
     """roman_session_frame_robot_t as a structured dtype."""
     return np.dtype([("seg0", np.int64), ("mask_off", np.int64), ("n_seg", np.int32), ("sub0", np.int32), ("n_sub", np.int32), ("frame0", np.int32),
@@ -1271,6 +1314,41 @@ class Context:
     def set_segment_block_min(self, n=0):
         """Measurement only (roman_ctx_set_segment_block_min): the point count from which a segment takes a workgroup; 0: the default."""
         self._check(self._lib.roman_ctx_set_segment_block_min(self._h, int(n)), "roman_ctx_set_segment_block_min")
+
+    # ------------------------------------------------------------------ frame data association scores (DESIGN.md §4.25)
+    def assoc_scores(self, aparams, points, cloud_off, N1, N2=-1, desc=None, want_sem=True, want_inter=True, want_n_vox=True):
+        """Host-pointer voxel IoU / IoM, cosine and score of every (row cloud, column cloud) pair (roman_assoc_scores): points
+        (P, 3), cloud_off (clouds + 1,) ascending from 0 to P — the first N1 clouds are the rows, the next N2 the columns; N2 = -1:
+        self mode, N1 x N1.  aparams an assoc_params() block; desc (clouds, d) or None.  -> AssocScores (sem None unless the
+        block asks for the cosine; inter / n_vox None when not wanted)."""
+        points, cloud_off, clouds = _segment_clouds(points, cloud_off)
+        N1, N2, cols, desc, d = _assoc_sizes(clouds, N1, N2, desc)
+        n_vox = np.zeros(clouds, dtype=np.int32) if want_n_vox else None
+        status = np.zeros(clouds, dtype=np.int32)
+        inter = np.zeros((N1, cols), dtype=np.int32) if want_inter else None
+        geo, score = np.zeros((N1, cols)), np.zeros((N1, cols))
+        sem = np.zeros((N1, cols)) if (want_sem and aparams.semantic) else None
+        self._generation += 1
+        rc = self._lib.roman_assoc_scores(self._h, C.byref(aparams), _ptr(points), _ptr(cloud_off), N1, N2, _ptr(desc), d,
+                                          _ptr(n_vox), _ptr(inter), _ptr(geo), _ptr(sem), _ptr(score), _ptr(status))
+        self._check(rc, "roman_assoc_scores")
+        return AssocScores(geo, sem, score, n_vox, inter, status)
+
+    def assoc_scores_dev(self, aparams, points_ptr, cloud_off_ptr, cloud_off, N1, N2, desc_ptr, d, geo_ptr, score_ptr, status_ptr,
+                         sem_ptr=None, inter_ptr=None, n_vox_ptr=None):
+        """Device-pointer form (roman_assoc_scores_dev): every array on the device, `cloud_off` the same offsets on the host (the
+        launches and the workspace are sized from them).  A pure enqueue on the context's stream."""
+        cloud_off = np.ascontiguousarray(cloud_off, dtype=np.int64).reshape(-1)
+        clouds = int(N1) if int(N2) < 0 else int(N1) + int(N2)
+        if cloud_off.shape[0] != clouds + 1:
+            raise ValueError("cloud_off must hold one offset per cloud and the end")
+        self._enqueue("roman_assoc_scores_dev", C.byref(aparams), _vp(points_ptr), _vp(cloud_off_ptr), _ptr(cloud_off), int(N1), int(N2), _vp(desc_ptr), int(d),
+                      _vp(n_vox_ptr), _vp(inter_ptr), _vp(geo_ptr), _vp(sem_ptr), _vp(score_ptr), _vp(status_ptr))
+
+    def set_assoc_cuts(self, wave_max=0, lds_max=0):
+        """Measurement only (roman_ctx_set_assoc_cuts): the point counts up to which a cloud's keys are sorted by one wave / by
+        one workgroup in LDS; 0: the default.  Results do not depend on them."""
+        self._check(self._lib.roman_ctx_set_assoc_cuts(self._h, int(wave_max), int(lds_max)), "roman_ctx_set_assoc_cuts")
 
     def grid_gate_aabb(self, gparams, box0, box1, pos0, T_w0, pos1, T_w1, time0=None, time1=None, desc0=None, desc1=None, pos_gt0=None, pos_gt1=None,
                        sim_in=None, pairs=None, T_ref=None, enable=None):
