@@ -1534,6 +1534,82 @@ ROMAN_API int roman_assoc_scores(roman_ctx_t* ctx, const roman_assoc_params_t* p
 ROMAN_API int roman_ctx_set_assoc_cuts(roman_ctx_t* ctx, int32_t wave_max, int32_t lds_max);
 
 /*
+ * roman_segment_integrate_dev: the segment update of the mapper's per-frame loop — what Segment.update does to a
+ * segment's cloud with every associated observation, Segment.__init__ with every new segment and update_from_segment with every
+ * merge [REF roman/object/segment.py:98-161]: the added cloud, transformed into the world frame
+ * [REF roman/object/segment.py:133-148], is appended to the segment's [REF roman/object/segment.py:163-175] and the whole is
+ * cleaned [REF roman/object/segment.py:177-193] by open3d's voxel_down_sample(voxel_size) and, when outlier_std is in use,
+ * remove_statistical_outlier(10, outlier_std).  One call takes a LIST OF JOBS.  Bulk data on the DEVICE; a PURE ENQUEUE on the
+ * context's stream: no synchronisation, no read-back.
+ *   points          float64[P][3]: n_clouds clouds one behind the other, P = cloud_off_host[n_clouds]
+ *   cloud_off_dev   int64[n_clouds + 1] on the device, cloud_off_host the same numbers on the HOST: ascending, [0] == 0
+ *   poses           float64[n_poses][16]: row-major 4 x 4 poses T_world_body [REF roman/object/segment.py:142-144]; may be NULL when no job names one
+ *   jobs_dev        roman_integrate_job_t[n_jobs] on the device, jobs_host the same on the HOST.  base: the cloud of the segment,
+ *                   -1 for a new segment; add: the cloud that is added; pose: the pose of the added cloud, -1 when it is in the
+ *                   world frame already (a merge; the clouds of SegmentClouds.from_observations).  A cloud is the base of at
+ *                   most one job
+ *   SLOTS           job j owns the elements [slot_j, slot_j + n(base_j) + n(add_j)) of out_points and out_avg, slot_j the
+ *                   exclusive prefix sum of n(base) + n(add) over the jobs in front of it, computed from cloud_off_host alone; all
+ *                   workspace is laid out the same way, and no write of a job leaves its slot
+ *   out_points      float64[total][3]: the first out_count[j] rows of slot j are job j's cleaned cloud; the rest of the slot is
+ *                   left untouched.  May be NULL when total == 0 (every slot is empty)
+ *   NO ALIASING     out_points, out_avg, out_count, out_status and out_thr must not overlap points, poses, cloud_off, jobs or each
+ *                   other: a job copies or reads its clouds from `points` while other jobs write their slots, in no defined order.
+ *                   To update clouds in place, write to a second array and swap the two between calls
+ *   out_count       int32[n_jobs]: 0 is what the reference stores as points = None [REF roman/object/segment.py:188-189]
+ *   out_status      int32[n_jobs], the vocabulary of roman_assoc_scores: ROMAN_ASSOC_OK; ROMAN_ASSOC_EMPTY: base and added cloud
+ *                   hold no point; ROMAN_ASSOC_RANGE: a (transformed) coordinate is not finite or a voxel index needs more than 21
+ *                   bits — count 0
+ *   out_avg         float64[total] or NULL: with the outlier step, the mean distance of every DOWN-SAMPLED point of the job to its
+ *                   min(10, m) nearest, itself included, in down-sampled order (ascending voxel key)
+ *   out_thr         float64[n_jobs] or NULL: with the outlier step, the distance threshold of every job that ran it
+ * Semantics (tests/_integrate_oracle.py states them line by line).  An EMPTY ADDED CLOUD returns the base unchanged, with no
+ * clean-up [REF roman/object/segment.py:165-166].  Otherwise: world point ((r0 x + r1 y) + r2 z) + t per row (the rounding of the
+ * reference's BLAS product is UNPINNED); base points then added points; voxel index floor((p - (min_bound - voxel_size / 2)) /
+ * voxel_size) per axis — open3d's documented rule, UNPINNED: not compared with a real open3d — one output point per index, the
+ * sum of its points one after another in input order from 0.0 divided by their number; output in ASCENDING VOXEL KEY (x most
+ * significant; open3d's own order is that of its hash map, UNPINNED).  Then, when outlier_std is finite and > 0
+ * [REF roman/params/mapper_params.py:100-103], open3d's published remove_statistical_outlier (UNPINNED in the same sense):
+ * avg_i the mean of the square roots of the min(10, m) smallest squared distances (dx dx + dy dy) + dz dz, added ascending;
+ * mean = sum(avg_i > 0) / m, std = sqrt(sum((avg_i - mean)^2, avg_i > 0) / (m - 1)), thr = mean + outlier_std std, both sums in
+ * the fixed order of DESIGN.md §4.26; point i is kept iff avg_i > 0 && avg_i < thr.  m <= 2 gives an empty cloud.  No atomics:
+ * two calls give the same bits, and so does every size class.  n_jobs == 0: ROMAN_OK, nothing written.
+ * Errors (ROMAN_E_INVALID with a roman_last_error text, nothing enqueued; the argument checks run before the context is looked
+ * at): NULL params; voxel_size not finite or <= 0; a NaN outlier_std; nb_neighbors != 10; a negative count; NULL cloud_off_host,
+ * [0] != 0 or descending; NULL jobs_host; a job whose add, base or pose is out of range; a base cloud named by two jobs; NULL
+ * poses when a job names one; NULL points with P > 0; NULL out_points / out_count / out_status; NULL ctx; NULL cloud_off_dev or
+ * jobs_dev.  More than INT32_MAX points in a cloud or 2^28 in a job: ROMAN_E_TOO_LARGE.
+ */
+#define ROMAN_INTEGRATE_NEIGHBORS 10
+#define ROMAN_INTEGRATE_WAVE_MAX  256   /* a job of at most so many points (base + added) is one wave's (roman_ctx_set_integrate_cuts) */
+#define ROMAN_INTEGRATE_LDS_MAX  4096   /* ... of at most so many is sorted by one workgroup in LDS; larger jobs merge through global memory */
+typedef struct roman_integrate_params {
+    double  voxel_size;        /* > 0, finite (segment_voxel_size) */
+    double  outlier_std;       /* segment_outlier_removal_std; not finite or <= 0: no outlier removal */
+    int32_t nb_neighbors;      /* ROMAN_INTEGRATE_NEIGHBORS; any other value is refused */
+} roman_integrate_params_t;
+typedef struct roman_integrate_job {
+    int32_t base;              /* cloud of the segment, -1: a new segment */
+    int32_t add;               /* cloud that is added */
+    int32_t pose;              /* pose of the added cloud, -1: it is in the world frame already */
+} roman_integrate_job_t;
+ROMAN_API int roman_segment_integrate_dev(roman_ctx_t* ctx, const roman_integrate_params_t* params, const double* points, const int64_t* cloud_off_dev,
+                                          const int64_t* cloud_off_host, int32_t n_clouds, const double* poses, int32_t n_poses,
+                                          const roman_integrate_job_t* jobs_dev, const roman_integrate_job_t* jobs_host, int32_t n_jobs,
+                                          double* out_points, int32_t* out_count, int32_t* out_status, double* out_avg, double* out_thr);
+
+/* The same with HOST pointers everywhere.  Synchronous.  What a job leaves untouched comes back as the caller had it. */
+ROMAN_API int roman_segment_integrate(roman_ctx_t* ctx, const roman_integrate_params_t* params, const double* points, const int64_t* cloud_off, int32_t n_clouds,
+                                      const double* poses, int32_t n_poses, const roman_integrate_job_t* jobs, int32_t n_jobs,
+                                      double* out_points, int32_t* out_count, int32_t* out_status, double* out_avg, double* out_thr);
+
+/* Measurement only: the two point counts (base + added) at which a job of roman_segment_integrate* changes its kernel set — up to
+   wave_max one wave, up to lds_max one workgroup sorting in LDS, beyond it one workgroup that sorts chunks of lds_max pairs and merges
+   them in global memory.  0: the default again (ROMAN_INTEGRATE_WAVE_MAX, ROMAN_INTEGRATE_LDS_MAX); wave_max <= lds_max,
+   2 <= lds_max <= 4096.  Every class gives the same bits, so results do not depend on the cuts. */
+ROMAN_API int roman_ctx_set_integrate_cuts(roman_ctx_t* ctx, int32_t wave_max, int32_t lds_max);
+
+/*
  * roman_session_gate_aabb_dev: roman_session_gate_dev with the bounding-box gate [REF roman/align/submap_align.py:101-103]
  * — what roman_grid_gate_aabb_dev is to roman_grid_gate_dev.  The arguments are roman_session_gate_dev's; then
  *   box        float64[S][6] over ALL submaps of the session, as roman_session_boxes_dev wrote them.  NEARBY is the six comparisons

@@ -315,6 +315,27 @@ ROMAN_ASSOC_WAVE_MAX = 256  # points up to which one wave sorts a cloud's keys (
 ROMAN_ASSOC_LDS_MAX = 8192  # ... up to which a workgroup sorts them in LDS alone (kernels.hip.h ASSOC_LDS_MAX)
 ASSOC_PARAMS_NBYTES = C.sizeof(RomanAssocParams)
 
+
+class RomanIntegrateParams(C.Structure):
+    """roman_integrate_params_t"""
+    _fields_ = [
+        ("voxel_size", C.c_double),
+        ("outlier_std", C.c_double),
+        ("nb_neighbors", C.c_int32),
+    ]
+
+
+class RomanIntegrateJob(C.Structure):
+    """roman_integrate_job_t"""
+    _fields_ = [("base", C.c_int32), ("add", C.c_int32), ("pose", C.c_int32)]
+
+
+ROMAN_INTEGRATE_NEIGHBORS = 10      # nb_neighbors of remove_statistical_outlier [REF roman/object/segment.py:183-184]; the only value served
+ROMAN_INTEGRATE_WAVE_MAX = 256      # points (base + added) up to which one wave takes a job (kernels.hip.h INTEG_WAVE_MAX)
+ROMAN_INTEGRATE_LDS_MAX = 4096      # ... up to which a workgroup sorts the job in LDS alone (kernels.hip.h INTEG_LDS_CAP)
+INTEGRATE_PARAMS_NBYTES = C.sizeof(RomanIntegrateParams)
+INTEGRATE_JOB_DTYPE = [("base", "<i4"), ("add", "<i4"), ("pose", "<i4")]      # roman_integrate_job_t as a structured dtype
+
 # flag bits of roman_grid_gate's flags[]
 ROMAN_GRID_NEARBY = 1
 ROMAN_GRID_SKIP = 2
@@ -457,6 +478,9 @@ def load_library():
         "roman_assoc_scores_dev": (C.c_int, [ctxp, P(RomanAssocParams), vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
         "roman_assoc_scores": (C.c_int, [ctxp, P(RomanAssocParams), vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
         "roman_ctx_set_assoc_cuts": (C.c_int, [ctxp, i32, i32]),
+        "roman_segment_integrate_dev": (C.c_int, [ctxp, P(RomanIntegrateParams), vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "roman_segment_integrate": (C.c_int, [ctxp, P(RomanIntegrateParams), vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+        "roman_ctx_set_integrate_cuts": (C.c_int, [ctxp, i32, i32]),
         "roman_ctx_has_history": (C.c_int, [ctxp, P(RomanParams), i32, P(i32)]),
         "roman_ctx_cosine_screen_stats": (C.c_int, [ctxp, P(C.c_int64), P(C.c_int64), P(C.c_double)]),
         "roman_create_all_to_all": (C.c_int, [i32, i32, vp]),
@@ -491,7 +515,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_shared_reduce_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_mno_lc_tail_dev", "roman_mno_lc_batch_dev", "roman_mno_lc_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ransac_lc_batch_dev", "roman_ransac_lc_batch", "roman_submaps_dev", "roman_submaps", "roman_session_submaps_dev", "roman_session_submaps", "roman_session_submaps_list_dev", "roman_session_submaps_list", "roman_grid_gate_dev", "roman_grid_gate", "roman_grid_gate_sim_dev", "roman_grid_gate_sim", "roman_submaps_fill_dev", "roman_submaps_fill", "roman_submap_boxes_dev", "roman_submap_boxes", "roman_grid_gate_aabb_dev", "roman_grid_gate_aabb", "roman_session_gate_dev", "roman_session_gate", "roman_session_gate_sim_dev", "roman_session_gate_sim", "roman_session_stacked_sim_dev", "roman_session_stacked_sim", "roman_session_stacked_sim_list_dev", "roman_session_stacked_sim_list", "roman_session_boxes_dev", "roman_session_boxes", "roman_session_gate_aabb_dev", "roman_session_gate_aabb", "roman_session_gate_list_dev", "roman_session_gate_list", "roman_frame_select_dev", "roman_frame_select", "roman_session_frame_select_list_dev", "roman_session_frame_select_list", "roman_stacked_sim_dev", "roman_stacked_sim", "roman_ctx_set_stacked_band", "roman_segment_shapes_dev", "roman_segment_shapes", "roman_ctx_set_segment_block_min", "roman_assoc_scores_dev", "roman_assoc_scores", "roman_ctx_set_assoc_cuts", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_shared_reduce_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_mno_lc_tail_dev", "roman_mno_lc_batch_dev", "roman_mno_lc_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ransac_lc_batch_dev", "roman_ransac_lc_batch", "roman_submaps_dev", "roman_submaps", "roman_session_submaps_dev", "roman_session_submaps", "roman_session_submaps_list_dev", "roman_session_submaps_list", "roman_grid_gate_dev", "roman_grid_gate", "roman_grid_gate_sim_dev", "roman_grid_gate_sim", "roman_submaps_fill_dev", "roman_submaps_fill", "roman_submap_boxes_dev", "roman_submap_boxes", "roman_grid_gate_aabb_dev", "roman_grid_gate_aabb", "roman_session_gate_dev", "roman_session_gate", "roman_session_gate_sim_dev", "roman_session_gate_sim", "roman_session_stacked_sim_dev", "roman_session_stacked_sim", "roman_session_stacked_sim_list_dev", "roman_session_stacked_sim_list", "roman_session_boxes_dev", "roman_session_boxes", "roman_session_gate_aabb_dev", "roman_session_gate_aabb", "roman_session_gate_list_dev", "roman_session_gate_list", "roman_frame_select_dev", "roman_frame_select", "roman_session_frame_select_list_dev", "roman_session_frame_select_list", "roman_stacked_sim_dev", "roman_stacked_sim", "roman_ctx_set_stacked_band", "roman_segment_shapes_dev", "roman_segment_shapes", "roman_ctx_set_segment_block_min", "roman_assoc_scores_dev", "roman_assoc_scores", "roman_ctx_set_assoc_cuts", "roman_segment_integrate_dev", "roman_segment_integrate", "roman_ctx_set_integrate_cuts", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

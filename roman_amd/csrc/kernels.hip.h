@@ -9481,4 +9481,347 @@ __global__ void __launch_bounds__(256) k_assoc_pairs(AssocPairArgs A)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Segment update: what Segment._add_points and _cleanup_points do to a segment's cloud with every associated
+// observation, every new segment and every merge [REF roman/object/segment.py:133-193] — append, open3d's voxel_down_sample,
+// open3d's remove_statistical_outlier(10, std) — for a list of jobs.  A TEAM (one wave or one workgroup of four) takes one job;
+// every array of a job lives in the job's SLOT, n(base) + n(add) elements from the host's prefix sum on, in every workspace.
+//   front   assemble base + (posed) added points into the slot of `wpts`, minima and maxima on the way; one (voxel key, input
+//           index) pair per point, sorted lexicographically — a bitonic network in LDS (k_integ_front_wave, k_integ_front_block<
+//           false>) or LDS-sorted chunks merged through a global ping-pong (k_integ_front_block<true>); then one thread per run of
+//           equal keys adds the run's points in index order from 0.0 and divides by the count: the down-sampled cloud, ascending key
+//   knn     every down-sampled point's ten smallest squared distances to all of them, kept ascending in ten registers by an
+//           unrolled compare-exchange chain (no indexing, no scratch); the columns go through LDS as SoA and every lane reads the
+//           same one.  Their square roots are added ascending and divided by their number: avg
+//   finish  mean, deviation and threshold of avg in ONE order for every class — lane l of a wave adds the elements l, l + 64, ...
+//           from 0.0, then the xor butterfly 32, 16, ..., 1 — and a ballot compaction of the kept points into the output slot
+// A (key, index) pair is unique, so every sort gives the same sequence, and every sum has one order: all classes give the same
+// bits.  No atomics.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int INTEG_NEIGHBORS = 10;          // nb_neighbors of remove_statistical_outlier [REF roman/object/segment.py:183-184]
+constexpr int INTEG_LDS_CAP = 4096;          // (key, index) pairs of LDS a team sorts in (48 KB)
+constexpr int INTEG_WAVE_MAX = 256;          // ROMAN_INTEGRATE_WAVE_MAX: a job of at most so many points is one wave's
+constexpr int INTEG_LDS_MAX = INTEG_LDS_CAP; // ROMAN_INTEGRATE_LDS_MAX: ... of at most so many is sorted in LDS alone
+constexpr int INTEG_KEY_TOP = (1 << 21) - 1; // the largest voxel index an axis of the key holds
+constexpr int INTEG_TILE = 256;              // query points of one workgroup of k_integ_knn_tile
+constexpr int INTEG_COLS_WAVE = 256, INTEG_COLS_BLOCK = 1024;   // column points staged in LDS at a time, per team
+
+struct IntegJob { int32_t base, add, pose; };                   // roman_integrate_job_t
+
+struct IntegArgs {
+    const double* pts; const int64_t* off;   // the clouds
+    const double* poses;                     // [n_poses][16], row-major 4 x 4
+    const IntegJob* jobs;
+    const int64_t* slot;                     // [n_jobs + 1]: the exclusive prefix sum of n(base) + n(add), from the host
+    const int64_t* items;                    // the host-cut lists: jobs by class; (job << 32 | query tile) for k_integ_knn_tile
+    double* wpts;                            // [total][3]: the assembled cloud
+    double* ds;                              // [total][3]: the down-sampled cloud in front of the outlier step
+    unsigned long long* keys; unsigned long long* keys2; int32_t* idx; int32_t* idx2;     // [total] each: the merge ping-pong
+    int32_t* m;                              // [n_jobs]: down-sampled points that wait for knn and finish (0: the job is done)
+    double* avg;                             // [total]: out_avg, or workspace
+    double* out_points; int32_t* out_count; int32_t* out_status; double* out_thr;
+    double vs, std; int outlier; int chunk;  // voxel size; outlier_std and whether it is in use; pairs per LDS-sorted chunk of the merge
+};
+
+template <int NW> struct IntegLds {
+    double red[NW * 6];
+    int cnt[NW];
+    unsigned long long k[INTEG_LDS_CAP];
+    int32_t ix[INTEG_LDS_CAP];
+};
+
+__device__ __forceinline__ bool integ_less(unsigned long long ka, int32_t ia, unsigned long long kb, int32_t ib)
+{
+    return ka < kb || (ka == kb && ia < ib);
+}
+
+// the m pairs (k, ix) (m a power of two, in LDS) ascending; ends behind a barrier
+template <int NW> __device__ __forceinline__ void integ_bitonic(unsigned long long* k, int32_t* ix, int m, int tid)
+{
+    constexpr int NT = 64 * NW;
+    for (int size = 2; size <= m; size <<= 1)
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < (m >> 1); t += NT) {
+                const int i = 2 * t - (t & (stride - 1)), j = i + stride;
+                const unsigned long long a = k[i], b = k[j];
+                const int32_t ia = ix[i], ib = ix[j];
+                if (integ_less(b, ib, a, ia) == ((i & size) == 0)) { k[i] = b; k[j] = a; ix[i] = ib; ix[j] = ia; }
+            }
+            seg_sync<NW>();
+        }
+}
+
+// the position of every flagged thread among the flagged ones of the team, and their number (on every thread)
+template <int NW> __device__ __forceinline__ int integ_rank(bool flag, int* cnt, int tid, int& total)
+{
+    const int lane = tid & 63, wave = tid >> 6;
+    const unsigned long long b = __ballot(flag);
+    int before = __popcll(b & ((1ull << lane) - 1ull));
+    total = __popcll(b);
+    if (NW > 1) {
+        if (lane == 0) cnt[wave] = total;
+        __syncthreads();
+        total = 0;
+        for (int w = 0; w < NW; ++w) { const int c = cnt[w]; if (w < wave) before += c; total += c; }
+        __syncthreads();
+    }
+    return before;
+}
+
+// open3d's voxel_down_sample over the sorted pairs: one thread per run of equal keys adds the run's points one after another, in
+// index order, from 0.0 (open3d's AccumulatedPoint) and divides by double(count); runs are written in key order -> their number
+template <int NW>
+__device__ __forceinline__ int integ_voxels(const unsigned long long* k, const int32_t* ix, int n, const double* __restrict__ w,
+                                            double* __restrict__ dst, int* cnt, int tid)
+{
+    constexpr int NT = 64 * NW;
+    int base = 0;
+    for (int c0 = 0; c0 < n; c0 += NT) {
+        const int i = c0 + tid;
+        unsigned long long v = 0ull;
+        bool head = false;
+        if (i < n) { v = k[i]; head = i == 0 || k[i - 1] != v; }
+        int total;
+        const int before = integ_rank<NW>(head, cnt, tid, total);
+        if (head) {
+            double sx = 0.0, sy = 0.0, sz = 0.0;
+            int c = 0;
+            for (int r = i; r < n && k[r] == v; ++r) { const double* p = w + 3 * (int64_t)ix[r]; sx += p[0]; sy += p[1]; sz += p[2]; ++c; }
+            double* o = dst + 3 * (int64_t)(base + before);
+            o[0] = sx / (double)c; o[1] = sy / (double)c; o[2] = sz / (double)c;
+        }
+        base += total;
+    }
+    return base;
+}
+
+// the job's front: assemble, box, keys, sort, voxel sums
+template <int NW, bool MERGE>
+__device__ __forceinline__ void integ_front(const IntegArgs& A, int j, IntegLds<NW>& L, int tid)
+{
+#pragma clang fp contract(off)
+    constexpr int NT = 64 * NW;
+    const IntegJob J = A.jobs[j];
+    const int64_t s0 = A.slot[j];
+    const int64_t b0 = J.base >= 0 ? A.off[J.base] : 0;
+    const int nb = J.base >= 0 ? (int)(A.off[J.base + 1] - b0) : 0;
+    const int64_t a0 = A.off[J.add];
+    const int na = (int)(A.off[J.add + 1] - a0), n = nb + na;
+    if (na == 0) {                           // _add_points' early return [REF roman/object/segment.py:165-166]: the base as it is
+        for (int e = tid; e < 3 * nb; e += NT) A.out_points[3 * s0 + e] = A.pts[3 * b0 + e];
+        if (tid == 0) { A.m[j] = 0; A.out_count[j] = nb; A.out_status[j] = nb > 0 ? ASSOC_ST_OK : ASSOC_ST_EMPTY; }
+        return;
+    }
+    double T[12];
+    if (J.pose >= 0) {
+#pragma unroll
+        for (int e = 0; e < 12; ++e) T[e] = A.poses[16 * (int64_t)J.pose + e];
+    }
+    double* w = A.wpts + 3 * s0;
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    int bad = 0;
+    for (int i = tid; i < n; i += NT) {
+        const double* p = i < nb ? A.pts + 3 * (b0 + i) : A.pts + 3 * (a0 + (i - nb));
+        double x = p[0], y = p[1], z = p[2];
+        if (i >= nb && J.pose >= 0) {        // R p + t row by row [REF roman/object/segment.py:142-147]; the reference's BLAS rounding is UNPINNED
+            const double wx = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+            const double wy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+            const double wz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+            x = wx; y = wy; z = wz;
+        }
+        w[3 * i] = x; w[3 * i + 1] = y; w[3 * i + 2] = z;
+        lo[0] = fmin(lo[0], x); lo[1] = fmin(lo[1], y); lo[2] = fmin(lo[2], z);
+        hi[0] = fmax(hi[0], x); hi[1] = fmax(hi[1], y); hi[2] = fmax(hi[2], z);
+        bad |= (int)!(fabs(x) < INFINITY) | (int)!(fabs(y) < INFINITY) | (int)!(fabs(z) < INFINITY);
+    }
+    seg_sync<NW>();
+    seg_team_minmax<NW>(lo, hi, L.red, tid);
+    bad = NW == 1 ? __any(bad) : __syncthreads_or(bad);
+    // UNPINNED: open3d's documented rule for voxel_down_sample — origin = min_bound - voxel_size / 2, index = floor((p - origin) / voxel_size)
+    double origin[3];
+    bool fits = !bad;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        origin[k] = lo[k] - A.vs * 0.5;
+        fits = fits && floor((hi[k] - origin[k]) / A.vs) <= (double)INTEG_KEY_TOP;
+    }
+    if (!fits) {
+        if (tid == 0) { A.m[j] = 0; A.out_count[j] = 0; A.out_status[j] = ASSOC_ST_RANGE; }
+        return;
+    }
+    auto key_of = [&](int i) {
+        const unsigned long long kx = (unsigned long long)(long long)floor((w[3 * i] - origin[0]) / A.vs);
+        const unsigned long long ky = (unsigned long long)(long long)floor((w[3 * i + 1] - origin[1]) / A.vs);
+        const unsigned long long kz = (unsigned long long)(long long)floor((w[3 * i + 2] - origin[2]) / A.vs);
+        return (kx << 42) | (ky << 21) | kz;
+    };
+    double* dst = A.outlier ? A.ds + 3 * s0 : A.out_points + 3 * s0;
+    int m;
+    if (!MERGE) {                            // n <= INTEG_LDS_CAP
+        const int m2 = assoc_pow2(n);
+        for (int i = tid; i < m2; i += NT) { const bool in = i < n; L.k[i] = in ? key_of(i) : ASSOC_KEY_PAD; L.ix[i] = in ? i : 0x7fffffff; }
+        seg_sync<NW>();
+        integ_bitonic<NW>(L.k, L.ix, m2, tid);
+        m = integ_voxels<NW>(L.k, L.ix, n, w, dst, L.cnt, tid);
+    } else {
+        // chunks of A.chunk pairs sorted in LDS, then runs merged pairwise through the ping-pong: every element finds its place by
+        // a binary search in the sibling run (the pairs are distinct).  Every access stays inside the slot's n elements.
+        unsigned long long* sk = A.keys + s0; unsigned long long* dk = A.keys2 + s0;
+        int32_t* si = A.idx + s0; int32_t* di = A.idx2 + s0;
+        const int chunk = A.chunk;
+        for (int c0 = 0; c0 < n; c0 += chunk) {
+            const int len = n - c0 < chunk ? n - c0 : chunk, m2 = assoc_pow2(len);
+            for (int i = tid; i < m2; i += NT) { const bool in = i < len; L.k[i] = in ? key_of(c0 + i) : ASSOC_KEY_PAD; L.ix[i] = in ? c0 + i : 0x7fffffff; }
+            seg_sync<NW>();
+            integ_bitonic<NW>(L.k, L.ix, m2, tid);
+            for (int i = tid; i < len; i += NT) { sk[c0 + i] = L.k[i]; si[c0 + i] = L.ix[i]; }
+            seg_sync<NW>();
+        }
+        for (int64_t wd = chunk; wd < n; wd <<= 1) {
+            for (int i = tid; i < n; i += NT) {
+                const int64_t base = i / (2 * wd) * (2 * wd), mid = base + wd < n ? base + wd : n, end = base + 2 * wd < n ? base + 2 * wd : n;
+                const unsigned long long v = sk[i];
+                const int32_t vi = si[i];
+                const bool left = i < mid;
+                int64_t l = left ? mid : base, h = left ? end : mid;            // the sibling run
+                const int64_t l0 = l;
+                while (l < h) {
+                    const int64_t c = (l + h) >> 1;
+                    if (integ_less(sk[c], si[c], v, vi)) l = c + 1; else h = c;
+                }
+                const int64_t at = base + (i - (left ? base : mid)) + (l - l0);
+                dk[at] = v; di[at] = vi;
+            }
+            seg_sync<NW>();
+            unsigned long long* tk = sk; sk = dk; dk = tk;
+            int32_t* ti = si; si = di; di = ti;
+        }
+        m = integ_voxels<NW>(sk, si, n, w, dst, L.cnt, tid);
+    }
+    if (tid == 0) {
+        A.out_status[j] = ASSOC_ST_OK;
+        if (A.outlier) A.m[j] = m; else { A.m[j] = 0; A.out_count[j] = m; }
+    }
+}
+
+// one wave per listed job (a workgroup of one wave: the team's LDS is INTEG_LDS_CAP pairs whatever the cut)
+__global__ void __launch_bounds__(64) k_integ_front_wave(IntegArgs A)
+{
+    __shared__ IntegLds<1> L;
+    integ_front<1, false>(A, (int)A.items[blockIdx.x], L, (int)threadIdx.x);
+}
+
+// one workgroup per listed job, from item `first` on
+template <bool MERGE>
+__global__ void __launch_bounds__(256) k_integ_front_block(IntegArgs A, int first)
+{
+    __shared__ IntegLds<4> L;
+    integ_front<4, MERGE>(A, (int)A.items[first + (int)blockIdx.x], L, (int)threadIdx.x);
+}
+
+// The mean distance of the query points q0 + tid of job j to their min(10, m) nearest of the job's m down-sampled points, the
+// point itself included.  best[] ascends; a candidate enters through ten compare-exchanges with compile-time indices.
+template <int NW, int COLS>
+__device__ __forceinline__ void integ_knn(const IntegArgs& A, int j, int q0, int m, double* cols, int tid)
+{
+#pragma clang fp contract(off)
+    constexpr int NT = 64 * NW;
+    const int64_t s0 = A.slot[j];
+    const double* __restrict__ P = A.ds + 3 * s0;
+    const int q = q0 + tid;
+    const bool valid = q < m;
+    const double qx = valid ? P[3 * q] : 0.0, qy = valid ? P[3 * q + 1] : 0.0, qz = valid ? P[3 * q + 2] : 0.0;
+    double best[INTEG_NEIGHBORS];
+#pragma unroll
+    for (int r = 0; r < INTEG_NEIGHBORS; ++r) best[r] = INFINITY;
+    double* cx = cols; double* cy = cols + COLS; double* cz = cols + 2 * COLS;
+    for (int c0 = 0; c0 < m; c0 += COLS) {
+        const int len = m - c0 < COLS ? m - c0 : COLS;
+        for (int e = tid; e < len; e += NT) { cx[e] = P[3 * (c0 + e)]; cy[e] = P[3 * (c0 + e) + 1]; cz[e] = P[3 * (c0 + e) + 2]; }
+        seg_sync<NW>();
+        for (int e = 0; e < len; ++e) {
+            const double dx = qx - cx[e], dy = qy - cy[e], dz = qz - cz[e];
+            double d = (dx * dx + dy * dy) + dz * dz;
+            if (d < best[INTEG_NEIGHBORS - 1]) {
+#pragma unroll
+                for (int r = 0; r < INTEG_NEIGHBORS; ++r) { const double lo = fmin(best[r], d); d = fmax(best[r], d); best[r] = lo; }
+            }
+        }
+        seg_sync<NW>();
+    }
+    const int k = m < INTEG_NEIGHBORS ? m : INTEG_NEIGHBORS;
+    double s = 0.0;
+#pragma unroll
+    for (int r = 0; r < INTEG_NEIGHBORS; ++r) if (r < k) s += sqrt(best[r]);
+    if (valid) A.avg[s0 + q] = s / (double)k;
+}
+
+// one wave per listed job, four to a workgroup; the waves never meet at a workgroup barrier.  Sized for the default cut, m <=
+// INTEG_WAVE_MAX = 256: every batch of 64 queries stages the job's whole column set again, at most four times there.  A cut raised
+// through roman_ctx_set_integrate_cuts (measurement and tests only) restages m / 64 times; such jobs belong to k_integ_knn_tile.
+__global__ void __launch_bounds__(256) k_integ_knn_wave(IntegArgs A, int n_items)
+{
+    __shared__ double cols[4][3 * INTEG_COLS_WAVE];
+    const int wave = (int)threadIdx.x >> 6, it = (int)blockIdx.x * 4 + wave;
+    if (it >= n_items) return;
+    const int j = (int)A.items[it], m = A.m[j];
+    for (int q0 = 0; q0 < m; q0 += 64) integ_knn<1, INTEG_COLS_WAVE>(A, j, q0, m, cols[wave], (int)threadIdx.x & 63);
+}
+
+// one workgroup per listed (job, query tile); the host lists the tiles of n(base) + n(add) points, those past m end at once
+__global__ void __launch_bounds__(256) k_integ_knn_tile(IntegArgs A, int first)
+{
+    __shared__ double cols[3 * INTEG_COLS_BLOCK];
+    const int64_t it = A.items[first + (int64_t)blockIdx.x];
+    const int j = (int)(it >> 32), q0 = (int)(it & 0xffffffffll) * INTEG_TILE, m = A.m[j];
+    if (q0 >= m) return;
+    integ_knn<4, INTEG_COLS_BLOCK>(A, j, q0, m, cols, (int)threadIdx.x);
+}
+
+// open3d's remove_statistical_outlier behind the distances: mean and deviation over the m values, the threshold, the kept points
+template <int NW>
+__device__ __forceinline__ void integ_finish(const IntegArgs& A, int j, int* cnt, int tid)
+{
+#pragma clang fp contract(off)
+    constexpr int NT = 64 * NW;
+    const int m = A.m[j];
+    if (m == 0) return;                      // the front finished the job
+    const int64_t s0 = A.slot[j];
+    const double* __restrict__ avg = A.avg + s0;
+    const int lane = tid & 63;
+    // every wave of the team forms the same two sums in the same order: no exchange between them is needed
+    double s = 0.0;
+    for (int i = lane; i < m; i += 64) { const double a = avg[i]; if (a > 0.0) s += a; }
+    const double mean = assoc_butterfly(s) / (double)m;
+    double q = 0.0;
+    for (int i = lane; i < m; i += 64) { const double a = avg[i]; if (a > 0.0) q += (a - mean) * (a - mean); }
+    const double thr = mean + A.std * sqrt(assoc_butterfly(q) / (double)(m - 1));
+    const double* __restrict__ P = A.ds + 3 * s0;
+    double* __restrict__ O = A.out_points + 3 * s0;
+    int base = 0;
+    for (int c0 = 0; c0 < m; c0 += NT) {
+        const int i = c0 + tid;
+        bool keep = false;
+        if (i < m) { const double a = avg[i]; keep = a > 0.0 && a < thr; }
+        int total;
+        const int before = integ_rank<NW>(keep, cnt, tid, total);
+        if (keep) { double* o = O + 3 * (int64_t)(base + before); o[0] = P[3 * i]; o[1] = P[3 * i + 1]; o[2] = P[3 * i + 2]; }
+        base += total;
+    }
+    if (tid == 0) { A.out_count[j] = base; if (A.out_thr) A.out_thr[j] = thr; }
+}
+
+__global__ void __launch_bounds__(256) k_integ_finish_wave(IntegArgs A, int n_items)
+{
+    const int it = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (it >= n_items) return;
+    integ_finish<1>(A, (int)A.items[it], nullptr, (int)threadIdx.x & 63);
+}
+
+__global__ void __launch_bounds__(256) k_integ_finish_block(IntegArgs A, int first)
+{
+    __shared__ int cnt[4];
+    integ_finish<4>(A, (int)A.items[first + (int)blockIdx.x], cnt, (int)threadIdx.x);
+}
+
 }  // namespace roman

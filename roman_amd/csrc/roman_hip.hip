@@ -211,6 +211,12 @@ struct roman_ctx {
     DevBuf asKeys, asScratch, asRec, asNorm, asItems;
     PinnedStage<int32_t> asStage;
     int assoc_wave_max = ASSOC_WAVE_MAX, assoc_lds_max = ASSOC_LDS_MAX;   // the two path cuts (roman_ctx_set_assoc_cuts)
+    // segment update (roman_segment_integrate*): every workspace holds one slot of n(base) + n(add) elements per job — the assembled
+    // and the down-sampled cloud, the (key, index) pairs and their merge half, the mean distances — then one count per job and the
+    // host-cut tables (slot offsets, job lists, query tiles) through pinned staging
+    DevBuf sgPts, sgDs, sgKeys, sgKeys2, sgIdx, sgIdx2, sgAvg, sgM, sgItems;
+    PinnedStage<int64_t> sgStage;
+    int integ_wave_max = INTEG_WAVE_MAX, integ_lds_max = INTEG_LDS_MAX;   // the two class cuts (roman_ctx_set_integrate_cuts)
 
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
@@ -1468,6 +1474,8 @@ int roman_ctx_destroy(roman_ctx_t* c)
     c->sfTab.release(); c->sfStage.release();
     c->segItems.release(); c->segStage.release();
     c->asKeys.release(); c->asScratch.release(); c->asRec.release(); c->asNorm.release(); c->asItems.release(); c->asStage.release();
+    c->sgPts.release(); c->sgDs.release(); c->sgKeys.release(); c->sgKeys2.release(); c->sgIdx.release(); c->sgIdx2.release();
+    c->sgAvg.release(); c->sgM.release(); c->sgItems.release(); c->sgStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -3481,6 +3489,158 @@ int roman_ctx_set_assoc_cuts(roman_ctx_t* c, int32_t wave_max, int32_t lds_max)
         return fail(c, ROMAN_E_INVALID, "wave_max = %d, lds_max = %d: 0 <= wave_max <= %d, wave_max <= lds_max, 2 <= lds_max <= %d (0: the default)",
                     wave_max, lds_max, ASSOC_WAVE_CAP, ASSOC_LDS_CAP);
     c->assoc_wave_max = w; c->assoc_lds_max = l;
+    return ROMAN_OK;
+}
+
+// --- segment update: integrate, down-sample, prune outliers for a list of jobs -------------------------------------
+static_assert(INTEG_WAVE_MAX == ROMAN_INTEGRATE_WAVE_MAX && INTEG_LDS_MAX == ROMAN_INTEGRATE_LDS_MAX && INTEG_NEIGHBORS == ROMAN_INTEGRATE_NEIGHBORS,
+              "kernels.hip.h and roman_hip.h name the same numbers");
+static_assert(sizeof(roman_integrate_params_t) == 24 && sizeof(roman_integrate_job_t) == 12 && sizeof(IntegJob) == sizeof(roman_integrate_job_t),
+              "roman_integrate_params_t: two doubles and an int32 word; roman_integrate_job_t: three int32 words");
+constexpr int64_t INTEG_JOB_MAX = 1ll << 28;    // points of one job: the kernels index 3 * point in 32 bits
+
+// Everything roman_segment_integrate* judge on host memory -> *total: the points of all slots.  The argument checks come first and
+// the context last, so that each of them answers without a device.
+static int integrate_check(roman_ctx* c, const roman_integrate_params_t* P, const void* points, const int64_t* cloud_off, int32_t n_clouds,
+                           const void* poses, int32_t n_poses, const roman_integrate_job_t* jobs, int32_t n_jobs,
+                           const void* out_points, const void* out_count, const void* out_status, int64_t* total)
+{
+    if (!P) return fail(c, ROMAN_E_INVALID, "params is NULL");
+    if (!(P->voxel_size > 0.0) || !std::isfinite(P->voxel_size)) return fail(c, ROMAN_E_INVALID, "voxel_size must be finite and > 0 (got %g)", P->voxel_size);
+    if (P->outlier_std != P->outlier_std) return fail(c, ROMAN_E_INVALID, "outlier_std is NaN (not finite or <= 0: no outlier removal)");
+    if (P->nb_neighbors != ROMAN_INTEGRATE_NEIGHBORS) return fail(c, ROMAN_E_INVALID, "nb_neighbors must be %d (got %d)", ROMAN_INTEGRATE_NEIGHBORS, P->nb_neighbors);
+    if (n_clouds < 0 || n_poses < 0 || n_jobs < 0) return fail(c, ROMAN_E_INVALID, "n_clouds = %d, n_poses = %d, n_jobs = %d: none may be negative", n_clouds, n_poses, n_jobs);
+    if (!cloud_off) return fail(c, ROMAN_E_INVALID, "cloud_off is NULL");
+    { const int rc = cloud_offsets_check(c, cloud_off, n_clouds, "cloud_off", "cloud"); if (rc) return rc; }
+    if (n_jobs > 0 && !jobs) return fail(c, ROMAN_E_INVALID, "jobs is NULL");
+    std::vector<char> named((size_t)n_clouds, 0);
+    bool posed = false;
+    *total = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) {
+        const roman_integrate_job_t& J = jobs[j];
+        if (J.add < 0 || J.add >= n_clouds) return fail(c, ROMAN_E_INVALID, "job %d: add = %d is not one of the %d clouds", j, J.add, n_clouds);
+        if (J.base < -1 || J.base >= n_clouds) return fail(c, ROMAN_E_INVALID, "job %d: base = %d is neither -1 nor one of the %d clouds", j, J.base, n_clouds);
+        if (J.pose < -1 || J.pose >= n_poses) return fail(c, ROMAN_E_INVALID, "job %d: pose = %d is neither -1 nor one of the %d poses", j, J.pose, n_poses);
+        if (J.base >= 0) {
+            if (named[(size_t)J.base]) return fail(c, ROMAN_E_INVALID, "job %d: base cloud %d is the base of an earlier job", j, J.base);
+            named[(size_t)J.base] = 1;
+        }
+        posed = posed || J.pose >= 0;
+        const int64_t n = (J.base >= 0 ? cloud_off[J.base + 1] - cloud_off[J.base] : 0) + (cloud_off[J.add + 1] - cloud_off[J.add]);
+        if (n > INTEG_JOB_MAX) return fail(c, ROMAN_E_TOO_LARGE, "job %d holds more than 2^28 points", j);
+        *total += n;
+    }
+    if (posed && !poses) return fail(c, ROMAN_E_INVALID, "poses is NULL and a job names one");
+    if (cloud_off[n_clouds] > 0 && !points) return fail(c, ROMAN_E_INVALID, "points is NULL");
+    if (n_jobs > 0 && (!out_count || !out_status || (*total > 0 && !out_points))) return fail(c, ROMAN_E_INVALID, "out_points / out_count / out_status is NULL");
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    return ROMAN_OK;
+}
+
+static inline bool integrate_outlier(const roman_integrate_params_t* P) { return P->outlier_std > 0.0 && std::isfinite(P->outlier_std); }
+
+int roman_segment_integrate_dev(roman_ctx_t* c, const roman_integrate_params_t* params, const double* points, const int64_t* cloud_off_dev,
+                                const int64_t* cloud_off_host, int32_t n_clouds, const double* poses, int32_t n_poses,
+                                const roman_integrate_job_t* jobs_dev, const roman_integrate_job_t* jobs_host, int32_t n_jobs,
+                                double* out_points, int32_t* out_count, int32_t* out_status, double* out_avg, double* out_thr)
+{
+    int64_t total = 0;
+    int rc = integrate_check(c, params, points, cloud_off_host, n_clouds, poses, n_poses, jobs_host, n_jobs, out_points, out_count, out_status, &total);
+    if (rc || n_jobs == 0) return rc;
+    if (!cloud_off_dev) return fail(c, ROMAN_E_INVALID, "cloud_off is NULL on the device");
+    if (!jobs_dev) return fail(c, ROMAN_E_INVALID, "jobs is NULL on the device");
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool outlier = integrate_outlier(params);
+    const int64_t cutW = c->integ_wave_max, cutL = c->integ_lds_max;
+    auto size_of = [&](int32_t j) {
+        const roman_integrate_job_t& J = jobs_host[j];
+        return (J.base >= 0 ? cloud_off_host[J.base + 1] - cloud_off_host[J.base] : 0) + (cloud_off_host[J.add + 1] - cloud_off_host[J.add]);
+    };
+    auto cleaned = [&](int32_t j) { return outlier && cloud_off_host[jobs_host[j].add + 1] > cloud_off_host[jobs_host[j].add]; };
+    // ---- the tables, cut on the host: slot offsets | the jobs of one wave, of a workgroup in LDS, of a workgroup that merges | the
+    // query tiles of the two workgroup classes (none for a job whose added cloud is empty: it has no clean-up) ----
+    size_t n_tiles = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) if (size_of(j) > cutW && cleaned(j)) n_tiles += (size_t)((size_of(j) + INTEG_TILE - 1) / INTEG_TILE);
+    const size_t oItems = (size_t)n_jobs + 1, oTiles = oItems + (size_t)n_jobs, n_tab = oTiles + n_tiles;
+    int64_t* tab = nullptr;
+    HIPCHK(c, c->sgStage.stage(n_tab, &tab));
+    tab[0] = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) tab[j + 1] = tab[j] + size_of(j);
+    int32_t nW = 0, nL = 0, nM = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) if (size_of(j) <= cutW) tab[oItems + nW++] = j;
+    for (int32_t j = 0; j < n_jobs; ++j) if (size_of(j) > cutW && size_of(j) <= cutL) tab[oItems + nW + nL++] = j;
+    for (int32_t j = 0; j < n_jobs; ++j) if (size_of(j) > cutL) tab[oItems + nW + nL + nM++] = j;
+    size_t t = oTiles;
+    for (int32_t k = nW; k < n_jobs; ++k) {
+        const int32_t j = (int32_t)tab[oItems + k];
+        if (!cleaned(j)) continue;
+        for (int64_t q = 0; q * INTEG_TILE < size_of(j); ++q) tab[t++] = ((int64_t)j << 32) | q;
+    }
+    // ---- the workspace, from the host offsets alone ----
+    const size_t room = (size_t)std::max<int64_t>(total, 1);
+    HIPCHK(c, c->sgPts.ensure(sizeof(double) * 3 * room));
+    if (nM) {
+        HIPCHK(c, c->sgKeys.ensure(sizeof(unsigned long long) * room)); HIPCHK(c, c->sgKeys2.ensure(sizeof(unsigned long long) * room));
+        HIPCHK(c, c->sgIdx.ensure(sizeof(int32_t) * room)); HIPCHK(c, c->sgIdx2.ensure(sizeof(int32_t) * room));
+    }
+    if (outlier) HIPCHK(c, c->sgDs.ensure(sizeof(double) * 3 * room));
+    if (outlier && !out_avg) HIPCHK(c, c->sgAvg.ensure(sizeof(double) * room));
+    HIPCHK(c, c->sgM.ensure(sizeof(int32_t) * (size_t)n_jobs));
+    HIPCHK(c, c->sgStage.upload(c->sgItems, n_tab, c->stream));
+    const int64_t* dTab = c->sgItems.as<int64_t>();
+    IntegArgs A{points, cloud_off_dev, poses, reinterpret_cast<const IntegJob*>(jobs_dev), dTab, dTab + oItems,
+                c->sgPts.as<double>(), c->sgDs.as<double>(), c->sgKeys.as<unsigned long long>(), c->sgKeys2.as<unsigned long long>(),
+                c->sgIdx.as<int32_t>(), c->sgIdx2.as<int32_t>(), c->sgM.as<int32_t>(), out_avg ? out_avg : c->sgAvg.as<double>(),
+                out_points, out_count, out_status, out_thr, params->voxel_size, params->outlier_std, outlier ? 1 : 0, (int)cutL};
+    if (nW) hipLaunchKernelGGL(k_integ_front_wave, dim3((unsigned)nW), dim3(64), 0, c->stream, A);
+    if (nL) hipLaunchKernelGGL(k_integ_front_block<false>, dim3((unsigned)nL), dim3(256), 0, c->stream, A, (int)nW);
+    if (nM) hipLaunchKernelGGL(k_integ_front_block<true>, dim3((unsigned)nM), dim3(256), 0, c->stream, A, (int)(nW + nL));
+    if (outlier) {
+        if (nW) hipLaunchKernelGGL(k_integ_knn_wave, dim3((unsigned)((nW + 3) / 4)), dim3(256), 0, c->stream, A, (int)nW);
+        if (n_tiles) hipLaunchKernelGGL(k_integ_knn_tile, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, A, (int)n_jobs);
+        if (nW) hipLaunchKernelGGL(k_integ_finish_wave, dim3((unsigned)((nW + 3) / 4)), dim3(256), 0, c->stream, A, (int)nW);
+        if (nL + nM) hipLaunchKernelGGL(k_integ_finish_block, dim3((unsigned)(nL + nM)), dim3(256), 0, c->stream, A, (int)nW);
+    }
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_segment_integrate(roman_ctx_t* c, const roman_integrate_params_t* params, const double* points, const int64_t* cloud_off, int32_t n_clouds,
+                            const double* poses, int32_t n_poses, const roman_integrate_job_t* jobs, int32_t n_jobs,
+                            double* out_points, int32_t* out_count, int32_t* out_status, double* out_avg, double* out_thr)
+{
+    int64_t total = 0;
+    int rc = integrate_check(c, params, points, cloud_off, n_clouds, poses, n_poses, jobs, n_jobs, out_points, out_count, out_status, &total);
+    if (rc || n_jobs == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    const bool outlier = integrate_outlier(params);
+    HostMirror m(c);
+    const auto dPts = m.in(points, sizeof(double) * 3 * (size_t)cloud_off[n_clouds]);
+    const auto dOff = m.in(cloud_off, sizeof(int64_t) * ((size_t)n_clouds + 1));
+    const auto dPose = m.in(poses, poses ? sizeof(double) * 16 * (size_t)n_poses : 0);
+    const auto dJobs = m.in(jobs, sizeof(roman_integrate_job_t) * (size_t)n_jobs);
+    // what a job leaves untouched — its slot past out_count, a threshold it does not form — comes back as the caller had it
+    const auto dOut = m.inout(out_points, sizeof(double) * 3 * (size_t)total);
+    const auto dCnt = m.out(out_count, sizeof(int32_t) * (size_t)n_jobs);
+    const auto dSt = m.out(out_status, sizeof(int32_t) * (size_t)n_jobs);
+    const auto dAvg = m.inout(out_avg, (out_avg && outlier) ? sizeof(double) * (size_t)total : 0);
+    const auto dThr = m.inout(out_thr, (out_thr && outlier) ? sizeof(double) * (size_t)n_jobs : 0);
+    rc = m.upload();
+    if (rc) return rc;
+    rc = roman_segment_integrate_dev(c, params, dPts.dev(), dOff.dev(), cloud_off, n_clouds, dPose.dev(), n_poses, dJobs.dev(), jobs, n_jobs,
+                                     dOut.dev() /* NULL when every slot is empty */, dCnt.dev(), dSt.dev(), dAvg.dev(), dThr.dev());
+    if (rc) return rc;
+    return m.download();
+}
+
+int roman_ctx_set_integrate_cuts(roman_ctx_t* c, int32_t wave_max, int32_t lds_max)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    const int w = wave_max ? wave_max : INTEG_WAVE_MAX, l = lds_max ? lds_max : INTEG_LDS_MAX;
+    if (wave_max < 0 || lds_max < 0 || l > INTEG_LDS_CAP || l < 2 || w > l)
+        return fail(c, ROMAN_E_INVALID, "wave_max = %d, lds_max = %d: 0 <= wave_max <= lds_max, 2 <= lds_max <= %d (0: the default)", wave_max, lds_max, INTEG_LDS_CAP);
+    c->integ_wave_max = w; c->integ_lds_max = l;
     return ROMAN_OK;
 }
 

@@ -424,6 +424,51 @@ def _assoc_sizes(clouds, N1, N2, desc):
     return N1, N2, (N1 if N2 < 0 else N2), desc, d
 
 
+def integrate_params(voxel_size=0.05, outlier_std=1.0):
+    """-> roman_integrate_params_t; the defaults are MapperParams' segment_voxel_size and segment_outlier_removal_std
+    [REF roman/params/mapper_params.py:73-74].  outlier_std None, not finite or <= 0: no outlier removal [REF :100-103]."""
+    P = _abi.RomanIntegrateParams()
+    P.voxel_size = float(voxel_size)
+    P.outlier_std = 0.0 if outlier_std is None else float(outlier_std)
+    P.nb_neighbors = _abi.ROMAN_INTEGRATE_NEIGHBORS
+    return P
+
+
+def integrate_jobs(jobs):
+    """The job table of a segment update in the C ABI's type: rows (base, add) or (base, add, pose); None stands for -1."""
+    rows = [tuple(-1 if v is None else int(v) for v in j) for j in jobs]
+    out = np.zeros(len(rows), dtype=_abi.INTEGRATE_JOB_DTYPE)
+    for k, r in enumerate(rows):
+        if len(r) not in (2, 3):
+            raise ValueError("a job is (base, add) or (base, add, pose)")
+        out[k] = (r[0], r[1], r[2] if len(r) == 3 else -1)
+    return out
+
+
+def integrate_slots(cloud_off, jobs):
+    """The slot offsets of a job table (n_jobs + 1,): the exclusive prefix sum of n(base) + n(add) — where roman_segment_integrate*
+    puts every job's output."""
+    n = np.diff(np.asarray(cloud_off, dtype=np.int64))
+    size = [(int(n[j["base"]]) if j["base"] >= 0 else 0) + int(n[j["add"]]) for j in jobs]
+    return np.concatenate([[0], np.cumsum(size, dtype=np.int64)]).astype(np.int64)
+
+
+@dataclass
+class IntegrateOutput:
+    """What roman_segment_integrate writes: points (total, 3) and avg (total,) by slot, count / status (n_jobs,) int32, thr
+    (n_jobs,), slot (n_jobs + 1,).  avg and thr are None when not asked for."""
+    points: np.ndarray
+    count: np.ndarray
+    status: np.ndarray
+    avg: Optional[np.ndarray]
+    thr: Optional[np.ndarray]
+    slot: np.ndarray
+
+    def cloud(self, j):
+        """Job j's cleaned cloud (count, 3)."""
+        return self.points[self.slot[j]:self.slot[j] + self.count[j]]
+
+
 def session_frame_robot_dtype():
     """roman_session_frame_robot_t as a structured dtype."""
     return np.dtype([("seg0", np.int64), ("mask_off", np.int64), ("n_seg", np.int32), ("sub0", np.int32), ("n_sub", np.int32), ("frame0", np.int32),
@@ -1349,6 +1394,52 @@ class Context:
         """Measurement only (roman_ctx_set_assoc_cuts): the point counts up to which a cloud's keys are sorted by one wave / by
         one workgroup in LDS; 0: the default.  Results do not depend on them."""
         self._check(self._lib.roman_ctx_set_assoc_cuts(self._h, int(wave_max), int(lds_max)), "roman_ctx_set_assoc_cuts")
+
+    # ------------------------------------------------------------------ segment update (DESIGN.md §4.26)
+    def segment_integrate(self, iparams, points, cloud_off, jobs, poses=None, want_avg=False, want_thr=True, out_points=None, out_avg=None, out_thr=None):
+        """Host-pointer segment update (roman_segment_integrate): points (P, 3), cloud_off (clouds + 1,), jobs an integrate_jobs()
+        table or rows (base, add[, pose]), poses (n_poses, 4, 4) or None; iparams an integrate_params() block.  out_points (total, 3),
+        out_avg (total,), out_thr (n_jobs,): arrays of the caller's, whose untouched elements keep their values (fresh ones start
+        at 0, the thresholds at NaN).  -> IntegrateOutput."""
+        points, cloud_off, clouds = _segment_clouds(points, cloud_off)
+        jobs = jobs if isinstance(jobs, np.ndarray) and jobs.dtype == np.dtype(_abi.INTEGRATE_JOB_DTYPE) else integrate_jobs(jobs)
+        jobs = np.ascontiguousarray(jobs)
+        n_jobs = int(jobs.shape[0])
+        if n_jobs and (jobs["add"].min() < 0 or max(jobs["add"].max(), jobs["base"].max()) >= clouds or jobs["base"].min() < -1):
+            raise ValueError(f"a job names a cloud outside the {clouds} given")
+        n_poses = 0
+        if poses is not None:
+            poses = _f64(poses)
+            if poses.ndim != 3 or poses.shape[1:] != (4, 4):
+                raise ValueError("poses must be (n_poses, 4, 4)")
+            n_poses = int(poses.shape[0])
+        slot = integrate_slots(cloud_off, jobs)
+        total = int(slot[-1])
+        out_points = _given(out_points, (total, 3), np.float64, 0.0)
+        count, status = np.zeros(n_jobs, dtype=np.int32), np.zeros(n_jobs, dtype=np.int32)
+        avg = _given(out_avg, (total,), np.float64, 0.0) if (want_avg or out_avg is not None) else None
+        thr = _given(out_thr, (n_jobs,), np.float64, np.nan) if (want_thr or out_thr is not None) else None
+        self._generation += 1
+        rc = self._lib.roman_segment_integrate(self._h, C.byref(iparams), _ptr(points), _ptr(cloud_off), clouds, _ptr(poses), n_poses,
+                                               _ptr(jobs), n_jobs, _ptr(out_points), _ptr(count), _ptr(status), _ptr(avg), _ptr(thr))
+        self._check(rc, "roman_segment_integrate")
+        return IntegrateOutput(out_points, count, status, avg, thr, slot)
+
+    def segment_integrate_dev(self, iparams, points_ptr, cloud_off_ptr, cloud_off, poses_ptr, n_poses, jobs_ptr, jobs, out_points_ptr, out_count_ptr,
+                              out_status_ptr, out_avg_ptr=None, out_thr_ptr=None):
+        """Device-pointer form (roman_segment_integrate_dev): every array on the device; `cloud_off` and `jobs` (an integrate_jobs()
+        table) are the same numbers on the host — the slots, the launches and the workspace are sized from them.  A pure enqueue
+        on the context's stream."""
+        cloud_off = np.ascontiguousarray(cloud_off, dtype=np.int64).reshape(-1)
+        jobs = np.ascontiguousarray(jobs, dtype=_abi.INTEGRATE_JOB_DTYPE)
+        self._enqueue("roman_segment_integrate_dev", C.byref(iparams), _vp(points_ptr), _vp(cloud_off_ptr), _ptr(cloud_off), int(cloud_off.shape[0]) - 1,
+                      _vp(poses_ptr), int(n_poses), _vp(jobs_ptr), _ptr(jobs), int(jobs.shape[0]), _vp(out_points_ptr), _vp(out_count_ptr),
+                      _vp(out_status_ptr), _vp(out_avg_ptr), _vp(out_thr_ptr))
+
+    def set_integrate_cuts(self, wave_max=0, lds_max=0):
+        """Measurement only (roman_ctx_set_integrate_cuts): the point counts (base + added) up to which a job is one wave's / is
+        sorted by one workgroup in LDS; 0: the default.  Results do not depend on them."""
+        self._check(self._lib.roman_ctx_set_integrate_cuts(self._h, int(wave_max), int(lds_max)), "roman_ctx_set_integrate_cuts")
 
     def grid_gate_aabb(self, gparams, box0, box1, pos0, T_w0, pos1, T_w1, time0=None, time1=None, desc0=None, desc1=None, pos_gt0=None, pos_gt1=None,
                        sim_in=None, pairs=None, T_ref=None, enable=None):
