@@ -10,13 +10,29 @@ asserts on the oracle alone that at most 1 % of the points of this file's clouds
 an empty result and is asserted as such.
 
 Every size class (one wave, a workgroup in LDS, a workgroup merging through global memory), both cut settings and two calls give
-identical bytes; slots are filled with a sentinel beforehand and nothing past out_count[j] changes."""
+identical bytes; slots are filled with a sentinel beforehand and nothing past out_count[j] changes.
+
+What the planted cases cover beyond random clouds (the clouds are tests/_integrate_clouds.py's):
+  the merge class at its real cut   jobs of 4097, 8192, 8193 and 4100 + 8200 points at the DEFAULT cuts, where the chunk is
+                                    ROMAN_INTEGRATE_LDS_MAX = 4096 pairs: chunks that fill the team's LDS, a last chunk of one pair,
+                                    a run without a sibling in a merge pass, the voxel sums over the global ping-pong, and a
+                                    threshold and compaction over m > 4096 points — each held to the oracle, to the chunks of 64
+                                    and to a second call.
+  the staging edges of the search   m = 1023, 1024, 1025 (1024 columns are staged at a time, 256 queries are one workgroup's).
+  keys planted on voxel faces       `faces` puts every quotient (p - origin) / vs within a rounding of an integer, at three voxel
+                                    sizes, as a new segment, as a posed observation and at 5000 points through the merge class.
+                                    tests/test_integrate_oracle_cpu.py shows on the CPU that a multiplication by 1 / vs changes voxel
+                                    indices of every one of these clouds (and none of a random blob): a kernel that divides
+                                    cheaply fails here bit for bit.
+  both sides of the RANGE edge      a span of 2^21 - 1 voxels — the last that fits, key 2^63 - 1 on all three axes — is OK, 2^21
+                                    is RANGE; as two points through one wave and, padded, through the two workgroup classes."""
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
 import _integrate_oracle as io
+from _integrate_clouds import FACE_CORNER, FACE_SIZES, SPAN_AXES, VS, blob, body, faces, lattice, pose, span_padded, span_pair
 from roman_amd import _abi
 from roman_amd.align import SegmentClouds
 from roman_amd.map import IntegrationParams, cleanup_points, integrate
@@ -25,35 +41,10 @@ from roman_amd.runtime import integrate_jobs, integrate_params, integrate_slots
 pytestmark = pytest.mark.gpu
 
 GUARD = -7.25e300
-VS = 0.05
 CUTS = {"wave": (4096, 4096), "default": (0, 0), "merge": (16, 64)}      # every job in one wave | the default classes | chunks of 64 merged
 SIZES = (1, 2, 9, 10, 11, 63, 64, 65, 256, 257)
-
-
-def blob(seed, n, side, centre=(0.0, 0.0, 0.0)):
-    """n points uniform in a cube of `side` voxels"""
-    return np.asarray(centre) + np.random.default_rng(seed).uniform(-0.5 * side, 0.5 * side, (n, 3)) * VS
-
-
-def lattice(seed, n, origin=(0.0, 0.0, 0.0)):
-    """n points, every one alone in its voxel: cell centres of a 7-wide lattice with gaps, jittered by a fifth of a voxel"""
-    i = np.arange(n)
-    cells = np.stack([i % 7, (i // 7) % 7, i // 49], axis=1) * np.array([1.0, 2.0, 1.0])
-    return np.asarray(origin) + (cells + 0.5 + np.random.default_rng(seed).uniform(-0.2, 0.2, (n, 3))) * VS
-
-
-def pose(seed):
-    rng = np.random.default_rng(seed)
-    T = np.eye(4)
-    q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
-    T[:3, :3] = q * np.sign(np.linalg.det(q))
-    T[:3, 3] = rng.normal(size=3)
-    return T
-
-
-def body(points, T):
-    """the points in the body frame of pose T (so that the posed cloud lands where `points` is, up to rounding)"""
-    return (np.asarray(points) - T[:3, 3]) @ T[:3, :3]
+STAGES = (1023, 1024, 1025)               # around the 1024 columns k_integ_knn_tile stages at a time: one stage | exactly one | a second of one column
+LDS_MAX = _abi.ROMAN_INTEGRATE_LDS_MAX
 
 
 # ----------------------------------------------------------------------------------------------------------------- the cases
@@ -85,15 +76,63 @@ def case_mixed():
     return SimpleNamespace(name="mixed", clouds=c, jobs=jobs, poses=np.array([T]))
 
 
-CASES = {c.name: c for c in (case_sizes(), case_large(600), case_large(2500), case_mixed())}
+def case_stages():
+    """m = n at the staging edges of the workgroup search"""
+    clouds = [lattice(n, n, (-1.0, 2.0, 0.3)) for n in STAGES]
+    return SimpleNamespace(name="stages", clouds=clouds, jobs=[(None, k, None) for k in range(len(clouds))], poses=None)
+
+
+def case_merge(n):
+    """One new segment beyond the default LDS cut: a lattice (m = n) at 4097, blobs of 30 voxels a side at 8192 and 8193."""
+    cloud = lattice(n, n, (-1.0, 2.0, 0.3)) if n == 4097 else blob(n, n, 30.0, FACE_CORNER)
+    return SimpleNamespace(name=f"merge{n}", clouds=[cloud], jobs=[(None, 0, None)], poses=None, merged=[0])
+
+
+def case_merge_two():
+    """A base of 4100 points with a posed observation of 8200 (pose 1 of two), and new segments of 300 and of 200 points: the
+    merging workgroup, the LDS workgroup and one wave in one call."""
+    T = pose(12300)
+    whole = blob(12300, 12300, 34.0, FACE_CORNER)
+    clouds = [whole[:4100], body(whole[4100:], T), blob(12301, 300, 7.0, (-2.0, 0.0, 1.0)), blob(12302, 200, 6.0, (0.0, 4.0, 0.0))]
+    return SimpleNamespace(name="merge_two", clouds=clouds, jobs=[(0, 1, 1), (None, 2, None), (None, 3, None)], poses=np.array([pose(12299), T]), merged=[0])
+
+
+def case_faces(vs):
+    """600 points on voxel faces as a new segment and as a posed observation onto an empty base (the assembled coordinates are
+    then a rounding away from the faces); at the file's voxel size also 5000 points in 24 voxels a side: the merge class at the
+    default cuts, many points per voxel."""
+    T = pose(600)
+    p = faces(600, 600, FACE_CORNER, 12, vs)
+    clouds, jobs = [p, np.zeros((0, 3)), body(p, T)], [(None, 0, None), (1, 2, 0)]
+    if vs == VS:
+        clouds, jobs = clouds + [faces(5000, 5000, FACE_CORNER, 24, vs)], jobs + [(None, 3, None)]
+    return SimpleNamespace(name=f"faces{vs}", clouds=clouds, jobs=jobs, poses=np.array([T]), vs=vs)
+
+
+def case_span(padded):
+    """Per SPAN_AXES a cloud whose span is the last that fits (index KEY_TOP: jobs 0-3) and one beyond it (jobs 4-7); as two
+    points, or padded with 300 points next to the first corner."""
+    clouds = [span_padded(40 + k, t, axes) if padded else span_pair(t, axes) for t in (io.KEY_TOP, io.KEY_TOP + 1) for k, axes in enumerate(SPAN_AXES)]
+    return SimpleNamespace(name="span_padded" if padded else "span", clouds=clouds, jobs=[(None, k, None) for k in range(len(clouds))], poses=None)
+
+
+MERGE = ("merge4097", "merge8192", "merge8193", "merge_two")
+FACES = tuple(f"faces{vs}" for vs in FACE_SIZES)
+CASES = {c.name: c for c in (case_sizes(), case_large(600), case_large(2500), case_mixed(), case_stages(), case_merge(4097), case_merge(8192),
+                             case_merge(8193), case_merge_two(), *(case_faces(vs) for vs in FACE_SIZES), case_span(False), case_span(True))}
 _ORACLE = {}
+
+
+def sizes_of(case):
+    """n(base) + n(add) per job: what the host cuts the classes by"""
+    return [(0 if b is None else len(case.clouds[b])) + len(case.clouds[a]) for b, a, _ in case.jobs]
 
 
 def oracle(name, std):
     """The oracle's answer per job of a case, computed once."""
     if (name, std) not in _ORACLE:
         c = CASES[name]
-        P = io.params(VS, std)
+        P = io.params(getattr(c, "vs", VS), std)
         _ORACLE[name, std] = [io.integrate(None if b is None else c.clouds[b], c.clouds[a], None if p is None else c.poses[p], P) for b, a, p in c.jobs]
     return _ORACLE[name, std]
 
@@ -111,7 +150,7 @@ def run(ctx, case, std, cuts="default"):
     total = int(integrate_slots(off, integrate_jobs(case.jobs))[-1])
     ctx.set_integrate_cuts(*CUTS[cuts])
     try:
-        return ctx.segment_integrate(integrate_params(VS, std), pts, off, case.jobs, case.poses, out_points=np.full((total, 3), GUARD),
+        return ctx.segment_integrate(integrate_params(getattr(case, "vs", VS), std), pts, off, case.jobs, case.poses, out_points=np.full((total, 3), GUARD),
                                      out_avg=np.full(total, GUARD), out_thr=np.full(n_jobs, GUARD))
     finally:
         ctx.set_integrate_cuts(0, 0)
@@ -205,8 +244,9 @@ def test_sizes_are_what_they_plant():
 
 @pytest.mark.parametrize("n", [600, 2500])
 def test_large_clouds_through_every_class(ctx, n):
-    """A cloud of n points as a new segment and as base + posed observation, through one wave, the LDS workgroup (2500: the merge
-    at default cuts would need more than 4096 points, so the default is the LDS class for both) and the merging workgroup."""
+    """A cloud of n points as a new segment and as base + posed observation, through one wave, the LDS workgroup (both sizes lie
+    below the default cut of 4096 points, so the default is the LDS class for both) and the merging workgroup with chunks of 64.
+    The merge at the default cuts, from 4097 points on, is test_merge_class_at_the_default_cuts'."""
     case = CASES[f"large{n}"]
     off = run(ctx, case, None)
     check_off(case, off)
@@ -215,6 +255,79 @@ def test_large_clouds_through_every_class(ctx, n):
     assert same(on, run(ctx, case, 1.0))
     for cuts in ("wave", "merge"):
         assert same(off, run(ctx, case, None, cuts)) and same(on, run(ctx, case, 1.0, cuts)), f"the {cuts} class differs"
+
+
+def through_every_class(ctx, case):
+    """Held to the oracle at the default cuts, step off and on; then a second call and both other cut settings give the same bytes."""
+    off = run(ctx, case, None)
+    check_off(case, off)
+    on = run(ctx, case, 1.0)
+    check_on(case, on, 1.0)
+    assert same(on, run(ctx, case, 1.0)) and same(off, run(ctx, case, 0.0)), "two calls differ"
+    for cuts in ("wave", "merge"):
+        assert same(off, run(ctx, case, None, cuts)) and same(on, run(ctx, case, 1.0, cuts)), f"the {cuts} class differs"
+    return off, on
+
+
+@pytest.mark.parametrize("name", MERGE)
+def test_merge_class_at_the_default_cuts(ctx, name):
+    """The merging workgroup as the mapper reaches it: chunks of ROMAN_INTEGRATE_LDS_MAX pairs.  4097 = one full chunk and one of
+    a single pair, m = n; 8192 = two full chunks, one pass; 8193 = three runs and two passes, the third run without a sibling in
+    the first; 4100 + 8200 posed points with an LDS-class and a wave-class job in the same call.  Every merged job is past the
+    cut by n and by m (the threshold and the compaction then run over m > 4096 too)."""
+    case = CASES[name]
+    n, ms = sizes_of(case), [len(r.down) for r in oracle(name, 1.0)]
+    assert all(n[j] > LDS_MAX and ms[j] > LDS_MAX for j in case.merged), (n, ms)
+    if name == "merge_two":
+        assert n == [3 * LDS_MAX + 12, 300, 200] and _abi.ROMAN_INTEGRATE_WAVE_MAX < n[1] <= LDS_MAX and n[2] <= _abi.ROMAN_INTEGRATE_WAVE_MAX
+    else:
+        assert n[0] == {"merge4097": LDS_MAX + 1, "merge8192": 2 * LDS_MAX, "merge8193": 2 * LDS_MAX + 1}[name] and (name != "merge4097" or ms[0] == n[0])
+    through_every_class(ctx, case)
+
+
+def test_staging_edges_of_the_neighbour_search(ctx):
+    """m = 1023, 1024, 1025 down-sampled points: no second stage of columns, none either with the first one full, and a second
+    stage of one column with a fifth query tile of one valid query — through the workgroup search (default) and the wave's."""
+    case = CASES["stages"]
+    assert [len(r.down) for r in oracle("stages", 1.0)] == list(STAGES) == sizes_of(case) and STAGES[1] == 1024 and max(STAGES) <= LDS_MAX
+    through_every_class(ctx, case)
+
+
+@pytest.mark.parametrize("name", FACES)
+def test_keys_planted_on_voxel_faces(ctx, name):
+    """Every quotient (p - origin) / vs of these clouds lies within a rounding of an integer, so the voxel a point falls in
+    depends on the correctly rounded subtraction and division (tests/test_integrate_oracle_cpu.py: the reciprocal moves points
+    of every one of them).  Bit for bit with the oracle, in every class."""
+    case = CASES[name]
+    if case.vs == VS:
+        assert sizes_of(case)[2] > LDS_MAX
+    off, _ = through_every_class(ctx, case)
+    assert off.count[0] < 600 and off.count[1] < 600              # points share voxels: the sums are not trivial
+
+
+def test_the_last_span_that_fits(ctx):
+    """Voxel index 2^21 - 1 on an axis is the last the key holds — on all three axes the key is 2^63 - 1, one below the padding
+    key's top bit — and 2^21 is RANGE: two points through one wave, then padded to 302 points through the LDS workgroup (default)
+    and the merging one."""
+    top = np.full(3, VS * (io.KEY_TOP - 0.5))
+    idx = io.voxel_indices(CASES["span_padded"].clouds[0], VS)
+    assert int(io.pack(idx)[1]) == 2 ** 63 - 1 and np.sum(np.all(idx == io.KEY_TOP, axis=1)) == 1
+    for name in ("span", "span_padded"):
+        case = CASES[name]
+        assert [r.status for r in oracle(name, None)] == [io.OK] * 4 + [io.RANGE] * 4
+        assert all(_abi.ROMAN_INTEGRATE_WAVE_MAX < n <= LDS_MAX for n in sizes_of(case)) if name == "span_padded" else sizes_of(case) == [2] * 8
+        off, on = through_every_class(ctx, case)
+        assert off.status.tolist() == on.status.tolist() == [io.OK] * 4 + [io.RANGE] * 4
+        assert np.all(off.count[4:] == 0) and np.all(on.count[4:] == 0) and np.all(off.points[off.slot[4]:] == GUARD) and np.all(on.points[on.slot[4]:] == GUARD)
+        for j, axes in enumerate(SPAN_AXES):
+            far = case.clouds[j][1]
+            got = off.cloud(j)
+            assert np.sum(np.all(got == far, axis=1)) == 1, (name, j, "the far point is alone in its voxel and comes back as it is")
+            if name == "span":
+                assert off.count[j] == 2 and got.tobytes() == case.clouds[j].tobytes() and on.count[j] == 0
+            else:
+                assert on.count[j] == off.count[j] - 1 and not np.any(np.all(on.cloud(j) == far, axis=1)), (name, j, "the far point alone is an outlier")
+        assert off.cloud(0)[-1].tobytes() == top.tobytes() and off.cloud(1)[-1].tobytes() == CASES[name].clouds[1][1].tobytes()      # sorted last: x is the most significant
 
 
 def test_range_status_and_other_deviations(ctx):

@@ -1,10 +1,12 @@
 """tests/_integrate_oracle.py held to itself and to SciPy, without a GPU: the sort-and-runs down-sample against
 the dict-of-accumulators form; the mean neighbour distances against scipy.spatial.cKDTree; the consequences of open3d's outlier
-rule at m = 1, 2, 9, 10, 11."""
+rule at m = 1, 2, 9, 10, 11; and what the planted clouds of tests/test_gpu_segment_integrate.py plant: that the `faces` clouds
+tell (p - origin) / vs from (p - origin) * (1 / vs) and a random blob does not, and both sides of the last span the key holds."""
 import numpy as np
 import pytest
 from scipy.spatial import cKDTree
 
+import _integrate_clouds as clouds
 import _integrate_oracle as io
 
 VOXEL_SIZES = (0.05, 0.1, 0.2, 0.3, 1.0)
@@ -44,6 +46,68 @@ def test_down_sample_order_and_range():
     assert io.down_sample(np.array([[0.0, 0.0, np.nan]]), vs) is None
     assert io.down_sample(np.array([[0.0, 0.0, 0.0], [vs * 2.0 ** 21, 0.0, 0.0]]), vs) is None
     assert len(io.down_sample(np.array([[0.0, 0.0, 0.0], [vs * (2.0 ** 21 - 2), 0.0, 0.0]]), vs)) == 2
+
+
+def posed(points, seed):
+    """`points` taken into the body frame of a random pose and back by the oracle's row-wise expression: a rounding off the faces"""
+    T = clouds.pose(seed)
+    return io.world_points(clouds.body(points, T), T)
+
+
+FACE_CLOUDS = {f"faces 600 vs {vs}": (lambda vs=vs: clouds.faces(600, 600, clouds.FACE_CORNER, 12, vs), vs) for vs in clouds.FACE_SIZES}
+FACE_CLOUDS.update({f"faces 600 posed vs {vs}": (lambda vs=vs: posed(clouds.faces(600, 600, clouds.FACE_CORNER, 12, vs), 600), vs) for vs in clouds.FACE_SIZES})
+FACE_CLOUDS["faces 5000 vs 0.05"] = (lambda: clouds.faces(5000, 5000, clouds.FACE_CORNER, 24, clouds.VS), clouds.VS)
+
+
+@pytest.mark.parametrize("name", list(FACE_CLOUDS))
+def test_face_clouds_tell_the_division_from_a_reciprocal(name):
+    """The evidence behind tests/test_gpu_segment_integrate.py::test_keys_planted_on_voxel_faces: on every `faces` cloud of that
+    file — as planted, and assembled through a pose — floor((p - origin) * (1 / vs)) differs from floor((p - origin) / vs) in at
+    least one row, so a kernel that multiplies by the reciprocal cannot return the oracle's bits there.  The two forms of the
+    oracle's down-sample agree on them."""
+    make, vs = FACE_CLOUDS[name]
+    p = make()
+    rows = clouds.cheap_rows(p, vs)
+    print(f"{name}: the reciprocal changes the voxel index of {rows} of {len(p)} rows")
+    assert rows >= 1
+    if "posed" not in name:
+        assert np.all(p >= p[0]) and p[0].tolist() == list(clouds.FACE_CORNER)     # the first point is the minimum corner
+    a, b = io.down_sample(p, vs), io.down_sample_literal(p, vs)
+    assert a.shape == b.shape and a.tobytes() == b.tobytes() and len(a) < len(p)
+
+
+def test_a_random_blob_does_not_tell_them_apart():
+    """... which is why the random clouds alone proved nothing about the division: no quotient of a blob comes near an integer."""
+    for seed, n, side in ((5000, 5000, 24.0), (600, 600, 7.0)):
+        rows = clouds.cheap_rows(clouds.blob(seed, n, side, clouds.FACE_CORNER), clouds.VS)
+        print(f"blob of {n}: the reciprocal changes the voxel index of {rows} rows")
+        assert rows == 0
+
+
+@pytest.mark.parametrize("axes", clouds.SPAN_AXES)
+def test_the_last_span_that_fits(axes):
+    """Voxel index KEY_TOP = 2^21 - 1 is the last an axis of the key holds; on all three axes the key is 2^63 - 1."""
+    vs = clouds.VS
+    fits, over = clouds.span_pair(io.KEY_TOP, axes), clouds.span_pair(io.KEY_TOP + 1, axes)
+    idx = io.voxel_indices(fits, vs)
+    assert idx[0].tolist() == [0, 0, 0] and idx[1].tolist() == [io.KEY_TOP if k in axes else 0 for k in range(3)]
+    if len(axes) == 3:
+        assert int(io.pack(idx)[1]) == 2 ** 63 - 1
+    assert io.down_sample(fits, vs).tobytes() == fits.tobytes() == io.down_sample_literal(fits, vs).tobytes()
+    r = io.cleanup(fits, io.params(vs, None))
+    assert r.status == io.OK and len(r.points) == 2
+    assert io.voxel_indices(over, vs) is None and io.down_sample(over, vs) is None
+    r = io.cleanup(over, io.params(vs, 1.0))
+    assert r.status == io.RANGE and len(r.points) == 0 and r.avg is None
+    # padded with 300 points in the positive octant the minimum corner, and so both answers, stay
+    seed = 40 + clouds.SPAN_AXES.index(axes)
+    for t, status in ((io.KEY_TOP, io.OK), (io.KEY_TOP + 1, io.RANGE)):
+        p = clouds.span_padded(seed, t, axes)
+        assert np.all(p.min(axis=0) == 0.0) and io.cleanup(p, io.params(vs, None)).status == status
+    p = clouds.span_padded(seed, io.KEY_TOP, axes)
+    idx = io.voxel_indices(p, vs)
+    far = np.all(idx == idx[1], axis=1)
+    assert far.sum() == 1 and (len(axes) < 3 or np.argmax(io.pack(idx)) == 1)
 
 
 def ulps(a, b):
