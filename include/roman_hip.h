@@ -1610,6 +1610,75 @@ ROMAN_API int roman_segment_integrate(roman_ctx_t* ctx, const roman_integrate_pa
 ROMAN_API int roman_ctx_set_integrate_cuts(roman_ctx_t* ctx, int32_t wave_max, int32_t lds_max);
 
 /*
+ * roman_segment_cluster_dev: what the mapper does to a segment that goes inactive — Segment.final_cleanup
+ * [REF roman/object/segment.py:195-220], called with clustering_epsilon when a segment has not been seen for max_t_no_sightings
+ * [REF roman/map/mapper.py:92-105]: open3d's cluster_dbscan(eps, min_points) over the segment's cloud, then "keep the largest
+ * cluster".  One call takes a LIST OF JOBS, one per segment going inactive.  Bulk data on the DEVICE; a PURE ENQUEUE on the
+ * context's stream: no synchronisation, no read-back.
+ *   params          roman_cluster_params_t, below
+ *   points          float64[P][3]: n_clouds clouds one behind the other, P = cloud_off_host[n_clouds] [REF roman/object/segment.py:203-205]
+ *   cloud_off_dev   int64[n_clouds + 1] on the device, cloud_off_host the same numbers on the HOST: ascending, [0] == 0
+ *   jobs_dev        int32[n_jobs] on the device, jobs_host the same on the HOST: the cloud of every job — the segments of
+ *                   to_rm [REF roman/map/mapper.py:93-95].  A cloud is named by at most one job
+ *   SLOTS           job j owns the elements [slot_j, slot_j + n(cloud_j)) of out_points and out_labels, slot_j the exclusive
+ *                   prefix sum of the point counts of the jobs in front of it, computed from cloud_off_host alone; all workspace
+ *                   is laid out the same way, and no write of a job leaves its slot
+ *   out_points      float64[total][3]: the first out_count[j] rows of slot j are the kept cluster's points in INPUT ORDER
+ *                   [REF roman/object/segment.py:217-218]; the rest of the slot is left untouched.  May be NULL when total == 0
+ *   out_count       int32[n_jobs]: 0 with n_clusters == 0 is the case in which the reference's np.argmax raises
+ *                   [REF roman/object/segment.py:211-214] and the mapper's except branch drops the segment [REF roman/map/mapper.py:97-105]
+ *   out_status      int32[n_jobs], the vocabulary of roman_assoc_scores: ROMAN_ASSOC_OK; ROMAN_ASSOC_EMPTY: the cloud holds no
+ *                   point (the reference does nothing to points = None [REF roman/object/segment.py:203]), count 0;
+ *                   ROMAN_ASSOC_RANGE: a coordinate is not finite — count 0, the slot of out_labels untouched.  Both write
+ *                   n_clusters 0 and kept -1
+ *   out_labels      int32[total] or NULL: open3d's label of every input point [REF roman/object/segment.py:205], -1: noise
+ *   out_n_clusters  int32[n_jobs]: max(label) + 1 [REF roman/object/segment.py:208-211]
+ *   out_kept        int32[n_jobs] or NULL: the label of the kept cluster [REF roman/object/segment.py:214], -1 when there is none
+ *   NO ALIASING     the rule of roman_segment_integrate_dev: no output may overlap points, cloud_off, jobs or another output
+ * Semantics (tests/_dbscan_oracle.py states them twice: open3d's loop literally, and the closed form below; a CPU test holds one
+ * to the other).  open3d is not compared with: three things are UNPINNED.  (1) THE ROUNDING OF d2: d2(i, j) = (dx dx + dy dy) +
+ * dz dz in double without contraction, the expression of roman_segment_integrate_dev.  (2) THE STRICT RADIUS COMPARISON: j is a
+ * neighbour of i iff d2 < eps eps (nanoflann's radius result set), eps eps formed once in double; every point is its own
+ * neighbour and the relation is symmetric bit for bit.  (3) THE CLOSED FORM OF THE LABEL ORDER: i is a core point iff it has at
+ * least min_points neighbours, itself included; clusters are the connected components of the core points under the neighbour
+ * relation, labelled 0, 1, ... in ascending order of their smallest core index; a non-core point with a core neighbour takes the
+ * smallest label among its core neighbours, one without is noise (-1) — what open3d's sequential loop (outer index ascending, a
+ * cluster expanded fully before the next, noise relabelled by a later cluster that reaches it) arrives at.  Then final_cleanup:
+ * sizes count core and border members; the largest cluster is kept, among equals the lowest label (np.argmax).  Integer atomics
+ * only, and the roots of the union-find do not depend on the schedule: two calls give the same bytes, and so does every size
+ * class.  n_jobs == 0: ROMAN_OK, nothing written.
+ * Errors (ROMAN_E_INVALID with a roman_last_error text, nothing enqueued; the argument checks run before the context is looked
+ * at): NULL params; eps not finite or <= 0; min_points < 1; a negative count; NULL cloud_off_host, [0] != 0 or descending; NULL
+ * jobs_host; a job out of range; a cloud named twice; NULL points with P > 0; NULL out_points / out_count / out_status /
+ * out_n_clusters; NULL ctx; NULL cloud_off_dev or jobs_dev.  More than INT32_MAX points in a cloud or 2^28 in the call:
+ * ROMAN_E_TOO_LARGE.
+ */
+#define ROMAN_CLUSTER_MIN_POINTS 10     /* final_cleanup's default [REF roman/object/segment.py:195] */
+#define ROMAN_CLUSTER_WAVE_MAX  256     /* a job of at most so many points is one wave's (roman_ctx_set_cluster_cuts) */
+#define ROMAN_CLUSTER_LDS_MAX  1536     /* ... of at most so many is one workgroup's, resident in LDS; larger jobs are tiled through global memory */
+#define ROMAN_CLUSTER_TILE      256     /* query points of one workgroup of the tiled class */
+#define ROMAN_CLUSTER_COLS     1024     /* column points the tiled class stages in LDS at a time */
+typedef struct roman_cluster_params {
+    double  eps;          /* clustering_epsilon [REF roman/params/mapper_params.py:68]; finite, > 0 */
+    int32_t min_points;   /* final_cleanup's default 10 [REF roman/object/segment.py:195]; >= 1; a RUN-TIME value */
+} roman_cluster_params_t;
+ROMAN_API int roman_segment_cluster_dev(roman_ctx_t* ctx, const roman_cluster_params_t* params, const double* points, const int64_t* cloud_off_dev,
+                                        const int64_t* cloud_off_host, int32_t n_clouds, const int32_t* jobs_dev, const int32_t* jobs_host, int32_t n_jobs,
+                                        double* out_points, int32_t* out_count, int32_t* out_status, int32_t* out_labels, int32_t* out_n_clusters,
+                                        int32_t* out_kept);
+
+/* The same with HOST pointers everywhere.  Synchronous.  What a job leaves untouched comes back as the caller had it. */
+ROMAN_API int roman_segment_cluster(roman_ctx_t* ctx, const roman_cluster_params_t* params, const double* points, const int64_t* cloud_off, int32_t n_clouds,
+                                    const int32_t* jobs, int32_t n_jobs, double* out_points, int32_t* out_count, int32_t* out_status,
+                                    int32_t* out_labels, int32_t* out_n_clusters, int32_t* out_kept);
+
+/* Measurement and tests only: the two point counts at which a job of roman_segment_cluster* changes its kernel set — up to wave_max
+   one wave, up to lds_max one workgroup with the job resident in LDS, beyond it (job, query tile) workgroups through global memory.
+   0: the default again (ROMAN_CLUSTER_WAVE_MAX, ROMAN_CLUSTER_LDS_MAX); wave_max <= 256, wave_max <= lds_max, 1 <= lds_max <= 1536.
+   Every class gives the same bytes, so results do not depend on the cuts. */
+ROMAN_API int roman_ctx_set_cluster_cuts(roman_ctx_t* ctx, int32_t wave_max, int32_t lds_max);
+
+/*
  * roman_session_gate_aabb_dev: roman_session_gate_dev with the bounding-box gate [REF roman/align/submap_align.py:101-103]
  * — what roman_grid_gate_aabb_dev is to roman_grid_gate_dev.  The arguments are roman_session_gate_dev's; then
  *   box        float64[S][6] over ALL submaps of the session, as roman_session_boxes_dev wrote them.  NEARBY is the six comparisons

@@ -336,6 +336,19 @@ ROMAN_INTEGRATE_LDS_MAX = 4096      # ... up to which a workgroup sorts the job 
 INTEGRATE_PARAMS_NBYTES = C.sizeof(RomanIntegrateParams)
 INTEGRATE_JOB_DTYPE = [("base", "<i4"), ("add", "<i4"), ("pose", "<i4")]      # roman_integrate_job_t as a structured dtype
 
+
+class RomanClusterParams(C.Structure):
+    """roman_cluster_params_t"""
+    _fields_ = [("eps", C.c_double), ("min_points", C.c_int32)]
+
+
+ROMAN_CLUSTER_MIN_POINTS = 10       # final_cleanup's default min_points [REF roman/object/segment.py:195]
+ROMAN_CLUSTER_WAVE_MAX = 256        # points up to which one wave takes a job (kernels.hip.h CLUS_WAVE_MAX)
+ROMAN_CLUSTER_LDS_MAX = 1536        # ... up to which a workgroup holds the job in LDS (kernels.hip.h CLUS_LDS_CAP)
+ROMAN_CLUSTER_TILE = 256            # query points of one workgroup of the tiled class (kernels.hip.h CLUS_TILE)
+ROMAN_CLUSTER_COLS = 1024           # column points the tiled class stages at a time (kernels.hip.h CLUS_COLS)
+CLUSTER_PARAMS_NBYTES = C.sizeof(RomanClusterParams)
+
 # flag bits of roman_grid_gate's flags[]
 ROMAN_GRID_NEARBY = 1
 ROMAN_GRID_SKIP = 2
@@ -481,6 +494,9 @@ def load_library():
         "roman_segment_integrate_dev": (C.c_int, [ctxp, P(RomanIntegrateParams), vp, vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
         "roman_segment_integrate": (C.c_int, [ctxp, P(RomanIntegrateParams), vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
         "roman_ctx_set_integrate_cuts": (C.c_int, [ctxp, i32, i32]),
+        "roman_segment_cluster_dev": (C.c_int, [ctxp, P(RomanClusterParams), vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "roman_segment_cluster": (C.c_int, [ctxp, P(RomanClusterParams), vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "roman_ctx_set_cluster_cuts": (C.c_int, [ctxp, i32, i32]),
         "roman_ctx_has_history": (C.c_int, [ctxp, P(RomanParams), i32, P(i32)]),
         "roman_ctx_cosine_screen_stats": (C.c_int, [ctxp, P(C.c_int64), P(C.c_int64), P(C.c_double)]),
         "roman_create_all_to_all": (C.c_int, [i32, i32, vp]),
@@ -515,7 +531,7 @@ def load_library():
 EXPORTED_SYMBOLS = (
     "roman_params_default", "roman_ctx_create", "roman_ctx_destroy", "roman_ctx_set_pipeline", "roman_ctx_sync", "roman_ctx_set_host_batching", "roman_ctx_set_wide_teams", "roman_ctx_join", "roman_ctx_join_on",
     "roman_ctx_skipped", "roman_last_error",
-    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_shared_reduce_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_mno_lc_tail_dev", "roman_mno_lc_batch_dev", "roman_mno_lc_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ransac_lc_batch_dev", "roman_ransac_lc_batch", "roman_submaps_dev", "roman_submaps", "roman_session_submaps_dev", "roman_session_submaps", "roman_session_submaps_list_dev", "roman_session_submaps_list", "roman_grid_gate_dev", "roman_grid_gate", "roman_grid_gate_sim_dev", "roman_grid_gate_sim", "roman_submaps_fill_dev", "roman_submaps_fill", "roman_submap_boxes_dev", "roman_submap_boxes", "roman_grid_gate_aabb_dev", "roman_grid_gate_aabb", "roman_session_gate_dev", "roman_session_gate", "roman_session_gate_sim_dev", "roman_session_gate_sim", "roman_session_stacked_sim_dev", "roman_session_stacked_sim", "roman_session_stacked_sim_list_dev", "roman_session_stacked_sim_list", "roman_session_boxes_dev", "roman_session_boxes", "roman_session_gate_aabb_dev", "roman_session_gate_aabb", "roman_session_gate_list_dev", "roman_session_gate_list", "roman_frame_select_dev", "roman_frame_select", "roman_session_frame_select_list_dev", "roman_session_frame_select_list", "roman_stacked_sim_dev", "roman_stacked_sim", "roman_ctx_set_stacked_band", "roman_segment_shapes_dev", "roman_segment_shapes", "roman_ctx_set_segment_block_min", "roman_assoc_scores_dev", "roman_assoc_scores", "roman_ctx_set_assoc_cuts", "roman_segment_integrate_dev", "roman_segment_integrate", "roman_ctx_set_integrate_cuts", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
+    "roman_align_batch_dev", "roman_align_batch", "roman_align_batch_resident", "roman_lc_tail_dev", "roman_align_lc_batch_dev", "roman_align_lc_batch", "roman_shared_ids_dev", "roman_shared_reduce_dev", "roman_align_lc_batch_ids", "roman_mno_batch_dev", "roman_mno_batch", "roman_mno_lc_tail_dev", "roman_mno_lc_batch_dev", "roman_mno_lc_batch", "roman_ransac_batch_dev", "roman_ransac_batch", "roman_ransac_lc_batch_dev", "roman_ransac_lc_batch", "roman_submaps_dev", "roman_submaps", "roman_session_submaps_dev", "roman_session_submaps", "roman_session_submaps_list_dev", "roman_session_submaps_list", "roman_grid_gate_dev", "roman_grid_gate", "roman_grid_gate_sim_dev", "roman_grid_gate_sim", "roman_submaps_fill_dev", "roman_submaps_fill", "roman_submap_boxes_dev", "roman_submap_boxes", "roman_grid_gate_aabb_dev", "roman_grid_gate_aabb", "roman_session_gate_dev", "roman_session_gate", "roman_session_gate_sim_dev", "roman_session_gate_sim", "roman_session_stacked_sim_dev", "roman_session_stacked_sim", "roman_session_stacked_sim_list_dev", "roman_session_stacked_sim_list", "roman_session_boxes_dev", "roman_session_boxes", "roman_session_gate_aabb_dev", "roman_session_gate_aabb", "roman_session_gate_list_dev", "roman_session_gate_list", "roman_frame_select_dev", "roman_frame_select", "roman_session_frame_select_list_dev", "roman_session_frame_select_list", "roman_stacked_sim_dev", "roman_stacked_sim", "roman_ctx_set_stacked_band", "roman_segment_shapes_dev", "roman_segment_shapes", "roman_ctx_set_segment_block_min", "roman_assoc_scores_dev", "roman_assoc_scores", "roman_ctx_set_assoc_cuts", "roman_segment_integrate_dev", "roman_segment_integrate", "roman_ctx_set_integrate_cuts", "roman_segment_cluster_dev", "roman_segment_cluster", "roman_ctx_set_cluster_cuts", "roman_ctx_has_history", "roman_ctx_cosine_screen_stats", "roman_deal_problems", "roman_create_all_to_all", "roman_score",
     "roman_set_matrix_data", "roman_solve", "roman_num_associations", "roman_num_selected",
     "roman_get_selected_associations", "roman_get_solution", "roman_get_dense_matrices",
     "roman_get_upper_csr", "roman_pose_batch", "roman_profile_enable", "roman_profile_reset",

@@ -9824,4 +9824,299 @@ __global__ void __launch_bounds__(256) k_integ_finish_block(IntegArgs A, int fir
     integ_finish<4>(A, (int)A.items[first + (int)blockIdx.x], cnt, (int)threadIdx.x);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Segment clustering: what Segment.final_cleanup does to a segment's cloud when the segment goes inactive
+// [REF roman/object/segment.py:195-220] — open3d's cluster_dbscan(eps, min_points), keep the largest cluster — for a list of jobs.
+// Every array of a job lives in the job's SLOT, n points from the host's prefix sum on, in every workspace.
+//   count   every point's number of neighbours (d2 < eps^2, itself included) over SoA columns in LDS that every lane reads at the
+//           same address -> the core flags; parent[i] = i
+//   union   every (core, core) neighbour pair i > j is united in a union-find over int32 parent[]: the larger root is hooked under
+//           the smaller by an integer atomicMin, retried from the value it returns.  parent[i] <= i always and parents only
+//           decrease, so the root of a component is its smallest core index whatever the order of the hooks: the partition and the
+//           roots do not depend on the schedule
+//   border  every non-core point's smallest root among its core neighbours (-1: noise), written where its parent stood
+//   finish  rank of every root among the roots (ballot + scan) = the cluster label; labels; sizes by an integer histogram; the
+//           largest cluster, the lowest label among equals; a ballot compaction of its points in input order
+// A job of at most CLUS_WAVE_MAX points is one wave's (four jobs per workgroup), of at most CLUS_LDS_MAX one workgroup's — both
+// hold the cloud, parent, flags and histogram in LDS and run all four steps in one kernel — a larger one runs count, union and
+// border over (job, query tile) workgroups through global memory (k_clus_tile<0 / 1 / 2>) and finish in one workgroup.  Every
+// loop that follows parents or retries a hook counts down from the index it starts at.  Integer atomics only: all classes and
+// any two calls give the same bytes.
+// ---------------------------------------------------------------------------------------------------------------------------
+constexpr int CLUS_WAVE_MAX = 256;           // ROMAN_CLUSTER_WAVE_MAX: a job of at most so many points is one wave's; also the wave's LDS capacity
+constexpr int CLUS_LDS_CAP = 1536;           // points a workgroup holds in LDS: 36 B each (three f64 columns, parent, flag, histogram) = 54 KB,
+                                             // two workgroups resident in a CU's 160 KB
+constexpr int CLUS_LDS_MAX = CLUS_LDS_CAP;   // ROMAN_CLUSTER_LDS_MAX: ... of at most so many is one workgroup's, resident in LDS
+constexpr int CLUS_TILE = 256;               // ROMAN_CLUSTER_TILE: query points of one workgroup of k_clus_tile
+constexpr int CLUS_COLS = 1024;              // ROMAN_CLUSTER_COLS: column points k_clus_tile stages in LDS at a time
+
+struct ClusArgs {
+    const double* pts; const int64_t* off;   // the clouds
+    const int32_t* jobs;                     // [n_jobs]: the cloud of every job
+    const int64_t* slot;                     // [n_jobs + 1]: the exclusive prefix sum of the jobs' point counts, from the host
+    const int64_t* items;                    // the host-cut lists: jobs by class; (job << 32 | query tile) for k_clus_tile
+    int32_t* par; int32_t* aux; int32_t* hist;   // [total] each, the tiled class's: parent / border root, core flag / root rank, cluster sizes
+    int32_t* lab;                            // [total]: out_labels, or workspace
+    double* out_points; int32_t* out_count; int32_t* out_status; int32_t* out_n_clusters; int32_t* out_kept;
+    double eps2; int min_points;
+};
+
+template <int CAP> struct ClusLds {
+    double x[CAP], y[CAP], z[CAP];
+    int32_t par[CAP], aux[CAP], hist[CAP];
+    unsigned long long red[4];
+    int cnt[4];
+};
+
+struct ClusCols { double x[CLUS_COLS], y[CLUS_COLS], z[CLUS_COLS]; int32_t tag[CLUS_COLS]; };
+
+// a word other threads (of other workgroups, in the tiled class) may have written with an atomic: read at the device's coherence point
+__device__ __forceinline__ int clus_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// j is a neighbour of i iff (dx dx + dy dy) + dz dz < eps^2, strictly and without contraction: symmetric bit for bit
+__device__ __forceinline__ bool clus_near(double qx, double qy, double qz, double cx, double cy, double cz, double eps2)
+{
+#pragma clang fp contract(off)
+    const double dx = qx - cx, dy = qy - cy, dz = qz - cz;
+    return (dx * dx + dy * dy) + dz * dz < eps2;
+}
+
+// the root above x.  parent[i] <= i and a walk only descends: at most x steps, and the countdown holds whatever the memory says
+__device__ __forceinline__ int clus_find(const int32_t* par, int x)
+{
+    for (int g = x; g > 0; --g) {
+        const int p = clus_ld(par + x);
+        if (p >= x || p < 0) break;
+        x = p;
+    }
+    return x;
+}
+
+// Unites the components of a and b: the larger root goes under the smaller.  atomicMin returns what stood there: the root itself
+// (hooked, done) or a smaller parent that another thread put there in between — then that parent is united with b, which also
+// mends the link the minimum may just have replaced.  The larger of the two roots strictly decreases from one trip to the
+// next, so max(a, b) trips suffice.
+__device__ __forceinline__ void clus_unite(int32_t* par, int a, int b)
+{
+    for (int g = a > b ? a : b; g >= 0; --g) {
+        a = clus_find(par, a); b = clus_find(par, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(par + a, b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// The last step of a job of n > 0 finite points, for a team of NW waves: par[i] is a parent (core points), the smallest root among
+// the core neighbours or -1 (the others); aux[i] != 0 marks the core points; hist[0, n) is 0.  par / aux / hist in LDS, or (GLOBAL) in global memory:
+// then every barrier stands behind a device-scope fence, so that what a thread stored is what the others load.
+template <int NW, bool GLOBAL>
+__device__ __forceinline__ void clus_finish(const ClusArgs& A, int j, int n, const double* __restrict__ P, int64_t s0,
+                                            int32_t* par, int32_t* aux, int32_t* hist, int* cnt, unsigned long long* red, int tid)
+{
+    constexpr int NT = 64 * NW;
+    int32_t* lab = A.lab + s0;
+    // the rank of every root among the roots, ascending index: the label of its cluster.  It replaces the root's flag
+    int nc = 0;
+    for (int c0 = 0; c0 < n; c0 += NT) {
+        const int i = c0 + tid;
+        const bool root = i < n && aux[i] != 0 && clus_ld(par + i) == i;
+        int total;
+        const int before = integ_rank<NW>(root, cnt, tid, total);
+        if (root) aux[i] = nc + before;
+        nc += total;
+    }
+    if (GLOBAL) __threadfence();
+    seg_sync<NW>();
+    for (int c0 = 0; c0 < n; c0 += NT) {
+        const int i = c0 + tid;
+        if (i < n) {
+            int r = clus_ld(par + i);
+            if (r >= 0) r = clus_find(par, r);
+            const int l = r < 0 ? -1 : clus_ld(aux + r);
+            lab[i] = l;
+            if (l >= 0) atomicAdd(hist + l, 1);
+        }
+    }
+    if (GLOBAL) __threadfence();
+    seg_sync<NW>();
+    // the largest cluster, the lowest label among equals: the maximum of (size, ~label)
+    unsigned long long best = 0ull;
+    for (int k = tid; k < nc; k += NT) {
+        const unsigned long long key = ((unsigned long long)(unsigned int)clus_ld(hist + k) << 32) | (unsigned long long)(unsigned int)(0x7fffffff - k);
+        best = key > best ? key : best;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned int hi = (unsigned int)__shfl_xor((int)(best >> 32), off), lo = (unsigned int)__shfl_xor((int)(best & 0xffffffffull), off);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        best = o > best ? o : best;
+    }
+    if (NW > 1) {
+        if ((tid & 63) == 0) red[tid >> 6] = best;
+        __syncthreads();
+        for (int w = 0; w < NW; ++w) best = red[w] > best ? red[w] : best;
+        __syncthreads();
+    }
+    const int kept = nc > 0 ? 0x7fffffff - (int)(unsigned int)(best & 0xffffffffull) : -1;
+    double* __restrict__ O = A.out_points + 3 * s0;
+    int base = 0;
+    for (int c0 = 0; c0 < n; c0 += NT) {
+        const int i = c0 + tid;
+        const bool keep = i < n && kept >= 0 && lab[i] == kept;          // lab[i]: this thread's own store
+        int total;
+        const int before = integ_rank<NW>(keep, cnt, tid, total);
+        if (keep) { double* o = O + 3 * (int64_t)(base + before); o[0] = P[3 * i]; o[1] = P[3 * i + 1]; o[2] = P[3 * i + 2]; }
+        base += total;
+    }
+    if (tid == 0) { A.out_count[j] = base; A.out_status[j] = ASSOC_ST_OK; A.out_n_clusters[j] = nc; if (A.out_kept) A.out_kept[j] = kept; }
+}
+
+// what a job without a cluster step leaves: no point (EMPTY) or a coordinate that is not finite (RANGE); labels untouched
+__device__ __forceinline__ void clus_refuse(const ClusArgs& A, int j, int status)
+{
+    A.out_count[j] = 0; A.out_status[j] = status; A.out_n_clusters[j] = 0;
+    if (A.out_kept) A.out_kept[j] = -1;
+}
+
+// a whole job of n <= CAP points by one team, resident in LDS
+template <int NW, int CAP>
+__device__ __forceinline__ void clus_team(const ClusArgs& A, int j, ClusLds<CAP>& L, int tid)
+{
+    constexpr int NT = 64 * NW;
+    const int c = A.jobs[j];
+    const int64_t p0 = A.off[c], s0 = A.slot[j];
+    const int n = (int)(A.off[c + 1] - p0);
+    const double* __restrict__ P = A.pts + 3 * p0;
+    int bad = n > CAP;                       // the host cuts the classes: never
+    for (int i = tid; i < n && i < CAP; i += NT) {
+        const double x = P[3 * i], y = P[3 * i + 1], z = P[3 * i + 2];
+        L.x[i] = x; L.y[i] = y; L.z[i] = z; L.par[i] = i; L.hist[i] = 0;
+        bad |= (int)!(fabs(x) < INFINITY) | (int)!(fabs(y) < INFINITY) | (int)!(fabs(z) < INFINITY);
+    }
+    bad = NW == 1 ? __any(bad) : __syncthreads_or(bad);
+    seg_sync<NW>();
+    if (n == 0 || bad) {
+        if (tid == 0) clus_refuse(A, j, n == 0 ? ASSOC_ST_EMPTY : ASSOC_ST_RANGE);
+        return;
+    }
+    // count -> core flags
+    for (int q0 = 0; q0 < n; q0 += NT) {
+        const int q = q0 + tid < n ? q0 + tid : n - 1;
+        const double qx = L.x[q], qy = L.y[q], qz = L.z[q];
+        int cnt = 0;
+        for (int e = 0; e < n; ++e) cnt += clus_near(qx, qy, qz, L.x[e], L.y[e], L.z[e], A.eps2) ? 1 : 0;
+        if (q0 + tid < n) L.aux[q] = cnt >= A.min_points ? 1 : 0;
+    }
+    seg_sync<NW>();
+    // union over the pairs i > j of core points; the columns end at the wave's last query
+    for (int q0 = 0; q0 < n; q0 += NT) {
+        const int q = q0 + tid < n ? q0 + tid : n - 1;
+        const bool core = q0 + tid < n && L.aux[q] != 0;
+        const double qx = L.x[q], qy = L.y[q], qz = L.z[q];
+        const int last = q0 + (tid | 63), top = last < n ? last : n;
+        for (int e = 0; e < top; ++e)
+            if (core && e < q && L.aux[e] != 0 && clus_near(qx, qy, qz, L.x[e], L.y[e], L.z[e], A.eps2)) clus_unite(L.par, q, e);
+    }
+    seg_sync<NW>();
+    // parents -> roots (a concurrent walk meets a parent or a root: both lie above it)
+    for (int i = tid; i < n; i += NT) if (L.aux[i] != 0) L.par[i] = clus_find(L.par, i);
+    seg_sync<NW>();
+    // border points: the smallest root among the core neighbours, where the parent stood (no walk reads a non-core point's)
+    for (int q0 = 0; q0 < n; q0 += NT) {
+        const int q = q0 + tid < n ? q0 + tid : n - 1;
+        const bool border = q0 + tid < n && L.aux[q] == 0;
+        const double qx = L.x[q], qy = L.y[q], qz = L.z[q];
+        int low = 0x7fffffff;
+        for (int e = 0; e < n; ++e)
+            if (border && L.aux[e] != 0 && clus_near(qx, qy, qz, L.x[e], L.y[e], L.z[e], A.eps2)) { const int r = L.par[e]; low = r < low ? r : low; }
+        if (border) L.par[q] = low == 0x7fffffff ? -1 : low;
+    }
+    seg_sync<NW>();
+    clus_finish<NW, false>(A, j, n, P, s0, L.par, L.aux, L.hist, L.cnt, L.red, tid);
+}
+
+// one wave per listed job, four to a workgroup; the waves never meet at a workgroup barrier
+__global__ void __launch_bounds__(256) k_clus_wave(ClusArgs A, int n_items)
+{
+    __shared__ ClusLds<CLUS_WAVE_MAX> L[4];
+    const int wave = (int)threadIdx.x >> 6, it = (int)blockIdx.x * 4 + wave;
+    if (it >= n_items) return;
+    clus_team<1, CLUS_WAVE_MAX>(A, (int)A.items[it], L[wave], (int)threadIdx.x & 63);
+}
+
+// one workgroup per listed job, from item `first` on
+__global__ void __launch_bounds__(256) k_clus_block(ClusArgs A, int first)
+{
+    __shared__ ClusLds<CLUS_LDS_CAP> L;
+    clus_team<4, CLUS_LDS_CAP>(A, (int)A.items[first + (int)blockIdx.x], L, (int)threadIdx.x);
+}
+
+// One workgroup per listed (job, query tile) of the tiled class; a tile past the job's n ends at once.  STAGE 0: count, 1: union,
+// 2: border.  The columns go through LDS CLUS_COLS at a time, with their core flags (1) or roots (2; -1: not a core point).
+template <int STAGE>
+__global__ void __launch_bounds__(256) k_clus_tile(ClusArgs A, int first)
+{
+    __shared__ ClusCols C;
+    const int tid = (int)threadIdx.x;
+    const int64_t it = A.items[first + (int64_t)blockIdx.x];
+    const int j = (int)(it >> 32), q0 = (int)(it & 0xffffffffll) * CLUS_TILE;
+    const int c = A.jobs[j];
+    const int64_t p0 = A.off[c], s0 = A.slot[j];
+    const int n = (int)(A.off[c + 1] - p0);
+    if (q0 >= n) return;
+    const double* __restrict__ P = A.pts + 3 * p0;
+    int32_t* par = A.par + s0; int32_t* aux = A.aux + s0;
+    const bool valid = q0 + tid < n;
+    const int q = valid ? q0 + tid : n - 1;
+    const double qx = P[3 * q], qy = P[3 * q + 1], qz = P[3 * q + 2];
+    const bool core = STAGE != 0 && aux[q] != 0;
+    const bool active = valid && (STAGE == 0 || (STAGE == 1) == core);
+    if (STAGE != 0 && !__syncthreads_or((int)active)) return;
+    const int ncol = STAGE == 1 ? (q0 + CLUS_TILE < n ? q0 + CLUS_TILE : n) : n;     // the union visits the pairs i > j alone
+    int acc = STAGE == 2 ? 0x7fffffff : 0;
+    for (int c0 = 0; c0 < ncol; c0 += CLUS_COLS) {
+        const int len = ncol - c0 < CLUS_COLS ? ncol - c0 : CLUS_COLS;
+        for (int e = tid; e < len; e += 256) {
+            C.x[e] = P[3 * (c0 + e)]; C.y[e] = P[3 * (c0 + e) + 1]; C.z[e] = P[3 * (c0 + e) + 2];
+            if (STAGE == 1) C.tag[e] = aux[c0 + e];
+            if (STAGE == 2) C.tag[e] = aux[c0 + e] != 0 ? clus_find(par, c0 + e) : -1;
+        }
+        __syncthreads();
+        if (STAGE == 0) {
+            for (int e = 0; e < len; ++e) acc += clus_near(qx, qy, qz, C.x[e], C.y[e], C.z[e], A.eps2) ? 1 : 0;
+        } else if (STAGE == 1) {
+            const int last = q0 + (tid | 63) - c0, top = last < len ? last : len;
+            for (int e = 0; e < top; ++e)
+                if (active && c0 + e < q && C.tag[e] != 0 && clus_near(qx, qy, qz, C.x[e], C.y[e], C.z[e], A.eps2)) clus_unite(par, q, c0 + e);
+        } else {
+            for (int e = 0; e < len; ++e)
+                if (active && C.tag[e] >= 0 && clus_near(qx, qy, qz, C.x[e], C.y[e], C.z[e], A.eps2)) acc = C.tag[e] < acc ? C.tag[e] : acc;
+        }
+        __syncthreads();
+    }
+    if (STAGE == 0 && valid) { aux[q] = acc >= A.min_points ? 1 : 0; par[q] = q; A.hist[s0 + q] = 0; }
+    if (STAGE == 2 && active) par[q] = acc == 0x7fffffff ? -1 : acc;     // no walk reads a non-core point's parent
+}
+
+// one workgroup per listed job of the tiled class: the finiteness of its coordinates, then clus_finish over the global arrays
+__global__ void __launch_bounds__(256) k_clus_finish_block(ClusArgs A, int first)
+{
+    __shared__ int cnt[4];
+    __shared__ unsigned long long red[4];
+    const int tid = (int)threadIdx.x, j = (int)A.items[first + (int)blockIdx.x];
+    const int c = A.jobs[j];
+    const int64_t p0 = A.off[c], s0 = A.slot[j];
+    const int n = (int)(A.off[c + 1] - p0);
+    const double* __restrict__ P = A.pts + 3 * p0;
+    int bad = 0;
+    for (int i = tid; i < n; i += 256) bad |= (int)!(fabs(P[3 * i]) < INFINITY) | (int)!(fabs(P[3 * i + 1]) < INFINITY) | (int)!(fabs(P[3 * i + 2]) < INFINITY);
+    bad = __syncthreads_or(bad);
+    if (n == 0 || bad) {
+        if (tid == 0) clus_refuse(A, j, n == 0 ? ASSOC_ST_EMPTY : ASSOC_ST_RANGE);
+        return;
+    }
+    clus_finish<4, true>(A, j, n, P, s0, A.par + s0, A.aux + s0, A.hist + s0, cnt, red, tid);
+}
+
 }  // namespace roman

@@ -217,6 +217,12 @@ struct roman_ctx {
     DevBuf sgPts, sgDs, sgKeys, sgKeys2, sgIdx, sgIdx2, sgAvg, sgM, sgItems;
     PinnedStage<int64_t> sgStage;
     int integ_wave_max = INTEG_WAVE_MAX, integ_lds_max = INTEG_LDS_MAX;   // the two class cuts (roman_ctx_set_integrate_cuts)
+    // segment clustering (roman_segment_cluster*): one slot of n points per job in every workspace — parent, flag and histogram
+    // words of the tiled class, the labels when the caller takes none — and the host-cut tables (slot offsets, job lists, query
+    // tiles) through pinned staging
+    DevBuf clPar, clAux, clHist, clLab, clItems;
+    PinnedStage<int64_t> clStage;
+    int clus_wave_max = CLUS_WAVE_MAX, clus_lds_max = CLUS_LDS_MAX;       // the two class cuts (roman_ctx_set_cluster_cuts)
 
     std::vector<std::pair<const void*, int>> ldsAttr;   // dynamic-LDS limits already set (per kernel function)
 
@@ -1476,6 +1482,7 @@ int roman_ctx_destroy(roman_ctx_t* c)
     c->asKeys.release(); c->asScratch.release(); c->asRec.release(); c->asNorm.release(); c->asItems.release(); c->asStage.release();
     c->sgPts.release(); c->sgDs.release(); c->sgKeys.release(); c->sgKeys2.release(); c->sgIdx.release(); c->sgIdx2.release();
     c->sgAvg.release(); c->sgM.release(); c->sgItems.release(); c->sgStage.release();
+    c->clPar.release(); c->clAux.release(); c->clHist.release(); c->clLab.release(); c->clItems.release(); c->clStage.release();
     if (c->evIn) (void)hipEventDestroy(c->evIn);
     if (c->coopDone) (void)hipEventDestroy(c->coopDone);
     for (int k = 0; k < ROMAN_MAX_PIPELINE; ++k) if (c->istream[k]) (void)hipStreamDestroy(c->istream[k]);
@@ -3641,6 +3648,130 @@ int roman_ctx_set_integrate_cuts(roman_ctx_t* c, int32_t wave_max, int32_t lds_m
     if (wave_max < 0 || lds_max < 0 || l > INTEG_LDS_CAP || l < 2 || w > l)
         return fail(c, ROMAN_E_INVALID, "wave_max = %d, lds_max = %d: 0 <= wave_max <= lds_max, 2 <= lds_max <= %d (0: the default)", wave_max, lds_max, INTEG_LDS_CAP);
     c->integ_wave_max = w; c->integ_lds_max = l;
+    return ROMAN_OK;
+}
+
+// --- segment clustering: final_cleanup's DBSCAN and "keep the largest cluster" for a list of jobs ---------------
+static_assert(CLUS_WAVE_MAX == ROMAN_CLUSTER_WAVE_MAX && CLUS_LDS_MAX == ROMAN_CLUSTER_LDS_MAX && CLUS_TILE == ROMAN_CLUSTER_TILE && CLUS_COLS == ROMAN_CLUSTER_COLS,
+              "kernels.hip.h and roman_hip.h name the same numbers");
+static_assert(sizeof(roman_cluster_params_t) == 16, "roman_cluster_params_t: a double and an int32 word");
+constexpr int64_t CLUS_CALL_MAX = 1ll << 28;    // points of one call: the kernels index 3 * point in 32 bits inside a job, the slots in 64
+
+// Everything roman_segment_cluster* judge on host memory -> *total: the points of all slots.  The argument checks come first and
+// the context last, so that each of them answers without a device.
+static int cluster_check(roman_ctx* c, const roman_cluster_params_t* P, const void* points, const int64_t* cloud_off, int32_t n_clouds,
+                         const int32_t* jobs, int32_t n_jobs, const void* out_points, const void* out_count, const void* out_status,
+                         const void* out_n_clusters, int64_t* total)
+{
+    if (!P) return fail(c, ROMAN_E_INVALID, "params is NULL");
+    if (!(P->eps > 0.0) || !std::isfinite(P->eps)) return fail(c, ROMAN_E_INVALID, "eps must be finite and > 0 (got %g)", P->eps);
+    if (P->min_points < 1) return fail(c, ROMAN_E_INVALID, "min_points must be >= 1 (got %d)", P->min_points);
+    if (n_clouds < 0 || n_jobs < 0) return fail(c, ROMAN_E_INVALID, "n_clouds = %d, n_jobs = %d: none may be negative", n_clouds, n_jobs);
+    if (!cloud_off) return fail(c, ROMAN_E_INVALID, "cloud_off is NULL");
+    { const int rc = cloud_offsets_check(c, cloud_off, n_clouds, "cloud_off", "cloud"); if (rc) return rc; }
+    if (n_jobs > 0 && !jobs) return fail(c, ROMAN_E_INVALID, "jobs is NULL");
+    std::vector<char> named((size_t)n_clouds, 0);
+    *total = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) {
+        if (jobs[j] < 0 || jobs[j] >= n_clouds) return fail(c, ROMAN_E_INVALID, "job %d: %d is not one of the %d clouds", j, jobs[j], n_clouds);
+        if (named[(size_t)jobs[j]]) return fail(c, ROMAN_E_INVALID, "job %d: cloud %d is named by an earlier job", j, jobs[j]);
+        named[(size_t)jobs[j]] = 1;
+        *total += cloud_off[jobs[j] + 1] - cloud_off[jobs[j]];
+    }
+    if (*total > CLUS_CALL_MAX) return fail(c, ROMAN_E_TOO_LARGE, "the jobs hold more than 2^28 points");
+    if (cloud_off[n_clouds] > 0 && !points) return fail(c, ROMAN_E_INVALID, "points is NULL");
+    if (n_jobs > 0 && (!out_count || !out_status || !out_n_clusters || (*total > 0 && !out_points)))
+        return fail(c, ROMAN_E_INVALID, "out_points / out_count / out_status / out_n_clusters is NULL");
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    return ROMAN_OK;
+}
+
+int roman_segment_cluster_dev(roman_ctx_t* c, const roman_cluster_params_t* params, const double* points, const int64_t* cloud_off_dev,
+                              const int64_t* cloud_off_host, int32_t n_clouds, const int32_t* jobs_dev, const int32_t* jobs_host, int32_t n_jobs,
+                              double* out_points, int32_t* out_count, int32_t* out_status, int32_t* out_labels, int32_t* out_n_clusters, int32_t* out_kept)
+{
+    int64_t total = 0;
+    int rc = cluster_check(c, params, points, cloud_off_host, n_clouds, jobs_host, n_jobs, out_points, out_count, out_status, out_n_clusters, &total);
+    if (rc || n_jobs == 0) return rc;
+    if (!cloud_off_dev) return fail(c, ROMAN_E_INVALID, "cloud_off is NULL on the device");
+    if (!jobs_dev) return fail(c, ROMAN_E_INVALID, "jobs is NULL on the device");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t cutW = c->clus_wave_max, cutL = c->clus_lds_max;
+    auto size_of = [&](int32_t j) { return cloud_off_host[jobs_host[j] + 1] - cloud_off_host[jobs_host[j]]; };
+    // ---- the tables, cut on the host: slot offsets | the jobs of one wave, of a workgroup in LDS, of the tiled class | its query tiles ----
+    size_t n_tiles = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) if (size_of(j) > cutL) n_tiles += (size_t)((size_of(j) + CLUS_TILE - 1) / CLUS_TILE);
+    const size_t oItems = (size_t)n_jobs + 1, oTiles = oItems + (size_t)n_jobs, n_tab = oTiles + n_tiles;
+    int64_t* tab = nullptr;
+    HIPCHK(c, c->clStage.stage(n_tab, &tab));
+    tab[0] = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) tab[j + 1] = tab[j] + size_of(j);
+    int32_t nW = 0, nL = 0, nT = 0;
+    for (int32_t j = 0; j < n_jobs; ++j) if (size_of(j) <= cutW) tab[oItems + nW++] = j;
+    for (int32_t j = 0; j < n_jobs; ++j) if (size_of(j) > cutW && size_of(j) <= cutL) tab[oItems + nW + nL++] = j;
+    for (int32_t j = 0; j < n_jobs; ++j) if (size_of(j) > cutL) tab[oItems + nW + nL + nT++] = j;
+    size_t t = oTiles;
+    for (int32_t k = nW + nL; k < n_jobs; ++k) {
+        const int32_t j = (int32_t)tab[oItems + k];
+        for (int64_t q = 0; q * CLUS_TILE < size_of(j); ++q) tab[t++] = ((int64_t)j << 32) | q;
+    }
+    // ---- the workspace, from the host offsets alone ----
+    const size_t room = sizeof(int32_t) * (size_t)std::max<int64_t>(total, 1);
+    if (nT) { HIPCHK(c, c->clPar.ensure(room)); HIPCHK(c, c->clAux.ensure(room)); HIPCHK(c, c->clHist.ensure(room)); }
+    if (!out_labels) HIPCHK(c, c->clLab.ensure(room));
+    HIPCHK(c, c->clStage.upload(c->clItems, n_tab, c->stream));
+    const int64_t* dTab = c->clItems.as<int64_t>();
+    const ClusArgs A{points, cloud_off_dev, jobs_dev, dTab, dTab + oItems, c->clPar.as<int32_t>(), c->clAux.as<int32_t>(), c->clHist.as<int32_t>(),
+                     out_labels ? out_labels : c->clLab.as<int32_t>(), out_points, out_count, out_status, out_n_clusters, out_kept,
+                     params->eps * params->eps, (int)params->min_points};
+    if (nW) hipLaunchKernelGGL(k_clus_wave, dim3((unsigned)((nW + 3) / 4)), dim3(256), 0, c->stream, A, (int)nW);
+    if (nL) hipLaunchKernelGGL(k_clus_block, dim3((unsigned)nL), dim3(256), 0, c->stream, A, (int)nW);
+    if (nT) {
+        hipLaunchKernelGGL(k_clus_tile<0>, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, A, (int)n_jobs);
+        hipLaunchKernelGGL(k_clus_tile<1>, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, A, (int)n_jobs);
+        hipLaunchKernelGGL(k_clus_tile<2>, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, A, (int)n_jobs);
+        hipLaunchKernelGGL(k_clus_finish_block, dim3((unsigned)nT), dim3(256), 0, c->stream, A, (int)(nW + nL));
+    }
+    HIPCHK(c, hipGetLastError());
+    return ROMAN_OK;
+}
+
+int roman_segment_cluster(roman_ctx_t* c, const roman_cluster_params_t* params, const double* points, const int64_t* cloud_off, int32_t n_clouds,
+                          const int32_t* jobs, int32_t n_jobs, double* out_points, int32_t* out_count, int32_t* out_status,
+                          int32_t* out_labels, int32_t* out_n_clusters, int32_t* out_kept)
+{
+    int64_t total = 0;
+    int rc = cluster_check(c, params, points, cloud_off, n_clouds, jobs, n_jobs, out_points, out_count, out_status, out_n_clusters, &total);
+    if (rc || n_jobs == 0) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    { int rc0 = use_ws0(c); if (rc0) return rc0; }
+    HostMirror m(c);
+    const auto dPts = m.in(points, sizeof(double) * 3 * (size_t)cloud_off[n_clouds]);
+    const auto dOff = m.in(cloud_off, sizeof(int64_t) * ((size_t)n_clouds + 1));
+    const auto dJobs = m.in(jobs, sizeof(int32_t) * (size_t)n_jobs);
+    // what a job leaves untouched — its slot past out_count, the labels of a RANGE job — comes back as the caller had it
+    const auto dOut = m.inout(out_points, sizeof(double) * 3 * (size_t)total);
+    const auto dCnt = m.out(out_count, sizeof(int32_t) * (size_t)n_jobs);
+    const auto dSt = m.out(out_status, sizeof(int32_t) * (size_t)n_jobs);
+    const auto dLab = m.inout(out_labels, out_labels ? sizeof(int32_t) * (size_t)total : 0);
+    const auto dNc = m.out(out_n_clusters, sizeof(int32_t) * (size_t)n_jobs);
+    const auto dKept = m.out(out_kept, out_kept ? sizeof(int32_t) * (size_t)n_jobs : 0);
+    rc = m.upload();
+    if (rc) return rc;
+    rc = roman_segment_cluster_dev(c, params, dPts.dev(), dOff.dev(), cloud_off, n_clouds, dJobs.dev(), jobs, n_jobs,
+                                   dOut.dev() /* NULL when every slot is empty */, dCnt.dev(), dSt.dev(), dLab.dev(), dNc.dev(), dKept.dev());
+    if (rc) return rc;
+    return m.download();
+}
+
+int roman_ctx_set_cluster_cuts(roman_ctx_t* c, int32_t wave_max, int32_t lds_max)
+{
+    if (!c) return fail(nullptr, ROMAN_E_INVALID, "ctx is NULL");
+    const int w = wave_max ? wave_max : CLUS_WAVE_MAX, l = lds_max ? lds_max : CLUS_LDS_MAX;
+    if (wave_max < 0 || lds_max < 0 || w > CLUS_WAVE_MAX || l > CLUS_LDS_CAP || w > l)
+        return fail(c, ROMAN_E_INVALID, "wave_max = %d, lds_max = %d: 0 <= wave_max <= %d, wave_max <= lds_max <= %d (0: the default)",
+                    wave_max, lds_max, CLUS_WAVE_MAX, CLUS_LDS_CAP);
+    c->clus_wave_max = w; c->clus_lds_max = l;
     return ROMAN_OK;
 }
 

@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 
 from ..align.segment_clouds import SegmentClouds
-from ..runtime import integrate_jobs, integrate_params
+from ..runtime import cluster_params, integrate_jobs, integrate_params
 from .association import _clouds
 
 
@@ -143,3 +143,98 @@ def cleanup_points(points, params, ctx=None):
         ctx = default_context()
     out = ctx.segment_integrate(iparams, points, np.array([0, len(points)], dtype=np.int64), [(None, 0, None)])
     return out.cloud(0).copy()
+
+
+# ------------------------------------------------------------------------------------------------ segment clustering
+@dataclass
+class ClusterParams:
+    """What Mapper.update hands to Segment.final_cleanup [REF roman/map/mapper.py:101]: MapperParams.clustering_epsilon
+    [REF roman/params/mapper_params.py:68] and final_cleanup's own min_points [REF roman/object/segment.py:195]."""
+    clustering_epsilon: float = 0.25
+    min_points: int = 10
+
+    @classmethod
+    def from_mapper_params(cls, p, min_points=10):
+        """Reads the reference's field name off a MapperParams-like object."""
+        return cls(float(p.clustering_epsilon), int(min_points))
+
+    def abi(self):
+        """-> roman_cluster_params_t.  Everything the C ABI would refuse is a ValueError here, before any context exists."""
+        eps = float(self.clustering_epsilon)
+        if not (np.isfinite(eps) and eps > 0):
+            raise ValueError(f"clustering_epsilon must be finite and > 0 (got {eps})")
+        if int(self.min_points) != self.min_points or int(self.min_points) < 1:
+            raise ValueError(f"min_points must be an integer >= 1 (got {self.min_points})")
+        return cluster_params(eps, int(self.min_points))
+
+
+@dataclass
+class CleanupResult:
+    """clouds: the kept clusters in `which` order (a dropped segment holds no point); dropped: the subset of `which` without a
+    cluster or without points — the mapper's except branch and its num_points == 0 branch [REF roman/map/mapper.py:97-105];
+    status, n_clusters, kept (len(which),): what roman_segment_cluster wrote."""
+    clouds: SegmentClouds
+    dropped: np.ndarray
+    status: np.ndarray
+    n_clusters: np.ndarray
+    kept: np.ndarray
+
+
+def _subset(segments, which, points, off):
+    desc = None if segments.descriptors is None else np.ascontiguousarray(np.asarray(segments.descriptors)[which])
+    return SegmentClouds(points, off, np.asarray(segments.ids)[which].astype(np.int64), np.asarray(segments.times, dtype=np.float64).reshape(-1, 2)[which], desc)
+
+
+def final_cleanup(segments, which, params, ctx=None) -> CleanupResult:
+    """Segment.final_cleanup [REF roman/object/segment.py:195-220] for the segments `which` (indices into `segments`, each at most
+    once) in one device call.  -> CleanupResult; ids, times and descriptors are carried over unchanged."""
+    cparams = params.abi()
+    points, off, _ = _clouds(segments, "segments")
+    which = np.asarray(which, dtype=np.int64).reshape(-1)
+    n = len(off) - 1
+    if len(which) and (which.min() < 0 or which.max() >= n):
+        raise ValueError(f"which names a segment outside the {n} given")
+    if len(np.unique(which)) != len(which):
+        raise ValueError("which names a segment twice")
+    if len(which) == 0:
+        z = np.zeros(0, np.int32)
+        return CleanupResult(_subset(segments, which, np.zeros((0, 3)), np.zeros(1, np.int64)), np.zeros(0, np.int64), z, z.copy(), z.copy())
+    if ctx is None:
+        from ..runtime import default_context
+        ctx = default_context()
+    out = ctx.segment_cluster(cparams, points, off, which, want_labels=False)
+    kept_off = np.concatenate([[0], np.cumsum(out.count, dtype=np.int64)]).astype(np.int64)
+    cloud = np.ascontiguousarray(np.vstack([out.cloud(j) for j in range(len(which))]))
+    return CleanupResult(_subset(segments, which, cloud, kept_off), which[out.count == 0], out.status, out.n_clusters, out.kept)
+
+
+def cluster_labels(points, params, ctx=None):
+    """open3d's cluster_dbscan labels of one cloud (n,) int32, -1: noise — as roman_segment_cluster restates them."""
+    cparams = params.abi()
+    points = np.ascontiguousarray(points, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != 3:
+        raise ValueError(f"points must be (n, 3) (got {points.shape})")
+    if len(points) == 0:
+        return np.zeros(0, np.int32)
+    if ctx is None:
+        from ..runtime import default_context
+        ctx = default_context()
+    return ctx.segment_cluster(cparams, points, np.array([0, len(points)], dtype=np.int64), [0]).labels(0).copy()
+
+
+def retire(segments, t, last_seen, max_t_no_sightings, params, ctx=None):
+    """The mapper's move to inactive [REF roman/map/mapper.py:92-105]: the segments with t - last_seen > max_t_no_sightings, or
+    without points, leave `segments`; those with points go through final_cleanup.  last_seen (N,) or None for segments.times[:, 1].
+    -> (indices that stay active, the inactive SegmentClouds, the ids that were dropped — no points, or no cluster)."""
+    _, off, _ = _clouds(segments, "segments")
+    n = len(off) - 1
+    seen = np.asarray(segments.times, dtype=np.float64).reshape(-1, 2)[:, 1] if last_seen is None else np.asarray(last_seen, dtype=np.float64).reshape(-1)
+    if seen.shape[0] != n:
+        raise ValueError(f"last_seen must hold one time per segment ({n})")
+    empty = np.diff(off) == 0
+    leave = (float(t) - seen > float(max_t_no_sightings)) | empty
+    res = final_cleanup(segments, np.flatnonzero(leave & ~empty), params, ctx=ctx)
+    alive = np.diff(res.clouds.seg_off) > 0
+    inactive = _subset(res.clouds, np.flatnonzero(alive), res.clouds.points, np.concatenate([[0], np.cumsum(np.diff(res.clouds.seg_off)[alive])]).astype(np.int64))
+    dropped = np.concatenate([np.asarray(segments.ids)[np.flatnonzero(empty)], np.asarray(res.clouds.ids)[~alive]]).astype(np.int64)
+    return np.flatnonzero(~leave), inactive, dropped

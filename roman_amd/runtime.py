@@ -469,6 +469,43 @@ class IntegrateOutput:
         return self.points[self.slot[j]:self.slot[j] + self.count[j]]
 
 
+def cluster_params(eps=0.25, min_points=_abi.ROMAN_CLUSTER_MIN_POINTS):
+    """-> roman_cluster_params_t; the defaults are MapperParams' clustering_epsilon [REF roman/params/mapper_params.py:68] and
+    final_cleanup's min_points [REF roman/object/segment.py:195]."""
+    P = _abi.RomanClusterParams()
+    P.eps, P.min_points = float(eps), int(min_points)
+    return P
+
+
+def cluster_slots(cloud_off, jobs):
+    """The slot offsets of a clustering job list (n_jobs + 1,): the exclusive prefix sum of the jobs' point counts — where
+    roman_segment_cluster* puts every job's output."""
+    n = np.diff(np.asarray(cloud_off, dtype=np.int64))
+    size = [int(n[int(j)]) for j in np.asarray(jobs, dtype=np.int64).reshape(-1)]
+    return np.concatenate([[0], np.cumsum(size, dtype=np.int64)]).astype(np.int64)
+
+
+@dataclass
+class ClusterOutput:
+    """What roman_segment_cluster writes: points (total, 3) and label (total,) int32 by slot; count, status, n_clusters, kept
+    (n_jobs,) int32; slot (n_jobs + 1,).  label and kept are None when not asked for."""
+    points: np.ndarray
+    count: np.ndarray
+    status: np.ndarray
+    label: Optional[np.ndarray]
+    n_clusters: np.ndarray
+    kept: Optional[np.ndarray]
+    slot: np.ndarray
+
+    def cloud(self, j):
+        """Job j's kept cluster (count, 3), in input order."""
+        return self.points[self.slot[j]:self.slot[j] + self.count[j]]
+
+    def labels(self, j):
+        """open3d's label of every input point of job j (n,)."""
+        return self.label[self.slot[j]:self.slot[j + 1]]
+
+
 def session_frame_robot_dtype():
     """roman_session_frame_robot_t as a structured dtype."""
     return np.dtype([("seg0", np.int64), ("mask_off", np.int64), ("n_seg", np.int32), ("sub0", np.int32), ("n_sub", np.int32), ("frame0", np.int32),
@@ -1440,6 +1477,43 @@ class Context:
         """Measurement only (roman_ctx_set_integrate_cuts): the point counts (base + added) up to which a job is one wave's / is
         sorted by one workgroup in LDS; 0: the default.  Results do not depend on them."""
         self._check(self._lib.roman_ctx_set_integrate_cuts(self._h, int(wave_max), int(lds_max)), "roman_ctx_set_integrate_cuts")
+
+    # ------------------------------------------------------------------ segment clustering (DESIGN.md §4.27)
+    def segment_cluster(self, cparams, points, cloud_off, jobs, want_labels=True, want_kept=True, out_points=None, out_labels=None):
+        """Host-pointer segment clustering (roman_segment_cluster): points (P, 3), cloud_off (clouds + 1,), jobs the cloud index
+        of every job; cparams a cluster_params() block.  out_points (total, 3), out_labels (total,): arrays of the caller's, whose
+        untouched elements keep their values (fresh ones start at 0, the labels at -1).  -> ClusterOutput."""
+        points, cloud_off, clouds = _segment_clouds(points, cloud_off)
+        jobs = np.ascontiguousarray(np.asarray(jobs, dtype=np.int32).reshape(-1))
+        n_jobs = int(jobs.shape[0])
+        if n_jobs and (jobs.min() < 0 or jobs.max() >= clouds):
+            raise ValueError(f"a job names a cloud outside the {clouds} given")
+        slot = cluster_slots(cloud_off, jobs)
+        total = int(slot[-1])
+        out_points = _given(out_points, (total, 3), np.float64, 0.0)
+        count, status, n_clusters = (np.zeros(n_jobs, dtype=np.int32) for _ in range(3))
+        label = _given(out_labels, (total,), np.int32, -1) if (want_labels or out_labels is not None) else None
+        kept = np.full(n_jobs, -1, dtype=np.int32) if want_kept else None
+        self._generation += 1
+        rc = self._lib.roman_segment_cluster(self._h, C.byref(cparams), _ptr(points), _ptr(cloud_off), clouds, _ptr(jobs), n_jobs,
+                                             _ptr(out_points), _ptr(count), _ptr(status), _ptr(label), _ptr(n_clusters), _ptr(kept))
+        self._check(rc, "roman_segment_cluster")
+        return ClusterOutput(out_points, count, status, label, n_clusters, kept, slot)
+
+    def segment_cluster_dev(self, cparams, points_ptr, cloud_off_ptr, cloud_off, jobs_ptr, jobs, out_points_ptr, out_count_ptr, out_status_ptr,
+                            out_n_clusters_ptr, out_labels_ptr=None, out_kept_ptr=None):
+        """Device-pointer form (roman_segment_cluster_dev): every array on the device; `cloud_off` and `jobs` are the same numbers
+        on the host — the slots, the launches and the workspace are sized from them.  A pure enqueue on the context's stream."""
+        cloud_off = np.ascontiguousarray(cloud_off, dtype=np.int64).reshape(-1)
+        jobs = np.ascontiguousarray(np.asarray(jobs, dtype=np.int32).reshape(-1))
+        self._enqueue("roman_segment_cluster_dev", C.byref(cparams), _vp(points_ptr), _vp(cloud_off_ptr), _ptr(cloud_off), int(cloud_off.shape[0]) - 1,
+                      _vp(jobs_ptr), _ptr(jobs), int(jobs.shape[0]), _vp(out_points_ptr), _vp(out_count_ptr), _vp(out_status_ptr),
+                      _vp(out_labels_ptr), _vp(out_n_clusters_ptr), _vp(out_kept_ptr))
+
+    def set_cluster_cuts(self, wave_max=0, lds_max=0):
+        """Measurement and tests only (roman_ctx_set_cluster_cuts): the point counts up to which a job is one wave's / is held in
+        LDS by one workgroup; 0: the default.  Results do not depend on them."""
+        self._check(self._lib.roman_ctx_set_cluster_cuts(self._h, int(wave_max), int(lds_max)), "roman_ctx_set_cluster_cuts")
 
     def grid_gate_aabb(self, gparams, box0, box1, pos0, T_w0, pos1, T_w1, time0=None, time1=None, desc0=None, desc1=None, pos_gt0=None, pos_gt1=None,
                        sim_in=None, pairs=None, T_ref=None, enable=None):
